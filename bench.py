@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — chain-evals/sec of the BGP hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--protocol auto|p2p|records|values]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--protocol auto|p2p|records|values] [--dump-outputs DIR]
 
 Workload (default: BASELINE.json configs[1], "C2"): serialNormal objective (2 params / 2 moments, ns = 10000 simulated draws per
 moment), 4096 BGP chains per GPU, FP64.  One "step" = one job of 200 iterations over all chains (= the metric's "4096 chains x
@@ -372,13 +372,38 @@ def cross_rank_check(ctx, torch, dist, rank, world, n_loc, same_device, last=8):
     return ok, "last %d iterations: %.3f of the chains exchanged, %d inconsistent partner marks across %d rank(s)" % (full.shape[0], frac, bad, world)
 
 
+DUMP_BYTES = 60 * 10 ** 6   # under the 64 MB a dump may take
+
+
+def dump_outputs(ctx, d):
+    """--dump-outputs: what the last timed step handed its caller — the history of its 200 iterations and the chains' state behind it —
+    as DIR/history_<field>.npy and DIR/state_<field>.npy, float64 (the integer fields convert exactly).  Where all chains would take more
+    than DUMP_BYTES, the same fixed, seeded sample of chains in every file (DIR/chains.npy: their indices); the chain is the last axis"""
+    import numpy as np
+    st = ctx.state()
+    h = ctx.history(st.iter - ITERS_PER_STEP, st.iter)
+    arrays = {"history_" + f: getattr(h, f) for f in h.FIELDS}
+    arrays.update({"state_" + f: getattr(st, f) for f in st.FIELDS})
+    n = st.sigma.shape[-1]
+    per_chain = sum(a.size // n for a in arrays.values()) * 8
+    chains = np.arange(n)
+    if per_chain * n > DUMP_BYTES:
+        chains = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // per_chain, replace=False))
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "chains.npy"), chains.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a[..., chains], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="timed steps of 200 iterations per repetition (default: c2 20, c5 8 = the steady state past 1600 iterations, else 5)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps of 200 iterations (default: c2 20, c5 8 = the steady state past 1600 iterations, else 5)")
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--reps", type=int, default=None, help="repetitions of the K timed steps, each bracketed by barrier + synchronize (default: as many as make the "
-                                                            "timed regions add up to >= 0.6 s, between 3 and 12, within 32 GB of history); value = the MEDIAN repetition")
+    ap.add_argument("--reps", type=int, default=1, help="repetitions of the K timed steps, each bracketed by barrier + synchronize (within 32 GB of history); "
+                                                         "value = the MEDIAN repetition.  The default 1 times exactly --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller (rank 0's shard) to DIR/<name>.npy, float64 (dump_outputs)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2")
     ap.add_argument("--protocol", choices=["auto", "p2p", "records", "values"], default=os.environ.get("SMM_BENCH_PROTOCOL", "auto"))
     ap.add_argument("--chains", type=int, default=None, help="chains per GPU (default: the workload's)")
@@ -387,6 +412,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-unfused", action="store_true", help="skip the reference timings on other contexts (the one-launch-per-iteration path, the unfused kernels): profiling runs")
     args = ap.parse_args()
+    if (args.steps is not None and args.steps < 1) or args.reps < 1:
+        ap.error("--steps and --reps must be at least 1")
 
     under_launcher = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not under_launcher:
@@ -426,7 +453,7 @@ def main():
         n_loc = args.chains or (W["chains"] // world if args.same_device else W["chains"])
         n_glob = n_loc * world
     if args.steps is None:
-        args.steps = 8 if args.workload in ("c5", "c5v1") else 20 if args.workload == "c2" else 5   # (c2: the driver's own --steps 20; 12 repetitions = 0.6 s of timed region)
+        args.steps = 8 if args.workload in ("c5", "c5v1") else 20 if args.workload == "c2" else 5   # (c2: the driver's own --steps 20)
     K, Wm = args.steps, args.warmup
 
     # the self-check runs the form the timed run will use: the same N_global and chains per rank (at least 1024: the large-population
@@ -446,7 +473,7 @@ def main():
     prob0, _ = build_problem(args.workload, n_loc, n_glob, rank, 1, device)
     row_bytes = n_loc * ((8 + prob0.np + prob0.nm + 1) & ~1) * 8
     # (a single shard repeats the SAME K steps from the state behind the warm-up: one repetition's worth of history; shards continue their chains)
-    reps_cap = max(1, min(args.reps or 12, int(32e9 // (row_bytes * ITERS_PER_STEP * K)))) if sharded else (args.reps or 12)
+    reps_cap = max(1, min(args.reps, int(32e9 // (row_bytes * ITERS_PER_STEP * K)))) if sharded else args.reps
     T = ITERS_PER_STEP * ((reps_cap if sharded else 1) * K + Wm + 2)
 
     def barrier():
@@ -475,9 +502,9 @@ def main():
         # again before each further repetition, outside the clock (a single shard; the generator is counter-based, so the iterations are the
         # same to the bit).  Continuing the chains instead measures another workload every time: over tens of thousands of iterations sigma keeps
         # adapting, more proposals leave the box, and a step of 200 iterations drifts from 2.55 to 2.80 ms (round 6, 12 x 20 steps in a row)
-        restore = (ctx.state(), ctx.history()) if not sharded else None
-        times, want = [], (args.reps or 3)
-        while len(times) < min(want, reps_cap):
+        restore = (ctx.state(), ctx.history()) if not sharded and reps_cap > 1 else None
+        times = []
+        while len(times) < reps_cap:
             if restore is not None and times:
                 ctx.set_state(*restore); ctx.sync(); torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -490,8 +517,6 @@ def main():
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
                 dt = float(tt.item())
             times.append(dt)
-            if args.reps is None and len(times) == 1:
-                want = max(3, min(12, int(0.6 / dt) + 1))
         return ctx, run_step, sync, times
 
     # the p2p windows meet real links here for the first time in earnest: a failure (a peer's stores never arrive: SMM_ERR_HIP after
@@ -514,6 +539,8 @@ def main():
     elif err is not None:
         raise RuntimeError(err)
     dt = sorted(times)[len(times) // 2]   # the median repetition (each already the max over the ranks)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, args.dump_outputs)
     # outside the clock: do the shards agree on the exchange of the last iterations?
     xok, xnote = cross_rank_check(ctx, torch, dist, rank, world, n_loc, args.same_device) if args.workload in ("c2", "c3", "c4", "c5", "c5v1") else (True, None)
     if not xok:

@@ -1,4 +1,5 @@
-"""`python bench.py --gpus N` must bring up its N ranks itself: the launcher, without a GPU (--dry-launch)."""
+"""`python bench.py --gpus N` must bring up its N ranks itself: the launcher, without a GPU (--dry-launch).
+`--steps K` times exactly K steps, and `--dump-outputs DIR` writes what the last of them computed, the same on every run."""
 import json
 import os
 import subprocess
@@ -76,3 +77,69 @@ def test_two_ranks_on_one_device_take_the_persistent_form():
     assert cfg["shard_form"].startswith("persistent"), cfg["shard_form"]
     assert d["roofline"]["kernel"] == "k_chain_persist_loc<2, false, true, false>" and d["roofline"]["persistent"]["repairs"] == 0
     assert "0 inconsistent partner marks across 2 rank(s)" in cfg["cross_rank_check"]
+
+
+class _FakeContext:
+    """history / state of N chains after `it` iterations, as a context hands them out (no device)"""
+
+    def __init__(self, N, np_, nm, it):
+        from smm_jl_amd import _abi as A
+        self.A, self.N, self.np, self.nm, self.it, self.asked = A, N, np_, nm, it, None
+
+    def _fill(self, b, seed):
+        import numpy as np
+        rng = np.random.default_rng(seed)
+        for f in b.FIELDS:
+            a = getattr(b, f)
+            a[...] = rng.integers(0, 100, a.shape) if a.dtype.kind in "iu" else rng.standard_normal(a.shape)
+        return b
+
+    def state(self):
+        s = self._fill(self.A.StateBuffers(self.N, self.np, self.nm), 1)
+        s.iter = self.it
+        return s
+
+    def history(self, t0, t1):
+        self.asked = (t0, t1)
+        return self._fill(self.A.HistoryBuffers(t1 - t0, self.N, self.np, self.nm), 2)
+
+
+def test_dump_outputs_writes_the_last_step_whole_or_a_seeded_sample_within_64_mb(tmp_path):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from smm_jl_amd import _abi as A
+    names = {"chains"} | {"history_" + f for f in A.HistoryBuffers.FIELDS} | {"state_" + f for f in A.StateBuffers.FIELDS}
+    small = _FakeContext(64, 2, 2, 600)
+    bench.dump_outputs(small, str(tmp_path / "small"))
+    assert small.asked == (400, 600)     # the last step's 200 iterations
+    got = {p.stem: np.load(p) for p in (tmp_path / "small").iterdir()}
+    assert set(got) == names and all(a.dtype == np.float64 for a in got.values())
+    h, s = small.history(400, 600), small.state()
+    assert np.array_equal(got["chains"], np.arange(64))
+    for f in A.HistoryBuffers.FIELDS:
+        assert np.array_equal(got["history_" + f], getattr(h, f)), f
+    for f in A.StateBuffers.FIELDS:
+        assert np.array_equal(got["state_" + f], getattr(s, f)), f
+    big = _FakeContext(4096, 50, 50, 400)     # c5's shape: 173 KB of history per chain, 708 MB in all
+    for d in ("big1", "big2"):
+        bench.dump_outputs(big, str(tmp_path / d))
+    assert sum(p.stat().st_size for p in (tmp_path / "big1").iterdir()) <= 64e6
+    c = np.load(tmp_path / "big1" / "chains.npy").astype(np.int64)
+    assert 0 < len(c) < 4096 and np.all(np.diff(c) > 0)
+    h = big.history(200, 400)
+    assert np.array_equal(np.load(tmp_path / "big1" / "history_params.npy"), h.params[..., c])
+    for p in (tmp_path / "big1").iterdir():      # the same sample every time
+        assert np.array_equal(np.load(p), np.load(tmp_path / "big2" / p.name)), p.name
+
+
+@pytest.mark.gpu
+def test_steps_are_the_timed_steps_and_the_dumped_outputs_repeat(tmp_path):
+    import numpy as np
+    lines = [run(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-unfused", "--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    for d in lines:
+        assert d["steps"] == 2 and d["repetitions"]["n"] == 1 and d["ms_per_step"] > 0
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert "history_value.npy" in files and sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64e6
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f), equal_nan=True), f

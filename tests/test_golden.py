@@ -176,17 +176,24 @@ def test_oracle_matches_reference_vectors(O):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not (os.path.exists(REF_JSON) and os.path.exists(REF_Z)),
-                    reason="tests/golden/ref_bgp.json / ref_Z.bin are produced by julia/reference_golden.jl (no julia in the build image)")
-def test_hip_matches_reference_vectors():
-    prob, opts, tab, T, exp = reference_case(REF_JSON, REF_Z)
-    check_against_reference(S.hip_context(prob, opts, tab), T, exp)
+def test_hip_matches_reference_vectors(O, tmp_path):
+    """The device's half of the pin.  With the files of julia/reference_golden.jl: the HIP path replays the reference's vectors.  Without
+    them (parity UNPINNED: test_oracle_matches_reference_vectors skips) the HIP path replays the same scenario against the ORACLE's own
+    run of it, to the bit, and warns: the device then matches the reference exactly when the oracle does, and the oracle's test is the pin."""
+    if os.path.exists(REF_JSON) and os.path.exists(REF_Z):
+        prob, opts, tab, T, exp = reference_case(REF_JSON, REF_Z)
+        check_against_reference(S.hip_context(prob, opts, tab), T, exp)
+        return
+    import warnings
+    warnings.warn("parity with the reference is unpinned: tests/golden/ref_bgp.json / ref_Z.bin (julia/reference_golden.jl) are not "
+                  "committed; the HIP path was checked against the oracle's run of the pin's scenario instead")
+    prob, opts, tab, T, exp = reference_case(*oracle_file_of_the_pin_scenario(O, tmp_path))
+    check_against_reference(S.hip_context(prob, opts, tab), T, exp, rtol=0)
 
 
-def test_reference_vector_loader_on_a_file_of_the_same_schema(O, tmp_path):
-    """THE LOADER, not a pin: a file in reference_golden.jl's schema written from the ORACLE's own run of the same scenario (same options,
-    the same LCG tables as the Julia script builds) must replay green — so that the day the real files arrive, a red test means a
-    difference with the reference and not a bug in the reading code."""
+def oracle_file_of_the_pin_scenario(O, tmp_path):
+    """a file pair in reference_golden.jl's schema, written from the ORACLE's own run of the script's scenario (same options, the same LCG
+    tables as the Julia script builds; numpy's generator for the shocks and pairs) into tmp_path: not a pin.  Returns the two paths."""
     import json
     N, T, ns = 6, 40, 10000
     s = 0x0123456789abcdef
@@ -231,7 +238,13 @@ def test_reference_vector_loader_on_a_file_of_the_same_schema(O, tmp_path):
                         params=h.params[:, :, c].tolist(), sim_moments=h.sim_moments[:, :, c].tolist(), sigma=float(st.sigma[c]),
                         accept_rate=float(st.accept_rate[c])) for c in range(N)]
     json.dump(d, open(jp, "w"))
-    prob, opts, tab, T_, exp = reference_case(str(jp), str(zpth))
+    return str(jp), str(zpth)
+
+
+def test_reference_vector_loader_on_a_file_of_the_same_schema(O, tmp_path):
+    """THE LOADER, not a pin: a file in reference_golden.jl's schema written from the ORACLE's own run of the same scenario must replay
+    green — so that the day the real files arrive, a red test means a difference with the reference and not a bug in the reading code."""
+    prob, opts, tab, T_, exp = reference_case(*oracle_file_of_the_pin_scenario(O, tmp_path))
     check_against_reference(O.OracleContext(prob, opts, tab), T_, exp, rtol=0)
     assert (exp["exchanged"] != 0).any() and 0 < exp["accepted"][1:].mean() < 1
 
