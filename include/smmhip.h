@@ -111,7 +111,29 @@ typedef enum {
  *                    double* value, int* status)   from the totals to moments, objective value, status.
  *
  * The library reduces the partials in a fixed order (numerical contract): inside each group of 64 lanes the
- * halving tree (offsets 32,16,..,1), then the group totals left to right. */
+ * halving tree (offsets 32,16,..,1), then the group totals left to right.
+ *
+ * Objectives that draw from the library's generator — smm_register_user_objective_rng(source, n_sums, lanes, &id):
+ * n_sums == 0 is the one-thread form (lanes ignored), n_sums >= 1 the map-reduce form (limits as for _lanes).  The source
+ * defines the same functions with a stream handle as one more argument:
+ *
+ *   SMM_USER_OBJECTIVE_RNG(const double* theta, int np, const double* mom, const double* w, int nm,
+ *                          const double* udata, int n_udata, smm_rng_t rng, double* sim_moments, double* value, int* status)
+ *   SMM_USER_PARTIAL_RNG(const double* theta, int np, const double* udata, int n_udata, smm_rng_t rng,
+ *                        int lane, int n_lanes, double* partial)          (+ SMM_USER_FINISH as above, without a stream)
+ *
+ * and may call, from any lane:
+ *   double smm_uniform(smm_rng_t r, uint64_t i)                          draw i of the stream, in [0, 1)
+ *   void   smm_normal2(smm_rng_t r, uint64_t j, double* z0, double* z1)  both standard normals of Philox block j
+ *   double smm_normal(smm_rng_t r, uint64_t i)                           normal i = component i & 1 of smm_normal2(r, i >> 1)
+ * Numerical contract: Philox4x32-10 with the key (k0, k1) = (lo32(seed), hi32(seed) ^ (6 * 0x9E3779B9)) (stream 6 of the
+ * library's generator).  smm_normal2: counter {lo32(j), hi32(j), 0, 0} -> x, u1 = ((x0:x1 >> 11) + 1) * 2^-53,
+ * u2 = (x2:x3 >> 11) * 2^-53 (x0:x1 = the 64-bit word x0 * 2^32 + x1), r = sqrt(-2 log u1), z0 = r cos(2 pi u2), z1 = r sin(2 pi u2)
+ * with the contract's log / sine / cosine (above).  smm_uniform: counter {lo32(i), hi32(i), 1, 0} -> (x0:x1 >> 11) * 2^-53.
+ * The seed: opts.seed in BGP steps and smm_eval_batch — the SAME stream for every chain, shard and iteration (common random
+ * numbers, as objfunc_norm's shocks; the role of Random.seed!(1234), ObjExamples.jl:74) —, base_seed + i for evaluation i of
+ * smm_eval_batch_noseed (fresh shocks per repetition: getSigma, econometrics.jl:125-145).  Both forms run in every kernel form
+ * the same objective without a stream runs in (the persistent ones included). */
 #define SMM_OBJ_USER_BASE 1000
 #define SMM_OBJ_USER 4   /* internal kind of every user objective */
 
@@ -235,6 +257,7 @@ int  smm_abi_version(void);
 /* compile a user objective; errors (with the compiler log) through smm_last_error(NULL) */
 int  smm_register_user_objective(const char* hip_source, int32_t* objective_id_out);
 int  smm_register_user_objective_lanes(const char* hip_source, int32_t n_sums, int32_t lanes, int32_t* objective_id_out);
+int  smm_register_user_objective_rng(const char* hip_source, int32_t n_sums, int32_t lanes, int32_t* objective_id_out);
 int  smm_device_count(void);
 
 /* MAlgoBGP(m,opts) constructor, AlgoBGP.jl:505-537 + BGPChain ctor :78-109 */
@@ -342,7 +365,8 @@ int  smm_eval_batch(void* ctx, const double* params, int32_t M,
                     double* value, double* sim_moments, int8_t* status);
 /* the same for objfunc_norm with options[:noseed] = true (ObjExamples.jl:71-75): evaluation i draws its own
  * shocks (generator keyed by base_seed + i) instead of the fixed seed-1234 matrix — the repetitions of
- * getSigma (econometrics.jl:125-145). */
+ * getSigma (econometrics.jl:125-145).  Also for user objectives registered with smm_register_user_objective_rng
+ * (their stream keyed by base_seed + i); other objectives have no stream to re-key: SMM_ERR_INVALID_ARG. */
 int  smm_eval_batch_noseed(void* ctx, const double* params, int32_t M, uint64_t base_seed,
                            double* value, double* sim_moments, int8_t* status);
 

@@ -14,7 +14,7 @@ module SMMHip
 using Libdl
 
 export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_state, hip_set_state!, hip_eval_batch,
-       hip_register_objective, hip_record_doubles
+       hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
@@ -385,6 +385,22 @@ value, status)`, see include/smmhip.h) for the device: the counterpart of `addEv
 function hip_register_objective(src::AbstractString)
     id = Ref{Int32}(0)
     rc = ccall(sym(:smm_register_user_objective), Cint, (Cstring, Ref{Int32}), src, id)
+    rc == 0 || throw(SMMHipError(Int(rc), last_error(Ptr{Cvoid}(C_NULL))))
+    return Int(id[])
+end
+
+"""
+    hip_register_objective_rng(src; n_sums = 0, lanes = 256) -> objective id
+
+A user objective that draws from the library's generator (include/smmhip.h): `n_sums = 0` — `src` defines
+`SMM_USER_OBJECTIVE_RNG(theta, np, mom, w, nm, udata, n_udata, rng, sim_moments, value, status)`; `n_sums >= 1` — the map-reduce
+form, `SMM_USER_PARTIAL_RNG(theta, np, udata, n_udata, rng, lane, n_lanes, partial)` + `SMM_USER_FINISH(...)` on `lanes` lanes.
+The source draws with `smm_normal(rng, i)`, `smm_normal2(rng, j, &z0, &z1)`, `smm_uniform(rng, i)`; such objectives also have
+noseed evaluations (`hip_eval_batch_noseed`, `getSigmaHip`).
+"""
+function hip_register_objective_rng(src::AbstractString; n_sums::Integer = 0, lanes::Integer = 256)
+    id = Ref{Int32}(0)
+    rc = ccall(sym(:smm_register_user_objective_rng), Cint, (Cstring, Int32, Int32, Ref{Int32}), src, Int32(n_sums), Int32(lanes), id)
     rc == 0 || throw(SMMHipError(Int(rc), last_error(Ptr{Cvoid}(C_NULL))))
     return Int(id[])
 end

@@ -18,8 +18,9 @@
 # objective, accept/reject, set_eval! for all chains and exchangeMoves!, AlgoBGP.jl:589-640) instead of pmap/map over chains.
 #
 # The objective must be a DEVICE objective: `SMM.objfunc_norm` maps to the built-in one; anything else is given as
-# `opts["hip_objective"]` = an id of SMMHip.hip_register_objective(source) (or :banana / :dense), with `opts["hip_ns"]`,
-# `opts["hip_obj_params"]` as needed.  A Julia closure cannot run inside the GPU iteration.
+# `opts["hip_objective"]` = an id of SMMHip.hip_register_objective(source) (or :banana / :dense, or the source text itself: registered
+# once, with opts["hip_rng"] = true as an objective that draws from the library's stream, SMM_USER_OBJECTIVE_RNG — opts["hip_n_sums"] /
+# opts["hip_lanes"] for its map-reduce form), with `opts["hip_ns"]`, `opts["hip_obj_params"]` as needed.  A Julia closure cannot run inside the GPU iteration.
 #
 # NOT EXECUTED IN THIS REPOSITORY'S CI (no julia binary in the image); see the header of SMMHip.jl for what is checked.
 module SMMHipBackend
@@ -62,10 +63,26 @@ function chain_vector(opts::Dict, key::String, default::Float64, N::Int)
     return v[1:N]
 end
 
+# user objectives given as source text in opts["hip_objective"], compiled once per (source, form)
+const USER_OBJECTIVES = Dict{Tuple{String,Bool,Int,Int},Cint}()
+
+function register_source(src::AbstractString, opts::Dict)
+    rng = Bool(get(opts, "hip_rng", false))             # the _RNG forms: the library's stream (noseed evaluations, getSigmaHip)
+    n_sums = Int(get(opts, "hip_n_sums", 0))            # 0: one thread per evaluation; >= 1: the map-reduce form
+    lanes = Int(get(opts, "hip_lanes", 256))
+    key = (String(src), rng, n_sums, lanes)
+    get!(USER_OBJECTIVES, key) do
+        rng && return Cint(SMMHip.hip_register_objective_rng(src; n_sums = n_sums, lanes = lanes))
+        n_sums == 0 || throw(ArgumentError("the map-reduce form of a source in opts[\"hip_objective\"] needs opts[\"hip_rng\"] = true"))
+        return Cint(SMMHip.hip_register_objective(src))
+    end
+end
+
 function device_objective(m::MProb, opts::Dict)
     if haskey(opts, "hip_objective")
         o = opts["hip_objective"]
         o isa Integer && return Cint(o)
+        o isa AbstractString && return register_source(o, opts)
         o == :norm && return SMMHip.OBJ_NORM
         o == :banana && return SMMHip.OBJ_BANANA
         o == :dense && return SMMHip.OBJ_DENSE

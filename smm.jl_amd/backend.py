@@ -224,7 +224,8 @@ class BGPContext:
         return value, simM, status
 
     def eval_batch_noseed(self, params, base_seed):
-        """objfunc_norm with noseed=true (ObjExamples.jl:71-75): evaluation i draws its own shocks (base_seed + i)"""
+        """objfunc_norm with noseed=true (ObjExamples.jl:71-75): evaluation i draws its own shocks (base_seed + i); likewise a user
+        objective registered with rng=True (its stream keyed by base_seed + i)"""
         params = A.f64(params)
         assert params.shape[0] == self.np
         M = params.shape[1]
@@ -283,15 +284,20 @@ class BGPContext:
         return z
 
 
-def register_user_objective(source, n_sums=None, lanes=256):
+def register_user_objective(source, n_sums=None, lanes=256, rng=False):
     """Compile a user objective for the device and return its objective_id handle (include/smmhip.h).
     n_sums=None: `source` defines SMM_USER_OBJECTIVE(...), evaluated by one thread per chain.
     n_sums=k:    map-reduce form — `source` defines SMM_USER_PARTIAL(...) and SMM_USER_FINISH(...); `lanes` threads
                  evaluate one chain and their k partial sums are reduced in a fixed order.
+    rng=True:    the same forms with the library's random stream as an argument — SMM_USER_OBJECTIVE_RNG(...) or
+                 SMM_USER_PARTIAL_RNG(...) + SMM_USER_FINISH(...), drawing with smm_normal / smm_normal2 / smm_uniform;
+                 such objectives also have noseed evaluations (eval_batch_noseed, getSigma).
     Raises with the compiler log if the source does not compile."""
     lib = A.load()
     oid = C.c_int32(0)
-    if n_sums is None:
+    if rng:
+        rc = lib.smm_register_user_objective_rng(source.encode(), 0 if n_sums is None else int(n_sums), int(lanes), C.byref(oid))
+    elif n_sums is None:
         rc = lib.smm_register_user_objective(source.encode(), C.byref(oid))
     else:
         rc = lib.smm_register_user_objective_lanes(source.encode(), int(n_sums), int(lanes), C.byref(oid))

@@ -432,7 +432,12 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistGenA
             if (r == 0) {
                 int st_u = 1;
                 double v_u = 0.0;
+#ifdef SMM_USER_RNG   // (the library's stream, keyed by the context's seed: the same draws for every chain and iteration)
+                smm_user_objective_rng(thp, np, s_const + 2 * PG_MAXP, s_const + 3 * PG_MAXP, nm, A.udata, A.n_udata, smm_rng_t{A.seed}, s_usm + cl * PG_MAXP,
+                                       &v_u, &st_u);
+#else
                 smm_user_objective(thp, np, s_const + 2 * PG_MAXP, s_const + 3 * PG_MAXP, nm, A.udata, A.n_udata, s_usm + cl * PG_MAXP, &v_u, &st_u);
+#endif
                 s_uval[cl] = v_u; s_ust[cl] = (double)st_u;
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

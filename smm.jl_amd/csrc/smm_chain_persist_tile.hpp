@@ -449,7 +449,11 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
                     double part[SMM_NSUMS];
 #pragma unroll
                     for (int i = 0; i < SMM_NSUMS; ++i) part[i] = 0.0;
+#ifdef SMM_USER_RNG   // (the library's stream, keyed by the context's seed: the same draws for every chain and iteration)
+                    smm_user_partial_rng(s_theta + cr * np, np, A.objp, A.n_udata, smm_rng_t{A.seed}, ll, UL, part);
+#else
                     smm_user_partial(s_theta + cr * np, np, A.objp, A.n_udata, ll, UL, part);
+#endif
 #pragma unroll
                     for (int i = 0; i < SMM_NSUMS; ++i) {
                         double a = part[i];

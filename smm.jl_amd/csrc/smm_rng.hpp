@@ -15,7 +15,7 @@
 
 namespace smm {
 
-enum : uint32_t { STREAM_U = 1, STREAM_PROP = 2, STREAM_Z = 3, STREAM_PAIRS = 4 };
+enum : uint32_t { STREAM_U = 1, STREAM_PROP = 2, STREAM_Z = 3, STREAM_PAIRS = 4, STREAM_USER = 6 };   // (5: the dense objectives' generated matrices)
 
 struct U4 { uint32_t x, y, z, w; };
 
@@ -165,6 +165,16 @@ __host__ __device__ inline double rng_Z(uint64_t seed, uint32_t k, uint32_t s) {
     double z0, z1;
     box_muller(philox_stream(seed, STREAM_Z, s, k >> 1, 0, 0), z0, z1);
     return (k & 1) ? z1 : z0;
+}
+
+// a user objective's stream (include/smmhip.h: smm_normal2 / smm_uniform): normals of block j at counter {lo32(j), hi32(j), 0, 0},
+// uniforms of draw i at {lo32(i), hi32(i), 1, 0}, keyed by (seed, STREAM_USER)
+__host__ __device__ inline void user_normal2(uint64_t seed, uint64_t j, double& z0, double& z1) {
+    box_muller(philox_stream(seed, STREAM_USER, (uint32_t)j, (uint32_t)(j >> 32), 0, 0), z0, z1);
+}
+__host__ __device__ inline double user_uniform(uint64_t seed, uint64_t i) {
+    const U4 x = philox_stream(seed, STREAM_USER, (uint32_t)i, (uint32_t)(i >> 32), 1, 0);
+    return u53(x.x, x.y);
 }
 
 // ---- exchange pairs: keyed bijection of the linear pair index (6-round Feistel, cycle walking) ----

@@ -95,6 +95,7 @@ struct UserObjective {
     std::vector<char> tile_code;           // k_chain_persist_tile with the user's map-reduce objective inside (smm_chain_persist_tile.hpp, SMM_TILE_USER)
     int tile_state = 0;                    // 0: not tried yet, 1: tile_code stands, -1: did not compile (tile_log)
     std::string tile_log;
+    bool rng = false;                      // SMM_USER_OBJECTIVE_RNG / SMM_USER_PARTIAL_RNG: takes the library's stream (smm_register_user_objective_rng)
 };
 // the device headers the persistent kernel is made of, as text: hiprtc compiles them together with the user's source
 struct EmbeddedSource { const char* name; const char* text; };
@@ -151,6 +152,94 @@ const char* USER_KERNEL_LANES =
     "    }\n"
     "}\n";
 
+// user objectives that draw from the library's generator (smm_register_user_objective_rng): the stream handle and its draws
+// (include/smmhip.h), on smm_rng.hpp's Philox4x32-10 and Box-Muller — compiled with the library's own headers (g_embedded)
+const char* USER_RNG_API =
+    "#include <stdint.h>\n#include \"smm_rng.hpp\"\n"
+    "typedef struct { uint64_t seed; } smm_rng_t;\n"
+    "__device__ inline double smm_uniform(smm_rng_t r, uint64_t i) { return smm::user_uniform(r.seed, i); }\n"
+    "__device__ inline void smm_normal2(smm_rng_t r, uint64_t j, double* z0, double* z1) { smm::user_normal2(r.seed, j, *z0, *z1); }\n"
+    "__device__ inline double smm_normal(smm_rng_t r, uint64_t i) {\n"
+    "    double z0, z1;\n"
+    "    smm::user_normal2(r.seed, i >> 1, z0, z1);\n"
+    "    return (i & 1) ? z1 : z0;\n"
+    "}\n";
+const char* USER_PRELUDE_RNG =
+    "#define SMM_USER_OBJECTIVE_RNG extern \"C\" __device__ void smm_user_objective_rng\n"
+    "extern \"C\" __device__ void smm_user_objective_rng(const double* theta, int np, const double* mom, const double* w, int nm,\n"
+    "                                                  const double* udata, int n_udata, smm_rng_t rng, double* sim_moments,\n"
+    "                                                  double* value, int* status);\n";
+// two kernels: keyed by the context's seed (BGP steps, smm_eval_batch), and evaluation c keyed by base_seed + c (smm_eval_batch_noseed)
+const char* USER_KERNEL_RNG =
+    "\n__device__ inline void smm_user_eval_one(const double* theta, int c, int np, const double* mom, const double* w, int nm,\n"
+    "        const double* udata, int n_udata, double* simM, double* value, int* status, uint64_t seed) {\n"
+    "    int st = 1; double v = 0.0;\n"
+    "    smm_user_objective_rng(theta + (size_t)c * np, np, mom, w, nm, udata, n_udata, smm_rng_t{seed}, simM + (size_t)c * nm, &v, &st);\n"
+    "    value[c] = v; status[c] = st;\n"
+    "}\n"
+    "extern \"C\" __global__ void smm_user_eval_kernel(const double* theta, int N, int np, const double* mom, const double* w, int nm,\n"
+    "        const double* udata, int n_udata, double* simM, double* value, int* status, uint64_t seed) {\n"
+    "    const int c = blockIdx.x * blockDim.x + threadIdx.x;\n"
+    "    if (c < N) smm_user_eval_one(theta, c, np, mom, w, nm, udata, n_udata, simM, value, status, seed);\n"
+    "}\n"
+    "extern \"C\" __global__ void smm_user_eval_noseed_kernel(const double* theta, int N, int np, const double* mom, const double* w, int nm,\n"
+    "        const double* udata, int n_udata, double* simM, double* value, int* status, uint64_t base_seed) {\n"
+    "    const int c = blockIdx.x * blockDim.x + threadIdx.x;\n"
+    "    if (c < N) smm_user_eval_one(theta, c, np, mom, w, nm, udata, n_udata, simM, value, status, base_seed + (uint64_t)c);\n"
+    "}\n";
+
+const char* USER_PRELUDE_LANES_RNG =
+    "#define SMM_USER_PARTIAL_RNG extern \"C\" __device__ void smm_user_partial_rng\n"
+    "#define SMM_USER_FINISH extern \"C\" __device__ void smm_user_finish\n"
+    "extern \"C\" __device__ void smm_user_partial_rng(const double* theta, int np, const double* udata, int n_udata, smm_rng_t rng,\n"
+    "                                                int lane, int n_lanes, double* partial);\n"
+    "extern \"C\" __device__ void smm_user_finish(const double* theta, int np, const double* totals, int n_sums, const double* mom,\n"
+    "                                           const double* w, int nm, const double* udata, int n_udata, double* sim_moments,\n"
+    "                                           double* value, int* status);\n";
+// the map-reduce kernel of USER_KERNEL_LANES with the stream handle passed to the partial sums: the same reduction order
+const char* USER_KERNEL_LANES_RNG =
+    "\n__device__ inline void smm_user_eval_lanes(const double* theta, int c, int np, const double* mom, const double* w, int nm,\n"
+    "        const double* udata, int n_udata, double* simM, double* value, int* status, uint64_t seed) {\n"
+    "    __shared__ double wsum[16][SMM_NSUMS];\n"
+    "    const int lane = threadIdx.x, nl = blockDim.x;\n"
+    "    double part[SMM_NSUMS];\n"
+    "    for (int i = 0; i < SMM_NSUMS; ++i) part[i] = 0.0;\n"
+    "    smm_user_partial_rng(theta + (size_t)c * np, np, udata, n_udata, smm_rng_t{seed}, lane, nl, part);\n"
+    "    for (int i = 0; i < SMM_NSUMS; ++i) {\n"
+    "        double a = part[i];\n"
+    "        for (int off = 32; off >= 1; off >>= 1) a = a + __shfl_xor(a, off, 64);\n"
+    "        if ((lane & 63) == 0) wsum[lane >> 6][i] = a;\n"
+    "    }\n"
+    "    __syncthreads();\n"
+    "    if (lane == 0) {\n"
+    "        double tot[SMM_NSUMS];\n"
+    "        for (int i = 0; i < SMM_NSUMS; ++i) { double a = wsum[0][i]; for (int wv = 1; wv < nl / 64; ++wv) a = a + wsum[wv][i]; tot[i] = a; }\n"
+    "        int st = 1; double v = 0.0;\n"
+    "        smm_user_finish(theta + (size_t)c * np, np, tot, SMM_NSUMS, mom, w, nm, udata, n_udata, simM + (size_t)c * nm, &v, &st);\n"
+    "        value[c] = v; status[c] = st;\n"
+    "    }\n"
+    "}\n"
+    "extern \"C\" __global__ void smm_user_eval_kernel(const double* theta, int N, int np, const double* mom, const double* w, int nm,\n"
+    "        const double* udata, int n_udata, double* simM, double* value, int* status, uint64_t seed) {\n"
+    "    smm_user_eval_lanes(theta, blockIdx.x, np, mom, w, nm, udata, n_udata, simM, value, status, seed);\n"
+    "}\n"
+    "extern \"C\" __global__ void smm_user_eval_noseed_kernel(const double* theta, int N, int np, const double* mom, const double* w, int nm,\n"
+    "        const double* udata, int n_udata, double* simM, double* value, int* status, uint64_t base_seed) {\n"
+    "    smm_user_eval_lanes(theta, blockIdx.x, np, mom, w, nm, udata, n_udata, simM, value, status, base_seed + (uint64_t)blockIdx.x);\n"
+    "}\n";
+
+// what hiprtc is given for #include: the library's device headers (g_embedded) and stand-ins for what they ask of the host's toolchain
+// (hiprtc brings its own runtime header and has no system headers to lean on)
+void rtc_headers(std::vector<const char*>& names, std::vector<const char*>& texts) {
+    for (const EmbeddedSource& e : g_embedded) { names.push_back(e.name); texts.push_back(e.text); }
+    static const char* stub_stdint = "typedef unsigned int uint32_t; typedef unsigned long uint64_t; typedef int int32_t; typedef long int64_t;\n"
+                                     "typedef unsigned short uint16_t; typedef unsigned char uint8_t; typedef signed char int8_t; typedef short int16_t;\n";
+    static const char* stub_math = "#ifndef INFINITY\n#define INFINITY __builtin_huge_val()\n#endif\n#ifndef NAN\n#define NAN __builtin_nan(\"\")\n#endif\n";
+    names.push_back("hip/hip_runtime.h"); texts.push_back("\n");
+    names.push_back("stdint.h"); texts.push_back(stub_stdint);
+    names.push_back("math.h"); texts.push_back(stub_math);
+}
+
 struct Hiprtc {
     void* lib = nullptr;
     decltype(&hiprtcCreateProgram) create = nullptr;
@@ -184,24 +273,19 @@ bool user_persist_compile(UserObjective& u) {   // (g_user_mutex held)
     if (u.source.empty() || u.lanes != 0) { u.persist_log = "not the one-thread-per-chain form"; return false; }
     std::string err;
     if (!g_rtc.load(err)) { u.persist_log = err; return false; }
-    std::string tu =
-        "#include <type_traits>\n#include <stdint.h>\n#include <math.h>\n"
-        "#define SMM_USER_OBJECTIVE extern \"C\" __device__ void smm_user_objective\n"
-        "extern \"C\" __device__ void smm_user_objective(const double* theta, int np, const double* mom, const double* w, int nm,\n"
-        "        const double* udata, int n_udata, double* sim_moments, double* value, int* status);\n";
+    std::string tu = "#include <type_traits>\n#include <stdint.h>\n#include <math.h>\n";
+    if (u.rng)
+        tu += std::string(USER_RNG_API) + USER_PRELUDE_RNG + "#define SMM_USER_RNG 1\n";
+    else
+        tu += "#define SMM_USER_OBJECTIVE extern \"C\" __device__ void smm_user_objective\n"
+              "extern \"C\" __device__ void smm_user_objective(const double* theta, int np, const double* mom, const double* w, int nm,\n"
+              "        const double* udata, int n_udata, double* sim_moments, double* value, int* status);\n";
     tu += u.source;
     tu += "\n#define SMM_GEN_USER 1\n#include \"smmhip.h\"\n#include \"smm_rng.hpp\"\nusing namespace smm;\n#include \"smm_params.hpp\"\n"
           "#include \"smm_walk_lean.hpp\"\n#include \"smm_propose.hpp\"\n#include \"smm_chain.hpp\"\n#include \"smm_p2p.hpp\"\n#include \"smm_chain_norm.hpp\"\n"
           "#include \"smm_chain_persist.hpp\"\n#include \"smm_chain_persist_gen.hpp\"\n";
     std::vector<const char*> names, texts;
-    for (const EmbeddedSource& e : g_embedded) { names.push_back(e.name); texts.push_back(e.text); }
-    // (what the headers ask the host's toolchain for: hiprtc brings its own runtime header and has no system headers to lean on)
-    static const char* stub_stdint = "typedef unsigned int uint32_t; typedef unsigned long uint64_t; typedef int int32_t; typedef long int64_t;\n"
-                                     "typedef unsigned short uint16_t; typedef unsigned char uint8_t; typedef signed char int8_t; typedef short int16_t;\n";
-    static const char* stub_math = "#ifndef INFINITY\n#define INFINITY __builtin_huge_val()\n#endif\n#ifndef NAN\n#define NAN __builtin_nan(\"\")\n#endif\n";
-    names.push_back("hip/hip_runtime.h"); texts.push_back("\n");
-    names.push_back("stdint.h"); texts.push_back(stub_stdint);
-    names.push_back("math.h"); texts.push_back(stub_math);
+    rtc_headers(names, texts);
     hiprtcProgram prog = nullptr;
     if (g_rtc.create(&prog, tu.c_str(), "smm_user_persist.hip", (int)names.size(), texts.data(), names.data()) != HIPRTC_SUCCESS) {
         u.persist_log = "hiprtcCreateProgram failed";
@@ -236,19 +320,16 @@ bool user_tile_compile(UserObjective& u) {   // (g_user_mutex held)
     std::string err;
     if (!g_rtc.load(err)) { u.tile_log = err; return false; }
     std::string tu = "#include <type_traits>\n#include <stdint.h>\n#include <math.h>\n";
-    tu += USER_PRELUDE_LANES;
+    if (u.rng)
+        tu += std::string(USER_RNG_API) + USER_PRELUDE_LANES_RNG + "#define SMM_USER_RNG 1\n";
+    else
+        tu += USER_PRELUDE_LANES;
     tu += u.source;
     tu += "\n#define SMM_TILE_USER 1\n#include \"smmhip.h\"\n#include \"smm_rng.hpp\"\nusing namespace smm;\n#include \"smm_params.hpp\"\n"
           "#include \"smm_walk_lean.hpp\"\n#include \"smm_propose.hpp\"\n#include \"smm_chain.hpp\"\n#include \"smm_p2p.hpp\"\n#include \"smm_chain_norm.hpp\"\n"
           "#include \"smm_chain_persist.hpp\"\n#include \"smm_chain_persist_loc.hpp\"\n#include \"smm_chain_persist_tile.hpp\"\n";
     std::vector<const char*> names, texts;
-    for (const EmbeddedSource& e : g_embedded) { names.push_back(e.name); texts.push_back(e.text); }
-    static const char* stub_stdint = "typedef unsigned int uint32_t; typedef unsigned long uint64_t; typedef int int32_t; typedef long int64_t;\n"
-                                     "typedef unsigned short uint16_t; typedef unsigned char uint8_t; typedef signed char int8_t; typedef short int16_t;\n";
-    static const char* stub_math = "#ifndef INFINITY\n#define INFINITY __builtin_huge_val()\n#endif\n#ifndef NAN\n#define NAN __builtin_nan(\"\")\n#endif\n";
-    names.push_back("hip/hip_runtime.h"); texts.push_back("\n");
-    names.push_back("stdint.h"); texts.push_back(stub_stdint);
-    names.push_back("math.h"); texts.push_back(stub_math);
+    rtc_headers(names, texts);
     hiprtcProgram prog = nullptr;
     if (g_rtc.create(&prog, tu.c_str(), "smm_user_persist_tile.hip", (int)names.size(), texts.data(), names.data()) != HIPRTC_SUCCESS) {
         u.tile_log = "hiprtcCreateProgram failed";
@@ -348,6 +429,8 @@ struct Ctx {
     int n_objp = 0;                 // doubles in P.objp
     hipModule_t umod = nullptr;     // user objective: this context's module and kernel
     hipFunction_t ufn = nullptr;
+    hipFunction_t ufn_noseed = nullptr;   // ... an objective with the library's stream: its noseed kernel (evaluation i keyed by base_seed + i)
+    bool u_rng = false;
     hipModule_t upmod = nullptr;    // ... and the persistent kernel compiled with it inside (smm_chain_persist_gen.hpp, SMM_GEN_USER)
     hipFunction_t upfn = nullptr;
     hipModule_t utmod = nullptr;    // ... and the persistent TILE kernel with its map-reduce form inside (smm_chain_persist_tile.hpp, SMM_TILE_USER)
@@ -705,17 +788,20 @@ void launch_chain_iter_norm(Ctx* c, int t, int flags) {
     }
 }
 
-// one thread per evaluation: theta [n][np] -> simM [n][nm], value [n], status [n]
-void launch_user_kernel(Ctx* c, const double* theta, int n, double* simM, double* value, int* status) {
+// one thread per evaluation: theta [n][np] -> simM [n][nm], value [n], status [n].  An objective with the library's stream draws from
+// the context's seed, or with base_seed (smm_eval_batch_noseed) evaluation i from base_seed + i
+void launch_user_kernel(Ctx* c, const double* theta, int n, double* simM, double* value, int* status, const uint64_t* base_seed = nullptr) {
     const KParams& P = c->P;
     int np = P.np, nm = P.nm, nud = c->n_objp;
     const double *mom = P.mom, *w = P.w, *ud = P.objp;
+    uint64_t seed = base_seed ? *base_seed : P.seed;
     void* args[] = {(void*)&theta, (void*)&n, (void*)&np, (void*)&mom, (void*)&w, (void*)&nm, (void*)&ud, (void*)&nud,
-                    (void*)&simM, (void*)&value, (void*)&status};
+                    (void*)&simM, (void*)&value, (void*)&status, (void*)&seed};
+    const hipFunction_t fn = base_seed ? c->ufn_noseed : c->ufn;
     if (c->u_lanes > 0)   // map-reduce form: one workgroup of u_lanes threads per evaluation
-        HIPCHK(hipModuleLaunchKernel(c->ufn, (unsigned)n, 1, 1, (unsigned)c->u_lanes, 1, 1, 0, c->stream, args, nullptr));
+        HIPCHK(hipModuleLaunchKernel(fn, (unsigned)n, 1, 1, (unsigned)c->u_lanes, 1, 1, 0, c->stream, args, nullptr));
     else
-        HIPCHK(hipModuleLaunchKernel(c->ufn, (unsigned)((n + 127) / 128), 1, 1, 128, 1, 1, 0, c->stream, args, nullptr));
+        HIPCHK(hipModuleLaunchKernel(fn, (unsigned)((n + 127) / 128), 1, 1, 128, 1, 1, 0, c->stream, args, nullptr));
 }
 
 void launch_chain_iter(Ctx* c, int t, int flags) {
@@ -1550,12 +1636,15 @@ int smm_debug_has_test_hooks(void) {
 #endif
 }
 
-static int register_user_source(const std::string& src, int n_sums, int lanes, int32_t* objective_id_out, const char* user_text = nullptr) {
+static int register_user_source(const std::string& src, int n_sums, int lanes, int32_t* objective_id_out, const char* user_text = nullptr,
+                                bool rng = false) {
     std::lock_guard<std::mutex> lock(g_user_mutex);
     std::string err;
     if (!g_rtc.load(err)) { g_create_err = err; return SMM_ERR_HIP; }
     hiprtcProgram prog = nullptr;
-    if (g_rtc.create(&prog, src.c_str(), "smm_user_objective.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
+    std::vector<const char*> names, texts;
+    if (rng) rtc_headers(names, texts);   // (the stream's draws: smm_rng.hpp)
+    if (g_rtc.create(&prog, src.c_str(), "smm_user_objective.hip", (int)names.size(), texts.data(), names.data()) != HIPRTC_SUCCESS) {
         g_create_err = "hiprtcCreateProgram failed";
         return SMM_ERR_HIP;
     }
@@ -1577,6 +1666,7 @@ static int register_user_source(const std::string& src, int n_sums, int lanes, i
     u.code.resize(cs);
     u.lanes = lanes;
     u.n_sums = n_sums > 0 ? n_sums : 1;
+    u.rng = rng;
     if (user_text) u.source = user_text;
     g_rtc.code(prog, u.code.data());
     g_rtc.destroy(&prog);
@@ -1597,6 +1687,19 @@ int smm_register_user_objective_lanes(const char* hip_source, int32_t n_sums, in
         return SMM_ERR_INVALID_ARG;
     }
     return register_user_source(std::string(USER_PRELUDE_LANES) + hip_source + USER_KERNEL_LANES, n_sums, lanes, objective_id_out, hip_source);
+}
+
+int smm_register_user_objective_rng(const char* hip_source, int32_t n_sums, int32_t lanes, int32_t* objective_id_out) {
+    if (!hip_source || !objective_id_out) { g_create_err = "smm_register_user_objective_rng: null argument"; return SMM_ERR_INVALID_ARG; }
+    if (n_sums < 0 || n_sums > 64 || (n_sums > 0 && (lanes < 64 || lanes > 1024 || lanes % 64 != 0))) {
+        g_create_err = "smm_register_user_objective_rng: need n_sums = 0 (one thread per evaluation) or 1 <= n_sums <= 64 with lanes a multiple "
+                       "of 64 in [64, 1024]";
+        return SMM_ERR_INVALID_ARG;
+    }
+    if (n_sums == 0)
+        return register_user_source(std::string(USER_RNG_API) + USER_PRELUDE_RNG + hip_source + USER_KERNEL_RNG, 1, 0, objective_id_out, hip_source, true);
+    return register_user_source(std::string(USER_RNG_API) + USER_PRELUDE_LANES_RNG + hip_source + USER_KERNEL_LANES_RNG, n_sums, lanes, objective_id_out,
+                                hip_source, true);
 }
 
 int smm_device_count(void) {
@@ -1705,9 +1808,10 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
                 std::lock_guard<std::mutex> lock(g_user_mutex);
                 const UserObjective& u = g_user_objectives[prob->objective_id - SMM_OBJ_USER_BASE];
                 HIPCHK(hipModuleLoadData(&c->umod, u.code.data()));
-                c->u_lanes = u.lanes; c->u_nsums = u.n_sums;
+                c->u_lanes = u.lanes; c->u_nsums = u.n_sums; c->u_rng = u.rng;
             }
             HIPCHK(hipModuleGetFunction(&c->ufn, c->umod, "smm_user_eval_kernel"));
+            if (c->u_rng) HIPCHK(hipModuleGetFunction(&c->ufn_noseed, c->umod, "smm_user_eval_noseed_kernel"));
             P.u_theta = dalloc<double>(c, (size_t)N * np);
             P.u_simM = dalloc<double>(c, (size_t)N * nm);
             P.u_value = dalloc<double>(c, N);
@@ -2886,6 +2990,27 @@ int smm_bgp_a2a_apply_dev(void* ctx, const void* recv_dev) {
     return SMM_OK;
 }
 
+// a user objective's evaluations (smm_eval_batch; with base_seed, smm_eval_batch_noseed): its kernel wants [M][np] / [M][nm], transposed on the host
+static void user_eval_batch(Ctx* c, const double* params, int32_t M, double* value, double* sim_moments, int8_t* status, const uint64_t* base_seed) {
+    const KParams& P = c->P;
+    DevBuf<double> dp((size_t)P.np * M), dv((size_t)M), dm((size_t)P.nm * M);
+    std::vector<double> tp((size_t)M * P.np), tm((size_t)M * P.nm);
+    std::vector<int> ts((size_t)M);
+    for (int i = 0; i < M; ++i)
+        for (int k = 0; k < P.np; ++k) tp[(size_t)i * P.np + k] = params[(size_t)k * M + i];
+    DevBuf<int> dsi((size_t)M);
+    HIPCHK(hipMemcpyAsync(dp.p, tp.data(), tp.size() * 8, hipMemcpyHostToDevice, c->stream));
+    launch_user_kernel(c, dp.p, M, dm.p, dv.p, dsi.p, base_seed);
+    HIPCHK(hipMemcpyAsync(value, dv.p, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(tm.data(), dm.p, tm.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(ts.data(), dsi.p, ts.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < M; ++i) {
+        status[i] = (int8_t)ts[i];
+        for (int k = 0; k < P.nm; ++k) sim_moments[(size_t)k * M + i] = tm[(size_t)i * P.nm + k];
+    }
+}
+
 int smm_eval_batch(void* ctx, const double* params, int32_t M, double* value, double* sim_moments, int8_t* status) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !params || M < 0 || !value || !sim_moments || !status) return SMM_ERR_INVALID_ARG;
@@ -2893,25 +3018,11 @@ int smm_eval_batch(void* ctx, const double* params, int32_t M, double* value, do
     try {
         HIPCHK(hipSetDevice(c->device));
         const KParams& P = c->P;
-        DevBuf<double> dp((size_t)P.np * M), dv((size_t)M), dm((size_t)P.nm * M);
-        if (c->obj == SMM_OBJ_USER) {   // the user's kernel wants [M][np] / [M][nm]: transpose on the host
-            std::vector<double> tp((size_t)M * P.np), tm((size_t)M * P.nm);
-            std::vector<int> ts((size_t)M);
-            for (int i = 0; i < M; ++i)
-                for (int k = 0; k < P.np; ++k) tp[(size_t)i * P.np + k] = params[(size_t)k * M + i];
-            DevBuf<int> dsi((size_t)M);
-            HIPCHK(hipMemcpyAsync(dp.p, tp.data(), tp.size() * 8, hipMemcpyHostToDevice, c->stream));
-            launch_user_kernel(c, dp.p, M, dm.p, dv.p, dsi.p);
-            HIPCHK(hipMemcpyAsync(value, dv.p, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(tm.data(), dm.p, tm.size() * 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(ts.data(), dsi.p, ts.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            for (int i = 0; i < M; ++i) {
-                status[i] = (int8_t)ts[i];
-                for (int k = 0; k < P.nm; ++k) sim_moments[(size_t)k * M + i] = tm[(size_t)i * P.nm + k];
-            }
+        if (c->obj == SMM_OBJ_USER) {
+            user_eval_batch(c, params, M, value, sim_moments, status, nullptr);
             return SMM_OK;
         }
+        DevBuf<double> dp((size_t)P.np * M), dv((size_t)M), dm((size_t)P.nm * M);
         DevBuf<int8_t> ds((size_t)M);
         HIPCHK(hipMemcpyAsync(dp.p, params, (size_t)P.np * M * 8, hipMemcpyHostToDevice, c->stream));
         constexpr int CT = 8;
@@ -2939,10 +3050,18 @@ int smm_eval_batch_noseed(void* ctx, const double* params, int32_t M, uint64_t b
                           int8_t* status) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !params || M < 0 || !value || !sim_moments || !status) return SMM_ERR_INVALID_ARG;
-    if (!is_sim(c->obj)) return fail(c, SMM_ERR_INVALID_ARG, "noseed evaluations exist for objfunc_norm only");
+    const bool user_rng = c->obj == SMM_OBJ_USER && c->u_rng;
+    if (!is_sim(c->obj) && !user_rng)
+        return fail(c, SMM_ERR_INVALID_ARG, "noseed evaluations exist for objfunc_norm and for user objectives that draw from the library's "
+                                            "stream (smm_register_user_objective_rng) only");
     if (M == 0) return SMM_OK;
     try {
         HIPCHK(hipSetDevice(c->device));
+        if (user_rng) {
+            const uint64_t bs = base_seed;
+            user_eval_batch(c, params, M, value, sim_moments, status, &bs);
+            return SMM_OK;
+        }
         const KParams& P = c->P;
         DevBuf<double> dp((size_t)P.np * M), dv((size_t)M), dm((size_t)P.nm * M);
         DevBuf<int8_t> ds((size_t)M);

@@ -40,13 +40,14 @@ def _no_mprob():
     raise ValueError("a device objective needs an Eval built from an MProb (Eval(mprob, p))")
 
 
-def user_objective(source, name="user_objective", n_sums=None, lanes=256):
+def user_objective(source, name="user_objective", n_sums=None, lanes=256, rng=False):
     """A user-written device objective (MProb.objfunc of the reference, mprob.jl:159): HIP/C++ text that defines
     SMM_USER_OBJECTIVE(...) — or, with n_sums=k, the map-reduce pair SMM_USER_PARTIAL / SMM_USER_FINISH evaluated by
     `lanes` threads per chain — see include/smmhip.h.  addEvalFunc(m, user_objective(src));
-    m.objfunc_opts["obj_params"] = [...] passes udata."""
+    m.objfunc_opts["obj_params"] = [...] passes udata.  rng=True: the _RNG forms, which draw from the library's generator
+    (smm_normal / smm_normal2 / smm_uniform) and so have noseed evaluations: getSigma / get_stdErrors work on them."""
     from .backend import register_user_objective
-    return DeviceObjective(name, register_user_objective(source, n_sums, lanes), ns=1)
+    return DeviceObjective(name, register_user_objective(source, n_sums, lanes, rng=rng), ns=1)
 
 
 objfunc_norm = DeviceObjective("objfunc_norm", A.SMM_OBJ_NORM, needs_square=True)   # ObjExamples.jl:59-116
