@@ -356,8 +356,123 @@ bool user_tile_compile(UserObjective& u) {   // (g_user_mutex held)
     return true;
 }
 
+// Test hooks, read once at the top of smm_ctx_create (SMM_HOOK: nothing of them in the shipped library; read_hooks names the
+// variables).  Every field holds the value that applies when its variable is not set.
+struct Hooks {
+    int fill = -1;                 // every allocation starts as this byte (reads of memory nobody wrote show up)
+    bool any_exchange = false;     // the any-size resolution kernel
+    bool dataflow = false;         // the ticket (data-flow) resolution kernel
+    bool big_exchange = false;     // the global-memory level kernels
+    bool key_exchange_off = false; // the global-memory walk instead of the key kernels
+    bool key_walk_off = false;     // no lean plan, no rows resolution (k_exch_resolve_key, 16-byte / split slots)
+    bool inline_walk_off = false;
+    bool norm_fast_off = false;    // the general kernel for objfunc_norm
+    int norm_narrow = -1;          // 0 never, 1 always
+    int tpw = 0;                   // 1 one tile per workgroup, 2 two at any size
+    bool dense_keys_off = false;   // the dense objective keeps the stand-alone resolution
+    bool no_cone = false;          // every workgroup walks the whole list
+    bool persist_off = false, persist_loc_off = false, persist_tile_off = false;   // the persistent forms: none, not the local, not the tile form
+    bool cone_big_off = false;     // k_exch_resolve_rows between the launches
+    bool plan_ahead_off = false;   // each window planned on the main stream when it is entered
+    int plan_cap = 1 << 30;        // short plan windows
+    int lvl_wg = 1024;             // tuning: the workgroup of k_exch_resolve_lvl
+    int scout_after = SMM_SCOUT_AFTER, scout_gl = 16;   // the scouting form of mysample's late tries
+    int a2a_cap = 0;               // a small capacity of the values form (0: a2a_capacity)
+    int pr_ring_k = PR_K, pr_slow_tile = -1, pr_slow_ticks = 0;   // the persistent kernels' ring depth, a tile made slow by so many ticks
+    bool rows_win_check = false;   // the p2p rows resolution checked against the plain kernels
+};
+Hooks read_hooks() {
+    Hooks H;
+    auto is = [](const char* v, char ch) { return v && v[0] == ch; };
+    if (const char* v = SMM_HOOK("SMMHIP_FILL")) H.fill = atoi(v);
+    H.any_exchange = is(SMM_HOOK("SMMHIP_ANY_EXCHANGE"), '1');
+    H.dataflow = is(SMM_HOOK("SMMHIP_DATAFLOW_EXCHANGE"), '1');
+    H.big_exchange = is(SMM_HOOK("SMMHIP_BIG_EXCHANGE"), '1');
+    H.key_exchange_off = is(SMM_HOOK("SMMHIP_KEY_EXCHANGE"), '0');
+    H.key_walk_off = is(SMM_HOOK("SMMHIP_KEY_WALK"), '0');
+    H.inline_walk_off = is(SMM_HOOK("SMMHIP_INLINE_WALK"), '0');
+    H.norm_fast_off = is(SMM_HOOK("SMMHIP_NORM_FAST"), '0');
+    if (const char* v = SMM_HOOK("SMMHIP_NORM_NARROW")) H.norm_narrow = v[0] == '0' ? 0 : v[0] == '1' ? 1 : -1;
+    if (const char* v = SMM_HOOK("SMMHIP_TPW")) H.tpw = v[0] == '1' ? 1 : v[0] == '2' ? 2 : 0;
+    H.dense_keys_off = is(SMM_HOOK("SMMHIP_DENSE_KEYS"), '0');
+    H.no_cone = is(SMM_HOOK("SMMHIP_NO_CONE"), '1');
+    H.persist_off = is(SMM_HOOK("SMMHIP_PERSIST"), '0');
+    H.persist_loc_off = is(SMM_HOOK("SMMHIP_PERSIST_LOC"), '0');
+    H.persist_tile_off = is(SMM_HOOK("SMMHIP_PERSIST_TILE"), '0');
+    H.cone_big_off = is(SMM_HOOK("SMMHIP_CONE_BIG"), '0');
+    H.plan_ahead_off = is(SMM_HOOK("SMMHIP_PLAN_AHEAD"), '0');
+    if (const char* v = SMM_HOOK("SMMHIP_PLAN_CAP")) H.plan_cap = atoi(v);
+    if (const char* v = SMM_HOOK("SMMHIP_LVL_WG")) H.lvl_wg = atoi(v);
+    if (const char* v = SMM_HOOK("SMMHIP_SCOUT_AFTER")) H.scout_after = atoi(v);
+    if (const char* v = SMM_HOOK("SMMHIP_SCOUT_GL")) H.scout_gl = atoi(v) == 8 ? 8 : 16;
+    if (const char* v = SMM_HOOK("SMMHIP_A2A_CAP")) H.a2a_cap = std::max(1, atoi(v));
+    if (const char* v = SMM_HOOK("SMMHIP_PR_RING")) { const int k = atoi(v); if (k == 2 || k == 4) H.pr_ring_k = k; }
+    if (const char* v = SMM_HOOK("SMMHIP_PR_SLOW_TILE")) H.pr_slow_tile = atoi(v);
+    if (const char* v = SMM_HOOK("SMMHIP_PR_SLOW_US")) H.pr_slow_ticks = 100 * atoi(v);
+    H.rows_win_check = SMM_HOOK("SMMHIP_ROWS_WIN_CHECK") != nullptr;
+    return H;
+}
+// Which stand-alone kernel resolves exchangeMoves! (AlgoBGP.jl:647-716) — ONE decision, taken once per context (select_forms),
+// from the population, the thresholds and dist_fun:
+//
+//   N_global        min_improve                      dist_fun   kernel                       slots / where
+//   <= 8192 (~7400) one value >= 0 for all chains    -          k_exch_resolve_lean          8-byte keys (0) or 16-byte values (> 0), LDS
+//   <= 4096         anything else                    any        k_exch_resolve_lvl<1024>     16-byte slots, LDS
+//   <= 8192         anything else                    any        k_exch_resolve_lvl_soa       split slots, LDS
+//   <= 32768        0 for all chains                 -          k_exch_keys + _rows          4-byte slots (17-bit keys), rows of 1024 pairs, LDS
+//   <= 32768        anything else                    -          k_exch_keys + _key           4-byte slots (16-bit keys, intervals), LDS
+//   <= 65535        anything else / other dist_fun   any        k_exch_resolve_lvl_big       16-byte slots, global memory
+//   above, or K > N_global                           any        k_exch_resolve_any           barrier rounds, global atomics
+//
+// (the p2p form of a sharded run launches k_exch_resolve_rows itself where this table says _rows — launch_resolve_rows_window:
+//  <., true> reads the tagged slots of its window instead of a key pre-pass, <false, true, true> keeps the partners of the rank's
+//  own chains only; every other p2p population resolves from the window's plain values through this table.)
+// (single shards of objfunc_norm up to 4096 chains do not get here in steady state: their chain kernel walks inline.)  The test
+// build can force an entry (SMM_TEST_HOOKS: Hooks) and adds the ticket kernel k_exch_resolve_lds.
+enum ExchKernel { XK_LEAN, XK_LVL, XK_LVL_SOA, XK_TICKETS, XK_ROWS, XK_KEY, XK_LVL_BIG, XK_ANY };
+// The forms a context runs, chosen once at creation from the problem, the device and the hooks (select_forms) and not changed after.
+enum PlanKind { PLAN_NONE, PLAN_LDS, PLAN_BIG };   // the look-ahead exchange plans: none (one chain), k_exch_plan, k_exch_plan_big
+enum PersistKind { PERSIST_NONE, PERSIST_GEN, PERSIST_LOC, PERSIST_TILE };   // the persistent chain kernel (smm_chain_persist*.hpp)
+struct Forms {
+    // the exchange
+    PlanKind plan = PLAN_NONE;
+    ExchKernel xk = XK_ANY;      // the stand-alone resolution (the table above)
+    int rows_cap = 0;            // XK_ROWS: rows of XWG pairs per iteration of the plan
+    bool lean_plan = false;      // the padded lean plan (smm_walk_lean.hpp) is made behind the level plan
+    bool lean_wide = false;      // ... on 16-byte units (one min_improve > 0, or thresholds by chain)
+    bool plan_ahead = false;     // big plans: the windows are planned ahead on a second stream into two sets of tables (PlanSet)
+    int win_cap = 0;             // iterations per window of pre-generated randomness
+    int plan_cap = 0;            // iterations per window of exchange plans
+    // the chain kernel
+    int ct = 8;                  // chains per simulation tile (4 and 16 were measured and rejected: more shock traffic / spills)
+    bool norm_fast = false;      // objfunc_norm with np == nm <= 4 and one proposal batch: k_chain_iter_norm (16-chain tiles)
+    bool norm_narrow = false;    // k_chain_iter_norm_narrow instead of k_chain_iter_norm<., false>: shards of more than one round of tiles
+    int tpw = 1;                 // tiles per workgroup of k_chain_iter (2 with the inline walk: one walk per CU)
+    int tile_off = 0;            // KParams::tile_off: doubles of LDS in front of the tile (the inline walk's slots)
+    // the inline exchange walk: in the prologue of the next chain kernel
+    bool inline_walk = false;
+    bool gen_lean = false;       // k_chain_iter walks inline on the lean form (16-byte slots) when the plan fits it
+    bool gen_keys = false;       // ... on the lean KEY form (8-byte slots): single shards of 4096 < N <= 8192 chains without a simulation (two 16-chain tiles per workgroup)
+    bool dense_keys = false;     // ... and the dense objective's tiles (one 16-chain tile per workgroup, N <= 4096): the walk's slots and lists UNDER the tile's blocks
+    bool cone = false;           // the key form of k_chain_iter walks its workgroups' cones (smm_cone.hpp)
+    bool cone_big = false;       // large single shards of objfunc_norm (8192 < N <= 32768): the narrow chain kernel's tiles walk their own, locally numbered cones (smm_cone_big.hpp)
+    bool walk_slots = false;     // the accept step writes the lean key walk's 8-byte slots (slot8_buf, walk_flags)
+    int cone_tiles = 0, cone_ct = 0;   // the cone tables: tiles and chains per tile (0 tiles: none)
+    bool cone_gather = false;    // ... with the tiles' gather lists (the persistent forms, the local cones)
+    // the persistent chain kernel: one launch for a run of iterations
+    PersistKind persist = PERSIST_NONE;
+    bool persist_wide = false;   // ... its 16-byte slots: one min_improve > 0 (or NaN) for all chains
+    bool persist_sh = false;     // ... as a SHARD of a sharded run: the ring lives in every rank's p2p window (smm_bgp_p2p_step)
+    bool persist_sh_big = false; // ... of a population past 8192 chains: k_exch_plan_big + k_cone_chains + k_cone_tiles list its tiles' cones (locally numbered)
+    bool persist_user = false;   // PERSIST_GEN launches upfn (the user's objective inside)
+    int max_tiles = 0;           // tiles of the persistent kernel this device holds at once (occupancy x compute units)
+    bool defer_resolve = false;  // the exchange of an iteration is left unresolved until somebody needs it (the next launch may be the persistent kernel's)
+};
+
 struct Ctx {
     KParams P{};
+    Hooks H;                   // read once at creation
+    Forms F;                   // chosen once at creation (select_forms)
     int obj = 0, device = 0, exchange_from = 2;
     int iter = 0;
     hipStream_t stream = nullptr;
@@ -366,10 +481,9 @@ struct Ctx {
     std::string err;
     smm_timing_t timing{};
     bool pending_timing = false;
-    int profiling = 0;   // 1: event brackets around the kernels; 2: the kernels' own begin/end timestamps (hipExtLaunchKernelGGL)
+    int profiling = 0;   // 1: event brackets around the kernels; 2: the kernels' own begin/end timestamps (launch)
     hipEvent_t kev0 = nullptr, kev1 = nullptr;   // mode 2: start/stop events of the next launch
     std::vector<char> pev_exch;
-    bool force_any_exchange = false;
     std::vector<hipEvent_t> pev;  // profiling events: 4 per iteration (the last two bracket nothing: the event overhead)
     int pev_iters = 0;
     // double-buffered last-accepted records [N][RW]
@@ -378,27 +492,20 @@ struct Ctx {
     bool pending = false;      // exchange of iteration `iter` resolved but not applied
     bool prev_open = false;    // accept-rate counters of iteration `iter` not closed yet
     // look-ahead windows
-    int win_cap = 0;           // iterations per window of pre-generated randomness
-    int plan_cap = 0;          // iterations per window of exchange plans
     double* win_rb = nullptr;
     unsigned long long* win_plan = nullptr;
     double* win_plan_mi = nullptr;
     uint32_t *win_lv_pairs = nullptr, *win_lv_off = nullptr, *win_lv_pairs_p = nullptr, *win_lv_offp = nullptr;
-    bool rows_exchange = false;  // min_improve == 0, 8192 < N_global <= 32768: k_exch_resolve_rows (falls back to k_exch_resolve_key's walk)
     uint32_t *win_lv_rows = nullptr, *win_lv_rowinfo = nullptr, *slots17 = nullptr, *nan_flags = nullptr;
     int32_t *a2a_send_idx = nullptr, *a2a_send_cnt = nullptr, *a2a_rowidx = nullptr;   // the values form of the sharded exchange
     int a2a_cap = 0, a2a_G = 0;
     bool a2a_open = false;
     int slots_iter = -1;        // single shard, rows exchange: the accept step of this iteration wrote the resolution's initial slots (no pre-pass)
-    int xk = 0;                 // ExchKernel: the stand-alone exchange resolution of this context (choose_exchange)
     bool exch_done = false;     // the three-phase / values forms: exchangeMoves! of iteration `iter` has been applied (cleared by the next local step)
     double* vals_buf[2] = {nullptr, nullptr};   // KParams::vals / vals_out, by iteration parity (point_values)
     uint2* slot8_buf[2] = {nullptr, nullptr};
     bool deep_plan = false;      // an injected pair list has an iteration of more than LV_MAXLEV dependency levels
     bool nan_values = false;     // the uploaded state holds NaN values (smm_set_state)
-    bool gen_lean = false;       // k_chain_iter walks inline on the lean form (16-byte slots) when the plan fits it
-    bool gen_keys = false;       // ... on the lean KEY form (8-byte slots): single shards of 4096 < N <= 8192 chains without a simulation (two 16-chain tiles per workgroup)
-    bool cone_big = false;       // large single shards of objfunc_norm (8192 < N <= 32768): the narrow chain kernel's tiles walk their own, locally numbered cones (smm_cone_big.hpp)
     uint32_t* cb_scratch = nullptr;
     std::vector<uint32_t> cone_big_ok;   // per iteration of the plan window: its cones fit their caps
     // ... their windows are planned AHEAD: the plan of a window depends on (seed, iteration) only, so while the chain kernels of one
@@ -412,16 +519,9 @@ struct Ctx {
         int t0 = 0, w = 0;             // iterations [t0, t0 + w) are (being) planned into this set
     } ps[2];
     int ps_act = 0;                      // the set the chain kernels read
-    bool plan_ahead = false;
     hipStream_t pstream = nullptr;
     hipEvent_t ev_free = nullptr;        // main stream: every launch that reads the set about to be planned into has been enqueued before it (plan_window_into)
-    bool dense_keys = false;     // ... and the dense objective's tiles (one 16-chain tile per workgroup, N <= 4096): the walk's slots and lists UNDER the tile's blocks
-    bool lean_resolve = false;   // one min_improve >= 0 for all chains, N_global <= 8192 (~7400 when > 0): k_exch_resolve_lean is the stand-alone resolve kernel
     double* win_lv_mi = nullptr;
-    bool lvl_exchange = false;
-    bool lvl_soa_exchange = false;   // XLVL_MAX < N_global <= XLDS_MAX: level walk on split chain slots
-    int tpw = 1;                // tiles per workgroup of k_chain_iter (2 with the inline walk: one walk per CU)
-    bool inline_walk = false;   // the exchange walk runs in the prologue of the next k_chain_iter (SMMHIP_INLINE_WALK=0: off)
     const double* ext_rec_in = nullptr;   // sharded_step: donor records come from / results go to the caller's gather buffers
     double* ext_rec_out = nullptr;
     bool pending_ext = false;   // sharded_step: the exchange of iteration `iter` is still to be resolved from the gathered records
@@ -436,19 +536,11 @@ struct Ctx {
     hipModule_t utmod = nullptr;    // ... and the persistent TILE kernel with its map-reduce form inside (smm_chain_persist_tile.hpp, SMM_TILE_USER)
     hipFunction_t utfn = nullptr;
     int u_nsums = 1;                // ... its partial sums per lane
-    bool persist_user = false;      // persist_gen launches upfn
-    bool defer_resolve = false;     // the exchange of an iteration is left unresolved until somebody needs it (the next launch may be the persistent kernel's)
     bool rec_external = false;  // the records after the last accept step were written to the caller's gather buffer (sharded_step)
     bool unresolved = false;    // exchangeMoves! of iteration `iter` is still to be resolved (inline, or by resolve_now)
-    bool big_exchange = false;   // 8192 < N_global <= 65535: level plan and walk in global memory
-    bool key_exchange = false;   // ... up to 32768: the walk in LDS on 4-byte slots (src + 16-bit order key), k_exch_resolve_key
     uint32_t* big_scratch = nullptr;
-    int lvl_wg = 1024;
     int rng_t0 = 0, rng_w = 0;    // window currently held: iterations [t0, t0+w)
     int plan_t0 = 0, plan_w = 0;
-    bool lds_exchange = false;
-    int ct = 8;
-    bool norm_fast = false;     // objfunc_norm with np == nm <= 4 and one proposal batch: k_chain_iter_norm (16-chain tiles)
     int failed = 0;             // a hard device error (AlgoBGP.jl:341,409) stopped the run at iteration `iter`: sticky until smm_set_state
     // the p2p form of the sharded iteration (smm_p2p.hpp)
     unsigned char* p2p_mine = nullptr;         // this rank's window (null: smm_bgp_p2p_init not called)
@@ -457,24 +549,14 @@ struct Ctx {
     unsigned long long p2p_seq = 0;            // pushes so far (every rank counts the same)
     bool p2p_current = false;                  // the windows hold the records after iteration `iter`
     bool p2p_inline = false;                   // the inline form is available: k_chain_iter_norm_p2p walks inline and pushes from its epilogue
-    bool norm_narrow = false;                  // k_chain_iter_norm_narrow instead of k_chain_iter_norm<., false>: shards of more than one round of tiles
-    bool cone = false;                         // the key form of k_chain_iter walks its workgroups' cones (smm_cone.hpp)
     bool p2p_rows = false;                     // the same kernel without the walk + k_exch_resolve_rows<., true> on the window's slots
     bool p2p_mode_inline = false;              // ... and is what the windows currently hold (decided at every publication)
     bool p2p_unwaited = false;                 // nobody has waited for the arrivals of the last push yet
     double* ext_vals_out = nullptr;            // p2p generic form: the accept step's values go into the window
     // the persistent chain kernel (smm_chain_persist.hpp): one launch for a run of iterations
-    bool persist = false;                      // this context can run it (objfunc_norm np <= 2, single shard of at most one tile per CU, key walk)
-    bool persist_gen = false;                  // ... its form for objectives without a simulation (smm_chain_persist_gen.hpp: banana, 4096 < N <= 8192)
-    bool persist_loc = false;                  // ... on locally numbered cones (smm_chain_persist_loc.hpp): thresholds (min_improve > 0), shards
-    bool persist_tile = false;                 // ... its form for objectives a whole tile evaluates (smm_chain_persist_tile.hpp): objfunc_norm of any size, the dense simulation
-    bool persist_wide = false;                 // ... its 16-byte slots: one min_improve > 0 (or NaN) for all chains
     unsigned char* prw = nullptr;              // persist_loc: the ring's window (pr_win_layout) — a single shard's own allocation, a shard's: inside its p2p window
-    bool persist_sh = false;                   // ... as a SHARD of a sharded run: the ring lives in every rank's p2p window (smm_bgp_p2p_step)
-    bool persist_sh_big = false;               // ... of a population past 8192 chains: k_exch_plan_big + k_cone_chains + k_cone_tiles list its tiles' cones (locally numbered)
     size_t prw_off = 0;                        // persist_sh: offset of the ring's window inside the p2p window
     int p2p_ranks_here = 1;                    // ranks whose windows live on THIS device (this one included): their tiles must all be resident together
-    int persist_max_tiles = 0;                 // tiles of the persistent kernel this device holds at once (occupancy x compute units)
     bool persist_proven = false;               // a launch of the persistent form has come through: its spins may last P2P_TIMEOUT_TICKS from now on
     int persist_strikes = 0;                   // time-outs so far (two: the form is off for the context)
     int persist_on = 1;                        // smm_set_persistent
@@ -482,7 +564,6 @@ struct Ctx {
     uint32_t pr_epoch = 0;                     // launches so far
     int persist_launches = 0, persist_repairs = 0;
     int pregen_seen_launches = 0;              // persist_launches when the last window of randomness blocks was made (ensure_windows)
-    int pr_ring_k = PR_K, pr_slow_tile = -1, pr_slow_ticks = 0;   // (test build: SMMHIP_PR_RING, SMMHIP_PR_SLOW_TILE, SMMHIP_PR_SLOW_US)
     bool failed_told = false;   // `failed` has been returned to the caller by some entry point
     bool in_repair = false;
     // ... and what persist_repair restores when a launch of it ends with the error word set: the state before the FIRST such launch
@@ -510,8 +591,7 @@ T* dalloc(Ctx* c, size_t n) {
     void* p = nullptr;
     HIPCHK(hipMalloc(&p, (n ? n : 1) * sizeof(T)));
     c->allocs.push_back(p);
-    if (const char* f = SMM_HOOK("SMMHIP_FILL"))   // test hook: every allocation starts as this byte (reads of memory nobody wrote show up)
-        HIPCHK(hipMemset(p, atoi(f), (n ? n : 1) * sizeof(T)));
+    if (c->H.fill >= 0) HIPCHK(hipMemset(p, c->H.fill, (n ? n : 1) * sizeof(T)));   // (test hook SMMHIP_FILL)
     return (T*)p;
 }
 template <class T>
@@ -519,6 +599,13 @@ T* dupload(Ctx* c, const T* h, size_t n) {
     T* d = dalloc<T>(c, n);
     if (h && n) HIPCHK(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
     return d;
+}
+
+// a kernel onto the context's stream; in profiling mode 2 with the begin/end of this dispatch as the command processor stamps them
+template <class Kern, class... Args>
+void launch(Ctx* c, Kern kern, dim3 grid, dim3 block, size_t smem, const Args&... args) {
+    if (c->kev0) hipExtLaunchKernelGGL(kern, grid, block, smem, c->stream, c->kev0, c->kev1, 0, args...);
+    else hipLaunchKernelGGL(kern, grid, block, smem, c->stream, args...);
 }
 
 bool is_sim(int obj) { return obj == SMM_OBJ_NORM || obj == SMM_OBJ_NORM_FAILBOX; }
@@ -545,16 +632,16 @@ size_t persist_tile_smem(const Ctx* c) {
 }
 size_t norm_smem(const Ctx* c) {   // k_chain_iter_norm: [walk: chain slots | pair list] theta, partial sums, parked state
     const size_t b = (size_t)c->P.tile_off * sizeof(double) + norm_tile_doubles(c->P.np) * sizeof(double);
-    return c->cone_big ? std::max(b, cone_local_lds_bytes()) : b;   // (the local cone walk lies UNDER the tile's blocks)
+    return c->F.cone_big ? std::max(b, cone_local_lds_bytes()) : b;   // (the local cone walk lies UNDER the tile's blocks)
 }
 size_t tile_smem(const Ctx* c, int ct, int tpw = 1) {   // dynamic LDS of k_chain_iter: tpw tiles; with the inline exchange
-    if (c->norm_fast) return norm_smem(c);
+    if (c->F.norm_fast) return norm_smem(c);
     const size_t base = tile_smem_base(c, ct);           // walk its chain slots in front and its pair list under the tiles
     const size_t tiles = (size_t)tpw * ((base + 15) & ~(size_t)15);
-    if (!c->inline_walk) return tiles;
-    if (c->dense_keys) return std::max(tiles, (size_t)(((c->P.Ng + 3) & ~3) + 4) * 8 + std::max((size_t)CONE_LEVELS * 64 * 4, (size_t)lean_walk_Kp(c->P.plan_K) * 4));
-    if (c->gen_keys) return (size_t)(((c->P.Ng + 3) & ~3) + 4) * 8 + std::max(tiles, (size_t)lean_walk_Kp(c->P.plan_K) * 4);
-    return c->gen_lean ? tile_lean_slot_bytes(c->P.Ng) + std::max(tiles, (size_t)lean_walk_Kp(c->P.plan_K) * 4)
+    if (!c->F.inline_walk) return tiles;
+    if (c->F.dense_keys) return std::max(tiles, (size_t)(((c->P.Ng + 3) & ~3) + 4) * 8 + std::max((size_t)CONE_LEVELS * 64 * 4, (size_t)lean_walk_Kp(c->P.plan_K) * 4));
+    if (c->F.gen_keys) return (size_t)(((c->P.Ng + 3) & ~3) + 4) * 8 + std::max(tiles, (size_t)lean_walk_Kp(c->P.plan_K) * 4);
+    return c->F.gen_lean ? tile_lean_slot_bytes(c->P.Ng) + std::max(tiles, (size_t)lean_walk_Kp(c->P.plan_K) * 4)
                        : walk_slot_bytes(c->P.Ng) + std::max(tiles, (size_t)c->P.plan_K * 4);
 }
 size_t plan_lds_bytes(int Ng, int K) { return (size_t)(Ng + 2) * 4 + (size_t)K * 8 + (size_t)K * 4 + 128 + 16; }
@@ -581,7 +668,7 @@ void plan_window_into(Ctx* c, int k, int t) {
     HIPCHK(hipEventRecord(c->ev_free, c->stream));
     HIPCHK(hipStreamWaitEvent(c->pstream, c->ev_free, 0));
     Pw.cone_ok = S.cone_ok; Pw.cone_hdr = S.cone_hdr; Pw.cone_pairs = S.cone_pairs; Pw.cone_gather = S.cone_gather;
-    const int W = std::min(c->plan_cap, Pw.T - t + 1);
+    const int W = std::min(c->F.plan_cap, Pw.T - t + 1);
     hipLaunchKernelGGL(k_exch_plan_big, dim3(W), dim3(XWG), plan_big_lds_bytes(Pw.Ng), c->pstream, Pw, t, c->big_scratch, S.lv_pairs, S.lv_mi, S.lv_off, S.lv_rows, S.lv_rowinfo);
     launch_cone_big(c, Pw, W, S.lv_pairs, S.lv_off, c->pstream);
     HIPCHK(hipMemcpyAsync(S.ok_host, S.cone_ok, (size_t)W * 4, hipMemcpyDeviceToHost, c->pstream));
@@ -592,20 +679,20 @@ void plan_window_into(Ctx* c, int k, int t) {
 // iteration t lies behind the plan window, the exchange of t - 1 is still to be walked: does the window planned ahead hold both?
 bool plan_ahead_covers(const Ctx* c, int t) {
     const Ctx::PlanSet& S = c->ps[c->ps_act ^ 1];
-    return c->plan_ahead && S.w >= 2 && S.t0 == t - 1;
+    return c->F.plan_ahead && S.w >= 2 && S.t0 == t - 1;
 }
 
 // make the look-ahead tables cover iteration t (1-based): a new window simply starts at t
 void ensure_windows(Ctx* c, int t, bool rng = true) {
     KParams& P = c->P;
     // (k_chain_iter_norm generates its randomness itself unless tables are injected: no randomness blocks)
-    const bool pregen = rng && !(c->norm_fast && !P.user_ntab && !P.user_utab);
+    const bool pregen = rng && !(c->F.norm_fast && !P.user_ntab && !P.user_utab);
     if (pregen && !(t >= c->rng_t0 && t < c->rng_t0 + c->rng_w)) {
-        int W = std::min(c->win_cap, P.T - t + 1);
+        int W = std::min(c->F.win_cap, P.T - t + 1);
         // (k_chain_persist_gen draws in the kernel too: blocks only for the iterations between its launches)
         // — and only where such launches are really being made: a caller that steps one iteration at a time (the reference's run! loop
         // over computeNextIteration!, AlgoAbstract.jl:38-45) never takes the persistent form and keeps its full windows
-        if ((c->persist_gen || c->persist_tile) && c->persist && c->persist_on && !c->persist_broken && !c->in_repair && !P.user_ntab && !P.user_utab &&
+        if ((c->F.persist == PERSIST_GEN || c->F.persist == PERSIST_TILE) && c->persist_on && !c->persist_broken && !c->in_repair && !P.user_ntab && !P.user_utab &&
             c->persist_launches != c->pregen_seen_launches) W = std::min(W, 2);
         c->pregen_seen_launches = c->persist_launches;
         const size_t Q = (size_t)(P.np + 1) / 2;
@@ -614,7 +701,7 @@ void ensure_windows(Ctx* c, int t, bool rng = true) {
         c->rng_t0 = t; c->rng_w = W;
         P.rb = c->win_rb; P.rb_t0 = t;
     }
-    if (c->plan_ahead && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
+    if (c->F.plan_ahead && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
         const int nx = c->ps_act ^ 1;
         Ctx::PlanSet& S = c->ps[nx];
         // (the window planned ahead starts with the LAST iteration of the one before it, so that an exchange of that iteration still
@@ -629,30 +716,30 @@ void ensure_windows(Ctx* c, int t, bool rng = true) {
         c->cone_big_ok.assign(S.ok_host, S.ok_host + S.w);
         // the next window, into the set the launches enqueued so far read
         c->ps[nx ^ 1].w = 0;
-        if (S.t0 + S.w <= P.T) plan_window_into(c, nx ^ 1, S.t0 + S.w - (S.w >= 2 && c->plan_cap >= 2 ? 1 : 0));
+        if (S.t0 + S.w <= P.T) plan_window_into(c, nx ^ 1, S.t0 + S.w - (S.w >= 2 && c->F.plan_cap >= 2 ? 1 : 0));
     }
-    if (c->big_exchange && !c->plan_ahead && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
-        const int W = std::min(c->plan_cap, P.T - t + 1);
+    if (c->F.plan == PLAN_BIG && !c->F.plan_ahead && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
+        const int W = std::min(c->F.plan_cap, P.T - t + 1);
         hipLaunchKernelGGL(k_exch_plan_big, dim3(W), dim3(XWG), plan_big_lds_bytes(P.Ng), c->stream, P, t, c->big_scratch, c->win_lv_pairs, c->win_lv_mi,
                            c->win_lv_off, c->win_lv_rows, c->win_lv_rowinfo);
         c->plan_t0 = t; c->plan_w = W;
         P.plan_t0 = t;
-        if (c->cone_big) {   // the tiles' locally numbered cones, from the plan's scratch (pairs in list order, their levels)
+        if (c->F.cone_big) {   // the tiles' locally numbered cones, from the plan's scratch (pairs in list order, their levels)
             launch_cone_big(c, P, W, c->win_lv_pairs, c->win_lv_off, c->stream);
             // a cone that does not fit its caps (a pair list of very deep dependency chains: the user's, or an unlucky sample) sends its
             // iteration to the stand-alone resolution: the host looks at the window's flags once (one synchronisation per window)
             c->cone_big_ok.resize((size_t)W);
             HIPCHK(hipMemcpyAsync(c->cone_big_ok.data(), P.cone_ok, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
-        } else if (c->persist_sh_big) {   // (the persistent kernel looks at the window's flags itself: no synchronisation)
+        } else if (c->F.persist_sh_big) {   // (the persistent kernel looks at the window's flags itself: no synchronisation)
             launch_cone_big(c, P, W, c->win_lv_pairs, c->win_lv_off, c->stream);
         }
         P.lv_rows = c->win_lv_rows; P.lv_rowinfo = c->win_lv_rowinfo;
         P.lv_pairs = c->win_lv_pairs; P.lv_mi = c->win_lv_mi; P.lv_off = c->win_lv_off;
     }
-    if (c->lds_exchange && P.Ng > 1 && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
-        const int W = std::min(c->plan_cap, P.T - t + 1);
-        hipLaunchKernelGGL(k_exch_plan, dim3(W), dim3(XWG), (c->cone || c->persist) ? std::max(plan_lds_bytes(P.Ng, P.plan_K), plan_cone_bytes()) : plan_lds_bytes(P.Ng, P.plan_K), c->stream, P, t, c->win_plan,
+    if (c->F.plan == PLAN_LDS && P.Ng > 1 && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
+        const int W = std::min(c->F.plan_cap, P.T - t + 1);
+        hipLaunchKernelGGL(k_exch_plan, dim3(W), dim3(XWG), (c->F.cone || c->F.persist != PERSIST_NONE) ? std::max(plan_lds_bytes(P.Ng, P.plan_K), plan_cone_bytes()) : plan_lds_bytes(P.Ng, P.plan_K), c->stream, P, t, c->win_plan,
                            c->win_plan_mi, c->win_lv_pairs, c->win_lv_mi, c->win_lv_off, c->win_lv_pairs_p, c->win_lv_offp);
         c->plan_t0 = t; c->plan_w = W;
         P.plan = c->win_plan; P.plan_mi = c->win_plan_mi; P.plan_t0 = t;
@@ -668,81 +755,31 @@ void launch_chain_iter_ct(Ctx* c, int t, int flags) {
     // an objective without a simulation (banana, user objectives) has work for the tile's control wave only: unless the exchange
     // walk runs inline (all lanes stage its inputs) the tile is launched as that one wave, so that every tile of a large
     // population is resident at once instead of queueing behind 448 idle lanes each
-    const bool slim = KIND == 0 && TPW == 1 && !(flags & F_WALK_INLINE) && !c->inline_walk;
+    const bool slim = KIND == 0 && TPW == 1 && !(flags & F_WALK_INLINE) && !c->F.inline_walk;
     const dim3 grid((tiles + TPW - 1) / TPW), block(slim ? 64 : WG * TPW);
     const double* rin = c->ext_rec_in ? c->ext_rec_in : (const double*)c->rec[c->cur];
     double* rout = c->ext_rec_out ? c->ext_rec_out : c->rec[c->cur ^ 1];
     // (contexts that never walk inline run the kernel compiled without the walk)
-    auto kern = c->inline_walk ? k_chain_iter<KIND, CT, TPW, true> : k_chain_iter<KIND, CT, TPW, false>;
-    if (c->kev0)   // profiling mode 2: begin/end of this dispatch as the command processor stamps them
-        hipExtLaunchKernelGGL(kern, grid, block, tile_smem(c, CT, TPW), c->stream, c->kev0, c->kev1, 0, P, t, rin, rout, flags);
-    else
-        hipLaunchKernelGGL(kern, grid, block, tile_smem(c, CT, TPW), c->stream, P, t, rin, rout, flags);
+    auto kern = c->F.inline_walk ? k_chain_iter<KIND, CT, TPW, true> : k_chain_iter<KIND, CT, TPW, false>;
+    launch(c, kern, grid, block, tile_smem(c, CT, TPW), P, t, rin, rout, flags);
 }
 
-template <int NP, bool WALK>
-void launch_chain_iter_norm_t(Ctx* c, int t, int flags) {
+// k_chain_iter_norm and its variants: one 16-chain tile per workgroup of `block` lanes
+template <class Kern>
+void launch_norm_kernel(Ctx* c, Kern kern, unsigned block, int t, int flags) {
     const KParams& P = c->P;
-    const dim3 grid((P.N + NORM_CT - 1) / NORM_CT), block(NORM_WG);
     const double* rin = c->ext_rec_in ? c->ext_rec_in : (const double*)c->rec[c->cur];
     double* rout = c->ext_rec_out ? c->ext_rec_out : c->rec[c->cur ^ 1];
-    if (c->kev0)
-        hipExtLaunchKernelGGL((k_chain_iter_norm<NP, WALK>), grid, block, norm_smem(c), c->stream, c->kev0, c->kev1, 0, P, t, rin, rout, flags);
-    else
-        hipLaunchKernelGGL((k_chain_iter_norm<NP, WALK>), grid, block, norm_smem(c), c->stream, P, t, rin, rout, flags);
-}
-template <int NP>
-void launch_chain_iter_norm_narrow_t(Ctx* c, int t, int flags) {
-    const KParams& P = c->P;
-    const dim3 grid((P.N + NORM_CT - 1) / NORM_CT), block(NORM_WG / 2);
-    const double* rin = c->ext_rec_in ? c->ext_rec_in : (const double*)c->rec[c->cur];
-    double* rout = c->ext_rec_out ? c->ext_rec_out : c->rec[c->cur ^ 1];
-    if (c->kev0)
-        hipExtLaunchKernelGGL((k_chain_iter_norm_narrow<NP>), grid, block, norm_smem(c), c->stream, c->kev0, c->kev1, 0, P, t, rin, rout, flags);
-    else
-        hipLaunchKernelGGL((k_chain_iter_norm_narrow<NP>), grid, block, norm_smem(c), c->stream, P, t, rin, rout, flags);
-}
-template <int NP>
-void launch_chain_iter_norm_wide_t(Ctx* c, int t, int flags) {
-    const KParams& P = c->P;
-    const dim3 grid((P.N + NORM_CT - 1) / NORM_CT), block(NORM_WG);
-    const double* rin = c->ext_rec_in ? c->ext_rec_in : (const double*)c->rec[c->cur];
-    double* rout = c->ext_rec_out ? c->ext_rec_out : c->rec[c->cur ^ 1];
-    if (c->kev0)
-        hipExtLaunchKernelGGL((k_chain_iter_norm_wide<NP>), grid, block, norm_smem(c), c->stream, c->kev0, c->kev1, 0, P, t, rin, rout, flags);
-    else
-        hipLaunchKernelGGL((k_chain_iter_norm_wide<NP>), grid, block, norm_smem(c), c->stream, P, t, rin, rout, flags);
-}
-template <int NP>
-void launch_chain_iter_norm_any_t(Ctx* c, int t, int flags) {
-    const KParams& P = c->P;
-    const dim3 grid((P.N + NORM_CT - 1) / NORM_CT), block(NORM_WG);
-    const double* rin = c->ext_rec_in ? c->ext_rec_in : (const double*)c->rec[c->cur];
-    double* rout = c->ext_rec_out ? c->ext_rec_out : c->rec[c->cur ^ 1];
-    if (c->kev0)
-        hipExtLaunchKernelGGL((k_chain_iter_norm_any<NP>), grid, block, norm_smem(c), c->stream, c->kev0, c->kev1, 0, P, t, rin, rout, flags);
-    else
-        hipLaunchKernelGGL((k_chain_iter_norm_any<NP>), grid, block, norm_smem(c), c->stream, P, t, rin, rout, flags);
-}
-template <int NP>
-void launch_chain_iter_norm_narrow_cone_t(Ctx* c, int t, int flags) {
-    const KParams& P = c->P;
-    const dim3 grid((P.N + NORM_CT - 1) / NORM_CT), block(NORM_WG / 2);
-    const double* rin = (const double*)c->rec[c->cur];
-    double* rout = c->rec[c->cur ^ 1];
-    if (c->kev0)
-        hipExtLaunchKernelGGL((k_chain_iter_norm_narrow_cone<NP>), grid, block, norm_smem(c), c->stream, c->kev0, c->kev1, 0, P, t, rin, rout, flags);
-    else
-        hipLaunchKernelGGL((k_chain_iter_norm_narrow_cone<NP>), grid, block, norm_smem(c), c->stream, P, t, rin, rout, flags);
+    launch(c, kern, dim3((P.N + NORM_CT - 1) / NORM_CT), dim3(block), norm_smem(c), P, t, rin, rout, flags);
 }
 void launch_chain_iter_norm(Ctx* c, int t, int flags) {
     const bool walk = (flags & F_WALK_INLINE) != 0;
-    if (walk && c->cone_big) {   // large single shards: every tile walks its own, locally numbered cone (smm_cone_big.hpp)
+    if (walk && c->F.cone_big) {   // large single shards: every tile walks its own, locally numbered cone (smm_cone_big.hpp)
         switch (c->P.np) {
-            case 1: launch_chain_iter_norm_narrow_cone_t<1>(c, t, flags); break;
-            case 2: launch_chain_iter_norm_narrow_cone_t<2>(c, t, flags); break;
-            case 3: launch_chain_iter_norm_narrow_cone_t<3>(c, t, flags); break;
-            default: launch_chain_iter_norm_narrow_cone_t<4>(c, t, flags); break;
+            case 1: launch_norm_kernel(c, k_chain_iter_norm_narrow_cone<1>, NORM_WG / 2, t, flags); break;
+            case 2: launch_norm_kernel(c, k_chain_iter_norm_narrow_cone<2>, NORM_WG / 2, t, flags); break;
+            case 3: launch_norm_kernel(c, k_chain_iter_norm_narrow_cone<3>, NORM_WG / 2, t, flags); break;
+            default: launch_norm_kernel(c, k_chain_iter_norm_narrow_cone<4>, NORM_WG / 2, t, flags); break;
         }
         return;
     }
@@ -751,40 +788,40 @@ void launch_chain_iter_norm(Ctx* c, int t, int flags) {
     // kernel with the walk on 16-byte slots {value, src, partner} runs
     if (walk && (!c->P.lv_pairs_p || c->deep_plan || c->nan_values || c->P.mi_pct)) {   // (mi_pct: the lean plan stands for the persistent launches only)
         switch (c->P.np) {
-            case 1: launch_chain_iter_norm_any_t<1>(c, t, flags); break;
-            case 2: launch_chain_iter_norm_any_t<2>(c, t, flags); break;
-            case 3: launch_chain_iter_norm_any_t<3>(c, t, flags); break;
-            default: launch_chain_iter_norm_any_t<4>(c, t, flags); break;
+            case 1: launch_norm_kernel(c, k_chain_iter_norm_any<1>, NORM_WG, t, flags); break;
+            case 2: launch_norm_kernel(c, k_chain_iter_norm_any<2>, NORM_WG, t, flags); break;
+            case 3: launch_norm_kernel(c, k_chain_iter_norm_any<3>, NORM_WG, t, flags); break;
+            default: launch_norm_kernel(c, k_chain_iter_norm_any<4>, NORM_WG, t, flags); break;
         }
         return;
     }
     if (walk && c->P.lean_wide) {   // one min_improve > 0 for all chains: the lean walk on 16-byte slots
         switch (c->P.np) {
-            case 1: launch_chain_iter_norm_wide_t<1>(c, t, flags); break;
-            case 2: launch_chain_iter_norm_wide_t<2>(c, t, flags); break;
-            case 3: launch_chain_iter_norm_wide_t<3>(c, t, flags); break;
-            default: launch_chain_iter_norm_wide_t<4>(c, t, flags); break;
+            case 1: launch_norm_kernel(c, k_chain_iter_norm_wide<1>, NORM_WG, t, flags); break;
+            case 2: launch_norm_kernel(c, k_chain_iter_norm_wide<2>, NORM_WG, t, flags); break;
+            case 3: launch_norm_kernel(c, k_chain_iter_norm_wide<3>, NORM_WG, t, flags); break;
+            default: launch_norm_kernel(c, k_chain_iter_norm_wide<4>, NORM_WG, t, flags); break;
         }
         return;
     }
-    if (!walk && c->norm_narrow) {   // more than one round of tiles: two half-size workgroups per CU (k_chain_iter_norm_narrow)
+    if (!walk && c->F.norm_narrow) {   // more than one round of tiles: two half-size workgroups per CU (k_chain_iter_norm_narrow)
         switch (c->P.np) {
-            case 1: launch_chain_iter_norm_narrow_t<1>(c, t, flags); break;
-            case 2: launch_chain_iter_norm_narrow_t<2>(c, t, flags); break;
-            case 3: launch_chain_iter_norm_narrow_t<3>(c, t, flags); break;
-            default: launch_chain_iter_norm_narrow_t<4>(c, t, flags); break;
+            case 1: launch_norm_kernel(c, k_chain_iter_norm_narrow<1>, NORM_WG / 2, t, flags); break;
+            case 2: launch_norm_kernel(c, k_chain_iter_norm_narrow<2>, NORM_WG / 2, t, flags); break;
+            case 3: launch_norm_kernel(c, k_chain_iter_norm_narrow<3>, NORM_WG / 2, t, flags); break;
+            default: launch_norm_kernel(c, k_chain_iter_norm_narrow<4>, NORM_WG / 2, t, flags); break;
         }
         return;
     }
     switch (c->P.np * 2 + (walk ? 1 : 0)) {
-        case 2: launch_chain_iter_norm_t<1, false>(c, t, flags); break;
-        case 3: launch_chain_iter_norm_t<1, true>(c, t, flags); break;
-        case 4: launch_chain_iter_norm_t<2, false>(c, t, flags); break;
-        case 5: launch_chain_iter_norm_t<2, true>(c, t, flags); break;
-        case 6: launch_chain_iter_norm_t<3, false>(c, t, flags); break;
-        case 7: launch_chain_iter_norm_t<3, true>(c, t, flags); break;
-        case 8: launch_chain_iter_norm_t<4, false>(c, t, flags); break;
-        default: launch_chain_iter_norm_t<4, true>(c, t, flags); break;
+        case 2: launch_norm_kernel(c, k_chain_iter_norm<1, false>, NORM_WG, t, flags); break;
+        case 3: launch_norm_kernel(c, k_chain_iter_norm<1, true>, NORM_WG, t, flags); break;
+        case 4: launch_norm_kernel(c, k_chain_iter_norm<2, false>, NORM_WG, t, flags); break;
+        case 5: launch_norm_kernel(c, k_chain_iter_norm<2, true>, NORM_WG, t, flags); break;
+        case 6: launch_norm_kernel(c, k_chain_iter_norm<3, false>, NORM_WG, t, flags); break;
+        case 7: launch_norm_kernel(c, k_chain_iter_norm<3, true>, NORM_WG, t, flags); break;
+        case 8: launch_norm_kernel(c, k_chain_iter_norm<4, false>, NORM_WG, t, flags); break;
+        default: launch_norm_kernel(c, k_chain_iter_norm<4, true>, NORM_WG, t, flags); break;
     }
 }
 
@@ -808,7 +845,7 @@ void launch_chain_iter(Ctx* c, int t, int flags) {
     point_values(c, c->P, t - 1, t);   // the inline walk reads what the accept step of t-1 wrote; this accept step writes the other array
     if (c->ext_vals_out) { c->P.vals_out = c->ext_vals_out; c->P.slot8_out = nullptr; }
     // large single shards (k_exch_resolve_rows): the accept step writes the resolution's initial slots itself
-    const bool own_slots = c->rows_exchange && c->P.N == c->P.Ng && !c->ext_rec_out && !c->ext_vals_out && c->obj != SMM_OBJ_USER;
+    const bool own_slots = c->F.xk == XK_ROWS && c->P.N == c->P.Ng && !c->ext_rec_out && !c->ext_vals_out && c->obj != SMM_OBJ_USER;
     c->P.slots17_out = own_slots ? c->slots17 : nullptr;
     c->P.nan_flags_out = own_slots ? c->nan_flags + (t & 1) : nullptr;
     if (own_slots) c->slots_iter = t;
@@ -823,18 +860,18 @@ void launch_chain_iter(Ctx* c, int t, int flags) {
         if (!c->ext_rec_out) c->cur ^= 1;
         return;
     }
-    if (c->norm_fast) {
+    if (c->F.norm_fast) {
         launch_chain_iter_norm(c, t, flags);
     } else if (is_sim(c->obj)) {
-        if (c->tpw == 2) launch_chain_iter_ct<1, 8, 2>(c, t, flags);
+        if (c->F.tpw == 2) launch_chain_iter_ct<1, 8, 2>(c, t, flags);
         else launch_chain_iter_ct<1, 8>(c, t, flags);
     } else if (c->obj == SMM_OBJ_DENSE) {
         launch_chain_iter_ct<2, 16>(c, t, flags);
-    } else if (c->gen_keys) {
+    } else if (c->F.gen_keys) {
         launch_chain_iter_ct<0, 16, 2>(c, t, flags);
-    } else if (tile_smem_base(c, 64) <= (size_t)60 * 1024 && !c->inline_walk) {
+    } else if (tile_smem_base(c, 64) <= (size_t)60 * 1024 && !c->F.inline_walk) {
         launch_chain_iter_ct<0, 64>(c, t, flags);
-    } else if (c->tpw == 2) {
+    } else if (c->F.tpw == 2) {
         launch_chain_iter_ct<0, 8, 2>(c, t, flags);
     } else {
         launch_chain_iter_ct<0, 8>(c, t, flags);
@@ -847,53 +884,19 @@ size_t resolve_lean_bytes(int Ng, int K, bool wide) { return std::max(wide ? lea
 void launch_resolve_p(Ctx* c, const KParams& P, int t, const double* gathered);
 void launch_resolve(Ctx* c, int t, const double* gathered) { launch_resolve_p(c, c->P, t, gathered); }
 // (P: the context's parameters, or a copy whose RW is the stride of the value column in `gathered`)
-// Which stand-alone kernel resolves exchangeMoves! (AlgoBGP.jl:647-716) — ONE decision, taken once per context (choose_exchange,
-// at the end of smm_ctx_create), from the population, the thresholds and dist_fun:
-//
-//   N_global        min_improve                      dist_fun   kernel                       slots / where
-//   <= 8192 (~7400) one value >= 0 for all chains    -          k_exch_resolve_lean          8-byte keys (0) or 16-byte values (> 0), LDS
-//   <= 4096         anything else                    any        k_exch_resolve_lvl<1024>     16-byte slots, LDS
-//   <= 8192         anything else                    any        k_exch_resolve_lvl_soa       split slots, LDS
-//   <= 32768        0 for all chains                 -          k_exch_keys + _rows          4-byte slots (17-bit keys), rows of 1024 pairs, LDS
-//   <= 32768        anything else                    -          k_exch_keys + _key           4-byte slots (16-bit keys, intervals), LDS
-//   <= 65535        anything else / other dist_fun   any        k_exch_resolve_lvl_big       16-byte slots, global memory
-//   above, or K > N_global                           any        k_exch_resolve_any           barrier rounds, global atomics
-//
-// (the p2p form of a sharded run launches k_exch_resolve_rows itself where this table says _rows — launch_resolve_rows_window:
-//  <., true> reads the tagged slots of its window instead of a key pre-pass, <false, true, true> keeps the partners of the rank's
-//  own chains only; every other p2p population resolves from the window's plain values through this table.)
-// (single shards of objfunc_norm up to 4096 chains do not get here in steady state: their chain kernel walks inline.)  The test
-// build can force an entry (SMM_TEST_HOOKS: SMMHIP_*_EXCHANGE, SMMHIP_KEY_WALK) and adds the ticket kernel k_exch_resolve_lds.
-enum ExchKernel { XK_LEAN, XK_LVL, XK_LVL_SOA, XK_TICKETS, XK_ROWS, XK_KEY, XK_LVL_BIG, XK_ANY };
-ExchKernel choose_exchange(const Ctx* c) {
-    if (c->lean_resolve) return XK_LEAN;
-    if (c->lvl_exchange) return XK_LVL;
-    if (c->lvl_soa_exchange) return XK_LVL_SOA;
-    if (c->lds_exchange) return XK_TICKETS;   // (test build only: SMMHIP_DATAFLOW_EXCHANGE)
-    if (c->key_exchange) return c->rows_exchange ? XK_ROWS : XK_KEY;
-    if (c->big_exchange) return XK_LVL_BIG;
-    return XK_ANY;
-}
 void launch_resolve_p(Ctx* c, const KParams& P_in, int t, const double* gathered) {
     KParams P = P_in;
     point_values(c, P, t, t);   // (single shard: the values the accept step of iteration t wrote)
-    switch ((ExchKernel)c->xk) {
+    switch ((ExchKernel)c->F.xk) {
     case XK_LEAN:
-        if (c->kev0)
-            hipExtLaunchKernelGGL(k_exch_resolve_lean, dim3(1), dim3(XWG), resolve_lean_bytes(P.Ng, P.plan_K, P.lean_wide != 0), c->stream, c->kev0, c->kev1, 0, P, t,
-                                  gathered);
-        else
-            hipLaunchKernelGGL(k_exch_resolve_lean, dim3(1), dim3(XWG), resolve_lean_bytes(P.Ng, P.plan_K, P.lean_wide != 0), c->stream, P, t, gathered);
+        launch(c, k_exch_resolve_lean, dim3(1), dim3(XWG), resolve_lean_bytes(P.Ng, P.plan_K, P.lean_wide != 0), P, t, gathered);
         break;
     case XK_LVL:
 #ifdef SMM_TEST_HOOKS
-        if (c->lvl_wg == 256) { hipLaunchKernelGGL(k_exch_resolve_lvl<256>, dim3(1), dim3(256), resolve_lvl_bytes(P.Ng, P.plan_K), c->stream, P, t, gathered); break; }
-        if (c->lvl_wg == 512) { hipLaunchKernelGGL(k_exch_resolve_lvl<512>, dim3(1), dim3(512), resolve_lvl_bytes(P.Ng, P.plan_K), c->stream, P, t, gathered); break; }
+        if (c->H.lvl_wg == 256) { hipLaunchKernelGGL(k_exch_resolve_lvl<256>, dim3(1), dim3(256), resolve_lvl_bytes(P.Ng, P.plan_K), c->stream, P, t, gathered); break; }
+        if (c->H.lvl_wg == 512) { hipLaunchKernelGGL(k_exch_resolve_lvl<512>, dim3(1), dim3(512), resolve_lvl_bytes(P.Ng, P.plan_K), c->stream, P, t, gathered); break; }
 #endif
-        if (c->kev0)
-            hipExtLaunchKernelGGL(k_exch_resolve_lvl<1024>, dim3(1), dim3(1024), resolve_lvl_bytes(P.Ng, P.plan_K), c->stream, c->kev0, c->kev1, 0, P, t, gathered);
-        else
-            hipLaunchKernelGGL(k_exch_resolve_lvl<1024>, dim3(1), dim3(1024), resolve_lvl_bytes(P.Ng, P.plan_K), c->stream, P, t, gathered);
+        launch(c, k_exch_resolve_lvl<1024>, dim3(1), dim3(1024), resolve_lvl_bytes(P.Ng, P.plan_K), P, t, gathered);
         break;
     case XK_LVL_SOA:
         hipLaunchKernelGGL(k_exch_resolve_lvl_soa<1024>, dim3(1), dim3(1024), resolve_lvl_soa_bytes(P.Ng, P.plan_K), c->stream, P, t, gathered);
@@ -910,13 +913,13 @@ void launch_resolve_p(Ctx* c, const KParams& P_in, int t, const double* gathered
         double* vals = gathered ? P.xval : P.vals;
         if (gathered || c->slots_iter != t)   // (a single shard's accept step of iteration t has made the slots already)
             hipLaunchKernelGGL(k_exch_keys, dim3((P.Ng + 255) / 256), dim3(256), 0, c->stream, src, gathered ? P.RW : 1, P.Ng, vals,
-                               (uint32_t*)P.xsrc, c->rows_exchange ? c->slots17 : (uint32_t*)nullptr, c->nan_flags, t);
+                               (uint32_t*)P.xsrc, c->F.xk == XK_ROWS ? c->slots17 : (uint32_t*)nullptr, c->nan_flags, t);
         const bool plds = P.Ng <= XKEY_PARTNER_MAX;   // partners in LDS, else the ballot replay
         const uint32_t* slots16 = (gathered || c->slots_iter != t) ? (const uint32_t*)P.xsrc : (const uint32_t*)nullptr;
-        if (c->xk == XK_ROWS && plds)
+        if (c->F.xk == XK_ROWS && plds)
             hipLaunchKernelGGL(k_exch_resolve_rows<true>, dim3(1), dim3(XWG), resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap), c->stream, P, t,
                                (const double*)vals, slots16, (const uint32_t*)c->slots17, c->nan_flags);
-        else if (c->xk == XK_ROWS)
+        else if (c->F.xk == XK_ROWS)
             hipLaunchKernelGGL(k_exch_resolve_rows<false>, dim3(1), dim3(XWG), resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap), c->stream, P, t,
                                (const double*)vals, slots16, (const uint32_t*)c->slots17, c->nan_flags);
         else if (plds)
@@ -1015,7 +1018,7 @@ int check_device_error(Ctx* c) {
     if (c->failed) return c->failed;   // err holds the message of the first failure
     unsigned long long e = ERR_NONE;
     HIPCHK(hipMemcpy(&e, c->P.err, sizeof e, hipMemcpyDeviceToHost));
-    if (c->persist_sh && c->snap_valid && !c->in_repair && c->p2p_mine) {
+    if (c->F.persist_sh && c->snap_valid && !c->in_repair && c->p2p_mine) {
         // launches of the persistent form ran on every rank: what one of them ended with concerns all (its tiles did not stop either)
         const unsigned long long eg = p2p_agree_error(c, e);
         if (eg != ERR_NONE) {
@@ -1107,11 +1110,7 @@ struct DevBuf {
 // ---- the p2p form of the sharded iteration (smm_p2p.hpp, include/smmhip.h) ----
 template <int NP, bool BIG>
 void launch_chain_iter_norm_p2p_tb(Ctx* c, const KParams& P, int t, int flags, size_t smem) {
-    const dim3 grid((P.N + NORM_CT - 1) / NORM_CT), block(NORM_WG);
-    if (c->kev0)
-        hipExtLaunchKernelGGL((k_chain_iter_norm_p2p<NP, BIG>), grid, block, smem, c->stream, c->kev0, c->kev1, 0, P, t, (const double*)nullptr, (double*)nullptr, flags);
-    else
-        hipLaunchKernelGGL((k_chain_iter_norm_p2p<NP, BIG>), grid, block, smem, c->stream, P, t, (const double*)nullptr, (double*)nullptr, flags);
+    launch(c, k_chain_iter_norm_p2p<NP, BIG>, dim3((P.N + NORM_CT - 1) / NORM_CT), dim3(NORM_WG), smem, P, t, (const double*)nullptr, (double*)nullptr, flags);
 }
 template <int NP>
 void launch_chain_iter_norm_p2p_t(Ctx* c, const KParams& P, int t, int flags, size_t smem) {
@@ -1122,16 +1121,11 @@ void launch_chain_iter_norm_p2p_t(Ctx* c, const KParams& P, int t, int flags, si
 size_t p2p_walk_bytes(const Ctx* c) { return (lean_walk_bytes(c->P.Ng, c->P.plan_K) + 15) & ~(size_t)15; }
 template <int NP>
 void launch_chain_iter_norm_p2p_rows_t(Ctx* c, const KParams& P, int t, int flags, size_t smem) {
-    const dim3 grid((P.N + NORM_CT - 1) / NORM_CT), block(c->norm_narrow ? NORM_WG / 2 : NORM_WG);
-    if (c->norm_narrow) {   // a shard of more than one round of tiles
-        if (c->kev0)
-            hipExtLaunchKernelGGL((k_chain_iter_norm_p2p_rows_narrow<NP>), grid, block, smem, c->stream, c->kev0, c->kev1, 0, P, t, (const double*)nullptr, (double*)nullptr, flags);
-        else
-            hipLaunchKernelGGL((k_chain_iter_norm_p2p_rows_narrow<NP>), grid, block, smem, c->stream, P, t, (const double*)nullptr, (double*)nullptr, flags);
-    } else if (c->kev0)
-        hipExtLaunchKernelGGL((k_chain_iter_norm_p2p_rows<NP>), grid, block, smem, c->stream, c->kev0, c->kev1, 0, P, t, (const double*)nullptr, (double*)nullptr, flags);
+    const dim3 grid((P.N + NORM_CT - 1) / NORM_CT), block(c->F.norm_narrow ? NORM_WG / 2 : NORM_WG);
+    if (c->F.norm_narrow)   // a shard of more than one round of tiles
+        launch(c, k_chain_iter_norm_p2p_rows_narrow<NP>, grid, block, smem, P, t, (const double*)nullptr, (double*)nullptr, flags);
     else
-        hipLaunchKernelGGL((k_chain_iter_norm_p2p_rows<NP>), grid, block, smem, c->stream, P, t, (const double*)nullptr, (double*)nullptr, flags);
+        launch(c, k_chain_iter_norm_p2p_rows<NP>, grid, block, smem, P, t, (const double*)nullptr, (double*)nullptr, flags);
 }
 void launch_chain_iter_norm_p2p(Ctx* c, int t, int flags) {
     KParams P = c->P;
@@ -1190,17 +1184,14 @@ void launch_resolve_rows_window(Ctx* c, int t) {
     const bool own = P.Ng > XKEY_PARTNER_MAX && P.N < P.Ng && resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap, P.N) <= (size_t)158 * 1024;
     if (own) {
         const size_t sm = resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap, P.N);
-        if (c->kev0) hipExtLaunchKernelGGL((k_exch_resolve_rows<false, true, true>), dim3(1), dim3(XWG), sm, c->stream, c->kev0, c->kev1, 0, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-        else hipLaunchKernelGGL((k_exch_resolve_rows<false, true, true>), dim3(1), dim3(XWG), sm, c->stream, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+        launch(c, k_exch_resolve_rows<false, true, true>, dim3(1), dim3(XWG), sm, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
         return;
     }
     const size_t smem = resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap);
     if (P.Ng <= XKEY_PARTNER_MAX) {
-        if (c->kev0) hipExtLaunchKernelGGL((k_exch_resolve_rows<true, true>), dim3(1), dim3(XWG), smem, c->stream, c->kev0, c->kev1, 0, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-        else hipLaunchKernelGGL((k_exch_resolve_rows<true, true>), dim3(1), dim3(XWG), smem, c->stream, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+        launch(c, k_exch_resolve_rows<true, true>, dim3(1), dim3(XWG), smem, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
     } else {
-        if (c->kev0) hipExtLaunchKernelGGL((k_exch_resolve_rows<false, true>), dim3(1), dim3(XWG), smem, c->stream, c->kev0, c->kev1, 0, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-        else hipLaunchKernelGGL((k_exch_resolve_rows<false, true>), dim3(1), dim3(XWG), smem, c->stream, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+        launch(c, k_exch_resolve_rows<false, true>, dim3(1), dim3(XWG), smem, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
     }
 }
 // ---- the persistent chain kernels (smm_chain_persist.hpp, smm_chain_persist_loc.hpp) ----
@@ -1216,13 +1207,13 @@ const void* persist_loc_fn(int np, bool wide, bool sh, bool pct = false) {
 // state, no exchange applied by the three-phase calls), and an exchange left to "the next chain kernel" must have its plan in the
 // current window together with this iteration's.
 bool persist_usable(const Ctx* c, int n_left) {
-    if (!(c->persist && c->persist_on && !c->persist_broken && !c->in_repair && !c->nan_values && n_left >= 2 && !c->ext_rec_in && !c->ext_rec_out &&
+    if (!(c->F.persist != PERSIST_NONE && c->persist_on && !c->persist_broken && !c->in_repair && !c->nan_values && n_left >= 2 && !c->ext_rec_in && !c->ext_rec_out &&
           !c->ext_vals_out && !c->rec_external && c->P.N == c->P.Ng))
         return false;
     if (c->iter < 1 || !c->prev_open || c->exch_done || (c->pending && !c->unresolved)) return false;
     const int t0 = c->iter + 1;
     // (the locally numbered form starts a new plan window at the pending exchange's iteration instead: launch_chain_persist)
-    if (!c->persist_loc && !c->persist_tile && c->unresolved && !(t0 - 1 >= c->plan_t0 && t0 + 1 < c->plan_t0 + c->plan_w)) return false;
+    if (c->F.persist != PERSIST_LOC && c->F.persist != PERSIST_TILE && c->unresolved && !(t0 - 1 >= c->plan_t0 && t0 + 1 < c->plan_t0 + c->plan_w)) return false;
     return true;
 }
 // ... as a shard (smm_bgp_p2p_step): from the p2p state — the records after iteration `iter` in the windows, its exchange not resolved
@@ -1231,8 +1222,8 @@ bool persist_sh_usable(const Ctx* c, int n_left) {
     // (NOT c->nan_values: that flag is this shard's own — smm_set_state saw a NaN among ITS values — and the form must be chosen from what every
     // rank knows, or one rank would take the per-iteration kernels while its peers wait at the launches' start barrier.  The launch reports such a
     // state itself — kind 3 at its first iteration, smm_chain_persist_loc.hpp —, the ranks agree on the word and replay the step on the other forms)
-    if (!(c->persist_sh && c->persist_on && !c->persist_broken && !c->in_repair && n_left >= 2 && c->p2p_mine)) return false;
-    if (c->p2p_ranks_here * ((c->P.N + NORM_CT - 1) / NORM_CT) > c->persist_max_tiles) return false;   // (ranks sharing this device: not resident together)
+    if (!(c->F.persist_sh && c->persist_on && !c->persist_broken && !c->in_repair && n_left >= 2 && c->p2p_mine)) return false;
+    if (c->p2p_ranks_here * ((c->P.N + NORM_CT - 1) / NORM_CT) > c->F.max_tiles) return false;   // (ranks sharing this device: not resident together)
     if (c->iter < 1 || !c->prev_open || c->exch_done || c->a2a_open) return false;
     if (c->p2p_current) return c->rec_external && (c->pending_ext || !exchange_active(c, c->iter));
     return !c->rec_external && (c->unresolved || !c->pending);
@@ -1258,8 +1249,8 @@ int launch_chain_persist(Ctx* c, int n_left) {
     // (k_chain_persist_norm and _gen draw in the kernel unless tables are injected)
     // (k_chain_persist_tile too, since round 5: its 512 lanes draw the next iteration's randomness behind the publication, where the tile waits for
     // its peers' stores anyway — k_pregen_rng was 2.2 us per iteration of C5 on the main stream)
-    const bool pregen = (c->persist_gen || c->persist_tile) ? (c->P.user_ntab || c->P.user_utab) : !(c->norm_fast && !c->P.user_ntab && !c->P.user_utab);
-    if ((c->persist_loc || c->persist_tile) && c->unresolved && !(t0 - 1 >= c->plan_t0 && t0 + 1 < c->plan_t0 + c->plan_w)) {
+    const bool pregen = (c->F.persist == PERSIST_GEN || c->F.persist == PERSIST_TILE) ? (c->P.user_ntab || c->P.user_utab) : !(c->F.norm_fast && !c->P.user_ntab && !c->P.user_utab);
+    if ((c->F.persist == PERSIST_LOC || c->F.persist == PERSIST_TILE) && c->unresolved && !(t0 - 1 >= c->plan_t0 && t0 + 1 < c->plan_t0 + c->plan_w)) {
         // the pending exchange's plan is not in a window that also reaches past this iteration: a new window from ITS iteration on (one
         // iteration planned twice per window; no per-iteration launch, no stand-alone resolution at the windows' ends)
         c->plan_w = 0;
@@ -1273,9 +1264,9 @@ int launch_chain_persist(Ctx* c, int n_left) {
     if (!c->snap_valid) persist_snapshot(c);
     ++c->pr_epoch;
     if ((c->pr_epoch & 0x7fu) == 0u) {   // the slot tags' epoch bits start over: nothing older may look current
-        if (c->persist_loc || c->persist_tile) {   // (a shard zeroes its own window's ring: its peers store into it only behind the launch's start barrier)
-            const PrWin WL = pr_win_layout(c->P.Ng, c->P.RW, c->persist_sh ? c->P.p2p_G : 1, (c->P.N + NORM_CT - 1) / NORM_CT);   // (PT_CT == NORM_CT)
-            unsigned char* base = c->persist_sh ? c->p2p_mine + c->prw_off : c->prw;
+        if (c->F.persist == PERSIST_LOC || c->F.persist == PERSIST_TILE) {   // (a shard zeroes its own window's ring: its peers store into it only behind the launch's start barrier)
+            const PrWin WL = pr_win_layout(c->P.Ng, c->P.RW, c->F.persist_sh ? c->P.p2p_G : 1, (c->P.N + NORM_CT - 1) / NORM_CT);   // (PT_CT == NORM_CT)
+            unsigned char* base = c->F.persist_sh ? c->p2p_mine + c->prw_off : c->prw;
             HIPCHK(hipMemsetAsync(base + WL.slot, 0, WL.total - WL.slot, c->stream));
         } else {
             HIPCHK(hipMemsetAsync(c->P.pr_slot, 0, persist_ring_slot_bytes(c->P.Ng), c->stream));
@@ -1288,15 +1279,15 @@ int launch_chain_persist(Ctx* c, int n_left) {
     // (a spin of the form may last 4 s — a peer is gone, not late — once a launch of this context has come through; until then a
     // tenth of that: tiles that are not resident together, a masked or partitioned device, must not look like a hang)
     // (a shard waits for its PEERS' launches at the start barrier: processes that start a second apart are late, not gone — 4 s from the start)
-    const unsigned long long tmo = (c->persist_proven || c->persist_sh) ? P2P_TIMEOUT_TICKS : PERSIST_TMO_FIRST;
-    if (c->persist_loc) {
+    const unsigned long long tmo = (c->persist_proven || c->F.persist_sh) ? P2P_TIMEOUT_TICKS : PERSIST_TMO_FIRST;
+    if (c->F.persist == PERSIST_LOC) {
         PersistLocArgs A{};
-        const int G = c->persist_sh ? P.p2p_G : 1;
+        const int G = c->F.persist_sh ? P.p2p_G : 1;
         const int tiles = (P.N + NORM_CT - 1) / NORM_CT;
         const PrWin WL = pr_win_layout(P.Ng, P.RW, G, tiles);
         A.cone_hdr = P.cone_hdr; A.cone_pairs = P.cone_pairs; A.cone_gather = P.cone_gather; A.cone_ok = P.cone_ok;
         for (int r = 0; r < P2P_MAXG; ++r) A.win[r] = nullptr;
-        if (c->persist_sh) {
+        if (c->F.persist_sh) {
             for (int r = 0; r < G; ++r) A.win[r] = P.p2p_win[r] + c->prw_off;
             A.self = c->p2p_mine + c->prw_off;
         } else { A.win[0] = c->prw; A.self = c->prw; }
@@ -1305,22 +1296,19 @@ int launch_chain_persist(Ctx* c, int n_left) {
         A.hrec = P.hrec; A.err = P.err; A.ts = P.ts;
         A.Z = P.Z; A.lb = P.lb; A.ub = P.ub; A.mom = P.mom; A.w = P.w; A.objp = P.objp;
         A.rb = pregen ? P.rb : nullptr;
-        A.N = P.N; A.Ng = P.Ng; A.offset = P.offset; A.G = G; A.rank = c->persist_sh ? P.p2p_rank : 0; A.ns = P.ns; A.zstride = P.zstride; A.plan_t0 = P.plan_t0;
+        A.N = P.N; A.Ng = P.Ng; A.offset = P.offset; A.G = G; A.rank = c->F.persist_sh ? P.p2p_rank : 0; A.ns = P.ns; A.zstride = P.zstride; A.plan_t0 = P.plan_t0;
         A.exch_from = c->exchange_from;
         A.sigma_update_steps = P.sigma_update_steps; A.smpl_iters = P.smpl_iters; A.t0 = t0; A.t1 = t1;
         A.rb_t0 = P.rb_t0; A.RBW = P.RBW; A.rb_tries = P.rb_tries; A.user_n = P.user_n;
         A.failbox = (P.obj == SMM_OBJ_NORM_FAILBOX && P.objp) ? 1 : 0;
         A.walk_first = c->unresolved ? 1 : 0;
-        A.ring_k = c->pr_ring_k; A.slow_tile = c->pr_slow_tile; A.slow_ticks = c->pr_slow_ticks;
-        A.tables_local = c->persist_sh_big ? 1 : 0; A.unit_sh = P.lean_unit == 16 ? 4 : (P.lean_unit == 8 ? 3 : 2);
+        A.ring_k = c->H.pr_ring_k; A.slow_tile = c->H.pr_slow_tile; A.slow_ticks = c->H.pr_slow_ticks;
+        A.tables_local = c->F.persist_sh_big ? 1 : 0; A.unit_sh = P.lean_unit == 16 ? 4 : (P.lean_unit == 8 ? 3 : 2);
         A.epoch = c->pr_epoch; A.sigma_adjust_by = P.sigma_adjust_by; A.thr = P.mi_value; A.seed = P.seed; A.tmo = tmo; A.mi_g = P.min_improve_g;
         const dim3 grid(tiles), block(NORM_WG);
         const size_t smem = persist_loc_smem_bytes(P.np);
-        auto go = [&](auto kern) {
-            if (c->kev0) hipExtLaunchKernelGGL(kern, grid, block, smem, c->stream, c->kev0, c->kev1, 0, A);
-            else hipLaunchKernelGGL(kern, grid, block, smem, c->stream, A);
-        };
-        const bool wd = c->persist_wide, sh = c->persist_sh;
+        auto go = [&](auto kern) { launch(c, kern, grid, block, smem, A); };
+        const bool wd = c->F.persist_wide, sh = c->F.persist_sh;
         if (P.mi_pct) { if (P.np == 1) go(k_chain_persist_loc<1, true, false, true>); else go(k_chain_persist_loc<2, true, false, true>); }
         else if (P.np == 1) {
             if (wd) { if (sh) go(k_chain_persist_loc<1, true, true>); else go(k_chain_persist_loc<1, true, false>); }
@@ -1329,7 +1317,7 @@ int launch_chain_persist(Ctx* c, int n_left) {
             if (wd) { if (sh) go(k_chain_persist_loc<2, true, true>); else go(k_chain_persist_loc<2, true, false>); }
             else { if (sh) go(k_chain_persist_loc<2, false, true>); else go(k_chain_persist_loc<2, false, false>); }
         }
-    } else if (c->persist_tile) {
+    } else if (c->F.persist == PERSIST_TILE) {
         PersistTileArgs A{};
         const int tiles = (P.N + PT_CT - 1) / PT_CT;
         const PrWin WL = pr_win_layout(P.Ng, P.RW, 1, tiles);
@@ -1344,23 +1332,20 @@ int launch_chain_persist(Ctx* c, int n_left) {
         A.batch_size = P.batch_size; A.failbox = (P.obj == SMM_OBJ_NORM_FAILBOX && P.objp) ? 1 : 0;
         A.plan_t0 = P.plan_t0; A.exch_from = c->exchange_from; A.sigma_update_steps = P.sigma_update_steps; A.smpl_iters = P.smpl_iters; A.t0 = t0; A.t1 = t1;
         A.rb_t0 = P.rb_t0; A.rb_tries = P.rb_tries; A.user_n = P.user_n;
-        A.ring_k = c->pr_ring_k; A.slow_tile = c->pr_slow_tile; A.slow_ticks = c->pr_slow_ticks; A.walk_first = c->unresolved ? 1 : 0;
+        A.ring_k = c->H.pr_ring_k; A.slow_tile = c->H.pr_slow_tile; A.slow_ticks = c->H.pr_slow_ticks; A.walk_first = c->unresolved ? 1 : 0;
         A.unit_sh = P.lean_unit == 16 ? 4 : (P.lean_unit == 8 ? 3 : 2); A.scout_after = P.scout_after; A.scout_gl = P.scout_gl;
         A.epoch = c->pr_epoch; A.sigma_adjust_by = P.sigma_adjust_by; A.thr = P.mi_value; A.seed = P.seed; A.tmo = tmo; A.mi_g = P.min_improve_g;
         const dim3 grid(tiles), block(WG);
         A.u_lanes = c->u_lanes; A.n_udata = c->n_objp;
         const size_t smem = persist_tile_smem(c);
-        auto go = [&](auto kern) {
-            if (c->kev0) hipExtLaunchKernelGGL(kern, grid, block, smem, c->stream, c->kev0, c->kev1, 0, A);
-            else hipLaunchKernelGGL(kern, grid, block, smem, c->stream, A);
-        };
+        auto go = [&](auto kern) { launch(c, kern, grid, block, smem, A); };
         if (c->utfn) {   // the same kernel, compiled with the user's map-reduce objective inside (user_tile_compile)
             void* args[] = {(void*)&A};
             if (c->kev0) HIPCHK(hipExtModuleLaunchKernel(c->utfn, grid.x * (unsigned)WG, 1, 1, WG, 1, 1, smem, c->stream, args, nullptr, c->kev0, c->kev1, 0));
             else HIPCHK(hipModuleLaunchKernel(c->utfn, grid.x, 1, 1, WG, 1, 1, (unsigned)smem, c->stream, args, nullptr));
         } else if (P.mi_pct) { if (kind == 2) go(k_chain_persist_tile<2, true>); else go(k_chain_persist_tile<1, true>); }
         else if (kind == 2) go(k_chain_persist_tile<2>); else go(k_chain_persist_tile<1>);
-    } else if (c->persist_gen) {
+    } else if (c->F.persist == PERSIST_GEN) {
         PersistGenArgs A{};
         A.cone_hdr = P.cone_hdr; A.cone_pairs = P.cone_pairs; A.cone_gather = P.cone_gather; A.cone_ok = P.cone_ok;
         A.pr_slot = P.pr_slot; A.pr_rec = P.pr_rec; A.pr_progress = P.pr_progress; A.pr_ctl = P.pr_ctl;
@@ -1372,17 +1357,16 @@ int launch_chain_persist(Ctx* c, int n_left) {
         A.sigma_update_steps = P.sigma_update_steps; A.smpl_iters = P.smpl_iters; A.t0 = t0; A.t1 = t1;
         A.rb_t0 = P.rb_t0; A.RBW = P.RBW; A.rb_tries = P.rb_tries; A.user_n = P.user_n;
         A.walk_first = c->unresolved ? 1 : 0;
-        A.ring_k = c->pr_ring_k; A.slow_tile = c->pr_slow_tile; A.slow_ticks = c->pr_slow_ticks;
+        A.ring_k = c->H.pr_ring_k; A.slow_tile = c->H.pr_slow_tile; A.slow_ticks = c->H.pr_slow_ticks;
         A.epoch = c->pr_epoch; A.sigma_adjust_by = P.sigma_adjust_by; A.seed = P.seed; A.tmo = tmo;
         A.udata = P.objp; A.n_udata = c->n_objp;
         const dim3 grid(P.N / PG_CT), block(1024);
-        const size_t smem = persist_gen_smem_bytes(P.Ng, P.np, P.RW, P.HW) + (c->persist_user ? persist_gen_user_bytes() : 0);
-        if (c->persist_user) {   // the same kernel, compiled with the user's objective inside (user_persist_compile)
+        const size_t smem = persist_gen_smem_bytes(P.Ng, P.np, P.RW, P.HW) + (c->F.persist_user ? persist_gen_user_bytes() : 0);
+        if (c->F.persist_user) {   // the same kernel, compiled with the user's objective inside (user_persist_compile)
             void* args[] = {(void*)&A};
             if (c->kev0) HIPCHK(hipExtModuleLaunchKernel(c->upfn, grid.x * 1024u, 1, 1, 1024, 1, 1, smem, c->stream, args, nullptr, c->kev0, c->kev1, 0));
             else HIPCHK(hipModuleLaunchKernel(c->upfn, grid.x, 1, 1, 1024, 1, 1, (unsigned)smem, c->stream, args, nullptr));
-        } else if (c->kev0) hipExtLaunchKernelGGL(k_chain_persist_gen, grid, block, smem, c->stream, c->kev0, c->kev1, 0, A);
-        else hipLaunchKernelGGL(k_chain_persist_gen, grid, block, smem, c->stream, A);
+        } else launch(c, k_chain_persist_gen, grid, block, smem, A);
     }
     c->cur ^= 1;
     ++c->persist_launches;
@@ -1417,10 +1401,11 @@ void enqueue_iterations(Ctx* c, int n_iters) {
         if (c->unresolved && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w) && !plan_ahead_covers(c, t)) resolve_now(c);
         // ... or if this chain kernel cannot walk (a user objective's launches): the resolution was only put off in case the persistent
         // kernel came next (defer_resolve)
-        if (c->unresolved && c->defer_resolve && !c->inline_walk) resolve_now(c);
+        if (c->unresolved && c->F.defer_resolve && !c->F.inline_walk) resolve_now(c);
         ensure_windows(c, t);
         const int flags = (c->prev_open ? F_CLOSE_PREV : 0) | (c->pending ? F_HAS_PENDING : 0) | (c->unresolved ? F_WALK_INLINE : 0);
-        const bool kscoped = c->profiling == 2 && c->lvl_exchange && c->lvl_wg == 1024;
+        // (populations of the level walk: the chain kernel and the stand-alone resolution take the profiling events themselves)
+        const bool kscoped = c->profiling == 2 && c->F.plan == PLAN_LDS && c->P.Ng <= XLVL_MAX && !c->H.dataflow && c->H.lvl_wg == 1024;
         if (c->profiling && !kscoped) HIPCHK(hipEventRecord(c->pev[4 * slot], c->stream));
         if (kscoped) { c->kev0 = c->pev[4 * slot]; c->kev1 = c->pev[4 * slot + 1]; }
         launch_chain_iter(c, t, flags);
@@ -1431,14 +1416,14 @@ void enqueue_iterations(Ctx* c, int n_iters) {
         if (c->profiling) c->pev_exch[slot] = 0;
         c->unresolved = false;
         if (exchange_active(c, t)) {
-            const bool cone_next = c->cone_big && !c->nan_values && !c->ext_rec_in && !c->ext_rec_out && !c->ext_vals_out && !c->rec_external &&
+            const bool cone_next = c->F.cone_big && !c->nan_values && !c->ext_rec_in && !c->ext_rec_out && !c->ext_vals_out && !c->rec_external &&
                                    t >= c->plan_t0 && t < c->plan_t0 + c->plan_w && c->cone_big_ok[(size_t)(t - c->plan_t0)] != 0u;
-            if (cone_next || (c->inline_walk && !(c->gen_keys && (c->deep_plan || c->nan_values))) ||
-                (c->defer_resolve && c->persist_on && !c->persist_broken && !c->in_repair && !c->nan_values)) {   // (the key form has no second walk to fall back to)
+            if (cone_next || (c->F.inline_walk && !(c->F.gen_keys && (c->deep_plan || c->nan_values))) ||
+                (c->F.defer_resolve && c->persist_on && !c->persist_broken && !c->in_repair && !c->nan_values)) {   // (the key form has no second walk to fall back to)
                 c->unresolved = true;   // resolved in the prologue of the next chain kernel (or by resolve_now)
             } else {
                 if (kscoped) { c->kev0 = c->pev[4 * slot + 2]; c->kev1 = c->pev[4 * slot + 3]; c->pev_exch[slot] = 1; }
-                launch_resolve(c, t, (c->lvl_exchange || c->lds_exchange || c->key_exchange) ? nullptr : c->rec[c->cur]);
+                launch_resolve(c, t, (c->F.plan == PLAN_LDS || c->F.xk == XK_ROWS || c->F.xk == XK_KEY) ? nullptr : c->rec[c->cur]);
                 c->kev0 = c->kev1 = nullptr;
             }
             c->pending = true;
@@ -1567,7 +1552,7 @@ void p2p_enqueue(Ctx* c, int n_iters) {
                     launch_resolve_rows_window(c, t - 1);
                     c->kev0 = c->kev1 = nullptr;
 #ifdef SMM_TEST_HOOKS
-                    if (SMM_HOOK("SMMHIP_ROWS_WIN_CHECK")) {   // the same exchange through the unpacked values and the plain kernels
+                    if (c->H.rows_win_check) {   // the same exchange through the unpacked values and the plain kernels
                         std::vector<unsigned long long> a((size_t)P.Ng), b((size_t)P.Ng);
                         HIPCHK(hipStreamSynchronize(c->stream));
                         HIPCHK(hipMemcpy(a.data(), P.xres, a.size() * 8, hipMemcpyDeviceToHost));
@@ -1594,7 +1579,7 @@ void p2p_enqueue(Ctx* c, int n_iters) {
         } else {
             if (c->pending_ext) {   // exchangeMoves! of iteration t-1 (before its plan window can move on)
                 if (c->p2p_unwaited) launch_p2p_wait(c);
-                if (prof && c->lean_resolve) { c->kev0 = c->pev[4 * slot + 2]; c->kev1 = c->pev[4 * slot + 3]; c->pev_exch[slot] = 1; }
+                if (prof && c->F.xk == XK_LEAN) { c->kev0 = c->pev[4 * slot + 2]; c->kev1 = c->pev[4 * slot + 3]; c->pev_exch[slot] = 1; }
                 launch_resolve_window(c, t - 1);
                 c->kev0 = c->kev1 = nullptr;
                 flags |= F_HAS_PENDING;
@@ -1619,6 +1604,293 @@ void p2p_enqueue(Ctx* c, int n_iters) {
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     HIPCHK(hipGetLastError());
     if (c->profiling == 2) c->pev_iters = slot;
+}
+
+// ---- the forms of a context (smm_ctx_create) ----
+// what the device says about a context's forms: its compute units, and the resident workgroups per CU of the one persistent kernel
+// that is the candidate (-1: not asked yet — select_forms then names the candidate; 0: it is not available, its user kernel did not compile)
+struct DeviceFacts { int n_cus = 256; int per_cu = -1; };
+
+// Every form a context runs, from the problem (c->P, c->obj, the user objective's lanes, the injected tables), the hooks and the device.
+// Decides and allocates nothing.  The order of preference between the persistent forms: gen -> gen_user -> gen_small / user -> loc /
+// shard -> tile, each only where none before it was taken.
+Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
+    const KParams& P = c->P;
+    const int np = P.np, nm = P.nm, ns = P.ns, N = P.N, Ng = P.Ng, K = P.plan_K, n_cus = dev.n_cus;
+    const bool user_obj = c->obj == SMM_OBJ_USER, minus = P.dist_fun == SMM_DIST_MINUS, chol = P.chol_L != nullptr;
+    const bool mi0 = P.mi_uniform && P.mi_value == 0.0;   // one threshold 0 for all chains
+    Forms F;
+    // the level plan in LDS, or in global memory
+    bool lds = Ng > 1 && Ng <= XLDS_MAX && K >= 1 && K <= Ng && !H.any_exchange;
+    bool lvl = lds && Ng <= XLVL_MAX && !H.dataflow;
+    bool lvl_soa = lds && !lvl && !H.dataflow;
+    // (... and a SHARD whose population is past what the lean plan's 16-byte walk holds in LDS — one min_improve > 0 for all chains of
+    // 7400 < N_global <= 8192, e.g. 2 x 4096 with the reference's default threshold —: the global-memory plan lists its tiles' cones,
+    // locally numbered, so that the shard can still take the persistent form)
+    const bool shard_wide_big = N < Ng && lds && P.mi_uniform && P.mi_value != 0.0 && !(P.mi_value < 0.0) && minus &&
+                                resolve_lean_bytes(Ng, K, true) > (size_t)160 * 1024;
+    const bool big = Ng > 1 && Ng <= 65535 && K >= 1 && K <= Ng && !H.any_exchange && (H.big_exchange || shard_wide_big || !lds);
+    if (big) lds = lvl = lvl_soa = false;
+    const bool key = big && Ng <= XKEY_MAX && K <= XKEY_MAX && !H.key_exchange_off && minus;   // (the keys order value_i - value_j)
+    F.plan = big ? PLAN_BIG : lds ? PLAN_LDS : PLAN_NONE;
+    // inline exchange walk: single shard, level plan available, and two tiles must still share a CU's 160 KB LDS
+    const int tile_ct = is_sim(c->obj) ? F.ct : (c->obj == SMM_OBJ_DENSE ? 16 : 8);
+    const size_t tile_b = (tile_smem_base(c, tile_ct) + 15) & ~(size_t)15;
+    F.norm_fast = is_sim(c->obj) && np == nm && np <= 4 && P.batch_size == np && P.dbg == 0 && !chol && !H.norm_fast_off;
+    // more tiles than CUs: the walk-free kernel on half-size workgroups, two to a CU (k_chain_iter_norm_narrow)
+    F.norm_narrow = F.norm_fast && ((N + NORM_CT - 1) / NORM_CT > n_cus || H.norm_narrow == 1) && H.norm_narrow != 0;
+    // k_chain_iter_norm: pair list NOT overlaid; room for either walk (16-byte slots, 4-byte slots + value table)
+    const bool wide_form = P.mi_uniform && P.mi_value != 0.0 && !(P.mi_value < 0.0);   // (the lean walk on 16-byte slots, below)
+    const size_t walk_b = std::max(walk_slot_bytes(Ng) + (((size_t)K * 4 + 15) & ~(size_t)15),
+                                   ((wide_form ? lean_wide_bytes(Ng, K) : lean_walk_bytes(Ng, K)) + 15) & ~(size_t)15);
+    F.inline_walk = !H.inline_walk_off && lvl && N == Ng && !user_obj &&
+                    (!F.norm_fast || minus) &&   // (k_chain_iter_norm's walks are for `-`)
+                    (F.norm_fast ? walk_b + norm_tile_doubles(np) * 8 <= (size_t)160 * 1024
+                                 : walk_slot_bytes(Ng) + std::max(tile_b, (size_t)K * 4) <= (size_t)80 * 1024);
+    F.tile_off = F.inline_walk ? (int)((F.norm_fast ? walk_b : walk_slot_bytes(Ng)) / sizeof(double)) : 0;
+    // (the lean plan: the same conditions as below)
+    const bool lean_plan = P.mi_uniform && !(P.mi_value < 0.0) && minus && K <= XLDS_MAX && !H.key_walk_off &&
+                           (P.mi_value == 0.0 || resolve_lean_bytes(Ng, K, true) <= (size_t)160 * 1024);
+    // two tiles per workgroup share one walk (the 2p/2m-style simulation tile of 8 chains only) — worth it only when two tiles would
+    // share a CU anyway (more tiles than CUs)
+    F.tpw = (F.inline_walk && !F.norm_fast && (is_sim(c->obj) ? F.ct == 8 : c->obj != SMM_OBJ_DENSE) && ((N + 7) / 8 > n_cus || H.tpw == 2) &&
+             H.tpw != 1 && walk_slot_bytes(Ng) + std::max(2 * tile_b, (size_t)K * 4) <= (size_t)160 * 1024) ? 2 : 1;
+    // k_chain_iter on the lean walk (16-byte slots, padded pair list): where its somewhat larger LDS keeps the same budget
+    F.gen_lean = F.inline_walk && !F.norm_fast && lean_plan &&
+                 tile_lean_slot_bytes(Ng) + std::max((size_t)F.tpw * tile_b, (size_t)lean_walk_Kp(K) * 4) <= (size_t)(F.tpw == 2 ? 160 : 80) * 1024;
+    if (F.gen_lean) F.tile_off = (int)(tile_lean_slot_bytes(Ng) / sizeof(double));
+    // single shards of 4096 < N <= 8192 chains without a simulation (banana, BASELINE config 4): the key walk inline, two
+    // 16-chain tiles per workgroup of 1024 lanes (256 workgroups at 8192 chains: one per CU, one launch per iteration)
+    const size_t tile16 = (tile_smem_base(c, 16) + 15) & ~(size_t)15;
+    const size_t slots = (size_t)(((Ng + 3) & ~3) + 4) * 8;
+    F.gen_keys = !F.inline_walk && !H.inline_walk_off && obj_kind(c->obj) == 0 && !user_obj && N == Ng && Ng > XLVL_MAX &&
+                 Ng <= XLDS_MAX && K <= XLDS_MAX && lds && mi0 && minus && !H.key_walk_off &&
+                 slots + std::max(2 * tile16, (size_t)lean_walk_Kp(K) * 4) <= (size_t)160 * 1024;
+    if (F.gen_keys) { F.inline_walk = true; F.tpw = 2; F.tile_off = (int)(slots / sizeof(double)); }
+    // the dense objective (BASELINE config 5): its tile fills a CU's LDS (143 KB at 50 parameters / 50 moments), so the key
+    // walk's slots and lists lie UNDER the tile's blocks — the walk is over before anything of the tile is written
+    F.dense_keys = !F.inline_walk && !H.inline_walk_off && !H.dense_keys_off && c->obj == SMM_OBJ_DENSE && N == Ng &&
+                   Ng >= 2 && Ng <= XLVL_MAX && K <= XLVL_MAX && lds && mi0 && minus && !H.key_walk_off && lean_walk_unit(Ng) == 8 &&
+                   std::max(tile16, slots + std::max((size_t)CONE_LEVELS * 64 * 4, (size_t)lean_walk_Kp(K) * 4)) <= (size_t)160 * 1024;
+    if (F.dense_keys) { F.gen_keys = true; F.inline_walk = true; F.tpw = 1; F.tile_off = 0; }
+
+    // the candidates for the persistent chain kernel and the cone tables behind the plan
+    // the workgroups' cones of the inline key walk (smm_cone.hpp): where k_chain_iter walks 8192 chains' keys in every workgroup
+    const bool want_cone = F.gen_keys && !H.no_cone && (F.dense_keys ? (N % 16 == 0 && N / 16 <= 256) : (F.tpw == 2 && N % 32 == 0 && N / 32 <= 256));
+    const int cone_ct = F.dense_keys ? 16 : 32;
+    const bool gen_ok = np <= PG_MAXP && nm <= PG_MAXP && P.batch_size == np && !chol && N == Ng && !c->deep_plan && P.dbg == 0 && !H.persist_off;
+    const bool gen_fits = persist_gen_smem_bytes(Ng, np, P.RW, P.HW) <= (size_t)160 * 1024;
+    // k_chain_persist_gen (smm_chain_persist_gen.hpp), objectives without a simulation: where k_chain_iter walks its workgroups'
+    // cones inline (4096 < N <= 8192 in whole workgroups of 32 chains, one per CU), one proposal batch, isotropic proposals
+    const bool want_gen = want_cone && !F.dense_keys && c->obj == SMM_OBJ_BANANA && gen_ok && N / PG_CT <= n_cus && gen_fits;
+    // ... and for the smaller populations of the same objective (up to 4096 chains in whole groups of 32: VERDICT r4 "banana at 2048
+    // chains takes the per-iteration path"): the same kernel — the cones are listed behind the lean plan whether or not the
+    // per-iteration kernel walks them
+    const bool gen_small_ok = gen_ok && N % PG_CT == 0 && N / PG_CT >= 1 && N / PG_CT <= n_cus && lds && mi0 && minus && K <= XLDS_MAX;
+    const bool want_gen_small = !want_cone && c->obj == SMM_OBJ_BANANA && F.inline_walk && gen_small_ok && gen_fits;
+    // ... and a USER objective (one thread per evaluation) in the same loop: the kernel compiled with the user's source inside
+    // (user_persist_compile)
+    const bool want_user = user_obj && c->u_lanes == 0 && gen_small_ok &&
+                           persist_gen_smem_bytes(Ng, np, P.RW, P.HW) + persist_gen_user_bytes() <= (size_t)160 * 1024;
+    // ... and on LOCALLY NUMBERED cones (smm_chain_persist_loc.hpp): the same objective with one threshold >= 0 (or NaN: nothing
+    // ever swaps) for all chains — min_improve > 0 is the reference's default (AlgoBGP.jl:522) —, whatever the population's size
+    // does to the tile's LDS
+    const bool mi_ok = (P.mi_uniform && !(P.mi_value < 0.0)) || P.mi_pct;   // one threshold >= 0 (or NaN) for all chains, or one per chain, each >= 0 (or NaN)
+    const bool loc_ok = F.norm_fast && np <= 2 && ns <= WG * PR_ZR && minus && !c->deep_plan && P.dbg == 0 && !H.persist_off && !H.persist_loc_off;
+    const bool want_loc = loc_ok && N == Ng && Ng >= 2 && F.inline_walk && mi_ok && K <= XLDS_MAX && Ng <= XLDS_MAX && (N + NORM_CT - 1) / NORM_CT <= n_cus;
+    // ... and as a shard of a sharded run (one process per GPU: smm_bgp_p2p_step): the same kernel, the ring in the ranks' windows
+    const bool want_sh = loc_ok && N < Ng && N > 0 && Ng % N == 0 && P.offset % N == 0 && Ng / N <= P2P_MAXG && N % NORM_CT == 0 &&
+                         P.mi_uniform && !(P.mi_value < 0.0) && N / NORM_CT <= n_cus &&
+                         (lds ? K <= XLDS_MAX : (big && Ng <= 32768 && K <= 65535 && (size_t)Ng * 4 <= (size_t)160 * 1024));
+    // ... and for the objectives a whole tile evaluates (smm_chain_persist_tile.hpp): objfunc_norm with any number of parameters — the
+    // reference's larger examples have 6 and 18, Examples.jl:210-230, 232-319 — and the dense simulation (BASELINE config 5); one
+    // threshold >= 0 (or NaN) for all chains, isotropic proposals, one 16-chain tile per workgroup, all of them resident
+    const int tile_kind = obj_kind(c->obj);
+    // ... and a USER objective in its map-reduce form (smm_register_user_objective_lanes) whose lanes are a whole share of the tile's 512
+    const bool user_tile = user_obj && c->u_lanes > 0 && c->u_lanes <= WG && WG % c->u_lanes == 0 && PT_CT % (WG / c->u_lanes) == 0 && !P.mi_pct;   // (compiled for ONE threshold)
+    const bool want_tile = (tile_kind == 1 || tile_kind == 2 || user_tile) && !(F.norm_fast && np <= 2 && ns <= WG * PR_ZR) && N == Ng && Ng >= 2 && lds &&
+                           mi_ok && minus && K <= XLDS_MAX && Ng <= XLDS_MAX && !c->deep_plan && !chol && P.dbg == 0 && !H.persist_off &&
+                           !H.persist_tile_off && P.RW <= PT_LPC * PT_NJ && (tile_kind != 2 || N % PT_CT == 0) && (N + PT_CT - 1) / PT_CT <= 2 * n_cus &&
+                           persist_tile_smem(c) <= (size_t)160 * 1024;
+    const size_t persist_tiles = (want_gen || want_gen_small || want_user) ? (size_t)N / PG_CT : (size_t)(N + NORM_CT - 1) / NORM_CT;
+    // large single shards of objfunc_norm (C3 on one GPU): the narrow chain kernel's tiles walk their own, locally numbered cones
+    // (smm_cone_big.hpp) instead of waiting for the one-workgroup resolution between two launches
+    const bool rows = key && mi0 && !H.key_walk_off;
+    const bool want_cone_big = big && rows && F.norm_fast && F.norm_narrow && N == Ng && N % NORM_CT == 0 && Ng <= 32768 && K <= 65535 &&
+                               P.dbg == 0 && !H.cone_big_off && (size_t)Ng * 4 <= (size_t)160 * 1024;
+
+    // look-ahead windows.  Two with budgets of their own (288 GB of HBM: a few hundred MiB of look-ahead tables are nothing), at most 256
+    // iterations each.  The plan kernels are launched with one workgroup per iteration of the window: a short window leaves
+    // the chip idle while they run — at 32768 chains k_exch_plan_big needs 1.7 ms per launch, which with the 26 iterations the
+    // former common budget of 192 MiB allowed was 63 us per iteration, more than the exchange itself (round 3, rocprofv3).
+    // (the plan's budget counts the tables of every candidate, taken or not)
+    const bool pregen = !(F.norm_fast && !P.user_ntab && !P.user_utab);   // (k_chain_iter_norm draws in the kernel)
+    const size_t rb_iter = (size_t)P.RBW * N * 8;
+    const size_t cone_iter = (size_t)(CONE_LEVELS * 64 + CONE_HDRW) * 4;   // one tile's header and sub-levels
+    const size_t plan_iter = (want_cone_big ? (size_t)(N / NORM_CT) * (cone_iter + CONE_GCAP * 2) + cone_big_scratch_words(Ng, K) * 4 : 0) + (size_t)K * 36 +
+                             (big ? BigPlanScratch::words(Ng, K) * 4 + (size_t)(XROWS_MAX + 1) * XWG * 4 : 0) +
+                             (size_t)lean_walk_Kp(K) * 4 + 1024 + (want_cone ? (size_t)(N / cone_ct) * cone_iter + 4 : 0) +
+                             ((want_loc || want_sh || want_tile) ? persist_tiles * (cone_iter + CONE_GCAP * 2) + 4 : 0) +
+                             ((want_sh && big) ? cone_big_scratch_words(Ng, K) * 4 : 0) +
+                             (want_gen ? persist_tiles * (CONE_GCAP * 2) : 0) +
+                             ((want_gen_small || want_user) ? persist_tiles * (cone_iter + CONE_GCAP * 2) + 4 : 0);
+    F.win_cap = pregen ? (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)768 << 20) / rb_iter)) : 1;
+    F.win_cap = std::min(F.win_cap, P.T);
+    F.plan_cap = (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)1536 << 20) / plan_iter));
+    F.plan_cap = std::max(1, std::min(std::min(F.plan_cap, P.T), H.plan_cap));
+
+    // the exchange: the big plan's forms
+    if (big && rows) {
+        F.rows_cap = std::min(XROWS_MAX, (K + XWG - 1) / XWG + LV_MAXLEV);
+        if (want_cone_big) { F.cone_big = true; F.plan_ahead = !H.plan_ahead_off; F.walk_slots = true; }
+    }
+    if (big && want_sh) {   // a shard of a large population: its own tiles' cones, locally numbered (smm_cone_big.hpp)
+        F.persist = PERSIST_LOC; F.persist_wide = P.mi_value != 0.0; F.persist_sh = true; F.persist_sh_big = true;
+    }
+    // ... the lean walk (smm_walk_lean.hpp) behind the LDS plan: one min_improve for every chain — 0: 8-byte slots of order keys; > 0 (or
+    // NaN: nothing ever swaps): 16-byte slots of values, as far as the 160 KB of LDS reach (~7400 chains)
+    // (thresholds by chain: the lean PLAN — padded levels on 16-byte units, the tiles' cones behind it — is made for the persistent launches; the
+    // stand-alone lean resolution and the inline lean walks, which test ONE threshold, stay off: XK_LEAN below, launch_chain_iter_norm)
+    const bool wide = P.mi_uniform && !mi0 && !(P.mi_value < 0.0) && resolve_lean_bytes(Ng, K, true) <= (size_t)160 * 1024;
+    const bool pct = P.mi_pct != 0 && (want_loc || want_tile);
+    F.lean_plan = lds && (mi0 || wide || pct) && K <= XLDS_MAX && !H.key_walk_off && minus;
+    F.lean_wide = F.lean_plan && (wide || pct);
+    if (F.lean_plan) {
+        // ... walked in the prologue of k_chain_iter_norm, or of k_chain_iter (key form)
+        if (mi0 && ((F.norm_fast && F.inline_walk && Ng <= XLVL_MAX && K <= XLVL_MAX) || F.gen_keys)) {
+            F.walk_slots = true;
+            F.cone = want_cone;
+            if (want_gen) F.persist = PERSIST_GEN;
+        }
+        const bool user_ok = want_user && mi0 && F.persist == PERSIST_NONE;
+        if ((want_gen_small || user_ok) && mi0 && F.persist == PERSIST_NONE) {
+            F.persist = PERSIST_GEN; F.persist_user = user_ok; F.defer_resolve = user_ok;
+        }
+        if ((want_loc || want_sh) && F.persist == PERSIST_NONE && F.norm_fast) {   // (k_exch_plan lists the tiles' cones behind the lean plan)
+            F.persist = PERSIST_LOC; F.persist_wide = wide || pct; F.persist_sh = want_sh;
+        }
+        // (the dense tiles of the per-iteration kernel walk the same cones: want_cone above)
+        if (want_tile && F.persist == PERSIST_NONE &&
+            (!F.cone || (cone_ct == PT_CT && (size_t)(N / cone_ct) == (size_t)(N + PT_CT - 1) / PT_CT))) {
+            F.persist = PERSIST_TILE; F.persist_wide = true;
+            F.defer_resolve = !F.inline_walk;   // (the exchange of an iteration is left to the next launch: it may be this kernel's)
+        }
+    }
+    // ... all of its tiles resident at once, or it is not taken (per_cu 0 also where a user objective's kernel did not compile)
+    if (F.persist != PERSIST_NONE && dev.per_cu >= 0) {
+        const int tiles = F.persist == PERSIST_GEN ? N / PG_CT : F.persist == PERSIST_LOC ? (N + NORM_CT - 1) / NORM_CT : (N + PT_CT - 1) / PT_CT;
+        if (F.persist != PERSIST_GEN) F.max_tiles = dev.per_cu * n_cus;
+        if (tiles > dev.per_cu * n_cus) {
+            F.persist = PERSIST_NONE;
+            F.persist_wide = F.persist_sh = F.persist_sh_big = F.persist_user = F.defer_resolve = false;
+        }
+    }
+    // the cone tables: the persistent form's (with gather lists), the local cones', or the inline key walk's
+    if (F.cone_big) { F.cone_tiles = N / NORM_CT; F.cone_ct = NORM_CT; F.cone_gather = true; }
+    else if (F.persist == PERSIST_GEN) { F.cone_tiles = N / PG_CT; F.cone_ct = PG_CT; F.cone_gather = true; }
+    else if (F.persist == PERSIST_LOC) { F.cone_tiles = (int)persist_tiles; F.cone_ct = NORM_CT; F.cone_gather = true; }
+    else if (F.persist == PERSIST_TILE) { F.cone_tiles = (N + PT_CT - 1) / PT_CT; F.cone_ct = PT_CT; F.cone_gather = true; }
+    else if (F.cone) { F.cone_tiles = N / cone_ct; F.cone_ct = cone_ct; }
+
+    // the stand-alone resolution
+    F.xk = (F.lean_plan && !pct) ? XK_LEAN : lvl ? XK_LVL : lvl_soa ? XK_LVL_SOA : lds ? XK_TICKETS   // (XK_TICKETS: test build only, SMMHIP_DATAFLOW_EXCHANGE)
+         : key ? (rows ? XK_ROWS : XK_KEY) : big ? XK_LVL_BIG : XK_ANY;
+    return F;
+}
+
+// the persistent kernel that is the candidate of F, asked how many of its workgroups a CU holds — with its dynamic LDS set first, as the
+// launches want it; a user objective's kernel is compiled (once per registered objective) and loaded here.  0: not available
+int persist_occupancy(Ctx* c, const Forms& F, int objective_id) {
+    const KParams& P = c->P;
+    int per_cu = 0;
+    if (F.persist == PERSIST_GEN && F.persist_user) {   // the kernel with the user's objective inside (user_persist_compile)
+        {
+            std::lock_guard<std::mutex> lock(g_user_mutex);
+            UserObjective& u = g_user_objectives[objective_id - SMM_OBJ_USER_BASE];
+            if (!user_persist_compile(u)) {
+                if (getenv("SMMHIP_VERBOSE")) fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n", u.persist_log.c_str());
+                return 0;
+            }
+            HIPCHK(hipModuleLoadData(&c->upmod, u.persist_code.data()));
+        }
+        HIPCHK(hipModuleGetFunction(&c->upfn, c->upmod, "smm_user_persist_kernel"));
+        const size_t smem = persist_gen_smem_bytes(P.Ng, P.np, P.RW, P.HW) + persist_gen_user_bytes();
+        (void)hipFuncSetAttribute((const void*)c->upfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);   // (a module's function: where the runtime takes it)
+        (void)hipGetLastError();
+        HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->upfn, 1024, smem));
+    } else if (F.persist == PERSIST_GEN) {
+        const size_t smem = persist_gen_smem_bytes(P.Ng, P.np, P.RW, P.HW);
+        HIPCHK(hipFuncSetAttribute((const void*)k_chain_persist_gen, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_chain_persist_gen, 1024, smem));
+    } else if (F.persist == PERSIST_LOC) {
+        const size_t smem = persist_loc_smem_bytes(P.np);
+        const void* fn = persist_loc_fn(P.np, F.persist_wide, F.persist_sh, P.mi_pct != 0);
+        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NORM_WG, smem));
+    } else if (F.persist == PERSIST_TILE) {
+        const size_t smem = persist_tile_smem(c);
+        if (c->obj == SMM_OBJ_USER) {   // the tile kernel with the user's map-reduce objective inside (user_tile_compile)
+            {
+                std::lock_guard<std::mutex> lock(g_user_mutex);
+                UserObjective& u = g_user_objectives[objective_id - SMM_OBJ_USER_BASE];
+                if (!user_tile_compile(u)) {
+                    if (getenv("SMMHIP_VERBOSE")) fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n", u.tile_log.c_str());
+                    return 0;
+                }
+                HIPCHK(hipModuleLoadData(&c->utmod, u.tile_code.data()));
+            }
+            HIPCHK(hipModuleGetFunction(&c->utfn, c->utmod, "smm_user_persist_tile_kernel"));
+            (void)hipFuncSetAttribute((const void*)c->utfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);   // (a module's function: not every runtime takes it this way; the launch asks for what it needs)
+            (void)hipGetLastError();
+            HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->utfn, WG, smem));
+        } else {
+            const int kind = obj_kind(c->obj);
+            const void* fn = P.mi_pct ? (kind == 2 ? (const void*)k_chain_persist_tile<2, true> : (const void*)k_chain_persist_tile<1, true>)
+                                      : (kind == 2 ? (const void*)k_chain_persist_tile<2> : (const void*)k_chain_persist_tile<1>);
+            HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, WG, smem));
+        }
+    }
+    return per_cu;
+}
+
+// one set of cone tables for the plan window (KParams or a PlanSet): tiles x CONE_HDRW header words, tiles x the sub-levels' pairs and,
+// with_gather, tiles x the gather lists, per iteration; cone_ok zeroed
+template <class Tables>
+void alloc_cones(Ctx* c, Tables& P, size_t tiles, bool with_gather) {
+    const size_t W = (size_t)c->F.plan_cap;
+    P.cone_ok = dalloc<uint32_t>(c, W);
+    P.cone_hdr = dalloc<uint32_t>(c, W * tiles * CONE_HDRW);
+    P.cone_pairs = dalloc<uint32_t>(c, W * tiles * (CONE_LEVELS * 64) + 1024);   // (+: whole 1 KB pieces are fetched)
+    P.cone_gather = with_gather ? dalloc<uint16_t>(c, W * tiles * CONE_GCAP + 512) : nullptr;
+    HIPCHK(hipMemset((void*)P.cone_ok, 0, W * 4));
+}
+
+// the persistent form's ring — k_chain_persist_gen's in KParams, the others' in one window (pr_win_layout; a shard's lives in its p2p
+// window: smm_bgp_p2p_init) — and the state persist_repair rolls back to (after the history's fill: hist_fill is a row of it)
+void alloc_persist(Ctx* c) {
+    KParams& P = c->P;
+    const size_t N = P.N;
+    if (c->F.persist == PERSIST_GEN) {
+        P.pr_slot = (uint2*)dalloc<unsigned char>(c, persist_ring_slot_bytes(P.Ng));
+        P.pr_rec = (uint4*)dalloc<unsigned char>(c, persist_ring_rec_bytes(P.Ng, P.RW));
+        P.pr_progress = dalloc<uint32_t>(c, N / PG_CT);
+        P.pr_ctl = dalloc<uint32_t>(c, 4);
+        HIPCHK(hipMemset(P.pr_slot, 0, persist_ring_slot_bytes(P.Ng)));
+        HIPCHK(hipMemset(P.pr_rec, 0, persist_ring_rec_bytes(P.Ng, P.RW)));
+        HIPCHK(hipMemset(P.pr_progress, 0, N / PG_CT * 4));
+        HIPCHK(hipMemset(P.pr_ctl, 0, 16));
+    } else if (!c->F.persist_sh) {
+        const PrWin WL = pr_win_layout(P.Ng, P.RW, 1, c->F.cone_tiles);
+        c->prw = dalloc<unsigned char>(c, WL.total);
+        HIPCHK(hipMemset(c->prw, 0, WL.total));
+    }
+    c->snap_cs = dalloc<double>(c, N * CSW);
+    c->snap_rec = dalloc<double>(c, N * P.RW);
+    for (int b = 0; b < 2; ++b) { c->snap_vals[b] = dalloc<double>(c, N + 4); c->snap_slot8[b] = dalloc<uint2>(c, N + 4 + 128); }
+    c->snap_xres = dalloc<unsigned long long>(c, P.Ng);
+    c->hist_fill = dalloc<double>(c, N * P.HW);
+    HIPCHK(hipMemcpy(c->hist_fill, P.hrec, N * P.HW * 8, hipMemcpyDeviceToDevice));   // (a row of the constructor's fill)
 }
 
 }  // namespace
@@ -1775,6 +2047,7 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
     if (opts->device < 0 || opts->device >= ndev) return fail(nullptr, SMM_ERR_INVALID_ARG, "bad device ordinal");
     Ctx* c = new Ctx();
     try {
+        c->H = read_hooks();
         c->device = opts->device;
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -1785,18 +2058,13 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
         c->exchange_from = opts->exchange_from_iter;
         P.exch_from = opts->exchange_from_iter;
         {
-            const char* e = SMM_HOOK("SMMHIP_ANY_EXCHANGE");  // test hook: force the any-size resolution kernel
-            c->force_any_exchange = e && e[0] == '1';
             const char* d = getenv("SMMHIP_DBG");
             P.dbg = d ? atoi(d) : 0;
-            const char* sa = SMM_HOOK("SMMHIP_SCOUT_AFTER");   // test hook: rounds before the scouting form of mysample's late tries
-            P.scout_after = sa ? atoi(sa) : SMM_SCOUT_AFTER;
-            const char* sg = SMM_HOOK("SMMHIP_SCOUT_GL");
-            P.scout_gl = (sg && atoi(sg) == 8) ? 8 : 16;
+            P.scout_after = c->H.scout_after;
+            P.scout_gl = c->H.scout_gl;
             const char* tsv = getenv("SMMHIP_TS");
             if (tsv && (tsv[0] == '1' || tsv[0] == '2')) P.ts = dalloc<unsigned long long>(c, (size_t)8 * 65536);
             P.ts_levels = tsv && tsv[0] == '2';   // also a stamp per level of the inline walk (the stamps stretch the levels: not with '1')
-            c->ct = 8;   // chains per simulation tile (4 and 16 were measured and rejected: more shock traffic / spills)
         }
         P.np = np; P.nm = nm; P.ns = ns; P.obj = c->obj;
         P.init = dupload(c, prob->init, np); P.lb = dupload(c, prob->lb, np); P.ub = dupload(c, prob->ub, np);
@@ -1926,365 +2194,73 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
         P.RBW = even_up(1 + P.rb_tries * np);
         const int K = exchange_K(c);
         P.plan_K = K;
-        c->lds_exchange = Ng > 1 && Ng <= XLDS_MAX && K >= 1 && K <= Ng && !c->force_any_exchange;
-        {
-            const char* e = SMM_HOOK("SMMHIP_DATAFLOW_EXCHANGE");  // test hook: force the ticket (data-flow) resolution kernel
-            c->lvl_exchange = c->lds_exchange && Ng <= XLVL_MAX && !(e && e[0] == '1');
-            c->lvl_soa_exchange = c->lds_exchange && !c->lvl_exchange && !(e && e[0] == '1');
-            const char* lw = SMM_HOOK("SMMHIP_LVL_WG");  // tuning hook
-            if (lw) c->lvl_wg = atoi(lw);
-            const char* be = SMM_HOOK("SMMHIP_BIG_EXCHANGE");  // test hook: force the global-memory level kernels
-            // (... and a SHARD whose population is past what the lean plan's 16-byte walk holds in LDS — one min_improve > 0 for all chains of
-            // 7400 < N_global <= 8192, e.g. 2 x 4096 with the reference's default threshold —: the global-memory plan lists its tiles' cones,
-            // locally numbered, so that the shard can still take the persistent form)
-            const bool shard_wide_big = N < Ng && c->lds_exchange && P.mi_uniform && P.mi_value != 0.0 && !(P.mi_value < 0.0) && opts->dist_fun == SMM_DIST_MINUS &&
-                                        resolve_lean_bytes(Ng, K, true) > (size_t)160 * 1024;
-            const bool force_big = (be && be[0] == '1') || shard_wide_big;
-            c->big_exchange = Ng > 1 && Ng <= 65535 && K >= 1 && K <= Ng && !c->force_any_exchange && (force_big || !c->lds_exchange);
-            if (c->big_exchange) { c->lds_exchange = false; c->lvl_exchange = false; c->lvl_soa_exchange = false; }
-            const char* ke = SMM_HOOK("SMMHIP_KEY_EXCHANGE");   // test hook: "0" keeps the global-memory walk
-            c->key_exchange = c->big_exchange && Ng <= XKEY_MAX && K <= XKEY_MAX && !(ke && ke[0] == '0') && opts->dist_fun == SMM_DIST_MINUS;   // (the keys order value_i - value_j)
-            // inline exchange walk: single shard, level plan available, and two tiles must still share a CU's 160 KB LDS
-            const char* iw = SMM_HOOK("SMMHIP_INLINE_WALK");
-            const int tile_ct = is_sim(c->obj) ? c->ct : (c->obj == SMM_OBJ_DENSE ? 16 : 8);
-            const size_t tile_b = (tile_smem_base(c, tile_ct) + 15) & ~(size_t)15;
-            const char* nf = SMM_HOOK("SMMHIP_NORM_FAST");   // test hook: "0" keeps the general kernel for objfunc_norm
-            c->norm_fast = is_sim(c->obj) && np == nm && np <= 4 && opts->batch_size == np && P.dbg == 0 && !opts->chol_L && !(nf && nf[0] == '0');
-            {   // more tiles than CUs: the walk-free kernel on half-size workgroups, two to a CU (k_chain_iter_norm_narrow)
-                int cus = 256;
-                (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-                const char* nn = SMM_HOOK("SMMHIP_NORM_NARROW");   // test hook: "0" never, "1" always
-                c->norm_narrow = c->norm_fast && ((N + NORM_CT - 1) / NORM_CT > cus || (nn && nn[0] == '1')) && !(nn && nn[0] == '0');
-            }
-            // k_chain_iter_norm: pair list NOT overlaid; room for either walk (16-byte slots, 4-byte slots + value table)
-            const bool wide_form = P.mi_uniform && P.mi_value != 0.0 && !(P.mi_value < 0.0);   // (the lean walk on 16-byte slots, below)
-            const size_t walk_b = std::max(walk_slot_bytes(Ng) + (((size_t)K * 4 + 15) & ~(size_t)15),
-                                           ((wide_form ? lean_wide_bytes(Ng, K) : lean_walk_bytes(Ng, K)) + 15) & ~(size_t)15);
-            c->inline_walk = !(iw && iw[0] == '0') && c->lvl_exchange && N == Ng && c->obj != SMM_OBJ_USER &&
-                             (!c->norm_fast || opts->dist_fun == SMM_DIST_MINUS) &&   // (k_chain_iter_norm's walks are for `-`)
-                             (c->norm_fast ? walk_b + norm_tile_doubles(np) * 8 <= (size_t)160 * 1024
-                                           : walk_slot_bytes(Ng) + std::max(tile_b, (size_t)K * 4) <= (size_t)80 * 1024);
-            P.tile_off = c->inline_walk ? (int)((c->norm_fast ? walk_b : walk_slot_bytes(Ng)) / sizeof(double)) : 0;
-            // (the lean plan: the same conditions as further down, where its tables are allocated)
-            const char* kw0 = SMM_HOOK("SMMHIP_KEY_WALK");
-            const bool lean_plan = P.mi_uniform && !(P.mi_value < 0.0) && opts->dist_fun == SMM_DIST_MINUS && K <= XLDS_MAX && !(kw0 && kw0[0] == '0') &&
-                                   (P.mi_value == 0.0 || resolve_lean_bytes(Ng, K, true) <= (size_t)160 * 1024);
-            // two tiles per workgroup share one walk (the 2p/2m-style simulation tile of 8 chains only)
-            const char* tp = SMM_HOOK("SMMHIP_TPW");
-            int n_cu = 256;
-            (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-            // ... worth it only when two tiles would share a CU anyway (more tiles than CUs)
-            const bool force2 = tp && tp[0] == '2';   // test hook: two tiles per workgroup at any size
-            c->tpw = (c->inline_walk && !c->norm_fast && (is_sim(c->obj) ? c->ct == 8 : c->obj != SMM_OBJ_DENSE) && ((N + 7) / 8 > n_cu || force2) &&
-                      !(tp && tp[0] == '1') &&
-                      walk_slot_bytes(Ng) + std::max(2 * tile_b, (size_t)K * 4) <= (size_t)160 * 1024) ? 2 : 1;
-            // k_chain_iter on the lean walk (16-byte slots, padded pair list): where its somewhat larger LDS keeps the same budget
-            c->gen_lean = c->inline_walk && !c->norm_fast && lean_plan &&
-                          tile_lean_slot_bytes(Ng) + std::max((size_t)c->tpw * tile_b, (size_t)lean_walk_Kp(K) * 4) <= (size_t)(c->tpw == 2 ? 160 : 80) * 1024;
-            if (c->gen_lean) { P.tile_off = (int)(tile_lean_slot_bytes(Ng) / sizeof(double)); P.gen_lean = 1; }
-            // single shards of 4096 < N <= 8192 chains without a simulation (banana, BASELINE config 4): the key walk inline, two
-            // 16-chain tiles per workgroup of 1024 lanes (256 workgroups at 8192 chains: one per CU, one launch per iteration)
-            {
-                const size_t tile16 = (tile_smem_base(c, 16) + 15) & ~(size_t)15;
-                const size_t slots = (size_t)(((Ng + 3) & ~3) + 4) * 8;
-                c->gen_keys = !c->inline_walk && !(iw && iw[0] == '0') && obj_kind(c->obj) == 0 && c->obj != SMM_OBJ_USER && N == Ng && Ng > XLVL_MAX &&
-                              Ng <= XLDS_MAX && K <= XLDS_MAX && c->lds_exchange && P.mi_uniform && P.mi_value == 0.0 && opts->dist_fun == SMM_DIST_MINUS &&
-                              !(kw0 && kw0[0] == '0') && slots + std::max(2 * tile16, (size_t)lean_walk_Kp(K) * 4) <= (size_t)160 * 1024;
-                if (c->gen_keys) { c->inline_walk = true; c->tpw = 2; P.gen_lean = 2; P.tile_off = (int)(slots / sizeof(double)); }
-                // the dense objective (BASELINE config 5): its tile fills a CU's LDS (143 KB at 50 parameters / 50 moments), so the key
-                // walk's slots and lists lie UNDER the tile's blocks — the walk is over before anything of the tile is written
-                const char* dk = SMM_HOOK("SMMHIP_DENSE_KEYS");   // test hook: "0" keeps the stand-alone resolution
-                c->dense_keys = !c->inline_walk && !c->gen_keys && !(iw && iw[0] == '0') && !(dk && dk[0] == '0') && c->obj == SMM_OBJ_DENSE && N == Ng &&
-                                Ng >= 2 && Ng <= XLVL_MAX && K <= XLVL_MAX && c->lds_exchange && P.mi_uniform && P.mi_value == 0.0 &&
-                                opts->dist_fun == SMM_DIST_MINUS && !(kw0 && kw0[0] == '0') && lean_walk_unit(Ng) == 8 &&
-                                std::max(tile16, slots + std::max((size_t)CONE_LEVELS * 64 * 4, (size_t)lean_walk_Kp(K) * 4)) <= (size_t)160 * 1024;
-                if (c->dense_keys) { c->gen_keys = true; c->inline_walk = true; c->tpw = 1; P.gen_lean = 2; P.tile_off = 0; }
-                // (its slots are written by the accept step, like the headline kernel's: allocated further down, with the lean plan)
-            }
+        // the forms: the device's compute units, then the candidate persistent kernel's occupancy, then the choice
+        DeviceFacts dev;
+        (void)hipDeviceGetAttribute(&dev.n_cus, hipDeviceAttributeMultiprocessorCount, c->device);
+        c->F = select_forms(c, c->H, dev);
+        if (c->F.persist != PERSIST_NONE) {
+            dev.per_cu = persist_occupancy(c, c->F, prob->objective_id);
+            c->F = select_forms(c, c->H, dev);
         }
-        {   // look-ahead window: as many iterations as ~192 MiB of tables allow, at most 256
-            const size_t per_iter = (size_t)P.RBW * N * 8 + (size_t)K * 36 + (c->big_exchange ? BigPlanScratch::words(Ng, K) * 4 : 0);
-            (void)per_iter;
-            // Two windows with budgets of their own (288 GB of HBM: a few hundred MiB of look-ahead tables are nothing), at most 256
-            // iterations each.  The plan kernels are launched with one workgroup per iteration of the window: a short window leaves
-            // the chip idle while they run — at 32768 chains k_exch_plan_big needs 1.7 ms per launch, which with the 26 iterations the
-            // former common budget of 192 MiB allowed was 63 us per iteration, more than the exchange itself (round 3, rocprofv3).
-            const bool pregen = !(c->norm_fast && !(tab && tab->prop_normals) && !(tab && tab->probs_acc));   // (k_chain_iter_norm draws in the kernel)
-            const size_t rb_iter = (size_t)P.RBW * N * 8;
-            // the workgroups' cones of the inline key walk (smm_cone.hpp): where k_chain_iter walks 8192 chains' keys in every workgroup
-            const char* nc = SMM_HOOK("SMMHIP_NO_CONE");   // test hook: every workgroup walks the whole list
-            const bool want_cone = c->gen_keys && !(nc && nc[0] == '1') &&
-                                   (c->dense_keys ? (N % 16 == 0 && N / 16 <= 256) : (c->tpw == 2 && N % 32 == 0 && N / 32 <= 256));
-            const int cone_ct = c->dense_keys ? 16 : 32;
-            // the persistent chain kernel (smm_chain_persist.hpp): objfunc_norm with at most two moments (the lane's shocks of ONE moment
-            // stay in registers), a single shard of at most one 16-chain tile per CU, the key walk's conditions (one threshold 0, `-`),
-            // a pair list the lean plan holds
-            const char* pe = SMM_HOOK("SMMHIP_PERSIST");   // test hook: "0" never
-            int n_cus = 256;
-            (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, c->device);
-            const char* ploc = SMM_HOOK("SMMHIP_PERSIST_LOC");   // test hook: "1" the locally numbered form wherever it applies, "0" never
-            // ... and its form for objectives without a simulation (smm_chain_persist_gen.hpp): where k_chain_iter walks its workgroups'
-            // cones inline (4096 < N <= 8192 in whole workgroups of 32 chains, one per CU), one proposal batch, isotropic proposals
-            const bool want_persist_gen = want_cone && !c->dense_keys && c->obj == SMM_OBJ_BANANA && np <= PG_MAXP && nm <= PG_MAXP && opts->batch_size == np && !opts->chol_L &&
-                                          N == Ng && N / PG_CT <= n_cus && !c->deep_plan && P.dbg == 0 &&
-                                          persist_gen_smem_bytes(Ng, np, P.RW, P.HW) <= (size_t)160 * 1024 && !(pe && pe[0] == '0');
-            // ... and for the smaller populations of the same objective (up to 4096 chains in whole groups of 32: VERDICT r4 "banana at 2048
-            // chains takes the per-iteration path"): the same kernel — the cones are listed behind the lean plan whether or not the
-            // per-iteration kernel walks them
-            const bool want_persist_gen_small = !want_cone && c->obj == SMM_OBJ_BANANA && np <= PG_MAXP && nm <= PG_MAXP && opts->batch_size == np && !opts->chol_L &&
-                                                N == Ng && N % PG_CT == 0 && N / PG_CT >= 1 && N / PG_CT <= n_cus && c->inline_walk && c->lds_exchange && P.mi_uniform &&
-                                                P.mi_value == 0.0 && opts->dist_fun == SMM_DIST_MINUS && K <= XLDS_MAX && !c->deep_plan && P.dbg == 0 &&
-                                                persist_gen_smem_bytes(Ng, np, P.RW, P.HW) <= (size_t)160 * 1024 && !(pe && pe[0] == '0');
-            // ... and a USER objective (one thread per evaluation) in the same loop: the kernel is compiled with the user's source inside
-            // (user_persist_compile), on demand, further down
-            const bool want_persist_user = user_obj && c->u_lanes == 0 && np <= PG_MAXP && nm <= PG_MAXP && opts->batch_size == np && !opts->chol_L &&
-                                           N == Ng && N % PG_CT == 0 && N / PG_CT >= 1 && N / PG_CT <= n_cus && c->lds_exchange && P.mi_uniform &&
-                                           P.mi_value == 0.0 && opts->dist_fun == SMM_DIST_MINUS && K <= XLDS_MAX && !c->deep_plan && P.dbg == 0 &&
-                                           persist_gen_smem_bytes(Ng, np, P.RW, P.HW) + persist_gen_user_bytes() <= (size_t)160 * 1024 && !(pe && pe[0] == '0');
-            // ... and on LOCALLY NUMBERED cones (smm_chain_persist_loc.hpp): the same objective with one threshold >= 0 (or NaN: nothing
-            // ever swaps) for all chains — min_improve > 0 is the reference's default (AlgoBGP.jl:522) —, whatever the population's size
-            // does to the tile's LDS
-            const bool mi_ok = (P.mi_uniform && !(P.mi_value < 0.0)) || P.mi_pct;   // one threshold >= 0 (or NaN) for all chains, or one per chain, each >= 0 (or NaN)
-            const bool want_persist_loc = c->norm_fast && np <= 2 && ns <= WG * PR_ZR && N == Ng && Ng >= 2 && c->inline_walk && mi_ok &&
-                                          opts->dist_fun == SMM_DIST_MINUS && K <= XLDS_MAX && Ng <= XLDS_MAX && !c->deep_plan && (N + NORM_CT - 1) / NORM_CT <= n_cus &&
-                                          P.dbg == 0 && !(pe && pe[0] == '0') && !(ploc && ploc[0] == '0');
-            // ... and as a shard of a sharded run (one process per GPU: smm_bgp_p2p_step): the same kernel, the ring in the ranks' windows
-            const bool want_persist_sh = N < Ng && N > 0 && Ng % N == 0 && opts->chain_offset % N == 0 && Ng / N <= P2P_MAXG && N % NORM_CT == 0 && c->norm_fast && np <= 2 &&
-                                         ns <= WG * PR_ZR && P.mi_uniform && !(P.mi_value < 0.0) && opts->dist_fun == SMM_DIST_MINUS && !c->deep_plan && N / NORM_CT <= n_cus &&
-                                         P.dbg == 0 && !(pe && pe[0] == '0') && !(ploc && ploc[0] == '0') &&
-                                         (c->lds_exchange ? K <= XLDS_MAX : (c->big_exchange && Ng <= 32768 && K <= 65535 && (size_t)Ng * 4 <= (size_t)160 * 1024));
-            // ... and for the objectives a whole tile evaluates (smm_chain_persist_tile.hpp): objfunc_norm with any number of parameters — the
-            // reference's larger examples have 6 and 18, Examples.jl:210-230, 232-319 — and the dense simulation (BASELINE config 5); one
-            // threshold >= 0 (or NaN) for all chains, isotropic proposals, one 16-chain tile per workgroup, all of them resident
-            const char* ptile = SMM_HOOK("SMMHIP_PERSIST_TILE");   // test hook: "0" never
-            const int tile_kind = obj_kind(c->obj);
-            // ... and a USER objective in its map-reduce form (smm_register_user_objective_lanes) whose lanes are a whole share of the tile's 512
-            const bool user_tile = user_obj && c->u_lanes > 0 && c->u_lanes <= WG && WG % c->u_lanes == 0 && PT_CT % (WG / c->u_lanes) == 0 && !P.mi_pct;   // (compiled for ONE threshold)
-            const bool want_persist_tile = (tile_kind == 1 || tile_kind == 2 || user_tile) && !(c->norm_fast && np <= 2 && ns <= WG * PR_ZR) && N == Ng && Ng >= 2 && c->lds_exchange &&
-                                           mi_ok && opts->dist_fun == SMM_DIST_MINUS && K <= XLDS_MAX && Ng <= XLDS_MAX && !c->deep_plan &&
-                                           !opts->chol_L && P.dbg == 0 && !(pe && pe[0] == '0') && !(ptile && ptile[0] == '0') && P.RW <= PT_LPC * PT_NJ &&
-                                           (tile_kind != 2 || N % PT_CT == 0) && (N + PT_CT - 1) / PT_CT <= 2 * n_cus &&
-                                           persist_tile_smem(c) <= (size_t)160 * 1024;
-            const size_t persist_tiles = (want_persist_gen || want_persist_gen_small || want_persist_user) ? (size_t)N / PG_CT : (size_t)(N + NORM_CT - 1) / NORM_CT;
-            // large single shards of objfunc_norm (C3 on one GPU): the narrow chain kernel's tiles walk their own, locally numbered cones
-            // (smm_cone_big.hpp) instead of waiting for the one-workgroup resolution between two launches
-            const char* cbh = SMM_HOOK("SMMHIP_CONE_BIG");   // test hook: "0" keeps k_exch_resolve_rows between the launches
-            const char* kwb = SMM_HOOK("SMMHIP_KEY_WALK");
-            const bool want_cone_big = c->big_exchange && c->key_exchange && P.mi_uniform && P.mi_value == 0.0 && !(kwb && kwb[0] == '0') && c->norm_fast && c->norm_narrow &&
-                                       N == Ng && N % NORM_CT == 0 && Ng <= 32768 && K <= 65535 && P.dbg == 0 && !(cbh && cbh[0] == '0') &&
-                                       (size_t)Ng * 4 <= (size_t)160 * 1024;
-            const size_t plan_iter = (want_cone_big ? (size_t)(N / NORM_CT) * ((CONE_LEVELS * 64 + CONE_HDRW) * 4 + CONE_GCAP * 2) + cone_big_scratch_words(Ng, K) * 4 : 0) + (size_t)K * 36 + (c->big_exchange ? BigPlanScratch::words(Ng, K) * 4 + (size_t)(XROWS_MAX + 1) * XWG * 4 : 0) +
-                                     (size_t)lean_walk_Kp(K) * 4 + 1024 + (want_cone ? (size_t)(N / cone_ct) * (CONE_LEVELS * 64 + CONE_HDRW) * 4 + 4 : 0) +
-                                     ((want_persist_loc || want_persist_sh || want_persist_tile) ? persist_tiles * ((CONE_LEVELS * 64 + CONE_HDRW) * 4 + CONE_GCAP * 2) + 4 : 0) +
-                                     ((want_persist_sh && c->big_exchange) ? cone_big_scratch_words(Ng, K) * 4 : 0) +
-                                     (want_persist_gen ? persist_tiles * (CONE_GCAP * 2) : 0) +
-                                     ((want_persist_gen_small || want_persist_user) ? persist_tiles * ((CONE_LEVELS * 64 + CONE_HDRW) * 4 + CONE_GCAP * 2) + 4 : 0);
-            c->win_cap = pregen ? (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)768 << 20) / rb_iter)) : 1;
-            c->win_cap = std::min(c->win_cap, T);
-            c->plan_cap = (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)1536 << 20) / plan_iter));
-            c->plan_cap = std::min(c->plan_cap, T);
-            if (const char* pc = SMM_HOOK("SMMHIP_PLAN_CAP")) c->plan_cap = std::max(1, std::min(c->plan_cap, atoi(pc)));   // test hook: short plan windows
-            c->win_rb = dalloc<double>(c, (size_t)c->win_cap * N * P.RBW);
-            HIPCHK(hipMemset(c->win_rb, 0, (size_t)c->win_cap * N * P.RBW * 8));
-            if (c->big_exchange) {
-                c->win_lv_pairs = dalloc<uint32_t>(c, (size_t)c->plan_cap * K);
-                c->win_lv_mi = dalloc<double>(c, (size_t)c->plan_cap * K);
-                c->win_lv_off = dalloc<uint32_t>(c, (size_t)c->plan_cap * (K + 2));
-                c->big_scratch = dalloc<uint32_t>(c, (size_t)c->plan_cap * BigPlanScratch::words(Ng, K));
-                const char* kw = SMM_HOOK("SMMHIP_KEY_WALK");   // test hook: "0" keeps k_exch_resolve_key
-                if (c->key_exchange && P.mi_uniform && P.mi_value == 0.0 && !(kw && kw[0] == '0')) {
-                    c->rows_exchange = true;
-                    P.rows_cap = std::min(XROWS_MAX, (K + XWG - 1) / XWG + LV_MAXLEV);
-                    c->win_lv_rows = dalloc<uint32_t>(c, (size_t)c->plan_cap * P.rows_cap * XWG);
-                    c->win_lv_rowinfo = dalloc<uint32_t>(c, (size_t)c->plan_cap * 4);
-                    c->slots17 = dalloc<uint32_t>(c, (size_t)Ng + 4);
-                    c->nan_flags = dalloc<uint32_t>(c, 4);
-                    HIPCHK(hipMemset(c->nan_flags, 0, 16));
-                    if (want_cone_big) {
-                        const size_t tiles = (size_t)N / NORM_CT;
-                        c->cone_big = true;
-                        P.cone_tiles = (int)tiles; P.cone_ct = NORM_CT;
-                        P.cone_ok = dalloc<uint32_t>(c, (size_t)c->plan_cap);
-                        P.cone_hdr = dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * CONE_HDRW);
-                        P.cone_pairs = dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * (CONE_LEVELS * 64));
-                        P.cone_gather = dalloc<uint16_t>(c, (size_t)c->plan_cap * tiles * CONE_GCAP);
-                        HIPCHK(hipMemset((void*)P.cone_ok, 0, (size_t)c->plan_cap * 4));
-                        c->cb_scratch = dalloc<uint32_t>(c, (size_t)c->plan_cap * cone_big_scratch_words(Ng, K));
-                        const char* pah = SMM_HOOK("SMMHIP_PLAN_AHEAD");   // test hook: "0" plans each window on the main stream when it is entered
-                        if (!(pah && pah[0] == '0')) {
-                            c->plan_ahead = true;
-                            HIPCHK(hipStreamCreateWithFlags(&c->pstream, hipStreamNonBlocking));
-                            HIPCHK(hipEventCreateWithFlags(&c->ev_free, hipEventDisableTiming));
-                            for (int b = 0; b < 2; ++b) {
-                                Ctx::PlanSet& S = c->ps[b];
-                                S.lv_pairs = b ? dalloc<uint32_t>(c, (size_t)c->plan_cap * K) : c->win_lv_pairs;
-                                S.lv_mi = b ? dalloc<double>(c, (size_t)c->plan_cap * K) : c->win_lv_mi;
-                                S.lv_off = b ? dalloc<uint32_t>(c, (size_t)c->plan_cap * (K + 2)) : c->win_lv_off;
-                                S.lv_rows = b ? dalloc<uint32_t>(c, (size_t)c->plan_cap * P.rows_cap * XWG) : c->win_lv_rows;
-                                S.lv_rowinfo = b ? dalloc<uint32_t>(c, (size_t)c->plan_cap * 4) : c->win_lv_rowinfo;
-                                S.cone_ok = b ? dalloc<uint32_t>(c, (size_t)c->plan_cap) : (uint32_t*)P.cone_ok;
-                                S.cone_hdr = b ? dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * CONE_HDRW) : (uint32_t*)P.cone_hdr;
-                                S.cone_pairs = b ? dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * (CONE_LEVELS * 64)) : (uint32_t*)P.cone_pairs;
-                                S.cone_gather = b ? dalloc<uint16_t>(c, (size_t)c->plan_cap * tiles * CONE_GCAP) : P.cone_gather;
-                                HIPCHK(hipHostMalloc((void**)&S.ok_host, (size_t)c->plan_cap * 4, hipHostMallocDefault));
-                                HIPCHK(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-                            }
-                        }
-                        for (int b = 0; b < 2; ++b) c->slot8_buf[b] = dalloc<uint2>(c, (size_t)N + 4 + 128);
-                        P.slot8 = c->slot8_buf[0];
-                        P.walk_flags = dalloc<uint32_t>(c, 4);
-                        HIPCHK(hipMemset(P.walk_flags, 0, 16));
-                    }
-                }
-            }
-            if (c->big_exchange && want_persist_sh) {   // a shard of a large population: its own tiles' cones, locally numbered (smm_cone_big.hpp)
-                const size_t tiles = persist_tiles;
-                P.cone_tiles = (int)tiles; P.cone_ct = NORM_CT;
-                P.cone_ok = dalloc<uint32_t>(c, (size_t)c->plan_cap);
-                P.cone_hdr = dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * CONE_HDRW);
-                P.cone_pairs = dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * (CONE_LEVELS * 64) + 1024);
-                P.cone_gather = dalloc<uint16_t>(c, (size_t)c->plan_cap * tiles * CONE_GCAP + 512);
-                HIPCHK(hipMemset((void*)P.cone_ok, 0, (size_t)c->plan_cap * 4));
-                c->cb_scratch = dalloc<uint32_t>(c, (size_t)c->plan_cap * cone_big_scratch_words(Ng, K));
-                c->persist = true; c->persist_loc = true; c->persist_wide = P.mi_value != 0.0; c->persist_sh = true; c->persist_sh_big = true;
-                if (const char* rk = SMM_HOOK("SMMHIP_PR_RING")) { const int k = atoi(rk); if (k == 2 || k == 4) c->pr_ring_k = k; }
-                if (const char* st = SMM_HOOK("SMMHIP_PR_SLOW_TILE")) c->pr_slow_tile = atoi(st);
-                if (const char* su = SMM_HOOK("SMMHIP_PR_SLOW_US")) c->pr_slow_ticks = 100 * atoi(su);
-            }
-            if (c->lds_exchange) {
-                c->win_plan = dalloc<unsigned long long>(c, (size_t)c->plan_cap * K);
-                c->win_plan_mi = dalloc<double>(c, (size_t)c->plan_cap * K);
-                c->win_lv_pairs = dalloc<uint32_t>(c, (size_t)c->plan_cap * K);
-                c->win_lv_mi = dalloc<double>(c, (size_t)c->plan_cap * K);
-                c->win_lv_off = dalloc<uint32_t>(c, (size_t)c->plan_cap * (K + 2));
-                // the lean walk (smm_walk_lean.hpp): one min_improve for every chain — 0: 8-byte slots of order keys; > 0 (or NaN:
-                // nothing ever swaps): 16-byte slots of values, as far as the 160 KB of LDS reach (~7400 chains)
-                const char* kw = SMM_HOOK("SMMHIP_KEY_WALK");   // test hook: "0" keeps the walks on 16-byte / split slots
-                const bool keys = P.mi_uniform && P.mi_value == 0.0;
-                const bool wide = P.mi_uniform && !keys && !(P.mi_value < 0.0) && resolve_lean_bytes(Ng, K, true) <= (size_t)160 * 1024;
-                // (thresholds by chain: the lean PLAN — padded levels on 16-byte units, the tiles' cones behind it — is made for the persistent launches; the
-                // stand-alone lean resolution and the inline lean walks, which test ONE threshold, stay off: lean_resolve below, launch_chain_iter_norm)
-                const bool pct = P.mi_pct != 0 && (want_persist_loc || want_persist_tile) && !c->persist;
-                if ((keys || wide || pct) && K <= XLDS_MAX && !(kw && kw[0] == '0') && opts->dist_fun == SMM_DIST_MINUS) {
-                    P.lean_wide = (wide || pct) ? 1 : 0;
-                    P.plan_Kp = lean_walk_Kp(K);
-                    P.lean_unit = (wide || pct) ? lean_wide_unit(Ng) : lean_walk_unit(Ng);
-                    c->win_lv_pairs_p = dalloc<uint32_t>(c, (size_t)c->plan_cap * P.plan_Kp + 512);   // (+512: whole 1 KB pieces may be read past the last iteration's words)
-                    c->win_lv_offp = dalloc<uint32_t>(c, (size_t)c->plan_cap * LV_OFFP);
-                    c->lean_resolve = !pct;
-                    if (keys && ((c->norm_fast && c->inline_walk && Ng <= XLVL_MAX && K <= XLVL_MAX) || c->gen_keys)) {   // ... in the prologue of k_chain_iter_norm, or of k_chain_iter (key form)
-                        for (int b = 0; b < 2; ++b) c->slot8_buf[b] = dalloc<uint2>(c, (size_t)N + 4 + 128);
-                        P.slot8 = c->slot8_buf[0];
-                        P.walk_flags = dalloc<uint32_t>(c, 4);
-                        HIPCHK(hipMemset(P.walk_flags, 0, 16));
-                        if (want_cone) {
-                            const size_t tiles = (size_t)N / cone_ct;
-                            c->cone = true;
-                            P.cone_tiles = (int)tiles; P.cone_ct = cone_ct;
-                            P.cone_ok = dalloc<uint32_t>(c, (size_t)c->plan_cap);
-                            P.cone_hdr = dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * CONE_HDRW);
-                            P.cone_pairs = dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * (CONE_LEVELS * 64) + 1024);   // (+: whole 1 KB pieces are fetched)
-                            HIPCHK(hipMemset((void*)P.cone_ok, 0, (size_t)c->plan_cap * 4));
-                            if (want_persist_gen) {
-                                P.cone_gather = dalloc<uint16_t>(c, (size_t)c->plan_cap * tiles * CONE_GCAP + 512);
-                                P.pr_slot = (uint2*)dalloc<unsigned char>(c, persist_ring_slot_bytes(Ng));
-                                P.pr_rec = (uint4*)dalloc<unsigned char>(c, persist_ring_rec_bytes(Ng, P.RW));
-                                P.pr_progress = dalloc<uint32_t>(c, tiles);
-                                P.pr_ctl = dalloc<uint32_t>(c, 4);
-                                HIPCHK(hipMemset(P.pr_slot, 0, persist_ring_slot_bytes(Ng)));
-                                HIPCHK(hipMemset(P.pr_rec, 0, persist_ring_rec_bytes(Ng, P.RW)));
-                                HIPCHK(hipMemset(P.pr_progress, 0, tiles * 4));
-                                HIPCHK(hipMemset(P.pr_ctl, 0, 16));
-                                c->persist = true; c->persist_gen = true;
-                                if (const char* rk = SMM_HOOK("SMMHIP_PR_RING")) { const int k = atoi(rk); if (k == 2 || k == 4) c->pr_ring_k = k; }
-                                if (const char* st = SMM_HOOK("SMMHIP_PR_SLOW_TILE")) c->pr_slow_tile = atoi(st);
-                                if (const char* su = SMM_HOOK("SMMHIP_PR_SLOW_US")) c->pr_slow_ticks = 100 * atoi(su);
-                            }
-                        }
-                    }
-                    bool user_ok = false;
-                    if (want_persist_user && keys && !c->persist) {   // the kernel with the user's objective inside: compiled now (once per registered objective)
-                        std::lock_guard<std::mutex> lock(g_user_mutex);
-                        UserObjective& u = g_user_objectives[prob->objective_id - SMM_OBJ_USER_BASE];
-                        if (user_persist_compile(u)) {
-                            HIPCHK(hipModuleLoadData(&c->upmod, u.persist_code.data()));
-                            HIPCHK(hipModuleGetFunction(&c->upfn, c->upmod, "smm_user_persist_kernel"));
-                            user_ok = true;
-                        } else if (getenv("SMMHIP_VERBOSE")) fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n", u.persist_log.c_str());
-                    }
-                    if ((want_persist_gen_small || user_ok) && keys && !c->persist) {
-                        const size_t tiles = persist_tiles;
-                        P.cone_tiles = (int)tiles; P.cone_ct = PG_CT;
-                        P.cone_ok = dalloc<uint32_t>(c, (size_t)c->plan_cap);
-                        P.cone_hdr = dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * CONE_HDRW);
-                        P.cone_pairs = dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * (CONE_LEVELS * 64) + 1024);
-                        P.cone_gather = dalloc<uint16_t>(c, (size_t)c->plan_cap * tiles * CONE_GCAP + 512);
-                        HIPCHK(hipMemset((void*)P.cone_ok, 0, (size_t)c->plan_cap * 4));
-                        P.pr_slot = (uint2*)dalloc<unsigned char>(c, persist_ring_slot_bytes(Ng));
-                        P.pr_rec = (uint4*)dalloc<unsigned char>(c, persist_ring_rec_bytes(Ng, P.RW));
-                        P.pr_progress = dalloc<uint32_t>(c, tiles);
-                        P.pr_ctl = dalloc<uint32_t>(c, 4);
-                        HIPCHK(hipMemset(P.pr_slot, 0, persist_ring_slot_bytes(Ng)));
-                        HIPCHK(hipMemset(P.pr_rec, 0, persist_ring_rec_bytes(Ng, P.RW)));
-                        HIPCHK(hipMemset(P.pr_progress, 0, tiles * 4));
-                        HIPCHK(hipMemset(P.pr_ctl, 0, 16));
-                        c->persist = true; c->persist_gen = true; c->persist_user = user_ok; c->defer_resolve = user_ok;
-                        if (const char* rk = SMM_HOOK("SMMHIP_PR_RING")) { const int k = atoi(rk); if (k == 2 || k == 4) c->pr_ring_k = k; }
-                        if (const char* st = SMM_HOOK("SMMHIP_PR_SLOW_TILE")) c->pr_slow_tile = atoi(st);
-                        if (const char* su = SMM_HOOK("SMMHIP_PR_SLOW_US")) c->pr_slow_ticks = 100 * atoi(su);
-                    }
-                    if ((want_persist_loc || want_persist_sh) && !c->persist && c->norm_fast) {   // (the lean plan stands: k_exch_plan lists the tiles' cones behind it)
-                        const size_t tiles = persist_tiles;
-                        P.cone_tiles = (int)tiles; P.cone_ct = NORM_CT;
-                        P.cone_ok = dalloc<uint32_t>(c, (size_t)c->plan_cap);
-                        P.cone_hdr = dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * CONE_HDRW);
-                        P.cone_pairs = dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * (CONE_LEVELS * 64) + 1024);   // (+: whole 1 KB pieces are fetched)
-                        P.cone_gather = dalloc<uint16_t>(c, (size_t)c->plan_cap * tiles * CONE_GCAP + 512);
-                        HIPCHK(hipMemset((void*)P.cone_ok, 0, (size_t)c->plan_cap * 4));
-                        if (!want_persist_sh) {   // (a shard's ring lives in its p2p window: smm_bgp_p2p_init)
-                            const PrWin WL = pr_win_layout(Ng, P.RW, 1, (int)tiles);
-                            c->prw = dalloc<unsigned char>(c, WL.total);
-                            HIPCHK(hipMemset(c->prw, 0, WL.total));
-                        }
-                        c->persist = true; c->persist_loc = true; c->persist_wide = wide || pct; c->persist_sh = want_persist_sh;
-                        if (const char* rk = SMM_HOOK("SMMHIP_PR_RING")) { const int k = atoi(rk); if (k == 2 || k == 4) c->pr_ring_k = k; }
-                        if (const char* st = SMM_HOOK("SMMHIP_PR_SLOW_TILE")) c->pr_slow_tile = atoi(st);
-                        if (const char* su = SMM_HOOK("SMMHIP_PR_SLOW_US")) c->pr_slow_ticks = 100 * atoi(su);
-                    }
-                    bool tile_ok = want_persist_tile && !c->persist;
-                    if (tile_ok && user_tile) {   // the tile kernel with the user's map-reduce objective inside: compiled now (once per registered objective)
-                        std::lock_guard<std::mutex> lock(g_user_mutex);
-                        UserObjective& u = g_user_objectives[prob->objective_id - SMM_OBJ_USER_BASE];
-                        if (user_tile_compile(u)) {
-                            HIPCHK(hipModuleLoadData(&c->utmod, u.tile_code.data()));
-                            HIPCHK(hipModuleGetFunction(&c->utfn, c->utmod, "smm_user_persist_tile_kernel"));
-                        } else {
-                            tile_ok = false;
-                            if (getenv("SMMHIP_VERBOSE")) fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n", u.tile_log.c_str());
-                        }
-                    }
-                    if (tile_ok) {   // (the lean plan stands: k_exch_plan lists the tiles' cones and gather lists behind it)
-                        const size_t tiles = (size_t)(N + PT_CT - 1) / PT_CT;
-                        if (!P.cone_ok) {   // (the dense tiles of the per-iteration kernel walk the same cones: want_cone above)
-                            P.cone_tiles = (int)tiles; P.cone_ct = PT_CT;
-                            P.cone_ok = dalloc<uint32_t>(c, (size_t)c->plan_cap);
-                            P.cone_hdr = dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * CONE_HDRW);
-                            P.cone_pairs = dalloc<uint32_t>(c, (size_t)c->plan_cap * tiles * (CONE_LEVELS * 64) + 1024);   // (+: whole 1 KB pieces are fetched)
-                            HIPCHK(hipMemset((void*)P.cone_ok, 0, (size_t)c->plan_cap * 4));
-                        }
-                        if (P.cone_ct == PT_CT && (size_t)P.cone_tiles == tiles) {
-                            P.cone_gather = dalloc<uint16_t>(c, (size_t)c->plan_cap * tiles * CONE_GCAP + 512);
-                            const PrWin WL = pr_win_layout(Ng, P.RW, 1, (int)tiles);
-                            c->prw = dalloc<unsigned char>(c, WL.total);
-                            HIPCHK(hipMemset(c->prw, 0, WL.total));
-                            c->persist = true; c->persist_tile = true; c->persist_wide = true;
-                            if (!c->inline_walk) c->defer_resolve = true;   // (the exchange of an iteration is left to the next launch: it may be this kernel's)
-                            if (const char* rk = SMM_HOOK("SMMHIP_PR_RING")) { const int k = atoi(rk); if (k == 2 || k == 4) c->pr_ring_k = k; }
-                            if (const char* st = SMM_HOOK("SMMHIP_PR_SLOW_TILE")) c->pr_slow_tile = atoi(st);
-                            if (const char* su = SMM_HOOK("SMMHIP_PR_SLOW_US")) c->pr_slow_ticks = 100 * atoi(su);
-                        }
-                    }
-                }
+        const Forms& F = c->F;
+        P.tile_off = F.tile_off;
+        P.gen_lean = F.gen_keys ? 2 : F.gen_lean ? 1 : 0;
+        P.rows_cap = F.rows_cap;
+        // the look-ahead tables
+        c->win_rb = dalloc<double>(c, (size_t)F.win_cap * N * P.RBW);
+        HIPCHK(hipMemset(c->win_rb, 0, (size_t)F.win_cap * N * P.RBW * 8));
+        const size_t W = (size_t)F.plan_cap;
+        if (F.plan != PLAN_NONE) {
+            c->win_lv_pairs = dalloc<uint32_t>(c, W * K);
+            c->win_lv_mi = dalloc<double>(c, W * K);
+            c->win_lv_off = dalloc<uint32_t>(c, W * (K + 2));
+        }
+        if (F.plan == PLAN_BIG) c->big_scratch = dalloc<uint32_t>(c, W * BigPlanScratch::words(Ng, K));
+        if (F.xk == XK_ROWS) {
+            c->win_lv_rows = dalloc<uint32_t>(c, W * P.rows_cap * XWG);
+            c->win_lv_rowinfo = dalloc<uint32_t>(c, W * 4);
+            c->slots17 = dalloc<uint32_t>(c, (size_t)Ng + 4);
+            c->nan_flags = dalloc<uint32_t>(c, 4);
+            HIPCHK(hipMemset(c->nan_flags, 0, 16));
+        }
+        if (F.plan == PLAN_LDS) {
+            c->win_plan = dalloc<unsigned long long>(c, W * K);
+            c->win_plan_mi = dalloc<double>(c, W * K);
+        }
+        if (F.lean_plan) {
+            P.lean_wide = F.lean_wide ? 1 : 0;
+            P.plan_Kp = lean_walk_Kp(K);
+            P.lean_unit = F.lean_wide ? lean_wide_unit(Ng) : lean_walk_unit(Ng);
+            c->win_lv_pairs_p = dalloc<uint32_t>(c, W * P.plan_Kp + 512);   // (+512: whole 1 KB pieces may be read past the last iteration's words)
+            c->win_lv_offp = dalloc<uint32_t>(c, W * LV_OFFP);
+        }
+        if (F.walk_slots) {   // the lean key walk's slots, written by the accept step
+            for (int b = 0; b < 2; ++b) c->slot8_buf[b] = dalloc<uint2>(c, (size_t)N + 4 + 128);
+            P.slot8 = c->slot8_buf[0];
+            P.walk_flags = dalloc<uint32_t>(c, 4);
+            HIPCHK(hipMemset(P.walk_flags, 0, 16));
+        }
+        if (F.cone_tiles) {
+            P.cone_tiles = F.cone_tiles; P.cone_ct = F.cone_ct;
+            alloc_cones(c, P, (size_t)F.cone_tiles, F.cone_gather);
+        }
+        if (F.cone_big || F.persist_sh_big) c->cb_scratch = dalloc<uint32_t>(c, W * cone_big_scratch_words(Ng, K));
+        if (F.plan_ahead) {   // the big plan's second set of tables (the first: the window's own)
+            HIPCHK(hipStreamCreateWithFlags(&c->pstream, hipStreamNonBlocking));
+            HIPCHK(hipEventCreateWithFlags(&c->ev_free, hipEventDisableTiming));
+            Ctx::PlanSet& S0 = c->ps[0];
+            S0.lv_pairs = c->win_lv_pairs; S0.lv_mi = c->win_lv_mi; S0.lv_off = c->win_lv_off; S0.lv_rows = c->win_lv_rows; S0.lv_rowinfo = c->win_lv_rowinfo;
+            S0.cone_ok = (uint32_t*)P.cone_ok; S0.cone_hdr = (uint32_t*)P.cone_hdr; S0.cone_pairs = (uint32_t*)P.cone_pairs; S0.cone_gather = P.cone_gather;
+            Ctx::PlanSet& S1 = c->ps[1];
+            S1.lv_pairs = dalloc<uint32_t>(c, W * K);
+            S1.lv_mi = dalloc<double>(c, W * K);
+            S1.lv_off = dalloc<uint32_t>(c, W * (K + 2));
+            S1.lv_rows = dalloc<uint32_t>(c, W * P.rows_cap * XWG);
+            S1.lv_rowinfo = dalloc<uint32_t>(c, W * 4);
+            alloc_cones(c, S1, (size_t)F.cone_tiles, true);
+            for (Ctx::PlanSet& S : c->ps) {
+                HIPCHK(hipHostMalloc((void**)&S.ok_host, W * 4, hipHostMallocDefault));
+                HIPCHK(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
             }
         }
         {   // chain state blocks and records (BGPChain ctor, AlgoBGP.jl:78-109: best = Inf, best_id = -1, ...)
@@ -2303,15 +2279,14 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
         P.xres = dalloc<unsigned long long>(c, Ng);
         if (N > 0 && Ng % N == 0 && opts->chain_offset % N == 0) {   // equal shards: the values form of the sharded exchange is available
             c->a2a_G = Ng / N;
-            const char* ce = SMM_HOOK("SMMHIP_A2A_CAP");   // test hook: a small capacity
-            c->a2a_cap = ce ? std::max(1, atoi(ce)) : a2a_capacity(N, c->a2a_G);
+            c->a2a_cap = c->H.a2a_cap ? c->H.a2a_cap : a2a_capacity(N, c->a2a_G);
             c->a2a_send_idx = dalloc<int32_t>(c, (size_t)c->a2a_G * c->a2a_cap);
             c->a2a_send_cnt = dalloc<int32_t>(c, (size_t)c->a2a_G);
             c->a2a_rowidx = dalloc<int32_t>(c, (size_t)N);
         }
         for (int b = 0; b < 2; ++b) c->vals_buf[b] = dalloc<double>(c, (size_t)N + 4);   // (+4: read as 16-byte pieces)
         P.vals = c->vals_buf[0];
-        if (!c->lds_exchange) {
+        if (F.plan != PLAN_LDS) {
             const int Kmax = std::max(K, 1);
             P.xval = dalloc<double>(c, Ng); P.xnext = dalloc<int32_t>(c, Ng); P.xpairs = dalloc<int32_t>(c, (size_t)Kmax * 2);
             P.xsrc = dalloc<int32_t>(c, Ng); P.xpartner = dalloc<int32_t>(c, Ng);
@@ -2337,61 +2312,10 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
             const unsigned long long e = ERR_NONE;
             HIPCHK(hipMemcpy(P.err, &e, 8, hipMemcpyHostToDevice));
         }
-        if (c->persist_user) {
-            const size_t smem = persist_gen_smem_bytes(Ng, np, P.RW, P.HW) + persist_gen_user_bytes();
-            (void)hipFuncSetAttribute((const void*)c->upfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);   // (a module's function: where the runtime takes it)
-            (void)hipGetLastError();
-            int per_cu = 0, cus = 0;
-            HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->upfn, 1024, smem));
-            HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-            if (N / PG_CT > per_cu * cus) { c->persist = false; c->persist_gen = false; c->persist_user = false; c->defer_resolve = false; }
-        } else if (c->persist_gen) {
-            const size_t smem = persist_gen_smem_bytes(Ng, np, P.RW, P.HW);
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_persist_gen, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            int per_cu = 0, cus = 0;
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_chain_persist_gen, 1024, smem));
-            HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-            if (N / PG_CT > per_cu * cus) { c->persist = false; c->persist_gen = false; }
-        } else if (c->persist_loc) {
-            const size_t smem = persist_loc_smem_bytes(np);
-            const void* fn = persist_loc_fn(np, c->persist_wide, c->persist_sh, P.mi_pct != 0);
-            HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            int per_cu = 0, cus = 0;
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NORM_WG, smem));
-            HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-            c->persist_max_tiles = per_cu * cus;
-            if ((N + NORM_CT - 1) / NORM_CT > per_cu * cus) { c->persist = false; c->persist_loc = false; c->persist_sh = false; }
-        }
-        if (c->persist_tile) {
-            const int kind = obj_kind(c->obj);
-            const size_t smem = persist_tile_smem(c);
-            int per_cu = 0, cus = 0;
-            if (c->utfn) {
-                (void)hipFuncSetAttribute((const void*)c->utfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);   // (a module's function: not every runtime takes it this way; the launch asks for what it needs)
-                (void)hipGetLastError();
-                HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->utfn, WG, smem));
-            } else {
-                const void* fn = P.mi_pct ? (kind == 2 ? (const void*)k_chain_persist_tile<2, true> : (const void*)k_chain_persist_tile<1, true>)
-                                          : (kind == 2 ? (const void*)k_chain_persist_tile<2> : (const void*)k_chain_persist_tile<1>);
-                HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, WG, smem));
-            }
-            HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-            c->persist_max_tiles = per_cu * cus;
-            if ((N + PT_CT - 1) / PT_CT > per_cu * cus) { c->persist = false; c->persist_tile = false; c->defer_resolve = false; }
-        }
-        if (c->persist) {
-            c->snap_cs = dalloc<double>(c, (size_t)N * CSW);
-            c->snap_rec = dalloc<double>(c, (size_t)N * P.RW);
-            for (int b = 0; b < 2; ++b) { c->snap_vals[b] = dalloc<double>(c, (size_t)N + 4); c->snap_slot8[b] = dalloc<uint2>(c, (size_t)N + 4 + 128); }
-            c->snap_xres = dalloc<unsigned long long>(c, Ng);
-            c->hist_fill = dalloc<double>(c, (size_t)N * P.HW);
-            HIPCHK(hipMemcpy(c->hist_fill, P.hrec, (size_t)N * P.HW * 8, hipMemcpyDeviceToDevice));   // (a row of the constructor's fill)
-        }
-        if (c->big_exchange)
+        if (F.persist != PERSIST_NONE) alloc_persist(c);
+        if (F.plan == PLAN_BIG)
             HIPCHK(hipFuncSetAttribute((const void*)k_exch_plan_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan_big_lds_bytes(65535)));
-        if (c->key_exchange)
-        {
+        if (F.xk == XK_ROWS || F.xk == XK_KEY) {
             HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_key<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)resolve_key_bytes(XKEY_MAX, XKEY_MAX)));
             HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_key<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2406,7 +2330,7 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
             HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_rows<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)resolve_rows_bytes(XKEY_PARTNER_MAX, XKEY_PARTNER_MAX, XROWS_MAX)));
         }
-        if (c->lds_exchange) {
+        if (F.plan == PLAN_LDS) {
 #ifdef SMM_TEST_HOOKS
             HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)resolve_lds_bytes(XLDS_MAX)));
@@ -2453,7 +2377,7 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
             HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_narrow_cone<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
             HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_narrow_cone<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
             HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_narrow_cone<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            if (c->cone_big) HIPCHK(hipFuncSetAttribute((const void*)k_cone_chains, hipFuncAttributeMaxDynamicSharedMemorySize, Ng * 4));
+            if (F.cone_big) HIPCHK(hipFuncSetAttribute((const void*)k_cone_chains, hipFuncAttributeMaxDynamicSharedMemorySize, Ng * 4));
             HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_wide<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
             HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_wide<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
             HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_wide<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
@@ -2481,10 +2405,9 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
             HIPCHK(hipFuncSetAttribute((const void*)k_eval_batch<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
             HIPCHK(hipFuncSetAttribute((const void*)k_eval_batch<2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
             HIPCHK(hipFuncSetAttribute((const void*)k_eval_batch<0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            if (tile_smem(c, is_sim(c->obj) ? c->ct : (c->obj == SMM_OBJ_DENSE ? 16 : 8)) > (size_t)lim)
+            if (tile_smem(c, is_sim(c->obj) ? F.ct : (c->obj == SMM_OBJ_DENSE ? 16 : 8)) > (size_t)lim)
                 throw std::string("tile does not fit the 160 KiB LDS");
         }
-        c->xk = (int)choose_exchange(c);
         HIPCHK(hipDeviceSynchronize());
     } catch (const std::string& m) {
         g_create_err = m;
@@ -2630,7 +2553,7 @@ int smm_bgp_sharded_step(void* ctx, const void* gathered_prev_dev, void* gathere
         }
         if (c->rec_external) {
             if (c->pending_ext) {   // exchangeMoves! of iteration t-1 over the gathered records (before its plan window can move on)
-                if (prof && c->lean_resolve) { c->kev0 = c->pev[4 * it + 2]; c->kev1 = c->pev[4 * it + 3]; c->pev_exch[it] = 1; }
+                if (prof && c->F.xk == XK_LEAN) { c->kev0 = c->pev[4 * it + 2]; c->kev1 = c->pev[4 * it + 3]; c->pev_exch[it] = 1; }
                 launch_resolve(c, t - 1, (const double*)gathered_prev_dev);
                 c->kev0 = c->kev1 = nullptr;
                 flags |= F_HAS_PENDING;
@@ -2712,7 +2635,7 @@ int smm_bgp_p2p_init(void* ctx, void* ipc_handle_out, void** window_dev_out) {
             // system-scope stores, self-validating words are re-read past the caches until their tag is the wanted one.)
             // (a shard that can run the persistent form keeps its ring behind the p2p window proper: one allocation, one IPC handle)
             size_t total = L.total;
-            if (c->persist_sh) {
+            if (c->F.persist_sh) {
                 c->prw_off = (L.total + 255) & ~(size_t)255;
                 total = c->prw_off + pr_win_layout(P.Ng, P.RW, c->a2a_G, (P.N + NORM_CT - 1) / NORM_CT).total;
             }
@@ -2737,12 +2660,12 @@ int smm_bgp_p2p_init(void* ctx, void* ipc_handle_out, void** window_dev_out) {
             c->p2p_current = false;
             // one launch per iteration (the lean key walk in the chain kernel's prologue, the push in its epilogue) where the
             // single shard has it too: objfunc_norm with np == nm <= 4, min_improve == 0, N_global <= 8192
-            c->p2p_inline = c->norm_fast && c->win_lv_pairs_p && !P.lean_wide && P.Ng <= XLDS_MAX && P.plan_K <= XLDS_MAX && !c->deep_plan &&
+            c->p2p_inline = c->F.norm_fast && c->F.lean_plan && !P.lean_wide && P.Ng <= XLDS_MAX && P.plan_K <= XLDS_MAX && !c->deep_plan &&
                             P.dist_fun == SMM_DIST_MINUS && p2p_walk_bytes(c) + norm_tile_doubles(P.np) * 8 <= (size_t)160 * 1024;
             // two launches per iteration for the large norm populations (8192 < N_global <= 32768, min_improve == 0: BASELINE
             // configs[2], 4 and 8 shards of 4096): k_exch_resolve_rows reads the window's tagged slots itself, the chain kernel
             // pushes from its epilogue like the inline form's
-            c->p2p_rows = c->norm_fast && !c->p2p_inline && c->xk == XK_ROWS;
+            c->p2p_rows = c->F.norm_fast && !c->p2p_inline && c->F.xk == XK_ROWS;
         }
         if (ipc_handle_out) {
             hipIpcMemHandle_t h;
@@ -3246,7 +3169,7 @@ int smm_set_persistent(void* ctx, int32_t on) {
 int smm_get_persistent(void* ctx, int32_t* available, int32_t* launches, int32_t* repairs) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return SMM_ERR_INVALID_ARG;
-    if (available) *available = (c->persist && c->persist_on && !c->persist_broken) ? 1 : 0;
+    if (available) *available = (c->F.persist != PERSIST_NONE && c->persist_on && !c->persist_broken) ? 1 : 0;
     if (launches) *launches = c->persist_launches;
     if (repairs) *repairs = c->persist_repairs;
     return SMM_OK;
@@ -3259,20 +3182,20 @@ int smm_describe(void* ctx, char* out, int32_t cap) {
     const KParams& P = c->P;
     const char* chain;
     if (c->obj == SMM_OBJ_USER) chain = c->u_lanes ? "user_lanes_3launches" : "user_3launches";
-    else if (c->norm_fast)
-        chain = c->cone_big ? "iter_norm_narrow_cone" : (!c->win_lv_pairs_p || c->deep_plan || c->nan_values || P.mi_pct) && c->inline_walk ? "iter_norm_any"
-              : (P.lean_wide && c->inline_walk) ? "iter_norm_wide" : c->norm_narrow ? "iter_norm_narrow" : "iter_norm";
-    else chain = c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "iter<dense2,16>" : "iter<dense,16>") : is_sim(c->obj) ? (c->tpw == 2 ? "iter<sim,8,2>" : "iter<sim,8>")
-               : (c->gen_keys ? "iter<gen,16,2>" : c->tpw == 2 ? "iter<gen,8,2>" : "iter<gen,8>");
+    else if (c->F.norm_fast)
+        chain = c->F.cone_big ? "iter_norm_narrow_cone" : (!c->F.lean_plan || c->deep_plan || c->nan_values || P.mi_pct) && c->F.inline_walk ? "iter_norm_any"
+              : (P.lean_wide && c->F.inline_walk) ? "iter_norm_wide" : c->F.norm_narrow ? "iter_norm_narrow" : "iter_norm";
+    else chain = c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "iter<dense2,16>" : "iter<dense,16>") : is_sim(c->obj) ? (c->F.tpw == 2 ? "iter<sim,8,2>" : "iter<sim,8>")
+               : (c->F.gen_keys ? "iter<gen,16,2>" : c->F.tpw == 2 ? "iter<gen,8,2>" : "iter<gen,8>");
     static const char* xk[] = {"lean", "lvl", "lvl_soa", "tickets", "rows", "key", "lvl_big", "any"};
-    const char* walk = c->cone_big ? "cone_local" : !c->inline_walk ? "standalone" : c->dense_keys ? "inline_keys_under_tile" : c->gen_keys ? (c->cone ? "inline_keys_cone" : "inline_keys")
-                     : c->norm_fast ? ((P.lean_wide && !P.mi_pct) ? "inline_lean_wide" : (c->win_lv_pairs_p && !P.mi_pct) ? "inline_lean" : "inline_slots") : c->gen_lean ? "inline_lean16" : "inline_slots";
-    const char* pers = !c->persist ? "none" : c->persist_loc ? (c->persist_sh ? (c->persist_sh_big ? (c->persist_wide ? "loc_wide_shard_bigplan" : "loc_shard_bigplan")
-                                                                                                    : (c->persist_wide ? "loc_wide_shard" : "loc_shard"))
-                                                                              : (c->persist_wide ? "loc_wide" : "loc"))
-                     : c->persist_tile ? (c->utfn ? "tile_user" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2" : "tile_dense") : "tile_sim") : c->persist_user ? "gen_user" : "gen";
-    snprintf(out, (size_t)cap, "chain=%s walk=%s exchange=%s persistent=%s plan=%s window=%d", chain, walk, xk[c->xk], pers,
-             c->big_exchange ? (c->plan_ahead ? "big_ahead" : "big") : c->lds_exchange ? "lds" : "none", c->plan_cap);
+    const char* walk = c->F.cone_big ? "cone_local" : !c->F.inline_walk ? "standalone" : c->F.dense_keys ? "inline_keys_under_tile" : c->F.gen_keys ? (c->F.cone ? "inline_keys_cone" : "inline_keys")
+                     : c->F.norm_fast ? ((P.lean_wide && !P.mi_pct) ? "inline_lean_wide" : (c->F.lean_plan && !P.mi_pct) ? "inline_lean" : "inline_slots") : c->F.gen_lean ? "inline_lean16" : "inline_slots";
+    const char* pers = c->F.persist == PERSIST_NONE ? "none" : c->F.persist == PERSIST_LOC ? (c->F.persist_sh ? (c->F.persist_sh_big ? (c->F.persist_wide ? "loc_wide_shard_bigplan" : "loc_shard_bigplan")
+                                                                                                    : (c->F.persist_wide ? "loc_wide_shard" : "loc_shard"))
+                                                                              : (c->F.persist_wide ? "loc_wide" : "loc"))
+                     : c->F.persist == PERSIST_TILE ? (c->utfn ? "tile_user" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2" : "tile_dense") : "tile_sim") : c->F.persist_user ? "gen_user" : "gen";
+    snprintf(out, (size_t)cap, "chain=%s walk=%s exchange=%s persistent=%s plan=%s window=%d", chain, walk, xk[c->F.xk], pers,
+             c->F.plan == PLAN_BIG ? (c->F.plan_ahead ? "big_ahead" : "big") : c->F.plan == PLAN_LDS ? "lds" : "none", c->F.plan_cap);
     return SMM_OK;
 }
 
