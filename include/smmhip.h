@@ -347,7 +347,11 @@ int  smm_bgp_sharded_finish(void* ctx, const void* gathered_dev);
  *   rendezvous and replay the step on the forms above.
  *   What a shard in the persistent form sends per chain, iteration and PEER: the parameters and the value of its last accepted
  *   record as self-validating granules — (np + 1) x 16 bytes, 48 at two parameters; the rest of a record (prob, status, simulated
- *   moments) stays in the owner's window and is fetched by the one chain that continues from it (swap_ev_ij!, AlgoBGP.jl:734-749). */
+ *   moments) stays in the owner's window and is fetched by the one chain that continues from it (swap_ev_ij!, AlgoBGP.jl:734-749).
+ *   The same holds for the shards of the objectives a whole tile evaluates (objfunc_norm with more than two parameters, SMM_OBJ_DENSE,
+ *   SMM_OBJ_DENSE2, a map-reduce user objective; below): 816 bytes per chain, iteration and peer at np = 50 (BASELINE config 5), the
+ *   donor's other granules read from its owner's window behind the objective.  The ring part of the window holds the context's own
+ *   records: PR_K x N_global x RW x 16 bytes (RW = 104 at np = nm = 50: 13.6 MB at 4096 chains). */
 #define SMM_P2P_HANDLE_BYTES 64
 int  smm_bgp_p2p_init(void* ctx, void* ipc_handle_out, void** window_dev_out);
 int  smm_bgp_p2p_attach(void* ctx, int32_t rank, const void* ipc_handle, void* window_dev);
@@ -407,12 +411,16 @@ int  smm_set_profiling(void* ctx, int32_t on);
  *     stand-alone kernel's reduction order — the same bits; it pays while an evaluation is short beside the ~40 us of three launches per
  *     iteration: a long simulation fills the device better from its own launches, smm_set_persistent(ctx, 0)):
  *     one proposal batch or several, isotropic proposals, dist_fun = `-`, ONE min_improve >= 0 (or NaN) for all chains, a single shard of
- *     at most two 16-chain tiles per compute unit whose blocks fit the LDS (np = nm = 50: yes; 64 + 64: no).
+ *     at most two 16-chain tiles per compute unit whose blocks fit the LDS (np = nm = 50: yes; 64 + 64: no) — or a SHARD of a sharded run
+ *     (smm_bgp_p2p_step; smm_chain_persist_tile.hpp, SH) with the same conditions and: equal shards of whole tiles (N a multiple of 16,
+ *     chain_offset a multiple of N, at most 8 ranks), N_global <= 8192 (the LDS plan), min_improve the same for every chain.  A
+ *     map-reduce user objective's shard form is a second hiprtc module, compiled only when a sharded context first wants it.
  *   - (round 6) min_improve BY CHAIN, what the reference's API takes (a vector, AlgoBGP.jl:522; the pair (i, j) is tested against chain i's,
  *     :688): single shards of the objfunc_norm and tile forms above walk one threshold per chain, every one >= 0 or NaN; a context's single
  *     iterations keep the per-iteration kernels' walk on any thresholds.
- * A negative threshold, other dist_fun, Cholesky proposals, user objectives with 1024 lanes, shards of anything but objfunc_norm with at
- * most two parameters and one threshold: the per-iteration kernels.
+ * A negative threshold, other dist_fun, Cholesky proposals, user objectives with 1024 lanes; as shards: thresholds by chain, N_global past
+ * 8192 for anything but objfunc_norm with at most two parameters (bench.py --gpus 8 --workload c5's weak-scaling 32768 chains among them),
+ * the banana and one-thread user objectives: the per-iteration kernels.
  * on = 0 keeps the one-launch-per-iteration kernels (default: on).  A hard error of the algorithm inside such a launch is found at
  * the next call that checks (smm_sync, smm_bgp_step, the state readers): the library then repeats those iterations from the state
  * it saved on the one-launch-per-iteration path, so that the context stands at the failing iteration exactly as documented above.

@@ -123,6 +123,7 @@ const OBJ_NORM = Cint(0)
 const OBJ_BANANA = Cint(1)
 const OBJ_NORM_FAILBOX = Cint(2)
 const OBJ_DENSE = Cint(3)
+const OBJ_DENSE2 = Cint(5)      # the dense simulation with its 256 x 256 stage: BASELINE config 5 as worded
 const OBJ_USER_BASE = Cint(1000)
 # smm_dist_fun_t (opts["dist_fun"], AlgoBGP.jl:537)
 const DIST_MINUS = Cint(0)

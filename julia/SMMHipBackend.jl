@@ -18,7 +18,8 @@
 # objective, accept/reject, set_eval! for all chains and exchangeMoves!, AlgoBGP.jl:589-640) instead of pmap/map over chains.
 #
 # The objective must be a DEVICE objective: `SMM.objfunc_norm` maps to the built-in one; anything else is given as
-# `opts["hip_objective"]` = an id of SMMHip.hip_register_objective(source) (or :banana / :dense, or the source text itself: registered
+# `opts["hip_objective"]` = an id of SMMHip.hip_register_objective(source) (or :banana / :dense / :dense2 — :dense2 is BASELINE config 5 as
+# worded, the dense simulation with its 256 x 256 stage —, or the source text itself: registered
 # once, with opts["hip_rng"] = true as an objective that draws from the library's stream, SMM_USER_OBJECTIVE_RNG — opts["hip_n_sums"] /
 # opts["hip_lanes"] for its map-reduce form), with `opts["hip_ns"]`, `opts["hip_obj_params"]` as needed.  A Julia closure cannot run inside the GPU iteration.
 #
@@ -86,6 +87,7 @@ function device_objective(m::MProb, opts::Dict)
         o == :norm && return SMMHip.OBJ_NORM
         o == :banana && return SMMHip.OBJ_BANANA
         o == :dense && return SMMHip.OBJ_DENSE
+        o == :dense2 && return SMMHip.OBJ_DENSE2
         throw(ArgumentError("unknown opts[\"hip_objective\"] = $o"))
     end
     m.objfunc === SMM.objfunc_norm && return SMMHip.OBJ_NORM

@@ -20,9 +20,15 @@
 //   * no role specialisation (every wave is needed by the proposal and the objective): what persist_loc's worker waves do under the
 //     simulation — the next lists by LDS-DMA, the re-numbering table, the next randomness — is issued before the objective and waited
 //     for behind it; the gather runs behind the publication, where the tile would otherwise wait for its peers' stores.
-// One proposal batch or several, isotropic proposals (no Cholesky factor), dist_fun = -, a single shard of at most one tile per
-// workgroup slot of the device.  Results are bit-identical to k_chain_iter's.  Errors, ring overrun guard, time-outs,
-// repair: as in smm_chain_persist.hpp.
+// One proposal batch or several, isotropic proposals (no Cholesky factor), dist_fun = -, at most one tile per workgroup slot of the
+// device.  Results are bit-identical to k_chain_iter's.  Errors, ring overrun guard, time-outs, repair: as in smm_chain_persist.hpp.
+// SH = a SHARD of a sharded run (equal shards, N_global <= 8192): smm_chain_persist_loc.hpp's protocol on this kernel's records — the
+// launches of the ranks meet in the start barrier, a tile publishes its chains' whole records (RW granules) into its own rank's window
+// and, into every peer's, only what a walk or a proposal reads: the value (granule 0) and the parameters (granules 3 .. 3 + np - 1),
+// (np + 1) x 16 bytes per chain and peer; the gather and an exchanged chain's value and parameters come from the own window, the rest of
+// a donor's record (prob, status, simulated moments) from its owner's, behind the objective — its rewritten history row of t - 1 is put
+// together after that; progress is announced into every rank's window, a give-up is mirrored to the peers, and a NaN value among the
+// records a launch starts from is reported as kind 3 (the ranks agree on the word and replay the step on the per-iteration forms).
 // Reference semantics: AlgoBGP.jl:589-640 (computeNextIteration!), :647-716 (exchangeMoves!), :734-749 (swap_ev_ij!).
 // ------------------------------------------------------------------------------------------
 constexpr int PT_CT = 16;          // chains per tile
@@ -46,6 +52,10 @@ struct PersistTileArgs {
     unsigned long long tmo;            // ticks a spin may last
     const double* mi_g;                // min_improve of every chain of the population (the wide walk's per-position thresholds, AlgoBGP.jl:522, :688)
     int u_lanes, n_udata;              // a user objective in its map-reduce form (SMM_TILE_USER below): lanes per evaluation, doubles of its data (objp)
+    unsigned char* win[P2P_MAXG];      // SH: the ranks' windows (self = win[rank])
+    uint32_t o_arrive;                 // SH: the start barrier's words (pr_win_layout)
+    int G, rank, offset;               // SH: ranks, this rank, the shard's first chain in the population (equal shards of N)
+    int slow_read;                     // SH, test build: the slow tile idles before its donors' remote reads instead of before its publication
 };
 
 // LDS: [slots 16 B x PL_LOCN | pair words | gather list | 4 headers | re-numbering table | flags, stamps] doubles: cs rec[2] theta
@@ -102,14 +112,21 @@ __device__ __attribute__((noinline)) uint4 pt_wait_ll(const PrWait W, const uint
 // evaluate 512 / lanes chains at a time, `lanes` lanes per chain exactly as the stand-alone smm_user_eval_kernel does (lane l of n_lanes, the halving tree
 // inside each group of 64, the groups' totals left to right: the numerical contract of include/smmhip.h — results are bit-identical), the chain's lane
 // calls the user's finish, and a failing evaluation (status < 0) is the rejection of mprob.jl:183-186 / AlgoBGP.jl:336-338.
+// (a shard's form of it is a module of its own, compiled with SMM_TILE_SH as well, only when a sharded context wants it: user_tile_compile)
 #ifdef SMM_TILE_USER
 extern "C" __global__ __launch_bounds__(WG) void smm_user_persist_tile_kernel(const PersistTileArgs A) {
     constexpr int KIND = 4;
     constexpr bool PCT = false;   // (one threshold for all chains)
+#ifdef SMM_TILE_SH
+    constexpr bool SH = true;
 #else
-template <int KIND, bool PCT = false>   // PCT: thresholds by chain (a form of its own: see k_chain_persist_loc)
+    constexpr bool SH = false;
+#endif
+#else
+template <int KIND, bool PCT = false, bool SH = false>   // PCT: thresholds by chain (a form of its own: see k_chain_persist_loc); SH: a shard
 __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs A) {
     static_assert(KIND == 1 || KIND == 2, "objfunc_norm (shocks streamed) or the dense simulation");
+    static_assert(!(PCT && SH), "thresholds by chain: single shards only");
 #endif
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int CT = PT_CT, LPC = PT_LPC;
@@ -150,12 +167,15 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
     uint32_t* const pr_progress = (uint32_t*)(mine + A.o_progress);
     const PrWait W{A.err, pr_ctl, s_abort, A.epoch, A.tmo};
     const int rmask = A.ring_k - 1;
-    const uint32_t c0g = (uint32_t)(tile * CT);   // the tile's first chain
+    const int goff = SH ? A.offset : 0;                    // the shard's first chain in the population
+    const int tiles_all = SH ? tiles * A.G : tiles;        // progress words: every rank's tiles
+    const uint32_t c0g = (uint32_t)(goff + tile * CT);     // the tile's first chain in the population
     const bool exch_any = A.Ng > 1;
     auto exch_on = [&](const int tx) { return exch_any && tx >= A.exch_from; };   // AlgoBGP.jl:637
     const bool rng_here = A.rb == nullptr;
     const int cc = tid / LPC, r2 = tid % LPC;     // chain of the tile, lane of the chain
     const int c = tile * CT + cc;
+    const int cg = goff + c;                      // ... its number in the population
     const bool valid = c < N;
     const bool chain_lane = valid && r2 == 0;
 
@@ -171,10 +191,10 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
                 const int cl = it / per, what = it - cl * per, c1 = tile * CT + cl;
                 if (c1 >= N) continue;
                 double* o = s_rb + cl * RBW;
-                if (what == 0) o[0] = rng_u(A.seed, (uint32_t)c1, (uint32_t)tn);       // probs_acc[iter], AlgoBGP.jl:85
+                if (what == 0) o[0] = rng_u(A.seed, (uint32_t)(goff + c1), (uint32_t)tn);       // probs_acc[iter], AlgoBGP.jl:85
                 else {
                     const int rr = (what - 1) / Q, q = (what - 1) - rr * Q;
-                    const double2 zz2 = rng_prop_normal2_outofline(A.seed, (uint32_t)c1, (uint32_t)tn, (uint32_t)rr, (uint32_t)q);   // rand(RAND, d), :404
+                    const double2 zz2 = rng_prop_normal2_outofline(A.seed, (uint32_t)(goff + c1), (uint32_t)tn, (uint32_t)rr, (uint32_t)q);   // rand(RAND, d), :404
                     o[1 + rr * np + 2 * q] = zz2.x;
                     if (2 * q + 1 < np) o[1 + rr * np + 2 * q + 1] = zz2.y;
                 }
@@ -202,10 +222,10 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
             const int cl = it / per, what = it - cl * per, c1 = tile * CT + cl;
             if (c1 >= N) continue;
             double* o = s_rb + cl * RBW;
-            if (what == 0) o[0] = rng_u(A.seed, (uint32_t)c1, (uint32_t)tn);       // probs_acc[iter], AlgoBGP.jl:85
+            if (what == 0) o[0] = rng_u(A.seed, (uint32_t)(goff + c1), (uint32_t)tn);       // probs_acc[iter], AlgoBGP.jl:85
             else {
                 const int rr = (what - 1) / Q, q = (what - 1) - rr * Q;
-                const double2 zz2 = rng_prop_normal2_outofline(A.seed, (uint32_t)c1, (uint32_t)tn, (uint32_t)rr, (uint32_t)q);   // rand(RAND, d), :404
+                const double2 zz2 = rng_prop_normal2_outofline(A.seed, (uint32_t)(goff + c1), (uint32_t)tn, (uint32_t)rr, (uint32_t)q);   // rand(RAND, d), :404
                 o[1 + rr * np + 2 * q] = zz2.x;
                 if (2 * q + 1 < np) o[1 + rr * np + 2 * q + 1] = zz2.y;
             }
@@ -268,15 +288,25 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
         }
         if (tid == WG - 1) { slots[CT + ngat] = make_uint4(0u, 0u, 0u, 0u); if constexpr (PCT) s_thr[CT + ngat] = 0.0; }   // the dummy pair's slot: 0 - 0 > 0 is false
     };
+    // SH: the granules a peer reads of a record — the value and the parameters (the walk's gather, a donor's proposal)
+    auto peer_granule = [&](const int f) { return f == 0 || (f >= 3 && f < 3 + np); };
+    // ... one of them into every peer's window (the ring's layout is the same in all)
+    auto store_peers = [&](const int rel, const int f, const p2p_u32x4 q) {
+        const size_t off = (size_t)A.o_rec + (((size_t)(rel & rmask) * A.Ng + (size_t)cg) * RW + (size_t)f) * 16;
+#pragma unroll
+        for (int p = 0; p < P2P_MAXG; ++p)
+            if (p < A.G && p != A.rank) asm volatile("global_store_dwordx4 %0, %1, off " PR_SC "\n\ts_nop 1" :: "v"(A.win[p] + off), "v"(q) : "memory");
+    };
     // a chain's record as iteration `rel` of the launch into the ring: self-validating granules, 32 lanes per chain
     // (lane r2 stores the granules r2, r2 + 32, ...: every store instruction writes 512 contiguous bytes per chain)
     auto publish = [&](const int rel, const double* rec) {
-        uint4* g_ll = ring_rec(rel) + (size_t)c * RW;
+        uint4* g_ll = ring_rec(rel) + (size_t)cg * RW;
         const uint32_t tag = pr_tag32(epoch, rel);
         for (int f = r2; f < RW; f += LPC) {
             const unsigned long long a = __builtin_bit_cast(unsigned long long, rec[f]);
             const p2p_u32x4 q = {(unsigned)a, tag, (unsigned)(a >> 32), tag};
             asm volatile("global_store_dwordx4 %0, %1, off " PR_SC "\n\ts_nop 1" :: "v"(g_ll + f), "v"(q) : "memory");
+            if (SH && peer_granule(f)) store_peers(rel, f, q);
         }
     };
 
@@ -288,6 +318,9 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
         for (int i = r2; i < RW / 2; i += LPC) ((double2*)(s_rec + ((t0 & 1) * CT + cc) * RW))[i] = g_rec[i];
         if (r2 == 0) {
             const double v0 = A.rec_in[(size_t)c * RW];
+            // (a NaN value — only an uploaded state holds one — orders under no key; a shard's form is chosen from what every rank knows,
+            // so the launch says it: smm_chain_persist_loc.hpp)
+            if (SH && v0 != v0) pr_report(A.err, 3, t0, cg);
             slots[cc] = make_uint4((uint32_t)__double2loint(v0), (uint32_t)__double2hiint(v0), (uint32_t)cc, 0u);
             if constexpr (PCT) s_thr[cc] = A.mi_g[c];
         }
@@ -301,7 +334,30 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
         if (t0 < t1 && exch_on(t0)) s_hdr[(t0 & 3) * 16 + lane] = A.cone_hdr[((size_t)(t0 - A.plan_t0) * tiles + tile) * CONE_HDRW + lane];
     }
     fetch_rb(t0);
+    if constexpr (SH) {
+        // the launches of the ranks meet (smm_chain_persist_loc.hpp): nobody stores into anybody's ring before every rank has arrived
+        if (tile == 0 && wave == 2 && lane < A.G) {
+            unsigned char* w = nullptr;
+#pragma unroll
+            for (int p = 0; p < P2P_MAXG; ++p) w = lane == p ? A.win[p] : w;
+            __hip_atomic_store((uint32_t*)(w + A.o_arrive + 128 * (size_t)A.rank), epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        if (wave == 2) {
+            const unsigned long long w0 = wall_clock64();
+            unsigned spins = 0;
+            bool there = lane >= A.G;
+            while (__ballot(!there) != 0ull) {
+                if (!there) there = (int)(__hip_atomic_load((const uint32_t*)(mine + A.o_arrive + 128 * (size_t)lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - epoch) >= 0;
+                if ((++spins & 63u) == 0u && (wall_clock64() - w0 > A.tmo)) {
+                    if (lane == 0) { pr_report(A.err, 3, t0, (int)c0g); __hip_atomic_store(pr_ctl, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(2);
+            }
+        }
+    }
     PR_BARRIER();
+    if (SH && tid == 0 && pr_load4_sys(pr_ctl) == epoch) *s_abort = 1u;
     if (A.walk_first) {
         // the previous kernel — of any form — left the exchange of its last iteration to this one: its lists, and the records the launch
         // starts from published as the launch's iteration 0 (the first walk gathers like any other)
@@ -351,14 +407,22 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
         }
         // ---- the donor's whole record (swap_ev_ij!, :734-749) out of the ring, by the chain's 32 lanes ----
         const bool donor = valid && src != (uint32_t)cc;
+        uint32_t src_g = 0u;   // (SH: the donor in the population, for the rest of its record behind the objective)
         if (donor) {
-            const uint32_t src_g = src < (uint32_t)CT ? c0g + src : (uint32_t)gl[src - CT];
+            src_g = src < (uint32_t)CT ? c0g + src : (uint32_t)gl[src - CT];
             const uint4* g_ll = ring_rec(rel - 1) + (size_t)src_g * RW;
             const uint32_t tag = pr_tag32(epoch, rel - 1);
-            if (RW <= LPC) {
+            if constexpr (SH) {   // its value and parameters: in the own window, whoever owns it
+                for (int f = r2; f < RW; f += LPC) {
+                    if (!peer_granule(f)) continue;
+                    uint4 q = pr_load16_sys(g_ll + f);
+                    if (__builtin_expect(!p2p_ll_ok(q, tag), 0)) q = pt_wait_ll(W, g_ll + f, tag, t, cg);
+                    rin[f] = p2p_ll_double(q);
+                }
+            } else if (RW <= LPC) {
                 if (r2 < RW) {
                     uint4 q = pr_load16_sys(g_ll + r2);
-                    if (__builtin_expect(!p2p_ll_ok(q, tag), 0)) q = pt_wait_ll(W, g_ll + r2, tag, t, c);
+                    if (__builtin_expect(!p2p_ll_ok(q, tag), 0)) q = pt_wait_ll(W, g_ll + r2, tag, t, cg);
                     rin[r2] = p2p_ll_double(q);
                 }
             } else {
@@ -376,16 +440,16 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
                     const int f = r2 + LPC * j;
                     if (f < RW) {
                         uint4 q = qq[j];
-                        if (__builtin_expect(!p2p_ll_ok(q, tag), 0)) q = pt_wait_ll(W, g_ll + f, tag, t, c);   // (the gather validated the value only)
+                        if (__builtin_expect(!p2p_ll_ok(q, tag), 0)) q = pt_wait_ll(W, g_ll + f, tag, t, cg);   // (the gather validated the value only)
                         rin[f] = p2p_ll_double(q);
                     }
                 }
             }
         }
         if (chain_lane) s_cs[cc * PR_STW + CS_PARTNER] = (double)partner;
-        PR_BARRIER();   // B2: every read of the ring's last entry, of the walk's lists and slots is done
+        PR_BARRIER();   // B2: every read of the ring's last entry (SH: of the own window's), of the walk's lists and slots is done
         if (tid == 0) {
-            __hip_atomic_store(pr_progress + tile, pr_progress_word(epoch, rel), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!SH) __hip_atomic_store(pr_progress + tile, pr_progress_word(epoch, rel), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             *s_rngctr = 0u;   // (the last iteration's draws ended before B0; the next ones start behind B5)
         }
         // the next exchange's lists and header; the progress of the slowest tile, the abort word (consumed behind the objective)
@@ -397,7 +461,7 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
         uint32_t ctl_w = 0u, ok_w = 1u;
         if (wave == 2) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) if (lane + 64 * j < tiles) pw_[j] = pr_load4_sys(pr_progress + lane + 64 * j);
+            for (int j = 0; j < 8; ++j) if (lane + 64 * j < tiles_all) pw_[j] = pr_load4_sys(pr_progress + lane + 64 * j);
             if (lane == 0) { ctl_w = pr_load4_sys(pr_ctl); if (lists) ok_w = A.cone_ok[t - A.plan_t0]; }
         }
         // ---- settle iteration t - 1 (set_acceptRate!, :253-257; swap_ev_ij!'s set_eval!, :231-243) ----
@@ -410,14 +474,16 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
                 const double dv = rin[0];
                 if (dv < csb[CS_BESTP]) { bp = dv; bpid = (double)(t - 1); }
                 else { bp = csb[CS_BESTP]; bpid = csb[CS_BESTPID]; }
-                double* hx = s_xrow + cc * HW;
-                hx[H_VALUE] = dv; hx[H_PROB] = rin[1]; hx[H_CURR] = dv; hx[H_BEST] = bp; hx[H_BESTID] = bpid;
-                hx[H_EXCH] = (double)partner; hx[H_ACC] = 1.0; hx[H_STATUS] = rin[2];
-                if (HW > H_PARAMS + np + nm) hx[HW - 1] = 0.0;
+                if (!SH) {   // (SH: behind the objective, once the rest of the donor's record is there)
+                    double* hx = s_xrow + cc * HW;
+                    hx[H_VALUE] = dv; hx[H_PROB] = rin[1]; hx[H_CURR] = dv; hx[H_BEST] = bp; hx[H_BESTID] = bpid;
+                    hx[H_EXCH] = (double)partner; hx[H_ACC] = 1.0; hx[H_STATUS] = rin[2];
+                    if (HW > H_PARAMS + np + nm) hx[HW - 1] = 0.0;
+                }
             } else { nn += 1; na += (int)csb[CS_LACC]; }
             csb[CS_NNOEX] = (double)nn; csb[CS_NACC] = (double)na; csb[CS_BEST] = bp; csb[CS_BESTID] = bpid;
         }
-        if (valid && partner != 0) {
+        if (!SH && valid && partner != 0) {
             copy_strided(s_xrow + cc * HW + H_PARAMS, rin + 3, np + nm, r2, LPC);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
@@ -432,7 +498,7 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
         // an iteration lasts as long as its slowest tile's work, and that work does not shrink by being done earlier; EXPERIMENTS.md R5.6)
         {
             const CoopProp X{s_rec + (t & 1) * CT * RW, RW, s_rec + ((t + 1) & 1) * CT * RW, RW, s_theta, np, s_hrow, HW, s_rb, RBW, s_cs, PR_STW, s_lb, s_ub,
-                             (unsigned long long*)s_hrow + 2, A.err, A.seed, 0, N, A.batch_size, A.rb_tries, A.user_n, A.smpl_iters, A.scout_after, A.scout_gl};
+                             (unsigned long long*)s_hrow + 2, A.err, A.seed, goff, N, A.batch_size, A.rb_tries, A.user_n, A.smpl_iters, A.scout_after, A.scout_gl};
             coop_mysample<CT>(X, t, tile, tid, WG / 64, tid == 0, PtBarrier());
         }
         PR_BARRIER();   // B3: the proposals stand; the randomness block and the rows' region are free
@@ -469,12 +535,32 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
         else dense_tile_v<CT>(np, A.dense_nOt, A.dense_Bf, A.dense_Af, A.dense_A2f, (uint32_t)((unsigned char*)s_theta - lds), (uint32_t)((unsigned char*)s_part - lds), tid);
 #endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's LDS-DMA (lists, randomness) has landed
+        if constexpr (SH) {
+#ifdef SMM_TEST_HOOKS
+            if (A.slow_read && tile == A.slow_tile) { const unsigned long long w0 = wall_clock64(); while (wall_clock64() - w0 < (unsigned long long)A.slow_ticks) __builtin_amdgcn_s_sleep(8); }
+#endif
+            // the rest of the donor's record — prob, status, simulated moments — from its OWNER's window (equal shards of A.N chains)
+            if (donor) {
+                const int owner = (int)src_g / A.N;
+                const unsigned char* dwin = mine;
+#pragma unroll
+                for (int p = 0; p < P2P_MAXG; ++p) dwin = owner == p ? A.win[p] : dwin;
+                const uint4* g_ll = (const uint4*)(dwin + A.o_rec) + ((size_t)((rel - 1) & rmask) * A.Ng + src_g) * RW;
+                const uint32_t tag = pr_tag32(epoch, rel - 1);
+                for (int f = r2; f < RW; f += LPC) {
+                    if (peer_granule(f)) continue;
+                    uint4 q = pr_load16_sys(g_ll + f);
+                    if (__builtin_expect(!p2p_ll_ok(q, tag), 0)) q = pt_wait_ll(W, g_ll + f, tag, t, cg);
+                    rin[f] = p2p_ll_double(q);
+                }
+            }
+        }
         if (want_hdr) s_hdr[((t + 1) & 3) * 16 + lane] = nhdr;
         if (wave == 2) {
             uint32_t m = 0xfffu;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                if (lane + 64 * j < tiles) {
+                if (lane + 64 * j < tiles_all) {   // (SH: every rank's tiles, at rank * tiles + tile)
                     const int d = (int)(((pw_[j] >> 12) - epoch) << 12) >> 12;   // (20-bit epochs, wrap-safe: pl_min_progress)
                     m = min(m, d == 0 ? (pw_[j] & 0xfffu) : (d > 0 ? 0xfffu : 0u));
                 }
@@ -486,8 +572,24 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
                 if (ctl_w == epoch) *s_abort = 1u;
                 if (ok_w == 0u) pr_report(A.err, 3, t + 1, (int)c0g);
             }
+            if constexpr (SH) {   // somebody of this rank gave up: the other ranks need not wait out their time
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if (*(volatile unsigned*)s_abort && lane < A.G) {
+                    unsigned char* w = nullptr;
+#pragma unroll
+                    for (int p = 0; p < P2P_MAXG; ++p) w = lane == p ? A.win[p] : w;
+                    __hip_atomic_store((uint32_t*)(w + A.o_ctl), epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+            }
         }
-        PR_BARRIER();   // B4: the partial sums are in LDS; the lists have landed
+        PR_BARRIER();   // B4: the partial sums are in LDS; the lists have landed (SH: and every donor's record)
+        if (SH && tid == 0) {   // every read of the ring's last entry is done: to every rank's window, at this rank's tiles' words
+            const size_t po = (size_t)A.o_progress + 4 * (size_t)(A.rank * tiles + tile);
+            const uint32_t word = pr_progress_word(epoch, rel);
+#pragma unroll
+            for (int p = 0; p < P2P_MAXG; ++p)
+                if (p < A.G) __hip_atomic_store((uint32_t*)(A.win[p] + po), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
         unsigned long long ts4 = 0;
         if (A.ts && tid == 0) ts4 = wall_clock64();
         // ---- the moments of a chain (wave totals -> mean -> squared weighted deviation) by its 32 lanes (ObjExamples.jl:79-100) ----
@@ -576,7 +678,7 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
             if (status < 0) {   // :336-338
                 prob = 0.0; acc = false;
             } else {
-                if (!(value >= 0.0)) pr_report(A.err, ERRK_NEGATIVE, t, c);   // :341
+                if (!(value >= 0.0)) pr_report(A.err, ERRK_NEGATIVE, t, cg);   // :341
                 const double e = pr_exp(atun * (old - value));
                 prob = (e != e) ? e : (e < 1.0 ? e : 1.0);   // minimum([1.0,e]), NaN propagates (:344)
                 if (!isfinite(prob)) { prob = 0.0; acc = false; status = -1; }   // :350-353
@@ -592,6 +694,12 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
             else { bestv = bp; bestid = bpid; }
             csb[CS_SIGMA] = nsig; csb[CS_RATE] = rate; csb[CS_LACC] = acc ? 1.0 : 0.0; csb[CS_WASX] = 0.0; csb[CS_BEST] = bestv; csb[CS_BESTID] = bestid;
             csb[CS_BESTP] = bp; csb[CS_BESTPID] = bpid;   // best after t - 1: needed if iteration t gets exchanged
+            if (SH && partner != 0) {   // set_eval!(ci, ej) of swap_ev_ij! as a history record (:231-243): the donor's record is whole now
+                double* hx = s_xrow + cc * HW;
+                hx[H_VALUE] = old; hx[H_PROB] = rin[1]; hx[H_CURR] = old; hx[H_BEST] = bp; hx[H_BESTID] = bpid;
+                hx[H_EXCH] = (double)partner; hx[H_ACC] = 1.0; hx[H_STATUS] = rin[2];
+                if (HW > H_PARAMS + np + nm) hx[HW - 1] = 0.0;
+            }
             double* hr = s_hrow + cc * HW;
             hr[H_VALUE] = value; hr[H_PROB] = prob; hr[H_CURR] = currv; hr[H_BEST] = bestv; hr[H_BESTID] = bestid;
             hr[H_EXCH] = 0.0; hr[H_ACC] = acc ? 1.0 : 0.0; hr[H_STATUS] = (double)status;
@@ -609,14 +717,14 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
         // self-validating record of iteration t into the ring (write-through stores), granule by granule as it is put together ----
         if (t < t1) {
             if (__builtin_expect(rel > rmask && __hip_atomic_load(s_minprog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < rel - rmask, 0))
-                pl_wait_progress(W, pr_progress, s_minprog, rel - rmask, tiles, lane, t, (int)c0g);
+                pl_wait_progress(W, pr_progress, s_minprog, rel - rmask, tiles_all, lane, t, (int)c0g);
 #ifdef SMM_TEST_HOOKS
-            if (tile == A.slow_tile) { const unsigned long long w0 = wall_clock64(); while (wall_clock64() - w0 < (unsigned long long)A.slow_ticks) __builtin_amdgcn_s_sleep(8); }
+            if (tile == A.slow_tile && !(SH && A.slow_read)) { const unsigned long long w0 = wall_clock64(); while (wall_clock64() - w0 < (unsigned long long)A.slow_ticks) __builtin_amdgcn_s_sleep(8); }
 #endif
         }
         if (valid) {
             const bool acc = s_hrow[cc * HW + H_ACC] != 0.0;
-            uint4* g_ll = ring_rec(rel) + (size_t)c * RW;
+            uint4* g_ll = ring_rec(rel) + (size_t)cg * RW;
             const uint32_t tag = pr_tag32(epoch, rel);
             for (int f = r2; f < RW; f += LPC) {
                 double v;
@@ -630,6 +738,7 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
                     const unsigned long long a = __builtin_bit_cast(unsigned long long, v);
                     const p2p_u32x4 q = {(unsigned)a, tag, (unsigned)(a >> 32), tag};
                     asm volatile("global_store_dwordx4 %0, %1, off " PR_SC "\n\ts_nop 1" :: "v"(g_ll + f), "v"(q) : "memory");
+                    if (SH && peer_granule(f)) store_peers(rel, f, q);
                 }
             }
         }
@@ -642,11 +751,13 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
         if (valid) {
             copy_strided(s_hrow + cc * HW + H_PARAMS, s_theta + cc * np, np, r2, LPC);
             copy_strided(s_hrow + cc * HW + H_PARAMS + np, s_sm + cc * nm, nm, r2, LPC);
+            if (SH && partner != 0) copy_strided(s_xrow + cc * HW + H_PARAMS, rin + 3, np + nm, r2, LPC);
         }
         if (lists) gather(t, rel, t + 1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         if (valid) coop_store_n(A.hrec + ((size_t)(t - 1) * N + c) * HW, s_hrow + cc * HW, HW, r2, LPC);
+        if (SH && valid && partner != 0) coop_store_n(A.hrec + ((size_t)(t - 2) * N + c) * HW, s_xrow + cc * HW, HW, r2, LPC);
         if (t < t1 && rng_here) fetch_rb_dyn(t + 1);
         if (A.ts && tid == 0) {   // (slot 0: from the publication to the next iteration's B0 — rows, gather, the wait for the tile's other waves)
             s_ts[1] += ts1 - ts0; s_ts[2] += ts2 - ts1; s_ts[3] += ts3 - ts2; s_ts[4] += ts4 - ts3; s_ts[5] += ts4b - ts4; s_ts[6] += ts5 - ts4b; s_ts[7] = ts5;

@@ -95,6 +95,9 @@ struct UserObjective {
     std::vector<char> tile_code;           // k_chain_persist_tile with the user's map-reduce objective inside (smm_chain_persist_tile.hpp, SMM_TILE_USER)
     int tile_state = 0;                    // 0: not tried yet, 1: tile_code stands, -1: did not compile (tile_log)
     std::string tile_log;
+    std::vector<char> tile_sh_code;        // ... its form for a SHARD (SMM_TILE_SH as well): compiled only when a sharded context first wants it
+    int tile_sh_state = 0;
+    std::string tile_sh_log;
     bool rng = false;                      // SMM_USER_OBJECTIVE_RNG / SMM_USER_PARTIAL_RNG: takes the library's stream (smm_register_user_objective_rng)
 };
 // the device headers the persistent kernel is made of, as text: hiprtc compiles them together with the user's source
@@ -312,19 +315,24 @@ bool user_persist_compile(UserObjective& u) {   // (g_user_mutex held)
 }
 
 // k_chain_persist_tile with a user objective in its MAP-REDUCE form inside (smm_register_user_objective_lanes; SMM_TILE_USER in
-// smm_chain_persist_tile.hpp): the same recipe, on demand, once per registered objective
-bool user_tile_compile(UserObjective& u) {   // (g_user_mutex held)
-    if (u.tile_state != 0) return u.tile_state > 0;
-    u.tile_state = -1;
-    if (u.source.empty() || u.lanes == 0) { u.tile_log = "not the map-reduce form"; return false; }
+// smm_chain_persist_tile.hpp): the same recipe, on demand, once per registered objective — and once more as a shard's form (sh: SMM_TILE_SH),
+// only when a sharded context wants it
+bool user_tile_compile(UserObjective& u, const bool sh = false) {   // (g_user_mutex held)
+    int& state = sh ? u.tile_sh_state : u.tile_state;
+    std::string& tlog = sh ? u.tile_sh_log : u.tile_log;
+    std::vector<char>& code = sh ? u.tile_sh_code : u.tile_code;
+    if (state != 0) return state > 0;
+    state = -1;
+    if (u.source.empty() || u.lanes == 0) { tlog = "not the map-reduce form"; return false; }
     std::string err;
-    if (!g_rtc.load(err)) { u.tile_log = err; return false; }
+    if (!g_rtc.load(err)) { tlog = err; return false; }
     std::string tu = "#include <type_traits>\n#include <stdint.h>\n#include <math.h>\n";
     if (u.rng)
         tu += std::string(USER_RNG_API) + USER_PRELUDE_LANES_RNG + "#define SMM_USER_RNG 1\n";
     else
         tu += USER_PRELUDE_LANES;
     tu += u.source;
+    if (sh) tu += "\n#define SMM_TILE_SH 1";
     tu += "\n#define SMM_TILE_USER 1\n#include \"smmhip.h\"\n#include \"smm_rng.hpp\"\nusing namespace smm;\n#include \"smm_params.hpp\"\n"
           "#include \"smm_walk_lean.hpp\"\n#include \"smm_propose.hpp\"\n#include \"smm_chain.hpp\"\n#include \"smm_p2p.hpp\"\n#include \"smm_chain_norm.hpp\"\n"
           "#include \"smm_chain_persist.hpp\"\n#include \"smm_chain_persist_loc.hpp\"\n#include \"smm_chain_persist_tile.hpp\"\n";
@@ -332,7 +340,7 @@ bool user_tile_compile(UserObjective& u) {   // (g_user_mutex held)
     rtc_headers(names, texts);
     hiprtcProgram prog = nullptr;
     if (g_rtc.create(&prog, tu.c_str(), "smm_user_persist_tile.hip", (int)names.size(), texts.data(), names.data()) != HIPRTC_SUCCESS) {
-        u.tile_log = "hiprtcCreateProgram failed";
+        tlog = "hiprtcCreateProgram failed";
         return false;
     }
     const std::string nsd = "-DSMM_NSUMS=" + std::to_string(u.n_sums);
@@ -343,16 +351,16 @@ bool user_tile_compile(UserObjective& u) {   // (g_user_mutex held)
         g_rtc.log_size(prog, &n);
         std::string log(n, ' ');
         if (n) g_rtc.log(prog, &log[0]);
-        u.tile_log = log;
+        tlog = log;
         g_rtc.destroy(&prog);
         return false;
     }
     size_t cs = 0;
     g_rtc.code_size(prog, &cs);
-    u.tile_code.resize(cs);
-    g_rtc.code(prog, u.tile_code.data());
+    code.resize(cs);
+    g_rtc.code(prog, code.data());
     g_rtc.destroy(&prog);
-    u.tile_state = 1;
+    state = 1;
     return true;
 }
 
@@ -379,6 +387,7 @@ struct Hooks {
     int scout_after = SMM_SCOUT_AFTER, scout_gl = 16;   // the scouting form of mysample's late tries
     int a2a_cap = 0;               // a small capacity of the values form (0: a2a_capacity)
     int pr_ring_k = PR_K, pr_slow_tile = -1, pr_slow_ticks = 0;   // the persistent kernels' ring depth, a tile made slow by so many ticks
+    int pr_slow_read = 0;   // ... k_chain_persist_tile's shard form: slow while it still reads the ring's last entry (a donor's remote granules), not before its publication
     bool rows_win_check = false;   // the p2p rows resolution checked against the plain kernels
 };
 Hooks read_hooks() {
@@ -409,6 +418,7 @@ Hooks read_hooks() {
     if (const char* v = SMM_HOOK("SMMHIP_PR_RING")) { const int k = atoi(v); if (k == 2 || k == 4) H.pr_ring_k = k; }
     if (const char* v = SMM_HOOK("SMMHIP_PR_SLOW_TILE")) H.pr_slow_tile = atoi(v);
     if (const char* v = SMM_HOOK("SMMHIP_PR_SLOW_US")) H.pr_slow_ticks = 100 * atoi(v);
+    H.pr_slow_read = is(SMM_HOOK("SMMHIP_PR_SLOW_READ"), '1');
     H.rows_win_check = SMM_HOOK("SMMHIP_ROWS_WIN_CHECK") != nullptr;
     return H;
 }
@@ -629,6 +639,11 @@ int lay_kind(const Ctx* c) { const int k = obj_kind(c->obj); return k == 2 && c-
 size_t persist_tile_smem(const Ctx* c) {
     const KParams& P = c->P;
     return pt_layout(P.np, P.nm, P.RW, P.HW, P.RBW, lay_kind(c), P.dense_nOt, PT_CT * (c->u_lanes / 64) * c->u_nsums).total;
+}
+// tiles of one rank's launch of the chosen persistent kernel (k_chain_persist_loc: NORM_CT chains per tile, k_chain_persist_tile: PT_CT)
+int persist_tiles_rank(const Ctx* c) {
+    const int ct = c->F.persist == PERSIST_TILE ? PT_CT : NORM_CT;
+    return (c->P.N + ct - 1) / ct;
 }
 size_t norm_smem(const Ctx* c) {   // k_chain_iter_norm: [walk: chain slots | pair list] theta, partial sums, parked state
     const size_t b = (size_t)c->P.tile_off * sizeof(double) + norm_tile_doubles(c->P.np) * sizeof(double);
@@ -970,7 +985,7 @@ void p2p_enqueue(Ctx* c, int n_iters);
 unsigned long long p2p_agree_error(Ctx* c, unsigned long long e_local) {
     const KParams& P = c->P;
     const int G = P.p2p_G;
-    const PrWin WL = pr_win_layout(P.Ng, P.RW, G, (P.N + NORM_CT - 1) / NORM_CT);
+    const PrWin WL = pr_win_layout(P.Ng, P.RW, G, persist_tiles_rank(c));
     const uint32_t seq = c->pr_epoch;
     for (int r = 0; r < G; ++r)
         HIPCHK(hipMemcpy(P.p2p_win[r] + c->prw_off + WL.fin + 128 * (size_t)P.p2p_rank, &e_local, 8, hipMemcpyHostToDevice));
@@ -1223,7 +1238,7 @@ bool persist_sh_usable(const Ctx* c, int n_left) {
     // rank knows, or one rank would take the per-iteration kernels while its peers wait at the launches' start barrier.  The launch reports such a
     // state itself — kind 3 at its first iteration, smm_chain_persist_loc.hpp —, the ranks agree on the word and replay the step on the other forms)
     if (!(c->F.persist_sh && c->persist_on && !c->persist_broken && !c->in_repair && n_left >= 2 && c->p2p_mine)) return false;
-    if (c->p2p_ranks_here * ((c->P.N + NORM_CT - 1) / NORM_CT) > c->F.max_tiles) return false;   // (ranks sharing this device: not resident together)
+    if (c->p2p_ranks_here * persist_tiles_rank(c) > c->F.max_tiles) return false;   // (ranks sharing this device: not resident together)
     if (c->iter < 1 || !c->prev_open || c->exch_done || c->a2a_open) return false;
     if (c->p2p_current) return c->rec_external && (c->pending_ext || !exchange_active(c, c->iter));
     return !c->rec_external && (c->unresolved || !c->pending);
@@ -1265,7 +1280,7 @@ int launch_chain_persist(Ctx* c, int n_left) {
     ++c->pr_epoch;
     if ((c->pr_epoch & 0x7fu) == 0u) {   // the slot tags' epoch bits start over: nothing older may look current
         if (c->F.persist == PERSIST_LOC || c->F.persist == PERSIST_TILE) {   // (a shard zeroes its own window's ring: its peers store into it only behind the launch's start barrier)
-            const PrWin WL = pr_win_layout(c->P.Ng, c->P.RW, c->F.persist_sh ? c->P.p2p_G : 1, (c->P.N + NORM_CT - 1) / NORM_CT);   // (PT_CT == NORM_CT)
+            const PrWin WL = pr_win_layout(c->P.Ng, c->P.RW, c->F.persist_sh ? c->P.p2p_G : 1, persist_tiles_rank(c));
             unsigned char* base = c->F.persist_sh ? c->p2p_mine + c->prw_off : c->prw;
             HIPCHK(hipMemsetAsync(base + WL.slot, 0, WL.total - WL.slot, c->stream));
         } else {
@@ -1320,10 +1335,18 @@ int launch_chain_persist(Ctx* c, int n_left) {
     } else if (c->F.persist == PERSIST_TILE) {
         PersistTileArgs A{};
         const int tiles = (P.N + PT_CT - 1) / PT_CT;
-        const PrWin WL = pr_win_layout(P.Ng, P.RW, 1, tiles);
+        const bool sh = c->F.persist_sh;
+        const int G = sh ? P.p2p_G : 1;
+        const PrWin WL = pr_win_layout(P.Ng, P.RW, G, tiles);
         const int kind = obj_kind(c->obj);
         A.cone_hdr = P.cone_hdr; A.cone_pairs = P.cone_pairs; A.cone_gather = P.cone_gather; A.cone_ok = P.cone_ok;
-        A.self = c->prw; A.o_ctl = WL.ctl; A.o_progress = WL.progress; A.o_rec = WL.rec;
+        for (int r = 0; r < P2P_MAXG; ++r) A.win[r] = nullptr;
+        if (sh) {
+            for (int r = 0; r < G; ++r) A.win[r] = P.p2p_win[r] + c->prw_off;
+            A.self = c->p2p_mine + c->prw_off;
+        } else { A.win[0] = c->prw; A.self = c->prw; }
+        A.o_ctl = WL.ctl; A.o_arrive = WL.arrive; A.o_progress = WL.progress; A.o_rec = WL.rec;
+        A.G = G; A.rank = sh ? P.p2p_rank : 0; A.offset = sh ? P.offset : 0;
         A.cs = P.cs; A.rec_in = c->rec[c->cur]; A.rec_out = c->rec[c->cur ^ 1]; A.vals_out = P.vals_out; A.slot8_out = P.slot8_out; A.walk_flags = P.walk_flags;
         A.hrec = P.hrec; A.err = P.err; A.ts = P.ts;
         A.Z = P.Z; A.lb = P.lb; A.ub = P.ub; A.mom = P.mom; A.w = P.w; A.objp = P.objp; A.dense_Bf = P.dense_Bf; A.dense_Af = P.dense_Af; A.dense_A2f = P.dense_A2f;
@@ -1332,7 +1355,7 @@ int launch_chain_persist(Ctx* c, int n_left) {
         A.batch_size = P.batch_size; A.failbox = (P.obj == SMM_OBJ_NORM_FAILBOX && P.objp) ? 1 : 0;
         A.plan_t0 = P.plan_t0; A.exch_from = c->exchange_from; A.sigma_update_steps = P.sigma_update_steps; A.smpl_iters = P.smpl_iters; A.t0 = t0; A.t1 = t1;
         A.rb_t0 = P.rb_t0; A.rb_tries = P.rb_tries; A.user_n = P.user_n;
-        A.ring_k = c->H.pr_ring_k; A.slow_tile = c->H.pr_slow_tile; A.slow_ticks = c->H.pr_slow_ticks; A.walk_first = c->unresolved ? 1 : 0;
+        A.ring_k = c->H.pr_ring_k; A.slow_tile = c->H.pr_slow_tile; A.slow_ticks = c->H.pr_slow_ticks; A.slow_read = c->H.pr_slow_read; A.walk_first = c->unresolved ? 1 : 0;
         A.unit_sh = P.lean_unit == 16 ? 4 : (P.lean_unit == 8 ? 3 : 2); A.scout_after = P.scout_after; A.scout_gl = P.scout_gl;
         A.epoch = c->pr_epoch; A.sigma_adjust_by = P.sigma_adjust_by; A.thr = P.mi_value; A.seed = P.seed; A.tmo = tmo; A.mi_g = P.min_improve_g;
         const dim3 grid(tiles), block(WG);
@@ -1343,7 +1366,8 @@ int launch_chain_persist(Ctx* c, int n_left) {
             void* args[] = {(void*)&A};
             if (c->kev0) HIPCHK(hipExtModuleLaunchKernel(c->utfn, grid.x * (unsigned)WG, 1, 1, WG, 1, 1, smem, c->stream, args, nullptr, c->kev0, c->kev1, 0));
             else HIPCHK(hipModuleLaunchKernel(c->utfn, grid.x, 1, 1, WG, 1, 1, (unsigned)smem, c->stream, args, nullptr));
-        } else if (P.mi_pct) { if (kind == 2) go(k_chain_persist_tile<2, true>); else go(k_chain_persist_tile<1, true>); }
+        } else if (sh) { if (kind == 2) go(k_chain_persist_tile<2, false, true>); else go(k_chain_persist_tile<1, false, true>); }
+        else if (P.mi_pct) { if (kind == 2) go(k_chain_persist_tile<2, true>); else go(k_chain_persist_tile<1, true>); }
         else if (kind == 2) go(k_chain_persist_tile<2>); else go(k_chain_persist_tile<1>);
     } else if (c->F.persist == PERSIST_GEN) {
         PersistGenArgs A{};
@@ -1712,6 +1736,13 @@ Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
                            mi_ok && minus && K <= XLDS_MAX && Ng <= XLDS_MAX && !c->deep_plan && !chol && P.dbg == 0 && !H.persist_off &&
                            !H.persist_tile_off && P.RW <= PT_LPC * PT_NJ && (tile_kind != 2 || N % PT_CT == 0) && (N + PT_CT - 1) / PT_CT <= 2 * n_cus &&
                            persist_tile_smem(c) <= (size_t)160 * 1024;
+    // ... and as a shard of a sharded run (smm_bgp_p2p_step; SH of smm_chain_persist_tile.hpp): equal shards of whole tiles, the LDS plan
+    // (N_global <= 8192: every rank's progress words fit wave 2's 512 lanes' worth), one threshold >= 0 (or NaN) for all chains
+    const bool want_tile_sh = (tile_kind == 1 || tile_kind == 2 || user_tile) && !(F.norm_fast && np <= 2 && ns <= WG * PR_ZR) &&
+                              N < Ng && N > 0 && Ng % N == 0 && P.offset % N == 0 && Ng / N <= P2P_MAXG && N % PT_CT == 0 && lds &&
+                              Ng <= XLDS_MAX && K <= XLDS_MAX && P.mi_uniform && !(P.mi_value < 0.0) && !P.mi_pct && minus && !c->deep_plan && !chol &&
+                              P.dbg == 0 && !H.persist_off && !H.persist_tile_off && P.RW <= PT_LPC * PT_NJ && N / PT_CT <= 2 * n_cus &&
+                              persist_tile_smem(c) <= (size_t)160 * 1024;
     const size_t persist_tiles = (want_gen || want_gen_small || want_user) ? (size_t)N / PG_CT : (size_t)(N + NORM_CT - 1) / NORM_CT;
     // large single shards of objfunc_norm (C3 on one GPU): the narrow chain kernel's tiles walk their own, locally numbered cones
     // (smm_cone_big.hpp) instead of waiting for the one-workgroup resolution between two launches
@@ -1730,7 +1761,7 @@ Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
     const size_t plan_iter = (want_cone_big ? (size_t)(N / NORM_CT) * (cone_iter + CONE_GCAP * 2) + cone_big_scratch_words(Ng, K) * 4 : 0) + (size_t)K * 36 +
                              (big ? BigPlanScratch::words(Ng, K) * 4 + (size_t)(XROWS_MAX + 1) * XWG * 4 : 0) +
                              (size_t)lean_walk_Kp(K) * 4 + 1024 + (want_cone ? (size_t)(N / cone_ct) * cone_iter + 4 : 0) +
-                             ((want_loc || want_sh || want_tile) ? persist_tiles * (cone_iter + CONE_GCAP * 2) + 4 : 0) +
+                             ((want_loc || want_sh || want_tile || want_tile_sh) ? persist_tiles * (cone_iter + CONE_GCAP * 2) + 4 : 0) +
                              ((want_sh && big) ? cone_big_scratch_words(Ng, K) * 4 : 0) +
                              (want_gen ? persist_tiles * (CONE_GCAP * 2) : 0) +
                              ((want_gen_small || want_user) ? persist_tiles * (cone_iter + CONE_GCAP * 2) + 4 : 0);
@@ -1775,6 +1806,7 @@ Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
             F.persist = PERSIST_TILE; F.persist_wide = true;
             F.defer_resolve = !F.inline_walk;   // (the exchange of an iteration is left to the next launch: it may be this kernel's)
         }
+        if (want_tile_sh && F.persist == PERSIST_NONE) { F.persist = PERSIST_TILE; F.persist_wide = true; F.persist_sh = true; }
     }
     // ... all of its tiles resident at once, or it is not taken (per_cu 0 also where a user objective's kernel did not compile)
     if (F.persist != PERSIST_NONE && dev.per_cu >= 0) {
@@ -1833,11 +1865,12 @@ int persist_occupancy(Ctx* c, const Forms& F, int objective_id) {
             {
                 std::lock_guard<std::mutex> lock(g_user_mutex);
                 UserObjective& u = g_user_objectives[objective_id - SMM_OBJ_USER_BASE];
-                if (!user_tile_compile(u)) {
-                    if (getenv("SMMHIP_VERBOSE")) fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n", u.tile_log.c_str());
+                if (!user_tile_compile(u, F.persist_sh)) {
+                    if (getenv("SMMHIP_VERBOSE"))
+                        fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n", (F.persist_sh ? u.tile_sh_log : u.tile_log).c_str());
                     return 0;
                 }
-                HIPCHK(hipModuleLoadData(&c->utmod, u.tile_code.data()));
+                HIPCHK(hipModuleLoadData(&c->utmod, (F.persist_sh ? u.tile_sh_code : u.tile_code).data()));
             }
             HIPCHK(hipModuleGetFunction(&c->utfn, c->utmod, "smm_user_persist_tile_kernel"));
             (void)hipFuncSetAttribute((const void*)c->utfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);   // (a module's function: not every runtime takes it this way; the launch asks for what it needs)
@@ -1845,7 +1878,8 @@ int persist_occupancy(Ctx* c, const Forms& F, int objective_id) {
             HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->utfn, WG, smem));
         } else {
             const int kind = obj_kind(c->obj);
-            const void* fn = P.mi_pct ? (kind == 2 ? (const void*)k_chain_persist_tile<2, true> : (const void*)k_chain_persist_tile<1, true>)
+            const void* fn = F.persist_sh ? (kind == 2 ? (const void*)k_chain_persist_tile<2, false, true> : (const void*)k_chain_persist_tile<1, false, true>)
+                           : P.mi_pct ? (kind == 2 ? (const void*)k_chain_persist_tile<2, true> : (const void*)k_chain_persist_tile<1, true>)
                                       : (kind == 2 ? (const void*)k_chain_persist_tile<2> : (const void*)k_chain_persist_tile<1>);
             HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
             HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, WG, smem));
@@ -2637,7 +2671,7 @@ int smm_bgp_p2p_init(void* ctx, void* ipc_handle_out, void** window_dev_out) {
             size_t total = L.total;
             if (c->F.persist_sh) {
                 c->prw_off = (L.total + 255) & ~(size_t)255;
-                total = c->prw_off + pr_win_layout(P.Ng, P.RW, c->a2a_G, (P.N + NORM_CT - 1) / NORM_CT).total;
+                total = c->prw_off + pr_win_layout(P.Ng, P.RW, c->a2a_G, persist_tiles_rank(c)).total;   // (the ring: RW granules of this context's records)
             }
             void* w = nullptr;
             HIPCHK(hipMalloc(&w, total));
@@ -3193,7 +3227,9 @@ int smm_describe(void* ctx, char* out, int32_t cap) {
     const char* pers = c->F.persist == PERSIST_NONE ? "none" : c->F.persist == PERSIST_LOC ? (c->F.persist_sh ? (c->F.persist_sh_big ? (c->F.persist_wide ? "loc_wide_shard_bigplan" : "loc_shard_bigplan")
                                                                                                     : (c->F.persist_wide ? "loc_wide_shard" : "loc_shard"))
                                                                               : (c->F.persist_wide ? "loc_wide" : "loc"))
-                     : c->F.persist == PERSIST_TILE ? (c->utfn ? "tile_user" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2" : "tile_dense") : "tile_sim") : c->F.persist_user ? "gen_user" : "gen";
+                     : c->F.persist == PERSIST_TILE ? (c->F.persist_sh ? (c->utfn ? "tile_user_shard" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2_shard" : "tile_dense_shard") : "tile_sim_shard")
+                                                                        : (c->utfn ? "tile_user" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2" : "tile_dense") : "tile_sim"))
+                     : c->F.persist_user ? "gen_user" : "gen";
     snprintf(out, (size_t)cap, "chain=%s walk=%s exchange=%s persistent=%s plan=%s window=%d", chain, walk, xk[c->F.xk], pers,
              c->F.plan == PLAN_BIG ? (c->F.plan_ahead ? "big_ahead" : "big") : c->F.plan == PLAN_LDS ? "lds" : "none", c->F.plan_cap);
     return SMM_OK;
