@@ -375,6 +375,48 @@ int  smm_eval_batch_noseed(void* ctx, const double* params, int32_t M, uint64_t 
                            double* value, double* sim_moments, int8_t* status);
 
 int  smm_get_history(void* ctx, int32_t t0, int32_t t1, smm_history_t* out);
+
+/* Chain summaries computed on the device from the history it holds: params / mean / median / CI / best / summary of the reference
+ * (AlgoBGP.jl:117-206, 541-550) for every LOCAL chain of the context (a shard reports its own N chains; partner ids are global),
+ * over the 0-based iterations [t0, t1), 0 <= t0 <= t1 <= completed iterations.  accepted_only != 0 selects the iterations with
+ * accepted != 0 (params(c), AlgoBGP.jl:120-131), otherwise every iteration of the window.  Caller-allocated; any pointer may be NULL
+ * (not returned; mean, median and quantile all NULL: no column is compacted).  The call is read-only (it settles, flushes and
+ * synchronises like smm_get_history, and changes no state, history or generator).  Scratch: allocated by the first call, kept in the
+ * ctx, freed with it — min(N x maxiter x (8 np + 4), max(256 MiB, 12 x maxiter)) bytes (a context holding more is reduced in
+ * batches of chains and, past that, of parameters, each batch reading the window once more), plus the call's results
+ * ((N + n_probs + (2 + n_probs) np N) x 8 + 16 N bytes, grown to the largest call's).  SMM_ERR_INVALID_ARG: NULL ctx or out, a bad
+ * window, n_probs < 0, probs NULL with n_probs > 0, a prob outside [0, 1] or NaN, quantile without probs.
+ *
+ * Numerical contract — NumPy's readers (np.mean, np.median, np.quantile(method="linear"), np.argmin, np.bincount(...).argmax() on
+ * the compacted column, as the Python host layer computes them), NOT Julia's Statistics, which sums differently.  Every operation
+ * rounded on its own (no fma).  x = the selected draws of one parameter in iteration order, m = count, s = x sorted by the IEEE
+ * total order (-0 before +0):
+ *   pw(x, lo, n): n < 8: r = 0.0, r = r + x[lo+i] for i = 0..n-1;  n <= 128: r[k] = x[lo+k] (k < 8), r[k] = r[k] + x[lo+i+k] for
+ *                 i = 8, 16, .. < n - n%8; s = ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then s = s + x[lo+i] for the n%8 last;
+ *                 otherwise n2 = n/2 - (n/2)%8: pw(x, lo, n2) + pw(x, lo+n2, n-n2)          (numpy's pairwise sum)
+ *   mean       = S / m with S = 0.0, S = S + pw(x, c, min(8192, m-c)) for c = 0, 8192, ..
+ *   median     = the mean above of the middle draw(s): (0.0 + s[m/2]) / 1 for odd m, ((0.0 + s[m/2-1]) + s[m/2]) / 2 for even m
+ *   quantile p = h = (m-1) p; h >= m-1: a = b = s[m-1], g = h + 1;  else j = floor(h), a = s[j], b = s[j+1], g = h - j;
+ *                d = b - a; g >= 0.5 ? b - d (1 - g) : a + d g                              (numpy's _lerp, indexes clipped as numpy)
+ *   a NaN among the selected draws: mean, median and every quantile NaN (count still reported); m == 0: NaN.
+ *   best       = the first NaN value of the window if any, else its first minimum (over EVERY iteration of the window, as best(c));
+ *                best_iter its 1-based iteration (t + 1); an empty window: NaN and 0.
+ *   most_exchanged_with = the most frequent non-zero partner of the window, ties to the smallest id; 0 = no exchange.
+ * numpy selects order statistics with a partition that does not order -0 and +0: its results and these can differ in the sign of
+ * a zero, nowhere else. */
+typedef struct {            /* caller-allocated; any pointer may be NULL = not computed                                        */
+    int32_t* count;         /* [N]            draws selected in the window                                                     */
+    double*  mean;          /* [np][N]                                                                                         */
+    double*  median;        /* [np][N]                                                                                         */
+    double*  quantile;      /* [n_probs][np][N]                                                                                */
+    double*  best_value;    /* [N]   findmin of value over the window (all iterations, as best(c))                             */
+    int32_t* best_iter;     /* [N]   1-based iteration of it                                                                   */
+    int32_t* n_exchanged;   /* [N]   iterations with exchanged != 0                                                            */
+    int32_t* most_exchanged_with; /* [N] mode of the non-zero partners (1-based global id), 0 = none                           */
+} smm_chain_stats_t;
+int  smm_get_chain_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only,
+                         const double* probs, int32_t n_probs, smm_chain_stats_t* out);
+
 int  smm_get_state(void* ctx, smm_state_t* out);
 /* smm_set_state is also the recovery from a hard error (AlgoBGP.jl:341,409): the context steps again from the uploaded state.  A failure that
  * no entry point has handed to the caller yet — raised on the device by asynchronous steps nobody synchronised; the state readers do not

@@ -17,6 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
+export hip_chain_stats
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
 const ABI_VERSION = 3
@@ -90,6 +91,17 @@ struct SmmHistory
     exchanged::Ptr{Int32}
     accepted::Ptr{UInt8}
     status::Ptr{Int8}
+end
+
+struct SmmChainStats
+    count::Ptr{Int32}
+    mean::Ptr{Cdouble}
+    median::Ptr{Cdouble}
+    quantile::Ptr{Cdouble}
+    best_value::Ptr{Cdouble}
+    best_iter::Ptr{Int32}
+    n_exchanged::Ptr{Int32}
+    most_exchanged_with::Ptr{Int32}
 end
 
 struct SmmState
@@ -301,6 +313,29 @@ function hip_history(h::HipBGP, t0::Integer, t1::Integer)
     end
     return (value = value, prob = prob, curr_val = curr, best_val = best, params = pars, sim_moments = simm,
             best_id = bid, exchanged = exch, accepted = acc, status = st)
+end
+
+"""
+    hip_chain_stats(h, t0, t1; accepted_only = true, probs = Float64[]) -> NamedTuple
+
+Summaries of every chain of the context over iterations `t0+1 .. t1`, reduced on the device without downloading the history
+(`smm_get_chain_stats`): `count[chain]`, `mean[chain, k]`, `median[chain, k]`, `quantile[chain, k, p]`, `best_value[chain]`,
+`best_iter[chain]` (1-based iteration), `n_exchanged[chain]`, `most_exchanged_with[chain]` (1-based global id, 0 = none).
+`accepted_only` selects the accepted draws, as `params(c)`.  The numbers are NumPy's (include/smmhip.h), not `Statistics`'.
+"""
+function hip_chain_stats(h::HipBGP, t0::Integer, t1::Integer; accepted_only::Bool = true, probs::Vector{Float64} = Float64[])
+    N, np, nq = h.N, h.np, length(probs)
+    count = Vector{Int32}(undef, N); mean = Matrix{Float64}(undef, N, np); median = similar(mean)
+    quant = Array{Float64}(undef, N, np, nq); bestv = Vector{Float64}(undef, N); besti = Vector{Int32}(undef, N)
+    nex = Vector{Int32}(undef, N); most = Vector{Int32}(undef, N)
+    GC.@preserve count mean median quant bestv besti nex most probs begin
+        cs = SmmChainStats(pointer(count), pointer(mean), pointer(median), nq > 0 ? pointer(quant) : Ptr{Cdouble}(C_NULL),
+                           pointer(bestv), pointer(besti), pointer(nex), pointer(most))
+        check(h.ctx, ccall(sym(:smm_get_chain_stats), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Cint, Ref{SmmChainStats}),
+                           h.ctx, t0, t1, accepted_only ? 1 : 0, nq > 0 ? pointer(probs) : Ptr{Cdouble}(C_NULL), nq, cs))
+    end
+    return (count = count, mean = mean, median = median, quantile = quant, best_value = bestv, best_iter = besti,
+            n_exchanged = nex, most_exchanged_with = most)
 end
 
 "per-chain state: what `save` / `readMalgo` / `restart!` need besides the history (AlgoAbstract.jl:83-102)"

@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -305,6 +305,20 @@ end
 function getproperty(algo::MAlgoBGPHip, s::Symbol)
     s === :chains && return sync_chains!(algo)
     return getfield(algo, s)
+end
+
+"""
+    chain_stats(algo; t0 = 0, t1 = nothing, accepted_only = true, probs = Float64[]) -> NamedTuple
+
+Per-chain count, mean, median, quantiles at `probs`, best value and iteration, exchanges and most frequent partner over
+iterations `t0+1 .. t1` (default: every completed one), computed on the device from the history it holds — no download, no sync of
+the chains (`SMMHip.hip_chain_stats`).  NumPy's summation and quantile rule (include/smmhip.h), so the numbers can differ in the
+last bits from `mean`, `median` and `CI` of the synced chains, which stay the reference's (`Statistics`).
+"""
+function chain_stats(algo::MAlgoBGPHip; t0::Integer = 0, t1 = nothing, accepted_only::Bool = true, probs::Vector{Float64} = Float64[])
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    return SMMHip.hip_chain_stats(hip, t0, t1 === nothing ? SMMHip.hip_iter(hip) : t1; accepted_only = accepted_only, probs = probs)
 end
 
 "`summary(m::MAlgoBGP)` (AlgoBGP.jl:541-550) on the synced chains"

@@ -95,6 +95,13 @@ class smm_state_t(C.Structure):
     ]
 
 
+class smm_chain_stats_t(C.Structure):
+    _fields_ = [
+        ("count", c_int32_p), ("mean", c_double_p), ("median", c_double_p), ("quantile", c_double_p),
+        ("best_value", c_double_p), ("best_iter", c_int32_p), ("n_exchanged", c_int32_p), ("most_exchanged_with", c_int32_p),
+    ]
+
+
 class smm_timing_t(C.Structure):
     _fields_ = [
         ("step_ms", C.c_double), ("iter_kernel_ms", C.c_double), ("exch_kernel_ms", C.c_double),
@@ -135,6 +142,8 @@ SYMBOLS = [
     ("smm_eval_batch", C.c_int, [C.c_void_p, c_double_p, C.c_int32, c_double_p, c_double_p, c_int8_p]),
     ("smm_eval_batch_noseed", C.c_int, [C.c_void_p, c_double_p, C.c_int32, C.c_uint64, c_double_p, c_double_p, c_int8_p]),
     ("smm_get_history", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(smm_history_t)]),
+    ("smm_get_chain_stats", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32,
+                                      C.POINTER(smm_chain_stats_t)]),
     ("smm_get_state", C.c_int, [C.c_void_p, C.POINTER(smm_state_t)]),
     ("smm_set_state", C.c_int, [C.c_void_p, C.POINTER(smm_state_t), C.POINTER(smm_history_t)]),
     ("smm_get_timing", C.c_int, [C.c_void_p, C.POINTER(smm_timing_t)]),

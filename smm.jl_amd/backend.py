@@ -242,6 +242,24 @@ class BGPContext:
         self._check(self._fn("get_history")(self._ctx, t0, t1, C.byref(hs)))
         return hb
 
+    def chain_stats(self, t0=0, t1=None, accepted_only=True, probs=()):
+        """summaries of every local chain over iterations [t0, t1), reduced on the device (smm_get_chain_stats, include/smmhip.h):
+        a dict of numpy arrays count [N], mean / median [np][N], quantile [len(probs)][np][N], best_value, best_iter, n_exchanged,
+        most_exchanged_with [N].  accepted_only: the accepted draws only, as params(c)"""
+        t1 = self.state().iter if t1 is None else t1
+        p = A.f64(probs).reshape(-1)
+        N, np_ = self.N, self.np
+        r = dict(count=np.empty(N, np.int32), mean=np.empty((np_, N)), median=np.empty((np_, N)), quantile=np.empty((len(p), np_, N)),
+                 best_value=np.empty(N), best_iter=np.empty(N, np.int32), n_exchanged=np.empty(N, np.int32),
+                 most_exchanged_with=np.empty(N, np.int32))
+        s = A.smm_chain_stats_t()
+        for f, t in A.smm_chain_stats_t._fields_:
+            if f != "quantile" or len(p):
+                setattr(s, f, r[f].ctypes.data_as(t))
+        self._check(self._fn("get_chain_stats")(self._ctx, int(t0), int(t1), int(bool(accepted_only)), A.dptr(p) if len(p) else None,
+                                                len(p), C.byref(s)))
+        return r
+
     def state(self):
         sb = A.StateBuffers(self.N, self.np, self.nm)
         ss = sb.struct()

@@ -66,6 +66,7 @@ using namespace smm;
 #include "smm_lookahead.hpp"
 #include "smm_exchange.hpp"
 #include "smm_cone_big.hpp"
+#include "smm_stats.hpp"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -554,6 +555,12 @@ struct Ctx {
     int failed = 0;             // a hard device error (AlgoBGP.jl:341,409) stopped the run at iteration `iter`: sticky until smm_set_state
     // the p2p form of the sharded iteration (smm_p2p.hpp)
     unsigned char* p2p_mine = nullptr;         // this rank's window (null: smm_bgp_p2p_init not called)
+    // smm_get_chain_stats: scratch for the compacted columns (allocated by the first call, bounded: chain_stats_scratch_bytes) and the
+    // results of a call (grown to the largest call's)
+    void* st_scr = nullptr;
+    size_t st_scr_bytes = 0;
+    void* st_res = nullptr;
+    size_t st_res_bytes = 0;
     void* p2p_opened[P2P_MAXG] = {};           // peers' windows opened through HIP IPC (closed with the context)
     unsigned p2p_attached = 0;                 // bit r: rank r's window is known
     unsigned long long p2p_seq = 0;            // pushes so far (every rank counts the same)
@@ -2027,6 +2034,8 @@ void smm_ctx_destroy(void* ctx) {
     for (void* p : c->allocs) (void)hipFree(p);
     for (void* w : c->p2p_opened) if (w) (void)hipIpcCloseMemHandle(w);
     if (c->p2p_mine) (void)hipFree(c->p2p_mine);
+    if (c->st_scr) (void)hipFree(c->st_scr);
+    if (c->st_res) (void)hipFree(c->st_res);
     if (c->umod) (void)hipModuleUnload(c->umod);
     if (c->upmod) (void)hipModuleUnload(c->upmod);
     if (c->utmod) (void)hipModuleUnload(c->utmod);
@@ -3068,6 +3077,114 @@ int smm_get_history(void* ctx, int32_t t0, int32_t t1, smm_history_t* out) {
                     for (size_t k = 0; k < nm; ++k) out->sim_moments[((size_t)(t - t0) * nm + k) * N + i] = h[H_PARAMS + np + k];
             }
         }
+    } catch (const std::string& m) {
+        return fail(c, SMM_ERR_HIP, m);
+    }
+    return SMM_OK;
+}
+
+// scratch of smm_get_chain_stats: the compacted columns of every chain for the context's whole capacity, at most STATS_SCRATCH_CAP
+// (but always one parameter column + one partner column of maxiter draws: 12 x maxiter bytes)
+static constexpr size_t STATS_SCRATCH_CAP = (size_t)256 << 20;
+static size_t chain_stats_scratch_bytes(const KParams& P) {
+    const size_t T = (size_t)P.T, all = (size_t)P.N * T * (8 * (size_t)P.np + 4);
+    return std::min(all, std::max(STATS_SCRATCH_CAP, 12 * T));
+}
+
+// mean / median / CI / best / summary of AlgoBGP.jl:117-206 for every local chain, reduced where the history lives (smm_stats.hpp)
+int smm_get_chain_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, const double* probs, int32_t n_probs,
+                        smm_chain_stats_t* out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !out) return SMM_ERR_INVALID_ARG;
+    if (n_probs < 0 || (n_probs > 0 && !probs)) return fail(c, SMM_ERR_INVALID_ARG, "n_probs < 0, or probs NULL with n_probs > 0");
+    if (out->quantile && n_probs == 0) return fail(c, SMM_ERR_INVALID_ARG, "quantile requested without probs");
+    for (int p = 0; p < n_probs; ++p)
+        if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) return fail(c, SMM_ERR_INVALID_ARG, "probs must lie in [0, 1]");
+    try {
+        HIPCHK(hipSetDevice(c->device));
+        settle_persist(c);
+        flush(c);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (t0 < 0 || t1 < t0 || t1 > c->iter)
+            return fail(c, SMM_ERR_INVALID_ARG, "window must satisfy 0 <= t0 <= t1 <= completed iterations");
+        const KParams& P = c->P;
+        const size_t N = P.N, np = P.np, nq = n_probs;
+        const int n = t1 - t0;
+        // results: doubles bestv[N], probs[nq], mean[np][N], median[np][N], quant[nq][np][N]; then ints count, nex, besti, most [N] each
+        const size_t nd = N + nq + 2 * np * N + nq * np * N, ni = 4 * N;
+        const size_t rbytes = nd * 8 + ni * 4;
+        if (rbytes > c->st_res_bytes) {
+            if (c->st_res) { HIPCHK(hipFree(c->st_res)); c->st_res = nullptr; c->st_res_bytes = 0; }
+            HIPCHK(hipMalloc(&c->st_res, rbytes));
+            c->st_res_bytes = rbytes;
+        }
+        double* d_bestv = (double*)c->st_res;
+        double* d_probs = d_bestv + N;
+        double* d_mean = d_probs + nq;
+        double* d_median = d_mean + np * N;
+        double* d_quant = d_median + np * N;
+        int* d_count = (int*)(d_quant + nq * np * N);
+        int* d_nex = d_count + N;
+        int* d_besti = d_nex + N;
+        int* d_most = d_besti + N;
+        std::vector<char> hres(rbytes);
+        if (n == 0) {   // nothing selected, nothing to find
+            double* hd = (double*)hres.data();
+            for (size_t i = 0; i < nd; ++i) hd[i] = NAN;
+            memset(hres.data() + nd * 8, 0, ni * 4);
+        } else {
+            if (!c->st_scr) {
+                c->st_scr_bytes = chain_stats_scratch_bytes(P);
+                HIPCHK(hipMalloc(&c->st_scr, c->st_scr_bytes));
+            }
+            if (nq) HIPCHK(hipMemcpyAsync(d_probs, probs, nq * 8, hipMemcpyHostToDevice, c->stream));
+            const bool cols = out->mean || out->median || out->quantile;
+            const size_t cap = c->st_scr_bytes;
+            auto per_chain = [&](size_t kb) { return (size_t)n * (8 * kb + 4); };
+            size_t kb = cols ? np : 0;
+            while (kb > 1 && per_chain(kb) > cap) kb = (kb + 1) / 2;
+            const int Nb = (int)std::min(N, cap / per_chain(kb));
+            const int lds_n = std::min(STATS_LDS_N, 1 << (int)ceil(log2((double)std::max(n, 2))));
+            const int bins = std::min(STATS_MODE_BINS, std::max(P.Ng, 64));
+            HIPCHK(hipFuncSetAttribute((const void*)k_stats_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+            HIPCHK(hipFuncSetAttribute((const void*)k_stats_mode, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_MODE_BINS * 4));
+            for (size_t k0 = 0; k0 < std::max(np, (size_t)1); k0 += std::max(kb, (size_t)1)) {
+                const int kbb = (int)std::min(kb, np - k0);
+                const int first = k0 == 0;
+                if (!first && !cols) break;
+                for (int c0 = 0; c0 < (int)N; c0 += Nb) {
+                    const int nb = std::min(Nb, (int)N - c0);
+                    double* col = (double*)c->st_scr;
+                    int* pcol = (int*)(col + (size_t)kbb * nb * n);
+                    hipLaunchKernelGGL(k_stats_gather, dim3(nb), dim3(STATS_WG), 0, c->stream, (const double*)P.hrec, (int)N, P.HW, t0, n,
+                                       (int)(accepted_only != 0), c0, nb, (int)k0, kbb, first, col, pcol, d_count, d_nex, d_bestv, d_besti);
+                    HIPCHK(hipGetLastError());
+                    if (kbb > 0) {
+                        hipLaunchKernelGGL(k_stats_column, dim3(nb, kbb), dim3(STATS_WG), (size_t)lds_n * 8, c->stream, (const double*)col, n,
+                                           (int)N, c0, nb, (int)k0, (const int*)d_count, (const double*)d_probs, (int)nq, (int)np, d_mean,
+                                           d_median, d_quant);
+                        HIPCHK(hipGetLastError());
+                    }
+                    if (first) {
+                        hipLaunchKernelGGL(k_stats_mode, dim3(nb), dim3(STATS_WG), (size_t)bins * 4, c->stream, (const int*)pcol, n, c0, bins,
+                                           (const int*)d_nex, d_most);
+                        HIPCHK(hipGetLastError());
+                    }
+                }
+            }
+            HIPCHK(hipMemcpyAsync(hres.data(), c->st_res, rbytes, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+        const double* hd = (const double*)hres.data();
+        const int* hi = (const int*)(hres.data() + nd * 8);
+        if (out->best_value) memcpy(out->best_value, hd, N * 8);
+        if (out->mean) memcpy(out->mean, hd + N + nq, np * N * 8);
+        if (out->median) memcpy(out->median, hd + N + nq + np * N, np * N * 8);
+        if (out->quantile) memcpy(out->quantile, hd + N + nq + 2 * np * N, nq * np * N * 8);
+        if (out->count) memcpy(out->count, hi, N * 4);
+        if (out->n_exchanged) memcpy(out->n_exchanged, hi + N, N * 4);
+        if (out->best_iter) memcpy(out->best_iter, hi + 2 * N, N * 4);
+        if (out->most_exchanged_with) memcpy(out->most_exchanged_with, hi + 3 * N, N * 4);
     } catch (const std::string& m) {
         return fail(c, SMM_ERR_HIP, m);
     }

@@ -361,23 +361,44 @@ def history(c):
         return cols
 
 
+def _stats(c, probs=()):
+    """the device's summaries of every chain of c's MAlgoBGP over its accepted draws (smm_get_chain_stats), one call per
+    (iteration, probs): mean, median, CI, best and summary read them instead of downloading the history"""
+    return c._algo._chain_stats(True, tuple(float(p) for p in probs))
+
+
 def best(c):
     """best(c) -> (val, idx), AlgoBGP.jl:167 (1-based index like findmin)"""
-    v = c._h().value[:, c._j]
-    i = int(np.argmin(v))
-    return float(v[i]), i + 1
+    if c._algo.i == 0:
+        np.argmin(np.empty(0))   # raises as findmin of an empty history
+    st = _stats(c)
+    return float(st["best_value"][c._j]), int(st["best_iter"][c._j])
+
+
+def _empty_selection(c, st):
+    return st["count"][c._j] == 0
 
 
 def mean(c):
-    return {k: float(np.mean(v)) for k, v in params(c).items()}
+    st = _stats(c)
+    if _empty_selection(c, st):
+        return {k: float(np.mean(np.empty(0))) for k in ps2s_names(c.m)}   # numpy's RuntimeWarning and NaN
+    return {k: float(st["mean"][i, c._j]) for i, k in enumerate(ps2s_names(c.m))}
 
 
 def median(c):
-    return {k: float(np.median(v)) for k, v in params(c).items()}
+    st = _stats(c)
+    if _empty_selection(c, st):
+        return {k: float(np.median(np.empty(0))) for k in ps2s_names(c.m)}
+    return {k: float(st["median"][i, c._j]) for i, k in enumerate(ps2s_names(c.m))}
 
 
 def CI(c, level=0.95):
-    return {k: np.quantile(v, [(1 - level) / 2, 1 - (1 - level) / 2]) for k, v in params(c).items()}
+    q = ((1 - level) / 2, 1 - (1 - level) / 2)
+    st = _stats(c, q)
+    if _empty_selection(c, st):
+        return {k: np.quantile(np.empty(0), list(q)) for k in ps2s_names(c.m)}   # raises IndexError, as np.quantile of no draw
+    return {k: st["quantile"][:, i, c._j].copy() for i, k in enumerate(ps2s_names(c.m))}
 
 
 def summary(x):
@@ -389,11 +410,13 @@ def summary(x):
             return pd.DataFrame(rows)
         except Exception:  # pragma: no cover
             return rows
-    ex = x.exchanged
-    ex_with = ex[ex != 0]
-    most = int(np.bincount(ex_with).argmax()) if len(ex_with) else 0  # mode(ex_with)
-    return OrderedDict(id=x.id, acc_rate=x.accept_rate, perc_exchanged=100.0 * np.sum(ex != 0) / len(ex),
-                       exchanged_most_with=most, best_val=float(x.best_val[-1]))
+    a, j = x._algo, x._j
+    st = _stats(x)
+    n = int(a.opts["maxiter"])
+    # best_val[-1] of the column padded to maxiter: the padding (inf) until the last iteration is done
+    best_last = float(a._last_row().best_val[0, j]) if a.i >= n else np.inf
+    return OrderedDict(id=x.id, acc_rate=x.accept_rate, perc_exchanged=100.0 * np.int64(st["n_exchanged"][j]) / n,
+                       exchanged_most_with=int(st["most_exchanged_with"][j]), best_val=best_last)
 
 
 # ------------------------------------------------------------------------------------------
@@ -446,8 +469,7 @@ class MAlgoBGP:
                      **self._flat)
         self._prob, self._bopts, self._tables = prob, bo, tables
         self._ctx = hip_context(prob, bo, tables)
-        self._hist = None
-        self._st = None
+        self._invalidate()
         self.chains = [BGPChain(self, j) for j in range(N)]
         self.dist_fun = lambda a, b: a - b
 
@@ -457,6 +479,19 @@ class MAlgoBGP:
     def _invalidate(self):
         self._hist = None
         self._st = None
+        self._stats = {}
+        self._last = None
+
+    def _chain_stats(self, accepted_only, probs):
+        key = (self.i, accepted_only, probs)
+        if key not in self._stats:
+            self._stats[key] = self._ctx.chain_stats(0, self.i, accepted_only, probs)
+        return self._stats[key]
+
+    def _last_row(self):
+        if self._last is None or self._last[0] != self.i:
+            self._last = (self.i, self._ctx.history(self.i - 1, self.i))
+        return self._last[1]
 
     def _history(self):
         if self._hist is None:
