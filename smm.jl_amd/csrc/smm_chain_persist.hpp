@@ -1,7 +1,8 @@
-// what the PERSISTENT chain kernels share — the ring's tags, stores and loads, the out-of-line waits, the simulation with the lane's
-// shocks in registers, mysample's late tries — part of libsmmhip (included by smmhip.hip inside its anonymous namespace; gfx950 device
-// code).  The kernels: smm_chain_persist_loc.hpp (objfunc_norm, locally numbered cones: single shards and shards of a sharded run,
-// thresholds) and smm_chain_persist_gen.hpp (objectives without a simulation).
+// what the PERSISTENT chain kernels share — their argument block (PersistArgs), the ring's window, tags, stores and loads, the out-of-line
+// waits, the simulation with the lane's shocks in registers, mysample's late tries — part of libsmmhip (included by smmhip.hip inside its
+// anonymous namespace; gfx950 device code).  The kernels: smm_chain_persist_loc.hpp (objfunc_norm, locally numbered cones: single shards
+// and shards of a sharded run, thresholds), smm_chain_persist_gen.hpp (objectives without a simulation) and smm_chain_persist_tile.hpp
+// (objectives a whole tile evaluates).
 #pragma once
 // ------------------------------------------------------------------------------------------
 // ONE launch for a whole run of iterations (up to the end of the look-ahead windows): next_eval for every chain and exchangeMoves!
@@ -45,8 +46,51 @@ constexpr int PR_STW = 12;       // doubles of chain state in front of the recor
 constexpr unsigned long long PERSIST_TMO_FIRST = 40000000ull;   // 0.4 s of the 100 MHz wall clock: the spins of a context's first launches (smmhip.hip, launch_chain_persist)
 
 __host__ __device__ inline int persist_line(int np) { return PR_STW + ((3 + 2 * np + 1) & ~1); }
-__host__ __device__ inline size_t persist_ring_slot_bytes(int Ng) { return (size_t)PR_K * (((size_t)Ng + 4) * 8); }
-__host__ __device__ inline size_t persist_ring_rec_bytes(int Ng, int RW) { return (size_t)PR_K * (size_t)Ng * RW * 16; }
+
+// the ring and its control words in a window (one per rank; a single shard has one of its own).  The slots: [PR_K][Ng + 4] x 8 bytes,
+// the records: [PR_K][Ng][RW] x 16 bytes, the progress words: one per tile of every rank (rank-major)
+struct PrWin { uint32_t ctl, arrive, fin, progress, slot, rec; size_t total; };
+__host__ __device__ inline PrWin pr_win_layout(const int Ng, const int RW, const int G, const int tiles_rank) {
+    PrWin L;
+    size_t o = 0;
+    L.ctl = (uint32_t)o; o += 128;                                            // word 0: the epoch of a launch somebody gave up on
+    L.arrive = (uint32_t)o; o += (size_t)128 * P2P_MAXG;                      // rank r's word: the last launch it has arrived at
+    L.fin = (uint32_t)o; o += (size_t)128 * P2P_MAXG;                         // rank r: {error word of its last launch (u64), epoch (u32)}
+    L.progress = (uint32_t)o; o += (((size_t)G * tiles_rank * 4) + 127) & ~(size_t)127;
+    L.slot = (uint32_t)o; o += ((size_t)PR_K * ((size_t)Ng + 4) * 8 + 127) & ~(size_t)127;
+    L.rec = (uint32_t)o; o += ((size_t)PR_K * (size_t)Ng * RW * 16 + 127) & ~(size_t)127;
+    L.total = o;
+    return L;
+}
+
+// The argument block of every persistent kernel, the hiprtc-compiled ones included (one layout for the library and the modules: no field
+// depends on a build's macros).  Every kernel reads the fields it needs; smmhip.hip (persist_args) fills all of them.  (The order of the
+// fields is the register allocator's business too: the kernels spill SGPRs already, and moving a field can move those spills into scratch
+// memory — tools/kernel_resources.py k_chain_persist.)
+struct PersistArgs {
+    const uint32_t* cone_hdr; const uint32_t* cone_pairs; const uint16_t* cone_gather; const uint32_t* cone_ok;
+    unsigned char* self;               // this rank's ring window (pr_win_layout) and its parts
+    uint32_t o_ctl, o_progress, o_rec;
+    double* cs; const double* rec_in; double* rec_out; double* vals_out; uint2* slot8_out; uint32_t* walk_flags;
+    double* hrec; unsigned long long* err; unsigned long long* ts;
+    const double *Z, *lb, *ub, *mom, *w, *objp, *dense_Bf, *dense_Af, *dense_A2f;   // objp: a user objective's own data too
+    const double* rb;                  // randomness blocks of injected tables / of the window (null: drawn in the kernel)
+    int N, Ng, np, nm, ns, zstride, RW, HW, RBW, dense_nOt, batch_size, failbox;
+    int plan_t0, exch_from, sigma_update_steps, smpl_iters, t0, t1, rb_t0, rb_tries, user_n;
+    int ring_k, slow_tile, slow_ticks, walk_first, unit_sh, scout_after, scout_gl;
+    uint32_t epoch;
+    double sigma_adjust_by, thr;
+    uint64_t seed;
+    unsigned long long tmo;            // ticks a spin may last
+    const double* mi_g;                // min_improve of every chain of the population (the wide walk's per-position thresholds, AlgoBGP.jl:522, :688)
+    int u_lanes, n_udata;              // a user objective: lanes per evaluation (its map-reduce form), doubles of its data (objp)
+    unsigned char* win[P2P_MAXG];      // the ranks' windows (a single shard: win[0] = self)
+    uint32_t o_arrive;                 // ... the start barrier's words (pr_win_layout)
+    int G, rank, offset;               // ranks, this rank, the shard's first chain in the population (equal shards of N)
+    int slow_read;                     // SH, test build: the slow tile idles before its donors' remote reads instead of before its publication
+    uint32_t o_slot;                   // the walk slots' part of the window (k_chain_persist_gen, k_chain_persist_loc)
+    int tables_local;                  // the plan's pair words name local slots already (k_cone_tiles); else population offsets in units of 1 << unit_sh bytes
+};
 
 // tags: never 0 (the ring starts zeroed and is zeroed again whenever the 7 epoch bits of the slot tag wrap)
 __device__ inline uint32_t pr_tag16(const uint32_t epoch, const int rel) { return 0x8000u | ((epoch & 0x7fu) << 8) | ((uint32_t)rel & 0xffu); }
@@ -198,13 +242,15 @@ struct PersistWalkValues {   // GUARD of the lean walk (smm_walk_lean.hpp)
 // to scratch memory there, and fetched back from it in every accept step (the same code as the inlined one: identical results)
 __device__ __attribute__((noinline)) double pr_exp(const double x) { return smm_exp(x); }   // (the contract exponential, smm_rng.hpp)
 
-// the slowest tile's progress in this launch (lanes of one wave; words of another launch count as "not started")
+// progress of the slowest tile of ALL ranks in this launch (lanes of one wave); a word of a LATER launch counts as "through" (its rank
+// has left this launch behind: nothing of it is waited for any more — on one device no word is ever later), of an earlier one as "not started"
 __device__ inline int pr_min_progress(const uint32_t* pr_progress, const uint32_t epoch, const int tiles, const int lane) {
     uint32_t m = 0xfffu;
     for (int b = lane; b < tiles; b += 64) {
-        const uint32_t w = pr_load4_sys(pr_progress + b);
-        const uint32_t rel = (w >> 12) == (epoch & 0xfffffu) ? (w & 0xfffu) : 0u;
-        m = min(m, rel);
+        // the word less this launch's epoch, signed: the epochs' difference (20 bits, wrap-safe) x 4096 + the word's iteration — negative
+        // for an earlier launch (0), past 0xfff for a later one (capped by m)
+        const int x = (int)(pr_load4_sys(pr_progress + b) - (epoch << 12));
+        m = min(m, (uint32_t)max(x, 0));
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) m = min(m, (uint32_t)__shfl_xor((int)m, off, 64));

@@ -28,23 +28,6 @@ constexpr int PG_CT = 32;          // chains per workgroup
 constexpr int PG_MAXP = 16;        // parameters (= moments)
 constexpr int PG_TRIES = 2;        // proposal tries whose normals are made ahead (the per-iteration path's rb_tries for np > 8)
 
-struct PersistGenArgs {
-    const uint32_t* cone_hdr; const uint32_t* cone_pairs; const uint16_t* cone_gather; const uint32_t* cone_ok;
-    uint2* pr_slot; uint4* pr_rec; uint32_t* pr_progress; uint32_t* pr_ctl;
-    double* cs; const double* rec_in; double* rec_out; double* vals_out; uint2* slot8_out; uint32_t* walk_flags;
-    double* hrec; unsigned long long* err; unsigned long long* ts;
-    const double *lb, *ub, *mom, *w;
-    const double* rb;                 // randomness blocks of injected tables (null: drawn in the kernel)
-    int N, Ng, np, nm, RW, HW, plan_t0, exch_from, sigma_update_steps, smpl_iters, t0, t1;
-    int rb_t0, RBW, rb_tries, user_n;
-    int ring_k, slow_tile, slow_ticks, walk_first;
-    unsigned long long tmo;           // ticks a spin may last
-    uint32_t epoch;
-    double sigma_adjust_by;
-    uint64_t seed;
-    const double* udata; int n_udata; // a user objective's own data (SMM_GEN_USER: the kernel compiled with the user's source, below)
-};
-
 __host__ __device__ inline int persist_gen_rngw(int np) { return (1 + PG_TRIES * np + 1) & ~1; }
 __host__ __device__ inline size_t persist_gen_smem_bytes(int Ng, int np, int RW, int HW) {
     const size_t slots = (size_t)(((Ng + 3) & ~3) + 4) * 8;
@@ -62,9 +45,9 @@ __host__ __device__ inline size_t persist_gen_smem_bytes(int Ng, int np, int RW,
 // moments are the function's, and a failing evaluation (status < 0) is the rejection of mprob.jl:183-186 / AlgoBGP.jl:336-338.
 __host__ __device__ inline size_t persist_gen_user_bytes() { return (size_t)PG_CT * PG_MAXP * 8 + (size_t)PG_CT * 8 + (size_t)PG_CT * 8; }
 #ifdef SMM_GEN_USER
-extern "C" __global__ __launch_bounds__(1024, 4) void smm_user_persist_kernel(const PersistGenArgs A) {
+extern "C" __global__ __launch_bounds__(1024, 4) void smm_user_persist_kernel(const PersistArgs A) {
 #else
-__global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistGenArgs A) {
+__global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistArgs A) {
 #endif
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = (int)threadIdx.x, lane = tid & 63;
@@ -104,7 +87,12 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistGenA
 #endif
     const uint32_t epoch = A.epoch;
     const int t0 = A.t0, t1 = A.t1;
-    const PrWait W{A.err, A.pr_ctl, s_abort, A.epoch, A.tmo};
+    unsigned char* const mine = A.self;   // the ring's window (pr_win_layout)
+    uint32_t* const pr_ctl = (uint32_t*)(mine + A.o_ctl);
+    uint32_t* const pr_progress = (uint32_t*)(mine + A.o_progress);
+    uint2* const pr_slot = (uint2*)(mine + A.o_slot);
+    uint4* const pr_rec = (uint4*)(mine + A.o_rec);
+    const PrWait W{A.err, pr_ctl, s_abort, A.epoch, A.tmo};
     const int rmask = A.ring_k - 1;
     const bool exch_any = A.Ng > 1;
     auto exch_on = [&](const int tx) { return exch_any && tx >= A.exch_from; };   // AlgoBGP.jl:637
@@ -238,10 +226,10 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistGenA
             }
             if (wave == 2) {
                 if (t < t1) make_rng(t + 1);
-                const int m = pr_min_progress(A.pr_progress, epoch, tiles, lane);
+                const int m = pr_min_progress(pr_progress, epoch, tiles, lane);
                 if (lane == 0) {
                     __hip_atomic_store(s_minprog, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (pr_load4_sys(A.pr_ctl) == epoch) *s_abort = 1u;
+                    if (pr_load4_sys(pr_ctl) == epoch) *s_abort = 1u;
                     if (t < t1 && exch_on(t) && A.cone_ok[t - A.plan_t0] == 0u) pr_report(A.err, 3, t + 1, tile * PG_CT);
                 }
             }
@@ -251,7 +239,7 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistGenA
                 while (__hip_atomic_load(s_pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 2u * (unsigned)rel) __builtin_amdgcn_s_sleep(1);
                 __builtin_amdgcn_s_sleep(PR_GATHER_DELAY);
                 const int ngat = (int)(s_hdr[(t & 3) * 16] >> 16);
-                const unsigned long long* rs = (const unsigned long long*)A.pr_slot + (size_t)(rel & rmask) * (A.Ng + 4);
+                const unsigned long long* rs = (const unsigned long long*)pr_slot + (size_t)(rel & rmask) * (A.Ng + 4);
                 const uint32_t want = pr_tag16(epoch, rel) << 16;
                 const uint16_t* gl = (const uint16_t*)(lds + gbase) + (t & 1) * CONE_GCAP;
                 for (int e = tid - 256; e < ngat; e += 512) {
@@ -296,7 +284,7 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistGenA
         if (exch && wave == 0) {
             // ---- the walk over the cone's sub-levels: wave 0 alone, no barriers ----
             const int nsub = (int)(s_hdr[((t - 1) & 3) * 16] & 0xffffu);
-            const PersistWalkValues values{W, (const uint4*)A.pr_rec + (size_t)((rel - 1) & rmask) * A.Ng * RW, first ? A.rec_in : nullptr, pr_tag32(epoch, rel - 1), RW, 0, t};
+            const PersistWalkValues values{W, (const uint4*)pr_rec + (size_t)((rel - 1) & rmask) * A.Ng * RW, first ? A.rec_in : nullptr, pr_tag32(epoch, rel - 1), RW, 0, t};
             if (US == 0) lean_walk_levels<64, 0, false, PersistWalkValues>(nullptr, 1, lbase, (uint32_t)(64 * lane), nsub, lane, 0, 0.0, values);
             else lean_walk_levels<64, 1, false, PersistWalkValues>(nullptr, 1, lbase, (uint32_t)(64 * lane), nsub, lane, 0, 0.0, values);
         }
@@ -324,7 +312,7 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistGenA
             if (__builtin_expect(first, 0)) {
                 if (donor) for (int i = r; i < RW; i += 4) rin[i] = A.rec_in[(size_t)src * RW + i];
             } else {
-                const uint4* g_ll = (const uint4*)A.pr_rec + ((size_t)((rel - 1) & rmask) * A.Ng + src) * RW;
+                const uint4* g_ll = (const uint4*)pr_rec + ((size_t)((rel - 1) & rmask) * A.Ng + src) * RW;
                 const uint32_t tag = pr_tag32(epoch, rel - 1);
                 const uint32_t land = (uint32_t)((unsigned char*)s_land - lds) + (uint32_t)wave * (uint32_t)NPC * 1024u;
                 if (donor) for (int j = 0; j < NPC; ++j) if (r + 4 * j < RW) pr_dma16(g_ll + r + 4 * j, land + (uint32_t)j * 1024u);
@@ -346,7 +334,7 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistGenA
         asm volatile("" ::: "memory");
         // every read of the ring's last entry is done — by both control waves: say so (the publication of iteration rel + K - 1 waits for it)
         if (lane == 0 && __hip_atomic_fetch_add(s_read, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + 1u == 2u * (unsigned)rel)
-            __hip_atomic_store(A.pr_progress + tile, pr_progress_word(epoch, rel), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(pr_progress + tile, pr_progress_word(epoch, rel), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         unsigned long long ts3 = 0;
         if (A.ts && tid == 0) ts3 = wall_clock64();
         // ---- proposal (mysample, AlgoBGP.jl:400-410; proposal :424-471): the tries in order, each tested by the chain's four lanes ----
@@ -433,10 +421,10 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistGenA
                 int st_u = 1;
                 double v_u = 0.0;
 #ifdef SMM_USER_RNG   // (the library's stream, keyed by the context's seed: the same draws for every chain and iteration)
-                smm_user_objective_rng(thp, np, s_const + 2 * PG_MAXP, s_const + 3 * PG_MAXP, nm, A.udata, A.n_udata, smm_rng_t{A.seed}, s_usm + cl * PG_MAXP,
+                smm_user_objective_rng(thp, np, s_const + 2 * PG_MAXP, s_const + 3 * PG_MAXP, nm, A.objp, A.n_udata, smm_rng_t{A.seed}, s_usm + cl * PG_MAXP,
                                        &v_u, &st_u);
 #else
-                smm_user_objective(thp, np, s_const + 2 * PG_MAXP, s_const + 3 * PG_MAXP, nm, A.udata, A.n_udata, s_usm + cl * PG_MAXP, &v_u, &st_u);
+                smm_user_objective(thp, np, s_const + 2 * PG_MAXP, s_const + 3 * PG_MAXP, nm, A.objp, A.n_udata, s_usm + cl * PG_MAXP, &v_u, &st_u);
 #endif
                 s_uval[cl] = v_u; s_ust[cl] = (double)st_u;
             }
@@ -489,14 +477,14 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistGenA
             // ---- publish: the walk slot and the self-validating record of iteration t (write-through stores) ----
             if (t < t1) {
                 if (__builtin_expect(rel > rmask && __hip_atomic_load(s_minprog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < rel - rmask, 0))
-                    pr_wait_progress(W, A.pr_progress, s_minprog, rel - rmask, tiles, lane, t, c);
+                    pr_wait_progress(W, pr_progress, s_minprog, rel - rmask, tiles, lane, t, c);
 #ifdef SMM_TEST_HOOKS
                 if (tile == A.slow_tile) { const unsigned long long w0 = wall_clock64(); while (wall_clock64() - w0 < (unsigned long long)A.slow_ticks) __builtin_amdgcn_s_sleep(8); }
 #endif
                 if (r == 0)
-                    pr_store8((uint2*)A.pr_slot + (size_t)(rel & rmask) * (A.Ng + 4) + c,
+                    pr_store8((uint2*)pr_slot + (size_t)(rel & rmask) * (A.Ng + 4) + c,
                               (unsigned long long)order_key32(v) | ((unsigned long long)((uint32_t)c | (pr_tag16(epoch, rel) << 16)) << 32));
-                unsigned char* g_ll = (unsigned char*)A.pr_rec + ((size_t)(rel & rmask) * A.Ng + c) * RW * 16;
+                unsigned char* g_ll = (unsigned char*)pr_rec + ((size_t)(rel & rmask) * A.Ng + c) * RW * 16;
                 const uint32_t tag = pr_tag32(epoch, rel);
                 for (int i = 2 * r; i < RW; i += 8)   // lane r: the pairs of doubles r, r + 4, ... (a 32-byte granule each)
                     pr_store_ll(g_ll + (size_t)i * 16, *(const double2*)(rout + i), tag);

@@ -32,41 +32,6 @@ constexpr int PL_LOCN = NORM_CT + CONE_GCAP + 2;                          // loc
 constexpr uint32_t PL_PBASE = ((16u * PL_LOCN + 127u) & ~127u);          // LDS offset of the pair lists (slots: 16 bytes reserved each, from address 0)
 constexpr int PL_HASH = 1024;                                             // slots of the re-numbering table (<= 512 entries)
 
-// the ring and its control words in a window (one per rank; a single shard has one of its own)
-struct PrWin { uint32_t ctl, arrive, fin, progress, slot, rec; size_t total; };
-__host__ __device__ inline PrWin pr_win_layout(const int Ng, const int RW, const int G, const int tiles_rank) {
-    PrWin L;
-    size_t o = 0;
-    L.ctl = (uint32_t)o; o += 128;                                            // word 0: the epoch of a launch somebody gave up on
-    L.arrive = (uint32_t)o; o += (size_t)128 * P2P_MAXG;                      // rank r's word: the last launch it has arrived at
-    L.fin = (uint32_t)o; o += (size_t)128 * P2P_MAXG;                         // rank r: {error word of its last launch (u64), epoch (u32)}
-    L.progress = (uint32_t)o; o += (((size_t)G * tiles_rank * 4) + 127) & ~(size_t)127;
-    L.slot = (uint32_t)o; o += ((size_t)PR_K * ((size_t)Ng + 4) * 8 + 127) & ~(size_t)127;
-    L.rec = (uint32_t)o; o += ((size_t)PR_K * (size_t)Ng * RW * 16 + 127) & ~(size_t)127;
-    L.total = o;
-    return L;
-}
-
-struct PersistLocArgs {
-    const uint32_t* cone_hdr; const uint32_t* cone_pairs; const uint16_t* cone_gather; const uint32_t* cone_ok;
-    unsigned char* win[P2P_MAXG];     // the ranks' windows (a single shard: win[0] = self)
-    unsigned char* self;              // this rank's window
-    uint32_t o_ctl, o_arrive, o_progress, o_slot, o_rec;
-    double* cs; const double* rec_in; double* rec_out; double* vals_out; uint2* slot8_out; uint32_t* walk_flags;
-    double* hrec; unsigned long long* err; unsigned long long* ts;
-    const double *Z, *lb, *ub, *mom, *w, *objp;
-    const double* rb;                 // randomness blocks of injected tables (null: drawn in the kernel)
-    int N, Ng, offset, G, rank, ns, zstride, plan_t0, exch_from, sigma_update_steps, smpl_iters, t0, t1;
-    int rb_t0, RBW, rb_tries, user_n, failbox;
-    int ring_k, slow_tile, slow_ticks, walk_first;
-    int tables_local;                 // the plan's pair words name local slots already (k_cone_tiles); else population offsets in units of 1 << unit_sh bytes
-    int unit_sh;
-    uint32_t epoch;
-    double sigma_adjust_by, thr;
-    uint64_t seed;
-    unsigned long long tmo;           // ticks a spin may last
-    const double* mi_g;               // WIDE: min_improve of every chain of the population (AlgoBGP.jl:522; the pair (i, j) is tested against chain i's, :688)
-};
 __host__ __device__ inline size_t persist_loc_smem_bytes(const int np) {
     const size_t hw = (size_t)((H_PARAMS + 2 * np + 1) & ~1);
     const size_t dbl = (size_t)NORM_CT * np + (size_t)np * 8 * NORM_CT + (size_t)NORM_CT * persist_line(np) + 2 * 64 * (size_t)(1 + 2 * np) +
@@ -141,31 +106,6 @@ struct PersistLocWalkValues {
 // (the ring's words travel at the system scope — sc0 sc1: pr_store8 / pr_store_ll / pr_dma16 and the loads of smm_chain_persist.hpp —
 // whether the tiles are one device's or the ranks': a remote store lands in this device's memory behind its L2)
 
-// progress of the slowest tile of ALL ranks in this launch; a word of a LATER launch counts as "through" (its rank has left this
-// launch behind: nothing of it is waited for any more), of an earlier one as "not started"
-__device__ inline int pl_min_progress(const uint32_t* pr_progress, const uint32_t epoch, const int tiles, const int lane) {
-    uint32_t m = 0xfffu;
-    for (int b = lane; b < tiles; b += 64) {
-        const uint32_t w = pr_load4_sys(pr_progress + b);
-        const int d = (int)(((w >> 12) - epoch) << 12) >> 12;   // (20-bit epochs, wrap-safe)
-        const uint32_t rel = d == 0 ? (w & 0xfffu) : (d > 0 ? 0xfffu : 0u);
-        m = min(m, rel);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) m = min(m, (uint32_t)__shfl_xor((int)m, off, 64));
-    return (int)m;
-}
-__device__ __attribute__((noinline)) void pl_wait_progress(const PrWait W, const uint32_t* pr_progress, int* s_minprog, const int need, const int tiles, const int lane,
-                                                           const int t, const int chain) {
-    unsigned spins = 0;
-    const unsigned long long w0 = wall_clock64();
-    while (__hip_atomic_load(s_minprog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < need && *W.s_abort == 0u) {
-        const int m = pl_min_progress(pr_progress, W.epoch, tiles, lane);
-        if (lane == 0) __hip_atomic_store(s_minprog, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if ((++spins & 15u) == 0u && pr_give_up(W, w0)) { if (lane == 0) pr_abort(W, t, chain); break; }
-        __builtin_amdgcn_s_sleep(4);
-    }
-}
 // out of line: the gather of the wide form — three self-validating pieces of the same chain's record, looked at again together
 struct PlGather3 { uint4 q0, q1, q2; };
 __device__ __attribute__((noinline)) PlGather3 pl_wait_gather3(const PrWait W, const uint4* p0, const uint4* p1, const uint4* p2, const uint32_t tag, const int t, const int g) {
@@ -189,7 +129,7 @@ __device__ __attribute__((noinline)) PlGather3 pl_wait_gather3(const PrWait W, c
 // (PCT: thresholds by chain — WIDE single shards only; a form of its own so that ONE threshold for all chains pays nothing for it: 11.84 -> 12.06 us per iteration when
 // the per-position read was always there, 12.27 as a run-time branch)
 template <int NP, bool WIDE, bool SH, bool PCT = false>
-__global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistLocArgs A) {
+__global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistArgs A) {
     static_assert(!PCT || (WIDE && !SH), "thresholds by chain: the wide walk of a single shard");
     static_assert(NP == 1 || NP == 2, "one moment per half of the workgroup");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -540,7 +480,7 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistL
             }
             if (wave == 1 && t < t1) make_rng(t + 1);
             if (wave == 2) {
-                const int m = pl_min_progress(pr_progress, epoch, tiles_all, lane);
+                const int m = pr_min_progress(pr_progress, epoch, tiles_all, lane);
                 if (lane == 0) {
                     __hip_atomic_store(Y.s_minprog, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     if (pr_load4_sys(pr_ctl) == epoch) *Y.s_abort = 1u;
@@ -807,7 +747,7 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistL
             // ---- publish: the walk slot and the self-validating record of iteration t into the ring(s) ----
             if (t < t1) {
                 if (__builtin_expect(rel > rmask && __hip_atomic_load(Y.s_minprog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < rel - rmask, 0))
-                    pl_wait_progress(W, pr_progress, Y.s_minprog, rel - rmask, tiles_all, lane, t, (int)c0g + cl);
+                    pr_wait_progress(W, pr_progress, Y.s_minprog, rel - rmask, tiles_all, lane, t, (int)c0g + cl);
 #ifdef SMM_TEST_HOOKS
                 if (tile == A.slow_tile) { const unsigned long long w0 = wall_clock64(); while (wall_clock64() - w0 < (unsigned long long)A.slow_ticks) __builtin_amdgcn_s_sleep(8); }
 #endif

@@ -1,7 +1,7 @@
 // the PERSISTENT chain kernel of objectives evaluated by a whole tile — objfunc_norm with any number of parameters (the shocks streamed
 // from L2) and the dense simulation on the FP64 matrix cores (BASELINE config 5): k_chain_persist_tile — part of libsmmhip (included by
-// smmhip.hip inside its anonymous namespace, behind smm_chain_persist_loc.hpp whose window, re-numbering table and progress words it
-// shares; gfx950 device code).
+// smmhip.hip inside its anonymous namespace, behind smm_chain_persist_loc.hpp whose local slots and re-numbering table it shares;
+// gfx950 device code).
 #pragma once
 // ------------------------------------------------------------------------------------------
 // k_chain_persist_loc (np <= 2: a lane's shocks in registers, a control wave of four lanes per chain) and k_chain_persist_gen (np <= 16,
@@ -34,29 +34,6 @@
 constexpr int PT_CT = 16;          // chains per tile
 constexpr int PT_LPC = WG / PT_CT; // lanes per chain (32: half a wave)
 constexpr int PT_NJ = 5;           // 16-byte pieces of a record per lane of its chain (RW <= 160)
-
-struct PersistTileArgs {
-    const uint32_t* cone_hdr; const uint32_t* cone_pairs; const uint16_t* cone_gather; const uint32_t* cone_ok;
-    unsigned char* self;               // the ring's window (pr_win_layout)
-    uint32_t o_ctl, o_progress, o_rec;
-    double* cs; const double* rec_in; double* rec_out; double* vals_out; uint2* slot8_out; uint32_t* walk_flags;
-    double* hrec; unsigned long long* err; unsigned long long* ts;
-    const double *Z, *lb, *ub, *mom, *w, *objp, *dense_Bf, *dense_Af, *dense_A2f;
-    const double* rb;                  // randomness blocks of the window (null: drawn in the kernel)
-    int N, Ng, np, nm, ns, zstride, RW, HW, RBW, dense_nOt, batch_size, failbox;
-    int plan_t0, exch_from, sigma_update_steps, smpl_iters, t0, t1, rb_t0, rb_tries, user_n;
-    int ring_k, slow_tile, slow_ticks, walk_first, unit_sh, scout_after, scout_gl;
-    uint32_t epoch;
-    double sigma_adjust_by, thr;
-    uint64_t seed;
-    unsigned long long tmo;            // ticks a spin may last
-    const double* mi_g;                // min_improve of every chain of the population (the wide walk's per-position thresholds, AlgoBGP.jl:522, :688)
-    int u_lanes, n_udata;              // a user objective in its map-reduce form (SMM_TILE_USER below): lanes per evaluation, doubles of its data (objp)
-    unsigned char* win[P2P_MAXG];      // SH: the ranks' windows (self = win[rank])
-    uint32_t o_arrive;                 // SH: the start barrier's words (pr_win_layout)
-    int G, rank, offset;               // SH: ranks, this rank, the shard's first chain in the population (equal shards of N)
-    int slow_read;                     // SH, test build: the slow tile idles before its donors' remote reads instead of before its publication
-};
 
 // LDS: [slots 16 B x PL_LOCN | pair words | gather list | 4 headers | re-numbering table | flags, stamps] doubles: cs rec[2] theta
 // const sm vk rb | region B: the objective's partial sums / the two history rows
@@ -114,7 +91,7 @@ __device__ __attribute__((noinline)) uint4 pt_wait_ll(const PrWait W, const uint
 // calls the user's finish, and a failing evaluation (status < 0) is the rejection of mprob.jl:183-186 / AlgoBGP.jl:336-338.
 // (a shard's form of it is a module of its own, compiled with SMM_TILE_SH as well, only when a sharded context wants it: user_tile_compile)
 #ifdef SMM_TILE_USER
-extern "C" __global__ __launch_bounds__(WG) void smm_user_persist_tile_kernel(const PersistTileArgs A) {
+extern "C" __global__ __launch_bounds__(WG) void smm_user_persist_tile_kernel(const PersistArgs A) {
     constexpr int KIND = 4;
     constexpr bool PCT = false;   // (one threshold for all chains)
 #ifdef SMM_TILE_SH
@@ -124,7 +101,7 @@ extern "C" __global__ __launch_bounds__(WG) void smm_user_persist_tile_kernel(co
 #endif
 #else
 template <int KIND, bool PCT = false, bool SH = false>   // PCT: thresholds by chain (a form of its own: see k_chain_persist_loc); SH: a shard
-__global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs A) {
+__global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistArgs A) {
     static_assert(KIND == 1 || KIND == 2, "objfunc_norm (shocks streamed) or the dense simulation");
     static_assert(!(PCT && SH), "thresholds by chain: single shards only");
 #endif
@@ -561,7 +538,7 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 if (lane + 64 * j < tiles_all) {   // (SH: every rank's tiles, at rank * tiles + tile)
-                    const int d = (int)(((pw_[j] >> 12) - epoch) << 12) >> 12;   // (20-bit epochs, wrap-safe: pl_min_progress)
+                    const int d = (int)(((pw_[j] >> 12) - epoch) << 12) >> 12;   // (20-bit epochs, wrap-safe: pr_min_progress)
                     m = min(m, d == 0 ? (pw_[j] & 0xfffu) : (d > 0 ? 0xfffu : 0u));
                 }
             }
@@ -717,7 +694,7 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistTileArgs
         // self-validating record of iteration t into the ring (write-through stores), granule by granule as it is put together ----
         if (t < t1) {
             if (__builtin_expect(rel > rmask && __hip_atomic_load(s_minprog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < rel - rmask, 0))
-                pl_wait_progress(W, pr_progress, s_minprog, rel - rmask, tiles_all, lane, t, (int)c0g);
+                pr_wait_progress(W, pr_progress, s_minprog, rel - rmask, tiles_all, lane, t, (int)c0g);
 #ifdef SMM_TEST_HOOKS
             if (tile == A.slow_tile && !(SH && A.slow_read)) { const unsigned long long w0 = wall_clock64(); while (wall_clock64() - w0 < (unsigned long long)A.slow_ticks) __builtin_amdgcn_s_sleep(8); }
 #endif

@@ -84,12 +84,6 @@ struct KParams {
     int cone_tiles, cone_ct;         // workgroups, chains per workgroup
     uint16_t* cone_gather;           // [W][tiles][CONE_GCAP] (k_chain_persist_norm; null otherwise): the chains of OTHER workgroups whose initial slots the
                                      //          cone needs; their number is in the high half of the header's word 0
-    // ... the ring of k_chain_persist_norm (smm_chain_persist.hpp; null otherwise): tagged walk slots and self-validating records of the
-    // last PR_K iterations, the tiles' progress words, the launch's abort word
-    uint2* pr_slot;                  // [PR_K][Ng + 4]
-    uint4* pr_rec;                   // [PR_K][Ng][RW]
-    uint32_t* pr_progress;           // [tiles]
-    uint32_t* pr_ctl;                // [0]: == pr_epoch when a tile of this launch gave up waiting
     uint32_t pr_epoch;               // launches of the persistent kernel so far (never 0): part of every tag
     int exch_from;                   // first iteration with an exchange (AlgoBGP.jl:637)
     // state

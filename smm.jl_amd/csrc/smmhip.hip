@@ -475,7 +475,7 @@ struct Forms {
     bool persist_wide = false;   // ... its 16-byte slots: one min_improve > 0 (or NaN) for all chains
     bool persist_sh = false;     // ... as a SHARD of a sharded run: the ring lives in every rank's p2p window (smm_bgp_p2p_step)
     bool persist_sh_big = false; // ... of a population past 8192 chains: k_exch_plan_big + k_cone_chains + k_cone_tiles list its tiles' cones (locally numbered)
-    bool persist_user = false;   // PERSIST_GEN launches upfn (the user's objective inside)
+    bool persist_user = false;   // PERSIST_GEN launches pfn (the user's objective inside)
     int max_tiles = 0;           // tiles of the persistent kernel this device holds at once (occupancy x compute units)
     bool defer_resolve = false;  // the exchange of an iteration is left unresolved until somebody needs it (the next launch may be the persistent kernel's)
 };
@@ -542,10 +542,8 @@ struct Ctx {
     hipFunction_t ufn = nullptr;
     hipFunction_t ufn_noseed = nullptr;   // ... an objective with the library's stream: its noseed kernel (evaluation i keyed by base_seed + i)
     bool u_rng = false;
-    hipModule_t upmod = nullptr;    // ... and the persistent kernel compiled with it inside (smm_chain_persist_gen.hpp, SMM_GEN_USER)
-    hipFunction_t upfn = nullptr;
-    hipModule_t utmod = nullptr;    // ... and the persistent TILE kernel with its map-reduce form inside (smm_chain_persist_tile.hpp, SMM_TILE_USER)
-    hipFunction_t utfn = nullptr;
+    hipModule_t pmod = nullptr;     // ... and the persistent kernel compiled with it inside: k_chain_persist_gen (SMM_GEN_USER), or
+    hipFunction_t pfn = nullptr;    //     k_chain_persist_tile with its map-reduce form (SMM_TILE_USER)
     int u_nsums = 1;                // ... its partial sums per lane
     bool rec_external = false;  // the records after the last accept step were written to the caller's gather buffer (sharded_step)
     bool unresolved = false;    // exchangeMoves! of iteration `iter` is still to be resolved (inline, or by resolve_now)
@@ -647,10 +645,12 @@ size_t persist_tile_smem(const Ctx* c) {
     const KParams& P = c->P;
     return pt_layout(P.np, P.nm, P.RW, P.HW, P.RBW, lay_kind(c), P.dense_nOt, PT_CT * (c->u_lanes / 64) * c->u_nsums).total;
 }
-// tiles of one rank's launch of the chosen persistent kernel (k_chain_persist_loc: NORM_CT chains per tile, k_chain_persist_tile: PT_CT)
-int persist_tiles_rank(const Ctx* c) {
-    const int ct = c->F.persist == PERSIST_TILE ? PT_CT : NORM_CT;
-    return (c->P.N + ct - 1) / ct;
+// tiles (workgroups) of one rank's launch of F's persistent kernel: k_chain_persist_gen has PG_CT chains per tile (whole tiles),
+// k_chain_persist_loc NORM_CT, k_chain_persist_tile PT_CT
+int persist_tiles_rank(const Forms& F, int N) {
+    if (F.persist == PERSIST_GEN) return N / PG_CT;
+    const int ct = F.persist == PERSIST_TILE ? PT_CT : NORM_CT;
+    return (N + ct - 1) / ct;
 }
 size_t norm_smem(const Ctx* c) {   // k_chain_iter_norm: [walk: chain slots | pair list] theta, partial sums, parked state
     const size_t b = (size_t)c->P.tile_off * sizeof(double) + norm_tile_doubles(c->P.np) * sizeof(double);
@@ -992,7 +992,7 @@ void p2p_enqueue(Ctx* c, int n_iters);
 unsigned long long p2p_agree_error(Ctx* c, unsigned long long e_local) {
     const KParams& P = c->P;
     const int G = P.p2p_G;
-    const PrWin WL = pr_win_layout(P.Ng, P.RW, G, persist_tiles_rank(c));
+    const PrWin WL = pr_win_layout(P.Ng, P.RW, G, persist_tiles_rank(c->F, c->P.N));
     const uint32_t seq = c->pr_epoch;
     for (int r = 0; r < G; ++r)
         HIPCHK(hipMemcpy(P.p2p_win[r] + c->prw_off + WL.fin + 128 * (size_t)P.p2p_rank, &e_local, 8, hipMemcpyHostToDevice));
@@ -1216,13 +1216,46 @@ void launch_resolve_rows_window(Ctx* c, int t) {
         launch(c, k_exch_resolve_rows<false, true>, dim3(1), dim3(XWG), smem, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
     }
 }
-// ---- the persistent chain kernels (smm_chain_persist.hpp, smm_chain_persist_loc.hpp) ----
-const void* persist_loc_fn(int np, bool wide, bool sh, bool pct = false) {
-    if (pct) return np == 1 ? (const void*)k_chain_persist_loc<1, true, false, true> : (const void*)k_chain_persist_loc<2, true, false, true>;
-    if (np == 1) return wide ? (sh ? (const void*)k_chain_persist_loc<1, true, true> : (const void*)k_chain_persist_loc<1, true, false>)
-                             : (sh ? (const void*)k_chain_persist_loc<1, false, true> : (const void*)k_chain_persist_loc<1, false, false>);
-    return wide ? (sh ? (const void*)k_chain_persist_loc<2, true, true> : (const void*)k_chain_persist_loc<2, true, false>)
-                : (sh ? (const void*)k_chain_persist_loc<2, false, true> : (const void*)k_chain_persist_loc<2, false, false>);
+// ---- the persistent chain kernels (smm_chain_persist*.hpp) ----
+// what launches F's persistent kernel: a kernel of the library (fn) or of a user objective's module (mfn: loaded by persist_occupancy),
+// its grid, block and dynamic LDS.  persist_occupancy sets its LDS attribute and asks for its occupancy, launch_chain_persist launches it.
+struct PersistKernel { const void* fn; hipFunction_t mfn; dim3 grid, block; size_t smem; };
+PersistKernel persist_kernel(const Ctx* c, const Forms& F) {
+    const KParams& P = c->P;
+    PersistKernel K{nullptr, nullptr, dim3(persist_tiles_rank(F, P.N)), dim3(1), 0};
+    if (F.persist == PERSIST_GEN) {
+        K.block = dim3(1024);
+        K.smem = persist_gen_smem_bytes(P.Ng, P.np, P.RW, P.HW) + (F.persist_user ? persist_gen_user_bytes() : 0);
+        if (F.persist_user) K.mfn = c->pfn;   // (the same kernel, compiled with the user's objective inside: user_persist_compile)
+        else K.fn = (const void*)k_chain_persist_gen;
+    } else if (F.persist == PERSIST_LOC) {
+        const bool one = P.np == 1, wd = F.persist_wide, sh = F.persist_sh;
+        K.block = dim3(NORM_WG);
+        K.smem = persist_loc_smem_bytes(P.np);
+        if (P.mi_pct) K.fn = one ? (const void*)k_chain_persist_loc<1, true, false, true> : (const void*)k_chain_persist_loc<2, true, false, true>;
+        else if (one) K.fn = wd ? (sh ? (const void*)k_chain_persist_loc<1, true, true> : (const void*)k_chain_persist_loc<1, true, false>)
+                                : (sh ? (const void*)k_chain_persist_loc<1, false, true> : (const void*)k_chain_persist_loc<1, false, false>);
+        else K.fn = wd ? (sh ? (const void*)k_chain_persist_loc<2, true, true> : (const void*)k_chain_persist_loc<2, true, false>)
+                       : (sh ? (const void*)k_chain_persist_loc<2, false, true> : (const void*)k_chain_persist_loc<2, false, false>);
+    } else if (F.persist == PERSIST_TILE) {
+        const bool dense = obj_kind(c->obj) == 2;
+        K.block = dim3(WG);
+        K.smem = persist_tile_smem(c);
+        if (c->obj == SMM_OBJ_USER) K.mfn = c->pfn;   // (the same kernel, compiled with the user's map-reduce objective inside: user_tile_compile)
+        else if (F.persist_sh) K.fn = dense ? (const void*)k_chain_persist_tile<2, false, true> : (const void*)k_chain_persist_tile<1, false, true>;
+        else if (P.mi_pct) K.fn = dense ? (const void*)k_chain_persist_tile<2, true> : (const void*)k_chain_persist_tile<1, true>;
+        else K.fn = dense ? (const void*)k_chain_persist_tile<2> : (const void*)k_chain_persist_tile<1>;
+    }
+    return K;
+}
+// K onto the context's stream with the argument block A; in profiling mode 2 with the begin/end of this dispatch as the command processor stamps them
+void launch_persist(Ctx* c, const PersistKernel& K, PersistArgs A) {
+    void* args[] = {(void*)&A};
+    if (K.mfn && c->kev0)
+        HIPCHK(hipExtModuleLaunchKernel(K.mfn, K.grid.x * K.block.x, 1, 1, K.block.x, 1, 1, K.smem, c->stream, args, nullptr, c->kev0, c->kev1, 0));
+    else if (K.mfn) HIPCHK(hipModuleLaunchKernel(K.mfn, K.grid.x, 1, 1, K.block.x, 1, 1, (unsigned)K.smem, c->stream, args, nullptr));
+    else if (c->kev0) HIPCHK(hipExtLaunchKernel(K.fn, K.grid, K.block, args, K.smem, c->stream, c->kev0, c->kev1, 0));
+    else HIPCHK(hipLaunchKernel(K.fn, K.grid, K.block, args, K.smem, c->stream));
 }
 // can the iterations from c->iter + 1 on run as one launch of it?  At least two (a single iteration is the ordinary kernel's), behind
 // an iteration some chain kernel has completed (the launch continues from the plain state blocks: no first iteration, no uploaded
@@ -1245,7 +1278,7 @@ bool persist_sh_usable(const Ctx* c, int n_left) {
     // rank knows, or one rank would take the per-iteration kernels while its peers wait at the launches' start barrier.  The launch reports such a
     // state itself — kind 3 at its first iteration, smm_chain_persist_loc.hpp —, the ranks agree on the word and replay the step on the other forms)
     if (!(c->F.persist_sh && c->persist_on && !c->persist_broken && !c->in_repair && n_left >= 2 && c->p2p_mine)) return false;
-    if (c->p2p_ranks_here * persist_tiles_rank(c) > c->F.max_tiles) return false;   // (ranks sharing this device: not resident together)
+    if (c->p2p_ranks_here * persist_tiles_rank(c->F, c->P.N) > c->F.max_tiles) return false;   // (ranks sharing this device: not resident together)
     if (c->iter < 1 || !c->prev_open || c->exch_done || c->a2a_open) return false;
     if (c->p2p_current) return c->rec_external && (c->pending_ext || !exchange_active(c, c->iter));
     return !c->rec_external && (c->unresolved || !c->pending);
@@ -1264,6 +1297,37 @@ void persist_snapshot(Ctx* c) {
     c->snap_iter = c->iter; c->snap_cur = c->cur; c->snap_slots_iter = c->slots_iter;
     c->snap_pending = c->pending; c->snap_prev_open = c->prev_open; c->snap_unresolved = c->unresolved; c->snap_exch_done = c->exch_done;
     c->snap_valid = true;
+}
+// the argument block of a launch of the persistent kernel over iterations t0 .. t1 (pregen: the randomness comes from the window's blocks;
+// tmo: ticks a spin may last)
+PersistArgs persist_args(const Ctx* c, int t0, int t1, bool pregen, unsigned long long tmo) {
+    const KParams& P = c->P;
+    const bool sh = c->F.persist_sh;
+    const int G = sh ? P.p2p_G : 1;
+    const PrWin WL = pr_win_layout(P.Ng, P.RW, G, persist_tiles_rank(c->F, P.N));
+    PersistArgs A{};
+    A.cone_hdr = P.cone_hdr; A.cone_pairs = P.cone_pairs; A.cone_gather = P.cone_gather; A.cone_ok = P.cone_ok;
+    if (sh) {
+        for (int r = 0; r < G; ++r) A.win[r] = P.p2p_win[r] + c->prw_off;
+        A.self = c->p2p_mine + c->prw_off;
+    } else { A.win[0] = c->prw; A.self = c->prw; }
+    A.o_ctl = WL.ctl; A.o_arrive = WL.arrive; A.o_progress = WL.progress; A.o_slot = WL.slot; A.o_rec = WL.rec;
+    A.cs = P.cs; A.rec_in = c->rec[c->cur]; A.rec_out = c->rec[c->cur ^ 1]; A.vals_out = P.vals_out; A.slot8_out = P.slot8_out; A.walk_flags = P.walk_flags;
+    A.hrec = P.hrec; A.err = P.err; A.ts = P.ts;
+    A.Z = P.Z; A.lb = P.lb; A.ub = P.ub; A.mom = P.mom; A.w = P.w; A.objp = P.objp; A.dense_Bf = P.dense_Bf; A.dense_Af = P.dense_Af; A.dense_A2f = P.dense_A2f;
+    A.rb = pregen ? P.rb : nullptr;
+    A.mi_g = P.min_improve_g;
+    A.N = P.N; A.Ng = P.Ng; A.np = P.np; A.nm = P.nm; A.ns = P.ns; A.zstride = P.zstride; A.RW = P.RW; A.HW = P.HW; A.RBW = P.RBW; A.dense_nOt = P.dense_nOt;
+    A.batch_size = P.batch_size; A.failbox = (P.obj == SMM_OBJ_NORM_FAILBOX && P.objp) ? 1 : 0;
+    A.G = G; A.rank = sh ? P.p2p_rank : 0; A.offset = P.offset;
+    A.plan_t0 = P.plan_t0; A.exch_from = c->exchange_from; A.sigma_update_steps = P.sigma_update_steps; A.smpl_iters = P.smpl_iters; A.t0 = t0; A.t1 = t1;
+    A.rb_t0 = P.rb_t0; A.rb_tries = P.rb_tries; A.user_n = P.user_n;
+    A.ring_k = c->H.pr_ring_k; A.slow_tile = c->H.pr_slow_tile; A.slow_ticks = c->H.pr_slow_ticks; A.walk_first = c->unresolved ? 1 : 0;
+    A.slow_read = c->H.pr_slow_read;
+    A.tables_local = c->F.persist_sh_big ? 1 : 0; A.unit_sh = P.lean_unit == 16 ? 4 : (P.lean_unit == 8 ? 3 : 2); A.scout_after = P.scout_after; A.scout_gl = P.scout_gl;
+    A.u_lanes = c->u_lanes; A.n_udata = c->n_objp;
+    A.epoch = c->pr_epoch; A.sigma_adjust_by = P.sigma_adjust_by; A.thr = P.mi_value; A.seed = P.seed; A.tmo = tmo;
+    return A;
 }
 // iterations c->iter + 1 .. as ONE launch, as far as the look-ahead windows reach; returns how many it covers (0: not this time)
 int launch_chain_persist(Ctx* c, int n_left) {
@@ -1286,14 +1350,10 @@ int launch_chain_persist(Ctx* c, int n_left) {
     if (!c->snap_valid) persist_snapshot(c);
     ++c->pr_epoch;
     if ((c->pr_epoch & 0x7fu) == 0u) {   // the slot tags' epoch bits start over: nothing older may look current
-        if (c->F.persist == PERSIST_LOC || c->F.persist == PERSIST_TILE) {   // (a shard zeroes its own window's ring: its peers store into it only behind the launch's start barrier)
-            const PrWin WL = pr_win_layout(c->P.Ng, c->P.RW, c->F.persist_sh ? c->P.p2p_G : 1, persist_tiles_rank(c));
-            unsigned char* base = c->F.persist_sh ? c->p2p_mine + c->prw_off : c->prw;
-            HIPCHK(hipMemsetAsync(base + WL.slot, 0, WL.total - WL.slot, c->stream));
-        } else {
-            HIPCHK(hipMemsetAsync(c->P.pr_slot, 0, persist_ring_slot_bytes(c->P.Ng), c->stream));
-            HIPCHK(hipMemsetAsync(c->P.pr_rec, 0, persist_ring_rec_bytes(c->P.Ng, c->P.RW), c->stream));
-        }
+        // (a shard zeroes its own window's ring: its peers store into it only behind the launch's start barrier)
+        const PrWin WL = pr_win_layout(c->P.Ng, c->P.RW, c->F.persist_sh ? c->P.p2p_G : 1, persist_tiles_rank(c->F, c->P.N));
+        unsigned char* base = c->F.persist_sh ? c->p2p_mine + c->prw_off : c->prw;
+        HIPCHK(hipMemsetAsync(base + WL.slot, 0, WL.total - WL.slot, c->stream));
     }
     KParams& P = c->P;
     P.pr_epoch = c->pr_epoch;
@@ -1302,103 +1362,7 @@ int launch_chain_persist(Ctx* c, int n_left) {
     // tenth of that: tiles that are not resident together, a masked or partitioned device, must not look like a hang)
     // (a shard waits for its PEERS' launches at the start barrier: processes that start a second apart are late, not gone — 4 s from the start)
     const unsigned long long tmo = (c->persist_proven || c->F.persist_sh) ? P2P_TIMEOUT_TICKS : PERSIST_TMO_FIRST;
-    if (c->F.persist == PERSIST_LOC) {
-        PersistLocArgs A{};
-        const int G = c->F.persist_sh ? P.p2p_G : 1;
-        const int tiles = (P.N + NORM_CT - 1) / NORM_CT;
-        const PrWin WL = pr_win_layout(P.Ng, P.RW, G, tiles);
-        A.cone_hdr = P.cone_hdr; A.cone_pairs = P.cone_pairs; A.cone_gather = P.cone_gather; A.cone_ok = P.cone_ok;
-        for (int r = 0; r < P2P_MAXG; ++r) A.win[r] = nullptr;
-        if (c->F.persist_sh) {
-            for (int r = 0; r < G; ++r) A.win[r] = P.p2p_win[r] + c->prw_off;
-            A.self = c->p2p_mine + c->prw_off;
-        } else { A.win[0] = c->prw; A.self = c->prw; }
-        A.o_ctl = WL.ctl; A.o_arrive = WL.arrive; A.o_progress = WL.progress; A.o_slot = WL.slot; A.o_rec = WL.rec;
-        A.cs = P.cs; A.rec_in = c->rec[c->cur]; A.rec_out = c->rec[c->cur ^ 1]; A.vals_out = P.vals_out; A.slot8_out = P.slot8_out; A.walk_flags = P.walk_flags;
-        A.hrec = P.hrec; A.err = P.err; A.ts = P.ts;
-        A.Z = P.Z; A.lb = P.lb; A.ub = P.ub; A.mom = P.mom; A.w = P.w; A.objp = P.objp;
-        A.rb = pregen ? P.rb : nullptr;
-        A.N = P.N; A.Ng = P.Ng; A.offset = P.offset; A.G = G; A.rank = c->F.persist_sh ? P.p2p_rank : 0; A.ns = P.ns; A.zstride = P.zstride; A.plan_t0 = P.plan_t0;
-        A.exch_from = c->exchange_from;
-        A.sigma_update_steps = P.sigma_update_steps; A.smpl_iters = P.smpl_iters; A.t0 = t0; A.t1 = t1;
-        A.rb_t0 = P.rb_t0; A.RBW = P.RBW; A.rb_tries = P.rb_tries; A.user_n = P.user_n;
-        A.failbox = (P.obj == SMM_OBJ_NORM_FAILBOX && P.objp) ? 1 : 0;
-        A.walk_first = c->unresolved ? 1 : 0;
-        A.ring_k = c->H.pr_ring_k; A.slow_tile = c->H.pr_slow_tile; A.slow_ticks = c->H.pr_slow_ticks;
-        A.tables_local = c->F.persist_sh_big ? 1 : 0; A.unit_sh = P.lean_unit == 16 ? 4 : (P.lean_unit == 8 ? 3 : 2);
-        A.epoch = c->pr_epoch; A.sigma_adjust_by = P.sigma_adjust_by; A.thr = P.mi_value; A.seed = P.seed; A.tmo = tmo; A.mi_g = P.min_improve_g;
-        const dim3 grid(tiles), block(NORM_WG);
-        const size_t smem = persist_loc_smem_bytes(P.np);
-        auto go = [&](auto kern) { launch(c, kern, grid, block, smem, A); };
-        const bool wd = c->F.persist_wide, sh = c->F.persist_sh;
-        if (P.mi_pct) { if (P.np == 1) go(k_chain_persist_loc<1, true, false, true>); else go(k_chain_persist_loc<2, true, false, true>); }
-        else if (P.np == 1) {
-            if (wd) { if (sh) go(k_chain_persist_loc<1, true, true>); else go(k_chain_persist_loc<1, true, false>); }
-            else { if (sh) go(k_chain_persist_loc<1, false, true>); else go(k_chain_persist_loc<1, false, false>); }
-        } else {
-            if (wd) { if (sh) go(k_chain_persist_loc<2, true, true>); else go(k_chain_persist_loc<2, true, false>); }
-            else { if (sh) go(k_chain_persist_loc<2, false, true>); else go(k_chain_persist_loc<2, false, false>); }
-        }
-    } else if (c->F.persist == PERSIST_TILE) {
-        PersistTileArgs A{};
-        const int tiles = (P.N + PT_CT - 1) / PT_CT;
-        const bool sh = c->F.persist_sh;
-        const int G = sh ? P.p2p_G : 1;
-        const PrWin WL = pr_win_layout(P.Ng, P.RW, G, tiles);
-        const int kind = obj_kind(c->obj);
-        A.cone_hdr = P.cone_hdr; A.cone_pairs = P.cone_pairs; A.cone_gather = P.cone_gather; A.cone_ok = P.cone_ok;
-        for (int r = 0; r < P2P_MAXG; ++r) A.win[r] = nullptr;
-        if (sh) {
-            for (int r = 0; r < G; ++r) A.win[r] = P.p2p_win[r] + c->prw_off;
-            A.self = c->p2p_mine + c->prw_off;
-        } else { A.win[0] = c->prw; A.self = c->prw; }
-        A.o_ctl = WL.ctl; A.o_arrive = WL.arrive; A.o_progress = WL.progress; A.o_rec = WL.rec;
-        A.G = G; A.rank = sh ? P.p2p_rank : 0; A.offset = sh ? P.offset : 0;
-        A.cs = P.cs; A.rec_in = c->rec[c->cur]; A.rec_out = c->rec[c->cur ^ 1]; A.vals_out = P.vals_out; A.slot8_out = P.slot8_out; A.walk_flags = P.walk_flags;
-        A.hrec = P.hrec; A.err = P.err; A.ts = P.ts;
-        A.Z = P.Z; A.lb = P.lb; A.ub = P.ub; A.mom = P.mom; A.w = P.w; A.objp = P.objp; A.dense_Bf = P.dense_Bf; A.dense_Af = P.dense_Af; A.dense_A2f = P.dense_A2f;
-        A.rb = pregen ? P.rb : nullptr;
-        A.N = P.N; A.Ng = P.Ng; A.np = P.np; A.nm = P.nm; A.ns = P.ns; A.zstride = P.zstride; A.RW = P.RW; A.HW = P.HW; A.RBW = P.RBW; A.dense_nOt = P.dense_nOt;
-        A.batch_size = P.batch_size; A.failbox = (P.obj == SMM_OBJ_NORM_FAILBOX && P.objp) ? 1 : 0;
-        A.plan_t0 = P.plan_t0; A.exch_from = c->exchange_from; A.sigma_update_steps = P.sigma_update_steps; A.smpl_iters = P.smpl_iters; A.t0 = t0; A.t1 = t1;
-        A.rb_t0 = P.rb_t0; A.rb_tries = P.rb_tries; A.user_n = P.user_n;
-        A.ring_k = c->H.pr_ring_k; A.slow_tile = c->H.pr_slow_tile; A.slow_ticks = c->H.pr_slow_ticks; A.slow_read = c->H.pr_slow_read; A.walk_first = c->unresolved ? 1 : 0;
-        A.unit_sh = P.lean_unit == 16 ? 4 : (P.lean_unit == 8 ? 3 : 2); A.scout_after = P.scout_after; A.scout_gl = P.scout_gl;
-        A.epoch = c->pr_epoch; A.sigma_adjust_by = P.sigma_adjust_by; A.thr = P.mi_value; A.seed = P.seed; A.tmo = tmo; A.mi_g = P.min_improve_g;
-        const dim3 grid(tiles), block(WG);
-        A.u_lanes = c->u_lanes; A.n_udata = c->n_objp;
-        const size_t smem = persist_tile_smem(c);
-        auto go = [&](auto kern) { launch(c, kern, grid, block, smem, A); };
-        if (c->utfn) {   // the same kernel, compiled with the user's map-reduce objective inside (user_tile_compile)
-            void* args[] = {(void*)&A};
-            if (c->kev0) HIPCHK(hipExtModuleLaunchKernel(c->utfn, grid.x * (unsigned)WG, 1, 1, WG, 1, 1, smem, c->stream, args, nullptr, c->kev0, c->kev1, 0));
-            else HIPCHK(hipModuleLaunchKernel(c->utfn, grid.x, 1, 1, WG, 1, 1, (unsigned)smem, c->stream, args, nullptr));
-        } else if (sh) { if (kind == 2) go(k_chain_persist_tile<2, false, true>); else go(k_chain_persist_tile<1, false, true>); }
-        else if (P.mi_pct) { if (kind == 2) go(k_chain_persist_tile<2, true>); else go(k_chain_persist_tile<1, true>); }
-        else if (kind == 2) go(k_chain_persist_tile<2>); else go(k_chain_persist_tile<1>);
-    } else if (c->F.persist == PERSIST_GEN) {
-        PersistGenArgs A{};
-        A.cone_hdr = P.cone_hdr; A.cone_pairs = P.cone_pairs; A.cone_gather = P.cone_gather; A.cone_ok = P.cone_ok;
-        A.pr_slot = P.pr_slot; A.pr_rec = P.pr_rec; A.pr_progress = P.pr_progress; A.pr_ctl = P.pr_ctl;
-        A.cs = P.cs; A.rec_in = c->rec[c->cur]; A.rec_out = c->rec[c->cur ^ 1]; A.vals_out = P.vals_out; A.slot8_out = P.slot8_out; A.walk_flags = P.walk_flags;
-        A.hrec = P.hrec; A.err = P.err; A.ts = P.ts;
-        A.lb = P.lb; A.ub = P.ub; A.mom = P.mom; A.w = P.w;
-        A.rb = pregen ? P.rb : nullptr;
-        A.N = P.N; A.Ng = P.Ng; A.np = P.np; A.nm = P.nm; A.RW = P.RW; A.HW = P.HW; A.plan_t0 = P.plan_t0; A.exch_from = c->exchange_from;
-        A.sigma_update_steps = P.sigma_update_steps; A.smpl_iters = P.smpl_iters; A.t0 = t0; A.t1 = t1;
-        A.rb_t0 = P.rb_t0; A.RBW = P.RBW; A.rb_tries = P.rb_tries; A.user_n = P.user_n;
-        A.walk_first = c->unresolved ? 1 : 0;
-        A.ring_k = c->H.pr_ring_k; A.slow_tile = c->H.pr_slow_tile; A.slow_ticks = c->H.pr_slow_ticks;
-        A.epoch = c->pr_epoch; A.sigma_adjust_by = P.sigma_adjust_by; A.seed = P.seed; A.tmo = tmo;
-        A.udata = P.objp; A.n_udata = c->n_objp;
-        const dim3 grid(P.N / PG_CT), block(1024);
-        const size_t smem = persist_gen_smem_bytes(P.Ng, P.np, P.RW, P.HW) + (c->F.persist_user ? persist_gen_user_bytes() : 0);
-        if (c->F.persist_user) {   // the same kernel, compiled with the user's objective inside (user_persist_compile)
-            void* args[] = {(void*)&A};
-            if (c->kev0) HIPCHK(hipExtModuleLaunchKernel(c->upfn, grid.x * 1024u, 1, 1, 1024, 1, 1, smem, c->stream, args, nullptr, c->kev0, c->kev1, 0));
-            else HIPCHK(hipModuleLaunchKernel(c->upfn, grid.x, 1, 1, 1024, 1, 1, (unsigned)smem, c->stream, args, nullptr));
-        } else launch(c, k_chain_persist_gen, grid, block, smem, A);
-    }
+    launch_persist(c, persist_kernel(c, c->F), persist_args(c, t0, t1, pregen, tmo));
     c->cur ^= 1;
     ++c->persist_launches;
     return t1 - t0 + 1;
@@ -1817,7 +1781,7 @@ Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
     }
     // ... all of its tiles resident at once, or it is not taken (per_cu 0 also where a user objective's kernel did not compile)
     if (F.persist != PERSIST_NONE && dev.per_cu >= 0) {
-        const int tiles = F.persist == PERSIST_GEN ? N / PG_CT : F.persist == PERSIST_LOC ? (N + NORM_CT - 1) / NORM_CT : (N + PT_CT - 1) / PT_CT;
+        const int tiles = persist_tiles_rank(F, N);
         if (F.persist != PERSIST_GEN) F.max_tiles = dev.per_cu * n_cus;
         if (tiles > dev.per_cu * n_cus) {
             F.persist = PERSIST_NONE;
@@ -1840,57 +1804,31 @@ Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
 // the persistent kernel that is the candidate of F, asked how many of its workgroups a CU holds — with its dynamic LDS set first, as the
 // launches want it; a user objective's kernel is compiled (once per registered objective) and loaded here.  0: not available
 int persist_occupancy(Ctx* c, const Forms& F, int objective_id) {
-    const KParams& P = c->P;
-    int per_cu = 0;
-    if (F.persist == PERSIST_GEN && F.persist_user) {   // the kernel with the user's objective inside (user_persist_compile)
+    if (F.persist_user || (F.persist == PERSIST_TILE && c->obj == SMM_OBJ_USER)) {   // (user_persist_compile / user_tile_compile)
+        const bool tile = F.persist == PERSIST_TILE;
         {
             std::lock_guard<std::mutex> lock(g_user_mutex);
             UserObjective& u = g_user_objectives[objective_id - SMM_OBJ_USER_BASE];
-            if (!user_persist_compile(u)) {
-                if (getenv("SMMHIP_VERBOSE")) fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n", u.persist_log.c_str());
+            if (!(tile ? user_tile_compile(u, F.persist_sh) : user_persist_compile(u))) {
+                if (getenv("SMMHIP_VERBOSE"))
+                    fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n",
+                            (tile ? (F.persist_sh ? u.tile_sh_log : u.tile_log) : u.persist_log).c_str());
                 return 0;
             }
-            HIPCHK(hipModuleLoadData(&c->upmod, u.persist_code.data()));
+            HIPCHK(hipModuleLoadData(&c->pmod, (tile ? (F.persist_sh ? u.tile_sh_code : u.tile_code) : u.persist_code).data()));
         }
-        HIPCHK(hipModuleGetFunction(&c->upfn, c->upmod, "smm_user_persist_kernel"));
-        const size_t smem = persist_gen_smem_bytes(P.Ng, P.np, P.RW, P.HW) + persist_gen_user_bytes();
-        (void)hipFuncSetAttribute((const void*)c->upfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);   // (a module's function: where the runtime takes it)
+        HIPCHK(hipModuleGetFunction(&c->pfn, c->pmod, tile ? "smm_user_persist_tile_kernel" : "smm_user_persist_kernel"));
+    }
+    const PersistKernel K = persist_kernel(c, F);
+    int per_cu = 0;
+    if (K.mfn) {
+        // (a module's function: not every runtime takes the attribute this way; the launch asks for what it needs)
+        (void)hipFuncSetAttribute((const void*)K.mfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K.smem);
         (void)hipGetLastError();
-        HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->upfn, 1024, smem));
-    } else if (F.persist == PERSIST_GEN) {
-        const size_t smem = persist_gen_smem_bytes(P.Ng, P.np, P.RW, P.HW);
-        HIPCHK(hipFuncSetAttribute((const void*)k_chain_persist_gen, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_chain_persist_gen, 1024, smem));
-    } else if (F.persist == PERSIST_LOC) {
-        const size_t smem = persist_loc_smem_bytes(P.np);
-        const void* fn = persist_loc_fn(P.np, F.persist_wide, F.persist_sh, P.mi_pct != 0);
-        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NORM_WG, smem));
-    } else if (F.persist == PERSIST_TILE) {
-        const size_t smem = persist_tile_smem(c);
-        if (c->obj == SMM_OBJ_USER) {   // the tile kernel with the user's map-reduce objective inside (user_tile_compile)
-            {
-                std::lock_guard<std::mutex> lock(g_user_mutex);
-                UserObjective& u = g_user_objectives[objective_id - SMM_OBJ_USER_BASE];
-                if (!user_tile_compile(u, F.persist_sh)) {
-                    if (getenv("SMMHIP_VERBOSE"))
-                        fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n", (F.persist_sh ? u.tile_sh_log : u.tile_log).c_str());
-                    return 0;
-                }
-                HIPCHK(hipModuleLoadData(&c->utmod, (F.persist_sh ? u.tile_sh_code : u.tile_code).data()));
-            }
-            HIPCHK(hipModuleGetFunction(&c->utfn, c->utmod, "smm_user_persist_tile_kernel"));
-            (void)hipFuncSetAttribute((const void*)c->utfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);   // (a module's function: not every runtime takes it this way; the launch asks for what it needs)
-            (void)hipGetLastError();
-            HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->utfn, WG, smem));
-        } else {
-            const int kind = obj_kind(c->obj);
-            const void* fn = F.persist_sh ? (kind == 2 ? (const void*)k_chain_persist_tile<2, false, true> : (const void*)k_chain_persist_tile<1, false, true>)
-                           : P.mi_pct ? (kind == 2 ? (const void*)k_chain_persist_tile<2, true> : (const void*)k_chain_persist_tile<1, true>)
-                                      : (kind == 2 ? (const void*)k_chain_persist_tile<2> : (const void*)k_chain_persist_tile<1>);
-            HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, WG, smem));
-        }
+        HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, K.mfn, K.block.x, K.smem));
+    } else {
+        HIPCHK(hipFuncSetAttribute(K.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K.smem));
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, K.fn, K.block.x, K.smem));
     }
     return per_cu;
 }
@@ -1907,22 +1845,13 @@ void alloc_cones(Ctx* c, Tables& P, size_t tiles, bool with_gather) {
     HIPCHK(hipMemset((void*)P.cone_ok, 0, W * 4));
 }
 
-// the persistent form's ring — k_chain_persist_gen's in KParams, the others' in one window (pr_win_layout; a shard's lives in its p2p
-// window: smm_bgp_p2p_init) — and the state persist_repair rolls back to (after the history's fill: hist_fill is a row of it)
+// the persistent form's ring — one window (pr_win_layout; a shard's lives in its p2p window: smm_bgp_p2p_init) — and the state
+// persist_repair rolls back to (after the history's fill: hist_fill is a row of it)
 void alloc_persist(Ctx* c) {
     KParams& P = c->P;
     const size_t N = P.N;
-    if (c->F.persist == PERSIST_GEN) {
-        P.pr_slot = (uint2*)dalloc<unsigned char>(c, persist_ring_slot_bytes(P.Ng));
-        P.pr_rec = (uint4*)dalloc<unsigned char>(c, persist_ring_rec_bytes(P.Ng, P.RW));
-        P.pr_progress = dalloc<uint32_t>(c, N / PG_CT);
-        P.pr_ctl = dalloc<uint32_t>(c, 4);
-        HIPCHK(hipMemset(P.pr_slot, 0, persist_ring_slot_bytes(P.Ng)));
-        HIPCHK(hipMemset(P.pr_rec, 0, persist_ring_rec_bytes(P.Ng, P.RW)));
-        HIPCHK(hipMemset(P.pr_progress, 0, N / PG_CT * 4));
-        HIPCHK(hipMemset(P.pr_ctl, 0, 16));
-    } else if (!c->F.persist_sh) {
-        const PrWin WL = pr_win_layout(P.Ng, P.RW, 1, c->F.cone_tiles);
+    if (!c->F.persist_sh) {
+        const PrWin WL = pr_win_layout(P.Ng, P.RW, 1, persist_tiles_rank(c->F, P.N));
         c->prw = dalloc<unsigned char>(c, WL.total);
         HIPCHK(hipMemset(c->prw, 0, WL.total));
     }
@@ -2037,8 +1966,7 @@ void smm_ctx_destroy(void* ctx) {
     if (c->st_scr) (void)hipFree(c->st_scr);
     if (c->st_res) (void)hipFree(c->st_res);
     if (c->umod) (void)hipModuleUnload(c->umod);
-    if (c->upmod) (void)hipModuleUnload(c->upmod);
-    if (c->utmod) (void)hipModuleUnload(c->utmod);
+    if (c->pmod) (void)hipModuleUnload(c->pmod);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->pev) (void)hipEventDestroy(e);
@@ -2680,7 +2608,7 @@ int smm_bgp_p2p_init(void* ctx, void* ipc_handle_out, void** window_dev_out) {
             size_t total = L.total;
             if (c->F.persist_sh) {
                 c->prw_off = (L.total + 255) & ~(size_t)255;
-                total = c->prw_off + pr_win_layout(P.Ng, P.RW, c->a2a_G, persist_tiles_rank(c)).total;   // (the ring: RW granules of this context's records)
+                total = c->prw_off + pr_win_layout(P.Ng, P.RW, c->a2a_G, persist_tiles_rank(c->F, c->P.N)).total;   // (the ring: RW granules of this context's records)
             }
             void* w = nullptr;
             HIPCHK(hipMalloc(&w, total));
@@ -3344,8 +3272,8 @@ int smm_describe(void* ctx, char* out, int32_t cap) {
     const char* pers = c->F.persist == PERSIST_NONE ? "none" : c->F.persist == PERSIST_LOC ? (c->F.persist_sh ? (c->F.persist_sh_big ? (c->F.persist_wide ? "loc_wide_shard_bigplan" : "loc_shard_bigplan")
                                                                                                     : (c->F.persist_wide ? "loc_wide_shard" : "loc_shard"))
                                                                               : (c->F.persist_wide ? "loc_wide" : "loc"))
-                     : c->F.persist == PERSIST_TILE ? (c->F.persist_sh ? (c->utfn ? "tile_user_shard" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2_shard" : "tile_dense_shard") : "tile_sim_shard")
-                                                                        : (c->utfn ? "tile_user" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2" : "tile_dense") : "tile_sim"))
+                     : c->F.persist == PERSIST_TILE ? (c->F.persist_sh ? (c->pfn ? "tile_user_shard" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2_shard" : "tile_dense_shard") : "tile_sim_shard")
+                                                                        : (c->pfn ? "tile_user" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2" : "tile_dense") : "tile_sim"))
                      : c->F.persist_user ? "gen_user" : "gen";
     snprintf(out, (size_t)cap, "chain=%s walk=%s exchange=%s persistent=%s plan=%s window=%d", chain, walk, xk[c->F.xk], pers,
              c->F.plan == PLAN_BIG ? (c->F.plan_ahead ? "big_ahead" : "big") : c->F.plan == PLAN_LDS ? "lds" : "none", c->F.plan_cap);
