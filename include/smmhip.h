@@ -417,6 +417,51 @@ typedef struct {            /* caller-allocated; any pointer may be NULL = not c
 int  smm_get_chain_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only,
                          const double* probs, int32_t n_probs, smm_chain_stats_t* out);
 
+/* Covariances of the chains' draws and the proposal factor between steps — adaptive Metropolis (Haario et al.) on top of chol_L: a
+ * pilot run, then each chain's proposal shaped by the covariance of its own draws, without leaving the device.
+ *
+ * smm_get_chain_cov: the covariance of every LOCAL chain's selected draws over the 0-based iterations [t0, t1), selected exactly as
+ * smm_get_chain_stats selects them (accepted_only != 0: params(c), AlgoBGP.jl:120-131).  unit_space != 0: the draws mapped to [0, 1]
+ * first, u = (x - lb) / (ub - lb) (mapto_01, mprob.jl:248, the kernels' own arithmetic) — the space the proposal lives in; 0: the
+ * parameters themselves.  count [N], mean [np][N], cov [np][np][N] (both triangles); any output may be NULL.  Works on any context;
+ * read-only: it settles, flushes and synchronises like smm_get_chain_stats and changes no state, history or generator.  It uses
+ * smm_get_chain_stats' scratch, grown where needed to one chain's maxiter x (8 np + 4) bytes, plus ((np + 1) np + 1) N x 8 + 16 N bytes
+ * of results.  SMM_ERR_INVALID_ARG: NULL ctx, a bad window (0 <= t0 <= t1 <= completed iterations).
+ *
+ * Numerical contract (every operation rounded on its own, no fma).  u = the compacted column (mapped when unit_space != 0), m = count:
+ *   mean_j  = the chain-stats mean of column j (the pw sum in chunks of 8192, divided by m)
+ *   d_j[i]  = u_j[i] - mean_j
+ *   cov_jk  = S(d_j[i] * d_k[i]) / (m - 1), S = the chain-stats chunked pairwise sum over i: bit for bit np.sum(dj * dk) / (m - 1) on
+ *             contiguous float64 columns; cov_kj is the same value.  m < 2: NaN.  A NaN among the draws propagates.
+ *   tau     = (((0 + C_00) + C_11) + ...) / np
+ *   chol    : for k = 0..np-1, j = 0..k: s = A_kj; s = s - L_ki * L_ji for i = 0..j-1 in that order; j == k: L_kk = sqrt(s), failing
+ *             when !(s > 0); otherwise L_kj = s / L_jj.
+ *
+ * The three proposal calls need a context created with chol_L (otherwise SMM_ERR_INVALID_ARG).  The factor(s) are [np][np] for a shared
+ * factor, [N][np][np] for per-chain factors (the LOCAL chains, global rows chain_offset .. chain_offset + N - 1: a shard reads and writes
+ * only its own chains' rows, the only rows its kernels read), row-major.  A context's forms do not change (smm_describe is the same):
+ * installing a factor overwrites the device buffer the per-iteration kernels read, on the context's stream.
+ *
+ * smm_get_proposal: the installed factor(s), zeros above the diagonal.
+ * smm_set_proposal: install factor(s) between steps (the matrix form of set_sigma!, AlgoBGP.jl:218-219); entries above the diagonal are
+ *   ignored.  SMM_ERR_INVALID_ARG (nothing installed): a non-finite entry on or below the diagonal, a diagonal entry not > 0.  On a
+ *   sharded context with a shared factor every rank must install the same factor.
+ * smm_adapt_proposal: per-chain contexts only (chol_per_chain = 1; a shared factor has no single history to take it from): for every
+ *   local chain C = smm_get_chain_cov(..., unit_space = 1) of the window, A = C / tau (normalize != 0) or A = C, A_kk = A_kk + ridge,
+ *   L = chol(A), installed where the chain's status is 0.  status [N] (may be NULL): 0 installed; 1 fewer than min_draws selected
+ *   draws; 2 a non-finite entry in C; 3 not positive definite (a pivot !(s > 0)).  A chain with a non-zero status keeps its factor.
+ *   SMM_ERR_INVALID_ARG: a bad window, min_draws < 2, ridge < 0 or not finite.
+ *
+ * Ordering and failures: smm_set_proposal and smm_adapt_proposal settle, flush and synchronise before they act, so an smm_bgp_step_async
+ * in flight is ordered before them.  A hard error standing on the context (AlgoBGP.jl:341,409) — reported before or not — is returned
+ * by them and nothing is installed; it counts as told, so the smm_set_state that recovers from it goes through at its first call. */
+int  smm_get_chain_cov(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, int32_t unit_space,
+                       int32_t* count /* [N] */, double* mean /* [np][N] */, double* cov /* [np][np][N] */);
+int  smm_get_proposal(void* ctx, double* L);
+int  smm_set_proposal(void* ctx, const double* L);
+int  smm_adapt_proposal(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, int32_t min_draws,
+                        int32_t normalize, double ridge, int32_t* status /* [N] */);
+
 int  smm_get_state(void* ctx, smm_state_t* out);
 /* smm_set_state is also the recovery from a hard error (AlgoBGP.jl:341,409): the context steps again from the uploaded state.  A failure that
  * no entry point has handed to the caller yet — raised on the device by asynchronous steps nobody synchronised; the state readers do not

@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats
+export hip_chain_stats, hip_chain_cov, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
 const ABI_VERSION = 3
@@ -164,6 +164,7 @@ mutable struct HipBGP
     np::Int
     nm::Int
     maxiter::Int
+    chol::Int        # the proposal factor: 0 none (isotropic), 1 shared, 2 per chain
 end
 
 function hip_destroy!(h::HipBGP)
@@ -219,7 +220,7 @@ function hip_create(init::Vector{Float64}, lb::Vector{Float64}, ub::Vector{Float
                    p, o, C_NULL, ctx)
         rc == 0 || throw(SMMHipError(Int(rc), last_error(Ptr{Cvoid}(C_NULL))))
     end
-    h = HipBGP(ctx[], Int(N), np, nm, Int(maxiter))
+    h = HipBGP(ctx[], Int(N), np, nm, Int(maxiter), chol_L === nothing ? 0 : per_chain == 1 ? 2 : 1)
     finalizer(hip_destroy!, h)
     return h
 end
@@ -336,6 +337,67 @@ function hip_chain_stats(h::HipBGP, t0::Integer, t1::Integer; accepted_only::Boo
     end
     return (count = count, mean = mean, median = median, quantile = quant, best_value = bestv, best_iter = besti,
             n_exchanged = nex, most_exchanged_with = most)
+end
+
+"""
+    hip_chain_cov(h, t0, t1; accepted_only = true, unit_space = false) -> NamedTuple
+
+Covariance of every chain's selected draws over iterations `t0+1 .. t1`, on the device (`smm_get_chain_cov`): `count[chain]`,
+`mean[chain, k]`, `cov[chain, j, k]`.  `unit_space` maps the draws to [0, 1] first (`mapto_01`, the space of the proposal).
+NumPy's summation (include/smmhip.h).
+"""
+function hip_chain_cov(h::HipBGP, t0::Integer, t1::Integer; accepted_only::Bool = true, unit_space::Bool = false)
+    N, np = h.N, h.np
+    count = Vector{Int32}(undef, N); mean = Matrix{Float64}(undef, N, np); cov = Array{Float64}(undef, N, np, np)
+    GC.@preserve count mean cov begin
+        check(h.ctx, ccall(sym(:smm_get_chain_cov), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}),
+                           h.ctx, t0, t1, accepted_only ? 1 : 0, unit_space ? 1 : 0, pointer(count), pointer(mean), pointer(cov)))
+    end
+    return (count = count, mean = mean, cov = cov)   # (the header's [np][N] / [np][np][N] row-major = these column-major arrays)
+end
+
+# the factor(s) between the header's row-major [np][np] / [N][np][np] and Julia's L[k, j] / L[k, j, c]
+proposal_length(h::HipBGP) = (h.chol == 2 ? h.N : 1) * h.np * h.np
+
+"""
+    hip_get_proposal(h) -> Array
+
+The installed proposal factor(s) (`smm_get_proposal`): `L[k, j]` (shared) or `L[k, j, c]` (per chain, the context's chains).
+"""
+function hip_get_proposal(h::HipBGP)
+    h.chol == 0 && throw(ArgumentError("the context has no proposal factor: create it with chol_L"))
+    buf = Vector{Float64}(undef, proposal_length(h))
+    GC.@preserve buf check(h.ctx, ccall(sym(:smm_get_proposal), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h.ctx, pointer(buf)))
+    return h.chol == 2 ? permutedims(reshape(buf, h.np, h.np, h.N), (2, 1, 3)) : permutedims(reshape(buf, h.np, h.np), (2, 1))
+end
+
+"""
+    hip_set_proposal!(h, L)
+
+Install proposal factor(s) between steps (`smm_set_proposal`, the matrix form of `set_sigma!`): `L[k, j]` (shared; the same on
+every shard) or `L[k, j, c]` (per chain).  Entries above the diagonal are ignored.
+"""
+function hip_set_proposal!(h::HipBGP, L::Array{Float64})
+    want = h.chol == 2 ? (h.np, h.np, h.N) : (h.np, h.np)
+    size(L) == want || throw(ArgumentError("the factor must be $(want)"))
+    Lrow = ndims(L) == 3 ? vec(permutedims(L, (2, 1, 3))) : vec(permutedims(L, (2, 1)))
+    GC.@preserve Lrow check(h.ctx, ccall(sym(:smm_set_proposal), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h.ctx, pointer(Lrow)))
+    return nothing
+end
+
+"""
+    hip_adapt_proposal!(h, t0, t1; accepted_only = true, min_draws = np + 1, normalize = true, ridge = 1e-8) -> Vector{Int32}
+
+Every chain's factor from the covariance of its own draws of iterations `t0+1 .. t1` in [0, 1]-space (`smm_adapt_proposal`,
+per-chain factors only): the status of each chain — 0 installed, 1 fewer than `min_draws` draws, 2 a non-finite covariance,
+3 not positive definite (the chain keeps its factor).
+"""
+function hip_adapt_proposal!(h::HipBGP, t0::Integer, t1::Integer; accepted_only::Bool = true, min_draws::Integer = h.np + 1,
+                             normalize::Bool = true, ridge::Real = 1e-8)
+    status = Vector{Int32}(undef, h.N)
+    GC.@preserve status check(h.ctx, ccall(sym(:smm_adapt_proposal), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cdouble, Ptr{Int32}),
+                                           h.ctx, t0, t1, accepted_only ? 1 : 0, min_draws, normalize ? 1 : 0, Float64(ridge), pointer(status)))
+    return status
 end
 
 "per-chain state: what `save` / `readMalgo` / `restart!` need besides the history (AlgoAbstract.jl:83-102)"

@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, adapt_proposal!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -109,6 +109,10 @@ function reference_chains(m::MProb, opts::Dict, N::Int, temps::Vector{Float64}, 
                              batch_size = get(opts, "batch_size", length(m.params_to_sample))) for i in 1:N]
 end
 
+# opts["chol_L"]: nothing, a factor L[k, j] / L[k, j, c], or :identity — one identity factor per chain: the isotropic kernel bit for bit,
+# and factors that adapt_proposal! can reshape
+chol_opt(L, np::Int, N::Int) = L === :identity ? repeat([Float64(k == j) for k in 1:np, j in 1:np], 1, 1, N) : L
+
 """
     hip_context(m, opts; N_local, chain_offset, device) -> (hip, N, temps, mi, acc, dist_fun, dist_id, pnames, mnames)
 
@@ -140,7 +144,7 @@ function hip_context(m::MProb, opts::Dict; N_local::Int = Int(opts["N"]), chain_
                             batch_size = Int(get(opts, "batch_size", length(init))),
                             seed = Int(get(opts, "seed", 12)), device = device,
                             N = N_local, N_global = N, chain_offset = chain_offset,
-                            chol_L = get(opts, "chol_L", nothing), dist_fun = dist_id)
+                            chol_L = chol_opt(get(opts, "chol_L", nothing), length(init), N), dist_fun = dist_id)
     return hip, N, temps, mi, acc, dist_fun, dist_id, pnames, mnames
 end
 
@@ -319,6 +323,22 @@ function chain_stats(algo::MAlgoBGPHip; t0::Integer = 0, t1 = nothing, accepted_
     flush_steps!(algo)
     hip = getfield(algo, :hip)
     return SMMHip.hip_chain_stats(hip, t0, t1 === nothing ? SMMHip.hip_iter(hip) : t1; accepted_only = accepted_only, probs = probs)
+end
+
+"""
+    adapt_proposal!(algo; t0 = 0, t1 = nothing, accepted_only = true, min_draws = np + 1, normalize = true, ridge = 1e-8)
+
+Adaptive Metropolis between runs: each chain's proposal factor from the covariance of its own draws of iterations `t0+1 .. t1`
+(default: every completed one), computed and installed on the device (`SMMHip.hip_adapt_proposal!`).  Needs per-chain factors
+(`opts["chol_L"] = :identity` or `L[k, j, c]`).  Returns the per-chain status (0 installed).  Not a method of `SMM`: the reference
+has no such function.
+"""
+function adapt_proposal!(algo::MAlgoBGPHip; t0::Integer = 0, t1 = nothing, accepted_only::Bool = true, min_draws = nothing,
+                         normalize::Bool = true, ridge::Real = 1e-8)
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    return SMMHip.hip_adapt_proposal!(hip, t0, t1 === nothing ? SMMHip.hip_iter(hip) : t1; accepted_only = accepted_only,
+                                      min_draws = min_draws === nothing ? hip.np + 1 : min_draws, normalize = normalize, ridge = ridge)
 end
 
 "`summary(m::MAlgoBGP)` (AlgoBGP.jl:541-550) on the synced chains"

@@ -144,6 +144,10 @@ SYMBOLS = [
     ("smm_get_history", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(smm_history_t)]),
     ("smm_get_chain_stats", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32,
                                       C.POINTER(smm_chain_stats_t)]),
+    ("smm_get_chain_cov", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
+    ("smm_get_proposal", C.c_int, [C.c_void_p, c_double_p]),
+    ("smm_set_proposal", C.c_int, [C.c_void_p, c_double_p]),
+    ("smm_adapt_proposal", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, c_int32_p]),
     ("smm_get_state", C.c_int, [C.c_void_p, C.POINTER(smm_state_t)]),
     ("smm_set_state", C.c_int, [C.c_void_p, C.POINTER(smm_state_t), C.POINTER(smm_history_t)]),
     ("smm_get_timing", C.c_int, [C.c_void_p, C.POINTER(smm_timing_t)]),

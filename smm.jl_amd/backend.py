@@ -130,6 +130,9 @@ class BGPContext:
             msg = self._fn("last_error")(None)
             raise A.SMMHipError(rc, msg.decode() if msg else "ctx_create failed")
         self.N, self.np, self.nm = opts.N, problem.np, problem.nm
+        # the proposal factor's layout, fixed at creation like the sizes above (the caller may reuse opts for other contexts):
+        # None (isotropic), "shared" [np][np] or "per_chain" [N][np][np] (the local chains)
+        self.proposal_layout = None if opts.chol_L is None else ("shared" if opts.chol_L.ndim == 2 else "per_chain")
 
     def _fn(self, name):
         return getattr(self._lib, self._p + name)
@@ -259,6 +262,45 @@ class BGPContext:
         self._check(self._fn("get_chain_stats")(self._ctx, int(t0), int(t1), int(bool(accepted_only)), A.dptr(p) if len(p) else None,
                                                 len(p), C.byref(s)))
         return r
+
+    def chain_cov(self, t0=0, t1=None, accepted_only=True, unit_space=False):
+        """covariance of every local chain's selected draws over iterations [t0, t1), on the device (smm_get_chain_cov,
+        include/smmhip.h): (count [N], mean [np][N], cov [np][np][N]); unit_space: the draws mapped to [0, 1] first"""
+        t1 = self.state().iter if t1 is None else t1
+        N, np_ = self.N, self.np
+        count, mean, cov = np.empty(N, np.int32), np.empty((np_, N)), np.empty((np_, np_, N))
+        self._check(self._fn("get_chain_cov")(self._ctx, int(t0), int(t1), int(bool(accepted_only)), int(bool(unit_space)),
+                                              count.ctypes.data_as(A.c_int32_p), A.dptr(mean), A.dptr(cov)))
+        return count, mean, cov
+
+    def _proposal_shape(self):
+        if self.proposal_layout is None:
+            return None
+        return (self.np, self.np) if self.proposal_layout == "shared" else (self.N, self.np, self.np)
+
+    def proposal(self):
+        """the installed proposal factor(s): [np][np] (shared) or [N][np][np] (the local chains), zeros above the diagonal"""
+        shape = self._proposal_shape()
+        L = np.empty(shape if shape is not None else (self.np, self.np))
+        self._check(self._fn("get_proposal")(self._ctx, A.dptr(L)))
+        return L
+
+    def set_proposal(self, L):
+        """install proposal factor(s) of proposal()'s shape between steps (smm_set_proposal); above the diagonal is ignored"""
+        shape = self._proposal_shape()
+        L = A.f64(L)
+        if shape is not None and L.shape != shape:
+            raise ValueError("set_proposal: the factor must be %s, got %s" % (shape, L.shape))
+        self._check(self._fn("set_proposal")(self._ctx, A.dptr(L)))
+
+    def adapt_proposal(self, t0, t1, accepted_only=True, min_draws=None, normalize=True, ridge=1e-8):
+        """each local chain's factor from the covariance of its own draws of [t0, t1) in [0, 1]-space (smm_adapt_proposal): returns
+        status [N] — 0 installed, 1 fewer than min_draws (default np + 1) draws, 2 non-finite covariance, 3 not positive definite"""
+        status = np.empty(self.N, np.int32)
+        md = self.np + 1 if min_draws is None else int(min_draws)
+        self._check(self._fn("adapt_proposal")(self._ctx, int(t0), int(t1), int(bool(accepted_only)), md, int(bool(normalize)),
+                                               float(ridge), status.ctypes.data_as(A.c_int32_p)))
+        return status
 
     def state(self):
         sb = A.StateBuffers(self.N, self.np, self.nm)

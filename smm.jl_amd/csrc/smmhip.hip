@@ -67,6 +67,7 @@ using namespace smm;
 #include "smm_exchange.hpp"
 #include "smm_cone_big.hpp"
 #include "smm_stats.hpp"
+#include "smm_cov.hpp"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -559,6 +560,9 @@ struct Ctx {
     size_t st_scr_bytes = 0;
     void* st_res = nullptr;
     size_t st_res_bytes = 0;
+    // smm_get_chain_cov / smm_adapt_proposal: the results of a call (grown to the largest call's; the columns use st_scr)
+    void* cv_res = nullptr;
+    size_t cv_res_bytes = 0;
     void* p2p_opened[P2P_MAXG] = {};           // peers' windows opened through HIP IPC (closed with the context)
     unsigned p2p_attached = 0;                 // bit r: rank r's window is known
     unsigned long long p2p_seq = 0;            // pushes so far (every rank counts the same)
@@ -1965,6 +1969,7 @@ void smm_ctx_destroy(void* ctx) {
     if (c->p2p_mine) (void)hipFree(c->p2p_mine);
     if (c->st_scr) (void)hipFree(c->st_scr);
     if (c->st_res) (void)hipFree(c->st_res);
+    if (c->cv_res) (void)hipFree(c->cv_res);
     if (c->umod) (void)hipModuleUnload(c->umod);
     if (c->pmod) (void)hipModuleUnload(c->pmod);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -3113,6 +3118,178 @@ int smm_get_chain_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only
         if (out->n_exchanged) memcpy(out->n_exchanged, hi + N, N * 4);
         if (out->best_iter) memcpy(out->best_iter, hi + 2 * N, N * 4);
         if (out->most_exchanged_with) memcpy(out->most_exchanged_with, hi + 3 * N, N * 4);
+    } catch (const std::string& m) {
+        return fail(c, SMM_ERR_HIP, m);
+    }
+    return SMM_OK;
+}
+
+// --- covariances of the chains' draws, and the proposal factor between steps (smm_cov.hpp) ---------------------------------------------
+
+// the covariance of every local chain's selected draws over [t0, t1) on the device: count [N], mean [np][N], cov [np][np][N] in c->cv_res
+// (status [N] behind them, for smm_adapt_proposal).  The caller has settled, flushed and synchronised, and checked the window.
+struct CovRes { int* count; double* mean; double* cov; int* status; };
+static CovRes chain_cov_device(Ctx* c, int t0, int t1, int accepted_only, int unit_space) {
+    const KParams& P = c->P;
+    const size_t N = P.N, np = P.np;
+    const int n = t1 - t0;
+    // doubles mean[np][N], cov[np][np][N], bestv[N]; ints count, nex, besti, status [N]
+    const size_t nd = np * N + np * np * N + N, rbytes = nd * 8 + 4 * N * 4;
+    if (rbytes > c->cv_res_bytes) {
+        if (c->cv_res) { HIPCHK(hipFree(c->cv_res)); c->cv_res = nullptr; c->cv_res_bytes = 0; }
+        HIPCHK(hipMalloc(&c->cv_res, rbytes));
+        c->cv_res_bytes = rbytes;
+    }
+    CovRes r;
+    r.mean = (double*)c->cv_res;
+    r.cov = r.mean + np * N;
+    double* d_bestv = r.cov + np * np * N;
+    r.count = (int*)(d_bestv + N);
+    int* d_nex = r.count + N;
+    int* d_besti = d_nex + N;
+    r.status = d_besti + N;
+    if (n == 0) {   // nothing selected: count 0, mean and cov NaN
+        HIPCHK(hipMemsetAsync(r.count, 0, N * 4, c->stream));
+        std::vector<double> nan((np + np * np) * N, NAN);
+        HIPCHK(hipMemcpyAsync(r.mean, nan.data(), nan.size() * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return r;
+    }
+    // every parameter of a chain at once: the scratch holds at least one chain's columns of the whole capacity
+    const size_t one = (size_t)P.T * (8 * np + 4), need = std::max(chain_stats_scratch_bytes(P), one);
+    if (c->st_scr && c->st_scr_bytes < one) { HIPCHK(hipFree(c->st_scr)); c->st_scr = nullptr; c->st_scr_bytes = 0; }
+    if (!c->st_scr) {
+        c->st_scr_bytes = need;
+        HIPCHK(hipMalloc(&c->st_scr, c->st_scr_bytes));
+    }
+    const size_t per_chain = (size_t)n * (8 * np + 4);
+    const int Nb = (int)std::min(N, c->st_scr_bytes / per_chain);
+    const int lds_n = std::min(STATS_LDS_N, 1 << (int)ceil(log2((double)std::max(n, 2))));
+    const int nt = ((int)np + COV_T - 1) / COV_T, ntiles = nt * (nt + 1) / 2;
+    HIPCHK(hipFuncSetAttribute((const void*)k_cov_center, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    for (int c0 = 0; c0 < (int)N; c0 += Nb) {
+        const int nb = std::min(Nb, (int)N - c0);
+        double* col = (double*)c->st_scr;
+        int* pcol = (int*)(col + np * nb * n);
+        hipLaunchKernelGGL(k_stats_gather, dim3(nb), dim3(STATS_WG), 0, c->stream, (const double*)P.hrec, (int)N, P.HW, t0, n,
+                           (int)(accepted_only != 0), c0, nb, 0, (int)np, 1, col, pcol, r.count, d_nex, d_bestv, d_besti);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_cov_center, dim3(nb, np), dim3(STATS_WG), (size_t)lds_n * 8, c->stream, col, n, (int)N, c0, nb,
+                           (int)(unit_space != 0), P.lb, P.ub, (const int*)r.count, r.mean);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_cov_pairs, dim3(nb, ntiles), dim3(COV_WG), 0, c->stream, (const double*)col, n, (int)N, c0, nb, (int)np,
+                           (const int*)r.count, r.cov);
+        HIPCHK(hipGetLastError());
+    }
+    return r;
+}
+
+static bool cov_window_ok(Ctx* c, int t0, int t1) { return !(t0 < 0 || t1 < t0 || t1 > c->iter); }
+
+int smm_get_chain_cov(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, int32_t unit_space, int32_t* count, double* mean,
+                      double* cov) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return SMM_ERR_INVALID_ARG;
+    try {
+        HIPCHK(hipSetDevice(c->device));
+        settle_persist(c);
+        flush(c);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (!cov_window_ok(c, t0, t1)) return fail(c, SMM_ERR_INVALID_ARG, "window must satisfy 0 <= t0 <= t1 <= completed iterations");
+        const size_t N = c->P.N, np = c->P.np;
+        const CovRes r = chain_cov_device(c, t0, t1, accepted_only, unit_space);
+        if (count) HIPCHK(hipMemcpyAsync(count, r.count, N * 4, hipMemcpyDeviceToHost, c->stream));
+        if (mean) HIPCHK(hipMemcpyAsync(mean, r.mean, np * N * 8, hipMemcpyDeviceToHost, c->stream));
+        if (cov) HIPCHK(hipMemcpyAsync(cov, r.cov, np * np * N * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    } catch (const std::string& m) {
+        return fail(c, SMM_ERR_HIP, m);
+    }
+    return SMM_OK;
+}
+
+// doubles of the factor(s) a caller reads or writes: [np][np] shared, [N][np][np] per chain (the local chains' rows)
+static size_t proposal_doubles(const KParams& P) { return (size_t)(P.chol_per_chain ? P.N : 1) * P.np * P.np; }
+static double* proposal_rows(const KParams& P) {
+    return (double*)P.chol_L + (P.chol_per_chain ? (size_t)P.offset * P.np * P.np : 0);
+}
+
+int smm_get_proposal(void* ctx, double* L) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !L) return SMM_ERR_INVALID_ARG;
+    const KParams& P = c->P;
+    if (!P.chol_L) return fail(c, SMM_ERR_INVALID_ARG, "the context has no proposal factor: create it with chol_L");
+    try {
+        HIPCHK(hipSetDevice(c->device));
+        const size_t n = proposal_doubles(P), np = P.np;
+        HIPCHK(hipMemcpyAsync(L, proposal_rows(P), n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (size_t b = 0; b < n; b += np * np)   // (what lies above the diagonal was never read)
+            for (size_t k = 0; k < np; ++k)
+                for (size_t j = k + 1; j < np; ++j) L[b + k * np + j] = 0.0;
+    } catch (const std::string& m) {
+        return fail(c, SMM_ERR_HIP, m);
+    }
+    return SMM_OK;
+}
+
+// the mutating calls: settled, flushed and synchronised; a hard failure standing on the context is handed to the caller (and marked told)
+static int proposal_prelude(Ctx* c) {
+    HIPCHK(hipSetDevice(c->device));
+    settle_persist(c);
+    flush(c);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)check_device_error(c);
+    return c->failed ? told(c) : SMM_OK;
+}
+
+int smm_set_proposal(void* ctx, const double* L) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !L) return SMM_ERR_INVALID_ARG;
+    const KParams& P = c->P;
+    if (!P.chol_L) return fail(c, SMM_ERR_INVALID_ARG, "the context has no proposal factor: create it with chol_L");
+    const size_t n = proposal_doubles(P), np = P.np;
+    std::vector<double> h(n);
+    for (size_t b = 0; b < n; b += np * np)
+        for (size_t k = 0; k < np; ++k)
+            for (size_t j = 0; j < np; ++j) {
+                const double v = j <= k ? L[b + k * np + j] : 0.0;
+                if (!std::isfinite(v)) return fail(c, SMM_ERR_INVALID_ARG, "smm_set_proposal: a non-finite entry on or below the diagonal");
+                if (j == k && !(v > 0.0)) return fail(c, SMM_ERR_INVALID_ARG, "smm_set_proposal: a diagonal entry is not > 0");
+                h[b + k * np + j] = v;
+            }
+    try {
+        const int rc = proposal_prelude(c);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(proposal_rows(P), h.data(), n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    } catch (const std::string& m) {
+        return fail(c, SMM_ERR_HIP, m);
+    }
+    return SMM_OK;
+}
+
+int smm_adapt_proposal(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, int32_t min_draws, int32_t normalize, double ridge,
+                       int32_t* status) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return SMM_ERR_INVALID_ARG;
+    const KParams& P = c->P;
+    if (!P.chol_L) return fail(c, SMM_ERR_INVALID_ARG, "the context has no proposal factor: create it with chol_L (per chain)");
+    if (!P.chol_per_chain)
+        return fail(c, SMM_ERR_INVALID_ARG, "smm_adapt_proposal needs per-chain factors (chol_per_chain = 1): a shared factor has no own history");
+    if (min_draws < 2) return fail(c, SMM_ERR_INVALID_ARG, "min_draws must be >= 2");
+    if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(c, SMM_ERR_INVALID_ARG, "ridge must be finite and >= 0");
+    try {
+        const int rc = proposal_prelude(c);
+        if (rc) return rc;
+        if (!cov_window_ok(c, t0, t1)) return fail(c, SMM_ERR_INVALID_ARG, "window must satisfy 0 <= t0 <= t1 <= completed iterations");
+        const size_t N = P.N;
+        const CovRes r = chain_cov_device(c, t0, t1, accepted_only, 1);
+        hipLaunchKernelGGL(k_cov_chol, dim3(N), dim3(64), 0, c->stream, (const double*)r.cov, (const int*)r.count, (int)N, P.np,
+                           (int)min_draws, (int)(normalize != 0), ridge, P.chol_per_chain ? P.offset : 0, (double*)P.chol_L, r.status);
+        HIPCHK(hipGetLastError());
+        if (status) HIPCHK(hipMemcpyAsync(status, r.status, N * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
     } catch (const std::string& m) {
         return fail(c, SMM_ERR_HIP, m);
     }

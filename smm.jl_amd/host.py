@@ -379,6 +379,14 @@ def _empty_selection(c, st):
     return st["count"][c._j] == 0
 
 
+def cov(c):
+    """the covariance matrix of chain c's accepted draws (np.cov(params(c)), ddof 1), reduced on the device (smm_get_chain_cov)"""
+    a = c._algo
+    if a._cov is None or a._cov[0] != a.i:
+        a._cov = (a.i, a._ctx.chain_cov(0, a.i, True, False))
+    return a._cov[1][2][:, :, c._j].copy()
+
+
 def mean(c):
     st = _stats(c)
     if _empty_selection(c, st):
@@ -442,6 +450,16 @@ def _dist_fun_id(f):
                               "not an arbitrary host function")
 
 
+def _chol_opt(L, N, np_):
+    """opts["chol_L"]: None (the reference's isotropic kernel), a factor [np][np] or [N][np][np], or "identity": one identity factor per
+    chain — the isotropic kernel bit for bit, and a context whose factors adapt_proposal can reshape"""
+    if isinstance(L, str):
+        if L != "identity":
+            raise ValueError('opts["chol_L"]: a factor, None or "identity"')
+        return np.ascontiguousarray(np.broadcast_to(np.eye(np_), (N, np_, np_)))
+    return L
+
+
 class MAlgoBGP:
     def __init__(self, m, opts=None, tables=None):
         opts = dict(_DEFAULT_OPTS) if opts is None else opts
@@ -465,7 +483,7 @@ class MAlgoBGP:
                      min_improve=self._min_improve, batch_size=opts.get("batch_size", None),
                      seed=int(opts.get("seed", 12)), device=int(opts.get("device", 0)),
                      dist_fun=self._dist_fun,
-                     chol_L=opts.get("chol_L", None),   # general Gaussian proposals (not in the reference: include/smmhip.h)
+                     chol_L=_chol_opt(opts.get("chol_L", None), N, len(prob.init)),   # general Gaussian proposals (include/smmhip.h)
                      **self._flat)
         self._prob, self._bopts, self._tables = prob, bo, tables
         self._ctx = hip_context(prob, bo, tables)
@@ -481,6 +499,7 @@ class MAlgoBGP:
         self._st = None
         self._stats = {}
         self._last = None
+        self._cov = None
 
     def _chain_stats(self, accepted_only, probs):
         key = (self.i, accepted_only, probs)
@@ -534,10 +553,27 @@ def run(algo):
     return algo
 
 
+def set_proposal(algo, L):
+    """install proposal factor(s) between iterations (smm_set_proposal): [np][np] on a shared-factor run, [N][np][np] per chain"""
+    algo._ctx.set_proposal(L)
+
+
+def adapt_proposal(algo, window=None, accepted_only=True, min_draws=None, normalize=True, ridge=1e-8):
+    """each chain's proposal factor from the covariance of its own draws (adaptive Metropolis, smm_adapt_proposal): window = (t0, t1)
+    0-based iterations, default all completed ones.  Needs per-chain factors (opts["chol_L"] = "identity" or [N][np][np]).
+    Returns the per-chain status (0 installed; 1 too few draws; 2 non-finite covariance; 3 not positive definite)"""
+    t0, t1 = (0, algo.i) if window is None else window
+    st = algo._ctx.adapt_proposal(t0, t1, accepted_only, min_draws, normalize, ridge)
+    algo._invalidate()
+    return st
+
+
 def save(algo, filename):
-    """save(algo, filename), AlgoAbstract.jl:83-88 (JLD2 there; a self-describing .npz here)"""
+    """save(algo, filename), AlgoAbstract.jl:83-88 (JLD2 there; a self-describing .npz here); the installed proposal factor too"""
     h, s = algo._ctx.history(0, algo.i), algo._ctx.state()
     d = {"i": algo.i}
+    if algo._ctx.proposal_layout is not None:
+        d["chol_L"] = algo._ctx.proposal()
     d.update({"h_" + f: getattr(h, f) for f in A.HistoryBuffers.FIELDS})
     d.update({"s_" + f: getattr(s, f) for f in A.StateBuffers.FIELDS})
     np.savez(filename if filename.endswith(".npz") else filename + ".npz", **d)
@@ -555,6 +591,8 @@ def readMalgo(algo, filename):
         getattr(sb, f)[...] = z["s_" + f]
     sb.iter = i
     algo._ctx.set_state(sb, hb)
+    if "chol_L" in z.files:
+        algo._ctx.set_proposal(z["chol_L"])
     algo.i = i
     algo._invalidate()
     return algo
@@ -573,6 +611,8 @@ def restart(algo, extra_iter):
     algo.opts["maxiter"] = new_maxiter
     bo = algo._bopts
     bo.maxiter = new_maxiter
+    if algo._ctx.proposal_layout is not None:   # the factor installed now (adapted or set since creation), not the creation-time one
+        bo.chol_L = algo._ctx.proposal()
     algo._ctx.close()
     algo._ctx = hip_context(algo._prob, bo, tb)
     s.iter = algo.i
