@@ -417,6 +417,46 @@ typedef struct {            /* caller-allocated; any pointer may be NULL = not c
 int  smm_get_chain_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only,
                          const double* probs, int32_t n_probs, smm_chain_stats_t* out);
 
+/* Convergence diagnostics computed on the device from the history it holds: each LOCAL chain's accept rate, and for each of its
+ * S = np + 1 series (s < np: parameter s; s = np: the objective value) the autocorrelation, the effective sample size by Geyer's initial
+ * monotone sequence, and the split R-hat of groups of local chains, over the 0-based iterations [t0, t1), n = t1 - t0 (a shard reports
+ * its own N chains; a group is made of local chains only).  Caller-allocated; any pointer may be NULL (not returned).  Read-only and
+ * ordered like smm_get_chain_stats (it settles, flushes and synchronises, and changes no state, history or generator), and uses its
+ * scratch, grown where needed to one chain's maxiter x 8 S bytes (a context holding more is reduced in batches of chains), plus
+ * ((5 + n_acf) S + 2) N x 8 bytes of results.  group [N]: the chain's group in [0, n_groups), or -1 for none.  SMM_ERR_INVALID_ARG:
+ * NULL ctx or out, t0 < 0, t1 > completed iterations, n < 4, max_lag outside [1, n - 1], n_acf outside [0, max_lag + 1],
+ * n_groups < 0, group NULL with n_groups > 0, a group id outside [-1, n_groups), rhat with n_groups == 0.
+ *
+ * Numerical contract (every operation rounded on its own, no fma).  S(.) = the chain-stats chunked pairwise sum (bit for bit np.sum of
+ * a contiguous float64 array), mean(.) = the chain-stats mean:
+ *   series    : a(t) = the last row r <= t with accepted[r] != 0, looking back before t0 as far as row 0 (swapped rows have accepted = 1,
+ *               AlgoBGP.jl:734-749, so a(t) is the chain's state, lastAccepted, AlgoBGP.jl:209-215); x_s(t) = params[a(t)][s] for
+ *               s < np, x_np(t) = value[a(t)] (= curr_val[t] for every history the library writes).  No such row: non-finite.
+ *   accept    : (double)A / (double)E, E = window iterations with exchanged == 0, A = those of them with accepted != 0 (NaN when
+ *               E == 0; set_acceptRate!, AlgoBGP.jl:253-257, restricted to the window)
+ *   acov_k    = S(d[0:n-k] * d[k:n]) / n with d = x - mean(x): np.sum(d[:n-k] * d[k:]) / n;  rho_k = acov_k / acov_0
+ *   ESS       : P_j = rho_2j + rho_2j+1 while 2j + 1 <= max_lag; J = the smallest j >= 1 with !(P_j > 0), else the number of pairs
+ *               (status 1); Q_0 = P_0, Q_j = P_j < Q_j-1 ? P_j : Q_j-1 (j < J); T = ((0.0 + Q_0) + Q_1) + .. + Q_J-1;
+ *               tau = -1.0 + 2.0 T; ess = n / tau
+ *   status    : first match wins: 3 a non-finite entry in the series (ess and every acf entry NaN); 2 acov_0 == 0 or !(tau > 0) (ess NaN,
+ *               acf as the arithmetic gives); 1 max_lag reached before truncation (ess as above: it overstates); 0 otherwise.  A
+ *               negative ESS is never reported.
+ *   split R-hat of group g, series s: h = n / 2 (integer); the members of g in ascending local index each give x[0:h] then x[n-h:n];
+ *               each half y: mu = mean(y), var = S((y - mu) * (y - mu)) / (h - 1) (np.var(y, ddof=1)).  Over the 2k halves:
+ *               W = mean(vars), v = S((mu_i - mean(mus)) * (mu_i - mean(mus))) / (2k - 1), var_plus = ((h - 1.0) / h) W + v,
+ *               rhat = sqrt(var_plus / W).  NaN when g is empty or a member's series has status 3; otherwise the arithmetic decides.
+ * The device stops computing lags once the sequence is truncated and every requested acf lag is done: the results are those of
+ * computing every lag up to max_lag. */
+typedef struct {            /* caller-allocated; any pointer may be NULL = not computed; S = np + 1 series                       */
+    double*  accept_rate;   /* [N]               accepted among the window's non-exchanged iterations                         */
+    double*  ess;           /* [S][N]            series s < np: parameter s; s = np: the objective value                      */
+    int32_t* status;        /* [S][N]            0 ok, 1 max_lag reached first, 2 undefined, 3 non-finite series             */
+    double*  acf;           /* [n_acf][S][N]     rho_k, k = 0 .. n_acf - 1                                                    */
+    double*  rhat;          /* [n_groups][S]     split R-hat of each group                                                    */
+} smm_chain_diag_t;
+int  smm_get_chain_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32_t n_acf,
+                        const int32_t* group /* [N] or NULL */, int32_t n_groups, smm_chain_diag_t* out);
+
 /* Covariances of the chains' draws and the proposal factor between steps — adaptive Metropolis (Haario et al.) on top of chol_L: a
  * pilot run, then each chain's proposal shaped by the covariance of its own draws, without leaving the device.
  *

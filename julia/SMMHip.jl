@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats, hip_chain_cov, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
 const ABI_VERSION = 3
@@ -102,6 +102,14 @@ struct SmmChainStats
     best_iter::Ptr{Int32}
     n_exchanged::Ptr{Int32}
     most_exchanged_with::Ptr{Int32}
+end
+
+struct SmmChainDiag
+    accept_rate::Ptr{Cdouble}
+    ess::Ptr{Cdouble}
+    status::Ptr{Int32}
+    acf::Ptr{Cdouble}
+    rhat::Ptr{Cdouble}
 end
 
 struct SmmState
@@ -354,6 +362,31 @@ function hip_chain_cov(h::HipBGP, t0::Integer, t1::Integer; accepted_only::Bool 
                            h.ctx, t0, t1, accepted_only ? 1 : 0, unit_space ? 1 : 0, pointer(count), pointer(mean), pointer(cov)))
     end
     return (count = count, mean = mean, cov = cov)   # (the header's [np][N] / [np][np][N] row-major = these column-major arrays)
+end
+
+"""
+    hip_chain_diag(h, t0, t1; max_lag = t1 - t0 - 1, n_acf = 0, groups = nothing) -> NamedTuple
+
+Convergence diagnostics of every chain over iterations `t0+1 .. t1`, on the device (`smm_get_chain_diag`): `accept_rate[chain]`,
+and per series s (the parameters, then the objective value, `np + 1` of them) `ess[chain, s]`, `status[chain, s]` (0 ok, 1 `max_lag`
+reached first, 2 undefined, 3 non-finite series), `acf[chain, s, k + 1]` (rho_k, k < `n_acf`) and, when `groups[chain]` (0-based group
+ids, -1 = none) is given, `rhat[s, g + 1]`: the split R-hat of each group.  NumPy's summation (include/smmhip.h).
+"""
+function hip_chain_diag(h::HipBGP, t0::Integer, t1::Integer; max_lag::Integer = t1 - t0 - 1, n_acf::Integer = 0,
+                        groups::Union{Nothing,AbstractVector{<:Integer}} = nothing)
+    N, S = h.N, h.np + 1
+    g = groups === nothing ? Int32[] : Vector{Int32}(groups)
+    groups === nothing || length(g) == N || throw(ArgumentError("groups needs one entry per chain"))
+    ng = isempty(g) ? 0 : Int(maximum(g)) + 1
+    rate = Vector{Float64}(undef, N); ess = Matrix{Float64}(undef, N, S); st = Matrix{Int32}(undef, N, S)
+    acf = Array{Float64}(undef, N, S, n_acf); rhat = Matrix{Float64}(undef, S, ng)
+    GC.@preserve g rate ess st acf rhat begin
+        cd = SmmChainDiag(pointer(rate), pointer(ess), pointer(st), n_acf > 0 ? pointer(acf) : Ptr{Cdouble}(C_NULL),
+                          ng > 0 ? pointer(rhat) : Ptr{Cdouble}(C_NULL))
+        check(h.ctx, ccall(sym(:smm_get_chain_diag), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Int32}, Cint, Ref{SmmChainDiag}),
+                           h.ctx, t0, t1, max_lag, n_acf, ng > 0 ? pointer(g) : Ptr{Int32}(C_NULL), ng, cd))
+    end
+    return (accept_rate = rate, ess = ess, status = st, acf = acf, rhat = rhat)   # (the header's row-major = these column-major arrays)
 end
 
 # the factor(s) between the header's row-major [np][np] / [N][np][np] and Julia's L[k, j] / L[k, j, c]

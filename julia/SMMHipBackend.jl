@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, adapt_proposal!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, adapt_proposal!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -323,6 +323,21 @@ function chain_stats(algo::MAlgoBGPHip; t0::Integer = 0, t1 = nothing, accepted_
     flush_steps!(algo)
     hip = getfield(algo, :hip)
     return SMMHip.hip_chain_stats(hip, t0, t1 === nothing ? SMMHip.hip_iter(hip) : t1; accepted_only = accepted_only, probs = probs)
+end
+
+"""
+    chain_diag(algo; t0 = 0, t1 = nothing, max_lag = nothing, n_acf = 0, groups = nothing) -> NamedTuple
+
+Per-chain accept rate, autocorrelation, effective sample size (Geyer's initial monotone sequence) and the split R-hat of groups of
+chains over iterations `t0+1 .. t1` (default: every completed one), computed on the device from the history it holds
+(`SMMHip.hip_chain_diag`).  `max_lag` defaults to `t1 - t0 - 1`; `groups[chain]` holds 0-based group ids (-1 = none).  Not a method
+of `SMM`: the reference has no such function.
+"""
+function chain_diag(algo::MAlgoBGPHip; t0::Integer = 0, t1 = nothing, max_lag = nothing, n_acf::Integer = 0, groups = nothing)
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    t1 = t1 === nothing ? SMMHip.hip_iter(hip) : t1
+    return SMMHip.hip_chain_diag(hip, t0, t1; max_lag = max_lag === nothing ? t1 - t0 - 1 : max_lag, n_acf = n_acf, groups = groups)
 end
 
 """

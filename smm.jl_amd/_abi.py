@@ -102,6 +102,12 @@ class smm_chain_stats_t(C.Structure):
     ]
 
 
+class smm_chain_diag_t(C.Structure):
+    _fields_ = [
+        ("accept_rate", c_double_p), ("ess", c_double_p), ("status", c_int32_p), ("acf", c_double_p), ("rhat", c_double_p),
+    ]
+
+
 class smm_timing_t(C.Structure):
     _fields_ = [
         ("step_ms", C.c_double), ("iter_kernel_ms", C.c_double), ("exch_kernel_ms", C.c_double),
@@ -144,6 +150,8 @@ SYMBOLS = [
     ("smm_get_history", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(smm_history_t)]),
     ("smm_get_chain_stats", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32,
                                       C.POINTER(smm_chain_stats_t)]),
+    ("smm_get_chain_diag", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32,
+                                     C.POINTER(smm_chain_diag_t)]),
     ("smm_get_chain_cov", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
     ("smm_get_proposal", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_proposal", C.c_int, [C.c_void_p, c_double_p]),

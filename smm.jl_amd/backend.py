@@ -273,6 +273,28 @@ class BGPContext:
                                               count.ctypes.data_as(A.c_int32_p), A.dptr(mean), A.dptr(cov)))
         return count, mean, cov
 
+    def chain_diag(self, t0=0, t1=None, max_lag=None, n_acf=0, groups=None):
+        """convergence diagnostics of every local chain over iterations [t0, t1), on the device (smm_get_chain_diag,
+        include/smmhip.h): a dict of numpy arrays accept_rate [N], ess / status [S][N] (S = np + 1: the parameters, then the objective
+        value), acf [n_acf][S][N] and, with groups (an int per chain, -1 = none), rhat [n_groups][S], n_groups = groups.max() + 1.
+        max_lag defaults to t1 - t0 - 1: the whole of Geyer's sequence, the device stopping where it is truncated"""
+        t1 = self.state().iter if t1 is None else t1
+        max_lag = t1 - t0 - 1 if max_lag is None else max_lag
+        N, S = self.N, self.np + 1
+        g = None if groups is None else np.ascontiguousarray(groups, np.int32)
+        if g is not None and g.shape != (N,):
+            raise ValueError("chain_diag: groups needs one entry per chain, got shape %s" % (g.shape,))
+        ng = int(g.max()) + 1 if g is not None and len(g) else 0
+        r = dict(accept_rate=np.empty(N), ess=np.empty((S, N)), status=np.empty((S, N), np.int32), acf=np.empty((max(int(n_acf), 0), S, N)),
+                 rhat=np.empty((max(ng, 0), S)))
+        s = A.smm_chain_diag_t()
+        for f, t in A.smm_chain_diag_t._fields_:
+            if (f != "acf" or n_acf > 0) and (f != "rhat" or ng > 0):
+                setattr(s, f, r[f].ctypes.data_as(t))
+        self._check(self._fn("get_chain_diag")(self._ctx, int(t0), int(t1), int(max_lag), int(n_acf),
+                                               g.ctypes.data_as(A.c_int32_p) if g is not None else None, ng, C.byref(s)))
+        return r
+
     def _proposal_shape(self):
         if self.proposal_layout is None:
             return None

@@ -68,6 +68,7 @@ using namespace smm;
 #include "smm_cone_big.hpp"
 #include "smm_stats.hpp"
 #include "smm_cov.hpp"
+#include "smm_diag.hpp"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -563,6 +564,9 @@ struct Ctx {
     // smm_get_chain_cov / smm_adapt_proposal: the results of a call (grown to the largest call's; the columns use st_scr)
     void* cv_res = nullptr;
     size_t cv_res_bytes = 0;
+    // smm_get_chain_diag: the results of a call (grown to the largest call's; the columns use st_scr)
+    void* dg_res = nullptr;
+    size_t dg_res_bytes = 0;
     void* p2p_opened[P2P_MAXG] = {};           // peers' windows opened through HIP IPC (closed with the context)
     unsigned p2p_attached = 0;                 // bit r: rank r's window is known
     unsigned long long p2p_seq = 0;            // pushes so far (every rank counts the same)
@@ -1970,6 +1974,7 @@ void smm_ctx_destroy(void* ctx) {
     if (c->st_scr) (void)hipFree(c->st_scr);
     if (c->st_res) (void)hipFree(c->st_res);
     if (c->cv_res) (void)hipFree(c->cv_res);
+    if (c->dg_res) (void)hipFree(c->dg_res);
     if (c->umod) (void)hipModuleUnload(c->umod);
     if (c->pmod) (void)hipModuleUnload(c->pmod);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -3290,6 +3295,141 @@ int smm_adapt_proposal(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only,
         HIPCHK(hipGetLastError());
         if (status) HIPCHK(hipMemcpyAsync(status, r.status, N * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
+    } catch (const std::string& m) {
+        return fail(c, SMM_ERR_HIP, m);
+    }
+    return SMM_OK;
+}
+
+// --- autocorrelation, ESS and split R-hat of the chains (smm_diag.hpp) --------------------------------------------------------------
+
+// the chain-stats sum on the host: numpy's pairwise sum over chunks of 8192 (include/smmhip.h), every operation rounded on its own
+static double host_pw(const double* x, size_t n) {
+    if (n < 8) {
+        double r = 0.0;
+        for (size_t i = 0; i < n; ++i) r = r + x[i];
+        return r;
+    }
+    if (n <= 128) {
+        double r[8];
+        for (int k = 0; k < 8; ++k) r[k] = x[k];
+        const size_t m = n - n % 8;
+        for (size_t i = 8; i < m; i += 8)
+            for (int k = 0; k < 8; ++k) r[k] = r[k] + x[i + k];
+        double s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (size_t i = m; i < n; ++i) s = s + x[i];
+        return s;
+    }
+    size_t n2 = n / 2;
+    n2 -= n2 % 8;
+    const double lf = host_pw(x, n2), rt = host_pw(x + n2, n - n2);
+    return lf + rt;
+}
+static double host_sum(const std::vector<double>& x) {
+    double S = 0.0;
+    for (size_t c = 0; c < x.size(); c += STATS_LDS_N) S = S + host_pw(x.data() + c, std::min((size_t)STATS_LDS_N, x.size() - c));
+    return S;
+}
+
+int smm_get_chain_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32_t n_acf, const int32_t* group, int32_t n_groups,
+                       smm_chain_diag_t* out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !out) return SMM_ERR_INVALID_ARG;
+    if (n_groups < 0 || (n_groups > 0 && !group)) return fail(c, SMM_ERR_INVALID_ARG, "n_groups < 0, or group NULL with n_groups > 0");
+    if (out->rhat && n_groups == 0) return fail(c, SMM_ERR_INVALID_ARG, "rhat requested without groups");
+    const size_t N = c->P.N;
+    if (group)
+        for (size_t i = 0; i < N; ++i)
+            if (group[i] < -1 || group[i] >= n_groups) return fail(c, SMM_ERR_INVALID_ARG, "a group id outside [-1, n_groups)");
+    try {
+        HIPCHK(hipSetDevice(c->device));
+        settle_persist(c);
+        flush(c);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (t0 < 0 || t1 < t0 || t1 > c->iter)
+            return fail(c, SMM_ERR_INVALID_ARG, "window must satisfy 0 <= t0 <= t1 <= completed iterations");
+        const int n = t1 - t0;
+        if (n < 4) return fail(c, SMM_ERR_INVALID_ARG, "the window must hold at least 4 iterations");
+        if (max_lag < 1 || max_lag > n - 1) return fail(c, SMM_ERR_INVALID_ARG, "max_lag must lie in [1, t1 - t0 - 1]");
+        if (n_acf < 0 || n_acf > max_lag + 1) return fail(c, SMM_ERR_INVALID_ARG, "n_acf must lie in [0, max_lag + 1]");
+        const KParams& P = c->P;
+        const size_t np = P.np, S = np + 1, SN = S * N, nacf = out->acf ? (size_t)n_acf : 0;
+        const bool halves = out->rhat != nullptr;
+        // results: doubles ess [S][N], acf [nacf][S][N], hmu [2][S][N], hvar [2][S][N]; ints status [S][N], nacc [N], noex [N]
+        const size_t nd = SN + nacf * SN + 4 * SN, ni = SN + 2 * N, rbytes = nd * 8 + ni * 4;
+        if (rbytes > c->dg_res_bytes) {
+            if (c->dg_res) { HIPCHK(hipFree(c->dg_res)); c->dg_res = nullptr; c->dg_res_bytes = 0; }
+            HIPCHK(hipMalloc(&c->dg_res, rbytes));
+            c->dg_res_bytes = rbytes;
+        }
+        double* d_ess = (double*)c->dg_res;
+        double* d_acf = d_ess + SN;
+        double* d_hmu = d_acf + nacf * SN;
+        double* d_hvar = d_hmu + 2 * SN;
+        int* d_status = (int*)(d_hvar + 2 * SN);
+        int* d_nacc = d_status + SN;
+        int* d_noex = d_nacc + N;
+        // the S columns of a chain at once: the scratch holds at least one chain's columns of the whole capacity
+        const size_t one = (size_t)P.T * 8 * S, need = std::max(chain_stats_scratch_bytes(P), one);
+        if (c->st_scr && c->st_scr_bytes < one) { HIPCHK(hipFree(c->st_scr)); c->st_scr = nullptr; c->st_scr_bytes = 0; }
+        if (!c->st_scr) {
+            c->st_scr_bytes = need;
+            HIPCHK(hipMalloc(&c->st_scr, c->st_scr_bytes));
+        }
+        const size_t per_chain = (size_t)n * 8 * S;
+        const int Nb = (int)std::min(N, c->st_scr_bytes / per_chain);
+        const int lds_n = std::min(STATS_LDS_N, n);
+        HIPCHK(hipFuncSetAttribute((const void*)k_diag_acov, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+        for (int c0 = 0; c0 < (int)N; c0 += Nb) {
+            const int nb = std::min(Nb, (int)N - c0);
+            double* col = (double*)c->st_scr;
+            hipLaunchKernelGGL(k_diag_gather, dim3(nb), dim3(DIAG_WG), 0, c->stream, (const double*)P.hrec, (int)N, P.HW, (int)np, t0, n, c0,
+                               nb, col, d_nacc, d_noex);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_diag_acov, dim3(nb, S), dim3(DIAG_WG), (size_t)lds_n * 8, c->stream, col, n, (int)N, c0, nb, (int)S,
+                               (int)max_lag, (int)nacf, (int)halves, d_ess, d_status, nacf ? d_acf : nullptr, d_hmu, d_hvar);
+            HIPCHK(hipGetLastError());
+        }
+        std::vector<char> hres(rbytes);
+        HIPCHK(hipMemcpyAsync(hres.data(), c->dg_res, rbytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        const double* hd = (const double*)hres.data();
+        const int* hs = (const int*)(hd + nd);
+        if (out->accept_rate)
+            for (size_t i = 0; i < N; ++i) out->accept_rate[i] = (double)hs[SN + i] / (double)hs[SN + N + i];
+        if (out->ess) memcpy(out->ess, hd, SN * 8);
+        if (out->status) memcpy(out->status, hs, SN * 4);
+        if (out->acf) memcpy(out->acf, hd + SN, nacf * SN * 8);
+        if (out->rhat) {   // split R-hat of each group and series, the members in ascending local index (include/smmhip.h)
+            const double* hmu = hd + SN + nacf * SN;
+            const double* hvar = hmu + 2 * SN;
+            const int h = n / 2;
+            std::vector<double> mus, vars, e;
+            for (int g = 0; g < n_groups; ++g)
+                for (size_t s = 0; s < S; ++s) {
+                    mus.clear(); vars.clear();
+                    bool bad = false;
+                    for (size_t i = 0; i < N; ++i) {
+                        if (group[i] != g) continue;
+                        bad |= hs[s * N + i] == 3;
+                        for (int hf = 0; hf < 2; ++hf) {
+                            mus.push_back(hmu[hf * SN + s * N + i]);
+                            vars.push_back(hvar[hf * SN + s * N + i]);
+                        }
+                    }
+                    double r = NAN;
+                    if (!mus.empty() && !bad) {
+                        const double k2 = (double)mus.size();
+                        const double W = host_sum(vars) / k2, mm = host_sum(mus) / k2;
+                        e.resize(mus.size());
+                        for (size_t q = 0; q < mus.size(); ++q) { const double dv = mus[q] - mm; e[q] = dv * dv; }
+                        const double v = host_sum(e) / (k2 - 1.0);
+                        const double vp = ((h - 1.0) / h) * W + v;
+                        r = sqrt(vp / W);
+                    }
+                    out->rhat[(size_t)g * S + s] = r;
+                }
+        }
     } catch (const std::string& m) {
         return fail(c, SMM_ERR_HIP, m);
     }

@@ -409,6 +409,35 @@ def CI(c, level=0.95):
     return {k: st["quantile"][:, i, c._j].copy() for i, k in enumerate(ps2s_names(c.m))}
 
 
+def _diag(algo, window, groups):
+    """the device's diagnostics of every chain of algo over window = (t0, t1) (default: every completed iteration; smm_get_chain_diag),
+    one call per (iteration, window, groups): ess and rhat read them instead of downloading the history"""
+    t0, t1 = (0, algo.i) if window is None else (int(window[0]), int(window[1]))
+    g = None if groups is None else tuple(int(v) for v in groups)
+    key = (algo.i, t0, t1, g)
+    if key not in algo._diag:
+        algo._diag[key] = algo._ctx.chain_diag(t0, t1, groups=None if g is None else np.asarray(g, np.int32))
+    return algo._diag[key]
+
+
+def ess(c, window=None):
+    """the effective sample size of each parameter of chain c over window = (t0, t1) (default: the whole run): Geyer's initial
+    monotone sequence on the chain's state, computed on the device (include/smmhip.h: smm_get_chain_diag); NaN where undefined"""
+    d = _diag(c._algo, window, None)
+    return OrderedDict((k, float(d["ess"][i, c._j])) for i, k in enumerate(ps2s_names(c.m)))
+
+
+def rhat(algo, groups=None, window=None):
+    """the split R-hat of each parameter in each group of chains over window = (t0, t1) (default: the whole run), on the device:
+    one OrderedDict per group.  groups: a group id per chain (-1 = none); by default the chains with equal acc_tuners entries, which
+    share a target density, numbered in order of first appearance"""
+    if groups is None:
+        ids = {}
+        groups = [ids.setdefault(float(a), len(ids)) for a in algo._acc_tuner]
+    d = _diag(algo, window, groups)
+    return [OrderedDict((k, float(d["rhat"][g, i])) for i, k in enumerate(ps2s_names(algo.m))) for g in range(d["rhat"].shape[0])]
+
+
 def summary(x):
     """summary(c::BGPChain) AlgoBGP.jl:197-206 / summary(m::MAlgoBGP) :541-550"""
     if isinstance(x, MAlgoBGP):
@@ -500,6 +529,7 @@ class MAlgoBGP:
         self._stats = {}
         self._last = None
         self._cov = None
+        self._diag = {}
 
     def _chain_stats(self, accepted_only, probs):
         key = (self.i, accepted_only, probs)
