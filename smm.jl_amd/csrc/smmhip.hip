@@ -392,6 +392,8 @@ struct Hooks {
     int pr_ring_k = PR_K, pr_slow_tile = -1, pr_slow_ticks = 0;   // the persistent kernels' ring depth, a tile made slow by so many ticks
     int pr_slow_read = 0;   // ... k_chain_persist_tile's shard form: slow while it still reads the ring's last entry (a donor's remote granules), not before its publication
     bool rows_win_check = false;   // the p2p rows resolution checked against the plain kernels
+    size_t stats_scratch = 0;      // the reducers' scratch cap instead of STATS_SCRATCH_CAP (0: that cap): batches of chains and parameters at small sizes
+    int stats_mode_bins = STATS_MODE_BINS;   // partner ids per pass of k_stats_mode (1 .. STATS_MODE_BINS): several passes at small populations
 };
 Hooks read_hooks() {
     Hooks H;
@@ -423,6 +425,8 @@ Hooks read_hooks() {
     if (const char* v = SMM_HOOK("SMMHIP_PR_SLOW_US")) H.pr_slow_ticks = 100 * atoi(v);
     H.pr_slow_read = is(SMM_HOOK("SMMHIP_PR_SLOW_READ"), '1');
     H.rows_win_check = SMM_HOOK("SMMHIP_ROWS_WIN_CHECK") != nullptr;
+    if (const char* v = SMM_HOOK("SMMHIP_STATS_SCRATCH")) H.stats_scratch = (size_t)strtoull(v, nullptr, 10);
+    if (const char* v = SMM_HOOK("SMMHIP_STATS_MODE_BINS")) H.stats_mode_bins = std::min(STATS_MODE_BINS, std::max(1, atoi(v)));
     return H;
 }
 // Which stand-alone kernel resolves exchangeMoves! (AlgoBGP.jl:647-716) — ONE decision, taken once per context (select_forms),
@@ -3022,11 +3026,14 @@ int smm_get_history(void* ctx, int32_t t0, int32_t t1, smm_history_t* out) {
 }
 
 // scratch of smm_get_chain_stats: the compacted columns of every chain for the context's whole capacity, at most STATS_SCRATCH_CAP
-// (but always one parameter column + one partner column of maxiter draws: 12 x maxiter bytes)
+// (but always one parameter column + one partner column of maxiter draws: 12 x maxiter bytes; the test seam SMMHIP_STATS_SCRATCH
+// replaces the cap)
 static constexpr size_t STATS_SCRATCH_CAP = (size_t)256 << 20;
-static size_t chain_stats_scratch_bytes(const KParams& P) {
+static size_t chain_stats_scratch_bytes(const Ctx* c) {
+    const KParams& P = c->P;
     const size_t T = (size_t)P.T, all = (size_t)P.N * T * (8 * (size_t)P.np + 4);
-    return std::min(all, std::max(STATS_SCRATCH_CAP, 12 * T));
+    const size_t cap = c->H.stats_scratch ? c->H.stats_scratch : STATS_SCRATCH_CAP;
+    return std::min(all, std::max(cap, 12 * T));
 }
 
 // mean / median / CI / best / summary of AlgoBGP.jl:117-206 for every local chain, reduced where the history lives (smm_stats.hpp)
@@ -3072,7 +3079,7 @@ int smm_get_chain_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only
             memset(hres.data() + nd * 8, 0, ni * 4);
         } else {
             if (!c->st_scr) {
-                c->st_scr_bytes = chain_stats_scratch_bytes(P);
+                c->st_scr_bytes = chain_stats_scratch_bytes(c);
                 HIPCHK(hipMalloc(&c->st_scr, c->st_scr_bytes));
             }
             if (nq) HIPCHK(hipMemcpyAsync(d_probs, probs, nq * 8, hipMemcpyHostToDevice, c->stream));
@@ -3083,7 +3090,7 @@ int smm_get_chain_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only
             while (kb > 1 && per_chain(kb) > cap) kb = (kb + 1) / 2;
             const int Nb = (int)std::min(N, cap / per_chain(kb));
             const int lds_n = std::min(STATS_LDS_N, 1 << (int)ceil(log2((double)std::max(n, 2))));
-            const int bins = std::min(STATS_MODE_BINS, std::max(P.Ng, 64));
+            const int bins = std::min(c->H.stats_mode_bins, std::max(P.Ng, 64));   // (STATS_MODE_BINS but for the test seam)
             HIPCHK(hipFuncSetAttribute((const void*)k_stats_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
             HIPCHK(hipFuncSetAttribute((const void*)k_stats_mode, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_MODE_BINS * 4));
             for (size_t k0 = 0; k0 < std::max(np, (size_t)1); k0 += std::max(kb, (size_t)1)) {
@@ -3161,7 +3168,7 @@ static CovRes chain_cov_device(Ctx* c, int t0, int t1, int accepted_only, int un
         return r;
     }
     // every parameter of a chain at once: the scratch holds at least one chain's columns of the whole capacity
-    const size_t one = (size_t)P.T * (8 * np + 4), need = std::max(chain_stats_scratch_bytes(P), one);
+    const size_t one = (size_t)P.T * (8 * np + 4), need = std::max(chain_stats_scratch_bytes(c), one);
     if (c->st_scr && c->st_scr_bytes < one) { HIPCHK(hipFree(c->st_scr)); c->st_scr = nullptr; c->st_scr_bytes = 0; }
     if (!c->st_scr) {
         c->st_scr_bytes = need;
@@ -3370,7 +3377,7 @@ int smm_get_chain_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32
         int* d_nacc = d_status + SN;
         int* d_noex = d_nacc + N;
         // the S columns of a chain at once: the scratch holds at least one chain's columns of the whole capacity
-        const size_t one = (size_t)P.T * 8 * S, need = std::max(chain_stats_scratch_bytes(P), one);
+        const size_t one = (size_t)P.T * 8 * S, need = std::max(chain_stats_scratch_bytes(c), one);
         if (c->st_scr && c->st_scr_bytes < one) { HIPCHK(hipFree(c->st_scr)); c->st_scr = nullptr; c->st_scr_bytes = 0; }
         if (!c->st_scr) {
             c->st_scr_bytes = need;

@@ -161,3 +161,4 @@ def test_the_shipped_library_has_no_test_seams():
         assert hasattr(hooks, n), "libsmmhip_hooks.so does not export %s" % n
     seams = sorted(set(m.decode() for m in re.findall(rb"SMMHIP_[A-Z0-9_]+", open(A.HOOKS_LIB_PATH, "rb").read())))
     assert "SMMHIP_INLINE_WALK" in seams and "SMMHIP_A2A_CAP" in seams
+    assert "SMMHIP_STATS_SCRATCH" in seams and "SMMHIP_STATS_MODE_BINS" in seams
