@@ -3,12 +3,13 @@
 // k_stats_gather (smm_stats.hpp) run with every parameter in one batch, so the selection and compaction are smm_get_chain_stats' own.
 //
 //   k_cov_center : one workgroup per (chain, parameter) column of the compacted scratch col [np][Nb][n]: the draws mapped to [0, 1]
-//                  (unit_space; mapto_01, the kernels' arithmetic), their mean by the chain-stats contract (stats_pw over chunks of
-//                  8192 staged in LDS), then the column overwritten in place by the centered draws d = u - mean.
+//                  (unit_space; mapto_01, the kernels' arithmetic, in pw_sum's staging), their mean by the chain-stats contract
+//                  (pw_sum, smm_stats.hpp), then the column overwritten in place by the centered draws d = u - mean.
 //   k_cov_pairs  : one workgroup of COV_WG = 128 lanes per (chain, tile of COV_T x COV_T pairs (j, k), tile row >= tile column).  The
 //                  leaves of the pairwise tree of a chunk depend only on the chain's count m: lane 0 lists them once per chunk, with
-//                  the number of combines the post-order walk of the tree makes after each leaf.  The tile's centered columns are
-//                  staged in LDS (rows padded against bank conflicts), COV_G draws at a time, in runs of whole leaves.  Lane = (2 x 2
+//                  the number of combines the post-order walk of the tree makes after each leaf (pw_leaves, smm_stats.hpp).  The
+//                  tile's centered columns are staged in LDS (rows padded against bank conflicts), COV_G draws at a time, in runs of
+//                  whole leaves.  Lane = (2 x 2
 //                  block of pairs, accumulator r[a] of the leaf, a = lane & 7): 4 products from 4 LDS reads per step (ds_read_b64 at
 //                  32 doubles per clock per CU against
 //                  about 64 FP64 adds: the blocked product keeps both busy).  After a leaf the 8 accumulators meet by a butterfly, lane
@@ -30,59 +31,23 @@ __global__ __launch_bounds__(STATS_WG) void k_cov_center(double* __restrict__ co
                                                          const double* __restrict__ lb, const double* __restrict__ ub,
                                                          const int* __restrict__ o_count, double* __restrict__ o_mean) {
     extern __shared__ __align__(16) double sx[];   // min(n, STATS_LDS_N)
-    __shared__ int loff[STATS_LEAF_MAX], lnum[STATS_LEAF_MAX];
-    __shared__ double lsum[STATS_LEAF_MAX];
-    __shared__ int tstk[64];
-    __shared__ double vstk[64];
-    __shared__ int nlv;
-    __shared__ double smean;
+    __shared__ PwTree pt;
     const int cl = blockIdx.x, k = blockIdx.y, c = c0 + cl, tid = threadIdx.x;
     double* x = col + ((size_t)k * Nb + cl) * n;
     const int m = o_count[c];
     const double lbk = lb[k], span = ub[k] - lbk;
-    double S = 0.0;
-    for (int c8 = 0; c8 < m; c8 += STATS_LDS_N) {
-        const int L = min(STATS_LDS_N, m - c8);
-        for (int i = tid; i < L; i += STATS_WG) {
-            double v = x[c8 + i];
-            if (unit) v = (v - lbk) / span;   // mapto_01, mprob.jl:248
-            sx[i] = v;
-        }
-        __syncthreads();
-        const double s = stats_pw(sx, L, loff, lnum, lsum, tstk, vstk, &nlv);
-        S = S + s;
-    }
-    if (tid == 0) {
-        smean = S / (double)m;
-        o_mean[(size_t)k * N + c] = smean;
-    }
-    __syncthreads();
-    const double mu = smean;
+    const double S = pw_sum(m, [&](int i) {
+        double v = x[i];
+        if (unit) v = (v - lbk) / span;   // mapto_01, mprob.jl:248
+        return v;
+    }, sx, pt);
+    const double mu = S / (double)m;
+    if (tid == 0) o_mean[(size_t)k * N + c] = mu;
     for (int i = tid; i < m; i += STATS_WG) {
         double v = x[i];
         if (unit) v = (v - lbk) / span;
         x[i] = v - mu;
     }
-}
-
-// the leaves of one chunk of L draws in order (offset, size), and after each leaf the number of (left + right) combines the post-order
-// walk of stats_pw_tree makes before the next leaf: the same tree, walked by one lane
-__device__ int cov_leaves(int L, int* __restrict__ loff, int* __restrict__ lnum, int* __restrict__ lcomb, int* __restrict__ tstk) {
-    int sp = 0, nl = 0, lo = 0;
-    tstk[sp++] = L;
-    while (sp > 0) {
-        const int t = tstk[--sp];
-        if (t < 0) ++lcomb[nl - 1];
-        else if (t <= 128) { loff[nl] = lo; lnum[nl] = t; lcomb[nl] = 0; lo += t; ++nl; }
-        else {
-            int n2 = t / 2;
-            n2 -= n2 % 8;
-            tstk[sp++] = -1;
-            tstk[sp++] = t - n2;
-            tstk[sp++] = n2;
-        }
-    }
-    return nl;
 }
 
 __global__ __launch_bounds__(COV_WG) void k_cov_pairs(const double* __restrict__ col, int n, int N, int c0, int Nb, int np,
@@ -107,7 +72,7 @@ __global__ __launch_bounds__(COV_WG) void k_cov_pairs(const double* __restrict__
     double S[4] = {0.0, 0.0, 0.0, 0.0};
     for (int c8 = 0; c8 < m; c8 += STATS_LDS_N) {
         const int L = min(STATS_LDS_N, m - c8);
-        if (tid == 0) snl = cov_leaves(L, loff, lnum, lcomb, tstk);
+        if (tid == 0) snl = pw_leaves(L, loff, lnum, lcomb, tstk);
         __syncthreads();
         const int nl = snl;
         sp = 0;

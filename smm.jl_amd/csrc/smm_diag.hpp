@@ -8,7 +8,7 @@
 //                   carry-forward columns col [S][Nb][n] (params[a(t)][s], then value[a(t)]; NaN while no row is accepted) and counts
 //                   the window's non-exchanged iterations E and the accepted ones among them A.
 //   k_diag_acov   : one workgroup per (chain, series) column: a non-finite entry ends it (status 3).  Otherwise the two halves' mean and
-//                   variance for R-hat (stats_pw over chunks staged in LDS), the column's mean, then d = x - mean (in LDS when n <= 8192,
+//                   variance for R-hat (pw_sum, smm_stats.hpp), the column's mean, then d = x - mean (in LDS when n <= 8192,
 //                   else in place in the scratch column, read from L2).  The lags then go in blocks of 256, lane = lag: each lane sums
 //                   its products d[i] d[i + k] by the pairwise tree of numpy over chunks of 8192, walked in registers (the tree of a
 //                   chunk is at most 7 levels deep; a leaf of <= 128 products keeps numpy's 8 strided accumulators).  After a block
@@ -35,9 +35,7 @@ __global__ __launch_bounds__(DIAG_WG) void k_diag_gather(const double* __restric
                                                          int* __restrict__ o_noex) {
     __shared__ int wred[DIAG_WG / 64];
     __shared__ int wtot[DIAG_WG / 64];
-    const int G = gridDim.x, b = blockIdx.x;
-    const int cl = (G & 7) ? b : (b & 7) * (G >> 3) + (b >> 3);   // neighbouring chains on one XCD: their records share lines
-    const int c = c0 + cl;
+    const int cl = xcd_chain(blockIdx.x, gridDim.x), c = c0 + cl;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int S = np + 1;
     const double qnan = __longlong_as_double(0x7ff8000000000000ll);
@@ -134,48 +132,24 @@ __device__ __forceinline__ double diag_pw(const double* __restrict__ d, int lo, 
     }
 }
 
-// the chain-stats chunked pairwise sum of y[0..L) staged through LDS (sx); f(i) = the i-th term, read from global memory.  Every thread
-// of the block calls it and gets the sum.
-template <class F>
-__device__ double diag_sum(int L, F f, double* sx, int* loff, int* lnum, double* lsum, int* tstk, double* vstk, int* nlv, double* bc) {
-    const int tid = threadIdx.x;
-    double S = 0.0;
-    for (int c8 = 0; c8 < L; c8 += STATS_LDS_N) {
-        const int Lc = min(STATS_LDS_N, L - c8);
-        for (int i = tid; i < Lc; i += DIAG_WG) sx[i] = f(c8 + i);
-        __syncthreads();
-        const double s = stats_pw(sx, Lc, loff, lnum, lsum, tstk, vstk, nlv);
-        S = S + s;
-    }
-    if (tid == 0) *bc = S;
-    __syncthreads();
-    S = *bc;
-    __syncthreads();
-    return S;
-}
-
 __global__ __launch_bounds__(DIAG_WG) void k_diag_acov(double* __restrict__ col, int n, int N, int c0, int Nb, int S, int max_lag,
                                                        int n_acf, int halves, double* __restrict__ o_ess, int* __restrict__ o_status,
                                                        double* __restrict__ o_acf, double* __restrict__ o_hmu, double* __restrict__ o_hvar) {
     extern __shared__ __align__(16) double sx[];   // min(n, STATS_LDS_N)
-    __shared__ int loff[STATS_LEAF_MAX], lnum[STATS_LEAF_MAX];
-    __shared__ double lsum[STATS_LEAF_MAX];
-    __shared__ int tstk[64];
-    __shared__ double vstk[64];
-    __shared__ int nlv, sbad, sdone;
-    __shared__ double bc;
+    __shared__ PwTree pt;   // (pt.flag: a non-finite entry)
+    __shared__ int sdone;
     __shared__ double sac[DIAG_WG];
     const int cl = blockIdx.x, s = blockIdx.y, c = c0 + cl, tid = threadIdx.x;
     double* x = col + ((size_t)s * Nb + cl) * n;
     const size_t o1 = (size_t)s * N + c;   // [S][N]
     const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    if (tid == 0) { sbad = 0; sdone = 0; }
+    if (tid == 0) { pt.flag = 0; sdone = 0; }
     __syncthreads();
     bool bad = false;
     for (int i = tid; i < n; i += DIAG_WG) bad |= !isfinite(x[i]);
-    if (bad) sbad = 1;
+    if (bad) pt.flag = 1;
     __syncthreads();
-    if (sbad) {
+    if (pt.flag) {
         if (tid == 0) { o_ess[o1] = qnan; o_status[o1] = 3; }
         if (o_acf)
             for (int k = tid; k < n_acf; k += DIAG_WG) o_acf[(size_t)k * S * N + o1] = qnan;
@@ -186,16 +160,15 @@ __global__ __launch_bounds__(DIAG_WG) void k_diag_acov(double* __restrict__ col,
         const int h = n / 2;
         for (int hf = 0; hf < 2; ++hf) {
             const double* y = x + (hf ? n - h : 0);
-            const double mu = diag_sum(h, [&](int i) { return y[i]; }, sx, loff, lnum, lsum, tstk, vstk, &nlv, &bc) / (double)h;
-            const double ss = diag_sum(h, [&](int i) { const double e = y[i] - mu; return e * e; }, sx, loff, lnum, lsum, tstk, vstk,
-                                       &nlv, &bc);
+            const double mu = pw_sum(h, [&](int i) { return y[i]; }, sx, pt) / (double)h;
+            const double ss = pw_sum(h, [&](int i) { const double e = y[i] - mu; return e * e; }, sx, pt);
             if (tid == 0) {
                 o_hmu[(size_t)hf * S * N + o1] = mu;
                 o_hvar[(size_t)hf * S * N + o1] = ss / (double)(h - 1);
             }
         }
     }
-    const double m = diag_sum(n, [&](int i) { return x[i]; }, sx, loff, lnum, lsum, tstk, vstk, &nlv, &bc) / dn;
+    const double m = pw_sum(n, [&](int i) { return x[i]; }, sx, pt) / dn;
     const double* d;
     if (n <= STATS_LDS_N) {
         for (int i = tid; i < n; i += DIAG_WG) sx[i] = x[i] - m;

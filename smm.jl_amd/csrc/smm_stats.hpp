@@ -12,6 +12,8 @@
 //                    bits, one pass over the column in L2 per digit) of every rank needed above that.  Both give the same values.
 //   k_stats_mode   : one workgroup per chain: the most frequent partner (ties to the smallest id) by an LDS histogram of the partner ids,
 //                    STATS_MODE_BINS ids per pass over the column.
+// Shared with smm_cov.hpp and smm_diag.hpp: the pairwise-sum core (pw_leaves walks numpy's tree of a chunk once, stats_pw sums the leaves
+// and replays the walk's combines, pw_sum stages the chunks through LDS; PwTree is its LDS) and the XCD chain swizzle (xcd_chain).
 #pragma once
 
 constexpr int STATS_WG = 256;
@@ -36,6 +38,9 @@ __device__ __forceinline__ bool stats_better(double v, int i, double bv, int bi)
     return v < bv || (v == bv && i < bi);
 }
 
+// the local chain of block b of a grid of G chains: neighbouring chains on one XCD, where their records share lines
+__device__ __forceinline__ int xcd_chain(int b, int G) { return (G & 7) ? b : (b & 7) * (G >> 3) + (b >> 3); }
+
 __global__ __launch_bounds__(STATS_WG) void k_stats_gather(const double* __restrict__ hrec, int N, int HW, int t0, int n, int acc_only,
                                                            int c0, int Nb, int k0, int kb, int first, double* __restrict__ col,
                                                            int* __restrict__ pcol, int* __restrict__ o_count, int* __restrict__ o_nex,
@@ -43,9 +48,7 @@ __global__ __launch_bounds__(STATS_WG) void k_stats_gather(const double* __restr
     __shared__ int wtot[2][STATS_WG / 64];
     __shared__ double wbv[STATS_WG / 64];
     __shared__ int wbi[STATS_WG / 64];
-    const int G = gridDim.x, b = blockIdx.x;
-    const int cl = (G & 7) ? b : (b & 7) * (G >> 3) + (b >> 3);   // neighbouring chains on one XCD: their records share lines
-    const int c = c0 + cl;
+    const int cl = xcd_chain(blockIdx.x, gridDim.x), c = c0 + cl;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const unsigned long long below = (1ull << lane) - 1ull;
     int base = 0, pbase = 0;
@@ -93,45 +96,49 @@ __global__ __launch_bounds__(STATS_WG) void k_stats_gather(const double* __restr
     }
 }
 
-// The pairwise tree of numpy over one chunk of L draws (include/smmhip.h): walked depth first, left before right, by ONE lane.
-// enumerate: list the leaves (offset, size) in order;  otherwise: combine the leaf sums in that order.  Stack in LDS (depth <= 2 x 8 + 1).
-__device__ double stats_pw_tree(int L, bool enumerate, int* __restrict__ loff, int* __restrict__ lnum, const double* __restrict__ lsum,
-                                int* __restrict__ tstk, double* __restrict__ vstk, int* nleaves) {
-    int sp = 0, vsp = 0, nl = 0, lo = 0;
+// The pairwise tree of numpy over one chunk of L draws (include/smmhip.h), walked depth first, left before right, by ONE lane: the leaves
+// in order (offset, size), and after each leaf the number of (left + right) combines the post-order walk makes before the next leaf.
+// Stack in LDS (depth <= 2 x 8 + 1).
+__device__ int pw_leaves(int L, int* __restrict__ loff, int* __restrict__ lnum, int* __restrict__ lcomb, int* __restrict__ tstk) {
+    int sp = 0, nl = 0, lo = 0;
     tstk[sp++] = L;
     while (sp > 0) {
         const int t = tstk[--sp];
-        if (t < 0) {                       // combine the two values on top: left + right
-            const double rt = vstk[--vsp];
-            const double lf = vstk[--vsp];
-            vstk[vsp++] = lf + rt;
-        } else if (t <= 128) {
-            if (enumerate) { loff[nl] = lo; lnum[nl] = t; lo += t; }
-            else vstk[vsp++] = lsum[nl];
-            ++nl;
-        } else {
+        if (t < 0) ++lcomb[nl - 1];
+        else if (t <= 128) { loff[nl] = lo; lnum[nl] = t; lcomb[nl] = 0; lo += t; ++nl; }
+        else {
             int n2 = t / 2;
             n2 -= n2 % 8;
-            if (!enumerate) tstk[sp++] = -1;
+            tstk[sp++] = -1;
             tstk[sp++] = t - n2;
             tstk[sp++] = n2;
         }
     }
-    *nleaves = nl;
-    return enumerate ? 0.0 : vstk[0];
+    return nl;
 }
 
-// pairwise sum of x[0..L) (L <= STATS_LDS_N, in LDS); every thread of the block calls it; the result is valid in thread 0
-__device__ double stats_pw(const double* __restrict__ x, int L, int* loff, int* lnum, double* lsum, int* tstk, double* vstk, int* nlv) {
+// the LDS of stats_pw: the tree of a chunk (leaves, their combine counts and sums, the two stacks, the leaf count) and a flag the
+// caller's staging may raise
+struct PwTree {
+    int loff[STATS_LEAF_MAX], lnum[STATS_LEAF_MAX], lcomb[STATS_LEAF_MAX];
+    double lsum[STATS_LEAF_MAX];
+    int tstk[64];
+    double vstk[64];
+    int nl, flag;
+};
+
+// pairwise sum of x[0..L) (L <= STATS_LDS_N, in LDS); every thread of the block calls it and gets the sum (left at the bottom of the
+// value stack)
+__device__ double stats_pw(const double* __restrict__ x, int L, PwTree& t) {
     const int tid = threadIdx.x;
-    if (tid == 0) { int nl; stats_pw_tree(L, true, loff, lnum, lsum, tstk, vstk, &nl); *nlv = nl; }
+    if (tid == 0) t.nl = pw_leaves(L, t.loff, t.lnum, t.lcomb, t.tstk);
     __syncthreads();
-    const int nl = *nlv;
+    const int nl = t.nl;
     const int g = tid >> 3, k = tid & 7;
     for (int b0 = 0; b0 < nl; b0 += STATS_WG / 8) {   // 8 lanes per leaf: lane k holds numpy's accumulator r[k]
         const int leaf = b0 + g;
         const bool has = leaf < nl;
-        const int lo = has ? loff[leaf] : 0, m = has ? lnum[leaf] : 0;
+        const int lo = has ? t.loff[leaf] : 0, m = has ? t.lnum[leaf] : 0;
         double r = 0.0;
         if (m >= 8) {
             r = x[lo + k];
@@ -150,14 +157,37 @@ __device__ double stats_pw(const double* __restrict__ x, int L, int* loff, int* 
                 s = r;
                 for (int i = m - m % 8; i < m; ++i) s = s + x[lo + i];
             }
-            lsum[leaf] = s;
+            t.lsum[leaf] = s;
         }
     }
     __syncthreads();
-    double s = 0.0;
-    if (tid == 0) { int nl2; s = stats_pw_tree(L, false, loff, lnum, lsum, tstk, vstk, &nl2); }
+    if (tid == 0) {   // the walk's post-order: push each leaf sum, then make its combines (pop right, pop left, push left + right)
+        int sp = 0;
+        for (int l = 0; l < nl; ++l) {
+            t.vstk[sp++] = t.lsum[l];
+            for (int q = t.lcomb[l]; q > 0; --q) {
+                --sp;
+                t.vstk[sp - 1] = t.vstk[sp - 1] + t.vstk[sp];
+            }
+        }
+    }
     __syncthreads();
-    return s;
+    return t.vstk[0];
+}
+
+// the chain-stats sum of f(0 .. L) (numpy's pairwise sum over chunks of STATS_LDS_N, include/smmhip.h): each chunk's terms staged
+// through sx (LDS), then stats_pw.  Every thread of the block calls it and gets the sum.
+template <class F>
+__device__ double pw_sum(int L, F f, double* __restrict__ sx, PwTree& t) {
+    double S = 0.0;
+    for (int c8 = 0; c8 < L; c8 += STATS_LDS_N) {
+        const int Lc = min(STATS_LDS_N, L - c8);
+        for (int i = threadIdx.x; i < Lc; i += STATS_WG) sx[i] = f(c8 + i);
+        __syncthreads();
+        const double s = stats_pw(sx, Lc, t);
+        S = S + s;
+    }
+    return S;
 }
 
 // the rank-th smallest key (0-based) of the column x[0..m) in global memory: radix select, block-wide
@@ -232,28 +262,16 @@ __global__ __launch_bounds__(STATS_WG) void k_stats_column(const double* __restr
                                                            int np, double* __restrict__ o_mean, double* __restrict__ o_median,
                                                            double* __restrict__ o_quant) {
     extern __shared__ __align__(16) double sx[];   // min(n, STATS_LDS_N) rounded up to a power of two
-    __shared__ int loff[STATS_LEAF_MAX], lnum[STATS_LEAF_MAX];
-    __shared__ double lsum[STATS_LEAF_MAX];
-    __shared__ int tstk[64];
-    __shared__ double vstk[64];
-    __shared__ int nlv, nan_seen, part[STATS_WG], res[2];
+    __shared__ PwTree pt;   // (pt.flag: a NaN among the draws)
+    __shared__ int part[STATS_WG], res[2];
     const int cl = blockIdx.x, kk = blockIdx.y, c = c0 + cl, k = k0 + kk, tid = threadIdx.x;
     const double* x = col + ((size_t)kk * Nb + cl) * n;
     const int m = o_count[c];
     const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    if (tid == 0) nan_seen = 0;
+    if (tid == 0) pt.flag = 0;
     __syncthreads();
-    double S = 0.0;
-    for (int c8 = 0; c8 < m; c8 += STATS_LDS_N) {
-        const int L = min(STATS_LDS_N, m - c8);
-        bool nanl = false;
-        for (int i = tid; i < L; i += STATS_WG) { const double v = x[c8 + i]; sx[i] = v; nanl |= v != v; }
-        if (nanl) nan_seen = 1;
-        __syncthreads();
-        const double s = stats_pw(sx, L, loff, lnum, lsum, tstk, vstk, &nlv);
-        S = S + s;
-    }
-    const bool bad = nan_seen != 0 || m == 0;
+    const double S = pw_sum(m, [&](int i) { const double v = x[i]; if (v != v) pt.flag = 1; return v; }, sx, pt);
+    const bool bad = pt.flag != 0 || m == 0;
     if (bad) {
         if (tid == 0) {
             o_mean[(size_t)k * N + c] = m == 0 ? qnan : S / (double)m;

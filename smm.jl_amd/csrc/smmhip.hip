@@ -559,18 +559,12 @@ struct Ctx {
     int failed = 0;             // a hard device error (AlgoBGP.jl:341,409) stopped the run at iteration `iter`: sticky until smm_set_state
     // the p2p form of the sharded iteration (smm_p2p.hpp)
     unsigned char* p2p_mine = nullptr;         // this rank's window (null: smm_bgp_p2p_init not called)
-    // smm_get_chain_stats: scratch for the compacted columns (allocated by the first call, bounded: chain_stats_scratch_bytes) and the
-    // results of a call (grown to the largest call's)
+    // the history reducers (smm_get_chain_stats / _cov / _diag, smm_adapt_proposal): their shared scratch for the compacted columns
+    // (reducer_scratch) and the results of a call (reducer_result: grown to the largest call's)
     void* st_scr = nullptr;
     size_t st_scr_bytes = 0;
-    void* st_res = nullptr;
-    size_t st_res_bytes = 0;
-    // smm_get_chain_cov / smm_adapt_proposal: the results of a call (grown to the largest call's; the columns use st_scr)
-    void* cv_res = nullptr;
-    size_t cv_res_bytes = 0;
-    // smm_get_chain_diag: the results of a call (grown to the largest call's; the columns use st_scr)
-    void* dg_res = nullptr;
-    size_t dg_res_bytes = 0;
+    void* red_res = nullptr;
+    size_t red_res_bytes = 0;
     void* p2p_opened[P2P_MAXG] = {};           // peers' windows opened through HIP IPC (closed with the context)
     unsigned p2p_attached = 0;                 // bit r: rank r's window is known
     unsigned long long p2p_seq = 0;            // pushes so far (every rank counts the same)
@@ -1875,6 +1869,78 @@ void alloc_persist(Ctx* c) {
     HIPCHK(hipMemcpy(c->hist_fill, P.hrec, N * P.HW * 8, hipMemcpyDeviceToDevice));   // (a row of the constructor's fill)
 }
 
+// --- the history readers (smm_get_history, smm_get_state) and reducers (smm_get_chain_stats / _cov / _diag, smm_adapt_proposal) -----
+
+// a reader's prelude: the iterations enqueued so far settled (a repair may move c->iter), flushed and finished
+void reader_prelude(Ctx* c) {
+    HIPCHK(hipSetDevice(c->device));
+    settle_persist(c);
+    flush(c);
+    HIPCHK(hipStreamSynchronize(c->stream));
+}
+
+// a reducer's window [t0, t1), checked after the prelude
+int check_window(Ctx* c, int t0, int t1) {
+    if (t0 < 0 || t1 < t0 || t1 > c->iter) return fail(c, SMM_ERR_INVALID_ARG, "window must satisfy 0 <= t0 <= t1 <= completed iterations");
+    return SMM_OK;
+}
+
+// the results of a reducer call on the device, one buffer grown to the largest call's
+void* reducer_result(Ctx* c, size_t bytes) {
+    if (bytes > c->red_res_bytes) {
+        if (c->red_res) { HIPCHK(hipFree(c->red_res)); c->red_res = nullptr; c->red_res_bytes = 0; }
+        HIPCHK(hipMalloc(&c->red_res, bytes));
+        c->red_res_bytes = bytes;
+    }
+    return c->red_res;
+}
+
+// a reducer's result layout, stated once: consecutive typed slices, placed in the device buffer and in its host copy alike
+template <class T>
+struct Slice {
+    size_t off;
+    T* in(void* base) const { return (T*)((char*)base + off); }
+};
+struct Carve {
+    size_t bytes = 0;
+    template <class T>
+    Slice<T> take(size_t n) { const Slice<T> s{bytes}; bytes += n * sizeof(T); return s; }
+};
+
+// the compacted columns of every chain for the context's whole capacity, at most STATS_SCRATCH_CAP (but always one parameter column +
+// one partner column of maxiter draws: 12 x maxiter bytes; the test seam SMMHIP_STATS_SCRATCH replaces the cap)
+constexpr size_t STATS_SCRATCH_CAP = (size_t)256 << 20;
+size_t chain_stats_scratch_bytes(const Ctx* c) {
+    const KParams& P = c->P;
+    const size_t T = (size_t)P.T, all = (size_t)P.N * T * (8 * (size_t)P.np + 4);
+    const size_t cap = c->H.stats_scratch ? c->H.stats_scratch : STATS_SCRATCH_CAP;
+    return std::min(all, std::max(cap, 12 * T));
+}
+
+// the reducers' shared scratch st_scr: chain_stats_scratch_bytes, but never less than one_chain_bytes (one chain's columns of the whole
+// capacity, for a reducer that takes them all at once; 0: no minimum).  One that is smaller is freed and allocated anew.
+void reducer_scratch(Ctx* c, size_t one_chain_bytes) {
+    if (c->st_scr && c->st_scr_bytes < one_chain_bytes) { HIPCHK(hipFree(c->st_scr)); c->st_scr = nullptr; c->st_scr_bytes = 0; }
+    if (!c->st_scr) {
+        c->st_scr_bytes = std::max(chain_stats_scratch_bytes(c), one_chain_bytes);
+        HIPCHK(hipMalloc(&c->st_scr, c->st_scr_bytes));
+    }
+}
+
+// the local chains in batches of as many as the scratch holds at per_chain bytes each: body(c0, nb)
+template <class Body>
+void chain_batches(Ctx* c, size_t per_chain, Body body) {
+    const int N = c->P.N, Nb = (int)std::min((size_t)N, c->st_scr_bytes / per_chain);
+    for (int c0 = 0; c0 < N; c0 += Nb) body(c0, std::min(Nb, N - c0));
+}
+
+// a reducer kernel onto the context's stream, its launch checked
+template <class Kern, class... Args>
+void launch_checked(Ctx* c, Kern kern, dim3 grid, dim3 block, size_t smem, const Args&... args) {
+    launch(c, kern, grid, block, smem, args...);
+    HIPCHK(hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" {
@@ -1976,9 +2042,7 @@ void smm_ctx_destroy(void* ctx) {
     for (void* w : c->p2p_opened) if (w) (void)hipIpcCloseMemHandle(w);
     if (c->p2p_mine) (void)hipFree(c->p2p_mine);
     if (c->st_scr) (void)hipFree(c->st_scr);
-    if (c->st_res) (void)hipFree(c->st_res);
-    if (c->cv_res) (void)hipFree(c->cv_res);
-    if (c->dg_res) (void)hipFree(c->dg_res);
+    if (c->red_res) (void)hipFree(c->red_res);
     if (c->umod) (void)hipModuleUnload(c->umod);
     if (c->pmod) (void)hipModuleUnload(c->pmod);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -2393,6 +2457,11 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
             if (tile_smem(c, is_sim(c->obj) ? F.ct : (c->obj == SMM_OBJ_DENSE ? 16 : 8)) > (size_t)lim)
                 throw std::string("tile does not fit the 160 KiB LDS");
         }
+        // the history reducers' dynamic LDS: a chunk of draws (k_stats_column, k_cov_center, k_diag_acov), the partner ids of a pass (k_stats_mode)
+        HIPCHK(hipFuncSetAttribute((const void*)k_stats_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+        HIPCHK(hipFuncSetAttribute((const void*)k_cov_center, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+        HIPCHK(hipFuncSetAttribute((const void*)k_diag_acov, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+        HIPCHK(hipFuncSetAttribute((const void*)k_stats_mode, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_MODE_BINS * 4));
         HIPCHK(hipDeviceSynchronize());
     } catch (const std::string& m) {
         g_create_err = m;
@@ -2993,10 +3062,7 @@ int smm_get_history(void* ctx, int32_t t0, int32_t t1, smm_history_t* out) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !out || t0 < 0 || t1 < t0 || t1 > c->P.T) return SMM_ERR_INVALID_ARG;
     try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        flush(c);
-        HIPCHK(hipStreamSynchronize(c->stream));
+        reader_prelude(c);
         const KParams& P = c->P;
         const size_t N = P.N, HW = P.HW, np = P.np, nm = P.nm;
         std::vector<double> row(N * HW);
@@ -3025,17 +3091,6 @@ int smm_get_history(void* ctx, int32_t t0, int32_t t1, smm_history_t* out) {
     return SMM_OK;
 }
 
-// scratch of smm_get_chain_stats: the compacted columns of every chain for the context's whole capacity, at most STATS_SCRATCH_CAP
-// (but always one parameter column + one partner column of maxiter draws: 12 x maxiter bytes; the test seam SMMHIP_STATS_SCRATCH
-// replaces the cap)
-static constexpr size_t STATS_SCRATCH_CAP = (size_t)256 << 20;
-static size_t chain_stats_scratch_bytes(const Ctx* c) {
-    const KParams& P = c->P;
-    const size_t T = (size_t)P.T, all = (size_t)P.N * T * (8 * (size_t)P.np + 4);
-    const size_t cap = c->H.stats_scratch ? c->H.stats_scratch : STATS_SCRATCH_CAP;
-    return std::min(all, std::max(cap, 12 * T));
-}
-
 // mean / median / CI / best / summary of AlgoBGP.jl:117-206 for every local chain, reduced where the history lives (smm_stats.hpp)
 int smm_get_chain_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, const double* probs, int32_t n_probs,
                         smm_chain_stats_t* out) {
@@ -3046,90 +3101,60 @@ int smm_get_chain_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only
     for (int p = 0; p < n_probs; ++p)
         if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) return fail(c, SMM_ERR_INVALID_ARG, "probs must lie in [0, 1]");
     try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        flush(c);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (t0 < 0 || t1 < t0 || t1 > c->iter)
-            return fail(c, SMM_ERR_INVALID_ARG, "window must satisfy 0 <= t0 <= t1 <= completed iterations");
+        reader_prelude(c);
+        if (const int rc = check_window(c, t0, t1)) return rc;
         const KParams& P = c->P;
         const size_t N = P.N, np = P.np, nq = n_probs;
         const int n = t1 - t0;
-        // results: doubles bestv[N], probs[nq], mean[np][N], median[np][N], quant[nq][np][N]; then ints count, nex, besti, most [N] each
-        const size_t nd = N + nq + 2 * np * N + nq * np * N, ni = 4 * N;
-        const size_t rbytes = nd * 8 + ni * 4;
-        if (rbytes > c->st_res_bytes) {
-            if (c->st_res) { HIPCHK(hipFree(c->st_res)); c->st_res = nullptr; c->st_res_bytes = 0; }
-            HIPCHK(hipMalloc(&c->st_res, rbytes));
-            c->st_res_bytes = rbytes;
-        }
-        double* d_bestv = (double*)c->st_res;
-        double* d_probs = d_bestv + N;
-        double* d_mean = d_probs + nq;
-        double* d_median = d_mean + np * N;
-        double* d_quant = d_median + np * N;
-        int* d_count = (int*)(d_quant + nq * np * N);
-        int* d_nex = d_count + N;
-        int* d_besti = d_nex + N;
-        int* d_most = d_besti + N;
-        std::vector<char> hres(rbytes);
+        Carve R;   // the doubles first (NaN for an empty window), then the ints (0)
+        const auto bestv = R.take<double>(N), dprobs = R.take<double>(nq), mean = R.take<double>(np * N), median = R.take<double>(np * N),
+                   quant = R.take<double>(nq * np * N);
+        const auto count = R.take<int>(N), nex = R.take<int>(N), besti = R.take<int>(N), most = R.take<int>(N);
+        void* d = reducer_result(c, R.bytes);
+        std::vector<char> hres(R.bytes);
         if (n == 0) {   // nothing selected, nothing to find
-            double* hd = (double*)hres.data();
-            for (size_t i = 0; i < nd; ++i) hd[i] = NAN;
-            memset(hres.data() + nd * 8, 0, ni * 4);
+            std::fill(bestv.in(hres.data()), (double*)count.in(hres.data()), NAN);
+            memset(count.in(hres.data()), 0, R.bytes - count.off);
         } else {
-            if (!c->st_scr) {
-                c->st_scr_bytes = chain_stats_scratch_bytes(c);
-                HIPCHK(hipMalloc(&c->st_scr, c->st_scr_bytes));
-            }
-            if (nq) HIPCHK(hipMemcpyAsync(d_probs, probs, nq * 8, hipMemcpyHostToDevice, c->stream));
+            reducer_scratch(c, 0);
+            if (nq) HIPCHK(hipMemcpyAsync(dprobs.in(d), probs, nq * 8, hipMemcpyHostToDevice, c->stream));
             const bool cols = out->mean || out->median || out->quantile;
-            const size_t cap = c->st_scr_bytes;
             auto per_chain = [&](size_t kb) { return (size_t)n * (8 * kb + 4); };
             size_t kb = cols ? np : 0;
-            while (kb > 1 && per_chain(kb) > cap) kb = (kb + 1) / 2;
-            const int Nb = (int)std::min(N, cap / per_chain(kb));
+            while (kb > 1 && per_chain(kb) > c->st_scr_bytes) kb = (kb + 1) / 2;
             const int lds_n = std::min(STATS_LDS_N, 1 << (int)ceil(log2((double)std::max(n, 2))));
             const int bins = std::min(c->H.stats_mode_bins, std::max(P.Ng, 64));   // (STATS_MODE_BINS but for the test seam)
-            HIPCHK(hipFuncSetAttribute((const void*)k_stats_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
-            HIPCHK(hipFuncSetAttribute((const void*)k_stats_mode, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_MODE_BINS * 4));
             for (size_t k0 = 0; k0 < std::max(np, (size_t)1); k0 += std::max(kb, (size_t)1)) {
                 const int kbb = (int)std::min(kb, np - k0);
                 const int first = k0 == 0;
                 if (!first && !cols) break;
-                for (int c0 = 0; c0 < (int)N; c0 += Nb) {
-                    const int nb = std::min(Nb, (int)N - c0);
+                chain_batches(c, per_chain(kb), [&](int c0, int nb) {
                     double* col = (double*)c->st_scr;
                     int* pcol = (int*)(col + (size_t)kbb * nb * n);
-                    hipLaunchKernelGGL(k_stats_gather, dim3(nb), dim3(STATS_WG), 0, c->stream, (const double*)P.hrec, (int)N, P.HW, t0, n,
-                                       (int)(accepted_only != 0), c0, nb, (int)k0, kbb, first, col, pcol, d_count, d_nex, d_bestv, d_besti);
-                    HIPCHK(hipGetLastError());
-                    if (kbb > 0) {
-                        hipLaunchKernelGGL(k_stats_column, dim3(nb, kbb), dim3(STATS_WG), (size_t)lds_n * 8, c->stream, (const double*)col, n,
-                                           (int)N, c0, nb, (int)k0, (const int*)d_count, (const double*)d_probs, (int)nq, (int)np, d_mean,
-                                           d_median, d_quant);
-                        HIPCHK(hipGetLastError());
-                    }
-                    if (first) {
-                        hipLaunchKernelGGL(k_stats_mode, dim3(nb), dim3(STATS_WG), (size_t)bins * 4, c->stream, (const int*)pcol, n, c0, bins,
-                                           (const int*)d_nex, d_most);
-                        HIPCHK(hipGetLastError());
-                    }
-                }
+                    launch_checked(c, k_stats_gather, dim3(nb), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n,
+                                   (int)(accepted_only != 0), c0, nb, (int)k0, kbb, first, col, pcol, count.in(d), nex.in(d), bestv.in(d),
+                                   besti.in(d));
+                    if (kbb > 0)
+                        launch_checked(c, k_stats_column, dim3(nb, kbb), dim3(STATS_WG), (size_t)lds_n * 8, (const double*)col, n, (int)N, c0,
+                                       nb, (int)k0, (const int*)count.in(d), (const double*)dprobs.in(d), (int)nq, (int)np, mean.in(d),
+                                       median.in(d), quant.in(d));
+                    if (first)
+                        launch_checked(c, k_stats_mode, dim3(nb), dim3(STATS_WG), (size_t)bins * 4, (const int*)pcol, n, c0, bins,
+                                       (const int*)nex.in(d), most.in(d));
+                });
             }
-            HIPCHK(hipMemcpyAsync(hres.data(), c->st_res, rbytes, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(hres.data(), d, R.bytes, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
         }
-        const double* hd = (const double*)hres.data();
-        const int* hi = (const int*)(hres.data() + nd * 8);
-        if (out->best_value) memcpy(out->best_value, hd, N * 8);
-        if (out->mean) memcpy(out->mean, hd + N + nq, np * N * 8);
-        if (out->median) memcpy(out->median, hd + N + nq + np * N, np * N * 8);
-        if (out->quantile) memcpy(out->quantile, hd + N + nq + 2 * np * N, nq * np * N * 8);
-        if (out->count) memcpy(out->count, hi, N * 4);
-        if (out->n_exchanged) memcpy(out->n_exchanged, hi + N, N * 4);
-        if (out->best_iter) memcpy(out->best_iter, hi + 2 * N, N * 4);
-        if (out->most_exchanged_with) memcpy(out->most_exchanged_with, hi + 3 * N, N * 4);
+        void* h = hres.data();
+        if (out->best_value) memcpy(out->best_value, bestv.in(h), N * 8);
+        if (out->mean) memcpy(out->mean, mean.in(h), np * N * 8);
+        if (out->median) memcpy(out->median, median.in(h), np * N * 8);
+        if (out->quantile) memcpy(out->quantile, quant.in(h), nq * np * N * 8);
+        if (out->count) memcpy(out->count, count.in(h), N * 4);
+        if (out->n_exchanged) memcpy(out->n_exchanged, nex.in(h), N * 4);
+        if (out->best_iter) memcpy(out->best_iter, besti.in(h), N * 4);
+        if (out->most_exchanged_with) memcpy(out->most_exchanged_with, most.in(h), N * 4);
     } catch (const std::string& m) {
         return fail(c, SMM_ERR_HIP, m);
     }
@@ -3138,28 +3163,18 @@ int smm_get_chain_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only
 
 // --- covariances of the chains' draws, and the proposal factor between steps (smm_cov.hpp) ---------------------------------------------
 
-// the covariance of every local chain's selected draws over [t0, t1) on the device: count [N], mean [np][N], cov [np][np][N] in c->cv_res
-// (status [N] behind them, for smm_adapt_proposal).  The caller has settled, flushed and synchronised, and checked the window.
+// the covariance of every local chain's selected draws over [t0, t1) on the device: count [N], mean [np][N], cov [np][np][N] in the
+// reducers' result buffer (status [N] behind them, for smm_adapt_proposal).  The caller has run the prelude and checked the window.
 struct CovRes { int* count; double* mean; double* cov; int* status; };
 static CovRes chain_cov_device(Ctx* c, int t0, int t1, int accepted_only, int unit_space) {
     const KParams& P = c->P;
     const size_t N = P.N, np = P.np;
     const int n = t1 - t0;
-    // doubles mean[np][N], cov[np][np][N], bestv[N]; ints count, nex, besti, status [N]
-    const size_t nd = np * N + np * np * N + N, rbytes = nd * 8 + 4 * N * 4;
-    if (rbytes > c->cv_res_bytes) {
-        if (c->cv_res) { HIPCHK(hipFree(c->cv_res)); c->cv_res = nullptr; c->cv_res_bytes = 0; }
-        HIPCHK(hipMalloc(&c->cv_res, rbytes));
-        c->cv_res_bytes = rbytes;
-    }
-    CovRes r;
-    r.mean = (double*)c->cv_res;
-    r.cov = r.mean + np * N;
-    double* d_bestv = r.cov + np * np * N;
-    r.count = (int*)(d_bestv + N);
-    int* d_nex = r.count + N;
-    int* d_besti = d_nex + N;
-    r.status = d_besti + N;
+    Carve R;
+    const auto mean = R.take<double>(np * N), cov = R.take<double>(np * np * N), bestv = R.take<double>(N);
+    const auto count = R.take<int>(N), nex = R.take<int>(N), besti = R.take<int>(N), status = R.take<int>(N);
+    void* d = reducer_result(c, R.bytes);
+    const CovRes r{count.in(d), mean.in(d), cov.in(d), status.in(d)};
     if (n == 0) {   // nothing selected: count 0, mean and cov NaN
         HIPCHK(hipMemsetAsync(r.count, 0, N * 4, c->stream));
         std::vector<double> nan((np + np * np) * N, NAN);
@@ -3167,47 +3182,29 @@ static CovRes chain_cov_device(Ctx* c, int t0, int t1, int accepted_only, int un
         HIPCHK(hipStreamSynchronize(c->stream));
         return r;
     }
-    // every parameter of a chain at once: the scratch holds at least one chain's columns of the whole capacity
-    const size_t one = (size_t)P.T * (8 * np + 4), need = std::max(chain_stats_scratch_bytes(c), one);
-    if (c->st_scr && c->st_scr_bytes < one) { HIPCHK(hipFree(c->st_scr)); c->st_scr = nullptr; c->st_scr_bytes = 0; }
-    if (!c->st_scr) {
-        c->st_scr_bytes = need;
-        HIPCHK(hipMalloc(&c->st_scr, c->st_scr_bytes));
-    }
-    const size_t per_chain = (size_t)n * (8 * np + 4);
-    const int Nb = (int)std::min(N, c->st_scr_bytes / per_chain);
+    reducer_scratch(c, (size_t)P.T * (8 * np + 4));   // every parameter of a chain at once
     const int lds_n = std::min(STATS_LDS_N, 1 << (int)ceil(log2((double)std::max(n, 2))));
     const int nt = ((int)np + COV_T - 1) / COV_T, ntiles = nt * (nt + 1) / 2;
-    HIPCHK(hipFuncSetAttribute((const void*)k_cov_center, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
-    for (int c0 = 0; c0 < (int)N; c0 += Nb) {
-        const int nb = std::min(Nb, (int)N - c0);
+    chain_batches(c, (size_t)n * (8 * np + 4), [&](int c0, int nb) {
         double* col = (double*)c->st_scr;
         int* pcol = (int*)(col + np * nb * n);
-        hipLaunchKernelGGL(k_stats_gather, dim3(nb), dim3(STATS_WG), 0, c->stream, (const double*)P.hrec, (int)N, P.HW, t0, n,
-                           (int)(accepted_only != 0), c0, nb, 0, (int)np, 1, col, pcol, r.count, d_nex, d_bestv, d_besti);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_cov_center, dim3(nb, np), dim3(STATS_WG), (size_t)lds_n * 8, c->stream, col, n, (int)N, c0, nb,
-                           (int)(unit_space != 0), P.lb, P.ub, (const int*)r.count, r.mean);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_cov_pairs, dim3(nb, ntiles), dim3(COV_WG), 0, c->stream, (const double*)col, n, (int)N, c0, nb, (int)np,
-                           (const int*)r.count, r.cov);
-        HIPCHK(hipGetLastError());
-    }
+        launch_checked(c, k_stats_gather, dim3(nb), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)(accepted_only != 0),
+                       c0, nb, 0, (int)np, 1, col, pcol, r.count, nex.in(d), bestv.in(d), besti.in(d));
+        launch_checked(c, k_cov_center, dim3(nb, np), dim3(STATS_WG), (size_t)lds_n * 8, col, n, (int)N, c0, nb, (int)(unit_space != 0), P.lb,
+                       P.ub, (const int*)r.count, r.mean);
+        launch_checked(c, k_cov_pairs, dim3(nb, ntiles), dim3(COV_WG), 0, (const double*)col, n, (int)N, c0, nb, (int)np, (const int*)r.count,
+                       r.cov);
+    });
     return r;
 }
-
-static bool cov_window_ok(Ctx* c, int t0, int t1) { return !(t0 < 0 || t1 < t0 || t1 > c->iter); }
 
 int smm_get_chain_cov(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, int32_t unit_space, int32_t* count, double* mean,
                       double* cov) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return SMM_ERR_INVALID_ARG;
     try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        flush(c);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (!cov_window_ok(c, t0, t1)) return fail(c, SMM_ERR_INVALID_ARG, "window must satisfy 0 <= t0 <= t1 <= completed iterations");
+        reader_prelude(c);
+        if (const int rc = check_window(c, t0, t1)) return rc;
         const size_t N = c->P.N, np = c->P.np;
         const CovRes r = chain_cov_device(c, t0, t1, accepted_only, unit_space);
         if (count) HIPCHK(hipMemcpyAsync(count, r.count, N * 4, hipMemcpyDeviceToHost, c->stream));
@@ -3247,10 +3244,7 @@ int smm_get_proposal(void* ctx, double* L) {
 
 // the mutating calls: settled, flushed and synchronised; a hard failure standing on the context is handed to the caller (and marked told)
 static int proposal_prelude(Ctx* c) {
-    HIPCHK(hipSetDevice(c->device));
-    settle_persist(c);
-    flush(c);
-    HIPCHK(hipStreamSynchronize(c->stream));
+    reader_prelude(c);
     (void)check_device_error(c);
     return c->failed ? told(c) : SMM_OK;
 }
@@ -3294,12 +3288,11 @@ int smm_adapt_proposal(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only,
     try {
         const int rc = proposal_prelude(c);
         if (rc) return rc;
-        if (!cov_window_ok(c, t0, t1)) return fail(c, SMM_ERR_INVALID_ARG, "window must satisfy 0 <= t0 <= t1 <= completed iterations");
+        if (const int rc = check_window(c, t0, t1)) return rc;
         const size_t N = P.N;
         const CovRes r = chain_cov_device(c, t0, t1, accepted_only, 1);
-        hipLaunchKernelGGL(k_cov_chol, dim3(N), dim3(64), 0, c->stream, (const double*)r.cov, (const int*)r.count, (int)N, P.np,
-                           (int)min_draws, (int)(normalize != 0), ridge, P.chol_per_chain ? P.offset : 0, (double*)P.chol_L, r.status);
-        HIPCHK(hipGetLastError());
+        launch_checked(c, k_cov_chol, dim3(N), dim3(64), 0, (const double*)r.cov, (const int*)r.count, (int)N, P.np, (int)min_draws,
+                       (int)(normalize != 0), ridge, P.chol_per_chain ? P.offset : 0, (double*)P.chol_L, r.status);
         if (status) HIPCHK(hipMemcpyAsync(status, r.status, N * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     } catch (const std::string& m) {
@@ -3349,12 +3342,8 @@ int smm_get_chain_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32
         for (size_t i = 0; i < N; ++i)
             if (group[i] < -1 || group[i] >= n_groups) return fail(c, SMM_ERR_INVALID_ARG, "a group id outside [-1, n_groups)");
     try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        flush(c);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (t0 < 0 || t1 < t0 || t1 > c->iter)
-            return fail(c, SMM_ERR_INVALID_ARG, "window must satisfy 0 <= t0 <= t1 <= completed iterations");
+        reader_prelude(c);
+        if (const int rc = check_window(c, t0, t1)) return rc;
         const int n = t1 - t0;
         if (n < 4) return fail(c, SMM_ERR_INVALID_ARG, "the window must hold at least 4 iterations");
         if (max_lag < 1 || max_lag > n - 1) return fail(c, SMM_ERR_INVALID_ARG, "max_lag must lie in [1, t1 - t0 - 1]");
@@ -3362,55 +3351,33 @@ int smm_get_chain_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32
         const KParams& P = c->P;
         const size_t np = P.np, S = np + 1, SN = S * N, nacf = out->acf ? (size_t)n_acf : 0;
         const bool halves = out->rhat != nullptr;
-        // results: doubles ess [S][N], acf [nacf][S][N], hmu [2][S][N], hvar [2][S][N]; ints status [S][N], nacc [N], noex [N]
-        const size_t nd = SN + nacf * SN + 4 * SN, ni = SN + 2 * N, rbytes = nd * 8 + ni * 4;
-        if (rbytes > c->dg_res_bytes) {
-            if (c->dg_res) { HIPCHK(hipFree(c->dg_res)); c->dg_res = nullptr; c->dg_res_bytes = 0; }
-            HIPCHK(hipMalloc(&c->dg_res, rbytes));
-            c->dg_res_bytes = rbytes;
-        }
-        double* d_ess = (double*)c->dg_res;
-        double* d_acf = d_ess + SN;
-        double* d_hmu = d_acf + nacf * SN;
-        double* d_hvar = d_hmu + 2 * SN;
-        int* d_status = (int*)(d_hvar + 2 * SN);
-        int* d_nacc = d_status + SN;
-        int* d_noex = d_nacc + N;
-        // the S columns of a chain at once: the scratch holds at least one chain's columns of the whole capacity
-        const size_t one = (size_t)P.T * 8 * S, need = std::max(chain_stats_scratch_bytes(c), one);
-        if (c->st_scr && c->st_scr_bytes < one) { HIPCHK(hipFree(c->st_scr)); c->st_scr = nullptr; c->st_scr_bytes = 0; }
-        if (!c->st_scr) {
-            c->st_scr_bytes = need;
-            HIPCHK(hipMalloc(&c->st_scr, c->st_scr_bytes));
-        }
-        const size_t per_chain = (size_t)n * 8 * S;
-        const int Nb = (int)std::min(N, c->st_scr_bytes / per_chain);
+        Carve R;
+        const auto ess = R.take<double>(SN), acf = R.take<double>(nacf * SN), hmu = R.take<double>(2 * SN), hvar = R.take<double>(2 * SN);
+        const auto status = R.take<int>(SN), nacc = R.take<int>(N), noex = R.take<int>(N);
+        void* d = reducer_result(c, R.bytes);
+        reducer_scratch(c, (size_t)P.T * 8 * S);   // the S columns of a chain at once
         const int lds_n = std::min(STATS_LDS_N, n);
-        HIPCHK(hipFuncSetAttribute((const void*)k_diag_acov, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
-        for (int c0 = 0; c0 < (int)N; c0 += Nb) {
-            const int nb = std::min(Nb, (int)N - c0);
+        chain_batches(c, (size_t)n * 8 * S, [&](int c0, int nb) {
             double* col = (double*)c->st_scr;
-            hipLaunchKernelGGL(k_diag_gather, dim3(nb), dim3(DIAG_WG), 0, c->stream, (const double*)P.hrec, (int)N, P.HW, (int)np, t0, n, c0,
-                               nb, col, d_nacc, d_noex);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_diag_acov, dim3(nb, S), dim3(DIAG_WG), (size_t)lds_n * 8, c->stream, col, n, (int)N, c0, nb, (int)S,
-                               (int)max_lag, (int)nacf, (int)halves, d_ess, d_status, nacf ? d_acf : nullptr, d_hmu, d_hvar);
-            HIPCHK(hipGetLastError());
-        }
-        std::vector<char> hres(rbytes);
-        HIPCHK(hipMemcpyAsync(hres.data(), c->dg_res, rbytes, hipMemcpyDeviceToHost, c->stream));
+            launch_checked(c, k_diag_gather, dim3(nb), dim3(DIAG_WG), 0, (const double*)P.hrec, (int)N, P.HW, (int)np, t0, n, c0, nb, col,
+                           nacc.in(d), noex.in(d));
+            launch_checked(c, k_diag_acov, dim3(nb, S), dim3(DIAG_WG), (size_t)lds_n * 8, col, n, (int)N, c0, nb, (int)S, (int)max_lag,
+                           (int)nacf, (int)halves, ess.in(d), status.in(d), nacf ? acf.in(d) : nullptr, hmu.in(d), hvar.in(d));
+        });
+        std::vector<char> hres(R.bytes);
+        HIPCHK(hipMemcpyAsync(hres.data(), d, R.bytes, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        const double* hd = (const double*)hres.data();
-        const int* hs = (const int*)(hd + nd);
+        void* h = hres.data();
+        const int* hs = status.in(h);
         if (out->accept_rate)
-            for (size_t i = 0; i < N; ++i) out->accept_rate[i] = (double)hs[SN + i] / (double)hs[SN + N + i];
-        if (out->ess) memcpy(out->ess, hd, SN * 8);
+            for (size_t i = 0; i < N; ++i) out->accept_rate[i] = (double)nacc.in(h)[i] / (double)noex.in(h)[i];
+        if (out->ess) memcpy(out->ess, ess.in(h), SN * 8);
         if (out->status) memcpy(out->status, hs, SN * 4);
-        if (out->acf) memcpy(out->acf, hd + SN, nacf * SN * 8);
+        if (out->acf) memcpy(out->acf, acf.in(h), nacf * SN * 8);
         if (out->rhat) {   // split R-hat of each group and series, the members in ascending local index (include/smmhip.h)
-            const double* hmu = hd + SN + nacf * SN;
-            const double* hvar = hmu + 2 * SN;
-            const int h = n / 2;
+            const double* hm = hmu.in(h);
+            const double* hv = hvar.in(h);
+            const int hl = n / 2;
             std::vector<double> mus, vars, e;
             for (int g = 0; g < n_groups; ++g)
                 for (size_t s = 0; s < S; ++s) {
@@ -3420,8 +3387,8 @@ int smm_get_chain_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32
                         if (group[i] != g) continue;
                         bad |= hs[s * N + i] == 3;
                         for (int hf = 0; hf < 2; ++hf) {
-                            mus.push_back(hmu[hf * SN + s * N + i]);
-                            vars.push_back(hvar[hf * SN + s * N + i]);
+                            mus.push_back(hm[hf * SN + s * N + i]);
+                            vars.push_back(hv[hf * SN + s * N + i]);
                         }
                     }
                     double r = NAN;
@@ -3431,7 +3398,7 @@ int smm_get_chain_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32
                         e.resize(mus.size());
                         for (size_t q = 0; q < mus.size(); ++q) { const double dv = mus[q] - mm; e[q] = dv * dv; }
                         const double v = host_sum(e) / (k2 - 1.0);
-                        const double vp = ((h - 1.0) / h) * W + v;
+                        const double vp = ((hl - 1.0) / hl) * W + v;
                         r = sqrt(vp / W);
                     }
                     out->rhat[(size_t)g * S + s] = r;
@@ -3447,10 +3414,7 @@ int smm_get_state(void* ctx, smm_state_t* s) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !s) return SMM_ERR_INVALID_ARG;
     try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        flush(c);
-        HIPCHK(hipStreamSynchronize(c->stream));
+        reader_prelude(c);
         const KParams& P = c->P;
         const size_t N = P.N, RW = P.RW, np = P.np, nm = P.nm;
         std::vector<double> cs(N * CSW), rec(N * RW);

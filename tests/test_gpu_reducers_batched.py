@@ -23,8 +23,8 @@ STATS_MODE_BINS = 16384          # smm_stats.hpp
 
 
 class Plan:
-    """the host's batch plan of the reducers (smmhip.hip: chain_stats_scratch_bytes, smm_get_chain_stats, chain_cov_device,
-    smm_get_chain_diag), following one context's shared scratch st_scr across its calls"""
+    """the host's batch plan of the reducers (smmhip.hip: chain_stats_scratch_bytes, reducer_scratch, chain_batches,
+    smm_get_chain_stats, chain_cov_device, smm_get_chain_diag), following one context's shared scratch st_scr across its calls"""
 
     def __init__(self, N, T, npar, cap=STATS_SCRATCH_CAP):
         self.N, self.T, self.np, self.cap = N, T, npar, cap
