@@ -457,6 +457,40 @@ typedef struct {            /* caller-allocated; any pointer may be NULL = not c
 int  smm_get_chain_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32_t n_acf,
                         const int32_t* group /* [N] or NULL */, int32_t n_groups, smm_chain_diag_t* out);
 
+/* Pooled summaries of groups of chains computed on the device from the history it holds: the posterior of a group's pooled draws (mean,
+ * median, quantiles, covariance over every member's draws), over the 0-based iterations [t0, t1).  Group g is made of the LOCAL chains
+ * with group[c] == g (-1: in no group; a shard reports its own groups of local chains), in ascending local index; group NULL with
+ * n_groups == 1: every local chain in group 0.  Pooled column of group g, parameter k: the concatenation over the members in that order of
+ * each member's selected draws of the window in iteration order, selected exactly as smm_get_chain_stats selects them (accepted_only) —
+ * bit for bit np.concatenate([params(c, accepted_only)[k] for c in members]).  Caller-allocated; any pointer may be NULL (not returned).
+ * Read-only and ordered like smm_get_chain_stats (it settles, flushes and synchronises, and changes no state, history or generator).  It
+ * uses smm_get_chain_stats' scratch, grown where needed to N x maxiter x 8 bytes (one parameter's pooled columns) and, for cov, to
+ * np x 8192 x 8 bytes (every parameter of one chunk); pooled columns that do not fit are reduced in batches of parameters, and the
+ * covariance in batches of chunks, each batch reading the window once more.  Results: ((2 + n_probs) np + np np) n_groups x 8 bytes and
+ * the plan's tables (chunk sums, ranks, up to 32 MiB of histograms).  SMM_ERR_INVALID_ARG: NULL ctx or out, a bad window, n_groups < 0,
+ * group NULL with n_groups != 1, a group id outside [-1, n_groups), n_probs < 0, probs NULL with n_probs > 0, a prob outside [0, 1] or
+ * NaN, quantile without probs.
+ *
+ * Numerical contract: smm_get_chain_stats' and smm_get_chain_cov's, on the pooled column x of m = count draws (every operation rounded on
+ * its own, no fma; ranks and counts 64-bit):
+ *   mean       = the chain-stats mean: S / m, S = S + pw(x, c, min(8192, m-c)) for c = 0, 8192, .. (chunks from the group's first draw,
+ *                straddling the members' boundaries)
+ *   median, quantile p = the chain-stats order statistics of x (numpy's _lerp); the -0/+0 caveat of smm_get_chain_stats holds
+ *   cov_jk     = S(d_j * d_k) / (m - 1), d_j = x_j - mean_j, S the same chunked pairwise sum; cov_kj the same value
+ *   a NaN among the group's draws: mean, median and every quantile NaN (and it propagates into cov); m == 0: NaN everywhere, count 0;
+ *   m < 2: cov NaN. */
+typedef struct {            /* caller-allocated; any pointer may be NULL = not computed                                        */
+    int64_t* count;         /* [n_groups]                 selected draws pooled in the group                                   */
+    int32_t* n_chains;      /* [n_groups]                 member chains                                                        */
+    double*  mean;          /* [n_groups][np]                                                                                  */
+    double*  median;        /* [n_groups][np]                                                                                  */
+    double*  quantile;      /* [n_probs][n_groups][np]                                                                         */
+    double*  cov;           /* [n_groups][np][np]  both triangles                                                              */
+} smm_group_stats_t;
+int  smm_get_group_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only,
+                         const int32_t* group /* [N] or NULL */, int32_t n_groups,
+                         const double* probs, int32_t n_probs, smm_group_stats_t* out);
+
 /* Covariances of the chains' draws and the proposal factor between steps — adaptive Metropolis (Haario et al.) on top of chol_L: a
  * pilot run, then each chain's proposal shaped by the covariance of its own draws, without leaving the device.
  *

@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_group_stats, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
 const ABI_VERSION = 3
@@ -110,6 +110,15 @@ struct SmmChainDiag
     status::Ptr{Int32}
     acf::Ptr{Cdouble}
     rhat::Ptr{Cdouble}
+end
+
+struct SmmGroupStats
+    count::Ptr{Int64}
+    n_chains::Ptr{Int32}
+    mean::Ptr{Cdouble}
+    median::Ptr{Cdouble}
+    quantile::Ptr{Cdouble}
+    cov::Ptr{Cdouble}
 end
 
 struct SmmState
@@ -387,6 +396,35 @@ function hip_chain_diag(h::HipBGP, t0::Integer, t1::Integer; max_lag::Integer = 
                            h.ctx, t0, t1, max_lag, n_acf, ng > 0 ? pointer(g) : Ptr{Int32}(C_NULL), ng, cd))
     end
     return (accept_rate = rate, ess = ess, status = st, acf = acf, rhat = rhat)   # (the header's row-major = these column-major arrays)
+end
+
+"""
+    hip_group_stats(h, t0, t1; accepted_only = true, groups = nothing, probs = Float64[]) -> NamedTuple
+
+The posterior of each group's pooled draws over iterations `t0+1 .. t1`, on the device (`smm_get_group_stats`): a group's pooled
+column is the concatenation of its members' selected draws, members in ascending chain order.  `groups[chain]` holds 0-based group
+ids (-1 = none); `nothing`: every chain in one group.  Returns `count[g]`, `n_chains[g]`, `mean[k, g]`, `median[k, g]`,
+`quantile[k, g, p]` and `cov[j, k, g]`.  NumPy's summation and order statistics (include/smmhip.h).
+"""
+function hip_group_stats(h::HipBGP, t0::Integer, t1::Integer; accepted_only::Bool = true,
+                         groups::Union{Nothing,AbstractVector{<:Integer}} = nothing, probs::AbstractVector{<:Real} = Float64[])
+    N, np = h.N, h.np
+    g = groups === nothing ? Int32[] : Vector{Int32}(groups)
+    groups === nothing || length(g) == N || throw(ArgumentError("groups needs one entry per chain"))
+    ng = groups === nothing ? 1 : (isempty(g) ? 0 : Int(maximum(g)) + 1)
+    p = Vector{Float64}(probs); nq = length(p)
+    count = Vector{Int64}(undef, ng); nch = Vector{Int32}(undef, ng)
+    mean = Matrix{Float64}(undef, np, ng); med = Matrix{Float64}(undef, np, ng)
+    quant = Array{Float64}(undef, np, ng, nq); cov = Array{Float64}(undef, np, np, ng)
+    GC.@preserve g p count nch mean med quant cov begin
+        gs = SmmGroupStats(pointer(count), pointer(nch), pointer(mean), pointer(med), nq > 0 ? pointer(quant) : Ptr{Cdouble}(C_NULL),
+                           pointer(cov))
+        check(h.ctx, ccall(sym(:smm_get_group_stats), Cint,
+                           (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Int32}, Cint, Ptr{Cdouble}, Cint, Ref{SmmGroupStats}),
+                           h.ctx, t0, t1, accepted_only ? 1 : 0, groups === nothing ? Ptr{Int32}(C_NULL) : pointer(g), ng,
+                           nq > 0 ? pointer(p) : Ptr{Cdouble}(C_NULL), nq, gs))
+    end
+    return (count = count, n_chains = nch, mean = mean, median = med, quantile = quant, cov = cov)   # (the header's row-major arrays)
 end
 
 # the factor(s) between the header's row-major [np][np] / [N][np][np] and Julia's L[k, j] / L[k, j, c]

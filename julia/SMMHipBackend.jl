@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, adapt_proposal!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, pooled_summary, adapt_proposal!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -338,6 +338,28 @@ function chain_diag(algo::MAlgoBGPHip; t0::Integer = 0, t1 = nothing, max_lag = 
     hip = getfield(algo, :hip)
     t1 = t1 === nothing ? SMMHip.hip_iter(hip) : t1
     return SMMHip.hip_chain_diag(hip, t0, t1; max_lag = max_lag === nothing ? t1 - t0 - 1 : max_lag, n_acf = n_acf, groups = groups)
+end
+
+"""
+    pooled_summary(algo; groups = nothing, window = nothing, level = 0.95, accepted_only = true) -> NamedTuple
+
+The posterior of each group's pooled draws, computed on the device from the history it holds (`SMMHip.hip_group_stats`): `count`,
+`n_chains`, `mean[k, g]`, `median[k, g]`, `CI[k, g, 1:2]` (the `level` credible interval) and `cov[j, k, g]`.  `groups[chain]` holds
+0-based group ids (-1 = none); by default the chains with equal `acc_tuners` entries, numbered in order of first appearance.
+`window = (t0, t1)` defaults to every completed iteration.  Not a method of `SMM`: the reference has no such function.
+"""
+function pooled_summary(algo::MAlgoBGPHip; groups = nothing, window = nothing, level::Real = 0.95, accepted_only::Bool = true)
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    t0, t1 = window === nothing ? (0, SMMHip.hip_iter(hip)) : window
+    if groups === nothing   # (MAlgoBGPHip holds every chain of the population: the context's N)
+        ids = Dict{Float64,Int32}()
+        opts = getfield(algo, :opts)
+        groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
+    end
+    q = ((1 - level) / 2, 1 - (1 - level) / 2)
+    r = SMMHip.hip_group_stats(hip, t0, t1; accepted_only = accepted_only, groups = groups, probs = collect(Float64, q))
+    return (count = r.count, n_chains = r.n_chains, mean = r.mean, median = r.median, CI = r.quantile, cov = r.cov)
 end
 
 """

@@ -108,6 +108,13 @@ class smm_chain_diag_t(C.Structure):
     ]
 
 
+class smm_group_stats_t(C.Structure):
+    _fields_ = [
+        ("count", C.POINTER(C.c_int64)), ("n_chains", c_int32_p), ("mean", c_double_p), ("median", c_double_p),
+        ("quantile", c_double_p), ("cov", c_double_p),
+    ]
+
+
 class smm_timing_t(C.Structure):
     _fields_ = [
         ("step_ms", C.c_double), ("iter_kernel_ms", C.c_double), ("exch_kernel_ms", C.c_double),
@@ -152,6 +159,8 @@ SYMBOLS = [
                                       C.POINTER(smm_chain_stats_t)]),
     ("smm_get_chain_diag", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32,
                                      C.POINTER(smm_chain_diag_t)]),
+    ("smm_get_group_stats", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_double_p, C.c_int32,
+                                      C.POINTER(smm_group_stats_t)]),
     ("smm_get_chain_cov", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
     ("smm_get_proposal", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_proposal", C.c_int, [C.c_void_p, c_double_p]),

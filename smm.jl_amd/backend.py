@@ -295,6 +295,29 @@ class BGPContext:
                                                g.ctypes.data_as(A.c_int32_p) if g is not None else None, ng, C.byref(s)))
         return r
 
+    def group_stats(self, t0=0, t1=None, accepted_only=True, groups=None, probs=(), n_groups=None):
+        """the pooled draws of groups of local chains over iterations [t0, t1), summarised on the device (smm_get_group_stats,
+        include/smmhip.h): a dict of numpy arrays count / n_chains [n_groups], mean / median [n_groups][np], quantile
+        [len(probs)][n_groups][np], cov [n_groups][np][np].  groups: an int per chain (-1 = none), n_groups by default groups.max() + 1;
+        None: every local chain in one group"""
+        t1 = self.state().iter if t1 is None else t1
+        p = A.f64(probs).reshape(-1)
+        N, np_ = self.N, self.np
+        g = None if groups is None else np.ascontiguousarray(groups, np.int32)
+        if g is not None and g.shape != (N,):
+            raise ValueError("group_stats: groups needs one entry per chain, got shape %s" % (g.shape,))
+        ng = (1 if g is None else (int(g.max()) + 1 if len(g) else 0)) if n_groups is None else int(n_groups)
+        r = dict(count=np.empty(ng, np.int64), n_chains=np.empty(ng, np.int32), mean=np.empty((ng, np_)), median=np.empty((ng, np_)),
+                 quantile=np.empty((len(p), ng, np_)), cov=np.empty((ng, np_, np_)))
+        s = A.smm_group_stats_t()
+        for f, t in A.smm_group_stats_t._fields_:
+            if f != "quantile" or len(p):
+                setattr(s, f, r[f].ctypes.data_as(t))
+        self._check(self._fn("get_group_stats")(self._ctx, int(t0), int(t1), int(bool(accepted_only)),
+                                                g.ctypes.data_as(A.c_int32_p) if g is not None else None, ng,
+                                                A.dptr(p) if len(p) else None, len(p), C.byref(s)))
+        return r
+
     def _proposal_shape(self):
         if self.proposal_layout is None:
             return None

@@ -14,6 +14,7 @@
 //                  32 doubles per clock per CU against
 //                  about 64 FP64 adds: the blocked product keeps both busy).  After a leaf the 8 accumulators meet by a butterfly, lane
 //                  a = 0 adds the tail, pushes the 4 leaf sums on the pairs' stacks in LDS and makes the leaf's combines there.
+//                  raw != 0 writes the sum S instead of S / (m - 1): smm_group.hpp runs it over 8192-draw chunks of pooled columns.
 //   k_cov_chol   : one wave per chain, lane = row k (np <= MAX_DIM = 64): A = C / tau (+ ridge on the diagonal) in LDS (32 KB at
 //                  np = 64); column j: lane j finishes the pivot, then lanes k > j their entry, each subtracting in i order — the
 //                  restatement's order.  The factor goes straight into the chain's rows of P.chol_L, and only where status is 0.
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(STATS_WG) void k_cov_center(double* __restrict__ co
 }
 
 __global__ __launch_bounds__(COV_WG) void k_cov_pairs(const double* __restrict__ col, int n, int N, int c0, int Nb, int np,
-                                                      const int* __restrict__ o_count, double* __restrict__ o_cov) {
+                                                      const int* __restrict__ o_count, double* __restrict__ o_cov, int raw) {
     __shared__ double sd[2 * COV_T][COV_G + COV_PAD];          // the tile's columns: rows j0.., then columns k0..
     __shared__ double stk[COV_T * COV_T][COV_STK];
     __shared__ int loff[STATS_LEAF_MAX], lnum[STATS_LEAF_MAX], lcomb[STATS_LEAF_MAX];
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(COV_WG) void k_cov_pairs(const double* __restrict__
     for (int q = 0; q < 4; ++q) {
         const int j = j0 + 2 * bj + (q >> 1), k = k0 + 2 * bk + (q & 1);
         if (j >= np || k >= np || k > j) continue;             // (the pairs above the diagonal of a diagonal tile: their mirror writes both)
-        const double v = m < 2 ? qnan : S[q] / den;
+        const double v = raw ? S[q] : m < 2 ? qnan : S[q] / den;   // (raw: the sum itself, for smm_group.hpp's chunks)
         o_cov[((size_t)j * np + k) * N + c] = v;
         o_cov[((size_t)k * np + j) * N + c] = v;
     }

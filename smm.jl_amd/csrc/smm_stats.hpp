@@ -243,18 +243,41 @@ __device__ unsigned long long stats_select(const double* __restrict__ x, int m, 
     return prefix;
 }
 
-// quantile of the sorted column by numpy's linear method (include/smmhip.h); at(i) = i-th smallest draw
-template <class At>
-__device__ double stats_quantile(int m, double p, At at) {
+// quantile of the sorted column by numpy's linear method (include/smmhip.h); at(i) = i-th smallest draw (I: int for a chain's
+// column, long long for a pooled one)
+template <class At, class I = int>
+__device__ double stats_quantile(I m, double p, At at) {
     const double h = (double)(m - 1) * p;
     double a, b, g;
     if (h >= (double)(m - 1)) { a = b = at(m - 1); g = h + 1.0; }   // numpy: both indexes clipped to -1, gamma = h - (-1)
     else {
-        const int j = (int)floor(h);
+        const I j = (I)floor(h);
         a = at(j); b = at(j + 1); g = h - (double)j;
     }
     const double d = b - a;
     return g >= 0.5 ? b - d * (1.0 - g) : a + d * g;
+}
+
+// the keys of x(0 .. m) (m <= STATS_LDS_N) sorted into sk[0 .. m) in LDS by a bitonic sort (padded with ~0 to a power of two); x(i) may
+// read sk[i] itself.  Every thread of the block calls it.
+template <class X>
+__device__ void stats_sort(unsigned long long* __restrict__ sk, int m, X x) {
+    const int tid = threadIdx.x;
+    int P = 2;
+    while (P < m) P <<= 1;
+    for (int i = tid; i < P; i += STATS_WG) sk[i] = i < m ? stats_key(x(i)) : ~0ull;
+    __syncthreads();
+    for (int kb = 2; kb <= P; kb <<= 1)
+        for (int j = kb >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += STATS_WG) {
+                const int ij = i ^ j;
+                if (ij > i) {
+                    const unsigned long long a = sk[i], b = sk[ij];
+                    if ((a > b) == ((i & kb) == 0)) { sk[i] = b; sk[ij] = a; }
+                }
+            }
+            __syncthreads();
+        }
 }
 
 __global__ __launch_bounds__(STATS_WG) void k_stats_column(const double* __restrict__ col, int n, int N, int c0, int Nb, int k0,
@@ -282,21 +305,7 @@ __global__ __launch_bounds__(STATS_WG) void k_stats_column(const double* __restr
     }
     if (m <= STATS_LDS_N) {   // the column is in LDS: sort its keys there
         unsigned long long* sk = (unsigned long long*)sx;
-        int P = 2;
-        while (P < m) P <<= 1;
-        for (int i = tid; i < P; i += STATS_WG) sk[i] = i < m ? stats_key(sx[i]) : ~0ull;
-        __syncthreads();
-        for (int kb = 2; kb <= P; kb <<= 1)
-            for (int j = kb >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < P; i += STATS_WG) {
-                    const int ij = i ^ j;
-                    if (ij > i) {
-                        const unsigned long long a = sk[i], b = sk[ij];
-                        if ((a > b) == ((i & kb) == 0)) { sk[i] = b; sk[ij] = a; }
-                    }
-                }
-                __syncthreads();
-            }
+        stats_sort(sk, m, [&](int i) { return sx[i]; });
         if (tid == 0) {
             auto at = [&](int i) { return stats_unkey(sk[i]); };
             o_mean[(size_t)k * N + c] = S / (double)m;

@@ -69,6 +69,7 @@ using namespace smm;
 #include "smm_stats.hpp"
 #include "smm_cov.hpp"
 #include "smm_diag.hpp"
+#include "smm_group.hpp"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -394,6 +395,7 @@ struct Hooks {
     bool rows_win_check = false;   // the p2p rows resolution checked against the plain kernels
     size_t stats_scratch = 0;      // the reducers' scratch cap instead of STATS_SCRATCH_CAP (0: that cap): batches of chains and parameters at small sizes
     int stats_mode_bins = STATS_MODE_BINS;   // partner ids per pass of k_stats_mode (1 .. STATS_MODE_BINS): several passes at small populations
+    long long group_wide_min = STATS_LDS_N + 1;   // pooled columns of at least so many draws take the grid-wide select (1 .. STATS_LDS_N + 1)
 };
 Hooks read_hooks() {
     Hooks H;
@@ -427,6 +429,7 @@ Hooks read_hooks() {
     H.rows_win_check = SMM_HOOK("SMMHIP_ROWS_WIN_CHECK") != nullptr;
     if (const char* v = SMM_HOOK("SMMHIP_STATS_SCRATCH")) H.stats_scratch = (size_t)strtoull(v, nullptr, 10);
     if (const char* v = SMM_HOOK("SMMHIP_STATS_MODE_BINS")) H.stats_mode_bins = std::min(STATS_MODE_BINS, std::max(1, atoi(v)));
+    if (const char* v = SMM_HOOK("SMMHIP_GROUP_WIDE_MIN")) H.group_wide_min = std::min((long long)STATS_LDS_N + 1, std::max(1ll, atoll(v)));
     return H;
 }
 // Which stand-alone kernel resolves exchangeMoves! (AlgoBGP.jl:647-716) — ONE decision, taken once per context (select_forms),
@@ -2457,11 +2460,13 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
             if (tile_smem(c, is_sim(c->obj) ? F.ct : (c->obj == SMM_OBJ_DENSE ? 16 : 8)) > (size_t)lim)
                 throw std::string("tile does not fit the 160 KiB LDS");
         }
-        // the history reducers' dynamic LDS: a chunk of draws (k_stats_column, k_cov_center, k_diag_acov), the partner ids of a pass (k_stats_mode)
+        // the history reducers' dynamic LDS: a chunk of draws (k_stats_column, k_cov_center, k_diag_acov, k_group_*), the partner ids of a pass (k_stats_mode)
         HIPCHK(hipFuncSetAttribute((const void*)k_stats_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
         HIPCHK(hipFuncSetAttribute((const void*)k_cov_center, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
         HIPCHK(hipFuncSetAttribute((const void*)k_diag_acov, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
         HIPCHK(hipFuncSetAttribute((const void*)k_stats_mode, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_MODE_BINS * 4));
+        HIPCHK(hipFuncSetAttribute((const void*)k_group_chunk_sum, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+        HIPCHK(hipFuncSetAttribute((const void*)k_group_small, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
         HIPCHK(hipDeviceSynchronize());
     } catch (const std::string& m) {
         g_create_err = m;
@@ -3193,7 +3198,7 @@ static CovRes chain_cov_device(Ctx* c, int t0, int t1, int accepted_only, int un
         launch_checked(c, k_cov_center, dim3(nb, np), dim3(STATS_WG), (size_t)lds_n * 8, col, n, (int)N, c0, nb, (int)(unit_space != 0), P.lb,
                        P.ub, (const int*)r.count, r.mean);
         launch_checked(c, k_cov_pairs, dim3(nb, ntiles), dim3(COV_WG), 0, (const double*)col, n, (int)N, c0, nb, (int)np, (const int*)r.count,
-                       r.cov);
+                       r.cov, 0);
     });
     return r;
 }
@@ -3404,6 +3409,175 @@ int smm_get_chain_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32
                     out->rhat[(size_t)g * S + s] = r;
                 }
         }
+    } catch (const std::string& m) {
+        return fail(c, SMM_ERR_HIP, m);
+    }
+    return SMM_OK;
+}
+
+// --- pooled summaries of groups of chains (smm_group.hpp) -------------------------------------------------------------------------------
+
+int smm_get_group_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, const int32_t* group, int32_t n_groups,
+                        const double* probs, int32_t n_probs, smm_group_stats_t* out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !out) return SMM_ERR_INVALID_ARG;
+    if (n_groups < 0 || (!group && n_groups != 1)) return fail(c, SMM_ERR_INVALID_ARG, "n_groups < 0, or group NULL with n_groups != 1");
+    const size_t N = c->P.N;
+    if (group)
+        for (size_t i = 0; i < N; ++i)
+            if (group[i] < -1 || group[i] >= n_groups) return fail(c, SMM_ERR_INVALID_ARG, "a group id outside [-1, n_groups)");
+    if (n_probs < 0 || (n_probs > 0 && !probs)) return fail(c, SMM_ERR_INVALID_ARG, "n_probs < 0, or probs NULL with n_probs > 0");
+    if (out->quantile && n_probs == 0) return fail(c, SMM_ERR_INVALID_ARG, "quantile requested without probs");
+    for (int p = 0; p < n_probs; ++p)
+        if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) return fail(c, SMM_ERR_INVALID_ARG, "probs must lie in [0, 1]");
+    try {
+        reader_prelude(c);
+        if (const int rc = check_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t np = P.np, G = n_groups, nq = out->quantile ? n_probs : 0;
+        const int n = t1 - t0;
+        const bool med = out->median != nullptr, ord = med || nq > 0, cov = out->cov != nullptr, cols = out->mean || ord || cov;
+        // the members' counts (k_group_gather's counting form), then the plan on the host: the pooled offsets and the chunks
+        std::vector<int> gid(N, 0), cnt(N);
+        if (group) std::copy(group, group + N, gid.begin());
+        DevBuf<int> dci(2 * N);
+        HIPCHK(hipMemcpyAsync(dci.p, gid.data(), N * 4, hipMemcpyHostToDevice, c->stream));
+        launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)(accepted_only != 0),
+                       (const int*)dci.p, (const long long*)nullptr, (const int*)nullptr, 0, 0, 0ll, 0, 0, (const double*)nullptr, (int)np,
+                       (double*)nullptr, dci.p + N, 1);
+        HIPCHK(hipMemcpyAsync(cnt.data(), dci.p + N, N * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        std::vector<long long> gm(G, 0), G0(G + 1, 0), off(N, 0), roff(N, 0);
+        std::vector<int> nch(G, 0), gch0(G + 1, 0), cch0(N, 0);
+        for (size_t i = 0; i < N; ++i)
+            if (gid[i] >= 0) { roff[i] = gm[gid[i]]; gm[gid[i]] += cnt[i]; ++nch[gid[i]]; }
+        std::vector<long long> cst;
+        std::vector<int> clen;
+        for (size_t g = 0; g < G; ++g) {
+            G0[g + 1] = G0[g] + gm[g];
+            for (long long q = 0; q < gm[g]; q += STATS_LDS_N) { cst.push_back(G0[g] + q); clen.push_back((int)std::min<long long>(STATS_LDS_N, gm[g] - q)); }
+            gch0[g + 1] = (int)cst.size();
+        }
+        for (size_t i = 0; i < N; ++i)
+            if (gid[i] >= 0) { off[i] = G0[gid[i]] + roff[i]; cch0[i] = gch0[gid[i]]; }
+        const long long Mtot = G0[G];
+        const int NC = (int)cst.size();
+        // the order statistics: short columns sorted in LDS, the others selected grid-wide at ranks R per column (rk: -1 = unused)
+        std::vector<int> sgrp, wgrp;
+        long long wmax = 0;
+        for (size_t g = 0; g < G; ++g)
+            if (gm[g] < c->H.group_wide_min) sgrp.push_back((int)g);
+            else { wgrp.push_back((int)g); wmax = std::max(wmax, gm[g]); }
+        const int R = ord ? (med ? 2 : 0) + 2 * (int)nq : 0;
+        std::vector<long long> rk(wgrp.size() * R, -1);
+        for (size_t wi = 0; wi < wgrp.size() && R; ++wi) {   // stats_quantile's and the median's indexes
+            const long long m = gm[wgrp[wi]];
+            long long* r = rk.data() + wi * R;
+            if (med) { r[0] = (m & 1) ? m / 2 : m / 2 - 1; r[1] = (m & 1) ? -1 : m / 2; r += 2; }
+            for (size_t p = 0; p < nq; ++p, r += 2) {
+                const double h = (double)(m - 1) * probs[p];
+                if (h >= (double)(m - 1)) r[0] = m - 1;
+                else { r[0] = (long long)floor(h); r[1] = r[0] + 1; }
+            }
+        }
+        if (Mtot > 0 && cols) reducer_scratch(c, std::max(N * (size_t)P.T * 8, cov ? np * STATS_LDS_N * 8 : 0));
+        const size_t kb = Mtot > 0 && cols ? std::min(np, c->st_scr_bytes / ((size_t)Mtot * 8)) : 0;
+        const size_t nwc = wgrp.size() * kb;   // long columns of a parameter batch, selected WB at a time
+        const int WB = R ? (int)std::min(nwc, std::max((size_t)1, GROUP_HIST_CAP / ((size_t)R * GROUP_BINS * 8))) : 0;
+        Carve Rv;   // 8-byte slices first
+        const auto mean = Rv.take<double>(G * np), median = Rv.take<double>(G * np), quant = Rv.take<double>(nq * G * np),
+                   covo = Rv.take<double>(cov ? G * np * np : 0), dprobs = Rv.take<double>(nq), csum = Rv.take<double>(kb * NC),
+                   csum2 = Rv.take<double>(cov ? np * np * NC : 0);
+        const auto doff = Rv.take<long long>(2 * N), dG0 = Rv.take<long long>(G + 1), dgm = Rv.take<long long>(G),
+                   dcst = Rv.take<long long>(NC), drk = Rv.take<long long>(rk.size()), rem = Rv.take<long long>(nwc * R);
+        const auto pre = Rv.take<unsigned long long>(nwc * R), ghist = Rv.take<unsigned long long>((size_t)WB * R * GROUP_BINS);
+        const auto dcch0 = Rv.take<int>(N), dgch0 = Rv.take<int>(G + 1), dclen = Rv.take<int>(NC), cnan = Rv.take<int>(kb * NC),
+                   gnan = Rv.take<int>(G * np), dsg = Rv.take<int>(sgrp.size()), dwg = Rv.take<int>(wgrp.size());
+        void* d = reducer_result(c, Rv.bytes);
+        auto up = [&](auto sl, const auto& v) {
+            if (!v.empty()) HIPCHK(hipMemcpyAsync(sl.in(d), v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, c->stream));
+        };
+        std::vector<long long> offs(off);
+        offs.insert(offs.end(), roff.begin(), roff.end());
+        up(doff, offs); up(dG0, G0); up(dgm, gm); up(dcst, cst); up(drk, rk);
+        up(dcch0, cch0); up(dgch0, gch0); up(dclen, clen); up(dsg, sgrp); up(dwg, wgrp);
+        if (nq) HIPCHK(hipMemcpyAsync(dprobs.in(d), probs, nq * 8, hipMemcpyHostToDevice, c->stream));
+        const int* dgid = dci.p;
+        const int* dcnt = dci.p + N;
+        std::vector<long long> remh(nwc * R);
+        if (kb > 0) {
+            double* col = (double*)c->st_scr;
+            const int B = (int)std::min<long long>(1024, std::max<long long>(1, (wmax + STATS_WG * 16 - 1) / (STATS_WG * 16)));
+            for (size_t k0 = 0; k0 < np; k0 += kb) {   // batches of parameters: the packed columns [kbb][Mtot]
+                const int kbb = (int)std::min(kb, np - k0);
+                launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n,
+                               (int)(accepted_only != 0), dgid, (const long long*)doff.in(d), (const int*)nullptr, (int)k0, kbb, Mtot, 0, 0,
+                               (const double*)nullptr, (int)np, col, (int*)dcnt, 0);
+                if (NC > 0)
+                    launch_checked(c, k_group_chunk_sum, dim3(NC, kbb), dim3(STATS_WG), (size_t)STATS_LDS_N * 8, (const double*)col, Mtot,
+                                   (const long long*)dcst.in(d), (const int*)dclen.in(d), NC, csum.in(d), cnan.in(d));
+                launch_checked(c, k_group_mean, dim3((unsigned)((G * kbb + 255) / 256)), dim3(256), 0, (const double*)csum.in(d),
+                               (const int*)cnan.in(d), NC, (const int*)dgch0.in(d), (const long long*)dgm.in(d), (int)G, (int)k0, kbb,
+                               (int)np, mean.in(d), gnan.in(d));
+                if (!ord) continue;
+                double* omed = med ? median.in(d) : nullptr;
+                if (!sgrp.empty())
+                    launch_checked(c, k_group_small, dim3((unsigned)sgrp.size(), kbb), dim3(STATS_WG), (size_t)STATS_LDS_N * 8,
+                                   (const double*)col, Mtot, (const int*)dsg.in(d), (const long long*)dG0.in(d), (const long long*)dgm.in(d),
+                                   (int)G, (int)k0, (int)np, (const int*)gnan.in(d), (const double*)dprobs.in(d), (int)nq, omed, quant.in(d));
+                if (wgrp.empty()) continue;
+                const int nw = (int)wgrp.size() * kbb;
+                for (int w = 0; w < nw; ++w)
+                    for (int r = 0; r < R; ++r) remh[(size_t)w * R + r] = rk[(size_t)(w / kbb) * R + r];
+                HIPCHK(hipMemcpyAsync(rem.in(d), remh.data(), (size_t)nw * R * 8, hipMemcpyHostToDevice, c->stream));
+                HIPCHK(hipMemsetAsync(pre.in(d), 0, (size_t)nw * R * 8, c->stream));
+                HIPCHK(hipMemsetAsync(ghist.in(d), 0, (size_t)WB * R * GROUP_BINS * 8, c->stream));   // (k_group_pick zeroes it again)
+                for (int w0 = 0; w0 < nw; w0 += WB) {
+                    const int wn = std::min(WB, nw - w0);
+                    for (int dg = 0; dg < 6; ++dg) {
+                        launch_checked(c, k_group_hist, dim3(wn, B, (R + GROUP_RB - 1) / GROUP_RB), dim3(STATS_WG), 0, (const double*)col,
+                                       Mtot, (const int*)dwg.in(d), (const long long*)dG0.in(d), (const long long*)dgm.in(d), kbb, R, dg, w0,
+                                       (const long long*)rem.in(d), (const unsigned long long*)pre.in(d), ghist.in(d));
+                        launch_checked(c, k_group_pick, dim3(wn * R), dim3(STATS_WG), 0, dg, w0 * R, ghist.in(d), rem.in(d), pre.in(d));
+                    }
+                }
+                launch_checked(c, k_group_finish, dim3((nw + 63) / 64), dim3(64), 0, nw, (const int*)dwg.in(d), (const long long*)dgm.in(d),
+                               (int)G, (int)k0, kbb, (int)np, R, (const long long*)drk.in(d), (const unsigned long long*)pre.in(d),
+                               (const int*)gnan.in(d), (const double*)dprobs.in(d), (int)nq, omed, quant.in(d));
+            }
+            if (cov) {   // batches of chunks: every parameter centred, [np][nb][STATS_LDS_N]; each chunk's pair sums, then the groups'
+                const int Nbc = (int)std::min<size_t>(NC, c->st_scr_bytes / (np * STATS_LDS_N * 8));
+                const int nt = ((int)np + COV_T - 1) / COV_T, ntiles = nt * (nt + 1) / 2;
+                for (int cb0 = 0; cb0 < NC; cb0 += Nbc) {
+                    const int nb = std::min(Nbc, NC - cb0);
+                    launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n,
+                                   (int)(accepted_only != 0), dgid, (const long long*)doff.in(d) + N, (const int*)dcch0.in(d), 0, (int)np,
+                                   Mtot, cb0, nb, (const double*)mean.in(d), (int)np, col, (int*)dcnt, 0);
+                    launch_checked(c, k_cov_pairs, dim3(nb, ntiles), dim3(COV_WG), 0, (const double*)col, STATS_LDS_N, NC, cb0, nb, (int)np,
+                                   (const int*)dclen.in(d), csum2.in(d), 1);
+                }
+            }
+        }
+        if (cov && G > 0)
+            launch_checked(c, k_group_cov, dim3((unsigned)((G * np * (np + 1) / 2 + 255) / 256)), dim3(256), 0, (const double*)csum2.in(d),
+                           NC, (const int*)dgch0.in(d), (const long long*)dgm.in(d), (int)G, (int)np, covo.in(d));
+        auto down = [&](auto sl, void* dst, size_t bytes) {
+            if (dst && bytes) HIPCHK(hipMemcpyAsync(dst, sl.in(d), bytes, hipMemcpyDeviceToHost, c->stream));
+        };
+        if (kb > 0) {   // (no draw in any group: every output NaN, filled below)
+            down(mean, out->mean, G * np * 8);
+            down(median, out->median, G * np * 8);
+            down(quant, out->quantile, nq * G * np * 8);
+        }
+        down(covo, out->cov, G * np * np * 8);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (kb == 0) {
+            if (out->mean) std::fill(out->mean, out->mean + G * np, NAN);
+            if (out->median) std::fill(out->median, out->median + G * np, NAN);
+            if (out->quantile) std::fill(out->quantile, out->quantile + nq * G * np, NAN);
+        }
+        if (out->count) std::copy(gm.begin(), gm.end(), out->count);
+        if (out->n_chains) std::copy(nch.begin(), nch.end(), out->n_chains);
     } catch (const std::string& m) {
         return fail(c, SMM_ERR_HIP, m);
     }

@@ -427,15 +427,38 @@ def ess(c, window=None):
     return OrderedDict((k, float(d["ess"][i, c._j])) for i, k in enumerate(ps2s_names(c.m)))
 
 
+def _default_groups(algo):
+    """the chains with equal acc_tuners entries, which share a target density, numbered in order of first appearance"""
+    ids = {}
+    return [ids.setdefault(float(a), len(ids)) for a in algo._acc_tuner]
+
+
 def rhat(algo, groups=None, window=None):
     """the split R-hat of each parameter in each group of chains over window = (t0, t1) (default: the whole run), on the device:
     one OrderedDict per group.  groups: a group id per chain (-1 = none); by default the chains with equal acc_tuners entries, which
     share a target density, numbered in order of first appearance"""
-    if groups is None:
-        ids = {}
-        groups = [ids.setdefault(float(a), len(ids)) for a in algo._acc_tuner]
-    d = _diag(algo, window, groups)
+    d = _diag(algo, window, _default_groups(algo) if groups is None else groups)
     return [OrderedDict((k, float(d["rhat"][g, i])) for i, k in enumerate(ps2s_names(algo.m))) for g in range(d["rhat"].shape[0])]
+
+
+def pooled(algo, groups=None, window=None, accepted_only=True, level=0.95):
+    """the posterior of each group's pooled draws over window = (t0, t1) (default: the whole run), summarised on the device
+    (include/smmhip.h: smm_get_group_stats): one OrderedDict per group with count, chains, mean / median (name -> value), CI
+    (name -> [lo, hi]) and cov (ndarray [np][np]).  groups: a group id per chain (-1 = none); by default those of rhat"""
+    t0, t1 = (0, algo.i) if window is None else (int(window[0]), int(window[1]))
+    g = tuple(int(v) for v in (_default_groups(algo) if groups is None else groups))
+    q = ((1 - level) / 2, 1 - (1 - level) / 2)
+    key = (algo.i, t0, t1, g, bool(accepted_only), q)
+    if key not in algo._pooled:
+        algo._pooled[key] = algo._ctx.group_stats(t0, t1, accepted_only, np.asarray(g, np.int32), q)
+    r = algo._pooled[key]
+    names = ps2s_names(algo.m)
+    return [OrderedDict(count=int(r["count"][j]), chains=int(r["n_chains"][j]),
+                        mean=OrderedDict((k, float(r["mean"][j, i])) for i, k in enumerate(names)),
+                        median=OrderedDict((k, float(r["median"][j, i])) for i, k in enumerate(names)),
+                        CI=OrderedDict((k, r["quantile"][:, j, i].copy()) for i, k in enumerate(names)),
+                        cov=r["cov"][j].copy())
+            for j in range(r["count"].shape[0])]
 
 
 def summary(x):
@@ -530,6 +553,7 @@ class MAlgoBGP:
         self._last = None
         self._cov = None
         self._diag = {}
+        self._pooled = {}
 
     def _chain_stats(self, accepted_only, probs):
         key = (self.i, accepted_only, probs)
