@@ -491,6 +491,53 @@ int  smm_get_group_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_onl
                          const int32_t* group /* [N] or NULL */, int32_t n_groups,
                          const double* probs, int32_t n_probs, smm_group_stats_t* out);
 
+/* Histograms of the draws of groups of chains computed on the device from the history it holds, over the 0-based iterations [t0, t1):
+ * for each group and parameter numpy's np.histogram(x, bins, range), and for each pair (j, k) of parameters np.histogram2d(x_j, x_k,
+ * bins2), bit for bit.  Groups as in smm_get_group_stats (group[c] in [-1, n_groups), -1: in no group; group NULL with n_groups == 1:
+ * every local chain in group 0; a shard reports its own local chains; per-chain histograms: group = 0 .. N-1).  Column x of group g,
+ * parameter k: the members' selected rows in ascending local index, each in iteration order:
+ *   select 0: every row of the window;  1: the rows with accepted != 0 (bit for bit np.concatenate([params(c, accepted_only)[k] for c in
+ *   members]), smm_get_chain_stats' selection);  2: the state series x(t) = params[a(t)] of smm_get_chain_diag (a(t) looks back before
+ *   t0; a row with no such a(t) is NaN) — the MCMC marginal, weighted by holding time.  count[g]: the selected rows of the members.
+ * Caller-allocated; any pointer may be NULL (not returned).  Read-only and ordered like smm_get_chain_stats (it settles, flushes and
+ * synchronises, and changes no state, history or generator).  Device memory (the reducers' result buffer): N x (12 + 20 np) bytes of
+ * per-chain ranges and lists plus the tables of a batch of groups, each group taking np ((bins + 1) + bins + (bins2 + 1)) x 8 + n_pairs bins2
+ * bins2 x 8 bytes; a batch holds as many groups as fit 256 MiB (at least one), and larger results are produced and copied out batch by
+ * batch.  Counts are integers added with integer atomics: they do not depend on the order of additions, and counts over a shared given
+ * range add across shards.  SMM_ERR_INVALID_ARG: NULL ctx or out, a bad window, select outside [0, 2], n_groups < 0, group NULL with
+ * n_groups != 1, a group id outside [-1, n_groups), bins outside [1, 65536], a range row not finite or with lo > hi, n_pairs outside
+ * [0, np np], pairs NULL with n_pairs > 0, a pair entry outside [0, np), bins2 outside [1, 512] with n_pairs > 0, hist2 or edges2
+ * requested with n_pairs == 0.
+ *
+ * Numerical contract (every operation rounded on its own, no fma):
+ *   outer edges : range given: (lo, hi) = range[k] for every group;  else the min and max of the column, (0, 1) for an empty column, and
+ *                 status 1 for a NaN or +-inf in it (numpy raises): lo, hi, edges NaN.  Then lo == hi: lo = lo - 0.5, hi = hi + 0.5.
+ *                 hi - lo not finite: status 2, edges NaN (numpy's index arithmetic is undefined there; the one stated departure).
+ *                 Autodetected lo, hi and edges may differ from numpy's in the sign of a zero; counts never do.
+ *   edges       : numpy's linspace(lo, hi, b + 1): delta = hi - lo, step = delta / b; step != 0: e[i] = i step + lo, else
+ *                 e[i] = (i / b) delta + lo; e[b] = hi.  (b = bins for edges, bins2 for edges2.)
+ *   1-D         : numpy's uniform-bins path.  Edges not strictly increasing (a narrow range at a large magnitude): status 3 (numpy raises
+ *                 "Too many bins"), 1-D counts 0, edges as computed.  Otherwise, for each x: kept only if x >= lo && x <= hi (NaN
+ *                 dropped); f = ((x - lo) / delta) * bins, i = (int64)f; i == bins: i = bins - 1; x < e[i]: i = i - 1; then
+ *                 x >= e[i + 1] && i != bins - 1: i = i + 1; hist[i] += 1.
+ *   2-D         : numpy's histogramdd, per axis over edges2 of that parameter's outer edges: i = searchsorted(e, x, side='right') (exact
+ *                 for repeated edges; NaN sorts last); x == e[bins2]: i = i - 1; counted in cell (i_j - 1, i_k - 1) only when both axes
+ *                 land in [1, bins2].  A pair with status 1 or 2 on either axis: counts 0 (status 3 does not apply to the 2-D axes).
+ * Counts are np.histogram's and np.histogram2d's (as int64): density and any weighting are the caller's. */
+typedef struct {            /* caller-allocated; any pointer may be NULL = not returned                                        */
+    int64_t* count;         /* [G]                     rows selected for the group (NaN / outliers included)                   */
+    int32_t* status;        /* [G][np]                 0 ok, 1 autodetected range not finite, 2 width not finite, 3 1-D edges repeat */
+    double*  lo;            /* [G][np]                 outer edges actually used (after numpy's +-0.5)                         */
+    double*  hi;            /* [G][np]                                                                                         */
+    double*  edges;         /* [G][np][bins + 1]       numpy's linspace(lo, hi, bins + 1)                                      */
+    int64_t* hist;          /* [G][np][bins]           np.histogram counts                                                     */
+    double*  edges2;        /* [G][np][bins2 + 1]      linspace(lo, hi, bins2 + 1), the 2-D axes                               */
+    int64_t* hist2;         /* [G][n_pairs][bins2][bins2]  np.histogram2d counts, rows = the pair's first parameter            */
+} smm_histogram_t;
+int  smm_get_histogram(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group /* [N] or NULL */, int32_t n_groups,
+                       int32_t bins, const double* range /* [np][2] or NULL */, const int32_t* pairs /* [n_pairs][2] */,
+                       int32_t n_pairs, int32_t bins2, smm_histogram_t* out);
+
 /* Covariances of the chains' draws and the proposal factor between steps — adaptive Metropolis (Haario et al.) on top of chol_L: a
  * pilot run, then each chain's proposal shaped by the covariance of its own draws, without leaving the device.
  *

@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_group_stats, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_group_stats, hip_histogram, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
 const ABI_VERSION = 3
@@ -119,6 +119,17 @@ struct SmmGroupStats
     median::Ptr{Cdouble}
     quantile::Ptr{Cdouble}
     cov::Ptr{Cdouble}
+end
+
+struct SmmHistogram
+    count::Ptr{Int64}
+    status::Ptr{Int32}
+    lo::Ptr{Cdouble}
+    hi::Ptr{Cdouble}
+    edges::Ptr{Cdouble}
+    hist::Ptr{Int64}
+    edges2::Ptr{Cdouble}
+    hist2::Ptr{Int64}
 end
 
 struct SmmState
@@ -425,6 +436,47 @@ function hip_group_stats(h::HipBGP, t0::Integer, t1::Integer; accepted_only::Boo
                            nq > 0 ? pointer(p) : Ptr{Cdouble}(C_NULL), nq, gs))
     end
     return (count = count, n_chains = nch, mean = mean, median = med, quantile = quant, cov = cov)   # (the header's row-major arrays)
+end
+
+const HIST_SELECT = Dict(:all => 0, :accepted => 1, :state => 2)
+
+"""
+    hip_histogram(h, t0, t1; select = :accepted, groups = nothing, bins = 10, range = nothing, pairs = Tuple{Int,Int}[],
+                  bins2 = bins) -> NamedTuple
+
+Histograms of the draws of groups of chains over iterations `t0+1 .. t1`, counted on the device (`smm_get_histogram`) without
+downloading the history.  `select`: `:all` rows, `:accepted` rows (`params(c)`), or `:state`, the chain's state series (weighted by
+holding time).  `groups[chain]` holds 0-based group ids (-1 = none); `nothing`: every chain in one group.  `range`: an `np x 2`
+matrix of given outer edges, `nothing`: each group's own min and max.  `pairs`: 1-based parameter indexes `(j, k)` of 2-D histograms.
+Returns `count[g]`, `status[k, g]`, `lo[k, g]`, `hi[k, g]`, `edges[:, k, g]`, `hist[:, k, g]` and, with pairs, `edges2[:, k, g]`,
+`hist2[k_bin, j_bin, p, g]` (the header's row-major arrays).  Bins follow numpy's `histogram` (the last bin is closed: `x == hi`
+counts in it), not `StatsBase.fit(Histogram)`'s right-open bins.
+"""
+function hip_histogram(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :accepted,
+                       groups::Union{Nothing,AbstractVector{<:Integer}} = nothing, bins::Integer = 10,
+                       range::Union{Nothing,AbstractMatrix{<:Real}} = nothing, pairs = Tuple{Int,Int}[], bins2::Integer = bins)
+    N, np = h.N, h.np
+    g = groups === nothing ? Int32[] : Vector{Int32}(groups)
+    groups === nothing || length(g) == N || throw(ArgumentError("groups needs one entry per chain"))
+    ng = groups === nothing ? 1 : (isempty(g) ? 0 : Int(maximum(g)) + 1)
+    rg = range === nothing ? Float64[] : vec(Matrix{Float64}(permutedims(range)))   # row k = (lo, hi)
+    pr = Int32[v - 1 for p in pairs for v in p]
+    npr = length(pairs)
+    b2 = npr > 0 ? Int(bins2) : 0
+    count = Vector{Int64}(undef, ng); st = Matrix{Int32}(undef, np, ng)
+    lo = Matrix{Float64}(undef, np, ng); hi = Matrix{Float64}(undef, np, ng)
+    edges = Array{Float64}(undef, bins + 1, np, ng); hist = Array{Int64}(undef, bins, np, ng)
+    edges2 = Array{Float64}(undef, b2 + 1, np, ng); hist2 = Array{Int64}(undef, b2, b2, npr, ng)
+    GC.@preserve g rg pr count st lo hi edges hist edges2 hist2 begin
+        hs = SmmHistogram(pointer(count), pointer(st), pointer(lo), pointer(hi), pointer(edges), pointer(hist),
+                          npr > 0 ? pointer(edges2) : Ptr{Cdouble}(C_NULL), npr > 0 ? pointer(hist2) : Ptr{Int64}(C_NULL))
+        check(h.ctx, ccall(sym(:smm_get_histogram), Cint,
+                           (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Int32}, Cint, Cint, Ptr{Cdouble}, Ptr{Int32}, Cint, Cint, Ref{SmmHistogram}),
+                           h.ctx, t0, t1, HIST_SELECT[select], groups === nothing ? Ptr{Int32}(C_NULL) : pointer(g), ng, bins,
+                           range === nothing ? Ptr{Cdouble}(C_NULL) : pointer(rg), npr > 0 ? pointer(pr) : Ptr{Int32}(C_NULL), npr,
+                           max(b2, 1), hs))
+    end
+    return (count = count, status = st, lo = lo, hi = hi, edges = edges, hist = hist, edges2 = edges2, hist2 = hist2)
 end
 
 # the factor(s) between the header's row-major [np][np] / [N][np][np] and Julia's L[k, j] / L[k, j, c]

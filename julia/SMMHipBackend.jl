@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, pooled_summary, adapt_proposal!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, pooled_summary, chain_histogram, adapt_proposal!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -360,6 +360,31 @@ function pooled_summary(algo::MAlgoBGPHip; groups = nothing, window = nothing, l
     q = ((1 - level) / 2, 1 - (1 - level) / 2)
     r = SMMHip.hip_group_stats(hip, t0, t1; accepted_only = accepted_only, groups = groups, probs = collect(Float64, q))
     return (count = r.count, n_chains = r.n_chains, mean = r.mean, median = r.median, CI = r.quantile, cov = r.cov)
+end
+
+"""
+    chain_histogram(algo; window = nothing, select = :accepted, groups = nothing, bins = 10, range = nothing,
+                    pairs = Tuple{Int,Int}[], bins2 = bins) -> NamedTuple
+
+The histograms a plot of the posterior needs, counted on the device from the history it holds (`SMMHip.hip_histogram`), without
+`sync_chains!`: per parameter `hist[:, k, g]` over `edges[:, k, g]` and, for each pair `(j, k)` of 1-based parameter indexes,
+`hist2[:, :, p, g]` over `edges2`.  `groups[chain]` holds 0-based group ids (-1 = none); by default the chains with equal `acc_tuners`
+entries, as `pooled_summary`; `0:N-1` gives one histogram per chain.  Bins follow numpy's rule: equal widths from the group's min to
+its max (or the given `range`, an `np x 2` matrix), the last bin closed; this is not `StatsBase.fit(Histogram)`, whose bins are
+right-open and whose edges are rounded to nice numbers.  `status[k, g]` != 0 where numpy would raise (a non-finite draw with an
+autodetected range, too many bins for the range).  Not a method of `SMM`: the reference plots `params(c)` through its recipe.
+"""
+function chain_histogram(algo::MAlgoBGPHip; window = nothing, select::Symbol = :accepted, groups = nothing, bins::Integer = 10,
+                         range = nothing, pairs = Tuple{Int,Int}[], bins2::Integer = bins)
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    t0, t1 = window === nothing ? (0, SMMHip.hip_iter(hip)) : window
+    if groups === nothing
+        ids = Dict{Float64,Int32}()
+        opts = getfield(algo, :opts)
+        groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
+    end
+    return SMMHip.hip_histogram(hip, t0, t1; select = select, groups = groups, bins = bins, range = range, pairs = pairs, bins2 = bins2)
 end
 
 """

@@ -115,6 +115,13 @@ class smm_group_stats_t(C.Structure):
     ]
 
 
+class smm_histogram_t(C.Structure):
+    _fields_ = [
+        ("count", C.POINTER(C.c_int64)), ("status", c_int32_p), ("lo", c_double_p), ("hi", c_double_p), ("edges", c_double_p),
+        ("hist", C.POINTER(C.c_int64)), ("edges2", c_double_p), ("hist2", C.POINTER(C.c_int64)),
+    ]
+
+
 class smm_timing_t(C.Structure):
     _fields_ = [
         ("step_ms", C.c_double), ("iter_kernel_ms", C.c_double), ("exch_kernel_ms", C.c_double),
@@ -161,6 +168,8 @@ SYMBOLS = [
                                      C.POINTER(smm_chain_diag_t)]),
     ("smm_get_group_stats", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_double_p, C.c_int32,
                                       C.POINTER(smm_group_stats_t)]),
+    ("smm_get_histogram", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32, c_double_p, c_int32_p,
+                                     C.c_int32, C.c_int32, C.POINTER(smm_histogram_t)]),
     ("smm_get_chain_cov", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
     ("smm_get_proposal", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_proposal", C.c_int, [C.c_void_p, c_double_p]),

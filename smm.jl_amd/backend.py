@@ -1,5 +1,6 @@
 """Thin object wrapper over the C ABI of include/smmhip.h (libsmmhip.so).
 There is deliberately no CPU code path in here."""
+import builtins as _builtins
 import ctypes as C
 
 import numpy as np
@@ -316,6 +317,43 @@ class BGPContext:
         self._check(self._fn("get_group_stats")(self._ctx, int(t0), int(t1), int(bool(accepted_only)),
                                                 g.ctypes.data_as(A.c_int32_p) if g is not None else None, ng,
                                                 A.dptr(p) if len(p) else None, len(p), C.byref(s)))
+        return r
+
+    _SELECT = {"all": 0, "accepted": 1, "state": 2}
+
+    def histogram(self, t0=0, t1=None, select="accepted", groups=None, bins=10, range=None, pairs=(), bins2=None, n_groups=None):
+        """histograms of the draws of groups of local chains over iterations [t0, t1), counted on the device (smm_get_histogram,
+        include/smmhip.h): a dict of numpy arrays count [n_groups], status / lo / hi [n_groups][np], edges [n_groups][np][bins + 1],
+        hist [n_groups][np][bins] and, with pairs, edges2 [n_groups][np][bins2 + 1], hist2 [n_groups][len(pairs)][bins2][bins2].
+        select: "all", "accepted" (params(c, accepted_only)) or "state" (the chain's state series); groups: an int per chain (-1 = none),
+        n_groups by default groups.max() + 1, None: every local chain in one group; range: [np][2] or a dict parameter index -> (lo, hi)
+        naming every parameter, None: each group's own min and max; pairs: (j, k) parameter indexes; bins2 defaults to bins"""
+        t1 = self.state().iter if t1 is None else t1
+        N, np_ = self.N, self.np
+        sel = self._SELECT[select] if isinstance(select, str) else int(select)
+        g = None if groups is None else np.ascontiguousarray(groups, np.int32)
+        if g is not None and g.shape != (N,):
+            raise ValueError("histogram: groups needs one entry per chain, got shape %s" % (g.shape,))
+        ng = (1 if g is None else (int(g.max()) + 1 if len(g) else 0)) if n_groups is None else int(n_groups)
+        if isinstance(range, dict):
+            if sorted(range) != list(_builtins.range(np_)):
+                raise ValueError("histogram: a range dict names every parameter index 0 .. np-1")
+            range = [range[k] for k in _builtins.range(np_)]
+        rg = None if range is None else np.ascontiguousarray(range, np.float64).reshape(np_, 2)
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        b, b2 = int(bins), int(bins if bins2 is None else bins2)
+        npr = len(pr)
+        r = dict(count=np.empty(ng, np.int64), status=np.empty((ng, np_), np.int32), lo=np.empty((ng, np_)), hi=np.empty((ng, np_)),
+                 edges=np.empty((ng, np_, max(b, 0) + 1)), hist=np.empty((ng, np_, max(b, 0)), np.int64))
+        if npr:
+            r.update(edges2=np.empty((ng, np_, max(b2, 0) + 1)), hist2=np.empty((ng, npr, max(b2, 0), max(b2, 0)), np.int64))
+        s = A.smm_histogram_t()
+        for f, t in A.smm_histogram_t._fields_:
+            if f in r:
+                setattr(s, f, r[f].ctypes.data_as(t))
+        self._check(self._fn("get_histogram")(self._ctx, int(t0), int(t1), sel, g.ctypes.data_as(A.c_int32_p) if g is not None else None,
+                                              ng, b, A.dptr(rg) if rg is not None else None,
+                                              pr.ctypes.data_as(A.c_int32_p) if npr else None, npr, b2, C.byref(s)))
         return r
 
     def _proposal_shape(self):

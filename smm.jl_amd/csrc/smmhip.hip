@@ -70,6 +70,7 @@ using namespace smm;
 #include "smm_cov.hpp"
 #include "smm_diag.hpp"
 #include "smm_group.hpp"
+#include "smm_hist.hpp"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -396,6 +397,7 @@ struct Hooks {
     size_t stats_scratch = 0;      // the reducers' scratch cap instead of STATS_SCRATCH_CAP (0: that cap): batches of chains and parameters at small sizes
     int stats_mode_bins = STATS_MODE_BINS;   // partner ids per pass of k_stats_mode (1 .. STATS_MODE_BINS): several passes at small populations
     long long group_wide_min = STATS_LDS_N + 1;   // pooled columns of at least so many draws take the grid-wide select (1 .. STATS_LDS_N + 1)
+    int hist_lds_bins = 1 << 30;   // bins (1-D) and bins2 (2-D) above this count into global memory, not LDS (1 ..)
 };
 Hooks read_hooks() {
     Hooks H;
@@ -430,6 +432,7 @@ Hooks read_hooks() {
     if (const char* v = SMM_HOOK("SMMHIP_STATS_SCRATCH")) H.stats_scratch = (size_t)strtoull(v, nullptr, 10);
     if (const char* v = SMM_HOOK("SMMHIP_STATS_MODE_BINS")) H.stats_mode_bins = std::min(STATS_MODE_BINS, std::max(1, atoi(v)));
     if (const char* v = SMM_HOOK("SMMHIP_GROUP_WIDE_MIN")) H.group_wide_min = std::min((long long)STATS_LDS_N + 1, std::max(1ll, atoll(v)));
+    if (const char* v = SMM_HOOK("SMMHIP_HIST_LDS_BINS")) H.hist_lds_bins = std::max(1, atoi(v));
     return H;
 }
 // Which stand-alone kernel resolves exchangeMoves! (AlgoBGP.jl:647-716) — ONE decision, taken once per context (select_forms),
@@ -2460,13 +2463,16 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
             if (tile_smem(c, is_sim(c->obj) ? F.ct : (c->obj == SMM_OBJ_DENSE ? 16 : 8)) > (size_t)lim)
                 throw std::string("tile does not fit the 160 KiB LDS");
         }
-        // the history reducers' dynamic LDS: a chunk of draws (k_stats_column, k_cov_center, k_diag_acov, k_group_*), the partner ids of a pass (k_stats_mode)
+        // the history reducers' dynamic LDS: a chunk of draws (k_stats_column, k_cov_center, k_diag_acov, k_group_*), the partner ids of a pass
+        // (k_stats_mode), the counters and edges of a batch of parameters or pairs (k_hist_count, k_hist_pairs)
         HIPCHK(hipFuncSetAttribute((const void*)k_stats_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
         HIPCHK(hipFuncSetAttribute((const void*)k_cov_center, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
         HIPCHK(hipFuncSetAttribute((const void*)k_diag_acov, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
         HIPCHK(hipFuncSetAttribute((const void*)k_stats_mode, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_MODE_BINS * 4));
         HIPCHK(hipFuncSetAttribute((const void*)k_group_chunk_sum, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
         HIPCHK(hipFuncSetAttribute((const void*)k_group_small, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+        HIPCHK(hipFuncSetAttribute((const void*)k_hist_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIST_LDS_BYTES));
+        HIPCHK(hipFuncSetAttribute((const void*)k_hist_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIST_LDS_BYTES));
         HIPCHK(hipDeviceSynchronize());
     } catch (const std::string& m) {
         g_create_err = m;
@@ -3578,6 +3584,135 @@ int smm_get_group_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only
         }
         if (out->count) std::copy(gm.begin(), gm.end(), out->count);
         if (out->n_chains) std::copy(nch.begin(), nch.end(), out->n_chains);
+    } catch (const std::string& m) {
+        return fail(c, SMM_ERR_HIP, m);
+    }
+    return SMM_OK;
+}
+
+// --- histograms of groups of chains (smm_hist.hpp) ---------------------------------------------------------------------------------------
+
+constexpr size_t HIST_BATCH_CAP = (size_t)256 << 20;   // bytes of a batch of groups' tables (the test seam SMMHIP_STATS_SCRATCH replaces it)
+
+int smm_get_histogram(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups, int32_t bins,
+                      const double* range, const int32_t* pairs, int32_t n_pairs, int32_t bins2, smm_histogram_t* out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !out) return SMM_ERR_INVALID_ARG;
+    const size_t N = c->P.N, np = c->P.np;
+    if (select < 0 || select > 2) return fail(c, SMM_ERR_INVALID_ARG, "select must be 0 (all), 1 (accepted) or 2 (state)");
+    if (n_groups < 0 || (!group && n_groups != 1)) return fail(c, SMM_ERR_INVALID_ARG, "n_groups < 0, or group NULL with n_groups != 1");
+    if (group)
+        for (size_t i = 0; i < N; ++i)
+            if (group[i] < -1 || group[i] >= n_groups) return fail(c, SMM_ERR_INVALID_ARG, "a group id outside [-1, n_groups)");
+    if (bins < 1 || bins > 65536) return fail(c, SMM_ERR_INVALID_ARG, "bins must lie in [1, 65536]");
+    if (range)
+        for (size_t k = 0; k < np; ++k)
+            if (!(std::isfinite(range[2 * k]) && std::isfinite(range[2 * k + 1]) && range[2 * k] <= range[2 * k + 1]))
+                return fail(c, SMM_ERR_INVALID_ARG, "a range row must be finite with lo <= hi");
+    if (n_pairs < 0 || (size_t)n_pairs > np * np || (n_pairs > 0 && !pairs))
+        return fail(c, SMM_ERR_INVALID_ARG, "n_pairs outside [0, np np], or pairs NULL with n_pairs > 0");
+    for (int p = 0; p < 2 * n_pairs; ++p)
+        if (pairs[p] < 0 || (size_t)pairs[p] >= np) return fail(c, SMM_ERR_INVALID_ARG, "a pair entry outside [0, np)");
+    if (n_pairs > 0 && (bins2 < 1 || bins2 > 512)) return fail(c, SMM_ERR_INVALID_ARG, "bins2 must lie in [1, 512]");
+    if (n_pairs == 0 && (out->hist2 || out->edges2)) return fail(c, SMM_ERR_INVALID_ARG, "hist2 or edges2 requested without pairs");
+    try {
+        reader_prelude(c);
+        if (const int rc = check_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t G = n_groups, B = bins, B2 = n_pairs > 0 ? bins2 : 0, NP = n_pairs;
+        const int n = t1 - t0;
+        const bool two = NP > 0 && (out->hist2 || out->edges2);
+        // the members of every group, group by group in ascending local index (gmem0: the CSR offsets)
+        std::vector<int> gid(N, 0), gmem0(G + 1, 0), mem;
+        if (group) std::copy(group, group + N, gid.begin());
+        for (size_t i = 0; i < N; ++i)
+            if (gid[i] >= 0) ++gmem0[gid[i] + 1];
+        for (size_t g = 0; g < G; ++g) gmem0[g + 1] += gmem0[g];
+        mem.resize(gmem0[G]);
+        {
+            std::vector<int> at(gmem0.begin(), gmem0.end() - 1);
+            for (size_t i = 0; i < N; ++i)
+                if (gid[i] >= 0) mem[at[gid[i]]++] = (int)i;
+        }
+        const int M = gmem0[G];
+        const bool autor = range == nullptr, cnt_pass = autor || (out->count && select == 1);
+        // a batch of groups: the edges (always: the counting reads them), the counts asked for, the 2-D axes and cells
+        const size_t per_group = np * (B + 1) * 8 + (out->hist ? np * B * 8 : 0) + (two ? np * (B2 + 1) * 8 : 0) +
+                                 (two && out->hist2 ? NP * B2 * B2 * 8 : 0);
+        const size_t cap = c->H.stats_scratch ? c->H.stats_scratch : HIST_BATCH_CAP;
+        const size_t gb = G ? std::max((size_t)1, std::min(G, cap / per_group)) : 0;
+        Carve Rv;   // 8-byte slices first
+        const auto cmin = Rv.take<double>(autor ? N * np : 0), cmax = Rv.take<double>(autor ? N * np : 0), drng = Rv.take<double>(autor ? 0 : 2 * np),
+                   dlo = Rv.take<double>(G * np), dhi = Rv.take<double>(G * np), edges = Rv.take<double>(gb * np * (B + 1)),
+                   edges2 = Rv.take<double>(two ? gb * np * (B2 + 1) : 0);
+        const auto hist = Rv.take<unsigned long long>(out->hist ? gb * np * B : 0),
+                   hist2 = Rv.take<unsigned long long>(two && out->hist2 ? gb * NP * B2 * B2 : 0);
+        const auto cbad = Rv.take<int>(autor ? N * np : 0), dcnt = Rv.take<int>(N), dst = Rv.take<int>(G * np), dgid = Rv.take<int>(N),
+                   dgm0 = Rv.take<int>(G + 1), dmem = Rv.take<int>(mem.size()), dpairs = Rv.take<int>(2 * NP);
+        void* d = reducer_result(c, Rv.bytes);
+        auto up = [&](auto sl, const auto* v, size_t count) {
+            if (count) HIPCHK(hipMemcpyAsync(sl.in(d), v, count * sizeof(v[0]), hipMemcpyHostToDevice, c->stream));
+        };
+        up(dgid, gid.data(), N); up(dgm0, gmem0.data(), G + 1); up(dmem, mem.data(), mem.size()); up(dpairs, pairs, 2 * NP);
+        if (!autor) up(drng, range, 2 * np);
+        if (cnt_pass && M > 0)
+            launch_checked(c, k_hist_range, dim3(M, autor ? (unsigned)((np + HIST_KMAX - 1) / HIST_KMAX) : 1), dim3(HIST_WG), 0,
+                           (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, (const int*)dmem.in(d), 0, (int)np, dcnt.in(d),
+                           autor ? cmin.in(d) : (double*)nullptr, cmax.in(d), cbad.in(d));
+        const int lb = c->H.hist_lds_bins;
+        const bool lds1 = (int)B <= lb && 12 * B + 8 <= HIST_LDS_BYTES, lds2 = two && (int)B2 <= lb && 16 * (B2 + 1) + 4 * B2 * B2 <= HIST_LDS_BYTES;
+        const int kb = lds1 ? (int)std::min({np, (size_t)HIST_KMAX, HIST_LDS_BYTES / (12 * B + 8)}) : (int)std::min(np, (size_t)HIST_KMAX);
+        const int kp = !two ? 0 : lds2 ? (int)std::min({NP, (size_t)HIST_KMAX, HIST_LDS_BYTES / (16 * (B2 + 1) + 4 * B2 * B2)})
+                                       : (int)std::min(NP, (size_t)HIST_KMAX);
+        for (size_t g0 = 0; g0 < G; g0 += gb) {
+            const size_t gn = std::min(gb, G - g0);
+            const int m0 = gmem0[g0], mb = gmem0[g0 + gn] - m0;
+            launch_checked(c, k_hist_edges, dim3((unsigned)gn, (unsigned)np), dim3(HIST_WG), 0, (const int*)dgm0.in(d), (const int*)dmem.in(d),
+                           (int)g0, (int)np, (const int*)dcnt.in(d), (const double*)cmin.in(d), (const double*)cmax.in(d),
+                           (const int*)cbad.in(d), autor ? (const double*)nullptr : (const double*)drng.in(d), (int)B, (int)B2, dlo.in(d),
+                           dhi.in(d), dst.in(d), edges.in(d), two ? edges2.in(d) : (double*)nullptr);
+            if (out->hist) {
+                HIPCHK(hipMemsetAsync(hist.in(d), 0, gn * np * B * 8, c->stream));
+                if (mb > 0)
+                    launch_checked(c, k_hist_count, dim3(mb, (unsigned)((np + kb - 1) / kb)), dim3(HIST_WG),
+                                   lds1 ? (size_t)kb * (12 * B + 8) : 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select,
+                                   (const int*)dmem.in(d), (const int*)dgid.in(d), (const int*)dgm0.in(d), m0, (int)g0, (int)np, kb, (int)B,
+                                   (int)lds1, (const double*)dlo.in(d), (const double*)dhi.in(d), (const int*)dst.in(d),
+                                   (const double*)edges.in(d), hist.in(d));
+            }
+            if (two && out->hist2) {
+                HIPCHK(hipMemsetAsync(hist2.in(d), 0, gn * NP * B2 * B2 * 8, c->stream));
+                if (mb > 0)
+                    launch_checked(c, k_hist_pairs, dim3(mb, (unsigned)((NP + kp - 1) / kp)), dim3(HIST_WG),
+                                   lds2 ? (size_t)kp * (16 * (B2 + 1) + 4 * B2 * B2) : 0, (const double*)P.hrec, (int)N, P.HW, t0, n,
+                                   (int)select, (const int*)dmem.in(d), (const int*)dgid.in(d), (const int*)dgm0.in(d), m0, (int)g0, (int)np,
+                                   (const int*)dpairs.in(d), (int)NP, kp, (int)B2, (int)lds2, (const int*)dst.in(d),
+                                   (const double*)edges2.in(d), hist2.in(d));
+            }
+            auto down = [&](auto sl, void* dst, size_t bytes) {
+                if (dst && bytes) HIPCHK(hipMemcpyAsync(dst, sl.in(d), bytes, hipMemcpyDeviceToHost, c->stream));
+            };
+            down(edges, out->edges ? out->edges + g0 * np * (B + 1) : nullptr, gn * np * (B + 1) * 8);
+            down(hist, out->hist ? out->hist + g0 * np * B : nullptr, gn * np * B * 8);
+            if (two) {
+                down(edges2, out->edges2 ? out->edges2 + g0 * np * (B2 + 1) : nullptr, gn * np * (B2 + 1) * 8);
+                down(hist2, out->hist2 ? out->hist2 + g0 * NP * B2 * B2 : nullptr, gn * NP * B2 * B2 * 8);
+            }
+            HIPCHK(hipStreamSynchronize(c->stream));   // (the next batch reuses the tables)
+        }
+        std::vector<int> cnt(N, n);
+        if (out->count && select == 1 && M > 0) HIPCHK(hipMemcpyAsync(cnt.data(), dcnt.in(d), N * 4, hipMemcpyDeviceToHost, c->stream));
+        if (G > 0) {
+            if (out->lo) HIPCHK(hipMemcpyAsync(out->lo, dlo.in(d), G * np * 8, hipMemcpyDeviceToHost, c->stream));
+            if (out->hi) HIPCHK(hipMemcpyAsync(out->hi, dhi.in(d), G * np * 8, hipMemcpyDeviceToHost, c->stream));
+            if (out->status) HIPCHK(hipMemcpyAsync(out->status, dst.in(d), G * np * 4, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (out->count) {
+            std::fill(out->count, out->count + G, (int64_t)0);
+            for (size_t i = 0; i < N; ++i)
+                if (gid[i] >= 0) out->count[gid[i]] += cnt[i];
+        }
     } catch (const std::string& m) {
         return fail(c, SMM_ERR_HIP, m);
     }

@@ -13,6 +13,7 @@ same C ABI with `ccall`.  Everything numerical happens in libsm
   computeNextIteration, run, restart, history, summary, ...         AlgoBGP.jl:589-640, AlgoAbstract.jl:27-76
 """
 import time as _time
+from builtins import range as _builtins_range
 from collections import OrderedDict
 
 import numpy as np
@@ -459,6 +460,97 @@ def pooled(algo, groups=None, window=None, accepted_only=True, level=0.95):
                         CI=OrderedDict((k, r["quantile"][:, j, i].copy()) for i, k in enumerate(names)),
                         cov=r["cov"][j].copy())
             for j in range(r["count"].shape[0])]
+
+
+def _hist_call(x, window, accepted_only, state, **kw):
+    """(algo, chain index or None, the device's histogram dict) of a chain (alone in group 0) or of the groups of an algo"""
+    if isinstance(x, BGPChain):
+        algo, j = x._algo, x._j
+        g = np.full(algo._ctx.N, -1, np.int32)
+        g[j] = 0
+        kw["n_groups"] = 1
+    else:
+        algo, j = x, None
+        g = np.asarray(_default_groups(algo) if kw.get("groups") is None else kw["groups"], np.int32)
+    kw.pop("groups", None)
+    t0, t1 = (0, algo.i) if window is None else (int(window[0]), int(window[1]))
+    sel = "state" if state else "accepted" if accepted_only else "all"
+    return algo, j, algo._ctx.histogram(t0, t1, sel, g, **kw)
+
+
+def _hist_range(rng, names):
+    """numpy's checks of a given range, then the rows [np][2] of the call (by name or in parameter order)"""
+    if rng is None:
+        return None
+    rows = [rng[k] for k in names] if isinstance(rng, dict) else list(rng)
+    for lo, hi in rows:
+        if lo > hi:
+            raise ValueError("max must be larger than min in range parameter.")
+        if not (np.isfinite(lo) and np.isfinite(hi)):
+            raise ValueError("supplied range of [{}, {}] is not finite".format(lo, hi))
+    return np.asarray(rows, np.float64).reshape(len(names), 2)
+
+
+def _hist_raise(st, lo, hi, bins, one_d=True):
+    """the ValueError numpy raises where the device reports a status (include/smmhip.h: smm_get_histogram)"""
+    if st == 1:
+        raise ValueError("autodetected range of [{}, {}] is not finite".format(lo, hi))
+    if st == 2:
+        raise ValueError("range of [{}, {}] has a width that is not finite".format(lo, hi))
+    if st == 3 and one_d:
+        raise ValueError("Too many bins for data range. Cannot create {} finite-sized bins.".format(bins))
+
+
+def histogram(x, bins=10, range=None, window=None, accepted_only=True, state=False, density=False, groups=None):
+    """np.histogram(params(c, accepted_only)[name], bins, range, density) of every parameter, counted on the device (include/smmhip.h:
+    smm_get_histogram) without downloading the history: an OrderedDict name -> (counts, edges) for a chain, a list of them (one per
+    group) for an algo, whose groups default to those of rhat / pooled.  window = (t0, t1) (default: the whole run); state: the chain's
+    state series (each iteration weighted by holding time) instead of its accepted draws; range: [np][2] or name -> (lo, hi).  Where
+    numpy raises (a non-finite autodetected range, a bad range, too many bins for the range), so does this"""
+    if int(bins) < 1:
+        raise ValueError("`bins` must be positive, when an integer")
+    names = ps2s_names(x.m)
+    _, j, r = _hist_call(x, window, accepted_only, state, groups=groups, bins=int(bins), range=_hist_range(range, names))
+    out = []
+    for g in _builtins_range(r["count"].shape[0]):
+        d = OrderedDict()
+        for i, k in enumerate(names):
+            _hist_raise(r["status"][g, i], r["lo"][g, i], r["hi"][g, i], bins)
+            n, e = r["hist"][g, i].copy(), r["edges"][g, i].copy()
+            if density:
+                db = np.diff(e)
+                n = n / db / n.sum()
+            d[k] = (n, e)
+        out.append(d)
+    return out[0] if j is not None else out
+
+
+def histogram2d(x, pair, bins=10, range=None, window=None, accepted_only=True, state=False, density=False, groups=None):
+    """np.histogram2d(params(c)[a], params(c)[b], bins, range, density) for pair = (a, b), parameter names, counted on the device:
+    (H, xedges, yedges) for a chain, a list of them (one per group) for an algo.  range: numpy's [[xmin, xmax], [ymin, ymax]] or None"""
+    if int(bins) < 1:
+        raise ValueError("`bins` must be positive, when an integer")
+    names = ps2s_names(x.m)
+    a, b = names.index(pair[0]), names.index(pair[1])
+    rg = None
+    if range is not None:
+        ax = _hist_range(list(range), [0, 1])
+        rg = np.tile([0.0, 1.0], (len(names), 1))
+        rg[a], rg[b] = ax[0], ax[1]
+    _, j, r = _hist_call(x, window, accepted_only, state, groups=groups, bins=1, range=rg, pairs=[(a, b)], bins2=int(bins))
+    out = []
+    for g in _builtins_range(r["count"].shape[0]):
+        for i in (a, b):
+            _hist_raise(r["status"][g, i], r["lo"][g, i], r["hi"][g, i], bins, one_d=False)
+        H = r["hist2"][g, 0].astype(float)
+        xe, ye = r["edges2"][g, a].copy(), r["edges2"][g, b].copy()
+        if density:
+            s = H.sum()
+            H = H / np.diff(xe).reshape(-1, 1)
+            H = H / np.diff(ye).reshape(1, -1)
+            H /= s
+        out.append((H, xe, ye))
+    return out[0] if j is not None else out
 
 
 def summary(x):
