@@ -25,8 +25,9 @@ _ORC_ONLY = [
     ("orc_gen_dense2", None, [C.c_uint64, C.c_int, C.c_int, A.c_double_p]),
     ("orc_tanh", None, [A.c_double_p, A.c_double_p, C.c_int]),
     ("orc_math", None, [C.c_int, A.c_double_p, A.c_double_p, C.c_int]),
-    ("orc_set_user_objective", None, [C.c_int, C.c_void_p]),
-    ("orc_set_user_objective_lanes", None, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    ("orc_set_user_objective", C.c_int, [C.c_int, C.c_void_p]),
+    ("orc_set_user_objective_lanes", C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    ("orc_max_user", C.c_int, []),
 ]
 _SHARED = ["smm_ctx_create", "smm_ctx_destroy", "smm_last_error", "smm_bgp_step", "smm_bgp_local_step",
            "smm_bgp_record_doubles", "smm_eval_batch", "smm_eval_batch_noseed", "smm_get_history", "smm_get_state", "smm_set_state", "smm_get_Z"]
@@ -141,6 +142,7 @@ def register_user_objective(source, objective_id, workdir=None, n_sums=None, lan
     map-reduce pair SMM_USER_PARTIAL / SMM_USER_FINISH) for the host with gcc (-ffp-contract=off like the device
     build) and hook it into the oracle under the device's handle."""
     import tempfile
+    check_user_id(objective_id)
     d = workdir or tempfile.mkdtemp(prefix="smm_user_obj_")
     src = os.path.join(d, "user_objective_%d.c" % objective_id)
     so = os.path.join(d, "user_objective_%d.so" % objective_id)
@@ -151,9 +153,22 @@ def register_user_objective(source, objective_id, workdir=None, n_sums=None, lan
     subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src, "-lm"])
     lib = C.CDLL(so)
     _user_libs.append(lib)
-    if n_sums is None:
-        load().orc_set_user_objective(int(objective_id), C.cast(lib.smm_user_objective, C.c_void_p))
-    else:
-        load().orc_set_user_objective_lanes(int(objective_id), C.cast(lib.smm_user_partial, C.c_void_p),
-                                            C.cast(lib.smm_user_finish, C.c_void_p), int(n_sums), int(lanes))
+    hook_user_objective(lib, objective_id, n_sums, lanes)
     return so
+
+
+def hook_user_objective(lib, objective_id, n_sums=None, lanes=256):
+    """(again) evaluate objective_id through `lib`, a host build of register_user_objective"""
+    if n_sums is None:
+        rc = load().orc_set_user_objective(int(objective_id), C.cast(lib.smm_user_objective, C.c_void_p))
+    else:
+        rc = load().orc_set_user_objective_lanes(int(objective_id), C.cast(lib.smm_user_partial, C.c_void_p),
+                                                 C.cast(lib.smm_user_finish, C.c_void_p), int(n_sums), int(lanes))
+    check_user_id(objective_id, rc)
+
+
+def check_user_id(objective_id, rc=0):
+    """the oracle holds user objectives 1000 .. 1000 + orc_max_user() - 1: a handle past them would evaluate as status -2 (raise instead)"""
+    n = load().orc_max_user()
+    if rc != 0 or not 1000 <= int(objective_id) < 1000 + n:
+        raise ValueError("user objective %d lies outside the oracle's table (handles 1000 .. %d)" % (int(objective_id), 999 + n))

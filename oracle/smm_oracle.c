@@ -629,17 +629,25 @@ static void evaluate_objective(const orc_t* o, const double* theta, double* simM
     }
 }
 
-void orc_set_user_objective_lanes(int objective_id, orc_user_partial_fn pf, orc_user_finish_fn ff, int n_sums, int lanes) {
-    if (objective_id >= ORC_OBJ_USER_BASE && objective_id - ORC_OBJ_USER_BASE < ORC_MAX_USER) {
-        const int u = objective_id - ORC_OBJ_USER_BASE;
-        g_user_partial[u] = pf; g_user_finish[u] = ff; g_user_nsums[u] = n_sums; g_user_lanes[u] = lanes;
-    }
+/* 0, or -1 where the handle lies outside the table (nothing is registered: its evaluations would read as status -2).  A handle
+ * registered again takes the new form only (the map-reduce form would otherwise shadow a later one-thread form) */
+int orc_set_user_objective_lanes(int objective_id, orc_user_partial_fn pf, orc_user_finish_fn ff, int n_sums, int lanes) {
+    if (!(objective_id >= ORC_OBJ_USER_BASE && objective_id - ORC_OBJ_USER_BASE < ORC_MAX_USER)) return -1;
+    const int u = objective_id - ORC_OBJ_USER_BASE;
+    g_user_partial[u] = pf; g_user_finish[u] = ff; g_user_nsums[u] = n_sums; g_user_lanes[u] = lanes;
+    g_user_fn[u] = NULL;
+    return 0;
 }
 
-void orc_set_user_objective(int objective_id, orc_user_fn fn) {
-    if (objective_id >= ORC_OBJ_USER_BASE && objective_id - ORC_OBJ_USER_BASE < ORC_MAX_USER)
-        g_user_fn[objective_id - ORC_OBJ_USER_BASE] = fn;
+int orc_set_user_objective(int objective_id, orc_user_fn fn) {
+    if (!(objective_id >= ORC_OBJ_USER_BASE && objective_id - ORC_OBJ_USER_BASE < ORC_MAX_USER)) return -1;
+    const int u = objective_id - ORC_OBJ_USER_BASE;
+    g_user_fn[u] = fn;
+    g_user_partial[u] = NULL; g_user_finish[u] = NULL;
+    return 0;
 }
+
+int orc_max_user(void) { return ORC_MAX_USER; }
 
 static double* dupd(const double* s, size_t n) {
     double* d = (double*)malloc((n ? n : 1) * sizeof(double));

@@ -651,6 +651,9 @@ size_t tile_smem_base(const Ctx* c, int ct) {
     const KParams& P = c->P;
     return tile_smem_doubles(ct, P.np, P.nm, P.RW, P.HW, P.RBW, lay_kind(c)) * sizeof(double);
 }
+// tile width (chains per workgroup) of k_chain_iter<0, CT> in a user objective's three launches per iteration: 64 where that tile's LDS
+// fits in 60 KB, else 8 (launch_chain_iter takes it, smm_describe reports it)
+int user_iter_ct(const Ctx* c) { return tile_smem_base(c, 64) <= (size_t)60 * 1024 ? 64 : 8; }
 int lay_kind(const Ctx* c) { const int k = obj_kind(c->obj); return k == 2 && c->P.dense_A2f ? 3 : (c->obj == SMM_OBJ_USER && c->u_lanes > 0) ? 4 : k; }
 // dynamic LDS of k_chain_persist_tile for this context (a user objective's wave totals: 16 chains x lanes / 64 groups x its sums)
 size_t persist_tile_smem(const Ctx* c) {
@@ -887,7 +890,7 @@ void launch_chain_iter(Ctx* c, int t, int flags) {
         // proposal launch (stores nothing but the proposals) -> the user's kernel -> accept launch (repeats the
         // deterministic prologue, takes value / moments / status from the user's kernel)
         const KParams& P = c->P;
-        const bool big = tile_smem_base(c, 64) <= (size_t)60 * 1024;
+        const bool big = user_iter_ct(c) == 64;
         if (big) launch_chain_iter_ct<0, 64>(c, t, flags | F_PROPOSE_ONLY); else launch_chain_iter_ct<0, 8>(c, t, flags | F_PROPOSE_ONLY);
         launch_user_kernel(c, P.u_theta, P.N, P.u_simM, P.u_value, P.u_status);
         if (big) launch_chain_iter_ct<0, 64>(c, t, flags); else launch_chain_iter_ct<0, 8>(c, t, flags);
@@ -3872,8 +3875,9 @@ int smm_describe(void* ctx, char* out, int32_t cap) {
                      : c->F.persist == PERSIST_TILE ? (c->F.persist_sh ? (c->pfn ? "tile_user_shard" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2_shard" : "tile_dense_shard") : "tile_sim_shard")
                                                                         : (c->pfn ? "tile_user" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2" : "tile_dense") : "tile_sim"))
                      : c->F.persist_user ? "gen_user" : "gen";
-    snprintf(out, (size_t)cap, "chain=%s walk=%s exchange=%s persistent=%s plan=%s window=%d", chain, walk, xk[c->F.xk], pers,
-             c->F.plan == PLAN_BIG ? (c->F.plan_ahead ? "big_ahead" : "big") : c->F.plan == PLAN_LDS ? "lds" : "none", c->F.plan_cap);
+    const int n = snprintf(out, (size_t)cap, "chain=%s walk=%s exchange=%s persistent=%s plan=%s window=%d", chain, walk, xk[c->F.xk], pers,
+                           c->F.plan == PLAN_BIG ? (c->F.plan_ahead ? "big_ahead" : "big") : c->F.plan == PLAN_LDS ? "lds" : "none", c->F.plan_cap);
+    if (c->obj == SMM_OBJ_USER && n >= 0 && n < cap) snprintf(out + n, (size_t)(cap - n), " ct=%d", user_iter_ct(c));   // (the three launches' tile width)
     return SMM_OK;
 }
 

@@ -75,14 +75,23 @@ def test_forms_of_shards(S, row):
     assert (d["persistent"], d["plan"]) == (pers, plan), (what, d)
 
 
-def test_form_of_a_user_objective(S):
+def test_form_of_a_user_objective(S, O):
     from test_user_objective import ar1_problem, AR1_SOURCE, PANEL_SOURCE, panel_problem
     oid = S.register_user_objective(AR1_SOURCE)
     d = S.hip_context(*ar1_problem(S, oid, N=256, T=8)).describe()
     assert (d["chain"], d["persistent"]) == ("user_3launches", "gen_user"), d
+    assert d["ct"] == "64", d   # the three launches' k_chain_iter<0, CT>: 2 parameters and 3 moments fit the 64-chain tile (40.1 KB of LDS)
     oid2 = S.register_user_objective(PANEL_SOURCE, n_sums=3, lanes=64)     # the map-reduce form: compiled into the persistent TILE kernel (round 6)
     d = S.hip_context(*panel_problem(S, oid2, N=64, T=8)).describe()
     assert (d["chain"], d["persistent"]) == ("user_lanes_3launches", "tile_user"), d
+    assert d["ct"] == "64", d   # (the layout of kind 4 adds a partial-sum block: 56.1 KB, still under 60)
     oid3 = S.register_user_objective(PANEL_SOURCE, n_sums=3, lanes=1024)   # more lanes than a tile has: its own launches
     d = S.hip_context(*panel_problem(S, oid3, N=64, T=8)).describe()
     assert d["persistent"] == "none", d
+    assert d["ct"] == "64", d
+    from test_gpu_user_shapes import ROWS, make   # five parameters and moments: the first one-thread shape past 60 KB, k_chain_iter<0, 8>
+    prob, opts, _ = make(S, O, next(r for r in ROWS if r[2:4] == (5, 5)))
+    d = S.hip_context(prob, opts).describe()
+    assert (d["chain"], d["persistent"], d["ct"]) == ("user_3launches", "gen_user", "8"), d
+    d = S.hip_context(*cm.serial_normal(N=64, T=8, ns=64)).describe()
+    assert "ct" not in d, d     # (reported for user objectives only)

@@ -202,10 +202,11 @@ class Shim:
         """the oracle evaluates objective_id through this build, its stream keyed by `seed`"""
         self.set_seed(seed)
         if self.n_sums is None:
-            O.load().orc_set_user_objective(int(objective_id), C.cast(self.lib.smm_user_objective, C.c_void_p))
+            rc = O.load().orc_set_user_objective(int(objective_id), C.cast(self.lib.smm_user_objective, C.c_void_p))
         else:
-            O.load().orc_set_user_objective_lanes(int(objective_id), C.cast(self.lib.smm_user_partial, C.c_void_p),
-                                                  C.cast(self.lib.smm_user_finish, C.c_void_p), int(self.n_sums), int(lanes))
+            rc = O.load().orc_set_user_objective_lanes(int(objective_id), C.cast(self.lib.smm_user_partial, C.c_void_p),
+                                                       C.cast(self.lib.smm_user_finish, C.c_void_p), int(self.n_sums), int(lanes))
+        O.check_user_id(objective_id, rc)
 
     def uniform(self, seed, i):
         return self.lib.smm_uniform(smm_rng_t(int(seed)), int(i))
