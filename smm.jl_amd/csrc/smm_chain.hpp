@@ -9,7 +9,8 @@
 // its first operand with the lower half of its second, v_permlane16_swap the odd rows of the first with the even rows of the
 // second.  Afterwards, in the lanes whose bit OFF is clear, x = own x and y = the partner lane's x; in the other lanes
 // x = the partner lane's y and y = own y: x + y is "mine + received" for the accumulator the lane keeps (3 instructions per
-// pair of 64-bit accumulators instead of 4 selects, 2 LDS permutes and the add).
+// pair of 64-bit accumulators instead of 4 selects, 2 LDS permutes and the add).  The offsets 8, 4, 2, 1 move by DPP inside
+// a row of 16 lanes (xor_lane below): the same partner lanes, the same additions, no LDS latency between two steps of the tree.
 template <int OFF>
 __device__ inline double swap_add(double x, double y) {
     static_assert(OFF == 32 || OFF == 16, "lane swaps exist for offsets 32 and 16");
@@ -28,6 +29,24 @@ __device__ inline double swap_add(double x, double y) {
     const double y2 = __builtin_bit_cast(double, ((unsigned long long)yh << 32) | yl);
     return x2 + y2;
 }
+// The value of lane (this lane ^ OFF) for the offsets inside a row of 16 lanes, by DPP (no LDS round trip, no ds_bpermute):
+// xor 8 = row_ror:8, xor 2 / xor 1 = quad_perm [2,3,0,1] / [1,0,3,2], xor 4 = quad_perm [3,2,1,0] (xor 3) then row_half_mirror (xor 7).
+template <int CTRL>
+__device__ inline unsigned dpp32(unsigned v) { return (unsigned)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, false); }
+template <int OFF>
+__device__ inline unsigned xor_lane32(unsigned v) {
+    static_assert(OFF == 8 || OFF == 4 || OFF == 2 || OFF == 1, "offsets inside a row");
+    if constexpr (OFF == 8) return dpp32<0x128>(v);
+    else if constexpr (OFF == 4) return dpp32<0x141>(dpp32<0x1b>(v));
+    else if constexpr (OFF == 2) return dpp32<0x4e>(v);
+    else return dpp32<0xb1>(v);
+}
+template <int OFF>
+__device__ inline double xor_lane(double v) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = xor_lane32<OFF>((unsigned)u), hi = xor_lane32<OFF>((unsigned)(u >> 32));
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
 template <int CT, int NN, int OFF>
 __device__ inline void wave_reduce_step(double (&a)[CT], int lane) {
     if constexpr (NN > 1) {
@@ -40,13 +59,16 @@ __device__ inline void wave_reduce_step(double (&a)[CT], int lane) {
             for (int i = 0; i < NN / 2; ++i) {
                 const double mine = upper ? a[i + NN / 2] : a[i];
                 const double send = upper ? a[i] : a[i + NN / 2];
-                const double recv = __shfl_xor(send, OFF, 64);
+                const double recv = xor_lane<OFF>(send);
                 a[i] = mine + recv;
             }
         }
         wave_reduce_step<CT, NN / 2, OFF / 2>(a, lane);
-    } else if constexpr (OFF >= 1) {
+    } else if constexpr (OFF >= 16) {
         a[0] = a[0] + __shfl_xor(a[0], OFF, 64);
+        wave_reduce_step<CT, 1, OFF / 2>(a, lane);
+    } else if constexpr (OFF >= 1) {
+        a[0] = a[0] + xor_lane<OFF>(a[0]);
         wave_reduce_step<CT, 1, OFF / 2>(a, lane);
     }
 }

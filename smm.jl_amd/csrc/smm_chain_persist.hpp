@@ -24,8 +24,10 @@
 //   * the next iteration's lists arrive by LDS-DMA under the simulation, its randomness is drawn by wave 1 behind its share of the
 //     simulation, and the gathering waves start looking for the other tiles' slots as soon as this tile has published;
 //   * the waves are ROLE-SPECIALISED (two loops in one kernel, the same number of workgroup barriers in each): wave 0 is the control
-//     wave (its shocks come out of LDS for its share of the simulation); history rows leave through LDS and are stored by a worker
-//     wave; what happens once per launch or almost never is out of line.
+//     wave (its shocks wait in LDS and come into registers behind its proposal, for the same straight-line share of the simulation
+//     as a worker's); every wave adds at a raised priority (s_setprio), so that the side jobs of the waves that are done with their
+//     share (the randomness, the tables, the lists) do not take the FP64 issue slots of those still adding; history rows leave
+//     through LDS and are stored by a worker wave; what happens once per launch or almost never is out of line.
 // Nobody waits for an acknowledgement, no grid barrier, no atomics on the way.  Why the ring cannot be overrun: a tile publishes
 // iteration i into entry i mod PR_K only after every tile has announced (progress word) that it has finished the prologue reads of
 // iteration i - PR_K + 1 — never failing in practice, holding under any skew (tests: a delayed workgroup, a ring of 2).  Deadlock
@@ -284,9 +286,10 @@ __device__ __forceinline__ void persist_add_draw(const double zu, const int u, c
         for (int c = 0; c < 8; ++c) { const double x = zu + mu[c]; acc[c] = acc[c] + x; }
     }
 }
+// (ts: the phase stamps are on — t_add is the wall clock when the last pass's adds are issued, ahead of its reduction)
 template <int NP, bool FULL>
 __device__ __forceinline__ void persist_simulate(const double (&z)[PR_ZR], const int nfull, const bool extra, const double* s_theta, double* s_part,
-                                                 const int h, const int wih) {
+                                                 const int h, const int wih, const bool ts, unsigned long long& t_add) {
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
         double acc[8], mu[8];
@@ -294,37 +297,12 @@ __device__ __forceinline__ void persist_simulate(const double (&z)[PR_ZR], const
         for (int c = 0; c < 8; ++c) { mu[c] = s_theta[(pass * 8 + c) * NP + h]; acc[c] = 0.0; }
 #pragma unroll
         for (int u = 0; u < PR_ZR; ++u) persist_add_draw<FULL>(z[u], u, nfull, extra, mu, acc);
+        if (pass == 1 && ts) t_add = wall_clock64();
         const int lane2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
         const double tot = wave_reduce_transposed<8>(acc, lane2);
         if ((lane2 & 7) == 0) s_part[(h * 8 + wih) * NORM_CT + pass * 8 + (lane2 >> 3)] = tot;
     }
 }
-// ... with the lane's shocks in LDS (the control wave, half 0, wave 0 of it: s_z0[u][64]), fetched half at a time: its registers belong
-// to the serial parts of the iteration
-template <int NP, bool FULL>
-__device__ __forceinline__ void persist_simulate_lds(const double* s_z0, const int ns, const int nfull, const double* s_theta, double* s_part) {
-    constexpr int HZ = PR_ZR / 2;
-    static_assert(PR_ZR % 2 == 0, "two halves");
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        const bool extra = lane < ns - nfull * WG;
-        double acc[8], mu[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) { mu[c] = s_theta[(pass * 8 + c) * NP]; acc[c] = 0.0; }
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            double z[HZ];
-#pragma unroll
-            for (int k = 0; k < HZ; ++k) z[k] = s_z0[(hh * HZ + k) * 64 + lane];
-#pragma unroll
-            for (int k = 0; k < HZ; ++k) persist_add_draw<FULL>(z[k], hh * HZ + k, nfull, extra, mu, acc);
-        }
-        const double tot = wave_reduce_transposed<8>(acc, lane);
-        if ((lane & 7) == 0) s_part[pass * 8 + (lane >> 3)] = tot;
-    }
-}
-
 // the workgroup barrier of role-specialised waves (every wave executes the same NUMBER of them per iteration, from different code).
 // Bare: the wave's LDS operations are complete (lgkmcnt), its GLOBAL ones stay in flight — a fence would wait for the write-through
 // publication, the LDS-DMA of the next lists and the history stores at every barrier, i.e. put their latency on the critical path.

@@ -31,11 +31,17 @@
 constexpr int PL_LOCN = NORM_CT + CONE_GCAP + 2;                          // local slots: own chains, gathered chains, the dummy pair's
 constexpr uint32_t PL_PBASE = ((16u * PL_LOCN + 127u) & ~127u);          // LDS offset of the pair lists (slots: 16 bytes reserved each, from address 0)
 constexpr int PL_HASH = 1024;                                             // slots of the re-numbering table (<= 512 entries)
+// SMMHIP_TS: the simulation phase wave by wave (tools/persist_waves.py) — 8 words per wave behind the tiles' 8 of the phase stamps, for the
+// first PL_TSW_TILES tiles: sums over the launch's iterations of the wall clock when the wave leaves BB [0], has issued its last add [1], has stored
+// its partials [2], and when the control wave's wait for them ends / a worker's side job of the iteration ends [3]; HW_ID [4]; iterations [5]
+constexpr size_t PL_TSW_BASE = (size_t)8 * 8192;
+constexpr int PL_TSW_TILES = 2048, PL_TSW = 8;
 
 __host__ __device__ inline size_t persist_loc_smem_bytes(const int np) {
     const size_t hw = (size_t)((H_PARAMS + 2 * np + 1) & ~1);
     const size_t dbl = (size_t)NORM_CT * np + (size_t)np * 8 * NORM_CT + (size_t)NORM_CT * persist_line(np) + 2 * 64 * (size_t)(1 + 2 * np) +
-                       2 * NORM_CT * hw + (size_t)PR_ZR * 64 + 16 + 16 + 2 * 64 * 2 + (size_t)PL_LOCN * np + (size_t)PL_LOCN;   // (+ a threshold per local slot: the wide walk's)
+                       2 * NORM_CT * hw + (size_t)PR_ZR * 64 + 16 + 16 + 2 * 64 * 2 + (size_t)PL_LOCN * np + (size_t)PL_LOCN +   // (+ a threshold per local slot: the wide walk's)
+                       (size_t)(NORM_WG / 64) * PL_TSW;   // (+ the per-wave stamps)
     return (size_t)PL_PBASE + 2 * (size_t)CONE_LEVELS * 64 * 4 + 2 * (size_t)CONE_GCAP * 2 + 4 * 16 * 4 + 2 * (size_t)PL_HASH * 4 + dbl * 8;
 }
 
@@ -47,7 +53,7 @@ struct PersistLocLds {
     uint32_t* s_hdr;
     double *s_theta, *s_part, *s_st, *s_rng, *s_hrow, *s_xrow, *s_z0, *s_const, *s_gth, *s_thr;
     uint4* s_donor;
-    unsigned long long* s_ts;
+    unsigned long long *s_ts, *s_wts;
     unsigned* s_arrived; int* s_minprog; unsigned* s_abort; unsigned* s_xmask; int* s_glready; int* s_pub; int* s_hready;
     __device__ inline PersistLocLds(unsigned char* lds) {
         pbase = PL_PBASE;
@@ -74,6 +80,7 @@ struct PersistLocLds {
         s_donor = (uint4*)(s_const + 16 + 16);
         s_gth = s_const + 16 + 16 + 2 * 64 * 2;   // [PL_LOCN][NP]: the parameters of the cone's chains' last accepted records, by LOCAL number
         s_thr = s_gth + PL_LOCN * NP;             // [PL_LOCN]: min_improve of the chain AT that local position (the wide walk's per-position thresholds)
+        s_wts = (unsigned long long*)(s_thr + PL_LOCN);   // [16][PL_TSW]: the per-wave stamps (SMMHIP_TS)
     }
 };
 
@@ -93,6 +100,17 @@ __device__ inline uint32_t pl_hash_get(const uint32_t* tab, const uint32_t chain
         h = (h + 1u) & (PL_HASH - 1);
     }
     return 0xffffu;   // (not in the cone's gather list: the plan and the kernel disagree — the caller reports it)
+}
+
+// SMMHIP_TS: a wave's stamps of one iteration into its sums (lane 0), and its sums into the stamp buffer at the end of the launch
+__device__ inline void pl_wts_add(unsigned long long* w, const unsigned long long a, const unsigned long long b, const unsigned long long c,
+                                  const unsigned long long d) {
+    w[0] += a; w[1] += b; w[2] += c; w[3] += d; w[5] += 1ull;
+}
+__device__ inline void pl_wts_out(unsigned long long* ts, const unsigned long long* w, const int tile, const int wave) {
+    if (tile >= PL_TSW_TILES) return;
+    unsigned long long* o = ts + PL_TSW_BASE + ((size_t)tile * (NORM_WG / 64) + (size_t)wave) * PL_TSW;
+    for (int k = 0; k < PL_TSW; ++k) o[k] = k == 4 ? (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) : w[k];   // (HW_REG_HW_ID: SIMD_ID in bits 5:4)
 }
 
 // GUARD of the lean walk on local numbers: the exact value of local chain s (a key tie) out of the ring
@@ -190,6 +208,7 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
         *Y.s_arrived = 0u; *Y.s_minprog = 0; *Y.s_abort = 0u; *Y.s_xmask = 0u; *Y.s_glready = t0 - 2; *Y.s_pub = t0 - 2; *Y.s_hready = t0 - 2;
     }
     if (tid >= 192 && tid < 200) Y.s_ts[tid - 192] = 0ull;
+    if (A.ts && tid >= 256 && tid < 256 + (NORM_WG / 64) * PL_TSW) Y.s_wts[tid - 256] = 0ull;
     if (wave == 3 && lane < CONE_HDRW) {
         if (A.walk_first) Y.s_hdr[((t0 - 1) & 3) * 16 + lane] = A.cone_hdr[((size_t)(t0 - 1 - A.plan_t0) * tiles + tile) * CONE_HDRW + lane];
         if (t0 < t1 && exch_on(t0)) Y.s_hdr[(t0 & 3) * 16 + lane] = A.cone_hdr[((size_t)(t0 - A.plan_t0) * tiles + tile) * CONE_HDRW + lane];
@@ -456,12 +475,17 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
             }
             if (t < t1 && exch_on(t)) request_lists(t);
             PR_BARRIER();   // BB
+            unsigned long long tw0 = 0, tw1 = 0, tw2 = 0;
+            if (A.ts) tw0 = wall_clock64();
             if (simw) {
-                if (nfull == PR_ZR - 1) persist_simulate<NP, true>(z, nfull, extra, Y.s_theta, Y.s_part, h, wih);
-                else persist_simulate<NP, false>(z, nfull, extra, Y.s_theta, Y.s_part, h, wih);
+                __builtin_amdgcn_s_setprio(1);   // the adds before any side job of a wave that is done with them (make_rng's FP64, the tables, the lists)
+                if (nfull == PR_ZR - 1) persist_simulate<NP, true>(z, nfull, extra, Y.s_theta, Y.s_part, h, wih, A.ts != nullptr, tw1);
+                else persist_simulate<NP, false>(z, nfull, extra, Y.s_theta, Y.s_part, h, wih, A.ts != nullptr, tw1);
+                if (A.ts) tw2 = wall_clock64();
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 const int lane3 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
                 if (lane3 == 0) __hip_atomic_fetch_add(Y.s_arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __builtin_amdgcn_s_setprio(0);
             }
             const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
             const bool lists = t < t1 && exch_on(t);
@@ -501,8 +525,10 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
                 __builtin_amdgcn_s_sleep(PR_GATHER_DELAY);
                 gather(t, rel, t + 1, wave * 64 + lane);
             }
+            if (A.ts && lane == 0) pl_wts_add(Y.s_wts + wave * PL_TSW, tw0, tw1, tw2, wall_clock64());
         }
         PR_BARRIER();   // the last epilogue is done
+        if (A.ts && lane == 0) pl_wts_out(A.ts, Y.s_wts + wave * PL_TSW, tile, wave);
         if (wave == 3) { store_rows(Y.s_hrow, t1, 0xffffu); store_rows(Y.s_xrow, t1 - 1, *Y.s_xmask); }
         if (wave == 1) {   // the result blocks where the next launch (of any form) expects them
             const int cl = lane >> 2, r = lane & 3, c = tile * CT + cl;
@@ -529,6 +555,7 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
     for (int t = t0; t <= t1; ++t) {
         const int rel = t - t0 + 1;
         const bool exch = t == t0 ? A.walk_first != 0 : exch_on(t - 1);
+        double z0[PR_ZR];   // the wave's shocks, for the simulation only: fetched behind the proposal, in registers from BB on
         PR_BARRIER();   // BA
         {
             const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -625,24 +652,34 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
                 st[CS_PARTNER] = (double)partner;
                 st[CS_WASX] = (double)src;   // (free during the launch: the LOCAL number the record comes from)
             }
+#pragma unroll
+            for (int u = 0; u < PR_ZR; ++u) z0[u] = Y.s_z0[u * 64 + lane];
             if (A.ts && lane == 0) {
                 const unsigned long long ts4 = wall_clock64();
                 Y.s_ts[1] += ts2 - ts1; Y.s_ts[3] += ts4 - ts2; Y.s_ts[6] = ts4;
             }
         }
         PR_BARRIER();   // BB
+        unsigned long long tw0 = 0, tw1 = 0, tw2 = 0, tw3 = 0;
+        if (A.ts) tw0 = wall_clock64();
         {
-            if (nfull0 == PR_ZR - 1) persist_simulate_lds<NP, true>(Y.s_z0, A.ns, nfull0, Y.s_theta, Y.s_part);
-            else persist_simulate_lds<NP, false>(Y.s_z0, A.ns, nfull0, Y.s_theta, Y.s_part);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            // its share is the place of wave 0 of half 0 — the same lanes, draws, sums and s_part slots as a worker's
             const int lane_a = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            const bool extra0 = lane_a < A.ns - nfull0 * WG;
+            __builtin_amdgcn_s_setprio(1);
+            if (nfull0 == PR_ZR - 1) persist_simulate<NP, true>(z0, nfull0, extra0, Y.s_theta, Y.s_part, 0, 0, A.ts != nullptr, tw1);
+            else persist_simulate<NP, false>(z0, nfull0, extra0, Y.s_theta, Y.s_part, 0, 0, A.ts != nullptr, tw1);
+            if (A.ts) tw2 = wall_clock64();
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (lane_a == 0) __hip_atomic_fetch_add(Y.s_arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __builtin_amdgcn_s_setprio(0);
         }
         {
             const unsigned want = (unsigned)(8 * NP) * (unsigned)rel;
             while (__hip_atomic_load(Y.s_arrived, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < want) __builtin_amdgcn_s_sleep(1);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
+        if (A.ts) tw3 = wall_clock64();
         const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
         const int cl = lane >> 2, r = lane & 3;
         const int c = tile * CT + cl;
@@ -812,11 +849,12 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
                 *Y.s_xmask = m;
             }
         }
-        if (A.ts && lane == 0) { const unsigned long long ts7 = wall_clock64(); Y.s_ts[2] += ts7 - Y.s_ts[6]; Y.s_ts[7] = ts7; }
+        if (A.ts && lane == 0) { const unsigned long long ts7 = wall_clock64(); Y.s_ts[2] += ts7 - Y.s_ts[6]; Y.s_ts[7] = ts7; pl_wts_add(Y.s_wts, tw0, tw1, tw2, tw3); }
     }
     PR_BARRIER();
     {
         const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
         if (A.ts && lane < 7) A.ts[(size_t)tile * 8 + lane] = lane < 6 ? Y.s_ts[lane] : (unsigned long long)(t1 - t0 + 1);
+        if (A.ts && lane == 0) pl_wts_out(A.ts, Y.s_wts, tile, 0);
     }
 }

@@ -3899,6 +3899,14 @@ int smm_debug_ts(void* ctx, unsigned long long* out, int n_wg) {
     if (hipMemcpy(out, c->P.ts, (size_t)n_wg * 8 * 8, hipMemcpyDeviceToHost) != hipSuccess) return SMM_ERR_HIP;
     return SMM_OK;
 }
+// debug (not part of the public header): k_chain_persist_loc's per-wave stamps of the simulation phase, [n_wg][16][PL_TSW] (tools/persist_waves.py)
+int smm_debug_ts_waves(void* ctx, unsigned long long* out, int n_wg) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !c->P.ts || n_wg < 0 || n_wg > PL_TSW_TILES) return SMM_ERR_INVALID_ARG;
+    const size_t words = (size_t)n_wg * (NORM_WG / 64) * PL_TSW;
+    if (hipMemcpy(out, c->P.ts + PL_TSW_BASE, words * 8, hipMemcpyDeviceToHost) != hipSuccess) return SMM_ERR_HIP;
+    return SMM_OK;
+}
 
 #ifdef SMM_TEST_HOOKS
 // debug (test build only, not part of the public header): the look-ahead window starting at iteration t, planned now; milliseconds of its
