@@ -102,11 +102,11 @@ def test_callers_on_the_device_match_the_oracle():
     for pp in ("p1", "p2"):
         for what in ("value", "mu1", "mu2"):
             a, b = sd.get(pp, what), so.get(pp, what)
-            assert np.array_equal(a["x"], b["x"]) and np.allclose(a["y"], b["y"], rtol=1e-12, atol=1e-13)
+            assert np.array_equal(a["x"], b["x"]) and np.array_equal(a["y"], b["y"])     # (eval_batch is bit-exact against the oracle: so is everything over it)
     p = OrderedDict([("p1", -0.7), ("p2", 8.0)])
-    assert np.allclose(S.FD_gradient(m, p), S.FD_gradient(m, p, evaluator=oracle_evaluator), rtol=1e-9, atol=1e-12)
+    assert np.array_equal(S.FD_gradient(m, p), S.FD_gradient(m, p, evaluator=oracle_evaluator))
     assert np.allclose(S.FD_gradient(m, p), np.eye(2), atol=1e-9)     # the moments are the parameters plus fixed shocks
-    assert np.allclose(S.getSigma(m, p, 64, seed=5), S.getSigma(m, p, 64, seed=5, evaluator=oracle_evaluator), rtol=1e-9)
+    assert np.array_equal(S.getSigma(m, p, 64, seed=5), S.getSigma(m, p, 64, seed=5, evaluator=oracle_evaluator))
     out = S.optSlices(m, 25, tol=1e-2, update=0.4)
     assert abs(out["best"]["p"]["p1"] + 1.0) < 0.1 and abs(out["best"]["p"]["p2"] - 10.0) < 0.5
     se = S.get_stdErrors(m, p, reps=100, seed=3)
