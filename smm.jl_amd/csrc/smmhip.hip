@@ -651,9 +651,6 @@ size_t tile_smem_base(const Ctx* c, int ct) {
     const KParams& P = c->P;
     return tile_smem_doubles(ct, P.np, P.nm, P.RW, P.HW, P.RBW, lay_kind(c)) * sizeof(double);
 }
-// tile width (chains per workgroup) of k_chain_iter<0, CT> in a user objective's three launches per iteration: 64 where that tile's LDS
-// fits in 60 KB, else 8 (launch_chain_iter takes it, smm_describe reports it)
-int user_iter_ct(const Ctx* c) { return tile_smem_base(c, 64) <= (size_t)60 * 1024 ? 64 : 8; }
 int lay_kind(const Ctx* c) { const int k = obj_kind(c->obj); return k == 2 && c->P.dense_A2f ? 3 : (c->obj == SMM_OBJ_USER && c->u_lanes > 0) ? 4 : k; }
 // dynamic LDS of k_chain_persist_tile for this context (a user objective's wave totals: 16 chains x lanes / 64 groups x its sums)
 size_t persist_tile_smem(const Ctx* c) {
@@ -785,81 +782,108 @@ void ensure_windows(Ctx* c, int t, bool rng = true) {
     }
 }
 
-template <int KIND, int CT, int TPW = 1>
-void launch_chain_iter_ct(Ctx* c, int t, int flags) {
+// ---- which per-iteration chain kernel (smm_chain.hpp, smm_chain_norm.hpp) ----
+// Every instantiation of the chain kernels' templates that a launch can take is named in chain_instance() and nowhere else: chain_kernel()
+// and chain_kernel_p2p() pick one for a launch, smm_ctx_create raises the dynamic LDS limit of every one of them, smm_describe prints the
+// pick's name.  A new instantiation is one line in chain_instance() (a new family: one more name in ChainFamily).
+// (name: what smm_describe's chain= says; block: lanes of a workgroup; ct: chains per tile; tpw: tiles per workgroup)
+struct ChainKernel { const void* fn; const char* name; unsigned block; int ct, tpw; };
+enum ChainFamily {
+    CF_SIM, CF_SIM_2, CF_DENSE, CF_GEN_KEYS, CF_GEN_64, CF_GEN_2, CF_GEN,   // k_chain_iter<KIND, CT, TPW, b>: b = compiled with the inline walk
+    CF_NORM_NARROW_CONE, CF_NORM_ANY, CF_NORM_WIDE, CF_NORM_NARROW,        // k_chain_iter_norm_*<np>
+    CF_NORM,                                                               // k_chain_iter_norm<np, b>: b = this launch walks
+    CF_P2P_ROWS_NARROW, CF_P2P_ROWS,                                       // k_chain_iter_norm_p2p_rows*<np>
+    CF_P2P,                                                                // k_chain_iter_norm_p2p<np, b>: b = staging loops for more than XLVL_MAX chains or pairs
+    CF_COUNT
+};
+// f(std::integral_constant<int, np>) for a parameter count known at run time: 1 .. 4, as the norm kernels are instantiated
+template <class F>
+const void* by_np(int np, F f) {
+    switch (np) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
+}
+// (np counts for the norm and p2p families only.  The order in which the kernels are named here is the order in which the compiler emits
+// them, and the register numbering of a few of them follows it: kept as the launchers named them before there was this table)
+ChainKernel chain_instance(int family, int np, bool b) {
+#define ITER(KIND, CT, TPW, NAME) \
+    ChainKernel{b ? (const void*)k_chain_iter<KIND, CT, TPW, true> : (const void*)k_chain_iter<KIND, CT, TPW, false>, NAME, WG * TPW, CT, TPW}
+#define NORM(KERN, NAME, BLOCK) ChainKernel{by_np(np, [](auto NP) { return (const void*)KERN<decltype(NP)::value>; }), NAME, BLOCK, NORM_CT, 1}
+#define NORM_B(KERN, NAME) \
+    ChainKernel{by_np(np, [b](auto NP) { return !b ? (const void*)KERN<decltype(NP)::value, false> : (const void*)KERN<decltype(NP)::value, true>; }), NAME, NORM_WG, NORM_CT, 1}
+    switch (family) {
+        case CF_SIM: return ITER(1, 8, 1, "iter<sim,8>");
+        case CF_SIM_2: return ITER(1, 8, 2, "iter<sim,8,2>");
+        case CF_DENSE: return ITER(2, 16, 1, "iter<dense,16>");
+        case CF_GEN_KEYS: return ITER(0, 16, 2, "iter<gen,16,2>");
+        case CF_GEN_64: return ITER(0, 64, 1, "iter<gen,8>");   // (smm_describe has always filed the 64-chain tile under the 8-chain tile's name)
+        case CF_GEN_2: return ITER(0, 8, 2, "iter<gen,8,2>");
+        case CF_GEN: return ITER(0, 8, 1, "iter<gen,8>");
+        case CF_NORM_NARROW_CONE: return NORM(k_chain_iter_norm_narrow_cone, "iter_norm_narrow_cone", NORM_WG / 2);
+        case CF_NORM_ANY: return NORM(k_chain_iter_norm_any, "iter_norm_any", NORM_WG);
+        case CF_NORM_WIDE: return NORM(k_chain_iter_norm_wide, "iter_norm_wide", NORM_WG);
+        case CF_NORM_NARROW: return NORM(k_chain_iter_norm_narrow, "iter_norm_narrow", NORM_WG / 2);
+        case CF_NORM: return NORM_B(k_chain_iter_norm, "iter_norm");
+        case CF_P2P_ROWS_NARROW: return NORM(k_chain_iter_norm_p2p_rows_narrow, "iter_norm_p2p_rows_narrow", NORM_WG / 2);
+        case CF_P2P_ROWS: return NORM(k_chain_iter_norm_p2p_rows, "iter_norm_p2p_rows", NORM_WG);
+        default: return NORM_B(k_chain_iter_norm_p2p, "iter_norm_p2p");
+    }
+#undef ITER
+#undef NORM
+#undef NORM_B
+}
+// what launch_chain_iter launches for this context as it stands now; flags & F_WALK_INLINE: the launch walks the previous iteration's
+// exchange.  Decides only: allocates nothing, launches nothing.
+ChainKernel chain_kernel(const Ctx* c, int flags) {
     const KParams& P = c->P;
-    const int tiles = (P.N + CT - 1) / CT;
+    const Forms& F = c->F;
+    const bool walk = (flags & F_WALK_INLINE) != 0, user = c->obj == SMM_OBJ_USER;
+    if (F.norm_fast && !user) {   // k_chain_iter_norm and its variants: one 16-chain tile per workgroup
+        // large single shards: every tile walks its own, locally numbered cone (smm_cone_big.hpp)
+        if (walk && F.cone_big) return chain_instance(CF_NORM_NARROW_CONE, P.np, false);
+        // the lean walks need a padded plan of at most 31 levels and values without NaN: where that is not given — per-chain or
+        // negative thresholds (no padded plan), an injected pair list that goes deeper, an uploaded state with NaN values — the
+        // kernel with the walk on 16-byte slots {value, src, partner} runs
+        // (mi_pct: the lean plan stands for the persistent launches only)
+        if (walk && (!F.lean_plan || c->deep_plan || c->nan_values || P.mi_pct)) return chain_instance(CF_NORM_ANY, P.np, false);
+        if (walk && P.lean_wide) return chain_instance(CF_NORM_WIDE, P.np, false);   // one min_improve > 0 for all chains: the lean walk on 16-byte slots
+        // more than one round of tiles: two half-size workgroups per CU (k_chain_iter_norm_narrow)
+        if (!walk && F.norm_narrow) return chain_instance(CF_NORM_NARROW, P.np, false);
+        return chain_instance(CF_NORM, P.np, walk);
+    }
+    // the general kernel (contexts that never walk inline run it compiled without the walk).  Objectives without a simulation take tiles
+    // of 64 chains where such a tile's LDS fits in 60 KB — a user objective's three launches per iteration wherever it does, ct says which
+    const bool fits64 = tile_smem_base(c, 64) <= (size_t)60 * 1024;
+    const int family = is_sim(c->obj) ? (F.tpw == 2 ? CF_SIM_2 : CF_SIM) : c->obj == SMM_OBJ_DENSE ? CF_DENSE : user ? (fits64 ? CF_GEN_64 : CF_GEN)
+                     : F.gen_keys ? CF_GEN_KEYS : (fits64 && !F.inline_walk) ? CF_GEN_64 : F.tpw == 2 ? CF_GEN_2 : CF_GEN;
+    ChainKernel K = chain_instance(family, P.np, F.inline_walk);
+    if (user) K.name = c->u_lanes ? "user_lanes_3launches" : "user_3launches";
+    if (c->obj == SMM_OBJ_DENSE && P.dense_A2f) K.name = "iter<dense2,16>";
     // an objective without a simulation (banana, user objectives) has work for the tile's control wave only: unless the exchange
     // walk runs inline (all lanes stage its inputs) the tile is launched as that one wave, so that every tile of a large
     // population is resident at once instead of queueing behind 448 idle lanes each
-    const bool slim = KIND == 0 && TPW == 1 && !(flags & F_WALK_INLINE) && !c->F.inline_walk;
-    const dim3 grid((tiles + TPW - 1) / TPW), block(slim ? 64 : WG * TPW);
-    const double* rin = c->ext_rec_in ? c->ext_rec_in : (const double*)c->rec[c->cur];
-    double* rout = c->ext_rec_out ? c->ext_rec_out : c->rec[c->cur ^ 1];
-    // (contexts that never walk inline run the kernel compiled without the walk)
-    auto kern = c->F.inline_walk ? k_chain_iter<KIND, CT, TPW, true> : k_chain_iter<KIND, CT, TPW, false>;
-    launch(c, kern, grid, block, tile_smem(c, CT, TPW), P, t, rin, rout, flags);
+    if (obj_kind(c->obj) == 0 && K.tpw == 1 && !walk && !F.inline_walk) K.block = 64;
+    return K;
 }
-
-// k_chain_iter_norm and its variants: one 16-chain tile per workgroup of `block` lanes
-template <class Kern>
-void launch_norm_kernel(Ctx* c, Kern kern, unsigned block, int t, int flags) {
+// ... and launch_chain_iter_norm_p2p (smm_p2p.hpp)
+ChainKernel chain_kernel_p2p(const Ctx* c) {
     const KParams& P = c->P;
-    const double* rin = c->ext_rec_in ? c->ext_rec_in : (const double*)c->rec[c->cur];
-    double* rout = c->ext_rec_out ? c->ext_rec_out : c->rec[c->cur ^ 1];
-    launch(c, kern, dim3((P.N + NORM_CT - 1) / NORM_CT), dim3(block), norm_smem(c), P, t, rin, rout, flags);
+    // the kernel without a walk, whose accept step stores the 4-byte slots of k_exch_resolve_rows<., true>: on half-size workgroups for a
+    // shard of more than one round of tiles
+    if (c->p2p_rows) return chain_instance(c->F.norm_narrow ? CF_P2P_ROWS_NARROW : CF_P2P_ROWS, P.np, false);
+    // (BIG: staging loops for up to 8192 chains — two shards of 4096; the small form serves populations up to 4096)
+    return chain_instance(CF_P2P, P.np, P.Ng > XLVL_MAX || P.plan_K > XLVL_MAX);
 }
-void launch_chain_iter_norm(Ctx* c, int t, int flags) {
-    const bool walk = (flags & F_WALK_INLINE) != 0;
-    if (walk && c->F.cone_big) {   // large single shards: every tile walks its own, locally numbered cone (smm_cone_big.hpp)
-        switch (c->P.np) {
-            case 1: launch_norm_kernel(c, k_chain_iter_norm_narrow_cone<1>, NORM_WG / 2, t, flags); break;
-            case 2: launch_norm_kernel(c, k_chain_iter_norm_narrow_cone<2>, NORM_WG / 2, t, flags); break;
-            case 3: launch_norm_kernel(c, k_chain_iter_norm_narrow_cone<3>, NORM_WG / 2, t, flags); break;
-            default: launch_norm_kernel(c, k_chain_iter_norm_narrow_cone<4>, NORM_WG / 2, t, flags); break;
-        }
-        return;
-    }
-    // the lean walks need a padded plan of at most 31 levels and values without NaN: where that is not given — per-chain or
-    // negative thresholds (no padded plan), an injected pair list that goes deeper, an uploaded state with NaN values — the
-    // kernel with the walk on 16-byte slots {value, src, partner} runs
-    if (walk && (!c->P.lv_pairs_p || c->deep_plan || c->nan_values || c->P.mi_pct)) {   // (mi_pct: the lean plan stands for the persistent launches only)
-        switch (c->P.np) {
-            case 1: launch_norm_kernel(c, k_chain_iter_norm_any<1>, NORM_WG, t, flags); break;
-            case 2: launch_norm_kernel(c, k_chain_iter_norm_any<2>, NORM_WG, t, flags); break;
-            case 3: launch_norm_kernel(c, k_chain_iter_norm_any<3>, NORM_WG, t, flags); break;
-            default: launch_norm_kernel(c, k_chain_iter_norm_any<4>, NORM_WG, t, flags); break;
-        }
-        return;
-    }
-    if (walk && c->P.lean_wide) {   // one min_improve > 0 for all chains: the lean walk on 16-byte slots
-        switch (c->P.np) {
-            case 1: launch_norm_kernel(c, k_chain_iter_norm_wide<1>, NORM_WG, t, flags); break;
-            case 2: launch_norm_kernel(c, k_chain_iter_norm_wide<2>, NORM_WG, t, flags); break;
-            case 3: launch_norm_kernel(c, k_chain_iter_norm_wide<3>, NORM_WG, t, flags); break;
-            default: launch_norm_kernel(c, k_chain_iter_norm_wide<4>, NORM_WG, t, flags); break;
-        }
-        return;
-    }
-    if (!walk && c->F.norm_narrow) {   // more than one round of tiles: two half-size workgroups per CU (k_chain_iter_norm_narrow)
-        switch (c->P.np) {
-            case 1: launch_norm_kernel(c, k_chain_iter_norm_narrow<1>, NORM_WG / 2, t, flags); break;
-            case 2: launch_norm_kernel(c, k_chain_iter_norm_narrow<2>, NORM_WG / 2, t, flags); break;
-            case 3: launch_norm_kernel(c, k_chain_iter_norm_narrow<3>, NORM_WG / 2, t, flags); break;
-            default: launch_norm_kernel(c, k_chain_iter_norm_narrow<4>, NORM_WG / 2, t, flags); break;
-        }
-        return;
-    }
-    switch (c->P.np * 2 + (walk ? 1 : 0)) {
-        case 2: launch_norm_kernel(c, k_chain_iter_norm<1, false>, NORM_WG, t, flags); break;
-        case 3: launch_norm_kernel(c, k_chain_iter_norm<1, true>, NORM_WG, t, flags); break;
-        case 4: launch_norm_kernel(c, k_chain_iter_norm<2, false>, NORM_WG, t, flags); break;
-        case 5: launch_norm_kernel(c, k_chain_iter_norm<2, true>, NORM_WG, t, flags); break;
-        case 6: launch_norm_kernel(c, k_chain_iter_norm<3, false>, NORM_WG, t, flags); break;
-        case 7: launch_norm_kernel(c, k_chain_iter_norm<3, true>, NORM_WG, t, flags); break;
-        case 8: launch_norm_kernel(c, k_chain_iter_norm<4, false>, NORM_WG, t, flags); break;
-        default: launch_norm_kernel(c, k_chain_iter_norm<4, true>, NORM_WG, t, flags); break;
-    }
+// K over the chains of P onto the context's stream, with `smem` bytes of dynamic LDS: every kernel of these families takes (P, t, rec_in,
+// rec_out, flags); in profiling mode 2 with the begin/end of this dispatch as the command processor stamps them
+void launch_chain_kernel(Ctx* c, const ChainKernel& K, size_t smem, const KParams& P, int t, const double* rec_in, double* rec_out, int flags) {
+    const dim3 grid((unsigned)(((P.N + K.ct - 1) / K.ct + K.tpw - 1) / K.tpw)), block(K.block);
+    void* args[] = {(void*)&P, (void*)&t, (void*)&rec_in, (void*)&rec_out, (void*)&flags};
+    if (c->kev0) HIPCHK(hipExtLaunchKernel(K.fn, grid, block, args, smem, c->stream, c->kev0, c->kev1, 0));
+    else HIPCHK(hipLaunchKernel(K.fn, grid, block, args, smem, c->stream));
 }
 
 // one thread per evaluation: theta [n][np] -> simM [n][nm], value [n], status [n].  An objective with the library's stream draws from
@@ -886,33 +910,18 @@ void launch_chain_iter(Ctx* c, int t, int flags) {
     c->P.slots17_out = own_slots ? c->slots17 : nullptr;
     c->P.nan_flags_out = own_slots ? c->nan_flags + (t & 1) : nullptr;
     if (own_slots) c->slots_iter = t;
+    const ChainKernel K = chain_kernel(c, flags);
+    const size_t smem = tile_smem(c, K.ct, K.tpw);
+    const double* rin = c->ext_rec_in ? c->ext_rec_in : (const double*)c->rec[c->cur];
+    double* rout = c->ext_rec_out ? c->ext_rec_out : c->rec[c->cur ^ 1];
     if (c->obj == SMM_OBJ_USER) {
         // proposal launch (stores nothing but the proposals) -> the user's kernel -> accept launch (repeats the
         // deterministic prologue, takes value / moments / status from the user's kernel)
         const KParams& P = c->P;
-        const bool big = user_iter_ct(c) == 64;
-        if (big) launch_chain_iter_ct<0, 64>(c, t, flags | F_PROPOSE_ONLY); else launch_chain_iter_ct<0, 8>(c, t, flags | F_PROPOSE_ONLY);
+        launch_chain_kernel(c, K, smem, P, t, rin, rout, flags | F_PROPOSE_ONLY);
         launch_user_kernel(c, P.u_theta, P.N, P.u_simM, P.u_value, P.u_status);
-        if (big) launch_chain_iter_ct<0, 64>(c, t, flags); else launch_chain_iter_ct<0, 8>(c, t, flags);
-        if (!c->ext_rec_out) c->cur ^= 1;
-        return;
     }
-    if (c->F.norm_fast) {
-        launch_chain_iter_norm(c, t, flags);
-    } else if (is_sim(c->obj)) {
-        if (c->F.tpw == 2) launch_chain_iter_ct<1, 8, 2>(c, t, flags);
-        else launch_chain_iter_ct<1, 8>(c, t, flags);
-    } else if (c->obj == SMM_OBJ_DENSE) {
-        launch_chain_iter_ct<2, 16>(c, t, flags);
-    } else if (c->F.gen_keys) {
-        launch_chain_iter_ct<0, 16, 2>(c, t, flags);
-    } else if (tile_smem_base(c, 64) <= (size_t)60 * 1024 && !c->F.inline_walk) {
-        launch_chain_iter_ct<0, 64>(c, t, flags);
-    } else if (c->F.tpw == 2) {
-        launch_chain_iter_ct<0, 8, 2>(c, t, flags);
-    } else {
-        launch_chain_iter_ct<0, 8>(c, t, flags);
-    }
+    launch_chain_kernel(c, K, smem, c->P, t, rin, rout, flags);
     if (!c->ext_rec_out) c->cur ^= 1;
 }
 
@@ -1145,46 +1154,14 @@ struct DevBuf {
 
 
 // ---- the p2p form of the sharded iteration (smm_p2p.hpp, include/smmhip.h) ----
-template <int NP, bool BIG>
-void launch_chain_iter_norm_p2p_tb(Ctx* c, const KParams& P, int t, int flags, size_t smem) {
-    launch(c, k_chain_iter_norm_p2p<NP, BIG>, dim3((P.N + NORM_CT - 1) / NORM_CT), dim3(NORM_WG), smem, P, t, (const double*)nullptr, (double*)nullptr, flags);
-}
-template <int NP>
-void launch_chain_iter_norm_p2p_t(Ctx* c, const KParams& P, int t, int flags, size_t smem) {
-    // (BIG: staging loops for up to 8192 chains — two shards of 4096; the small form serves populations up to 4096)
-    if (P.Ng > XLVL_MAX || P.plan_K > XLVL_MAX) launch_chain_iter_norm_p2p_tb<NP, true>(c, P, t, flags, smem);
-    else launch_chain_iter_norm_p2p_tb<NP, false>(c, P, t, flags, smem);
-}
 size_t p2p_walk_bytes(const Ctx* c) { return (lean_walk_bytes(c->P.Ng, c->P.plan_K) + 15) & ~(size_t)15; }
-template <int NP>
-void launch_chain_iter_norm_p2p_rows_t(Ctx* c, const KParams& P, int t, int flags, size_t smem) {
-    const dim3 grid((P.N + NORM_CT - 1) / NORM_CT), block(c->F.norm_narrow ? NORM_WG / 2 : NORM_WG);
-    if (c->F.norm_narrow)   // a shard of more than one round of tiles
-        launch(c, k_chain_iter_norm_p2p_rows_narrow<NP>, grid, block, smem, P, t, (const double*)nullptr, (double*)nullptr, flags);
-    else
-        launch(c, k_chain_iter_norm_p2p_rows<NP>, grid, block, smem, P, t, (const double*)nullptr, (double*)nullptr, flags);
-}
 void launch_chain_iter_norm_p2p(Ctx* c, int t, int flags) {
     KParams P = c->P;
     point_values(c, P, t - 1, t);
     const bool walk = (flags & F_WALK_INLINE) != 0;
     P.tile_off = walk ? (int)(p2p_walk_bytes(c) / sizeof(double)) : 0;
     const size_t smem = (size_t)P.tile_off * sizeof(double) + norm_tile_doubles(P.np) * sizeof(double);
-    if (c->p2p_rows) {   // the kernel without a walk; its accept step stores the 4-byte slots of k_exch_resolve_rows<., true>
-        switch (P.np) {
-            case 1: launch_chain_iter_norm_p2p_rows_t<1>(c, P, t, flags, smem); break;
-            case 2: launch_chain_iter_norm_p2p_rows_t<2>(c, P, t, flags, smem); break;
-            case 3: launch_chain_iter_norm_p2p_rows_t<3>(c, P, t, flags, smem); break;
-            default: launch_chain_iter_norm_p2p_rows_t<4>(c, P, t, flags, smem); break;
-        }
-        return;
-    }
-    switch (P.np) {
-        case 1: launch_chain_iter_norm_p2p_t<1>(c, P, t, flags, smem); break;
-        case 2: launch_chain_iter_norm_p2p_t<2>(c, P, t, flags, smem); break;
-        case 3: launch_chain_iter_norm_p2p_t<3>(c, P, t, flags, smem); break;
-        default: launch_chain_iter_norm_p2p_t<4>(c, P, t, flags, smem); break;
-    }
+    launch_chain_kernel(c, chain_kernel_p2p(c), smem, P, t, nullptr, nullptr, flags);
 }
 // this rank's slice after iteration t -> every rank's window (parity t & 1); rec_src: out of the context's own record array (a
 // publication), else out of its own window (generic form, after a chain kernel); ll: the self-validating form of the inline kernels
@@ -1233,20 +1210,23 @@ void launch_resolve_rows_window(Ctx* c, int t) {
 }
 // ---- the persistent chain kernels (smm_chain_persist*.hpp) ----
 // what launches F's persistent kernel: a kernel of the library (fn) or of a user objective's module (mfn: loaded by persist_occupancy),
-// its grid, block and dynamic LDS.  persist_occupancy sets its LDS attribute and asks for its occupancy, launch_chain_persist launches it.
-struct PersistKernel { const void* fn; hipFunction_t mfn; dim3 grid, block; size_t smem; };
+// its grid, block and dynamic LDS.  persist_occupancy sets its LDS attribute and asks for its occupancy, launch_chain_persist launches it,
+// smm_describe prints its name.
+struct PersistKernel { const void* fn; hipFunction_t mfn; dim3 grid, block; size_t smem; const char* name; };
 PersistKernel persist_kernel(const Ctx* c, const Forms& F) {
     const KParams& P = c->P;
-    PersistKernel K{nullptr, nullptr, dim3(persist_tiles_rank(F, P.N)), dim3(1), 0};
+    PersistKernel K{nullptr, nullptr, dim3(persist_tiles_rank(F, P.N)), dim3(1), 0, "none"};
     if (F.persist == PERSIST_GEN) {
         K.block = dim3(1024);
         K.smem = persist_gen_smem_bytes(P.Ng, P.np, P.RW, P.HW) + (F.persist_user ? persist_gen_user_bytes() : 0);
+        K.name = F.persist_user ? "gen_user" : "gen";
         if (F.persist_user) K.mfn = c->pfn;   // (the same kernel, compiled with the user's objective inside: user_persist_compile)
         else K.fn = (const void*)k_chain_persist_gen;
     } else if (F.persist == PERSIST_LOC) {
         const bool one = P.np == 1, wd = F.persist_wide, sh = F.persist_sh;
         K.block = dim3(NORM_WG);
         K.smem = persist_loc_smem_bytes(P.np);
+        K.name = sh ? (F.persist_sh_big ? (wd ? "loc_wide_shard_bigplan" : "loc_shard_bigplan") : (wd ? "loc_wide_shard" : "loc_shard")) : (wd ? "loc_wide" : "loc");
         if (P.mi_pct) K.fn = one ? (const void*)k_chain_persist_loc<1, true, false, true> : (const void*)k_chain_persist_loc<2, true, false, true>;
         else if (one) K.fn = wd ? (sh ? (const void*)k_chain_persist_loc<1, true, true> : (const void*)k_chain_persist_loc<1, true, false>)
                                 : (sh ? (const void*)k_chain_persist_loc<1, false, true> : (const void*)k_chain_persist_loc<1, false, false>);
@@ -1256,6 +1236,8 @@ PersistKernel persist_kernel(const Ctx* c, const Forms& F) {
         const bool dense = obj_kind(c->obj) == 2;
         K.block = dim3(WG);
         K.smem = persist_tile_smem(c);
+        K.name = c->obj == SMM_OBJ_USER ? (F.persist_sh ? "tile_user_shard" : "tile_user") : !dense ? (F.persist_sh ? "tile_sim_shard" : "tile_sim")
+               : P.dense_A2f ? (F.persist_sh ? "tile_dense2_shard" : "tile_dense2") : (F.persist_sh ? "tile_dense_shard" : "tile_dense");
         if (c->obj == SMM_OBJ_USER) K.mfn = c->pfn;   // (the same kernel, compiled with the user's map-reduce objective inside: user_tile_compile)
         else if (F.persist_sh) K.fn = dense ? (const void*)k_chain_persist_tile<2, false, true> : (const void*)k_chain_persist_tile<1, false, true>;
         else if (P.mi_pct) K.fn = dense ? (const void*)k_chain_persist_tile<2, true> : (const void*)k_chain_persist_tile<1, true>;
@@ -2410,56 +2392,11 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
         }
         {   // tiles of problems with many parameters need more than the default 64 KiB of dynamic LDS
             const int lim = 160 * 1024;
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter<1, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter<2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter<0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter<0, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter<0, 16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter<1, 8, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter<2, 16, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter<0, 8, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_narrow<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_narrow<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_narrow<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_narrow<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_narrow_cone<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_narrow_cone<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_narrow_cone<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_narrow_cone<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
+            // (every kernel chain_kernel / chain_kernel_p2p can pick: what chain_instance names)
+            for (int family = 0; family < CF_COUNT; ++family)
+                for (int np = 1; np <= 4; ++np)
+                    for (int b = 0; b < 2; ++b) HIPCHK(hipFuncSetAttribute(chain_instance(family, np, b != 0).fn, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
             if (F.cone_big) HIPCHK(hipFuncSetAttribute((const void*)k_cone_chains, hipFuncAttributeMaxDynamicSharedMemorySize, Ng * 4));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_wide<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_wide<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_wide<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_wide<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_any<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_any<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_any<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_any<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p_rows_narrow<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p_rows_narrow<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p_rows_narrow<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p_rows_narrow<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p_rows<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p_rows<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p_rows<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p_rows<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_chain_iter_norm_p2p<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
             HIPCHK(hipFuncSetAttribute((const void*)k_eval_batch<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
             HIPCHK(hipFuncSetAttribute((const void*)k_eval_batch<2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
             HIPCHK(hipFuncSetAttribute((const void*)k_eval_batch<0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
@@ -3859,25 +3796,18 @@ int smm_describe(void* ctx, char* out, int32_t cap) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !out || cap < 1) return SMM_ERR_INVALID_ARG;
     const KParams& P = c->P;
-    const char* chain;
-    if (c->obj == SMM_OBJ_USER) chain = c->u_lanes ? "user_lanes_3launches" : "user_3launches";
-    else if (c->F.norm_fast)
-        chain = c->F.cone_big ? "iter_norm_narrow_cone" : (!c->F.lean_plan || c->deep_plan || c->nan_values || P.mi_pct) && c->F.inline_walk ? "iter_norm_any"
-              : (P.lean_wide && c->F.inline_walk) ? "iter_norm_wide" : c->F.norm_narrow ? "iter_norm_narrow" : "iter_norm";
-    else chain = c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "iter<dense2,16>" : "iter<dense,16>") : is_sim(c->obj) ? (c->F.tpw == 2 ? "iter<sim,8,2>" : "iter<sim,8>")
-               : (c->F.gen_keys ? "iter<gen,16,2>" : c->F.tpw == 2 ? "iter<gen,8,2>" : "iter<gen,8>");
+    // the kernel of the iterations that walk the previous exchange inline, where the context has such iterations and a kernel made for
+    // them (narrow_cone, any, wide); else the kernel of the others (k_chain_iter_norm<np, true> is "iter_norm" like <np, false>, and where
+    // the walk-free iterations take the narrow kernel that one is named)
+    const bool walks = c->F.inline_walk || c->F.cone_big;
+    ChainKernel chain = chain_kernel(c, walks ? F_WALK_INLINE : 0);
+    if (walks && !strcmp(chain.name, "iter_norm")) chain = chain_kernel(c, 0);
     static const char* xk[] = {"lean", "lvl", "lvl_soa", "tickets", "rows", "key", "lvl_big", "any"};
     const char* walk = c->F.cone_big ? "cone_local" : !c->F.inline_walk ? "standalone" : c->F.dense_keys ? "inline_keys_under_tile" : c->F.gen_keys ? (c->F.cone ? "inline_keys_cone" : "inline_keys")
                      : c->F.norm_fast ? ((P.lean_wide && !P.mi_pct) ? "inline_lean_wide" : (c->F.lean_plan && !P.mi_pct) ? "inline_lean" : "inline_slots") : c->F.gen_lean ? "inline_lean16" : "inline_slots";
-    const char* pers = c->F.persist == PERSIST_NONE ? "none" : c->F.persist == PERSIST_LOC ? (c->F.persist_sh ? (c->F.persist_sh_big ? (c->F.persist_wide ? "loc_wide_shard_bigplan" : "loc_shard_bigplan")
-                                                                                                    : (c->F.persist_wide ? "loc_wide_shard" : "loc_shard"))
-                                                                              : (c->F.persist_wide ? "loc_wide" : "loc"))
-                     : c->F.persist == PERSIST_TILE ? (c->F.persist_sh ? (c->pfn ? "tile_user_shard" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2_shard" : "tile_dense_shard") : "tile_sim_shard")
-                                                                        : (c->pfn ? "tile_user" : c->obj == SMM_OBJ_DENSE ? (P.dense_A2f ? "tile_dense2" : "tile_dense") : "tile_sim"))
-                     : c->F.persist_user ? "gen_user" : "gen";
-    const int n = snprintf(out, (size_t)cap, "chain=%s walk=%s exchange=%s persistent=%s plan=%s window=%d", chain, walk, xk[c->F.xk], pers,
+    const int n = snprintf(out, (size_t)cap, "chain=%s walk=%s exchange=%s persistent=%s plan=%s window=%d", chain.name, walk, xk[c->F.xk], persist_kernel(c, c->F).name,
                            c->F.plan == PLAN_BIG ? (c->F.plan_ahead ? "big_ahead" : "big") : c->F.plan == PLAN_LDS ? "lds" : "none", c->F.plan_cap);
-    if (c->obj == SMM_OBJ_USER && n >= 0 && n < cap) snprintf(out + n, (size_t)(cap - n), " ct=%d", user_iter_ct(c));   // (the three launches' tile width)
+    if (c->obj == SMM_OBJ_USER && n >= 0 && n < cap) snprintf(out + n, (size_t)(cap - n), " ct=%d", chain.ct);   // (the three launches' tile width)
     return SMM_OK;
 }
 

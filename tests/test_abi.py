@@ -162,3 +162,25 @@ def test_the_shipped_library_has_no_test_seams():
     seams = sorted(set(m.decode() for m in re.findall(rb"SMMHIP_[A-Z0-9_]+", open(A.HOOKS_LIB_PATH, "rb").read())))
     assert "SMMHIP_INLINE_WALK" in seams and "SMMHIP_A2A_CAP" in seams
     assert "SMMHIP_STATS_SCRATCH" in seams and "SMMHIP_STATS_MODE_BINS" in seams
+
+
+def test_chain_kernel_instantiations_are_named_in_the_chooser_only():
+    """smmhip.hip names the per-iteration chain kernels (k_chain_iter*, smm_chain.hpp and smm_chain_norm.hpp) in chain_instance() and
+    nowhere else: the launchers, the dynamic-LDS attribute at context creation and smm_describe all go through it, so a kernel that can
+    be launched has its attribute set and its name reported by construction.  Reads the sources only."""
+    csrc = os.path.join(ROOT, "smm.jl_amd", "csrc")
+    strip = lambda txt: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    code = strip(open(os.path.join(csrc, "smmhip.hip")).read())
+    head = "ChainKernel chain_instance(int family, int np, bool b) {"
+    assert code.count(head) == 1
+    a = code.index(head)
+    b = code.index("\n}\n", a)
+    body, rest = code[a:b], code[:a] + code[b:]
+    assert not re.findall(r"\bk_chain_iter\w*", rest), "a chain kernel is named outside chain_instance()"
+    declared = set()
+    for h in ("smm_chain.hpp", "smm_chain_norm.hpp"):
+        declared |= set(re.findall(r"__global__[^;{]*?\b(k_chain_iter\w*)\s*\(", strip(open(os.path.join(csrc, h)).read())))
+    assert len(declared) >= 9 and set(re.findall(r"\bk_chain_iter\w*", body)) == declared
+    for line in code.splitlines():
+        assert not ("hipFuncAttributeMaxDynamicSharedMemorySize" in line and "k_chain_iter" in line), line
+    assert "chain_instance(family, np, b != 0).fn, hipFuncAttributeMaxDynamicSharedMemorySize" in rest
