@@ -538,6 +538,56 @@ int  smm_get_histogram(void* ctx, int32_t t0, int32_t t1, int32_t select, const 
                        int32_t bins, const double* range /* [np][2] or NULL */, const int32_t* pairs /* [n_pairs][2] */,
                        int32_t n_pairs, int32_t bins2, smm_histogram_t* out);
 
+/* The population per iteration computed on the device from the history it holds: for each kept iteration of the 0-based window
+ * [t0, t1) and each group of chains, the across-chain mean, variance, median and quantiles of every series, the members' accept,
+ * exchange and failure counts, and the best value among them — the readers above collapse the iterations of a window per chain or
+ * group; this one collapses the member chains of a group per iteration.  Row i is iteration t0 + i stride, i < nt =
+ * ceil((t1 - t0) / stride) (0 for an empty window).  Groups as in smm_get_group_stats / smm_get_histogram (group[c] in [-1, n_groups),
+ * -1: in no group; group NULL with n_groups == 1: every local chain in group 0; a shard reports its own local chains; per-chain
+ * traces: group = 0 .. N-1), members in ascending local index.  S = np + 1 series, or np + 1 + nm with moments != 0: s < np parameter s,
+ * s == np the objective value, s = np + 1 + k simulated moment k.  Column x of (row i, group g, series s), t = t0 + i stride:
+ *   select 0: every member's row t itself — params[t], value[t], sim_moments[t] (what params(c, accepted_only = false) plots);
+ *   1: the same of the members with accepted[t] != 0 only, so count varies with t;
+ *   2: the state series of smm_get_chain_diag — every member's row a(t), the last row r <= t with accepted[r] != 0, looking back
+ *      before t0 as far as row 0; that row supplies parameters, value and moments alike; a member with no such row contributes NaN.
+ * Caller-allocated; any pointer may be NULL (not returned; mean, var, median and quantile all NULL: no column is gathered).  Read-only
+ * and ordered like smm_get_chain_stats (it settles, flushes and synchronises, and changes no state, history or generator).  Device
+ * memory is bounded: the kept iterations go in batches.  A kept iteration takes M x (8 S + 4) bytes (+ 4) of smm_get_chain_stats'
+ * scratch (M <= N member chains: the columns and the state table; the scratch is grown where needed to one series of one iteration,
+ * at most 12 N + 4 bytes, and an iteration whose columns do not fit goes in batches of series, each reading its rows once more) and
+ * n_groups x ((3 + n_probs) S x 8 + 28) bytes of the result buffer; a batch holds as many kept iterations as fit the scratch and
+ * 256 MiB of results (at least one), and results are produced and copied out batch by batch, so nt x n_groups x S may be gigabytes
+ * of host memory (per-chain groups) without being so on the device.  Plus 4 (n_groups + 1 + M) + 8 n_probs bytes of lists.
+ * SMM_ERR_INVALID_ARG: NULL ctx or out, a bad window, stride < 1, select outside [0, 2], n_groups < 0, group NULL with n_groups != 1,
+ * a group id outside [-1, n_groups), n_probs < 0, probs NULL with n_probs > 0, a prob outside [0, 1] or NaN, quantile without probs.
+ *
+ * Numerical contract: numpy's on the contiguous column x of the m = count selected members in ascending local index (every operation
+ * rounded on its own, no fma):
+ *   mean       = the chain-stats mean (the pw sum in chunks of 8192, divided by m): np.mean(x)
+ *   var        = S((x - mu) * (x - mu)) / (m - 1), mu = mean(x), S the same chunked pairwise sum (smm_get_chain_diag's half variance):
+ *                np.var(x, ddof = 1); m < 2: NaN
+ *   median, quantile p = the chain-stats order statistics of x (numpy's _lerp); the -0/+0 caveat of smm_get_chain_stats holds
+ *   a NaN in the column: mean, var, median and every quantile NaN (count still reported); m == 0: NaN
+ *   best       = the first NaN of value[t] over the group's members if any, else its first minimum, in ascending local index
+ *                (np.argmin; EVERY member, whatever select); best_chain its 1-based GLOBAL chain id; an empty group: NaN and 0. */
+typedef struct {            /* caller-allocated; any pointer may be NULL = not returned; S = np + 1 (+ nm with moments != 0)          */
+    int32_t* iter;          /* [nt]                  the 0-based iteration of row i: t0 + i * stride                                   */
+    int32_t* n_chains;      /* [G]                   member chains                                                                      */
+    int32_t* count;         /* [nt][G]               members selected at that iteration (= n_chains for select 0 and 2)                 */
+    int32_t* n_accepted;    /* [nt][G]               members with accepted != 0 and exchanged == 0                                      */
+    int32_t* n_exchanged;   /* [nt][G]               members with exchanged != 0                                                        */
+    int32_t* n_failed;      /* [nt][G]               members with status < 0                                                            */
+    double*  mean;          /* [nt][G][S]                                                                                               */
+    double*  var;           /* [nt][G][S]            np.var(x, ddof = 1)                                                                */
+    double*  median;        /* [nt][G][S]                                                                                               */
+    double*  quantile;      /* [n_probs][nt][G][S]                                                                                      */
+    double*  best_value;    /* [nt][G]               np.argmin order over the members' value[t] (every member, whatever select)         */
+    int32_t* best_chain;    /* [nt][G]               1-based GLOBAL chain id of it; 0 for an empty group                                */
+} smm_trace_t;
+int  smm_get_trace(void* ctx, int32_t t0, int32_t t1, int32_t stride, int32_t select, int32_t moments,
+                   const int32_t* group /* [N] or NULL */, int32_t n_groups,
+                   const double* probs, int32_t n_probs, smm_trace_t* out);
+
 /* Covariances of the chains' draws and the proposal factor between steps — adaptive Metropolis (Haario et al.) on top of chol_L: a
  * pilot run, then each chain's proposal shaped by the covariance of its own draws, without leaving the device.
  *

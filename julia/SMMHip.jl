@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_group_stats, hip_histogram, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
 const ABI_VERSION = 3
@@ -130,6 +130,21 @@ struct SmmHistogram
     hist::Ptr{Int64}
     edges2::Ptr{Cdouble}
     hist2::Ptr{Int64}
+end
+
+struct SmmTrace
+    iter::Ptr{Int32}
+    n_chains::Ptr{Int32}
+    count::Ptr{Int32}
+    n_accepted::Ptr{Int32}
+    n_exchanged::Ptr{Int32}
+    n_failed::Ptr{Int32}
+    mean::Ptr{Cdouble}
+    var::Ptr{Cdouble}
+    median::Ptr{Cdouble}
+    quantile::Ptr{Cdouble}
+    best_value::Ptr{Cdouble}
+    best_chain::Ptr{Int32}
 end
 
 struct SmmState
@@ -477,6 +492,44 @@ function hip_histogram(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :ac
                            max(b2, 1), hs))
     end
     return (count = count, status = st, lo = lo, hi = hi, edges = edges, hist = hist, edges2 = edges2, hist2 = hist2)
+end
+
+"""
+    hip_trace(h, t0, t1; stride = 1, select = :state, moments = false, groups = nothing, probs = Float64[]) -> NamedTuple
+
+The population per iteration over the kept iterations `t0+1, t0+1+stride, .. <= t1`, reduced across the chains of each group on the
+device (`smm_get_trace`) without downloading the history.  `select`: `:all` (every member's row itself), `:accepted` (the members
+accepted at that iteration) or `:state` (every member's last accepted row).  `groups[chain]` holds 0-based group ids (-1 = none);
+`nothing`: every chain in one group.  The `S` series are the parameters, the objective value and, with `moments`, the simulated
+moments.  Returns `iter[i]` (0-based), `n_chains[g]`, `count[g, i]`, `n_accepted[g, i]`, `n_exchanged[g, i]`, `n_failed[g, i]`,
+`best_value[g, i]`, `best_chain[g, i]` (1-based global id), `mean[s, g, i]`, `var[s, g, i]`, `median[s, g, i]` and
+`quantile[s, g, i, p]` (the header's row-major arrays).  NumPy's summation and order statistics (include/smmhip.h).
+"""
+function hip_trace(h::HipBGP, t0::Integer, t1::Integer; stride::Integer = 1, select::Symbol = :state, moments::Bool = false,
+                   groups::Union{Nothing,AbstractVector{<:Integer}} = nothing, probs::AbstractVector{<:Real} = Float64[])
+    N = h.N
+    S = h.np + 1 + (moments ? h.nm : 0)
+    stride >= 1 || throw(ArgumentError("stride must be at least 1"))
+    g = groups === nothing ? Int32[] : Vector{Int32}(groups)
+    groups === nothing || length(g) == N || throw(ArgumentError("groups needs one entry per chain"))
+    ng = groups === nothing ? 1 : (isempty(g) ? 0 : Int(maximum(g)) + 1)
+    p = Vector{Float64}(probs); nq = length(p)
+    nt = max(0, cld(t1 - t0, stride))
+    iter = Vector{Int32}(undef, nt); nch = Vector{Int32}(undef, ng)
+    count = Matrix{Int32}(undef, ng, nt); nacc = Matrix{Int32}(undef, ng, nt); nex = Matrix{Int32}(undef, ng, nt)
+    nfail = Matrix{Int32}(undef, ng, nt); bestv = Matrix{Float64}(undef, ng, nt); bestc = Matrix{Int32}(undef, ng, nt)
+    mean = Array{Float64}(undef, S, ng, nt); var = Array{Float64}(undef, S, ng, nt); med = Array{Float64}(undef, S, ng, nt)
+    quant = Array{Float64}(undef, S, ng, nt, nq)
+    GC.@preserve g p iter nch count nacc nex nfail bestv bestc mean var med quant begin
+        tr = SmmTrace(pointer(iter), pointer(nch), pointer(count), pointer(nacc), pointer(nex), pointer(nfail), pointer(mean), pointer(var),
+                      pointer(med), nq > 0 ? pointer(quant) : Ptr{Cdouble}(C_NULL), pointer(bestv), pointer(bestc))
+        check(h.ctx, ccall(sym(:smm_get_trace), Cint,
+                           (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Ptr{Int32}, Cint, Ptr{Cdouble}, Cint, Ref{SmmTrace}),
+                           h.ctx, t0, t1, stride, HIST_SELECT[select], moments ? 1 : 0, groups === nothing ? Ptr{Int32}(C_NULL) : pointer(g), ng,
+                           nq > 0 ? pointer(p) : Ptr{Cdouble}(C_NULL), nq, tr))
+    end
+    return (iter = iter, n_chains = nch, count = count, n_accepted = nacc, n_exchanged = nex, n_failed = nfail, mean = mean, var = var,
+            median = med, quantile = quant, best_value = bestv, best_chain = bestc)
 end
 
 # the factor(s) between the header's row-major [np][np] / [N][np][np] and Julia's L[k, j] / L[k, j, c]

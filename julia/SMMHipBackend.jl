@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, pooled_summary, chain_histogram, adapt_proposal!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, pooled_summary, chain_histogram, population_trace, adapt_proposal!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -385,6 +385,31 @@ function chain_histogram(algo::MAlgoBGPHip; window = nothing, select::Symbol = :
         groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
     end
     return SMMHip.hip_histogram(hip, t0, t1; select = select, groups = groups, bins = bins, range = range, pairs = pairs, bins2 = bins2)
+end
+
+"""
+    population_trace(algo; window = nothing, stride = 1, select = :state, moments = false, groups = nothing,
+                     probs = [0.025, 0.5, 0.975]) -> NamedTuple
+
+The trace a convergence plot needs, reduced across the chains of each group on the device from the history it holds
+(`SMMHip.hip_trace`), without `sync_chains!`: for every `stride`-th iteration of the window the across-chain `mean[s, g, i]`,
+`var[s, g, i]`, `median[s, g, i]` and `quantile[s, g, i, p]` of each parameter, of the objective value and, with `moments`, of each
+simulated moment, the members' `n_accepted[g, i]`, `n_exchanged[g, i]` and `n_failed[g, i]`, and `best_value[g, i]` with its
+`best_chain[g, i]`.  `groups[chain]` holds 0-based group ids (-1 = none); by default the chains with equal `acc_tuners` entries, as
+`pooled_summary`.  `select = :state` follows each chain's current state (its last accepted row), `:all` the rows themselves, as the
+reference's chain plot draws them.  Not a method of `SMM`: the reference plots one line per chain through its recipe.
+"""
+function population_trace(algo::MAlgoBGPHip; window = nothing, stride::Integer = 1, select::Symbol = :state, moments::Bool = false,
+                          groups = nothing, probs = [0.025, 0.5, 0.975])
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    t0, t1 = window === nothing ? (0, SMMHip.hip_iter(hip)) : window
+    if groups === nothing
+        ids = Dict{Float64,Int32}()
+        opts = getfield(algo, :opts)
+        groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
+    end
+    return SMMHip.hip_trace(hip, t0, t1; stride = stride, select = select, moments = moments, groups = groups, probs = collect(Float64, probs))
 end
 
 """

@@ -12,7 +12,7 @@ from .host import (CI, BGPChain, adapt_proposal, cov, ess, histogram, histogram2
                    banana, best, computeNextIteration, dataMoment, dataMomentd, dataMomentW, dataMomentWd,
                    evaluateObjective, fill, dense_sim, dense_sim2, history, mean, median, ms_names, objfunc_norm, param, paramd, params,
                    ps2s_names, ps_names, readMalgo, restart, run, save, serialNormal, setMoments, setValue, snorm_impl,
-                   summary, user_objective)
+                   summary, trace, user_objective)
 from .callers import (FD_gradient, Slice, doSlices, evaluateObjectives, getSigma, get_stdErrors, optSlices, range_length)
 
 __all__ = [n for n in dir() if not n.startswith("_")] + ["_abi"]

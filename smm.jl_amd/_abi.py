@@ -122,6 +122,14 @@ class smm_histogram_t(C.Structure):
     ]
 
 
+class smm_trace_t(C.Structure):
+    _fields_ = [
+        ("iter", c_int32_p), ("n_chains", c_int32_p), ("count", c_int32_p), ("n_accepted", c_int32_p), ("n_exchanged", c_int32_p),
+        ("n_failed", c_int32_p), ("mean", c_double_p), ("var", c_double_p), ("median", c_double_p), ("quantile", c_double_p),
+        ("best_value", c_double_p), ("best_chain", c_int32_p),
+    ]
+
+
 class smm_timing_t(C.Structure):
     _fields_ = [
         ("step_ms", C.c_double), ("iter_kernel_ms", C.c_double), ("exch_kernel_ms", C.c_double),
@@ -170,6 +178,8 @@ SYMBOLS = [
                                       C.POINTER(smm_group_stats_t)]),
     ("smm_get_histogram", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32, c_double_p, c_int32_p,
                                      C.c_int32, C.c_int32, C.POINTER(smm_histogram_t)]),
+    ("smm_get_trace", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_double_p, C.c_int32,
+                                C.POINTER(smm_trace_t)]),
     ("smm_get_chain_cov", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
     ("smm_get_proposal", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_proposal", C.c_int, [C.c_void_p, c_double_p]),

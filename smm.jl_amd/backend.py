@@ -356,6 +356,37 @@ class BGPContext:
                                               pr.ctypes.data_as(A.c_int32_p) if npr else None, npr, b2, C.byref(s)))
         return r
 
+    def trace(self, t0=0, t1=None, stride=1, select="state", moments=False, groups=None, probs=(), n_groups=None):
+        """the population per iteration over the kept iterations t0, t0 + stride, .. < t1, reduced across the chains of each group on the
+        device (smm_get_trace, include/smmhip.h): a dict of numpy arrays iter [nt], n_chains [n_groups], count / n_accepted / n_exchanged /
+        n_failed / best_value / best_chain [nt][n_groups], mean / var / median [nt][n_groups][S], quantile [len(probs)][nt][n_groups][S];
+        the S series are the parameters, the objective value and, with moments, the simulated moments.  select: "all", "accepted" or
+        "state" (the chain's state series); groups: an int per chain (-1 = none), n_groups by default groups.max() + 1, None: every
+        local chain in one group"""
+        t1 = self.state().iter if t1 is None else t1
+        p = A.f64(probs).reshape(-1)
+        N = self.N
+        sel = self._SELECT[select] if isinstance(select, str) else int(select)
+        g = None if groups is None else np.ascontiguousarray(groups, np.int32)
+        if g is not None and g.shape != (N,):
+            raise ValueError("trace: groups needs one entry per chain, got shape %s" % (g.shape,))
+        ng = (1 if g is None else (int(g.max()) + 1 if len(g) else 0)) if n_groups is None else int(n_groups)
+        st = int(stride)
+        nt = max(0, -(-(int(t1) - int(t0)) // st)) if st >= 1 else 0
+        G, S = max(ng, 0), self.np + 1 + (self.nm if moments else 0)
+        r = dict(iter=np.empty(nt, np.int32), n_chains=np.empty(G, np.int32), count=np.empty((nt, G), np.int32),
+                 n_accepted=np.empty((nt, G), np.int32), n_exchanged=np.empty((nt, G), np.int32), n_failed=np.empty((nt, G), np.int32),
+                 mean=np.empty((nt, G, S)), var=np.empty((nt, G, S)), median=np.empty((nt, G, S)), quantile=np.empty((len(p), nt, G, S)),
+                 best_value=np.empty((nt, G)), best_chain=np.empty((nt, G), np.int32))
+        s = A.smm_trace_t()
+        for f, t in A.smm_trace_t._fields_:
+            if f != "quantile" or len(p):
+                setattr(s, f, r[f].ctypes.data_as(t))
+        self._check(self._fn("get_trace")(self._ctx, int(t0), int(t1), st, sel, int(bool(moments)),
+                                          g.ctypes.data_as(A.c_int32_p) if g is not None else None, ng, A.dptr(p) if len(p) else None, len(p),
+                                          C.byref(s)))
+        return r
+
     def _proposal_shape(self):
         if self.proposal_layout is None:
             return None

@@ -71,6 +71,7 @@ using namespace smm;
 #include "smm_diag.hpp"
 #include "smm_group.hpp"
 #include "smm_hist.hpp"
+#include "smm_trace.hpp"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -2413,6 +2414,7 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
         HIPCHK(hipFuncSetAttribute((const void*)k_group_small, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
         HIPCHK(hipFuncSetAttribute((const void*)k_hist_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIST_LDS_BYTES));
         HIPCHK(hipFuncSetAttribute((const void*)k_hist_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIST_LDS_BYTES));
+        HIPCHK(hipFuncSetAttribute((const void*)k_trace_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
         HIPCHK(hipDeviceSynchronize());
     } catch (const std::string& m) {
         g_create_err = m;
@@ -3652,6 +3654,103 @@ int smm_get_histogram(void* ctx, int32_t t0, int32_t t1, int32_t select, const i
             std::fill(out->count, out->count + G, (int64_t)0);
             for (size_t i = 0; i < N; ++i)
                 if (gid[i] >= 0) out->count[gid[i]] += cnt[i];
+        }
+    } catch (const std::string& m) {
+        return fail(c, SMM_ERR_HIP, m);
+    }
+    return SMM_OK;
+}
+
+// --- the population per iteration (smm_trace.hpp) ----------------------------------------------------------------------------------------
+
+constexpr size_t TRACE_BATCH_CAP = (size_t)256 << 20;   // bytes of a batch of kept iterations' results (the test seam SMMHIP_STATS_SCRATCH replaces it)
+
+int smm_get_trace(void* ctx, int32_t t0, int32_t t1, int32_t stride, int32_t select, int32_t moments, const int32_t* group, int32_t n_groups,
+                  const double* probs, int32_t n_probs, smm_trace_t* out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !out) return SMM_ERR_INVALID_ARG;
+    const size_t N = c->P.N;
+    if (stride < 1) return fail(c, SMM_ERR_INVALID_ARG, "stride must be at least 1");
+    if (select < 0 || select > 2) return fail(c, SMM_ERR_INVALID_ARG, "select must be 0 (all), 1 (accepted) or 2 (state)");
+    if (n_groups < 0 || (!group && n_groups != 1)) return fail(c, SMM_ERR_INVALID_ARG, "n_groups < 0, or group NULL with n_groups != 1");
+    if (group)
+        for (size_t i = 0; i < N; ++i)
+            if (group[i] < -1 || group[i] >= n_groups) return fail(c, SMM_ERR_INVALID_ARG, "a group id outside [-1, n_groups)");
+    if (n_probs < 0 || (n_probs > 0 && !probs)) return fail(c, SMM_ERR_INVALID_ARG, "n_probs < 0, or probs NULL with n_probs > 0");
+    if (out->quantile && n_probs == 0) return fail(c, SMM_ERR_INVALID_ARG, "quantile requested without probs");
+    for (int p = 0; p < n_probs; ++p)
+        if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) return fail(c, SMM_ERR_INVALID_ARG, "probs must lie in [0, 1]");
+    try {
+        reader_prelude(c);
+        if (const int rc = check_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t np = P.np, S = np + 1 + (moments ? (size_t)P.nm : 0), G = n_groups, nq = out->quantile ? n_probs : 0;
+        const int nt = (int)(((long long)(t1 - t0) + stride - 1) / stride);
+        // the members of every group, group by group in ascending local index (gmem0: the CSR offsets)
+        std::vector<int> gid(N, 0), gmem0(G + 1, 0), mem;
+        if (group) std::copy(group, group + N, gid.begin());
+        for (size_t i = 0; i < N; ++i)
+            if (gid[i] >= 0) ++gmem0[gid[i] + 1];
+        int longest = 0;
+        for (size_t g = 0; g < G; ++g) { longest = std::max(longest, gmem0[g + 1]); gmem0[g + 1] += gmem0[g]; }
+        mem.resize(gmem0[G]);
+        {
+            std::vector<int> at(gmem0.begin(), gmem0.end() - 1);
+            for (size_t i = 0; i < N; ++i)
+                if (gid[i] >= 0) mem[at[gid[i]]++] = (int)i;
+        }
+        for (size_t g = 0; g < G && out->n_chains; ++g) out->n_chains[g] = gmem0[g + 1] - gmem0[g];
+        for (int i = 0; i < nt && out->iter; ++i) out->iter[i] = t0 + (int32_t)((long long)i * stride);
+        if (nt == 0 || G == 0) return SMM_OK;
+        const int M = gmem0[G];
+        const size_t Mx = std::max(M, 1), Me = (Mx + 1) & ~(size_t)1;   // (the state table's rows keep the columns behind them 8-byte aligned)
+        const bool cols = out->mean || out->var || out->median || out->quantile;
+        // a batch of kept iterations: the state table and the columns in the scratch, the results in the result buffer; a batch of one
+        // kept iteration whose columns do not fit goes in batches of series
+        auto per_iter = [&](size_t sb) { return Me * 4 + sb * Mx * 8; };
+        reducer_scratch(c, per_iter(1));
+        const size_t hook = c->H.stats_scratch;
+        const size_t budget = hook ? std::min(c->st_scr_bytes, std::max(hook, per_iter(1))) : c->st_scr_bytes;
+        const size_t res_iter = G * ((3 + nq) * S * 8 + 8 + 5 * 4), res_cap = hook ? hook : TRACE_BATCH_CAP;
+        const size_t nib = std::min<size_t>(nt, std::max<size_t>(1, std::min(budget / per_iter(cols ? S : 0), res_cap / res_iter)));
+        const size_t sb = !cols ? 0 : per_iter(S) <= budget ? S : std::max<size_t>(1, (budget - Me * 4) / (Mx * 8));
+        Carve Rv;   // 8-byte slices first
+        const auto dprobs = Rv.take<double>(nq), mean = Rv.take<double>(nib * G * S), var = Rv.take<double>(nib * G * S),
+                   median = Rv.take<double>(nib * G * S), quant = Rv.take<double>(nq * nib * G * S), bestv = Rv.take<double>(nib * G);
+        const auto count = Rv.take<int>(nib * G), nacc = Rv.take<int>(nib * G), nex = Rv.take<int>(nib * G), nfail = Rv.take<int>(nib * G),
+                   bestc = Rv.take<int>(nib * G), dgm0 = Rv.take<int>(G + 1), dmem = Rv.take<int>(mem.size());
+        void* d = reducer_result(c, Rv.bytes);
+        HIPCHK(hipMemcpyAsync(dgm0.in(d), gmem0.data(), (G + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        if (M > 0) HIPCHK(hipMemcpyAsync(dmem.in(d), mem.data(), (size_t)M * 4, hipMemcpyHostToDevice, c->stream));
+        if (nq) HIPCHK(hipMemcpyAsync(dprobs.in(d), probs, nq * 8, hipMemcpyHostToDevice, c->stream));
+        int* tab = (int*)c->st_scr;
+        const int lds_n = std::min(STATS_LDS_N, 1 << (int)ceil(log2((double)std::max(longest, 2))));
+        for (size_t i0 = 0; i0 < (size_t)nt; i0 += nib) {
+            const int nk = (int)std::min(nib, (size_t)nt - i0), tb = t0 + (int)((long long)i0 * stride);
+            double* col = (double*)((char*)c->st_scr + (size_t)nk * Me * 4);
+            if (select == 2 && M > 0)
+                launch_checked(c, k_trace_state, dim3(M), dim3(TRACE_WG), 0, (const double*)P.hrec, (int)N, P.HW, (const int*)dmem.in(d), (int)Me,
+                               tb, nk, (int)stride, tab);
+            for (size_t s0 = 0; s0 < (cols ? S : 1); s0 += std::max(sb, (size_t)1)) {   // (no column asked for: the counts and the best only)
+                const int sbb = (int)std::min(sb, S - s0);
+                launch_checked(c, k_trace_gather, dim3((unsigned)(nk * G), (unsigned)std::max(1, (sbb + TRACE_KMAX - 1) / TRACE_KMAX)),
+                               dim3(TRACE_WG), 0, (const double*)P.hrec, (int)N, P.HW, (int)np, (const int*)dmem.in(d), (const int*)dgm0.in(d),
+                               (int)G, M, (int)Me, P.offset, tb, (int)stride, (int)select, (const int*)tab, (int)s0, sbb, (int)(s0 == 0), col,
+                               count.in(d), nacc.in(d), nex.in(d), nfail.in(d), bestv.in(d), bestc.in(d));
+                if (sbb > 0)
+                    launch_checked(c, k_trace_column, dim3((unsigned)(nk * G), (unsigned)sbb), dim3(TRACE_WG), (size_t)lds_n * 8,
+                                   (const double*)col, M, (const int*)dgm0.in(d), (int)G, (int)s0, sbb, (int)S, (const int*)count.in(d),
+                                   (const double*)dprobs.in(d), (int)nq, nib * G * S, mean.in(d), out->var ? var.in(d) : (double*)nullptr,
+                                   out->median ? median.in(d) : (double*)nullptr, quant.in(d));
+            }
+            auto down = [&](auto sl, auto* dst, size_t per, size_t src_off = 0, size_t dst_off = 0) {
+                if (dst) HIPCHK(hipMemcpyAsync(dst + dst_off + i0 * per, sl.in(d) + src_off, (size_t)nk * per * sizeof(*dst), hipMemcpyDeviceToHost, c->stream));
+            };
+            down(mean, out->mean, G * S); down(var, out->var, G * S); down(median, out->median, G * S);
+            for (size_t p = 0; p < nq; ++p) down(quant, out->quantile, G * S, p * nib * G * S, p * (size_t)nt * G * S);
+            down(bestv, out->best_value, G); down(count, out->count, G); down(nacc, out->n_accepted, G); down(nex, out->n_exchanged, G);
+            down(nfail, out->n_failed, G); down(bestc, out->best_chain, G);
+            HIPCHK(hipStreamSynchronize(c->stream));   // (the next batch reuses the scratch and the results)
         }
     } catch (const std::string& m) {
         return fail(c, SMM_ERR_HIP, m);

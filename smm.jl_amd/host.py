@@ -553,6 +553,29 @@ def histogram2d(x, pair, bins=10, range=None, window=None, accepted_only=True, s
     return out[0] if j is not None else out
 
 
+def trace(algo, groups=None, window=None, stride=1, state=True, moments=False, probs=(0.025, 0.5, 0.975)):
+    """the population per iteration, reduced across the chains of each group on the device (include/smmhip.h: smm_get_trace) without
+    downloading the history: one OrderedDict per group with iter [nt] (0-based), chains, count / n_accepted / n_exchanged / n_failed /
+    best_value / best_chain [nt], and mean / var / median (series name -> [nt]) and quantile (series name -> [len(probs)][nt]) of every
+    parameter, of "value" and, with moments, of every simulated moment.  window = (t0, t1) (default: the whole run), every stride-th
+    iteration of it; state: the chains' state series (the row last accepted) instead of the rows themselves, as params(c,
+    accepted_only=False) holds them; groups: a group id per chain (-1 = none), by default those of rhat / pooled"""
+    t0, t1 = (0, algo.i) if window is None else (int(window[0]), int(window[1]))
+    g = np.asarray(_default_groups(algo) if groups is None else groups, np.int32)
+    r = algo._ctx.trace(t0, t1, int(stride), "state" if state else "all", moments, g, tuple(float(p) for p in probs))
+    names = list(ps2s_names(algo.m)) + ["value"] + (list(ms_names(algo.m)) if moments else [])
+    out = []
+    for j in _builtins_range(r["n_chains"].shape[0]):
+        d = OrderedDict(iter=r["iter"].copy(), chains=int(r["n_chains"][j]))
+        for f in ("count", "n_accepted", "n_exchanged", "n_failed", "best_value", "best_chain"):
+            d[f] = r[f][:, j].copy()
+        for f in ("mean", "var", "median"):
+            d[f] = OrderedDict((k, r[f][:, j, i].copy()) for i, k in enumerate(names))
+        d["quantile"] = OrderedDict((k, r["quantile"][:, :, j, i].copy()) for i, k in enumerate(names))
+        out.append(d)
+    return out
+
+
 def summary(x):
     """summary(c::BGPChain) AlgoBGP.jl:197-206 / summary(m::MAlgoBGP) :541-550"""
     if isinstance(x, MAlgoBGP):
