@@ -239,8 +239,35 @@ class BGPContext:
         return value, simM, status
 
     # --- read back --------------------------------------------------------------------
+    def _t1(self, t1):
+        """a window's end: by default the iterations completed so far"""
+        return self.state().iter if t1 is None else t1
+
+    def _groups(self, who, groups, n_groups=None, default=1):
+        """who's groups argument as the ABI takes it: (the int32 vector the pointer points into, or None; the pointer, or None; the number
+        of groups: n_groups, else groups.max() + 1, else `default` without a vector)"""
+        g = None if groups is None else np.ascontiguousarray(groups, np.int32)
+        if g is not None and g.shape != (self.N,):
+            raise ValueError("%s: groups needs one entry per chain, got shape %s" % (who, g.shape))
+        ng = (default if g is None else (int(g.max()) + 1 if len(g) else 0)) if n_groups is None else int(n_groups)
+        return g, (g.ctypes.data_as(A.c_int32_p) if g is not None else None), ng
+
+    _SELECT = {"all": 0, "accepted": 1, "state": 2}
+
+    def _select(self, select):
+        return self._SELECT[select] if isinstance(select, str) else int(select)
+
+    @staticmethod
+    def _out(struct_t, arrays, skip=()):
+        """a call's out-struct pointing at the arrays of its fields' names, but for the fields to skip (left NULL: not asked for)"""
+        s = struct_t()
+        for f, t in struct_t._fields_:
+            if f in arrays and f not in skip:
+                setattr(s, f, arrays[f].ctypes.data_as(t))
+        return s
+
     def history(self, t0=0, t1=None):
-        t1 = self.state().iter if t1 is None else t1
+        t1 = self._t1(t1)
         hb = A.HistoryBuffers(t1 - t0, self.N, self.np, self.nm)
         hs = hb.struct()
         self._check(self._fn("get_history")(self._ctx, t0, t1, C.byref(hs)))
@@ -250,16 +277,13 @@ class BGPContext:
         """summaries of every local chain over iterations [t0, t1), reduced on the device (smm_get_chain_stats, include/smmhip.h):
         a dict of numpy arrays count [N], mean / median [np][N], quantile [len(probs)][np][N], best_value, best_iter, n_exchanged,
         most_exchanged_with [N].  accepted_only: the accepted draws only, as params(c)"""
-        t1 = self.state().iter if t1 is None else t1
+        t1 = self._t1(t1)
         p = A.f64(probs).reshape(-1)
         N, np_ = self.N, self.np
         r = dict(count=np.empty(N, np.int32), mean=np.empty((np_, N)), median=np.empty((np_, N)), quantile=np.empty((len(p), np_, N)),
                  best_value=np.empty(N), best_iter=np.empty(N, np.int32), n_exchanged=np.empty(N, np.int32),
                  most_exchanged_with=np.empty(N, np.int32))
-        s = A.smm_chain_stats_t()
-        for f, t in A.smm_chain_stats_t._fields_:
-            if f != "quantile" or len(p):
-                setattr(s, f, r[f].ctypes.data_as(t))
+        s = self._out(A.smm_chain_stats_t, r, () if len(p) else ("quantile",))
         self._check(self._fn("get_chain_stats")(self._ctx, int(t0), int(t1), int(bool(accepted_only)), A.dptr(p) if len(p) else None,
                                                 len(p), C.byref(s)))
         return r
@@ -267,7 +291,7 @@ class BGPContext:
     def chain_cov(self, t0=0, t1=None, accepted_only=True, unit_space=False):
         """covariance of every local chain's selected draws over iterations [t0, t1), on the device (smm_get_chain_cov,
         include/smmhip.h): (count [N], mean [np][N], cov [np][np][N]); unit_space: the draws mapped to [0, 1] first"""
-        t1 = self.state().iter if t1 is None else t1
+        t1 = self._t1(t1)
         N, np_ = self.N, self.np
         count, mean, cov = np.empty(N, np.int32), np.empty((np_, N)), np.empty((np_, np_, N))
         self._check(self._fn("get_chain_cov")(self._ctx, int(t0), int(t1), int(bool(accepted_only)), int(bool(unit_space)),
@@ -279,21 +303,14 @@ class BGPContext:
         include/smmhip.h): a dict of numpy arrays accept_rate [N], ess / status [S][N] (S = np + 1: the parameters, then the objective
         value), acf [n_acf][S][N] and, with groups (an int per chain, -1 = none), rhat [n_groups][S], n_groups = groups.max() + 1.
         max_lag defaults to t1 - t0 - 1: the whole of Geyer's sequence, the device stopping where it is truncated"""
-        t1 = self.state().iter if t1 is None else t1
+        t1 = self._t1(t1)
         max_lag = t1 - t0 - 1 if max_lag is None else max_lag
         N, S = self.N, self.np + 1
-        g = None if groups is None else np.ascontiguousarray(groups, np.int32)
-        if g is not None and g.shape != (N,):
-            raise ValueError("chain_diag: groups needs one entry per chain, got shape %s" % (g.shape,))
-        ng = int(g.max()) + 1 if g is not None and len(g) else 0
+        g, gp, ng = self._groups("chain_diag", groups, default=0)
         r = dict(accept_rate=np.empty(N), ess=np.empty((S, N)), status=np.empty((S, N), np.int32), acf=np.empty((max(int(n_acf), 0), S, N)),
                  rhat=np.empty((max(ng, 0), S)))
-        s = A.smm_chain_diag_t()
-        for f, t in A.smm_chain_diag_t._fields_:
-            if (f != "acf" or n_acf > 0) and (f != "rhat" or ng > 0):
-                setattr(s, f, r[f].ctypes.data_as(t))
-        self._check(self._fn("get_chain_diag")(self._ctx, int(t0), int(t1), int(max_lag), int(n_acf),
-                                               g.ctypes.data_as(A.c_int32_p) if g is not None else None, ng, C.byref(s)))
+        s = self._out(A.smm_chain_diag_t, r, (() if n_acf > 0 else ("acf",)) + (() if ng > 0 else ("rhat",)))
+        self._check(self._fn("get_chain_diag")(self._ctx, int(t0), int(t1), int(max_lag), int(n_acf), gp, ng, C.byref(s)))
         return r
 
     def group_stats(self, t0=0, t1=None, accepted_only=True, groups=None, probs=(), n_groups=None):
@@ -301,25 +318,16 @@ class BGPContext:
         include/smmhip.h): a dict of numpy arrays count / n_chains [n_groups], mean / median [n_groups][np], quantile
         [len(probs)][n_groups][np], cov [n_groups][np][np].  groups: an int per chain (-1 = none), n_groups by default groups.max() + 1;
         None: every local chain in one group"""
-        t1 = self.state().iter if t1 is None else t1
+        t1 = self._t1(t1)
         p = A.f64(probs).reshape(-1)
-        N, np_ = self.N, self.np
-        g = None if groups is None else np.ascontiguousarray(groups, np.int32)
-        if g is not None and g.shape != (N,):
-            raise ValueError("group_stats: groups needs one entry per chain, got shape %s" % (g.shape,))
-        ng = (1 if g is None else (int(g.max()) + 1 if len(g) else 0)) if n_groups is None else int(n_groups)
+        np_ = self.np
+        g, gp, ng = self._groups("group_stats", groups, n_groups)
         r = dict(count=np.empty(ng, np.int64), n_chains=np.empty(ng, np.int32), mean=np.empty((ng, np_)), median=np.empty((ng, np_)),
                  quantile=np.empty((len(p), ng, np_)), cov=np.empty((ng, np_, np_)))
-        s = A.smm_group_stats_t()
-        for f, t in A.smm_group_stats_t._fields_:
-            if f != "quantile" or len(p):
-                setattr(s, f, r[f].ctypes.data_as(t))
-        self._check(self._fn("get_group_stats")(self._ctx, int(t0), int(t1), int(bool(accepted_only)),
-                                                g.ctypes.data_as(A.c_int32_p) if g is not None else None, ng,
+        s = self._out(A.smm_group_stats_t, r, () if len(p) else ("quantile",))
+        self._check(self._fn("get_group_stats")(self._ctx, int(t0), int(t1), int(bool(accepted_only)), gp, ng,
                                                 A.dptr(p) if len(p) else None, len(p), C.byref(s)))
         return r
-
-    _SELECT = {"all": 0, "accepted": 1, "state": 2}
 
     def histogram(self, t0=0, t1=None, select="accepted", groups=None, bins=10, range=None, pairs=(), bins2=None, n_groups=None):
         """histograms of the draws of groups of local chains over iterations [t0, t1), counted on the device (smm_get_histogram,
@@ -328,13 +336,10 @@ class BGPContext:
         select: "all", "accepted" (params(c, accepted_only)) or "state" (the chain's state series); groups: an int per chain (-1 = none),
         n_groups by default groups.max() + 1, None: every local chain in one group; range: [np][2] or a dict parameter index -> (lo, hi)
         naming every parameter, None: each group's own min and max; pairs: (j, k) parameter indexes; bins2 defaults to bins"""
-        t1 = self.state().iter if t1 is None else t1
-        N, np_ = self.N, self.np
-        sel = self._SELECT[select] if isinstance(select, str) else int(select)
-        g = None if groups is None else np.ascontiguousarray(groups, np.int32)
-        if g is not None and g.shape != (N,):
-            raise ValueError("histogram: groups needs one entry per chain, got shape %s" % (g.shape,))
-        ng = (1 if g is None else (int(g.max()) + 1 if len(g) else 0)) if n_groups is None else int(n_groups)
+        t1 = self._t1(t1)
+        np_ = self.np
+        sel = self._select(select)
+        g, gp, ng = self._groups("histogram", groups, n_groups)
         if isinstance(range, dict):
             if sorted(range) != list(_builtins.range(np_)):
                 raise ValueError("histogram: a range dict names every parameter index 0 .. np-1")
@@ -347,12 +352,8 @@ class BGPContext:
                  edges=np.empty((ng, np_, max(b, 0) + 1)), hist=np.empty((ng, np_, max(b, 0)), np.int64))
         if npr:
             r.update(edges2=np.empty((ng, np_, max(b2, 0) + 1)), hist2=np.empty((ng, npr, max(b2, 0), max(b2, 0)), np.int64))
-        s = A.smm_histogram_t()
-        for f, t in A.smm_histogram_t._fields_:
-            if f in r:
-                setattr(s, f, r[f].ctypes.data_as(t))
-        self._check(self._fn("get_histogram")(self._ctx, int(t0), int(t1), sel, g.ctypes.data_as(A.c_int32_p) if g is not None else None,
-                                              ng, b, A.dptr(rg) if rg is not None else None,
+        s = self._out(A.smm_histogram_t, r)
+        self._check(self._fn("get_histogram")(self._ctx, int(t0), int(t1), sel, gp, ng, b, A.dptr(rg) if rg is not None else None,
                                               pr.ctypes.data_as(A.c_int32_p) if npr else None, npr, b2, C.byref(s)))
         return r
 
@@ -363,14 +364,10 @@ class BGPContext:
         the S series are the parameters, the objective value and, with moments, the simulated moments.  select: "all", "accepted" or
         "state" (the chain's state series); groups: an int per chain (-1 = none), n_groups by default groups.max() + 1, None: every
         local chain in one group"""
-        t1 = self.state().iter if t1 is None else t1
+        t1 = self._t1(t1)
         p = A.f64(probs).reshape(-1)
-        N = self.N
-        sel = self._SELECT[select] if isinstance(select, str) else int(select)
-        g = None if groups is None else np.ascontiguousarray(groups, np.int32)
-        if g is not None and g.shape != (N,):
-            raise ValueError("trace: groups needs one entry per chain, got shape %s" % (g.shape,))
-        ng = (1 if g is None else (int(g.max()) + 1 if len(g) else 0)) if n_groups is None else int(n_groups)
+        sel = self._select(select)
+        g, gp, ng = self._groups("trace", groups, n_groups)
         st = int(stride)
         nt = max(0, -(-(int(t1) - int(t0)) // st)) if st >= 1 else 0
         G, S = max(ng, 0), self.np + 1 + (self.nm if moments else 0)
@@ -378,13 +375,9 @@ class BGPContext:
                  n_accepted=np.empty((nt, G), np.int32), n_exchanged=np.empty((nt, G), np.int32), n_failed=np.empty((nt, G), np.int32),
                  mean=np.empty((nt, G, S)), var=np.empty((nt, G, S)), median=np.empty((nt, G, S)), quantile=np.empty((len(p), nt, G, S)),
                  best_value=np.empty((nt, G)), best_chain=np.empty((nt, G), np.int32))
-        s = A.smm_trace_t()
-        for f, t in A.smm_trace_t._fields_:
-            if f != "quantile" or len(p):
-                setattr(s, f, r[f].ctypes.data_as(t))
-        self._check(self._fn("get_trace")(self._ctx, int(t0), int(t1), st, sel, int(bool(moments)),
-                                          g.ctypes.data_as(A.c_int32_p) if g is not None else None, ng, A.dptr(p) if len(p) else None, len(p),
-                                          C.byref(s)))
+        s = self._out(A.smm_trace_t, r, () if len(p) else ("quantile",))
+        self._check(self._fn("get_trace")(self._ctx, int(t0), int(t1), st, sel, int(bool(moments)), gp, ng,
+                                          A.dptr(p) if len(p) else None, len(p), C.byref(s)))
         return r
 
     def _proposal_shape(self):

@@ -1,0 +1,774 @@
+// the host side of the history reducers — part of libsmmhip (included once by smmhip.hip, behind its host helpers; hiprtc never sees it).
+// The family: smm_get_chain_stats, smm_get_chain_cov, smm_get_proposal / _set_ / _adapt_, smm_get_chain_diag, smm_get_group_stats,
+// smm_get_histogram, smm_get_trace (kernels: smm_stats.hpp, smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_hist.hpp, smm_trace.hpp).
+// What they share is stated here once: the frame of a call (reducer_call), the checks of the arguments they have in common (check_groups,
+// check_probs, check_select), the prelude and the window behind them (settled_window: reader_prelude and check_window of smmhip.hip), the
+// members of the groups (Groups), one result buffer per context (reducer_result, laid out by Carve / Slice, copied by up / down), one
+// scratch per context for the compacted columns (reducer_scratch, chain_batches) and the cap on the scratch and on a batch of results
+// (reducer_batch_cap: REDUCER_BATCH_CAP, or what the test seam SMMHIP_STATS_SCRATCH gives, so that small cases reach the batched paths).
+// A call's own batch plan, result layout, launches, empty-window branch and host-side finish stay in the call.
+#pragma once
+
+namespace {
+
+// the frame of an entry point: body(c) returns SMM_OK or what fail() returned
+template <class Body>
+int reducer_call(void* ctx, bool args_given, Body body) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !args_given) return SMM_ERR_INVALID_ARG;
+    try {
+        return body(c);
+    } catch (const std::string& m) {
+        return fail(c, SMM_ERR_HIP, m);
+    }
+}
+
+// the prelude, then the window: what a call over a window does once its arguments have passed
+int settled_window(Ctx* c, int t0, int t1) { reader_prelude(c); return check_window(c, t0, t1); }
+
+// the group vector [N] (-1: in no group) and its count; without a vector GROUPS_OPTIONAL is no group at all (the diagnostics: no R-hat),
+// GROUPS_DEFAULT_ONE every chain in one group
+enum GroupNull { GROUPS_OPTIONAL, GROUPS_DEFAULT_ONE };
+int check_groups(Ctx* c, const int32_t* group, int n_groups, GroupNull null_is) {
+    if (null_is == GROUPS_OPTIONAL) {
+        if (n_groups < 0 || (n_groups > 0 && !group)) return fail(c, SMM_ERR_INVALID_ARG, "n_groups < 0, or group NULL with n_groups > 0");
+    } else if (n_groups < 0 || (!group && n_groups != 1))
+        return fail(c, SMM_ERR_INVALID_ARG, "n_groups < 0, or group NULL with n_groups != 1");
+    for (int i = 0; group && i < c->P.N; ++i)
+        if (group[i] < -1 || group[i] >= n_groups) return fail(c, SMM_ERR_INVALID_ARG, "a group id outside [-1, n_groups)");
+    return SMM_OK;
+}
+
+int check_probs(Ctx* c, const double* probs, int n_probs, bool wants_quantile) {
+    if (n_probs < 0 || (n_probs > 0 && !probs)) return fail(c, SMM_ERR_INVALID_ARG, "n_probs < 0, or probs NULL with n_probs > 0");
+    if (wants_quantile && n_probs == 0) return fail(c, SMM_ERR_INVALID_ARG, "quantile requested without probs");
+    for (int p = 0; p < n_probs; ++p)
+        if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) return fail(c, SMM_ERR_INVALID_ARG, "probs must lie in [0, 1]");
+    return SMM_OK;
+}
+
+int check_select(Ctx* c, int select) {
+    return select < 0 || select > 2 ? fail(c, SMM_ERR_INVALID_ARG, "select must be 0 (all), 1 (accepted) or 2 (state)") : SMM_OK;
+}
+
+// the groups of a checked group vector (NULL: every chain in group 0)
+struct Groups {
+    std::vector<int> gid;          // [N] each local chain's group, -1: none
+    std::vector<int> n_chains;     // [G] members per group
+    std::vector<int> gmem0, mem;   // group g's members are mem[gmem0[g] .. gmem0[g + 1]), in ascending local index
+    int M = 0, longest = 0;        // members of all groups, and of the largest
+};
+Groups group_members(const int32_t* group, size_t G, size_t N) {
+    Groups g;
+    g.gid.assign(N, 0);
+    if (group) std::copy(group, group + N, g.gid.begin());
+    g.n_chains.assign(G, 0);
+    for (size_t i = 0; i < N; ++i)
+        if (g.gid[i] >= 0) ++g.n_chains[g.gid[i]];
+    g.gmem0.assign(G + 1, 0);
+    for (size_t k = 0; k < G; ++k) { g.gmem0[k + 1] = g.gmem0[k] + g.n_chains[k]; g.longest = std::max(g.longest, g.n_chains[k]); }
+    g.M = g.gmem0[G];
+    g.mem.resize(g.M);
+    std::vector<int> at(g.gmem0.begin(), g.gmem0.end() - 1);
+    for (size_t i = 0; i < N; ++i)
+        if (g.gid[i] >= 0) g.mem[at[g.gid[i]]++] = (int)i;
+    return g;
+}
+
+// the results of a reducer call on the device, one buffer grown to the largest call's
+void* reducer_result(Ctx* c, size_t bytes) {
+    if (bytes > c->red_res_bytes) {
+        if (c->red_res) { HIPCHK(hipFree(c->red_res)); c->red_res = nullptr; c->red_res_bytes = 0; }
+        HIPCHK(hipMalloc(&c->red_res, bytes));
+        c->red_res_bytes = bytes;
+    }
+    return c->red_res;
+}
+
+// a reducer's result layout, stated once: consecutive typed slices, placed in the device buffer and in its host copy alike
+template <class T>
+struct Slice {
+    size_t off;
+    T* in(void* base) const { return (T*)((char*)base + off); }
+    Slice at(size_t n) const { return Slice{off + n * sizeof(T)}; }   // the slice from its n-th element on
+};
+struct Carve {
+    size_t bytes = 0;
+    template <class T>
+    Slice<T> take(size_t n) { const Slice<T> s{bytes}; bytes += n * sizeof(T); return s; }
+};
+
+// count elements of a slice of the device buffer d from / to the host, on the context's stream; nothing where there is nothing to copy
+template <class T>
+void up(Ctx* c, void* d, Slice<T> sl, const void* src, size_t count) {
+    if (src && count) HIPCHK(hipMemcpyAsync(sl.in(d), src, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
+}
+template <class T>
+void up(Ctx* c, void* d, Slice<T> sl, const std::vector<T>& v) { up(c, d, sl, v.data(), v.size()); }
+template <class T>
+void down(Ctx* c, void* d, Slice<T> sl, void* dst, size_t count) {
+    if (dst && count) HIPCHK(hipMemcpyAsync(dst, sl.in(d), count * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+}
+
+// bytes of the scratch and of a batch of results (the test seam SMMHIP_STATS_SCRATCH replaces the cap)
+constexpr size_t REDUCER_BATCH_CAP = (size_t)256 << 20;
+size_t reducer_batch_cap(const Ctx* c) { return c->H.stats_scratch ? c->H.stats_scratch : REDUCER_BATCH_CAP; }
+
+// the compacted columns of every chain for the context's whole capacity, at most reducer_batch_cap (but always one parameter column +
+// one partner column of maxiter draws: 12 x maxiter bytes)
+size_t chain_stats_scratch_bytes(const Ctx* c) {
+    const KParams& P = c->P;
+    const size_t T = (size_t)P.T, all = (size_t)P.N * T * (8 * (size_t)P.np + 4);
+    return std::min(all, std::max(reducer_batch_cap(c), 12 * T));
+}
+
+// the reducers' shared scratch st_scr: chain_stats_scratch_bytes, but never less than one_chain_bytes (one chain's columns of the whole
+// capacity, for a reducer that takes them all at once; 0: no minimum).  One that is smaller is freed and allocated anew.
+void reducer_scratch(Ctx* c, size_t one_chain_bytes) {
+    if (c->st_scr && c->st_scr_bytes < one_chain_bytes) { HIPCHK(hipFree(c->st_scr)); c->st_scr = nullptr; c->st_scr_bytes = 0; }
+    if (!c->st_scr) {
+        c->st_scr_bytes = std::max(chain_stats_scratch_bytes(c), one_chain_bytes);
+        HIPCHK(hipMalloc(&c->st_scr, c->st_scr_bytes));
+    }
+}
+
+// the local chains in batches of as many as the scratch holds at per_chain bytes each: body(c0, nb)
+template <class Body>
+void chain_batches(Ctx* c, size_t per_chain, Body body) {
+    const int N = c->P.N, Nb = (int)std::min((size_t)N, c->st_scr_bytes / per_chain);
+    for (int c0 = 0; c0 < N; c0 += Nb) body(c0, std::min(Nb, N - c0));
+}
+
+// a reducer kernel onto the context's stream, its launch checked
+template <class Kern, class... Args>
+void launch_checked(Ctx* c, Kern kern, dim3 grid, dim3 block, size_t smem, const Args&... args) {
+    launch(c, kern, grid, block, smem, args...);
+    HIPCHK(hipGetLastError());
+}
+
+// the keys a workgroup sorts in LDS for a column of n draws: the power of two at or above n (and 2), at most STATS_LDS_N
+int sort_lds_n(int n) { return std::min(STATS_LDS_N, 1 << (int)ceil(log2((double)std::max(n, 2)))); }
+
+// the reducers' dynamic LDS (smm_ctx_create): a chunk of draws (k_stats_column, k_cov_center, k_diag_acov, k_group_*, k_trace_column),
+// the partner ids of a pass (k_stats_mode), the counters and edges of a batch of parameters or pairs (k_hist_count, k_hist_pairs)
+void reducer_kernel_attributes() {
+    HIPCHK(hipFuncSetAttribute((const void*)k_stats_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_cov_center, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_diag_acov, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_stats_mode, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_MODE_BINS * 4));
+    HIPCHK(hipFuncSetAttribute((const void*)k_group_chunk_sum, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_group_small, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_hist_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIST_LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute((const void*)k_hist_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIST_LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute((const void*)k_trace_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+}
+
+}  // namespace
+
+extern "C" {
+
+// mean / median / CI / best / summary of AlgoBGP.jl:117-206 for every local chain, reduced where the history lives (smm_stats.hpp)
+int smm_get_chain_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, const double* probs, int32_t n_probs,
+                        smm_chain_stats_t* out) {
+    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        if (const int rc = check_probs(c, probs, n_probs, out->quantile != nullptr)) return rc;
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t N = P.N, np = P.np, nq = n_probs;
+        const int n = t1 - t0;
+        Carve R;   // the doubles first (NaN for an empty window), then the ints (0)
+        const auto bestv = R.take<double>(N), dprobs = R.take<double>(nq), mean = R.take<double>(np * N), median = R.take<double>(np * N),
+                   quant = R.take<double>(nq * np * N);
+        const auto count = R.take<int>(N), nex = R.take<int>(N), besti = R.take<int>(N), most = R.take<int>(N);
+        void* d = reducer_result(c, R.bytes);
+        std::vector<char> hres(R.bytes);
+        if (n == 0) {   // nothing selected, nothing to find
+            std::fill(bestv.in(hres.data()), (double*)count.in(hres.data()), NAN);
+            memset(count.in(hres.data()), 0, R.bytes - count.off);
+        } else {
+            reducer_scratch(c, 0);
+            up(c, d, dprobs, probs, nq);
+            const bool cols = out->mean || out->median || out->quantile;
+            auto per_chain = [&](size_t kb) { return (size_t)n * (8 * kb + 4); };
+            size_t kb = cols ? np : 0;
+            while (kb > 1 && per_chain(kb) > c->st_scr_bytes) kb = (kb + 1) / 2;
+            const int lds_n = sort_lds_n(n);
+            const int bins = std::min(c->H.stats_mode_bins, std::max(P.Ng, 64));   // (STATS_MODE_BINS but for the test seam)
+            for (size_t k0 = 0; k0 < std::max(np, (size_t)1); k0 += std::max(kb, (size_t)1)) {
+                const int kbb = (int)std::min(kb, np - k0);
+                const int first = k0 == 0;
+                if (!first && !cols) break;
+                chain_batches(c, per_chain(kb), [&](int c0, int nb) {
+                    double* col = (double*)c->st_scr;
+                    int* pcol = (int*)(col + (size_t)kbb * nb * n);
+                    launch_checked(c, k_stats_gather, dim3(nb), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n,
+                                   (int)(accepted_only != 0), c0, nb, (int)k0, kbb, first, col, pcol, count.in(d), nex.in(d), bestv.in(d),
+                                   besti.in(d));
+                    if (kbb > 0)
+                        launch_checked(c, k_stats_column, dim3(nb, kbb), dim3(STATS_WG), (size_t)lds_n * 8, (const double*)col, n, (int)N, c0,
+                                       nb, (int)k0, (const int*)count.in(d), (const double*)dprobs.in(d), (int)nq, (int)np, mean.in(d),
+                                       median.in(d), quant.in(d));
+                    if (first)
+                        launch_checked(c, k_stats_mode, dim3(nb), dim3(STATS_WG), (size_t)bins * 4, (const int*)pcol, n, c0, bins,
+                                       (const int*)nex.in(d), most.in(d));
+                });
+            }
+            HIPCHK(hipMemcpyAsync(hres.data(), d, R.bytes, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+        void* h = hres.data();
+        if (out->best_value) memcpy(out->best_value, bestv.in(h), N * 8);
+        if (out->mean) memcpy(out->mean, mean.in(h), np * N * 8);
+        if (out->median) memcpy(out->median, median.in(h), np * N * 8);
+        if (out->quantile) memcpy(out->quantile, quant.in(h), nq * np * N * 8);
+        if (out->count) memcpy(out->count, count.in(h), N * 4);
+        if (out->n_exchanged) memcpy(out->n_exchanged, nex.in(h), N * 4);
+        if (out->best_iter) memcpy(out->best_iter, besti.in(h), N * 4);
+        if (out->most_exchanged_with) memcpy(out->most_exchanged_with, most.in(h), N * 4);
+        return SMM_OK;
+    });
+}
+
+// --- covariances of the chains' draws, and the proposal factor between steps (smm_cov.hpp) ---------------------------------------------
+
+// the covariance of every local chain's selected draws over [t0, t1) on the device: count [N], mean [np][N], cov [np][np][N] in the
+// reducers' result buffer (status [N] behind them, for smm_adapt_proposal).  The caller has run the prelude and checked the window.
+struct CovRes { int* count; double* mean; double* cov; int* status; };
+static CovRes chain_cov_device(Ctx* c, int t0, int t1, int accepted_only, int unit_space) {
+    const KParams& P = c->P;
+    const size_t N = P.N, np = P.np;
+    const int n = t1 - t0;
+    Carve R;
+    const auto mean = R.take<double>(np * N), cov = R.take<double>(np * np * N), bestv = R.take<double>(N);
+    const auto count = R.take<int>(N), nex = R.take<int>(N), besti = R.take<int>(N), status = R.take<int>(N);
+    void* d = reducer_result(c, R.bytes);
+    const CovRes r{count.in(d), mean.in(d), cov.in(d), status.in(d)};
+    if (n == 0) {   // nothing selected: count 0, mean and cov NaN
+        HIPCHK(hipMemsetAsync(r.count, 0, N * 4, c->stream));
+        std::vector<double> nan((np + np * np) * N, NAN);
+        HIPCHK(hipMemcpyAsync(r.mean, nan.data(), nan.size() * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return r;
+    }
+    reducer_scratch(c, (size_t)P.T * (8 * np + 4));   // every parameter of a chain at once
+    const int lds_n = sort_lds_n(n);
+    const int nt = ((int)np + COV_T - 1) / COV_T, ntiles = nt * (nt + 1) / 2;
+    chain_batches(c, (size_t)n * (8 * np + 4), [&](int c0, int nb) {
+        double* col = (double*)c->st_scr;
+        int* pcol = (int*)(col + np * nb * n);
+        launch_checked(c, k_stats_gather, dim3(nb), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)(accepted_only != 0),
+                       c0, nb, 0, (int)np, 1, col, pcol, r.count, nex.in(d), bestv.in(d), besti.in(d));
+        launch_checked(c, k_cov_center, dim3(nb, np), dim3(STATS_WG), (size_t)lds_n * 8, col, n, (int)N, c0, nb, (int)(unit_space != 0), P.lb,
+                       P.ub, (const int*)r.count, r.mean);
+        launch_checked(c, k_cov_pairs, dim3(nb, ntiles), dim3(COV_WG), 0, (const double*)col, n, (int)N, c0, nb, (int)np, (const int*)r.count,
+                       r.cov, 0);
+    });
+    return r;
+}
+
+int smm_get_chain_cov(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, int32_t unit_space, int32_t* count, double* mean,
+                      double* cov) {
+    return reducer_call(ctx, true, [&](Ctx* c) -> int {
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const size_t N = c->P.N, np = c->P.np;
+        const CovRes r = chain_cov_device(c, t0, t1, accepted_only, unit_space);
+        if (count) HIPCHK(hipMemcpyAsync(count, r.count, N * 4, hipMemcpyDeviceToHost, c->stream));
+        if (mean) HIPCHK(hipMemcpyAsync(mean, r.mean, np * N * 8, hipMemcpyDeviceToHost, c->stream));
+        if (cov) HIPCHK(hipMemcpyAsync(cov, r.cov, np * np * N * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return SMM_OK;
+    });
+}
+
+// doubles of the factor(s) a caller reads or writes: [np][np] shared, [N][np][np] per chain (the local chains' rows)
+static size_t proposal_doubles(const KParams& P) { return (size_t)(P.chol_per_chain ? P.N : 1) * P.np * P.np; }
+static double* proposal_rows(const KParams& P) {
+    return (double*)P.chol_L + (P.chol_per_chain ? (size_t)P.offset * P.np * P.np : 0);
+}
+
+int smm_get_proposal(void* ctx, double* L) {
+    return reducer_call(ctx, L != nullptr, [&](Ctx* c) -> int {
+        const KParams& P = c->P;
+        if (!P.chol_L) return fail(c, SMM_ERR_INVALID_ARG, "the context has no proposal factor: create it with chol_L");
+        HIPCHK(hipSetDevice(c->device));   // (reads the factor as it stands: no prelude)
+        const size_t n = proposal_doubles(P), np = P.np;
+        HIPCHK(hipMemcpyAsync(L, proposal_rows(P), n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (size_t b = 0; b < n; b += np * np)   // (what lies above the diagonal was never read)
+            for (size_t k = 0; k < np; ++k)
+                for (size_t j = k + 1; j < np; ++j) L[b + k * np + j] = 0.0;
+        return SMM_OK;
+    });
+}
+
+// the mutating calls: settled, flushed and synchronised; a hard failure standing on the context is handed to the caller (and marked told)
+static int proposal_prelude(Ctx* c) {
+    reader_prelude(c);
+    (void)check_device_error(c);
+    return c->failed ? told(c) : SMM_OK;
+}
+
+int smm_set_proposal(void* ctx, const double* L) {
+    return reducer_call(ctx, L != nullptr, [&](Ctx* c) -> int {
+        const KParams& P = c->P;
+        if (!P.chol_L) return fail(c, SMM_ERR_INVALID_ARG, "the context has no proposal factor: create it with chol_L");
+        const size_t n = proposal_doubles(P), np = P.np;
+        std::vector<double> h(n);
+        for (size_t b = 0; b < n; b += np * np)
+            for (size_t k = 0; k < np; ++k)
+                for (size_t j = 0; j < np; ++j) {
+                    const double v = j <= k ? L[b + k * np + j] : 0.0;
+                    if (!std::isfinite(v)) return fail(c, SMM_ERR_INVALID_ARG, "smm_set_proposal: a non-finite entry on or below the diagonal");
+                    if (j == k && !(v > 0.0)) return fail(c, SMM_ERR_INVALID_ARG, "smm_set_proposal: a diagonal entry is not > 0");
+                    h[b + k * np + j] = v;
+                }
+        if (const int rc = proposal_prelude(c)) return rc;
+        HIPCHK(hipMemcpyAsync(proposal_rows(P), h.data(), n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return SMM_OK;
+    });
+}
+
+int smm_adapt_proposal(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, int32_t min_draws, int32_t normalize, double ridge,
+                       int32_t* status) {
+    return reducer_call(ctx, true, [&](Ctx* c) -> int {
+        const KParams& P = c->P;
+        if (!P.chol_L) return fail(c, SMM_ERR_INVALID_ARG, "the context has no proposal factor: create it with chol_L (per chain)");
+        if (!P.chol_per_chain)
+            return fail(c, SMM_ERR_INVALID_ARG, "smm_adapt_proposal needs per-chain factors (chol_per_chain = 1): a shared factor has no own history");
+        if (min_draws < 2) return fail(c, SMM_ERR_INVALID_ARG, "min_draws must be >= 2");
+        if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(c, SMM_ERR_INVALID_ARG, "ridge must be finite and >= 0");
+        if (const int rc = proposal_prelude(c)) return rc;   // (a failure standing on the context comes before the window)
+        if (const int rc = check_window(c, t0, t1)) return rc;
+        const size_t N = P.N;
+        const CovRes r = chain_cov_device(c, t0, t1, accepted_only, 1);
+        launch_checked(c, k_cov_chol, dim3(N), dim3(64), 0, (const double*)r.cov, (const int*)r.count, (int)N, P.np, (int)min_draws,
+                       (int)(normalize != 0), ridge, P.chol_per_chain ? P.offset : 0, (double*)P.chol_L, r.status);
+        if (status) HIPCHK(hipMemcpyAsync(status, r.status, N * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return SMM_OK;
+    });
+}
+
+// --- autocorrelation, ESS and split R-hat of the chains (smm_diag.hpp) --------------------------------------------------------------
+
+// the chain-stats sum on the host: numpy's pairwise sum over chunks of 8192 (include/smmhip.h), every operation rounded on its own
+static double host_pw(const double* x, size_t n) {
+    if (n < 8) {
+        double r = 0.0;
+        for (size_t i = 0; i < n; ++i) r = r + x[i];
+        return r;
+    }
+    if (n <= 128) {
+        double r[8];
+        for (int k = 0; k < 8; ++k) r[k] = x[k];
+        const size_t m = n - n % 8;
+        for (size_t i = 8; i < m; i += 8)
+            for (int k = 0; k < 8; ++k) r[k] = r[k] + x[i + k];
+        double s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (size_t i = m; i < n; ++i) s = s + x[i];
+        return s;
+    }
+    size_t n2 = n / 2;
+    n2 -= n2 % 8;
+    const double lf = host_pw(x, n2), rt = host_pw(x + n2, n - n2);
+    return lf + rt;
+}
+static double host_sum(const std::vector<double>& x) {
+    double S = 0.0;
+    for (size_t c = 0; c < x.size(); c += STATS_LDS_N) S = S + host_pw(x.data() + c, std::min((size_t)STATS_LDS_N, x.size() - c));
+    return S;
+}
+
+int smm_get_chain_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32_t n_acf, const int32_t* group, int32_t n_groups,
+                       smm_chain_diag_t* out) {
+    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        // (between check_groups' NULL rule and its ids; ahead of both it decides the same, as no count fails this and the NULL rule)
+        if (out->rhat && n_groups == 0) return fail(c, SMM_ERR_INVALID_ARG, "rhat requested without groups");
+        if (const int rc = check_groups(c, group, n_groups, GROUPS_OPTIONAL)) return rc;
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const size_t N = c->P.N;
+        const int n = t1 - t0;
+        if (n < 4) return fail(c, SMM_ERR_INVALID_ARG, "the window must hold at least 4 iterations");
+        if (max_lag < 1 || max_lag > n - 1) return fail(c, SMM_ERR_INVALID_ARG, "max_lag must lie in [1, t1 - t0 - 1]");
+        if (n_acf < 0 || n_acf > max_lag + 1) return fail(c, SMM_ERR_INVALID_ARG, "n_acf must lie in [0, max_lag + 1]");
+        const KParams& P = c->P;
+        const size_t np = P.np, S = np + 1, SN = S * N, nacf = out->acf ? (size_t)n_acf : 0;
+        const bool halves = out->rhat != nullptr;
+        Carve R;
+        const auto ess = R.take<double>(SN), acf = R.take<double>(nacf * SN), hmu = R.take<double>(2 * SN), hvar = R.take<double>(2 * SN);
+        const auto status = R.take<int>(SN), nacc = R.take<int>(N), noex = R.take<int>(N);
+        void* d = reducer_result(c, R.bytes);
+        reducer_scratch(c, (size_t)P.T * 8 * S);   // the S columns of a chain at once
+        const int lds_n = std::min(STATS_LDS_N, n);
+        chain_batches(c, (size_t)n * 8 * S, [&](int c0, int nb) {
+            double* col = (double*)c->st_scr;
+            launch_checked(c, k_diag_gather, dim3(nb), dim3(DIAG_WG), 0, (const double*)P.hrec, (int)N, P.HW, (int)np, t0, n, c0, nb, col,
+                           nacc.in(d), noex.in(d));
+            launch_checked(c, k_diag_acov, dim3(nb, S), dim3(DIAG_WG), (size_t)lds_n * 8, col, n, (int)N, c0, nb, (int)S, (int)max_lag,
+                           (int)nacf, (int)halves, ess.in(d), status.in(d), nacf ? acf.in(d) : nullptr, hmu.in(d), hvar.in(d));
+        });
+        std::vector<char> hres(R.bytes);
+        HIPCHK(hipMemcpyAsync(hres.data(), d, R.bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        void* h = hres.data();
+        const int* hs = status.in(h);
+        if (out->accept_rate)
+            for (size_t i = 0; i < N; ++i) out->accept_rate[i] = (double)nacc.in(h)[i] / (double)noex.in(h)[i];
+        if (out->ess) memcpy(out->ess, ess.in(h), SN * 8);
+        if (out->status) memcpy(out->status, hs, SN * 4);
+        if (out->acf) memcpy(out->acf, acf.in(h), nacf * SN * 8);
+        if (out->rhat) {   // split R-hat of each group and series, the members in ascending local index (include/smmhip.h)
+            const double* hm = hmu.in(h);
+            const double* hv = hvar.in(h);
+            const int hl = n / 2;
+            std::vector<double> mus, vars, e;
+            for (int g = 0; g < n_groups; ++g)
+                for (size_t s = 0; s < S; ++s) {
+                    mus.clear(); vars.clear();
+                    bool bad = false;
+                    for (size_t i = 0; i < N; ++i) {
+                        if (group[i] != g) continue;
+                        bad |= hs[s * N + i] == 3;
+                        for (int hf = 0; hf < 2; ++hf) {
+                            mus.push_back(hm[hf * SN + s * N + i]);
+                            vars.push_back(hv[hf * SN + s * N + i]);
+                        }
+                    }
+                    double r = NAN;
+                    if (!mus.empty() && !bad) {
+                        const double k2 = (double)mus.size();
+                        const double W = host_sum(vars) / k2, mm = host_sum(mus) / k2;
+                        e.resize(mus.size());
+                        for (size_t q = 0; q < mus.size(); ++q) { const double dv = mus[q] - mm; e[q] = dv * dv; }
+                        const double v = host_sum(e) / (k2 - 1.0);
+                        const double vp = ((hl - 1.0) / hl) * W + v;
+                        r = sqrt(vp / W);
+                    }
+                    out->rhat[(size_t)g * S + s] = r;
+                }
+        }
+        return SMM_OK;
+    });
+}
+
+// --- pooled summaries of groups of chains (smm_group.hpp) -------------------------------------------------------------------------------
+
+int smm_get_group_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, const int32_t* group, int32_t n_groups,
+                        const double* probs, int32_t n_probs, smm_group_stats_t* out) {
+    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
+        if (const int rc = check_probs(c, probs, n_probs, out->quantile != nullptr)) return rc;
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t N = P.N, np = P.np, G = n_groups, nq = out->quantile ? n_probs : 0;
+        const int n = t1 - t0;
+        const bool med = out->median != nullptr, ord = med || nq > 0, cov = out->cov != nullptr, cols = out->mean || ord || cov;
+        // the members' counts (k_group_gather's counting form), then the plan on the host: the pooled offsets and the chunks
+        const Groups grp = group_members(group, G, N);
+        const std::vector<int>& gid = grp.gid;
+        std::vector<int> cnt(N);
+        DevBuf<int> dci(2 * N);
+        HIPCHK(hipMemcpyAsync(dci.p, gid.data(), N * 4, hipMemcpyHostToDevice, c->stream));
+        launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)(accepted_only != 0),
+                       (const int*)dci.p, (const long long*)nullptr, (const int*)nullptr, 0, 0, 0ll, 0, 0, (const double*)nullptr, (int)np,
+                       (double*)nullptr, dci.p + N, 1);
+        HIPCHK(hipMemcpyAsync(cnt.data(), dci.p + N, N * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        std::vector<long long> gm(G, 0), G0(G + 1, 0), off(N, 0), roff(N, 0);
+        std::vector<int> gch0(G + 1, 0), cch0(N, 0);
+        for (size_t i = 0; i < N; ++i)
+            if (gid[i] >= 0) { roff[i] = gm[gid[i]]; gm[gid[i]] += cnt[i]; }
+        std::vector<long long> cst;
+        std::vector<int> clen;
+        for (size_t g = 0; g < G; ++g) {
+            G0[g + 1] = G0[g] + gm[g];
+            for (long long q = 0; q < gm[g]; q += STATS_LDS_N) { cst.push_back(G0[g] + q); clen.push_back((int)std::min<long long>(STATS_LDS_N, gm[g] - q)); }
+            gch0[g + 1] = (int)cst.size();
+        }
+        for (size_t i = 0; i < N; ++i)
+            if (gid[i] >= 0) { off[i] = G0[gid[i]] + roff[i]; cch0[i] = gch0[gid[i]]; }
+        const long long Mtot = G0[G];
+        const int NC = (int)cst.size();
+        // the order statistics: short columns sorted in LDS, the others selected grid-wide at ranks R per column (rk: -1 = unused)
+        std::vector<int> sgrp, wgrp;
+        long long wmax = 0;
+        for (size_t g = 0; g < G; ++g)
+            if (gm[g] < c->H.group_wide_min) sgrp.push_back((int)g);
+            else { wgrp.push_back((int)g); wmax = std::max(wmax, gm[g]); }
+        const int R = ord ? (med ? 2 : 0) + 2 * (int)nq : 0;
+        std::vector<long long> rk(wgrp.size() * R, -1);
+        for (size_t wi = 0; wi < wgrp.size() && R; ++wi) {   // stats_quantile's and the median's indexes
+            const long long m = gm[wgrp[wi]];
+            long long* r = rk.data() + wi * R;
+            if (med) { r[0] = (m & 1) ? m / 2 : m / 2 - 1; r[1] = (m & 1) ? -1 : m / 2; r += 2; }
+            for (size_t p = 0; p < nq; ++p, r += 2) {
+                const double h = (double)(m - 1) * probs[p];
+                if (h >= (double)(m - 1)) r[0] = m - 1;
+                else { r[0] = (long long)floor(h); r[1] = r[0] + 1; }
+            }
+        }
+        if (Mtot > 0 && cols) reducer_scratch(c, std::max(N * (size_t)P.T * 8, cov ? np * STATS_LDS_N * 8 : 0));
+        const size_t kb = Mtot > 0 && cols ? std::min(np, c->st_scr_bytes / ((size_t)Mtot * 8)) : 0;
+        const size_t nwc = wgrp.size() * kb;   // long columns of a parameter batch, selected WB at a time
+        const int WB = R ? (int)std::min(nwc, std::max((size_t)1, GROUP_HIST_CAP / ((size_t)R * GROUP_BINS * 8))) : 0;
+        Carve Rv;   // 8-byte slices first
+        const auto mean = Rv.take<double>(G * np), median = Rv.take<double>(G * np), quant = Rv.take<double>(nq * G * np),
+                   covo = Rv.take<double>(cov ? G * np * np : 0), dprobs = Rv.take<double>(nq), csum = Rv.take<double>(kb * NC),
+                   csum2 = Rv.take<double>(cov ? np * np * NC : 0);
+        const auto doff = Rv.take<long long>(2 * N), dG0 = Rv.take<long long>(G + 1), dgm = Rv.take<long long>(G),
+                   dcst = Rv.take<long long>(NC), drk = Rv.take<long long>(rk.size()), rem = Rv.take<long long>(nwc * R);
+        const auto pre = Rv.take<unsigned long long>(nwc * R), ghist = Rv.take<unsigned long long>((size_t)WB * R * GROUP_BINS);
+        const auto dcch0 = Rv.take<int>(N), dgch0 = Rv.take<int>(G + 1), dclen = Rv.take<int>(NC), cnan = Rv.take<int>(kb * NC),
+                   gnan = Rv.take<int>(G * np), dsg = Rv.take<int>(sgrp.size()), dwg = Rv.take<int>(wgrp.size());
+        void* d = reducer_result(c, Rv.bytes);
+        std::vector<long long> offs(off);
+        offs.insert(offs.end(), roff.begin(), roff.end());
+        up(c, d, doff, offs); up(c, d, dG0, G0); up(c, d, dgm, gm); up(c, d, dcst, cst); up(c, d, drk, rk);
+        up(c, d, dcch0, cch0); up(c, d, dgch0, gch0); up(c, d, dclen, clen); up(c, d, dsg, sgrp); up(c, d, dwg, wgrp);
+        up(c, d, dprobs, probs, nq);
+        const int* dgid = dci.p;
+        const int* dcnt = dci.p + N;
+        std::vector<long long> remh(nwc * R);
+        if (kb > 0) {
+            double* col = (double*)c->st_scr;
+            const int B = (int)std::min<long long>(1024, std::max<long long>(1, (wmax + STATS_WG * 16 - 1) / (STATS_WG * 16)));
+            for (size_t k0 = 0; k0 < np; k0 += kb) {   // batches of parameters: the packed columns [kbb][Mtot]
+                const int kbb = (int)std::min(kb, np - k0);
+                launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n,
+                               (int)(accepted_only != 0), dgid, (const long long*)doff.in(d), (const int*)nullptr, (int)k0, kbb, Mtot, 0, 0,
+                               (const double*)nullptr, (int)np, col, (int*)dcnt, 0);
+                if (NC > 0)
+                    launch_checked(c, k_group_chunk_sum, dim3(NC, kbb), dim3(STATS_WG), (size_t)STATS_LDS_N * 8, (const double*)col, Mtot,
+                                   (const long long*)dcst.in(d), (const int*)dclen.in(d), NC, csum.in(d), cnan.in(d));
+                launch_checked(c, k_group_mean, dim3((unsigned)((G * kbb + 255) / 256)), dim3(256), 0, (const double*)csum.in(d),
+                               (const int*)cnan.in(d), NC, (const int*)dgch0.in(d), (const long long*)dgm.in(d), (int)G, (int)k0, kbb,
+                               (int)np, mean.in(d), gnan.in(d));
+                if (!ord) continue;
+                double* omed = med ? median.in(d) : nullptr;
+                if (!sgrp.empty())
+                    launch_checked(c, k_group_small, dim3((unsigned)sgrp.size(), kbb), dim3(STATS_WG), (size_t)STATS_LDS_N * 8,
+                                   (const double*)col, Mtot, (const int*)dsg.in(d), (const long long*)dG0.in(d), (const long long*)dgm.in(d),
+                                   (int)G, (int)k0, (int)np, (const int*)gnan.in(d), (const double*)dprobs.in(d), (int)nq, omed, quant.in(d));
+                if (wgrp.empty()) continue;
+                const int nw = (int)wgrp.size() * kbb;
+                for (int w = 0; w < nw; ++w)
+                    for (int r = 0; r < R; ++r) remh[(size_t)w * R + r] = rk[(size_t)(w / kbb) * R + r];
+                up(c, d, rem, remh.data(), (size_t)nw * R);
+                HIPCHK(hipMemsetAsync(pre.in(d), 0, (size_t)nw * R * 8, c->stream));
+                HIPCHK(hipMemsetAsync(ghist.in(d), 0, (size_t)WB * R * GROUP_BINS * 8, c->stream));   // (k_group_pick zeroes it again)
+                for (int w0 = 0; w0 < nw; w0 += WB) {
+                    const int wn = std::min(WB, nw - w0);
+                    for (int dg = 0; dg < 6; ++dg) {
+                        launch_checked(c, k_group_hist, dim3(wn, B, (R + GROUP_RB - 1) / GROUP_RB), dim3(STATS_WG), 0, (const double*)col,
+                                       Mtot, (const int*)dwg.in(d), (const long long*)dG0.in(d), (const long long*)dgm.in(d), kbb, R, dg, w0,
+                                       (const long long*)rem.in(d), (const unsigned long long*)pre.in(d), ghist.in(d));
+                        launch_checked(c, k_group_pick, dim3(wn * R), dim3(STATS_WG), 0, dg, w0 * R, ghist.in(d), rem.in(d), pre.in(d));
+                    }
+                }
+                launch_checked(c, k_group_finish, dim3((nw + 63) / 64), dim3(64), 0, nw, (const int*)dwg.in(d), (const long long*)dgm.in(d),
+                               (int)G, (int)k0, kbb, (int)np, R, (const long long*)drk.in(d), (const unsigned long long*)pre.in(d),
+                               (const int*)gnan.in(d), (const double*)dprobs.in(d), (int)nq, omed, quant.in(d));
+            }
+            if (cov) {   // batches of chunks: every parameter centred, [np][nb][STATS_LDS_N]; each chunk's pair sums, then the groups'
+                const int Nbc = (int)std::min<size_t>(NC, c->st_scr_bytes / (np * STATS_LDS_N * 8));
+                const int nt = ((int)np + COV_T - 1) / COV_T, ntiles = nt * (nt + 1) / 2;
+                for (int cb0 = 0; cb0 < NC; cb0 += Nbc) {
+                    const int nb = std::min(Nbc, NC - cb0);
+                    launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n,
+                                   (int)(accepted_only != 0), dgid, (const long long*)doff.in(d) + N, (const int*)dcch0.in(d), 0, (int)np,
+                                   Mtot, cb0, nb, (const double*)mean.in(d), (int)np, col, (int*)dcnt, 0);
+                    launch_checked(c, k_cov_pairs, dim3(nb, ntiles), dim3(COV_WG), 0, (const double*)col, STATS_LDS_N, NC, cb0, nb, (int)np,
+                                   (const int*)dclen.in(d), csum2.in(d), 1);
+                }
+            }
+        }
+        if (cov && G > 0)
+            launch_checked(c, k_group_cov, dim3((unsigned)((G * np * (np + 1) / 2 + 255) / 256)), dim3(256), 0, (const double*)csum2.in(d),
+                           NC, (const int*)dgch0.in(d), (const long long*)dgm.in(d), (int)G, (int)np, covo.in(d));
+        if (kb > 0) {   // (no draw in any group: every output NaN, filled below)
+            down(c, d, mean, out->mean, G * np);
+            down(c, d, median, out->median, G * np);
+            down(c, d, quant, out->quantile, nq * G * np);
+        }
+        down(c, d, covo, out->cov, G * np * np);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (kb == 0) {
+            if (out->mean) std::fill(out->mean, out->mean + G * np, NAN);
+            if (out->median) std::fill(out->median, out->median + G * np, NAN);
+            if (out->quantile) std::fill(out->quantile, out->quantile + nq * G * np, NAN);
+        }
+        if (out->count) std::copy(gm.begin(), gm.end(), out->count);
+        if (out->n_chains) std::copy(grp.n_chains.begin(), grp.n_chains.end(), out->n_chains);
+        return SMM_OK;
+    });
+}
+
+// --- histograms of groups of chains (smm_hist.hpp) ---------------------------------------------------------------------------------------
+
+int smm_get_histogram(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups, int32_t bins,
+                      const double* range, const int32_t* pairs, int32_t n_pairs, int32_t bins2, smm_histogram_t* out) {
+    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        const size_t N = c->P.N, np = c->P.np;
+        if (const int rc = check_select(c, select)) return rc;
+        if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
+        if (bins < 1 || bins > 65536) return fail(c, SMM_ERR_INVALID_ARG, "bins must lie in [1, 65536]");
+        if (range)
+            for (size_t k = 0; k < np; ++k)
+                if (!(std::isfinite(range[2 * k]) && std::isfinite(range[2 * k + 1]) && range[2 * k] <= range[2 * k + 1]))
+                    return fail(c, SMM_ERR_INVALID_ARG, "a range row must be finite with lo <= hi");
+        if (n_pairs < 0 || (size_t)n_pairs > np * np || (n_pairs > 0 && !pairs))
+            return fail(c, SMM_ERR_INVALID_ARG, "n_pairs outside [0, np np], or pairs NULL with n_pairs > 0");
+        for (int p = 0; p < 2 * n_pairs; ++p)
+            if (pairs[p] < 0 || (size_t)pairs[p] >= np) return fail(c, SMM_ERR_INVALID_ARG, "a pair entry outside [0, np)");
+        if (n_pairs > 0 && (bins2 < 1 || bins2 > 512)) return fail(c, SMM_ERR_INVALID_ARG, "bins2 must lie in [1, 512]");
+        if (n_pairs == 0 && (out->hist2 || out->edges2)) return fail(c, SMM_ERR_INVALID_ARG, "hist2 or edges2 requested without pairs");
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t G = n_groups, B = bins, B2 = n_pairs > 0 ? bins2 : 0, NP = n_pairs;
+        const int n = t1 - t0;
+        const bool two = NP > 0 && (out->hist2 || out->edges2);
+        const Groups grp = group_members(group, G, N);
+        const int M = grp.M;
+        const bool autor = range == nullptr, cnt_pass = autor || (out->count && select == 1);
+        // a batch of groups: the edges (always: the counting reads them), the counts asked for, the 2-D axes and cells
+        const size_t per_group = np * (B + 1) * 8 + (out->hist ? np * B * 8 : 0) + (two ? np * (B2 + 1) * 8 : 0) +
+                                 (two && out->hist2 ? NP * B2 * B2 * 8 : 0);
+        const size_t gb = G ? std::max((size_t)1, std::min(G, reducer_batch_cap(c) / per_group)) : 0;
+        Carve Rv;   // 8-byte slices first
+        const auto cmin = Rv.take<double>(autor ? N * np : 0), cmax = Rv.take<double>(autor ? N * np : 0), drng = Rv.take<double>(autor ? 0 : 2 * np),
+                   dlo = Rv.take<double>(G * np), dhi = Rv.take<double>(G * np), edges = Rv.take<double>(gb * np * (B + 1)),
+                   edges2 = Rv.take<double>(two ? gb * np * (B2 + 1) : 0);
+        const auto hist = Rv.take<unsigned long long>(out->hist ? gb * np * B : 0),
+                   hist2 = Rv.take<unsigned long long>(two && out->hist2 ? gb * NP * B2 * B2 : 0);
+        const auto cbad = Rv.take<int>(autor ? N * np : 0), dcnt = Rv.take<int>(N), dst = Rv.take<int>(G * np), dgid = Rv.take<int>(N),
+                   dgm0 = Rv.take<int>(G + 1), dmem = Rv.take<int>(M), dpairs = Rv.take<int>(2 * NP);
+        void* d = reducer_result(c, Rv.bytes);
+        up(c, d, dgid, grp.gid); up(c, d, dgm0, grp.gmem0); up(c, d, dmem, grp.mem); up(c, d, dpairs, pairs, 2 * NP);
+        up(c, d, drng, range, 2 * np);
+        if (cnt_pass && M > 0)
+            launch_checked(c, k_hist_range, dim3(M, autor ? (unsigned)((np + HIST_KMAX - 1) / HIST_KMAX) : 1), dim3(HIST_WG), 0,
+                           (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, (const int*)dmem.in(d), 0, (int)np, dcnt.in(d),
+                           autor ? cmin.in(d) : (double*)nullptr, cmax.in(d), cbad.in(d));
+        const int lb = c->H.hist_lds_bins;
+        const bool lds1 = (int)B <= lb && 12 * B + 8 <= HIST_LDS_BYTES, lds2 = two && (int)B2 <= lb && 16 * (B2 + 1) + 4 * B2 * B2 <= HIST_LDS_BYTES;
+        const int kb = lds1 ? (int)std::min({np, (size_t)HIST_KMAX, HIST_LDS_BYTES / (12 * B + 8)}) : (int)std::min(np, (size_t)HIST_KMAX);
+        const int kp = !two ? 0 : lds2 ? (int)std::min({NP, (size_t)HIST_KMAX, HIST_LDS_BYTES / (16 * (B2 + 1) + 4 * B2 * B2)})
+                                       : (int)std::min(NP, (size_t)HIST_KMAX);
+        for (size_t g0 = 0; g0 < G; g0 += gb) {
+            const size_t gn = std::min(gb, G - g0);
+            const int m0 = grp.gmem0[g0], mb = grp.gmem0[g0 + gn] - m0;
+            launch_checked(c, k_hist_edges, dim3((unsigned)gn, (unsigned)np), dim3(HIST_WG), 0, (const int*)dgm0.in(d), (const int*)dmem.in(d),
+                           (int)g0, (int)np, (const int*)dcnt.in(d), (const double*)cmin.in(d), (const double*)cmax.in(d),
+                           (const int*)cbad.in(d), autor ? (const double*)nullptr : (const double*)drng.in(d), (int)B, (int)B2, dlo.in(d),
+                           dhi.in(d), dst.in(d), edges.in(d), two ? edges2.in(d) : (double*)nullptr);
+            if (out->hist) {
+                HIPCHK(hipMemsetAsync(hist.in(d), 0, gn * np * B * 8, c->stream));
+                if (mb > 0)
+                    launch_checked(c, k_hist_count, dim3(mb, (unsigned)((np + kb - 1) / kb)), dim3(HIST_WG),
+                                   lds1 ? (size_t)kb * (12 * B + 8) : 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select,
+                                   (const int*)dmem.in(d), (const int*)dgid.in(d), (const int*)dgm0.in(d), m0, (int)g0, (int)np, kb, (int)B,
+                                   (int)lds1, (const double*)dlo.in(d), (const double*)dhi.in(d), (const int*)dst.in(d),
+                                   (const double*)edges.in(d), hist.in(d));
+            }
+            if (two && out->hist2) {
+                HIPCHK(hipMemsetAsync(hist2.in(d), 0, gn * NP * B2 * B2 * 8, c->stream));
+                if (mb > 0)
+                    launch_checked(c, k_hist_pairs, dim3(mb, (unsigned)((NP + kp - 1) / kp)), dim3(HIST_WG),
+                                   lds2 ? (size_t)kp * (16 * (B2 + 1) + 4 * B2 * B2) : 0, (const double*)P.hrec, (int)N, P.HW, t0, n,
+                                   (int)select, (const int*)dmem.in(d), (const int*)dgid.in(d), (const int*)dgm0.in(d), m0, (int)g0, (int)np,
+                                   (const int*)dpairs.in(d), (int)NP, kp, (int)B2, (int)lds2, (const int*)dst.in(d),
+                                   (const double*)edges2.in(d), hist2.in(d));
+            }
+            down(c, d, edges, out->edges ? out->edges + g0 * np * (B + 1) : nullptr, gn * np * (B + 1));
+            down(c, d, hist, out->hist ? out->hist + g0 * np * B : nullptr, gn * np * B);
+            if (two) {
+                down(c, d, edges2, out->edges2 ? out->edges2 + g0 * np * (B2 + 1) : nullptr, gn * np * (B2 + 1));
+                down(c, d, hist2, out->hist2 ? out->hist2 + g0 * NP * B2 * B2 : nullptr, gn * NP * B2 * B2);
+            }
+            HIPCHK(hipStreamSynchronize(c->stream));   // (the next batch reuses the tables)
+        }
+        std::vector<int> cnt(N, n);
+        if (out->count && select == 1 && M > 0) down(c, d, dcnt, cnt.data(), N);
+        down(c, d, dlo, out->lo, G * np); down(c, d, dhi, out->hi, G * np); down(c, d, dst, out->status, G * np);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (out->count) {
+            std::fill(out->count, out->count + G, (int64_t)0);
+            for (size_t i = 0; i < N; ++i)
+                if (grp.gid[i] >= 0) out->count[grp.gid[i]] += cnt[i];
+        }
+        return SMM_OK;
+    });
+}
+
+// --- the population per iteration (smm_trace.hpp) ----------------------------------------------------------------------------------------
+
+int smm_get_trace(void* ctx, int32_t t0, int32_t t1, int32_t stride, int32_t select, int32_t moments, const int32_t* group, int32_t n_groups,
+                  const double* probs, int32_t n_probs, smm_trace_t* out) {
+    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        if (stride < 1) return fail(c, SMM_ERR_INVALID_ARG, "stride must be at least 1");
+        if (const int rc = check_select(c, select)) return rc;
+        if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
+        if (const int rc = check_probs(c, probs, n_probs, out->quantile != nullptr)) return rc;
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t N = P.N, np = P.np, S = np + 1 + (moments ? (size_t)P.nm : 0), G = n_groups, nq = out->quantile ? n_probs : 0;
+        const int nt = (int)(((long long)(t1 - t0) + stride - 1) / stride);
+        const Groups grp = group_members(group, G, N);
+        if (out->n_chains) std::copy(grp.n_chains.begin(), grp.n_chains.end(), out->n_chains);
+        for (int i = 0; i < nt && out->iter; ++i) out->iter[i] = t0 + (int32_t)((long long)i * stride);
+        if (nt == 0 || G == 0) return SMM_OK;
+        const int M = grp.M;
+        const size_t Mx = std::max(M, 1), Me = (Mx + 1) & ~(size_t)1;   // (the state table's rows keep the columns behind them 8-byte aligned)
+        const bool cols = out->mean || out->var || out->median || out->quantile;
+        // a batch of kept iterations: the state table and the columns in the scratch, the results in the result buffer; a batch of one
+        // kept iteration whose columns do not fit goes in batches of series
+        auto per_iter = [&](size_t sb) { return Me * 4 + sb * Mx * 8; };
+        reducer_scratch(c, per_iter(1));
+        const size_t hook = c->H.stats_scratch;
+        const size_t budget = hook ? std::min(c->st_scr_bytes, std::max(hook, per_iter(1))) : c->st_scr_bytes;
+        const size_t res_iter = G * ((3 + nq) * S * 8 + 8 + 5 * 4), res_cap = reducer_batch_cap(c);
+        const size_t nib = std::min<size_t>(nt, std::max<size_t>(1, std::min(budget / per_iter(cols ? S : 0), res_cap / res_iter)));
+        const size_t sb = !cols ? 0 : per_iter(S) <= budget ? S : std::max<size_t>(1, (budget - Me * 4) / (Mx * 8));
+        Carve Rv;   // 8-byte slices first
+        const auto dprobs = Rv.take<double>(nq), mean = Rv.take<double>(nib * G * S), var = Rv.take<double>(nib * G * S),
+                   median = Rv.take<double>(nib * G * S), quant = Rv.take<double>(nq * nib * G * S), bestv = Rv.take<double>(nib * G);
+        const auto count = Rv.take<int>(nib * G), nacc = Rv.take<int>(nib * G), nex = Rv.take<int>(nib * G), nfail = Rv.take<int>(nib * G),
+                   bestc = Rv.take<int>(nib * G), dgm0 = Rv.take<int>(G + 1), dmem = Rv.take<int>(M);
+        void* d = reducer_result(c, Rv.bytes);
+        up(c, d, dgm0, grp.gmem0); up(c, d, dmem, grp.mem); up(c, d, dprobs, probs, nq);
+        int* tab = (int*)c->st_scr;
+        const int lds_n = sort_lds_n(grp.longest);
+        for (size_t i0 = 0; i0 < (size_t)nt; i0 += nib) {
+            const int nk = (int)std::min(nib, (size_t)nt - i0), tb = t0 + (int)((long long)i0 * stride);
+            double* col = (double*)((char*)c->st_scr + (size_t)nk * Me * 4);
+            if (select == 2 && M > 0)
+                launch_checked(c, k_trace_state, dim3(M), dim3(TRACE_WG), 0, (const double*)P.hrec, (int)N, P.HW, (const int*)dmem.in(d), (int)Me,
+                               tb, nk, (int)stride, tab);
+            for (size_t s0 = 0; s0 < (cols ? S : 1); s0 += std::max(sb, (size_t)1)) {   // (no column asked for: the counts and the best only)
+                const int sbb = (int)std::min(sb, S - s0);
+                launch_checked(c, k_trace_gather, dim3((unsigned)(nk * G), (unsigned)std::max(1, (sbb + TRACE_KMAX - 1) / TRACE_KMAX)),
+                               dim3(TRACE_WG), 0, (const double*)P.hrec, (int)N, P.HW, (int)np, (const int*)dmem.in(d), (const int*)dgm0.in(d),
+                               (int)G, M, (int)Me, P.offset, tb, (int)stride, (int)select, (const int*)tab, (int)s0, sbb, (int)(s0 == 0), col,
+                               count.in(d), nacc.in(d), nex.in(d), nfail.in(d), bestv.in(d), bestc.in(d));
+                if (sbb > 0)
+                    launch_checked(c, k_trace_column, dim3((unsigned)(nk * G), (unsigned)sbb), dim3(TRACE_WG), (size_t)lds_n * 8,
+                                   (const double*)col, M, (const int*)dgm0.in(d), (int)G, (int)s0, sbb, (int)S, (const int*)count.in(d),
+                                   (const double*)dprobs.in(d), (int)nq, nib * G * S, mean.in(d), out->var ? var.in(d) : (double*)nullptr,
+                                   out->median ? median.in(d) : (double*)nullptr, quant.in(d));
+            }
+            // this batch's nk rows of per elements each, to their place among the nt rows of the caller's array
+            auto down_rows = [&](auto sl, auto* dst, size_t per, size_t src_off = 0, size_t dst_off = 0) {
+                if (dst) down(c, d, sl.at(src_off), dst + dst_off + i0 * per, (size_t)nk * per);
+            };
+            down_rows(mean, out->mean, G * S); down_rows(var, out->var, G * S); down_rows(median, out->median, G * S);
+            for (size_t p = 0; p < nq; ++p) down_rows(quant, out->quantile, G * S, p * nib * G * S, p * (size_t)nt * G * S);
+            down_rows(bestv, out->best_value, G); down_rows(count, out->count, G); down_rows(nacc, out->n_accepted, G);
+            down_rows(nex, out->n_exchanged, G); down_rows(nfail, out->n_failed, G); down_rows(bestc, out->best_chain, G);
+            HIPCHK(hipStreamSynchronize(c->stream));   // (the next batch reuses the scratch and the results)
+        }
+        return SMM_OK;
+    });
+}
+
+}  // extern "C"

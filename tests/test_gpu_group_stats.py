@@ -15,12 +15,12 @@ import group_stats_ref as GR
 
 pytestmark = pytest.mark.gpu
 PROBS = (0.0, 0.025, 0.3, 0.5, 0.975, 1.0)
-STATS_SCRATCH_CAP = 256 << 20    # smmhip.hip
+STATS_SCRATCH_CAP = 256 << 20    # smm_reducers_host.hpp: REDUCER_BATCH_CAP
 LDS_N = 8192                     # smm_stats.hpp: STATS_LDS_N
 
 
 def plan(N, T, npar, counts, cov, cap=STATS_SCRATCH_CAP, wide_min=LDS_N + 1):
-    """the host's plan of a first call on a fresh context (smmhip.hip: smm_get_group_stats, reducer_scratch): parameters per batch kb,
+    """the host's plan of a first call on a fresh context (smm_reducers_host.hpp: smm_get_group_stats, reducer_scratch): parameters per batch kb,
     chunks per cov batch Nbc, and which groups take the grid-wide select"""
     counts = np.asarray(counts, np.int64)
     Mtot = int(counts.sum())

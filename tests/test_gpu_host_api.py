@@ -172,3 +172,75 @@ def test_sharded_protocols_on_one_rank(S, protocol):
     cm.assert_history_equal(a.history(), b.history(), exact_floats=True)
     cm.assert_state_equal(a.state(), b.state(), rtol=0)
     assert (a.history().exchanged != 0).any()
+
+
+def test_reducers_refuse_the_same_arguments_in_the_same_words():
+    # the history reducers share their argument rules (smm_reducers_host.hpp): through the raw ABI every member that has a rule gets
+    # one call that breaks it and must answer SMM_ERR_INVALID_ARG with that rule's message (the strings as include/smmhip.h's
+    # implementation has always worded them, written out here); then every member answers a good call
+    import ctypes as C
+    A = S._abi
+    WINDOW = "window must satisfy 0 <= t0 <= t1 <= completed iterations"
+    GROUP_ID = "a group id outside [-1, n_groups)"
+    NULL_DIAG = "n_groups < 0, or group NULL with n_groups > 0"
+    NULL_ONE = "n_groups < 0, or group NULL with n_groups != 1"
+    PROBS = "probs must lie in [0, 1]"
+    QUANTILE = "quantile requested without probs"
+    SELECT = "select must be 0 (all), 1 (accepted) or 2 (state)"
+    N, T = 32, 8
+    prob, opts = cm.serial_normal(N=N, T=T, ns=64, chol_L=np.ascontiguousarray(np.broadcast_to(np.eye(2), (N, 2, 2))))
+    h = S.hip_context(prob, opts)
+    h.step(T)
+    lib, ctx = h._lib, h._ctx
+    groups = np.arange(N, dtype=np.int32) % 2
+    bad_groups = groups.copy(); bad_groups[N - 1] = 2
+    ip = lambda a: a.ctypes.data_as(A.c_int32_p)
+    good_p, bad_p = A.f64([0.5]), A.f64([0.5, 1.5])
+    room = np.empty(2 * 2 * (2 + 1 + 2) * N * T)   # (more than any quantile output here; never written: the calls fail first)
+    st, gs, tr = A.smm_chain_stats_t(), A.smm_group_stats_t(), A.smm_trace_t()
+    stq, gsq, trq = A.smm_chain_stats_t(), A.smm_group_stats_t(), A.smm_trace_t()
+    for q in (stq, gsq, trq):
+        q.quantile = A.dptr(room)
+    dg, hi = A.smm_chain_diag_t(), A.smm_histogram_t()
+    bad = [
+        ("chain_stats", WINDOW, lambda: lib.smm_get_chain_stats(ctx, 0, T + 1, 1, None, 0, C.byref(st))),
+        ("chain_stats", PROBS, lambda: lib.smm_get_chain_stats(ctx, 0, T, 1, A.dptr(bad_p), 2, C.byref(st))),
+        ("chain_stats", QUANTILE, lambda: lib.smm_get_chain_stats(ctx, 0, T, 1, None, 0, C.byref(stq))),
+        ("chain_cov", WINDOW, lambda: lib.smm_get_chain_cov(ctx, 0, T + 1, 1, 0, None, None, None)),
+        ("adapt_proposal", WINDOW, lambda: lib.smm_adapt_proposal(ctx, 0, T + 1, 1, 3, 1, 1e-8, None)),
+        ("chain_diag", WINDOW, lambda: lib.smm_get_chain_diag(ctx, 0, T + 1, 3, 0, None, 0, C.byref(dg))),
+        ("chain_diag", GROUP_ID, lambda: lib.smm_get_chain_diag(ctx, 0, T, 3, 0, ip(bad_groups), 2, C.byref(dg))),
+        ("chain_diag", NULL_DIAG, lambda: lib.smm_get_chain_diag(ctx, 0, T, 3, 0, None, 1, C.byref(dg))),
+        ("group_stats", WINDOW, lambda: lib.smm_get_group_stats(ctx, 0, T + 1, 1, None, 1, None, 0, C.byref(gs))),
+        ("group_stats", GROUP_ID, lambda: lib.smm_get_group_stats(ctx, 0, T, 1, ip(bad_groups), 2, None, 0, C.byref(gs))),
+        ("group_stats", NULL_ONE, lambda: lib.smm_get_group_stats(ctx, 0, T, 1, None, 2, None, 0, C.byref(gs))),
+        ("group_stats", PROBS, lambda: lib.smm_get_group_stats(ctx, 0, T, 1, None, 1, A.dptr(bad_p), 2, C.byref(gs))),
+        ("group_stats", QUANTILE, lambda: lib.smm_get_group_stats(ctx, 0, T, 1, None, 1, None, 0, C.byref(gsq))),
+        ("histogram", WINDOW, lambda: lib.smm_get_histogram(ctx, 0, T + 1, 1, None, 1, 4, None, None, 0, 4, C.byref(hi))),
+        ("histogram", GROUP_ID, lambda: lib.smm_get_histogram(ctx, 0, T, 1, ip(bad_groups), 2, 4, None, None, 0, 4, C.byref(hi))),
+        ("histogram", NULL_ONE, lambda: lib.smm_get_histogram(ctx, 0, T, 1, None, 2, 4, None, None, 0, 4, C.byref(hi))),
+        ("histogram", SELECT, lambda: lib.smm_get_histogram(ctx, 0, T, 3, None, 1, 4, None, None, 0, 4, C.byref(hi))),
+        ("trace", WINDOW, lambda: lib.smm_get_trace(ctx, 0, T + 1, 1, 2, 0, None, 1, None, 0, C.byref(tr))),
+        ("trace", GROUP_ID, lambda: lib.smm_get_trace(ctx, 0, T, 1, 2, 0, ip(bad_groups), 2, None, 0, C.byref(tr))),
+        ("trace", NULL_ONE, lambda: lib.smm_get_trace(ctx, 0, T, 1, 2, 0, None, 0, None, 0, C.byref(tr))),
+        ("trace", PROBS, lambda: lib.smm_get_trace(ctx, 0, T, 1, 2, 0, None, 1, A.dptr(bad_p), 2, C.byref(tr))),
+        ("trace", QUANTILE, lambda: lib.smm_get_trace(ctx, 0, T, 1, 2, 0, None, 1, None, 0, C.byref(trq))),
+        ("trace", SELECT, lambda: lib.smm_get_trace(ctx, 0, T, 1, 3, 0, None, 1, None, 0, C.byref(tr))),
+    ]
+    for member, message, call in bad:
+        rc = call()
+        said = lib.smm_last_error(ctx).decode()
+        assert rc == A.SMM_ERR_INVALID_ARG and message in said, (member, message, rc, said)
+    # (smm_get_proposal and smm_set_proposal take no window, groups, probs or select: they share the frame only)
+    assert h.chain_stats(probs=good_p)["count"].shape == (N,)
+    assert h.chain_cov()[2].shape == (2, 2, N)
+    L = h.proposal()
+    assert np.array_equal(L, np.broadcast_to(np.eye(2), (N, 2, 2)))
+    h.set_proposal(2.0 * L)
+    assert np.array_equal(h.proposal(), 2.0 * L)
+    assert set(h.adapt_proposal(0, T).tolist()) <= {0, 1, 2, 3}
+    assert h.chain_diag(groups=groups)["rhat"].shape == (2, 3)
+    assert h.group_stats(groups=groups, probs=good_p)["n_chains"].tolist() == [N // 2, N // 2]
+    assert h.histogram(groups=groups, bins=4)["hist"].shape == (2, 2, 4)
+    t = h.trace(groups=groups, probs=good_p)
+    assert t["n_chains"].tolist() == [N // 2, N // 2] and t["iter"].tolist() == list(range(T)) and (t["count"] == N // 2).all()

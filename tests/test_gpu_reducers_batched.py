@@ -18,12 +18,12 @@ import common as cm
 
 pytestmark = pytest.mark.gpu
 PROBS = (0.0, 0.025, 0.5, 0.975, 1.0)
-STATS_SCRATCH_CAP = 256 << 20    # smmhip.hip
+STATS_SCRATCH_CAP = 256 << 20    # smm_reducers_host.hpp: REDUCER_BATCH_CAP
 STATS_MODE_BINS = 16384          # smm_stats.hpp
 
 
 class Plan:
-    """the host's batch plan of the reducers (smmhip.hip: chain_stats_scratch_bytes, reducer_scratch, chain_batches,
+    """the host's batch plan of the reducers (smm_reducers_host.hpp: chain_stats_scratch_bytes, reducer_scratch, chain_batches,
     smm_get_chain_stats, chain_cov_device, smm_get_chain_diag), following one context's shared scratch st_scr across its calls"""
 
     def __init__(self, N, T, npar, cap=STATS_SCRATCH_CAP):

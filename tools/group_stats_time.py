@@ -18,7 +18,7 @@ from smm_jl_amd.workloads import build_problem   # noqa: E402
 
 SHAPES = {"c3": (4096, 2000), "c5": (4096, 2000)}
 PROBS = (0.025, 0.975)
-CAP = 256 << 20       # smmhip.hip: STATS_SCRATCH_CAP
+CAP = 256 << 20       # smm_reducers_host.hpp: REDUCER_BATCH_CAP
 LDS_N = 8192          # smm_stats.hpp: STATS_LDS_N
 
 
@@ -47,7 +47,7 @@ def host_path(hist, groups, G, probs):
 
 
 def plan_and_bytes(N, T, npar, HW, counts, R):
-    """(kb, Nbc, bytes): the host's plan of a call with cov (smmhip.hip: smm_get_group_stats) and the HBM bytes it moves: the counting
+    """(kb, Nbc, bytes): the host's plan of a call with cov (smm_reducers_host.hpp: smm_get_group_stats) and the HBM bytes it moves: the counting
     pass reads one 64-B sector of every record; each parameter batch re-reads the records' sectors holding its kb parameters, writes and
     re-reads the packed columns (chunk sums), and reads each long column 6 x ceil(R / 4) times (the select's digits); the cov pass reads
     every record's np parameters, writes the centred chunks and reads 16 columns per tile of 8 x 8 pairs"""
