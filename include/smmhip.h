@@ -611,7 +611,8 @@ int  smm_get_trace(void* ctx, int32_t t0, int32_t t1, int32_t stride, int32_t se
  * The three proposal calls need a context created with chol_L (otherwise SMM_ERR_INVALID_ARG).  The factor(s) are [np][np] for a shared
  * factor, [N][np][np] for per-chain factors (the LOCAL chains, global rows chain_offset .. chain_offset + N - 1: a shard reads and writes
  * only its own chains' rows, the only rows its kernels read), row-major.  A context's forms do not change (smm_describe is the same):
- * installing a factor overwrites the device buffer the per-iteration kernels read, on the context's stream.
+ * installing a factor overwrites the device buffer the chain kernels read — the per-iteration ones and the persistent tile form, which
+ * reads the factor at every iteration — on the context's stream.
  *
  * smm_get_proposal: the installed factor(s), zeros above the diagonal.
  * smm_set_proposal: install factor(s) between steps (the matrix form of set_sigma!, AlgoBGP.jl:218-219); entries above the diagonal are
@@ -662,13 +663,16 @@ int  smm_set_profiling(void* ctx, int32_t on);
  *     the persistent kernel once more with the user's source inside, through hiprtc, when the first such context is created: ~1.5 s),
  *     with at most 16 parameters / moments (one proposal batch, isotropic, min_improve == 0) on a single shard of up to 8192 chains in
  *     whole groups of 32;
- *   - objfunc_norm with MORE than two parameters (the reference's own larger examples have 6 and 18, Examples.jl:210-230, 232-319), the
+ *   - objfunc_norm with MORE than two parameters (the reference's own larger examples have 6 and 18, Examples.jl:210-230, 232-319; with a
+ *     Cholesky factor: any number), the
  *     dense objectives (SMM_OBJ_DENSE, SMM_OBJ_DENSE2), or a USER objective in its MAP-REDUCE form (smm_register_user_objective_lanes with
  *     64, 128, 256 or 512 lanes per evaluation: the library compiles the persistent tile kernel once more with the user's source inside,
  *     through hiprtc, when the first such context is created; a tile's 512 lanes then evaluate 512 / lanes chains at a time with the
  *     stand-alone kernel's reduction order — the same bits; it pays while an evaluation is short beside the ~40 us of three launches per
  *     iteration: a long simulation fills the device better from its own launches, smm_set_persistent(ctx, 0)):
- *     one proposal batch or several, isotropic proposals, dist_fun = `-`, ONE min_improve >= 0 (or NaN) for all chains, a single shard of
+ *     one proposal batch or several, isotropic proposals or — single shards only — a Cholesky factor (chol_L, shared or per chain; a
+ *     map-reduce user objective's form for a factor is a further hiprtc module, compiled only when a context with a factor first wants
+ *     it), dist_fun = `-`, ONE min_improve >= 0 (or NaN) for all chains, a single shard of
  *     at most two 16-chain tiles per compute unit whose blocks fit the LDS (np = nm = 50: yes; 64 + 64: no) — or a SHARD of a sharded run
  *     (smm_bgp_p2p_step; smm_chain_persist_tile.hpp, SH) with the same conditions and: equal shards of whole tiles (N a multiple of 16,
  *     chain_offset a multiple of N, at most 8 ranks), N_global <= 8192 (the LDS plan), min_improve the same for every chain.  A
@@ -676,7 +680,8 @@ int  smm_set_profiling(void* ctx, int32_t on);
  *   - (round 6) min_improve BY CHAIN, what the reference's API takes (a vector, AlgoBGP.jl:522; the pair (i, j) is tested against chain i's,
  *     :688): single shards of the objfunc_norm and tile forms above walk one threshold per chain, every one >= 0 or NaN; a context's single
  *     iterations keep the per-iteration kernels' walk on any thresholds.
- * A negative threshold, other dist_fun, Cholesky proposals, user objectives with 1024 lanes; as shards: thresholds by chain, N_global past
+ * A negative threshold, other dist_fun, Cholesky proposals of the banana or a one-thread user objective,
+ * user objectives with 1024 lanes; as shards: Cholesky proposals, thresholds by chain, N_global past
  * 8192 for anything but objfunc_norm with at most two parameters (bench.py --gpus 8 --workload c5's weak-scaling 32768 chains among them),
  * the banana and one-thread user objectives: the per-iteration kernels.
  * on = 0 keeps the one-launch-per-iteration kernels (default: on).  A hard error of the algorithm inside such a launch is found at

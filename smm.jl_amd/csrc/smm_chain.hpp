@@ -1274,14 +1274,19 @@ __global__ __launch_bounds__(WG * TPW, 4) void k_chain_iter(const KParams P, con
             // 64 * waves / CT lanes of ONE wave, a lane by the component pairs q = sl, sl + LPC, ... (one generator call per pair
             // and try).  The tries are taken in order, each one tested by all the chain's lanes at once (a segment of the
             // wave's ballot); the first one inside the unit box wins: same tries, same order, same winner as the serial form.
-            const bool coop = bs >= SMM_COOP_MIN_BATCH && !P.chol_L;   // (uniform)
+            // With a Cholesky factor (bs == np) a lane segment keeps the np normals of the try it evaluates in the moments' part of its
+            // (still unused) history row, behind the candidate: nm doubles.  Contexts with FEWER MOMENTS THAN PARAMETERS (nm < np: a
+            // dense objective like 33 x 17, a user objective with a few moments) have no room there and keep the serial form below.
+            const bool coop = bs >= SMM_COOP_MIN_BATCH && (!P.chol_L || nm >= np);   // (uniform)
             if (coop) {
                 __syncthreads();   // the blocks the control wave staged (records, state, randomness) are every wave's now
                 // (smm_propose.hpp: every wave of the tile works, 64 * waves / CT lanes per chain)
                 const CoopProp X{S.rec, RW, S.rout, RW, S.theta, np, S.h, HW, S.rb, RBW, S.cs, CSW, S.lb, S.ub,
                                  (unsigned long long*)(S.h - (size_t)st * ((tile_smem_doubles(CT, np, nm, RW, HW, RBW, KIND) + 1) & ~(size_t)1)) + 2, P.err,
-                                 P.seed, P.offset, N, bs, P.rb_tries, P.user_n, P.smpl_iters, P.scout_after, P.scout_gl};
-                coop_mysample<CT>(X, t, tile, tid, (int)blockDim.x / (64 * TPW), threadIdx.x == 0, CoopSyncThreads());
+                                 P.seed, P.offset, N, bs, P.rb_tries, P.user_n, P.smpl_iters, P.scout_after, P.scout_gl,
+                                 P.chol_L, P.chol_per_chain, S.h + H_PARAMS + np, HW};
+                if (P.chol_L) coop_mysample<CT, true>(X, t, tile, tid, (int)blockDim.x / (64 * TPW), threadIdx.x == 0, CoopSyncThreads());
+                else coop_mysample<CT, false>(X, t, tile, tid, (int)blockDim.x / (64 * TPW), threadIdx.x == 0, CoopSyncThreads());
             } else if (ctl) {
             if (valid)
                 for (int k = r; k < np; k += NR) {

@@ -92,6 +92,8 @@ struct PersistArgs {
     int slow_read;                     // SH, test build: the slow tile idles before its donors' remote reads instead of before its publication
     uint32_t o_slot;                   // the walk slots' part of the window (k_chain_persist_gen, k_chain_persist_loc)
     int tables_local;                  // the plan's pair words name local slots already (k_cone_tiles); else population offsets in units of 1 << unit_sh bytes
+    const double* chol_L;              // a Cholesky factor of the proposals (KParams::chol_L; k_chain_persist_tile's CH form), read at every iteration
+    int chol_per_chain;
 };
 
 // tags: never 0 (the ring starts zeroed and is zeroed again whenever the 7 epoch bits of the slot tag wrap)

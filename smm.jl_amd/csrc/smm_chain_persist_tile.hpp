@@ -20,8 +20,12 @@
 //   * no role specialisation (every wave is needed by the proposal and the objective): what persist_loc's worker waves do under the
 //     simulation — the next lists by LDS-DMA, the re-numbering table, the next randomness — is issued before the objective and waited
 //     for behind it; the gather runs behind the publication, where the tile would otherwise wait for its peers' stores.
-// One proposal batch or several, isotropic proposals (no Cholesky factor), dist_fun = -, at most one tile per workgroup slot of the
-// device.  Results are bit-identical to k_chain_iter's.  Errors, ring overrun guard, time-outs, repair: as in smm_chain_persist.hpp.
+// One proposal batch or several, dist_fun = -, at most one tile per workgroup slot of the device.  Results are bit-identical to
+// k_chain_iter's.  Errors, ring overrun guard, time-outs, repair: as in smm_chain_persist.hpp.
+// CH = proposals with a Cholesky factor (KParams::chol_L, shared or per chain; single shards): coop_mysample's CHOL form
+// (smm_propose.hpp).  The factor is read from global memory at every iteration — smm_set_proposal and smm_adapt_proposal between two steps
+// need nothing else —, and the normals of a generated try lie in the lane segment's row of the rewritten history rows of t - 1, which
+// are stored before the proposal starts: no LDS of its own, the layout is the isotropic form's.
 // SH = a SHARD of a sharded run (equal shards, N_global <= 8192): smm_chain_persist_loc.hpp's protocol on this kernel's records — the
 // launches of the ranks meet in the start barrier, a tile publishes its chains' whole records (RW granules) into its own rank's window
 // and, into every peer's, only what a walk or a proposal reads: the value (granule 0) and the parameters (granules 3 .. 3 + np - 1),
@@ -99,12 +103,18 @@ extern "C" __global__ __launch_bounds__(WG) void smm_user_persist_tile_kernel(co
 #else
     constexpr bool SH = false;
 #endif
+#ifdef SMM_TILE_CHOL
+    constexpr bool CH = true;
 #else
-template <int KIND, bool PCT = false, bool SH = false>   // PCT: thresholds by chain (a form of its own: see k_chain_persist_loc); SH: a shard
+    constexpr bool CH = false;
+#endif
+#else
+template <int KIND, bool PCT = false, bool SH = false, bool CH = false>   // PCT: thresholds by chain (a form of its own: see k_chain_persist_loc); SH: a shard; CH: a Cholesky factor
 __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistArgs A) {
     static_assert(KIND == 1 || KIND == 2, "objfunc_norm (shocks streamed) or the dense simulation");
     static_assert(!(PCT && SH), "thresholds by chain: single shards only");
 #endif
+    static_assert(!(CH && SH), "a Cholesky factor: single shards only (a shard's rewritten rows are put together behind the objective)");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int CT = PT_CT, LPC = PT_LPC;
     const int tid = (int)threadIdx.x, lane = tid & 63;
@@ -475,8 +485,9 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistArgs A) 
         // an iteration lasts as long as its slowest tile's work, and that work does not shrink by being done earlier; EXPERIMENTS.md R5.6)
         {
             const CoopProp X{s_rec + (t & 1) * CT * RW, RW, s_rec + ((t + 1) & 1) * CT * RW, RW, s_theta, np, s_hrow, HW, s_rb, RBW, s_cs, PR_STW, s_lb, s_ub,
-                             (unsigned long long*)s_hrow + 2, A.err, A.seed, goff, N, A.batch_size, A.rb_tries, A.user_n, A.smpl_iters, A.scout_after, A.scout_gl};
-            coop_mysample<CT>(X, t, tile, tid, WG / 64, tid == 0, PtBarrier());
+                             (unsigned long long*)s_hrow + 2, A.err, A.seed, goff, N, A.batch_size, A.rb_tries, A.user_n, A.smpl_iters, A.scout_after, A.scout_gl,
+                             A.chol_L, A.chol_per_chain, s_xrow, HW};   // (s_xrow: the rewritten rows of t - 1 are on their way to the history)
+            coop_mysample<CT, CH>(X, t, tile, tid, WG / 64, tid == 0, PtBarrier());
         }
         PR_BARRIER();   // B3: the proposals stand; the randomness block and the rows' region are free
         unsigned long long ts3 = 0;

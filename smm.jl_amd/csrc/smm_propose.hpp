@@ -9,6 +9,16 @@
 // a lane by the component pairs q = sl, sl + LPC, ... (one generator call per pair and try).  The tries are taken in order, each one
 // tested by all the chain's lanes at once (a segment of the wave's ballot); the first one inside the unit box wins: same tries, same
 // order, same winner as the serial form.
+// CHOL: a Cholesky factor of the proposal covariance (KParams::chol_L; one batch of all np components, smm_ctx_create) — component k is
+// (L z)_k, prop_direction's sum: products rounded, added left to right.  It needs the whole prefix z[0 .. k] of its try, so a try's normals
+// lie in LDS before its components are evaluated: those of the first rb_tries tries in the randomness block already, a later try's
+// drawn pair by pair as ever (the same counters) into the row `zst` of the lane segment that evaluates it.  The chain's lanes then take the
+// rows of the factor in a serpentine — sl, 2 LPC - 1 - sl, 2 LPC + sl, ... — so that every lane walks about the same number of
+// products (row k has k + 1 of them).  The factor is read from global memory, every lane its own rows: 20 KB per chain at 50
+// parameters, sixteen chains to a tile — nothing LDS holds — and the rows of one chain, read again by every try, stay in L2.
+// No scouting phase (scout_after is not read): the rounds of shared tries go on until every chain has its draw or the tries are used up
+// — a try's cost no longer lies in its generator calls alone.  A failing try is evaluated in full: an exit at the first finished row
+// outside the box (rows finish in ascending cost) would be valid and is not built (MEASUREMENTS.md has the adapted-factor figures).  Same tries, same order, same winner, same last point, same error as the serial loop.
 // ------------------------------------------------------------------------------------------
 struct CoopProp {
     const double* rec; int RW;          // [CT][RW]: the records the chains continue from (parameters at 3 ..)
@@ -22,11 +32,14 @@ struct CoopProp {
     unsigned long long* err;
     uint64_t seed;
     int offset, N, bs, rb_tries, user_n, smpl_iters, scout_after, scout_gl;
+    // CHOL only
+    const double* chol_L; int chol_per_chain;   // [np][np], or [Ng][np][np] by the chain's number in the population
+    double* zst; int zstw;                      // [CT][zstw >= np]: scratch, the normals of the try a lane segment evaluates
 };
 struct CoopSyncThreads { __device__ __forceinline__ void operator()() const { __syncthreads(); } };
 
 // tid: the lane of the tile, nwv: waves per tile (LPC = 64 nwv / CT lanes per chain, a power of two), lead: one thread of the workgroup
-template <int CT, class BAR>
+template <int CT, bool CHOL, class BAR>
 __device__ __forceinline__ void coop_mysample(const CoopProp X, const int t, const int tile, const int tid, const int nwv, const bool lead, const BAR bar) {
     const int np = X.np, bs = X.bs, RW = X.RW, HW = X.HW, RBW = X.RBW, N = X.N;
     const int lane = tid & 63;
@@ -58,6 +71,41 @@ __device__ __forceinline__ void coop_mysample(const CoopProp X, const int t, con
         const double* m01u = X.m01 + u * X.m01w;
         const double* zzu = X.rb + u * RBW + 1;
         bool okl = true;
+        if constexpr (CHOL) {   // (b0 = 0, bs = np)
+            const double* zv = zzu + rr * np;
+            if (rr >= X.rb_tries) {
+                double* st = X.zst + cc * X.zstw;
+                for (int q = sl; 2 * q < np; q += LPC) {
+                    const double2 zz2 = rng_prop_normal2_outofline(X.seed, gu, (uint32_t)t, (uint32_t)rr, (uint32_t)q);
+                    st[2 * q] = zz2.x;
+                    if (2 * q + 1 < np) st[2 * q + 1] = zz2.y;
+                }
+                zv = st;
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_wave_barrier();   // (the segment's lanes sit in one wave)
+            }
+            const double* __restrict__ Lu = X.chol_L + (X.chol_per_chain ? (size_t)gu * np * np : 0);
+            for (int k0 = 0; k0 < np; k0 += LPC) {
+                const int k = k0 + (((k0 / LPC) & 1) ? LPC - 1 - sl : sl);
+                if (k >= np) continue;
+                const double* __restrict__ Lk = Lu + (size_t)k * np;
+                double y = Lk[0] * zv[0];
+                for (int j = 1; j <= k; ++j) {
+                    const double pr = Lk[j] * zv[j];
+                    y = y + pr;
+                }
+                const double lbk = X.lb[k];
+                const double span = X.ub[k] - lbk;
+                const double step = sgu * y;               // x = mu + sigma * (L z)_k
+                const double x = m01u[k] + step;
+                if (!(x >= 0.0 && x <= 1.0)) okl = false;  // inclusive bounds, :405
+                const double sc = x * span;
+                out[k] = sc + lbk;   // mapto_ab, mprob.jl:271
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();   // (zst is read: the segment's next try may overwrite it)
+            return okl;
+        }
         for (int q = sl; 2 * q < b0 + bs; q += LPC) {
             if (2 * q + 1 < b0) continue;
             double z0, z1;
@@ -99,7 +147,7 @@ __device__ __forceinline__ void coop_mysample(const CoopProp X, const int t, con
             ++round_id;
             if (sl == 0) { head[0] = done ? 0ull : 1ull; head[1] = 0ull; if (!done) *round_word = round_id; }
             bar();
-            if (*round_word != round_id || base >= max_tries || rounds >= X.scout_after) break;   // (uniform over the workgroup: nobody open, no try left, or the stubborn chains' turn below)
+            if (*round_word != round_id || base >= max_tries || (!CHOL && rounds >= X.scout_after)) break;   // (uniform over the workgroup: nobody open, no try left, or the stubborn chains' turn below)
             const unsigned long long open = __ballot(lane < CT && *(const unsigned long long*)(X.h + lane * HW) != 0ull);
             const int n_open = __popcll(open);
             const int per = n_open ? CT / n_open : 0;      // tries per open chain in this round (>= 1)
@@ -141,7 +189,7 @@ __device__ __forceinline__ void coop_mysample(const CoopProp X, const int t, con
         // and is then evaluated once more, in full, by the chain's own lanes (one_try: the same arithmetic as ever).
         // Scratch: the head of the chain's (still unused) history row — [0]: open, [1]: lowest successful try, [3]: next try
         // to hand out ([2] of row 0 is the workgroup's round word); double 4 of rows 0 .. CT / 8 - 1: the open chains' numbers, a byte each.
-        {
+        if constexpr (!CHOL) {
             unsigned long long* head = (unsigned long long*)(X.h + cc * HW);
             ++round_id;
             const bool more = !done && base < max_tries;

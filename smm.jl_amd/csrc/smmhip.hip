@@ -104,6 +104,9 @@ struct UserObjective {
     std::vector<char> tile_sh_code;        // ... its form for a SHARD (SMM_TILE_SH as well): compiled only when a sharded context first wants it
     int tile_sh_state = 0;
     std::string tile_sh_log;
+    std::vector<char> tile_chol_code;      // ... its form for proposals with a Cholesky factor (SMM_TILE_CHOL as well): compiled only when a context with a factor first wants it
+    int tile_chol_state = 0;
+    std::string tile_chol_log;
     bool rng = false;                      // SMM_USER_OBJECTIVE_RNG / SMM_USER_PARTIAL_RNG: takes the library's stream (smm_register_user_objective_rng)
 };
 // the device headers the persistent kernel is made of, as text: hiprtc compiles them together with the user's source
@@ -322,11 +325,12 @@ bool user_persist_compile(UserObjective& u) {   // (g_user_mutex held)
 
 // k_chain_persist_tile with a user objective in its MAP-REDUCE form inside (smm_register_user_objective_lanes; SMM_TILE_USER in
 // smm_chain_persist_tile.hpp): the same recipe, on demand, once per registered objective — and once more as a shard's form (sh: SMM_TILE_SH),
-// only when a sharded context wants it
-bool user_tile_compile(UserObjective& u, const bool sh = false) {   // (g_user_mutex held)
-    int& state = sh ? u.tile_sh_state : u.tile_state;
-    std::string& tlog = sh ? u.tile_sh_log : u.tile_log;
-    std::vector<char>& code = sh ? u.tile_sh_code : u.tile_code;
+// only when a sharded context wants it, and as the form for a Cholesky factor (chol: SMM_TILE_CHOL; never a shard's), only when a context
+// with a factor wants it
+bool user_tile_compile(UserObjective& u, const bool sh = false, const bool chol = false) {   // (g_user_mutex held)
+    int& state = chol ? u.tile_chol_state : sh ? u.tile_sh_state : u.tile_state;
+    std::string& tlog = chol ? u.tile_chol_log : sh ? u.tile_sh_log : u.tile_log;
+    std::vector<char>& code = chol ? u.tile_chol_code : sh ? u.tile_sh_code : u.tile_code;
     if (state != 0) return state > 0;
     state = -1;
     if (u.source.empty() || u.lanes == 0) { tlog = "not the map-reduce form"; return false; }
@@ -339,6 +343,7 @@ bool user_tile_compile(UserObjective& u, const bool sh = false) {   // (g_user_m
         tu += USER_PRELUDE_LANES;
     tu += u.source;
     if (sh) tu += "\n#define SMM_TILE_SH 1";
+    if (chol) tu += "\n#define SMM_TILE_CHOL 1";
     tu += "\n#define SMM_TILE_USER 1\n#include \"smmhip.h\"\n#include \"smm_rng.hpp\"\nusing namespace smm;\n#include \"smm_params.hpp\"\n"
           "#include \"smm_walk_lean.hpp\"\n#include \"smm_propose.hpp\"\n#include \"smm_chain.hpp\"\n#include \"smm_p2p.hpp\"\n#include \"smm_chain_norm.hpp\"\n"
           "#include \"smm_chain_persist.hpp\"\n#include \"smm_chain_persist_loc.hpp\"\n#include \"smm_chain_persist_tile.hpp\"\n";
@@ -1241,6 +1246,8 @@ PersistKernel persist_kernel(const Ctx* c, const Forms& F) {
                : P.dense_A2f ? (F.persist_sh ? "tile_dense2_shard" : "tile_dense2") : (F.persist_sh ? "tile_dense_shard" : "tile_dense");
         if (c->obj == SMM_OBJ_USER) K.mfn = c->pfn;   // (the same kernel, compiled with the user's map-reduce objective inside: user_tile_compile)
         else if (F.persist_sh) K.fn = dense ? (const void*)k_chain_persist_tile<2, false, true> : (const void*)k_chain_persist_tile<1, false, true>;
+        else if (P.chol_L && P.mi_pct) K.fn = dense ? (const void*)k_chain_persist_tile<2, true, false, true> : (const void*)k_chain_persist_tile<1, true, false, true>;
+        else if (P.chol_L) K.fn = dense ? (const void*)k_chain_persist_tile<2, false, false, true> : (const void*)k_chain_persist_tile<1, false, false, true>;
         else if (P.mi_pct) K.fn = dense ? (const void*)k_chain_persist_tile<2, true> : (const void*)k_chain_persist_tile<1, true>;
         else K.fn = dense ? (const void*)k_chain_persist_tile<2> : (const void*)k_chain_persist_tile<1>;
     }
@@ -1324,6 +1331,7 @@ PersistArgs persist_args(const Ctx* c, int t0, int t1, bool pregen, unsigned lon
     A.slow_read = c->H.pr_slow_read;
     A.tables_local = c->F.persist_sh_big ? 1 : 0; A.unit_sh = P.lean_unit == 16 ? 4 : (P.lean_unit == 8 ? 3 : 2); A.scout_after = P.scout_after; A.scout_gl = P.scout_gl;
     A.u_lanes = c->u_lanes; A.n_udata = c->n_objp;
+    A.chol_L = P.chol_L; A.chol_per_chain = P.chol_per_chain;
     A.epoch = c->pr_epoch; A.sigma_adjust_by = P.sigma_adjust_by; A.thr = P.mi_value; A.seed = P.seed; A.tmo = tmo;
     return A;
 }
@@ -1697,12 +1705,13 @@ Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
                          (lds ? K <= XLDS_MAX : (big && Ng <= 32768 && K <= 65535 && (size_t)Ng * 4 <= (size_t)160 * 1024));
     // ... and for the objectives a whole tile evaluates (smm_chain_persist_tile.hpp): objfunc_norm with any number of parameters — the
     // reference's larger examples have 6 and 18, Examples.jl:210-230, 232-319 — and the dense simulation (BASELINE config 5); one
-    // threshold >= 0 (or NaN) for all chains, isotropic proposals, one 16-chain tile per workgroup, all of them resident
+    // threshold >= 0 (or NaN) for all chains, isotropic proposals or a Cholesky factor (the kernel's CH form: no LDS of its own), one 16-chain
+    // tile per workgroup, all of them resident
     const int tile_kind = obj_kind(c->obj);
     // ... and a USER objective in its map-reduce form (smm_register_user_objective_lanes) whose lanes are a whole share of the tile's 512
     const bool user_tile = user_obj && c->u_lanes > 0 && c->u_lanes <= WG && WG % c->u_lanes == 0 && PT_CT % (WG / c->u_lanes) == 0 && !P.mi_pct;   // (compiled for ONE threshold)
     const bool want_tile = (tile_kind == 1 || tile_kind == 2 || user_tile) && !(F.norm_fast && np <= 2 && ns <= WG * PR_ZR) && N == Ng && Ng >= 2 && lds &&
-                           mi_ok && minus && K <= XLDS_MAX && Ng <= XLDS_MAX && !c->deep_plan && !chol && P.dbg == 0 && !H.persist_off &&
+                           mi_ok && minus && K <= XLDS_MAX && Ng <= XLDS_MAX && !c->deep_plan && P.dbg == 0 && !H.persist_off &&
                            !H.persist_tile_off && P.RW <= PT_LPC * PT_NJ && (tile_kind != 2 || N % PT_CT == 0) && (N + PT_CT - 1) / PT_CT <= 2 * n_cus &&
                            persist_tile_smem(c) <= (size_t)160 * 1024;
     // ... and as a shard of a sharded run (smm_bgp_p2p_step; SH of smm_chain_persist_tile.hpp): equal shards of whole tiles, the LDS plan
@@ -1807,13 +1816,14 @@ int persist_occupancy(Ctx* c, const Forms& F, int objective_id) {
         {
             std::lock_guard<std::mutex> lock(g_user_mutex);
             UserObjective& u = g_user_objectives[objective_id - SMM_OBJ_USER_BASE];
-            if (!(tile ? user_tile_compile(u, F.persist_sh) : user_persist_compile(u))) {
+            const bool chol = tile && !F.persist_sh && c->P.chol_L != nullptr;   // (select_forms gives a shard with a factor no persistent form)
+            if (!(tile ? user_tile_compile(u, F.persist_sh, chol) : user_persist_compile(u))) {
                 if (getenv("SMMHIP_VERBOSE"))
                     fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n",
-                            (tile ? (F.persist_sh ? u.tile_sh_log : u.tile_log) : u.persist_log).c_str());
+                            (tile ? (chol ? u.tile_chol_log : F.persist_sh ? u.tile_sh_log : u.tile_log) : u.persist_log).c_str());
                 return 0;
             }
-            HIPCHK(hipModuleLoadData(&c->pmod, (tile ? (F.persist_sh ? u.tile_sh_code : u.tile_code) : u.persist_code).data()));
+            HIPCHK(hipModuleLoadData(&c->pmod, (tile ? (chol ? u.tile_chol_code : F.persist_sh ? u.tile_sh_code : u.tile_code) : u.persist_code).data()));
         }
         HIPCHK(hipModuleGetFunction(&c->pfn, c->pmod, tile ? "smm_user_persist_tile_kernel" : "smm_user_persist_kernel"));
     }
