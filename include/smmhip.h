@@ -640,6 +640,52 @@ int  smm_get_state(void* ctx, smm_state_t* out);
  * raise — is returned by THIS call, once, and nothing is uploaded: an error never disappears into a recovery the caller did not know it was
  * making.  The next smm_set_state goes through. */
 int  smm_set_state(void* ctx, const smm_state_t* in, const smm_history_t* hist /* iterations 0..iter-1 */);
+
+/* The starting population: every chain from its own point, installed on the device as the chain's COMPLETED iteration 1.  The reference
+ * starts all chains at MProb.initial_value (iteration 1 of every chain proposes it, AlgoBGP.jl:426-427); the search over a space-filling set
+ * of points in the box is the role of its sobolsearch.jl.  Both calls are valid only on a context that has completed no iteration (iter == 0;
+ * later: SMM_ERR_STATE); after success iter == 1 and stepping continues at iteration 2 in whatever form the context has chosen.
+ *
+ * Install contract: for every chain the device holds exactly what a fresh context would hold after smm_bgp_step(ctx, 1) if that chain's
+ * initial_value were its start (as smm_get_history / smm_get_state report it): history row 0 — params = the start, value and sim_moments
+ * = its evaluation, status = 1 and prob = 1 (doAcceptReject! at iteration 1 accepts whatever the objective returned, AlgoBGP.jl:326-332),
+ * accepted = 1, curr_val = best_val = value, best_id = 1, exchanged = 0 —, the last-accepted record (the same evaluation), and the chain
+ * state: accept_rate = 1, n_noex = n_acc_noex = 1, best = (value, 1), sigma untouched.  The context's bookkeeping is what smm_set_state
+ * leaves for iter == 1 (no exchange pending; a NaN value among the installed ones is remembered as there).  No exchange belongs to
+ * iteration 1 (exchange_from_iter >= 2).
+ *
+ * smm_set_population: the caller supplies the starts, [np][N] for the LOCAL chains; each is evaluated once (evaluated = N) and installed
+ *   whatever its evaluation says; pick = 0 for every chain.  A start outside [lb, ub], or a NaN: SMM_ERR_INVALID_ARG with the (1-based global)
+ *   chain and the parameter in the message, nothing installed.  Scratch: N x ((np + nm + 1) x 8 + 4) bytes, one batch.
+ * smm_scatter_population: for each chain M >= 1 candidates are generated, evaluated and reduced on the device; initial_value is evaluated once
+ *   (evaluated = N x M + 1).
+ *   Candidates (numerical contract; every operation rounded on its own, no fma).  Candidate m of global chain g = chain_offset + i,
+ *   parameter k: the Philox4x32-10 block x = philox(counter {g, m, k >> 1, 0}, key (lo32(seed), hi32(seed) ^ (7 * 0x9E3779B9))) (stream 7 of the
+ *   library's generator, smm.jl_amd/csrc/smm_rng.hpp: STREAM_POP); u = (x0:x1 >> 11) * 2^-53 for even k, (x2:x3 >> 11) * 2^-53 for odd k; with
+ *   c = (init_k - lb_k) / (ub_k - lb_k) (mapto_01, mprob.jl:248) and 0 < spread <= 1: lo = max(0, c - spread / 2), hi = min(1, c + spread / 2),
+ *   x01 = lo + u * (hi - lo), theta_k = x01 * (ub_k - lb_k) + lb_k (mapto_ab, mprob.jl:271, as the proposal computes it).  spread == 1 around a
+ *   centred init covers the whole box.  The key is the GLOBAL chain id: a shard generates exactly the candidates the single-shard run
+ *   generates for its chains.
+ *   Selection: a candidate is valid when its status >= 1 and its value is finite and >= 0; invalid ones are skipped (in a search they are not
+ *   a hard error).  The valid candidate with the lowest value wins, ties to the lowest m.  With keep_init != 0 initial_value competes as
+ *   candidate -1 and wins ties; when no candidate is valid it is the start whatever keep_init says (pick = -1).  The winner's evaluation is
+ *   installed as computed (value, sim_moments); it is not evaluated a second time.  A user objective with a stream draws from opts.seed, as in
+ *   BGP steps (common random numbers).
+ *   SMM_ERR_INVALID_ARG: M < 1, spread outside (0, 1] or NaN, (int64)M * N_global >= 2^31.
+ *   Scratch: chains go in batches whose candidates and results — M x ((np + nm + 1) x 8 + 4) bytes per chain — stay under 64 MiB (at least one
+ *   chain per batch); freed before the call returns.
+ * Both: out may be NULL, and so may any pointer in it.  Ordered on smm_stream behind everything enqueued before (a persistent launch is
+ * settled first, as smm_set_state does) and synchronised before they return.  A hard error nobody has been told of yet is returned once, and
+ * nothing is installed.  SMM_ERR_MAXITER on a context without room for one iteration.  smm_describe then ends in "population=set" or
+ * "population=scatter pop_M=.. pop_spread=..". */
+typedef struct {            /* caller-allocated, any pointer may be NULL */
+    double*  start;         /* [np][N] the point each chain starts from            */
+    double*  value;         /* [N]     its objective value                          */
+    int32_t* pick;          /* [N]     index of the chosen candidate, -1 = initial_value */
+    int64_t  evaluated;     /* out: objective evaluations performed                 */
+} smm_population_t;
+int  smm_set_population(void* ctx, const double* starts /* [np][N], host */, smm_population_t* out);
+int  smm_scatter_population(void* ctx, int32_t M, double spread, int32_t keep_init, smm_population_t* out);
 int  smm_get_timing(void* ctx, smm_timing_t* out);
 /* on = 1: bracket every kernel of smm_bgp_step with hipEvents on the ctx stream so that
  * smm_get_timing reports iter_kernel_ms / exch_kernel_ms (sums over the last step; each bracket

@@ -18,6 +18,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
 export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_set_population!, hip_scatter_population!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
 const ABI_VERSION = 3
@@ -145,6 +146,13 @@ struct SmmTrace
     quantile::Ptr{Cdouble}
     best_value::Ptr{Cdouble}
     best_chain::Ptr{Int32}
+end
+
+struct SmmPopulation
+    start::Ptr{Cdouble}
+    value::Ptr{Cdouble}
+    pick::Ptr{Int32}
+    evaluated::Int64
 end
 
 struct SmmState
@@ -574,6 +582,42 @@ function hip_adapt_proposal!(h::HipBGP, t0::Integer, t1::Integer; accepted_only:
     GC.@preserve status check(h.ctx, ccall(sym(:smm_adapt_proposal), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cdouble, Ptr{Int32}),
                                            h.ctx, t0, t1, accepted_only ? 1 : 0, min_draws, normalize ? 1 : 0, Float64(ridge), pointer(status)))
     return status
+end
+
+# the starting population (include/smmhip.h): both calls fill (start [N, np], value [N], pick [N], evaluated)
+function population_call(h::HipBGP, call)
+    start = Matrix{Float64}(undef, h.N, h.np); value = Vector{Float64}(undef, h.N); pick = Vector{Int32}(undef, h.N)
+    evaluated = 0
+    GC.@preserve start value pick begin
+        out = Ref(SmmPopulation(pointer(start), pointer(value), pointer(pick), 0))
+        check(h.ctx, call(out))
+        evaluated = Int(out[].evaluated)
+    end
+    return (start = start, value = value, pick = pick, evaluated = evaluated)
+end
+
+"""
+    hip_set_population!(h, starts) -> (start, value, pick, evaluated)
+
+Every chain from its own point: `starts[c, k]` (chain, parameter), installed on the device as each chain's completed iteration 1
+(`smm_set_population`).  Only on a context that has not stepped; afterwards `hip_iter(h) == 1`.
+"""
+function hip_set_population!(h::HipBGP, starts::Matrix{Float64})
+    size(starts) == (h.N, h.np) || throw(ArgumentError("starts must be (N, np) = $((h.N, h.np))"))
+    return GC.@preserve starts population_call(h, out -> ccall(sym(:smm_set_population), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{SmmPopulation}),
+                                                                 h.ctx, pointer(starts), out))
+end
+
+"""
+    hip_scatter_population!(h, M; spread = 1.0, keep_init = true) -> (start, value, pick, evaluated)
+
+Scatter search on the device (`smm_scatter_population`, the role of the reference's sobolsearch.jl): `M` candidates per chain in the box
+of width `spread` (in [0, 1]-space) around the initial value, the best valid one installed as the chain's completed iteration 1;
+`pick[c] == -1`: chain `c` starts from the initial value.  Only on a context that has not stepped.
+"""
+function hip_scatter_population!(h::HipBGP, M::Integer; spread::Real = 1.0, keep_init::Bool = true)
+    return population_call(h, out -> ccall(sym(:smm_scatter_population), Cint, (Ptr{Cvoid}, Cint, Cdouble, Cint, Ptr{SmmPopulation}),
+                                           h.ctx, M, Float64(spread), keep_init ? 1 : 0, out))
 end
 
 "per-chain state: what `save` / `readMalgo` / `restart!` need besides the history (AlgoAbstract.jl:83-102)"

@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, pooled_summary, chain_histogram, population_trace, adapt_proposal!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -426,6 +426,21 @@ function adapt_proposal!(algo::MAlgoBGPHip; t0::Integer = 0, t1 = nothing, accep
     hip = getfield(algo, :hip)
     return SMMHip.hip_adapt_proposal!(hip, t0, t1 === nothing ? SMMHip.hip_iter(hip) : t1; accepted_only = accepted_only,
                                       min_draws = min_draws === nothing ? hip.np + 1 : min_draws, normalize = normalize, ridge = ridge)
+end
+
+"""
+    scatter_start!(algo; M = 64, spread = 1.0, keep_init = true) -> (start, value, pick, evaluated)
+
+Scatter search for every chain's start on the device (`SMMHip.hip_scatter_population!`; the role of the reference's sobolsearch.jl):
+only on an algorithm that has not stepped.  Afterwards `algo.i == 1` and the chains hold their first iteration, as after one
+`computeNextIteration!`.  Not a method of `SMM`: the reference starts every chain at the initial value.
+"""
+function scatter_start!(algo::MAlgoBGPHip; M::Integer = 64, spread::Real = 1.0, keep_init::Bool = true)
+    (getfield(algo, :stepped) == 0 && getfield(algo, :deferred) == 0) || error("scatter_start!: the algorithm has stepped already")
+    r = SMMHip.hip_scatter_population!(getfield(algo, :hip), M; spread = spread, keep_init = keep_init)
+    setfield!(algo, :stepped, 1)
+    setfield!(algo, :i, 1)
+    return r
 end
 
 "`summary(m::MAlgoBGP)` (AlgoBGP.jl:541-550) on the synced chains"

@@ -130,6 +130,12 @@ class smm_trace_t(C.Structure):
     ]
 
 
+class smm_population_t(C.Structure):
+    _fields_ = [
+        ("start", c_double_p), ("value", c_double_p), ("pick", c_int32_p), ("evaluated", C.c_int64),
+    ]
+
+
 class smm_timing_t(C.Structure):
     _fields_ = [
         ("step_ms", C.c_double), ("iter_kernel_ms", C.c_double), ("exch_kernel_ms", C.c_double),
@@ -186,6 +192,8 @@ SYMBOLS = [
     ("smm_adapt_proposal", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, c_int32_p]),
     ("smm_get_state", C.c_int, [C.c_void_p, C.POINTER(smm_state_t)]),
     ("smm_set_state", C.c_int, [C.c_void_p, C.POINTER(smm_state_t), C.POINTER(smm_history_t)]),
+    ("smm_set_population", C.c_int, [C.c_void_p, c_double_p, C.POINTER(smm_population_t)]),
+    ("smm_scatter_population", C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.POINTER(smm_population_t)]),
     ("smm_get_timing", C.c_int, [C.c_void_p, C.POINTER(smm_timing_t)]),
     ("smm_get_Z", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_profiling", C.c_int, [C.c_void_p, C.c_int32]),

@@ -420,6 +420,29 @@ class BGPContext:
         ss, hs = sb.struct(), hb.struct()
         self._check(self._fn("set_state")(self._ctx, C.byref(ss), C.byref(hs)))
 
+    # --- the starting population (include/smmhip.h: smm_set_population, smm_scatter_population) --------------------------------
+    def _population(self, call):
+        r = dict(start=np.empty((self.np, self.N)), value=np.empty(self.N), pick=np.empty(self.N, np.int32))
+        s = self._out(A.smm_population_t, r)
+        self._check(call(C.byref(s)))
+        r["evaluated"] = int(s.evaluated)
+        return r
+
+    def set_population(self, starts):
+        """every local chain from its own point, starts [np][N], installed on the device as the chain's completed iteration 1
+        (smm_set_population; only before the first step).  Returns a dict: start [np][N], value [N], pick [N] (0), evaluated"""
+        st = A.f64(starts)
+        if st.shape != (self.np, self.N):
+            raise ValueError("set_population: starts must be [np][N] = %s, got %s" % ((self.np, self.N), st.shape))
+        return self._population(lambda out: self._fn("set_population")(self._ctx, A.dptr(st), out))
+
+    def scatter_population(self, M, spread=1.0, keep_init=True):
+        """scatter search on the device (smm_scatter_population; only before the first step): M candidates per chain in the box of width
+        `spread` (in [0, 1]-space) around initial_value, evaluated, the best valid one installed as the chain's completed iteration 1;
+        keep_init: initial_value competes (and wins ties).  Returns a dict: start [np][N], value [N], pick [N] (the chosen candidate,
+        -1 = initial_value), evaluated"""
+        return self._population(lambda out: self._fn("scatter_population")(self._ctx, int(M), float(spread), int(bool(keep_init)), out))
+
     def timing(self):
         t = A.smm_timing_t()
         self._check(self._fn("get_timing")(self._ctx, C.byref(t)))

@@ -72,6 +72,7 @@ using namespace smm;
 #include "smm_group.hpp"
 #include "smm_hist.hpp"
 #include "smm_trace.hpp"
+#include "smm_population.hpp"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -404,6 +405,7 @@ struct Hooks {
     int stats_mode_bins = STATS_MODE_BINS;   // partner ids per pass of k_stats_mode (1 .. STATS_MODE_BINS): several passes at small populations
     long long group_wide_min = STATS_LDS_N + 1;   // pooled columns of at least so many draws take the grid-wide select (1 .. STATS_LDS_N + 1)
     int hist_lds_bins = 1 << 30;   // bins (1-D) and bins2 (2-D) above this count into global memory, not LDS (1 ..)
+    size_t pop_scratch = 0;        // the candidate scratch cap of smm_scatter_population instead of POP_SCRATCH_CAP (0: that cap): several batches of chains at small sizes
 };
 Hooks read_hooks() {
     Hooks H;
@@ -439,6 +441,7 @@ Hooks read_hooks() {
     if (const char* v = SMM_HOOK("SMMHIP_STATS_MODE_BINS")) H.stats_mode_bins = std::min(STATS_MODE_BINS, std::max(1, atoi(v)));
     if (const char* v = SMM_HOOK("SMMHIP_GROUP_WIDE_MIN")) H.group_wide_min = std::min((long long)STATS_LDS_N + 1, std::max(1ll, atoll(v)));
     if (const char* v = SMM_HOOK("SMMHIP_HIST_LDS_BINS")) H.hist_lds_bins = std::max(1, atoi(v));
+    if (const char* v = SMM_HOOK("SMMHIP_POP_SCRATCH")) H.pop_scratch = (size_t)strtoull(v, nullptr, 10);
     return H;
 }
 // Which stand-alone kernel resolves exchangeMoves! (AlgoBGP.jl:647-716) — ONE decision, taken once per context (select_forms),
@@ -535,6 +538,8 @@ struct Ctx {
     uint2* slot8_buf[2] = {nullptr, nullptr};
     bool deep_plan = false;      // an injected pair list has an iteration of more than LV_MAXLEV dependency levels
     bool nan_values = false;     // the uploaded state holds NaN values (smm_set_state)
+    int pop_kind = 0, pop_M = 0; // the starting population installed on this context: 0 none, 1 smm_set_population, 2 smm_scatter_population (smm_describe)
+    double pop_spread = 0.0;
     uint32_t* cb_scratch = nullptr;
     std::vector<uint32_t> cone_big_ok;   // per iteration of the plan window: its cones fit their caps
     // ... their windows are planned AHEAD: the plan of a window depends on (seed, iteration) only, so while the chain kernels of one
@@ -906,6 +911,25 @@ void launch_user_kernel(Ctx* c, const double* theta, int n, double* simM, double
         HIPCHK(hipModuleLaunchKernel(fn, (unsigned)n, 1, 1, (unsigned)c->u_lanes, 1, 1, 0, c->stream, args, nullptr));
     else
         HIPCHK(hipModuleLaunchKernel(fn, (unsigned)((n + 127) / 128), 1, 1, 128, 1, 1, 0, c->stream, args, nullptr));
+}
+
+// n evaluations on device pointers, onto the context's stream (smm_eval_batch and the starting population share it): the built-in objectives read
+// params [np][n] and write simM [nm][n] and status as int8; a user objective's kernel (launch_user_kernel) reads theta [n][np] and writes
+// simM [n][nm] and status as int
+void launch_eval_dev(Ctx* c, const double* params, int n, double* value, double* simM, void* status) {
+    const KParams& P = c->P;
+    if (c->obj == SMM_OBJ_USER) {
+        launch_user_kernel(c, params, n, simM, value, (int*)status);
+        return;
+    }
+    constexpr int CT = 8;
+    if (is_sim(c->obj))
+        hipLaunchKernelGGL((k_eval_batch<1, CT>), dim3((n + CT - 1) / CT), dim3(WG), tile_smem_base(c, CT), c->stream, P, params, n, value, simM, (int8_t*)status);
+    else if (c->obj == SMM_OBJ_DENSE)
+        hipLaunchKernelGGL((k_eval_batch<2, 16>), dim3((n + 15) / 16), dim3(WG), tile_smem_base(c, 16), c->stream, P, params, n, value, simM, (int8_t*)status);
+    else
+        hipLaunchKernelGGL((k_eval_batch<0, CT>), dim3((n + CT - 1) / CT), dim3(WG), tile_smem_base(c, CT), c->stream, P, params, n, value, simM, (int8_t*)status);
+    HIPCHK(hipGetLastError());
 }
 
 void launch_chain_iter(Ctx* c, int t, int flags) {
@@ -1890,6 +1914,7 @@ int check_window(Ctx* c, int t0, int t1) {
 }  // namespace
 
 #include "smm_reducers_host.hpp"
+#include "smm_population_host.hpp"
 
 extern "C" {
 
@@ -2876,7 +2901,8 @@ static void user_eval_batch(Ctx* c, const double* params, int32_t M, double* val
         for (int k = 0; k < P.np; ++k) tp[(size_t)i * P.np + k] = params[(size_t)k * M + i];
     DevBuf<int> dsi((size_t)M);
     HIPCHK(hipMemcpyAsync(dp.p, tp.data(), tp.size() * 8, hipMemcpyHostToDevice, c->stream));
-    launch_user_kernel(c, dp.p, M, dm.p, dv.p, dsi.p, base_seed);
+    if (base_seed) launch_user_kernel(c, dp.p, M, dm.p, dv.p, dsi.p, base_seed);
+    else launch_eval_dev(c, dp.p, M, dv.p, dm.p, dsi.p);
     HIPCHK(hipMemcpyAsync(value, dv.p, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(tm.data(), dm.p, tm.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(ts.data(), dsi.p, ts.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -2901,17 +2927,7 @@ int smm_eval_batch(void* ctx, const double* params, int32_t M, double* value, do
         DevBuf<double> dp((size_t)P.np * M), dv((size_t)M), dm((size_t)P.nm * M);
         DevBuf<int8_t> ds((size_t)M);
         HIPCHK(hipMemcpyAsync(dp.p, params, (size_t)P.np * M * 8, hipMemcpyHostToDevice, c->stream));
-        constexpr int CT = 8;
-        if (is_sim(c->obj))
-            hipLaunchKernelGGL((k_eval_batch<1, CT>), dim3((M + CT - 1) / CT), dim3(WG), tile_smem_base(c, CT), c->stream, P, dp.p, M, dv.p,
-                               dm.p, ds.p);
-        else if (c->obj == SMM_OBJ_DENSE)
-            hipLaunchKernelGGL((k_eval_batch<2, 16>), dim3((M + 15) / 16), dim3(WG), tile_smem_base(c, 16), c->stream, P, dp.p, M, dv.p, dm.p,
-                               ds.p);
-        else
-            hipLaunchKernelGGL((k_eval_batch<0, CT>), dim3((M + CT - 1) / CT), dim3(WG), tile_smem_base(c, CT), c->stream, P, dp.p, M, dv.p,
-                               dm.p, ds.p);
-        HIPCHK(hipGetLastError());
+        launch_eval_dev(c, dp.p, M, dv.p, dm.p, ds.p);
         HIPCHK(hipMemcpyAsync(value, dv.p, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(sim_moments, dm.p, (size_t)P.nm * M * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(status, ds.p, (size_t)M, hipMemcpyDeviceToHost, c->stream));
@@ -3138,7 +3154,11 @@ int smm_describe(void* ctx, char* out, int32_t cap) {
                      : c->F.norm_fast ? ((P.lean_wide && !P.mi_pct) ? "inline_lean_wide" : (c->F.lean_plan && !P.mi_pct) ? "inline_lean" : "inline_slots") : c->F.gen_lean ? "inline_lean16" : "inline_slots";
     const int n = snprintf(out, (size_t)cap, "chain=%s walk=%s exchange=%s persistent=%s plan=%s window=%d", chain.name, walk, xk[c->F.xk], persist_kernel(c, c->F).name,
                            c->F.plan == PLAN_BIG ? (c->F.plan_ahead ? "big_ahead" : "big") : c->F.plan == PLAN_LDS ? "lds" : "none", c->F.plan_cap);
-    if (c->obj == SMM_OBJ_USER && n >= 0 && n < cap) snprintf(out + n, (size_t)(cap - n), " ct=%d", chain.ct);   // (the three launches' tile width)
+    int n2 = n;
+    if (c->obj == SMM_OBJ_USER && n >= 0 && n < cap) n2 = n + snprintf(out + n, (size_t)(cap - n), " ct=%d", chain.ct);   // (the three launches' tile width)
+    // (only once a starting population has been installed: smm_set_population / smm_scatter_population)
+    if (c->pop_kind == 1 && n2 >= 0 && n2 < cap) snprintf(out + n2, (size_t)(cap - n2), " population=set");
+    if (c->pop_kind == 2 && n2 >= 0 && n2 < cap) snprintf(out + n2, (size_t)(cap - n2), " population=scatter pop_M=%d pop_spread=%.17g", c->pop_M, c->pop_spread);
     return SMM_OK;
 }
 

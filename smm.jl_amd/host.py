@@ -722,6 +722,31 @@ def run(algo):
     return algo
 
 
+def _install_start(algo, r):
+    algo._invalidate()
+    algo.i = algo._ctx.state().iter
+    return r
+
+
+def set_start(algo, starts):
+    """every chain from its own point instead of MProb.initial_value: starts [np][N] (or a list of N parameter dicts), installed on the
+    device as every chain's completed iteration 1 (smm_set_population).  Only on a fresh MAlgoBGP (algo.i == 0); afterwards algo.i == 1
+    and run / computeNextIteration / history / summary / save / readMalgo / restart behave as after one iteration.  Returns a dict:
+    start [np][N], value [N], pick [N], evaluated"""
+    if len(starts) and isinstance(starts[0], dict):
+        names = ps2s_names(algo.m)
+        starts = np.array([[float(d[k]) for d in starts] for k in names])
+    return _install_start(algo, algo._ctx.set_population(starts))
+
+
+def scatter_start(algo, M=64, spread=1.0, keep_init=True):
+    """scatter search for every chain's start, on the device (smm_scatter_population; the role of the reference's sobolsearch.jl): M
+    candidates per chain in the box of width `spread` (in [0, 1]-space) around MProb.initial_value, the best valid one installed as the
+    chain's completed iteration 1; keep_init: initial_value competes and wins ties.  Only on a fresh MAlgoBGP (algo.i == 0); afterwards
+    algo.i == 1.  Returns a dict: start [np][N], value [N], pick [N] (-1 = initial_value), evaluated"""
+    return _install_start(algo, algo._ctx.scatter_population(M, spread, keep_init))
+
+
 def set_proposal(algo, L):
     """install proposal factor(s) between iterations (smm_set_proposal): [np][np] on a shared-factor run, [N][np][np] per chain"""
     algo._ctx.set_proposal(L)
