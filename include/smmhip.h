@@ -588,6 +588,61 @@ int  smm_get_trace(void* ctx, int32_t t0, int32_t t1, int32_t stride, int32_t se
                    const int32_t* group /* [N] or NULL */, int32_t n_groups,
                    const double* probs, int32_t n_probs, smm_trace_t* out);
 
+/* Rank-normalised convergence diagnostics of groups of chains computed on the device from the history it holds (Vehtari, Gelman, Simpson,
+ * Carpenter, Buerkner 2021): the rank-normalised split R-hat (bulk, folded, and their maximum), the multi-chain bulk, tail and mean ESS,
+ * and every chain's rank histogram (the rank plot), for each group g and each of smm_get_chain_diag's S = np + 1 state series, over the
+ * 0-based iterations [t0, t1), n = t1 - t0.  Group g is made of the LOCAL chains with group[c] == g (-1: in no group; a shard reports its
+ * own chains and its own groups), in ascending local index; group NULL with n_groups == 1: every local chain in group 0.
+ * Caller-allocated; any pointer may be NULL (not returned).  Read-only and ordered like smm_get_chain_stats (it settles, flushes and
+ * synchronises, and changes no state, history or generator; it can sit between smm_bgp_step_async calls).  It uses smm_get_chain_stats'
+ * scratch, grown where needed to one series of the largest group: 72 bytes per pooled value (values, keys, indices, ranks, scores) and
+ * (80 + 32 min(256, max_lag + 1)) bytes per split chain, 256 KB more for a column above 8192 values; what does not fit is reduced in
+ * batches of series and, where one series of every group does not fit, of groups, each batch reading the window once more.  Results:
+ * 31 S n_groups x 8 bytes and, with rank_hist, n_bins S N x 8.  SMM_ERR_INVALID_ARG: NULL ctx or out, t0 < 0, t1 > completed iterations,
+ * n < 8, max_lag outside [1, h - 1] (h = n / 2), n_bins < 0, rank_hist with n_bins == 0, n_groups < 1, group NULL with n_groups != 1, a
+ * group id outside [-1, n_groups), a group whose pooled column would hold more than 2^31 - 1 values; the outputs are then untouched.
+ *
+ * Numerical contract (every operation rounded on its own, no fma; counts and ranks are 64-bit).  S(.), mean(.), the median and the
+ * quantile are the chain-stats ones; x_s(t) is smm_get_chain_diag's state series:
+ *   split chains : h = n / 2; the k members of g in ascending local index each give x[0:h] then x[n-h:n]: m = 2 k chains of length h,
+ *                  pooled in that order into M = m h values.
+ *   rank2_i      = 2 L + E + 1, L the number of pooled values strictly less than x_i, E the number equal to it, itself included (twice the
+ *                  average rank); -0.0 and +0.0 are equal.
+ *   z_i          = ndtri(((double)rank2_i * 0.5 - 0.375) / ((double)M + 0.25)), ndtri = Wichura's AS 241 PPND16 with its operations in
+ *                  their order, the logarithm smm_log, the square root IEEE's.
+ *   R-hat of m chains y_j: mu_j = mean(y_j), var_j = S((y_j - mu_j) (y_j - mu_j)) / (h - 1), W = mean(var), v = S((mu_j - mean(mu))
+ *                  (mu_j - mean(mu))) / (m - 1), var_plus = ((h - 1.0) / h) W + v, rhat = sqrt(var_plus / W): smm_get_chain_diag's
+ *                  arithmetic on the chains as they stand.  rhat_bulk: of the z chains.  rhat_folded: of the normal scores of
+ *                  f_i = |x_i - med|, med the median of the M pooled values (taken with -0.0 as +0.0).  rhat_rank = rhat_bulk >
+ *                  rhat_folded ? rhat_bulk : rhat_folded, NaN if either is.
+ *   ESS of m chains y_j: d_j = y_j - mu_j, acov_{j,t} = S(d_j[0:h-t] d_j[t:h]) / h, A_t = mean_j(acov_{j,t}), rho_0 = 1.0,
+ *                  rho_t = 1.0 - (W - A_t) / var_plus; P_j, J, Q_j, T and tau = -1.0 + 2.0 T from the rho exactly as in
+ *                  smm_get_chain_diag; ess = (double)M / tau.  This is the library's Geyer truncation (initial positive, monotone
+ *                  sequence) applied to the combined autocorrelation: Stan's estimator without its extra odd-lag term and without its
+ *                  M log10 M cap.  ess_bulk: of the z chains; ess_mean: of the x chains; ess_tail: the smaller of the ESS of the
+ *                  indicator chains (x <= q05 ? 1.0 : 0.0) and (x <= q95 ? 1.0 : 0.0), q the quantiles 0.05 and 0.95 of the pooled
+ *                  values, NaN if either is.
+ *   status       : [0] bulk, [3] mean: 2 when W == 0, var_plus == 0 or !(tau > 0) (ess NaN), else 1 when max_lag came before the
+ *                  truncation, else 0; [2] tail: the larger of its two chains' statuses; [1] folded: 2 when W == 0 or var_plus == 0,
+ *                  else 0.  A non-finite pooled value: 3 in all four, every statistic of the cell NaN and no count in rank_hist from
+ *                  it.  A group without members: 2 and NaN.
+ *   rank_hist    : a value of rank rank2 falls in bin ((rank2 - 1) n_bins) / (2 M) (64-bit integer division); chain c collects its 2 h
+ *                  values of series s in rank_hist[.][s][c]; a chain in no group gets zeros.
+ * The device stops computing the lags of a cell once its sequence is truncated: the results are those of computing every lag up to
+ * max_lag. */
+typedef struct {               /* caller-allocated; any pointer may be NULL; S = np + 1 series as in smm_chain_diag_t */
+    double*  rhat_rank;        /* [n_groups][S]  max(bulk, folded) rank-normalised split R-hat            */
+    double*  rhat_bulk;        /* [n_groups][S]                                                            */
+    double*  rhat_folded;      /* [n_groups][S]                                                            */
+    double*  ess_bulk;         /* [n_groups][S]  multi-chain ESS of the rank-normalised split chains       */
+    double*  ess_tail;         /* [n_groups][S]  min of the ESS of I(x <= q05) and of I(x <= q95)          */
+    double*  ess_mean;         /* [n_groups][S]  multi-chain ESS of the raw split chains                   */
+    int32_t* status;           /* [4][n_groups][S]  for bulk, folded, tail, mean: 0 ok, 1 max_lag first, 2 undefined, 3 non-finite */
+    int64_t* rank_hist;        /* [n_bins][S][N] each chain's pooled ranks, binned: the rank plot          */
+} smm_rank_diag_t;
+int  smm_get_rank_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32_t n_bins,
+                       const int32_t* group /* [N] or NULL */, int32_t n_groups, smm_rank_diag_t* out);
+
 /* Covariances of the chains' draws and the proposal factor between steps — adaptive Metropolis (Haario et al.) on top of chol_L: a
  * pilot run, then each chain's proposal shaped by the covariance of its own draws, without leaving the device.
  *

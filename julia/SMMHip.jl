@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_set_population!, hip_scatter_population!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
@@ -111,6 +111,17 @@ struct SmmChainDiag
     status::Ptr{Int32}
     acf::Ptr{Cdouble}
     rhat::Ptr{Cdouble}
+end
+
+struct SmmRankDiag
+    rhat_rank::Ptr{Cdouble}
+    rhat_bulk::Ptr{Cdouble}
+    rhat_folded::Ptr{Cdouble}
+    ess_bulk::Ptr{Cdouble}
+    ess_tail::Ptr{Cdouble}
+    ess_mean::Ptr{Cdouble}
+    status::Ptr{Int32}
+    rank_hist::Ptr{Int64}
 end
 
 struct SmmGroupStats
@@ -430,6 +441,34 @@ function hip_chain_diag(h::HipBGP, t0::Integer, t1::Integer; max_lag::Integer = 
                            h.ctx, t0, t1, max_lag, n_acf, ng > 0 ? pointer(g) : Ptr{Int32}(C_NULL), ng, cd))
     end
     return (accept_rate = rate, ess = ess, status = st, acf = acf, rhat = rhat)   # (the header's row-major = these column-major arrays)
+end
+
+"""
+    hip_rank_diag(h, t0, t1; max_lag = (t1 - t0) ÷ 2 - 1, n_bins = 20, groups = nothing) -> NamedTuple
+
+Rank-normalised diagnostics of groups of chains over iterations `t0+1 .. t1`, on the device (`smm_get_rank_diag`; Vehtari et al.
+2021): per series s (the parameters, then the objective value, `np + 1` of them) and group g `rhat_rank[s, g]` (the larger of
+`rhat_bulk` and `rhat_folded`), `ess_bulk[s, g]`, `ess_tail[s, g]`, `ess_mean[s, g]`, `status[s, g, 1:4]` (bulk, folded, tail, mean:
+0 ok, 1 `max_lag` reached first, 2 undefined, 3 non-finite) and `rank_hist[chain, s, bin]`, each chain's ranks in its group's pooled
+sample, binned (the rank plot).  `groups[chain]` holds 0-based group ids (-1 = none); `nothing`: every chain in one group.
+"""
+function hip_rank_diag(h::HipBGP, t0::Integer, t1::Integer; max_lag::Integer = (t1 - t0) ÷ 2 - 1, n_bins::Integer = 20,
+                       groups::Union{Nothing,AbstractVector{<:Integer}} = nothing)
+    N, S = h.N, h.np + 1
+    g = groups === nothing ? Int32[] : Vector{Int32}(groups)
+    groups === nothing || length(g) == N || throw(ArgumentError("groups needs one entry per chain"))
+    ng = groups === nothing ? 1 : (isempty(g) ? 0 : Int(maximum(g)) + 1)
+    rr = Matrix{Float64}(undef, S, ng); rb = Matrix{Float64}(undef, S, ng); rf = Matrix{Float64}(undef, S, ng)
+    eb = Matrix{Float64}(undef, S, ng); et = Matrix{Float64}(undef, S, ng); em = Matrix{Float64}(undef, S, ng)
+    st = Array{Int32}(undef, S, ng, 4); rh = Array{Int64}(undef, N, S, n_bins)
+    GC.@preserve g rr rb rf eb et em st rh begin
+        rd = SmmRankDiag(pointer(rr), pointer(rb), pointer(rf), pointer(eb), pointer(et), pointer(em), pointer(st),
+                         n_bins > 0 ? pointer(rh) : Ptr{Int64}(C_NULL))
+        check(h.ctx, ccall(sym(:smm_get_rank_diag), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Int32}, Cint, Ref{SmmRankDiag}),
+                           h.ctx, t0, t1, max_lag, n_bins, groups === nothing ? Ptr{Int32}(C_NULL) : pointer(g), ng, rd))
+    end
+    return (rhat_rank = rr, rhat_bulk = rb, rhat_folded = rf, ess_bulk = eb, ess_tail = et, ess_mean = em, status = st,
+            rank_hist = rh)   # (the header's row-major = these column-major arrays)
 end
 
 """

@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -338,6 +338,21 @@ function chain_diag(algo::MAlgoBGPHip; t0::Integer = 0, t1 = nothing, max_lag = 
     hip = getfield(algo, :hip)
     t1 = t1 === nothing ? SMMHip.hip_iter(hip) : t1
     return SMMHip.hip_chain_diag(hip, t0, t1; max_lag = max_lag === nothing ? t1 - t0 - 1 : max_lag, n_acf = n_acf, groups = groups)
+end
+
+"""
+    rank_diag(algo; t0 = 0, t1 = nothing, max_lag = nothing, n_bins = 20, groups = nothing) -> NamedTuple
+
+The rank-normalised split R-hat, the multi-chain bulk, tail and mean ESS and the rank plot of groups of chains over iterations
+`t0+1 .. t1` (default: every completed one), computed on the device from the history it holds (`SMMHip.hip_rank_diag`).  `max_lag`
+defaults to `(t1 - t0) ÷ 2 - 1`; `groups[chain]` holds 0-based group ids (-1 = none), `nothing`: every chain in one group.  Not a
+method of `SMM`: the reference has no such function.
+"""
+function rank_diag(algo::MAlgoBGPHip; t0::Integer = 0, t1 = nothing, max_lag = nothing, n_bins::Integer = 20, groups = nothing)
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    t1 = t1 === nothing ? SMMHip.hip_iter(hip) : t1
+    return SMMHip.hip_rank_diag(hip, t0, t1; max_lag = max_lag === nothing ? (t1 - t0) ÷ 2 - 1 : max_lag, n_bins = n_bins, groups = groups)
 end
 
 """

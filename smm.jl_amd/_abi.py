@@ -130,6 +130,13 @@ class smm_trace_t(C.Structure):
     ]
 
 
+class smm_rank_diag_t(C.Structure):
+    _fields_ = [
+        ("rhat_rank", c_double_p), ("rhat_bulk", c_double_p), ("rhat_folded", c_double_p), ("ess_bulk", c_double_p),
+        ("ess_tail", c_double_p), ("ess_mean", c_double_p), ("status", c_int32_p), ("rank_hist", C.POINTER(C.c_int64)),
+    ]
+
+
 class smm_population_t(C.Structure):
     _fields_ = [
         ("start", c_double_p), ("value", c_double_p), ("pick", c_int32_p), ("evaluated", C.c_int64),
@@ -186,6 +193,8 @@ SYMBOLS = [
                                      C.c_int32, C.c_int32, C.POINTER(smm_histogram_t)]),
     ("smm_get_trace", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_double_p, C.c_int32,
                                 C.POINTER(smm_trace_t)]),
+    ("smm_get_rank_diag", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32,
+                                    C.POINTER(smm_rank_diag_t)]),
     ("smm_get_chain_cov", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
     ("smm_get_proposal", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_proposal", C.c_int, [C.c_void_p, c_double_p]),

@@ -313,6 +313,33 @@ class BGPContext:
         self._check(self._fn("get_chain_diag")(self._ctx, int(t0), int(t1), int(max_lag), int(n_acf), gp, ng, C.byref(s)))
         return r
 
+    def rank_diag(self, t0=0, t1=None, max_lag=None, n_bins=20, groups=None, n_groups=None):
+        """rank-normalised diagnostics of groups of local chains over iterations [t0, t1), on the device (smm_get_rank_diag,
+        include/smmhip.h): a dict of numpy arrays rhat_rank / rhat_bulk / rhat_folded / ess_bulk / ess_tail / ess_mean [n_groups][S]
+        (S = np + 1: the parameters, then the objective value), status [4][n_groups][S] (bulk, folded, tail, mean) and rank_hist
+        [n_bins][S][N], each chain's pooled ranks binned (the rank plot; n_bins = 0: none).  groups: an int per chain (-1 = none),
+        n_groups by default groups.max() + 1, None: every local chain in one group.  max_lag defaults to (t1 - t0) // 2 - 1: the whole of
+        Geyer's sequence, the device stopping where it is truncated"""
+        t1 = self._t1(t1)
+        t0, t1, n_bins = int(t0), int(t1), int(n_bins)
+        if t1 - t0 < 8:
+            raise ValueError("rank_diag: the window must hold at least 8 iterations, got [%d, %d)" % (t0, t1))
+        h = (t1 - t0) // 2
+        max_lag = h - 1 if max_lag is None else int(max_lag)
+        if not 1 <= max_lag <= h - 1:
+            raise ValueError("rank_diag: max_lag must lie in [1, %d], got %d" % (h - 1, max_lag))
+        if n_bins < 0:
+            raise ValueError("rank_diag: n_bins must be >= 0, got %d" % n_bins)
+        g, gp, ng = self._groups("rank_diag", groups, n_groups)
+        if ng < 1:
+            raise ValueError("rank_diag: n_groups must be at least 1, got %d" % ng)
+        N, S = self.N, self.np + 1
+        r = {f: np.empty((ng, S)) for f in ("rhat_rank", "rhat_bulk", "rhat_folded", "ess_bulk", "ess_tail", "ess_mean")}
+        r.update(status=np.empty((4, ng, S), np.int32), rank_hist=np.empty((n_bins, S, N), np.int64))
+        s = self._out(A.smm_rank_diag_t, r, () if n_bins > 0 else ("rank_hist",))
+        self._check(self._fn("get_rank_diag")(self._ctx, t0, t1, max_lag, n_bins, gp, ng, C.byref(s)))
+        return r
+
     def group_stats(self, t0=0, t1=None, accepted_only=True, groups=None, probs=(), n_groups=None):
         """the pooled draws of groups of local chains over iterations [t0, t1), summarised on the device (smm_get_group_stats,
         include/smmhip.h): a dict of numpy arrays count / n_chains [n_groups], mean / median [n_groups][np], quantile

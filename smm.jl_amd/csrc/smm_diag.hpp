@@ -6,7 +6,8 @@
 //                   (a block-wide max of accepted ? row : -1); then the window 256 rows at a time (lane = iteration): a(t) is the
 //                   max-scan of accepted ? t : -1 across the lanes and the four waves, carried from block to block.  Writes the S = np + 1
 //                   carry-forward columns col [S][Nb][n] (params[a(t)][s], then value[a(t)]; NaN while no row is accepted) and counts
-//                   the window's non-exchanged iterations E and the accepted ones among them A.
+//                   the window's non-exchanged iterations E and the accepted ones among them A.  The walk itself is diag_state_rows,
+//                   which smm_rank.hpp's gather shares.
 //   k_diag_acov   : one workgroup per (chain, series) column: a non-finite entry ends it (status 3).  Otherwise the two halves' mean and
 //                   variance for R-hat (pw_sum, smm_stats.hpp), the column's mean, then d = x - mean (in LDS when n <= 8192,
 //                   else in place in the scratch column, read from L2).  The lags then go in blocks of 256, lane = lag: each lane sums
@@ -30,22 +31,19 @@ __device__ __forceinline__ int diag_block_max(int v, int* wred) {   // every thr
     return r;
 }
 
-__global__ __launch_bounds__(DIAG_WG) void k_diag_gather(const double* __restrict__ hrec, int N, int HW, int np, int t0, int n, int c0,
-                                                         int Nb, double* __restrict__ col, int* __restrict__ o_nacc,
-                                                         int* __restrict__ o_noex) {
-    __shared__ int wred[DIAG_WG / 64];
-    __shared__ int wtot[DIAG_WG / 64];
-    const int cl = xcd_chain(blockIdx.x, gridDim.x), c = c0 + cl;
+// the state rows of chain c over the window [t0, t0 + n), 256 iterations at a time (lane = iteration): emit(r, a) for every window
+// position r with a = a(t0 + r), the last accepted row at or before it (-1: none); counts the window's non-exchanged iterations (noex)
+// and the accepted ones among them (nacc) per thread.  Every thread of the block calls it.
+template <class Emit>
+__device__ __forceinline__ void diag_state_rows(const double* __restrict__ hrec, int N, int HW, int c, int t0, int n, int* wred, int* wtot,
+                                                int& nacc, int& noex, Emit emit) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int S = np + 1;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
     int carry = -1;   // a(t0 - 1): the look-back goes as far as row 0
     for (int r1 = t0; r1 > 0 && carry < 0; r1 -= DIAG_WG) {
         const int r = r1 - DIAG_WG + tid;
         const int v = (r >= 0 && hrec[((size_t)r * N + c) * HW + H_ACC] != 0.0) ? r : -1;
         carry = diag_block_max(v, wred);
     }
-    int nacc = 0, noex = 0;
     for (int r0 = 0; r0 < n; r0 += DIAG_WG) {
         const int r = r0 + tid;
         const bool valid = r < n;
@@ -72,18 +70,31 @@ __global__ __launch_bounds__(DIAG_WG) void k_diag_gather(const double* __restric
         __syncthreads();
         a = max(a, pre);
         carry = all;
-        if (valid) {
-            double* o = col + (size_t)cl * n + r;
-            const size_t cs = (size_t)Nb * n;
-            if (a < 0) {
-                for (int s = 0; s < S; ++s) o[s * cs] = qnan;
-            } else {
-                const double* h = hrec + ((size_t)a * N + c) * HW;
-                for (int s = 0; s < np; ++s) o[s * cs] = h[H_PARAMS + s];
-                o[np * cs] = h[H_VALUE];
-            }
-        }
+        if (valid) emit(r, a);
     }
+}
+
+__global__ __launch_bounds__(DIAG_WG) void k_diag_gather(const double* __restrict__ hrec, int N, int HW, int np, int t0, int n, int c0,
+                                                         int Nb, double* __restrict__ col, int* __restrict__ o_nacc,
+                                                         int* __restrict__ o_noex) {
+    __shared__ int wred[DIAG_WG / 64];
+    __shared__ int wtot[DIAG_WG / 64];
+    const int cl = xcd_chain(blockIdx.x, gridDim.x), c = c0 + cl;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int S = np + 1;
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    int nacc = 0, noex = 0;
+    diag_state_rows(hrec, N, HW, c, t0, n, wred, wtot, nacc, noex, [&](int r, int a) {
+        double* o = col + (size_t)cl * n + r;
+        const size_t cs = (size_t)Nb * n;
+        if (a < 0) {
+            for (int s = 0; s < S; ++s) o[s * cs] = qnan;
+        } else {
+            const double* h = hrec + ((size_t)a * N + c) * HW;
+            for (int s = 0; s < np; ++s) o[s * cs] = h[H_PARAMS + s];
+            o[np * cs] = h[H_VALUE];
+        }
+    });
     for (int o = 32; o > 0; o >>= 1) { nacc += __shfl_xor(nacc, o, 64); noex += __shfl_xor(noex, o, 64); }
     if (lane == 0) { wred[w] = nacc; wtot[w] = noex; }
     __syncthreads();

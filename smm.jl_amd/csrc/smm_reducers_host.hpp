@@ -1,6 +1,7 @@
 // the host side of the history reducers — part of libsmmhip (included once by smmhip.hip, behind its host helpers; hiprtc never sees it).
 // The family: smm_get_chain_stats, smm_get_chain_cov, smm_get_proposal / _set_ / _adapt_, smm_get_chain_diag, smm_get_group_stats,
-// smm_get_histogram, smm_get_trace (kernels: smm_stats.hpp, smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_hist.hpp, smm_trace.hpp).
+// smm_get_histogram, smm_get_trace, smm_get_rank_diag (kernels: smm_stats.hpp, smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_hist.hpp,
+// smm_trace.hpp, smm_rank.hpp).
 // What they share is stated here once: the frame of a call (reducer_call), the checks of the arguments they have in common (check_groups,
 // check_probs, check_select), the prelude and the window behind them (settled_window: reader_prelude and check_window of smmhip.hip), the
 // members of the groups (Groups), one result buffer per context (reducer_result, laid out by Carve / Slice, copied by up / down), one
@@ -150,7 +151,8 @@ void launch_checked(Ctx* c, Kern kern, dim3 grid, dim3 block, size_t smem, const
 int sort_lds_n(int n) { return std::min(STATS_LDS_N, 1 << (int)ceil(log2((double)std::max(n, 2)))); }
 
 // the reducers' dynamic LDS (smm_ctx_create): a chunk of draws (k_stats_column, k_cov_center, k_diag_acov, k_group_*, k_trace_column),
-// the partner ids of a pass (k_stats_mode), the counters and edges of a batch of parameters or pairs (k_hist_count, k_hist_pairs)
+// the partner ids of a pass (k_stats_mode), the counters and edges of a batch of parameters or pairs (k_hist_count, k_hist_pairs), a
+// split chain (k_rank_chain_mom, k_rank_acov)
 void reducer_kernel_attributes() {
     HIPCHK(hipFuncSetAttribute((const void*)k_stats_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_cov_center, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
@@ -161,6 +163,8 @@ void reducer_kernel_attributes() {
     HIPCHK(hipFuncSetAttribute((const void*)k_hist_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIST_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)k_hist_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HIST_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)k_trace_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_rank_chain_mom, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_rank_acov, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
 }
 
 }  // namespace
@@ -767,6 +771,143 @@ int smm_get_trace(void* ctx, int32_t t0, int32_t t1, int32_t stride, int32_t sel
             down_rows(nex, out->n_exchanged, G); down_rows(nfail, out->n_failed, G); down_rows(bestc, out->best_chain, G);
             HIPCHK(hipStreamSynchronize(c->stream));   // (the next batch reuses the scratch and the results)
         }
+        return SMM_OK;
+    });
+}
+
+// --- rank-normalised R-hat, bulk / tail / mean ESS and rank histograms of groups of chains (smm_rank.hpp) -----------------------------------
+
+int smm_get_rank_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32_t n_bins, const int32_t* group, int32_t n_groups,
+                      smm_rank_diag_t* out) {
+    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        if (n_groups == 0) return fail(c, SMM_ERR_INVALID_ARG, "n_groups must be at least 1");
+        if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
+        if (n_bins < 0) return fail(c, SMM_ERR_INVALID_ARG, "n_bins must be >= 0");
+        if (out->rank_hist && n_bins == 0) return fail(c, SMM_ERR_INVALID_ARG, "rank_hist requested with n_bins == 0");
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const int n = t1 - t0, h = n / 2;
+        if (n < 8) return fail(c, SMM_ERR_INVALID_ARG, "the window must hold at least 8 iterations");
+        if (max_lag < 1 || max_lag > h - 1) return fail(c, SMM_ERR_INVALID_ARG, "max_lag must lie in [1, (t1 - t0) / 2 - 1]");
+        const KParams& P = c->P;
+        const size_t N = P.N, np = P.np, S = np + 1, G = n_groups, GS = G * S;
+        const Groups grp = group_members(group, G, N);
+        if (2ll * grp.longest * h > 0x7fffffffll) return fail(c, SMM_ERR_INVALID_ARG, "a group's pooled column holds more than 2^31 - 1 values");
+        // the plan: bytes of one series of group g (the value arrays, keys, indices and ranks of its M = 2 k h pooled values, the moments
+        // and a block of LB lags of its 2 k split chains, a long column's digit table), the batches of groups and the series per batch
+        const int LB = std::min(RANK_WG, max_lag + 1);
+        auto col_len = [&](size_t g) { return (size_t)2 * grp.n_chains[g] * h; };
+        auto per_g = [&](size_t g) {
+            return col_len(g) * 72 + (size_t)2 * grp.n_chains[g] * (80 + 32 * (size_t)LB) + (col_len(g) > (size_t)RANK_SMALL ? (size_t)RANK_TABLE * 4 : 0);
+        };
+        size_t one = 0, all = 0;
+        for (size_t g = 0; g < G; ++g) { one = std::max(one, per_g(g)); all += per_g(g); }
+        reducer_scratch(c, one);
+        const size_t hook = c->H.stats_scratch;
+        const size_t budget = hook ? std::min(c->st_scr_bytes, std::max(hook, one)) : c->st_scr_bytes;
+        std::vector<int> bg0{0};   // batch i: the groups [bg0[i], bg0[i + 1])
+        size_t sb = S;
+        if (all <= budget) {
+            bg0.push_back((int)G);
+            if (all > 0) sb = std::min(S, budget / all);
+        } else {
+            sb = 1;
+            size_t used = 0;
+            for (size_t g = 0; g < G; ++g) {
+                if (used > 0 && used + per_g(g) > budget) { bg0.push_back((int)g); used = 0; }
+                used += per_g(g);
+            }
+            bg0.push_back((int)G);
+        }
+        std::vector<int> qgrp(2 * (size_t)grp.M), large(G, 0);
+        for (size_t g = 0; g < G; ++g)
+            for (int q = 2 * grp.gmem0[g]; q < 2 * grp.gmem0[g + 1]; ++q) qgrp[q] = (int)g;
+        for (size_t i = 0; i + 1 < bg0.size(); ++i) {
+            int nl = 0;
+            for (int g = bg0[i]; g < bg0[i + 1]; ++g) large[g] = col_len(g) > (size_t)RANK_SMALL ? nl++ : 0;
+        }
+        const size_t nh = out->rank_hist ? (size_t)n_bins * S * N : 0;
+        Carve Rv;   // 8-byte slices first
+        const auto o_rr = Rv.take<double>(GS), o_rb = Rv.take<double>(GS), o_rf = Rv.take<double>(GS), o_eb = Rv.take<double>(GS),
+                   o_et = Rv.take<double>(GS), o_em = Rv.take<double>(GS), ord = Rv.take<double>(3 * GS), cW = Rv.take<double>(RANK_KINDS * GS),
+                   cvp = Rv.take<double>(RANK_KINDS * GS), gQ = Rv.take<double>(RANK_ESS_KINDS * GS), gT = Rv.take<double>(RANK_ESS_KINDS * GS);
+        const auto hist = Rv.take<unsigned long long>(nh);
+        const auto o_st = Rv.take<int>(4 * GS), gst = Rv.take<int>(RANK_ESS_KINDS * GS), flag = Rv.take<int>(GS), dgm0 = Rv.take<int>(G + 1),
+                   dmem = Rv.take<int>(grp.M), dq = Rv.take<int>(qgrp.size()), dlarge = Rv.take<int>(G);
+        void* d = reducer_result(c, Rv.bytes);
+        up(c, d, dgm0, grp.gmem0); up(c, d, dmem, grp.mem); up(c, d, dq, qgrp); up(c, d, dlarge, large);
+        HIPCHK(hipMemsetAsync(flag.in(d), 0, GS * 4, c->stream));
+        if (nh) HIPCHK(hipMemsetAsync(hist.in(d), 0, nh * 8, c->stream));
+        unsigned long long* dh = nh ? hist.in(d) : nullptr;
+        for (size_t bi = 0; bi + 1 < bg0.size(); ++bi) {
+            const int g0 = bg0[bi], gn = bg0[bi + 1] - g0;
+            const int q0 = 2 * grp.gmem0[g0], mtot = 2 * grp.gmem0[g0 + gn] - q0;
+            const size_t Mtot = (size_t)mtot * h;
+            size_t Mmax = 0, nlarge = 0;
+            for (int g = g0; g < g0 + gn; ++g) { Mmax = std::max(Mmax, col_len(g)); nlarge += col_len(g) > (size_t)RANK_SMALL; }
+            const unsigned nbz = (unsigned)std::min<size_t>(RANK_NBLK, std::max<size_t>(1, (Mmax + RANK_SMALL - 1) / RANK_SMALL));
+            for (size_t s0 = 0; s0 < S; s0 += sb) {
+                const int sbb = (int)std::min(sb, S - s0);
+                const size_t E = (size_t)sbb * Mtot, Qn = (size_t)sbb * mtot;
+                // the scratch of the batch: the kinds' values, the two key buffers, the ranks, the chains' moments and lags; then the 4-byte ones
+                double* Y = (double*)c->st_scr;
+                unsigned long long* KA = (unsigned long long*)(Y + RANK_KINDS * E);
+                unsigned long long* KB = KA + E;
+                long long* R2 = (long long*)(KB + E);
+                double* cmu = (double*)(R2 + E);
+                double* cvar = cmu + RANK_KINDS * Qn;
+                double* acov = cvar + RANK_KINDS * Qn;
+                unsigned* IA = (unsigned*)(acov + RANK_ESS_KINDS * Qn * LB);
+                unsigned* IB = IA + E;
+                int* table = (int*)(IB + E);
+                const RankBatch b{dgm0.in(d), dmem.in(d), dq.in(d), dlarge.in(d), g0, gn, (int)s0, sbb, (int)S, q0, mtot, h, n, (long long)Mtot};
+                const dim3 cols(gn, sbb), cells((gn * sbb + 63) / 64);
+                if (mtot > 0)
+                    launch_checked(c, k_rank_gather, dim3(mtot / 2), dim3(RANK_WG), 0, (const double*)P.hrec, (int)N, P.HW, (int)np, t0, b, Y + E);
+                auto rank_columns = [&](int fold) {   // rank2 of every column of the batch: of x, or of |x - med|
+                    launch_checked(c, k_rank_keys, dim3(gn, sbb, nbz), dim3(RANK_WG), 0, b, fold, (const double*)(Y + E), (const double*)ord.in(d),
+                                   KA, IA, flag.in(d));
+                    launch_checked(c, k_rank_sort_small, cols, dim3(RANK_WG), 0, b, KA, IA, KB, IB);
+                    for (int pass = 0; pass < 8 && nlarge > 0; ++pass) {
+                        unsigned long long* Kin = (pass & 1) ? KB : KA;
+                        unsigned long long* Kout = (pass & 1) ? KA : KB;
+                        unsigned* Iin = (pass & 1) ? IB : IA;
+                        unsigned* Iout = (pass & 1) ? IA : IB;
+                        launch_checked(c, k_rank_count, dim3(gn, sbb, RANK_NBLK), dim3(RANK_WG), 0, b, pass, (const unsigned long long*)Kin, table);
+                        launch_checked(c, k_rank_scan, cols, dim3(RANK_WG), 0, b, table);
+                        launch_checked(c, k_rank_scatter, dim3(gn, sbb, RANK_NBLK), dim3(RANK_WG), 0, b, pass, (const unsigned long long*)Kin,
+                                       (const unsigned*)Iin, Kout, Iout, (const int*)table);
+                    }
+                    launch_checked(c, k_rank_ties, dim3(gn, sbb, nbz), dim3(RANK_WG), 0, b, (const unsigned long long*)KA, (const unsigned*)IA, R2);
+                };
+                rank_columns(0);
+                launch_checked(c, k_rank_order, cells, dim3(64), 0, b, (const unsigned long long*)KA, ord.in(d));
+                if (mtot > 0)
+                    launch_checked(c, k_rank_scores, dim3(mtot, sbb), dim3(RANK_WG), 0, b, 0, (const long long*)R2, (const double*)ord.in(d),
+                                   (const int*)flag.in(d), Y, (int)n_bins, (int)N, dh);
+                rank_columns(1);
+                const size_t lds = (size_t)std::min(h, STATS_LDS_N) * 8;
+                if (mtot > 0) {
+                    launch_checked(c, k_rank_scores, dim3(mtot, sbb), dim3(RANK_WG), 0, b, 1, (const long long*)R2, (const double*)ord.in(d),
+                                   (const int*)flag.in(d), Y, (int)n_bins, (int)N, dh);
+                    launch_checked(c, k_rank_chain_mom, dim3(mtot, sbb, RANK_KINDS), dim3(RANK_WG), lds, b, Y, cmu, cvar);
+                }
+                launch_checked(c, k_rank_cell_mom, dim3((gn * sbb * RANK_KINDS + 63) / 64), dim3(64), 0, b, (int)GS, (const double*)cmu,
+                               (const double*)cvar, cW.in(d), cvp.in(d), gQ.in(d), gT.in(d), gst.in(d), o_rb.in(d), o_rf.in(d));
+                for (int kb = 0; kb <= max_lag && mtot > 0; kb += RANK_WG) {   // (a cell whose sequence is truncated computes no further lag)
+                    launch_checked(c, k_rank_acov, dim3(mtot, sbb, RANK_ESS_KINDS), dim3(RANK_WG), lds, b, (int)GS, kb, (int)max_lag, LB,
+                                   (const double*)Y, (const int*)gst.in(d), acov);
+                    launch_checked(c, k_rank_geyer, dim3(gn * sbb, RANK_ESS_KINDS), dim3(RANK_WG), 0, b, (int)GS, kb, (int)max_lag, LB,
+                                   (const double*)acov, (const double*)cW.in(d), (const double*)cvp.in(d), gQ.in(d), gT.in(d), gst.in(d));
+                }
+                launch_checked(c, k_rank_finish, cells, dim3(64), 0, b, (int)GS, (const int*)flag.in(d), (const double*)cW.in(d),
+                               (const double*)cvp.in(d), (const double*)gT.in(d), (const int*)gst.in(d), o_rr.in(d), o_rb.in(d), o_rf.in(d),
+                               o_eb.in(d), o_et.in(d), o_em.in(d), o_st.in(d));
+            }
+        }
+        down(c, d, o_rr, out->rhat_rank, GS); down(c, d, o_rb, out->rhat_bulk, GS); down(c, d, o_rf, out->rhat_folded, GS);
+        down(c, d, o_eb, out->ess_bulk, GS); down(c, d, o_et, out->ess_tail, GS); down(c, d, o_em, out->ess_mean, GS);
+        down(c, d, o_st, out->status, 4 * GS); down(c, d, hist, out->rank_hist, nh);
+        HIPCHK(hipStreamSynchronize(c->stream));
         return SMM_OK;
     });
 }

@@ -442,6 +442,48 @@ def rhat(algo, groups=None, window=None):
     return [OrderedDict((k, float(d["rhat"][g, i])) for i, k in enumerate(ps2s_names(algo.m))) for g in range(d["rhat"].shape[0])]
 
 
+def _rank_diag(algo, window, groups, bins):
+    """the device's rank-normalised diagnostics of the groups of algo over window = (t0, t1) (default: every completed iteration;
+    smm_get_rank_diag), one call per (iteration, window, groups, bins)"""
+    t0, t1 = (0, algo.i) if window is None else (int(window[0]), int(window[1]))
+    g = tuple(int(v) for v in (_default_groups(algo) if groups is None else groups))
+    key = ("rank", algo.i, t0, t1, g, int(bins))
+    if key not in algo._diag:
+        algo._diag[key] = algo._ctx.rank_diag(t0, t1, n_bins=int(bins), groups=np.asarray(g, np.int32))
+    return algo._diag[key]
+
+
+def _per_group(algo, a):
+    return [OrderedDict((k, float(a[g, i])) for i, k in enumerate(ps2s_names(algo.m))) for g in range(a.shape[0])]
+
+
+def rhat_rank(algo, groups=None, window=None):
+    """the rank-normalised split R-hat (the larger of the bulk and the folded statistic; Vehtari et al. 2021) of each parameter in each
+    group of chains over window = (t0, t1) (default: the whole run), on the device (include/smmhip.h: smm_get_rank_diag): one
+    OrderedDict per group.  groups and window as in rhat"""
+    return _per_group(algo, _rank_diag(algo, window, groups, 0)["rhat_rank"])
+
+
+def ess_bulk(algo, groups=None, window=None):
+    """the multi-chain bulk ESS (of the rank-normalised split chains) of each parameter in each group's pooled sample, on the device
+    (include/smmhip.h: smm_get_rank_diag): one OrderedDict per group; NaN where undefined.  groups and window as in rhat"""
+    return _per_group(algo, _rank_diag(algo, window, groups, 0)["ess_bulk"])
+
+
+def ess_tail(algo, groups=None, window=None):
+    """the multi-chain tail ESS (the smaller of the ESS of the 5 % and of the 95 % quantile indicators) of each parameter in each
+    group's pooled sample, on the device (include/smmhip.h: smm_get_rank_diag): one OrderedDict per group; NaN where undefined"""
+    return _per_group(algo, _rank_diag(algo, window, groups, 0)["ess_tail"])
+
+
+def rank_plot(algo, groups=None, window=None, bins=20):
+    """the rank plot of every chain: an OrderedDict name -> int64 array [N][bins], chain c's draws of the window counted by the bin of
+    their rank in the pooled sample of c's group (uniform when the chains of a group agree), on the device (include/smmhip.h:
+    smm_get_rank_diag); zeros for a chain in no group.  groups and window as in rhat"""
+    h = _rank_diag(algo, window, groups, bins)["rank_hist"]
+    return OrderedDict((k, h[:, i, :].T.copy()) for i, k in enumerate(ps2s_names(algo.m)))
+
+
 def pooled(algo, groups=None, window=None, accepted_only=True, level=0.95):
     """the posterior of each group's pooled draws over window = (t0, t1) (default: the whole run), summarised on the device
     (include/smmhip.h: smm_get_group_stats): one OrderedDict per group with count, chains, mean / median (name -> value), CI
