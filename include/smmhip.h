@@ -643,6 +643,48 @@ typedef struct {               /* caller-allocated; any pointer may be NULL; S =
 int  smm_get_rank_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32_t n_bins,
                        const int32_t* group /* [N] or NULL */, int32_t n_groups, smm_rank_diag_t* out);
 
+/* The posterior sample itself: thinned draws of groups of chains, exported row by row from the history the device holds — parameters,
+ * value, simulated moments and where each row comes from (chain and iteration) — without downloading the history.  Window, groups and
+ * select as in smm_get_histogram and smm_get_trace: the 0-based iterations [t0, t1), n = t1 - t0; group g is made of the LOCAL chains
+ * with group[c] == g (-1: in no group; a shard reports its own chains), in ascending local index; group NULL with n_groups == 1: every
+ * local chain in group 0.  select 0: all rows; 1: the rows with accepted != 0; 2: the state series, row a(t) = the last accepted row
+ * r <= t, looking back before t0 (a t without one gives a row of quiet NaNs with src_iter 0).
+ * Read-only and ordered like smm_get_chain_stats (it settles, flushes and synchronises, and changes no state, history or generator; it
+ * can sit between smm_bgp_step_async calls).
+ *
+ * Selection contract (integers only):
+ *   per chain : chain c's selected rows of the window in iteration order are s_c[0 .. m_c) (select 0, 2: m_c = n, s_c[i] = t0 + i).
+ *               Thinning keeps s_c[i] with i % thin == 0: m'_c = ceil(m_c / thin) rows.
+ *   pool      : group g's pooled sequence is the members' kept rows, member after member in ascending local index; its length m_g is
+ *               count[g].
+ *   cap       : K = max_rows.  m_g <= K: every pooled row is written.  Otherwise exactly K rows: row j is pooled position
+ *               floor(j m_g / K), in 64-bit integers (strictly increasing, as m_g > K): systematic thinning, spread evenly over the
+ *               members' series.
+ *   packing   : the groups in order, row0[g + 1] = row0[g] + min(m_g, K); a group without members or without rows writes none.
+ *   bits      : every double written is the history's double, bit for bit, NaNs included; nothing is computed on a value.
+ * Sizing call: with params, value, sim_moments, chain, iter and src_iter all NULL the call fills count, n_chains and row0 only and
+ * ignores rows_cap; the caller sizes its arrays by row0[n_groups] = R.  Row call: the arrays hold rows_cap rows; R > rows_cap is
+ * SMM_ERR_INVALID_ARG with R in the message.  SMM_ERR_INVALID_ARG also for: NULL ctx or out, t0 < 0, t1 < t0, t1 > completed iterations,
+ * select outside [0, 2], n_groups < 0, group NULL with n_groups != 1, a group id outside [-1, n_groups), thin < 1, max_rows outside
+ * [1, 1 << 24] (j m_g then stays below 2^63 at any population and capacity), rows_cap < 0 in a row call.  On an error nothing is written.
+ * Device memory: no list of selected iterations is built.  Select 1 and 2 keep one 64-bit mask word and one 32-bit running count per
+ * chain and 64 iterations (of the window; of [0, t1) for select 2) in smm_get_chain_stats' scratch, in batches of chains where they do
+ * not fit; the rows are produced and copied out in batches of at most 256 MB at 8 (np + 1 + nm) + 12 bytes a row. */
+typedef struct {            /* caller-allocated; any pointer may be NULL = not returned                          */
+    int64_t* count;         /* [G]      draws of the group after per-chain thinning, before the cap (m_g)       */
+    int32_t* n_chains;      /* [G]      member chains                                                            */
+    int64_t* row0;          /* [G + 1]  group g's rows are [row0[g], row0[g + 1]); row0[G] = R, the rows written */
+    double*  params;        /* [R][np]  ROW-major: one draw per row                                              */
+    double*  value;         /* [R]                                                                               */
+    double*  sim_moments;   /* [R][nm]                                                                           */
+    int32_t* chain;         /* [R]      1-based GLOBAL chain id (as smm_get_trace's best_chain)                  */
+    int32_t* iter;          /* [R]      1-based iteration t + 1 the draw stands for                              */
+    int32_t* src_iter;      /* [R]      1-based iteration of the row that supplied it (= iter for select 0, 1;
+                                        a(t) + 1 for select 2, 0 where there is none)                            */
+} smm_draws_t;
+int  smm_get_draws(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group /* [N] or NULL */,
+                   int32_t n_groups, int32_t thin, int32_t max_rows, int64_t rows_cap, smm_draws_t* out);
+
 /* Covariances of the chains' draws and the proposal factor between steps — adaptive Metropolis (Haario et al.) on top of chol_L: a
  * pilot run, then each chain's proposal shaped by the covariance of its own draws, without leaving the device.
  *

@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_set_population!, hip_scatter_population!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
@@ -122,6 +122,18 @@ struct SmmRankDiag
     ess_mean::Ptr{Cdouble}
     status::Ptr{Int32}
     rank_hist::Ptr{Int64}
+end
+
+struct SmmDraws
+    count::Ptr{Int64}
+    n_chains::Ptr{Int32}
+    row0::Ptr{Int64}
+    params::Ptr{Cdouble}
+    value::Ptr{Cdouble}
+    sim_moments::Ptr{Cdouble}
+    chain::Ptr{Int32}
+    iter::Ptr{Int32}
+    src_iter::Ptr{Int32}
 end
 
 struct SmmGroupStats
@@ -577,6 +589,45 @@ function hip_trace(h::HipBGP, t0::Integer, t1::Integer; stride::Integer = 1, sel
     end
     return (iter = iter, n_chains = nch, count = count, n_accepted = nacc, n_exchanged = nex, n_failed = nfail, mean = mean, var = var,
             median = med, quantile = quant, best_value = bestv, best_chain = bestc)
+end
+
+"""
+    hip_get_draws(h, t0, t1; select = :accepted, groups = nothing, thin = 1, max_rows = 10000, moments = true) -> NamedTuple
+
+The posterior sample itself: thinned draws of groups of chains over iterations `t0+1 .. t1`, gathered on the device (`smm_get_draws`)
+without downloading the history.  `select`: `:all`, `:accepted` or `:state` (each chain's last accepted row, looking back before the
+window).  Every `thin`-th selected row of a chain is kept; a group with more than `max_rows` kept rows is thinned systematically to
+`max_rows`.  `groups[chain]` holds 0-based group ids (-1 = none); `nothing`: every chain in one group.  Returns `count[g]` (kept rows
+before the cap), `n_chains[g]`, `row0[g]` (0-based: group g's rows are `row0[g]+1 : row0[g+1]`), `params[k, r]`, `value[r]`,
+`sim_moments[k, r]` (empty without `moments`), `chain[r]` (1-based global id), `iter[r]` and `src_iter[r]` (1-based; 0: a state row
+that does not exist yet, a NaN row).  A sizing call, then the row call.
+"""
+function hip_get_draws(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :accepted,
+                       groups::Union{Nothing,AbstractVector{<:Integer}} = nothing, thin::Integer = 1, max_rows::Integer = 10000,
+                       moments::Bool = true)
+    N = h.N
+    g = groups === nothing ? Int32[] : Vector{Int32}(groups)
+    groups === nothing || length(g) == N || throw(ArgumentError("groups needs one entry per chain"))
+    ng = groups === nothing ? 1 : (isempty(g) ? 0 : Int(maximum(g)) + 1)
+    gp = groups === nothing ? Ptr{Int32}(C_NULL) : pointer(g)
+    count = Vector{Int64}(undef, ng); nch = Vector{Int32}(undef, ng); row0 = zeros(Int64, ng + 1)
+    GC.@preserve g count nch row0 begin
+        sz = SmmDraws(pointer(count), pointer(nch), pointer(row0), Ptr{Cdouble}(C_NULL), Ptr{Cdouble}(C_NULL), Ptr{Cdouble}(C_NULL),
+                      Ptr{Int32}(C_NULL), Ptr{Int32}(C_NULL), Ptr{Int32}(C_NULL))
+        check(h.ctx, ccall(sym(:smm_get_draws), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Int32}, Cint, Cint, Cint, Int64, Ref{SmmDraws}),
+                           h.ctx, t0, t1, HIST_SELECT[select], gp, ng, thin, max_rows, 0, sz))
+    end
+    R = Int(row0[ng + 1])
+    params = Matrix{Float64}(undef, h.np, R); value = Vector{Float64}(undef, R); mom = Matrix{Float64}(undef, h.nm, moments ? R : 0)
+    chain = Vector{Int32}(undef, R); iter = Vector{Int32}(undef, R); src = Vector{Int32}(undef, R)
+    GC.@preserve g count nch row0 params value mom chain iter src begin
+        dr = SmmDraws(pointer(count), pointer(nch), pointer(row0), pointer(params), pointer(value),
+                      moments ? pointer(mom) : Ptr{Cdouble}(C_NULL), pointer(chain), pointer(iter), pointer(src))
+        check(h.ctx, ccall(sym(:smm_get_draws), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Int32}, Cint, Cint, Cint, Int64, Ref{SmmDraws}),
+                           h.ctx, t0, t1, HIST_SELECT[select], gp, ng, thin, max_rows, R, dr))
+    end
+    return (count = count, n_chains = nch, row0 = row0, params = params, value = value, sim_moments = mom, chain = chain, iter = iter,
+            src_iter = src)   # (the header's row-major [R][np] = these column-major [np, R] arrays)
 end
 
 # the factor(s) between the header's row-major [np][np] / [N][np][np] and Julia's L[k, j] / L[k, j, c]

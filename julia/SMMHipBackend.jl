@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -425,6 +425,29 @@ function population_trace(algo::MAlgoBGPHip; window = nothing, stride::Integer =
         groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
     end
     return SMMHip.hip_trace(hip, t0, t1; stride = stride, select = select, moments = moments, groups = groups, probs = collect(Float64, probs))
+end
+
+"""
+    posterior_draws(algo; window = nothing, select = :accepted, groups = nothing, thin = 1, max_rows = 10000, moments = false) -> NamedTuple
+
+The posterior sample itself, gathered on the device from the history it holds (`SMMHip.hip_get_draws`), without `sync_chains!`: for
+each group of chains every `thin`-th selected draw of its members, thinned systematically to at most `max_rows` rows, with
+`params[k, r]`, `value[r]`, `sim_moments[k, r]` (with `moments`), `chain[r]` and `iter[r]`; group g's rows are
+`row0[g]+1 : row0[g+1]`.  `groups[chain]` holds 0-based group ids (-1 = none); by default the chains with equal `acc_tuners`
+entries, as `pooled_summary`.  What a corner plot, a posterior-predictive check or a DataFrame needs.  Not a method of `SMM`: the
+reference reads `params(chain)` of every chain.
+"""
+function posterior_draws(algo::MAlgoBGPHip; window = nothing, select::Symbol = :accepted, groups = nothing, thin::Integer = 1,
+                         max_rows::Integer = 10000, moments::Bool = false)
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    t0, t1 = window === nothing ? (0, SMMHip.hip_iter(hip)) : window
+    if groups === nothing
+        ids = Dict{Float64,Int32}()
+        opts = getfield(algo, :opts)
+        groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
+    end
+    return SMMHip.hip_get_draws(hip, t0, t1; select = select, groups = groups, thin = thin, max_rows = max_rows, moments = moments)
 end
 
 """

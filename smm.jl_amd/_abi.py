@@ -137,6 +137,13 @@ class smm_rank_diag_t(C.Structure):
     ]
 
 
+class smm_draws_t(C.Structure):
+    _fields_ = [
+        ("count", C.POINTER(C.c_int64)), ("n_chains", c_int32_p), ("row0", C.POINTER(C.c_int64)), ("params", c_double_p),
+        ("value", c_double_p), ("sim_moments", c_double_p), ("chain", c_int32_p), ("iter", c_int32_p), ("src_iter", c_int32_p),
+    ]
+
+
 class smm_population_t(C.Structure):
     _fields_ = [
         ("start", c_double_p), ("value", c_double_p), ("pick", c_int32_p), ("evaluated", C.c_int64),
@@ -195,6 +202,8 @@ SYMBOLS = [
                                 C.POINTER(smm_trace_t)]),
     ("smm_get_rank_diag", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32,
                                     C.POINTER(smm_rank_diag_t)]),
+    ("smm_get_draws", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                C.POINTER(smm_draws_t)]),
     ("smm_get_chain_cov", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
     ("smm_get_proposal", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_proposal", C.c_int, [C.c_void_p, c_double_p]),

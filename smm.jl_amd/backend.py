@@ -407,6 +407,27 @@ class BGPContext:
                                           A.dptr(p) if len(p) else None, len(p), C.byref(s)))
         return r
 
+    def draws(self, t0=0, t1=None, select=1, groups=None, thin=1, max_rows=10000, moments=True, n_groups=None):
+        """the posterior sample itself: thinned draws of groups of local chains over iterations [t0, t1), gathered on the device
+        (smm_get_draws, include/smmhip.h): a dict of numpy arrays count / n_chains [n_groups], row0 [n_groups + 1] (group g's rows are
+        row0[g] .. row0[g + 1]), params [R][np], value [R], sim_moments [R][nm] (moments=False: [0][nm], not read), chain / iter /
+        src_iter [R] (1-based; chain is the global id).  select: 0 / "all", 1 / "accepted" or 2 / "state"; every thin-th selected row of
+        a chain is kept, and a group with more than max_rows kept rows is thinned systematically to max_rows.  groups: an int per chain
+        (-1 = none), n_groups by default groups.max() + 1, None: every local chain in one group.  A sizing call, then the row call"""
+        t0, t1 = int(t0), int(self._t1(t1))
+        sel, thin, max_rows = self._select(select), int(thin), int(max_rows)
+        g, gp, ng = self._groups("draws", groups, n_groups)
+        G = max(ng, 0)
+        r = dict(count=np.zeros(G, np.int64), n_chains=np.zeros(G, np.int32), row0=np.zeros(G + 1, np.int64))
+        fn = self._fn("get_draws")
+        self._check(fn(self._ctx, t0, t1, sel, gp, ng, thin, max_rows, 0, C.byref(self._out(A.smm_draws_t, r))))
+        R = int(r["row0"][G])
+        r.update(params=np.empty((R, self.np)), value=np.empty(R), sim_moments=np.empty((R if moments else 0, self.nm)),
+                 chain=np.empty(R, np.int32), iter=np.empty(R, np.int32), src_iter=np.empty(R, np.int32))
+        s = self._out(A.smm_draws_t, r, () if moments else ("sim_moments",))
+        self._check(fn(self._ctx, t0, t1, sel, gp, ng, thin, max_rows, R, C.byref(s)))
+        return r
+
     def _proposal_shape(self):
         if self.proposal_layout is None:
             return None

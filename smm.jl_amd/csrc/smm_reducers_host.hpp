@@ -1,7 +1,7 @@
 // the host side of the history reducers — part of libsmmhip (included once by smmhip.hip, behind its host helpers; hiprtc never sees it).
 // The family: smm_get_chain_stats, smm_get_chain_cov, smm_get_proposal / _set_ / _adapt_, smm_get_chain_diag, smm_get_group_stats,
-// smm_get_histogram, smm_get_trace, smm_get_rank_diag (kernels: smm_stats.hpp, smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_hist.hpp,
-// smm_trace.hpp, smm_rank.hpp).
+// smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws (kernels: smm_stats.hpp, smm_cov.hpp, smm_diag.hpp, smm_group.hpp,
+// smm_hist.hpp, smm_trace.hpp, smm_rank.hpp, smm_draws.hpp).
 // What they share is stated here once: the frame of a call (reducer_call), the checks of the arguments they have in common (check_groups,
 // check_probs, check_select), the prelude and the window behind them (settled_window: reader_prelude and check_window of smmhip.hip), the
 // members of the groups (Groups), one result buffer per context (reducer_result, laid out by Carve / Slice, copied by up / down), one
@@ -908,6 +908,106 @@ int smm_get_rank_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32_
         down(c, d, o_eb, out->ess_bulk, GS); down(c, d, o_et, out->ess_tail, GS); down(c, d, o_em, out->ess_mean, GS);
         down(c, d, o_st, out->status, 4 * GS); down(c, d, hist, out->rank_hist, nh);
         HIPCHK(hipStreamSynchronize(c->stream));
+        return SMM_OK;
+    });
+}
+
+// --- the thinned draws of groups of chains, row by row (smm_draws.hpp) ---------------------------------------------------------------------
+
+int smm_get_draws(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups, int32_t thin, int32_t max_rows,
+                  int64_t rows_cap, smm_draws_t* out) {
+    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        if (const int rc = check_select(c, select)) return rc;
+        if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
+        if (thin < 1) return fail(c, SMM_ERR_INVALID_ARG, "thin must be at least 1");
+        if (max_rows < 1 || max_rows > (1 << 24)) return fail(c, SMM_ERR_INVALID_ARG, "max_rows must lie in [1, 1 << 24]");
+        const bool sizing = !out->params && !out->value && !out->sim_moments && !out->chain && !out->iter && !out->src_iter;
+        if (!sizing && rows_cap < 0) return fail(c, SMM_ERR_INVALID_ARG, "rows_cap must be >= 0");
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t N = P.N, np = P.np, nm = P.nm, G = n_groups;
+        const int n = t1 - t0;
+        const Groups grp = group_members(group, G, N);
+        const size_t M = grp.M;
+        // the masks of a chain: W words and their running popcounts over the window (select 1) or over [0, t1) (select 2); none for select 0
+        const int tb = select == 1 ? t0 : 0, W = select == 0 ? 0 : (t1 - tb + 63) / 64;
+        const size_t per_chain = (size_t)W * 12;
+        // the sizes first: the members' prefixes, m_g and min(m_g, K) on the device, the scan across the groups here
+        Carve Rh;   // 8-byte slices first
+        const auto prefix = Rh.take<long long>(M), dgm = Rh.take<long long>(G), dtake = Rh.take<long long>(G), drow0 = Rh.take<long long>(G + 1);
+        const auto dmc = Rh.take<int>(N), dgm0 = Rh.take<int>(G + 1), dmem = Rh.take<int>(M);
+        const size_t head = (Rh.bytes + 7) & ~(size_t)7;
+        void* d = reducer_result(c, head);
+        up(c, d, dgm0, grp.gmem0); up(c, d, dmem, grp.mem);
+        int resident_c0 = -1, n_chain_batches = 0;   // the chains whose masks the scratch holds
+        auto masks = [&](int c0, int nb) {
+            unsigned long long* mk = (unsigned long long*)c->st_scr;
+            launch_checked(c, k_draws_mask, dim3((nb + 63) / 64), dim3(DRAWS_WG), 0, (const double*)P.hrec, (int)N, P.HW, tb, t1, c0, nb, W, mk,
+                           (unsigned*)(mk + (size_t)nb * W), dmc.in(d));
+            resident_c0 = c0;
+        };
+        if (W > 0) {
+            reducer_scratch(c, per_chain);
+            chain_batches(c, per_chain, [&](int, int) { ++n_chain_batches; });
+        }
+        if (select == 1) {
+            HIPCHK(hipMemsetAsync(dmc.in(d), 0, N * 4, c->stream));   // (an empty window: no word, no set bit)
+            if (W > 0) chain_batches(c, per_chain, masks);
+        }
+        std::vector<long long> gm(G, 0), take(G, 0), row0(G + 1, 0);
+        if (G > 0) {
+            launch_checked(c, k_draws_offsets, dim3((unsigned)G), dim3(DRAWS_WG), 0, (const int*)dmem.in(d), (const int*)dgm0.in(d),
+                           select == 1 ? (const int*)dmc.in(d) : (const int*)nullptr, n, (int)thin, (long long)max_rows, prefix.in(d), dgm.in(d),
+                           dtake.in(d));
+            down(c, d, dgm, gm.data(), G); down(c, d, dtake, take.data(), G);
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (size_t g = 0; g < G; ++g) row0[g + 1] = row0[g] + take[g];
+        const long long R = row0[G];
+        if (!sizing && R > rows_cap)
+            return fail(c, SMM_ERR_INVALID_ARG, "smm_get_draws: the call writes " + std::to_string(R) + " rows, rows_cap is " + std::to_string(rows_cap));
+        if (out->count) std::copy(gm.begin(), gm.end(), out->count);
+        if (out->n_chains) std::copy(grp.n_chains.begin(), grp.n_chains.end(), out->n_chains);
+        if (out->row0) std::copy(row0.begin(), row0.end(), out->row0);
+        if (sizing || R == 0) return SMM_OK;
+        // the rows, in batches that fit the cap of the result buffer (at least one row); a batch's rows of every chain batch's chains
+        const size_t row_bytes = 8 * (np + 1 + nm) + 12;
+        const size_t rb = (size_t)std::min<long long>(R, (long long)std::max<size_t>(1, reducer_batch_cap(c) / row_bytes));
+        Carve Rv;
+        Rv.bytes = head;
+        const auto o_par = Rv.take<double>(out->params ? rb * np : 0), o_val = Rv.take<double>(out->value ? rb : 0),
+                   o_mom = Rv.take<double>(out->sim_moments ? rb * nm : 0);
+        const auto o_chain = Rv.take<int>(out->chain ? rb : 0), o_iter = Rv.take<int>(out->iter ? rb : 0), o_src = Rv.take<int>(out->src_iter ? rb : 0);
+        if (Rv.bytes > c->red_res_bytes) {   // (growing the buffer frees it: the head's tables move with it)
+            std::vector<char> keep(head);
+            HIPCHK(hipMemcpy(keep.data(), d, head, hipMemcpyDeviceToHost));
+            d = reducer_result(c, Rv.bytes);
+            HIPCHK(hipMemcpy(d, keep.data(), head, hipMemcpyHostToDevice));
+        }
+        up(c, d, drow0, row0);
+        for (long long r0 = 0; r0 < R; r0 += (long long)rb) {
+            const int rn = (int)std::min<long long>((long long)rb, R - r0);
+            auto gather = [&](int c0, int nb) {
+                if (W > 0 && (n_chain_batches > 1 || resident_c0 != c0)) masks(c0, nb);
+                const unsigned long long* mk = (const unsigned long long*)c->st_scr;
+                launch_checked(c, k_draws_gather, dim3((rn + DRAWS_WG - 1) / DRAWS_WG), dim3(DRAWS_WG), 0, (const double*)P.hrec, (int)N, P.HW,
+                               (int)np, (int)nm, t0, (int)select, (int)thin, (const int*)dmem.in(d), (const int*)dgm0.in(d), (int)G,
+                               (const long long*)drow0.in(d), (const long long*)prefix.in(d), (const long long*)dgm.in(d), c0, nb, W, tb,
+                               W > 0 ? mk : nullptr, W > 0 ? (const unsigned*)(mk + (size_t)nb * W) : nullptr, P.offset, r0, rn,
+                               out->params ? o_par.in(d) : (double*)nullptr, out->value ? o_val.in(d) : (double*)nullptr,
+                               out->sim_moments ? o_mom.in(d) : (double*)nullptr, out->chain ? o_chain.in(d) : (int*)nullptr,
+                               out->iter ? o_iter.in(d) : (int*)nullptr, out->src_iter ? o_src.in(d) : (int*)nullptr);
+            };
+            if (W > 0) chain_batches(c, per_chain, gather);
+            else gather(0, (int)N);
+            down(c, d, o_par, out->params ? out->params + (size_t)r0 * np : nullptr, (size_t)rn * np);
+            down(c, d, o_val, out->value ? out->value + r0 : nullptr, (size_t)rn);
+            down(c, d, o_mom, out->sim_moments ? out->sim_moments + (size_t)r0 * nm : nullptr, (size_t)rn * nm);
+            down(c, d, o_chain, out->chain ? out->chain + r0 : nullptr, (size_t)rn);
+            down(c, d, o_iter, out->iter ? out->iter + r0 : nullptr, (size_t)rn);
+            down(c, d, o_src, out->src_iter ? out->src_iter + r0 : nullptr, (size_t)rn);
+            HIPCHK(hipStreamSynchronize(c->stream));   // (the next batch reuses the rows)
+        }
         return SMM_OK;
     });
 }

@@ -73,6 +73,7 @@ using namespace smm;
 #include "smm_hist.hpp"
 #include "smm_trace.hpp"
 #include "smm_rank.hpp"
+#include "smm_draws.hpp"
 #include "smm_population.hpp"
 
 // ------------------------------------------------------------------------------------------

@@ -618,6 +618,43 @@ def trace(algo, groups=None, window=None, stride=1, state=True, moments=False, p
     return out
 
 
+def draws(x, groups=None, window=None, accepted_only=True, state=False, thin=1, max_rows=10000, moments=False):
+    """the posterior sample itself, gathered on the device (include/smmhip.h: smm_get_draws) without downloading the history: one
+    table per group (a pandas DataFrame when pandas is importable, else an OrderedDict of columns, as history(c)) with the columns
+    chain and iter (1-based), value, every parameter and, with moments, every simulated moment.  Every thin-th selected draw of a chain
+    is kept and a group with more than max_rows of them is thinned systematically to max_rows.  window = (t0, t1) (default: the whole
+    run); state: the chains' state series instead of their accepted draws; groups: a group id per chain (-1 = none), by default those
+    of rhat / pooled.  For a chain: that chain's table (alone in group 0)"""
+    if isinstance(x, BGPChain):
+        algo, j = x._algo, x._j
+        g = np.full(algo._ctx.N, -1, np.int32)
+        g[j] = 0
+        ng = 1
+    else:
+        algo, j = x, None
+        g = np.asarray(_default_groups(algo) if groups is None else groups, np.int32)
+        ng = None
+    t0, t1 = (0, algo.i) if window is None else (int(window[0]), int(window[1]))
+    sel = "state" if state else "accepted" if accepted_only else "all"
+    r = algo._ctx.draws(t0, t1, sel, g, int(thin), int(max_rows), bool(moments), n_groups=ng)
+    out = []
+    for k in _builtins_range(r["count"].shape[0]):
+        a, b = int(r["row0"][k]), int(r["row0"][k + 1])
+        cols = OrderedDict(chain=r["chain"][a:b].astype(np.int64), iter=r["iter"][a:b].astype(np.int64), value=r["value"][a:b].copy())
+        for i, name in enumerate(ps2s_names(algo.m)):
+            cols[name] = r["params"][a:b, i].copy()
+        if moments:
+            for i, name in enumerate(ms_names(algo.m)):
+                cols[name] = r["sim_moments"][a:b, i].copy()
+        try:
+            import pandas as pd
+            cols = pd.DataFrame(cols)
+        except Exception:  # pragma: no cover
+            pass
+        out.append(cols)
+    return out[0] if j is not None else out
+
+
 def summary(x):
     """summary(c::BGPChain) AlgoBGP.jl:197-206 / summary(m::MAlgoBGP) :541-550"""
     if isinstance(x, MAlgoBGP):
