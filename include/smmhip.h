@@ -685,6 +685,69 @@ typedef struct {            /* caller-allocated; any pointer may be NULL = not r
 int  smm_get_draws(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group /* [N] or NULL */,
                    int32_t n_groups, int32_t thin, int32_t max_rows, int64_t rows_cap, smm_draws_t* out);
 
+/* The simulated moments of groups of chains computed on the device from the history it holds: the first table of an SMM paper (the data
+ * moments next to the simulated moments at the estimate), and from the same pooled draws the Jacobian dm/dtheta linearised over the
+ * posterior (the regression of the simulated moments on the parameters over a group's draws), the sensitivity matrix of Andrews,
+ * Gentzkow & Shapiro (2017) and sandwich standard errors — no further evaluation of the objective and no finite-difference step.
+ * Window and groups as in smm_get_group_stats: the 0-based iterations [t0, t1); group g is made of the LOCAL chains with group[c] == g
+ * (-1: in no group; a shard reports its own chains), in ascending local index; group NULL with n_groups == 1: every local chain in
+ * group 0.  select as in smm_get_histogram: 0 every row of the window; 1 the rows with accepted != 0; 2 the state series, row a(t) of
+ * smm_get_chain_diag supplying the parameters and the simulated moments alike (a(t) looks back before t0; a row with no a(t) is NaN) —
+ * the MCMC posterior itself, weighted by holding time.  Caller-allocated; any pointer may be NULL (not computed).  Read-only and ordered
+ * like smm_get_chain_stats (it settles, flushes and synchronises, and changes no state, history or generator).  It uses
+ * smm_get_chain_stats' scratch, grown where needed to N x maxiter x 8 bytes (one pooled column) and, for the covariances, to
+ * (np + nm) x 8192 x 8 bytes (every joint column of one chunk); pooled columns that do not fit are reduced in batches of columns, and
+ * the covariance in batches of chunks (whose (np + nm)^2 pair sums per chunk stay under 256 MiB of the result buffer), each batch
+ * reading the window once more.  SMM_ERR_INVALID_ARG: NULL ctx or out, a bad window, select outside [0, 2], n_groups < 0, group NULL
+ * with n_groups != 1, a group id outside [-1, n_groups), n_probs < 0, probs NULL with n_probs > 0, a prob outside [0, 1] or NaN,
+ * m_quantile without probs, ridge negative or not finite; nothing is written then.
+ *
+ * Numerical contract (every operation rounded on its own, no fma; counts and ranks 64-bit):
+ *   pooled columns : the members' selected rows in member order, then iteration order, m = count of them.  Joint column k < np is the
+ *                parameter k of the row; column np + k is the simulated moment k stored behind the parameters in the same record;
+ *                D = np + nm.
+ *   mean, median, quantile p = the chain-stats ones on the pooled column (chunks of 8192 counted from the group's first row, pw,
+ *                numpy's _lerp; the -0/+0 caveat of smm_get_chain_stats holds).
+ *   cov_ab     = S(d_a * d_b) / (m - 1), d centred by the column's own mean above, S the chunked pairwise sum: smm_get_group_stats'
+ *                covariance over the D joint columns.  cov_pp = the block a, b < np (bit for bit smm_get_group_stats' cov on select
+ *                1), cov_pm[j][k] = cov_{j, np + k}, cov_mm[k][l] = cov_{np + k, np + l}; mirrored entries hold the same value.
+ *   fit_z_k    = (m_mean_k - mom_k) / sqrt(cov_mm_kk): the data moment's distance from the posterior predictive, in its standard
+ *                deviations.
+ *   Cholesky   : A = cov_pp with A_jj = C_jj + ridge * C_jj.  For k = 0..np-1, j = 0..k: s = A_kj; s = s - L_ki * L_ji for i = 0..j-1
+ *                in that order; j == k: L_kk = sqrt(s), status 3 when !(s > 0); otherwise L_kj = s / L_jj (smm_adapt_proposal's order).
+ *   solve(L, b): y_i = (b_i - L_i0 y_0 - .. - L_i,i-1 y_i-1) / L_ii for i = 0..np-1, then x_i = (y_i - L_i+1,i x_i+1 - .. -
+ *                L_np-1,i x_np-1) / L_ii for i = np-1..0; the products subtracted one by one in ascending index.
+ *   jac        : J = Cov(m, theta) Cov(theta, theta)^-1, row k = solve(L, column k of cov_pm).
+ *   weights    : s_k = w_k if it is finite and not zero, else 1.0; W_k = 1.0 / (s_k * s_k) — objfunc_norm's reading of the weights,
+ *                ((sim - mom) / w)^2; a NaN weight means no weight.
+ *   sens       : Lambda = -(J'WJ)^-1 J'W.  B_ij = ((J_0i * W_0) * J_0j + (J_1i * W_1) * J_1j) + .., from 0.0 over k ascending; its
+ *                lower Cholesky factor as above without a ridge, status 4 when a pivot is not > 0; column k of Lambda =
+ *                solve(L_B, b) with b_i = -(J_ki * W_k).
+ *   se_j       = sqrt(S), S = 0.0, S = S + (Lambda_jk * Lambda_jk) * (s_k * s_k) over k ascending; sqrt and / are IEEE.  se takes the
+ *                weights as the data moments' standard deviations, Lambda diag(s^2) Lambda'; a caller with a full covariance Sigma
+ *                of the data moments computes Lambda Sigma Lambda' from sens.
+ *   status     : the first that applies: 1 count < 2 (the covariances and everything derived from them NaN); 2 a non-finite value
+ *                among the selected parameters or moments (everything but count and n_chains NaN); 3 a pivot of the factor of A is
+ *                not > 0 (jac, sens, se NaN); 4 a pivot of the factor of J'WJ is not > 0 (sens, se NaN); 0 otherwise. */
+typedef struct {            /* caller-allocated; any pointer may be NULL = not computed; G = n_groups                          */
+    int64_t* count;         /* [G]               selected rows pooled in the group                                             */
+    int32_t* n_chains;      /* [G]               member chains                                                                 */
+    int32_t* status;        /* [G]               0 ok, 1 fewer than 2 rows, 2 non-finite value, 3 Cov(theta) not PD, 4 J'WJ not PD */
+    double*  p_mean;        /* [G][np]           pooled parameter mean                                                         */
+    double*  m_mean;        /* [G][nm]           pooled simulated-moment mean                                                  */
+    double*  m_median;      /* [G][nm]                                                                                         */
+    double*  m_quantile;    /* [n_probs][G][nm]                                                                                */
+    double*  cov_pp;        /* [G][np][np]       parameter covariance                                                          */
+    double*  cov_pm;        /* [G][np][nm]       parameter-moment covariance                                                   */
+    double*  cov_mm;        /* [G][nm][nm]       moment covariance                                                             */
+    double*  fit_z;         /* [G][nm]           (m_mean - mom) / sqrt(diag cov_mm)                                            */
+    double*  jac;           /* [G][nm][np]       J = Cov(m, theta) Cov(theta, theta)^-1                                        */
+    double*  sens;          /* [G][np][nm]       Lambda = -(J'WJ)^-1 J'W                                                       */
+    double*  se;            /* [G][np]           sqrt(diag(Lambda diag(s^2) Lambda'))                                          */
+} smm_moment_stats_t;
+int  smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group /* [N] or NULL */,
+                          int32_t n_groups, const double* probs, int32_t n_probs, double ridge, smm_moment_stats_t* out);
+
 /* Covariances of the chains' draws and the proposal factor between steps — adaptive Metropolis (Haario et al.) on top of chol_L: a
  * pilot run, then each chain's proposal shaped by the covariance of its own draws, without leaving the device.
  *

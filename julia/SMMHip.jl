@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_set_population!, hip_scatter_population!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
@@ -134,6 +134,23 @@ struct SmmDraws
     chain::Ptr{Int32}
     iter::Ptr{Int32}
     src_iter::Ptr{Int32}
+end
+
+struct SmmMomentStats
+    count::Ptr{Int64}
+    n_chains::Ptr{Int32}
+    status::Ptr{Int32}
+    p_mean::Ptr{Cdouble}
+    m_mean::Ptr{Cdouble}
+    m_median::Ptr{Cdouble}
+    m_quantile::Ptr{Cdouble}
+    cov_pp::Ptr{Cdouble}
+    cov_pm::Ptr{Cdouble}
+    cov_mm::Ptr{Cdouble}
+    fit_z::Ptr{Cdouble}
+    jac::Ptr{Cdouble}
+    sens::Ptr{Cdouble}
+    se::Ptr{Cdouble}
 end
 
 struct SmmGroupStats
@@ -628,6 +645,44 @@ function hip_get_draws(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :ac
     end
     return (count = count, n_chains = nch, row0 = row0, params = params, value = value, sim_moments = mom, chain = chain, iter = iter,
             src_iter = src)   # (the header's row-major [R][np] = these column-major [np, R] arrays)
+end
+
+"""
+    hip_moment_stats(h, t0, t1; select = :state, groups = nothing, probs = Float64[], ridge = 0.0) -> NamedTuple
+
+The simulated moments of groups of chains over iterations `t0+1 .. t1`, on the device (`smm_get_moment_stats`) without downloading the
+history: their pooled mean, median and quantiles next to the data moments (`fit_z`), the joint covariance of parameters and moments,
+the Jacobian `jac` (the regression of the simulated moments on the parameters over the pooled draws), the sensitivity `sens` of
+Andrews, Gentzkow & Shapiro (2017) and the sandwich standard errors `se` (the weights read as the data moments' standard deviations).
+`select`: `:all`, `:accepted` or `:state`.  `groups[chain]` holds 0-based group ids (-1 = none); `nothing`: every chain in one group.
+Returns `count[g]`, `n_chains[g]`, `status[g]` (0 ok, 1 fewer than 2 rows, 2 a non-finite value, 3 / 4 the parameter covariance /
+J'WJ not positive definite), `p_mean[k, g]`, `m_mean[k, g]`, `m_median[k, g]`, `m_quantile[k, g, p]`, `cov_pp[k, j, g]`,
+`cov_pm[m, k, g]`, `cov_mm[l, k, g]`, `fit_z[k, g]`, `jac[k, m, g]`, `sens[m, k, g]`, `se[k, g]` (the header's row-major arrays).
+"""
+function hip_moment_stats(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :state,
+                          groups::Union{Nothing,AbstractVector{<:Integer}} = nothing, probs::AbstractVector{<:Real} = Float64[],
+                          ridge::Real = 0.0)
+    N, np, nm = h.N, h.np, h.nm
+    g = groups === nothing ? Int32[] : Vector{Int32}(groups)
+    groups === nothing || length(g) == N || throw(ArgumentError("groups needs one entry per chain"))
+    ng = groups === nothing ? 1 : (isempty(g) ? 0 : Int(maximum(g)) + 1)
+    p = Vector{Float64}(probs); nq = length(p)
+    count = Vector{Int64}(undef, ng); nch = Vector{Int32}(undef, ng); st = Vector{Int32}(undef, ng)
+    pmean = Matrix{Float64}(undef, np, ng); mmean = Matrix{Float64}(undef, nm, ng); mmed = Matrix{Float64}(undef, nm, ng)
+    mq = Array{Float64}(undef, nm, ng, nq); cpp = Array{Float64}(undef, np, np, ng); cpm = Array{Float64}(undef, nm, np, ng)
+    cmm = Array{Float64}(undef, nm, nm, ng); z = Matrix{Float64}(undef, nm, ng); jac = Array{Float64}(undef, np, nm, ng)
+    sens = Array{Float64}(undef, nm, np, ng); se = Matrix{Float64}(undef, np, ng)
+    GC.@preserve g p count nch st pmean mmean mmed mq cpp cpm cmm z jac sens se begin
+        ms = SmmMomentStats(pointer(count), pointer(nch), pointer(st), pointer(pmean), pointer(mmean), pointer(mmed),
+                            nq > 0 ? pointer(mq) : Ptr{Cdouble}(C_NULL), pointer(cpp), pointer(cpm), pointer(cmm), pointer(z), pointer(jac),
+                            pointer(sens), pointer(se))
+        check(h.ctx, ccall(sym(:smm_get_moment_stats), Cint,
+                           (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Int32}, Cint, Ptr{Cdouble}, Cint, Cdouble, Ref{SmmMomentStats}),
+                           h.ctx, t0, t1, HIST_SELECT[select], groups === nothing ? Ptr{Int32}(C_NULL) : pointer(g), ng,
+                           nq > 0 ? pointer(p) : Ptr{Cdouble}(C_NULL), nq, Float64(ridge), ms))
+    end
+    return (count = count, n_chains = nch, status = st, p_mean = pmean, m_mean = mmean, m_median = mmed, m_quantile = mq, cov_pp = cpp,
+            cov_pm = cpm, cov_mm = cmm, fit_z = z, jac = jac, sens = sens, se = se)
 end
 
 # the factor(s) between the header's row-major [np][np] / [N][np][np] and Julia's L[k, j] / L[k, j, c]

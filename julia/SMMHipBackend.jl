@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -448,6 +448,46 @@ function posterior_draws(algo::MAlgoBGPHip; window = nothing, select::Symbol = :
         groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
     end
     return SMMHip.hip_get_draws(hip, t0, t1; select = select, groups = groups, thin = thin, max_rows = max_rows, moments = moments)
+end
+
+# the device's moment statistics of algo's groups (by default the chains with equal `acc_tuners` entries, as `pooled_summary`)
+function moment_stats(algo::MAlgoBGPHip, window, select::Symbol, groups, probs, ridge)
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    t0, t1 = window === nothing ? (0, SMMHip.hip_iter(hip)) : window
+    if groups === nothing
+        ids = Dict{Float64,Int32}()
+        opts = getfield(algo, :opts)
+        groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
+    end
+    return SMMHip.hip_moment_stats(hip, t0, t1; select = select, groups = groups, probs = collect(Float64, probs), ridge = ridge)
+end
+
+"""
+    moment_fit(algo; window = nothing, select = :state, groups = nothing, level = 0.95) -> NamedTuple
+
+The first table of an SMM paper, computed on the device from the history it holds (`SMMHip.hip_moment_stats`), without
+`sync_chains!`: for each group of chains `count[g]`, `n_chains[g]`, `status[g]`, and of the simulated moments over the group's pooled
+draws `mean[k, g]`, `median[k, g]`, `band[k, g, 1:2]` (the quantiles at `level`) and `z[k, g]`, the data moment's distance from the
+posterior predictive in its standard deviations.  `select = :state`: the chains' state series, the MCMC posterior itself.  Not a
+method of `SMM`: the reference has no such table.
+"""
+function moment_fit(algo::MAlgoBGPHip; window = nothing, select::Symbol = :state, groups = nothing, level::Real = 0.95)
+    r = moment_stats(algo, window, select, groups, ((1 - level) / 2, 1 - (1 - level) / 2), 0.0)
+    return (count = r.count, n_chains = r.n_chains, status = r.status, mean = r.m_mean, median = r.m_median, band = r.m_quantile, z = r.fit_z)
+end
+
+"""
+    sensitivity(algo; window = nothing, select = :state, groups = nothing, ridge = 0.0) -> NamedTuple
+
+Identification and standard errors from the pooled draws, on the device (`SMMHip.hip_moment_stats`): `jac[k, m, g]` (dm/dtheta, the
+regression of the simulated moments on the parameters), `sens[m, k, g]` (Andrews, Gentzkow & Shapiro 2017), `se[k, g]` (the sandwich
+standard errors, the weights read as the data moments' standard deviations) and `status[g]`.  No further evaluation of the objective
+and no finite-difference step, unlike `get_stdErrors`.
+"""
+function sensitivity(algo::MAlgoBGPHip; window = nothing, select::Symbol = :state, groups = nothing, ridge::Real = 0.0)
+    r = moment_stats(algo, window, select, groups, Float64[], ridge)
+    return (count = r.count, n_chains = r.n_chains, status = r.status, jac = r.jac, sens = r.sens, se = r.se)
 end
 
 """

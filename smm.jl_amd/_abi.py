@@ -144,6 +144,14 @@ class smm_draws_t(C.Structure):
     ]
 
 
+class smm_moment_stats_t(C.Structure):
+    _fields_ = [
+        ("count", C.POINTER(C.c_int64)), ("n_chains", c_int32_p), ("status", c_int32_p), ("p_mean", c_double_p), ("m_mean", c_double_p),
+        ("m_median", c_double_p), ("m_quantile", c_double_p), ("cov_pp", c_double_p), ("cov_pm", c_double_p), ("cov_mm", c_double_p),
+        ("fit_z", c_double_p), ("jac", c_double_p), ("sens", c_double_p), ("se", c_double_p),
+    ]
+
+
 class smm_population_t(C.Structure):
     _fields_ = [
         ("start", c_double_p), ("value", c_double_p), ("pick", c_int32_p), ("evaluated", C.c_int64),
@@ -204,6 +212,8 @@ SYMBOLS = [
                                     C.POINTER(smm_rank_diag_t)]),
     ("smm_get_draws", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                 C.POINTER(smm_draws_t)]),
+    ("smm_get_moment_stats", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_double_p, C.c_int32, C.c_double,
+                                       C.POINTER(smm_moment_stats_t)]),
     ("smm_get_chain_cov", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
     ("smm_get_proposal", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_proposal", C.c_int, [C.c_void_p, c_double_p]),

@@ -428,6 +428,28 @@ class BGPContext:
         self._check(fn(self._ctx, t0, t1, sel, gp, ng, thin, max_rows, R, C.byref(s)))
         return r
 
+    def moment_stats(self, t0=0, t1=None, select="state", groups=None, probs=(), ridge=0.0, n_groups=None):
+        """the simulated moments of groups of local chains over iterations [t0, t1), on the device (smm_get_moment_stats,
+        include/smmhip.h): a dict of numpy arrays count / n_chains / status [n_groups], p_mean / se [n_groups][np], m_mean / m_median /
+        fit_z [n_groups][nm], m_quantile [len(probs)][n_groups][nm], cov_pp [n_groups][np][np], cov_pm / sens [n_groups][np][nm], cov_mm
+        [n_groups][nm][nm], jac [n_groups][nm][np].  select: 0 / "all", 1 / "accepted" or 2 / "state"; groups: an int per chain
+        (-1 = none), n_groups by default groups.max() + 1, None: every local chain in one group; ridge: the relative ridge on the
+        diagonal of the parameter covariance before it is factored"""
+        t1 = self._t1(t1)
+        p = A.f64(probs).reshape(-1)
+        np_, nm = self.np, self.nm
+        sel = self._select(select)
+        g, gp, ng = self._groups("moment_stats", groups, n_groups)
+        G = max(ng, 0)
+        r = dict(count=np.empty(G, np.int64), n_chains=np.empty(G, np.int32), status=np.empty(G, np.int32), p_mean=np.empty((G, np_)),
+                 m_mean=np.empty((G, nm)), m_median=np.empty((G, nm)), m_quantile=np.empty((len(p), G, nm)), cov_pp=np.empty((G, np_, np_)),
+                 cov_pm=np.empty((G, np_, nm)), cov_mm=np.empty((G, nm, nm)), fit_z=np.empty((G, nm)), jac=np.empty((G, nm, np_)),
+                 sens=np.empty((G, np_, nm)), se=np.empty((G, np_)))
+        s = self._out(A.smm_moment_stats_t, r, () if len(p) else ("m_quantile",))
+        self._check(self._fn("get_moment_stats")(self._ctx, int(t0), int(t1), sel, gp, ng, A.dptr(p) if len(p) else None, len(p),
+                                                 float(ridge), C.byref(s)))
+        return r
+
     def _proposal_shape(self):
         if self.proposal_layout is None:
             return None

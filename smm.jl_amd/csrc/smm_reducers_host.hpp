@@ -1,7 +1,7 @@
 // the host side of the history reducers — part of libsmmhip (included once by smmhip.hip, behind its host helpers; hiprtc never sees it).
 // The family: smm_get_chain_stats, smm_get_chain_cov, smm_get_proposal / _set_ / _adapt_, smm_get_chain_diag, smm_get_group_stats,
-// smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws (kernels: smm_stats.hpp, smm_cov.hpp, smm_diag.hpp, smm_group.hpp,
-// smm_hist.hpp, smm_trace.hpp, smm_rank.hpp, smm_draws.hpp).
+// smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws, smm_get_moment_stats (kernels: smm_stats.hpp, smm_cov.hpp,
+// smm_diag.hpp, smm_group.hpp, smm_moments.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp, smm_draws.hpp).
 // What they share is stated here once: the frame of a call (reducer_call), the checks of the arguments they have in common (check_groups,
 // check_probs, check_select), the prelude and the window behind them (settled_window: reader_prelude and check_window of smmhip.hip), the
 // members of the groups (Groups), one result buffer per context (reducer_result, laid out by Carve / Slice, copied by up / down), one
@@ -152,7 +152,7 @@ int sort_lds_n(int n) { return std::min(STATS_LDS_N, 1 << (int)ceil(log2((double
 
 // the reducers' dynamic LDS (smm_ctx_create): a chunk of draws (k_stats_column, k_cov_center, k_diag_acov, k_group_*, k_trace_column),
 // the partner ids of a pass (k_stats_mode), the counters and edges of a batch of parameters or pairs (k_hist_count, k_hist_pairs), a
-// split chain (k_rank_chain_mom, k_rank_acov)
+// split chain (k_rank_chain_mom, k_rank_acov), the three matrices of a group (k_moment_solve: 3 x 64 x 65 doubles)
 void reducer_kernel_attributes() {
     HIPCHK(hipFuncSetAttribute((const void*)k_stats_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_cov_center, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
@@ -165,6 +165,7 @@ void reducer_kernel_attributes() {
     HIPCHK(hipFuncSetAttribute((const void*)k_trace_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_rank_chain_mom, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_rank_acov, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_moment_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * MAX_DIM * (MAX_DIM + 1) * 8));
 }
 
 }  // namespace
@@ -1008,6 +1009,188 @@ int smm_get_draws(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32
             down(c, d, o_src, out->src_iter ? out->src_iter + r0 : nullptr, (size_t)rn);
             HIPCHK(hipStreamSynchronize(c->stream));   // (the next batch reuses the rows)
         }
+        return SMM_OK;
+    });
+}
+
+// --- simulated moments per group: fit, Jacobian, sensitivity, standard errors (smm_moments.hpp) -------------------------------------------
+
+int smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups, const double* probs,
+                         int32_t n_probs, double ridge, smm_moment_stats_t* out) {
+    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        if (const int rc = check_select(c, select)) return rc;
+        if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
+        if (const int rc = check_probs(c, probs, n_probs, out->m_quantile != nullptr)) return rc;
+        if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(c, SMM_ERR_INVALID_ARG, "ridge must be finite and >= 0");
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t N = P.N, np = P.np, nm = P.nm, D = np + nm, G = n_groups, nq = out->m_quantile ? n_probs : 0;
+        const int n = t1 - t0;
+        const bool med = out->m_median != nullptr, ord = med || nq > 0;
+        const bool solve = out->status || out->jac || out->sens || out->se;
+        const bool cov = solve || out->cov_pp || out->cov_pm || out->cov_mm || out->fit_z;
+        const bool cols = cov || ord || out->p_mean || out->m_mean;
+        // the members' counts (select 1: k_group_gather's counting form; otherwise every row of the window), then smm_get_group_stats'
+        // plan on the host: the pooled offsets and the chunks
+        const Groups grp = group_members(group, G, N);
+        const std::vector<int>& gid = grp.gid;
+        std::vector<int> cnt(N, n);
+        DevBuf<int> dci(2 * N);
+        HIPCHK(hipMemcpyAsync(dci.p, gid.data(), N * 4, hipMemcpyHostToDevice, c->stream));
+        if (select == 1) {
+            launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, 1, (const int*)dci.p,
+                           (const long long*)nullptr, (const int*)nullptr, 0, 0, 0ll, 0, 0, (const double*)nullptr, (int)np, (double*)nullptr,
+                           dci.p + N, 1);
+            HIPCHK(hipMemcpyAsync(cnt.data(), dci.p + N, N * 4, hipMemcpyDeviceToHost, c->stream));
+        } else
+            HIPCHK(hipMemcpyAsync(dci.p + N, cnt.data(), N * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        std::vector<long long> gm(G, 0), G0(G + 1, 0), off(N, 0), roff(N, 0);
+        std::vector<int> gch0(G + 1, 0), cch0(N, 0);
+        for (size_t i = 0; i < N; ++i)
+            if (gid[i] >= 0) { roff[i] = gm[gid[i]]; gm[gid[i]] += cnt[i]; }
+        std::vector<long long> cst;
+        std::vector<int> clen;
+        for (size_t g = 0; g < G; ++g) {
+            G0[g + 1] = G0[g] + gm[g];
+            for (long long q = 0; q < gm[g]; q += STATS_LDS_N) { cst.push_back(G0[g] + q); clen.push_back((int)std::min<long long>(STATS_LDS_N, gm[g] - q)); }
+            gch0[g + 1] = (int)cst.size();
+        }
+        for (size_t i = 0; i < N; ++i)
+            if (gid[i] >= 0) { off[i] = G0[gid[i]] + roff[i]; cch0[i] = gch0[gid[i]]; }
+        const long long Mtot = G0[G];
+        const int NC = (int)cst.size();
+        if (out->count) std::copy(gm.begin(), gm.end(), out->count);
+        if (out->n_chains) std::copy(grp.n_chains.begin(), grp.n_chains.end(), out->n_chains);
+        if (!cols || G == 0) return SMM_OK;
+        if (Mtot == 0) {   // no row in any group: status 1, everything else NaN
+            auto nan = [](double* p, size_t k) { if (p) std::fill(p, p + k, NAN); };
+            if (out->status) std::fill(out->status, out->status + G, 1);
+            nan(out->p_mean, G * np); nan(out->m_mean, G * nm); nan(out->m_median, G * nm); nan(out->m_quantile, nq * G * nm);
+            nan(out->cov_pp, G * np * np); nan(out->cov_pm, G * np * nm); nan(out->cov_mm, G * nm * nm); nan(out->fit_z, G * nm);
+            nan(out->jac, G * nm * np); nan(out->sens, G * np * nm); nan(out->se, G * np);
+            return SMM_OK;
+        }
+        // the moments' order statistics: short columns sorted in LDS, the others selected grid-wide at ranks R per column (rk: -1 = unused)
+        std::vector<int> sgrp, wgrp;
+        long long wmax = 0;
+        for (size_t g = 0; g < G; ++g)
+            if (gm[g] < c->H.group_wide_min) sgrp.push_back((int)g);
+            else { wgrp.push_back((int)g); wmax = std::max(wmax, gm[g]); }
+        const int R = ord ? (med ? 2 : 0) + 2 * (int)nq : 0;
+        std::vector<long long> rk(wgrp.size() * R, -1);
+        for (size_t wi = 0; wi < wgrp.size() && R; ++wi) {   // stats_quantile's and the median's indexes
+            const long long m = gm[wgrp[wi]];
+            long long* r = rk.data() + wi * R;
+            if (med) { r[0] = (m & 1) ? m / 2 : m / 2 - 1; r[1] = (m & 1) ? -1 : m / 2; r += 2; }
+            for (size_t p = 0; p < nq; ++p, r += 2) {
+                const double h = (double)(m - 1) * probs[p];
+                if (h >= (double)(m - 1)) r[0] = m - 1;
+                else { r[0] = (long long)floor(h); r[1] = r[0] + 1; }
+            }
+        }
+        // the batch plan: kb packed joint columns at a time in the scratch; the covariance Nbc chunks at a time, every joint column of a
+        // chunk in the scratch and the chunks' D x D pair sums in the result buffer, both under the cap
+        reducer_scratch(c, std::max(N * (size_t)P.T * 8, cov ? D * STATS_LDS_N * 8 : 0));
+        const size_t hook = c->H.stats_scratch;
+        const size_t budget = hook ? std::min(c->st_scr_bytes, std::max({hook, (size_t)Mtot * 8, cov ? D * STATS_LDS_N * 8 : 0})) : c->st_scr_bytes;
+        const size_t kb = std::min(D, budget / ((size_t)Mtot * 8));
+        const int Nbc = !cov ? 0 : (int)std::max<size_t>(1, std::min({(size_t)NC, budget / (D * STATS_LDS_N * 8), reducer_batch_cap(c) / (D * D * 8)}));
+        const size_t nwc = wgrp.size() * std::min(kb, nm);   // long moment columns of a batch, selected WB at a time
+        const int WB = R ? (int)std::min(nwc, std::max((size_t)1, GROUP_HIST_CAP / ((size_t)R * GROUP_BINS * 8))) : 0;
+        Carve Rv;   // 8-byte slices first
+        const auto mean = Rv.take<double>(G * D), median = Rv.take<double>(G * D), quant = Rv.take<double>(nq * G * D),
+                   acc = Rv.take<double>(cov ? G * D * D : 0), dprobs = Rv.take<double>(nq), csum = Rv.take<double>(kb * NC),
+                   csum2 = Rv.take<double>(cov ? D * D * (size_t)Nbc : 0);
+        const auto o_pmean = Rv.take<double>(G * np), o_mmean = Rv.take<double>(G * nm), o_mmed = Rv.take<double>(G * nm),
+                   o_mq = Rv.take<double>(nq * G * nm), o_cpp = Rv.take<double>(G * np * np), o_cpm = Rv.take<double>(G * np * nm),
+                   o_cmm = Rv.take<double>(G * nm * nm), o_z = Rv.take<double>(G * nm), o_jac = Rv.take<double>(G * nm * np),
+                   o_sens = Rv.take<double>(G * np * nm), o_se = Rv.take<double>(G * np);
+        const auto doff = Rv.take<long long>(2 * N), dG0 = Rv.take<long long>(G + 1), dgm = Rv.take<long long>(G),
+                   dcst = Rv.take<long long>(NC), drk = Rv.take<long long>(rk.size()), rem = Rv.take<long long>(nwc * R);
+        const auto pre = Rv.take<unsigned long long>(nwc * R), ghist = Rv.take<unsigned long long>((size_t)WB * R * GROUP_BINS);
+        const auto dcch0 = Rv.take<int>(N), dgch0 = Rv.take<int>(G + 1), dclen = Rv.take<int>(NC), cnan = Rv.take<int>(kb * NC),
+                   gnan = Rv.take<int>(G * D), dsg = Rv.take<int>(sgrp.size()), dwg = Rv.take<int>(wgrp.size()), gbad = Rv.take<int>(G),
+                   o_st = Rv.take<int>(G);
+        void* d = reducer_result(c, Rv.bytes);
+        std::vector<long long> offs(off);
+        offs.insert(offs.end(), roff.begin(), roff.end());
+        up(c, d, doff, offs); up(c, d, dG0, G0); up(c, d, dgm, gm); up(c, d, dcst, cst); up(c, d, drk, rk);
+        up(c, d, dcch0, cch0); up(c, d, dgch0, gch0); up(c, d, dclen, clen); up(c, d, dsg, sgrp); up(c, d, dwg, wgrp);
+        up(c, d, dprobs, probs, nq);
+        HIPCHK(hipMemsetAsync(gbad.in(d), 0, G * 4, c->stream));
+        const int* dgid = dci.p;
+        const int* dcnt = dci.p + N;
+        double* col = (double*)c->st_scr;
+        double* omed = med ? median.in(d) : nullptr;
+        std::vector<long long> remh(nwc * R);
+        const int B = (int)std::min<long long>(1024, std::max<long long>(1, (wmax + STATS_WG * 16 - 1) / (STATS_WG * 16)));
+        for (size_t k0 = 0; k0 < D; k0 += kb) {   // batches of joint columns: the packed columns [kbb][Mtot]
+            const int kbb = (int)std::min(kb, D - k0);
+            launch_checked(c, k_moment_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, dgid,
+                           (const long long*)doff.in(d), (const int*)nullptr, (int)k0, kbb, Mtot, 0, 0, (const double*)nullptr, (int)D, col,
+                           dcnt, gbad.in(d));
+            launch_checked(c, k_group_chunk_sum, dim3(NC, kbb), dim3(STATS_WG), (size_t)STATS_LDS_N * 8, (const double*)col, Mtot,
+                           (const long long*)dcst.in(d), (const int*)dclen.in(d), NC, csum.in(d), cnan.in(d));
+            launch_checked(c, k_group_mean, dim3((unsigned)((G * kbb + 255) / 256)), dim3(256), 0, (const double*)csum.in(d),
+                           (const int*)cnan.in(d), NC, (const int*)dgch0.in(d), (const long long*)dgm.in(d), (int)G, (int)k0, kbb, (int)D,
+                           mean.in(d), gnan.in(d));
+            const size_t ks = std::max(k0, np);   // the batch's moment columns [ks, k0 + kbb): the order statistics are theirs alone
+            if (!ord || ks >= k0 + kbb) continue;
+            const int km = (int)(k0 + kbb - ks);
+            const double* mcol = col + (ks - k0) * (size_t)Mtot;
+            if (!sgrp.empty())
+                launch_checked(c, k_group_small, dim3((unsigned)sgrp.size(), km), dim3(STATS_WG), (size_t)STATS_LDS_N * 8, mcol, Mtot,
+                               (const int*)dsg.in(d), (const long long*)dG0.in(d), (const long long*)dgm.in(d), (int)G, (int)ks, (int)D,
+                               (const int*)gnan.in(d), (const double*)dprobs.in(d), (int)nq, omed, quant.in(d));
+            if (wgrp.empty()) continue;
+            const int nw = (int)wgrp.size() * km;
+            for (int w = 0; w < nw; ++w)
+                for (int r = 0; r < R; ++r) remh[(size_t)w * R + r] = rk[(size_t)(w / km) * R + r];
+            up(c, d, rem, remh.data(), (size_t)nw * R);
+            HIPCHK(hipMemsetAsync(pre.in(d), 0, (size_t)nw * R * 8, c->stream));
+            HIPCHK(hipMemsetAsync(ghist.in(d), 0, (size_t)WB * R * GROUP_BINS * 8, c->stream));   // (k_group_pick zeroes it again)
+            for (int w0 = 0; w0 < nw; w0 += WB) {
+                const int wn = std::min(WB, nw - w0);
+                for (int dg = 0; dg < 6; ++dg) {
+                    launch_checked(c, k_group_hist, dim3(wn, B, (R + GROUP_RB - 1) / GROUP_RB), dim3(STATS_WG), 0, mcol, Mtot,
+                                   (const int*)dwg.in(d), (const long long*)dG0.in(d), (const long long*)dgm.in(d), km, R, dg, w0,
+                                   (const long long*)rem.in(d), (const unsigned long long*)pre.in(d), ghist.in(d));
+                    launch_checked(c, k_group_pick, dim3(wn * R), dim3(STATS_WG), 0, dg, w0 * R, ghist.in(d), rem.in(d), pre.in(d));
+                }
+            }
+            launch_checked(c, k_group_finish, dim3((nw + 63) / 64), dim3(64), 0, nw, (const int*)dwg.in(d), (const long long*)dgm.in(d), (int)G,
+                           (int)ks, km, (int)D, R, (const long long*)drk.in(d), (const unsigned long long*)pre.in(d), (const int*)gnan.in(d),
+                           (const double*)dprobs.in(d), (int)nq, omed, quant.in(d));
+        }
+        if (cov) {   // batches of chunks: every joint column centred, [D][nb][STATS_LDS_N]; each chunk's pair sums, added onto the groups'
+            HIPCHK(hipMemsetAsync(acc.in(d), 0, G * D * D * 8, c->stream));
+            const int nt = ((int)D + COV_T - 1) / COV_T, ntiles = nt * (nt + 1) / 2;
+            for (int cb0 = 0; cb0 < NC; cb0 += Nbc) {
+                const int nb = std::min(Nbc, NC - cb0);
+                launch_checked(c, k_moment_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, dgid,
+                               (const long long*)doff.in(d) + N, (const int*)dcch0.in(d), 0, (int)D, Mtot, cb0, nb, (const double*)mean.in(d),
+                               (int)D, col, dcnt, (int*)nullptr);
+                launch_checked(c, k_cov_pairs, dim3(nb, ntiles), dim3(COV_WG), 0, (const double*)col, STATS_LDS_N, nb, 0, nb, (int)D,
+                               (const int*)dclen.in(d) + cb0, csum2.in(d), 1);
+                launch_checked(c, k_moment_cov_acc, dim3((unsigned)((G * D * (D + 1) / 2 + 255) / 256)), dim3(256), 0,
+                               (const double*)csum2.in(d), nb, cb0, (const int*)dgch0.in(d), (int)G, (int)D, acc.in(d));
+            }
+        }
+        auto want = [&](const void* p, auto sl) { return p ? sl.in(d) : nullptr; };
+        const MomentOut mo{want(out->status, o_st), want(out->p_mean, o_pmean), want(out->m_mean, o_mmean), want(out->m_median, o_mmed),
+                           want(out->m_quantile, o_mq), want(out->cov_pp, o_cpp), want(out->cov_pm, o_cpm), want(out->cov_mm, o_cmm),
+                           want(out->fit_z, o_z), want(out->jac, o_jac), want(out->sens, o_sens), want(out->se, o_se)};
+        launch_checked(c, k_moment_solve, dim3((unsigned)G), dim3(MOMENT_WG), (2 * np + nm) * (np + 1) * 8,
+                       cov ? (const double*)acc.in(d) : (const double*)nullptr, (const double*)mean.in(d), (const double*)omed,
+                       (const double*)quant.in(d), (const long long*)dgm.in(d), (const int*)gbad.in(d), (int)G, (int)np, (int)nm, (int)nq, ridge,
+                       P.mom, P.w, (int)solve, mo);
+        down(c, d, o_st, out->status, G); down(c, d, o_pmean, out->p_mean, G * np); down(c, d, o_mmean, out->m_mean, G * nm);
+        down(c, d, o_mmed, out->m_median, G * nm); down(c, d, o_mq, out->m_quantile, nq * G * nm);
+        down(c, d, o_cpp, out->cov_pp, G * np * np); down(c, d, o_cpm, out->cov_pm, G * np * nm); down(c, d, o_cmm, out->cov_mm, G * nm * nm);
+        down(c, d, o_z, out->fit_z, G * nm); down(c, d, o_jac, out->jac, G * nm * np); down(c, d, o_sens, out->sens, G * np * nm);
+        down(c, d, o_se, out->se, G * np);
+        HIPCHK(hipStreamSynchronize(c->stream));
         return SMM_OK;
     });
 }

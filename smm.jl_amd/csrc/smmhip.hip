@@ -70,6 +70,7 @@ using namespace smm;
 #include "smm_cov.hpp"
 #include "smm_diag.hpp"
 #include "smm_group.hpp"
+#include "smm_moments.hpp"
 #include "smm_hist.hpp"
 #include "smm_trace.hpp"
 #include "smm_rank.hpp"

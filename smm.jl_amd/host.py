@@ -655,6 +655,47 @@ def draws(x, groups=None, window=None, accepted_only=True, state=False, thin=1, 
     return out[0] if j is not None else out
 
 
+def _moment_stats(algo, groups, window, state, accepted_only, probs, ridge):
+    """the device's moment statistics of the groups of algo (smm_get_moment_stats): window = (t0, t1) (default: the whole run)"""
+    t0, t1 = (0, algo.i) if window is None else (int(window[0]), int(window[1]))
+    g = np.asarray(_default_groups(algo) if groups is None else groups, np.int32)
+    sel = "state" if state else "accepted" if accepted_only else "all"
+    return algo._ctx.moment_stats(t0, t1, sel, g, tuple(float(p) for p in probs), float(ridge))
+
+
+def moment_fit(algo, groups=None, window=None, state=True, level=0.95, accepted_only=True):
+    """the first table of an SMM paper, from the device (include/smmhip.h: smm_get_moment_stats) without downloading the history: one
+    OrderedDict per group with count, chains, status and, keyed by ms_names, data (the data moment), mean and median (of the simulated
+    moments over the group's pooled draws), band ([lo, hi] at `level`) and z (the data moment's distance from the posterior predictive
+    in its standard deviations).  state: the chains' state series, the MCMC posterior itself (default), else their accepted draws
+    (accepted_only) or every row; groups: a group id per chain (-1 = none), by default those of rhat / pooled"""
+    q = ((1 - level) / 2, 1 - (1 - level) / 2)
+    r = _moment_stats(algo, groups, window, state, accepted_only, q, 0.0)
+    names = ms_names(algo.m)
+    return [OrderedDict(count=int(r["count"][j]), chains=int(r["n_chains"][j]), status=int(r["status"][j]),
+                        data=OrderedDict((k, float(algo.m.moments[k]["value"])) for k in names),
+                        mean=OrderedDict((k, float(r["m_mean"][j, i])) for i, k in enumerate(names)),
+                        median=OrderedDict((k, float(r["m_median"][j, i])) for i, k in enumerate(names)),
+                        band=OrderedDict((k, r["m_quantile"][:, j, i].copy()) for i, k in enumerate(names)),
+                        z=OrderedDict((k, float(r["fit_z"][j, i])) for i, k in enumerate(names)))
+            for j in _builtins_range(r["count"].shape[0])]
+
+
+def sensitivity(algo, groups=None, window=None, state=True, ridge=0.0, accepted_only=True):
+    """identification and standard errors from the pooled draws, on the device (include/smmhip.h: smm_get_moment_stats): one OrderedDict
+    per group with count, chains, status (0 ok; 1 too few rows; 2 a non-finite value; 3 the parameter covariance, 4 J'WJ not positive
+    definite), jac (moment name -> parameter name -> dm/dtheta, the regression of the simulated moments on the parameters), sens
+    (parameter name -> moment name -> the sensitivity of Andrews, Gentzkow & Shapiro 2017) and se (parameter name -> the sandwich
+    standard error, the moments' weights read as the data moments' standard deviations).  groups, window and state as in moment_fit"""
+    r = _moment_stats(algo, groups, window, state, accepted_only, (), ridge)
+    ps, ms = ps2s_names(algo.m), ms_names(algo.m)
+    return [OrderedDict(count=int(r["count"][j]), chains=int(r["n_chains"][j]), status=int(r["status"][j]),
+                        jac=OrderedDict((k, OrderedDict((q, float(r["jac"][j, a, b])) for b, q in enumerate(ps))) for a, k in enumerate(ms)),
+                        sens=OrderedDict((q, OrderedDict((k, float(r["sens"][j, b, a])) for a, k in enumerate(ms))) for b, q in enumerate(ps)),
+                        se=OrderedDict((q, float(r["se"][j, b])) for b, q in enumerate(ps)))
+            for j in _builtins_range(r["count"].shape[0])]
+
+
 def summary(x):
     """summary(c::BGPChain) AlgoBGP.jl:197-206 / summary(m::MAlgoBGP) :541-550"""
     if isinstance(x, MAlgoBGP):
