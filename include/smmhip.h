@@ -748,6 +748,65 @@ typedef struct {            /* caller-allocated; any pointer may be NULL = not c
 int  smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group /* [N] or NULL */,
                           int32_t n_groups, const double* probs, int32_t n_probs, double ridge, smm_moment_stats_t* out);
 
+/* The objective and the simulated moments binned along parameters, computed on the device from the history it holds: for each group of
+ * chains and each parameter, over smm_get_histogram's bins of that parameter, the profile of the objective (the smallest value among the
+ * rows of the bin and the row that attains it, with its full parameter vector: the lower envelope a slice plot draws, over everywhere the
+ * chains went), the mean value and the mean of every simulated moment; and for each pair of parameters the same minima and means over
+ * smm_get_histogram's 2-D cells (the objective surface for a contour plot).  No further evaluation of the objective.  The window, the
+ * groups and select (0 all rows, 1 accepted rows, 2 the state series through a(t)) are exactly those of smm_get_histogram; a shard
+ * reports its own local chains.  For select 2, row a(t) supplies the parameters, the value and the moments alike, as in
+ * smm_get_moment_stats; min_iter is the window iteration t of the pooled row, not a(t).  Caller-allocated; any pointer may be NULL (not
+ * computed).  Read-only and ordered like smm_get_chain_stats (it settles, flushes and synchronises, and changes no state, history or
+ * generator).  Device memory: the reducers' scratch and result buffer, in batches of groups and of axes (an axis: a parameter with
+ * nseg = bins segments, or a pair with nseg = bins2 bins2).  A batch of mb member chains and an axes takes mb n 12 + an mb (8 n + 4 nseg)
+ * bytes of the scratch (n = t1 - t0: each pooled row's source row and value; per axis its segment, its slot in the compacted list and
+ * the per-member segment counts) and, for its gn groups, gn an nseg (60 + 8 np + 8 nm) bytes of results plus 12 + 8 (1 + nm) bytes per
+ * chunk of 8192 scored rows, N x (12 + 20 np) bytes of per-chain ranges and lists and smm_get_histogram's edge tables.  Groups are taken
+ * while one axis of them fits the scratch (256 MiB unless the whole history's columns are smaller) and 256 MiB of results, then as many
+ * axes as fit; the scratch is grown where needed to one axis of the largest group.  SMM_ERR_INVALID_ARG: NULL ctx or out, a bad window,
+ * select outside [0, 2], n_groups < 0, group NULL with n_groups != 1, a group id outside [-1, n_groups), bins outside [1, 4096], a range
+ * row not finite or with lo > hi, n_pairs outside [0, np np], pairs NULL with n_pairs > 0, a pair entry outside [0, np), bins2 outside
+ * [1, 256] with n_pairs > 0, a 2-D output requested with n_pairs == 0, a group whose pooled rows would number more than 2^31 - 1;
+ * nothing is written then.
+ *
+ * Numerical contract (every operation rounded on its own, no fma; ranks and counts 64-bit):
+ *   axes       : smm_get_histogram's 1-D and 2-D rules bit for bit: the outer edges, edges, edges2, status, the bin of a row and the
+ *                cell of a row.  A row that numpy drops is dropped here (outside [lo, hi], NaN, or a 2-D axis out of range).  An axis
+ *                with status 1-3 (a pair with status 1 or 2 on either axis) has n = 0 and every double NaN.  n and n2 equal hist and
+ *                hist2 of smm_get_histogram called with the same arguments.
+ *   segment    : the rows of a bin or cell in pooled order: the members in ascending local index, each in iteration order.  A row is
+ *                scored when |value| <= DBL_MAX; failed evaluations and NaN values count in n but in nothing else.
+ *   v_mean, v_mean2, m_mean[..][k] : the chain-stats mean of the segment's m = n_scored scored rows as a contiguous column: S / m,
+ *                S = S + pw(x, c, min(8192, m - c)) for c = 0, 8192, .. counted from the segment's first scored row: np.mean(col[idx]).
+ *                m == 0: NaN.  A moment that is NaN in a scored row propagates into that moment's mean only.
+ *   v_min      : the first minimum of the scored column in pooled order; ties go to the earliest row, -0 and +0 compare equal (the
+ *                earlier one is reported, with its sign).  min_chain: that row's 1-based GLOBAL chain id, min_iter: its 1-based
+ *                iteration t + 1 (smm_get_draws' chain and iter), theta_at_min: its np parameters bit for bit.  m == 0: v_min NaN,
+ *                min_chain and min_iter 0, theta_at_min NaN. */
+typedef struct {            /* caller-allocated; any pointer may be NULL = not computed; G = n_groups, B = bins, B2 = bins2 */
+    int64_t* count;         /* [G]                      rows selected for the group                                  */
+    int32_t* status;        /* [G][np]                  smm_get_histogram's status of the axis                        */
+    double*  edges;         /* [G][np][B + 1]                                                                          */
+    int64_t* n;             /* [G][np][B]               rows in the bin (== smm_get_histogram's hist)                  */
+    int64_t* n_scored;      /* [G][np][B]               of them, rows with a finite value                              */
+    double*  v_min;         /* [G][np][B]               profile: smallest value among the scored rows                  */
+    int32_t* min_chain;     /* [G][np][B]               the row that attains it: chain and iteration, numbered as      */
+    int32_t* min_iter;      /* [G][np][B]               smm_get_draws numbers a row's chain and iteration; 0 = none    */
+    double*  theta_at_min;  /* [G][np][B][np]           that row's parameters (the profile path)                       */
+    double*  v_mean;        /* [G][np][B]               mean value over the scored rows                                */
+    double*  m_mean;        /* [G][np][B][nm]           mean simulated moment over the scored rows                     */
+    double*  edges2;        /* [G][np][B2 + 1]                                                                         */
+    int64_t* n2;            /* [G][n_pairs][B2][B2]     (== smm_get_histogram's hist2)                                 */
+    int64_t* n_scored2;     /* [G][n_pairs][B2][B2]                                                                    */
+    double*  v_min2;        /* [G][n_pairs][B2][B2]                                                                    */
+    int32_t* min_chain2;    /* [G][n_pairs][B2][B2]                                                                    */
+    int32_t* min_iter2;     /* [G][n_pairs][B2][B2]                                                                    */
+    double*  v_mean2;       /* [G][n_pairs][B2][B2]                                                                    */
+} smm_profile_t;
+int  smm_get_profile(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group /* [N] or NULL */, int32_t n_groups,
+                     int32_t bins, const double* range /* [np][2] or NULL */, const int32_t* pairs /* [n_pairs][2] */,
+                     int32_t n_pairs, int32_t bins2, smm_profile_t* out);
+
 /* Covariances of the chains' draws and the proposal factor between steps — adaptive Metropolis (Haario et al.) on top of chol_L: a
  * pilot run, then each chain's proposal shaped by the covariance of its own draws, without leaving the device.
  *

@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_profile, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_set_population!, hip_scatter_population!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
@@ -151,6 +151,27 @@ struct SmmMomentStats
     jac::Ptr{Cdouble}
     sens::Ptr{Cdouble}
     se::Ptr{Cdouble}
+end
+
+struct SmmProfile
+    count::Ptr{Int64}
+    status::Ptr{Int32}
+    edges::Ptr{Cdouble}
+    n::Ptr{Int64}
+    n_scored::Ptr{Int64}
+    v_min::Ptr{Cdouble}
+    min_chain::Ptr{Int32}
+    min_iter::Ptr{Int32}
+    theta_at_min::Ptr{Cdouble}
+    v_mean::Ptr{Cdouble}
+    m_mean::Ptr{Cdouble}
+    edges2::Ptr{Cdouble}
+    n2::Ptr{Int64}
+    n_scored2::Ptr{Int64}
+    v_min2::Ptr{Cdouble}
+    min_chain2::Ptr{Int32}
+    min_iter2::Ptr{Int32}
+    v_mean2::Ptr{Cdouble}
 end
 
 struct SmmGroupStats
@@ -568,6 +589,52 @@ function hip_histogram(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :ac
                            max(b2, 1), hs))
     end
     return (count = count, status = st, lo = lo, hi = hi, edges = edges, hist = hist, edges2 = edges2, hist2 = hist2)
+end
+
+"""
+    hip_profile(h, t0, t1; select = :accepted, groups = nothing, bins = 20, range = nothing, pairs = Tuple{Int,Int}[],
+                bins2 = bins, moments = true) -> NamedTuple
+
+The objective and the simulated moments binned along parameters over iterations `t0+1 .. t1`, on the device (`smm_get_profile`)
+without downloading the history: per group, parameter and `hip_histogram` bin the rows `n`, the scored rows `n_scored` (finite value),
+the smallest value `v_min` with the row that attains it (`min_chain`, `min_iter`, 1-based, 0 = none; `theta_at_min[:, b, k, g]`), the
+mean value `v_mean` and, with `moments`, the mean simulated moments `m_mean[:, b, k, g]`; with `pairs` the same over the 2-D cells
+(`n2`, `n_scored2`, `v_min2`, `min_chain2`, `min_iter2`, `v_mean2`, each `[k_bin, j_bin, p, g]`).  Arguments as `hip_histogram`.
+Arrays are the header's row-major ones.
+"""
+function hip_profile(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :accepted,
+                     groups::Union{Nothing,AbstractVector{<:Integer}} = nothing, bins::Integer = 20,
+                     range::Union{Nothing,AbstractMatrix{<:Real}} = nothing, pairs = Tuple{Int,Int}[], bins2::Integer = bins,
+                     moments::Bool = true)
+    N, np, nm = h.N, h.np, h.nm
+    g = groups === nothing ? Int32[] : Vector{Int32}(groups)
+    groups === nothing || length(g) == N || throw(ArgumentError("groups needs one entry per chain"))
+    ng = groups === nothing ? 1 : (isempty(g) ? 0 : Int(maximum(g)) + 1)
+    rg = range === nothing ? Float64[] : vec(Matrix{Float64}(permutedims(range)))   # row k = (lo, hi)
+    pr = Int32[v - 1 for p in pairs for v in p]
+    npr = length(pairs)
+    b2 = npr > 0 ? Int(bins2) : 0
+    count = Vector{Int64}(undef, ng); st = Matrix{Int32}(undef, np, ng); edges = Array{Float64}(undef, bins + 1, np, ng)
+    n = Array{Int64}(undef, bins, np, ng); nsc = Array{Int64}(undef, bins, np, ng); vmin = Array{Float64}(undef, bins, np, ng)
+    mch = Array{Int32}(undef, bins, np, ng); mit = Array{Int32}(undef, bins, np, ng); theta = Array{Float64}(undef, np, bins, np, ng)
+    vmean = Array{Float64}(undef, bins, np, ng); mmean = Array{Float64}(undef, moments ? nm : 0, bins, np, ng)
+    edges2 = Array{Float64}(undef, b2 + 1, np, ng); n2 = Array{Int64}(undef, b2, b2, npr, ng); nsc2 = Array{Int64}(undef, b2, b2, npr, ng)
+    vmin2 = Array{Float64}(undef, b2, b2, npr, ng); mch2 = Array{Int32}(undef, b2, b2, npr, ng); mit2 = Array{Int32}(undef, b2, b2, npr, ng)
+    vmean2 = Array{Float64}(undef, b2, b2, npr, ng)
+    two(a, T) = npr > 0 ? pointer(a) : Ptr{T}(C_NULL)
+    GC.@preserve g rg pr count st edges n nsc vmin mch mit theta vmean mmean edges2 n2 nsc2 vmin2 mch2 mit2 vmean2 begin
+        ps = SmmProfile(pointer(count), pointer(st), pointer(edges), pointer(n), pointer(nsc), pointer(vmin), pointer(mch), pointer(mit),
+                        pointer(theta), pointer(vmean), moments ? pointer(mmean) : Ptr{Cdouble}(C_NULL), two(edges2, Cdouble),
+                        two(n2, Int64), two(nsc2, Int64), two(vmin2, Cdouble), two(mch2, Int32), two(mit2, Int32), two(vmean2, Cdouble))
+        check(h.ctx, ccall(sym(:smm_get_profile), Cint,
+                           (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Int32}, Cint, Cint, Ptr{Cdouble}, Ptr{Int32}, Cint, Cint, Ref{SmmProfile}),
+                           h.ctx, t0, t1, HIST_SELECT[select], groups === nothing ? Ptr{Int32}(C_NULL) : pointer(g), ng, bins,
+                           range === nothing ? Ptr{Cdouble}(C_NULL) : pointer(rg), npr > 0 ? pointer(pr) : Ptr{Int32}(C_NULL), npr,
+                           max(b2, 1), ps))
+    end
+    return (count = count, status = st, edges = edges, n = n, n_scored = nsc, v_min = vmin, min_chain = mch, min_iter = mit,
+            theta_at_min = theta, v_mean = vmean, m_mean = mmean, edges2 = edges2, n2 = n2, n_scored2 = nsc2, v_min2 = vmin2,
+            min_chain2 = mch2, min_iter2 = mit2, v_mean2 = vmean2)
 end
 
 """

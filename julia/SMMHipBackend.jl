@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, profile_objective, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -400,6 +400,30 @@ function chain_histogram(algo::MAlgoBGPHip; window = nothing, select::Symbol = :
         groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
     end
     return SMMHip.hip_histogram(hip, t0, t1; select = select, groups = groups, bins = bins, range = range, pairs = pairs, bins2 = bins2)
+end
+
+"""
+    profile_objective(algo; window = nothing, select = :accepted, groups = nothing, bins = 20, range = nothing,
+                      pairs = Tuple{Int,Int}[], bins2 = bins, moments = true) -> NamedTuple
+
+What `doSlices` draws, read from the run itself: the objective value and every simulated moment against each parameter, binned on the
+device over every row the chains evaluated (`SMMHip.hip_profile`), without `sync_chains!` and without a further evaluation.  Per
+group, parameter and bin: `v_min` (the profile, the lower envelope of the value) with `theta_at_min`, `min_chain`, `min_iter`;
+`v_mean`; `m_mean`; the counts `n` and `n_scored`; with `pairs` the surface `v_min2` / `v_mean2` over the 2-D cells.  Groups, window,
+range and bins as `chain_histogram`.  Not a method of `SMM`: the reference evaluates `np x npoints` new points along the axes.
+"""
+function profile_objective(algo::MAlgoBGPHip; window = nothing, select::Symbol = :accepted, groups = nothing, bins::Integer = 20,
+                           range = nothing, pairs = Tuple{Int,Int}[], bins2::Integer = bins, moments::Bool = true)
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    t0, t1 = window === nothing ? (0, SMMHip.hip_iter(hip)) : window
+    if groups === nothing
+        ids = Dict{Float64,Int32}()
+        opts = getfield(algo, :opts)
+        groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
+    end
+    return SMMHip.hip_profile(hip, t0, t1; select = select, groups = groups, bins = bins, range = range, pairs = pairs, bins2 = bins2,
+                              moments = moments)
 end
 
 """

@@ -152,6 +152,16 @@ class smm_moment_stats_t(C.Structure):
     ]
 
 
+class smm_profile_t(C.Structure):
+    _fields_ = [
+        ("count", C.POINTER(C.c_int64)), ("status", c_int32_p), ("edges", c_double_p), ("n", C.POINTER(C.c_int64)),
+        ("n_scored", C.POINTER(C.c_int64)), ("v_min", c_double_p), ("min_chain", c_int32_p), ("min_iter", c_int32_p),
+        ("theta_at_min", c_double_p), ("v_mean", c_double_p), ("m_mean", c_double_p), ("edges2", c_double_p),
+        ("n2", C.POINTER(C.c_int64)), ("n_scored2", C.POINTER(C.c_int64)), ("v_min2", c_double_p), ("min_chain2", c_int32_p),
+        ("min_iter2", c_int32_p), ("v_mean2", c_double_p),
+    ]
+
+
 class smm_population_t(C.Structure):
     _fields_ = [
         ("start", c_double_p), ("value", c_double_p), ("pick", c_int32_p), ("evaluated", C.c_int64),
@@ -214,6 +224,8 @@ SYMBOLS = [
                                 C.POINTER(smm_draws_t)]),
     ("smm_get_moment_stats", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_double_p, C.c_int32, C.c_double,
                                        C.POINTER(smm_moment_stats_t)]),
+    ("smm_get_profile", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32, c_double_p, c_int32_p,
+                                   C.c_int32, C.c_int32, C.POINTER(smm_profile_t)]),
     ("smm_get_chain_cov", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
     ("smm_get_proposal", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_proposal", C.c_int, [C.c_void_p, c_double_p]),

@@ -450,6 +450,41 @@ class BGPContext:
                                                  float(ridge), C.byref(s)))
         return r
 
+    def profile(self, t0=0, t1=None, select="accepted", groups=None, bins=20, range=None, pairs=(), bins2=None, n_groups=None,
+                moments=True):
+        """the objective and the simulated moments binned along parameters over iterations [t0, t1), on the device (smm_get_profile,
+        include/smmhip.h): a dict of numpy arrays count [n_groups], status [n_groups][np], edges [n_groups][np][bins + 1], n / n_scored /
+        v_min / min_chain / min_iter / v_mean [n_groups][np][bins], theta_at_min [n_groups][np][bins][np], with moments m_mean
+        [n_groups][np][bins][nm] and, with pairs, edges2 [n_groups][np][bins2 + 1] and n2 / n_scored2 / v_min2 / min_chain2 / min_iter2 /
+        v_mean2 [n_groups][len(pairs)][bins2][bins2].  select, groups, range, pairs and bins2 as in histogram"""
+        t1 = self._t1(t1)
+        np_, nm = self.np, self.nm
+        sel = self._select(select)
+        g, gp, ng = self._groups("profile", groups, n_groups)
+        if isinstance(range, dict):
+            if sorted(range) != list(_builtins.range(np_)):
+                raise ValueError("profile: a range dict names every parameter index 0 .. np-1")
+            range = [range[k] for k in _builtins.range(np_)]
+        rg = None if range is None else np.ascontiguousarray(range, np.float64).reshape(np_, 2)
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        b, b2 = int(bins), int(bins if bins2 is None else bins2)
+        npr, G, bb, bb2 = len(pr), max(ng, 0), max(b, 0), max(b2, 0)
+        r = dict(count=np.empty(G, np.int64), status=np.empty((G, np_), np.int32), edges=np.empty((G, np_, bb + 1)),
+                 n=np.empty((G, np_, bb), np.int64), n_scored=np.empty((G, np_, bb), np.int64), v_min=np.empty((G, np_, bb)),
+                 min_chain=np.empty((G, np_, bb), np.int32), min_iter=np.empty((G, np_, bb), np.int32),
+                 theta_at_min=np.empty((G, np_, bb, np_)), v_mean=np.empty((G, np_, bb)))
+        if moments:
+            r.update(m_mean=np.empty((G, np_, bb, nm)))
+        if npr:
+            r.update(edges2=np.empty((G, np_, bb2 + 1)), n2=np.empty((G, npr, bb2, bb2), np.int64),
+                     n_scored2=np.empty((G, npr, bb2, bb2), np.int64), v_min2=np.empty((G, npr, bb2, bb2)),
+                     min_chain2=np.empty((G, npr, bb2, bb2), np.int32), min_iter2=np.empty((G, npr, bb2, bb2), np.int32),
+                     v_mean2=np.empty((G, npr, bb2, bb2)))
+        s = self._out(A.smm_profile_t, r)
+        self._check(self._fn("get_profile")(self._ctx, int(t0), int(t1), sel, gp, ng, b, A.dptr(rg) if rg is not None else None,
+                                            pr.ctypes.data_as(A.c_int32_p) if npr else None, npr, b2, C.byref(s)))
+        return r
+
     def _proposal_shape(self):
         if self.proposal_layout is None:
             return None

@@ -1,7 +1,7 @@
 // the host side of the history reducers — part of libsmmhip (included once by smmhip.hip, behind its host helpers; hiprtc never sees it).
 // The family: smm_get_chain_stats, smm_get_chain_cov, smm_get_proposal / _set_ / _adapt_, smm_get_chain_diag, smm_get_group_stats,
-// smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws, smm_get_moment_stats (kernels: smm_stats.hpp, smm_cov.hpp,
-// smm_diag.hpp, smm_group.hpp, smm_moments.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp, smm_draws.hpp).
+// smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws, smm_get_moment_stats, smm_get_profile (kernels: smm_stats.hpp,
+// smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_moments.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp, smm_draws.hpp, smm_profile.hpp).
 // What they share is stated here once: the frame of a call (reducer_call), the checks of the arguments they have in common (check_groups,
 // check_probs, check_select), the prelude and the window behind them (settled_window: reader_prelude and check_window of smmhip.hip), the
 // members of the groups (Groups), one result buffer per context (reducer_result, laid out by Carve / Slice, copied by up / down), one
@@ -152,7 +152,8 @@ int sort_lds_n(int n) { return std::min(STATS_LDS_N, 1 << (int)ceil(log2((double
 
 // the reducers' dynamic LDS (smm_ctx_create): a chunk of draws (k_stats_column, k_cov_center, k_diag_acov, k_group_*, k_trace_column),
 // the partner ids of a pass (k_stats_mode), the counters and edges of a batch of parameters or pairs (k_hist_count, k_hist_pairs), a
-// split chain (k_rank_chain_mom, k_rank_acov), the three matrices of a group (k_moment_solve: 3 x 64 x 65 doubles)
+// split chain (k_rank_chain_mom, k_rank_acov), the three matrices of a group (k_moment_solve: 3 x 64 x 65 doubles), a chunk of a
+// segment (k_prof_chunk)
 void reducer_kernel_attributes() {
     HIPCHK(hipFuncSetAttribute((const void*)k_stats_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_cov_center, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
@@ -166,6 +167,7 @@ void reducer_kernel_attributes() {
     HIPCHK(hipFuncSetAttribute((const void*)k_rank_chain_mom, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_rank_acov, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_moment_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * MAX_DIM * (MAX_DIM + 1) * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_prof_chunk, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
 }
 
 }  // namespace
@@ -1191,6 +1193,212 @@ int smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, cons
         down(c, d, o_z, out->fit_z, G * nm); down(c, d, o_jac, out->jac, G * nm * np); down(c, d, o_sens, out->sens, G * np * nm);
         down(c, d, o_se, out->se, G * np);
         HIPCHK(hipStreamSynchronize(c->stream));
+        return SMM_OK;
+    });
+}
+
+// --- the objective and the moments binned along parameters (smm_profile.hpp) ------------------------------------------------------------
+
+int smm_get_profile(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups, int32_t bins,
+                    const double* range, const int32_t* pairs, int32_t n_pairs, int32_t bins2, smm_profile_t* out) {
+    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        const size_t N = c->P.N, np = c->P.np, nm = c->P.nm;
+        if (const int rc = check_select(c, select)) return rc;
+        if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
+        if (bins < 1 || bins > 4096) return fail(c, SMM_ERR_INVALID_ARG, "bins must lie in [1, 4096]");
+        if (range)
+            for (size_t k = 0; k < np; ++k)
+                if (!(std::isfinite(range[2 * k]) && std::isfinite(range[2 * k + 1]) && range[2 * k] <= range[2 * k + 1]))
+                    return fail(c, SMM_ERR_INVALID_ARG, "a range row must be finite with lo <= hi");
+        if (n_pairs < 0 || (size_t)n_pairs > np * np || (n_pairs > 0 && !pairs))
+            return fail(c, SMM_ERR_INVALID_ARG, "n_pairs outside [0, np np], or pairs NULL with n_pairs > 0");
+        for (int p = 0; p < 2 * n_pairs; ++p)
+            if (pairs[p] < 0 || (size_t)pairs[p] >= np) return fail(c, SMM_ERR_INVALID_ARG, "a pair entry outside [0, np)");
+        if (n_pairs > 0 && (bins2 < 1 || bins2 > 256)) return fail(c, SMM_ERR_INVALID_ARG, "bins2 must lie in [1, 256]");
+        const bool cells = out->n2 || out->n_scored2 || out->v_min2 || out->min_chain2 || out->min_iter2 || out->v_mean2;
+        if (n_pairs == 0 && (cells || out->edges2)) return fail(c, SMM_ERR_INVALID_ARG, "a 2-D output requested without pairs");
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t G = n_groups, B = bins, B2 = n_pairs > 0 ? bins2 : 0, NP = n_pairs;
+        const int n = t1 - t0;
+        const bool one = out->n || out->n_scored || out->v_min || out->min_chain || out->min_iter || out->theta_at_min || out->v_mean ||
+                         out->m_mean;
+        const bool two = NP > 0 && (cells || out->edges2);
+        const Groups grp = group_members(group, G, N);
+        const int M = grp.M;
+        if ((size_t)grp.longest * (size_t)n > (size_t)INT_MAX)
+            return fail(c, SMM_ERR_INVALID_ARG, "a group whose pooled rows would number more than 2^31 - 1");
+        const bool autor = range == nullptr, cnt_pass = autor || (out->count && select == 1);
+        // the plan.  Scratch of a batch of mb members x an axes of nseg segments: mb n 12 (tab, val) + an mb (8 n + 4 nseg) (code, list,
+        // table).  Results of gn groups x an axes: seg_bytes per segment.  Groups are taken while one axis of them fits both; then as many
+        // axes as fit
+        const size_t nseg1 = one ? B : 0, nseg2 = two && cells ? B2 * B2 : 0, nsegx = std::max(nseg1, nseg2);
+        const size_t ncolx = 1 + (out->m_mean ? nm : 0);
+        const size_t seg_bytes = 8 * 3 + 4 * 3 + 8 * 2 + 4 * 2 + 8 * np + 8 * nm + (8 + 4 + 8 * ncolx) /* a chunk */;
+        auto scratch_of = [&](size_t mb, size_t an, size_t nseg) { return mb * (size_t)n * 12 + an * mb * (8 * (size_t)n + 4 * nseg); };
+        const size_t least = scratch_of(grp.longest, 1, nsegx);
+        reducer_scratch(c, least);
+        const size_t hook = c->H.stats_scratch;
+        const size_t budget = hook ? std::min(c->st_scr_bytes, std::max(hook, least)) : c->st_scr_bytes, rcap = reducer_batch_cap(c);
+        struct GB { size_t g0, gn, mb, an1, an2; };
+        std::vector<GB> plan;
+        size_t segx = 0, gnx = 0, rowx = 0;
+        auto axes = [&](const GB& b, size_t A, size_t nseg) {
+            if (A == 0 || nseg == 0) return (size_t)0;
+            size_t an = A;
+            if (b.mb > 0) {
+                const size_t fixed = b.mb * (size_t)n * 12, per = b.mb * (8 * (size_t)n + 4 * nseg);
+                an = std::min(an, budget > fixed ? (budget - fixed) / per : 0);
+            }
+            an = std::max<size_t>(1, std::min(an, rcap / (b.gn * nseg * seg_bytes)));
+            segx = std::max(segx, b.gn * an * nseg);
+            rowx = std::max(rowx, an * b.mb * (size_t)n);
+            return an;
+        };
+        for (size_t g0 = 0; g0 < G;) {
+            GB b{g0, 0, 0, 0, 0};
+            while (b.g0 + b.gn < G) {
+                const size_t mb = b.mb + grp.n_chains[b.g0 + b.gn];
+                if (b.gn > 0 && (scratch_of(mb, 1, nsegx) > budget || mb * (size_t)n > (size_t)INT_MAX ||
+                                 (b.gn + 1) * std::max<size_t>(nsegx, 1) * seg_bytes > rcap))
+                    break;
+                b.mb = mb; ++b.gn;
+            }
+            b.an1 = axes(b, one ? np : 0, nseg1);
+            b.an2 = axes(b, nseg2 ? NP : 0, nseg2);
+            gnx = std::max(gnx, b.gn);
+            plan.push_back(b);
+            g0 += b.gn;
+        }
+        const size_t NCx = segx + rowx / STATS_LDS_N + 1;
+        Carve Rv;   // 8-byte slices first
+        const auto cmin = Rv.take<double>(autor ? N * np : 0), cmax = Rv.take<double>(autor ? N * np : 0), drng = Rv.take<double>(autor ? 0 : 2 * np),
+                   dlo = Rv.take<double>(G * np), dhi = Rv.take<double>(G * np), edges = Rv.take<double>(gnx * np * (B + 1)),
+                   edges2 = Rv.take<double>(two ? gnx * np * (B2 + 1) : 0), vmin = Rv.take<double>(segx), vmean = Rv.take<double>(segx),
+                   theta = Rv.take<double>(out->theta_at_min ? segx * np : 0), mmean = Rv.take<double>(out->m_mean ? segx * nm : 0),
+                   csum = Rv.take<double>(NCx * ncolx);
+        const auto dn = Rv.take<unsigned long long>(segx), dnsc = Rv.take<unsigned long long>(segx), minkey = Rv.take<unsigned long long>(segx),
+                   dcst = Rv.take<unsigned long long>(NCx);
+        const auto minpos = Rv.take<unsigned>(segx), segstart = Rv.take<unsigned>(segx);
+        const auto chain = Rv.take<int>(segx), iter = Rv.take<int>(segx), segch0 = Rv.take<int>(segx + 1), dclen = Rv.take<int>(NCx),
+                   cbad = Rv.take<int>(autor ? N * np : 0), dcnt = Rv.take<int>(N), dst = Rv.take<int>(G * np), dgid = Rv.take<int>(N),
+                   dgm0 = Rv.take<int>(G + 1), dmem = Rv.take<int>(M), dpairs = Rv.take<int>(2 * NP);
+        void* d = reducer_result(c, Rv.bytes);
+        up(c, d, dgid, grp.gid); up(c, d, dgm0, grp.gmem0); up(c, d, dmem, grp.mem); up(c, d, dpairs, pairs, 2 * NP);
+        up(c, d, drng, range, 2 * np);
+        if (cnt_pass && M > 0)
+            launch_checked(c, k_hist_range, dim3(M, autor ? (unsigned)((np + HIST_KMAX - 1) / HIST_KMAX) : 1), dim3(HIST_WG), 0,
+                           (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, (const int*)dmem.in(d), 0, (int)np, dcnt.in(d),
+                           autor ? cmin.in(d) : (double*)nullptr, cmax.in(d), cbad.in(d));
+        std::vector<unsigned long long> hnsc(segx), hcst;
+        std::vector<unsigned> hstart(segx);
+        std::vector<int> hch0(segx + 1), hclen;
+        // a [gn][an][per] block of the batch into the caller's [G][A][per] array
+        auto block = [&](auto sl, auto* dst, const GB& b, size_t a0, size_t an, size_t A, size_t per) {
+            if (!dst) return;
+            for (size_t gl = 0; gl < b.gn; ++gl)
+                down(c, d, sl.at(gl * an * per), dst + ((b.g0 + gl) * A + a0) * per, an * per);
+        };
+        for (const GB& b : plan) {
+            const int m0 = grp.gmem0[b.g0], mb = (int)b.mb;
+            launch_checked(c, k_hist_edges, dim3((unsigned)b.gn, (unsigned)np), dim3(HIST_WG), 0, (const int*)dgm0.in(d), (const int*)dmem.in(d),
+                           (int)b.g0, (int)np, (const int*)dcnt.in(d), (const double*)cmin.in(d), (const double*)cmax.in(d),
+                           (const int*)cbad.in(d), autor ? (const double*)nullptr : (const double*)drng.in(d), (int)B, (int)B2, dlo.in(d),
+                           dhi.in(d), dst.in(d), edges.in(d), two ? edges2.in(d) : (double*)nullptr);
+            down(c, d, edges, out->edges ? out->edges + b.g0 * np * (B + 1) : nullptr, b.gn * np * (B + 1));
+            if (two) down(c, d, edges2, out->edges2 ? out->edges2 + b.g0 * np * (B2 + 1) : nullptr, b.gn * np * (B2 + 1));
+            double* val = (double*)c->st_scr;
+            int* tab = (int*)(val + (size_t)mb * n);
+            if (mb > 0 && (one || nseg2))
+                launch_checked(c, k_prof_rows, dim3(mb), dim3(PROF_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select,
+                               (const int*)dmem.in(d), m0, tab, val);
+            for (int ph = 0; ph < 2; ++ph) {
+                const size_t A = ph ? NP : np, an_max = ph ? b.an2 : b.an1, nseg = ph ? nseg2 : nseg1;
+                if (an_max == 0) continue;
+                const bool means = ph ? out->v_mean2 != nullptr : (out->v_mean || out->m_mean);
+                const bool where = ph ? (out->v_min2 || out->min_chain2 || out->min_iter2)
+                                      : (out->v_min || out->min_chain || out->min_iter || out->theta_at_min);
+                const int ncol = ph ? 1 : (int)ncolx;
+                for (size_t a0 = 0; a0 < A; a0 += an_max) {
+                    const size_t an = std::min(an_max, A - a0), segs = b.gn * an * nseg, rows = an * (size_t)mb * n;
+                    ProfBatch pb{};
+                    pb.hrec = (const double*)P.hrec; pb.N = (int)N; pb.HW = P.HW; pb.np = (int)np; pb.nm = (int)nm; pb.t0 = t0; pb.n = n; pb.offset = P.offset;
+                    pb.mem = dmem.in(d); pb.gmem0 = dgm0.in(d); pb.gid = dgid.in(d); pb.m0 = m0; pb.mb = mb; pb.g0 = (int)b.g0; pb.gn = (int)b.gn;
+                    pb.two = ph; pb.a0 = (int)a0; pb.an = (int)an; pb.nseg = (int)nseg; pb.B = (int)(ph ? B2 : B);
+                    pb.lds = nseg <= (size_t)std::min(PROF_LDS_SEGS, c->H.hist_lds_bins);
+                    pb.pairs = dpairs.in(d); pb.st = dst.in(d); pb.lo = dlo.in(d); pb.hi = dhi.in(d); pb.edges = ph ? edges2.in(d) : edges.in(d);
+                    pb.tab = tab; pb.val = val; pb.code = tab + (size_t)mb * n; pb.list = (unsigned*)pb.code + rows; pb.table = pb.list + rows;
+                    pb.cnt = dn.in(d); pb.nsc = dnsc.in(d); pb.minkey = minkey.in(d); pb.minpos = minpos.in(d);
+                    pb.segstart = segstart.in(d); pb.segch0 = segch0.in(d); pb.cst = dcst.in(d); pb.clen = dclen.in(d); pb.csum = csum.in(d);
+                    pb.ncol = ncol;
+                    pb.vmin = (ph ? out->v_min2 : out->v_min) ? vmin.in(d) : nullptr;
+                    pb.chain = (ph ? out->min_chain2 : out->min_chain) ? chain.in(d) : nullptr;
+                    pb.iter = (ph ? out->min_iter2 : out->min_iter) ? iter.in(d) : nullptr;
+                    pb.theta = !ph && out->theta_at_min ? theta.in(d) : nullptr;
+                    pb.vmean = (ph ? out->v_mean2 : out->v_mean) ? vmean.in(d) : nullptr;
+                    pb.mmean = !ph && out->m_mean ? mmean.in(d) : nullptr;
+                    HIPCHK(hipMemsetAsync(dn.in(d), 0, segs * 8, c->stream));
+                    HIPCHK(hipMemsetAsync(minkey.in(d), 0xff, segs * 8, c->stream));
+                    HIPCHK(hipMemsetAsync(minpos.in(d), 0xff, segs * 4, c->stream));
+                    const unsigned sblocks = (unsigned)((segs + 255) / 256);
+                    if (mb > 0) {
+                        if (!pb.lds) HIPCHK(hipMemsetAsync(pb.table, 0, an * (size_t)mb * nseg * 4, c->stream));
+                        launch_checked(c, k_prof_count, dim3(mb, (unsigned)an), dim3(PROF_WG), pb.lds ? nseg * 8 : 0, pb);
+                    }
+                    launch_checked(c, k_prof_scan, dim3(sblocks), dim3(256), 0, pb);
+                    int NC = 0, longest = 1;
+                    if (means) {   // the segments' starts in the axis' list and their chunks, planned on the host from the scored counts
+                        HIPCHK(hipMemcpyAsync(hnsc.data(), dnsc.in(d), segs * 8, hipMemcpyDeviceToHost, c->stream));
+                        HIPCHK(hipStreamSynchronize(c->stream));
+                        hcst.clear(); hclen.clear();
+                        for (size_t al = 0; al < an; ++al) {
+                            size_t run = 0;
+                            for (size_t gl = 0; gl < b.gn; ++gl)
+                                for (size_t s = 0; s < nseg; ++s) { hstart[(gl * an + al) * nseg + s] = (unsigned)run; run += hnsc[(gl * an + al) * nseg + s]; }
+                        }
+                        for (size_t e = 0; e < segs; ++e) {
+                            const size_t al = (e / nseg) % an;
+                            hch0[e] = (int)hcst.size();
+                            for (size_t q = 0; q < hnsc[e]; q += STATS_LDS_N) {
+                                hcst.push_back(al * (size_t)mb * n + hstart[e] + q);
+                                hclen.push_back((int)std::min<size_t>(STATS_LDS_N, hnsc[e] - q));
+                                longest = std::max(longest, hclen.back());
+                            }
+                        }
+                        hch0[segs] = NC = (int)hcst.size();
+                        up(c, d, segstart, hstart.data(), segs); up(c, d, segch0, hch0.data(), segs + 1);
+                        up(c, d, dcst, hcst.data(), (size_t)NC); up(c, d, dclen, hclen.data(), (size_t)NC);
+                    }
+                    if (mb > 0 && (means || where))
+                        launch_checked(c, k_prof_scatter, dim3(mb, (unsigned)an), dim3(PROF_WG), pb.lds && means ? nseg * 4 : 0, pb, (int)means);
+                    if (NC > 0)
+                        launch_checked(c, k_prof_chunk, dim3(NC, ncol), dim3(STATS_WG), (size_t)longest * 8, pb);
+                    launch_checked(c, k_prof_finish, dim3(sblocks), dim3(256), 0, pb);
+                    const auto dn64 = Slice<int64_t>{dn.off}, dnsc64 = Slice<int64_t>{dnsc.off};
+                    if (!ph) {
+                        block(dn64, out->n, b, a0, an, A, nseg); block(dnsc64, out->n_scored, b, a0, an, A, nseg);
+                        block(vmin, out->v_min, b, a0, an, A, nseg); block(chain, out->min_chain, b, a0, an, A, nseg);
+                        block(iter, out->min_iter, b, a0, an, A, nseg); block(theta, out->theta_at_min, b, a0, an, A, nseg * np);
+                        block(vmean, out->v_mean, b, a0, an, A, nseg); block(mmean, out->m_mean, b, a0, an, A, nseg * nm);
+                    } else {
+                        block(dn64, out->n2, b, a0, an, A, nseg); block(dnsc64, out->n_scored2, b, a0, an, A, nseg);
+                        block(vmin, out->v_min2, b, a0, an, A, nseg); block(chain, out->min_chain2, b, a0, an, A, nseg);
+                        block(iter, out->min_iter2, b, a0, an, A, nseg); block(vmean, out->v_mean2, b, a0, an, A, nseg);
+                    }
+                    HIPCHK(hipStreamSynchronize(c->stream));   // (the next batch reuses the tables)
+                }
+            }
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+        std::vector<int> cnt(N, n);
+        if (out->count && select == 1 && M > 0) down(c, d, dcnt, cnt.data(), N);
+        down(c, d, dst, out->status, G * np);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (out->count) {
+            std::fill(out->count, out->count + G, (int64_t)0);
+            for (size_t i = 0; i < N; ++i)
+                if (grp.gid[i] >= 0) out->count[grp.gid[i]] += cnt[i];
+        }
         return SMM_OK;
     });
 }

@@ -72,6 +72,7 @@ using namespace smm;
 #include "smm_group.hpp"
 #include "smm_moments.hpp"
 #include "smm_hist.hpp"
+#include "smm_profile.hpp"
 #include "smm_trace.hpp"
 #include "smm_rank.hpp"
 #include "smm_draws.hpp"

@@ -595,6 +595,76 @@ def histogram2d(x, pair, bins=10, range=None, window=None, accepted_only=True, s
     return out[0] if j is not None else out
 
 
+def _profile_call(x, window, accepted_only, state, **kw):
+    """(chain index or None, the device's profile dict) of a chain (alone in group 0) or of the groups of an algo"""
+    if isinstance(x, BGPChain):
+        algo, j = x._algo, x._j
+        g = np.full(algo._ctx.N, -1, np.int32)
+        g[j] = 0
+        kw["n_groups"] = 1
+    else:
+        algo, j = x, None
+        g = np.asarray(_default_groups(algo) if kw.get("groups") is None else kw["groups"], np.int32)
+    kw.pop("groups", None)
+    t0, t1 = (0, algo.i) if window is None else (int(window[0]), int(window[1]))
+    sel = "state" if state else "accepted" if accepted_only else "all"
+    return j, algo._ctx.profile(t0, t1, sel, g, **kw)
+
+
+def profile(x, bins=20, range=None, window=None, accepted_only=True, state=False, groups=None, moments=True):
+    """what the reference's slices draw (doSlices: the objective value and every simulated moment against one parameter), read from the
+    run itself on the device (include/smmhip.h: smm_get_profile) without downloading the history and without a further evaluation: an
+    OrderedDict parameter name -> OrderedDict(edges [bins + 1], n, n_scored, v_min (the profile: the smallest value in the bin), min_chain,
+    min_iter (1-based, 0 = none), theta_at_min (parameter name -> [bins]), v_mean and, with moments, m_mean (moment name -> [bins])) for a
+    chain, a list of them (one per group) for an algo, whose groups default to those of rhat / pooled.  bins, range, window,
+    accepted_only and state as in histogram, raising where it raises"""
+    if int(bins) < 1:
+        raise ValueError("`bins` must be positive, when an integer")
+    ps, ms = ps2s_names(x.m), ms_names(x.m)
+    j, r = _profile_call(x, window, accepted_only, state, groups=groups, bins=int(bins), range=_hist_range(range, ps), moments=bool(moments))
+    out = []
+    for g in _builtins_range(r["count"].shape[0]):
+        d = OrderedDict()
+        for i, k in enumerate(ps):
+            lo, hi = (r["edges"][g, i, 0], r["edges"][g, i, -1])
+            _hist_raise(r["status"][g, i], lo, hi, bins)
+            e = OrderedDict(edges=r["edges"][g, i].copy())
+            for f in ("n", "n_scored", "v_min", "min_chain", "min_iter"):
+                e[f] = r[f][g, i].copy()
+            e["theta_at_min"] = OrderedDict((q, r["theta_at_min"][g, i, :, b].copy()) for b, q in enumerate(ps))
+            e["v_mean"] = r["v_mean"][g, i].copy()
+            if moments:
+                e["m_mean"] = OrderedDict((q, r["m_mean"][g, i, :, b].copy()) for b, q in enumerate(ms))
+            d[k] = e
+        out.append(d)
+    return out[0] if j is not None else out
+
+
+def profile2d(x, pair, bins=20, range=None, window=None, accepted_only=True, state=False, groups=None):
+    """the objective surface over pair = (a, b), parameter names, on np.histogram2d's cells (a contour plot next to histogram2d), from
+    the device: an OrderedDict(xedges, yedges, n, n_scored, v_min, min_chain, min_iter, v_mean, each [bins][bins]) for a chain, a list of
+    them (one per group) for an algo.  range: numpy's [[xmin, xmax], [ymin, ymax]] or None"""
+    if int(bins) < 1:
+        raise ValueError("`bins` must be positive, when an integer")
+    names = ps2s_names(x.m)
+    a, b = names.index(pair[0]), names.index(pair[1])
+    rg = None
+    if range is not None:
+        ax = _hist_range(list(range), [0, 1])
+        rg = np.tile([0.0, 1.0], (len(names), 1))
+        rg[a], rg[b] = ax[0], ax[1]
+    j, r = _profile_call(x, window, accepted_only, state, groups=groups, bins=1, range=rg, pairs=[(a, b)], bins2=int(bins), moments=False)
+    out = []
+    for g in _builtins_range(r["count"].shape[0]):
+        for i in (a, b):
+            _hist_raise(r["status"][g, i], r["edges2"][g, i, 0], r["edges2"][g, i, -1], bins, one_d=False)
+        d = OrderedDict(xedges=r["edges2"][g, a].copy(), yedges=r["edges2"][g, b].copy())
+        for f in ("n", "n_scored", "v_min", "min_chain", "min_iter", "v_mean"):
+            d[f] = r[f + "2"][g, 0].copy()
+        out.append(d)
+    return out[0] if j is not None else out
+
+
 def trace(algo, groups=None, window=None, stride=1, state=True, moments=False, probs=(0.025, 0.5, 0.975)):
     """the population per iteration, reduced across the chains of each group on the device (include/smmhip.h: smm_get_trace) without
     downloading the history: one OrderedDict per group with iter [nt] (0-based), chains, count / n_accepted / n_exchanged / n_failed /
