@@ -2,12 +2,10 @@
 // (included by smmhip.hip inside its anonymous namespace after smm_stats.hpp; gfx950 device code).  Reads the history records hrec
 // [T][N][HW] (smm_params.hpp: H_*) and nothing else; writes only the scratch and result buffers of the call.
 //
-//   k_diag_gather : one workgroup per chain: a(t0 - 1), the last accepted row before the window, by looking back 256 rows at a time
-//                   (a block-wide max of accepted ? row : -1); then the window 256 rows at a time (lane = iteration): a(t) is the
-//                   max-scan of accepted ? t : -1 across the lanes and the four waves, carried from block to block.  Writes the S = np + 1
-//                   carry-forward columns col [S][Nb][n] (params[a(t)][s], then value[a(t)]; NaN while no row is accepted) and counts
-//                   the window's non-exchanged iterations E and the accepted ones among them A.  The walk itself is diag_state_rows,
-//                   which smm_rank.hpp's gather shares.
+//   k_diag_gather : one workgroup per chain walks the window's state rows (state_walk, smm_window.hpp: lane = iteration, a(t) = the last
+//                   accepted row at or before t) and writes the S = np + 1 carry-forward columns col [S][Nb][n] (params[a(t)][s], then
+//                   value[a(t)]; NaN while no row is accepted); counts the window's non-exchanged iterations E and the accepted ones
+//                   among them A.
 //   k_diag_acov   : one workgroup per (chain, series) column: a non-finite entry ends it (status 3).  Otherwise the two halves' mean and
 //                   variance for R-hat (pw_sum, smm_stats.hpp), the column's mean, then d = x - mean (in LDS when n <= 8192,
 //                   else in place in the scratch column, read from L2).  The lags then go in blocks of 256, lane = lag: each lane sums
@@ -20,60 +18,6 @@
 
 constexpr int DIAG_WG = 256;   // lanes of both kernels; also the lags of one block of k_diag_acov
 
-__device__ __forceinline__ int diag_block_max(int v, int* wred) {   // every thread of the block gets the max of v
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    if (lane == 0) wred[w] = v;
-    __syncthreads();
-    int r = wred[0];
-    for (int q = 1; q < DIAG_WG / 64; ++q) r = max(r, wred[q]);
-    __syncthreads();
-    return r;
-}
-
-// the state rows of chain c over the window [t0, t0 + n), 256 iterations at a time (lane = iteration): emit(r, a) for every window
-// position r with a = a(t0 + r), the last accepted row at or before it (-1: none); counts the window's non-exchanged iterations (noex)
-// and the accepted ones among them (nacc) per thread.  Every thread of the block calls it.
-template <class Emit>
-__device__ __forceinline__ void diag_state_rows(const double* __restrict__ hrec, int N, int HW, int c, int t0, int n, int* wred, int* wtot,
-                                                int& nacc, int& noex, Emit emit) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int carry = -1;   // a(t0 - 1): the look-back goes as far as row 0
-    for (int r1 = t0; r1 > 0 && carry < 0; r1 -= DIAG_WG) {
-        const int r = r1 - DIAG_WG + tid;
-        const int v = (r >= 0 && hrec[((size_t)r * N + c) * HW + H_ACC] != 0.0) ? r : -1;
-        carry = diag_block_max(v, wred);
-    }
-    for (int r0 = 0; r0 < n; r0 += DIAG_WG) {
-        const int r = r0 + tid;
-        const bool valid = r < n;
-        const int t = t0 + r;
-        double acc = 0.0, ex = 0.0;
-        if (valid) {
-            const double* h = hrec + ((size_t)t * N + c) * HW;
-            acc = h[H_ACC];
-            ex = h[H_EXCH];
-        }
-        if (valid && ex == 0.0) { ++noex; if (acc != 0.0) ++nacc; }
-        int a = (valid && acc != 0.0) ? t : -1;
-        for (int o = 1; o < 64; o <<= 1) {   // inclusive max-scan across the wave
-            const int y = __shfl_up(a, o, 64);
-            if (lane >= o) a = max(a, y);
-        }
-        if (lane == 63) wtot[w] = a;
-        __syncthreads();
-        int pre = carry, all = carry;
-        for (int q = 0; q < DIAG_WG / 64; ++q) {
-            if (q < w) pre = max(pre, wtot[q]);
-            all = max(all, wtot[q]);
-        }
-        __syncthreads();
-        a = max(a, pre);
-        carry = all;
-        if (valid) emit(r, a);
-    }
-}
-
 __global__ __launch_bounds__(DIAG_WG) void k_diag_gather(const double* __restrict__ hrec, int N, int HW, int np, int t0, int n, int c0,
                                                          int Nb, double* __restrict__ col, int* __restrict__ o_nacc,
                                                          int* __restrict__ o_noex) {
@@ -84,7 +28,8 @@ __global__ __launch_bounds__(DIAG_WG) void k_diag_gather(const double* __restric
     const int S = np + 1;
     const double qnan = __longlong_as_double(0x7ff8000000000000ll);
     int nacc = 0, noex = 0;
-    diag_state_rows(hrec, N, HW, c, t0, n, wred, wtot, nacc, noex, [&](int r, int a) {
+    state_walk<H_EXCH>(hrec, N, HW, c, t0, n, wred, [&](int r, int a, bool acc, double ex) {
+        if (ex == 0.0) { ++noex; if (acc) ++nacc; }
         double* o = col + (size_t)cl * n + r;
         const size_t cs = (size_t)Nb * n;
         if (a < 0) {

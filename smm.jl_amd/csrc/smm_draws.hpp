@@ -24,7 +24,6 @@
 #pragma once
 
 constexpr int DRAWS_WG = STATS_WG;   // lanes of every kernel; also the output rows of one k_draws_gather workgroup
-static_assert(DRAWS_WG == 256, "k_draws_mask splits a tile's words over four waves");
 
 // grid (ceil(nb / 64)).  Chains [c0, c0 + nb) of the N local ones; mask, pre [nb][W]; o_mc [N] (indexed by local chain)
 __global__ __launch_bounds__(DRAWS_WG) void k_draws_mask(const double* __restrict__ hrec, int N, int HW, int tb, int t1, int c0, int nb, int W,

@@ -4,10 +4,12 @@
 // chains' selected draws, members in ascending local index; the groups' pooled columns lie one after another in the pooled index space
 // (group g from G0[g]), and each group's column is cut into chunks of STATS_LDS_N draws starting at its own first draw.
 //
-//   k_group_gather    : one workgroup per chain streams the chain's records of the window, 256 iterations at a time (lane = iteration;
-//                       rank among the selected ones by a ballot per wave, as k_stats_gather).  kb = 0: the count only.  Packed form:
-//                       parameters [k0, k0 + kb) to col [kb][Mtot] at off[c] + rank.  Chunked form: every parameter, centred by its
-//                       group's mean, to col [np][Nbc][STATS_LDS_N] at (chunk, position in chunk) for the chunks [cb0, cb0 + Nbc) only.
+//   k_group_gather    : one workgroup per chain streams the chain's records of the window, 256 iterations at a time (lane = iteration):
+//                       the rows of select 0 / 1 at their rank among the selected ones (block_rank), the state rows of select 2 at their
+//                       iteration (state_walk; both smm_window.hpp).  kb = 0: the count only.  Packed form: columns [k0, k0 + kb) to col
+//                       [kb][Mtot] at off[c] + rank.  Chunked form: every column, centred by its group's mean, to col [D][Nbc]
+//                       [STATS_LDS_N] at (chunk, position in chunk) for the chunks [cb0, cb0 + Nbc) only.  The columns are the np
+//                       parameters (smm_get_group_stats) or the D = np + nm joint columns (smm_get_moment_stats, smm_moments.hpp).
 //   k_group_chunk_sum : one workgroup per (chunk, parameter) of the packed columns: the chunk's pairwise sum (stats_pw through pw_sum,
 //                       smm_stats.hpp) and whether it holds a NaN.
 //   k_group_mean      : one lane per (group, parameter): the chunk sums added in order, S = S + s_c, then S / m (the chain-stats mean).
@@ -25,29 +27,16 @@ constexpr int GROUP_RB = 4;          // ranks one k_group_hist workgroup counts 
 constexpr int GROUP_BINS = 2048;     // bins of a digit (11 bits; the last digit uses 512)
 constexpr size_t GROUP_HIST_CAP = (size_t)32 << 20;   // bytes of global histograms: the long columns are selected this many at a time
 
-// the selected draws' rank within the window of one chain, a block of 256 iterations at a time: the count of selected iterations before
-// this lane's, and base advanced by the block's total (the ballot of each wave, the wave totals through wtot)
-__device__ __forceinline__ long long group_rank(bool sel, int* __restrict__ wtot, long long& base) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long ms = __ballot(sel);
-    if (lane == 0) wtot[w] = __popcll(ms);
-    __syncthreads();
-    long long off = base;
-    for (int q = 0; q < STATS_WG / 64; ++q) {
-        if (q < w) off += wtot[q];
-        base += wtot[q];
-    }
-    __syncthreads();
-    return off + __popcll(ms & ((1ull << lane) - 1ull));
-}
-
-// counting != 0: count[c] = the chain's selected draws (kb = 0).  Otherwise count[c] is read: a chain outside every group, or with no
-// draw in the chunks [cb0, cb0 + Nbc) of the chunked form (cch0 != NULL), reads nothing.
-__global__ __launch_bounds__(STATS_WG) void k_group_gather(const double* __restrict__ hrec, int N, int HW, int t0, int n, int acc_only,
+// One workgroup per chain.  sel: 0 every row of the window, 1 the accepted rows, 2 row a(t) of every iteration (a row without one reads
+// NaN).  Columns [k0, k0 + kb) of the D pooled ones, which lie behind H_PARAMS in the record (the parameters, then the simulated moments).
+// counting != 0 (sel 0 / 1, kb = 0): count[c] = the chain's selected rows.  Otherwise count[c] is read: a chain outside every group, or
+// with no row in the chunks [cb0, cb0 + Nbc) of the chunked form (cch0 != NULL), reads nothing.  gbad (packed form; NULL: not tested):
+// gbad[g] = 1 for a value that is not finite.
+__global__ __launch_bounds__(STATS_WG) void k_group_gather(const double* __restrict__ hrec, int N, int HW, int t0, int n, int sel,
                                                            const int* __restrict__ gid, const long long* __restrict__ off,
                                                            const int* __restrict__ cch0, int k0, int kb, long long Mtot, int cb0, int Nbc,
-                                                           const double* __restrict__ gmean, int np, double* __restrict__ col,
-                                                           int* __restrict__ count, int counting) {
+                                                           const double* __restrict__ gmean, int D, double* __restrict__ col,
+                                                           int* __restrict__ count, int counting, int* __restrict__ gbad) {
     __shared__ int wtot[STATS_WG / 64];
     const int c = xcd_chain(blockIdx.x, gridDim.x), tid = threadIdx.x;
     const int g = gid[c];
@@ -58,25 +47,39 @@ __global__ __launch_bounds__(STATS_WG) void k_group_gather(const double* __restr
         o = off[c];
         if (chunked && (cch0[c] + o / STATS_LDS_N >= cb0 + Nbc || cch0[c] + (o + count[c] - 1) / STATS_LDS_N < cb0)) return;
     }
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    // pooled position pos takes the columns of record h (NULL: no state row yet)
+    auto put = [&](long long pos, const double* __restrict__ h) {
+        if (!chunked) {
+            bool bad = false;
+            for (int kk = 0; kk < kb; ++kk) {
+                const double v = h ? h[H_PARAMS + k0 + kk] : qnan;
+                if (gbad) bad |= !isfinite(v);
+                col[(size_t)kk * Mtot + pos] = v;
+            }
+            if (bad) gbad[g] = 1;
+        } else {
+            const long long ch = cch0[c] + pos / STATS_LDS_N - cb0;
+            if (ch < 0 || ch >= Nbc) return;
+            const size_t at = (size_t)ch * STATS_LDS_N + (size_t)(pos % STATS_LDS_N);
+            for (int kk = 0; kk < kb; ++kk) {
+                const double v = h ? h[H_PARAMS + k0 + kk] : qnan;
+                col[(size_t)kk * Nbc * STATS_LDS_N + at] = v - gmean[(size_t)g * D + k0 + kk];
+            }
+        }
+    };
+    if (sel == 2) {
+        state_walk(hrec, N, HW, c, t0, n, wtot, [&](int r, int a, bool) { put(o + r, a < 0 ? nullptr : hrec + ((size_t)a * N + c) * HW); });
+        return;
+    }
     long long base = 0;
     for (int r0 = 0; r0 < n; r0 += STATS_WG) {
         const int r = r0 + tid;
         const bool valid = r < n;
         const double* h = hrec + ((size_t)(t0 + (valid ? r : 0)) * N + c) * HW;
-        const bool sel = valid && (!acc_only || h[H_ACC] != 0.0);
-        const long long pos = o + group_rank(sel, wtot, base);
-        if (!sel || kb == 0) continue;
-        if (!chunked) {
-            for (int kk = 0; kk < kb; ++kk) col[(size_t)kk * Mtot + pos] = h[H_PARAMS + k0 + kk];
-        } else {
-            const long long ch = cch0[c] + pos / STATS_LDS_N - cb0;
-            if (ch < 0 || ch >= Nbc) continue;
-            const size_t at = (size_t)ch * STATS_LDS_N + (size_t)(pos % STATS_LDS_N);
-            for (int kk = 0; kk < kb; ++kk) {
-                const double v = h[H_PARAMS + k0 + kk];
-                col[(size_t)kk * Nbc * STATS_LDS_N + at] = v - gmean[(size_t)g * np + k0 + kk];
-            }
-        }
+        const bool take = valid && (sel == 0 || h[H_ACC] != 0.0);
+        const long long pos = o + block_rank(take, wtot, base);
+        if (take && kb > 0) put(pos, h);
     }
     if (counting && tid == 0) count[c] = (int)base;
 }

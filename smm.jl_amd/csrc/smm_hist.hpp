@@ -5,7 +5,7 @@
 //
 // Every kernel takes one member chain per workgroup (mem[m0 + xcd_chain(blockIdx.x)]: the members of a batch of groups, group by group)
 // and walks the chain's window HIST_WG rows at a time through hist_rows: lane = iteration picks the row it selects into LDS (select 2:
-// a(t), the max-scan of k_diag_gather carried from block to block); then the workgroup's threads read the block's rows as (row, column)
+// a(t) by state_before and state_scan, smm_window.hpp); then the workgroup's threads read the block's rows as (row, column)
 // pairs, the columns consecutive across lanes (a row's parameters are contiguous).
 //
 //   k_hist_range  : the chain's selected rows and, per parameter (64 per workgroup), the min, the max and whether a draw is not finite.
@@ -30,13 +30,8 @@ __device__ __forceinline__ bool hist_finite(double x) { return fabs(x) <= 1.7976
 template <class Body>
 __device__ int hist_rows(const double* __restrict__ hrec, int N, int HW, int c, int t0, int n, int sel, int* __restrict__ rows,
                          int* __restrict__ wred, Body body) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int carry = -1;   // a(t0 - 1) (select 2): the look-back goes as far as row 0
-    if (sel == 2)
-        for (int r1 = t0; r1 > 0 && carry < 0; r1 -= HIST_WG) {
-            const int r = r1 - HIST_WG + tid;
-            carry = diag_block_max((r >= 0 && hrec[((size_t)r * N + c) * HW + H_ACC] != 0.0) ? r : -1, wred);
-        }
+    const int tid = threadIdx.x;
+    int carry = sel == 2 ? state_before(hrec, N, HW, c, t0, wred) : -1;
     int cnt = 0;
     for (int r0 = 0; r0 < n; r0 += HIST_WG) {
         const int r = r0 + tid, t = t0 + r;
@@ -44,22 +39,8 @@ __device__ int hist_rows(const double* __restrict__ hrec, int N, int HW, int c, 
         const bool acc = valid && sel != 0 && hrec[((size_t)t * N + c) * HW + H_ACC] != 0.0;
         int src;
         if (sel == 2) {
-            int a = acc ? t : -1;
-            for (int o = 1; o < 64; o <<= 1) {   // inclusive max-scan across the wave
-                const int y = __shfl_up(a, o, 64);
-                if (lane >= o) a = max(a, y);
-            }
-            if (lane == 63) wred[w] = a;
-            __syncthreads();
-            int pre = carry, all = carry;
-            for (int q = 0; q < HIST_WG / 64; ++q) {
-                if (q < w) pre = max(pre, wred[q]);
-                all = max(all, wred[q]);
-            }
-            __syncthreads();
-            a = max(a, pre);
-            carry = all;
-            src = valid ? (a >= 0 ? a : -1) : -2;
+            const int a = state_scan(acc ? t : -1, carry, wred);
+            src = valid ? a : -2;
         } else {
             src = valid && (sel == 0 || acc) ? t : -2;
         }
@@ -70,18 +51,6 @@ __device__ int hist_rows(const double* __restrict__ hrec, int N, int HW, int c, 
         __syncthreads();
     }
     return cnt;
-}
-
-__device__ __forceinline__ int hist_block_sum(int v, int* wred) {   // every thread gets the block's sum of v
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if (lane == 0) wred[w] = v;
-    __syncthreads();
-    int r = 0;
-    for (int q = 0; q < HIST_WG / 64; ++q) r += wred[q];
-    __syncthreads();
-    return r;
 }
 
 // numpy's uniform-bins index of x (include/smmhip.h, 1-D), -1 when x is dropped; e: the bins + 1 edges
@@ -135,7 +104,7 @@ __global__ __launch_bounds__(HIST_WG) void k_hist_range(const double* __restrict
             if (x > mx) mx = x;
         }
     });
-    const int total = hist_block_sum(cnt, wred);
+    const int total = block_sum(cnt, wred);
     if (blockIdx.y == 0 && tid == 0) o_cnt[c] = total;
     if (!cmin) return;
     smn[tid] = mn; smx[tid] = mx; sbad[tid] = bad;

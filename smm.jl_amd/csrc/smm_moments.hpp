@@ -2,15 +2,10 @@
 // (included by smmhip.hip inside its anonymous namespace after smm_group.hpp; gfx950 device code).  Reads the history records hrec
 // [T][N][HW] (smm_params.hpp: H_*) and nothing else; writes only the scratch and result buffers of the call.  The D = np + nm joint
 // columns of a group (the parameters, then the simulated moments stored behind them in the record) are pooled, cut into chunks and
-// summed exactly as smm_group.hpp pools the parameters, and its kernels and k_cov_pairs (smm_cov.hpp) run on them with np = D: the
-// cov_pp block is smm_get_group_stats' covariance bit for bit.
+// summed exactly as smm_group.hpp pools the parameters: its kernels, k_group_gather (the three selections, the not-finite flag gbad)
+// among them, and k_cov_pairs (smm_cov.hpp) run on them with D columns, so the cov_pp block is smm_get_group_stats' covariance bit for
+// bit.  What is the moments' own:
 //
-//   k_moment_gather  : k_group_gather for the joint columns and the three selections.  One workgroup per chain streams the chain's
-//                      records of the window, 256 iterations at a time (lane = iteration): select 0 every row, select 1 the accepted
-//                      rows (rank by group_rank's ballot), select 2 row a(t) of diag_state_rows (smm_diag.hpp: the one look-back walk),
-//                      a row without one NaN.  A record's parameters and moments are contiguous: a lane reads its record once for the
-//                      columns [k0, k0 + kb).  Packed form: col [kb][Mtot], and gbad[g] = 1 for a non-finite value.  Chunked form: every
-//                      column centred by its group's mean, col [D][Nbc][STATS_LDS_N], for the chunks [cb0, cb0 + Nbc) only.
 //   k_moment_cov_acc : one lane per (group, pair a >= b): the batch's chunk sums of k_cov_pairs added in chunk order onto the group's
 //                      running sum, S = S + s_c; across the batches of chunks that is the contract's sum from 0.0.
 //   k_moment_solve   : one workgroup of one wave per group, lane = row.  Splits the joint results into the call's blocks (means, medians,
@@ -22,61 +17,7 @@
 #pragma once
 
 constexpr int MOMENT_WG = 64;   // lanes of k_moment_solve: a row of the largest matrix each
-static_assert(STATS_WG == DIAG_WG, "k_moment_gather runs group_rank and diag_state_rows with the same workgroup");
 static_assert(MAX_DIM <= MOMENT_WG, "k_moment_solve: lane = row");
-
-// count[c]: the chain's selected rows (n for select 0 and 2); a chain outside every group, or with no row in the chunks [cb0, cb0 + Nbc)
-// of the chunked form (cch0 != NULL), reads nothing
-__global__ __launch_bounds__(STATS_WG) void k_moment_gather(const double* __restrict__ hrec, int N, int HW, int t0, int n, int sel,
-                                                            const int* __restrict__ gid, const long long* __restrict__ off,
-                                                            const int* __restrict__ cch0, int k0, int kb, long long Mtot, int cb0, int Nbc,
-                                                            const double* __restrict__ gmean, int D, double* __restrict__ col,
-                                                            const int* __restrict__ count, int* __restrict__ gbad) {
-    __shared__ int wtot[STATS_WG / 64];
-    __shared__ int wred[STATS_WG / 64];
-    const int c = xcd_chain(blockIdx.x, gridDim.x), tid = threadIdx.x;
-    const int g = gid[c];
-    const bool chunked = cch0 != nullptr;
-    if (g < 0 || count[c] == 0) return;
-    const long long o = off[c];
-    if (chunked && (cch0[c] + o / STATS_LDS_N >= cb0 + Nbc || cch0[c] + (o + count[c] - 1) / STATS_LDS_N < cb0)) return;
-    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-    // pooled position pos takes the columns of record h (NULL: no state row yet)
-    auto put = [&](long long pos, const double* __restrict__ h) {
-        if (!chunked) {
-            bool bad = false;
-            for (int kk = 0; kk < kb; ++kk) {
-                const double v = h ? h[H_PARAMS + k0 + kk] : qnan;
-                bad |= !isfinite(v);
-                col[(size_t)kk * Mtot + pos] = v;
-            }
-            if (bad) gbad[g] = 1;
-        } else {
-            const long long ch = cch0[c] + pos / STATS_LDS_N - cb0;
-            if (ch < 0 || ch >= Nbc) return;
-            const size_t at = (size_t)ch * STATS_LDS_N + (size_t)(pos % STATS_LDS_N);
-            for (int kk = 0; kk < kb; ++kk) {
-                const double v = h ? h[H_PARAMS + k0 + kk] : qnan;
-                col[(size_t)kk * Nbc * STATS_LDS_N + at] = v - gmean[(size_t)g * D + k0 + kk];
-            }
-        }
-    };
-    if (sel == 2) {
-        int nacc = 0, noex = 0;
-        diag_state_rows(hrec, N, HW, c, t0, n, wred, wtot, nacc, noex,
-                        [&](int r, int a) { put(o + r, a < 0 ? nullptr : hrec + ((size_t)a * N + c) * HW); });
-        return;
-    }
-    long long base = 0;
-    for (int r0 = 0; r0 < n; r0 += STATS_WG) {
-        const int r = r0 + tid;
-        const bool valid = r < n;
-        const double* h = hrec + ((size_t)(t0 + (valid ? r : 0)) * N + c) * HW;
-        const bool take = valid && (sel == 0 || h[H_ACC] != 0.0);
-        const long long pos = o + group_rank(take, wtot, base);
-        if (take) put(pos, h);
-    }
-}
 
 // csum2 [D][D][nb]: k_cov_pairs' raw sums of the chunks [cb0, cb0 + nb); acc [G][D][D], entry (a, b), a >= b
 __global__ void k_moment_cov_acc(const double* __restrict__ csum2, int nb, int cb0, const int* __restrict__ gch0, int G, int D,

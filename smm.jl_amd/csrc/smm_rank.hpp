@@ -7,7 +7,7 @@
 // that chain qb of series sl lies at [sl][qb h .. qb h + h) of every value array [sb][Mtot], Mtot = mtot h, and group g's pooled column
 // (M = 2 k h values) starts at (2 gm0[g] - q0) h.  Cells are numbered g S + s over the whole call.
 //
-//   k_rank_gather     : one workgroup per member chain: the state series (diag_state_rows, smm_diag.hpp) into split-chain layout X.
+//   k_rank_gather     : one workgroup per member chain: the state series (state_walk, smm_window.hpp) into split-chain layout X.
 //   k_rank_keys       : the order keys (stats_key, -0 taken as +0) of x, or of |x - med| (fold), with the pooled index; a non-finite x
 //                       raises the cell's flag.
 //   k_rank_sort_small : one workgroup per column of <= RANK_SMALL values: the 8 passes of an LSD radix sort, 8 bits each, between the two
@@ -54,10 +54,8 @@ __device__ __forceinline__ long long rank_col_off(const RankBatch& b, int g, int
 __global__ __launch_bounds__(RANK_WG) void k_rank_gather(const double* __restrict__ hrec, int N, int HW, int np, int t0, RankBatch b,
                                                          double* __restrict__ X) {
     __shared__ int wred[RANK_WG / 64];
-    __shared__ int wtot[RANK_WG / 64];
     const int bi = blockIdx.x, c = b.mem[b.gm0[b.g0] + bi];
-    int nacc = 0, noex = 0;
-    diag_state_rows(hrec, N, HW, c, t0, b.n, wred, wtot, nacc, noex, [&](int r, int a) {
+    state_walk(hrec, N, HW, c, t0, b.n, wred, [&](int r, int a, bool) {
         long long pos;
         if (r < b.h) pos = (long long)(2 * bi) * b.h + r;
         else if (r >= b.n - b.h) pos = (long long)(2 * bi + 1) * b.h + (r - (b.n - b.h));

@@ -1,16 +1,23 @@
 // the host side of the history reducers — part of libsmmhip (included once by smmhip.hip, behind its host helpers; hiprtc never sees it).
 // The family: smm_get_chain_stats, smm_get_chain_cov, smm_get_proposal / _set_ / _adapt_, smm_get_chain_diag, smm_get_group_stats,
 // smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws, smm_get_moment_stats, smm_get_profile (kernels: smm_stats.hpp,
-// smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_moments.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp, smm_draws.hpp, smm_profile.hpp).
+// smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_moments.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp, smm_draws.hpp, smm_profile.hpp;
+// the walk over a chain's window that their gathers share: smm_window.hpp).
 // What they share is stated here once: the frame of a call (reducer_call), the checks of the arguments they have in common (check_groups,
 // check_probs, check_select), the prelude and the window behind them (settled_window: reader_prelude and check_window of smmhip.hip), the
 // members of the groups (Groups), one result buffer per context (reducer_result, laid out by Carve / Slice, copied by up / down), one
-// scratch per context for the compacted columns (reducer_scratch, chain_batches) and the cap on the scratch and on a batch of results
-// (reducer_batch_cap: REDUCER_BATCH_CAP, or what the test seam SMMHIP_STATS_SCRATCH gives, so that small cases reach the batched paths).
+// scratch per context for the compacted columns (reducer_scratch, chain_batches), the cap on the scratch and on a batch of results
+// (reducer_batch_cap: REDUCER_BATCH_CAP, or what the test seam SMMHIP_STATS_SCRATCH gives, so that small cases reach the batched paths),
+// and the pooled columns of groups: the members' counts, where the pooled rows and their chunks lie, the plan of the order statistics,
+// both on the device and the order statistics' launches (pool_counts, PoolPlan, OrderPlan, PoolDev, pool_order).
 // A call's own batch plan, result layout, launches, empty-window branch and host-side finish stay in the call.
 #pragma once
 
 namespace {
+
+static_assert(STATS_WG == WINDOW_WG && DIAG_WG == WINDOW_WG && HIST_WG == WINDOW_WG && TRACE_WG == WINDOW_WG && DRAWS_WG == WINDOW_WG &&
+                  PROF_WG == WINDOW_WG && RANK_WG == WINDOW_WG && WINDOW_WG == 256,
+              "smm_window.hpp walks a window 256 rows at a time, four waves' totals through LDS; k_draws_mask splits a tile over four waves");
 
 // the frame of an entry point: body(c) returns SMM_OK or what fail() returned
 template <class Body>
@@ -149,6 +156,146 @@ void launch_checked(Ctx* c, Kern kern, dim3 grid, dim3 block, size_t smem, const
 
 // the keys a workgroup sorts in LDS for a column of n draws: the power of two at or above n (and 2), at most STATS_LDS_N
 int sort_lds_n(int n) { return std::min(STATS_LDS_N, 1 << (int)ceil(log2((double)std::max(n, 2)))); }
+
+// --- the pooled columns of groups (smm_group.hpp; smm_get_group_stats over the parameters, smm_get_moment_stats over the joint columns) ---
+
+// the members' selected rows of the window [t0, t0 + n): k_group_gather's counting form for select 1, n otherwise.  dci [2][N] on the
+// device gets the chains' groups, then these counts.
+std::vector<int> pool_counts(Ctx* c, const Groups& grp, int t0, int n, int sel, int* dci) {
+    const KParams& P = c->P;
+    const size_t N = P.N;
+    std::vector<int> cnt(N, n);
+    HIPCHK(hipMemcpyAsync(dci, grp.gid.data(), N * 4, hipMemcpyHostToDevice, c->stream));
+    if (sel == 1) {
+        launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, 1, (const int*)dci,
+                       (const long long*)nullptr, (const int*)nullptr, 0, 0, 0ll, 0, 0, (const double*)nullptr, 0, (double*)nullptr, dci + N, 1,
+                       (int*)nullptr);
+        HIPCHK(hipMemcpyAsync(cnt.data(), dci + N, N * 4, hipMemcpyDeviceToHost, c->stream));
+    } else
+        HIPCHK(hipMemcpyAsync(dci + N, cnt.data(), N * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return cnt;
+}
+
+// where the pooled rows lie: group g's column is rows [G0[g], G0[g] + gm[g]) of the pooled index space, its members one after another
+// (member i from off[i], roff[i] within the group), cut into chunks of STATS_LDS_N rows from its own first row (chunk ch: clen[ch] rows
+// from cst[ch]; group g's are [gch0[g], gch0[g + 1]), cch0[i] the first of member i's group)
+struct PoolPlan {
+    std::vector<long long> gm, G0, off, roff, cst;
+    std::vector<int> clen, gch0, cch0;
+    long long Mtot = 0;
+    int NC = 0;
+};
+PoolPlan pool_plan(const Groups& grp, const std::vector<int>& cnt) {
+    const size_t N = cnt.size(), G = grp.n_chains.size();
+    const std::vector<int>& gid = grp.gid;
+    PoolPlan p;
+    p.gm.assign(G, 0); p.G0.assign(G + 1, 0); p.off.assign(N, 0); p.roff.assign(N, 0);
+    p.gch0.assign(G + 1, 0); p.cch0.assign(N, 0);
+    for (size_t i = 0; i < N; ++i)
+        if (gid[i] >= 0) { p.roff[i] = p.gm[gid[i]]; p.gm[gid[i]] += cnt[i]; }
+    for (size_t g = 0; g < G; ++g) {
+        p.G0[g + 1] = p.G0[g] + p.gm[g];
+        for (long long q = 0; q < p.gm[g]; q += STATS_LDS_N) {
+            p.cst.push_back(p.G0[g] + q);
+            p.clen.push_back((int)std::min<long long>(STATS_LDS_N, p.gm[g] - q));
+        }
+        p.gch0[g + 1] = (int)p.cst.size();
+    }
+    for (size_t i = 0; i < N; ++i)
+        if (gid[i] >= 0) { p.off[i] = p.G0[gid[i]] + p.roff[i]; p.cch0[i] = p.gch0[gid[i]]; }
+    p.Mtot = p.G0[G];
+    p.NC = (int)p.cst.size();
+    return p;
+}
+
+// the order statistics of the pooled columns: short columns (sgrp) sorted in LDS, the others (wgrp, the longest wmax) selected grid-wide
+// at R ranks per column: rk [wgrp][R], the median's and stats_quantile's indexes of the nq probs (-1: unused)
+struct OrderPlan {
+    const double* probs; size_t nq;   // (the caller's, on the host)
+    std::vector<int> sgrp, wgrp;
+    long long wmax = 0;
+    int R = 0;
+    std::vector<long long> rk;
+};
+OrderPlan order_plan(const Ctx* c, const PoolPlan& pp, bool med, const double* probs, size_t nq) {
+    OrderPlan o{probs, nq};
+    for (size_t g = 0; g < pp.gm.size(); ++g)
+        if (pp.gm[g] < c->H.group_wide_min) o.sgrp.push_back((int)g);
+        else { o.wgrp.push_back((int)g); o.wmax = std::max(o.wmax, pp.gm[g]); }
+    o.R = (med ? 2 : 0) + 2 * (int)nq;
+    o.rk.assign(o.wgrp.size() * o.R, -1);
+    for (size_t wi = 0; wi < o.wgrp.size() && o.R; ++wi) {
+        const long long m = pp.gm[o.wgrp[wi]];
+        long long* r = o.rk.data() + wi * o.R;
+        if (med) { r[0] = (m & 1) ? m / 2 : m / 2 - 1; r[1] = (m & 1) ? -1 : m / 2; r += 2; }
+        for (size_t p = 0; p < nq; ++p, r += 2) {
+            const double h = (double)(m - 1) * probs[p];
+            if (h >= (double)(m - 1)) r[0] = m - 1;
+            else { r[0] = (long long)floor(h); r[1] = r[0] + 1; }
+        }
+    }
+    return o;
+}
+
+// both plans on the device, and the grid-wide select's work space for nwc long columns at a time (their histograms WB columns at a
+// time): carved behind the call's own 8-byte slices and ahead of its 4-byte ones, uploaded once the result buffer is there
+struct PoolDev {
+    Slice<double> probs;
+    Slice<long long> off, G0, gm, cst, rk, rem;
+    Slice<unsigned long long> pre, ghist;
+    Slice<int> cch0, gch0, clen, sgrp, wgrp;
+    int WB;
+    PoolDev(Carve& Rv, const PoolPlan& pp, const OrderPlan& op, size_t nwc) {
+        const size_t N = pp.off.size(), G = pp.gm.size(), R = op.R;
+        WB = R ? (int)std::min(nwc, std::max((size_t)1, GROUP_HIST_CAP / (R * GROUP_BINS * 8))) : 0;
+        probs = Rv.take<double>(op.nq);
+        off = Rv.take<long long>(2 * N); G0 = Rv.take<long long>(G + 1); gm = Rv.take<long long>(G); cst = Rv.take<long long>(pp.NC);
+        rk = Rv.take<long long>(op.rk.size()); rem = Rv.take<long long>(nwc * R);
+        pre = Rv.take<unsigned long long>(nwc * R); ghist = Rv.take<unsigned long long>((size_t)WB * R * GROUP_BINS);
+        cch0 = Rv.take<int>(N); gch0 = Rv.take<int>(G + 1); clen = Rv.take<int>(pp.NC);
+        sgrp = Rv.take<int>(op.sgrp.size()); wgrp = Rv.take<int>(op.wgrp.size());
+    }
+    void upload(Ctx* c, void* d, const PoolPlan& pp, const OrderPlan& op) const {
+        std::vector<long long> offs(pp.off);   // off [N], then roff [N]
+        offs.insert(offs.end(), pp.roff.begin(), pp.roff.end());
+        up(c, d, off, offs); up(c, d, G0, pp.G0); up(c, d, gm, pp.gm); up(c, d, cst, pp.cst); up(c, d, rk, op.rk);
+        up(c, d, cch0, pp.cch0); up(c, d, gch0, pp.gch0); up(c, d, clen, pp.clen); up(c, d, sgrp, op.sgrp); up(c, d, wgrp, op.wgrp);
+        up(c, d, probs, op.probs, op.nq);
+    }
+};
+
+// median (omed NULL: none) and quantiles of the km packed columns col [km][Mtot], the result columns [ks, ks + km) of D: the short ones
+// by k_group_small; the long ones by the six digits of the radix select, WB columns' histograms at a time, then k_group_finish
+void pool_order(Ctx* c, void* d, const PoolDev& pd, const PoolPlan& pp, const OrderPlan& op, const double* col, int km, int ks, int D,
+                const int* gnan, double* omed, double* quant) {
+    const int G = (int)pp.gm.size(), R = op.R, nq = (int)op.nq;
+    const long long *dG0 = pd.G0.in(d), *dgm = pd.gm.in(d);
+    const double* dprobs = pd.probs.in(d);
+    if (!op.sgrp.empty())
+        launch_checked(c, k_group_small, dim3((unsigned)op.sgrp.size(), km), dim3(STATS_WG), (size_t)STATS_LDS_N * 8, col, pp.Mtot,
+                       (const int*)pd.sgrp.in(d), dG0, dgm, G, ks, D, gnan, dprobs, nq, omed, quant);
+    if (op.wgrp.empty()) return;
+    const int nw = (int)op.wgrp.size() * km, WB = pd.WB;
+    const int B = (int)std::min<long long>(1024, std::max<long long>(1, (op.wmax + STATS_WG * 16 - 1) / (STATS_WG * 16)));
+    std::vector<long long> remh((size_t)nw * R);
+    for (int w = 0; w < nw; ++w)
+        for (int r = 0; r < R; ++r) remh[(size_t)w * R + r] = op.rk[(size_t)(w / km) * R + r];
+    up(c, d, pd.rem, remh);
+    HIPCHK(hipMemsetAsync(pd.pre.in(d), 0, (size_t)nw * R * 8, c->stream));
+    HIPCHK(hipMemsetAsync(pd.ghist.in(d), 0, (size_t)WB * R * GROUP_BINS * 8, c->stream));   // (k_group_pick zeroes it again)
+    for (int w0 = 0; w0 < nw; w0 += WB) {
+        const int wn = std::min(WB, nw - w0);
+        for (int dg = 0; dg < 6; ++dg) {
+            launch_checked(c, k_group_hist, dim3(wn, B, (R + GROUP_RB - 1) / GROUP_RB), dim3(STATS_WG), 0, col, pp.Mtot,
+                           (const int*)pd.wgrp.in(d), dG0, dgm, km, R, dg, w0, (const long long*)pd.rem.in(d),
+                           (const unsigned long long*)pd.pre.in(d), pd.ghist.in(d));
+            launch_checked(c, k_group_pick, dim3(wn * R), dim3(STATS_WG), 0, dg, w0 * R, pd.ghist.in(d), pd.rem.in(d), pd.pre.in(d));
+        }
+    }
+    launch_checked(c, k_group_finish, dim3((nw + 63) / 64), dim3(64), 0, nw, (const int*)pd.wgrp.in(d), dgm, G, ks, km, D, R,
+                   (const long long*)pd.rk.in(d), (const unsigned long long*)pd.pre.in(d), gnan, dprobs, nq, omed, quant);
+}
 
 // the reducers' dynamic LDS (smm_ctx_create): a chunk of draws (k_stats_column, k_cov_center, k_diag_acov, k_group_*, k_trace_column),
 // the partner ids of a pass (k_stats_mode), the counters and edges of a batch of parameters or pairs (k_hist_count, k_hist_pairs), a
@@ -471,128 +618,57 @@ int smm_get_group_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only
         const size_t N = P.N, np = P.np, G = n_groups, nq = out->quantile ? n_probs : 0;
         const int n = t1 - t0;
         const bool med = out->median != nullptr, ord = med || nq > 0, cov = out->cov != nullptr, cols = out->mean || ord || cov;
-        // the members' counts (k_group_gather's counting form), then the plan on the host: the pooled offsets and the chunks
         const Groups grp = group_members(group, G, N);
-        const std::vector<int>& gid = grp.gid;
-        std::vector<int> cnt(N);
         DevBuf<int> dci(2 * N);
-        HIPCHK(hipMemcpyAsync(dci.p, gid.data(), N * 4, hipMemcpyHostToDevice, c->stream));
-        launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)(accepted_only != 0),
-                       (const int*)dci.p, (const long long*)nullptr, (const int*)nullptr, 0, 0, 0ll, 0, 0, (const double*)nullptr, (int)np,
-                       (double*)nullptr, dci.p + N, 1);
-        HIPCHK(hipMemcpyAsync(cnt.data(), dci.p + N, N * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        std::vector<long long> gm(G, 0), G0(G + 1, 0), off(N, 0), roff(N, 0);
-        std::vector<int> gch0(G + 1, 0), cch0(N, 0);
-        for (size_t i = 0; i < N; ++i)
-            if (gid[i] >= 0) { roff[i] = gm[gid[i]]; gm[gid[i]] += cnt[i]; }
-        std::vector<long long> cst;
-        std::vector<int> clen;
-        for (size_t g = 0; g < G; ++g) {
-            G0[g + 1] = G0[g] + gm[g];
-            for (long long q = 0; q < gm[g]; q += STATS_LDS_N) { cst.push_back(G0[g] + q); clen.push_back((int)std::min<long long>(STATS_LDS_N, gm[g] - q)); }
-            gch0[g + 1] = (int)cst.size();
-        }
-        for (size_t i = 0; i < N; ++i)
-            if (gid[i] >= 0) { off[i] = G0[gid[i]] + roff[i]; cch0[i] = gch0[gid[i]]; }
-        const long long Mtot = G0[G];
-        const int NC = (int)cst.size();
-        // the order statistics: short columns sorted in LDS, the others selected grid-wide at ranks R per column (rk: -1 = unused)
-        std::vector<int> sgrp, wgrp;
-        long long wmax = 0;
-        for (size_t g = 0; g < G; ++g)
-            if (gm[g] < c->H.group_wide_min) sgrp.push_back((int)g);
-            else { wgrp.push_back((int)g); wmax = std::max(wmax, gm[g]); }
-        const int R = ord ? (med ? 2 : 0) + 2 * (int)nq : 0;
-        std::vector<long long> rk(wgrp.size() * R, -1);
-        for (size_t wi = 0; wi < wgrp.size() && R; ++wi) {   // stats_quantile's and the median's indexes
-            const long long m = gm[wgrp[wi]];
-            long long* r = rk.data() + wi * R;
-            if (med) { r[0] = (m & 1) ? m / 2 : m / 2 - 1; r[1] = (m & 1) ? -1 : m / 2; r += 2; }
-            for (size_t p = 0; p < nq; ++p, r += 2) {
-                const double h = (double)(m - 1) * probs[p];
-                if (h >= (double)(m - 1)) r[0] = m - 1;
-                else { r[0] = (long long)floor(h); r[1] = r[0] + 1; }
-            }
-        }
+        const PoolPlan pp = pool_plan(grp, pool_counts(c, grp, t0, n, accepted_only != 0, dci.p));
+        const OrderPlan op = order_plan(c, pp, med, probs, nq);
+        const long long Mtot = pp.Mtot;
+        const int NC = pp.NC;
         if (Mtot > 0 && cols) reducer_scratch(c, std::max(N * (size_t)P.T * 8, cov ? np * STATS_LDS_N * 8 : 0));
         const size_t kb = Mtot > 0 && cols ? std::min(np, c->st_scr_bytes / ((size_t)Mtot * 8)) : 0;
-        const size_t nwc = wgrp.size() * kb;   // long columns of a parameter batch, selected WB at a time
-        const int WB = R ? (int)std::min(nwc, std::max((size_t)1, GROUP_HIST_CAP / ((size_t)R * GROUP_BINS * 8))) : 0;
         Carve Rv;   // 8-byte slices first
         const auto mean = Rv.take<double>(G * np), median = Rv.take<double>(G * np), quant = Rv.take<double>(nq * G * np),
-                   covo = Rv.take<double>(cov ? G * np * np : 0), dprobs = Rv.take<double>(nq), csum = Rv.take<double>(kb * NC),
+                   covo = Rv.take<double>(cov ? G * np * np : 0), csum = Rv.take<double>(kb * NC),
                    csum2 = Rv.take<double>(cov ? np * np * NC : 0);
-        const auto doff = Rv.take<long long>(2 * N), dG0 = Rv.take<long long>(G + 1), dgm = Rv.take<long long>(G),
-                   dcst = Rv.take<long long>(NC), drk = Rv.take<long long>(rk.size()), rem = Rv.take<long long>(nwc * R);
-        const auto pre = Rv.take<unsigned long long>(nwc * R), ghist = Rv.take<unsigned long long>((size_t)WB * R * GROUP_BINS);
-        const auto dcch0 = Rv.take<int>(N), dgch0 = Rv.take<int>(G + 1), dclen = Rv.take<int>(NC), cnan = Rv.take<int>(kb * NC),
-                   gnan = Rv.take<int>(G * np), dsg = Rv.take<int>(sgrp.size()), dwg = Rv.take<int>(wgrp.size());
+        const PoolDev pd(Rv, pp, op, op.wgrp.size() * kb);   // (the long columns of a parameter batch)
+        const auto cnan = Rv.take<int>(kb * NC), gnan = Rv.take<int>(G * np);
         void* d = reducer_result(c, Rv.bytes);
-        std::vector<long long> offs(off);
-        offs.insert(offs.end(), roff.begin(), roff.end());
-        up(c, d, doff, offs); up(c, d, dG0, G0); up(c, d, dgm, gm); up(c, d, dcst, cst); up(c, d, drk, rk);
-        up(c, d, dcch0, cch0); up(c, d, dgch0, gch0); up(c, d, dclen, clen); up(c, d, dsg, sgrp); up(c, d, dwg, wgrp);
-        up(c, d, dprobs, probs, nq);
-        const int* dgid = dci.p;
-        const int* dcnt = dci.p + N;
-        std::vector<long long> remh(nwc * R);
+        pd.upload(c, d, pp, op);
+        const int sel = accepted_only != 0;
+        const int *dgid = dci.p, *dgch0 = pd.gch0.in(d), *dclen = pd.clen.in(d);
+        int* dcnt = dci.p + N;
+        const long long* dgm = pd.gm.in(d);
         if (kb > 0) {
             double* col = (double*)c->st_scr;
-            const int B = (int)std::min<long long>(1024, std::max<long long>(1, (wmax + STATS_WG * 16 - 1) / (STATS_WG * 16)));
             for (size_t k0 = 0; k0 < np; k0 += kb) {   // batches of parameters: the packed columns [kbb][Mtot]
                 const int kbb = (int)std::min(kb, np - k0);
-                launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n,
-                               (int)(accepted_only != 0), dgid, (const long long*)doff.in(d), (const int*)nullptr, (int)k0, kbb, Mtot, 0, 0,
-                               (const double*)nullptr, (int)np, col, (int*)dcnt, 0);
+                launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, sel, dgid,
+                               (const long long*)pd.off.in(d), (const int*)nullptr, (int)k0, kbb, Mtot, 0, 0, (const double*)nullptr, (int)np,
+                               col, dcnt, 0, (int*)nullptr);
                 if (NC > 0)
                     launch_checked(c, k_group_chunk_sum, dim3(NC, kbb), dim3(STATS_WG), (size_t)STATS_LDS_N * 8, (const double*)col, Mtot,
-                                   (const long long*)dcst.in(d), (const int*)dclen.in(d), NC, csum.in(d), cnan.in(d));
+                                   (const long long*)pd.cst.in(d), dclen, NC, csum.in(d), cnan.in(d));
                 launch_checked(c, k_group_mean, dim3((unsigned)((G * kbb + 255) / 256)), dim3(256), 0, (const double*)csum.in(d),
-                               (const int*)cnan.in(d), NC, (const int*)dgch0.in(d), (const long long*)dgm.in(d), (int)G, (int)k0, kbb,
-                               (int)np, mean.in(d), gnan.in(d));
-                if (!ord) continue;
-                double* omed = med ? median.in(d) : nullptr;
-                if (!sgrp.empty())
-                    launch_checked(c, k_group_small, dim3((unsigned)sgrp.size(), kbb), dim3(STATS_WG), (size_t)STATS_LDS_N * 8,
-                                   (const double*)col, Mtot, (const int*)dsg.in(d), (const long long*)dG0.in(d), (const long long*)dgm.in(d),
-                                   (int)G, (int)k0, (int)np, (const int*)gnan.in(d), (const double*)dprobs.in(d), (int)nq, omed, quant.in(d));
-                if (wgrp.empty()) continue;
-                const int nw = (int)wgrp.size() * kbb;
-                for (int w = 0; w < nw; ++w)
-                    for (int r = 0; r < R; ++r) remh[(size_t)w * R + r] = rk[(size_t)(w / kbb) * R + r];
-                up(c, d, rem, remh.data(), (size_t)nw * R);
-                HIPCHK(hipMemsetAsync(pre.in(d), 0, (size_t)nw * R * 8, c->stream));
-                HIPCHK(hipMemsetAsync(ghist.in(d), 0, (size_t)WB * R * GROUP_BINS * 8, c->stream));   // (k_group_pick zeroes it again)
-                for (int w0 = 0; w0 < nw; w0 += WB) {
-                    const int wn = std::min(WB, nw - w0);
-                    for (int dg = 0; dg < 6; ++dg) {
-                        launch_checked(c, k_group_hist, dim3(wn, B, (R + GROUP_RB - 1) / GROUP_RB), dim3(STATS_WG), 0, (const double*)col,
-                                       Mtot, (const int*)dwg.in(d), (const long long*)dG0.in(d), (const long long*)dgm.in(d), kbb, R, dg, w0,
-                                       (const long long*)rem.in(d), (const unsigned long long*)pre.in(d), ghist.in(d));
-                        launch_checked(c, k_group_pick, dim3(wn * R), dim3(STATS_WG), 0, dg, w0 * R, ghist.in(d), rem.in(d), pre.in(d));
-                    }
-                }
-                launch_checked(c, k_group_finish, dim3((nw + 63) / 64), dim3(64), 0, nw, (const int*)dwg.in(d), (const long long*)dgm.in(d),
-                               (int)G, (int)k0, kbb, (int)np, R, (const long long*)drk.in(d), (const unsigned long long*)pre.in(d),
-                               (const int*)gnan.in(d), (const double*)dprobs.in(d), (int)nq, omed, quant.in(d));
+                               (const int*)cnan.in(d), NC, dgch0, dgm, (int)G, (int)k0, kbb, (int)np, mean.in(d), gnan.in(d));
+                if (ord)
+                    pool_order(c, d, pd, pp, op, col, kbb, (int)k0, (int)np, gnan.in(d), med ? median.in(d) : nullptr, quant.in(d));
             }
             if (cov) {   // batches of chunks: every parameter centred, [np][nb][STATS_LDS_N]; each chunk's pair sums, then the groups'
                 const int Nbc = (int)std::min<size_t>(NC, c->st_scr_bytes / (np * STATS_LDS_N * 8));
                 const int nt = ((int)np + COV_T - 1) / COV_T, ntiles = nt * (nt + 1) / 2;
                 for (int cb0 = 0; cb0 < NC; cb0 += Nbc) {
                     const int nb = std::min(Nbc, NC - cb0);
-                    launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n,
-                                   (int)(accepted_only != 0), dgid, (const long long*)doff.in(d) + N, (const int*)dcch0.in(d), 0, (int)np,
-                                   Mtot, cb0, nb, (const double*)mean.in(d), (int)np, col, (int*)dcnt, 0);
+                    launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, sel, dgid,
+                                   (const long long*)pd.off.in(d) + N, (const int*)pd.cch0.in(d), 0, (int)np, Mtot, cb0, nb,
+                                   (const double*)mean.in(d), (int)np, col, dcnt, 0, (int*)nullptr);
                     launch_checked(c, k_cov_pairs, dim3(nb, ntiles), dim3(COV_WG), 0, (const double*)col, STATS_LDS_N, NC, cb0, nb, (int)np,
-                                   (const int*)dclen.in(d), csum2.in(d), 1);
+                                   dclen, csum2.in(d), 1);
                 }
             }
         }
         if (cov && G > 0)
             launch_checked(c, k_group_cov, dim3((unsigned)((G * np * (np + 1) / 2 + 255) / 256)), dim3(256), 0, (const double*)csum2.in(d),
-                           NC, (const int*)dgch0.in(d), (const long long*)dgm.in(d), (int)G, (int)np, covo.in(d));
+                           NC, dgch0, dgm, (int)G, (int)np, covo.in(d));
         if (kb > 0) {   // (no draw in any group: every output NaN, filled below)
             down(c, d, mean, out->mean, G * np);
             down(c, d, median, out->median, G * np);
@@ -605,7 +681,7 @@ int smm_get_group_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only
             if (out->median) std::fill(out->median, out->median + G * np, NAN);
             if (out->quantile) std::fill(out->quantile, out->quantile + nq * G * np, NAN);
         }
-        if (out->count) std::copy(gm.begin(), gm.end(), out->count);
+        if (out->count) std::copy(pp.gm.begin(), pp.gm.end(), out->count);
         if (out->n_chains) std::copy(grp.n_chains.begin(), grp.n_chains.end(), out->n_chains);
         return SMM_OK;
     });
@@ -1032,37 +1108,12 @@ int smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, cons
         const bool solve = out->status || out->jac || out->sens || out->se;
         const bool cov = solve || out->cov_pp || out->cov_pm || out->cov_mm || out->fit_z;
         const bool cols = cov || ord || out->p_mean || out->m_mean;
-        // the members' counts (select 1: k_group_gather's counting form; otherwise every row of the window), then smm_get_group_stats'
-        // plan on the host: the pooled offsets and the chunks
         const Groups grp = group_members(group, G, N);
-        const std::vector<int>& gid = grp.gid;
-        std::vector<int> cnt(N, n);
         DevBuf<int> dci(2 * N);
-        HIPCHK(hipMemcpyAsync(dci.p, gid.data(), N * 4, hipMemcpyHostToDevice, c->stream));
-        if (select == 1) {
-            launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, 1, (const int*)dci.p,
-                           (const long long*)nullptr, (const int*)nullptr, 0, 0, 0ll, 0, 0, (const double*)nullptr, (int)np, (double*)nullptr,
-                           dci.p + N, 1);
-            HIPCHK(hipMemcpyAsync(cnt.data(), dci.p + N, N * 4, hipMemcpyDeviceToHost, c->stream));
-        } else
-            HIPCHK(hipMemcpyAsync(dci.p + N, cnt.data(), N * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        std::vector<long long> gm(G, 0), G0(G + 1, 0), off(N, 0), roff(N, 0);
-        std::vector<int> gch0(G + 1, 0), cch0(N, 0);
-        for (size_t i = 0; i < N; ++i)
-            if (gid[i] >= 0) { roff[i] = gm[gid[i]]; gm[gid[i]] += cnt[i]; }
-        std::vector<long long> cst;
-        std::vector<int> clen;
-        for (size_t g = 0; g < G; ++g) {
-            G0[g + 1] = G0[g] + gm[g];
-            for (long long q = 0; q < gm[g]; q += STATS_LDS_N) { cst.push_back(G0[g] + q); clen.push_back((int)std::min<long long>(STATS_LDS_N, gm[g] - q)); }
-            gch0[g + 1] = (int)cst.size();
-        }
-        for (size_t i = 0; i < N; ++i)
-            if (gid[i] >= 0) { off[i] = G0[gid[i]] + roff[i]; cch0[i] = gch0[gid[i]]; }
-        const long long Mtot = G0[G];
-        const int NC = (int)cst.size();
-        if (out->count) std::copy(gm.begin(), gm.end(), out->count);
+        const PoolPlan pp = pool_plan(grp, pool_counts(c, grp, t0, n, select, dci.p));
+        const long long Mtot = pp.Mtot;
+        const int NC = pp.NC;
+        if (out->count) std::copy(pp.gm.begin(), pp.gm.end(), out->count);
         if (out->n_chains) std::copy(grp.n_chains.begin(), grp.n_chains.end(), out->n_chains);
         if (!cols || G == 0) return SMM_OK;
         if (Mtot == 0) {   // no row in any group: status 1, everything else NaN
@@ -1073,24 +1124,7 @@ int smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, cons
             nan(out->jac, G * nm * np); nan(out->sens, G * np * nm); nan(out->se, G * np);
             return SMM_OK;
         }
-        // the moments' order statistics: short columns sorted in LDS, the others selected grid-wide at ranks R per column (rk: -1 = unused)
-        std::vector<int> sgrp, wgrp;
-        long long wmax = 0;
-        for (size_t g = 0; g < G; ++g)
-            if (gm[g] < c->H.group_wide_min) sgrp.push_back((int)g);
-            else { wgrp.push_back((int)g); wmax = std::max(wmax, gm[g]); }
-        const int R = ord ? (med ? 2 : 0) + 2 * (int)nq : 0;
-        std::vector<long long> rk(wgrp.size() * R, -1);
-        for (size_t wi = 0; wi < wgrp.size() && R; ++wi) {   // stats_quantile's and the median's indexes
-            const long long m = gm[wgrp[wi]];
-            long long* r = rk.data() + wi * R;
-            if (med) { r[0] = (m & 1) ? m / 2 : m / 2 - 1; r[1] = (m & 1) ? -1 : m / 2; r += 2; }
-            for (size_t p = 0; p < nq; ++p, r += 2) {
-                const double h = (double)(m - 1) * probs[p];
-                if (h >= (double)(m - 1)) r[0] = m - 1;
-                else { r[0] = (long long)floor(h); r[1] = r[0] + 1; }
-            }
-        }
+        const OrderPlan op = order_plan(c, pp, med, probs, nq);
         // the batch plan: kb packed joint columns at a time in the scratch; the covariance Nbc chunks at a time, every joint column of a
         // chunk in the scratch and the chunks' D x D pair sums in the result buffer, both under the cap
         reducer_scratch(c, std::max(N * (size_t)P.T * 8, cov ? D * STATS_LDS_N * 8 : 0));
@@ -1098,85 +1132,49 @@ int smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, cons
         const size_t budget = hook ? std::min(c->st_scr_bytes, std::max({hook, (size_t)Mtot * 8, cov ? D * STATS_LDS_N * 8 : 0})) : c->st_scr_bytes;
         const size_t kb = std::min(D, budget / ((size_t)Mtot * 8));
         const int Nbc = !cov ? 0 : (int)std::max<size_t>(1, std::min({(size_t)NC, budget / (D * STATS_LDS_N * 8), reducer_batch_cap(c) / (D * D * 8)}));
-        const size_t nwc = wgrp.size() * std::min(kb, nm);   // long moment columns of a batch, selected WB at a time
-        const int WB = R ? (int)std::min(nwc, std::max((size_t)1, GROUP_HIST_CAP / ((size_t)R * GROUP_BINS * 8))) : 0;
         Carve Rv;   // 8-byte slices first
         const auto mean = Rv.take<double>(G * D), median = Rv.take<double>(G * D), quant = Rv.take<double>(nq * G * D),
-                   acc = Rv.take<double>(cov ? G * D * D : 0), dprobs = Rv.take<double>(nq), csum = Rv.take<double>(kb * NC),
+                   acc = Rv.take<double>(cov ? G * D * D : 0), csum = Rv.take<double>(kb * NC),
                    csum2 = Rv.take<double>(cov ? D * D * (size_t)Nbc : 0);
         const auto o_pmean = Rv.take<double>(G * np), o_mmean = Rv.take<double>(G * nm), o_mmed = Rv.take<double>(G * nm),
                    o_mq = Rv.take<double>(nq * G * nm), o_cpp = Rv.take<double>(G * np * np), o_cpm = Rv.take<double>(G * np * nm),
                    o_cmm = Rv.take<double>(G * nm * nm), o_z = Rv.take<double>(G * nm), o_jac = Rv.take<double>(G * nm * np),
                    o_sens = Rv.take<double>(G * np * nm), o_se = Rv.take<double>(G * np);
-        const auto doff = Rv.take<long long>(2 * N), dG0 = Rv.take<long long>(G + 1), dgm = Rv.take<long long>(G),
-                   dcst = Rv.take<long long>(NC), drk = Rv.take<long long>(rk.size()), rem = Rv.take<long long>(nwc * R);
-        const auto pre = Rv.take<unsigned long long>(nwc * R), ghist = Rv.take<unsigned long long>((size_t)WB * R * GROUP_BINS);
-        const auto dcch0 = Rv.take<int>(N), dgch0 = Rv.take<int>(G + 1), dclen = Rv.take<int>(NC), cnan = Rv.take<int>(kb * NC),
-                   gnan = Rv.take<int>(G * D), dsg = Rv.take<int>(sgrp.size()), dwg = Rv.take<int>(wgrp.size()), gbad = Rv.take<int>(G),
-                   o_st = Rv.take<int>(G);
+        const PoolDev pd(Rv, pp, op, op.wgrp.size() * std::min(kb, nm));   // (the long moment columns of a batch)
+        const auto cnan = Rv.take<int>(kb * NC), gnan = Rv.take<int>(G * D), gbad = Rv.take<int>(G), o_st = Rv.take<int>(G);
         void* d = reducer_result(c, Rv.bytes);
-        std::vector<long long> offs(off);
-        offs.insert(offs.end(), roff.begin(), roff.end());
-        up(c, d, doff, offs); up(c, d, dG0, G0); up(c, d, dgm, gm); up(c, d, dcst, cst); up(c, d, drk, rk);
-        up(c, d, dcch0, cch0); up(c, d, dgch0, gch0); up(c, d, dclen, clen); up(c, d, dsg, sgrp); up(c, d, dwg, wgrp);
-        up(c, d, dprobs, probs, nq);
+        pd.upload(c, d, pp, op);
         HIPCHK(hipMemsetAsync(gbad.in(d), 0, G * 4, c->stream));
-        const int* dgid = dci.p;
-        const int* dcnt = dci.p + N;
+        const int *dgid = dci.p, *dgch0 = pd.gch0.in(d), *dclen = pd.clen.in(d);
+        int* dcnt = dci.p + N;
+        const long long* dgm = pd.gm.in(d);
         double* col = (double*)c->st_scr;
         double* omed = med ? median.in(d) : nullptr;
-        std::vector<long long> remh(nwc * R);
-        const int B = (int)std::min<long long>(1024, std::max<long long>(1, (wmax + STATS_WG * 16 - 1) / (STATS_WG * 16)));
         for (size_t k0 = 0; k0 < D; k0 += kb) {   // batches of joint columns: the packed columns [kbb][Mtot]
             const int kbb = (int)std::min(kb, D - k0);
-            launch_checked(c, k_moment_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, dgid,
-                           (const long long*)doff.in(d), (const int*)nullptr, (int)k0, kbb, Mtot, 0, 0, (const double*)nullptr, (int)D, col,
-                           dcnt, gbad.in(d));
+            launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, dgid,
+                           (const long long*)pd.off.in(d), (const int*)nullptr, (int)k0, kbb, Mtot, 0, 0, (const double*)nullptr, (int)D, col,
+                           dcnt, 0, gbad.in(d));
             launch_checked(c, k_group_chunk_sum, dim3(NC, kbb), dim3(STATS_WG), (size_t)STATS_LDS_N * 8, (const double*)col, Mtot,
-                           (const long long*)dcst.in(d), (const int*)dclen.in(d), NC, csum.in(d), cnan.in(d));
+                           (const long long*)pd.cst.in(d), dclen, NC, csum.in(d), cnan.in(d));
             launch_checked(c, k_group_mean, dim3((unsigned)((G * kbb + 255) / 256)), dim3(256), 0, (const double*)csum.in(d),
-                           (const int*)cnan.in(d), NC, (const int*)dgch0.in(d), (const long long*)dgm.in(d), (int)G, (int)k0, kbb, (int)D,
-                           mean.in(d), gnan.in(d));
+                           (const int*)cnan.in(d), NC, dgch0, dgm, (int)G, (int)k0, kbb, (int)D, mean.in(d), gnan.in(d));
             const size_t ks = std::max(k0, np);   // the batch's moment columns [ks, k0 + kbb): the order statistics are theirs alone
-            if (!ord || ks >= k0 + kbb) continue;
-            const int km = (int)(k0 + kbb - ks);
-            const double* mcol = col + (ks - k0) * (size_t)Mtot;
-            if (!sgrp.empty())
-                launch_checked(c, k_group_small, dim3((unsigned)sgrp.size(), km), dim3(STATS_WG), (size_t)STATS_LDS_N * 8, mcol, Mtot,
-                               (const int*)dsg.in(d), (const long long*)dG0.in(d), (const long long*)dgm.in(d), (int)G, (int)ks, (int)D,
-                               (const int*)gnan.in(d), (const double*)dprobs.in(d), (int)nq, omed, quant.in(d));
-            if (wgrp.empty()) continue;
-            const int nw = (int)wgrp.size() * km;
-            for (int w = 0; w < nw; ++w)
-                for (int r = 0; r < R; ++r) remh[(size_t)w * R + r] = rk[(size_t)(w / km) * R + r];
-            up(c, d, rem, remh.data(), (size_t)nw * R);
-            HIPCHK(hipMemsetAsync(pre.in(d), 0, (size_t)nw * R * 8, c->stream));
-            HIPCHK(hipMemsetAsync(ghist.in(d), 0, (size_t)WB * R * GROUP_BINS * 8, c->stream));   // (k_group_pick zeroes it again)
-            for (int w0 = 0; w0 < nw; w0 += WB) {
-                const int wn = std::min(WB, nw - w0);
-                for (int dg = 0; dg < 6; ++dg) {
-                    launch_checked(c, k_group_hist, dim3(wn, B, (R + GROUP_RB - 1) / GROUP_RB), dim3(STATS_WG), 0, mcol, Mtot,
-                                   (const int*)dwg.in(d), (const long long*)dG0.in(d), (const long long*)dgm.in(d), km, R, dg, w0,
-                                   (const long long*)rem.in(d), (const unsigned long long*)pre.in(d), ghist.in(d));
-                    launch_checked(c, k_group_pick, dim3(wn * R), dim3(STATS_WG), 0, dg, w0 * R, ghist.in(d), rem.in(d), pre.in(d));
-                }
-            }
-            launch_checked(c, k_group_finish, dim3((nw + 63) / 64), dim3(64), 0, nw, (const int*)dwg.in(d), (const long long*)dgm.in(d), (int)G,
-                           (int)ks, km, (int)D, R, (const long long*)drk.in(d), (const unsigned long long*)pre.in(d), (const int*)gnan.in(d),
-                           (const double*)dprobs.in(d), (int)nq, omed, quant.in(d));
+            if (ord && ks < k0 + kbb)
+                pool_order(c, d, pd, pp, op, col + (ks - k0) * (size_t)Mtot, (int)(k0 + kbb - ks), (int)ks, (int)D, gnan.in(d), omed, quant.in(d));
         }
         if (cov) {   // batches of chunks: every joint column centred, [D][nb][STATS_LDS_N]; each chunk's pair sums, added onto the groups'
             HIPCHK(hipMemsetAsync(acc.in(d), 0, G * D * D * 8, c->stream));
             const int nt = ((int)D + COV_T - 1) / COV_T, ntiles = nt * (nt + 1) / 2;
             for (int cb0 = 0; cb0 < NC; cb0 += Nbc) {
                 const int nb = std::min(Nbc, NC - cb0);
-                launch_checked(c, k_moment_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, dgid,
-                               (const long long*)doff.in(d) + N, (const int*)dcch0.in(d), 0, (int)D, Mtot, cb0, nb, (const double*)mean.in(d),
-                               (int)D, col, dcnt, (int*)nullptr);
+                launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, dgid,
+                               (const long long*)pd.off.in(d) + N, (const int*)pd.cch0.in(d), 0, (int)D, Mtot, cb0, nb, (const double*)mean.in(d),
+                               (int)D, col, dcnt, 0, (int*)nullptr);
                 launch_checked(c, k_cov_pairs, dim3(nb, ntiles), dim3(COV_WG), 0, (const double*)col, STATS_LDS_N, nb, 0, nb, (int)D,
-                               (const int*)dclen.in(d) + cb0, csum2.in(d), 1);
+                               dclen + cb0, csum2.in(d), 1);
                 launch_checked(c, k_moment_cov_acc, dim3((unsigned)((G * D * (D + 1) / 2 + 255) / 256)), dim3(256), 0,
-                               (const double*)csum2.in(d), nb, cb0, (const int*)dgch0.in(d), (int)G, (int)D, acc.in(d));
+                               (const double*)csum2.in(d), nb, cb0, dgch0, (int)G, (int)D, acc.in(d));
             }
         }
         auto want = [&](const void* p, auto sl) { return p ? sl.in(d) : nullptr; };
@@ -1185,7 +1183,7 @@ int smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, cons
                            want(out->fit_z, o_z), want(out->jac, o_jac), want(out->sens, o_sens), want(out->se, o_se)};
         launch_checked(c, k_moment_solve, dim3((unsigned)G), dim3(MOMENT_WG), (2 * np + nm) * (np + 1) * 8,
                        cov ? (const double*)acc.in(d) : (const double*)nullptr, (const double*)mean.in(d), (const double*)omed,
-                       (const double*)quant.in(d), (const long long*)dgm.in(d), (const int*)gbad.in(d), (int)G, (int)np, (int)nm, (int)nq, ridge,
+                       (const double*)quant.in(d), dgm, (const int*)gbad.in(d), (int)G, (int)np, (int)nm, (int)nq, ridge,
                        P.mom, P.w, (int)solve, mo);
         down(c, d, o_st, out->status, G); down(c, d, o_pmean, out->p_mean, G * np); down(c, d, o_mmean, out->m_mean, G * nm);
         down(c, d, o_mmed, out->m_median, G * nm); down(c, d, o_mq, out->m_quantile, nq * G * nm);

@@ -4,7 +4,7 @@
 //
 //   k_stats_gather : one workgroup per chain streams the chain's records of the window, 256 iterations at a time (lane = iteration), and
 //                    compacts the selected draws of parameters [k0, k0 + kb) into column-major scratch col [kb][Nb][n] (position = rank
-//                    of the iteration among the selected ones: a ballot per wave, the four wave totals through LDS).  In the first
+//                    of the iteration among the selected ones: block_rank, smm_window.hpp, for the draws and the exchanges at once).  In the first
 //                    parameter batch also: count, findmin of value, the exchanges and the compacted non-zero partner ids pcol [Nb][n].
 //   k_stats_column : one workgroup per compacted column: the mean by the pairwise contract (chunks of 8192 staged in LDS: 8 lanes per
 //                    leaf of <= 128 draws, the combining tree replayed by one lane), then the order statistics — a bitonic sort of the
@@ -49,9 +49,8 @@ __global__ __launch_bounds__(STATS_WG) void k_stats_gather(const double* __restr
     __shared__ double wbv[STATS_WG / 64];
     __shared__ int wbi[STATS_WG / 64];
     const int cl = xcd_chain(blockIdx.x, gridDim.x), c = c0 + cl;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int base = 0, pbase = 0;
+    const int tid = threadIdx.x;
+    int base[2] = {0, 0};   // the selected draws and the exchanges so far
     double bv = 0.0;
     int bi = -1;
     for (int r0 = 0; r0 < n; r0 += STATS_WG) {
@@ -60,37 +59,19 @@ __global__ __launch_bounds__(STATS_WG) void k_stats_gather(const double* __restr
         const double* h = hrec + ((size_t)(t0 + (valid ? r : 0)) * N + c) * HW;
         double v = 0.0, ex = 0.0, acc = 0.0;
         if (valid) { v = h[H_VALUE]; ex = h[H_EXCH]; acc = h[H_ACC]; }
-        const bool sel = valid && (!acc_only || acc != 0.0);
-        const bool isx = valid && ex != 0.0;
+        const bool take[2] = {valid && (!acc_only || acc != 0.0), valid && ex != 0.0};
         if (valid && stats_better(v, t0 + r, bv, bi)) { bv = v; bi = t0 + r; }
-        const unsigned long long ms = __ballot(sel), mx = __ballot(isx);
-        if (lane == 0) { wtot[0][w] = __popcll(ms); wtot[1][w] = __popcll(mx); }
-        __syncthreads();
-        int off = base, poff = pbase;
-        for (int q = 0; q < STATS_WG / 64; ++q) {
-            if (q < w) { off += wtot[0][q]; poff += wtot[1][q]; }
-            base += wtot[0][q]; pbase += wtot[1][q];
-        }
-        __syncthreads();
-        if (sel) {
-            const size_t pos = (size_t)off + __popcll(ms & below);
-            for (int kk = 0; kk < kb; ++kk) col[((size_t)kk * Nb + cl) * n + pos] = h[H_PARAMS + k0 + kk];
-        }
-        if (first && isx) pcol[(size_t)cl * n + poff + __popcll(mx & below)] = (int)ex;
+        int pos[2];
+        block_rank(take, wtot, base, pos);
+        if (take[0])
+            for (int kk = 0; kk < kb; ++kk) col[((size_t)kk * Nb + cl) * n + (size_t)pos[0]] = h[H_PARAMS + k0 + kk];
+        if (first && take[1]) pcol[(size_t)cl * n + pos[1]] = (int)ex;
     }
     if (!first) return;
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (stats_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { wbv[w] = bv; wbi[w] = bi; }
-    __syncthreads();
+    block_best(bv, bi, wbv, wbi, stats_better);
     if (tid == 0) {
-        for (int q = 1; q < STATS_WG / 64; ++q)
-            if (stats_better(wbv[q], wbi[q], bv, bi)) { bv = wbv[q]; bi = wbi[q]; }
-        o_count[c] = base;
-        o_nex[c] = pbase;
+        o_count[c] = base[0];
+        o_nex[c] = base[1];
         o_bestv[c] = bi < 0 ? __longlong_as_double(0x7ff8000000000000ll) : bv;
         o_besti[c] = bi + 1;   // 1-based iteration; 0 for an empty window
     }

@@ -4,12 +4,11 @@
 // group; these collapse the member chains of a group per kept iteration.  mem [M]: the members of every group, group by group in
 // ascending local index (gmem0: the CSR offsets), as smm_get_histogram lists them.
 //
-//   k_trace_state  : (select 2) one workgroup per member walks the member's rows from the batch's first kept iteration to its last, 256
-//                    rows at a time (lane = row): a(t) is k_diag_gather's look-back and max-scan; the kept rows' a(t) (-1: none) go to
-//                    tab [kept iteration][member].
+//   k_trace_state  : (select 2) one workgroup per member walks the member's state rows from the batch's first kept iteration to its
+//                    last (state_walk, smm_window.hpp); the kept rows' a(t) (-1: none) go to tab [kept iteration][member].
 //   k_trace_gather : one workgroup per (kept iteration, group), TRACE_KMAX series of the series batch per blockIdx.y, walks the group's
-//                    members 256 at a time (lane = member): the row each member contributes and its rank among the selected ones (a
-//                    ballot per wave, the wave totals through LDS, as k_stats_gather ranks along time); then the threads read the
+//                    members 256 at a time (lane = member): the row each member contributes and its rank among the selected ones (block_rank,
+//                    smm_window.hpp, as k_stats_gather ranks along time); then the threads read the
 //                    block's (member, series) pairs, the series consecutive across lanes (a record's fields are contiguous), into the
 //                    contiguous column col [kept iteration][series][M] at the group's offset + rank.  The first workgroup of a (kept
 //                    iteration, group) in the first series batch also counts the members selected, accepted, exchanged and failed
@@ -30,33 +29,9 @@ __global__ __launch_bounds__(TRACE_WG) void k_trace_state(const double* __restri
                                                           int tb, int nk, int stride, int* __restrict__ tab) {
     __shared__ int wred[TRACE_WG / 64];
     const int p = xcd_chain(blockIdx.x, gridDim.x), c = mem[p];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int carry = -1;   // a(tb - 1): the look-back goes as far as row 0
-    for (int r1 = tb; r1 > 0 && carry < 0; r1 -= TRACE_WG) {
-        const int r = r1 - TRACE_WG + tid;
-        carry = diag_block_max((r >= 0 && hrec[((size_t)r * N + c) * HW + H_ACC] != 0.0) ? r : -1, wred);
-    }
-    const int n = (nk - 1) * stride + 1;
-    for (int r0 = 0; r0 < n; r0 += TRACE_WG) {
-        const int r = r0 + tid, t = tb + r;
-        const bool valid = r < n;
-        int a = (valid && hrec[((size_t)t * N + c) * HW + H_ACC] != 0.0) ? t : -1;
-        for (int o = 1; o < 64; o <<= 1) {   // inclusive max-scan across the wave
-            const int y = __shfl_up(a, o, 64);
-            if (lane >= o) a = max(a, y);
-        }
-        if (lane == 63) wred[w] = a;
-        __syncthreads();
-        int pre = carry, all = carry;
-        for (int q = 0; q < TRACE_WG / 64; ++q) {
-            if (q < w) pre = max(pre, wred[q]);
-            all = max(all, wred[q]);
-        }
-        __syncthreads();
-        a = max(a, pre);
-        carry = all;
-        if (valid && r % stride == 0) tab[(size_t)(r / stride) * Me + p] = a;
-    }
+    state_walk(hrec, N, HW, c, tb, (nk - 1) * stride + 1, wred, [&](int r, int a, bool) {
+        if (r % stride == 0) tab[(size_t)(r / stride) * Me + p] = a;
+    });
 }
 
 // grid (nk G, max(1, ceil(sb / TRACE_KMAX))).  Kept iteration il of the batch is row tb + il stride; series [s0, s0 + sb) to col
@@ -71,14 +46,13 @@ __global__ __launch_bounds__(TRACE_WG) void k_trace_gather(const double* __restr
     __shared__ int wtot[TRACE_WG / 64], wbi[TRACE_WG / 64];
     __shared__ double wbv[TRACE_WG / 64];
     const int b = xcd_chain(blockIdx.x, gridDim.x), il = b / G, g = b - il * G;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     const int t = tb + il * stride;
     const int m0 = gmem0[g], mg = gmem0[g + 1] - m0;
     const int k0 = blockIdx.y * TRACE_KMAX, kn = min(TRACE_KMAX, sb - k0);
     const int P = max(kn, 1), R = TRACE_WG / P, rr0 = tid / P, kk = tid - rr0 * P;
     const int field = trace_field(s0 + k0 + kk, np);
     const bool head = first != 0 && blockIdx.y == 0;
-    const unsigned long long below = (1ull << lane) - 1ull;
     const double qnan = __longlong_as_double(0x7ff8000000000000ll);
     int base = 0, nacc = 0, nex = 0, nfail = 0, bi = -1;
     double bv = 0.0;
@@ -96,16 +70,8 @@ __global__ __launch_bounds__(TRACE_WG) void k_trace_gather(const double* __restr
             if (h[H_STATUS] < 0.0) ++nfail;
             if (stats_better(v, j, bv, bi)) { bv = v; bi = j; }
         }
-        const unsigned long long ms = __ballot(take);
-        if (lane == 0) wtot[w] = __popcll(ms);
-        __syncthreads();
-        int off = base;
-        for (int q = 0; q < TRACE_WG / 64; ++q) {
-            if (q < w) off += wtot[q];
-            base += wtot[q];
-        }
+        posn[tid] = block_rank<int, false>(take, wtot, base);   // (the barrier behind rows[] closes it)
         rows[tid] = !take ? -2 : sel == 2 ? tab[(size_t)il * Me + m0 + j] : t;   // (-1: no state, a NaN; -2: not selected)
-        posn[tid] = off + __popcll(ms & below);
         cidx[tid] = c;
         __syncthreads();
         if (kn > 0 && rr0 < R) {
@@ -120,19 +86,11 @@ __global__ __launch_bounds__(TRACE_WG) void k_trace_gather(const double* __restr
         __syncthreads();
     }
     if (!head) return;
-    nacc = hist_block_sum(nacc, wtot);
-    nex = hist_block_sum(nex, wtot);
-    nfail = hist_block_sum(nfail, wtot);
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (stats_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { wbv[w] = bv; wbi[w] = bi; }
-    __syncthreads();
+    nacc = block_sum(nacc, wtot);
+    nex = block_sum(nex, wtot);
+    nfail = block_sum(nfail, wtot);
+    block_best(bv, bi, wbv, wbi, stats_better);
     if (tid == 0) {
-        for (int q = 1; q < TRACE_WG / 64; ++q)
-            if (stats_better(wbv[q], wbi[q], bv, bi)) { bv = wbv[q]; bi = wbi[q]; }
         o_count[b] = base;
         o_nacc[b] = nacc;
         o_nex[b] = nex;

@@ -66,6 +66,7 @@ using namespace smm;
 #include "smm_lookahead.hpp"
 #include "smm_exchange.hpp"
 #include "smm_cone_big.hpp"
+#include "smm_window.hpp"
 #include "smm_stats.hpp"
 #include "smm_cov.hpp"
 #include "smm_diag.hpp"

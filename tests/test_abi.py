@@ -188,18 +188,28 @@ def test_chain_kernel_instantiations_are_named_in_the_chooser_only():
 
 def test_reducer_kernels_and_shared_rules_live_in_the_reducers_host_file():
     """The host side of the history reducers is smm_reducers_host.hpp: smmhip.hip names none of their kernels (smm_stats.hpp, smm_cov.hpp,
-    smm_diag.hpp, smm_group.hpp, smm_hist.hpp, smm_trace.hpp), and the rules the family's members share are written there once, so
-    that every member refuses the same arguments in the same words.  Reads the sources only."""
+    smm_diag.hpp, smm_group.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp, smm_draws.hpp, smm_moments.hpp, smm_profile.hpp), and the
+    rules the family's members share are written there once, so that every member refuses the same arguments in the same words; the
+    order statistics of pooled columns are launched from one place, and the max-scan of the state walk lives in smm_window.hpp only.
+    Reads the sources only."""
     csrc = os.path.join(ROOT, "smm.jl_amd", "csrc")
     strip = lambda txt: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
-    main = strip(open(os.path.join(csrc, "smmhip.hip")).read())
-    assert not re.findall(r"\bk_(?:stats|cov|diag|group|hist|trace)_\w*", main), "smmhip.hip names a reducer kernel"
+    src = lambda name: strip(open(os.path.join(csrc, name)).read())
+    kernels = r"\bk_(?:stats|cov|diag|group|hist|trace|rank|draws|moment|prof)_\w*"
+    main = src("smmhip.hip")
+    assert not re.findall(kernels, main), "smmhip.hip names a reducer kernel"
     assert main.count('#include "smm_reducers_host.hpp"') == 1
-    host = strip(open(os.path.join(csrc, "smm_reducers_host.hpp")).read())
+    host = src("smm_reducers_host.hpp")
     declared = set()
-    for h in ("smm_stats.hpp", "smm_cov.hpp", "smm_diag.hpp", "smm_group.hpp", "smm_hist.hpp", "smm_trace.hpp"):
-        declared |= set(re.findall(r"__global__[^;{]*?\b(k_\w+)\s*\(", strip(open(os.path.join(csrc, h)).read())))
-    assert len(declared) >= 20 and set(re.findall(r"\bk_(?:stats|cov|diag|group|hist|trace)_\w*", host)) == declared
+    for h in ("smm_stats.hpp", "smm_cov.hpp", "smm_diag.hpp", "smm_group.hpp", "smm_hist.hpp", "smm_trace.hpp", "smm_rank.hpp",
+              "smm_draws.hpp", "smm_moments.hpp", "smm_profile.hpp"):
+        declared |= set(re.findall(r"__global__[^;{]*?\b(k_\w+)\s*\(", src(h)))
+    assert len(declared) >= 20 and set(re.findall(kernels, host)) == declared
+    for k in ("k_group_small", "k_group_hist", "k_group_pick", "k_group_finish"):
+        assert len(re.findall(r"launch_checked\(c, %s\b" % k, host)) == 1, k
+    for h in ("smm_diag.hpp", "smm_hist.hpp", "smm_trace.hpp"):
+        assert "__shfl_up" not in src(h), h
+    assert "__shfl_up" in src("smm_window.hpp")
     for message in ("a group id outside [-1, n_groups)", "probs must lie in [0, 1]", "quantile requested without probs",
                     "select must be 0 (all), 1 (accepted) or 2 (state)", "n_groups < 0, or group NULL with n_groups > 0",
                     "n_groups < 0, or group NULL with n_groups != 1"):
