@@ -29,7 +29,7 @@ int pop_enter(Ctx* c) {
     (void)check_device_error(c);
     if (c->failed && !c->failed_told) { c->failed_told = true; return c->failed; }
     if (c->failed) return told(c);
-    if (c->iter != 0) return fail(c, SMM_ERR_STATE, "the starting population is installed before the first iteration only (completed iterations: " + std::to_string(c->iter) + ")");
+    if (c->run.iter != 0) return fail(c, SMM_ERR_STATE, "the starting population is installed before the first iteration only (completed iterations: " + std::to_string(c->run.iter) + ")");
     if (c->P.T < 1) return fail(c, SMM_ERR_MAXITER, "maxiter == 0: no room for the chains' first iteration");
     return SMM_OK;
 }
@@ -50,14 +50,14 @@ void pop_finish(Ctx* c, PopBufs& B, smm_population_t* out, int64_t evaluated, in
     HIPCHK(hipStreamSynchronize(c->stream));
     if (out) out->evaluated = evaluated;
     c->nan_values = flag != 0u;
-    c->iter = 1;
-    c->rec_external = false; c->pending_ext = false; c->unresolved = false;
-    c->pending = false;
-    c->prev_open = false;
+    c->run.iter = 1;
+    c->rec_external = false; c->pending_ext = false; c->run.unresolved = false;
+    c->run.pending = false;
+    c->run.prev_open = false;
     c->a2a_open = false;
     c->p2p_current = false;
-    c->exch_done = false;
-    c->slots_iter = -1;
+    c->run.exch_done = false;
+    c->run.slots_iter = -1;
     if (P.walk_flags) HIPCHK(hipMemset(P.walk_flags, 0, 16));
     c->pop_kind = kind; c->pop_M = M; c->pop_spread = spread;
 }
@@ -67,7 +67,7 @@ PopArgs pop_args(Ctx* c, PopBufs& B) {
     A.cand = B.cand.p; A.value = B.value.p; A.simM = B.simM.p; A.status = B.status.p;
     A.user = c->obj == SMM_OBJ_USER ? 1 : 0;
     A.init_simM = B.i_simM.p;
-    A.rec_out = c->rec[c->cur];
+    A.rec_out = c->rec[c->run.cur];
     A.o_start = B.o_start.p; A.o_value = B.o_value.p; A.o_pick = B.o_pick.p; A.nan_flag = B.flag.p;
     return A;
 }
@@ -77,9 +77,7 @@ PopArgs pop_args(Ctx* c, PopBufs& B) {
 extern "C" {
 
 int smm_set_population(void* ctx, const double* starts, smm_population_t* out) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return SMM_ERR_INVALID_ARG;
-    try {
+    return api_call(ctx, true, [&](Ctx* c) -> int {
         if (const int rc = pop_enter(c)) return rc;
         if (!starts) return fail(c, SMM_ERR_INVALID_ARG, "smm_set_population: starts is NULL");
         const KParams& P = c->P;
@@ -110,16 +108,12 @@ int smm_set_population(void* ctx, const double* starts, smm_population_t* out) {
         A.c0 = 0; A.nb = (int)N; A.M = 1; A.n = (int)N; A.force = 1;
         pop_launch_select(c, A);
         pop_finish(c, B, out, (int64_t)N, 1, 0, 0.0);
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
+        return SMM_OK;
+    });
 }
 
 int smm_scatter_population(void* ctx, int32_t M, double spread, int32_t keep_init, smm_population_t* out) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return SMM_ERR_INVALID_ARG;
-    try {
+    return api_call(ctx, true, [&](Ctx* c) -> int {
         if (const int rc = pop_enter(c)) return rc;
         const KParams& P = c->P;
         if (M < 1) return fail(c, SMM_ERR_INVALID_ARG, "smm_scatter_population: M < 1");
@@ -147,10 +141,8 @@ int smm_scatter_population(void* ctx, int32_t M, double spread, int32_t keep_ini
             pop_launch_select(c, A);
         }
         pop_finish(c, B, out, (int64_t)M * P.N + 1, 2, M, spread);
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
+        return SMM_OK;
+    });
 }
 
 }  // extern "C"

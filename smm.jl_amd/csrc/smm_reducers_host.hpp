@@ -3,7 +3,7 @@
 // smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws, smm_get_moment_stats, smm_get_profile (kernels: smm_stats.hpp,
 // smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_moments.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp, smm_draws.hpp, smm_profile.hpp;
 // the walk over a chain's window that their gathers share: smm_window.hpp).
-// What they share is stated here once: the frame of a call (reducer_call), the checks of the arguments they have in common (check_groups,
+// What they share is stated here once: the frame of a call (api_call of smmhip.hip), the checks of the arguments they have in common (check_groups,
 // check_probs, check_select), the prelude and the window behind them (settled_window: reader_prelude and check_window of smmhip.hip), the
 // members of the groups (Groups), one result buffer per context (reducer_result, laid out by Carve / Slice, copied by up / down), one
 // scratch per context for the compacted columns (reducer_scratch, chain_batches), the cap on the scratch and on a batch of results
@@ -18,18 +18,6 @@ namespace {
 static_assert(STATS_WG == WINDOW_WG && DIAG_WG == WINDOW_WG && HIST_WG == WINDOW_WG && TRACE_WG == WINDOW_WG && DRAWS_WG == WINDOW_WG &&
                   PROF_WG == WINDOW_WG && RANK_WG == WINDOW_WG && WINDOW_WG == 256,
               "smm_window.hpp walks a window 256 rows at a time, four waves' totals through LDS; k_draws_mask splits a tile over four waves");
-
-// the frame of an entry point: body(c) returns SMM_OK or what fail() returned
-template <class Body>
-int reducer_call(void* ctx, bool args_given, Body body) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !args_given) return SMM_ERR_INVALID_ARG;
-    try {
-        return body(c);
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-}
 
 // the prelude, then the window: what a call over a window does once its arguments have passed
 int settled_window(Ctx* c, int t0, int t1) { reader_prelude(c); return check_window(c, t0, t1); }
@@ -324,7 +312,7 @@ extern "C" {
 // mean / median / CI / best / summary of AlgoBGP.jl:117-206 for every local chain, reduced where the history lives (smm_stats.hpp)
 int smm_get_chain_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, const double* probs, int32_t n_probs,
                         smm_chain_stats_t* out) {
-    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
         if (const int rc = check_probs(c, probs, n_probs, out->quantile != nullptr)) return rc;
         if (const int rc = settled_window(c, t0, t1)) return rc;
         const KParams& P = c->P;
@@ -422,7 +410,7 @@ static CovRes chain_cov_device(Ctx* c, int t0, int t1, int accepted_only, int un
 
 int smm_get_chain_cov(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, int32_t unit_space, int32_t* count, double* mean,
                       double* cov) {
-    return reducer_call(ctx, true, [&](Ctx* c) -> int {
+    return api_call(ctx, true, [&](Ctx* c) -> int {
         if (const int rc = settled_window(c, t0, t1)) return rc;
         const size_t N = c->P.N, np = c->P.np;
         const CovRes r = chain_cov_device(c, t0, t1, accepted_only, unit_space);
@@ -441,7 +429,7 @@ static double* proposal_rows(const KParams& P) {
 }
 
 int smm_get_proposal(void* ctx, double* L) {
-    return reducer_call(ctx, L != nullptr, [&](Ctx* c) -> int {
+    return api_call(ctx, L != nullptr, [&](Ctx* c) -> int {
         const KParams& P = c->P;
         if (!P.chol_L) return fail(c, SMM_ERR_INVALID_ARG, "the context has no proposal factor: create it with chol_L");
         HIPCHK(hipSetDevice(c->device));   // (reads the factor as it stands: no prelude)
@@ -463,7 +451,7 @@ static int proposal_prelude(Ctx* c) {
 }
 
 int smm_set_proposal(void* ctx, const double* L) {
-    return reducer_call(ctx, L != nullptr, [&](Ctx* c) -> int {
+    return api_call(ctx, L != nullptr, [&](Ctx* c) -> int {
         const KParams& P = c->P;
         if (!P.chol_L) return fail(c, SMM_ERR_INVALID_ARG, "the context has no proposal factor: create it with chol_L");
         const size_t n = proposal_doubles(P), np = P.np;
@@ -485,7 +473,7 @@ int smm_set_proposal(void* ctx, const double* L) {
 
 int smm_adapt_proposal(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, int32_t min_draws, int32_t normalize, double ridge,
                        int32_t* status) {
-    return reducer_call(ctx, true, [&](Ctx* c) -> int {
+    return api_call(ctx, true, [&](Ctx* c) -> int {
         const KParams& P = c->P;
         if (!P.chol_L) return fail(c, SMM_ERR_INVALID_ARG, "the context has no proposal factor: create it with chol_L (per chain)");
         if (!P.chol_per_chain)
@@ -536,7 +524,7 @@ static double host_sum(const std::vector<double>& x) {
 
 int smm_get_chain_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32_t n_acf, const int32_t* group, int32_t n_groups,
                        smm_chain_diag_t* out) {
-    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
         // (between check_groups' NULL rule and its ids; ahead of both it decides the same, as no count fails this and the NULL rule)
         if (out->rhat && n_groups == 0) return fail(c, SMM_ERR_INVALID_ARG, "rhat requested without groups");
         if (const int rc = check_groups(c, group, n_groups, GROUPS_OPTIONAL)) return rc;
@@ -610,7 +598,7 @@ int smm_get_chain_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32
 
 int smm_get_group_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only, const int32_t* group, int32_t n_groups,
                         const double* probs, int32_t n_probs, smm_group_stats_t* out) {
-    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
         if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
         if (const int rc = check_probs(c, probs, n_probs, out->quantile != nullptr)) return rc;
         if (const int rc = settled_window(c, t0, t1)) return rc;
@@ -691,7 +679,7 @@ int smm_get_group_stats(void* ctx, int32_t t0, int32_t t1, int32_t accepted_only
 
 int smm_get_histogram(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups, int32_t bins,
                       const double* range, const int32_t* pairs, int32_t n_pairs, int32_t bins2, smm_histogram_t* out) {
-    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
         const size_t N = c->P.N, np = c->P.np;
         if (const int rc = check_select(c, select)) return rc;
         if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
@@ -788,7 +776,7 @@ int smm_get_histogram(void* ctx, int32_t t0, int32_t t1, int32_t select, const i
 
 int smm_get_trace(void* ctx, int32_t t0, int32_t t1, int32_t stride, int32_t select, int32_t moments, const int32_t* group, int32_t n_groups,
                   const double* probs, int32_t n_probs, smm_trace_t* out) {
-    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
         if (stride < 1) return fail(c, SMM_ERR_INVALID_ARG, "stride must be at least 1");
         if (const int rc = check_select(c, select)) return rc;
         if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
@@ -858,7 +846,7 @@ int smm_get_trace(void* ctx, int32_t t0, int32_t t1, int32_t stride, int32_t sel
 
 int smm_get_rank_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32_t n_bins, const int32_t* group, int32_t n_groups,
                       smm_rank_diag_t* out) {
-    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
         if (n_groups == 0) return fail(c, SMM_ERR_INVALID_ARG, "n_groups must be at least 1");
         if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
         if (n_bins < 0) return fail(c, SMM_ERR_INVALID_ARG, "n_bins must be >= 0");
@@ -995,7 +983,7 @@ int smm_get_rank_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32_
 
 int smm_get_draws(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups, int32_t thin, int32_t max_rows,
                   int64_t rows_cap, smm_draws_t* out) {
-    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
         if (const int rc = check_select(c, select)) return rc;
         if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
         if (thin < 1) return fail(c, SMM_ERR_INVALID_ARG, "thin must be at least 1");
@@ -1095,7 +1083,7 @@ int smm_get_draws(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32
 
 int smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups, const double* probs,
                          int32_t n_probs, double ridge, smm_moment_stats_t* out) {
-    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
         if (const int rc = check_select(c, select)) return rc;
         if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
         if (const int rc = check_probs(c, probs, n_probs, out->m_quantile != nullptr)) return rc;
@@ -1199,7 +1187,7 @@ int smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, cons
 
 int smm_get_profile(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups, int32_t bins,
                     const double* range, const int32_t* pairs, int32_t n_pairs, int32_t bins2, smm_profile_t* out) {
-    return reducer_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
         const size_t N = c->P.N, np = c->P.np, nm = c->P.nm;
         if (const int rc = check_select(c, select)) return rc;
         if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;

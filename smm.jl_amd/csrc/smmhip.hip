@@ -13,7 +13,8 @@
 //   k_exch_resolve_*  : the same exchange resolution as a kernel of one workgroup (sharded path, larger
 //                       populations, and whenever the result is needed before the next chain kernel).
 // Files: smm_params.hpp (parameter block, layouts), smm_chain.hpp (chain kernel and its parts), smm_lookahead.hpp (k_pregen_rng,
-// k_exch_plan), smm_exchange.hpp (stand-alone exchange kernels), smm_reducers_host.hpp (the history reducers' host side), this file (host).
+// k_exch_plan), smm_exchange.hpp (stand-alone exchange kernels), this file (host: contexts, forms, choosers, windows, the call frame), smm_run_host.hpp (the run's host side:
+// stepping, settling, the sharded protocol), smm_reducers_host.hpp (the history reducers' host side), smm_population_host.hpp (the starting population's).
 // Everything that does not depend on the chains' state is produced ahead of the dependent loop by
 // wide, latency-tolerant kernels, one window of iterations at a time:
 //   k_pregen_rng      : proposal normals (first tries) and the MH uniforms (probs_acc, :85)
@@ -506,45 +507,69 @@ struct Forms {
     bool defer_resolve = false;  // the exchange of an iteration is left unresolved until somebody needs it (the next launch may be the persistent kernel's)
 };
 
+// Where the run stands, as the host keeps it: what persist_snapshot saves and persist_repair puts back, whole
+struct Run {
+    int iter = 0;
+    int cur = 0;               // rec[cur] holds the records after the last accept step
+    int slots_iter = -1;       // single shard, rows exchange: the accept step of this iteration wrote the resolution's initial slots (no pre-pass)
+    bool pending = false;      // exchange of iteration `iter` resolved but not applied
+    bool prev_open = false;    // accept-rate counters of iteration `iter` not closed yet
+    bool unresolved = false;   // exchangeMoves! of iteration `iter` is still to be resolved (inline, or by resolve_now)
+    bool exch_done = false;    // the three-phase / values forms: exchangeMoves! of iteration `iter` has been applied (cleared by the next local step)
+};
+
 struct Ctx {
     KParams P{};
     Hooks H;                   // read once at creation
     Forms F;                   // chosen once at creation (select_forms)
     int obj = 0, device = 0, exchange_from = 2;
-    int iter = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<void*> allocs;
     std::string err;
-    smm_timing_t timing{};
-    bool pending_timing = false;
-    int profiling = 0;   // 1: event brackets around the kernels; 2: the kernels' own begin/end timestamps (launch)
-    hipEvent_t kev0 = nullptr, kev1 = nullptr;   // mode 2: start/stop events of the next launch
-    std::vector<char> pev_exch;
-    std::vector<hipEvent_t> pev;  // profiling events: 4 per iteration (the last two bracket nothing: the event overhead)
-    int pev_iters = 0;
+    int u_lanes = 0;                // user objective: lanes per evaluation (0 = one thread per chain)
+    int n_objp = 0;                 // doubles in P.objp
+    hipModule_t umod = nullptr;     // user objective: this context's module and kernel
+    hipFunction_t ufn = nullptr;
+    hipFunction_t ufn_noseed = nullptr;   // ... an objective with the library's stream: its noseed kernel (evaluation i keyed by base_seed + i)
+    bool u_rng = false;
+    hipModule_t pmod = nullptr;     // ... and the persistent kernel compiled with it inside: k_chain_persist_gen (SMM_GEN_USER), or
+    hipFunction_t pfn = nullptr;    //     k_chain_persist_tile with its map-reduce form (SMM_TILE_USER)
+    int u_nsums = 1;                // ... its partial sums per lane
+    int pop_kind = 0, pop_M = 0; // the starting population installed on this context: 0 none, 1 smm_set_population, 2 smm_scatter_population (smm_describe)
+    double pop_spread = 0.0;
+
+    // ---- run state ----
+    Run run;
+    // (a shard's flags: not part of what persist_snapshot saves — persist_repair sets them itself)
+    bool rec_external = false;  // the records after the last accept step were written to the caller's gather buffer (sharded_step)
+    bool pending_ext = false;   // sharded_step: the exchange of iteration `run.iter` is still to be resolved from the gathered records
+    bool a2a_open = false;
+    bool p2p_current = false;                  // the windows hold the records after iteration `run.iter`
+    bool p2p_unwaited = false;                 // nobody has waited for the arrivals of the last push yet
+    int failed = 0;             // a hard device error (AlgoBGP.jl:341,409) stopped the run at iteration `run.iter`: sticky until smm_set_state
+    bool failed_told = false;   // `failed` has been returned to the caller by some entry point
     // double-buffered last-accepted records [N][RW]
     double* rec[2] = {nullptr, nullptr};
-    int cur = 0;               // rec[cur] holds the records after the last accept step
-    bool pending = false;      // exchange of iteration `iter` resolved but not applied
-    bool prev_open = false;    // accept-rate counters of iteration `iter` not closed yet
-    // look-ahead windows
+    double* vals_buf[2] = {nullptr, nullptr};   // KParams::vals / vals_out, by iteration parity (point_values)
+    uint2* slot8_buf[2] = {nullptr, nullptr};
+    bool deep_plan = false;      // an injected pair list has an iteration of more than LV_MAXLEV dependency levels
+    bool nan_values = false;     // the uploaded state holds NaN values (smm_set_state)
+    // (set for one launch: ExternalRecords, smm_run_host.hpp)
+    const double* ext_rec_in = nullptr;   // sharded_step: donor records come from / results go to the caller's gather buffers
+    double* ext_rec_out = nullptr;
+    double* ext_vals_out = nullptr;            // p2p generic form: the accept step's values go into the window
+
+    // ---- look-ahead windows ----
     double* win_rb = nullptr;
     unsigned long long* win_plan = nullptr;
     double* win_plan_mi = nullptr;
     uint32_t *win_lv_pairs = nullptr, *win_lv_off = nullptr, *win_lv_pairs_p = nullptr, *win_lv_offp = nullptr;
     uint32_t *win_lv_rows = nullptr, *win_lv_rowinfo = nullptr, *slots17 = nullptr, *nan_flags = nullptr;
-    int32_t *a2a_send_idx = nullptr, *a2a_send_cnt = nullptr, *a2a_rowidx = nullptr;   // the values form of the sharded exchange
-    int a2a_cap = 0, a2a_G = 0;
-    bool a2a_open = false;
-    int slots_iter = -1;        // single shard, rows exchange: the accept step of this iteration wrote the resolution's initial slots (no pre-pass)
-    bool exch_done = false;     // the three-phase / values forms: exchangeMoves! of iteration `iter` has been applied (cleared by the next local step)
-    double* vals_buf[2] = {nullptr, nullptr};   // KParams::vals / vals_out, by iteration parity (point_values)
-    uint2* slot8_buf[2] = {nullptr, nullptr};
-    bool deep_plan = false;      // an injected pair list has an iteration of more than LV_MAXLEV dependency levels
-    bool nan_values = false;     // the uploaded state holds NaN values (smm_set_state)
-    int pop_kind = 0, pop_M = 0; // the starting population installed on this context: 0 none, 1 smm_set_population, 2 smm_scatter_population (smm_describe)
-    double pop_spread = 0.0;
+    double* win_lv_mi = nullptr;
+    uint32_t* big_scratch = nullptr;
+    int rng_t0 = 0, rng_w = 0;    // window currently held: iterations [t0, t0+w)
+    int plan_t0 = 0, plan_w = 0;
     uint32_t* cb_scratch = nullptr;
     std::vector<uint32_t> cone_big_ok;   // per iteration of the plan window: its cones fit their caps
     // ... their windows are planned AHEAD: the plan of a window depends on (seed, iteration) only, so while the chain kernels of one
@@ -560,46 +585,24 @@ struct Ctx {
     int ps_act = 0;                      // the set the chain kernels read
     hipStream_t pstream = nullptr;
     hipEvent_t ev_free = nullptr;        // main stream: every launch that reads the set about to be planned into has been enqueued before it (plan_window_into)
-    double* win_lv_mi = nullptr;
-    const double* ext_rec_in = nullptr;   // sharded_step: donor records come from / results go to the caller's gather buffers
-    double* ext_rec_out = nullptr;
-    bool pending_ext = false;   // sharded_step: the exchange of iteration `iter` is still to be resolved from the gathered records
-    int u_lanes = 0;                // user objective: lanes per evaluation (0 = one thread per chain)
-    int n_objp = 0;                 // doubles in P.objp
-    hipModule_t umod = nullptr;     // user objective: this context's module and kernel
-    hipFunction_t ufn = nullptr;
-    hipFunction_t ufn_noseed = nullptr;   // ... an objective with the library's stream: its noseed kernel (evaluation i keyed by base_seed + i)
-    bool u_rng = false;
-    hipModule_t pmod = nullptr;     // ... and the persistent kernel compiled with it inside: k_chain_persist_gen (SMM_GEN_USER), or
-    hipFunction_t pfn = nullptr;    //     k_chain_persist_tile with its map-reduce form (SMM_TILE_USER)
-    int u_nsums = 1;                // ... its partial sums per lane
-    bool rec_external = false;  // the records after the last accept step were written to the caller's gather buffer (sharded_step)
-    bool unresolved = false;    // exchangeMoves! of iteration `iter` is still to be resolved (inline, or by resolve_now)
-    uint32_t* big_scratch = nullptr;
-    int rng_t0 = 0, rng_w = 0;    // window currently held: iterations [t0, t0+w)
-    int plan_t0 = 0, plan_w = 0;
-    int failed = 0;             // a hard device error (AlgoBGP.jl:341,409) stopped the run at iteration `iter`: sticky until smm_set_state
-    // the p2p form of the sharded iteration (smm_p2p.hpp)
+
+    // ---- the values form of the sharded exchange ----
+    int32_t *a2a_send_idx = nullptr, *a2a_send_cnt = nullptr, *a2a_rowidx = nullptr;
+    int a2a_cap = 0, a2a_G = 0;
+
+    // ---- the p2p form of the sharded iteration (smm_p2p.hpp) ----
     unsigned char* p2p_mine = nullptr;         // this rank's window (null: smm_bgp_p2p_init not called)
-    // the history reducers (smm_get_chain_stats / _cov / _diag, smm_adapt_proposal): their shared scratch for the compacted columns
-    // (reducer_scratch) and the results of a call (reducer_result: grown to the largest call's), both in smm_reducers_host.hpp
-    void* st_scr = nullptr;
-    size_t st_scr_bytes = 0;
-    void* red_res = nullptr;
-    size_t red_res_bytes = 0;
     void* p2p_opened[P2P_MAXG] = {};           // peers' windows opened through HIP IPC (closed with the context)
     unsigned p2p_attached = 0;                 // bit r: rank r's window is known
     unsigned long long p2p_seq = 0;            // pushes so far (every rank counts the same)
-    bool p2p_current = false;                  // the windows hold the records after iteration `iter`
     bool p2p_inline = false;                   // the inline form is available: k_chain_iter_norm_p2p walks inline and pushes from its epilogue
     bool p2p_rows = false;                     // the same kernel without the walk + k_exch_resolve_rows<., true> on the window's slots
     bool p2p_mode_inline = false;              // ... and is what the windows currently hold (decided at every publication)
-    bool p2p_unwaited = false;                 // nobody has waited for the arrivals of the last push yet
-    double* ext_vals_out = nullptr;            // p2p generic form: the accept step's values go into the window
-    // the persistent chain kernel (smm_chain_persist.hpp): one launch for a run of iterations
+    int p2p_ranks_here = 1;                    // ranks whose windows live on THIS device (this one included): their tiles must all be resident together
+
+    // ---- the persistent chain kernel (smm_chain_persist.hpp): one launch for a run of iterations ----
     unsigned char* prw = nullptr;              // persist_loc: the ring's window (pr_win_layout) — a single shard's own allocation, a shard's: inside its p2p window
     size_t prw_off = 0;                        // persist_sh: offset of the ring's window inside the p2p window
-    int p2p_ranks_here = 1;                    // ranks whose windows live on THIS device (this one included): their tiles must all be resident together
     bool persist_proven = false;               // a launch of the persistent form has come through: its spins may last P2P_TIMEOUT_TICKS from now on
     int persist_strikes = 0;                   // time-outs so far (two: the form is off for the context)
     int persist_on = 1;                        // smm_set_persistent
@@ -607,16 +610,31 @@ struct Ctx {
     uint32_t pr_epoch = 0;                     // launches so far
     int persist_launches = 0, persist_repairs = 0;
     int pregen_seen_launches = 0;              // persist_launches when the last window of randomness blocks was made (ensure_windows)
-    bool failed_told = false;   // `failed` has been returned to the caller by some entry point
     bool in_repair = false;
     // ... and what persist_repair restores when a launch of it ends with the error word set: the state before the FIRST such launch
     // since the last check of the error word
     bool snap_valid = false;
-    int snap_iter = 0, snap_cur = 0, snap_slots_iter = -1;
-    bool snap_pending = false, snap_prev_open = false, snap_unresolved = false, snap_exch_done = false;
+    Run snap;
     double *snap_cs = nullptr, *snap_rec = nullptr, *snap_vals[2] = {nullptr, nullptr}, *hist_fill = nullptr;
     uint2* snap_slot8[2] = {nullptr, nullptr};
     unsigned long long* snap_xres = nullptr;
+
+    // ---- the history reducers (smm_get_chain_stats / _cov / _diag, smm_adapt_proposal) ----
+    // their shared scratch for the compacted columns (reducer_scratch) and the results of a call (reducer_result: grown to the largest
+    // call's), both in smm_reducers_host.hpp
+    void* st_scr = nullptr;
+    size_t st_scr_bytes = 0;
+    void* red_res = nullptr;
+    size_t red_res_bytes = 0;
+
+    // ---- profiling ----
+    smm_timing_t timing{};
+    bool pending_timing = false;
+    int profiling = 0;   // 1: event brackets around the kernels; 2: the kernels' own begin/end timestamps (launch)
+    hipEvent_t kev0 = nullptr, kev1 = nullptr;   // mode 2: start/stop events of the next launch (set for that launch: KernelEvents, smm_run_host.hpp)
+    std::vector<char> pev_exch;
+    std::vector<hipEvent_t> pev;  // profiling events: 4 per iteration (the last two bracket nothing: the event overhead)
+    int pev_iters = 0;
 };
 
 #define HIPCHK(call)                                                                                  \
@@ -944,11 +962,11 @@ void launch_chain_iter(Ctx* c, int t, int flags) {
     const bool own_slots = c->F.xk == XK_ROWS && c->P.N == c->P.Ng && !c->ext_rec_out && !c->ext_vals_out && c->obj != SMM_OBJ_USER;
     c->P.slots17_out = own_slots ? c->slots17 : nullptr;
     c->P.nan_flags_out = own_slots ? c->nan_flags + (t & 1) : nullptr;
-    if (own_slots) c->slots_iter = t;
+    if (own_slots) c->run.slots_iter = t;
     const ChainKernel K = chain_kernel(c, flags);
     const size_t smem = tile_smem(c, K.ct, K.tpw);
-    const double* rin = c->ext_rec_in ? c->ext_rec_in : (const double*)c->rec[c->cur];
-    double* rout = c->ext_rec_out ? c->ext_rec_out : c->rec[c->cur ^ 1];
+    const double* rin = c->ext_rec_in ? c->ext_rec_in : (const double*)c->rec[c->run.cur];
+    double* rout = c->ext_rec_out ? c->ext_rec_out : c->rec[c->run.cur ^ 1];
     if (c->obj == SMM_OBJ_USER) {
         // proposal launch (stores nothing but the proposals) -> the user's kernel -> accept launch (repeats the
         // deterministic prologue, takes value / moments / status from the user's kernel)
@@ -957,7 +975,7 @@ void launch_chain_iter(Ctx* c, int t, int flags) {
         launch_user_kernel(c, P.u_theta, P.N, P.u_simM, P.u_value, P.u_status);
     }
     launch_chain_kernel(c, K, smem, c->P, t, rin, rout, flags);
-    if (!c->ext_rec_out) c->cur ^= 1;
+    if (!c->ext_rec_out) c->run.cur ^= 1;
 }
 
 size_t resolve_lean_bytes(int Ng, int K, bool wide) { return std::max(wide ? lean_wide_bytes(Ng, K) : lean_walk_bytes(Ng, K), resolve_lvl_soa_bytes(Ng, K)); }
@@ -992,11 +1010,11 @@ void launch_resolve_p(Ctx* c, const KParams& P_in, int t, const double* gathered
         // values and initial slots by the whole chip (gathered records: their value column; single shard: the compact array)
         const double* src = gathered ? gathered : (const double*)P.vals;
         double* vals = gathered ? P.xval : P.vals;
-        if (gathered || c->slots_iter != t)   // (a single shard's accept step of iteration t has made the slots already)
+        if (gathered || c->run.slots_iter != t)   // (a single shard's accept step of iteration t has made the slots already)
             hipLaunchKernelGGL(k_exch_keys, dim3((P.Ng + 255) / 256), dim3(256), 0, c->stream, src, gathered ? P.RW : 1, P.Ng, vals,
                                (uint32_t*)P.xsrc, c->F.xk == XK_ROWS ? c->slots17 : (uint32_t*)nullptr, c->nan_flags, t);
         const bool plds = P.Ng <= XKEY_PARTNER_MAX;   // partners in LDS, else the ballot replay
-        const uint32_t* slots16 = (gathered || c->slots_iter != t) ? (const uint32_t*)P.xsrc : (const uint32_t*)nullptr;
+        const uint32_t* slots16 = (gathered || c->run.slots_iter != t) ? (const uint32_t*)P.xsrc : (const uint32_t*)nullptr;
         if (c->F.xk == XK_ROWS && plds)
             hipLaunchKernelGGL(k_exch_resolve_rows<true>, dim3(1), dim3(XWG), resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap), c->stream, P, t,
                                (const double*)vals, slots16, (const uint32_t*)c->slots17, c->nan_flags);
@@ -1020,161 +1038,23 @@ void launch_resolve_p(Ctx* c, const KParams& P_in, int t, const double* gathered
     }
 }
 
-// settle the open end of the last iteration (no-op when nothing is open)
-// the exchange of iteration c->iter has been left to the next chain kernel, but something else needs it now
-void resolve_now(Ctx* c) {
-    if (!c->unresolved) return;
-    launch_resolve(c, c->iter, nullptr);
-    c->unresolved = false;
-}
-
-void flush(Ctx* c) {
-    if (c->rec_external) throw std::string("records are in the gather buffer: call smm_bgp_sharded_finish first");
-    if (c->unresolved && c->P.N < c->P.Ng) throw std::string("the exchange of the last iteration needs every shard's records: call smm_bgp_p2p_finish first");
-    if (!c->pending && !c->prev_open) return;
-    resolve_now(c);
-    const KParams& P = c->P;
-    const int flags = (c->prev_open ? F_CLOSE_PREV : 0) | (c->pending ? F_HAS_PENDING : 0);
-    hipLaunchKernelGGL(k_flush, dim3((P.N + 255) / 256), dim3(256), 0, c->stream, P, c->iter + 1, (const double*)c->rec[c->cur],
-                       c->rec[c->cur ^ 1], flags);
-    c->cur ^= 1;
-    c->pending = false;
-    c->prev_open = false;
-}
-
-void persist_repair(Ctx* c, int n_replay = -1);
-void p2p_enqueue(Ctx* c, int n_iters);
-// The ranks of a sharded run agree on what their launches of the persistent form ended with: every rank writes its error word into
-// every rank's window — {word, number of its last launch} — and reads its own window until all ranks' words of that launch are there
-// (the host side of a rendezvous every rank reaches: smm_sync / smm_bgp_p2p_finish behind the same steps).  The smallest word wins,
-// as it does among the chains of one device: the first failing iteration, the first failing chain of the population.
-unsigned long long p2p_agree_error(Ctx* c, unsigned long long e_local) {
-    const KParams& P = c->P;
-    const int G = P.p2p_G;
-    const PrWin WL = pr_win_layout(P.Ng, P.RW, G, persist_tiles_rank(c->F, c->P.N));
-    const uint32_t seq = c->pr_epoch;
-    for (int r = 0; r < G; ++r)
-        HIPCHK(hipMemcpy(P.p2p_win[r] + c->prw_off + WL.fin + 128 * (size_t)P.p2p_rank, &e_local, 8, hipMemcpyHostToDevice));
-    for (int r = 0; r < G; ++r)   // (the word is there before the number that says so)
-        HIPCHK(hipMemcpy(P.p2p_win[r] + c->prw_off + WL.fin + 128 * (size_t)P.p2p_rank + 8, &seq, 4, hipMemcpyHostToDevice));
-    std::vector<unsigned char> buf((size_t)128 * G);
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned long long e = e_local;
-    for (;;) {
-        HIPCHK(hipMemcpy(buf.data(), c->p2p_mine + c->prw_off + WL.fin, buf.size(), hipMemcpyDeviceToHost));
-        bool all = true;
-        e = e_local;
-        for (int r = 0; r < G; ++r) {
-            uint32_t s_r; unsigned long long e_r;
-            memcpy(&e_r, buf.data() + 128 * (size_t)r, 8); memcpy(&s_r, buf.data() + 128 * (size_t)r + 8, 4);
-            if (s_r != seq) { all = false; break; }
-            e = std::min(e, e_r);
-        }
-        if (all) {
-            // (word and number arrive by two copies and are read by one unfenced DMA: a number seen with the word of the launch before is
-            // possible in theory — ADVICE r5 —: every number is there now, so one more look holds every word that was written before its number)
-            HIPCHK(hipMemcpy(buf.data(), c->p2p_mine + c->prw_off + WL.fin, buf.size(), hipMemcpyDeviceToHost));
-            e = e_local;
-            for (int r = 0; r < G; ++r) { unsigned long long e_r; memcpy(&e_r, buf.data() + 128 * (size_t)r, 8); e = std::min(e, e_r); }
-            return e;
-        }
-        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(30)) throw std::string("sharded run: a rank did not report the end of its step within 30 s (is every rank calling smm_sync / smm_bgp_p2p_finish?)");
-        std::this_thread::sleep_for(std::chrono::microseconds(50));
-    }
-}
-// the second launch of the persistent form that gave up (its tiles not resident together: a masked or shared device; a cone that did not fit;
-// a state the form cannot walk): the form is off for this context from here on — said ONCE on stderr, since nothing else changes for the
-// caller but the speed (smm_get_persistent / smm_describe report it too)
-void persist_give_up(Ctx* c) {
-    if (!c->persist_broken)
-        fprintf(stderr, "libsmmhip: context %p (device %d, chains %d of %d): the persistent form gave up twice (iteration %d) and is OFF for this context; "
-                        "the per-iteration kernels run instead (same results, more launches). smm_get_persistent reports it.\n",
-                (void*)c, c->device, c->P.N, c->P.Ng, c->iter);
-    c->persist_broken = true;
-}
-// (an entry point hands the sticky failure to its caller)
-int told(Ctx* c) { c->failed_told = true; return c->failed; }
-int told(Ctx* c, int rc) { if (rc != SMM_OK && rc == c->failed) c->failed_told = true; return rc; }
-int check_device_error(Ctx* c) {
-    if (c->failed) return c->failed;   // err holds the message of the first failure
-    unsigned long long e = ERR_NONE;
-    HIPCHK(hipMemcpy(&e, c->P.err, sizeof e, hipMemcpyDeviceToHost));
-    if (c->F.persist_sh && c->snap_valid && !c->in_repair && c->p2p_mine) {
-        // launches of the persistent form ran on every rank: what one of them ended with concerns all (its tiles did not stop either)
-        const unsigned long long eg = p2p_agree_error(c, e);
-        if (eg != ERR_NONE) {
-            const int kind = (int)(eg & 3), it = (int)(eg >> 34);
-            if (kind == ERRK_FORM && ++c->persist_strikes >= 2) persist_give_up(c);
-            // a hard error (AlgoBGP.jl:341,409): every rank replays up to and including the failing iteration — which completes for all
-            // chains, as everywhere — and stands there; a time-out or a cone that did not fit: the whole step again, on the other forms
-            // (a hard error raised BEFORE the first of these launches — by a one-iteration launch ahead of them on the stream —: they saw the word at
-            // their entry and stored nothing; n = 0 puts the host's bookkeeping back to the snapshot and replays nothing)
-            persist_repair(c, (kind == ERRK_NO_DRAW || kind == ERRK_NEGATIVE) ? std::max(0, it - c->snap_iter) : -1);
-            HIPCHK(hipMemcpy(&e, c->P.err, sizeof e, hipMemcpyDeviceToHost));
-            if (kind == ERRK_NO_DRAW || kind == ERRK_NEGATIVE) e = std::min(e, eg);   // (the first failing chain of the POPULATION — maybe another rank's: every rank reports the same)
-        }
-        c->snap_valid = false;
-        if (eg == ERR_NONE) c->persist_proven = true;
-    } else if (e != ERR_NONE && c->snap_valid && !c->in_repair) {
-        // launches of the persistent kernel ran since the last check: their tiles do not stop at the failing iteration.  Back to the
-        // state before the first of them, and the same iterations again on the one-launch-per-iteration path, which does.
-        // (a tile gave up waiting, or a cone did not fit.  Once may be somebody else's doing — another context or process held compute
-        // units while the tiles wanted to be resident together —: the form is tried again; the second time it is off for the context)
-        if ((e & 3) != 3 && (int)(e >> 34) <= c->snap_iter) {
-            // ... unless the word was raised BEFORE the first of them, by a one-iteration launch ahead of them on the stream that nobody had
-            // looked at yet: they saw the word at their entry and stored nothing.  Nothing to replay — rolling back, clearing the word and
-            // running on LOST the error (tools/fuzz_errors.py, 2 of 600 cases) —: the host's bookkeeping back to the snapshot, the word stays
-            const unsigned long long keep = e;
-            persist_repair(c, 0);
-            HIPCHK(hipMemcpy(c->P.err, &keep, sizeof keep, hipMemcpyHostToDevice));
-            e = keep;
-        } else {
-            if ((e & 3) == 3 && ++c->persist_strikes >= 2) persist_give_up(c);
-            persist_repair(c);
-            HIPCHK(hipMemcpy(&e, c->P.err, sizeof e, hipMemcpyDeviceToHost));
-        }
-    }
-    if (!c->in_repair) {
-        if (e == ERR_NONE && c->snap_valid) c->persist_proven = true;   // launches of the persistent form came through: its tiles ARE resident together
-        c->snap_valid = false;
-    }
-    if (e == ERR_NONE) return SMM_OK;
-    const int kind = (int)(e & 3), chain = (int)((e >> 2) & 0xffffffffu), it = (int)(e >> 34);
-    char b[256];
-    int rc;
-    if (kind == ERRK_FORM) {
-        snprintf(b, sizeof b, "internal error: the exchange of iteration %d could not be resolved in the form chosen for it (chain %d)", it, chain + 1);
-        rc = SMM_ERR_HIP;
-    } else if (kind == ERRK_CAPACITY) {
-        snprintf(b, sizeof b, "values form of the sharded exchange: more than %d records between one pair of ranks (chain %d, iteration %d): "
-                 "use the record all-gather (smm_bgp_exchange_dev / smm_bgp_sharded_step)", c->a2a_cap, chain + 1, it);
-        rc = SMM_ERR_EXCHANGE_CAPACITY;
-    } else if (kind == ERRK_NEGATIVE) {
-        snprintf(b, sizeof b, "AlgoBGP assumes that your objective function returns a non-negative number "
-                 "(chain %d, iteration %d)", chain + 1, it);
-        rc = SMM_ERR_NEGATIVE_OBJECTIVE;
-    } else {
-        snprintf(b, sizeof b, "no draw in support after %d trials (chain %d, iteration %d): increase smpl_iters",
-                 c->P.user_n ? std::min(c->P.rb_tries, c->P.smpl_iters) : c->P.smpl_iters, chain + 1, it);
-        rc = SMM_ERR_NO_DRAW_IN_SUPPORT;
-    }
-    c->err = b;
-    // The reference aborts inside the failing iteration (AlgoBGP.jl:341,409).  Here that iteration completes for all chains
-    // and every later launch of the step sees the error word and stores nothing: the run stands at the failing iteration,
-    // its exchange is never applied, and the context refuses to go on until smm_set_state.
-    if (kind != ERRK_FORM && it >= 1 && it <= c->iter) {   // (kind 0, a block of the values form overflowed: the exchange of iteration `it` was not applied either)
-        c->iter = it;
-        c->pending = false; c->prev_open = false; c->unresolved = false; c->pending_ext = false; c->rec_external = false;
-        c->a2a_open = false; c->p2p_current = false;
-    }
-    c->failed = rc;
-    return rc;
-}
-
 int fail(Ctx* c, int code, const std::string& m) {
     if (c) c->err = m;
     else g_create_err = m;
     return code;
+}
+
+// the frame of every entry point that takes a context and can throw: body(c) returns SMM_OK or what fail() (or an early return) gave;
+// its checks that do not throw stand inside it, in their order
+template <class Body>
+int api_call(void* ctx, bool args_given, Body body) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c || !args_given) return SMM_ERR_INVALID_ARG;
+    try {
+        return body(c);
+    } catch (const std::string& m) {
+        return fail(c, SMM_ERR_HIP, m);
+    }
 }
 
 // temporary device buffer of one call (freed on every exit path)
@@ -1211,7 +1091,7 @@ void launch_p2p_push(Ctx* c, int t, const double* rec_src, bool ll) {
 void launch_p2p_wait(Ctx* c) {
     KParams P = c->P;
     P.p2p_want = (unsigned long long)p2p_units(P.N) * c->p2p_seq;
-    hipLaunchKernelGGL(k_p2p_wait, dim3(1), dim3(64), 0, c->stream, P, c->iter);
+    hipLaunchKernelGGL(k_p2p_wait, dim3(1), dim3(64), 0, c->stream, P, c->run.iter);
     c->p2p_unwaited = false;
 }
 // inline form: everybody's records and values after iteration t, out of their self-validating form into this rank's plain arrays
@@ -1290,350 +1170,6 @@ void launch_persist(Ctx* c, const PersistKernel& K, PersistArgs A) {
     else if (K.mfn) HIPCHK(hipModuleLaunchKernel(K.mfn, K.grid.x, 1, 1, K.block.x, 1, 1, (unsigned)K.smem, c->stream, args, nullptr));
     else if (c->kev0) HIPCHK(hipExtLaunchKernel(K.fn, K.grid, K.block, args, K.smem, c->stream, c->kev0, c->kev1, 0));
     else HIPCHK(hipLaunchKernel(K.fn, K.grid, K.block, args, K.smem, c->stream));
-}
-// can the iterations from c->iter + 1 on run as one launch of it?  At least two (a single iteration is the ordinary kernel's), behind
-// an iteration some chain kernel has completed (the launch continues from the plain state blocks: no first iteration, no uploaded
-// state, no exchange applied by the three-phase calls), and an exchange left to "the next chain kernel" must have its plan in the
-// current window together with this iteration's.
-bool persist_usable(const Ctx* c, int n_left) {
-    if (!(c->F.persist != PERSIST_NONE && c->persist_on && !c->persist_broken && !c->in_repair && !c->nan_values && n_left >= 2 && !c->ext_rec_in && !c->ext_rec_out &&
-          !c->ext_vals_out && !c->rec_external && c->P.N == c->P.Ng))
-        return false;
-    if (c->iter < 1 || !c->prev_open || c->exch_done || (c->pending && !c->unresolved)) return false;
-    const int t0 = c->iter + 1;
-    // (the locally numbered form starts a new plan window at the pending exchange's iteration instead: launch_chain_persist)
-    if (c->F.persist != PERSIST_LOC && c->F.persist != PERSIST_TILE && c->unresolved && !(t0 - 1 >= c->plan_t0 && t0 + 1 < c->plan_t0 + c->plan_w)) return false;
-    return true;
-}
-// ... as a shard (smm_bgp_p2p_step): from the p2p state — the records after iteration `iter` in the windows, its exchange not resolved
-// yet — or behind a launch of its own; the first iteration of a run, the iteration behind a settled state are the per-iteration forms'
-bool persist_sh_usable(const Ctx* c, int n_left) {
-    // (NOT c->nan_values: that flag is this shard's own — smm_set_state saw a NaN among ITS values — and the form must be chosen from what every
-    // rank knows, or one rank would take the per-iteration kernels while its peers wait at the launches' start barrier.  The launch reports such a
-    // state itself — kind 3 at its first iteration, smm_chain_persist_loc.hpp —, the ranks agree on the word and replay the step on the other forms)
-    if (!(c->F.persist_sh && c->persist_on && !c->persist_broken && !c->in_repair && n_left >= 2 && c->p2p_mine)) return false;
-    if (c->p2p_ranks_here * persist_tiles_rank(c->F, c->P.N) > c->F.max_tiles) return false;   // (ranks sharing this device: not resident together)
-    if (c->iter < 1 || !c->prev_open || c->exch_done || c->a2a_open) return false;
-    if (c->p2p_current) return c->rec_external && (c->pending_ext || !exchange_active(c, c->iter));
-    return !c->rec_external && (c->unresolved || !c->pending);
-}
-// the state a failed launch of the persistent kernel is rolled back to (device copies on the stream, before anything of the step runs)
-void persist_snapshot(Ctx* c) {
-    const KParams& P = c->P;
-    const size_t N = P.N;
-    HIPCHK(hipMemcpyAsync(c->snap_cs, P.cs, N * CSW * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->snap_rec, c->rec[c->cur], N * P.RW * 8, hipMemcpyDeviceToDevice, c->stream));
-    for (int b = 0; b < 2; ++b) {
-        HIPCHK(hipMemcpyAsync(c->snap_vals[b], c->vals_buf[b], (N + 4) * 8, hipMemcpyDeviceToDevice, c->stream));
-        if (c->slot8_buf[b]) HIPCHK(hipMemcpyAsync(c->snap_slot8[b], c->slot8_buf[b], (N + 4 + 128) * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
-    HIPCHK(hipMemcpyAsync(c->snap_xres, P.xres, (size_t)P.Ng * 8, hipMemcpyDeviceToDevice, c->stream));
-    c->snap_iter = c->iter; c->snap_cur = c->cur; c->snap_slots_iter = c->slots_iter;
-    c->snap_pending = c->pending; c->snap_prev_open = c->prev_open; c->snap_unresolved = c->unresolved; c->snap_exch_done = c->exch_done;
-    c->snap_valid = true;
-}
-// the argument block of a launch of the persistent kernel over iterations t0 .. t1 (pregen: the randomness comes from the window's blocks;
-// tmo: ticks a spin may last)
-PersistArgs persist_args(const Ctx* c, int t0, int t1, bool pregen, unsigned long long tmo) {
-    const KParams& P = c->P;
-    const bool sh = c->F.persist_sh;
-    const int G = sh ? P.p2p_G : 1;
-    const PrWin WL = pr_win_layout(P.Ng, P.RW, G, persist_tiles_rank(c->F, P.N));
-    PersistArgs A{};
-    A.cone_hdr = P.cone_hdr; A.cone_pairs = P.cone_pairs; A.cone_gather = P.cone_gather; A.cone_ok = P.cone_ok;
-    if (sh) {
-        for (int r = 0; r < G; ++r) A.win[r] = P.p2p_win[r] + c->prw_off;
-        A.self = c->p2p_mine + c->prw_off;
-    } else { A.win[0] = c->prw; A.self = c->prw; }
-    A.o_ctl = WL.ctl; A.o_arrive = WL.arrive; A.o_progress = WL.progress; A.o_slot = WL.slot; A.o_rec = WL.rec;
-    A.cs = P.cs; A.rec_in = c->rec[c->cur]; A.rec_out = c->rec[c->cur ^ 1]; A.vals_out = P.vals_out; A.slot8_out = P.slot8_out; A.walk_flags = P.walk_flags;
-    A.hrec = P.hrec; A.err = P.err; A.ts = P.ts;
-    A.Z = P.Z; A.lb = P.lb; A.ub = P.ub; A.mom = P.mom; A.w = P.w; A.objp = P.objp; A.dense_Bf = P.dense_Bf; A.dense_Af = P.dense_Af; A.dense_A2f = P.dense_A2f;
-    A.rb = pregen ? P.rb : nullptr;
-    A.mi_g = P.min_improve_g;
-    A.N = P.N; A.Ng = P.Ng; A.np = P.np; A.nm = P.nm; A.ns = P.ns; A.zstride = P.zstride; A.RW = P.RW; A.HW = P.HW; A.RBW = P.RBW; A.dense_nOt = P.dense_nOt;
-    A.batch_size = P.batch_size; A.failbox = (P.obj == SMM_OBJ_NORM_FAILBOX && P.objp) ? 1 : 0;
-    A.G = G; A.rank = sh ? P.p2p_rank : 0; A.offset = P.offset;
-    A.plan_t0 = P.plan_t0; A.exch_from = c->exchange_from; A.sigma_update_steps = P.sigma_update_steps; A.smpl_iters = P.smpl_iters; A.t0 = t0; A.t1 = t1;
-    A.rb_t0 = P.rb_t0; A.rb_tries = P.rb_tries; A.user_n = P.user_n;
-    A.ring_k = c->H.pr_ring_k; A.slow_tile = c->H.pr_slow_tile; A.slow_ticks = c->H.pr_slow_ticks; A.walk_first = c->unresolved ? 1 : 0;
-    A.slow_read = c->H.pr_slow_read;
-    A.tables_local = c->F.persist_sh_big ? 1 : 0; A.unit_sh = P.lean_unit == 16 ? 4 : (P.lean_unit == 8 ? 3 : 2); A.scout_after = P.scout_after; A.scout_gl = P.scout_gl;
-    A.u_lanes = c->u_lanes; A.n_udata = c->n_objp;
-    A.chol_L = P.chol_L; A.chol_per_chain = P.chol_per_chain;
-    A.epoch = c->pr_epoch; A.sigma_adjust_by = P.sigma_adjust_by; A.thr = P.mi_value; A.seed = P.seed; A.tmo = tmo;
-    return A;
-}
-// iterations c->iter + 1 .. as ONE launch, as far as the look-ahead windows reach; returns how many it covers (0: not this time)
-int launch_chain_persist(Ctx* c, int n_left) {
-    const int t0 = c->iter + 1;
-    // (k_chain_persist_norm and _gen draw in the kernel unless tables are injected)
-    // (k_chain_persist_tile too, since round 5: its 512 lanes draw the next iteration's randomness behind the publication, where the tile waits for
-    // its peers' stores anyway — k_pregen_rng was 2.2 us per iteration of C5 on the main stream)
-    const bool pregen = (c->F.persist == PERSIST_GEN || c->F.persist == PERSIST_TILE) ? (c->P.user_ntab || c->P.user_utab) : !(c->F.norm_fast && !c->P.user_ntab && !c->P.user_utab);
-    if ((c->F.persist == PERSIST_LOC || c->F.persist == PERSIST_TILE) && c->unresolved && !(t0 - 1 >= c->plan_t0 && t0 + 1 < c->plan_t0 + c->plan_w)) {
-        // the pending exchange's plan is not in a window that also reaches past this iteration: a new window from ITS iteration on (one
-        // iteration planned twice per window; no per-iteration launch, no stand-alone resolution at the windows' ends)
-        c->plan_w = 0;
-        ensure_windows(c, t0 - 1, pregen);
-    } else if (!c->unresolved) ensure_windows(c, t0, pregen);   // (with an exchange pending the window holds its plan and this iteration's: persist_usable)
-    if (pregen && !(t0 >= c->rng_t0 && t0 < c->rng_t0 + c->rng_w)) ensure_windows(c, t0);
-    int t1 = std::min(c->iter + n_left, c->plan_t0 + c->plan_w - 1);
-    if (pregen) t1 = std::min(t1, c->rng_t0 + c->rng_w - 1);
-    t1 = std::min(t1, t0 + PR_MAX_ITERS - 1);
-    if (t1 - t0 + 1 < 2) return 0;
-    if (!c->snap_valid) persist_snapshot(c);
-    ++c->pr_epoch;
-    if ((c->pr_epoch & 0x7fu) == 0u) {   // the slot tags' epoch bits start over: nothing older may look current
-        // (a shard zeroes its own window's ring: its peers store into it only behind the launch's start barrier)
-        const PrWin WL = pr_win_layout(c->P.Ng, c->P.RW, c->F.persist_sh ? c->P.p2p_G : 1, persist_tiles_rank(c->F, c->P.N));
-        unsigned char* base = c->F.persist_sh ? c->p2p_mine + c->prw_off : c->prw;
-        HIPCHK(hipMemsetAsync(base + WL.slot, 0, WL.total - WL.slot, c->stream));
-    }
-    KParams& P = c->P;
-    P.pr_epoch = c->pr_epoch;
-    point_values(c, P, t0 - 1, t1);   // (nothing is read from the value arrays: the last iteration writes them)
-    // (a spin of the form may last 4 s — a peer is gone, not late — once a launch of this context has come through; until then a
-    // tenth of that: tiles that are not resident together, a masked or partitioned device, must not look like a hang)
-    // (a shard waits for its PEERS' launches at the start barrier: processes that start a second apart are late, not gone — 4 s from the start)
-    const unsigned long long tmo = (c->persist_proven || c->F.persist_sh) ? P2P_TIMEOUT_TICKS : PERSIST_TMO_FIRST;
-    launch_persist(c, persist_kernel(c, c->F), persist_args(c, t0, t1, pregen, tmo));
-    c->cur ^= 1;
-    ++c->persist_launches;
-    return t1 - t0 + 1;
-}
-
-// n_iters iterations onto the stream (smm_bgp_step_async, and persist_repair with the persistent kernel off)
-void enqueue_iterations(Ctx* c, int n_iters) {
-    int slot = 0;   // profiling: events of this launch
-    for (int it = 0; it < n_iters;) {
-        const int t = c->iter + 1;
-        int n = 0;
-        if (persist_usable(c, n_iters - it)) {
-            if (c->profiling == 1) HIPCHK(hipEventRecord(c->pev[4 * slot], c->stream));
-            if (c->profiling == 2) { c->kev0 = c->pev[4 * slot]; c->kev1 = c->pev[4 * slot + 1]; }
-            n = launch_chain_persist(c, n_iters - it);
-            c->kev0 = c->kev1 = nullptr;
-        }
-        if (n > 0) {
-            if (c->profiling == 1) { for (int e = 1; e < 4; ++e) HIPCHK(hipEventRecord(c->pev[4 * slot + e], c->stream)); }
-            if (c->profiling) c->pev_exch[slot] = 0;
-            ++slot;
-            const int t1 = c->iter + n;
-            c->prev_open = true;
-            c->pending = false; c->unresolved = false;
-            if (exchange_active(c, t1)) { c->unresolved = true; c->pending = true; }   // resolved in the prologue of the next chain kernel (or by resolve_now)
-            c->iter = t1; c->exch_done = false;
-            it += n;
-            continue;
-        }
-        // an exchange left to this chain kernel needs its plan: resolve it now if the plan window is about to move on
-        if (c->unresolved && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w) && !plan_ahead_covers(c, t)) resolve_now(c);
-        // ... or if this chain kernel cannot walk (a user objective's launches): the resolution was only put off in case the persistent
-        // kernel came next (defer_resolve)
-        if (c->unresolved && c->F.defer_resolve && !c->F.inline_walk) resolve_now(c);
-        ensure_windows(c, t);
-        const int flags = (c->prev_open ? F_CLOSE_PREV : 0) | (c->pending ? F_HAS_PENDING : 0) | (c->unresolved ? F_WALK_INLINE : 0);
-        // (populations of the level walk: the chain kernel and the stand-alone resolution take the profiling events themselves)
-        const bool kscoped = c->profiling == 2 && c->F.plan == PLAN_LDS && c->P.Ng <= XLVL_MAX && !c->H.dataflow && c->H.lvl_wg == 1024;
-        if (c->profiling && !kscoped) HIPCHK(hipEventRecord(c->pev[4 * slot], c->stream));
-        if (kscoped) { c->kev0 = c->pev[4 * slot]; c->kev1 = c->pev[4 * slot + 1]; }
-        launch_chain_iter(c, t, flags);
-        c->kev0 = c->kev1 = nullptr;
-        if (c->profiling && !kscoped) HIPCHK(hipEventRecord(c->pev[4 * slot + 1], c->stream));
-        c->prev_open = true;
-        c->pending = false;
-        if (c->profiling) c->pev_exch[slot] = 0;
-        c->unresolved = false;
-        if (exchange_active(c, t)) {
-            const bool cone_next = c->F.cone_big && !c->nan_values && !c->ext_rec_in && !c->ext_rec_out && !c->ext_vals_out && !c->rec_external &&
-                                   t >= c->plan_t0 && t < c->plan_t0 + c->plan_w && c->cone_big_ok[(size_t)(t - c->plan_t0)] != 0u;
-            if (cone_next || (c->F.inline_walk && !(c->F.gen_keys && (c->deep_plan || c->nan_values))) ||
-                (c->F.defer_resolve && c->persist_on && !c->persist_broken && !c->in_repair && !c->nan_values)) {   // (the key form has no second walk to fall back to)
-                c->unresolved = true;   // resolved in the prologue of the next chain kernel (or by resolve_now)
-            } else {
-                if (kscoped) { c->kev0 = c->pev[4 * slot + 2]; c->kev1 = c->pev[4 * slot + 3]; c->pev_exch[slot] = 1; }
-                launch_resolve(c, t, (c->F.plan == PLAN_LDS || c->F.xk == XK_ROWS || c->F.xk == XK_KEY) ? nullptr : c->rec[c->cur]);
-                c->kev0 = c->kev1 = nullptr;
-            }
-            c->pending = true;
-        }
-        if (c->profiling && !kscoped) { HIPCHK(hipEventRecord(c->pev[4 * slot + 2], c->stream)); HIPCHK(hipEventRecord(c->pev[4 * slot + 3], c->stream)); }
-        c->iter = t; c->exch_done = false;
-        ++slot; ++it;
-    }
-    if (c->profiling) c->pev_iters = slot;
-}
-
-// A launch of the persistent kernel ended with the error word set (a hard error of the algorithm, AlgoBGP.jl:341,409 — or a tile gave
-// up waiting).  Its tiles do not stop at the failing iteration, so: the state of before (persist_snapshot), the history rows of the
-// iterations since filled as the constructor fills them, the error word cleared, and the same iterations again, one launch each —
-// that path stops at the failing iteration with the documented state (include/smmhip.h), or runs through if the failure was the form's.
-void persist_repair(Ctx* c, int n_replay) {
-    KParams& P = c->P;
-    const size_t N = P.N;
-    const int n = n_replay >= 0 ? std::min(n_replay, c->iter - c->snap_iter) : c->iter - c->snap_iter;
-    c->in_repair = true;
-    ++c->persist_repairs;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(P.cs, c->snap_cs, N * CSW * 8, hipMemcpyDeviceToDevice));
-    HIPCHK(hipMemcpy(c->rec[c->snap_cur], c->snap_rec, N * P.RW * 8, hipMemcpyDeviceToDevice));
-    for (int b = 0; b < 2; ++b) {
-        HIPCHK(hipMemcpy(c->vals_buf[b], c->snap_vals[b], (N + 4) * 8, hipMemcpyDeviceToDevice));
-        if (c->slot8_buf[b]) HIPCHK(hipMemcpy(c->slot8_buf[b], c->snap_slot8[b], (N + 4 + 128) * 8, hipMemcpyDeviceToDevice));
-    }
-    HIPCHK(hipMemcpy(P.xres, c->snap_xres, (size_t)P.Ng * 8, hipMemcpyDeviceToDevice));
-    // (an exchanged chain's row of iteration snap_iter may have been rewritten by the first launch's prologue: the replay rewrites it identically)
-    for (int t = c->snap_iter; t < c->iter; ++t)
-        HIPCHK(hipMemcpy(P.hrec + (size_t)t * N * P.HW, c->hist_fill, N * P.HW * 8, hipMemcpyDeviceToDevice));
-    const unsigned long long e = ERR_NONE;
-    HIPCHK(hipMemcpy(P.err, &e, 8, hipMemcpyHostToDevice));
-    c->iter = c->snap_iter; c->cur = c->snap_cur; c->slots_iter = c->snap_slots_iter;
-    c->pending = c->snap_pending; c->prev_open = c->snap_prev_open; c->unresolved = c->snap_unresolved; c->exch_done = c->snap_exch_done;
-    c->plan_w = 0; c->rng_w = 0; c->ps[0].w = c->ps[1].w = 0;   // (the windows are rebuilt: cheap, and nothing assumes where the failed run left them)
-    // ... with the exchange of the snapshot's iteration still to be applied, its plan must be in the window the replay starts with: the
-    // failed launches may have moved the window on (a step across a window boundary), and what enqueue_iterations does for an
-    // iteration outside the window — resolve the pending exchange from "the window that just ended" — would read another window's plan
-    if (c->unresolved) ensure_windows(c, c->iter);
-    const int prof = c->profiling;
-    c->profiling = 0;
-    if (P.N < P.Ng) {   // a shard: the same iterations through the windows, one (or two) launches each — every rank does (smm_sync agrees on the error first)
-        c->rec_external = false; c->pending_ext = false; c->p2p_current = false; c->p2p_unwaited = false;
-        p2p_enqueue(c, n);
-    } else enqueue_iterations(c, n);
-    c->profiling = prof;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->in_repair = false;
-    c->snap_valid = false;
-}
-// calls that read or change the run's state other than by stepping: first make sure that what stands there is final (see persist_repair)
-void settle_persist(Ctx* c) {
-    if (!c->snap_valid) return;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)check_device_error(c);
-}
-
-// ---- a shard between its two states (smm_bgp_p2p_step) ----
-// "p2p": the records after iteration `iter` are in the ranks' windows (rec_external), the exchange of `iter` not resolved yet (pending_ext);
-// "plain": they are in the context's own array, as the persistent form reads and leaves them (unresolved: the exchange still pending).
-// plain -> p2p: a publication.  With the exchange of `iter` still pending it travels as it is — a shard cannot settle it alone.
-void p2p_publish(Ctx* c) {
-    if (c->p2p_current) return;
-    const bool carry = c->unresolved && c->P.N < c->P.Ng;
-    if (!carry) flush(c);
-    // the form is decided from what EVERY rank knows (population, objective, thresholds): a rank that looked at its own shard's
-    // values here (an uploaded state with a NaN) could choose differently from its peers, and each side would wait for words the
-    // other never sends.  A NaN in any shard reaches every window with the publication (in the slot words themselves, and the NaN word
-    // tagged with the epoch): the rows form resolves such an iteration on the exact values inside its launch, the inline form
-    // (N_global <= 8192) reports it — on every rank, in the same iteration (include/smmhip.h).
-    c->p2p_mode_inline = c->p2p_inline || c->p2p_rows;
-    c->P.p2p_epoch += 1;   // (a new generation of tags: words of an earlier publication are nobody's any more)
-    launch_p2p_push(c, c->iter, c->rec[c->cur], c->p2p_mode_inline);
-    c->p2p_current = true;
-    c->pending_ext = false;
-    if (carry) { c->pending_ext = true; c->rec_external = true; c->pending = false; c->unresolved = false; }
-}
-// p2p -> plain: this rank's own records after iteration `iter` out of its window into the context's array (its own stores: complete)
-void p2p_to_plain(Ctx* c) {
-    if (!c->p2p_current) return;
-    const KParams& P = c->P;
-    const P2PLayout L = p2p_layout(P.Ng, P.RW);
-    if (c->p2p_mode_inline)
-        hipLaunchKernelGGL(k_p2p_own_records, dim3((unsigned)((P.N * P.RW + 255) / 256)), dim3(256), 0, c->stream, P, c->iter, c->rec[c->cur]);
-    else
-        HIPCHK(hipMemcpyAsync(c->rec[c->cur], (const double*)(c->p2p_mine + L.rec[c->iter & 1]) + (size_t)P.offset * P.RW, (size_t)P.N * P.RW * 8,
-                              hipMemcpyDeviceToDevice, c->stream));
-    c->unresolved = c->pending_ext; c->pending = c->pending_ext;
-    c->pending_ext = false; c->rec_external = false; c->p2p_current = false; c->p2p_unwaited = false;
-}
-
-// n iterations of a shard onto the stream (smm_bgp_p2p_step; persist_repair with the persistent form off)
-void p2p_enqueue(Ctx* c, int n_iters) {
-    KParams& P = c->P;
-    const P2PLayout L = p2p_layout(P.Ng, P.RW);
-    int slot = 0;   // profiling: events of this launch
-    for (int it = 0; it < n_iters; ++it) {
-        if (persist_sh_usable(c, n_iters - it)) {   // as many of the remaining iterations as the look-ahead windows hold, in ONE launch
-            p2p_to_plain(c);
-            if (c->profiling == 2) { c->kev0 = c->pev[4 * slot]; c->kev1 = c->pev[4 * slot + 1]; }
-            const int n = launch_chain_persist(c, n_iters - it);
-            c->kev0 = c->kev1 = nullptr;
-            if (n > 0) {
-                const int t1 = c->iter + n;
-                c->prev_open = true; c->pending = false; c->unresolved = false;
-                if (exchange_active(c, t1)) { c->unresolved = true; c->pending = true; }
-                c->iter = t1; c->exch_done = false;
-                it += n - 1; ++slot;
-                continue;
-            }
-        }
-        p2p_publish(c);
-        const int t = c->iter + 1;
-        const bool prof = c->profiling == 2;
-        int flags = (c->prev_open ? F_CLOSE_PREV : 0) | F_GLOBAL_REC;
-        if (c->p2p_mode_inline) {
-            if (c->pending_ext) {
-                flags |= F_HAS_PENDING;
-                // the walk of iteration t-1 needs that iteration's plan: where the plan window is about to move on, the
-                // exchange is resolved by the stand-alone kernel first (once per window of 256 iterations)
-                if (c->p2p_rows) {
-                    if (prof) { c->kev0 = c->pev[4 * slot + 2]; c->kev1 = c->pev[4 * slot + 3]; c->pev_exch[slot] = 1; }
-                    launch_resolve_rows_window(c, t - 1);
-                    c->kev0 = c->kev1 = nullptr;
-#ifdef SMM_TEST_HOOKS
-                    if (c->H.rows_win_check) {   // the same exchange through the unpacked values and the plain kernels
-                        std::vector<unsigned long long> a((size_t)P.Ng), b((size_t)P.Ng);
-                        HIPCHK(hipStreamSynchronize(c->stream));
-                        HIPCHK(hipMemcpy(a.data(), P.xres, a.size() * 8, hipMemcpyDeviceToHost));
-                        launch_p2p_unpack(c, t - 1);
-                        launch_resolve_window(c, t - 1);
-                        HIPCHK(hipStreamSynchronize(c->stream));
-                        HIPCHK(hipMemcpy(b.data(), P.xres, b.size() * 8, hipMemcpyDeviceToHost));
-                        int bad = 0;
-                        for (int g = 0; g < P.Ng; ++g)
-                            if (a[g] != b[g] && bad++ < 8) fprintf(stderr, "rows window check: iteration %d chain %d: %llx != %llx\n", t - 1, g, a[g], b[g]);
-                        fprintf(stderr, "rows window check: iteration %d: %d of %d differ\n", t - 1, bad, P.Ng);
-                    }
-#endif
-                } else if (t >= c->plan_t0 && t < c->plan_t0 + c->plan_w) flags |= F_WALK_INLINE;
-                else {
-                    launch_p2p_unpack(c, t - 1);
-                    launch_resolve_window(c, t - 1);
-                }
-            }
-            ensure_windows(c, t);
-            if (prof) { c->kev0 = c->pev[4 * slot]; c->kev1 = c->pev[4 * slot + 1]; }
-            launch_chain_iter_norm_p2p(c, t, flags);
-            c->kev0 = c->kev1 = nullptr;
-        } else {
-            if (c->pending_ext) {   // exchangeMoves! of iteration t-1 (before its plan window can move on)
-                if (c->p2p_unwaited) launch_p2p_wait(c);
-                if (prof && c->F.xk == XK_LEAN) { c->kev0 = c->pev[4 * slot + 2]; c->kev1 = c->pev[4 * slot + 3]; c->pev_exch[slot] = 1; }
-                launch_resolve_window(c, t - 1);
-                c->kev0 = c->kev1 = nullptr;
-                flags |= F_HAS_PENDING;
-            }
-            ensure_windows(c, t);
-            c->ext_rec_in = (const double*)(c->p2p_mine + L.rec[(t - 1) & 1]);
-            c->ext_rec_out = (double*)(c->p2p_mine + L.rec[t & 1]) + (size_t)P.offset * P.RW;
-            c->ext_vals_out = (double*)(c->p2p_mine + L.val[t & 1]) + P.offset;
-            if (prof) { c->kev0 = c->pev[4 * slot]; c->kev1 = c->pev[4 * slot + 1]; }
-            launch_chain_iter(c, t, flags);
-            c->kev0 = c->kev1 = nullptr;
-            c->ext_rec_in = nullptr; c->ext_rec_out = nullptr; c->ext_vals_out = nullptr;
-            launch_p2p_push(c, t, nullptr, false);
-        }
-        c->prev_open = true;
-        c->pending = false;
-        c->rec_external = true;
-        c->pending_ext = exchange_active(c, t);
-        c->iter = t; c->exch_done = false;
-        ++slot;
-    }
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipGetLastError());
-    if (c->profiling == 2) c->pev_iters = slot;
 }
 
 // ---- the forms of a context (smm_ctx_create) ----
@@ -1900,9 +1436,15 @@ void alloc_persist(Ctx* c) {
     HIPCHK(hipMemcpy(c->hist_fill, P.hrec, N * P.HW * 8, hipMemcpyDeviceToDevice));   // (a row of the constructor's fill)
 }
 
+}  // namespace
+
+#include "smm_run_host.hpp"
+
+namespace {
+
 // --- the history readers (smm_get_history, smm_get_state); the reducers built on these two are in smm_reducers_host.hpp ----------------
 
-// a reader's prelude: the iterations enqueued so far settled (a repair may move c->iter), flushed and finished
+// a reader's prelude: the iterations enqueued so far settled (a repair may move c->run.iter), flushed and finished
 void reader_prelude(Ctx* c) {
     HIPCHK(hipSetDevice(c->device));
     settle_persist(c);
@@ -1912,7 +1454,7 @@ void reader_prelude(Ctx* c) {
 
 // a reducer's window [t0, t1), checked after the prelude
 int check_window(Ctx* c, int t0, int t1) {
-    if (t0 < 0 || t1 < t0 || t1 > c->iter) return fail(c, SMM_ERR_INVALID_ARG, "window must satisfy 0 <= t0 <= t1 <= completed iterations");
+    if (t0 < 0 || t1 < t0 || t1 > c->run.iter) return fail(c, SMM_ERR_INVALID_ARG, "window must satisfy 0 <= t0 <= t1 <= completed iterations");
     return SMM_OK;
 }
 
@@ -2403,499 +1945,6 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
 
 void* smm_stream(void* ctx) { return ctx ? (void*)((Ctx*)ctx)->stream : nullptr; }
 
-int smm_sync(void* ctx) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return SMM_ERR_INVALID_ARG;
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->pending_timing) {
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-            c->timing.step_ms = ms;
-            c->pending_timing = false;
-            c->timing.iter_kernel_ms = 0.0;
-            c->timing.exch_kernel_ms = 0.0;
-            c->timing.null_bracket_ms = 0.0;
-            for (int i = 0; i < c->pev_iters; ++i) {
-                float a = 0.f, b = 0.f, n = 0.f;
-                HIPCHK(hipEventElapsedTime(&a, c->pev[4 * i], c->pev[4 * i + 1]));
-                if (c->profiling == 2) {
-                    if (c->pev_exch[i]) HIPCHK(hipEventElapsedTime(&b, c->pev[4 * i + 2], c->pev[4 * i + 3]));
-                } else {
-                    HIPCHK(hipEventElapsedTime(&b, c->pev[4 * i + 1], c->pev[4 * i + 2]));
-                    HIPCHK(hipEventElapsedTime(&n, c->pev[4 * i + 2], c->pev[4 * i + 3]));
-                }
-                c->timing.iter_kernel_ms += a;
-                c->timing.exch_kernel_ms += b;
-                c->timing.null_bracket_ms += n;
-            }
-            c->pev_iters = 0;
-        }
-        return told(c, check_device_error(c));
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-}
-
-int smm_bgp_step_async(void* ctx, int32_t n_iters) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || n_iters < 0) return SMM_ERR_INVALID_ARG;
-    if (c->failed) return told(c);
-    if (c->P.N != c->P.Ng) return fail(c, SMM_ERR_STATE, "smm_bgp_step needs a single shard (N == N_global); use the sharded calls");
-    if (c->iter + n_iters > c->P.T) return fail(c, SMM_ERR_MAXITER, "step beyond maxiter (history capacity)");
-    if (c->rec_external) return fail(c, SMM_ERR_STATE, "records are in the gather buffer: call smm_bgp_sharded_finish first");
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        if (c->profiling) {
-            while ((int)c->pev.size() < 4 * n_iters) {
-                hipEvent_t e;
-                HIPCHK(hipEventCreate(&e));
-                c->pev.push_back(e);
-            }
-            c->pev_exch.assign((size_t)n_iters, 0);
-        }
-        c->pev_iters = 0;
-        HIPCHK(hipEventRecord(c->ev0, c->stream));
-        enqueue_iterations(c, n_iters);
-        HIPCHK(hipEventRecord(c->ev1, c->stream));
-        HIPCHK(hipGetLastError());
-        c->pending_timing = true;
-        c->timing.iters = n_iters;
-        c->timing.chain_evals = (int64_t)n_iters * c->P.N;
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
-int smm_bgp_step(void* ctx, int32_t n_iters) {
-    const int rc = smm_bgp_step_async(ctx, n_iters);
-    if (rc != SMM_OK) return rc;
-    return smm_sync(ctx);
-}
-
-int smm_bgp_local_step(void* ctx) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return SMM_ERR_INVALID_ARG;
-    if (c->failed) return told(c);
-    if (c->rec_external) return fail(c, SMM_ERR_STATE, "records are in the gather buffer: call smm_bgp_sharded_finish first");
-    if (c->a2a_open) return fail(c, SMM_ERR_STATE, "smm_bgp_a2a_pack_dev without smm_bgp_a2a_apply_dev: the exchange of this iteration would be dropped");
-    if (c->iter + 1 > c->P.T) return fail(c, SMM_ERR_MAXITER, "step beyond maxiter (history capacity)");
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        if (c->failed) return told(c);
-        const int t = c->iter + 1;
-        // smm_bgp_step leaves the exchange of its last iteration to the next chain kernel (inline walk): the three-phase
-        // form reads P.xres, so resolve it now (local_step after step read an unresolved xres)
-        resolve_now(c);
-        ensure_windows(c, t);
-        const int flags = (c->prev_open ? F_CLOSE_PREV : 0) | (c->pending ? F_HAS_PENDING : 0);
-        launch_chain_iter(c, t, flags);
-        HIPCHK(hipGetLastError());
-        c->prev_open = true;
-        c->pending = false;
-        c->iter = t; c->exch_done = false;
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
-// Sharded iteration in two enqueues (instead of local_step / export / exchange = five): the exchange of the previous
-// iteration is resolved from gathered_prev, the chain kernel takes every chain's continuation record (its own or the
-// donor's) straight from gathered_prev and writes the new records into this shard's slice of gathered_next.
-int smm_bgp_sharded_step(void* ctx, const void* gathered_prev_dev, void* gathered_next_dev) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !gathered_next_dev) return SMM_ERR_INVALID_ARG;
-    if (c->failed) return told(c);
-    if (c->iter + 1 > c->P.T) return fail(c, SMM_ERR_MAXITER, "step beyond maxiter (history capacity)");
-    if (c->rec_external && !gathered_prev_dev) return fail(c, SMM_ERR_INVALID_ARG, "gathered_prev required: the last records live there");
-    if (c->unresolved) return fail(c, SMM_ERR_STATE, "mixing smm_bgp_step and smm_bgp_sharded_step without a flush");
-    if (c && c->p2p_current) return fail(c, SMM_ERR_STATE, "the records of the last iteration are in the p2p windows: call smm_bgp_p2p_finish first");
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        if (c->failed) return told(c);
-        const int t = c->iter + 1;
-        const KParams& P = c->P;
-        int flags = (c->prev_open ? F_CLOSE_PREV : 0);
-        // profiling mode 2: this call is one more iteration of the "step" smm_sync sums up (the kernels' own begin/end stamps)
-        const bool prof = c->profiling == 2;
-        const int it = c->pev_iters;
-        if (prof) {
-            while ((int)c->pev.size() < 4 * (it + 1)) {
-                hipEvent_t e;
-                HIPCHK(hipEventCreate(&e));
-                c->pev.push_back(e);
-            }
-            c->pev_exch.resize((size_t)it + 1, 0);
-            c->pev_exch[it] = 0;
-            if (it == 0) HIPCHK(hipEventRecord(c->ev0, c->stream));
-        }
-        if (c->rec_external) {
-            if (c->pending_ext) {   // exchangeMoves! of iteration t-1 over the gathered records (before its plan window can move on)
-                if (prof && c->F.xk == XK_LEAN) { c->kev0 = c->pev[4 * it + 2]; c->kev1 = c->pev[4 * it + 3]; c->pev_exch[it] = 1; }
-                launch_resolve(c, t - 1, (const double*)gathered_prev_dev);
-                c->kev0 = c->kev1 = nullptr;
-                flags |= F_HAS_PENDING;
-            }
-            flags |= F_GLOBAL_REC;
-            c->ext_rec_in = (const double*)gathered_prev_dev;
-        } else if (c->pending) {
-            flags |= F_HAS_PENDING;   // resolved earlier through the three-phase calls
-        }
-        ensure_windows(c, t);
-        c->ext_rec_out = (double*)gathered_next_dev + (size_t)P.offset * P.RW;
-        if (prof) { c->kev0 = c->pev[4 * it]; c->kev1 = c->pev[4 * it + 1]; }
-        launch_chain_iter(c, t, flags);
-        c->kev0 = c->kev1 = nullptr;
-        c->ext_rec_in = nullptr; c->ext_rec_out = nullptr;
-        if (prof) {
-            HIPCHK(hipEventRecord(c->ev1, c->stream));
-            c->pev_iters = it + 1;
-            c->pending_timing = true;
-            c->timing.iters = it + 1;
-            c->timing.chain_evals = (int64_t)(it + 1) * P.N;
-        }
-        HIPCHK(hipGetLastError());
-        c->prev_open = true;
-        c->pending = false;
-        c->rec_external = true;
-        c->pending_ext = exchange_active(c, t);
-        c->iter = t; c->exch_done = false;
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
-// settle the last sharded_step: resolve its exchange from the gathered records and bring records, history and
-// counters into the context (afterwards history/state can be read, or stepping continues in either form)
-int smm_bgp_sharded_finish(void* ctx, const void* gathered_dev) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return SMM_ERR_INVALID_ARG;
-    if (!c->rec_external) return SMM_OK;
-    if (!gathered_dev) return SMM_ERR_INVALID_ARG;
-    if (c && c->p2p_current) return fail(c, SMM_ERR_STATE, "the records of the last iteration are in the p2p windows: call smm_bgp_p2p_finish first");
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        if (c->failed) return told(c);
-        const KParams& P = c->P;
-        int flags = (c->prev_open ? F_CLOSE_PREV : 0) | F_GLOBAL_REC;
-        if (c->pending_ext) {
-            launch_resolve(c, c->iter, (const double*)gathered_dev);
-            flags |= F_HAS_PENDING;
-        }
-        hipLaunchKernelGGL(k_flush, dim3((P.N + 255) / 256), dim3(256), 0, c->stream, P, c->iter + 1, (const double*)gathered_dev,
-                           c->rec[c->cur ^ 1], flags);
-        HIPCHK(hipGetLastError());
-        c->cur ^= 1;
-        c->pending = false; c->prev_open = false; c->rec_external = false; c->pending_ext = false;
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
-int smm_bgp_p2p_init(void* ctx, void* ipc_handle_out, void** window_dev_out) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return SMM_ERR_INVALID_ARG;
-    if (c->a2a_G < 1) return fail(c, SMM_ERR_STATE, "the p2p form needs equal shards (N_global a multiple of N, chain_offset a multiple of N)");
-    if (c->a2a_G > P2P_MAXG) return fail(c, SMM_ERR_INVALID_ARG, "the p2p form serves up to 8 ranks (one node)");
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        KParams& P = c->P;
-        const P2PLayout L = p2p_layout(P.Ng, P.RW);
-        if (!c->p2p_mine) {
-            // Plain device memory — what the receive buffers of the collective libraries are.  (An UNCACHED allocation,
-            // hipDeviceMallocUncached, looked like the natural choice and was the first one: it passed every test of its own file and
-            // failed in the full suite, in both forms, whenever the process had run other contexts before — later kernels were served
-            // lines that an earlier allocation at the same address had left behind; the cache maintenance at kernel boundaries, which
-            // plain memory gets, does not seem to cover it.  Within a launch nothing relies on the caches: stores into a window are
-            // system-scope stores, self-validating words are re-read past the caches until their tag is the wanted one.)
-            // (a shard that can run the persistent form keeps its ring behind the p2p window proper: one allocation, one IPC handle)
-            size_t total = L.total;
-            if (c->F.persist_sh) {
-                c->prw_off = (L.total + 255) & ~(size_t)255;
-                total = c->prw_off + pr_win_layout(P.Ng, P.RW, c->a2a_G, persist_tiles_rank(c->F, c->P.N)).total;   // (the ring: RW granules of this context's records)
-            }
-            void* w = nullptr;
-            HIPCHK(hipMalloc(&w, total));
-            c->p2p_mine = (unsigned char*)w;
-            HIPCHK(hipMemset(w, 0, total));
-            HIPCHK(hipDeviceSynchronize());
-            P.p2p_G = c->a2a_G;
-            P.p2p_rank = P.offset / P.N;
-            for (int r = 0; r < P2P_MAXG; ++r) P.p2p_win[r] = nullptr;
-            P.p2p_win[P.p2p_rank] = c->p2p_mine;
-            P.p2p_self = c->p2p_mine;
-            for (int b = 0; b < 2; ++b) {
-                P.p2p_off[b] = (uint32_t)L.rec[b]; P.p2p_off[2 + b] = (uint32_t)L.val[b]; P.p2p_off[4 + b] = (uint32_t)L.slot[b];
-                P.p2p_off[6 + b] = (uint32_t)L.llrec[b]; P.p2p_off[8 + b] = (uint32_t)L.llval[b];
-                P.p2p_off[10 + b] = (uint32_t)L.slot4[b];
-            }
-            if (L.total >= ((size_t)1 << 32)) throw std::string("p2p window larger than 4 GiB");
-            c->p2p_attached = 1u << P.p2p_rank;
-            c->p2p_seq = 0;
-            c->p2p_current = false;
-            // one launch per iteration (the lean key walk in the chain kernel's prologue, the push in its epilogue) where the
-            // single shard has it too: objfunc_norm with np == nm <= 4, min_improve == 0, N_global <= 8192
-            c->p2p_inline = c->F.norm_fast && c->F.lean_plan && !P.lean_wide && P.Ng <= XLDS_MAX && P.plan_K <= XLDS_MAX && !c->deep_plan &&
-                            P.dist_fun == SMM_DIST_MINUS && p2p_walk_bytes(c) + norm_tile_doubles(P.np) * 8 <= (size_t)160 * 1024;
-            // two launches per iteration for the large norm populations (8192 < N_global <= 32768, min_improve == 0: BASELINE
-            // configs[2], 4 and 8 shards of 4096): k_exch_resolve_rows reads the window's tagged slots itself, the chain kernel
-            // pushes from its epilogue like the inline form's
-            c->p2p_rows = c->F.norm_fast && !c->p2p_inline && c->F.xk == XK_ROWS;
-        }
-        if (ipc_handle_out) {
-            hipIpcMemHandle_t h;
-            HIPCHK(hipIpcGetMemHandle(&h, c->p2p_mine));
-            static_assert(sizeof(hipIpcMemHandle_t) == SMM_P2P_HANDLE_BYTES, "hipIpcMemHandle_t is 64 bytes");
-            memcpy(ipc_handle_out, &h, sizeof h);
-        }
-        if (window_dev_out) *window_dev_out = c->p2p_mine;
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
-int smm_bgp_p2p_attach(void* ctx, int32_t rank, const void* ipc_handle, void* window_dev) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || (!ipc_handle) == (!window_dev)) return SMM_ERR_INVALID_ARG;
-    if (!c->p2p_mine) return fail(c, SMM_ERR_STATE, "smm_bgp_p2p_init comes first");
-    if (rank < 0 || rank >= c->P.p2p_G || rank == c->P.p2p_rank) return fail(c, SMM_ERR_INVALID_ARG, "smm_bgp_p2p_attach: rank of ANOTHER shard, 0 <= rank < N_global / N");
-    if (c->p2p_attached & (1u << rank)) return fail(c, SMM_ERR_STATE, "smm_bgp_p2p_attach: this rank's window is attached already");
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        void* w = window_dev;
-        if (ipc_handle) {
-            hipIpcMemHandle_t h;
-            memcpy(&h, ipc_handle, sizeof h);
-            HIPCHK(hipIpcOpenMemHandle(&w, h, hipIpcMemLazyEnablePeerAccess));
-            c->p2p_opened[rank] = w;
-            // (a peer PROCESS on this very device — several ranks on one GPU, the tests' way: its tiles compete with this rank's for
-            // the compute units, and the persistent form needs all of them resident at once)
-            hipPointerAttribute_t at;
-            if (hipPointerGetAttributes(&at, w) == hipSuccess && at.device == c->device) c->p2p_ranks_here += 1;
-            (void)hipGetLastError();
-        } else {   // a context of this process: on another device the two must see each other
-            hipPointerAttribute_t at;
-            HIPCHK(hipPointerGetAttributes(&at, w));
-            if (at.device == c->device) c->p2p_ranks_here += 1;
-            if (at.device != c->device) {
-                const hipError_t e = hipDeviceEnablePeerAccess(at.device, 0);
-                if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIPCHK(e);
-                (void)hipGetLastError();
-            }
-        }
-        c->P.p2p_win[rank] = (unsigned char*)w;
-        c->p2p_attached |= 1u << rank;
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
-int smm_bgp_p2p_step(void* ctx, int32_t n_iters) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || n_iters < 0) return SMM_ERR_INVALID_ARG;
-    if (c->failed) return told(c);
-    if (!c->p2p_mine) return fail(c, SMM_ERR_STATE, "smm_bgp_p2p_init comes first");
-    if (c->p2p_attached != (1u << c->P.p2p_G) - 1u) return fail(c, SMM_ERR_STATE, "smm_bgp_p2p_step: not every rank's window is attached");
-    if (c->iter + n_iters > c->P.T) return fail(c, SMM_ERR_MAXITER, "step beyond maxiter (history capacity)");
-    if (c->rec_external && !c->p2p_current) return fail(c, SMM_ERR_STATE, "records are in the gather buffer: call smm_bgp_sharded_finish first");
-    if (c->a2a_open) return fail(c, SMM_ERR_STATE, "smm_bgp_a2a_apply_dev comes first");
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        // (launches of the persistent form that this step simply continues are looked at — and agreed upon by the ranks — when the run is
-        // synchronised, not between two steps: the host stays out of the way)
-        if (!(!c->p2p_current && persist_sh_usable(c, n_iters))) settle_persist(c);
-        if (c->failed) return told(c);
-        KParams& P = c->P;
-        if (c->profiling == 2) {
-            while ((int)c->pev.size() < 4 * n_iters) {
-                hipEvent_t e;
-                HIPCHK(hipEventCreate(&e));
-                c->pev.push_back(e);
-            }
-            c->pev_exch.assign((size_t)n_iters, 0);
-        }
-        c->pev_iters = 0;
-        HIPCHK(hipEventRecord(c->ev0, c->stream));
-        p2p_enqueue(c, n_iters);
-        c->pending_timing = true;
-        c->timing.iters = n_iters;
-        c->timing.chain_evals = (int64_t)n_iters * P.N;
-    } catch (const std::string& m) {
-        c->kev0 = c->kev1 = nullptr; c->ext_rec_in = nullptr; c->ext_rec_out = nullptr; c->ext_vals_out = nullptr;
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
-// settle the last p2p step (its exchange, history, counters) into the context, like smm_bgp_sharded_finish
-int smm_bgp_p2p_finish(void* ctx) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return SMM_ERR_INVALID_ARG;
-    if (c->p2p_current && !c->rec_external) return SMM_OK;
-    if (!c->p2p_current && !(c->p2p_mine && c->unresolved && c->P.N < c->P.Ng)) return SMM_OK;
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        if (c->failed) return told(c);
-        p2p_publish(c);   // (behind a launch of the persistent form: the records after `iter` into the windows, their exchange still to be resolved)
-        const KParams& P = c->P;
-        const P2PLayout L = p2p_layout(P.Ng, P.RW);
-        int flags = (c->prev_open ? F_CLOSE_PREV : 0) | F_GLOBAL_REC;
-        // the donors' records of the last iteration must have landed, in plain form
-        if (c->p2p_mode_inline) launch_p2p_unpack(c, c->iter);
-        else if (c->p2p_unwaited) launch_p2p_wait(c);
-        if (c->pending_ext) {
-            launch_resolve_window(c, c->iter);
-            flags |= F_HAS_PENDING;
-        }
-        hipLaunchKernelGGL(k_flush, dim3((P.N + 255) / 256), dim3(256), 0, c->stream, P, c->iter + 1,
-                           (const double*)(c->p2p_mine + L.rec[c->iter & 1]), c->rec[c->cur ^ 1], flags);
-        HIPCHK(hipGetLastError());
-        c->cur ^= 1;
-        c->pending = false; c->prev_open = false; c->rec_external = false; c->pending_ext = false; c->p2p_current = false;
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
-int smm_bgp_record_doubles(void* ctx) {
-    Ctx* c = (Ctx*)ctx;
-    return c ? c->P.RW : SMM_ERR_INVALID_ARG;
-}
-
-int smm_bgp_export_records_dev(void* ctx, void* rec_dev) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !rec_dev) return SMM_ERR_INVALID_ARG;
-    if (c->failed) return told(c);
-    if (c->rec_external) return fail(c, SMM_ERR_STATE, "records are in the gather buffer: call smm_bgp_sharded_finish first");
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        if (c->failed) return told(c);
-        // after smm_bgp_step the exchange of the last iteration is still pending (resolved or not): the exported records must
-        // be the ones AFTER that exchange, as the three-phase protocol defines them
-        if (c->pending || c->unresolved) flush(c);
-        HIPCHK(hipMemcpyAsync(rec_dev, c->rec[c->cur], (size_t)c->P.RW * c->P.N * sizeof(double), hipMemcpyDeviceToDevice,
-                              c->stream));
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
-int smm_bgp_exchange_dev(void* ctx, const void* gathered_dev) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !gathered_dev) return SMM_ERR_INVALID_ARG;
-    if (c->failed) return told(c);
-    if (c->iter < 1) return fail(c, SMM_ERR_STATE, "exchange before the first local step");
-    if (c->pending || c->exch_done || c->a2a_open) return fail(c, SMM_ERR_STATE, "exchange already resolved for this iteration");
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        if (c->failed) return told(c);
-        c->exch_done = true;
-        if (exchange_active(c, c->iter)) {
-            const KParams& P = c->P;
-            launch_resolve(c, c->iter, (const double*)gathered_dev);
-            hipLaunchKernelGGL(k_exch_apply, dim3((P.N + 255) / 256), dim3(256), 0, c->stream, P, c->iter,
-                               (const double*)gathered_dev, c->rec[c->cur]);
-        }
-        HIPCHK(hipGetLastError());
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
-// ---- the values form of the sharded exchange (include/smmhip.h) ----
-int smm_bgp_a2a_capacity(void* ctx) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return SMM_ERR_INVALID_ARG;
-    return c->a2a_cap;
-}
-
-int smm_bgp_export_values_dev(void* ctx, void* vals_dev) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !vals_dev) return SMM_ERR_INVALID_ARG;
-    if (c->failed) return told(c);
-    if (c->rec_external) return fail(c, SMM_ERR_STATE, "records are in the gather buffer: call smm_bgp_sharded_finish first");
-    if (c->iter < 1) return fail(c, SMM_ERR_STATE, "no iteration yet");
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        if (c->failed) return told(c);
-        if (c->pending || c->unresolved) flush(c);
-        HIPCHK(hipMemcpyAsync(vals_dev, c->vals_buf[c->iter & 1], (size_t)c->P.N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
-int smm_bgp_a2a_pack_dev(void* ctx, const void* vals_all_dev, void* send_dev) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !vals_all_dev || !send_dev) return SMM_ERR_INVALID_ARG;
-    if (c->failed) return told(c);
-    if (c->a2a_cap <= 0) return fail(c, SMM_ERR_STATE, "the values form needs equal shards (N_global a multiple of N, chain_offset a multiple of N)");
-    if (c->iter < 1) return fail(c, SMM_ERR_STATE, "exchange before the first local step");
-    if (c->pending || c->a2a_open || c->exch_done) return fail(c, SMM_ERR_STATE, "exchange already resolved for this iteration");
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        if (c->failed) return told(c);
-        if (exchange_active(c, c->iter)) {
-            KParams P1 = c->P;
-            P1.RW = 1;   // (the resolve kernels read value s at gathered[s * RW])
-            launch_resolve_p(c, P1, c->iter, (const double*)vals_all_dev);
-            const KParams& P = c->P;
-            hipLaunchKernelGGL(k_a2a_index, dim3(c->a2a_G), dim3(XWG), 0, c->stream, P, c->iter, c->a2a_G, c->a2a_cap, c->a2a_send_idx,
-                               c->a2a_send_cnt, c->a2a_rowidx);
-            const size_t ne = (size_t)c->a2a_G * c->a2a_cap * P.RW;
-            hipLaunchKernelGGL(k_a2a_pack, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, c->stream, P, c->a2a_G, c->a2a_cap,
-                               (const int32_t*)c->a2a_send_idx, (const int32_t*)c->a2a_send_cnt, (const double*)c->rec[c->cur], (double*)send_dev);
-        }
-        HIPCHK(hipGetLastError());
-        c->a2a_open = true;
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
-int smm_bgp_a2a_apply_dev(void* ctx, const void* recv_dev) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !recv_dev) return SMM_ERR_INVALID_ARG;
-    if (c->failed) return told(c);
-    if (!c->a2a_open) return fail(c, SMM_ERR_STATE, "smm_bgp_a2a_pack_dev comes first");
-    try {
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        if (c->failed) return told(c);
-        if (exchange_active(c, c->iter)) {
-            const KParams& P = c->P;
-            hipLaunchKernelGGL(k_a2a_apply, dim3((P.N + 255) / 256), dim3(256), 0, c->stream, P, c->iter, (const double*)recv_dev,
-                               (const int32_t*)c->a2a_rowidx, c->rec[c->cur]);
-        }
-        HIPCHK(hipGetLastError());
-        c->a2a_open = false;
-        c->exch_done = true;
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
-}
-
 // a user objective's evaluations (smm_eval_batch; with base_seed, smm_eval_batch_noseed): its kernel wants [M][np] / [M][nm], transposed on the host
 static void user_eval_batch(Ctx* c, const double* params, int32_t M, double* value, double* sim_moments, int8_t* status, const uint64_t* base_seed) {
     const KParams& P = c->P;
@@ -2919,10 +1968,8 @@ static void user_eval_batch(Ctx* c, const double* params, int32_t M, double* val
 }
 
 int smm_eval_batch(void* ctx, const double* params, int32_t M, double* value, double* sim_moments, int8_t* status) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !params || M < 0 || !value || !sim_moments || !status) return SMM_ERR_INVALID_ARG;
-    if (M == 0) return SMM_OK;
-    try {
+    return api_call(ctx, params && M >= 0 && value && sim_moments && status, [&](Ctx* c) -> int {
+        if (M == 0) return SMM_OK;
         HIPCHK(hipSetDevice(c->device));
         const KParams& P = c->P;
         if (c->obj == SMM_OBJ_USER) {
@@ -2937,22 +1984,17 @@ int smm_eval_batch(void* ctx, const double* params, int32_t M, double* value, do
         HIPCHK(hipMemcpyAsync(sim_moments, dm.p, (size_t)P.nm * M * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(status, ds.p, (size_t)M, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
+        return SMM_OK;
+    });
 }
 
-int smm_eval_batch_noseed(void* ctx, const double* params, int32_t M, uint64_t base_seed, double* value, double* sim_moments,
-                          int8_t* status) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !params || M < 0 || !value || !sim_moments || !status) return SMM_ERR_INVALID_ARG;
-    const bool user_rng = c->obj == SMM_OBJ_USER && c->u_rng;
-    if (!is_sim(c->obj) && !user_rng)
-        return fail(c, SMM_ERR_INVALID_ARG, "noseed evaluations exist for objfunc_norm and for user objectives that draw from the library's "
-                                            "stream (smm_register_user_objective_rng) only");
-    if (M == 0) return SMM_OK;
-    try {
+int smm_eval_batch_noseed(void* ctx, const double* params, int32_t M, uint64_t base_seed, double* value, double* sim_moments, int8_t* status) {
+    return api_call(ctx, params && M >= 0 && value && sim_moments && status, [&](Ctx* c) -> int {
+        const bool user_rng = c->obj == SMM_OBJ_USER && c->u_rng;
+        if (!is_sim(c->obj) && !user_rng)
+            return fail(c, SMM_ERR_INVALID_ARG, "noseed evaluations exist for objfunc_norm and for user objectives that draw from the library's "
+                                                "stream (smm_register_user_objective_rng) only");
+        if (M == 0) return SMM_OK;
         HIPCHK(hipSetDevice(c->device));
         if (user_rng) {
             const uint64_t bs = base_seed;
@@ -2970,18 +2012,15 @@ int smm_eval_batch_noseed(void* ctx, const double* params, int32_t M, uint64_t b
         HIPCHK(hipMemcpyAsync(sim_moments, dm.p, (size_t)P.nm * M * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(status, ds.p, (size_t)M, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
+        return SMM_OK;
+    });
 }
 
 // history(c) (AlgoBGP.jl:138-160): download iterations t0..t1-1 and transpose the per-chain history
 // records into the ABI's structure-of-arrays buffers.
 int smm_get_history(void* ctx, int32_t t0, int32_t t1, smm_history_t* out) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !out || t0 < 0 || t1 < t0 || t1 > c->P.T) return SMM_ERR_INVALID_ARG;
-    try {
+    return api_call(ctx, out && t0 >= 0 && t1 >= t0, [&](Ctx* c) -> int {
+        if (t1 > c->P.T) return SMM_ERR_INVALID_ARG;
         reader_prelude(c);
         const KParams& P = c->P;
         const size_t N = P.N, HW = P.HW, np = P.np, nm = P.nm;
@@ -3005,23 +2044,19 @@ int smm_get_history(void* ctx, int32_t t0, int32_t t1, smm_history_t* out) {
                     for (size_t k = 0; k < nm; ++k) out->sim_moments[((size_t)(t - t0) * nm + k) * N + i] = h[H_PARAMS + np + k];
             }
         }
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
+        return SMM_OK;
+    });
 }
 
 int smm_get_state(void* ctx, smm_state_t* s) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !s) return SMM_ERR_INVALID_ARG;
-    try {
+    return api_call(ctx, s != nullptr, [&](Ctx* c) -> int {
         reader_prelude(c);
         const KParams& P = c->P;
         const size_t N = P.N, RW = P.RW, np = P.np, nm = P.nm;
         std::vector<double> cs(N * CSW), rec(N * RW);
         HIPCHK(hipMemcpy(cs.data(), P.cs, cs.size() * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(rec.data(), c->rec[c->cur], rec.size() * 8, hipMemcpyDeviceToHost));
-        s->iter = c->iter;
+        HIPCHK(hipMemcpy(rec.data(), c->rec[c->run.cur], rec.size() * 8, hipMemcpyDeviceToHost));
+        s->iter = c->run.iter;
         for (size_t i = 0; i < N; ++i) {
             const double* b = cs.data() + i * CSW;
             const double* r = rec.data() + i * RW;
@@ -3039,24 +2074,21 @@ int smm_get_state(void* ctx, smm_state_t* s) {
             if (s->la_sim_moments)
                 for (size_t k = 0; k < nm; ++k) s->la_sim_moments[k * N + i] = r[3 + np + k];
         }
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
+        return SMM_OK;
+    });
 }
 
 // restart! (AlgoBGP.jl:804-884) with clean resume semantics: continue at iteration iter+1
 int smm_set_state(void* ctx, const smm_state_t* s, const smm_history_t* h) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !s || s->iter < 0 || s->iter > c->P.T) return SMM_ERR_INVALID_ARG;
-    if (s->iter > 0 && !h) return fail(c, SMM_ERR_INVALID_ARG, "history of iterations 0..iter-1 required");
-    if (!s->sigma || !s->accept_rate || !s->n_noex || !s->n_acc_noex || !s->best_val || !s->best_id || !s->la_value ||
-        !s->la_prob || !s->la_status || !s->la_params || !s->la_sim_moments)
-        return fail(c, SMM_ERR_INVALID_ARG, "smm_set_state needs every field of smm_state_t");
-    if (s->iter > 0 && (!h->value || !h->prob || !h->curr_val || !h->best_val || !h->params || !h->sim_moments ||
-                        !h->best_id || !h->exchanged || !h->accepted || !h->status))
-        return fail(c, SMM_ERR_INVALID_ARG, "smm_set_state needs every field of smm_history_t");
-    try {
+    return api_call(ctx, s && s->iter >= 0, [&](Ctx* c) -> int {
+        if (s->iter > c->P.T) return SMM_ERR_INVALID_ARG;
+        if (s->iter > 0 && !h) return fail(c, SMM_ERR_INVALID_ARG, "history of iterations 0..iter-1 required");
+        if (!s->sigma || !s->accept_rate || !s->n_noex || !s->n_acc_noex || !s->best_val || !s->best_id || !s->la_value ||
+            !s->la_prob || !s->la_status || !s->la_params || !s->la_sim_moments)
+            return fail(c, SMM_ERR_INVALID_ARG, "smm_set_state needs every field of smm_state_t");
+        if (s->iter > 0 && (!h->value || !h->prob || !h->curr_val || !h->best_val || !h->params || !h->sim_moments ||
+                            !h->best_id || !h->exchanged || !h->accepted || !h->status))
+            return fail(c, SMM_ERR_INVALID_ARG, "smm_set_state needs every field of smm_history_t");
         HIPCHK(hipSetDevice(c->device));
         settle_persist(c);
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -3085,7 +2117,7 @@ int smm_set_state(void* ctx, const smm_state_t* s, const smm_history_t* h) {
         }
         c->nan_values = nan_seen;
         HIPCHK(hipMemcpy(P.cs, cs.data(), cs.size() * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->rec[c->cur], rec.data(), rec.size() * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(c->rec[c->run.cur], rec.data(), rec.size() * 8, hipMemcpyHostToDevice));
         std::vector<double> row(N * HW, 0.0);
         for (int t = 0; t < s->iter; ++t) {
             const size_t o = (size_t)t * N;
@@ -3100,24 +2132,22 @@ int smm_set_state(void* ctx, const smm_state_t* s, const smm_history_t* h) {
             }
             HIPCHK(hipMemcpy(P.hrec + (size_t)t * N * HW, row.data(), row.size() * 8, hipMemcpyHostToDevice));
         }
-        c->iter = s->iter;
+        c->run.iter = s->iter;
         if (c->failed) {   // a state from before the failure: the run may go on
             const unsigned long long e = ERR_NONE;
             HIPCHK(hipMemcpy(P.err, &e, 8, hipMemcpyHostToDevice));
             c->failed = 0; c->failed_told = false;
         }
-        c->rec_external = false; c->pending_ext = false; c->unresolved = false;
-        c->pending = false;
-        c->prev_open = false;
+        c->rec_external = false; c->pending_ext = false; c->run.unresolved = false;
+        c->run.pending = false;
+        c->run.prev_open = false;
         c->a2a_open = false;
         c->p2p_current = false;   // (the next smm_bgp_p2p_step publishes the uploaded state)
-        c->exch_done = false;
-        c->slots_iter = -1;
+        c->run.exch_done = false;
+        c->run.slots_iter = -1;
         if (P.walk_flags) HIPCHK(hipMemset(P.walk_flags, 0, 16));   // (the values the next exchange sees are written by the next accept step)
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
+        return SMM_OK;
+    });
 }
 
 int smm_get_timing(void* ctx, smm_timing_t* out) {
@@ -3198,9 +2228,7 @@ int smm_debug_ts_waves(void* ctx, unsigned long long* out, int n_wg) {
 // debug (test build only, not part of the public header): the look-ahead window starting at iteration t, planned now; milliseconds of its
 // kernels on the stream (tools/exp/shard_plan_time.py: what a shard of 8 x 4096 spends on its plan per window)
 int smm_debug_plan_window(void* ctx, int t, double* ms_out, int* window_out) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !ms_out) return SMM_ERR_INVALID_ARG;
-    try {
+    return api_call(ctx, ms_out != nullptr, [&](Ctx* c) -> int {
         HIPCHK(hipSetDevice(c->device));
         hipEvent_t e0, e1;
         HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
@@ -3214,10 +2242,8 @@ int smm_debug_plan_window(void* ctx, int t, double* ms_out, int* window_out) {
         *ms_out = ms;
         if (window_out) *window_out = c->plan_w;
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
+        return SMM_OK;
+    });
 }
 // debug (test build only, not part of the public header): the cone of one tile in iteration plan_t0 + w of the current plan window
 int smm_debug_cone(void* ctx, int w, int tile, uint32_t* hdr, uint32_t* pairs, uint16_t* gather, int32_t* info) {
@@ -3236,17 +2262,13 @@ int smm_debug_cone(void* ctx, int w, int tile, uint32_t* hdr, uint32_t* pairs, u
 #endif
 
 int smm_get_Z(void* ctx, double* Z) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !Z) return SMM_ERR_INVALID_ARG;
-    try {
+    return api_call(ctx, Z != nullptr, [&](Ctx* c) -> int {
         HIPCHK(hipSetDevice(c->device));
         for (int k = 0; k < c->P.nm; ++k)
             HIPCHK(hipMemcpy(Z + (size_t)k * c->P.ns, c->P.Z + (size_t)k * c->P.zstride, (size_t)c->P.ns * sizeof(double),
                              hipMemcpyDeviceToHost));
-    } catch (const std::string& m) {
-        return fail(c, SMM_ERR_HIP, m);
-    }
-    return SMM_OK;
+        return SMM_OK;
+    });
 }
 
 }  // extern "C"

@@ -175,7 +175,7 @@ def test_chain_kernel_instantiations_are_named_in_the_chooser_only():
     assert code.count(head) == 1
     a = code.index(head)
     b = code.index("\n}\n", a)
-    body, rest = code[a:b], code[:a] + code[b:]
+    body, rest = code[a:b], code[:a] + code[b:] + strip(open(os.path.join(csrc, "smm_run_host.hpp")).read())
     assert not re.findall(r"\bk_chain_iter\w*", rest), "a chain kernel is named outside chain_instance()"
     declared = set()
     for h in ("smm_chain.hpp", "smm_chain_norm.hpp"):
@@ -198,6 +198,7 @@ def test_reducer_kernels_and_shared_rules_live_in_the_reducers_host_file():
     kernels = r"\bk_(?:stats|cov|diag|group|hist|trace|rank|draws|moment|prof)_\w*"
     main = src("smmhip.hip")
     assert not re.findall(kernels, main), "smmhip.hip names a reducer kernel"
+    assert not re.findall(kernels, src("smm_run_host.hpp")), "smm_run_host.hpp names a reducer kernel"
     assert main.count('#include "smm_reducers_host.hpp"') == 1
     host = src("smm_reducers_host.hpp")
     declared = set()
@@ -215,3 +216,53 @@ def test_reducer_kernels_and_shared_rules_live_in_the_reducers_host_file():
                     "n_groups < 0, or group NULL with n_groups != 1"):
         assert host.count('"%s"' % message) == 1, message
         assert message not in main, message
+
+
+def test_the_run_lives_in_the_run_host_file_with_one_frame_and_one_rule_book():
+    """The host side of everything that advances or settles a run is smm_run_host.hpp, included once by smmhip.hip ahead of the reducers'
+    host side (whose prelude settles and flushes through it).  Every entry point that takes a context and can throw goes through one frame,
+    api_call; the refusals of the sharded protocol that several entry points give are written once; the state a failed persistent launch
+    is rolled back to is one struct (Run), not loose members.  Reads the sources only."""
+    csrc = os.path.join(ROOT, "smm.jl_amd", "csrc")
+    strip = lambda txt: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    names = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")))
+    code = {f: strip(open(os.path.join(csrc, f)).read()) for f in names}
+    main = code["smmhip.hip"]
+    assert main.count('#include "smm_run_host.hpp"') == 1
+    assert main.index('#include "smm_run_host.hpp"') < main.index('#include "smm_reducers_host.hpp"')
+    assert sum(c.count('"smm_run_host.hpp"') for c in code.values()) == 1
+    assert "smm_run_host.hpp" not in open(os.path.join(csrc, "Makefile")).read()   # (not among the sources hiprtc is given)
+    everything = "\n".join(code.values())
+    for text in ("records are in the gather buffer: call smm_bgp_sharded_finish first", "step beyond maxiter (history capacity)",
+                 "the records of the last iteration are in the p2p windows: call smm_bgp_p2p_finish first", "smm_bgp_p2p_init comes first",
+                 "exchange before the first local step", "exchange already resolved for this iteration"):
+        assert everything.count(text) == 1, text
+        assert code["smm_run_host.hpp"].count(text) == 1, text
+
+    def functions_with(pattern):
+        """the functions (by name) whose definitions hold the pattern: the nearest line above that starts a definition at column 0"""
+        found = set()
+        for f in ("smmhip.hip", "smm_run_host.hpp", "smm_reducers_host.hpp", "smm_population_host.hpp"):
+            lines = code[f].splitlines()
+            for i, line in enumerate(lines):
+                if pattern not in line:
+                    continue
+                j = i
+                while not re.match(r"[A-Za-z_].*\b\w+\(.*\{", lines[j]):
+                    j -= 1
+                found.add(re.match(r"[^(]*?(\w+)\(", lines[j]).group(1))
+        return found
+
+    no_throw = {"smm_last_error", "smm_stream", "smm_ctx_destroy", "smm_bgp_record_doubles", "smm_bgp_a2a_capacity", "smm_get_timing",
+                "smm_set_persistent", "smm_get_persistent", "smm_describe", "smm_set_profiling", "smm_debug_ts", "smm_debug_ts_waves",
+                "smm_debug_cone"}
+    assert functions_with("(Ctx*)ctx") == {"api_call"} | no_throw
+    assert functions_with("catch (const std::string") == {"api_call", "smm_ctx_create"}
+    assert "reducer_call" not in everything
+    assert not re.findall(r"\bsnap_(?:iter|cur|pending|prev_open|unresolved|exch_done|slots_iter)\b", everything)
+    assert re.search(r"struct Run \{[^}]*\};", main) and len(re.findall(r"^    Run (?:run|snap);", main, flags=re.M)) == 2
+    run = code["smm_run_host.hpp"]
+    assert "c->snap = c->run;" in run and "c->run = c->snap;" in run
+    assert everything.count("k_flush,") == 1 and "void launch_flush(" in run
+    assert not re.findall(r"c->kev[01] = |c->ext_(?:rec_in|rec_out|vals_out) = ", main + code["smm_reducers_host.hpp"] + code["smm_population_host.hpp"])
+    assert len(re.findall(r"c->kev0 = ", run)) == 2 and len(re.findall(r"c->ext_rec_in = ", run)) == 2   # (the two scope objects)
