@@ -494,10 +494,7 @@ __device__ inline void moment_term(const KParams& P, const double* s_part, const
         tot = tot + (dense ? s_part[((size_t)wv * nmp + k) * 16 + ci] : s_part[(wv * CT + ci) * P.nm + k]);
     const double m = dense ? tot : tot / (double)P.ns;
     m_out = m;
-    double d = m - s_mom[k];
-    const double wk = s_w[k];
-    if (!isnan(wk)) d = d / wk;
-    v_out = d * d;
+    v_out = moment_sq(m, s_mom[k], s_w[k]);
 }
 
 template <int CT>
@@ -511,41 +508,27 @@ __device__ inline void finish_objective(const KParams& P, const double* theta /*
         return;
     }
     if (P.obj == SMM_OBJ_BANANA) {
-        double v = 0.0;
-        for (int i = 0; i + 1 < P.np; ++i) {
-            const double a = theta[i], b = theta[i + 1];
-            const double t1 = b - a * a;
-            const double t2 = 1.0 - a;
-            const double term = 100.0 * (t1 * t1) + t2 * t2;
-            v = (i == 0) ? term : v + term;
-        }
+        const double v = banana_value(theta, P.np);
         for (int k = 0; k < P.nm; ++k) simM[k] = s_mom[k] + 2.2;
         value = v;
         status = 1;
         return;
     }
-    if (P.obj == SMM_OBJ_NORM_FAILBOX && P.objp && theta[0] >= P.objp[0] && theta[0] <= P.objp[1]) {
+    if (P.obj == SMM_OBJ_NORM_FAILBOX && P.objp && in_failbox(theta[0], P.objp)) {
         for (int k = 0; k < P.nm; ++k) simM[k] = NAN;
         value = -1.0;  // Eval() default, Eval.jl:84
         status = -2;
         return;
     }
     double vsum = 0.0;
-    int k = 0;
-    if (vk) {   // mean and squared deviation already there (moment_term by the chain's lanes): eight at a time from LDS, added in order
-        for (; k + 8 <= P.nm; k += 8) {
-            double v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = vk[k + u];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) vsum = (k + u == 0) ? v[u] : vsum + v[u];
+    if (vk) {   // mean and squared deviation already there (moment_term by the chain's lanes): from LDS, added in order
+        vsum = sum_in_order(vk, P.nm);
+    } else {
+        for (int k = 0; k < P.nm; ++k) {
+            double v;
+            moment_term<CT>(P, s_part, s_mom, s_w, ci, k, simM[k], v);
+            vsum = (k == 0) ? v : vsum + v;
         }
-    }
-    for (; k < P.nm; ++k) {
-        double v;
-        if (vk) v = vk[k];
-        else moment_term<CT>(P, s_part, s_mom, s_w, ci, k, simM[k], v);
-        vsum = (k == 0) ? v : vsum + v;
     }
     value = vsum / (double)P.nm;
     status = 1;
@@ -652,18 +635,6 @@ __device__ inline void coop_store_n(double* __restrict__ g, const double* lds_bl
     for (int i = r; i < W / 2; i += nr) gd[i] = ld[i];
 }
 
-// set_eval!(ci, ej) of swap_ev_ij! (AlgoBGP.jl:734-749) as a history record: the chain's record of
-// the exchanged iteration tp is the donor's last accepted one (accepted = true, the donor's
-// prob/status), curr = donor value, best recomputed against iteration tp-1 (:231-243).
-__device__ inline void make_swapped_history(const KParams& P, double* hrec /*[HW]*/, const double* donor /*[RW]*/, int tp,
-                                            int partner, double bpp, double bppid, double& bestv, double& bestid) {
-    const double value = donor[0];
-    if (value < bpp) { bestv = value; bestid = (double)tp; }
-    else { bestv = bpp; bestid = bppid; }
-    hrec[H_VALUE] = value; hrec[H_PROB] = donor[1]; hrec[H_CURR] = value; hrec[H_BEST] = bestv;
-    hrec[H_BESTID] = bestid; hrec[H_EXCH] = (double)partner; hrec[H_ACC] = 1.0; hrec[H_STATUS] = donor[2];
-    // (the parameters and moments of the donor's record are copied by all lanes of the chain: copy_strided below)
-}
 // dst[k] = src[k] for k = r, r + nr, ... < n: a copy shared by the nr lanes that serve one chain
 __device__ inline void copy_strided(double* dst, const double* src, const int n, const int r, const int nr) {
     for (int k = r; k < n; k += nr) dst[k] = src[k];
@@ -1239,7 +1210,9 @@ __global__ __launch_bounds__(WG * TPW, 4) void k_chain_iter(const KParams P, con
             bool exch_prev = false;
             if (partner != 0) {  // swap_ev_ij!, :734-749: iteration t-1's record becomes the donor's
                 exch_prev = true;
-                make_swapped_history(P, S.hp + cl * HW, S.rec + cl * RW, t - 1, partner, csb[CS_BESTP], csb[CS_BESTPID], bp, bpid);
+                // (the parameters and moments of the donor's record are copied by all lanes of the chain: copy_strided below)
+                const Best b = swapped_head(S.hp + cl * HW, S.rec + cl * RW, partner, t - 1, csb + CS_BESTP);
+                bp = b.best; bpid = b.best_id;
             } else if (csb[CS_WASX] != 0.0) {  // sharded path: k_exch_apply already rewrote record and history
                 exch_prev = true;
             }
@@ -1434,43 +1407,26 @@ __global__ __launch_bounds__(WG * TPW, 4) void k_chain_iter(const KParams P, con
         const double u = t > 1 ? S.rb[cl * RBW] : 0.0;  // probs_acc[iter], :85
 
         const double old = rc[0];
-        double prob;
-        bool acc;
-        if (t == 1) {  // :326-332
-            prob = 1.0; acc = true; status = 1;
-        } else if (status < 0) {  // :336-338
-            prob = 0.0; acc = false;
-        } else {
-            if (!(value >= 0.0)) report_error(P, ERRK_NEGATIVE, t, gc);  // :341
-            const double e = smm_exp(atun * (old - value));   // (the contract exponential, smm_rng.hpp)
-            prob = (e != e) ? e : (e < 1.0 ? e : 1.0);  // minimum([1.0,e]), NaN propagates (:344)
-            if (!isfinite(prob)) { prob = 0.0; acc = false; status = -1; }  // :350-353
-            else if (!isfinite(old)) { prob = 1.0; acc = true; }            // :355-359
-            else { status = 1; acc = prob > u; }                            // strict >, :362-367
-        }
+        const AcceptDecision d = accept_decide(t == 1, status, value, old, atun, u, smm_exp);
+        if (d.negative) report_error(P, ERRK_NEGATIVE, t, gc);
+        const double prob = d.prob;
+        const bool acc = d.acc;
+        status = d.status;
         TS_MARK(7);
-        // set_acceptRate!, :253-257 (iteration t has exchanged==0 at this point)
-        const double rate = (double)(na + (acc ? 1 : 0)) / (double)(nn + 1);
+        const double rate = accept_rate(na, nn, acc);   // (iteration t has exchanged==0 at this point)
         double nsig = sig;
-        if (t > 1 && (t % P.sigma_update_steps) == 0)  // :381-390
-            nsig = (rate > 0.234) ? sig * (1.0 + P.sigma_adjust_by) : sig * (1.0 - P.sigma_adjust_by);
-        // set_eval!, :220-245
-        double bestv, currv, bestid;
-        if (t == 1) { bestv = value; currv = value; bestid = 1.0; }
-        else {
-            currv = acc ? value : old;  // curr_val[t-1] == value of the last accepted record
-            if (value < bp) { bestv = value; bestid = (double)t; }
-            else { bestv = bp; bestid = bpid; }
-        }
+        if (t > 1 && (t % P.sigma_update_steps) == 0) nsig = sigma_next(sig, rate, P.sigma_adjust_by);
+        // set_eval!: curr_val[t-1] == value of the last accepted record
+        const double currv = acc ? value : old;
+        const Best b = t == 1 ? Best{value, 1.0} : best_of(value, t, bp, bpid);
+        const double bestv = b.best, bestid = b.best_id;
         csb[CS_SIGMA] = nsig; csb[CS_RATE] = rate; csb[CS_NNOEX] = (double)nn; csb[CS_NACC] = (double)na;
         csb[CS_LACC] = acc ? 1.0 : 0.0; csb[CS_WASX] = 0.0; csb[CS_BEST] = bestv; csb[CS_BESTID] = bestid;
         csb[CS_BESTP] = bp; csb[CS_BESTPID] = bpid;  // best after t-1: needed if iteration t gets exchanged
-        hr[H_VALUE] = value; hr[H_PROB] = prob; hr[H_CURR] = currv; hr[H_BEST] = bestv; hr[H_BESTID] = bestid;
-        hr[H_EXCH] = 0.0; hr[H_ACC] = acc ? 1.0 : 0.0; hr[H_STATUS] = (double)status;
-        // the chain's last accepted record (lastAccepted :209-215) = input of the exchange step: its head here, the
+        history_head(hr, value, prob, currv, bestv, bestid, 0.0, acc ? 1.0 : 0.0, (double)status);
+        // the chain's last accepted record = input of the exchange step: its head here, the
         // parameter and moment arrays (and the history row's parameters) by all lanes of the chain below
-        if (acc) { ro[0] = value; ro[1] = prob; ro[2] = (double)status; }
-        else { ro[0] = rc[0]; ro[1] = rc[1]; ro[2] = rc[2]; }
+        record_head(ro, rc, acc, value, prob, status);
         const double vnew = acc ? value : old;
         P.vals_out[c] = vnew;
         if (P.slots17_out) {   // the chain's initial slots of k_exch_resolve_rows / _key (what k_exch_keys would make of vals[c])
@@ -1548,14 +1504,9 @@ __global__ void k_flush(const KParams P, const int t_next, const double* __restr
             const int tp = t_next - 1;
             const double* donor = rec_in + (size_t)s * RW;
             double* hrec = P.hrec + ((size_t)(tp - 1) * N + c) * HW;
-            const double value = donor[0];
-            double bestv, bestid;
-            if (value < csb[CS_BESTP]) { bestv = value; bestid = (double)tp; }
-            else { bestv = csb[CS_BESTP]; bestid = csb[CS_BESTPID]; }
-            hrec[H_VALUE] = value; hrec[H_PROB] = donor[1]; hrec[H_CURR] = value; hrec[H_BEST] = bestv;
-            hrec[H_BESTID] = bestid; hrec[H_EXCH] = (double)partner; hrec[H_ACC] = 1.0; hrec[H_STATUS] = donor[2];
+            const Best b = swapped_head(hrec, donor, partner, tp, csb + CS_BESTP);
             for (int k = 0; k < P.np + P.nm; ++k) hrec[H_PARAMS + k] = donor[3 + k];
-            csb[CS_BEST] = bestv; csb[CS_BESTID] = bestid;
+            csb[CS_BEST] = b.best; csb[CS_BESTID] = b.best_id;
         }
     } else if (csb[CS_WASX] != 0.0) {
         exch = true;
@@ -1638,10 +1589,7 @@ __global__ __launch_bounds__(WG) void k_eval_batch_noseed(const KParams P, const
             for (int wv = 1; wv < WG / 64; ++wv) tot = tot + smem[wv * nm + k];
             const double m = tot / (double)ns;
             simM[(size_t)k * M + i] = m;
-            double d = m - P.mom[k];
-            const double wk = P.w[k];
-            if (!isnan(wk)) d = d / wk;
-            const double v = d * d;
+            const double v = moment_sq(m, P.mom[k], P.w[k]);
             vsum = (k == 0) ? v : vsum + v;
         }
         value[i] = vsum / (double)nm;

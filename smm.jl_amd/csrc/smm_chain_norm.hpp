@@ -543,16 +543,13 @@ __device__ __forceinline__ void chain_iter_norm_body(const KParams& P, const int
             if (valid && t > 1) {
                 bool exch_prev = false;
                 if (partner != 0) {
-                    // set_eval!(ci, ej) of swap_ev_ij! as a history record: the chain's record of iteration t-1 is the donor's last
-                    // accepted one (accepted = true, the donor's prob/status), curr = donor value, best against iteration t-2 (:231-243)
+                    // the chain's record of iteration t-1 becomes the donor's last accepted one
                     exch_prev = true;
-                    const double value = rc[0];
-                    if (value < csq[4].x) { bp = value; bpid = (double)(t - 1); }
-                    else { bp = csq[4].x; bpid = csq[4].y; }
+                    const Best b = best_of(rc[0], t - 1, csq[4].x, csq[4].y);
+                    bp = b.best; bpid = b.best_id;
                     if (!poisoned) {
                         double hv[HW];
-                        hv[H_VALUE] = value; hv[H_PROB] = rc[1]; hv[H_CURR] = value; hv[H_BEST] = bp; hv[H_BESTID] = bpid;
-                        hv[H_EXCH] = (double)partner; hv[H_ACC] = 1.0; hv[H_STATUS] = rc[2];
+                        swapped_head(hv, rc, partner, b);
 #pragma unroll
                         for (int k = 0; k < 2 * NP; ++k) hv[H_PARAMS + k] = rc[3 + k];
                         if (HW > H_PARAMS + 2 * NP) hv[HW - 1] = 0.0;
@@ -719,7 +716,37 @@ __global__ __launch_bounds__(NORM_WG / 2, 4) void k_chain_iter_norm_p2p_rows_nar
     chain_iter_norm_body<NP, false, false, true, true, true, 1>(P, t, rec_in, rec_out, flags);
 }
 
-// objective value (ObjExamples.jl:79-110), doAcceptReject! (:324-392), set_eval! (:220-245) and the result blocks
+// objfunc_norm's finish by the four lanes of a chain's quad (this kernel and k_chain_persist_loc): lane r finishes moment r — wave totals
+// left to right, mean, weighted deviation —, the squares are added in moment order.  part: the chain's column of the partial sums
+// [moment][wave][NORM_CT]; failed: SMM_OBJ_NORM_FAILBOX's "exception" (smm_accept.hpp: in_failbox)
+template <int NP>
+__device__ __forceinline__ void norm_quad_finish(const bool failed, const int r, const double* part, const double ns, const double* mom,
+                                                 const double* w, double (&sm)[NP], double& value, int& status) {
+    if (failed) {
+#pragma unroll
+        for (int k = 0; k < NP; ++k) sm[k] = NAN;
+        value = -1.0;   // Eval() default, Eval.jl:84
+        status = -2;
+        return;
+    }
+    double mk = 0.0, vk = 0.0;
+    if (r < NP) {
+        double tot = part[(r * 8 + 0) * NORM_CT];
+#pragma unroll
+        for (int wv = 1; wv < 8; ++wv) tot = tot + part[(r * 8 + wv) * NORM_CT];
+        mk = tot / ns;
+        vk = moment_sq(mk, mom[r], w[r]);
+    }
+    sm[0] = quad_bcast<0>(mk);
+    double vsum = quad_bcast<0>(vk);
+    if constexpr (NP > 1) { sm[1] = quad_bcast<1>(mk); vsum = vsum + quad_bcast<1>(vk); }
+    if constexpr (NP > 2) { sm[2] = quad_bcast<2>(mk); vsum = vsum + quad_bcast<2>(vk); }
+    if constexpr (NP > 3) { sm[3] = quad_bcast<3>(mk); vsum = vsum + quad_bcast<3>(vk); }
+    value = vsum / (double)NP;
+    status = 1;
+}
+
+// objective value, the accept step (smm_accept.hpp) and the result blocks
 // (BIG: the kernel without an inline walk — the one large populations run: their stand-alone resolution takes its initial slots
 // from the accept step when the host says so, KParams::slots17_out)
 template <int NP, bool P2P, bool BIG>
@@ -744,62 +771,21 @@ __device__ inline void epilogue_norm(const KParams& P, const int t, double* __re
     for (int k = 0; k < NP; ++k) th[k] = s_theta[cl * NP + k];
     double value;
     int status;
-    if (P.obj == SMM_OBJ_NORM_FAILBOX && P.objp && th[0] >= P.objp[0] && th[0] <= P.objp[1]) {   // "exception": mprob.jl:183-186
-#pragma unroll
-        for (int k = 0; k < NP; ++k) sm[k] = NAN;
-        value = -1.0;   // Eval() default, Eval.jl:84
-        status = -2;
-    } else {
-        // lane r finishes moment r: wave totals left to right, mean, weighted deviation; the squares are added in moment order
-        double mk = 0.0, vk = 0.0;
-        if (r < NP) {
-            double tot = s_part[(r * 8 + 0) * CT + cl];
-#pragma unroll
-            for (int wv = 1; wv < 8; ++wv) tot = tot + s_part[(r * 8 + wv) * CT + cl];
-            mk = tot / (double)P.ns;
-            double d = mk - P.mom[r];
-            const double wk = P.w[r];
-            if (!isnan(wk)) d = d / wk;
-            vk = d * d;
-        }
-        double vsum = 0.0;
-        {
-            const double m0 = quad_bcast<0>(mk), v0 = quad_bcast<0>(vk);
-            sm[0] = m0; vsum = v0;
-            if constexpr (NP > 1) { const double m1 = quad_bcast<1>(mk), v1 = quad_bcast<1>(vk); sm[1] = m1; vsum = vsum + v1; }
-            if constexpr (NP > 2) { const double m2 = quad_bcast<2>(mk), v2 = quad_bcast<2>(vk); sm[2] = m2; vsum = vsum + v2; }
-            if constexpr (NP > 3) { const double m3 = quad_bcast<3>(mk), v3 = quad_bcast<3>(vk); sm[3] = m3; vsum = vsum + v3; }
-        }
-        value = vsum / (double)NP;
-        status = 1;
-    }
+    norm_quad_finish<NP>(P.obj == SMM_OBJ_NORM_FAILBOX && P.objp && in_failbox(th[0], P.objp), r, s_part + cl, (double)P.ns, P.mom, P.w,
+                         sm, value, status);
     const double old = rc[0];
-    double prob;
-    bool acc;
-    if (t == 1) {   // :326-332
-        prob = 1.0; acc = true; status = 1;
-    } else if (status < 0) {   // :336-338
-        prob = 0.0; acc = false;
-    } else {
-        if (!(value >= 0.0) && r == 0) report_error(P, ERRK_NEGATIVE, t, gc);   // :341
-        const double e = smm_exp(atun * (old - value));   // (the contract exponential, smm_rng.hpp)
-        prob = (e != e) ? e : (e < 1.0 ? e : 1.0);   // minimum([1.0,e]), NaN propagates (:344)
-        if (!isfinite(prob)) { prob = 0.0; acc = false; status = -1; }   // :350-353
-        else if (!isfinite(old)) { prob = 1.0; acc = true; }             // :355-359
-        else { status = 1; acc = prob > uu; }                            // strict >, :362-367
-    }
+    const AcceptDecision d = accept_decide(t == 1, status, value, old, atun, uu, smm_exp);
+    if (d.negative && r == 0) report_error(P, ERRK_NEGATIVE, t, gc);
+    const double prob = d.prob;
+    const bool acc = d.acc;
+    status = d.status;
     TS_MARK(7);
-    const double rate = (double)(na + (acc ? 1 : 0)) / (double)(nn + 1);   // set_acceptRate!, :253-257
+    const double rate = accept_rate(na, nn, acc);
     double nsig = sig;
-    if (t > 1 && (t % P.sigma_update_steps) == 0)   // :381-390
-        nsig = (rate > 0.234) ? sig * (1.0 + P.sigma_adjust_by) : sig * (1.0 - P.sigma_adjust_by);
-    double bestv, currv, bestid;   // set_eval!, :220-245
-    if (t == 1) { bestv = value; currv = value; bestid = 1.0; }
-    else {
-        currv = acc ? value : old;
-        if (value < bp) { bestv = value; bestid = (double)t; }
-        else { bestv = bp; bestid = bpid; }
-    }
+    if (t > 1 && (t % P.sigma_update_steps) == 0) nsig = sigma_next(sig, rate, P.sigma_adjust_by);
+    const double currv = acc ? value : old;   // (iteration 1 is accepted)
+    const Best b = t == 1 ? Best{value, 1.0} : best_of(value, t, bp, bpid);
+    const double bestv = b.best, bestid = b.best_id;
     const int pb = t & 1;
     if (r == 0) {
         const double v = acc ? value : old;
@@ -835,9 +821,9 @@ __device__ inline void epilogue_norm(const KParams& P, const int t, double* __re
         const double accd = acc ? 1.0 : 0.0;
         g_cs[r] = sel4(r, make_double2(nsig, rate), make_double2((double)nn, (double)na), make_double2(accd, 0.0), make_double2(bestv, bestid));
         if (r < 2) g_cs[4 + r] = r == 0 ? make_double2(bp, bpid) : make_double2(atun, pk[7]);
-        // the chain's last accepted record (lastAccepted :209-215) = input of the exchange step
+        // the chain's last accepted record = input of the exchange step
         double nr[RW];
-        nr[0] = acc ? value : rc[0]; nr[1] = acc ? prob : rc[1]; nr[2] = acc ? (double)status : rc[2];
+        record_head(nr, rc, acc, value, prob, status);
 #pragma unroll
         for (int k = 0; k < NP; ++k) { nr[3 + k] = acc ? th[k] : rc[3 + k]; nr[3 + NP + k] = acc ? sm[k] : rc[3 + NP + k]; }
         if (RW > 3 + 2 * NP) nr[RW - 1] = 0.0;
@@ -855,8 +841,7 @@ __device__ inline void epilogue_norm(const KParams& P, const int t, double* __re
             }
         }
         double hv[HW];
-        hv[H_VALUE] = value; hv[H_PROB] = prob; hv[H_CURR] = currv; hv[H_BEST] = bestv; hv[H_BESTID] = bestid;
-        hv[H_EXCH] = 0.0; hv[H_ACC] = accd; hv[H_STATUS] = (double)status;
+        history_head(hv, value, prob, currv, bestv, bestid, 0.0, accd, (double)status);
 #pragma unroll
         for (int k = 0; k < NP; ++k) { hv[H_PARAMS + k] = th[k]; hv[H_PARAMS + NP + k] = sm[k]; }
         if (HW > H_PARAMS + 2 * NP) hv[HW - 1] = 0.0;

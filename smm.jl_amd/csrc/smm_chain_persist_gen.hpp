@@ -432,31 +432,18 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistArgs
             __builtin_amdgcn_wave_barrier();
             value = s_uval[cl];
             status = (int)s_ust[cl];
-            const bool failed = status < 0;          // the objective's "exception": status -2, rejected with prob 0 (mprob.jl:183-186, AlgoBGP.jl:336-338)
+            // (the objective's "exception": a status < 0, rejected with prob 0 — mprob.jl:183-186)
 #else
-            for (int i = 0; i + 1 < np; ++i) {
-                const double a = thp[i], b = thp[i + 1];
-                const double t1_ = b - a * a;
-                const double t2_ = 1.0 - a;
-                const double term = 100.0 * (t1_ * t1_) + t2_ * t2_;
-                value = (i == 0) ? term : value + term;
-            }
-            const bool failed = false;
+            value = banana_value(thp, np);
 #endif
             const double atun = cs[CS_ATUN];
             const double uu = rows[0];
             const double old = rin[0];
-            double prob;
-            bool acc;
-            if (failed) { prob = 0.0; acc = false; }                     // :336-338
-            else {
-                if (!(value >= 0.0) && r == 0) pr_report(A.err, ERRK_NEGATIVE, t, c);   // :341
-                const double e = pr_exp(atun * (old - value));
-                prob = (e != e) ? e : (e < 1.0 ? e : 1.0);   // minimum([1.0,e]), NaN propagates (:344)
-                if (!isfinite(prob)) { prob = 0.0; acc = false; status = -1; }   // :350-353
-                else if (!isfinite(old)) { prob = 1.0; acc = true; }             // :355-359
-                else { status = 1; acc = prob > uu; }                            // strict >, :362-367
-            }
+            const AcceptDecision d = accept_decide(false, status, value, old, atun, uu, pr_exp);
+            if (d.negative && r == 0) pr_report(A.err, ERRK_NEGATIVE, t, c);
+            const double prob = d.prob;
+            const bool acc = d.acc;
+            status = d.status;
             const double accd = acc ? 1.0 : 0.0;
             const double v = acc ? value : old;
             // ---- the chain's last accepted record (lastAccepted :209-215) = input of the exchange step: by the quad's lanes into LDS ----
@@ -469,7 +456,7 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistArgs
                 for (int k = r; k < np; k += 4) rout[3 + k] = acc ? thp[k] : rin[3 + k];
                 for (int k = r; k < nm; k += 4) rout[3 + np + k] = acc ? msim[k] : rin[3 + np + k];
                 if (r == 0) {
-                    rout[0] = v; rout[1] = acc ? prob : rin[1]; rout[2] = acc ? (double)status : rin[2];
+                    record_head(rout, rin, acc, value, prob, status);
                     if (RW > 3 + np + nm) rout[RW - 1] = 0.0;
                 }
             }
@@ -498,34 +485,30 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistArgs
             const double sig = sigma;
             int nn = (int)cs[CS_NNOEX], na = (int)cs[CS_NACC];
             double bp = cs[CS_BEST], bpid = cs[CS_BESTID];
-            if (partner != 0) {   // set_eval!(ci, ej) of swap_ev_ij! as a history record (:231-243)
-                const double dv = old;
-                if (dv < cs[CS_BESTP]) { bp = dv; bpid = (double)(t - 1); }
-                else { bp = cs[CS_BESTP]; bpid = cs[CS_BESTPID]; }
+            if (partner != 0) {   // the record of iteration t - 1 becomes the donor's (rin: the record the chain continues from)
+                const Best b = best_of(old, t - 1, cs[CS_BESTP], cs[CS_BESTPID]);
+                bp = b.best; bpid = b.best_id;
                 double* hx = s_xrow + cl * HW;
                 if (r == 0) {
-                    hx[H_VALUE] = dv; hx[H_PROB] = rin[1]; hx[H_CURR] = dv; hx[H_BEST] = bp; hx[H_BESTID] = bpid;
-                    hx[H_EXCH] = (double)partner; hx[H_ACC] = 1.0; hx[H_STATUS] = rin[2];
+                    swapped_head(hx, rin, partner, b);
                     if (HW > H_PARAMS + np + nm) hx[HW - 1] = 0.0;
                 }
                 for (int k = r; k < np + nm; k += 4) hx[H_PARAMS + k] = rin[3 + k];
-            } else { nn += 1; na += (int)cs[CS_LACC]; }   // set_acceptRate!, :253-257
+            } else { nn += 1; na += (int)cs[CS_LACC]; }   // (exchanged iterations do not count in the accept rate)
             double nsig = sig;
             const bool upd = (t % A.sigma_update_steps) == 0;
             double rate = 0.0;
-            if (upd || t == t1) {
-                rate = (double)(na + (acc ? 1 : 0)) / (double)(nn + 1);
-                if (upd) nsig = (rate > 0.234) ? sig * (1.0 + A.sigma_adjust_by) : sig * (1.0 - A.sigma_adjust_by);   // :381-390
+            if (upd || t == t1) {   // (the rate is read at an update and behind the launch only)
+                rate = accept_rate(na, nn, acc);
+                if (upd) nsig = sigma_next(sig, rate, A.sigma_adjust_by);
             }
-            double bestv, bestid;
             const double currv = acc ? value : old;
-            if (value < bp) { bestv = value; bestid = (double)t; }
-            else { bestv = bp; bestid = bpid; }
+            const Best b = best_of(value, t, bp, bpid);
+            const double bestv = b.best, bestid = b.best_id;
             // the history row (through LDS: wave 3 stores it)
             double* hv = s_hrow + cl * HW;
             if (r == 0) {
-                hv[H_VALUE] = value; hv[H_PROB] = prob; hv[H_CURR] = currv; hv[H_BEST] = bestv; hv[H_BESTID] = bestid;
-                hv[H_EXCH] = 0.0; hv[H_ACC] = accd; hv[H_STATUS] = (double)status;
+                history_head(hv, value, prob, currv, bestv, bestid, 0.0, accd, (double)status);
                 if (HW > H_PARAMS + np + nm) hv[HW - 1] = 0.0;
             }
             for (int k = r; k < np; k += 4) hv[H_PARAMS + k] = thp[k];

@@ -727,7 +727,7 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
                 for (int f = 0; f < RW; ++f) rc2[f] = rr[pr_ring_index<NP>(f)];
             }
             if (lane == 0) announce(rel);   // every read of the ring's last entry is done
-            // ---- objective value (ObjExamples.jl:79-110), doAcceptReject! (:324-392) ----
+            // ---- objective value, the accept decision (smm_accept.hpp; the failbox bounds, moments, weights and ns staged in s_const) ----
             const double atun = st[CS_ATUN];
             const double uu = Y.s_rng[((t & 1) * 64 + lane) * RNGW];
             double th2[NP], sm[NP];
@@ -735,49 +735,18 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
             for (int k = 0; k < NP; ++k) th2[k] = Y.s_theta[cl * NP + k];
             double value;
             int status;
-            if (th2[0] >= Y.s_const[4 * NP] && th2[0] <= Y.s_const[4 * NP + 1]) {   // NORM_FAILBOX's "exception": mprob.jl:183-186
-#pragma unroll
-                for (int k = 0; k < NP; ++k) sm[k] = NAN;
-                value = -1.0;   // Eval() default, Eval.jl:84
-                status = -2;
-            } else {
-                double mk = 0.0, vk = 0.0;
-                if (r < NP) {
-                    double tot = Y.s_part[(r * 8 + 0) * CT + cl];
-#pragma unroll
-                    for (int wv = 1; wv < 8; ++wv) tot = tot + Y.s_part[(r * 8 + wv) * CT + cl];
-                    mk = tot / Y.s_const[4 * NP + 2];
-                    double d = mk - Y.s_const[2 * NP + r];
-                    const double wk = Y.s_const[3 * NP + r];
-                    if (!isnan(wk)) d = d / wk;
-                    vk = d * d;
-                }
-                double vsum = 0.0;
-                {
-                    const double m0 = quad_bcast<0>(mk), v0 = quad_bcast<0>(vk);
-                    sm[0] = m0; vsum = v0;
-                    if constexpr (NP > 1) { const double m1 = quad_bcast<1>(mk), v1 = quad_bcast<1>(vk); sm[1] = m1; vsum = vsum + v1; }
-                }
-                value = vsum / (double)NP;
-                status = 1;
-            }
+            norm_quad_finish<NP>(in_failbox(th2[0], Y.s_const + 4 * NP), r, Y.s_part + cl, Y.s_const[4 * NP + 2],
+                                 Y.s_const + 2 * NP, Y.s_const + 3 * NP, sm, value, status);
             const double old = rc2[0];
-            double prob;
-            bool acc;
-            if (status < 0) {   // :336-338
-                prob = 0.0; acc = false;
-            } else {
-                if (!(value >= 0.0) && r == 0) pr_report(A.err, ERRK_NEGATIVE, t, (int)c0g + cl);   // :341
-                const double e = pr_exp(atun * (old - value));
-                prob = (e != e) ? e : (e < 1.0 ? e : 1.0);   // minimum([1.0,e]), NaN propagates (:344)
-                if (!isfinite(prob)) { prob = 0.0; acc = false; status = -1; }   // :350-353
-                else if (!isfinite(old)) { prob = 1.0; acc = true; }             // :355-359
-                else { status = 1; acc = prob > uu; }                            // strict >, :362-367
-            }
+            const AcceptDecision d = accept_decide(false, status, value, old, atun, uu, pr_exp);
+            if (d.negative && r == 0) pr_report(A.err, ERRK_NEGATIVE, t, (int)c0g + cl);
+            const double prob = d.prob;
+            const bool acc = d.acc;
+            status = d.status;
             const double accd = acc ? 1.0 : 0.0;
             const double v = acc ? value : old;
-            double nr[RW];   // the chain's last accepted record (lastAccepted :209-215) = input of the exchange step
-            nr[0] = v; nr[1] = acc ? prob : rc2[1]; nr[2] = acc ? (double)status : rc2[2];
+            double nr[RW];   // the chain's last accepted record = input of the exchange step
+            record_head(nr, rc2, acc, value, prob, status);
 #pragma unroll
             for (int k = 0; k < NP; ++k) { nr[3 + k] = acc ? th2[k] : rc2[3 + k]; nr[3 + NP + k] = acc ? sm[k] : rc2[3 + NP + k]; }
             if (RW > 3 + 2 * NP) nr[RW - 1] = 0.0;
@@ -798,30 +767,27 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
             int nn = (int)st[CS_NNOEX], na = (int)st[CS_NACC];
             double bp = st[CS_BEST], bpid = st[CS_BESTID];
             if (partner != 0) {
-                // set_eval!(ci, ej) of swap_ev_ij! as a history record (:231-243)
-                const double dv = rc2[0];
-                if (dv < st[CS_BESTP]) { bp = dv; bpid = (double)(t - 1); }
-                else { bp = st[CS_BESTP]; bpid = st[CS_BESTPID]; }
+                // the record of iteration t - 1 becomes the donor's
+                const Best b = best_of(rc2[0], t - 1, st[CS_BESTP], st[CS_BESTPID]);
+                bp = b.best; bpid = b.best_id;
                 if (r == 0) {
                     double* hx = Y.s_xrow + cl * HW;
-                    hx[H_VALUE] = dv; hx[H_PROB] = rc2[1]; hx[H_CURR] = dv; hx[H_BEST] = bp; hx[H_BESTID] = bpid;
-                    hx[H_EXCH] = (double)partner; hx[H_ACC] = 1.0; hx[H_STATUS] = rc2[2];
+                    swapped_head(hx, rc2, partner, b);
 #pragma unroll
                     for (int k = 0; k < 2 * NP; ++k) hx[H_PARAMS + k] = rc2[3 + k];
                     if (HW > H_PARAMS + 2 * NP) hx[HW - 1] = 0.0;
                 }
-            } else { nn += 1; na += (int)st[CS_LACC]; }   // set_acceptRate!, :253-257 (exchanged iterations do not count)
+            } else { nn += 1; na += (int)st[CS_LACC]; }   // (exchanged iterations do not count in the accept rate)
             double nsig = sig;
             const bool upd = (t % A.sigma_update_steps) == 0;
-            if (upd || t == t1) {
-                const double rate = (double)(na + (acc ? 1 : 0)) / (double)(nn + 1);   // set_acceptRate!, :253-257
-                if (upd) nsig = (rate > 0.234) ? sig * (1.0 + A.sigma_adjust_by) : sig * (1.0 - A.sigma_adjust_by);   // :381-390
+            if (upd || t == t1) {   // (the rate is read at an update and behind the launch only)
+                const double rate = accept_rate(na, nn, acc);
+                if (upd) nsig = sigma_next(sig, rate, A.sigma_adjust_by);
                 if (r == 0) st[CS_RATE] = rate;
             }
-            double bestv, bestid;
             const double currv = acc ? value : old;
-            if (value < bp) { bestv = value; bestid = (double)t; }
-            else { bestv = bp; bestid = bpid; }
+            const Best b = best_of(value, t, bp, bpid);
+            const double bestv = b.best, bestid = b.best_id;
             if (r == 0) {
                 // the tile's own slots and parameters of the next walk (a donor may be a chain of the same tile)
                 if constexpr (WIDE) ((uint4*)lds)[cl] = make_uint4((uint32_t)__double2loint(v), (uint32_t)__double2hiint(v), (uint32_t)cl, 0u);
@@ -833,8 +799,7 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
 #pragma unroll
                 for (int f = 0; f < RW; ++f) st[PR_STW + f] = nr[f];
                 double* hv = Y.s_hrow + cl * HW;
-                hv[H_VALUE] = value; hv[H_PROB] = prob; hv[H_CURR] = currv; hv[H_BEST] = bestv; hv[H_BESTID] = bestid;
-                hv[H_EXCH] = 0.0; hv[H_ACC] = accd; hv[H_STATUS] = (double)status;
+                history_head(hv, value, prob, currv, bestv, bestid, 0.0, accd, (double)status);
 #pragma unroll
                 for (int k = 0; k < NP; ++k) { hv[H_PARAMS + k] = th2[k]; hv[H_PARAMS + NP + k] = sm[k]; }
                 if (HW > H_PARAMS + 2 * NP) hv[HW - 1] = 0.0;

@@ -458,13 +458,11 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistArgs A) 
             int nn = (int)csb[CS_NNOEX], na = (int)csb[CS_NACC];
             double bp = csb[CS_BEST], bpid = csb[CS_BESTID];
             if (partner != 0) {
-                const double dv = rin[0];
-                if (dv < csb[CS_BESTP]) { bp = dv; bpid = (double)(t - 1); }
-                else { bp = csb[CS_BESTP]; bpid = csb[CS_BESTPID]; }
+                const Best b = best_of(rin[0], t - 1, csb[CS_BESTP], csb[CS_BESTPID]);
+                bp = b.best; bpid = b.best_id;
                 if (!SH) {   // (SH: behind the objective, once the rest of the donor's record is there)
                     double* hx = s_xrow + cc * HW;
-                    hx[H_VALUE] = dv; hx[H_PROB] = rin[1]; hx[H_CURR] = dv; hx[H_BEST] = bp; hx[H_BESTID] = bpid;
-                    hx[H_EXCH] = (double)partner; hx[H_ACC] = 1.0; hx[H_STATUS] = rin[2];
+                    swapped_head(hx, rin, partner, b);
                     if (HW > H_PARAMS + np + nm) hx[HW - 1] = 0.0;
                 }
             } else { nn += 1; na += (int)csb[CS_LACC]; }
@@ -581,7 +579,7 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistArgs A) 
         unsigned long long ts4 = 0;
         if (A.ts && tid == 0) ts4 = wall_clock64();
         // ---- the moments of a chain (wave totals -> mean -> squared weighted deviation) by its 32 lanes (ObjExamples.jl:79-100) ----
-        const bool failed = KIND == 1 && A.failbox && valid && s_theta[cc * np] >= A.objp[0] && s_theta[cc * np] <= A.objp[1];   // mprob.jl:183-186
+        const bool failed = KIND == 1 && A.failbox && valid && in_failbox(s_theta[cc * np], A.objp);
 #ifdef SMM_TILE_USER
         if (chain_lane) {   // the groups' totals left to right (numerical contract), then the user's finish: moments, value, status
             const int nwv = A.u_lanes / 64;
@@ -608,11 +606,9 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistArgs A) 
                     double tot = s_part[((size_t)0 * nmp + k) * 16 + c16];
 #pragma unroll
                     for (int wv = 1; wv < WG / 64; ++wv) tot = tot + s_part[((size_t)wv * nmp + k) * 16 + c16];
-                    double d = tot - s_mom[k];
-                    const double wk = s_w[k];
-                    if (!isnan(wk)) d = d / wk;
+                    const double v = moment_sq(tot, s_mom[k], s_w[k]);
                     s_sm[c16 * nm + k] = tot;
-                    s_vk[c16 * nm + k] = d * d;
+                    s_vk[c16 * nm + k] = v;
                 }
             }
         } else if (valid) {
@@ -621,11 +617,9 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistArgs A) 
 #pragma unroll
                 for (int wv = 1; wv < WG / 64; ++wv) tot = tot + s_part[(wv * CT + cc) * nm + k];
                 const double m = tot / (double)A.ns;
-                double d = m - s_mom[k];
-                const double wk = s_w[k];
-                if (!isnan(wk)) d = d / wk;
+                const double v = moment_sq(m, s_mom[k], s_w[k]);
                 s_sm[cc * nm + k] = failed ? NAN : m;
-                s_vk[cc * nm + k] = d * d;
+                s_vk[cc * nm + k] = v;
             }
         }
 #endif
@@ -645,56 +639,34 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistArgs A) 
             if (failed) { value = -1.0; status = -2; }   // Eval() default, Eval.jl:84
 #endif
             else {
-                double vsum = 0.0;
-                int k = 0;
-                for (; k + 8 <= nm; k += 8) {
-                    double v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = vk[k + u];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) vsum = (k + u == 0) ? v[u] : vsum + v[u];
-                }
-                for (; k < nm; ++k) vsum = (k == 0) ? vk[k] : vsum + vk[k];
-                value = vsum / (double)nm;
+                value = sum_in_order(vk, nm) / (double)nm;
                 status = 1;
             }
             const double sig = csb[CS_SIGMA], bp = csb[CS_BEST], bpid = csb[CS_BESTID], atun = csb[CS_ATUN];
             const int nn = (int)csb[CS_NNOEX], na = (int)csb[CS_NACC];
             const double old = rin[0];
-            double prob;
-            bool acc;
-            if (status < 0) {   // :336-338
-                prob = 0.0; acc = false;
-            } else {
-                if (!(value >= 0.0)) pr_report(A.err, ERRK_NEGATIVE, t, cg);   // :341
-                const double e = pr_exp(atun * (old - value));
-                prob = (e != e) ? e : (e < 1.0 ? e : 1.0);   // minimum([1.0,e]), NaN propagates (:344)
-                if (!isfinite(prob)) { prob = 0.0; acc = false; status = -1; }   // :350-353
-                else if (!isfinite(old)) { prob = 1.0; acc = true; }             // :355-359
-                else { status = 1; acc = prob > uu; }                            // strict >, :362-367
-            }
-            const double rate = (double)(na + (acc ? 1 : 0)) / (double)(nn + 1);   // set_acceptRate!, :253-257
+            const AcceptDecision d = accept_decide(false, status, value, old, atun, uu, pr_exp);
+            if (d.negative) pr_report(A.err, ERRK_NEGATIVE, t, cg);
+            const double prob = d.prob;
+            const bool acc = d.acc;
+            status = d.status;
+            const double rate = accept_rate(na, nn, acc);
             double nsig = sig;
-            if ((t % A.sigma_update_steps) == 0) nsig = (rate > 0.234) ? sig * (1.0 + A.sigma_adjust_by) : sig * (1.0 - A.sigma_adjust_by);   // :381-390
+            if ((t % A.sigma_update_steps) == 0) nsig = sigma_next(sig, rate, A.sigma_adjust_by);
             const double currv = acc ? value : old;
-            double bestv, bestid;
-            if (value < bp) { bestv = value; bestid = (double)t; }
-            else { bestv = bp; bestid = bpid; }
-            csb[CS_SIGMA] = nsig; csb[CS_RATE] = rate; csb[CS_LACC] = acc ? 1.0 : 0.0; csb[CS_WASX] = 0.0; csb[CS_BEST] = bestv; csb[CS_BESTID] = bestid;
+            const Best b = best_of(value, t, bp, bpid);
+            csb[CS_SIGMA] = nsig; csb[CS_RATE] = rate; csb[CS_LACC] = acc ? 1.0 : 0.0; csb[CS_WASX] = 0.0; csb[CS_BEST] = b.best; csb[CS_BESTID] = b.best_id;
             csb[CS_BESTP] = bp; csb[CS_BESTPID] = bpid;   // best after t - 1: needed if iteration t gets exchanged
-            if (SH && partner != 0) {   // set_eval!(ci, ej) of swap_ev_ij! as a history record (:231-243): the donor's record is whole now
+            if (SH && partner != 0) {   // the swapped row of iteration t - 1 (its best settled ahead of the proposal): the donor's record is whole now
                 double* hx = s_xrow + cc * HW;
-                hx[H_VALUE] = old; hx[H_PROB] = rin[1]; hx[H_CURR] = old; hx[H_BEST] = bp; hx[H_BESTID] = bpid;
-                hx[H_EXCH] = (double)partner; hx[H_ACC] = 1.0; hx[H_STATUS] = rin[2];
+                swapped_head(hx, rin, partner, Best{bp, bpid});
                 if (HW > H_PARAMS + np + nm) hx[HW - 1] = 0.0;
             }
             double* hr = s_hrow + cc * HW;
-            hr[H_VALUE] = value; hr[H_PROB] = prob; hr[H_CURR] = currv; hr[H_BEST] = bestv; hr[H_BESTID] = bestid;
-            hr[H_EXCH] = 0.0; hr[H_ACC] = acc ? 1.0 : 0.0; hr[H_STATUS] = (double)status;
+            history_head(hr, value, prob, currv, b.best, b.best_id, 0.0, acc ? 1.0 : 0.0, (double)status);
             if (HW > H_PARAMS + np + nm) hr[HW - 1] = 0.0;
-            // the chain's last accepted record (lastAccepted :209-215) = input of the exchange step: its head here, the arrays below
-            if (acc) { rout[0] = value; rout[1] = prob; rout[2] = (double)status; }
-            else { rout[0] = rin[0]; rout[1] = rin[1]; rout[2] = rin[2]; }
+            // the chain's last accepted record = input of the exchange step: its head here, the arrays below
+            record_head(rout, rin, acc, value, prob, status);
             if (RW > 3 + np + nm) rout[RW - 1] = 0.0;
             const double vnew = acc ? value : old;
             slots[cc] = make_uint4((uint32_t)__double2loint(vnew), (uint32_t)__double2hiint(vnew), (uint32_t)cc, 0u);   // the tile's own slots of the next walk

@@ -725,10 +725,11 @@ __global__ __launch_bounds__(XWG) void k_exch_resolve_any(const KParams P, const
         P.xres[g] = (unsigned long long)(unsigned)P.xsrc[g] | ((unsigned long long)(unsigned)P.xpartner[g] << 32);
 }
 
-// k_exch_apply (sharded path): set_eval!(ci, ej) + set_exchanged! of swap_ev_ij! (AlgoBGP.jl:734-749)
-// for the local chains, reading the donor records from the all-gathered buffer [Ng][RW];
-// rec = this shard's own post-accept records [N][RW], updated in place.
-__global__ void k_exch_apply(const KParams P, const int t, const double* __restrict__ gathered, double* __restrict__ rec) {
+// the sharded paths' set_eval!(ci, ej) + set_exchanged! of swap_ev_ij! (AlgoBGP.jl:734-749) for the local chains, one thread per chain:
+// rec = this shard's own post-accept records [N][RW], updated in place; rows [.][RW]: the donors' records, donor_row(c, s): the row of
+// the donor of chain c, global chain s
+template <class DonorRow>
+__device__ inline void exch_apply_chain(const KParams& P, const int t, const double* __restrict__ rows, double* __restrict__ rec, DonorRow donor_row) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= P.N) return;
     if (*(const volatile unsigned long long*)P.err != ERR_NONE) return;   // the run stopped at the failing iteration
@@ -736,19 +737,18 @@ __global__ void k_exch_apply(const KParams P, const int t, const double* __restr
     const unsigned long long xr = P.xres[P.offset + c];
     const int partner = (int)(xr >> 32);
     if (partner == 0) return;
-    const int s = (int)(unsigned)(xr & 0xffffffffu);
-    const double* __restrict__ donor = gathered + (size_t)s * RW;
+    const double* __restrict__ donor = rows + (size_t)donor_row(c, (int)(unsigned)(xr & 0xffffffffu)) * RW;
     double* csb = P.cs + (size_t)c * CSW;
     double* hrec = P.hrec + ((size_t)(t - 1) * N + c) * HW;
-    const double value = donor[0];
-    double bestv, bestid;
-    if (value < csb[CS_BESTP]) { bestv = value; bestid = (double)t; }
-    else { bestv = csb[CS_BESTP]; bestid = csb[CS_BESTPID]; }
-    csb[CS_BEST] = bestv; csb[CS_BESTID] = bestid; csb[CS_WASX] = 1.0;
-    hrec[H_VALUE] = value; hrec[H_PROB] = donor[1]; hrec[H_CURR] = value; hrec[H_BEST] = bestv;
-    hrec[H_BESTID] = bestid; hrec[H_EXCH] = (double)partner; hrec[H_ACC] = 1.0; hrec[H_STATUS] = donor[2];
+    const Best b = best_of(donor[0], t, csb + CS_BESTP);
+    csb[CS_BEST] = b.best; csb[CS_BESTID] = b.best_id; csb[CS_WASX] = 1.0;
+    swapped_head(hrec, donor, partner, b);
     for (int k = 0; k < P.np + P.nm; ++k) hrec[H_PARAMS + k] = donor[3 + k];
     for (int f = 0; f < RW; ++f) rec[(size_t)c * RW + f] = donor[f];
+}
+// k_exch_apply: the donors' records in the all-gathered buffer [Ng][RW], in global chain order
+__global__ void k_exch_apply(const KParams P, const int t, const double* __restrict__ gathered, double* __restrict__ rec) {
+    exch_apply_chain(P, t, gathered, rec, [](int, int s) { return s; });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1352,23 +1352,5 @@ __global__ void k_a2a_pack(const KParams P, const int G, const int cap, const in
 }
 __global__ void k_a2a_apply(const KParams P, const int t, const double* __restrict__ recv, const int32_t* __restrict__ rowidx,
                             double* __restrict__ rec) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= P.N) return;
-    if (*(const volatile unsigned long long*)P.err != ERR_NONE) return;   // the run stopped at the failing iteration
-    const int N = P.N, RW = P.RW, HW = P.HW;
-    const unsigned long long xr = P.xres[P.offset + c];
-    const int partner = (int)(xr >> 32);
-    if (partner == 0) return;
-    const double* __restrict__ donor = recv + (size_t)rowidx[c] * RW;
-    double* csb = P.cs + (size_t)c * CSW;
-    double* hrec = P.hrec + ((size_t)(t - 1) * N + c) * HW;
-    const double value = donor[0];
-    double bestv, bestid;
-    if (value < csb[CS_BESTP]) { bestv = value; bestid = (double)t; }
-    else { bestv = csb[CS_BESTP]; bestid = csb[CS_BESTPID]; }
-    csb[CS_BEST] = bestv; csb[CS_BESTID] = bestid; csb[CS_WASX] = 1.0;
-    hrec[H_VALUE] = value; hrec[H_PROB] = donor[1]; hrec[H_CURR] = value; hrec[H_BEST] = bestv;
-    hrec[H_BESTID] = bestid; hrec[H_EXCH] = (double)partner; hrec[H_ACC] = 1.0; hrec[H_STATUS] = donor[2];
-    for (int k = 0; k < P.np + P.nm; ++k) hrec[H_PARAMS + k] = donor[3 + k];
-    for (int f = 0; f < RW; ++f) rec[(size_t)c * RW + f] = donor[f];
+    exch_apply_chain(P, t, recv, rec, [&](int c, int) { return rowidx[c]; });   // the donors' records as received [G][cap][RW]: each chain's row by index
 }

@@ -12,8 +12,8 @@ constexpr int P2P_MAXG = 8;           // ranks of the p2p sharded form (one node
 constexpr int CSW = 16;
 enum : int { CS_SIGMA = 0, CS_RATE, CS_NNOEX, CS_NACC, CS_LACC, CS_WASX, CS_BEST, CS_BESTID, CS_BESTP, CS_BESTPID, CS_ATUN,
              CS_PARTNER /* LDS only */ };
-// history record
-enum : int { H_VALUE = 0, H_PROB, H_CURR, H_BEST, H_BESTID, H_EXCH, H_ACC, H_STATUS, H_PARAMS };
+// history record (H_*), and the rules of the accept step that fill it
+#include "smm_accept.hpp"
 
 // error word: min over (iter<<34 | chain<<2 | kind); 1 negative objective, 2 no draw, 3 internal
 constexpr unsigned long long ERR_NONE = ~0ull;

@@ -99,8 +99,7 @@ __global__ __launch_bounds__(64 * POP_WPB) void k_pop_select(const KParams P, co
     for (int f = 3 + np + nm + lane; f < P.RW; f += 64) ro[f] = 0.0;
     if (lane == 0) {
         // doAcceptReject! at iteration 1 (AlgoBGP.jl:326-332): accepted with prob 1 and status 1, whatever the evaluation said
-        hr[H_VALUE] = value; hr[H_PROB] = 1.0; hr[H_CURR] = value; hr[H_BEST] = value; hr[H_BESTID] = 1.0;
-        hr[H_EXCH] = 0.0; hr[H_ACC] = 1.0; hr[H_STATUS] = 1.0;
+        history_head(hr, value, 1.0, value, value, 1.0, 0.0, 1.0, 1.0);
         ro[0] = value; ro[1] = 1.0; ro[2] = 1.0;
         double* csb = P.cs + (size_t)c * CSW;        // (sigma and acc_tuner stay: iteration 1 updates neither)
         csb[CS_RATE] = 1.0; csb[CS_NNOEX] = 1.0; csb[CS_NACC] = 1.0; csb[CS_LACC] = 0.0; csb[CS_WASX] = 0.0;

@@ -12,7 +12,7 @@
 //                       are reduced by a transposed wave reduction and combined through LDS.
 //   k_exch_resolve_*  : the same exchange resolution as a kernel of one workgroup (sharded path, larger
 //                       populations, and whenever the result is needed before the next chain kernel).
-// Files: smm_params.hpp (parameter block, layouts), smm_chain.hpp (chain kernel and its parts), smm_lookahead.hpp (k_pregen_rng,
+// Files: smm_params.hpp (parameter block, layouts), smm_accept.hpp (the accept step's rules, written once for every kernel), smm_chain.hpp (chain kernel and its parts), smm_lookahead.hpp (k_pregen_rng,
 // k_exch_plan), smm_exchange.hpp (stand-alone exchange kernels), this file (host: contexts, forms, choosers, windows, the call frame), smm_run_host.hpp (the run's host side:
 // stepping, settling, the sharded protocol), smm_reducers_host.hpp (the history reducers' host side), smm_population_host.hpp (the starting population's).
 // Everything that does not depend on the chains' state is produced ahead of the dependent loop by
@@ -1863,10 +1863,7 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
         }
         {   // history: NaN values, curr/best = Inf, best_id = -1, exchanged = accepted = status = 0
             std::vector<double> row((size_t)N * P.HW, NAN);
-            for (int i = 0; i < N; ++i) {
-                double* h = row.data() + (size_t)i * P.HW;
-                h[H_CURR] = INFINITY; h[H_BEST] = INFINITY; h[H_BESTID] = -1.0; h[H_EXCH] = 0.0; h[H_ACC] = 0.0; h[H_STATUS] = 0.0;
-            }
+            for (int i = 0; i < N; ++i) history_head(row.data() + (size_t)i * P.HW, NAN, NAN, INFINITY, INFINITY, -1.0, 0.0, 0.0, 0.0);
             P.hrec = dalloc<double>(c, TN * P.HW);
             // (one row from the host, then doubling copies on the device: a long history — bench.py's repetitions hold 50 000 iterations — is filled
             // at HBM speed instead of row by row over PCIe)
@@ -2123,10 +2120,8 @@ int smm_set_state(void* ctx, const smm_state_t* s, const smm_history_t* h) {
             const size_t o = (size_t)t * N;
             for (size_t i = 0; i < N; ++i) {
                 double* hr = row.data() + i * HW;
-                hr[H_VALUE] = h->value[o + i]; hr[H_PROB] = h->prob[o + i]; hr[H_CURR] = h->curr_val[o + i];
-                hr[H_BEST] = h->best_val[o + i]; hr[H_BESTID] = (double)h->best_id[o + i];
-                hr[H_EXCH] = (double)h->exchanged[o + i]; hr[H_ACC] = (double)h->accepted[o + i];
-                hr[H_STATUS] = (double)h->status[o + i];
+                history_head(hr, h->value[o + i], h->prob[o + i], h->curr_val[o + i], h->best_val[o + i], (double)h->best_id[o + i],
+                             (double)h->exchanged[o + i], (double)h->accepted[o + i], (double)h->status[o + i]);
                 for (size_t k = 0; k < np; ++k) hr[H_PARAMS + k] = h->params[((size_t)t * np + k) * N + i];
                 for (size_t k = 0; k < nm; ++k) hr[H_PARAMS + np + k] = h->sim_moments[((size_t)t * nm + k) * N + i];
             }

@@ -266,3 +266,22 @@ def test_the_run_lives_in_the_run_host_file_with_one_frame_and_one_rule_book():
     assert everything.count("k_flush,") == 1 and "void launch_flush(" in run
     assert not re.findall(r"c->kev[01] = |c->ext_(?:rec_in|rec_out|vals_out) = ", main + code["smm_reducers_host.hpp"] + code["smm_population_host.hpp"])
     assert len(re.findall(r"c->kev0 = ", run)) == 2 and len(re.findall(r"c->ext_rec_in = ", run)) == 2   # (the two scope objects)
+
+
+def test_the_accept_step_is_written_once_in_smm_accept_hpp():
+    """What a chain does at the end of an iteration — the accept decision, the accept rate and the sigma update, best and best_id, the head
+    of a history row, the swapped row, the banana — is written in smm_accept.hpp and nowhere else: the five chain kernels, k_flush, the two
+    apply kernels of the sharded paths and the population's install call it.  hiprtc is given the header ahead of the files that use it.
+    Reads the sources only."""
+    csrc = os.path.join(ROOT, "smm.jl_amd", "csrc")
+    strip = lambda txt: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    names = sorted(f for f in os.listdir(csrc) if f.endswith(".hpp") or f == "smmhip.hip")
+    code = {f: strip(open(os.path.join(csrc, f)).read()) for f in names}
+    assert "smm_accept.hpp" in code
+    for what, pattern in (("the sigma update's threshold", r"0\.234"), ("the test for a finite prob", r"isfinite\(prob\)"),
+                          ("an assignment to a row's exchanged field", r"\[H_EXCH\]\s*="), ("the banana's term", r"100\.0 \*")):
+        holders = [f for f in names if re.search(pattern, code[f])]
+        assert holders == ["smm_accept.hpp"], (what, holders)
+    assert not any("make_swapped_history" in c for c in code.values())
+    embed = re.search(r"^EMBED = (.*)$", open(os.path.join(csrc, "Makefile")).read(), flags=re.M).group(1).split()
+    assert embed.index("smm_accept.hpp") < embed.index("smm_chain.hpp")
