@@ -1,7 +1,9 @@
 """tests/rank_diag_ref.py, the restatement of smm_get_rank_diag's contract (include/smmhip.h) the GPU tests hold the device against, held
 against brute force (the ranks), statistics.NormalDist (ndtri) and theory (independent normal chains; a shifted and a scaled chain); the
 tolerance of the outputs behind ndtri measured on the GPU tests' shapes; the Python argument checks, which raise without a device; and
-the ctypes and Julia mirrors of smm_rank_diag_t against the header.  No GPU."""
+the ctypes and Julia mirrors of smm_rank_diag_t against the header; and the preconditions of tests/test_gpu_rank_edges.py: the crafted
+columns' ranks against a count, the digits of their keys, their tie runs against the sort's segments, the vectorised normal scores
+against the scalar ones, and every edge shape's tolerance measured with no cell left out.  No GPU."""
 import math
 import os
 import statistics
@@ -180,3 +182,175 @@ def test_the_mirrors_of_smm_rank_diag_t():
     assert [f for f, _ in A.smm_rank_diag_t._fields_] == [f for f, _ in want]
     argtypes = dict((n, a) for n, _, a in A.SYMBOLS)["smm_get_rank_diag"]
     assert len(argtypes) == 8 and argtypes[-1]._type_ is A.smm_rank_diag_t
+
+
+# --- the preconditions of tests/test_gpu_rank_edges.py, on the CPU ----------------------------------------------------------------------
+
+UP = lambda x: math.nextafter(math.log(x), math.inf)
+DOWN = lambda x: math.nextafter(math.log(x), -math.inf)
+
+
+def test_the_vectorised_scores_are_the_scalar_ones():
+    rng = np.random.default_rng(3)
+    for M in (8, 354, 2000, 9554, 40000):
+        for r2 in (R.rank2(rng.standard_normal(M)), R.rank2(np.round(rng.standard_normal(M), 1)), R.rank2(np.zeros(M))):
+            for log in (math.log, UP, DOWN):
+                assert np.array_equal(R.scores(r2, log), R.scores_scalar(r2, log)), M
+    p = np.r_[np.linspace(1e-7, 1 - 1e-7, 5001), 0.075, 0.925, 0.5, 1.3e-11, 1 - 1e-11]      # the three branches and their borders
+    assert np.array_equal(R.ndtri_array(p), np.array([R.ndtri(float(v)) for v in p]))
+    assert (np.abs(p - 0.5) <= 0.425).any() and (R.ndtri_array(p) > 5.0).any() and (R.ndtri_array(p) < -6.0).any()
+
+
+def crafted_columns():
+    """the pooled columns of cases 1 and 2 at a few hundred values"""
+    cols = R.three_orders(R.key_values(R.KEYS_M - R.N_KEY_VALUES), 3)
+    cols += R.three_orders(R.tie_column(600, (1, 2, 63, 64, 65, 301), R.TIES_SEED)[0], R.TIES_SEED)
+    return cols + list(R.zeros_columns())
+
+
+def test_the_ranks_of_the_crafted_columns_equal_a_count_of_less_and_equal():
+    for x in crafted_columns():
+        assert np.array_equal(R.rank2(x), brute(x))
+    z = R.zeros_columns()
+    assert np.array_equal(np.unique(R.rank2(z[0])), [R.ZEROS_M, 2 * R.ZEROS_M]) and np.array_equal(np.unique(R.rank2(z[1])), [2, R.ZEROS_M + 2])
+    assert np.signbit(z[:, ::2]).all() and not np.signbit(z[:, 1::2]).any() and (np.sort(z, axis=1)[:, 1:-1] == 0).all()
+    m = [float(np.median(c)) for c in z]                    # (the contract's median takes -0 as +0)
+    assert m == [0.0, 0.0, 0.0]
+
+
+def test_every_radix_pass_meets_at_least_three_digits_in_the_crafted_keys():
+    col = R.key_values(R.KEYS_M - R.N_KEY_VALUES)
+    assert len(col) == R.KEYS_M <= R.RANK_SMALL and np.array_equal(R.pooled_to_series(col, R.KEYS_N, R.KEYS_T)[:, :59].ravel(), col.reshape(3, 2, 59)[:, 0].ravel())
+    for b in range(8):                                      # the values of one family differ in byte b only
+        fam = col[np.isin(col.view(np.uint64) & ~np.uint64(0xFF << (8 * b)), [R.KEY_BASE & ~(0xFF << (8 * b))])]
+        fam = fam[fam > 0]
+        assert len(fam) >= 10 and np.isin(-fam, col).all()     # (the negated family's keys are the complements)
+        for f in (fam, -fam):
+            assert len(np.unique(R.key_digits(f)[b])) == len(f) and all(len(np.unique(R.key_digits(f)[o])) == 1 for o in range(8) if o != b)
+    for cols in (R.three_orders(col, 3), R.ties_short_series()[1], R.ties_long_series()[1]):
+        for c in cols:
+            assert all(len(np.unique(d)) >= 3 for d in R.key_digits(c))
+    k = R.sort_keys(col)
+    assert (np.diff(k.astype(object)) >= 0).all() and (np.diff(k.astype(object)) == 0).sum() == 1   # ascending; -0 and +0 share a key
+    for v in (0.0, -0.0, 5e-324, -5e-324, 2.2250738585072014e-308, -1.7976931348623157e308, 1.7976931348623157e308, 1e16, 1e16 + 4):
+        assert (col == v).any(), v
+    assert np.signbit(col[col == 0]).tolist() == [True, False]
+
+
+def runs_of(col):
+    s = np.sort(np.asarray(col) + 0.0)
+    starts = np.flatnonzero(np.r_[True, s[1:] != s[:-1]])
+    return starts, np.diff(np.r_[starts, len(s)])
+
+
+def test_the_tie_runs_meet_the_segments_edges():
+    nseg, seg = R.rank_segments(R.TIES_SHORT_M)
+    assert (nseg, seg) == (4, 512) and R.rank_nblk(R.TIES_SHORT_M) == 1
+    _, cols = R.ties_short_series()
+    la, lb = set(runs_of(cols[0])[1]), set(runs_of(cols[1])[1])
+    assert {1, 2, 63, 64, 65, seg - 1, seg, seg + 1} <= la and la == set(runs_of(cols[2])[1])
+    assert {1, 2, 63, 64, 65} <= lb and max(lb) > R.TIES_SHORT_M // 2
+    M = R.TIES_LONG_M
+    nseg, seg = R.rank_segments(M)
+    assert (nseg, seg) == (8, 1216) and R.rank_nblk(M) == 2 and R.RANK_SMALL < M <= 10000
+    _, cols = R.ties_long_series()
+    for c in cols:
+        starts, lens = runs_of(c)
+        assert {1, 2, 63, 64, 65, seg - 1, seg, seg + 1} <= set(lens) and lens.max() > M // 2
+        i = int(np.argmax(lens))
+        edge = 4 * seg                                      # the first place of the second workgroup's segments
+        assert starts[i] + 64 < edge < starts[i] + lens[i] - 64, (starts[i], lens[i])
+        z = np.asarray(c)[np.asarray(c) == 0]
+        assert len(z) == 65 and 0 < np.signbit(z).sum() < 65    # the run on zero holds both signs
+    assert all(len(np.unique(np.sign(np.diff(c)))) <= 2 for c in cols[:2]) and (np.diff(cols[2]) < 0).any() and (np.diff(cols[2]) > 0).any()
+
+
+def test_the_pairwise_sum_of_140_split_chains_has_the_leaves_64_and_76():
+    from chain_stats_ref import pw
+    x = [float(v) for v in np.random.default_rng(8).standard_normal(140) * 1e3]
+    assert 2 * int((R.WIDE_GROUPS == 0).sum()) == 140
+    assert D.S(x) == 0.0 + (pw(x, 0, 64) + pw(x, 64, 76)) and D.S(x) != pw(x, 0, 72) + pw(x, 72, 68)
+    assert D.S(x) == float(np.sum(np.array(x)))
+
+
+@pytest.fixture(scope="module")
+def edge_calls(O):
+    """name -> [(X [S][N][n], max_lag, groups, n_groups)]: every call of tests/test_gpu_rank_edges.py that is held to a tolerance, the
+    generated histories from the CPU oracle, whose history is the device's"""
+    import common as cm
+
+    def history(kw, steps=None):
+        prob, opts = cm.serial_normal(**kw)
+        o = O.OracleContext(prob, opts)
+        o.step(steps or kw["T"])
+        return o.history(0, steps or kw["T"])
+
+    def of(h, windows, ml, g, ng=None):
+        return [(D.series_from_history(h, t0, t1)[0], (t1 - t0) // 2 - 1 if ml is None else ml, g, ng) for t0, t1 in windows]
+
+    hl = history(R.LENGTHS_KW)
+    hn = history(R.NONFINITE_KW)
+    hn.accepted[...] = 1
+    R.make_nonfinite(hn.params, hn.value)
+    ts, tl = R.ties_short_series()[0], R.ties_long_series()[0]
+    return dict(
+        keys=[(R.keys_series(), R.KEYS_T // 2 - 1, None, None)],
+        ties_short=[(ts, R.TIES_SHORT_T // 2 - 1, R.TIES_SHORT_GROUPS, None)],
+        ties_long=[(tl, R.TIES_LONG_T // 2 - 1, None, None)],
+        lengths=of(hl, R.LENGTHS_WINDOWS, None, R.LENGTHS_GROUPS, R.LENGTHS_NG),
+        tiny=of(hl, R.TINY_WINDOWS, None, R.TINY_GROUPS),
+        wide=of(history(R.WIDE_KW), ((0, R.WIDE_KW["T"]),), None, R.WIDE_GROUPS),
+        two_long=of(history(R.TWO_LONG_KW, R.TWO_LONG_STEPS), ((0, R.TWO_LONG_STEPS),), R.TWO_LONG_LAG, R.TWO_LONG_GROUPS, R.TWO_LONG_NG),
+        cap=of(history(R.CAP_KW), ((0, R.CAP_KW["T"]),), R.CAP_LAG, R.CAP_GROUPS),
+        lags=of(history(R.LAGS_KW), ((0, R.LAGS_KW["T"]),), None, R.LAGS_GROUPS),
+        nonfinite=of(hn, ((0, R.NONFINITE_KW["T"]),), None, R.NONFINITE_GROUPS, R.NONFINITE_NG),
+    )
+
+
+@pytest.mark.parametrize("name", sorted(R.EDGE_RTOL))
+def test_each_edge_shape_leaves_no_cell_out_and_has_its_tolerance_measured(edge_calls, name):
+    """the one-ulp logarithm moved either way on the shape's own calls: the integer outputs, ess_tail and ess_mean do not move, the
+    outputs behind ndtri by less than RANK_LOG_CHANGE (then the shape is compared at RANK_RTOL) or the shape's rtol is 8 x its own
+    figure; and no cell's truncating pair lies within the tolerance of zero"""
+    worst = 0.0
+    for X, ml, g, ng in edge_calls[name]:
+        with np.errstate(all="ignore"):
+            base = R.rank_diag_from_series(X, ml, 4, g, ng)
+            moved = [R.rank_diag_from_series(X, ml, 4, g, ng, log=log) for log in (UP, DOWN)]
+        assert not R.near_sign_change(base, R.EDGE_RTOL[name]).any(), base["pair_at_truncation"]
+        for mv in moved:
+            for f in R.EXACT:
+                assert np.array_equal(mv[f], base[f], equal_nan=True), f
+            for f in R.TOLERANCED:
+                a, b = mv[f], base[f]
+                assert np.array_equal(np.isnan(a), np.isnan(b)), f
+                fin = ~np.isnan(b)
+                worst = max(worst, float(np.max(np.abs(a[fin] - b[fin]) / np.abs(b[fin]), initial=0.0)))
+    print("%s: largest relative change %.3g; rtol %.3g" % (name, worst, R.EDGE_RTOL[name]))
+    if worst <= R.RANK_LOG_CHANGE:
+        assert R.EDGE_RTOL[name] == R.RANK_RTOL
+    else:
+        assert 8 * worst <= R.EDGE_RTOL[name] <= 8 * 1.25 * worst      # (the shape's own figure, rounded up)
+
+
+def test_the_edge_shapes_reach_their_paths(edge_calls):
+    assert R.rank_nblk(8192) == 1 and R.rank_nblk(8704) == 2 and R.rank_segments(8704) == (8, 1088) and 7 * 1088 < 8704 <= 8 * 1088
+    assert R.rank_nblk(524800) == R.RANK_NBLK and R.rank_segments(524800) == (256, 2112) and R.rank_nblk(32800) == 5
+    assert R.rank_nblk(9600) == 2 and R.rank_nblk(16800) == 3
+    N, T = R.TWO_LONG_KW["N"], R.TWO_LONG_KW["T"]
+    per = [R.rank_bytes(int((R.TWO_LONG_GROUPS == g).sum()), R.TWO_LONG_STEPS // 2, R.TWO_LONG_LAG) for g in range(R.TWO_LONG_NG)]
+    assert per[3] == 0 and sum(per[:3]) == R.TWO_LONG_SCRATCH < sum(per) and R.TWO_LONG_SCRATCH <= N * T * 20   # A, short, B | short
+    (X, ml, g, ng), = edge_calls["cap"]
+    assert X.shape[2] // 2 == 8200 > 8192 and R.CAP_BINS > R.RANK_HIST_LDS
+    (X, ml, g, ng), = edge_calls["lags"]
+    with np.errstate(all="ignore"):
+        want = R.rank_diag_from_series(X, ml, 4, g, ng)
+    print("lags: status", want["status"].tolist())
+    assert ml == 299 and (want["status"][[0, 2, 3]] == 1).any()     # a kind of a cell still open at max_lag = 299 > 256
+    (X, ml, g, ng), = edge_calls["nonfinite"]
+    with np.errstate(all="ignore"):
+        want = R.rank_diag_from_series(X, ml, 4, g, ng)
+    st = want["status"]
+    assert (st[:, 0, 1] == 3).all() and (st[:, 1, 2] == 3).all() and (st[:, 3] == 2).all() and ((st == 3).sum(), (st[:, 2] < 2).all()) == (8, True)
+    assert (want["rank_hist"][:, 1, :3] == 0).all() and (want["rank_hist"][:, 2, 3:6] == 0).all()
+    assert (want["rank_hist"].sum(axis=0)[[0, 2]][:, :3] == 40).all() and (want["rank_hist"].sum(axis=0)[:, 6:] == 40).all()
