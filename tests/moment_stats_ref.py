@@ -19,6 +19,12 @@ FIELDS = ("count", "n_chains", "status", "p_mean", "m_mean", "m_median", "m_quan
 # np.linalg (the procedure of rank_diag_ref.RANK_RTOL).
 MOMENT_LINALG_DEV = 9.41e-15           # measured (test_jac_sens_se_against_numpy_linalg prints it): 9.41e-15 over its 30 groups
 MOMENT_LINALG_RTOL = 10 * MOMENT_LINALG_DEV
+# the same on crafted_linear's histories of CAP_SHAPES (N = 8, T = 48, two groups, the three selections), and jac against the J_true
+# those moments were made from, which the 1e-3 noise moves as well, in units of J_true's largest entry
+MOMENT_LINALG_CAPS_DEV = 5.74e-11      # measured (test_jac_sens_se_against_numpy_linalg_at_the_caps prints it): over its 24 status-0 groups
+MOMENT_LINALG_CAPS_RTOL = 10 * MOMENT_LINALG_CAPS_DEV
+MOMENT_JTRUE_CAPS_DEV = 9.23e-3        # measured by the same test, over the 36 groups whose status is 0 or 4
+MOMENT_JTRUE_CAPS_RTOL = 10 * MOMENT_JTRUE_CAPS_DEV
 
 
 def dense_problem(npar, nm, N, T, seed=3):
@@ -104,6 +110,39 @@ def solve(L, b):
     return x
 
 
+def cholesky_columns(A):
+    """cholesky's (L, ok) column by column, the rows below a pivot at once: every entry by cholesky's operations in cholesky's order
+    (tests/test_moment_stats.py holds the two equal bit for bit), in O(n^2) numpy calls for the shapes at the size cap"""
+    n = A.shape[0]
+    L = np.zeros((n, n))
+    for j in range(n):
+        s = np.array(A[j:, j], np.float64)
+        for i in range(j):
+            s = s - L[j:, i] * L[j, i]
+        if not s[0] > 0:
+            return L, False
+        L[j, j] = np.sqrt(s[0])
+        L[j + 1:, j] = s[1:] / L[j, j]
+    return L, True
+
+
+def solve_columns(L, B):
+    """solve's x for every column of B [n][r] at once: the same subtractions in the same order, column by column"""
+    n = L.shape[0]
+    x = np.array(B, np.float64)
+    for i in range(n):
+        s = x[i].copy()
+        for j in range(i):
+            s = s - L[i, j] * x[j]
+        x[i] = s / L[i, i]
+    for i in range(n - 1, -1, -1):
+        s = x[i].copy()
+        for j in range(i + 1, n):
+            s = s - L[j, i] * x[j]
+        x[i] = s / L[i, i]
+    return x
+
+
 def weights(w):
     """(s, W): s_k = w_k if finite and not zero, else 1.0; W_k = 1.0 / (s_k * s_k)"""
     w = np.asarray(w, np.float64)
@@ -144,6 +183,58 @@ def linear_part(cov_pp, cov_pm, w, ridge):
     return 0, jac, sens, se
 
 
+def linear_part_columns(cov_pp, cov_pm, w, ridge):
+    """linear_part's (status, jac, sens, se), bit for bit (tests/test_moment_stats.py), through cholesky_columns and solve_columns:
+    what moment_stats_from_history calls, so that np = nm = 64 takes milliseconds"""
+    npar, nm = cov_pm.shape
+    jac, sens, se = np.full((nm, npar), np.nan), np.full((npar, nm), np.nan), np.full(npar, np.nan)
+    A = np.array(cov_pp, np.float64)
+    for j in range(npar):
+        A[j, j] = cov_pp[j, j] + np.float64(ridge) * cov_pp[j, j]
+    L, ok = cholesky_columns(A)
+    if not ok:
+        return 3, jac, sens, se
+    jac = np.ascontiguousarray(solve_columns(L, cov_pm).T)
+    s, W = weights(w)
+    B = np.zeros((npar, npar))
+    for k in range(nm):
+        B = B + (jac[k][:, None] * W[k]) * jac[k][None, :]
+    LB, ok = cholesky_columns(B)
+    if not ok:
+        return 4, jac, sens, se
+    sens = solve_columns(LB, -(jac.T * W[None, :]))
+    S = np.zeros(npar)
+    for k in range(nm):
+        S = S + (sens[:, k] * sens[:, k]) * (s[k] * s[k])
+    return 0, jac, sens, np.sqrt(S)
+
+
+def crafted_linear(npar, nm, N, T, seed, into=None):
+    """(h, J_true): a history whose moments are linear in the parameters, written into the HistoryBuffers `into` (default: a zeroed
+    one of T iterations, N chains) — params i.i.d. standard normal scaled per column by geomspace(1, 1e-2, np), sim_moments = J_true
+    theta + 1e-3 noise with J_true [nm][np] standard normal, value half the squared distance of the moments from 0, accepted a 0/1
+    pattern at rate 0.7 whose row 0 is accepted in every chain (the state series exists from the first row).  Only these four fields
+    are written; everything is a function of the arguments"""
+    from smm_jl_amd import _abi as A
+    if into is None:
+        into = A.HistoryBuffers(T, N, npar, nm)
+        for f in A.HistoryBuffers.FIELDS:
+            getattr(into, f)[...] = 0
+    assert into.params.shape == (T, npar, N) and into.sim_moments.shape == (T, nm, N)
+    rng = np.random.default_rng([seed, npar, nm, N, T])
+    J = rng.standard_normal((nm, npar))
+    theta = rng.standard_normal((T, npar, N)) * np.geomspace(1.0, 1e-2, npar)[None, :, None]
+    mom = np.einsum("kj,tjc->tkc", J, theta) + 1e-3 * rng.standard_normal((T, nm, N))
+    acc = (rng.random((T, N)) < 0.7).astype(np.uint8)
+    acc[0] = 1
+    into.params[...], into.sim_moments[...], into.accepted[...] = theta, mom, acc
+    into.value[...] = 0.5 * (mom * mom).sum(axis=1)
+    return into, J
+
+
+CAP_SHAPES = ((1, 1), (1, 64), (64, 1), (64, 64), (63, 34), (33, 64))   # (np, nm) of crafted_linear's cases: the caps, and D = 97 twice
+
+
 def moment_stats_from_history(h, t0, t1, select, groups, probs, ridge, mom, w, n_groups=None):
     """what smm_get_moment_stats returns, from a HistoryBuffers of iterations [0, >= t1), the data moments mom [nm] and the weights w
     [nm]; groups None: every chain in group 0; n_groups defaults to groups.max() + 1"""
@@ -175,7 +266,7 @@ def moment_stats_from_history(h, t0, t1, select, groups, probs, ridge, mom, w, n
                 continue                                  # the covariances and everything derived NaN
             out["cov_pp"][g], out["cov_pm"][g], out["cov_mm"][g] = cov[:npar, :npar], cov[:npar, npar:], cov[npar:, npar:]
             out["fit_z"][g] = (mean[npar:] - mom) / np.sqrt(np.diagonal(cov[npar:, npar:]))
-            out["status"][g], out["jac"][g], out["sens"][g], out["se"][g] = linear_part(cov[:npar, :npar], cov[:npar, npar:], w, ridge)
+            out["status"][g], out["jac"][g], out["sens"][g], out["se"][g] = linear_part_columns(cov[:npar, :npar], cov[:npar, npar:], w, ridge)
     return out
 
 

@@ -131,6 +131,97 @@ def profile_from_history(h, t0, t1, select, groups, bins, range=None, pairs=(), 
     return out
 
 
+# the crafted history of the segment-cap cases (tests/test_gpu_reducer_caps.py; its design is checked in tests/test_profile.py): serialNormal's
+# np = nm = 2, T = 600 (three 256-row blocks of k_prof_scatter per member), group 2 of 14 members so that one segment of it holds more
+# than 8192 scored rows, group 4 without a member and chain 5 in no group
+CAPS_T = 600
+CAPS_GROUPS = np.array([0, 0, 0, 1, 1, -1, 2, 2, 2, 2, 3, 0] + [2] * 10, np.int32)
+CAPS_NG = 5
+CAPS_RANGE = np.array([[0.0, 1.0], [0.0, 1.0]])
+CAPS_BINS = (2, 3, 7)                 # every bins / bins2 the cases bin CAPS_RANGE into: rows lie on all their edges
+CAPS_MIN = (7, 10)                    # (chain, iteration) of the first of group 2's equal minima in pooled order
+
+
+def crafted_caps(h, seed=11):
+    """h (a HistoryBuffers of CAPS_T iterations of len(CAPS_GROUPS) chains, np = nm = 2) overwritten in params, sim_moments, value,
+    accepted and status, a function of the seed alone:
+      every chain : x uniform in [-0.05, 1.05] (rows outside CAPS_RANGE), the value 1 + |normal|, accepted at rate 0.6, row 0 accepted;
+      group 2     : x = (0.4, 0.6) but for 8 rows per member: one segment (1-D) and one cell (2-D) of at least 8260 scored rows, every
+                    member adding to it in each of its three blocks; the value -3 (the minimum) at chain 7's rows 10 and 300 (two blocks
+                    of one member) and at chain 13's rows 5 and 400: the earliest pooled row is CAPS_MIN; chain 7's row 10 is not
+                    accepted, so the accepted rows' minimum is at row 300; two unscored rows per member (NaN, +Inf);
+      group 0     : unscored rows (NaN, -Inf, a failed evaluation: +Inf with status -1), a NaN moment in a scored row, and x = (0.9,
+                    0.1) with the values -0.0 at chain 0's row 20 and +0.0 at chain 1's row 450: -0.0 comes first;
+      group 3     : x = (0.9, 0.1) with +0.0 at row 7 and -0.0 at row 300: +0.0 comes first;
+      chain 3     : x walks over every edge of CAPS_RANGE cut into CAPS_BINS bins, lo and hi included, in both parameters."""
+    import hist_ref as HR
+    T, N = h.value.shape
+    assert T == CAPS_T and N == len(CAPS_GROUPS) and h.params.shape[1] == 2 and h.sim_moments.shape[1] == 2
+    rng = np.random.default_rng(seed)
+    h.params[...] = rng.uniform(-0.05, 1.05, (T, 2, N))
+    h.sim_moments[...] = rng.standard_normal((T, 2, N))
+    h.value[...] = 1.0 + np.abs(rng.standard_normal((T, N)))
+    h.accepted[...] = rng.random((T, N)) < 0.6
+    h.accepted[0] = 1
+    h.status[...] = 0
+    for c in np.flatnonzero(CAPS_GROUPS == 2):
+        away = rng.choice(np.arange(20, T), 10, replace=False)
+        keep = np.ones(T, bool)
+        keep[away[:8]] = False
+        h.params[keep, 0, c], h.params[keep, 1, c] = 0.4, 0.6
+        h.value[away[8], c], h.value[away[9], c] = np.nan, np.inf                 # (in the big segment: x stays (0.4, 0.6) there)
+    for c, t in ((7, 10), (7, 300), (13, 5), (13, 400)):
+        h.params[t, :, c], h.value[t, c], h.accepted[t, c] = (0.4, 0.6), -3.0, 1
+    h.accepted[10, 7] = 0
+    h.value[30, 0], h.value[31, 1], h.value[290, 2] = np.nan, -np.inf, np.nan
+    h.value[40, 11], h.status[40, 11] = np.inf, -1
+    h.value[33, 2], h.sim_moments[33, 0, 2], h.params[33, :, 2] = 1.5, np.nan, (0.5, 0.5)
+    for c, t, z in ((0, 20, -0.0), (1, 450, 0.0), (10, 7, 0.0), (10, 300, -0.0)):
+        h.params[t, :, c], h.value[t, c], h.accepted[t, c] = (0.9, 0.1), z, 1
+    E = np.concatenate([HR.linspace(0.0, 1.0, b) for b in CAPS_BINS])
+    t = np.arange(1, T)
+    h.params[1:, 0, 3], h.params[1:, 1, 3] = E[t % len(E)], E[(t // len(E)) % len(E)]
+    return h
+
+
+def crafted_wide(h, seed=12):
+    """h (np = nm = 64 and the like: any sizes) overwritten in params, sim_moments, value, accepted and status: x uniform in [0, 1],
+    standard normal moments, the value 1 + |normal| with a NaN, an Inf and a pair of equal minima in every chain, accepted at rate
+    0.6 with row 0 accepted"""
+    T, N = h.value.shape
+    rng = np.random.default_rng(seed)
+    h.params[...] = rng.uniform(0.0, 1.0, h.params.shape)
+    h.sim_moments[...] = rng.standard_normal(h.sim_moments.shape)
+    h.value[...] = 1.0 + np.abs(rng.standard_normal((T, N)))
+    h.accepted[...] = rng.random((T, N)) < 0.6
+    h.accepted[0] = 1
+    h.status[...] = 0
+    for c in range(N):
+        t = rng.choice(T, 4, replace=False)
+        h.value[t[0], c], h.value[t[1], c], h.value[t[2], c], h.value[t[3], c] = np.nan, np.inf, 0.25, 0.25
+    return h
+
+
+def zeroed_history(T, N, npar, nm):
+    """a HistoryBuffers with every field 0, for a generator to write into without a context"""
+    from smm_jl_amd import _abi as A
+    h = A.HistoryBuffers(T, N, npar, nm)
+    for f in A.HistoryBuffers.FIELDS:
+        getattr(h, f)[...] = 0
+    return h
+
+
+CRAFTED_FIELDS = ("params", "sim_moments", "value", "accepted")
+
+
+def assert_crafted_read_back(back, crafted):
+    """the four fields a generator writes, as smm_get_history returns them after smm_set_state: bit for bit"""
+    for f in CRAFTED_FIELDS:
+        a, b = getattr(back, f), getattr(crafted, f)
+        assert a.shape == b.shape and np.array_equal(a, b, equal_nan=True), f
+    assert np.array_equal(np.signbit(back.value), np.signbit(crafted.value))
+
+
 def assert_profile_equal(got, want, fields=None):
     """every field array_equal, NaN equal to NaN (the sign of a zero in an autodetected edge aside, as in hist_ref)"""
     for f in fields or want:

@@ -79,6 +79,27 @@ def test_draws_ref_against_a_brute_force_restatement(O):
     assert (got["src_iter"][got["chain"] == 5] == 0).all() and np.isnan(got["value"][got["chain"] == 5]).all() and (got["chain"] == 5).sum() == 6
 
 
+def test_wide_rows_case_by_brute_force():
+    """the design of the wide-row case of tests/test_gpu_reducer_caps.py (np = nm = 64, three groups, a chain in no group, a cap that
+    cuts a group) on profile_ref.crafted_wide's history, against the brute-force list"""
+    import profile_ref as PR
+    N, T = 8, 40
+    h = PR.crafted_wide(PR.zeroed_history(T, N, 64, 64))
+    groups = np.array([0, 1, 1, -1, 2, 0, 2, 2], np.int32)
+    for select in (0, 1, 2):
+        for thin, K in ((1, 10000), (3, 10000), (1, 50), (3, 17)):
+            want = brute(h, 3, T, select, groups, 3, thin, K)
+            got = DR.draws_from_history(h, 3, T, select, groups, thin, K, n_groups=3)
+            rows = [r for _, rs in want for r in rs]
+            assert got["count"].tolist() == [m for m, _ in want] and len(rows) == got["row0"][3]
+            assert K > 50 or (got["count"] > K).any()                              # the cap cuts a group
+            assert got["chain"].tolist() == [c + 1 for c, _, _ in rows] and got["src_iter"].tolist() == [s + 1 for _, _, s in rows]
+            assert got["params"].shape == (len(rows), 64) and got["sim_moments"].shape == (len(rows), 64)
+            for q, (c, t, s) in enumerate(rows):
+                assert np.array_equal(got["params"][q], h.params[s, :, c]) and np.array_equal(got["sim_moments"][q], h.sim_moments[s, :, c])
+                assert np.array_equal(got["value"][q], h.value[s, c], equal_nan=True)
+
+
 def test_position_rule():
     for m in range(0, 41):
         for K in range(1, 13):

@@ -1,7 +1,9 @@
 """tests/moment_stats_ref.py, the restatement of smm_get_moment_stats' contract (include/smmhip.h) the GPU tests hold the device against,
 held on histories of the CPU oracle against group_stats_ref (the cov_pp block, bit for bit), a direct covariance of one parameter and
 one moment (np != nm: a transposed index cannot pass), the weights' reading, the status table, and np.linalg.lstsq / np.linalg.solve
-for jac, sens and se; and the ctypes mirror of smm_moment_stats_t against the header compiled with gcc.  No GPU."""
+for jac, sens and se, at the earlier small shapes and on moment_stats_ref.crafted_linear's histories of the shapes at the size cap (np, nm up
+to 64: the statuses by design, J_true as a second anchor, linear_part_columns equal to linear_part bit for bit); and the ctypes mirror of
+smm_moment_stats_t against the header compiled with gcc.  No GPU."""
 import ctypes as C
 import os
 import subprocess
@@ -167,6 +169,92 @@ def test_jac_sens_se_against_numpy_linalg(mixing, dense57):
     print("largest relative deviation from np.linalg over %d groups: %.3g (MOMENT_LINALG_DEV %.3g)" % (cells, worst, MR.MOMENT_LINALG_DEV))
     assert cells == 2 * 3 * (3 + 2)
     assert worst <= MR.MOMENT_LINALG_RTOL
+
+
+CAP_N, CAP_T = 8, 48
+CAP_GROUPS = (np.arange(CAP_N) % 2).astype(np.int32)
+
+
+@pytest.fixture(scope="module")
+def capped():
+    """crafted_linear's history of every shape of MR.CAP_SHAPES with dense_problem's data moments and weights: (prob, h, J_true)"""
+    out = {}
+    for npar, nm in MR.CAP_SHAPES:
+        prob, _ = MR.dense_problem(npar, nm, N=CAP_N, T=CAP_T)
+        h, J = MR.crafted_linear(npar, nm, CAP_N, CAP_T, seed=npar * 100 + nm)
+        out[npar, nm] = prob, h, J
+    return out
+
+
+def test_linear_part_columns_is_linear_part_bit_for_bit(mixing, dense57, capped):
+    def same(cov_pp, cov_pm, w, ridge):
+        a, b = MR.linear_part(cov_pp, cov_pm, w, ridge), MR.linear_part_columns(cov_pp, cov_pm, w, ridge)
+        assert a[0] == b[0]
+        for x, y in zip(a[1:], b[1:]):
+            assert x.shape == y.shape and np.array_equal(x, y, equal_nan=True) and np.array_equal(np.signbit(x), np.signbit(y))
+        return a[0]
+    seen = set()
+    for prob, h in (mixing, dense57):
+        npar = h.params.shape[1]
+        for x in MR.joint_columns(h, 0, h.value.shape[0], 2, np.zeros(h.value.shape[1], np.int32), 1):
+            cov = GS.column_cov(x)[1]
+            for ridge in (0.0, 1e-6):
+                seen.add(same(cov[:npar, :npar], cov[:npar, npar:], prob.w, ridge))
+    for (npar, nm), (prob, h, _) in capped.items():            # one group of each shape at the caps, and one short of rows
+        for t1, ridge in ((CAP_T, 0.0), (CAP_T, 1e-8), (3, 0.0)) if (npar, nm) != (64, 64) else ((CAP_T, 0.0), (3, 0.0)):
+            cov = GS.column_cov(MR.joint_columns(h, 0, t1, 0, CAP_GROUPS, 2)[0])[1]
+            seen.add(same(cov[:npar, :npar], cov[:npar, npar:], prob.w, ridge))
+    seen.add(same(np.eye(3), np.zeros((3, 2)), [1.0, 2.0], 0.0))
+    assert seen == {0, 3, 4}, seen                             # both early exits were compared too
+
+
+def test_capped_shapes_statuses_by_design(capped):
+    """every shape with nm >= np: J'WJ has full rank, status 0 in both groups over all 192 pooled rows; np = 64 against nm = 1: rank 1"""
+    for (npar, nm), (prob, h, _) in capped.items():
+        r = MR.moment_stats_from_history(h, 0, CAP_T, 0, CAP_GROUPS, PROBS, 0.0, prob.mom, prob.w)
+        assert r["count"].tolist() == [4 * CAP_T] * 2 and 4 * CAP_T > npar + 1
+        print("np %d nm %d: status %s" % (npar, nm, r["status"].tolist()))
+        if nm >= npar:
+            assert r["status"].tolist() == [0, 0], (npar, nm)
+            assert np.isfinite(r["jac"]).all() and np.isfinite(r["sens"]).all() and np.isfinite(r["se"]).all()
+        elif (npar, nm) == (64, 1):
+            # the 63 later pivots of J'WJ are zero in exact arithmetic; rounded they are noise of either sign.  On this history the first
+            # of them is not positive: 4.  (A 0 would be accepted as the existing nm < np case accepts it: the GPU test follows this table)
+            assert r["status"].tolist() == [4, 4] and np.isfinite(r["jac"]).all() and np.isnan(r["sens"]).all()
+        else:
+            assert set(r["status"].tolist()) <= {0, 4}
+    prob, h, _ = capped[64, 64]                                # a group short of rows: 40 < np + 1, Cov(theta, theta) is singular
+    g3 = np.array([0, 1, 0, 1, 0, 1, 0, 2], np.int32)
+    r = MR.moment_stats_from_history(h, 5, 45, 0, g3, PROBS, 0.0, prob.mom, prob.w)
+    print("a group of 40 rows at np = 64: status", r["status"].tolist())
+    assert r["count"].tolist() == [160, 120, 40] and r["status"][2] == 3 and np.isnan(r["jac"][2]).all() and np.isnan(r["se"][2]).all()
+    assert np.isfinite(r["cov_pp"][2]).all() and np.isfinite(r["fit_z"][2]).all()
+
+
+def test_jac_sens_se_against_numpy_linalg_at_the_caps(capped):
+    """the independent anchor of the capped shapes: jac against lstsq, sens and se against solve, jac against the J_true the moments
+    were made from (1e-3 noise on top), over every status-0 group (jac alone where the status is 4)"""
+    worst, worst_true, cells = 0.0, 0.0, 0
+    for (npar, nm), (prob, h, J) in capped.items():
+        for sel in (0, 1, 2):
+            r = MR.moment_stats_from_history(h, 0, CAP_T, sel, CAP_GROUPS, (), 0.0, prob.mom, prob.w)
+            cols = MR.joint_columns(h, 0, CAP_T, sel, CAP_GROUPS, 2)
+            for g in range(2):
+                if r["status"][g] not in (0, 4):
+                    continue
+                d = cols[g] - cols[g].mean(axis=1, keepdims=True)
+                want = np.linalg.lstsq(d[:npar].T, d[npar:].T, rcond=None)[0].T
+                worst = max(worst, float(np.max(np.abs(r["jac"][g] - want)) / np.max(np.abs(want))))
+                worst_true = max(worst_true, float(np.max(np.abs(r["jac"][g] - J)) / np.max(np.abs(J))))
+                if r["status"][g] == 0:
+                    cells += 1
+                    for got, want in zip((r["jac"][g], r["sens"][g], r["se"][g]), linalg(cols[g], npar, prob.w)):
+                        worst = max(worst, float(np.max(np.abs(got - want)) / np.max(np.abs(want))))
+    print("largest relative deviation from np.linalg over %d status-0 groups at the caps: %.3g (MOMENT_LINALG_CAPS_DEV %.3g); from J_true: "
+          "%.3g (MOMENT_JTRUE_CAPS_DEV %.3g)" % (cells, worst, MR.MOMENT_LINALG_CAPS_DEV, worst_true, MR.MOMENT_JTRUE_CAPS_DEV))
+    assert cells >= 2 * 5                                      # at least select 0 of the five shapes with nm >= np
+    assert worst <= MR.MOMENT_LINALG_CAPS_RTOL
+    assert worst_true <= MR.MOMENT_JTRUE_CAPS_RTOL
 
 
 def test_a_ridge_moves_the_jacobian_a_little(mixing):

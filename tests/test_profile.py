@@ -139,6 +139,64 @@ def test_ties_signed_zeros_unscored_rows_and_empty_bins(mixing):
         PR.assert_profile_equal(bad, r)
 
 
+@pytest.fixture(scope="module")
+def caps():
+    return PR.crafted_caps(PR.zeroed_history(PR.CAPS_T, len(PR.CAPS_GROUPS), 2, 2))
+
+
+def test_crafted_caps_history_holds_what_the_cap_cases_need(caps):
+    """the design of profile_ref.crafted_caps, on the restatement alone, and its counts against np.histogram / np.histogram2d"""
+    h, g, T = caps, PR.CAPS_GROUPS, PR.CAPS_T
+    pairs = [(0, 1), (1, 0), (1, 1)]
+    for bins, B2 in ((3, 2), (7, 3)):
+        r = PR.profile_from_history(h, 0, T, 0, g, bins, PR.CAPS_RANGE, pairs, B2, n_groups=PR.CAPS_NG)
+        assert r["count"].tolist() == [4 * T, 2 * T, 14 * T, T, 0] and (r["status"] == 0).all()
+        big = int(np.argmax(r["n_scored"][2, 0]))
+        assert r["n_scored"][2, 0, big] >= 8260 > 8192 and r["n_scored2"][2, 0].max() >= 8260     # a second chunk, 1-D and 2-D
+        assert (r["v_min"][2, 0, big], r["min_chain"][2, 0, big], r["min_iter"][2, 0, big]) == (-3.0, PR.CAPS_MIN[0] + 1, PR.CAPS_MIN[1] + 1)
+        hot = int(np.searchsorted(r["edges"][0, 0], 0.9, "right")) - 1                            # the segment of x = 0.9
+        assert r["v_min"][0, 0, hot] == 0.0 and np.signbit(r["v_min"][0, 0, hot]) and r["min_iter"][0, 0, hot] == 21
+        assert r["v_min"][3, 0, hot] == 0.0 and not np.signbit(r["v_min"][3, 0, hot]) and r["min_iter"][3, 0, hot] == 8
+        assert (r["n"][0] > r["n_scored"][0]).any() and np.isnan(r["m_mean"][0, ..., 0]).any() and np.isfinite(r["m_mean"][0, ..., 1]).all()
+        assert r["n"][0, 0].sum() < 4 * T                                                          # rows outside the range
+        for q in (0, 1, 2, 3):                                                                     # the rows on edges land where numpy puts them
+            x = np.concatenate([h.params[:, :, c] for c in np.flatnonzero(g == q)])
+            for k in range(2):
+                n, e = np.histogram(x[:, k], bins, PR.CAPS_RANGE[k])
+                assert np.array_equal(r["n"][q, k], n) and np.array_equal(r["edges"][q, k], e)
+            for p, (a, b) in enumerate(pairs):
+                H = np.histogram2d(x[:, a], x[:, b], B2, [PR.CAPS_RANGE[a], PR.CAPS_RANGE[b]])[0]
+                assert np.array_equal(r["n2"][q, p], H.astype(np.int64))
+        e = r["edges"][1, 0]
+        assert all((h.params[:, 0, 3] == v).any() and (h.params[:, 1, 3] == v).any() for v in e)  # on every edge, lo and hi included
+    acc = PR.profile_from_history(h, 0, T, 1, g, 3, PR.CAPS_RANGE, n_groups=PR.CAPS_NG)
+    big = int(np.argmax(acc["n_scored"][2, 0]))
+    assert (acc["v_min"][2, 0, big], acc["min_chain"][2, 0, big], acc["min_iter"][2, 0, big]) == (-3.0, 8, 301)   # the same member's next block
+    late = PR.profile_from_history(h, 137, 590, 0, g, 3, PR.CAPS_RANGE, n_groups=PR.CAPS_NG)
+    assert (late["min_chain"][2, 0, big], late["min_iter"][2, 0, big]) == (8, 301)
+    # the means of the big segment against np.mean (numpy's pairwise sum of one chunk is not the chunked sum: to rounding)
+    full = PR.profile_from_history(h, 0, T, 0, g, 3, PR.CAPS_RANGE, n_groups=PR.CAPS_NG)
+    mem = np.flatnonzero(g == 2)
+    x, v = np.concatenate([h.params[:, 0, c] for c in mem]), np.concatenate([h.value[:, c] for c in mem])
+    m1 = np.concatenate([h.sim_moments[:, 1, c] for c in mem])
+    idx = (x >= full["edges"][2, 0, big]) & (x < full["edges"][2, 0, big + 1]) & PR.scored(v)
+    assert idx.sum() == full["n_scored"][2, 0, big]
+    assert full["v_mean"][2, 0, big] == pytest.approx(v[idx].mean(), rel=1e-13) and full["m_mean"][2, 0, big, 1] == pytest.approx(m1[idx].mean(), rel=1e-11)
+
+
+def test_profile_ref_at_the_segment_caps_against_numpy():
+    """bins = 4096 and bins2 = 256 (65,536 cells a pair) on 40 iterations: the counts are numpy's (the restatement walks the occupied
+    segments only: well under a second)"""
+    h = PR.crafted_wide(PR.zeroed_history(40, len(PR.CAPS_GROUPS), 2, 2))
+    r = PR.profile_from_history(h, 0, 40, 2, PR.CAPS_GROUPS, 4096, None, [(1, 0)], 256, n_groups=PR.CAPS_NG)
+    assert r["n"].shape == (5, 2, 4096) and r["v_mean2"].shape == (5, 1, 256, 256)
+    assert r["n"].sum(axis=2).tolist() == [[160] * 2, [80] * 2, [560] * 2, [40] * 2, [0] * 2] and r["n2"].sum() == 840
+    c, _, s = PR.pooled_rows(h, 0, 40, 2, PR.CAPS_GROUPS, 5)[2]
+    xs = h.params[s, :, c]
+    assert np.array_equal(r["n"][2, 0], np.histogram(xs[:, 0], 4096)[0])
+    assert np.array_equal(r["n2"][2, 0], np.histogram2d(xs[:, 1], xs[:, 0], 256)[0].astype(np.int64))
+
+
 def test_ctypes_layout_matches_the_header():
     names = [f for f, _ in A.smm_profile_t._fields_]
     assert names == list(PR.FIELDS) and len(names) == 18
