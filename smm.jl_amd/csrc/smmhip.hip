@@ -13,7 +13,7 @@
 //   k_exch_resolve_*  : the same exchange resolution as a kernel of one workgroup (sharded path, larger
 //                       populations, and whenever the result is needed before the next chain kernel).
 // Files: smm_params.hpp (parameter block, layouts), smm_accept.hpp (the accept step's rules, written once for every kernel), smm_chain.hpp (chain kernel and its parts), smm_lookahead.hpp (k_pregen_rng,
-// k_exch_plan), smm_exchange.hpp (stand-alone exchange kernels), this file (host: contexts, forms, choosers, windows, the call frame), smm_run_host.hpp (the run's host side:
+// k_exch_plan), smm_exchange.hpp (stand-alone exchange kernels), this file (host: the types, user objectives, launch helpers, choosers, windows, the call frame), smm_forms_host.hpp (which forms a context runs and the LDS they take: select_forms), smm_create_host.hpp (context creation, step by step), smm_run_host.hpp (the run's host side:
 // stepping, settling, the sharded protocol), smm_reducers_host.hpp (the history reducers' host side), smm_population_host.hpp (the starting population's).
 // Everything that does not depend on the chains' state is produced ahead of the dependent loop by
 // wide, latency-tolerant kernels, one window of iterations at a time:
@@ -507,6 +507,16 @@ struct Forms {
     bool defer_resolve = false;  // the exchange of an iteration is left unresolved until somebody needs it (the next launch may be the persistent kernel's)
 };
 
+// the device for select_forms: its compute units, and the candidate persistent kernel's resident workgroups per CU (-1: not asked yet; 0: not available)
+struct DeviceFacts { int n_cus = 256; int per_cu = -1; };
+// what a chooser hands a launcher (name: what smm_describe says; block: lanes of a workgroup; ct: chains per tile; tpw: tiles per workgroup)
+struct ChainKernel { const void* fn; const char* name; unsigned block; int ct, tpw; };
+struct PersistKernel { const void* fn; hipFunction_t mfn; dim3 grid, block; size_t smem; const char* name; };
+// one set of the plan window's tables: the levels' pairs, thresholds and offsets, the rows of k_exch_resolve_rows, the tiles' cones
+struct LevelTables {
+    uint32_t *lv_pairs = nullptr, *lv_off = nullptr, *lv_rows = nullptr, *lv_rowinfo = nullptr, *cone_ok = nullptr, *cone_hdr = nullptr, *cone_pairs = nullptr;
+    double* lv_mi = nullptr; uint16_t* cone_gather = nullptr;
+};
 // Where the run stands, as the host keeps it: what persist_snapshot saves and persist_repair puts back, whole
 struct Run {
     int iter = 0;
@@ -522,6 +532,9 @@ struct Ctx {
     KParams P{};
     Hooks H;                   // read once at creation
     Forms F;                   // chosen once at creation (select_forms)
+    DeviceFacts dev;           // ... with these
+    // what will be uploaded, known before it is (create_facts; select_forms reads these, not the pointers): a factor, the 256 x 256 stage, injected normals / uniforms
+    bool has_chol = false, dense2 = false, has_ntab = false, has_utab = false;
     int obj = 0, device = 0, exchange_from = 2;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -564,9 +577,8 @@ struct Ctx {
     double* win_rb = nullptr;
     unsigned long long* win_plan = nullptr;
     double* win_plan_mi = nullptr;
-    uint32_t *win_lv_pairs = nullptr, *win_lv_off = nullptr, *win_lv_pairs_p = nullptr, *win_lv_offp = nullptr;
-    uint32_t *win_lv_rows = nullptr, *win_lv_rowinfo = nullptr, *slots17 = nullptr, *nan_flags = nullptr;
-    double* win_lv_mi = nullptr;
+    LevelTables win;              // the plan window's own set of tables
+    uint32_t *win_lv_pairs_p = nullptr, *win_lv_offp = nullptr, *slots17 = nullptr, *nan_flags = nullptr;
     uint32_t* big_scratch = nullptr;
     int rng_t0 = 0, rng_w = 0;    // window currently held: iterations [t0, t0+w)
     int plan_t0 = 0, plan_w = 0;
@@ -574,10 +586,7 @@ struct Ctx {
     std::vector<uint32_t> cone_big_ok;   // per iteration of the plan window: its cones fit their caps
     // ... their windows are planned AHEAD: the plan of a window depends on (seed, iteration) only, so while the chain kernels of one
     // window run, the three plan kernels of the next run beside them on a second stream into the other of two sets of tables
-    struct PlanSet {
-        uint32_t *lv_pairs = nullptr, *lv_off = nullptr, *lv_rows = nullptr, *lv_rowinfo = nullptr, *cone_ok = nullptr, *cone_hdr = nullptr, *cone_pairs = nullptr;
-        double* lv_mi = nullptr;
-        uint16_t* cone_gather = nullptr;
+    struct PlanSet : LevelTables {
         uint32_t* ok_host = nullptr;   // (pinned) cone_ok as the host reads it
         hipEvent_t done = nullptr;
         int t0 = 0, w = 0;             // iterations [t0, t0 + w) are (being) planned into this set
@@ -671,59 +680,23 @@ void launch(Ctx* c, Kern kern, dim3 grid, dim3 block, size_t smem, const Args&..
 
 bool is_sim(int obj) { return obj == SMM_OBJ_NORM || obj == SMM_OBJ_NORM_FAILBOX; }
 int obj_kind(int obj) { return is_sim(obj) ? 1 : obj == SMM_OBJ_DENSE ? 2 : 0; }
-// ... as the LDS layouts see it: 3 = the dense objective's spec v2 (SMM_OBJ_DENSE2: internally SMM_OBJ_DENSE with the 256 x 256 stage's
-// operand set; its first hidden layer is staged in the partial sums' region)
-int lay_kind(const Ctx* c);
-
 // the two value arrays (and slot arrays) alternate by iteration: reads of iteration t_read's values, writes of iteration t_write's
 void point_values(const Ctx* c, KParams& P, int t_read, int t_write) {
     P.vals = c->vals_buf[t_read & 1]; P.vals_out = c->vals_buf[t_write & 1];
     P.slot8 = c->slot8_buf[t_read & 1]; P.slot8_out = c->slot8_buf[t_write & 1];
 }
 
-size_t tile_smem_base(const Ctx* c, int ct) {
-    const KParams& P = c->P;
-    return tile_smem_doubles(ct, P.np, P.nm, P.RW, P.HW, P.RBW, lay_kind(c)) * sizeof(double);
-}
-int lay_kind(const Ctx* c) { const int k = obj_kind(c->obj); return k == 2 && c->P.dense_A2f ? 3 : (c->obj == SMM_OBJ_USER && c->u_lanes > 0) ? 4 : k; }
-// dynamic LDS of k_chain_persist_tile for this context (a user objective's wave totals: 16 chains x lanes / 64 groups x its sums)
-size_t persist_tile_smem(const Ctx* c) {
-    const KParams& P = c->P;
-    return pt_layout(P.np, P.nm, P.RW, P.HW, P.RBW, lay_kind(c), P.dense_nOt, PT_CT * (c->u_lanes / 64) * c->u_nsums).total;
-}
-// tiles (workgroups) of one rank's launch of F's persistent kernel: k_chain_persist_gen has PG_CT chains per tile (whole tiles),
-// k_chain_persist_loc NORM_CT, k_chain_persist_tile PT_CT
-int persist_tiles_rank(const Forms& F, int N) {
-    if (F.persist == PERSIST_GEN) return N / PG_CT;
-    const int ct = F.persist == PERSIST_TILE ? PT_CT : NORM_CT;
-    return (N + ct - 1) / ct;
-}
-size_t norm_smem(const Ctx* c) {   // k_chain_iter_norm: [walk: chain slots | pair list] theta, partial sums, parked state
-    const size_t b = (size_t)c->P.tile_off * sizeof(double) + norm_tile_doubles(c->P.np) * sizeof(double);
-    return c->F.cone_big ? std::max(b, cone_local_lds_bytes()) : b;   // (the local cone walk lies UNDER the tile's blocks)
-}
-size_t tile_smem(const Ctx* c, int ct, int tpw = 1) {   // dynamic LDS of k_chain_iter: tpw tiles; with the inline exchange
-    if (c->F.norm_fast) return norm_smem(c);
-    const size_t base = tile_smem_base(c, ct);           // walk its chain slots in front and its pair list under the tiles
-    const size_t tiles = (size_t)tpw * ((base + 15) & ~(size_t)15);
-    if (!c->F.inline_walk) return tiles;
-    if (c->F.dense_keys) return std::max(tiles, (size_t)(((c->P.Ng + 3) & ~3) + 4) * 8 + std::max((size_t)CONE_LEVELS * 64 * 4, (size_t)lean_walk_Kp(c->P.plan_K) * 4));
-    if (c->F.gen_keys) return (size_t)(((c->P.Ng + 3) & ~3) + 4) * 8 + std::max(tiles, (size_t)lean_walk_Kp(c->P.plan_K) * 4);
-    return c->F.gen_lean ? tile_lean_slot_bytes(c->P.Ng) + std::max(tiles, (size_t)lean_walk_Kp(c->P.plan_K) * 4)
-                       : walk_slot_bytes(c->P.Ng) + std::max(tiles, (size_t)c->P.plan_K * 4);
-}
-size_t plan_lds_bytes(int Ng, int K) { return (size_t)(Ng + 2) * 4 + (size_t)K * 8 + (size_t)K * 4 + 128 + 16; }
-#ifdef SMM_TEST_HOOKS
-size_t resolve_lds_bytes(int Ng) { return (size_t)Ng * 16 + 16; }
-#endif
-size_t resolve_lvl_soa_bytes(int Ng, int K) { return (size_t)Ng * 12 + (size_t)K * 4 + 16; }
-size_t resolve_lvl_bytes(int Ng, int K) { return (size_t)Ng * 16 + (size_t)K * 12 + 64 * 8 + 64; }
+}  // namespace
 
-int exchange_K(const Ctx* c) { return c->P.pairtab ? c->P.n_pairs_tab : n_exchange_pairs(c->P.Ng); }
+#include "smm_forms_host.hpp"
+
+namespace {
+
+int exchange_K(const Ctx* c) { return c->P.n_pairs_tab > 0 ? c->P.n_pairs_tab : n_exchange_pairs(c->P.Ng); }   // (an injected pair list: its length)
 bool exchange_active(const Ctx* c, int t) { return t >= c->exchange_from && c->P.Ng > 1; }  // AlgoBGP.jl:637
 
 void launch_cone_big(Ctx* c, const KParams& Pw, int W, const uint32_t* lv_pairs, const uint32_t* lv_off, hipStream_t st) {
-    hipLaunchKernelGGL(k_cone_chains, dim3(W), dim3(XWG), (size_t)Pw.Ng * 4, st, Pw, lv_pairs, lv_off, c->cb_scratch);
+    hipLaunchKernelGGL(k_cone_chains, dim3(W), dim3(XWG), cone_chains_lds_bytes(Pw.Ng), st, Pw, lv_pairs, lv_off, c->cb_scratch);
     hipLaunchKernelGGL(k_cone_tiles, dim3((unsigned)(((Pw.cone_tiles + CONEB_WAVES - 1) / CONEB_WAVES) * ((W + 7) & ~7))), dim3(64 * CONEB_WAVES), cone_tiles_lds_bytes(Pw.plan_K),
                        st, Pw, W, (const uint32_t*)c->cb_scratch);
     HIPCHK(hipGetLastError());
@@ -788,30 +761,30 @@ void ensure_windows(Ctx* c, int t, bool rng = true) {
     }
     if (c->F.plan == PLAN_BIG && !c->F.plan_ahead && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
         const int W = std::min(c->F.plan_cap, P.T - t + 1);
-        hipLaunchKernelGGL(k_exch_plan_big, dim3(W), dim3(XWG), plan_big_lds_bytes(P.Ng), c->stream, P, t, c->big_scratch, c->win_lv_pairs, c->win_lv_mi,
-                           c->win_lv_off, c->win_lv_rows, c->win_lv_rowinfo);
+        hipLaunchKernelGGL(k_exch_plan_big, dim3(W), dim3(XWG), plan_big_lds_bytes(P.Ng), c->stream, P, t, c->big_scratch, c->win.lv_pairs, c->win.lv_mi,
+                           c->win.lv_off, c->win.lv_rows, c->win.lv_rowinfo);
         c->plan_t0 = t; c->plan_w = W;
         P.plan_t0 = t;
         if (c->F.cone_big) {   // the tiles' locally numbered cones, from the plan's scratch (pairs in list order, their levels)
-            launch_cone_big(c, P, W, c->win_lv_pairs, c->win_lv_off, c->stream);
+            launch_cone_big(c, P, W, c->win.lv_pairs, c->win.lv_off, c->stream);
             // a cone that does not fit its caps (a pair list of very deep dependency chains: the user's, or an unlucky sample) sends its
             // iteration to the stand-alone resolution: the host looks at the window's flags once (one synchronisation per window)
             c->cone_big_ok.resize((size_t)W);
             HIPCHK(hipMemcpyAsync(c->cone_big_ok.data(), P.cone_ok, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
         } else if (c->F.persist_sh_big) {   // (the persistent kernel looks at the window's flags itself: no synchronisation)
-            launch_cone_big(c, P, W, c->win_lv_pairs, c->win_lv_off, c->stream);
+            launch_cone_big(c, P, W, c->win.lv_pairs, c->win.lv_off, c->stream);
         }
-        P.lv_rows = c->win_lv_rows; P.lv_rowinfo = c->win_lv_rowinfo;
-        P.lv_pairs = c->win_lv_pairs; P.lv_mi = c->win_lv_mi; P.lv_off = c->win_lv_off;
+        P.lv_rows = c->win.lv_rows; P.lv_rowinfo = c->win.lv_rowinfo;
+        P.lv_pairs = c->win.lv_pairs; P.lv_mi = c->win.lv_mi; P.lv_off = c->win.lv_off;
     }
     if (c->F.plan == PLAN_LDS && P.Ng > 1 && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
         const int W = std::min(c->F.plan_cap, P.T - t + 1);
         hipLaunchKernelGGL(k_exch_plan, dim3(W), dim3(XWG), (c->F.cone || c->F.persist != PERSIST_NONE) ? std::max(plan_lds_bytes(P.Ng, P.plan_K), plan_cone_bytes()) : plan_lds_bytes(P.Ng, P.plan_K), c->stream, P, t, c->win_plan,
-                           c->win_plan_mi, c->win_lv_pairs, c->win_lv_mi, c->win_lv_off, c->win_lv_pairs_p, c->win_lv_offp);
+                           c->win_plan_mi, c->win.lv_pairs, c->win.lv_mi, c->win.lv_off, c->win_lv_pairs_p, c->win_lv_offp);
         c->plan_t0 = t; c->plan_w = W;
         P.plan = c->win_plan; P.plan_mi = c->win_plan_mi; P.plan_t0 = t;
-        P.lv_pairs = c->win_lv_pairs; P.lv_mi = c->win_lv_mi; P.lv_off = c->win_lv_off;
+        P.lv_pairs = c->win.lv_pairs; P.lv_mi = c->win.lv_mi; P.lv_off = c->win.lv_off;
         P.lv_pairs_p = c->win_lv_pairs_p; P.lv_offp = c->win_lv_offp;
     }
 }
@@ -820,8 +793,6 @@ void ensure_windows(Ctx* c, int t, bool rng = true) {
 // Every instantiation of the chain kernels' templates that a launch can take is named in chain_instance() and nowhere else: chain_kernel()
 // and chain_kernel_p2p() pick one for a launch, smm_ctx_create raises the dynamic LDS limit of every one of them, smm_describe prints the
 // pick's name.  A new instantiation is one line in chain_instance() (a new family: one more name in ChainFamily).
-// (name: what smm_describe's chain= says; block: lanes of a workgroup; ct: chains per tile; tpw: tiles per workgroup)
-struct ChainKernel { const void* fn; const char* name; unsigned block; int ct, tpw; };
 enum ChainFamily {
     CF_SIM, CF_SIM_2, CF_DENSE, CF_GEN_KEYS, CF_GEN_64, CF_GEN_2, CF_GEN,   // k_chain_iter<KIND, CT, TPW, b>: b = compiled with the inline walk
     CF_NORM_NARROW_CONE, CF_NORM_ANY, CF_NORM_WIDE, CF_NORM_NARROW,        // k_chain_iter_norm_*<np>
@@ -895,7 +866,7 @@ ChainKernel chain_kernel(const Ctx* c, int flags) {
                      : F.gen_keys ? CF_GEN_KEYS : (fits64 && !F.inline_walk) ? CF_GEN_64 : F.tpw == 2 ? CF_GEN_2 : CF_GEN;
     ChainKernel K = chain_instance(family, P.np, F.inline_walk);
     if (user) K.name = c->u_lanes ? "user_lanes_3launches" : "user_3launches";
-    if (c->obj == SMM_OBJ_DENSE && P.dense_A2f) K.name = "iter<dense2,16>";
+    if (c->obj == SMM_OBJ_DENSE && c->dense2) K.name = "iter<dense2,16>";
     // an objective without a simulation (banana, user objectives) has work for the tile's control wave only: unless the exchange
     // walk runs inline (all lanes stage its inputs) the tile is launched as that one wave, so that every tile of a large
     // population is resident at once instead of queueing behind 448 idle lanes each
@@ -964,7 +935,7 @@ void launch_chain_iter(Ctx* c, int t, int flags) {
     c->P.nan_flags_out = own_slots ? c->nan_flags + (t & 1) : nullptr;
     if (own_slots) c->run.slots_iter = t;
     const ChainKernel K = chain_kernel(c, flags);
-    const size_t smem = tile_smem(c, K.ct, K.tpw);
+    const size_t smem = tile_smem(c, c->F, K.ct, K.tpw);
     const double* rin = c->ext_rec_in ? c->ext_rec_in : (const double*)c->rec[c->run.cur];
     double* rout = c->ext_rec_out ? c->ext_rec_out : c->rec[c->run.cur ^ 1];
     if (c->obj == SMM_OBJ_USER) {
@@ -977,8 +948,6 @@ void launch_chain_iter(Ctx* c, int t, int flags) {
     launch_chain_kernel(c, K, smem, c->P, t, rin, rout, flags);
     if (!c->ext_rec_out) c->run.cur ^= 1;
 }
-
-size_t resolve_lean_bytes(int Ng, int K, bool wide) { return std::max(wide ? lean_wide_bytes(Ng, K) : lean_walk_bytes(Ng, K), resolve_lvl_soa_bytes(Ng, K)); }
 
 void launch_resolve_p(Ctx* c, const KParams& P, int t, const double* gathered);
 void launch_resolve(Ctx* c, int t, const double* gathered) { launch_resolve_p(c, c->P, t, gathered); }
@@ -1127,13 +1096,12 @@ void launch_resolve_rows_window(Ctx* c, int t) {
 // what launches F's persistent kernel: a kernel of the library (fn) or of a user objective's module (mfn: loaded by persist_occupancy),
 // its grid, block and dynamic LDS.  persist_occupancy sets its LDS attribute and asks for its occupancy, launch_chain_persist launches it,
 // smm_describe prints its name.
-struct PersistKernel { const void* fn; hipFunction_t mfn; dim3 grid, block; size_t smem; const char* name; };
 PersistKernel persist_kernel(const Ctx* c, const Forms& F) {
     const KParams& P = c->P;
     PersistKernel K{nullptr, nullptr, dim3(persist_tiles_rank(F, P.N)), dim3(1), 0, "none"};
     if (F.persist == PERSIST_GEN) {
         K.block = dim3(1024);
-        K.smem = persist_gen_smem_bytes(P.Ng, P.np, P.RW, P.HW) + (F.persist_user ? persist_gen_user_bytes() : 0);
+        K.smem = persist_gen_smem(c, F.persist_user);
         K.name = F.persist_user ? "gen_user" : "gen";
         if (F.persist_user) K.mfn = c->pfn;   // (the same kernel, compiled with the user's objective inside: user_persist_compile)
         else K.fn = (const void*)k_chain_persist_gen;
@@ -1152,11 +1120,11 @@ PersistKernel persist_kernel(const Ctx* c, const Forms& F) {
         K.block = dim3(WG);
         K.smem = persist_tile_smem(c);
         K.name = c->obj == SMM_OBJ_USER ? (F.persist_sh ? "tile_user_shard" : "tile_user") : !dense ? (F.persist_sh ? "tile_sim_shard" : "tile_sim")
-               : P.dense_A2f ? (F.persist_sh ? "tile_dense2_shard" : "tile_dense2") : (F.persist_sh ? "tile_dense_shard" : "tile_dense");
+               : c->dense2 ? (F.persist_sh ? "tile_dense2_shard" : "tile_dense2") : (F.persist_sh ? "tile_dense_shard" : "tile_dense");
         if (c->obj == SMM_OBJ_USER) K.mfn = c->pfn;   // (the same kernel, compiled with the user's map-reduce objective inside: user_tile_compile)
         else if (F.persist_sh) K.fn = dense ? (const void*)k_chain_persist_tile<2, false, true> : (const void*)k_chain_persist_tile<1, false, true>;
-        else if (P.chol_L && P.mi_pct) K.fn = dense ? (const void*)k_chain_persist_tile<2, true, false, true> : (const void*)k_chain_persist_tile<1, true, false, true>;
-        else if (P.chol_L) K.fn = dense ? (const void*)k_chain_persist_tile<2, false, false, true> : (const void*)k_chain_persist_tile<1, false, false, true>;
+        else if (c->has_chol && P.mi_pct) K.fn = dense ? (const void*)k_chain_persist_tile<2, true, false, true> : (const void*)k_chain_persist_tile<1, true, false, true>;
+        else if (c->has_chol) K.fn = dense ? (const void*)k_chain_persist_tile<2, false, false, true> : (const void*)k_chain_persist_tile<1, false, false, true>;
         else if (P.mi_pct) K.fn = dense ? (const void*)k_chain_persist_tile<2, true> : (const void*)k_chain_persist_tile<1, true>;
         else K.fn = dense ? (const void*)k_chain_persist_tile<2> : (const void*)k_chain_persist_tile<1>;
     }
@@ -1170,270 +1138,6 @@ void launch_persist(Ctx* c, const PersistKernel& K, PersistArgs A) {
     else if (K.mfn) HIPCHK(hipModuleLaunchKernel(K.mfn, K.grid.x, 1, 1, K.block.x, 1, 1, (unsigned)K.smem, c->stream, args, nullptr));
     else if (c->kev0) HIPCHK(hipExtLaunchKernel(K.fn, K.grid, K.block, args, K.smem, c->stream, c->kev0, c->kev1, 0));
     else HIPCHK(hipLaunchKernel(K.fn, K.grid, K.block, args, K.smem, c->stream));
-}
-
-// ---- the forms of a context (smm_ctx_create) ----
-// what the device says about a context's forms: its compute units, and the resident workgroups per CU of the one persistent kernel
-// that is the candidate (-1: not asked yet — select_forms then names the candidate; 0: it is not available, its user kernel did not compile)
-struct DeviceFacts { int n_cus = 256; int per_cu = -1; };
-
-// Every form a context runs, from the problem (c->P, c->obj, the user objective's lanes, the injected tables), the hooks and the device.
-// Decides and allocates nothing.  The order of preference between the persistent forms: gen -> gen_user -> gen_small / user -> loc /
-// shard -> tile, each only where none before it was taken.
-Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
-    const KParams& P = c->P;
-    const int np = P.np, nm = P.nm, ns = P.ns, N = P.N, Ng = P.Ng, K = P.plan_K, n_cus = dev.n_cus;
-    const bool user_obj = c->obj == SMM_OBJ_USER, minus = P.dist_fun == SMM_DIST_MINUS, chol = P.chol_L != nullptr;
-    const bool mi0 = P.mi_uniform && P.mi_value == 0.0;   // one threshold 0 for all chains
-    Forms F;
-    // the level plan in LDS, or in global memory
-    bool lds = Ng > 1 && Ng <= XLDS_MAX && K >= 1 && K <= Ng && !H.any_exchange;
-    bool lvl = lds && Ng <= XLVL_MAX && !H.dataflow;
-    bool lvl_soa = lds && !lvl && !H.dataflow;
-    // (... and a SHARD whose population is past what the lean plan's 16-byte walk holds in LDS — one min_improve > 0 for all chains of
-    // 7400 < N_global <= 8192, e.g. 2 x 4096 with the reference's default threshold —: the global-memory plan lists its tiles' cones,
-    // locally numbered, so that the shard can still take the persistent form)
-    const bool shard_wide_big = N < Ng && lds && P.mi_uniform && P.mi_value != 0.0 && !(P.mi_value < 0.0) && minus &&
-                                resolve_lean_bytes(Ng, K, true) > (size_t)160 * 1024;
-    const bool big = Ng > 1 && Ng <= 65535 && K >= 1 && K <= Ng && !H.any_exchange && (H.big_exchange || shard_wide_big || !lds);
-    if (big) lds = lvl = lvl_soa = false;
-    const bool key = big && Ng <= XKEY_MAX && K <= XKEY_MAX && !H.key_exchange_off && minus;   // (the keys order value_i - value_j)
-    F.plan = big ? PLAN_BIG : lds ? PLAN_LDS : PLAN_NONE;
-    // inline exchange walk: single shard, level plan available, and two tiles must still share a CU's 160 KB LDS
-    const int tile_ct = is_sim(c->obj) ? F.ct : (c->obj == SMM_OBJ_DENSE ? 16 : 8);
-    const size_t tile_b = (tile_smem_base(c, tile_ct) + 15) & ~(size_t)15;
-    F.norm_fast = is_sim(c->obj) && np == nm && np <= 4 && P.batch_size == np && P.dbg == 0 && !chol && !H.norm_fast_off;
-    // more tiles than CUs: the walk-free kernel on half-size workgroups, two to a CU (k_chain_iter_norm_narrow)
-    F.norm_narrow = F.norm_fast && ((N + NORM_CT - 1) / NORM_CT > n_cus || H.norm_narrow == 1) && H.norm_narrow != 0;
-    // k_chain_iter_norm: pair list NOT overlaid; room for either walk (16-byte slots, 4-byte slots + value table)
-    const bool wide_form = P.mi_uniform && P.mi_value != 0.0 && !(P.mi_value < 0.0);   // (the lean walk on 16-byte slots, below)
-    const size_t walk_b = std::max(walk_slot_bytes(Ng) + (((size_t)K * 4 + 15) & ~(size_t)15),
-                                   ((wide_form ? lean_wide_bytes(Ng, K) : lean_walk_bytes(Ng, K)) + 15) & ~(size_t)15);
-    F.inline_walk = !H.inline_walk_off && lvl && N == Ng && !user_obj &&
-                    (!F.norm_fast || minus) &&   // (k_chain_iter_norm's walks are for `-`)
-                    (F.norm_fast ? walk_b + norm_tile_doubles(np) * 8 <= (size_t)160 * 1024
-                                 : walk_slot_bytes(Ng) + std::max(tile_b, (size_t)K * 4) <= (size_t)80 * 1024);
-    F.tile_off = F.inline_walk ? (int)((F.norm_fast ? walk_b : walk_slot_bytes(Ng)) / sizeof(double)) : 0;
-    // (the lean plan: the same conditions as below)
-    const bool lean_plan = P.mi_uniform && !(P.mi_value < 0.0) && minus && K <= XLDS_MAX && !H.key_walk_off &&
-                           (P.mi_value == 0.0 || resolve_lean_bytes(Ng, K, true) <= (size_t)160 * 1024);
-    // two tiles per workgroup share one walk (the 2p/2m-style simulation tile of 8 chains only) — worth it only when two tiles would
-    // share a CU anyway (more tiles than CUs)
-    F.tpw = (F.inline_walk && !F.norm_fast && (is_sim(c->obj) ? F.ct == 8 : c->obj != SMM_OBJ_DENSE) && ((N + 7) / 8 > n_cus || H.tpw == 2) &&
-             H.tpw != 1 && walk_slot_bytes(Ng) + std::max(2 * tile_b, (size_t)K * 4) <= (size_t)160 * 1024) ? 2 : 1;
-    // k_chain_iter on the lean walk (16-byte slots, padded pair list): where its somewhat larger LDS keeps the same budget
-    F.gen_lean = F.inline_walk && !F.norm_fast && lean_plan &&
-                 tile_lean_slot_bytes(Ng) + std::max((size_t)F.tpw * tile_b, (size_t)lean_walk_Kp(K) * 4) <= (size_t)(F.tpw == 2 ? 160 : 80) * 1024;
-    if (F.gen_lean) F.tile_off = (int)(tile_lean_slot_bytes(Ng) / sizeof(double));
-    // single shards of 4096 < N <= 8192 chains without a simulation (banana, BASELINE config 4): the key walk inline, two
-    // 16-chain tiles per workgroup of 1024 lanes (256 workgroups at 8192 chains: one per CU, one launch per iteration)
-    const size_t tile16 = (tile_smem_base(c, 16) + 15) & ~(size_t)15;
-    const size_t slots = (size_t)(((Ng + 3) & ~3) + 4) * 8;
-    F.gen_keys = !F.inline_walk && !H.inline_walk_off && obj_kind(c->obj) == 0 && !user_obj && N == Ng && Ng > XLVL_MAX &&
-                 Ng <= XLDS_MAX && K <= XLDS_MAX && lds && mi0 && minus && !H.key_walk_off &&
-                 slots + std::max(2 * tile16, (size_t)lean_walk_Kp(K) * 4) <= (size_t)160 * 1024;
-    if (F.gen_keys) { F.inline_walk = true; F.tpw = 2; F.tile_off = (int)(slots / sizeof(double)); }
-    // the dense objective (BASELINE config 5): its tile fills a CU's LDS (143 KB at 50 parameters / 50 moments), so the key
-    // walk's slots and lists lie UNDER the tile's blocks — the walk is over before anything of the tile is written
-    F.dense_keys = !F.inline_walk && !H.inline_walk_off && !H.dense_keys_off && c->obj == SMM_OBJ_DENSE && N == Ng &&
-                   Ng >= 2 && Ng <= XLVL_MAX && K <= XLVL_MAX && lds && mi0 && minus && !H.key_walk_off && lean_walk_unit(Ng) == 8 &&
-                   std::max(tile16, slots + std::max((size_t)CONE_LEVELS * 64 * 4, (size_t)lean_walk_Kp(K) * 4)) <= (size_t)160 * 1024;
-    if (F.dense_keys) { F.gen_keys = true; F.inline_walk = true; F.tpw = 1; F.tile_off = 0; }
-
-    // the candidates for the persistent chain kernel and the cone tables behind the plan
-    // the workgroups' cones of the inline key walk (smm_cone.hpp): where k_chain_iter walks 8192 chains' keys in every workgroup
-    const bool want_cone = F.gen_keys && !H.no_cone && (F.dense_keys ? (N % 16 == 0 && N / 16 <= 256) : (F.tpw == 2 && N % 32 == 0 && N / 32 <= 256));
-    const int cone_ct = F.dense_keys ? 16 : 32;
-    const bool gen_ok = np <= PG_MAXP && nm <= PG_MAXP && P.batch_size == np && !chol && N == Ng && !c->deep_plan && P.dbg == 0 && !H.persist_off;
-    const bool gen_fits = persist_gen_smem_bytes(Ng, np, P.RW, P.HW) <= (size_t)160 * 1024;
-    // k_chain_persist_gen (smm_chain_persist_gen.hpp), objectives without a simulation: where k_chain_iter walks its workgroups'
-    // cones inline (4096 < N <= 8192 in whole workgroups of 32 chains, one per CU), one proposal batch, isotropic proposals
-    const bool want_gen = want_cone && !F.dense_keys && c->obj == SMM_OBJ_BANANA && gen_ok && N / PG_CT <= n_cus && gen_fits;
-    // ... and for the smaller populations of the same objective (up to 4096 chains in whole groups of 32: VERDICT r4 "banana at 2048
-    // chains takes the per-iteration path"): the same kernel — the cones are listed behind the lean plan whether or not the
-    // per-iteration kernel walks them
-    const bool gen_small_ok = gen_ok && N % PG_CT == 0 && N / PG_CT >= 1 && N / PG_CT <= n_cus && lds && mi0 && minus && K <= XLDS_MAX;
-    const bool want_gen_small = !want_cone && c->obj == SMM_OBJ_BANANA && F.inline_walk && gen_small_ok && gen_fits;
-    // ... and a USER objective (one thread per evaluation) in the same loop: the kernel compiled with the user's source inside
-    // (user_persist_compile)
-    const bool want_user = user_obj && c->u_lanes == 0 && gen_small_ok &&
-                           persist_gen_smem_bytes(Ng, np, P.RW, P.HW) + persist_gen_user_bytes() <= (size_t)160 * 1024;
-    // ... and on LOCALLY NUMBERED cones (smm_chain_persist_loc.hpp): the same objective with one threshold >= 0 (or NaN: nothing
-    // ever swaps) for all chains — min_improve > 0 is the reference's default (AlgoBGP.jl:522) —, whatever the population's size
-    // does to the tile's LDS
-    const bool mi_ok = (P.mi_uniform && !(P.mi_value < 0.0)) || P.mi_pct;   // one threshold >= 0 (or NaN) for all chains, or one per chain, each >= 0 (or NaN)
-    const bool loc_ok = F.norm_fast && np <= 2 && ns <= WG * PR_ZR && minus && !c->deep_plan && P.dbg == 0 && !H.persist_off && !H.persist_loc_off;
-    const bool want_loc = loc_ok && N == Ng && Ng >= 2 && F.inline_walk && mi_ok && K <= XLDS_MAX && Ng <= XLDS_MAX && (N + NORM_CT - 1) / NORM_CT <= n_cus;
-    // ... and as a shard of a sharded run (one process per GPU: smm_bgp_p2p_step): the same kernel, the ring in the ranks' windows
-    const bool want_sh = loc_ok && N < Ng && N > 0 && Ng % N == 0 && P.offset % N == 0 && Ng / N <= P2P_MAXG && N % NORM_CT == 0 &&
-                         P.mi_uniform && !(P.mi_value < 0.0) && N / NORM_CT <= n_cus &&
-                         (lds ? K <= XLDS_MAX : (big && Ng <= 32768 && K <= 65535 && (size_t)Ng * 4 <= (size_t)160 * 1024));
-    // ... and for the objectives a whole tile evaluates (smm_chain_persist_tile.hpp): objfunc_norm with any number of parameters — the
-    // reference's larger examples have 6 and 18, Examples.jl:210-230, 232-319 — and the dense simulation (BASELINE config 5); one
-    // threshold >= 0 (or NaN) for all chains, isotropic proposals or a Cholesky factor (the kernel's CH form: no LDS of its own), one 16-chain
-    // tile per workgroup, all of them resident
-    const int tile_kind = obj_kind(c->obj);
-    // ... and a USER objective in its map-reduce form (smm_register_user_objective_lanes) whose lanes are a whole share of the tile's 512
-    const bool user_tile = user_obj && c->u_lanes > 0 && c->u_lanes <= WG && WG % c->u_lanes == 0 && PT_CT % (WG / c->u_lanes) == 0 && !P.mi_pct;   // (compiled for ONE threshold)
-    const bool want_tile = (tile_kind == 1 || tile_kind == 2 || user_tile) && !(F.norm_fast && np <= 2 && ns <= WG * PR_ZR) && N == Ng && Ng >= 2 && lds &&
-                           mi_ok && minus && K <= XLDS_MAX && Ng <= XLDS_MAX && !c->deep_plan && P.dbg == 0 && !H.persist_off &&
-                           !H.persist_tile_off && P.RW <= PT_LPC * PT_NJ && (tile_kind != 2 || N % PT_CT == 0) && (N + PT_CT - 1) / PT_CT <= 2 * n_cus &&
-                           persist_tile_smem(c) <= (size_t)160 * 1024;
-    // ... and as a shard of a sharded run (smm_bgp_p2p_step; SH of smm_chain_persist_tile.hpp): equal shards of whole tiles, the LDS plan
-    // (N_global <= 8192: every rank's progress words fit wave 2's 512 lanes' worth), one threshold >= 0 (or NaN) for all chains
-    const bool want_tile_sh = (tile_kind == 1 || tile_kind == 2 || user_tile) && !(F.norm_fast && np <= 2 && ns <= WG * PR_ZR) &&
-                              N < Ng && N > 0 && Ng % N == 0 && P.offset % N == 0 && Ng / N <= P2P_MAXG && N % PT_CT == 0 && lds &&
-                              Ng <= XLDS_MAX && K <= XLDS_MAX && P.mi_uniform && !(P.mi_value < 0.0) && !P.mi_pct && minus && !c->deep_plan && !chol &&
-                              P.dbg == 0 && !H.persist_off && !H.persist_tile_off && P.RW <= PT_LPC * PT_NJ && N / PT_CT <= 2 * n_cus &&
-                              persist_tile_smem(c) <= (size_t)160 * 1024;
-    const size_t persist_tiles = (want_gen || want_gen_small || want_user) ? (size_t)N / PG_CT : (size_t)(N + NORM_CT - 1) / NORM_CT;
-    // large single shards of objfunc_norm (C3 on one GPU): the narrow chain kernel's tiles walk their own, locally numbered cones
-    // (smm_cone_big.hpp) instead of waiting for the one-workgroup resolution between two launches
-    const bool rows = key && mi0 && !H.key_walk_off;
-    const bool want_cone_big = big && rows && F.norm_fast && F.norm_narrow && N == Ng && N % NORM_CT == 0 && Ng <= 32768 && K <= 65535 &&
-                               P.dbg == 0 && !H.cone_big_off && (size_t)Ng * 4 <= (size_t)160 * 1024;
-
-    // look-ahead windows.  Two with budgets of their own (288 GB of HBM: a few hundred MiB of look-ahead tables are nothing), at most 256
-    // iterations each.  The plan kernels are launched with one workgroup per iteration of the window: a short window leaves
-    // the chip idle while they run — at 32768 chains k_exch_plan_big needs 1.7 ms per launch, which with the 26 iterations the
-    // former common budget of 192 MiB allowed was 63 us per iteration, more than the exchange itself (round 3, rocprofv3).
-    // (the plan's budget counts the tables of every candidate, taken or not)
-    const bool pregen = !(F.norm_fast && !P.user_ntab && !P.user_utab);   // (k_chain_iter_norm draws in the kernel)
-    const size_t rb_iter = (size_t)P.RBW * N * 8;
-    const size_t cone_iter = (size_t)(CONE_LEVELS * 64 + CONE_HDRW) * 4;   // one tile's header and sub-levels
-    const size_t plan_iter = (want_cone_big ? (size_t)(N / NORM_CT) * (cone_iter + CONE_GCAP * 2) + cone_big_scratch_words(Ng, K) * 4 : 0) + (size_t)K * 36 +
-                             (big ? BigPlanScratch::words(Ng, K) * 4 + (size_t)(XROWS_MAX + 1) * XWG * 4 : 0) +
-                             (size_t)lean_walk_Kp(K) * 4 + 1024 + (want_cone ? (size_t)(N / cone_ct) * cone_iter + 4 : 0) +
-                             ((want_loc || want_sh || want_tile || want_tile_sh) ? persist_tiles * (cone_iter + CONE_GCAP * 2) + 4 : 0) +
-                             ((want_sh && big) ? cone_big_scratch_words(Ng, K) * 4 : 0) +
-                             (want_gen ? persist_tiles * (CONE_GCAP * 2) : 0) +
-                             ((want_gen_small || want_user) ? persist_tiles * (cone_iter + CONE_GCAP * 2) + 4 : 0);
-    F.win_cap = pregen ? (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)768 << 20) / rb_iter)) : 1;
-    F.win_cap = std::min(F.win_cap, P.T);
-    F.plan_cap = (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)1536 << 20) / plan_iter));
-    F.plan_cap = std::max(1, std::min(std::min(F.plan_cap, P.T), H.plan_cap));
-
-    // the exchange: the big plan's forms
-    if (big && rows) {
-        F.rows_cap = std::min(XROWS_MAX, (K + XWG - 1) / XWG + LV_MAXLEV);
-        if (want_cone_big) { F.cone_big = true; F.plan_ahead = !H.plan_ahead_off; F.walk_slots = true; }
-    }
-    if (big && want_sh) {   // a shard of a large population: its own tiles' cones, locally numbered (smm_cone_big.hpp)
-        F.persist = PERSIST_LOC; F.persist_wide = P.mi_value != 0.0; F.persist_sh = true; F.persist_sh_big = true;
-    }
-    // ... the lean walk (smm_walk_lean.hpp) behind the LDS plan: one min_improve for every chain — 0: 8-byte slots of order keys; > 0 (or
-    // NaN: nothing ever swaps): 16-byte slots of values, as far as the 160 KB of LDS reach (~7400 chains)
-    // (thresholds by chain: the lean PLAN — padded levels on 16-byte units, the tiles' cones behind it — is made for the persistent launches; the
-    // stand-alone lean resolution and the inline lean walks, which test ONE threshold, stay off: XK_LEAN below, launch_chain_iter_norm)
-    const bool wide = P.mi_uniform && !mi0 && !(P.mi_value < 0.0) && resolve_lean_bytes(Ng, K, true) <= (size_t)160 * 1024;
-    const bool pct = P.mi_pct != 0 && (want_loc || want_tile);
-    F.lean_plan = lds && (mi0 || wide || pct) && K <= XLDS_MAX && !H.key_walk_off && minus;
-    F.lean_wide = F.lean_plan && (wide || pct);
-    if (F.lean_plan) {
-        // ... walked in the prologue of k_chain_iter_norm, or of k_chain_iter (key form)
-        if (mi0 && ((F.norm_fast && F.inline_walk && Ng <= XLVL_MAX && K <= XLVL_MAX) || F.gen_keys)) {
-            F.walk_slots = true;
-            F.cone = want_cone;
-            if (want_gen) F.persist = PERSIST_GEN;
-        }
-        const bool user_ok = want_user && mi0 && F.persist == PERSIST_NONE;
-        if ((want_gen_small || user_ok) && mi0 && F.persist == PERSIST_NONE) {
-            F.persist = PERSIST_GEN; F.persist_user = user_ok; F.defer_resolve = user_ok;
-        }
-        if ((want_loc || want_sh) && F.persist == PERSIST_NONE && F.norm_fast) {   // (k_exch_plan lists the tiles' cones behind the lean plan)
-            F.persist = PERSIST_LOC; F.persist_wide = wide || pct; F.persist_sh = want_sh;
-        }
-        // (the dense tiles of the per-iteration kernel walk the same cones: want_cone above)
-        if (want_tile && F.persist == PERSIST_NONE &&
-            (!F.cone || (cone_ct == PT_CT && (size_t)(N / cone_ct) == (size_t)(N + PT_CT - 1) / PT_CT))) {
-            F.persist = PERSIST_TILE; F.persist_wide = true;
-            F.defer_resolve = !F.inline_walk;   // (the exchange of an iteration is left to the next launch: it may be this kernel's)
-        }
-        if (want_tile_sh && F.persist == PERSIST_NONE) { F.persist = PERSIST_TILE; F.persist_wide = true; F.persist_sh = true; }
-    }
-    // ... all of its tiles resident at once, or it is not taken (per_cu 0 also where a user objective's kernel did not compile)
-    if (F.persist != PERSIST_NONE && dev.per_cu >= 0) {
-        const int tiles = persist_tiles_rank(F, N);
-        if (F.persist != PERSIST_GEN) F.max_tiles = dev.per_cu * n_cus;
-        if (tiles > dev.per_cu * n_cus) {
-            F.persist = PERSIST_NONE;
-            F.persist_wide = F.persist_sh = F.persist_sh_big = F.persist_user = F.defer_resolve = false;
-        }
-    }
-    // the cone tables: the persistent form's (with gather lists), the local cones', or the inline key walk's
-    if (F.cone_big) { F.cone_tiles = N / NORM_CT; F.cone_ct = NORM_CT; F.cone_gather = true; }
-    else if (F.persist == PERSIST_GEN) { F.cone_tiles = N / PG_CT; F.cone_ct = PG_CT; F.cone_gather = true; }
-    else if (F.persist == PERSIST_LOC) { F.cone_tiles = (int)persist_tiles; F.cone_ct = NORM_CT; F.cone_gather = true; }
-    else if (F.persist == PERSIST_TILE) { F.cone_tiles = (N + PT_CT - 1) / PT_CT; F.cone_ct = PT_CT; F.cone_gather = true; }
-    else if (F.cone) { F.cone_tiles = N / cone_ct; F.cone_ct = cone_ct; }
-
-    // the stand-alone resolution
-    F.xk = (F.lean_plan && !pct) ? XK_LEAN : lvl ? XK_LVL : lvl_soa ? XK_LVL_SOA : lds ? XK_TICKETS   // (XK_TICKETS: test build only, SMMHIP_DATAFLOW_EXCHANGE)
-         : key ? (rows ? XK_ROWS : XK_KEY) : big ? XK_LVL_BIG : XK_ANY;
-    return F;
-}
-
-// the persistent kernel that is the candidate of F, asked how many of its workgroups a CU holds — with its dynamic LDS set first, as the
-// launches want it; a user objective's kernel is compiled (once per registered objective) and loaded here.  0: not available
-int persist_occupancy(Ctx* c, const Forms& F, int objective_id) {
-    if (F.persist_user || (F.persist == PERSIST_TILE && c->obj == SMM_OBJ_USER)) {   // (user_persist_compile / user_tile_compile)
-        const bool tile = F.persist == PERSIST_TILE;
-        {
-            std::lock_guard<std::mutex> lock(g_user_mutex);
-            UserObjective& u = g_user_objectives[objective_id - SMM_OBJ_USER_BASE];
-            const bool chol = tile && !F.persist_sh && c->P.chol_L != nullptr;   // (select_forms gives a shard with a factor no persistent form)
-            if (!(tile ? user_tile_compile(u, F.persist_sh, chol) : user_persist_compile(u))) {
-                if (getenv("SMMHIP_VERBOSE"))
-                    fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n",
-                            (tile ? (chol ? u.tile_chol_log : F.persist_sh ? u.tile_sh_log : u.tile_log) : u.persist_log).c_str());
-                return 0;
-            }
-            HIPCHK(hipModuleLoadData(&c->pmod, (tile ? (chol ? u.tile_chol_code : F.persist_sh ? u.tile_sh_code : u.tile_code) : u.persist_code).data()));
-        }
-        HIPCHK(hipModuleGetFunction(&c->pfn, c->pmod, tile ? "smm_user_persist_tile_kernel" : "smm_user_persist_kernel"));
-    }
-    const PersistKernel K = persist_kernel(c, F);
-    int per_cu = 0;
-    if (K.mfn) {
-        // (a module's function: not every runtime takes the attribute this way; the launch asks for what it needs)
-        (void)hipFuncSetAttribute((const void*)K.mfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K.smem);
-        (void)hipGetLastError();
-        HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, K.mfn, K.block.x, K.smem));
-    } else {
-        HIPCHK(hipFuncSetAttribute(K.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K.smem));
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, K.fn, K.block.x, K.smem));
-    }
-    return per_cu;
-}
-
-// one set of cone tables for the plan window (KParams or a PlanSet): tiles x CONE_HDRW header words, tiles x the sub-levels' pairs and,
-// with_gather, tiles x the gather lists, per iteration; cone_ok zeroed
-template <class Tables>
-void alloc_cones(Ctx* c, Tables& P, size_t tiles, bool with_gather) {
-    const size_t W = (size_t)c->F.plan_cap;
-    P.cone_ok = dalloc<uint32_t>(c, W);
-    P.cone_hdr = dalloc<uint32_t>(c, W * tiles * CONE_HDRW);
-    P.cone_pairs = dalloc<uint32_t>(c, W * tiles * (CONE_LEVELS * 64) + 1024);   // (+: whole 1 KB pieces are fetched)
-    P.cone_gather = with_gather ? dalloc<uint16_t>(c, W * tiles * CONE_GCAP + 512) : nullptr;
-    HIPCHK(hipMemset((void*)P.cone_ok, 0, W * 4));
-}
-
-// the persistent form's ring — one window (pr_win_layout; a shard's lives in its p2p window: smm_bgp_p2p_init) — and the state
-// persist_repair rolls back to (after the history's fill: hist_fill is a row of it)
-void alloc_persist(Ctx* c) {
-    KParams& P = c->P;
-    const size_t N = P.N;
-    if (!c->F.persist_sh) {
-        const PrWin WL = pr_win_layout(P.Ng, P.RW, 1, persist_tiles_rank(c->F, P.N));
-        c->prw = dalloc<unsigned char>(c, WL.total);
-        HIPCHK(hipMemset(c->prw, 0, WL.total));
-    }
-    c->snap_cs = dalloc<double>(c, N * CSW);
-    c->snap_rec = dalloc<double>(c, N * P.RW);
-    for (int b = 0; b < 2; ++b) { c->snap_vals[b] = dalloc<double>(c, N + 4); c->snap_slot8[b] = dalloc<uint2>(c, N + 4 + 128); }
-    c->snap_xres = dalloc<unsigned long long>(c, P.Ng);
-    c->hist_fill = dalloc<double>(c, N * P.HW);
-    HIPCHK(hipMemcpy(c->hist_fill, P.hrec, N * P.HW * 8, hipMemcpyDeviceToDevice));   // (a row of the constructor's fill)
 }
 
 }  // namespace
@@ -1462,6 +1166,7 @@ int check_window(Ctx* c, int t0, int t1) {
 
 #include "smm_reducers_host.hpp"
 #include "smm_population_host.hpp"
+#include "smm_create_host.hpp"
 
 extern "C" {
 
@@ -1549,396 +1254,6 @@ int smm_device_count(void) {
 }
 
 const char* smm_last_error(void* ctx) { return ctx ? ((Ctx*)ctx)->err.c_str() : g_create_err.c_str(); }
-
-void smm_ctx_destroy(void* ctx) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->pstream) { (void)hipStreamSynchronize(c->pstream); (void)hipStreamDestroy(c->pstream); }
-    if (c->ev_free) (void)hipEventDestroy(c->ev_free);
-    for (Ctx::PlanSet& S : c->ps) { if (S.done) (void)hipEventDestroy(S.done); if (S.ok_host) (void)hipHostFree(S.ok_host); }
-    for (void* p : c->allocs) (void)hipFree(p);
-    for (void* w : c->p2p_opened) if (w) (void)hipIpcCloseMemHandle(w);
-    if (c->p2p_mine) (void)hipFree(c->p2p_mine);
-    if (c->st_scr) (void)hipFree(c->st_scr);
-    if (c->red_res) (void)hipFree(c->red_res);
-    if (c->umod) (void)hipModuleUnload(c->umod);
-    if (c->pmod) (void)hipModuleUnload(c->pmod);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    for (hipEvent_t e : c->pev) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
-
-int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const smm_tables_t* tab, void** out) {
-    if (!prob || !opts || !out) return fail(nullptr, SMM_ERR_INVALID_ARG, "null argument");
-    const int np = prob->np, nm = prob->nm, ns = prob->ns, N = opts->N, T = opts->maxiter, Ng = opts->N_global;
-    if (np < 1 || nm < 1 || ns < 1 || np > MAX_DIM || nm > MAX_DIM)
-        return fail(nullptr, SMM_ERR_INVALID_ARG, "need 1 <= np,nm <= 64 and ns >= 1");
-    if (N < 1 || T < 1 || Ng < N || opts->chain_offset < 0 || opts->chain_offset + N > Ng || (Ng % N) != 0)
-        return fail(nullptr, SMM_ERR_INVALID_ARG, "bad N / N_global / chain_offset / maxiter");
-    const bool user_obj = prob->objective_id >= SMM_OBJ_USER_BASE;
-    if (user_obj) {
-        std::lock_guard<std::mutex> lock(g_user_mutex);
-        if (prob->objective_id - SMM_OBJ_USER_BASE >= (int)g_user_objectives.size())
-            return fail(nullptr, SMM_ERR_INVALID_ARG, "unknown user objective handle");
-    } else if (prob->objective_id < 0 || (prob->objective_id > SMM_OBJ_DENSE && prob->objective_id != SMM_OBJ_DENSE2))
-        return fail(nullptr, SMM_ERR_INVALID_ARG, "unknown objective_id");
-    if (is_sim(prob->objective_id) && np != nm)
-        return fail(nullptr, SMM_ERR_INVALID_ARG, "objfunc_norm needs one moment per parameter (ObjExamples.jl:66-78)");
-    if (opts->batch_size < 1 || opts->batch_size > np || (np % opts->batch_size) != 0)
-        return fail(nullptr, SMM_ERR_BAD_BATCH, "batch_size must divide the number of parameters (AlgoBGP.jl:95-103)");
-    if (opts->sigma_update_steps < 1) return fail(nullptr, SMM_ERR_INVALID_ARG, "sigma_update_steps < 1");
-    if (opts->smpl_iters < 1) return fail(nullptr, SMM_ERR_INVALID_ARG, "smpl_iters < 1 (AlgoBGP.jl:521: at least one proposal try)");
-    // the exchange of iteration t reads the history of iteration t-1: the reference starts at algo.i >= 2 (AlgoBGP.jl:637)
-    if (opts->exchange_from_iter < 2) return fail(nullptr, SMM_ERR_INVALID_ARG, "exchange_from_iter < 2 (AlgoBGP.jl:637)");
-    if (!prob->init || !prob->lb || !prob->ub || !prob->mom || !prob->w)
-        return fail(nullptr, SMM_ERR_INVALID_ARG, "smm_problem_t: init / lb / ub / mom / w must not be NULL");
-    if (!opts->sigma || !opts->acc_tuner || !opts->min_improve)
-        return fail(nullptr, SMM_ERR_INVALID_ARG, "smm_bgp_opts_t: sigma / acc_tuner / min_improve must not be NULL (length N_global)");
-    if (prob->n_obj_params > 0 && !prob->obj_params) return fail(nullptr, SMM_ERR_INVALID_ARG, "n_obj_params > 0 but obj_params is NULL");
-    if (tab && tab->pairs && tab->n_pairs > 0) {   // injected pair lists: 0 <= i < j < N_global (16-bit packing in the plans)
-        for (size_t q = 0; q < (size_t)T * tab->n_pairs; ++q) {
-            const int32_t i = tab->pairs[2 * q], j = tab->pairs[2 * q + 1];
-            if (i < 0 || j <= i || j >= Ng) return fail(nullptr, SMM_ERR_INVALID_ARG, "smm_tables_t.pairs: need 0 <= i < j < N_global");
-        }
-    }
-    if (tab && tab->prop_normals && tab->prop_tries < 1) return fail(nullptr, SMM_ERR_INVALID_ARG, "prop_normals given but prop_tries < 1");
-    if (opts->dist_fun < SMM_DIST_MINUS || opts->dist_fun > SMM_DIST_RELDIFF)
-        return fail(nullptr, SMM_ERR_INVALID_ARG, "smm_bgp_opts_t.dist_fun: SMM_DIST_MINUS, SMM_DIST_ABSDIFF or SMM_DIST_RELDIFF");
-    if (opts->chol_L && opts->batch_size != np)
-        return fail(nullptr, SMM_ERR_BAD_BATCH, "Cholesky proposals (chol_L) draw all parameters in one batch: batch_size must equal np");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(nullptr, SMM_ERR_NO_DEVICE, "no HIP device available: libsmmhip has no CPU fallback");
-    if (opts->device < 0 || opts->device >= ndev) return fail(nullptr, SMM_ERR_INVALID_ARG, "bad device ordinal");
-    Ctx* c = new Ctx();
-    try {
-        c->H = read_hooks();
-        c->device = opts->device;
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreate(&c->ev0));
-        HIPCHK(hipEventCreate(&c->ev1));
-        KParams& P = c->P;
-        c->obj = user_obj ? SMM_OBJ_USER : prob->objective_id == SMM_OBJ_DENSE2 ? SMM_OBJ_DENSE : prob->objective_id;   // (spec v2: the dense kind with P.dense_A2f set)
-        c->exchange_from = opts->exchange_from_iter;
-        P.exch_from = opts->exchange_from_iter;
-        {
-            const char* d = getenv("SMMHIP_DBG");
-            P.dbg = d ? atoi(d) : 0;
-            P.scout_after = c->H.scout_after;
-            P.scout_gl = c->H.scout_gl;
-            const char* tsv = getenv("SMMHIP_TS");
-            if (tsv && (tsv[0] == '1' || tsv[0] == '2')) P.ts = dalloc<unsigned long long>(c, (size_t)8 * 65536);
-            P.ts_levels = tsv && tsv[0] == '2';   // also a stamp per level of the inline walk (the stamps stretch the levels: not with '1')
-        }
-        P.np = np; P.nm = nm; P.ns = ns; P.obj = c->obj;
-        P.init = dupload(c, prob->init, np); P.lb = dupload(c, prob->lb, np); P.ub = dupload(c, prob->ub, np);
-        P.mom = dupload(c, prob->mom, nm); P.w = dupload(c, prob->w, nm);
-        P.objp = prob->n_obj_params > 0 ? dupload(c, prob->obj_params, prob->n_obj_params) : nullptr;
-        c->n_objp = prob->n_obj_params > 0 ? prob->n_obj_params : 0;
-        if (user_obj) {
-            {
-                std::lock_guard<std::mutex> lock(g_user_mutex);
-                const UserObjective& u = g_user_objectives[prob->objective_id - SMM_OBJ_USER_BASE];
-                HIPCHK(hipModuleLoadData(&c->umod, u.code.data()));
-                c->u_lanes = u.lanes; c->u_nsums = u.n_sums; c->u_rng = u.rng;
-            }
-            HIPCHK(hipModuleGetFunction(&c->ufn, c->umod, "smm_user_eval_kernel"));
-            if (c->u_rng) HIPCHK(hipModuleGetFunction(&c->ufn_noseed, c->umod, "smm_user_eval_noseed_kernel"));
-            P.u_theta = dalloc<double>(c, (size_t)N * np);
-            P.u_simM = dalloc<double>(c, (size_t)N * nm);
-            P.u_value = dalloc<double>(c, N);
-            P.u_status = dalloc<int>(c, N);
-        }
-        if (prob->objective_id == SMM_OBJ_DENSE || prob->objective_id == SMM_OBJ_DENSE2) {
-            const bool v2 = prob->objective_id == SMM_OBJ_DENSE2;   // [B, A2, A]: with the 256 x 256 stage
-            const size_t nB = (size_t)DENSE_D * np, n2 = v2 ? (size_t)DENSE_D * DENSE_D : 0, nA = (size_t)nm * DENSE_D;
-            if (prob->n_obj_params != 0 && (size_t)prob->n_obj_params != nB + n2 + nA)
-                throw std::string(v2 ? "SMM_OBJ_DENSE2: obj_params must hold B (256 x np), A2 (256 x 256) and A (nm x 256), or be empty"
-                                     : "SMM_OBJ_DENSE: obj_params must hold B (256 x np) and A (nm x 256), or be empty");
-            std::vector<double> M(nB + n2 + nA);
-            if (prob->n_obj_params) memcpy(M.data(), prob->obj_params, M.size() * 8);
-            else {  // N(0,1)/sqrt(fan-in) from the counter RNG, stream 5
-                for (size_t i = 0; i < M.size(); i += 2) {
-                    double z0, z1;
-                    box_muller(philox_stream(opts->seed, 5, (uint32_t)(i >> 1), (uint32_t)((i >> 1) >> 32), 0, 0), z0, z1);
-                    M[i] = z0 / sqrt(i < nB ? (double)np : (double)DENSE_D);
-                    if (i + 1 < M.size()) M[i + 1] = z1 / sqrt(i + 1 < nB ? (double)np : (double)DENSE_D);
-                }
-            }
-            const int nPs = (np + 3) / 4, nOt = (nm + 15) / 16;
-            std::vector<double> Bf((size_t)(DENSE_D / 16) * nPs * 64, 0.0), Af((size_t)nOt * (DENSE_D / 16) * 4 * 64, 0.0);
-            for (int T = 0; T < DENSE_D / 16; ++T)
-                for (int s = 0; s < nPs; ++s)
-                    for (int l = 0; l < 64; ++l) {
-                        const int d = 16 * T + (l & 15), p = 4 * s + (l >> 4);
-                        if (p < np) Bf[((size_t)T * nPs + s) * 64 + l] = M[(size_t)d * np + p];
-                    }
-            for (int o = 0; o < nOt; ++o)
-                for (int T = 0; T < DENSE_D / 16; ++T)
-                    for (int s = 0; s < 4; ++s)
-                        for (int l = 0; l < 64; ++l) {
-                            const int k = 16 * o + (l & 15), d = 16 * T + 4 * s + (l >> 4);
-                            if (k < nm) Af[(((size_t)o * (DENSE_D / 16) + T) * 4 + s) * 64 + l] = M[nB + n2 + (size_t)k * DENSE_D + d];
-                        }
-            P.dense_Bf = dupload(c, Bf.data(), Bf.size());
-            P.dense_Af = dupload(c, Af.data(), Af.size());
-            P.dense_nOt = nOt;
-            if (v2) {   // A2 in fragment order [wave][k-step][lane][the wave's two row tiles] (smm_chain.hpp: dense2_tile_n)
-                std::vector<double> A2f((size_t)DENSE_D * DENSE_D);
-                for (int wv = 0; wv < 8; ++wv)
-                    for (int s = 0; s < DENSE_D / 4; ++s)
-                        for (int l = 0; l < 64; ++l)
-                            for (int tt = 0; tt < 2; ++tt) {
-                                const int j = 16 * (2 * wv + tt) + (l & 15), d = 4 * s + (l >> 4);
-                                A2f[(((size_t)wv * (DENSE_D / 4) + s) * 64 + l) * 2 + tt] = M[nB + (size_t)j * DENSE_D + d];
-                            }
-                P.dense_A2f = dupload(c, A2f.data(), A2f.size());
-            }
-        }
-        {
-            const int rows = (ns + WG - 1) / WG;
-            P.zstride = ((rows + ZU) / ZU) * ZU * WG;  // at least one chunk beyond the last full one
-            std::vector<double> Z((size_t)nm * P.zstride, 0.0);
-            for (int k = 0; k < nm; ++k)
-                for (int s = 0; s < ns; ++s)
-                    Z[(size_t)k * P.zstride + s] = (tab && tab->Z) ? tab->Z[(size_t)k * ns + s] : rng_Z(opts->seed, (uint32_t)k, (uint32_t)s);
-            P.Z = dupload(c, Z.data(), Z.size());
-        }
-        P.N = N; P.Ng = Ng; P.offset = opts->chain_offset; P.T = T;
-        P.sigma_update_steps = opts->sigma_update_steps; P.smpl_iters = opts->smpl_iters;
-        P.batch_size = opts->batch_size; P.sigma_adjust_by = opts->sigma_adjust_by; P.seed = opts->seed;
-        P.min_improve_g = dupload(c, opts->min_improve, Ng);
-        if (opts->chol_L) {
-            P.chol_per_chain = opts->chol_per_chain ? 1 : 0;
-            P.chol_L = dupload(c, opts->chol_L, (size_t)(P.chol_per_chain ? Ng : 1) * np * np);
-        }
-        P.dist_fun = opts->dist_fun;
-        P.mi_uniform = 1; P.mi_value = opts->min_improve[0];
-        for (int i = 1; i < Ng; ++i)
-            if (!(opts->min_improve[i] == P.mi_value || (opts->min_improve[i] != opts->min_improve[i] && P.mi_value != P.mi_value))) P.mi_uniform = 0;   // (NaN everywhere is one threshold too: nothing ever swaps)
-        // per-chain thresholds (what the reference's API takes: opts["min_improve"] is a vector, AlgoBGP.jl:522): the persistent forms walk them too
-        // (a threshold per slot position, smm_walk_lean.hpp PCT) while this context's single iterations keep the forms they had (the level walk on any
-        // thresholds): every threshold >= 0 or NaN (the dummy pair's 0 - 0 must not exceed it), dist_fun = `-`
-        P.mi_pct = 0;
-        if (!P.mi_uniform && opts->dist_fun == SMM_DIST_MINUS) {
-            P.mi_pct = 1;
-            for (int i = 0; i < Ng; ++i) if (opts->min_improve[i] < 0.0) P.mi_pct = 0;
-        }
-        const size_t TN = (size_t)T * N;
-        if (tab && tab->probs_acc) P.user_utab = dupload(c, tab->probs_acc, TN);
-        if (tab && tab->prop_normals && tab->prop_tries > 0) {
-            P.rb_tries = tab->prop_tries; P.user_n = 1;
-            P.user_ntab = dupload(c, tab->prop_normals, TN * (size_t)tab->prop_tries * np);
-        } else {
-            // tries of mysample whose normals are made ahead of time (k_pregen_rng); later ones come from the generator inside the chain
-            // kernel, ~1.4 us per try and tile.  Past 8 parameters: two (C4, 10 parameters: four cost 9 % — 398 -> 433 M chain-evals/s
-            // with two, 447 with one; a first try outside the support is rare, a second one rarer)
-            P.rb_tries = np <= 8 ? 8 : 2;
-        }
-        if ((size_t)P.rb_tries * (size_t)((np + 1) / 2) * (size_t)N >= ((size_t)1 << 31))   // (k_pregen_rng indexes one iteration's pieces in 32 bits)
-            throw std::string("injected proposal normals: tries x parameters x chains of one iteration must stay below 2^31 pieces");
-        if (tab && tab->pairs && tab->n_pairs > 0) {
-            P.n_pairs_tab = tab->n_pairs;
-            P.pairtab = dupload(c, tab->pairs, (size_t)T * tab->n_pairs * 2);
-            {   // dependency depth of the injected lists (pairs sharing a chain keep their order): the lean walks hold LV_MAXLEV levels
-                std::vector<int> last((size_t)Ng);
-                for (int it = 0; it < T && !c->deep_plan; ++it) {
-                    std::fill(last.begin(), last.end(), 0);
-                    for (int q = 0; q < tab->n_pairs; ++q) {
-                        const int32_t i = tab->pairs[2 * ((size_t)it * tab->n_pairs + q)], j = tab->pairs[2 * ((size_t)it * tab->n_pairs + q) + 1];
-                        const int lv = std::max(last[i], last[j]) + 1;
-                        last[i] = last[j] = lv;
-                        if (lv > LV_MAXLEV) { c->deep_plan = true; break; }
-                    }
-                }
-            }
-        }
-        P.RW = even_up(3 + np + nm);
-        P.HW = even_up(H_PARAMS + np + nm);
-        P.RBW = even_up(1 + P.rb_tries * np);
-        const int K = exchange_K(c);
-        P.plan_K = K;
-        // the forms: the device's compute units, then the candidate persistent kernel's occupancy, then the choice
-        DeviceFacts dev;
-        (void)hipDeviceGetAttribute(&dev.n_cus, hipDeviceAttributeMultiprocessorCount, c->device);
-        c->F = select_forms(c, c->H, dev);
-        if (c->F.persist != PERSIST_NONE) {
-            dev.per_cu = persist_occupancy(c, c->F, prob->objective_id);
-            c->F = select_forms(c, c->H, dev);
-        }
-        const Forms& F = c->F;
-        P.tile_off = F.tile_off;
-        P.gen_lean = F.gen_keys ? 2 : F.gen_lean ? 1 : 0;
-        P.rows_cap = F.rows_cap;
-        // the look-ahead tables
-        c->win_rb = dalloc<double>(c, (size_t)F.win_cap * N * P.RBW);
-        HIPCHK(hipMemset(c->win_rb, 0, (size_t)F.win_cap * N * P.RBW * 8));
-        const size_t W = (size_t)F.plan_cap;
-        if (F.plan != PLAN_NONE) {
-            c->win_lv_pairs = dalloc<uint32_t>(c, W * K);
-            c->win_lv_mi = dalloc<double>(c, W * K);
-            c->win_lv_off = dalloc<uint32_t>(c, W * (K + 2));
-        }
-        if (F.plan == PLAN_BIG) c->big_scratch = dalloc<uint32_t>(c, W * BigPlanScratch::words(Ng, K));
-        if (F.xk == XK_ROWS) {
-            c->win_lv_rows = dalloc<uint32_t>(c, W * P.rows_cap * XWG);
-            c->win_lv_rowinfo = dalloc<uint32_t>(c, W * 4);
-            c->slots17 = dalloc<uint32_t>(c, (size_t)Ng + 4);
-            c->nan_flags = dalloc<uint32_t>(c, 4);
-            HIPCHK(hipMemset(c->nan_flags, 0, 16));
-        }
-        if (F.plan == PLAN_LDS) {
-            c->win_plan = dalloc<unsigned long long>(c, W * K);
-            c->win_plan_mi = dalloc<double>(c, W * K);
-        }
-        if (F.lean_plan) {
-            P.lean_wide = F.lean_wide ? 1 : 0;
-            P.plan_Kp = lean_walk_Kp(K);
-            P.lean_unit = F.lean_wide ? lean_wide_unit(Ng) : lean_walk_unit(Ng);
-            c->win_lv_pairs_p = dalloc<uint32_t>(c, W * P.plan_Kp + 512);   // (+512: whole 1 KB pieces may be read past the last iteration's words)
-            c->win_lv_offp = dalloc<uint32_t>(c, W * LV_OFFP);
-        }
-        if (F.walk_slots) {   // the lean key walk's slots, written by the accept step
-            for (int b = 0; b < 2; ++b) c->slot8_buf[b] = dalloc<uint2>(c, (size_t)N + 4 + 128);
-            P.slot8 = c->slot8_buf[0];
-            P.walk_flags = dalloc<uint32_t>(c, 4);
-            HIPCHK(hipMemset(P.walk_flags, 0, 16));
-        }
-        if (F.cone_tiles) {
-            P.cone_tiles = F.cone_tiles; P.cone_ct = F.cone_ct;
-            alloc_cones(c, P, (size_t)F.cone_tiles, F.cone_gather);
-        }
-        if (F.cone_big || F.persist_sh_big) c->cb_scratch = dalloc<uint32_t>(c, W * cone_big_scratch_words(Ng, K));
-        if (F.plan_ahead) {   // the big plan's second set of tables (the first: the window's own)
-            HIPCHK(hipStreamCreateWithFlags(&c->pstream, hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&c->ev_free, hipEventDisableTiming));
-            Ctx::PlanSet& S0 = c->ps[0];
-            S0.lv_pairs = c->win_lv_pairs; S0.lv_mi = c->win_lv_mi; S0.lv_off = c->win_lv_off; S0.lv_rows = c->win_lv_rows; S0.lv_rowinfo = c->win_lv_rowinfo;
-            S0.cone_ok = (uint32_t*)P.cone_ok; S0.cone_hdr = (uint32_t*)P.cone_hdr; S0.cone_pairs = (uint32_t*)P.cone_pairs; S0.cone_gather = P.cone_gather;
-            Ctx::PlanSet& S1 = c->ps[1];
-            S1.lv_pairs = dalloc<uint32_t>(c, W * K);
-            S1.lv_mi = dalloc<double>(c, W * K);
-            S1.lv_off = dalloc<uint32_t>(c, W * (K + 2));
-            S1.lv_rows = dalloc<uint32_t>(c, W * P.rows_cap * XWG);
-            S1.lv_rowinfo = dalloc<uint32_t>(c, W * 4);
-            alloc_cones(c, S1, (size_t)F.cone_tiles, true);
-            for (Ctx::PlanSet& S : c->ps) {
-                HIPCHK(hipHostMalloc((void**)&S.ok_host, W * 4, hipHostMallocDefault));
-                HIPCHK(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-            }
-        }
-        {   // chain state blocks and records (BGPChain ctor, AlgoBGP.jl:78-109: best = Inf, best_id = -1, ...)
-            std::vector<double> cs((size_t)N * CSW, 0.0);
-            for (int i = 0; i < N; ++i) {
-                double* b = cs.data() + (size_t)i * CSW;
-                b[CS_SIGMA] = opts->sigma[opts->chain_offset + i];
-                b[CS_BEST] = INFINITY; b[CS_BESTID] = -1.0; b[CS_BESTP] = INFINITY; b[CS_BESTPID] = -1.0;
-                b[CS_ATUN] = opts->acc_tuner[opts->chain_offset + i];
-            }
-            P.cs = dupload(c, cs.data(), cs.size());
-            std::vector<double> rec((size_t)N * P.RW, 0.0);
-            for (int i = 0; i < N; ++i) rec[(size_t)i * P.RW] = INFINITY;  // value: Inf until the first accept
-            for (int b = 0; b < 2; ++b) c->rec[b] = dupload(c, rec.data(), rec.size());
-        }
-        P.xres = dalloc<unsigned long long>(c, Ng);
-        if (N > 0 && Ng % N == 0 && opts->chain_offset % N == 0) {   // equal shards: the values form of the sharded exchange is available
-            c->a2a_G = Ng / N;
-            c->a2a_cap = c->H.a2a_cap ? c->H.a2a_cap : a2a_capacity(N, c->a2a_G);
-            c->a2a_send_idx = dalloc<int32_t>(c, (size_t)c->a2a_G * c->a2a_cap);
-            c->a2a_send_cnt = dalloc<int32_t>(c, (size_t)c->a2a_G);
-            c->a2a_rowidx = dalloc<int32_t>(c, (size_t)N);
-        }
-        for (int b = 0; b < 2; ++b) c->vals_buf[b] = dalloc<double>(c, (size_t)N + 4);   // (+4: read as 16-byte pieces)
-        P.vals = c->vals_buf[0];
-        if (F.plan != PLAN_LDS) {
-            const int Kmax = std::max(K, 1);
-            P.xval = dalloc<double>(c, Ng); P.xnext = dalloc<int32_t>(c, Ng); P.xpairs = dalloc<int32_t>(c, (size_t)Kmax * 2);
-            P.xsrc = dalloc<int32_t>(c, Ng); P.xpartner = dalloc<int32_t>(c, Ng);
-            P.xslot = dalloc<double>(c, (size_t)Ng * 2);
-        }
-        {   // history: NaN values, curr/best = Inf, best_id = -1, exchanged = accepted = status = 0
-            std::vector<double> row((size_t)N * P.HW, NAN);
-            for (int i = 0; i < N; ++i) history_head(row.data() + (size_t)i * P.HW, NAN, NAN, INFINITY, INFINITY, -1.0, 0.0, 0.0, 0.0);
-            P.hrec = dalloc<double>(c, TN * P.HW);
-            // (one row from the host, then doubling copies on the device: a long history — bench.py's repetitions hold 50 000 iterations — is filled
-            // at HBM speed instead of row by row over PCIe)
-            HIPCHK(hipMemcpy(P.hrec, row.data(), row.size() * 8, hipMemcpyHostToDevice));
-            for (size_t have = 1; have < (size_t)T; have *= 2) {
-                const size_t n = std::min(have, (size_t)T - have);
-                HIPCHK(hipMemcpy(P.hrec + have * N * P.HW, P.hrec, n * N * P.HW * 8, hipMemcpyDeviceToDevice));
-            }
-        }
-        P.err = dalloc<unsigned long long>(c, 1);
-        {
-            const unsigned long long e = ERR_NONE;
-            HIPCHK(hipMemcpy(P.err, &e, 8, hipMemcpyHostToDevice));
-        }
-        if (F.persist != PERSIST_NONE) alloc_persist(c);
-        if (F.plan == PLAN_BIG)
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_plan_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan_big_lds_bytes(65535)));
-        if (F.xk == XK_ROWS || F.xk == XK_KEY) {
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_key<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)resolve_key_bytes(XKEY_MAX, XKEY_MAX)));
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_key<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)resolve_key_bytes(XKEY_PARTNER_MAX, XKEY_PARTNER_MAX)));
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_rows<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)resolve_rows_bytes(XKEY_MAX, XKEY_MAX, XROWS_MAX)));
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_rows<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)resolve_rows_bytes(XKEY_PARTNER_MAX, XKEY_PARTNER_MAX, XROWS_MAX)));
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_rows<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)resolve_rows_bytes(XKEY_MAX, XKEY_MAX, XROWS_MAX)));
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_rows<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_rows<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)resolve_rows_bytes(XKEY_PARTNER_MAX, XKEY_PARTNER_MAX, XROWS_MAX)));
-        }
-        if (F.plan == PLAN_LDS) {
-#ifdef SMM_TEST_HOOKS
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)resolve_lds_bytes(XLDS_MAX)));
-#endif
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_plan, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)std::max(plan_lds_bytes(XLDS_MAX, XLDS_MAX), plan_cone_bytes())));
-#ifdef SMM_TEST_HOOKS
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_lvl<256>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)resolve_lvl_bytes(XLVL_MAX, XLVL_MAX)));
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_lvl<512>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)resolve_lvl_bytes(XLVL_MAX, XLVL_MAX)));
-#endif
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_lvl_soa<1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)resolve_lvl_soa_bytes(XLDS_MAX, XLDS_MAX)));
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_lvl<1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)resolve_lvl_bytes(XLVL_MAX, XLVL_MAX)));
-            HIPCHK(hipFuncSetAttribute((const void*)k_exch_resolve_lean, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024));
-        }
-        {   // tiles of problems with many parameters need more than the default 64 KiB of dynamic LDS
-            const int lim = 160 * 1024;
-            // (every kernel chain_kernel / chain_kernel_p2p can pick: what chain_instance names)
-            for (int family = 0; family < CF_COUNT; ++family)
-                for (int np = 1; np <= 4; ++np)
-                    for (int b = 0; b < 2; ++b) HIPCHK(hipFuncSetAttribute(chain_instance(family, np, b != 0).fn, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            if (F.cone_big) HIPCHK(hipFuncSetAttribute((const void*)k_cone_chains, hipFuncAttributeMaxDynamicSharedMemorySize, Ng * 4));
-            HIPCHK(hipFuncSetAttribute((const void*)k_eval_batch<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_eval_batch<2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute((const void*)k_eval_batch<0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            if (tile_smem(c, is_sim(c->obj) ? F.ct : (c->obj == SMM_OBJ_DENSE ? 16 : 8)) > (size_t)lim)
-                throw std::string("tile does not fit the 160 KiB LDS");
-        }
-        reducer_kernel_attributes();
-        HIPCHK(hipDeviceSynchronize());
-    } catch (const std::string& m) {
-        g_create_err = m;
-        smm_ctx_destroy(c);
-        return SMM_ERR_HIP;
-    }
-    *out = c;
-    return SMM_OK;
-}
 
 void* smm_stream(void* ctx) { return ctx ? (void*)((Ctx*)ctx)->stream : nullptr; }
 
@@ -2165,30 +1480,6 @@ int smm_get_persistent(void* ctx, int32_t* available, int32_t* launches, int32_t
     if (available) *available = (c->F.persist != PERSIST_NONE && c->persist_on && !c->persist_broken) ? 1 : 0;
     if (launches) *launches = c->persist_launches;
     if (repairs) *repairs = c->persist_repairs;
-    return SMM_OK;
-}
-
-// which forms this context was given at creation (one line; tests/test_gpu_forms.py pins the table)
-int smm_describe(void* ctx, char* out, int32_t cap) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c || !out || cap < 1) return SMM_ERR_INVALID_ARG;
-    const KParams& P = c->P;
-    // the kernel of the iterations that walk the previous exchange inline, where the context has such iterations and a kernel made for
-    // them (narrow_cone, any, wide); else the kernel of the others (k_chain_iter_norm<np, true> is "iter_norm" like <np, false>, and where
-    // the walk-free iterations take the narrow kernel that one is named)
-    const bool walks = c->F.inline_walk || c->F.cone_big;
-    ChainKernel chain = chain_kernel(c, walks ? F_WALK_INLINE : 0);
-    if (walks && !strcmp(chain.name, "iter_norm")) chain = chain_kernel(c, 0);
-    static const char* xk[] = {"lean", "lvl", "lvl_soa", "tickets", "rows", "key", "lvl_big", "any"};
-    const char* walk = c->F.cone_big ? "cone_local" : !c->F.inline_walk ? "standalone" : c->F.dense_keys ? "inline_keys_under_tile" : c->F.gen_keys ? (c->F.cone ? "inline_keys_cone" : "inline_keys")
-                     : c->F.norm_fast ? ((P.lean_wide && !P.mi_pct) ? "inline_lean_wide" : (c->F.lean_plan && !P.mi_pct) ? "inline_lean" : "inline_slots") : c->F.gen_lean ? "inline_lean16" : "inline_slots";
-    const int n = snprintf(out, (size_t)cap, "chain=%s walk=%s exchange=%s persistent=%s plan=%s window=%d", chain.name, walk, xk[c->F.xk], persist_kernel(c, c->F).name,
-                           c->F.plan == PLAN_BIG ? (c->F.plan_ahead ? "big_ahead" : "big") : c->F.plan == PLAN_LDS ? "lds" : "none", c->F.plan_cap);
-    int n2 = n;
-    if (c->obj == SMM_OBJ_USER && n >= 0 && n < cap) n2 = n + snprintf(out + n, (size_t)(cap - n), " ct=%d", chain.ct);   // (the three launches' tile width)
-    // (only once a starting population has been installed: smm_set_population / smm_scatter_population)
-    if (c->pop_kind == 1 && n2 >= 0 && n2 < cap) snprintf(out + n2, (size_t)(cap - n2), " population=set");
-    if (c->pop_kind == 2 && n2 >= 0 && n2 < cap) snprintf(out + n2, (size_t)(cap - n2), " population=scatter pop_M=%d pop_spread=%.17g", c->pop_M, c->pop_spread);
     return SMM_OK;
 }
 

@@ -175,7 +175,8 @@ def test_chain_kernel_instantiations_are_named_in_the_chooser_only():
     assert code.count(head) == 1
     a = code.index(head)
     b = code.index("\n}\n", a)
-    body, rest = code[a:b], code[:a] + code[b:] + strip(open(os.path.join(csrc, "smm_run_host.hpp")).read())
+    body, rest = code[a:b], code[:a] + code[b:] + "".join(strip(open(os.path.join(csrc, f)).read())
+                                                           for f in ("smm_run_host.hpp", "smm_forms_host.hpp", "smm_create_host.hpp"))
     assert not re.findall(r"\bk_chain_iter\w*", rest), "a chain kernel is named outside chain_instance()"
     declared = set()
     for h in ("smm_chain.hpp", "smm_chain_norm.hpp"):
@@ -242,7 +243,7 @@ def test_the_run_lives_in_the_run_host_file_with_one_frame_and_one_rule_book():
     def functions_with(pattern):
         """the functions (by name) whose definitions hold the pattern: the nearest line above that starts a definition at column 0"""
         found = set()
-        for f in ("smmhip.hip", "smm_run_host.hpp", "smm_reducers_host.hpp", "smm_population_host.hpp"):
+        for f in ("smmhip.hip", "smm_forms_host.hpp", "smm_create_host.hpp", "smm_run_host.hpp", "smm_reducers_host.hpp", "smm_population_host.hpp"):
             lines = code[f].splitlines()
             for i, line in enumerate(lines):
                 if pattern not in line:
@@ -255,7 +256,7 @@ def test_the_run_lives_in_the_run_host_file_with_one_frame_and_one_rule_book():
 
     no_throw = {"smm_last_error", "smm_stream", "smm_ctx_destroy", "smm_bgp_record_doubles", "smm_bgp_a2a_capacity", "smm_get_timing",
                 "smm_set_persistent", "smm_get_persistent", "smm_describe", "smm_set_profiling", "smm_debug_ts", "smm_debug_ts_waves",
-                "smm_debug_cone"}
+                "smm_debug_cone", "smm_debug_forms"}
     assert functions_with("(Ctx*)ctx") == {"api_call"} | no_throw
     assert functions_with("catch (const std::string") == {"api_call", "smm_ctx_create"}
     assert "reducer_call" not in everything
@@ -266,6 +267,41 @@ def test_the_run_lives_in_the_run_host_file_with_one_frame_and_one_rule_book():
     assert everything.count("k_flush,") == 1 and "void launch_flush(" in run
     assert not re.findall(r"c->kev[01] = |c->ext_(?:rec_in|rec_out|vals_out) = ", main + code["smm_reducers_host.hpp"] + code["smm_population_host.hpp"])
     assert len(re.findall(r"c->kev0 = ", run)) == 2 and len(re.findall(r"c->ext_rec_in = ", run)) == 2   # (the two scope objects)
+
+
+def test_the_forms_and_context_creation_live_in_their_host_files_with_each_rule_once():
+    """What a context runs and how much LDS that takes is smm_forms_host.hpp, which calls nothing of the HIP API; how a context is made is
+    smm_create_host.hpp.  smmhip.hip includes each once and defines none of their functions, hiprtc is given neither.  A compute unit's
+    160 KiB of LDS and the key walk's slot block are written once, and every refusal of check_create_args is one text in the tree.
+    Reads the sources only."""
+    csrc = os.path.join(ROOT, "smm.jl_amd", "csrc")
+    strip = lambda txt: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    names = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")))
+    code = {f: strip(open(os.path.join(csrc, f)).read()) for f in names}
+    main, forms, create = code["smmhip.hip"], code["smm_forms_host.hpp"], code["smm_create_host.hpp"]
+    makefile = open(os.path.join(csrc, "Makefile")).read()
+    for f in ("smm_forms_host.hpp", "smm_create_host.hpp"):
+        assert main.count('#include "%s"' % f) == 1 and sum(c.count('"%s"' % f) for c in code.values()) == 1, f
+        assert f not in makefile, f   # (not among the sources hiprtc is given)
+    assert main.index('#include "smm_forms_host.hpp"') < main.index('#include "smm_run_host.hpp"') < main.index('#include "smm_create_host.hpp"')
+    assert not re.findall(r"\bhip[A-Z]\w*\(", forms) and "HIPCHK" not in forms
+    for fn, home in (("select_forms", forms), ("smm_ctx_create", create), ("alloc_persist", create), ("persist_occupancy", create),
+                     ("tile_smem", forms), ("check_create_args", create), ("create_facts", create), ("describe_text", forms)):
+        definition = r"^[A-Za-z_][\w:<>\*& ]*\b%s\([^;]*\) \{" % fn
+        assert len(re.findall(definition, home, flags=re.M)) == 1, fn
+        assert not re.findall(definition, main, flags=re.M), fn
+    three = main + forms + create
+    assert len(re.findall(r"160 \* 1024", three)) == 1 and "160 * 1024" in forms
+    assert not re.findall(r"\b80 \* 1024", three)
+    assert len(re.findall(r"\(\(\(\w+ \+ 3\) & ~3\) \+ 4\) \* 8", three)) == 1 and "size_t key_slot_bytes(int Ng)" in forms
+    a = create.index("int check_create_args(")
+    refusals = re.findall(r'fail\(nullptr, SMM_ERR_\w+, "([^"]+)"\)', create[a:create.index("\n}\n", a)])
+    assert len(refusals) == 17 and len(set(refusals)) == 17
+    everything = "\n".join(code.values())
+    for text in refusals:
+        assert everything.count('"%s"' % text) == 1, text
+    assert "hipGetDeviceCount" not in create[a:create.index("\n}\n", a)]
+    assert create.index("check_create_args(prob, opts, tab, out)") < create.index("hipGetDeviceCount(&ndev)")
 
 
 def test_the_accept_step_is_written_once_in_smm_accept_hpp():

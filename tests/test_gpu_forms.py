@@ -1,11 +1,14 @@
 """Which forms a context is given at creation (smm_describe) — the table VERDICT r4 "Next #7" asked for: (objective, N, N_global, parameters,
 thresholds, ...) -> per-iteration chain kernel, where exchangeMoves! (AlgoBGP.jl:647-716) is walked, the stand-alone resolution, the
-persistent form, the look-ahead plan.  The selection itself lives in smm_ctx_create (smmhip.hip); this file is its specification: a change of
-the selection logic that moves a row shows up here, on purpose or not."""
+persistent form, the look-ahead plan.  The selection itself is select_forms (smm_forms_host.hpp), called by smm_ctx_create
+(smm_create_host.hpp) on what create_facts makes of the arguments; this file is its specification: a change of the selection logic that
+moves a row shows up here, on purpose or not.  tests/test_forms.py checks the same rows, and a grid around them, without a GPU through
+the test seam smm_debug_forms; the last test here ties that device-free path to what creation really used."""
 import numpy as np
 import pytest
 
 import common as cm
+import forms_grid
 from smm_jl_amd import _abi as A
 from test_gpu_p2p import shard_opts
 
@@ -95,3 +98,22 @@ def test_form_of_a_user_objective(S, O):
     assert (d["chain"], d["persistent"], d["ct"]) == ("user_3launches", "gen_user", "8"), d
     d = S.hip_context(*cm.serial_normal(N=64, T=8, ns=64)).describe()
     assert "ct" not in d, d     # (reported for user objectives only)
+
+
+def test_live_contexts_and_the_device_free_seam_agree(hooks, O):
+    """every row above once more, on the test build: the seam's line of the live context (its Forms, the DeviceFacts it was created
+    with) is the line the seam gives without a device for the same problem and options on those DeviceFacts — creation chose from the
+    facts create_facts makes of the arguments, and nothing else.  Creates contexts only."""
+    R = forms_grid.LiveRecorder()
+    for row in TABLE:
+        test_forms_of_single_shards(R, row)
+    for row in SHARDS:
+        test_forms_of_shards(R, row)
+    with forms_grid.own_registrations():
+        test_form_of_a_user_objective(R, O)
+    assert len(R.made) == len(TABLE) + len(SHARDS) + 5
+    for prob, opts, tab, ctx in R.made:
+        live = forms_grid.line_of_context(ctx)
+        d = forms_grid.fields(live)
+        assert int(d["n_cus"]) > 0 and int(d["per_cu"]) >= -1, live
+        assert forms_grid.line_without_device(prob, opts, tab, int(d["n_cus"]), int(d["per_cu"])) == live

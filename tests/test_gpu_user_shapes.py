@@ -4,6 +4,7 @@ iteration (k_chain_iter<0, CT> proposing, the user's kernel, the accept launch; 
 compiled with the user's source inside (gen_user: k_chain_persist_gen; tile_user: k_chain_persist_tile).  Every row asserts the forms it was
 given (describe: persistent, ct), then compares the device with the oracle (the gcc build of the same text) and, at dyadic theta, with the
 numpy restatement — to the bit — and a persistent run with its twin on the three launches, to the bit."""
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -37,6 +38,18 @@ def register(S, O, source, n_sums=None, lanes=256, rng=False, seed=None):
     else:
         O.hook_user_objective(host, oid, n_sums, lanes)
     return oid, host
+
+
+@contextlib.contextmanager
+def fresh_registrations():
+    """registrations made inside are kept apart from the process's: for callers that make another library current (the test build has a
+    registry of its own, and a handle of one registry means nothing to the other)"""
+    global _reg
+    saved, _reg = _reg, {}
+    try:
+        yield
+    finally:
+        _reg = saved
 
 
 def problem(S, oid, np_, nm, sums, A, N, T, seed=17, mi=0.0, batch_size=None, chol=None):
