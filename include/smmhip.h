@@ -748,6 +748,76 @@ typedef struct {            /* caller-allocated; any pointer may be NULL = not c
 int  smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group /* [N] or NULL */,
                           int32_t n_groups, const double* probs, int32_t n_probs, double ridge, smm_moment_stats_t* out);
 
+/* The regression-adjusted posterior of groups of chains, computed on the device from the history it holds: the local-linear adjustment
+ * of Beaumont, Zhang & Balding (2002).  A chain keeps a draw whose simulated moments lie near the data moments, not at them, so every
+ * posterior over the history is an ABC posterior at a non-zero tolerance; here the draws of a group are weighted by how close their
+ * simulated moments are to the data, the parameters are regressed on the moment discrepancy, and every draw is moved to where it would
+ * lie at zero discrepancy, theta* = theta - beta'(s - s_obs).  No further evaluation of the objective.  Window, groups and select are
+ * exactly those of smm_get_moment_stats (select 0 all rows, 1 the accepted rows, 2 the state series through a(t); a shard reports its own
+ * local chains; group NULL with n_groups == 1: every local chain in group 0).  tol is the accepted fraction, in (0, 1]; kernel 0 is the
+ * uniform kernel, 1 Epanechnikov's; scale NULL or nm values, each finite and > 0 (the usual per-moment standard deviation is sqrt(diag
+ * cov_mm) of smm_get_moment_stats); ridge finite and >= 0.  Caller-allocated; any pointer may be NULL (not computed).  Read-only and
+ * ordered like smm_get_chain_stats (it settles, flushes and synchronises, and changes no state, history or generator).  Device memory:
+ * smm_get_chain_stats' scratch, grown where needed to 2 x N x maxiter x 8 bytes (the distance column, later the integer weights, and one
+ * column of adjusted parameters) plus (np + nm + 2) x 8192 x 8 bytes (every joint column of one chunk, the weight and its square); the
+ * rows are taken in batches of chunks (whose (np + nm)^2 pair sums per chunk stay under 256 MiB of the result buffer) and the adjusted
+ * parameters in batches of columns, each batch reading the window once more.  SMM_ERR_INVALID_ARG: NULL ctx or out, a bad window,
+ * select outside [0, 2], n_groups < 0, group NULL with n_groups != 1, a group id outside [-1, n_groups), n_probs < 0, probs NULL with
+ * n_probs > 0, a prob outside [0, 1] or NaN, adj_quantile without probs, tol outside (0, 1] or NaN, kernel not 0 or 1, a scale not
+ * finite or not > 0, ridge negative or not finite; nothing is written then.
+ *
+ * Numerical contract (every operation rounded on its own, no fma; counts and integer weights 64-bit):
+ *   pooled rows: smm_get_moment_stats' rows: the members in ascending local index, each in iteration order; m = count.  Row i has the
+ *                parameters theta_ij (j < np) and the simulated moments s_ik (k < nm).
+ *   scale      : sc_k = scale[k] when given, else smm_get_moment_stats' s_k (w_k if it is finite and not zero, else 1.0).
+ *   discrepancy: x_ik = (s_ik - mom_k) / sc_k.
+ *   distance   : d2_i = 0.0, d2_i = d2_i + x_ik * x_ik over k ascending.
+ *   bandwidth  : delta2 = the chain-stats quantile tol of the pooled column d2 (numpy's _lerp; chunks and order as smm_get_group_stats).
+ *   weight     : kernel 0: w_i = d2_i <= delta2 ? 1.0 : 0.0; kernel 1: w_i = d2_i < delta2 ? 1.0 - d2_i / delta2 : 0.0; r_i = sqrt(w_i).
+ *   n_kept     : the rows with w_i > 0.
+ *   sum_w, ess : sum_w = S(w_i), S the chunked pairwise sum of the pooled column (chunks of 8192 counted from the group's first row);
+ *                sum_w2 = S(w_i * w_i); ess = (sum_w * sum_w) / sum_w2.
+ *   joint columns: D = nm + np; column c < nm is x_.c, column nm + j is theta_.j.
+ *   means      : mu_c = S(w_i * v_ic) / sum_w; x_mean the first nm of them, raw_mean the rest.
+ *   e_ic       = r_i * (v_ic - mu_c) over all m rows (a row with w = 0 contributes zeros).
+ *   pair sums  : C_ab = S(e_ia * e_ib): smm_get_chain_cov's pair sums over chunks of 8192, the chunks' sums added in order from 0.0 as
+ *                smm_get_moment_stats adds them; mirrored entries hold the same value.
+ *   factor     : A = C_xx (a, b < nm) with A_kk = C_kk + ridge * C_kk; its lower Cholesky factor in smm_get_moment_stats' order.
+ *   beta       : column j = solve(L, b) of smm_get_moment_stats with b_k = C_{k, nm + j}; stored [nm][np].
+ *   adj_mean_j = mu_{nm + j} - t, t = 0.0, t = t + mu_k * beta_kj over k ascending (the data sit at x = 0).
+ *   adj_sd_j   = sqrt((C_{nm + j, nm + j} - u) / sum_w), u = 0.0, u = u + beta_kj * C_{k, nm + j} over k ascending; a negative radicand
+ *                gives NaN as IEEE sqrt does.
+ *   adjusted draw: for the rows with w_i > 0, theta*_ij = theta_ij - t, t = 0.0, t = t + x_ik * beta_kj over k ascending.
+ *   n_outside_j: the kept rows with theta*_ij < lb_j or theta*_ij > ub_j (nothing is clamped).
+ *   adj_quantile: integer weights, so that no sum depends on an order: q_i = (int64) ceil(w_i * 1048576.0), exact and at least 1 for a
+ *                kept row; Q = the sum of them (below 2^51 with fewer than 2^31 rows, so (double) Q is exact); for prob p, target =
+ *                max(1, (int64) ceil(p * (double) Q)); the quantile is the smallest v among the kept theta*_.j for which the q of the
+ *                rows with theta* <= v add up to at least target: the inverted weighted CDF, without interpolation.  Doubles are
+ *                ordered by smm_get_chain_stats' sort keys, so the result is defined up to the sign of a zero, as there.
+ *   status     : the first that applies: 1 m < 2; 2 a non-finite value among the selected parameters or moments (1, 2: everything but
+ *                count and n_chains NaN, the integers 0); 3 kernel 1 with !(delta2 > 0), or n_kept < nm + 2; 4 a pivot of the factor
+ *                of A is not > 0 (3, 4: bandwidth, n_kept, sum_w, ess, x_mean and raw_mean keep the values defined above, beta and
+ *                adj_* are NaN, n_outside 0); 0 otherwise.  An empty window or a group without rows: status 1. */
+typedef struct {             /* caller-allocated; any pointer may be NULL = not computed; G = n_groups                          */
+    int64_t* count;          /* [G]              selected rows pooled in the group                                               */
+    int32_t* n_chains;       /* [G]              member chains                                                                   */
+    int32_t* status;         /* [G]              0 ok, 1 fewer than 2 rows, 2 non-finite value, 3 nothing to regress on, 4 not PD */
+    int64_t* n_kept;         /* [G]              rows with weight > 0                                                            */
+    double*  bandwidth;      /* [G]              delta2: the squared distance at which the weight reaches 0                      */
+    double*  sum_w;          /* [G]                                                                                              */
+    double*  ess;            /* [G]              sum_w^2 / sum of w^2 (Kish)                                                     */
+    double*  x_mean;         /* [G][nm]          weighted mean discrepancy of the kept draws                                     */
+    double*  raw_mean;       /* [G][np]          weighted parameter mean: the unadjusted (rejection) estimate                    */
+    double*  beta;           /* [G][nm][np]      regression of the parameters on the discrepancy                                 */
+    double*  adj_mean;       /* [G][np]          the intercept: E[theta | s = s_obs]                                             */
+    double*  adj_sd;         /* [G][np]          weighted residual standard deviation                                            */
+    double*  adj_quantile;   /* [n_probs][G][np] weighted quantiles of the adjusted draws                                        */
+    int64_t* n_outside;      /* [G][np]          kept rows whose adjusted value leaves [lb, ub] (nothing is clamped)             */
+} smm_adjustment_t;
+int  smm_get_adjustment(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group /* [N] or NULL */, int32_t n_groups,
+                        double tol, int32_t kernel, const double* scale /* [nm] or NULL */, double ridge, const double* probs,
+                        int32_t n_probs, smm_adjustment_t* out);
+
 /* The objective and the simulated moments binned along parameters, computed on the device from the history it holds: for each group of
  * chains and each parameter, over smm_get_histogram's bins of that parameter, the profile of the objective (the smallest value among the
  * rows of the bin and the row that attains it, with its full parameter vector: the lower envelope a slice plot draws, over everywhere the

@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_profile, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_adjustment, hip_profile, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_set_population!, hip_scatter_population!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
@@ -134,6 +134,23 @@ struct SmmDraws
     chain::Ptr{Int32}
     iter::Ptr{Int32}
     src_iter::Ptr{Int32}
+end
+
+struct SmmAdjustment
+    count::Ptr{Int64}
+    n_chains::Ptr{Int32}
+    status::Ptr{Int32}
+    n_kept::Ptr{Int64}
+    bandwidth::Ptr{Cdouble}
+    sum_w::Ptr{Cdouble}
+    ess::Ptr{Cdouble}
+    x_mean::Ptr{Cdouble}
+    raw_mean::Ptr{Cdouble}
+    beta::Ptr{Cdouble}
+    adj_mean::Ptr{Cdouble}
+    adj_sd::Ptr{Cdouble}
+    adj_quantile::Ptr{Cdouble}
+    n_outside::Ptr{Int64}
 end
 
 struct SmmMomentStats
@@ -750,6 +767,53 @@ function hip_moment_stats(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = 
     end
     return (count = count, n_chains = nch, status = st, p_mean = pmean, m_mean = mmean, m_median = mmed, m_quantile = mq, cov_pp = cpp,
             cov_pm = cpm, cov_mm = cmm, fit_z = z, jac = jac, sens = sens, se = se)
+end
+
+const ADJUST_KERNEL = Dict(:uniform => 0, :epanechnikov => 1)
+
+"""
+    hip_adjustment(h, t0, t1; select = :state, groups = nothing, tol = 0.2, kernel = :epanechnikov, scale = nothing, ridge = 0.0,
+                   probs = Float64[]) -> NamedTuple
+
+The regression-adjusted posterior of groups of chains over iterations `t0+1 .. t1`, on the device (`smm_get_adjustment`) without
+downloading the history: the local-linear adjustment of Beaumont, Zhang & Balding (2002).  The fraction `tol` of a group's pooled rows
+whose simulated moments lie nearest the data moments is kept and weighted by `kernel` (`:uniform` or `:epanechnikov`), the parameters
+are regressed on the moment discrepancy `(s - mom) / scale` (`scale = nothing`: the moments' weights), and every kept draw is moved to
+zero discrepancy.  `select`: `:all`, `:accepted` or `:state`.  `groups[chain]` holds 0-based group ids (-1 = none); `nothing`: every
+chain in one group.  Returns `count[g]`, `n_chains[g]`, `status[g]` (0 ok, 1 fewer than 2 rows, 2 a non-finite value, 3 nothing to
+regress on, 4 the moments' weighted covariance not positive definite), `n_kept[g]`, `bandwidth[g]`, `sum_w[g]`, `ess[g]`,
+`x_mean[m, g]`, `raw_mean[k, g]`, `beta[k, m, g]`, `adj_mean[k, g]`, `adj_sd[k, g]`, `adj_quantile[k, g, p]` and `n_outside[k, g]`
+(the header's row-major arrays).
+"""
+function hip_adjustment(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :state,
+                        groups::Union{Nothing,AbstractVector{<:Integer}} = nothing, tol::Real = 0.2, kernel::Symbol = :epanechnikov,
+                        scale::Union{Nothing,AbstractVector{<:Real}} = nothing, ridge::Real = 0.0,
+                        probs::AbstractVector{<:Real} = Float64[])
+    N, np, nm = h.N, h.np, h.nm
+    g = groups === nothing ? Int32[] : Vector{Int32}(groups)
+    groups === nothing || length(g) == N || throw(ArgumentError("groups needs one entry per chain"))
+    ng = groups === nothing ? 1 : (isempty(g) ? 0 : Int(maximum(g)) + 1)
+    sc = scale === nothing ? Float64[] : Vector{Float64}(scale)
+    scale === nothing || length(sc) == nm || throw(ArgumentError("scale needs one entry per moment"))
+    p = Vector{Float64}(probs); nq = length(p)
+    count = Vector{Int64}(undef, ng); nch = Vector{Int32}(undef, ng); st = Vector{Int32}(undef, ng); kept = Vector{Int64}(undef, ng)
+    bw = Vector{Float64}(undef, ng); sw = Vector{Float64}(undef, ng); ess = Vector{Float64}(undef, ng)
+    xmean = Matrix{Float64}(undef, nm, ng); rmean = Matrix{Float64}(undef, np, ng); beta = Array{Float64}(undef, np, nm, ng)
+    amean = Matrix{Float64}(undef, np, ng); asd = Matrix{Float64}(undef, np, ng); aq = Array{Float64}(undef, np, ng, nq)
+    nout = Matrix{Int64}(undef, np, ng)
+    GC.@preserve g sc p count nch st kept bw sw ess xmean rmean beta amean asd aq nout begin
+        ad = SmmAdjustment(pointer(count), pointer(nch), pointer(st), pointer(kept), pointer(bw), pointer(sw), pointer(ess), pointer(xmean),
+                           pointer(rmean), pointer(beta), pointer(amean), pointer(asd), nq > 0 ? pointer(aq) : Ptr{Cdouble}(C_NULL),
+                           pointer(nout))
+        check(h.ctx, ccall(sym(:smm_get_adjustment), Cint,
+                           (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Int32}, Cint, Cdouble, Cint, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Cint,
+                            Ref{SmmAdjustment}),
+                           h.ctx, t0, t1, HIST_SELECT[select], groups === nothing ? Ptr{Int32}(C_NULL) : pointer(g), ng, Float64(tol),
+                           ADJUST_KERNEL[kernel], scale === nothing ? Ptr{Cdouble}(C_NULL) : pointer(sc), Float64(ridge),
+                           nq > 0 ? pointer(p) : Ptr{Cdouble}(C_NULL), nq, ad))
+    end
+    return (count = count, n_chains = nch, status = st, n_kept = kept, bandwidth = bw, sum_w = sw, ess = ess, x_mean = xmean,
+            raw_mean = rmean, beta = beta, adj_mean = amean, adj_sd = asd, adj_quantile = aq, n_outside = nout)
 end
 
 # the factor(s) between the header's row-major [np][np] / [N][np][np] and Julia's L[k, j] / L[k, j, c]

@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, profile_objective, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, profile_objective, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -512,6 +512,37 @@ and no finite-difference step, unlike `get_stdErrors`.
 function sensitivity(algo::MAlgoBGPHip; window = nothing, select::Symbol = :state, groups = nothing, ridge::Real = 0.0)
     r = moment_stats(algo, window, select, groups, Float64[], ridge)
     return (count = r.count, n_chains = r.n_chains, status = r.status, jac = r.jac, sens = r.sens, se = r.se)
+end
+
+"""
+    regression_adjust(algo; window = nothing, select = :state, groups = nothing, tol = 0.2, kernel = :epanechnikov, scale = nothing,
+                      ridge = 0.0, level = 0.95) -> NamedTuple
+
+The posterior at zero tolerance, on the device (`SMMHip.hip_adjustment`): the local-linear regression adjustment of Beaumont, Zhang &
+Balding (2002) over each group's pooled draws.  `raw_mean[k, g]` is the weighted (rejection) estimate, `adj_mean[k, g]` and
+`adj_sd[k, g]` the adjusted one, `band[k, g, 1:2]` the weighted quantiles of the adjusted draws at `level`, with `n_kept[g]`,
+`ess[g]`, `n_outside[k, g]` (adjusted draws that leave the parameter's bounds; nothing is clamped) and `status[g]`.  `scale = :sd`
+scales the discrepancy by the moments' pooled standard deviations (`sqrt(diag cov_mm)` of `SMMHip.hip_moment_stats`, which must be
+the same for every group: pass one group, or a vector).  Not a method of `SMM`: the reference has no such function.
+"""
+function regression_adjust(algo::MAlgoBGPHip; window = nothing, select::Symbol = :state, groups = nothing, tol::Real = 0.2,
+                           kernel::Symbol = :epanechnikov, scale = nothing, ridge::Real = 0.0, level::Real = 0.95)
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    t0, t1 = window === nothing ? (0, SMMHip.hip_iter(hip)) : window
+    if groups === nothing
+        ids = Dict{Float64,Int32}()
+        opts = getfield(algo, :opts)
+        groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
+    end
+    if scale === :sd
+        ms = SMMHip.hip_moment_stats(hip, t0, t1; select = select, groups = zeros(Int32, length(groups)))
+        scale = [sqrt(ms.cov_mm[k, k, 1]) for k in 1:size(ms.cov_mm, 1)]
+    end
+    r = SMMHip.hip_adjustment(hip, t0, t1; select = select, groups = groups, tol = tol, kernel = kernel, scale = scale, ridge = ridge,
+                              probs = [(1 - level) / 2, 1 - (1 - level) / 2])
+    return (count = r.count, n_chains = r.n_chains, status = r.status, n_kept = r.n_kept, ess = r.ess, raw_mean = r.raw_mean,
+            adj_mean = r.adj_mean, adj_sd = r.adj_sd, band = r.adj_quantile, n_outside = r.n_outside)
 end
 
 """

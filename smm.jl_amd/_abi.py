@@ -152,6 +152,15 @@ class smm_moment_stats_t(C.Structure):
     ]
 
 
+class smm_adjustment_t(C.Structure):
+    _fields_ = [
+        ("count", C.POINTER(C.c_int64)), ("n_chains", c_int32_p), ("status", c_int32_p), ("n_kept", C.POINTER(C.c_int64)),
+        ("bandwidth", c_double_p), ("sum_w", c_double_p), ("ess", c_double_p), ("x_mean", c_double_p), ("raw_mean", c_double_p),
+        ("beta", c_double_p), ("adj_mean", c_double_p), ("adj_sd", c_double_p), ("adj_quantile", c_double_p),
+        ("n_outside", C.POINTER(C.c_int64)),
+    ]
+
+
 class smm_profile_t(C.Structure):
     _fields_ = [
         ("count", C.POINTER(C.c_int64)), ("status", c_int32_p), ("edges", c_double_p), ("n", C.POINTER(C.c_int64)),
@@ -224,6 +233,8 @@ SYMBOLS = [
                                 C.POINTER(smm_draws_t)]),
     ("smm_get_moment_stats", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_double_p, C.c_int32, C.c_double,
                                        C.POINTER(smm_moment_stats_t)]),
+    ("smm_get_adjustment", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_double, C.c_int32, c_double_p,
+                                     C.c_double, c_double_p, C.c_int32, C.POINTER(smm_adjustment_t)]),
     ("smm_get_profile", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32, c_double_p, c_int32_p,
                                    C.c_int32, C.c_int32, C.POINTER(smm_profile_t)]),
     ("smm_get_chain_cov", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),

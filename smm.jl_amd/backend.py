@@ -450,6 +450,36 @@ class BGPContext:
                                                  float(ridge), C.byref(s)))
         return r
 
+    ADJUST_KERNELS = {"uniform": 0, "epanechnikov": 1}
+
+    def adjustment(self, t0=0, t1=None, select="state", groups=None, tol=0.2, kernel="epanechnikov", scale=None, ridge=0.0, probs=(),
+                   n_groups=None):
+        """the regression-adjusted posterior of groups of local chains over iterations [t0, t1), on the device (smm_get_adjustment,
+        include/smmhip.h: Beaumont, Zhang & Balding's local-linear adjustment): a dict of numpy arrays count / n_chains / status /
+        n_kept / bandwidth / sum_w / ess [n_groups], x_mean [n_groups][nm], raw_mean / adj_mean / adj_sd / n_outside [n_groups][np],
+        beta [n_groups][nm][np], adj_quantile [len(probs)][n_groups][np].  select and groups as in moment_stats; tol: the fraction of a
+        group's rows kept; kernel: 0 / "uniform" or 1 / "epanechnikov"; scale: None (the moments' weights) or nm positive values;
+        ridge: the relative ridge on the diagonal of the discrepancies' weighted pair sums before they are factored"""
+        t1 = self._t1(t1)
+        p = A.f64(probs).reshape(-1)
+        np_, nm = self.np, self.nm
+        sel = self._select(select)
+        kern = self.ADJUST_KERNELS[kernel] if isinstance(kernel, str) else int(kernel)
+        sc = None if scale is None else A.f64(scale).reshape(-1)
+        if sc is not None and len(sc) != nm:
+            raise ValueError("adjustment: scale needs one value per moment")
+        g, gp, ng = self._groups("adjustment", groups, n_groups)
+        G = max(ng, 0)
+        r = dict(count=np.empty(G, np.int64), n_chains=np.empty(G, np.int32), status=np.empty(G, np.int32), n_kept=np.empty(G, np.int64),
+                 bandwidth=np.empty(G), sum_w=np.empty(G), ess=np.empty(G), x_mean=np.empty((G, nm)), raw_mean=np.empty((G, np_)),
+                 beta=np.empty((G, nm, np_)), adj_mean=np.empty((G, np_)), adj_sd=np.empty((G, np_)),
+                 adj_quantile=np.empty((len(p), G, np_)), n_outside=np.empty((G, np_), np.int64))
+        s = self._out(A.smm_adjustment_t, r, () if len(p) else ("adj_quantile",))
+        self._check(self._fn("get_adjustment")(self._ctx, int(t0), int(t1), sel, gp, ng, float(tol), kern,
+                                               A.dptr(sc) if sc is not None else None, float(ridge), A.dptr(p) if len(p) else None, len(p),
+                                               C.byref(s)))
+        return r
+
     def profile(self, t0=0, t1=None, select="accepted", groups=None, bins=20, range=None, pairs=(), bins2=None, n_groups=None,
                 moments=True):
         """the objective and the simulated moments binned along parameters over iterations [t0, t1), on the device (smm_get_profile,

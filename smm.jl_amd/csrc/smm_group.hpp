@@ -30,8 +30,8 @@ constexpr size_t GROUP_HIST_CAP = (size_t)32 << 20;   // bytes of global histogr
 // One workgroup per chain.  sel: 0 every row of the window, 1 the accepted rows, 2 row a(t) of every iteration (a row without one reads
 // NaN).  Columns [k0, k0 + kb) of the D pooled ones, which lie behind H_PARAMS in the record (the parameters, then the simulated moments).
 // counting != 0 (sel 0 / 1, kb = 0): count[c] = the chain's selected rows.  Otherwise count[c] is read: a chain outside every group, or
-// with no row in the chunks [cb0, cb0 + Nbc) of the chunked form (cch0 != NULL), reads nothing.  gbad (packed form; NULL: not tested):
-// gbad[g] = 1 for a value that is not finite.
+// with no row in the chunks [cb0, cb0 + Nbc) of the chunked form (cch0 != NULL), reads nothing.  gbad (NULL: not tested): gbad[g] = 1
+// for a value that is not finite among the columns written (the chunked form: of the rows of its chunks, before they are centred).
 __global__ __launch_bounds__(STATS_WG) void k_group_gather(const double* __restrict__ hrec, int N, int HW, int t0, int n, int sel,
                                                            const int* __restrict__ gid, const long long* __restrict__ off,
                                                            const int* __restrict__ cch0, int k0, int kb, long long Mtot, int cb0, int Nbc,
@@ -62,10 +62,13 @@ __global__ __launch_bounds__(STATS_WG) void k_group_gather(const double* __restr
             const long long ch = cch0[c] + pos / STATS_LDS_N - cb0;
             if (ch < 0 || ch >= Nbc) return;
             const size_t at = (size_t)ch * STATS_LDS_N + (size_t)(pos % STATS_LDS_N);
+            bool bad = false;
             for (int kk = 0; kk < kb; ++kk) {
                 const double v = h ? h[H_PARAMS + k0 + kk] : qnan;
+                if (gbad) bad |= !isfinite(v);
                 col[(size_t)kk * Nbc * STATS_LDS_N + at] = v - gmean[(size_t)g * D + k0 + kk];
             }
+            if (bad) gbad[g] = 1;
         }
     };
     if (sel == 2) {

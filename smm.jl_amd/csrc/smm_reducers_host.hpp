@@ -1,7 +1,8 @@
 // the host side of the history reducers — part of libsmmhip (included once by smmhip.hip, behind its host helpers; hiprtc never sees it).
 // The family: smm_get_chain_stats, smm_get_chain_cov, smm_get_proposal / _set_ / _adapt_, smm_get_chain_diag, smm_get_group_stats,
-// smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws, smm_get_moment_stats, smm_get_profile (kernels: smm_stats.hpp,
-// smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_moments.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp, smm_draws.hpp, smm_profile.hpp;
+// smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws, smm_get_moment_stats, smm_get_adjustment, smm_get_profile (kernels:
+// smm_stats.hpp, smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_moments.hpp, smm_adjust.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp,
+// smm_draws.hpp, smm_profile.hpp;
 // the walk over a chain's window that their gathers share: smm_window.hpp).
 // What they share is stated here once: the frame of a call (api_call of smmhip.hip), the checks of the arguments they have in common (check_groups,
 // check_probs, check_select), the prelude and the window behind them (settled_window: reader_prelude and check_window of smmhip.hip), the
@@ -253,6 +254,20 @@ struct PoolDev {
     }
 };
 
+// the six digits of a grid-wide radix select of nw columns at R ranks each, WB columns' histograms ghist [WB][R][GROUP_BINS] at a time:
+// hist(w0, wn, dg) counts digit dg of the columns [w0, w0 + wn) into them, k_group_pick finds each rank's digit (rem, pre [nw][R]) and
+// zeroes them again.  The counts are k_group_hist's (pool_order) or the integer weights of k_adjust_hist (smm_get_adjustment).
+template <class Hist>
+void radix_digits(Ctx* c, int nw, int R, int WB, unsigned long long* ghist, long long* rem, unsigned long long* pre, Hist hist) {
+    for (int w0 = 0; w0 < nw; w0 += WB) {
+        const int wn = std::min(WB, nw - w0);
+        for (int dg = 0; dg < 6; ++dg) {
+            hist(w0, wn, dg);
+            launch_checked(c, k_group_pick, dim3(wn * R), dim3(STATS_WG), 0, dg, w0 * R, ghist, rem, pre);
+        }
+    }
+}
+
 // median (omed NULL: none) and quantiles of the km packed columns col [km][Mtot], the result columns [ks, ks + km) of D: the short ones
 // by k_group_small; the long ones by the six digits of the radix select, WB columns' histograms at a time, then k_group_finish
 void pool_order(Ctx* c, void* d, const PoolDev& pd, const PoolPlan& pp, const OrderPlan& op, const double* col, int km, int ks, int D,
@@ -272,23 +287,19 @@ void pool_order(Ctx* c, void* d, const PoolDev& pd, const PoolPlan& pp, const Or
     up(c, d, pd.rem, remh);
     HIPCHK(hipMemsetAsync(pd.pre.in(d), 0, (size_t)nw * R * 8, c->stream));
     HIPCHK(hipMemsetAsync(pd.ghist.in(d), 0, (size_t)WB * R * GROUP_BINS * 8, c->stream));   // (k_group_pick zeroes it again)
-    for (int w0 = 0; w0 < nw; w0 += WB) {
-        const int wn = std::min(WB, nw - w0);
-        for (int dg = 0; dg < 6; ++dg) {
-            launch_checked(c, k_group_hist, dim3(wn, B, (R + GROUP_RB - 1) / GROUP_RB), dim3(STATS_WG), 0, col, pp.Mtot,
-                           (const int*)pd.wgrp.in(d), dG0, dgm, km, R, dg, w0, (const long long*)pd.rem.in(d),
-                           (const unsigned long long*)pd.pre.in(d), pd.ghist.in(d));
-            launch_checked(c, k_group_pick, dim3(wn * R), dim3(STATS_WG), 0, dg, w0 * R, pd.ghist.in(d), pd.rem.in(d), pd.pre.in(d));
-        }
-    }
+    radix_digits(c, nw, R, WB, pd.ghist.in(d), pd.rem.in(d), pd.pre.in(d), [&](int w0, int wn, int dg) {
+        launch_checked(c, k_group_hist, dim3(wn, B, (R + GROUP_RB - 1) / GROUP_RB), dim3(STATS_WG), 0, col, pp.Mtot,
+                       (const int*)pd.wgrp.in(d), dG0, dgm, km, R, dg, w0, (const long long*)pd.rem.in(d),
+                       (const unsigned long long*)pd.pre.in(d), pd.ghist.in(d));
+    });
     launch_checked(c, k_group_finish, dim3((nw + 63) / 64), dim3(64), 0, nw, (const int*)pd.wgrp.in(d), dgm, G, ks, km, D, R,
                    (const long long*)pd.rk.in(d), (const unsigned long long*)pd.pre.in(d), gnan, dprobs, nq, omed, quant);
 }
 
 // the reducers' dynamic LDS (smm_ctx_create): a chunk of draws (k_stats_column, k_cov_center, k_diag_acov, k_group_*, k_trace_column),
 // the partner ids of a pass (k_stats_mode), the counters and edges of a batch of parameters or pairs (k_hist_count, k_hist_pairs), a
-// split chain (k_rank_chain_mom, k_rank_acov), the three matrices of a group (k_moment_solve: 3 x 64 x 65 doubles), a chunk of a
-// segment (k_prof_chunk)
+// split chain (k_rank_chain_mom, k_rank_acov), the three matrices of a group (k_moment_solve: 3 x 64 x 65 doubles), the two of
+// k_adjust_solve, a chunk of a segment (k_prof_chunk)
 void reducer_kernel_attributes() {
     HIPCHK(hipFuncSetAttribute((const void*)k_stats_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_cov_center, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
@@ -302,6 +313,7 @@ void reducer_kernel_attributes() {
     HIPCHK(hipFuncSetAttribute((const void*)k_rank_chain_mom, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_rank_acov, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_moment_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * MAX_DIM * (MAX_DIM + 1) * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_adjust_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * MAX_DIM * (MAX_DIM + 1) * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_prof_chunk, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
 }
 
@@ -1178,6 +1190,166 @@ int smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, cons
         down(c, d, o_cpp, out->cov_pp, G * np * np); down(c, d, o_cpm, out->cov_pm, G * np * nm); down(c, d, o_cmm, out->cov_mm, G * nm * nm);
         down(c, d, o_z, out->fit_z, G * nm); down(c, d, o_jac, out->jac, G * nm * np); down(c, d, o_sens, out->sens, G * np * nm);
         down(c, d, o_se, out->se, G * np);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return SMM_OK;
+    });
+}
+
+// --- the regression-adjusted posterior of groups of chains (smm_adjust.hpp) ---------------------------------------------------------------
+
+int smm_get_adjustment(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups, double tol, int32_t kernel,
+                       const double* scale, double ridge, const double* probs, int32_t n_probs, smm_adjustment_t* out) {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        if (const int rc = check_select(c, select)) return rc;
+        if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
+        if (const int rc = check_probs(c, probs, n_probs, out->adj_quantile != nullptr)) return rc;
+        if (!(tol > 0.0 && tol <= 1.0)) return fail(c, SMM_ERR_INVALID_ARG, "tol must lie in (0, 1]");
+        if (kernel != 0 && kernel != 1) return fail(c, SMM_ERR_INVALID_ARG, "kernel must be 0 (uniform) or 1 (Epanechnikov)");
+        for (int k = 0; scale && k < c->P.nm; ++k)
+            if (!(std::isfinite(scale[k]) && scale[k] > 0.0)) return fail(c, SMM_ERR_INVALID_ARG, "a scale must be finite and > 0");
+        if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(c, SMM_ERR_INVALID_ARG, "ridge must be finite and >= 0");
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t N = P.N, np = P.np, nm = P.nm, D = np + nm, DC = D + 2, G = n_groups, nq = out->adj_quantile ? n_probs : 0;
+        const int n = t1 - t0;
+        const bool pass4 = nq > 0 || out->n_outside;
+        const bool cols = pass4 || out->status || out->n_kept || out->bandwidth || out->sum_w || out->ess || out->x_mean || out->raw_mean ||
+                          out->beta || out->adj_mean || out->adj_sd;
+        const Groups grp = group_members(group, G, N);
+        DevBuf<int> dci(2 * N);
+        const PoolPlan pp = pool_plan(grp, pool_counts(c, grp, t0, n, select, dci.p));
+        const long long Mtot = pp.Mtot;
+        const int NC = pp.NC;
+        if (out->count) std::copy(pp.gm.begin(), pp.gm.end(), out->count);
+        if (out->n_chains) std::copy(grp.n_chains.begin(), grp.n_chains.end(), out->n_chains);
+        if (!cols || G == 0) return SMM_OK;
+        if (Mtot == 0) {   // no row in any group: status 1, the doubles NaN, the integers 0
+            auto nan = [](double* p, size_t k) { if (p) std::fill(p, p + k, NAN); };
+            if (out->status) std::fill(out->status, out->status + G, 1);
+            if (out->n_kept) std::fill(out->n_kept, out->n_kept + G, 0);
+            if (out->n_outside) std::fill(out->n_outside, out->n_outside + G * np, 0);
+            nan(out->bandwidth, G); nan(out->sum_w, G); nan(out->ess, G); nan(out->x_mean, G * nm); nan(out->raw_mean, G * np);
+            nan(out->beta, G * nm * np); nan(out->adj_mean, G * np); nan(out->adj_sd, G * np); nan(out->adj_quantile, nq * G * np);
+            return SMM_OK;
+        }
+        const OrderPlan op = order_plan(c, pp, false, &tol, 1);   // the bandwidth: the quantile tol of the distance column
+        // the batch plan.  The scratch: one packed column (the distances, later the integer weights), Nbc chunks of the D + 2 columns
+        // (whose D x D pair sums stay under the result cap), and for the select jb packed columns of adjusted parameters
+        const size_t col8 = (size_t)Mtot * 8, chunk8 = DC * STATS_LDS_N * 8;
+        reducer_scratch(c, 2 * N * (size_t)P.T * 8 + chunk8);
+        const size_t hook = c->H.stats_scratch;
+        const size_t budget = hook ? std::min(c->st_scr_bytes, std::max(hook, 2 * col8 + chunk8)) : c->st_scr_bytes;
+        const size_t avail = budget - 2 * col8;   // (at least one chunk)
+        const int Nbc = (int)std::max<size_t>(1, std::min({(size_t)NC, avail / 2 / chunk8, reducer_batch_cap(c) / (D * D * 8)}));
+        const size_t jb = std::min(np, 1 + (avail - Nbc * chunk8) / col8);
+        std::vector<int> cgrp(NC);
+        for (size_t g = 0; g < G; ++g) std::fill(cgrp.begin() + pp.gch0[g], cgrp.begin() + pp.gch0[g + 1], (int)g);
+        std::vector<long long> lcst(Nbc);
+        for (int i = 0; i < Nbc; ++i) lcst[i] = (long long)i * STATS_LDS_N;
+        // the weighted select: every group's columns of a batch of parameters, R = nq targets each
+        const int R = (int)nq;
+        const size_t nwc = pass4 && R ? G * jb : 0;
+        const int WB = nwc ? (int)std::min(nwc, std::max((size_t)1, GROUP_HIST_CAP / ((size_t)R * GROUP_BINS * 8))) : 0;
+        Carve Rv;   // 8-byte slices first
+        const auto delta = Rv.take<double>(G), sums = Rv.take<double>(G * DC), mu = Rv.take<double>(G * D), zero = Rv.take<double>(G * D),
+                   acc = Rv.take<double>(G * D * D), csum = Rv.take<double>(DC * Nbc), csum2 = Rv.take<double>(D * D * (size_t)Nbc),
+                   betai = Rv.take<double>(G * nm * np), dscale = Rv.take<double>(scale ? nm : 0), dprobs = Rv.take<double>(nq);
+        const auto o_bw = Rv.take<double>(G), o_sw = Rv.take<double>(G), o_ess = Rv.take<double>(G), o_xm = Rv.take<double>(G * nm),
+                   o_rm = Rv.take<double>(G * np), o_beta = Rv.take<double>(G * nm * np), o_am = Rv.take<double>(G * np),
+                   o_sd = Rv.take<double>(G * np), o_q = Rv.take<double>(nq * G * np);
+        const auto o_kept = Rv.take<long long>(G), dlcst = Rv.take<long long>(Nbc), srem = Rv.take<long long>(nwc * R);
+        const auto nkept = Rv.take<unsigned long long>(G), qsum = Rv.take<unsigned long long>(G), nout = Rv.take<unsigned long long>(G * np),
+                   spre = Rv.take<unsigned long long>(nwc * R), sghist = Rv.take<unsigned long long>((size_t)WB * R * GROUP_BINS);
+        const PoolDev pd(Rv, pp, op, op.wgrp.size());
+        const auto cnan = Rv.take<int>(DC * Nbc), dcgrp = Rv.take<int>(NC), gbad = Rv.take<int>(G), st = Rv.take<int>(G);
+        void* d = reducer_result(c, Rv.bytes);
+        pd.upload(c, d, pp, op);
+        up(c, d, dscale, scale, scale ? nm : 0); up(c, d, dprobs, probs, nq); up(c, d, dlcst, lcst); up(c, d, dcgrp, cgrp);
+        auto clear = [&](auto sl, size_t count) { HIPCHK(hipMemsetAsync(sl.in(d), 0, count * sizeof(*sl.in(d)), c->stream)); };
+        clear(sums, G * DC); clear(zero, G * D); clear(acc, G * D * D);   // (the running sums from 0.0; the gather's mean of zeros)
+        clear(nkept, G); clear(qsum, G); clear(nout, G * np); clear(gbad, G);
+        const int *dgid = dci.p, *dgch0 = pd.gch0.in(d), *dclen = pd.clen.in(d);
+        int* dcnt = dci.p + N;
+        const long long *dgm = pd.gm.in(d), *dG0 = pd.G0.in(d);
+        double* d2col = (double*)c->st_scr;                       // [Mtot]; the select's integer weights once the bandwidth is known
+        long long* qcol = (long long*)c->st_scr;
+        double* buf = d2col + Mtot;                               // [DC][Nbc][STATS_LDS_N]
+        double* ts = buf + (size_t)DC * Nbc * STATS_LDS_N;        // [jb][Mtot]
+        // the chunks [cb0, cb0 + nb) as k_group_gather's chunked form gathers them, centred by zeros: body(rows); flag: the groups'
+        // not-finite flags of the first sweep (NULL: not tested again)
+        auto chunk_batches = [&](int* flag, auto body) {
+            for (int cb0 = 0; cb0 < NC; cb0 += Nbc) {
+                const int nb = std::min(Nbc, NC - cb0);
+                launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, dgid,
+                               (const long long*)pd.off.in(d) + N, (const int*)pd.cch0.in(d), 0, (int)D, Mtot, cb0, nb, (const double*)zero.in(d),
+                               (int)D, buf, dcnt, 0, flag);
+                body(AdjRows{buf, nb, cb0, (int)np, (int)nm, dclen, (const int*)dcgrp.in(d), (const long long*)pd.cst.in(d), (const double*)P.mom,
+                             (const double*)P.w, scale ? (const double*)dscale.in(d) : (const double*)nullptr, (const double*)delta.in(d),
+                             (int)kernel});
+            }
+        };
+        auto rows = [&](const AdjRows& a, int mode) {
+            launch_checked(c, k_adjust_rows, dim3(STATS_LDS_N / ADJ_WG, a.nb), dim3(ADJ_WG), 0, a, mode, d2col,
+                           (const double*)mu.in(d), nkept.in(d), qsum.in(d));
+        };
+        chunk_batches(gbad.in(d), [&](const AdjRows& a) { rows(a, 0); });
+        pool_order(c, d, pd, pp, op, d2col, 1, 0, 1, gbad.in(d), nullptr, delta.in(d));
+        chunk_batches(nullptr, [&](const AdjRows& a) {   // the weights; the sums of w v, w and w w
+            rows(a, 1);
+            launch_checked(c, k_group_chunk_sum, dim3(a.nb, DC), dim3(STATS_WG), (size_t)STATS_LDS_N * 8, (const double*)buf,
+                           (long long)a.nb * STATS_LDS_N, (const long long*)dlcst.in(d), dclen + a.cb0, a.nb, csum.in(d), cnan.in(d));
+            launch_checked(c, k_adjust_sum_acc, dim3((unsigned)((G * DC + 255) / 256)), dim3(256), 0, (const double*)csum.in(d), a.nb, a.cb0,
+                           dgch0, (int)G, (int)DC, sums.in(d));
+        });
+        launch_checked(c, k_adjust_means, dim3((unsigned)((G * D + 255) / 256)), dim3(256), 0, (const double*)sums.in(d), (int)G, (int)D,
+                       mu.in(d));
+        const int nt = ((int)D + COV_T - 1) / COV_T, ntiles = nt * (nt + 1) / 2;
+        chunk_batches(nullptr, [&](const AdjRows& a) {   // the centred, weighted columns; their pair sums
+            rows(a, 2);
+            launch_checked(c, k_cov_pairs, dim3(a.nb, ntiles), dim3(COV_WG), 0, (const double*)buf, STATS_LDS_N, a.nb, 0, a.nb, (int)D,
+                           dclen + a.cb0, csum2.in(d), 1);
+            launch_checked(c, k_moment_cov_acc, dim3((unsigned)((G * D * (D + 1) / 2 + 255) / 256)), dim3(256), 0, (const double*)csum2.in(d),
+                           a.nb, a.cb0, dgch0, (int)G, (int)D, acc.in(d));
+        });
+        auto want = [&](const void* p, auto sl) { return p ? sl.in(d) : nullptr; };
+        const AdjustOut ao{want(out->n_kept, o_kept), want(out->bandwidth, o_bw), want(out->sum_w, o_sw), want(out->ess, o_ess),
+                           want(out->x_mean, o_xm), want(out->raw_mean, o_rm), want(out->beta, o_beta), want(out->adj_mean, o_am),
+                           want(out->adj_sd, o_sd)};
+        launch_checked(c, k_adjust_solve, dim3((unsigned)G), dim3(MOMENT_WG), (nm + np) * (nm + 1) * 8, (const double*)acc.in(d),
+                       (const double*)sums.in(d), (const double*)mu.in(d), (const double*)delta.in(d), dgm, (const int*)gbad.in(d),
+                       (const unsigned long long*)nkept.in(d), (int)np, (int)nm, (int)kernel, ridge, st.in(d), betai.in(d), ao);
+        if (pass4) {   // batches of parameters: the adjusted columns of every group, then their weighted quantiles
+            long long wmax = 0;
+            for (size_t g = 0; g < G; ++g) wmax = std::max(wmax, pp.gm[g]);
+            // a workgroup of a column counts blocks of per = STATS_WG x 16 consecutive rows (the seam SMMHIP_GROUP_WIDE_MIN: as few as
+            // one row, so that the weights of a short column are added across workgroups)
+            const long long per = std::min<long long>(STATS_WG * 16, std::max<long long>(1, c->H.group_wide_min - 1));
+            const int B = (int)std::min<long long>(1024, std::max<long long>(1, (wmax + per - 1) / per));
+            for (size_t j0 = 0; j0 < np; j0 += jb) {
+                const int jbb = (int)std::min(jb, np - j0);
+                chunk_batches(nullptr, [&](const AdjRows& a) {
+                    launch_checked(c, k_adjust_apply, dim3(STATS_LDS_N / ADJ_WG, a.nb), dim3(ADJ_WG), nm * jbb * 8 + (size_t)jbb * 4, a, (int)j0,
+                                   jbb, Mtot, (const int*)st.in(d), (const double*)betai.in(d), (const double*)P.lb, (const double*)P.ub, ts,
+                                   qcol, nout.in(d));
+                });
+                if (!R) continue;
+                const int nw = (int)G * jbb;
+                launch_checked(c, k_adjust_targets, dim3((unsigned)((nw * R + 255) / 256)), dim3(256), 0, (const unsigned long long*)qsum.in(d),
+                               (const int*)st.in(d), (const double*)dprobs.in(d), (int)G, jbb, R, srem.in(d), spre.in(d));
+                HIPCHK(hipMemsetAsync(sghist.in(d), 0, (size_t)WB * R * GROUP_BINS * 8, c->stream));   // (k_group_pick zeroes it again)
+                radix_digits(c, nw, R, WB, sghist.in(d), srem.in(d), spre.in(d), [&](int w0, int wn, int dg) {
+                    launch_checked(c, k_adjust_hist, dim3(wn, B, (R + ADJ_RB - 1) / ADJ_RB), dim3(STATS_WG), 0, (const double*)ts,
+                                   (const long long*)qcol, Mtot, dG0, dgm, jbb, R, dg, w0, per, (const long long*)srem.in(d),
+                                   (const unsigned long long*)spre.in(d), sghist.in(d));
+                });
+                launch_checked(c, k_adjust_finish, dim3((unsigned)((nw * R + 255) / 256)), dim3(256), 0, (const unsigned long long*)spre.in(d),
+                               (const int*)st.in(d), (int)G, (int)np, (int)j0, jbb, R, o_q.in(d));
+            }
+        }
+        down(c, d, st, out->status, G); down(c, d, o_kept, out->n_kept, G); down(c, d, o_bw, out->bandwidth, G);
+        down(c, d, o_sw, out->sum_w, G); down(c, d, o_ess, out->ess, G); down(c, d, o_xm, out->x_mean, G * nm);
+        down(c, d, o_rm, out->raw_mean, G * np); down(c, d, o_beta, out->beta, G * nm * np); down(c, d, o_am, out->adj_mean, G * np);
+        down(c, d, o_sd, out->adj_sd, G * np); down(c, d, o_q, out->adj_quantile, nq * G * np); down(c, d, nout, out->n_outside, G * np);
         HIPCHK(hipStreamSynchronize(c->stream));
         return SMM_OK;
     });

@@ -73,6 +73,7 @@ using namespace smm;
 #include "smm_diag.hpp"
 #include "smm_group.hpp"
 #include "smm_moments.hpp"
+#include "smm_adjust.hpp"
 #include "smm_hist.hpp"
 #include "smm_profile.hpp"
 #include "smm_trace.hpp"

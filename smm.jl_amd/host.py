@@ -766,6 +766,36 @@ def sensitivity(algo, groups=None, window=None, state=True, ridge=0.0, accepted_
             for j in _builtins_range(r["count"].shape[0])]
 
 
+def adjusted(algo, groups=None, window=None, state=True, tol=0.2, kernel="epanechnikov", scale=None, ridge=0.0, level=0.95,
+             accepted_only=True):
+    """the posterior at zero tolerance, from the device (include/smmhip.h: smm_get_adjustment) without downloading the history: the
+    local-linear regression adjustment of Beaumont, Zhang & Balding (2002) over each group's pooled draws.  One OrderedDict per group
+    with count, chains, status (0 ok; 1 too few rows; 2 a non-finite value; 3 nothing to regress on; 4 the discrepancies' weighted
+    covariance not positive definite), n_kept, ess and, keyed by ps2s_names, raw_mean (the weighted, unadjusted estimate), adj_mean,
+    adj_sd, band ([lo, hi]: the weighted quantiles of the adjusted draws at `level`) and n_outside (adjusted draws that leave the
+    parameter's bounds; nothing is clamped).  tol: the fraction of a group's rows kept, those whose simulated moments lie nearest the
+    data; kernel: "uniform" or "epanechnikov"; scale: None (the moments' weights), nm positive values, or "sd": the simulated moments'
+    standard deviations over every chain's rows of the window (sqrt(diag cov_mm) of smm_get_moment_stats, fetched first).  groups,
+    window and state as in moment_fit"""
+    t0, t1 = (0, algo.i) if window is None else (int(window[0]), int(window[1]))
+    g = np.asarray(_default_groups(algo) if groups is None else groups, np.int32)
+    sel = "state" if state else "accepted" if accepted_only else "all"
+    if isinstance(scale, str):
+        if scale != "sd":
+            raise ValueError("adjusted: scale is None, 'sd' or one value per moment")
+        scale = np.sqrt(np.diagonal(algo._ctx.moment_stats(t0, t1, sel, None, (), 0.0)["cov_mm"][0]))
+    q = ((1 - level) / 2, 1 - (1 - level) / 2)
+    r = algo._ctx.adjustment(t0, t1, sel, g, float(tol), kernel, scale, float(ridge), q)
+    ps = ps2s_names(algo.m)
+    per = lambda f, j, cast: OrderedDict((k, cast(r[f][j, i])) for i, k in enumerate(ps))
+    return [OrderedDict(count=int(r["count"][j]), chains=int(r["n_chains"][j]), status=int(r["status"][j]), n_kept=int(r["n_kept"][j]),
+                        ess=float(r["ess"][j]), raw_mean=per("raw_mean", j, float), adj_mean=per("adj_mean", j, float),
+                        adj_sd=per("adj_sd", j, float),
+                        band=OrderedDict((k, r["adj_quantile"][:, j, i].copy()) for i, k in enumerate(ps)),
+                        n_outside=per("n_outside", j, int))
+            for j in _builtins_range(r["count"].shape[0])]
+
+
 def summary(x):
     """summary(c::BGPChain) AlgoBGP.jl:197-206 / summary(m::MAlgoBGP) :541-550"""
     if isinstance(x, MAlgoBGP):
