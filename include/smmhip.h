@@ -793,7 +793,8 @@ int  smm_get_moment_stats(void* ctx, int32_t t0, int32_t t1, int32_t select, con
  *                kept row; Q = the sum of them (below 2^51 with fewer than 2^31 rows, so (double) Q is exact); for prob p, target =
  *                max(1, (int64) ceil(p * (double) Q)); the quantile is the smallest v among the kept theta*_.j for which the q of the
  *                rows with theta* <= v add up to at least target: the inverted weighted CDF, without interpolation.  Doubles are
- *                ordered by smm_get_chain_stats' sort keys, so the result is defined up to the sign of a zero, as there.
+ *                ordered by smm_get_chain_stats' sort keys, the IEEE total order (-0.0 before +0.0), and the result is one of the
+ *                kept theta*, never interpolated: a quantile that is a zero carries the sign of the row it is.
  *   status     : the first that applies: 1 m < 2; 2 a non-finite value among the selected parameters or moments (1, 2: everything but
  *                count and n_chains NaN, the integers 0); 3 kernel 1 with !(delta2 > 0), or n_kept < nm + 2; 4 a pivot of the factor
  *                of A is not > 0 (3, 4: bandwidth, n_kept, sum_w, ess, x_mean and raw_mean keep the values defined above, beta and

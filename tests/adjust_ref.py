@@ -3,7 +3,9 @@ regression adjustment of Beaumont, Zhang & Balding (2002) over the pooled rows o
 (joint_columns: every row, the accepted rows or the state series), the sums chain_cov_ref's chunked pairwise sums, the bandwidth
 chain_stats_ref's quantile of the distance column, the factor and the substitutions moment_stats_ref's; the weights, the centred
 columns, the adjusted draws and the weighted quantiles are stated here.  tests/test_adjustment.py holds it against np.linalg.lstsq, the
-exact identities and the status table; the GPU tests hold the device against it, over the history downloaded with smm_get_history."""
+exact identities and the status table; the GPU tests hold the device against it, over the history downloaded with smm_get_history.
+Its edges (bound counts, the weighted select's keys and weights, a tie run at the bandwidth, batch seams) are tested on adjust_craft.py's
+crafted histories: tests/test_adjustment_edges.py here, tests/test_gpu_adjustment_edges.py on the device, bit for bit."""
 import numpy as np
 
 import chain_cov_ref as V
