@@ -369,36 +369,16 @@ void init_state(Ctx* c, const smm_bgp_opts_t* opts) {
     HIPCHK(hipMemcpy(P.err, &e, 8, hipMemcpyHostToDevice));
 }
 
-// the dynamic LDS every kernel of this context may ask for beyond the default 64 KiB: one table {taken, function, bytes}, walked once
+// the dynamic LDS every kernel of this context may ask for beyond the default 64 KiB
 void lds_limits(Ctx* c) {
     const Forms& F = c->F;
-    const bool big = F.plan == PLAN_BIG, keys = F.xk == XK_ROWS || F.xk == XK_KEY, lds = F.plan == PLAN_LDS;
-    const size_t rows_all = resolve_rows_bytes(XKEY_MAX, XKEY_MAX, XROWS_MAX), rows_part = resolve_rows_bytes(XKEY_PARTNER_MAX, XKEY_PARTNER_MAX, XROWS_MAX);
-    const struct { bool on; const void* fn; size_t bytes; } limits[] = {
-        {big, (const void*)k_exch_plan_big, plan_big_lds_bytes(65535)},
-        {keys, (const void*)k_exch_resolve_key<false>, resolve_key_bytes(XKEY_MAX, XKEY_MAX)},
-        {keys, (const void*)k_exch_resolve_key<true>, resolve_key_bytes(XKEY_PARTNER_MAX, XKEY_PARTNER_MAX)},
-        {keys, (const void*)k_exch_resolve_rows<false>, rows_all},
-        {keys, (const void*)k_exch_resolve_rows<true>, rows_part},
-        {keys, (const void*)k_exch_resolve_rows<false, true>, rows_all},
-        {keys, (const void*)k_exch_resolve_rows<false, true, true>, (size_t)158 * 1024},
-        {keys, (const void*)k_exch_resolve_rows<true, true>, rows_part},
-#ifdef SMM_TEST_HOOKS
-        {lds, (const void*)k_exch_resolve_lds, resolve_lds_bytes(XLDS_MAX)},
-        {lds, (const void*)k_exch_resolve_lvl<256>, resolve_lvl_bytes(XLVL_MAX, XLVL_MAX)},
-        {lds, (const void*)k_exch_resolve_lvl<512>, resolve_lvl_bytes(XLVL_MAX, XLVL_MAX)},
-#endif
-        {lds, (const void*)k_exch_plan, std::max(plan_lds_bytes(XLDS_MAX, XLDS_MAX), plan_cone_bytes())},
-        {lds, (const void*)k_exch_resolve_lvl_soa<1024>, resolve_lvl_soa_bytes(XLDS_MAX, XLDS_MAX)},
-        {lds, (const void*)k_exch_resolve_lvl<1024>, resolve_lvl_bytes(XLVL_MAX, XLVL_MAX)},
-        {lds, (const void*)k_exch_resolve_lean, LDS_CU},
-        {F.cone_big, (const void*)k_cone_chains, cone_chains_lds_bytes(c->P.Ng)},
-        {true, (const void*)k_eval_batch<1, 8>, LDS_CU},
-        {true, (const void*)k_eval_batch<2, 16>, LDS_CU},
-        {true, (const void*)k_eval_batch<0, 8>, LDS_CU},
-    };
-    for (const auto& l : limits)
-        if (l.on) HIPCHK(hipFuncSetAttribute(l.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.bytes));
+    const bool on[] = {F.plan == PLAN_BIG, F.xk == XK_ROWS || F.xk == XK_KEY, F.plan == PLAN_LDS, F.cone_big};   // (by ExchGroup: the rows of exch_instance's table this context's forms include)
+    for (int id = 0; id < XI_COUNT; ++id) {
+        const ExchInstance I = exch_instance(id, c->P.Ng);
+        if (I.fn && I.cap && on[I.group]) HIPCHK(hipFuncSetAttribute(I.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)I.cap));
+    }
+    for (const void* fn : {(const void*)k_eval_batch<1, 8>, (const void*)k_eval_batch<2, 16>, (const void*)k_eval_batch<0, 8>})
+        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CU));
     // (every kernel chain_kernel / chain_kernel_p2p can pick: what chain_instance names)
     for (int family = 0; family < CF_COUNT; ++family)
         for (int np = 1; np <= 4; ++np)

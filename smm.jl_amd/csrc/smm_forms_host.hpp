@@ -40,9 +40,7 @@ size_t tile_smem(const Ctx* c, const Forms& F, int ct, int tpw = 1) {   // dynam
 }
 size_t cone_chains_lds_bytes(int Ng) { return (size_t)Ng * 4; }   // k_cone_chains: a word per chain
 size_t plan_lds_bytes(int Ng, int K) { return (size_t)(Ng + 2) * 4 + (size_t)K * 8 + (size_t)K * 4 + 128 + 16; }
-#ifdef SMM_TEST_HOOKS
-size_t resolve_lds_bytes(int Ng) { return (size_t)Ng * 16 + 16; }
-#endif
+size_t resolve_lds_bytes(int Ng) { return (size_t)Ng * 16 + 16; }   // (the ticket kernel: test build only)
 size_t resolve_lvl_soa_bytes(int Ng, int K) { return (size_t)Ng * 12 + (size_t)K * 4 + 16; }
 size_t resolve_lvl_bytes(int Ng, int K) { return (size_t)Ng * 16 + (size_t)K * 12 + 64 * 8 + 64; }
 size_t resolve_lean_bytes(int Ng, int K, bool wide) { return std::max(wide ? lean_wide_bytes(Ng, K) : lean_walk_bytes(Ng, K), resolve_lvl_soa_bytes(Ng, K)); }
@@ -209,7 +207,8 @@ Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
     return F;
 }
 
-ChainKernel chain_kernel(const Ctx* c, int flags); PersistKernel persist_kernel(const Ctx* c, const Forms& F);   // (the choosers: smmhip.hip, behind this file)
+// (the choosers and the exchange's table: smmhip.hip, behind this file)
+ChainKernel chain_kernel(const Ctx* c, int flags); PersistKernel persist_kernel(const Ctx* c, const Forms& F); ExchLaunch resolve_kernel(const Ctx* c, const KParams& P); ExchInstance exch_instance(int id, int Ng);
 // which forms this context was given at creation (one line; tests/test_gpu_forms.py pins the table)
 std::string describe_text(const Ctx* c) {
     const KParams& P = c->P;
@@ -218,11 +217,10 @@ std::string describe_text(const Ctx* c) {
     const bool walks = F.inline_walk || F.cone_big;
     ChainKernel chain = chain_kernel(c, walks ? F_WALK_INLINE : 0);
     if (walks && !strcmp(chain.name, "iter_norm")) chain = chain_kernel(c, 0);
-    static const char* xk[] = {"lean", "lvl", "lvl_soa", "tickets", "rows", "key", "lvl_big", "any"};
     const char* walk = F.cone_big ? "cone_local" : !F.inline_walk ? "standalone" : F.dense_keys ? "inline_keys_under_tile" : F.gen_keys ? (F.cone ? "inline_keys_cone" : "inline_keys")
                      : F.norm_fast ? ((P.lean_wide && !P.mi_pct) ? "inline_lean_wide" : (F.lean_plan && !P.mi_pct) ? "inline_lean" : "inline_slots") : F.gen_lean ? "inline_lean16" : "inline_slots";
     char b[160];
-    std::string s = std::string("chain=") + chain.name + " walk=" + walk + " exchange=" + xk[F.xk] + " persistent=" + persist_kernel(c, F).name +
+    std::string s = std::string("chain=") + chain.name + " walk=" + walk + " exchange=" + exch_instance(resolve_kernel(c, P).id, 0).name + " persistent=" + persist_kernel(c, F).name +
                     " plan=" + (F.plan == PLAN_BIG ? (F.plan_ahead ? "big_ahead" : "big") : F.plan == PLAN_LDS ? "lds" : "none") + " window=" + std::to_string(F.plan_cap);
     if (c->obj == SMM_OBJ_USER) s += " ct=" + std::to_string(chain.ct);   // (the three launches' tile width)
     // (only once a starting population has been installed: smm_set_population / smm_scatter_population)

@@ -139,7 +139,7 @@ void chain_batches(Ctx* c, size_t per_chain, Body body) {
 // a reducer kernel onto the context's stream, its launch checked
 template <class Kern, class... Args>
 void launch_checked(Ctx* c, Kern kern, dim3 grid, dim3 block, size_t smem, const Args&... args) {
-    launch(c, kern, grid, block, smem, args...);
+    hipLaunchKernelGGL(kern, grid, block, smem, c->stream, args...);
     HIPCHK(hipGetLastError());
 }
 

@@ -361,8 +361,7 @@ void enqueue_iterations(Ctx* c, int n_iters) {
         if (c->run.unresolved && c->F.defer_resolve && !c->F.inline_walk) resolve_now(c);
         ensure_windows(c, t);
         const int flags = (c->run.prev_open ? F_CLOSE_PREV : 0) | (c->run.pending ? F_HAS_PENDING : 0) | (c->run.unresolved ? F_WALK_INLINE : 0);
-        // (populations of the level walk: the chain kernel and the stand-alone resolution take the profiling events themselves)
-        const bool kscoped = c->profiling == 2 && c->F.plan == PLAN_LDS && c->P.Ng <= XLVL_MAX && !c->H.dataflow && c->H.lvl_wg == 1024;
+        const bool kscoped = c->profiling == 2 && resolve_stamped(c, false);   // (where the stand-alone resolution takes the profiling events itself, the chain kernel does too)
         if (c->profiling && !kscoped) HIPCHK(hipEventRecord(c->pev[4 * slot], c->stream));
         {
             const KernelEvents stamped(c, kscoped, 4 * slot);
@@ -536,8 +535,9 @@ void p2p_enqueue(Ctx* c, int n_iters) {
         } else {
             if (c->pending_ext) {   // exchangeMoves! of iteration t-1 (before its plan window can move on)
                 if (c->p2p_unwaited) launch_p2p_wait(c);
-                if (prof && c->F.xk == XK_LEAN) c->pev_exch[slot] = 1;
-                const KernelEvents stamped(c, prof && c->F.xk == XK_LEAN, 4 * slot + 2);
+                const bool xprof = prof && resolve_stamped(c, true);
+                if (xprof) c->pev_exch[slot] = 1;
+                const KernelEvents stamped(c, xprof, 4 * slot + 2);
                 launch_resolve_window(c, t - 1);
                 flags |= F_HAS_PENDING;
             }
@@ -674,8 +674,9 @@ int smm_bgp_sharded_step(void* ctx, const void* gathered_prev_dev, void* gathere
         const double* donors = nullptr;   // (null: the chains continue from the context's own records)
         if (c->rec_external) {
             if (c->pending_ext) {   // exchangeMoves! of iteration t-1 over the gathered records (before its plan window can move on)
-                if (prof && c->F.xk == XK_LEAN) c->pev_exch[it] = 1;
-                const KernelEvents stamped(c, prof && c->F.xk == XK_LEAN, 4 * it + 2);
+                const bool xprof = prof && resolve_stamped(c, true);
+                if (xprof) c->pev_exch[it] = 1;
+                const KernelEvents stamped(c, xprof, 4 * it + 2);
                 launch_resolve(c, t - 1, (const double*)gathered_prev_dev);
                 flags |= F_HAS_PENDING;
             }
@@ -902,8 +903,7 @@ int smm_bgp_exchange_dev(void* ctx, const void* gathered_dev) {
         if (exchange_active(c, c->run.iter)) {
             const KParams& P = c->P;
             launch_resolve(c, c->run.iter, (const double*)gathered_dev);
-            hipLaunchKernelGGL(k_exch_apply, dim3((P.N + 255) / 256), dim3(256), 0, c->stream, P, c->run.iter,
-                               (const double*)gathered_dev, c->rec[c->run.cur]);
+            launch_exch(c, XI_APPLY, dim3((P.N + 255) / 256), 0, c->stream, P, c->run.iter, (const double*)gathered_dev, c->rec[c->run.cur]);
         }
         HIPCHK(hipGetLastError());
         return SMM_OK;

@@ -451,23 +451,7 @@ Hooks read_hooks() {
     if (const char* v = SMM_HOOK("SMMHIP_POP_SCRATCH")) H.pop_scratch = (size_t)strtoull(v, nullptr, 10);
     return H;
 }
-// Which stand-alone kernel resolves exchangeMoves! (AlgoBGP.jl:647-716) — ONE decision, taken once per context (select_forms),
-// from the population, the thresholds and dist_fun:
-//
-//   N_global        min_improve                      dist_fun   kernel                       slots / where
-//   <= 8192 (~7400) one value >= 0 for all chains    -          k_exch_resolve_lean          8-byte keys (0) or 16-byte values (> 0), LDS
-//   <= 4096         anything else                    any        k_exch_resolve_lvl<1024>     16-byte slots, LDS
-//   <= 8192         anything else                    any        k_exch_resolve_lvl_soa       split slots, LDS
-//   <= 32768        0 for all chains                 -          k_exch_keys + _rows          4-byte slots (17-bit keys), rows of 1024 pairs, LDS
-//   <= 32768        anything else                    -          k_exch_keys + _key           4-byte slots (16-bit keys, intervals), LDS
-//   <= 65535        anything else / other dist_fun   any        k_exch_resolve_lvl_big       16-byte slots, global memory
-//   above, or K > N_global                           any        k_exch_resolve_any           barrier rounds, global atomics
-//
-// (the p2p form of a sharded run launches k_exch_resolve_rows itself where this table says _rows — launch_resolve_rows_window:
-//  <., true> reads the tagged slots of its window instead of a key pre-pass, <false, true, true> keeps the partners of the rank's
-//  own chains only; every other p2p population resolves from the window's plain values through this table.)
-// (single shards of objfunc_norm up to 4096 chains do not get here in steady state: their chain kernel walks inline.)  The test
-// build can force an entry (SMM_TEST_HOOKS: Hooks) and adds the ticket kernel k_exch_resolve_lds.
+// which stand-alone resolution of exchangeMoves! (AlgoBGP.jl:647-716) a context takes: decided once (select_forms); the kernels: exch_instance's table
 enum ExchKernel { XK_LEAN, XK_LVL, XK_LVL_SOA, XK_TICKETS, XK_ROWS, XK_KEY, XK_LVL_BIG, XK_ANY };
 // The forms a context runs, chosen once at creation from the problem, the device and the hooks (select_forms) and not changed after.
 enum PlanKind { PLAN_NONE, PLAN_LDS, PLAN_BIG };   // the look-ahead exchange plans: none (one chain), k_exch_plan, k_exch_plan_big
@@ -513,6 +497,13 @@ struct DeviceFacts { int n_cus = 256; int per_cu = -1; };
 // what a chooser hands a launcher (name: what smm_describe says; block: lanes of a workgroup; ct: chains per tile; tpw: tiles per workgroup)
 struct ChainKernel { const void* fn; const char* name; unsigned block; int ct, tpw; };
 struct PersistKernel { const void* fn; hipFunction_t mfn; dim3 grid, block; size_t smem; const char* name; };
+// a row of exch_instance's table (cap: the dynamic LDS limit raised at creation where the context's forms include the row's group, 0: the default
+// will do; stamped: takes the dispatch's own stamps in profiling mode 2), and a chooser's pick for one launch (the row, this launch's dynamic LDS)
+enum ExchId { XI_CONE_CHAINS, XI_CONE_TILES, XI_PLAN_BIG, XI_PLAN, XI_LEAN, XI_LVL_256, XI_LVL_512, XI_LVL, XI_LVL_SOA, XI_TICKETS, XI_KEYS, XI_ROWS_PLDS,
+              XI_ROWS, XI_KEY_PLDS, XI_KEY, XI_LVL_BIG, XI_ANY, XI_ROWS_WIN_OWN, XI_ROWS_WIN_PLDS, XI_ROWS_WIN, XI_APPLY, XI_COUNT };
+enum ExchGroup { XG_BIG, XG_KEYS, XG_LDS, XG_CONE_BIG };
+struct ExchInstance { const void* fn; unsigned block; size_t cap; ExchGroup group; const char* name; bool stamped; };
+struct ExchLaunch { int id; size_t smem; };
 // one set of the plan window's tables: the levels' pairs, thresholds and offsets, the rows of k_exch_resolve_rows, the tiles' cones
 struct LevelTables {
     uint32_t *lv_pairs = nullptr, *lv_off = nullptr, *lv_rows = nullptr, *lv_rowinfo = nullptr, *cone_ok = nullptr, *cone_hdr = nullptr, *cone_pairs = nullptr;
@@ -640,7 +631,7 @@ struct Ctx {
     // ---- profiling ----
     smm_timing_t timing{};
     bool pending_timing = false;
-    int profiling = 0;   // 1: event brackets around the kernels; 2: the kernels' own begin/end timestamps (launch)
+    int profiling = 0;   // 1: event brackets around the kernels; 2: the kernels' own begin/end timestamps (launch_fn)
     hipEvent_t kev0 = nullptr, kev1 = nullptr;   // mode 2: start/stop events of the next launch (set for that launch: KernelEvents, smm_run_host.hpp)
     std::vector<char> pev_exch;
     std::vector<hipEvent_t> pev;  // profiling events: 4 per iteration (the last two bracket nothing: the event overhead)
@@ -672,11 +663,11 @@ T* dupload(Ctx* c, const T* h, size_t n) {
     return d;
 }
 
-// a kernel onto the context's stream; in profiling mode 2 with the begin/end of this dispatch as the command processor stamps them
-template <class Kern, class... Args>
-void launch(Ctx* c, Kern kern, dim3 grid, dim3 block, size_t smem, const Args&... args) {
-    if (c->kev0) hipExtLaunchKernelGGL(kern, grid, block, smem, c->stream, c->kev0, c->kev1, 0, args...);
-    else hipLaunchKernelGGL(kern, grid, block, smem, c->stream, args...);
+// a kernel known by its address (the choosers' tables) onto a stream, the launch's result checked here; in profiling mode 2 (kev0 set: a KernelEvents
+// scope) a launch on the context's own stream that takes them (stamped) carries the begin/end of its dispatch as the command processor stamps them
+void launch_fn(Ctx* c, const void* fn, dim3 grid, dim3 block, size_t smem, hipStream_t st, void** args, bool stamped = true) {
+    if (stamped && c->kev0 && st == c->stream) HIPCHK(hipExtLaunchKernel(fn, grid, block, args, smem, st, c->kev0, c->kev1, 0));
+    else HIPCHK(hipLaunchKernel(fn, grid, block, args, smem, st));
 }
 
 bool is_sim(int obj) { return obj == SMM_OBJ_NORM || obj == SMM_OBJ_NORM_FAILBOX; }
@@ -696,11 +687,23 @@ namespace {
 int exchange_K(const Ctx* c) { return c->P.n_pairs_tab > 0 ? c->P.n_pairs_tab : n_exchange_pairs(c->P.Ng); }   // (an injected pair list: its length)
 bool exchange_active(const Ctx* c, int t) { return t >= c->exchange_from && c->P.Ng > 1; }  // AlgoBGP.jl:637
 
-void launch_cone_big(Ctx* c, const KParams& Pw, int W, const uint32_t* lv_pairs, const uint32_t* lv_off, hipStream_t st) {
-    hipLaunchKernelGGL(k_cone_chains, dim3(W), dim3(XWG), cone_chains_lds_bytes(Pw.Ng), st, Pw, lv_pairs, lv_off, c->cb_scratch);
-    hipLaunchKernelGGL(k_cone_tiles, dim3((unsigned)(((Pw.cone_tiles + CONEB_WAVES - 1) / CONEB_WAVES) * ((W + 7) & ~7))), dim3(64 * CONEB_WAVES), cone_tiles_lds_bytes(Pw.plan_K),
-                       st, Pw, W, (const uint32_t*)c->cb_scratch);
-    HIPCHK(hipGetLastError());
+ExchInstance exch_instance(int id, int Ng = 0);   // (the table stands behind the chain kernels': the kernels are emitted in the order in which they are named)
+// row `id` of that table onto stream st: every launch of the exchange family (args: exactly the kernel's parameter types — they travel as addresses)
+template <class... Args>
+void launch_exch(Ctx* c, int id, dim3 grid, size_t smem, hipStream_t st, const Args&... args) {
+    const ExchInstance I = exch_instance(id);
+    if (!I.fn) throw std::string("exchange kernel ") + I.name + " is not part of this build";
+    void* a[] = {(void*)&args...};
+    launch_fn(c, I.fn, grid, dim3(I.block), smem, st, a, I.stamped);
+}
+size_t plan_smem(int Ng, int K, bool cones) { return cones ? std::max(plan_lds_bytes(Ng, K), plan_cone_bytes()) : plan_lds_bytes(Ng, K); }   // k_exch_plan's dynamic LDS (cones: it lists the tiles' cones too)
+// the big plan of W iterations from t on into the tables L on stream st; cones: and the tiles' locally numbered cones, from the plan's scratch (pairs in list order, their levels)
+void launch_plan_big(Ctx* c, const KParams& P, int t, int W, const LevelTables& L, hipStream_t st, bool cones) {
+    launch_exch(c, XI_PLAN_BIG, dim3(W), plan_big_lds_bytes(P.Ng), st, P, t, c->big_scratch, L.lv_pairs, L.lv_mi, L.lv_off, L.lv_rows, L.lv_rowinfo);
+    if (!cones) return;
+    launch_exch(c, XI_CONE_CHAINS, dim3(W), cone_chains_lds_bytes(P.Ng), st, P, (const uint32_t*)L.lv_pairs, (const uint32_t*)L.lv_off, c->cb_scratch);
+    const unsigned blocks = ((P.cone_tiles + CONEB_WAVES - 1) / CONEB_WAVES) * ((W + 7) & ~7);
+    launch_exch(c, XI_CONE_TILES, dim3(blocks), cone_tiles_lds_bytes(P.plan_K), st, P, W, (const uint32_t*)c->cb_scratch);
 }
 // the plan window starting at iteration t into set k, on the plan stream (the kernels' scratch is theirs alone: one window at a time
 // there) — behind every launch enqueued on the main stream so far: the ones that read set k are all among them (k is not the active set)
@@ -711,8 +714,7 @@ void plan_window_into(Ctx* c, int k, int t) {
     HIPCHK(hipStreamWaitEvent(c->pstream, c->ev_free, 0));
     Pw.cone_ok = S.cone_ok; Pw.cone_hdr = S.cone_hdr; Pw.cone_pairs = S.cone_pairs; Pw.cone_gather = S.cone_gather;
     const int W = std::min(c->F.plan_cap, Pw.T - t + 1);
-    hipLaunchKernelGGL(k_exch_plan_big, dim3(W), dim3(XWG), plan_big_lds_bytes(Pw.Ng), c->pstream, Pw, t, c->big_scratch, S.lv_pairs, S.lv_mi, S.lv_off, S.lv_rows, S.lv_rowinfo);
-    launch_cone_big(c, Pw, W, S.lv_pairs, S.lv_off, c->pstream);
+    launch_plan_big(c, Pw, t, W, S, c->pstream, true);
     HIPCHK(hipMemcpyAsync(S.ok_host, S.cone_ok, (size_t)W * 4, hipMemcpyDeviceToHost, c->pstream));
     HIPCHK(hipEventRecord(S.done, c->pstream));
     S.t0 = t; S.w = W;
@@ -762,27 +764,23 @@ void ensure_windows(Ctx* c, int t, bool rng = true) {
     }
     if (c->F.plan == PLAN_BIG && !c->F.plan_ahead && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
         const int W = std::min(c->F.plan_cap, P.T - t + 1);
-        hipLaunchKernelGGL(k_exch_plan_big, dim3(W), dim3(XWG), plan_big_lds_bytes(P.Ng), c->stream, P, t, c->big_scratch, c->win.lv_pairs, c->win.lv_mi,
-                           c->win.lv_off, c->win.lv_rows, c->win.lv_rowinfo);
+        launch_plan_big(c, P, t, W, c->win, c->stream, c->F.cone_big || c->F.persist_sh_big);
         c->plan_t0 = t; c->plan_w = W;
         P.plan_t0 = t;
-        if (c->F.cone_big) {   // the tiles' locally numbered cones, from the plan's scratch (pairs in list order, their levels)
-            launch_cone_big(c, P, W, c->win.lv_pairs, c->win.lv_off, c->stream);
+        if (c->F.cone_big) {   // (the persistent kernel of a shard looks at the window's flags itself: no synchronisation)
             // a cone that does not fit its caps (a pair list of very deep dependency chains: the user's, or an unlucky sample) sends its
             // iteration to the stand-alone resolution: the host looks at the window's flags once (one synchronisation per window)
             c->cone_big_ok.resize((size_t)W);
             HIPCHK(hipMemcpyAsync(c->cone_big_ok.data(), P.cone_ok, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
-        } else if (c->F.persist_sh_big) {   // (the persistent kernel looks at the window's flags itself: no synchronisation)
-            launch_cone_big(c, P, W, c->win.lv_pairs, c->win.lv_off, c->stream);
         }
         P.lv_rows = c->win.lv_rows; P.lv_rowinfo = c->win.lv_rowinfo;
         P.lv_pairs = c->win.lv_pairs; P.lv_mi = c->win.lv_mi; P.lv_off = c->win.lv_off;
     }
     if (c->F.plan == PLAN_LDS && P.Ng > 1 && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
         const int W = std::min(c->F.plan_cap, P.T - t + 1);
-        hipLaunchKernelGGL(k_exch_plan, dim3(W), dim3(XWG), (c->F.cone || c->F.persist != PERSIST_NONE) ? std::max(plan_lds_bytes(P.Ng, P.plan_K), plan_cone_bytes()) : plan_lds_bytes(P.Ng, P.plan_K), c->stream, P, t, c->win_plan,
-                           c->win_plan_mi, c->win.lv_pairs, c->win.lv_mi, c->win.lv_off, c->win_lv_pairs_p, c->win_lv_offp);
+        launch_exch(c, XI_PLAN, dim3(W), plan_smem(P.Ng, P.plan_K, c->F.cone || c->F.persist != PERSIST_NONE), c->stream, P, t, c->win_plan, c->win_plan_mi,
+                    c->win.lv_pairs, c->win.lv_mi, c->win.lv_off, c->win_lv_pairs_p, c->win_lv_offp);
         c->plan_t0 = t; c->plan_w = W;
         P.plan = c->win_plan; P.plan_mi = c->win_plan_mi; P.plan_t0 = t;
         P.lv_pairs = c->win.lv_pairs; P.lv_mi = c->win.lv_mi; P.lv_off = c->win.lv_off;
@@ -883,13 +881,11 @@ ChainKernel chain_kernel_p2p(const Ctx* c) {
     // (BIG: staging loops for up to 8192 chains — two shards of 4096; the small form serves populations up to 4096)
     return chain_instance(CF_P2P, P.np, P.Ng > XLVL_MAX || P.plan_K > XLVL_MAX);
 }
-// K over the chains of P onto the context's stream, with `smem` bytes of dynamic LDS: every kernel of these families takes (P, t, rec_in,
-// rec_out, flags); in profiling mode 2 with the begin/end of this dispatch as the command processor stamps them
+// K over the chains of P onto the context's stream, with `smem` bytes of dynamic LDS: every kernel of these families takes (P, t, rec_in, rec_out, flags)
 void launch_chain_kernel(Ctx* c, const ChainKernel& K, size_t smem, const KParams& P, int t, const double* rec_in, double* rec_out, int flags) {
     const dim3 grid((unsigned)(((P.N + K.ct - 1) / K.ct + K.tpw - 1) / K.tpw)), block(K.block);
     void* args[] = {(void*)&P, (void*)&t, (void*)&rec_in, (void*)&rec_out, (void*)&flags};
-    if (c->kev0) HIPCHK(hipExtLaunchKernel(K.fn, grid, block, args, smem, c->stream, c->kev0, c->kev1, 0));
-    else HIPCHK(hipLaunchKernel(K.fn, grid, block, args, smem, c->stream));
+    launch_fn(c, K.fn, grid, block, smem, c->stream, args);
 }
 
 // one thread per evaluation: theta [n][np] -> simM [n][nm], value [n], status [n].  An objective with the library's stream draws from
@@ -950,63 +946,101 @@ void launch_chain_iter(Ctx* c, int t, int flags) {
     if (!c->ext_rec_out) c->run.cur ^= 1;
 }
 
-void launch_resolve_p(Ctx* c, const KParams& P, int t, const double* gathered);
-void launch_resolve(Ctx* c, int t, const double* gathered) { launch_resolve_p(c, c->P, t, gathered); }
+// ---- the stand-alone kernels of the exchange (smm_lookahead.hpp, smm_exchange.hpp, smm_cone_big.hpp) ----
+// Every instantiation of them that a launch can take is named in exch_instance() and nowhere else: launch_exch launches a row, resolve_kernel()
+// and resolve_rows_window_kernel() pick the resolution's, lds_limits raises every row's dynamic LDS limit, smm_describe prints the pick's name.
+// A new instantiation is one row here and one name in ExchId.  What resolves exchangeMoves! (F.xk: select_forms):
+//   N_global        min_improve                      dist_fun   F.xk        rows                slots / where
+//   <= 8192 (~7400) one value >= 0 for all chains    -          XK_LEAN     lean                8-byte keys (0) or 16-byte values (> 0), LDS
+//   <= 4096         anything else                    any        XK_LVL      lvl<1024>           16-byte slots, LDS
+//   <= 8192         anything else                    any        XK_LVL_SOA  lvl_soa             split slots, LDS
+//   <= 32768        0 for all chains                 -          XK_ROWS     keys + rows<PLDS>   4-byte slots (17-bit keys), rows of 1024 pairs, LDS
+//   <= 32768        anything else                    -          XK_KEY      keys + key<PLDS>    4-byte slots (16-bit keys, intervals), LDS
+//   <= 65535        anything else / other dist_fun   any        XK_LVL_BIG  lvl_big             16-byte slots, global memory
+//   above, or K > N_global                           any        XK_ANY      any                 barrier rounds, global atomics
+// (PLDS: the partners in LDS up to XKEY_PARTNER_MAX chains, else the ballot replay.  The p2p form of a sharded run launches the rows kernel itself
+//  where this table says XK_ROWS — resolve_rows_window_kernel: <., true> reads the tagged slots of its window instead of a key pre-pass, <false,
+//  true, true> keeps the partners of the rank's own chains only; every other p2p population resolves from the window's plain values through this
+//  table.  Single shards of objfunc_norm up to 4096 chains do not get here in steady state: their chain kernel walks inline.  The test build can
+//  force an entry (SMM_TEST_HOOKS: Hooks) and adds the ticket kernel and two workgroups of lvl.  The rows stand in the order in which the host code
+//  named these kernels before there was this table, behind chain_instance's: kernels are emitted, and a few numbered, in that order.  Ng: for k_cone_chains' cap.)
+constexpr size_t ROWS_OWN_MAX = (size_t)158 * 1024;   // <false, true, true>: the slots, the rows and the own chains' partners of one workgroup
+ExchInstance exch_instance(int id, int Ng) {
+    const size_t rows_all = resolve_rows_bytes(XKEY_MAX, XKEY_MAX, XROWS_MAX), rows_part = resolve_rows_bytes(XKEY_PARTNER_MAX, XKEY_PARTNER_MAX, XROWS_MAX),
+                 lvl = resolve_lvl_bytes(XLVL_MAX, XLVL_MAX);
+    switch (id) {
+        case XI_CONE_CHAINS: return {(const void*)k_cone_chains, XWG, cone_chains_lds_bytes(Ng), XG_CONE_BIG, "cone_chains", false};
+        case XI_CONE_TILES: return {(const void*)k_cone_tiles, 64 * CONEB_WAVES, 0, XG_CONE_BIG, "cone_tiles", false};
+        case XI_PLAN_BIG: return {(const void*)k_exch_plan_big, XWG, plan_big_lds_bytes(65535), XG_BIG, "plan_big", false};
+        case XI_PLAN: return {(const void*)k_exch_plan, XWG, plan_smem(XLDS_MAX, XLDS_MAX, true), XG_LDS, "plan", false};
+        case XI_LEAN: return {(const void*)k_exch_resolve_lean, XWG, LDS_CU, XG_LDS, "lean", true};
+#ifdef SMM_TEST_HOOKS
+        case XI_LVL_256: return {(const void*)k_exch_resolve_lvl<256>, 256, lvl, XG_LDS, "lvl", false};
+        case XI_LVL_512: return {(const void*)k_exch_resolve_lvl<512>, 512, lvl, XG_LDS, "lvl", false};
+        case XI_TICKETS: return {(const void*)k_exch_resolve_lds, XWG, resolve_lds_bytes(XLDS_MAX), XG_LDS, "tickets", false};
+#endif
+        case XI_LVL: return {(const void*)k_exch_resolve_lvl<1024>, 1024, lvl, XG_LDS, "lvl", true};
+        case XI_LVL_SOA: return {(const void*)k_exch_resolve_lvl_soa<1024>, 1024, resolve_lvl_soa_bytes(XLDS_MAX, XLDS_MAX), XG_LDS, "lvl_soa", false};
+        case XI_KEYS: return {(const void*)k_exch_keys, 256, 0, XG_KEYS, "keys", false};   // (values and initial slots: the pre-pass of rows and key)
+        case XI_ROWS_PLDS: return {(const void*)k_exch_resolve_rows<true>, XWG, rows_part, XG_KEYS, "rows", false};
+        case XI_ROWS: return {(const void*)k_exch_resolve_rows<false>, XWG, rows_all, XG_KEYS, "rows", false};
+        case XI_KEY_PLDS: return {(const void*)k_exch_resolve_key<true>, XWG, resolve_key_bytes(XKEY_PARTNER_MAX, XKEY_PARTNER_MAX), XG_KEYS, "key", false};
+        case XI_KEY: return {(const void*)k_exch_resolve_key<false>, XWG, resolve_key_bytes(XKEY_MAX, XKEY_MAX), XG_KEYS, "key", false};
+        case XI_LVL_BIG: return {(const void*)k_exch_resolve_lvl_big, XWG, 0, XG_BIG, "lvl_big", false};
+        case XI_ANY: return {(const void*)k_exch_resolve_any, XWG, 0, XG_BIG, "any", false};
+        case XI_ROWS_WIN_OWN: return {(const void*)k_exch_resolve_rows<false, true, true>, XWG, ROWS_OWN_MAX, XG_KEYS, "rows_window_own", true};
+        case XI_ROWS_WIN_PLDS: return {(const void*)k_exch_resolve_rows<true, true>, XWG, rows_part, XG_KEYS, "rows_window", true};
+        case XI_ROWS_WIN: return {(const void*)k_exch_resolve_rows<false, true>, XWG, rows_all, XG_KEYS, "rows_window", true};
+        case XI_APPLY: return {(const void*)k_exch_apply, 256, 0, XG_BIG, "apply", false};   // (the three-phase calls: the resolved swaps into the records)
+        default: return {nullptr, 0, 0, XG_LDS, id == XI_TICKETS ? "tickets" : "lvl", false};   // (a row of the test build)
+    }
+}
+// what launch_resolve_p launches for this context as it stands (P: its parameters or the caller's copy): F.xk, the partners-in-LDS split, the hooks' workgroup of lvl.  Decides only.
+ExchLaunch resolve_kernel(const Ctx* c, const KParams& P) {
+    const bool plds = P.Ng <= XKEY_PARTNER_MAX;   // partners in LDS, else the ballot replay
+    switch (c->F.xk) {
+        case XK_LEAN: return {XI_LEAN, resolve_lean_bytes(P.Ng, P.plan_K, P.lean_wide != 0)};
+        case XK_LVL: return {c->H.lvl_wg == 256 ? XI_LVL_256 : c->H.lvl_wg == 512 ? XI_LVL_512 : XI_LVL, resolve_lvl_bytes(P.Ng, P.plan_K)};
+        case XK_LVL_SOA: return {XI_LVL_SOA, resolve_lvl_soa_bytes(P.Ng, P.plan_K)};
+        case XK_TICKETS: return {XI_TICKETS, resolve_lds_bytes(P.Ng)};
+        case XK_ROWS: return {plds ? XI_ROWS_PLDS : XI_ROWS, resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap)};
+        case XK_KEY: return {plds ? XI_KEY_PLDS : XI_KEY, resolve_key_bytes(P.Ng, P.plan_K)};
+        case XK_LVL_BIG: return {XI_LVL_BIG, 0};
+        default: return {XI_ANY, 0};
+    }
+}
+// ... and launch_resolve_rows_window.  A shard of a population past XKEY_PARTNER_MAX keeps its own chains' partners only (written by the swaps), where that fits
+ExchLaunch resolve_rows_window_kernel(const Ctx* c) {
+    const KParams& P = c->P;
+    const size_t own = resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap, P.N);
+    if (P.Ng > XKEY_PARTNER_MAX && P.N < P.Ng && own <= ROWS_OWN_MAX) return {XI_ROWS_WIN_OWN, own};
+    return {P.Ng <= XKEY_PARTNER_MAX ? XI_ROWS_WIN_PLDS : XI_ROWS_WIN, resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap)};
+}
+// Profiling mode 2, stated once: does the resolution take the dispatch's own stamps (a KernelEvents scope around its launch, pev_exch set), or do
+// event brackets stand around the iteration and the exchange reports 0?  Only `stamped` rows ever do; a single shard's steps also ask for a population
+// of the level walk (its chain kernel is stamped under the same condition), a shard's stamp the lean kernel only (the cases: DESIGN.md section 3)
+bool resolve_stamped(const Ctx* c, bool shard) {
+    const int id = resolve_kernel(c, c->P).id;
+    return exch_instance(id).stamped && (shard ? id == XI_LEAN : c->P.Ng <= XLVL_MAX && !c->H.dataflow && c->H.lvl_wg == 1024);
+}
+
 // (P: the context's parameters, or a copy whose RW is the stride of the value column in `gathered`)
 void launch_resolve_p(Ctx* c, const KParams& P_in, int t, const double* gathered) {
     KParams P = P_in;
     point_values(c, P, t, t);   // (single shard: the values the accept step of iteration t wrote)
-    switch ((ExchKernel)c->F.xk) {
-    case XK_LEAN:
-        launch(c, k_exch_resolve_lean, dim3(1), dim3(XWG), resolve_lean_bytes(P.Ng, P.plan_K, P.lean_wide != 0), P, t, gathered);
-        break;
-    case XK_LVL:
-#ifdef SMM_TEST_HOOKS
-        if (c->H.lvl_wg == 256) { hipLaunchKernelGGL(k_exch_resolve_lvl<256>, dim3(1), dim3(256), resolve_lvl_bytes(P.Ng, P.plan_K), c->stream, P, t, gathered); break; }
-        if (c->H.lvl_wg == 512) { hipLaunchKernelGGL(k_exch_resolve_lvl<512>, dim3(1), dim3(512), resolve_lvl_bytes(P.Ng, P.plan_K), c->stream, P, t, gathered); break; }
-#endif
-        launch(c, k_exch_resolve_lvl<1024>, dim3(1), dim3(1024), resolve_lvl_bytes(P.Ng, P.plan_K), P, t, gathered);
-        break;
-    case XK_LVL_SOA:
-        hipLaunchKernelGGL(k_exch_resolve_lvl_soa<1024>, dim3(1), dim3(1024), resolve_lvl_soa_bytes(P.Ng, P.plan_K), c->stream, P, t, gathered);
-        break;
-    case XK_TICKETS:
-#ifdef SMM_TEST_HOOKS
-        hipLaunchKernelGGL(k_exch_resolve_lds, dim3(1), dim3(XWG), resolve_lds_bytes(P.Ng), c->stream, P, t, gathered);
-#endif
-        break;
-    case XK_ROWS:
-    case XK_KEY: {
-        // values and initial slots by the whole chip (gathered records: their value column; single shard: the compact array)
-        const double* src = gathered ? gathered : (const double*)P.vals;
-        double* vals = gathered ? P.xval : P.vals;
-        if (gathered || c->run.slots_iter != t)   // (a single shard's accept step of iteration t has made the slots already)
-            hipLaunchKernelGGL(k_exch_keys, dim3((P.Ng + 255) / 256), dim3(256), 0, c->stream, src, gathered ? P.RW : 1, P.Ng, vals,
-                               (uint32_t*)P.xsrc, c->F.xk == XK_ROWS ? c->slots17 : (uint32_t*)nullptr, c->nan_flags, t);
-        const bool plds = P.Ng <= XKEY_PARTNER_MAX;   // partners in LDS, else the ballot replay
-        const uint32_t* slots16 = (gathered || c->run.slots_iter != t) ? (const uint32_t*)P.xsrc : (const uint32_t*)nullptr;
-        if (c->F.xk == XK_ROWS && plds)
-            hipLaunchKernelGGL(k_exch_resolve_rows<true>, dim3(1), dim3(XWG), resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap), c->stream, P, t,
-                               (const double*)vals, slots16, (const uint32_t*)c->slots17, c->nan_flags);
-        else if (c->F.xk == XK_ROWS)
-            hipLaunchKernelGGL(k_exch_resolve_rows<false>, dim3(1), dim3(XWG), resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap), c->stream, P, t,
-                               (const double*)vals, slots16, (const uint32_t*)c->slots17, c->nan_flags);
-        else if (plds)
-            hipLaunchKernelGGL(k_exch_resolve_key<true>, dim3(1), dim3(XWG), resolve_key_bytes(P.Ng, P.plan_K), c->stream, P, t,
-                               (const double*)vals, (const uint32_t*)P.xsrc);
-        else
-            hipLaunchKernelGGL(k_exch_resolve_key<false>, dim3(1), dim3(XWG), resolve_key_bytes(P.Ng, P.plan_K), c->stream, P, t,
-                               (const double*)vals, (const uint32_t*)P.xsrc);
-        break;
-    }
-    case XK_LVL_BIG:
-        hipLaunchKernelGGL(k_exch_resolve_lvl_big, dim3(1), dim3(XWG), 0, c->stream, P, t, gathered);
-        break;
-    case XK_ANY:
-        hipLaunchKernelGGL(k_exch_resolve_any, dim3(1), dim3(XWG), 0, c->stream, P, t, gathered);
-        break;
-    }
+    const ExchLaunch L = resolve_kernel(c, P);
+    if (c->F.xk != XK_ROWS && c->F.xk != XK_KEY) return launch_exch(c, L.id, dim3(1), L.smem, c->stream, P, t, gathered);
+    // values and initial slots by the whole chip (gathered records: their value column; single shard: the compact array)
+    const bool prepass = gathered || c->run.slots_iter != t;   // (a single shard's accept step of iteration t has made the slots already)
+    const double* vals = gathered ? P.xval : P.vals;
+    const uint32_t *slots16 = prepass ? (const uint32_t*)P.xsrc : nullptr, *slots17 = c->slots17;
+    if (prepass)
+        launch_exch(c, XI_KEYS, dim3((P.Ng + 255) / 256), 0, c->stream, gathered ? gathered : (const double*)P.vals, gathered ? P.RW : 1, P.Ng, (double*)vals, (uint32_t*)P.xsrc,
+                    c->F.xk == XK_ROWS ? c->slots17 : (uint32_t*)nullptr, c->nan_flags, t);
+    if (c->F.xk == XK_ROWS) launch_exch(c, L.id, dim3(1), L.smem, c->stream, P, t, vals, slots16, slots17, c->nan_flags);
+    else launch_exch(c, L.id, dim3(1), L.smem, c->stream, P, t, vals, (const uint32_t*)P.xsrc);
 }
+void launch_resolve(Ctx* c, int t, const double* gathered) { launch_resolve_p(c, c->P, t, gathered); }
 
 int fail(Ctx* c, int code, const std::string& m) {
     if (c) c->err = m;
@@ -1075,23 +1109,10 @@ void launch_resolve_window(Ctx* c, int t) {
     P1.RW = 1;   // (the resolve kernels read value s at gathered[s * RW])
     launch_resolve_p(c, P1, t, (const double*)(c->p2p_mine + L.val[t & 1]));
 }
-// the same straight from the tagged slots and self-validating values of the window (p2p form of large norm populations): no wait,
-// no unpacking, no key pre-pass in front of k_exch_resolve_rows
+// the same straight from the window's tagged slots and self-validating values (p2p form of large norm populations): no wait, no unpacking, no key pre-pass
 void launch_resolve_rows_window(Ctx* c, int t) {
-    const KParams& P = c->P;
-    // a shard of a population past XKEY_PARTNER_MAX: partners of its own chains only, written by the swaps (no second pass over the rows)
-    const bool own = P.Ng > XKEY_PARTNER_MAX && P.N < P.Ng && resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap, P.N) <= (size_t)158 * 1024;
-    if (own) {
-        const size_t sm = resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap, P.N);
-        launch(c, k_exch_resolve_rows<false, true, true>, dim3(1), dim3(XWG), sm, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-        return;
-    }
-    const size_t smem = resolve_rows_bytes(P.Ng, P.plan_K, P.rows_cap);
-    if (P.Ng <= XKEY_PARTNER_MAX) {
-        launch(c, k_exch_resolve_rows<true, true>, dim3(1), dim3(XWG), smem, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-    } else {
-        launch(c, k_exch_resolve_rows<false, true>, dim3(1), dim3(XWG), smem, P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-    }
+    const ExchLaunch L = resolve_rows_window_kernel(c);
+    launch_exch(c, L.id, dim3(1), L.smem, c->stream, c->P, t, (const double*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
 }
 // ---- the persistent chain kernels (smm_chain_persist*.hpp) ----
 // what launches F's persistent kernel: a kernel of the library (fn) or of a user objective's module (mfn: loaded by persist_occupancy),
@@ -1137,8 +1158,7 @@ void launch_persist(Ctx* c, const PersistKernel& K, PersistArgs A) {
     if (K.mfn && c->kev0)
         HIPCHK(hipExtModuleLaunchKernel(K.mfn, K.grid.x * K.block.x, 1, 1, K.block.x, 1, 1, K.smem, c->stream, args, nullptr, c->kev0, c->kev1, 0));
     else if (K.mfn) HIPCHK(hipModuleLaunchKernel(K.mfn, K.grid.x, 1, 1, K.block.x, 1, 1, (unsigned)K.smem, c->stream, args, nullptr));
-    else if (c->kev0) HIPCHK(hipExtLaunchKernel(K.fn, K.grid, K.block, args, K.smem, c->stream, c->kev0, c->kev1, 0));
-    else HIPCHK(hipLaunchKernel(K.fn, K.grid, K.block, args, K.smem, c->stream));
+    else launch_fn(c, K.fn, K.grid, K.block, K.smem, c->stream, args);
 }
 
 }  // namespace

@@ -187,6 +187,44 @@ def test_chain_kernel_instantiations_are_named_in_the_chooser_only():
     assert "chain_instance(family, np, b != 0).fn, hipFuncAttributeMaxDynamicSharedMemorySize" in rest
 
 
+def test_exchange_kernel_instantiations_are_named_in_the_table_only():
+    """The host sources name the stand-alone kernels of the exchange (k_exch_*, k_cone_*: smm_exchange.hpp, smm_lookahead.hpp,
+    smm_cone_big.hpp) in exch_instance() and nowhere else: every launch of the family, the dynamic-LDS attribute at context creation and
+    the name smm_describe prints after exchange= go through that table, so a kernel that can be launched has its attribute set and its
+    launch checked by construction.  Reads the sources only."""
+    csrc = os.path.join(ROOT, "smm.jl_amd", "csrc")
+    strip = lambda txt: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    src = lambda name: strip(open(os.path.join(csrc, name)).read())
+    code = src("smmhip.hip")
+    head = "ExchInstance exch_instance(int id, int Ng) {"
+    assert code.count(head) == 1
+    a = code.index(head)
+    b = code.index("\n}\n", a)
+    body = code[a:b]
+    rest = code[:a] + code[b:] + "".join(src(f) for f in ("smm_forms_host.hpp", "smm_create_host.hpp", "smm_run_host.hpp", "smm_p2p.hpp"))
+    family = r"\bk_(?:exch|cone)_\w+"
+    assert not re.findall(family + r"\s*[<,)]", rest), "an exchange kernel is named outside exch_instance()"
+    declared = set()
+    for h in ("smm_exchange.hpp", "smm_lookahead.hpp", "smm_cone_big.hpp"):
+        declared |= set(re.findall(r"__global__[^;{]*?\b(k_(?:exch|cone)_\w+)\s*\(", src(h)))
+    assert len(declared) >= 14 and set(re.findall(family, body)) == declared
+    # the bound of the rows kernel that keeps a shard's own partners: once, in any source of the tree
+    hits = 0
+    for top in ("smm.jl_amd", "tests", "tools", "oracle", "include", "julia"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                if f.endswith((".hip", ".hpp", ".h", ".py", ".c", ".jl", ".sh")) and os.path.join(dirpath, f) != os.path.abspath(__file__):
+                    hits += len(re.findall(r"158 \* 1024", open(os.path.join(dirpath, f), errors="ignore").read()))
+    assert hits == 1 and "158 * 1024" in code
+    forms = src("smm_forms_host.hpp")
+    a = forms.index("std::string describe_text(")
+    describe = forms[a:forms.index("\n}\n", a)]
+    assert "[]" not in describe and '"lean"' not in describe and '"lvl_big"' not in describe
+    assert "exch_instance(resolve_kernel(c, P).id" in describe
+    create = src("smm_create_host.hpp")
+    assert "exch_instance(id, c->P.Ng)" in create and "id < XI_COUNT" in create
+
+
 def test_reducer_kernels_and_shared_rules_live_in_the_reducers_host_file():
     """The host side of the history reducers is smm_reducers_host.hpp: smmhip.hip names none of their kernels (smm_stats.hpp, smm_cov.hpp,
     smm_diag.hpp, smm_group.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp, smm_draws.hpp, smm_moments.hpp, smm_profile.hpp), and the
