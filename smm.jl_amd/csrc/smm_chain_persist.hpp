@@ -22,7 +22,8 @@
 //     chain, waves 4..7), looks again where a tag is still the old one, lets wave 0 walk the cone's sub-levels alone, and fetches a
 //     donor's record only for a chain that was exchanged;
 //   * the next iteration's lists arrive by LDS-DMA under the simulation, its randomness is drawn by wave 1 behind its share of the
-//     simulation, and the gathering waves start looking for the other tiles' slots as soon as this tile has published;
+//     simulation (k_chain_persist_loc: and the proposal's tries 5-8 by wave 2 behind ALL waves' shares, PR_AHEAD), and the gathering
+//     waves start looking for the other tiles' slots as soon as this tile has published;
 //   * the waves are ROLE-SPECIALISED (two loops in one kernel, the same number of workgroup barriers in each): wave 0 is the control
 //     wave (its shocks wait in LDS and come into registers behind its proposal, for the same straight-line share of the simulation
 //     as a worker's); every wave adds at a raised priority (s_setprio), so that the side jobs of the waves that are done with their
@@ -311,31 +312,40 @@ __device__ __forceinline__ void persist_simulate(const double (&z)[PR_ZR], const
 // Whoever hands global data over waits for it itself (vmcnt(0) behind the LDS-DMA).
 #define PR_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
-// out of line (once per launch / almost never): proposal tries past the first four of mysample (AlgoBGP.jl:400-410) for the chains of the
-// control wave that have not found a point inside the box yet; the same loop as k_chain_iter_norm's
+// batches of NORM_NR proposal tries per chain that k_chain_persist_loc draws AHEAD, under the simulation, into s_rng (its RNGW): the first is
+// evaluated inline by the control wave, the later ones by persist_late_tries; past them the generator runs on the path between two publications
+constexpr int PR_AHEAD = 2;
+static_assert(PR_AHEAD == 1 || PR_AHEAD == 2, "s_rng holds two batches per lane (the table path stages two)");
+
+// out of line: proposal tries past the first four of mysample (AlgoBGP.jl:400-410) for the chains of the control wave that have not found a
+// point inside the box yet; the same loop as k_chain_iter_norm's.  NOT rare: on the headline instance (4096 chains) some chain of the
+// population is past its first four tries in 30-98 % of the iterations as sigma adapts (tools/late_tries_estimate.py), and every tile of its
+// cone waits for that chain's tile — so the tries NORM_NR .. 2 NORM_NR - 1 are drawn ahead too and the control wave evaluates them inline;
+// this call is left to the tries past PR_AHEAD batches (1-10 % of the iterations: the generator's FP64 log / sqrt / sin / cos, as a lone
+// wave) and to tables of fewer than 2 NORM_NR tries, whose second batch (j_first = NORM_NR) mixes s_rng and the generator
 struct PrTries { const double* rb; uint64_t seed; int rb_t0, N, RBW, rb_tries, user_n, smpl_iters, goff /* first chain of the shard in the population */; };
 template <int NP>
 struct PrTh { double th[NP]; bool found; };
 template <int NP>
 __device__ __attribute__((noinline)) PrTh<NP> persist_late_tries(const PrTries A, const double* o, const int t, const int c, const bool valid, const int lane,
                                                                  bool found, const double sigma, const double mu0, const double mu1, const double* s_const,
-                                                                 const double th0, const double th1) {
+                                                                 const double th0, const double th1, const int j_first /* NORM_NR, or past the batches evaluated inline */) {
     const int r = lane & 3;
     double mu01[NP], th[NP];
     mu01[0] = mu0; th[0] = th0;
     if constexpr (NP > 1) { mu01[1] = mu1; th[1] = th1; }
     const bool rng_here = A.rb == nullptr;
-    const int rb_tries = rng_here ? NORM_NR : A.rb_tries;
+    const int rb_tries = rng_here ? PR_AHEAD * NORM_NR : A.rb_tries;   // tries held in s_rng or memory; later ones come from the generator
     const int max_tries = A.user_n ? min(A.rb_tries, A.smpl_iters) : A.smpl_iters;
     const double* g_rb = A.rb + ((size_t)(t - A.rb_t0) * A.N + (valid ? c : 0)) * A.RBW;
-    for (int j0 = NORM_NR; __any(!found) && j0 < max_tries; j0 += NORM_NR) {
+    for (int j0 = j_first; __any(!found) && j0 < max_tries; j0 += NORM_NR) {
         const int j = j0 + r;
         double x[NP], zz[NP];
 #pragma unroll
         for (int k = 0; k < NP; ++k) { x[k] = 0.0; zz[k] = 0.0; }
         bool ok = !found && j < max_tries;
         if (ok) {
-            if (j0 == NORM_NR && !rng_here) {
+            if (j0 == NORM_NR && (PR_AHEAD > 1 || !rng_here)) {   // the second batch of s_rng (a table's tries past rb_tries: zeros, replaced below)
 #pragma unroll
                 for (int k = 0; k < NP; ++k) zz[k] = o[1 + NP + k];
             } else if (j < rb_tries) {

@@ -33,9 +33,15 @@ constexpr uint32_t PL_PBASE = ((16u * PL_LOCN + 127u) & ~127u);          // LDS 
 constexpr int PL_HASH = 1024;                                             // slots of the re-numbering table (<= 512 entries)
 // SMMHIP_TS: the simulation phase wave by wave (tools/persist_waves.py) — 8 words per wave behind the tiles' 8 of the phase stamps, for the
 // first PL_TSW_TILES tiles: sums over the launch's iterations of the wall clock when the wave leaves BB [0], has issued its last add [1], has stored
-// its partials [2], and when the control wave's wait for them ends / a worker's side job of the iteration ends [3]; HW_ID [4]; iterations [5]
+// its partials [2], and when the control wave's wait for them ends / a worker's side job of the iteration ends [3]; HW_ID [4]; iterations [5];
+// the control wave only: the iterations in which it entered persist_late_tries [6] and the ticks it spent there [7].  Behind the per-wave
+// stamps, PL_LATE_N words: the number of tiles that entered persist_late_tries in iteration t, at t mod PL_LATE_N (never reset: the reader
+// takes differences; tools/late_tries_time.py)
 constexpr size_t PL_TSW_BASE = (size_t)8 * 8192;
 constexpr int PL_TSW_TILES = 2048, PL_TSW = 8;
+constexpr size_t PL_LATE_BASE = PL_TSW_BASE + (size_t)PL_TSW_TILES * (NORM_WG / 64) * PL_TSW;
+constexpr int PL_LATE_N = 16384;
+static_assert(PL_LATE_BASE + PL_LATE_N <= (size_t)8 * 60000, "the stamp buffer: the exchange kernels' words start at 8 * 60000");
 
 __host__ __device__ inline size_t persist_loc_smem_bytes(const int np) {
     const size_t hw = (size_t)((H_PARAMS + 2 * np + 1) & ~1);
@@ -410,7 +416,7 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
 
     if (wave != 0) {
         // =====================================================================================================================
-        // the WORKER waves 1..15: simulation (all), randomness (1), progress (2), gather list + table + history (3), gather (4..7), pair lists (8..15)
+        // the WORKER waves 1..15: simulation (all), randomness (1; the tries drawn ahead past the first four: 2), progress (2), gather list + table + history (3), gather (4..7), pair lists (8..15)
         // =====================================================================================================================
         const int h = wave >> 3, wih = wave & 7;
         const bool simw = h < NP;
@@ -429,21 +435,25 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
 #pragma unroll
             for (int u = 0; u < PR_ZR; ++u) z[u] = 0.0;
         }
-        auto make_rng = [&](const int tn) {
+        // iteration tn's randomness into s_rng, drawn under the simulation of tn - 1: batch 0 = the uniform and the tries 0 .. NORM_NR - 1
+        // (wave 1), batch 1 = the tries NORM_NR .. 2 NORM_NR - 1 (generated: wave 2, behind ALL waves' adds; from a table: wave 1 with batch 0)
+        auto make_rng = [&](const int tn, const int batch) {
             const int c1 = tile * CT + (lane >> 2);
             if (c1 >= N) return;
             const uint32_t g1 = c0g + (uint32_t)(lane >> 2);
             double* o = Y.s_rng + ((tn & 1) * 64 + lane) * RNGW;
             if (rng_here) {
-                o[0] = rng_u(A.seed, g1, (uint32_t)tn);                               // probs_acc[iter], AlgoBGP.jl:85
+                if (batch == 0) o[0] = rng_u(A.seed, g1, (uint32_t)tn);              // probs_acc[iter], AlgoBGP.jl:85
+                uint32_t tr = (uint32_t)(batch * NORM_NR + (lane & 3));
+                asm volatile("" : "+v"(tr));   // (opaque: the try is a value of the iteration, not one the launch's prologue can compute ahead and keep)
 #pragma unroll
-                for (int q = 0; 2 * q < NP; ++q) {                                    // rand(RAND, d) of try r, :404
+                for (int q = 0; 2 * q < NP; ++q) {                                    // rand(RAND, d) of try batch * NORM_NR + r, :404
                     double z0, z1;
-                    rng_prop_normal2(A.seed, g1, (uint32_t)tn, (uint32_t)(lane & 3), (uint32_t)q, z0, z1);
-                    o[1 + 2 * q] = z0;
-                    if (2 * q + 1 < NP) o[1 + 2 * q + 1] = z1;
+                    rng_prop_normal2(A.seed, g1, (uint32_t)tn, tr, (uint32_t)q, z0, z1);
+                    o[1 + batch * NP + 2 * q] = z0;
+                    if (2 * q + 1 < NP) o[1 + batch * NP + 2 * q + 1] = z1;
                 }
-            } else {
+            } else if (batch == 0) {
                 const double* g_rb = A.rb + ((size_t)(tn - A.rb_t0) * N + c1) * A.RBW;
                 const int rr = lane & 3;
                 o[0] = g_rb[0];
@@ -460,7 +470,7 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
                 if (c < N && ((mask >> cl) & 1u)) ((double2*)(A.hrec + ((size_t)(trow - 1) * N + c) * HW))[i] = ((const double2*)(s_row + cl * HW))[i];
             }
         };
-        if (wave == 1) make_rng(t0);
+        if (wave == 1 || (wave == 2 && PR_AHEAD > 1)) make_rng(t0, wave - 1);
         for (int t = t0; t <= t1; ++t) {
             const int rel = t - t0 + 1;
             PR_BARRIER();   // BA
@@ -502,7 +512,6 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
                     fix_lists(t, t + 1, lane);
                 }
             }
-            if (wave == 1 && t < t1) make_rng(t + 1);
             if (wave == 2) {
                 const int m = pr_min_progress(pr_progress, epoch, tiles_all, lane);
                 if (lane == 0) {
@@ -519,6 +528,13 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
                     }
                 }
             }
+            if (wave == 2 && PR_AHEAD > 1 && rng_here && t < t1) {
+                // the second batch's FP64 work behind ALL waves' adds (the simulation runs at the FP64 issue floor: a log / sqrt / sincos issued
+                // under it is time added to it), in the idle pipes of the control wave's accept step and the hand-off
+                const unsigned want = (unsigned)(8 * NP) * (unsigned)rel;
+                while (__hip_atomic_load(Y.s_arrived, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < want) __builtin_amdgcn_s_sleep(2);
+            }
+            if ((wave == 1 || (wave == 2 && PR_AHEAD > 1)) && t < t1) make_rng(t + 1, wave - 1);   // (one copy of the generator's code for both waves)
             if (wave >= 4 && wave < 8 && lists) {
                 while (__hip_atomic_load(Y.s_glready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != t) __builtin_amdgcn_s_sleep(1);
                 while (__hip_atomic_load(Y.s_pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != t) __builtin_amdgcn_s_sleep(1);
@@ -638,13 +654,48 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
                     found = true;
                 }
             }
-            if (__builtin_expect(__any(!found), 0)) {
-                const PrTries TR{A.rb, A.seed, A.rb_t0, A.N, A.RBW, A.rb_tries, A.user_n, A.smpl_iters, A.offset};
-                const PrTh<NP> lt = persist_late_tries<NP>(TR, o, t, c, valid, lane, found, sigma, mu01[0], mu01[NP - 1], Y.s_const, th[0], th[NP - 1]);
+            if (__builtin_expect(__any(!found), 0)) {   // some chain's first NORM_NR tries all left the box (not rare: smm_chain_persist.hpp)
+                if (A.ts && lane == 0) Y.s_wts[7] -= wall_clock64();   // (the stamp lives in LDS over the call, not in a register)
+                int j_next = NORM_NR;
+                if (PR_AHEAD > 1 && (A.rb == nullptr || A.rb_tries >= 2 * NORM_NR)) {
+                    // ---- the batch drawn ahead: lane r evaluates try NORM_NR + r from s_rng, as above (a table with fewer tries mixes
+                    //      table and generator inside the batch: persist_late_tries does) ----
+                    double x[NP];
+                    bool ok = !found;
 #pragma unroll
-                for (int k = 0; k < NP; ++k) th[k] = lt.th[k];
-                found = lt.found;
-                if (!found && r == 0) pr_report(A.err, ERRK_NO_DRAW, t, (int)c0g + cl);   // :409
+                    for (int k = 0; k < NP; ++k) {
+                        const double step = sigma * o[1 + NP + k];
+                        x[k] = mu01[k] + step;
+                        if (!(x[k] >= 0.0 && x[k] <= 1.0)) ok = false;
+                    }
+                    if (NORM_NR + r >= A.smpl_iters || (A.user_n && NORM_NR + r >= A.rb_tries)) ok = false;
+                    const unsigned long long m = __ballot(ok);
+                    const unsigned quad = (unsigned)(m >> (lane & ~3)) & 0xfu;
+                    if (!found && quad) {
+                        const int rwin = __builtin_ctz(quad);
+#pragma unroll
+                        for (int k = 0; k < NP; ++k) {
+                            const double lbk = Y.s_const[k];
+                            const double sc = x[k] * (Y.s_const[NP + k] - lbk);
+                            const double thk = sc + lbk;   // mapto_ab, mprob.jl:271
+                            th[k] = quad_bcast_dyn(thk, lane, rwin);
+                        }
+                        found = true;
+                    }
+                    j_next = 2 * NORM_NR;
+                }
+                if (__any(!found)) {   // past the batches in LDS: the generator, or the table in memory (out of line)
+                    const PrTries TR{A.rb, A.seed, A.rb_t0, A.N, A.RBW, A.rb_tries, A.user_n, A.smpl_iters, A.offset};
+                    const PrTh<NP> lt = persist_late_tries<NP>(TR, o, t, c, valid, lane, found, sigma, mu01[0], mu01[NP - 1], Y.s_const, th[0], th[NP - 1], j_next);
+#pragma unroll
+                    for (int k = 0; k < NP; ++k) th[k] = lt.th[k];
+                    found = lt.found;
+                    if (!found && r == 0) pr_report(A.err, ERRK_NO_DRAW, t, (int)c0g + cl);   // :409
+                }
+                if (A.ts && lane == 0) {   // SMMHIP_TS: the tile's late-try events and their time, and the tiles with one by iteration
+                    Y.s_wts[6] += 1ull; Y.s_wts[7] += wall_clock64();
+                    atomicAdd(A.ts + PL_LATE_BASE + (size_t)(t & (PL_LATE_N - 1)), 1ull);
+                }
             }
             if (r == 0) {
 #pragma unroll

@@ -1515,6 +1515,11 @@ int smm_set_profiling(void* ctx, int32_t on) {
 int smm_debug_ts(void* ctx, unsigned long long* out, int n_wg) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !c->P.ts) return SMM_ERR_INVALID_ARG;
+    if (n_wg == -2) {  // k_chain_persist_loc's counts of the tiles that entered persist_late_tries, by iteration mod PL_LATE_N (PL_LATE_N words;
+                       // never reset, not even at allocation: take differences — tools/late_tries_time.py)
+        if (hipMemcpy(out, c->P.ts + PL_LATE_BASE, (size_t)PL_LATE_N * 8, hipMemcpyDeviceToHost) != hipSuccess) return SMM_ERR_HIP;
+        return SMM_OK;
+    }
     if (n_wg < 0) {  // the exchange kernel's stamps
         if (hipMemcpy(out, c->P.ts + (size_t)8 * 60000, 8 * 100, hipMemcpyDeviceToHost) != hipSuccess) return SMM_ERR_HIP;
         return SMM_OK;
