@@ -91,12 +91,19 @@ def test_selection_rules_on_a_hand_made_table():
                   [0.5, 0.4, 0.3, 0.2],      # status decides before the value
                   [nan, -2.0, inf, 1.0],     # nothing valid
                   [2.0, 2.0, 2.0, 2.0],      # equal to initial_value
-                  [9.0, 8.0, 7.0, 0.0]])
-    st = np.array([[1, 1, 1, 1], [1, 1, 1, 1], [1, -2, -2, -2], [1, 1, 1, -2], [1, 1, 1, 1], [1, 1, 1, 1]])
-    assert pr.select(v, st, 2.0, 1, False).tolist() == [1, 3, 0, -1, 0, 3]
-    assert pr.select(v, st, 2.0, 1, True).tolist() == [1, -1, 0, -1, -1, 3]      # initial_value wins ties and whatever is worse
-    assert pr.select(v, st, 2.0, -2, True).tolist() == [1, 3, 0, -1, 0, 3]       # an invalid initial_value does not compete ...
-    assert pr.select(v, st, nan, 1, True).tolist() == [1, 3, 0, -1, 0, 3]
+                  [9.0, 8.0, 7.0, 0.0],
+                  [1.0, 0.0, -0.0, 0.0],     # -0.0 ties +0.0: the lowest m, whatever its sign
+                  [1.0, -0.0, 0.0, 2.0 ** -1074],
+                  [0.1, 0.5, 0.3, 0.2]])     # status 0 is as invalid as -2; status 2 is valid
+    st = np.array([[1, 1, 1, 1], [1, 1, 1, 1], [1, -2, -2, -2], [1, 1, 1, -2], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1],
+                   [0, 1, 2, -2]])
+    assert pr.select(v, st, 2.0, 1, False).tolist() == [1, 3, 0, -1, 0, 3, 1, 1, 2]
+    assert pr.select(v, st, 2.0, 1, True).tolist() == [1, -1, 0, -1, -1, 3, 1, 1, 2]      # initial_value wins ties and whatever is worse
+    assert pr.select(v, st, 2.0, -2, True).tolist() == [1, 3, 0, -1, 0, 3, 1, 1, 2]       # an invalid initial_value does not compete ...
+    assert pr.select(v, st, nan, 1, True).tolist() == [1, 3, 0, -1, 0, 3, 1, 1, 2]
+    assert pr.select(v, st, 2.0, 0, True).tolist() == [1, 3, 0, -1, 0, 3, 1, 1, 2]        # (status 0)
+    assert pr.select(v, st, 0.0, 1, True).tolist() == [-1, -1, -1, -1, -1, -1, -1, -1, -1]   # +0.0 ties -0.0 and wins the tie
+    assert pr.select(v, st, -0.0, 1, True).tolist() == [-1, -1, -1, -1, -1, -1, -1, -1, -1]
     assert pr.select(v[3:4], st[3:4], -1.0, -2, False).tolist() == [-1]          # ... but is the start when nothing else is valid
 
 
