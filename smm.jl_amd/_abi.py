@@ -301,6 +301,9 @@ def load_hooks():
         lib.smm_debug_has_test_hooks.restype = C.c_int
         if lib.smm_abi_version() != 3 or lib.smm_debug_has_test_hooks() != 1:
             raise ImportError("libsmmhip_hooks.so: wrong ABI version or built without -DSMM_TEST_HOOKS")
+        # (a seam of the test build, not part of include/smmhip.h: size and FNV-1a of the code hiprtc gave for a form of a user objective)
+        lib.smm_debug_user_form.restype = C.c_int
+        lib.smm_debug_user_form.argtypes = [C.c_int32, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_char_p, C.c_int]
         _hooks_lib = lib
     return _hooks_lib
 

@@ -5,21 +5,19 @@ namespace {
 
 // workgroups per CU of F's candidate persistent kernel, its dynamic LDS set first; a user objective's kernel is compiled and loaded here.  0: not available
 int persist_occupancy(Ctx* c, const Forms& F, int objective_id) {
-    if (F.persist_user || (F.persist == PERSIST_TILE && c->obj == SMM_OBJ_USER)) {   // (user_persist_compile / user_tile_compile)
-        const bool tile = F.persist == PERSIST_TILE;
+    if (F.persist_user || (F.persist == PERSIST_TILE && c->obj == SMM_OBJ_USER)) {   // (user_form_compile)
+        const UserForm form = user_form_wanted(F, c->has_chol);
         {
             std::lock_guard<std::mutex> lock(g_user_mutex);
             UserObjective& u = g_user_objectives[objective_id - SMM_OBJ_USER_BASE];
-            const bool chol = tile && !F.persist_sh && c->has_chol;   // (select_forms gives a shard with a factor no persistent form)
-            if (!(tile ? user_tile_compile(u, F.persist_sh, chol) : user_persist_compile(u))) {
+            if (!user_form_compile(u, form)) {
                 if (getenv("SMMHIP_VERBOSE"))
-                    fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n",
-                            (tile ? (chol ? u.tile_chol_log : F.persist_sh ? u.tile_sh_log : u.tile_log) : u.persist_log).c_str());
+                    fprintf(stderr, "libsmmhip: the persistent form of this user objective is not available:\n%s\n", u.form[form].log.c_str());
                 return 0;
             }
-            HIPCHK(hipModuleLoadData(&c->pmod, (tile ? (chol ? u.tile_chol_code : F.persist_sh ? u.tile_sh_code : u.tile_code) : u.persist_code).data()));
+            HIPCHK(hipModuleLoadData(&c->pmod, u.form[form].code.data()));
         }
-        HIPCHK(hipModuleGetFunction(&c->pfn, c->pmod, tile ? "smm_user_persist_tile_kernel" : "smm_user_persist_kernel"));
+        HIPCHK(hipModuleGetFunction(&c->pfn, c->pmod, user_form_kernel(form)));
     }
     const PersistKernel K = persist_kernel(c, F);
     int per_cu = 0;

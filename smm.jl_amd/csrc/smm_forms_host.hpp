@@ -111,7 +111,7 @@ Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
     // ... and for smaller populations of the same objective (whole groups of 32): the cones are listed behind the lean plan either way
     const bool gen_small_ok = gen_ok && N % PG_CT == 0 && N / PG_CT >= 1 && N / PG_CT <= n_cus && lds && mi0 && minus && K <= XLDS_MAX;
     const bool want_gen_small = !want_cone && c->obj == SMM_OBJ_BANANA && F.inline_walk && gen_small_ok && gen_fits;
-    // ... and a USER objective (one thread per evaluation) in the same loop, compiled with the user's source inside (user_persist_compile)
+    // ... and a USER objective (one thread per evaluation) in the same loop, compiled with the user's source inside (user_form_compile)
     const bool want_user = user_obj && c->u_lanes == 0 && gen_small_ok && persist_gen_smem(c, true) <= LDS_CU;
     // ... and on LOCALLY NUMBERED cones (smm_chain_persist_loc.hpp): objfunc_norm of the loc shape, thresholds >= 0 (or NaN), any population size
     const bool mi_ok = one_threshold(P) || P.mi_pct;   // one threshold >= 0 (or NaN) for all chains, or one per chain, each >= 0 (or NaN)
@@ -207,7 +207,7 @@ Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
     return F;
 }
 
-// (the choosers and the exchange's table: smmhip.hip, behind this file)
+// (the choosers and the exchange's table: smm_launch_host.hpp, behind this file)
 ChainKernel chain_kernel(const Ctx* c, int flags); PersistKernel persist_kernel(const Ctx* c, const Forms& F); ExchLaunch resolve_kernel(const Ctx* c, const KParams& P); ExchInstance exch_instance(int id, int Ng);
 // which forms this context was given at creation (one line; tests/test_gpu_forms.py pins the table)
 std::string describe_text(const Ctx* c) {

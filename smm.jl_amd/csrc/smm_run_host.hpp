@@ -1,4 +1,4 @@
-// the host side of a run — part of libsmmhip (included once by smmhip.hip, behind its launch helpers and kernel choosers and ahead of
+// the host side of a run — part of libsmmhip (included once by smmhip.hip, behind the launchers and kernel choosers of smm_launch_host.hpp and ahead of
 // smm_reducers_host.hpp, whose prelude settles and flushes through this file; hiprtc never sees it).  Everything that advances or settles
 // a run: the error path (told, persist_give_up, p2p_agree_error, check_device_error), the run's launches and their bookkeeping
 // (persist_usable .. launch_chain_persist, enqueue_iterations, persist_repair, settle_persist, p2p_publish, p2p_to_plain, p2p_enqueue,

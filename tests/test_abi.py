@@ -165,18 +165,18 @@ def test_the_shipped_library_has_no_test_seams():
 
 
 def test_chain_kernel_instantiations_are_named_in_the_chooser_only():
-    """smmhip.hip names the per-iteration chain kernels (k_chain_iter*, smm_chain.hpp and smm_chain_norm.hpp) in chain_instance() and
-    nowhere else: the launchers, the dynamic-LDS attribute at context creation and smm_describe all go through it, so a kernel that can
+    """The host sources name the per-iteration chain kernels (k_chain_iter*, smm_chain.hpp and smm_chain_norm.hpp) in chain_instance()
+    (smm_launch_host.hpp) and nowhere else: the launchers, the dynamic-LDS attribute at context creation and smm_describe all go through it, so a kernel that can
     be launched has its attribute set and its name reported by construction.  Reads the sources only."""
     csrc = os.path.join(ROOT, "smm.jl_amd", "csrc")
     strip = lambda txt: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
-    code = strip(open(os.path.join(csrc, "smmhip.hip")).read())
+    code = strip(open(os.path.join(csrc, "smm_launch_host.hpp")).read())
     head = "ChainKernel chain_instance(int family, int np, bool b) {"
     assert code.count(head) == 1
     a = code.index(head)
     b = code.index("\n}\n", a)
     body, rest = code[a:b], code[:a] + code[b:] + "".join(strip(open(os.path.join(csrc, f)).read())
-                                                           for f in ("smm_run_host.hpp", "smm_forms_host.hpp", "smm_create_host.hpp"))
+                                                           for f in ("smmhip.hip", "smm_user_host.hpp", "smm_run_host.hpp", "smm_forms_host.hpp", "smm_create_host.hpp"))
     assert not re.findall(r"\bk_chain_iter\w*", rest), "a chain kernel is named outside chain_instance()"
     declared = set()
     for h in ("smm_chain.hpp", "smm_chain_norm.hpp"):
@@ -195,13 +195,13 @@ def test_exchange_kernel_instantiations_are_named_in_the_table_only():
     csrc = os.path.join(ROOT, "smm.jl_amd", "csrc")
     strip = lambda txt: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
     src = lambda name: strip(open(os.path.join(csrc, name)).read())
-    code = src("smmhip.hip")
+    code = src("smm_launch_host.hpp")
     head = "ExchInstance exch_instance(int id, int Ng) {"
     assert code.count(head) == 1
     a = code.index(head)
     b = code.index("\n}\n", a)
     body = code[a:b]
-    rest = code[:a] + code[b:] + "".join(src(f) for f in ("smm_forms_host.hpp", "smm_create_host.hpp", "smm_run_host.hpp", "smm_p2p.hpp"))
+    rest = code[:a] + code[b:] + "".join(src(f) for f in ("smmhip.hip", "smm_user_host.hpp", "smm_forms_host.hpp", "smm_create_host.hpp", "smm_run_host.hpp", "smm_p2p.hpp"))
     family = r"\bk_(?:exch|cone)_\w+"
     assert not re.findall(family + r"\s*[<,)]", rest), "an exchange kernel is named outside exch_instance()"
     declared = set()
@@ -223,6 +223,37 @@ def test_exchange_kernel_instantiations_are_named_in_the_table_only():
     assert "exch_instance(resolve_kernel(c, P).id" in describe
     create = src("smm_create_host.hpp")
     assert "exch_instance(id, c->P.Ng)" in create and "id < XI_COUNT" in create
+
+
+def test_persistent_kernel_instantiations_are_named_in_the_table_only():
+    """The host sources name the persistent chain kernels (k_chain_persist_*: smm_chain_persist_gen.hpp, _loc.hpp, _tile.hpp) in
+    persist_instance() (smm_launch_host.hpp) and nowhere else: persist_kernel() picks a row of that table, and the occupancy check, every
+    launch and the name smm_describe prints after persistent= go through its pick.  Reads the sources only."""
+    csrc = os.path.join(ROOT, "smm.jl_amd", "csrc")
+    strip = lambda txt: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    src = lambda name: strip(open(os.path.join(csrc, name)).read())
+    code = src("smm_launch_host.hpp")
+    head = "PersistInstance persist_instance(int id) {"
+    assert code.count(head) == 1
+    a = code.index(head)
+    b = code.index("\n}\n", a)
+    body = code[a:b]
+    hosts = sorted(f for f in os.listdir(csrc) if f.endswith("_host.hpp") and f != "smm_launch_host.hpp")
+    assert "smm_user_host.hpp" in hosts and "smm_create_host.hpp" in hosts
+    rest = code[:a] + code[b:] + src("smmhip.hip") + "".join(src(f) for f in hosts)
+    family = r"\bk_chain_persist_\w+"
+    assert not re.findall(family, rest), "a persistent kernel is named outside persist_instance()"
+    declared = set()
+    for h in sorted(f for f in os.listdir(csrc) if re.fullmatch(r"smm_chain_persist\w*\.hpp", f)):
+        declared |= set(re.findall(r"__global__[^;{]*?\b(k_chain_persist_\w+)\s*\(", src(h)))
+    assert len(declared) == 3 and set(re.findall(family, body)) == declared
+    assert len(re.findall(family, body)) == 21   # one row per instantiation
+    for fn, home in (("PersistKernel persist_kernel(", code), ("int persist_occupancy(", src("smm_create_host.hpp"))):
+        assert home.count(fn) == 1, fn
+        a = home.index(fn)
+        assert "k_chain_persist" not in home[a:home.index("\n}\n", a)], fn
+    a = code.index("PersistKernel persist_kernel(")
+    assert "persist_instance(id)" in code[a:code.index("\n}\n", a)]
 
 
 def test_reducer_kernels_and_shared_rules_live_in_the_reducers_host_file():
@@ -281,7 +312,8 @@ def test_the_run_lives_in_the_run_host_file_with_one_frame_and_one_rule_book():
     def functions_with(pattern):
         """the functions (by name) whose definitions hold the pattern: the nearest line above that starts a definition at column 0"""
         found = set()
-        for f in ("smmhip.hip", "smm_forms_host.hpp", "smm_create_host.hpp", "smm_run_host.hpp", "smm_reducers_host.hpp", "smm_population_host.hpp"):
+        for f in ("smmhip.hip", "smm_user_host.hpp", "smm_forms_host.hpp", "smm_launch_host.hpp", "smm_create_host.hpp", "smm_run_host.hpp",
+                  "smm_reducers_host.hpp", "smm_population_host.hpp"):
             lines = code[f].splitlines()
             for i, line in enumerate(lines):
                 if pattern not in line:
@@ -303,7 +335,7 @@ def test_the_run_lives_in_the_run_host_file_with_one_frame_and_one_rule_book():
     run = code["smm_run_host.hpp"]
     assert "c->snap = c->run;" in run and "c->run = c->snap;" in run
     assert everything.count("k_flush,") == 1 and "void launch_flush(" in run
-    assert not re.findall(r"c->kev[01] = |c->ext_(?:rec_in|rec_out|vals_out) = ", main + code["smm_reducers_host.hpp"] + code["smm_population_host.hpp"])
+    assert not re.findall(r"c->kev[01] = |c->ext_(?:rec_in|rec_out|vals_out) = ", main + code["smm_user_host.hpp"] + code["smm_launch_host.hpp"] + code["smm_reducers_host.hpp"] + code["smm_population_host.hpp"])
     assert len(re.findall(r"c->kev0 = ", run)) == 2 and len(re.findall(r"c->ext_rec_in = ", run)) == 2   # (the two scope objects)
 
 
@@ -318,17 +350,32 @@ def test_the_forms_and_context_creation_live_in_their_host_files_with_each_rule_
     code = {f: strip(open(os.path.join(csrc, f)).read()) for f in names}
     main, forms, create = code["smmhip.hip"], code["smm_forms_host.hpp"], code["smm_create_host.hpp"]
     makefile = open(os.path.join(csrc, "Makefile")).read()
-    for f in ("smm_forms_host.hpp", "smm_create_host.hpp"):
+    for f in ("smm_user_host.hpp", "smm_forms_host.hpp", "smm_launch_host.hpp", "smm_create_host.hpp"):
         assert main.count('#include "%s"' % f) == 1 and sum(c.count('"%s"' % f) for c in code.values()) == 1, f
         assert f not in makefile, f   # (not among the sources hiprtc is given)
-    assert main.index('#include "smm_forms_host.hpp"') < main.index('#include "smm_run_host.hpp"') < main.index('#include "smm_create_host.hpp"')
+    order = [main.index('#include "%s"' % f) for f in ("smm_user_host.hpp", "smm_forms_host.hpp", "smm_launch_host.hpp", "smm_run_host.hpp",
+                                                        "smm_create_host.hpp")]
+    assert order == sorted(order)
     assert not re.findall(r"\bhip[A-Z]\w*\(", forms) and "HIPCHK" not in forms
+    user, launch = code["smm_user_host.hpp"], code["smm_launch_host.hpp"]
     for fn, home in (("select_forms", forms), ("smm_ctx_create", create), ("alloc_persist", create), ("persist_occupancy", create),
-                     ("tile_smem", forms), ("check_create_args", create), ("create_facts", create), ("describe_text", forms)):
+                     ("tile_smem", forms), ("check_create_args", create), ("create_facts", create), ("describe_text", forms),
+                     ("rtc_compile", user), ("user_form_compile", user), ("user_form_wanted", user), ("register_user_source", user),
+                     ("smm_register_user_objective", user), ("smm_register_user_objective_lanes", user), ("smm_register_user_objective_rng", user),
+                     ("exchange_K", launch), ("ensure_windows", launch), ("plan_window_into", launch), ("point_tables", launch),
+                     ("chain_instance", launch), ("chain_kernel", launch), ("chain_kernel_p2p", launch), ("launch_chain_iter", launch),
+                     ("exch_instance", launch), ("resolve_kernel", launch), ("resolve_rows_window_kernel", launch), ("launch_resolve_p", launch),
+                     ("launch_p2p_push", launch), ("launch_resolve_rows_window", launch), ("persist_instance", launch), ("persist_kernel", launch),
+                     ("launch_persist", launch)):
         definition = r"^[A-Za-z_][\w:<>\*& ]*\b%s\([^;]*\) \{" % fn
         assert len(re.findall(definition, home, flags=re.M)) == 1, fn
         assert not re.findall(definition, main, flags=re.M), fn
-    three = main + forms + create
+    # the way through hiprtc is smm_user_host.hpp's alone, and so are its one refusal and the map-reduce reduction's text
+    hosts = "\n".join(code[f] for f in names if f == "smmhip.hip" or f.endswith("_host.hpp"))
+    assert not re.findall(r"\bhiprtc\w*\(", main) and "g_rtc" not in main
+    assert hosts.count('"hiprtcCreateProgram failed"') == 1 and '"hiprtcCreateProgram failed"' in user
+    assert hosts.count("a = a + __shfl_xor(a, off, 64);") == 1 and "a = a + __shfl_xor(a, off, 64);" in user
+    three = main + user + forms + launch + create   # (the three files this code stood in, and the two that took the rest of smmhip.hip's)
     assert len(re.findall(r"160 \* 1024", three)) == 1 and "160 * 1024" in forms
     assert not re.findall(r"\b80 \* 1024", three)
     assert len(re.findall(r"\(\(\(\w+ \+ 3\) & ~3\) \+ 4\) \* 8", three)) == 1 and "size_t key_slot_bytes(int Ng)" in forms

@@ -1,4 +1,5 @@
 """User-defined device objectives (include/smmhip.h SMM_USER_OBJECTIVE)."""
+import ctypes as C
 import os
 import sys
 
@@ -242,3 +243,53 @@ def test_map_reduce_user_objective_in_the_persistent_loop(S, O, lanes, N, steps,
         assert (hh.exchanged != 0).any()
     if fail_above is not None:
         assert (hh.status == -2).any()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the persistent forms' way through hiprtc, without a device (the test build's seam smm_debug_user_form)
+# ------------------------------------------------------------------------------------------------------------------------------
+USER_FORMS = {"gen": 1, "tile": 2, "tile_shard": 3, "tile_chol": 4}   # (0: the evaluation kernels made at registration)
+
+
+def user_form(A, oid, form):
+    """-> (return value, size, FNV-1a, log) of one form of a registered objective's code"""
+    size, fnv, log = C.c_ulonglong(), C.c_ulonglong(), C.create_string_buffer(1 << 16)
+    rc = A.load_hooks().smm_debug_user_form(oid, form, C.byref(size), C.byref(fnv), log, len(log))
+    return rc, size.value, fnv.value, log.value.decode()
+
+
+@pytest.mark.parametrize("kind,rng", [("one_thread", False), ("one_thread", True), ("map_reduce", False), ("map_reduce", True)])
+def test_every_persistent_form_compiles_where_it_applies_and_is_refused_where_not(S, hooks, kind, rng):
+    # every header a form's translation unit includes must be among the texts the library carries: a missing one fails here, not only
+    # when a context is created on a GPU
+    from user_rng_src import AR1_RNG_SOURCE, PANEL_RNG_SOURCE
+    if kind == "one_thread":
+        oid = S.register_user_objective(AR1_RNG_SOURCE if rng else AR1_SOURCE, rng=rng)
+        applies, refusal = ["gen"], "not the map-reduce form"
+    else:
+        oid = S.register_user_objective(PANEL_RNG_SOURCE if rng else PANEL_SOURCE, n_sums=3, lanes=128, rng=rng)
+        applies, refusal = ["tile", "tile_shard", "tile_chol"], "not the one-thread-per-chain form"
+    rc, size, fnv, _ = user_form(hooks, oid, 0)
+    assert rc == 1 and size > 0
+    seen = {fnv}
+    for name, form in USER_FORMS.items():
+        first = user_form(hooks, oid, form)
+        if name in applies:
+            assert first[0] == 1 and first[1] > 0, (name, first[3])
+            seen.add(first[2])
+        else:
+            assert first == (0, 0, 0, refusal), name
+        assert user_form(hooks, oid, form) == first, name   # (the second request: what the first one made)
+    assert len(seen) == 1 + len(applies)   # every form is code of its own
+    lib = hooks.load_hooks()
+    assert lib.smm_debug_user_form(oid, 5, None, None, None, 0) < 0 and lib.smm_debug_user_form(oid, -1, None, None, None, 0) < 0
+    assert lib.smm_debug_user_form(999, 1, None, None, None, 0) < 0 and lib.smm_debug_user_form(1000 + 10 ** 6, 1, None, None, None, 0) < 0
+
+
+def test_a_source_that_fails_only_inside_the_persistent_kernel_is_refused_with_the_log(S, hooks):
+    # ZBuf is a struct of smm_chain.hpp: the evaluation kernel's translation unit does not include it, the persistent form's does
+    oid = S.register_user_objective(AR1_SOURCE + "\nstruct ZBuf { int mine; };\n")
+    assert user_form(hooks, oid, 0)[0] == 1
+    rc, size, fnv, log = user_form(hooks, oid, USER_FORMS["gen"])
+    assert (rc, size, fnv) == (0, 0, 0) and "ZBuf" in log and "error" in log, log
+    assert user_form(hooks, oid, USER_FORMS["gen"]) == (rc, size, fnv, log)

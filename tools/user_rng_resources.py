@@ -1,6 +1,6 @@
 """Registers / spills / scratch / LDS of the kernels a user objective with the library's stream is compiled into, as the compiler reports them
 (cross-compiles for gfx950, no GPU needed).  The translation units are assembled from the same prelude and kernel texts libsmmhip hands to
-hiprtc (the string constants of smmhip.hip), around tests/user_rng_src.py's sources:
+hiprtc (the string constants of smm_user_host.hpp), around tests/user_rng_src.py's sources:
   python tools/user_rng_resources.py"""
 import ast
 import os
@@ -15,11 +15,14 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from user_objective_src import AR1_SOURCE, PANEL_SOURCE  # noqa: E402
 from user_rng_src import AR1_RNG_SOURCE, PANEL_RNG_SOURCE  # noqa: E402
 
-HIP = open(os.path.join(CSRC, "smmhip.hip")).read()
+HIP = open(os.path.join(CSRC, "smm_user_host.hpp")).read()
+# (the map-reduce kernels' shared ending is a macro of string literals: put where it is used)
+_reduce = re.search(r"#define USER_REDUCE_LANES \\\n((?:[^\n]*\\\n)*[^\n]*)\n", HIP)
+HIP = HIP[:_reduce.start()] + HIP[_reduce.end():].replace("USER_REDUCE_LANES", _reduce.group(1).replace("\\\n", "\n"))
 
 
 def text(name):
-    """the C string constant `const char* name = "..." "...";` of smmhip.hip"""
+    """the C string constant `const char* name = "..." "...";` of smm_user_host.hpp"""
     m = re.search(r"const char\* %s =\s*((?:\s*\"(?:[^\"\\]|\\.)*\")+)\s*;" % name, HIP)
     return "".join(ast.literal_eval(s) for s in re.findall(r"\"(?:[^\"\\]|\\.)*\"", m.group(1)))
 
