@@ -283,6 +283,7 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistArgs
         const uint32_t lbase = pbase + (uint32_t)((t - 1) & 1) * (CONE_LEVELS * 64 * 4);
         if (exch && wave == 0) {
             // ---- the walk over the cone's sub-levels: wave 0 alone, no barriers ----
+            // (lean_walk_levels, not lean_walk_sub64: with the latter this kernel measured 1.2 % slower on banana at 8192 chains, EXPERIMENTS R9.1)
             const int nsub = (int)(s_hdr[((t - 1) & 3) * 16] & 0xffffu);
             const PersistWalkValues values{W, (const uint4*)pr_rec + (size_t)((rel - 1) & rmask) * A.Ng * RW, first ? A.rec_in : nullptr, pr_tag32(epoch, rel - 1), RW, 0, t};
             if (US == 0) lean_walk_levels<64, 0, false, PersistWalkValues>(nullptr, 1, lbase, (uint32_t)(64 * lane), nsub, lane, 0, 0.0, values);

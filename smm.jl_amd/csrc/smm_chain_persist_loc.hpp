@@ -13,7 +13,8 @@
 //     by the waves that brought them, under the simulation (a hash of the gather list built by wave 3: nothing of it is on the path
 //     between two publications); k_cone_tiles' (N_global > 8192) are local already;
 //   * WIDE = one min_improve > 0 for all chains (dist_fun = -): 16-byte slots {value, local | stamp << 16}, the test is the
-//     subtraction itself (lean_walk_levels<., ., true>), the gathered value is the record's own self-validating copy;
+//     subtraction itself (lean_walk_sub64<., true>: the lone-wave walk over whole sub-levels of 64 pair words, smm_walk_lean.hpp — both
+//     forms of this kernel walk with it), the gathered value is the record's own self-validating copy;
 //   * SH = a shard of a sharded run (one process per GPU, smm_p2p.hpp's windows): the ring lives in every rank's window; a tile
 //     publishes its chains' WHOLE records into its own rank's window and, into every PEER's (fire-and-forget stores over xGMI), only
 //     what every walk consumes — the parameters and the value, NP + 1 self-validating granules = 48 bytes per chain and peer at two
@@ -119,13 +120,19 @@ __device__ inline void pl_wts_out(unsigned long long* ts, const unsigned long lo
     for (int k = 0; k < PL_TSW; ++k) o[k] = k == 4 ? (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) : w[k];   // (HW_REG_HW_ID: SIMD_ID in bits 5:4)
 }
 
-// GUARD of the lean walk on local numbers: the exact value of local chain s (a key tie) out of the ring
+// GUARD of the lean walk on local numbers: the exact value of local chain s (a key tie) out of the ring.  It holds what the kernel
+// has at hand anyway; the ring entry's address and its tag are worked out where a tie is met, out of line (only a tie reads them:
+// built ahead of the walk they were ~25 scalar instructions and their registers on the path of every iteration)
+__device__ __attribute__((noinline, cold)) double pl_tie_value(const PrWait W, const unsigned char* win, const uint32_t o_rec, const int rel, const int rmask, const int Ng,
+                                                               const uint32_t gl, const uint32_t c0g, const int RW, const int NPV, const int t, const uint32_t s) {
+    // (gl: the LDS offset of the exchange's gather list)
+    const uint32_t g = s < (uint32_t)NORM_CT ? c0g + s : (uint32_t)*(const __attribute__((address_space(3))) uint16_t*)(size_t)(gl + 2u * (s - (uint32_t)NORM_CT));
+    const uint4* ring = (const uint4*)(win + o_rec) + (size_t)((rel - 1) & rmask) * Ng * RW;
+    return pr_tie_value(W, ring, nullptr, pr_tag32(W.epoch, rel - 1), RW, NPV, t, g);
+}
 struct PersistLocWalkValues {
-    PrWait W; const uint4* ring; const uint16_t* gl; uint32_t c0g; uint32_t tag; int RW; int NPV; int t;
-    __device__ __forceinline__ double value(const uint32_t s) const {
-        const uint32_t g = s < (uint32_t)NORM_CT ? c0g + s : (uint32_t)gl[s - NORM_CT];
-        return pr_tie_value(W, ring, nullptr, tag, RW, NPV, t, g);
-    }
+    PrWait W; const unsigned char* win; uint32_t o_rec; int rel; int rmask; int Ng; uint32_t gl; uint32_t c0g; int RW; int NPV; int t;
+    __device__ __forceinline__ double value(const uint32_t s) const { return pl_tie_value(W, win, o_rec, rel, rmask, Ng, gl, c0g, RW, NPV, t, s); }
 };
 // (the ring's words travel at the system scope — sc0 sc1: pr_store8 / pr_store_ll / pr_dma16 and the loads of smm_chain_persist.hpp —
 // whether the tiles are one device's or the ranks': a remote store lands in this device's memory behind its L2)
@@ -571,7 +578,16 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
     for (int t = t0; t <= t1; ++t) {
         const int rel = t - t0 + 1;
         const bool exch = t == t0 ? A.walk_first != 0 : exch_on(t - 1);
-        double z0[PR_ZR];   // the wave's shocks, for the simulation only: fetched behind the proposal, in registers from BB on
+        double z0[PR_ZR];   // the wave's shocks, for the simulation only: fetched behind BB (the barrier does not wait for them)
+        // Between BA and BB stands only what the proposal needs of the walk: `src`, the local number of the chain whose record this
+        // chain continues from.  The slot's word goes over BB in a register (wmeta = src | stamp << 16; no walk: the chain's own number,
+        // no stamp), and what else hangs on it — the partner, the donor's record, st[CS_PARTNER] / st[CS_WASX] — follows behind BB, where
+        // the other fifteen waves already simulate.  What that relies on:
+        //   * nobody but this wave writes the tile's own slots [0..15] before "behind the publication" (the gather writes slots >= 16);
+        //   * the pair and gather lists of parity (t - 1) & 1 stand until request_lists(t + 1), behind the next BA;
+        //   * ring entry rel - 1 stays readable until announce(rel), behind the donor's validation as before;
+        //   * the s_waitcnt vmcnt(0) ahead of the donor's look is where it was: it covers the later request just the same.
+        uint32_t wmeta;
         PR_BARRIER();   // BA
         {
             const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -582,43 +598,22 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
             unsigned long long ts1 = 0;
             if (A.ts && lane == 0) { ts1 = wall_clock64(); if (t != t0) Y.s_ts[0] += ts1 - Y.s_ts[7]; }
             // ---- the walk over the cone's sub-levels, on local slots: this wave alone, no barriers ----
-            uint32_t src = (uint32_t)cl;    // local number of the chain whose record this chain continues from
-            int partner = 0;                // 1 + the partner's number in the population
-            const uint32_t lbase = Y.pbase + (uint32_t)((t - 1) & 1) * (CONE_LEVELS * 64 * 4);
-            const uint16_t* gl = (const uint16_t*)(lds + Y.gbase) + ((t - 1) & 1) * CONE_GCAP;
+            wmeta = (uint32_t)cl;
             if (exch) {
-                const int nsub = (int)(Y.s_hdr[((t - 1) & 3) * 16] & 0xffffu);
+                const uint32_t lbase = Y.pbase + (uint32_t)((t - 1) & 1) * (CONE_LEVELS * 64 * 4);
+                uint32_t hw, pw0;   // the cone's header word (nsub) and the lane's first pair word: one LDS round trip
+                lean_sub64_head(Y.hbase + (uint32_t)((t - 1) & 3) * 64u, lbase, lane, hw, pw0);
+                const int nsub = (int)((uint32_t)__builtin_amdgcn_readfirstlane((int)hw) & 0xffffu);
                 if constexpr (WIDE) {
-                    lean_walk_levels<64, 0, true, WalkNoGuard, PCT>(nullptr, 1, lbase, (uint32_t)(64 * lane), nsub, lane, 0, A.thr, WalkNoGuard(),
-                                                                    (uint32_t)((unsigned char*)Y.s_thr - lds));
+                    lean_walk_sub64<0, true, WalkNoGuard, PCT>(lbase, nsub, lane, pw0, A.thr, WalkNoGuard(), (uint32_t)((unsigned char*)Y.s_thr - lds));
                 } else {
-                    const PersistLocWalkValues values{W, (const uint4*)(mine + A.o_rec) + (size_t)((rel - 1) & rmask) * A.Ng * RW, gl, c0g, pr_tag32(epoch, rel - 1), RW, NP, t};
-                    lean_walk_levels<64, 0, false, PersistLocWalkValues>(nullptr, 1, lbase, (uint32_t)(64 * lane), nsub, lane, 0, 0.0, values);
+                    const PersistLocWalkValues values{W, mine, A.o_rec, rel, rmask, A.Ng, Y.gbase + (uint32_t)((t - 1) & 1) * (CONE_GCAP * 2), c0g, RW, NP, t};
+                    lean_walk_sub64<0, false, PersistLocWalkValues>(lbase, nsub, lane, pw0, 0.0, values);
                 }
-                if (valid) {
-                    const uint32_t kmeta = WIDE ? ((const uint4*)lds)[cl].z : ((const uint2*)lds)[cl].y;
-                    src = kmeta & 0xffffu;
-                    if (kmeta >> 16) {   // set_exchanged!, :747-748
-                        const uint32_t pl = lean_partner<0, WIDE ? 4 : 3>(lds, lbase, kmeta, (uint32_t)cl) - 1u;
-                        partner = 1 + (int)(pl < (uint32_t)CT ? c0g + pl : (uint32_t)gl[pl - CT]);
-                    }
-                }
+                if (valid) wmeta = WIDE ? ((const uint4*)lds)[cl].z : ((const uint2*)lds)[cl].y;
             }
+            const uint32_t src = wmeta & 0xffffu;    // local number of the chain whose record this chain continues from
             const bool donor = valid && src != (uint32_t)cl;
-            const uint32_t src_g = src < (uint32_t)CT ? c0g + src : (uint32_t)gl[src - CT];
-            // the donor's whole record (swap_ev_ij!, :734-749), requested now and looked at behind the simulation (LDS-DMA, past the caches)
-            if (donor) {
-                const unsigned char* dwin = mine;
-                if constexpr (SH) {   // (the donor's OWNER holds the whole record: equal shards of A.N chains)
-                    const int owner = (int)src_g / A.N;
-#pragma unroll
-                    for (int p = 0; p < P2P_MAXG; ++p) dwin = owner == p ? A.win[p] : dwin;
-                }
-                const uint4* g_ll = (const uint4*)(dwin + A.o_rec) + ((size_t)((rel - 1) & rmask) * A.Ng + src_g) * RW;
-                const uint32_t dbase = (uint32_t)((unsigned char*)Y.s_donor - lds);
-                pr_dma16(g_ll + r, dbase);
-                if (4 + r < RW) pr_dma16(g_ll + 4 + r, dbase + 64 * 16);
-            }
             unsigned long long ts2 = 0;
             if (A.ts && lane == 0) ts2 = wall_clock64();
             // ---- proposal: lane r evaluates try r; the chain's first try inside the unit box wins (mysample, :400-410) ----
@@ -700,11 +695,7 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
             if (r == 0) {
 #pragma unroll
                 for (int k = 0; k < NP; ++k) Y.s_theta[cl * NP + k] = th[k];
-                st[CS_PARTNER] = (double)partner;
-                st[CS_WASX] = (double)src;   // (free during the launch: the LOCAL number the record comes from)
             }
-#pragma unroll
-            for (int u = 0; u < PR_ZR; ++u) z0[u] = Y.s_z0[u * 64 + lane];
             if (A.ts && lane == 0) {
                 const unsigned long long ts4 = wall_clock64();
                 Y.s_ts[1] += ts2 - ts1; Y.s_ts[3] += ts4 - ts2; Y.s_ts[6] = ts4;
@@ -717,6 +708,40 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
             // its share is the place of wave 0 of half 0 — the same lanes, draws, sums and s_part slots as a worker's
             const int lane_a = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
             const bool extra0 = lane_a < A.ns - nfull0 * WG;
+#pragma unroll
+            for (int u = 0; u < PR_ZR; ++u) z0[u] = Y.s_z0[u * 64 + lane_a];
+            {
+                // ---- what else hangs on the walk (above): the partner, the donor's record, the chain's state words of them ----
+                const int cl = lane_a >> 2, r = lane_a & 3;
+                const bool valid = tile * CT + cl < N;
+                const uint32_t src = wmeta & 0xffffu;
+                const uint32_t lbase = Y.pbase + (uint32_t)((t - 1) & 1) * (CONE_LEVELS * 64 * 4);
+                const uint16_t* gl = (const uint16_t*)(lds + Y.gbase) + ((t - 1) & 1) * CONE_GCAP;
+                int partner = 0;                // 1 + the partner's number in the population
+                if (wmeta >> 16) {   // set_exchanged!, :747-748
+                    const uint32_t pl = lean_partner<0, WIDE ? 4 : 3>(lds, lbase, wmeta, (uint32_t)cl) - 1u;
+                    partner = 1 + (int)(pl < (uint32_t)CT ? c0g + pl : (uint32_t)gl[pl - CT]);
+                }
+                // the donor's whole record (swap_ev_ij!, :734-749), requested now and looked at behind the simulation (LDS-DMA, past the caches)
+                if (valid && src != (uint32_t)cl) {
+                    const uint32_t src_g = src < (uint32_t)CT ? c0g + src : (uint32_t)gl[src - CT];
+                    const unsigned char* dwin = mine;
+                    if constexpr (SH) {   // (the donor's OWNER holds the whole record: equal shards of A.N chains)
+                        const int owner = (int)src_g / A.N;
+#pragma unroll
+                        for (int p = 0; p < P2P_MAXG; ++p) dwin = owner == p ? A.win[p] : dwin;
+                    }
+                    const uint4* g_ll = (const uint4*)(dwin + A.o_rec) + ((size_t)((rel - 1) & rmask) * A.Ng + src_g) * RW;
+                    const uint32_t dbase = (uint32_t)((unsigned char*)Y.s_donor - lds);
+                    pr_dma16(g_ll + r, dbase);
+                    if (4 + r < RW) pr_dma16(g_ll + 4 + r, dbase + 64 * 16);
+                }
+                if (r == 0) {
+                    double* st = Y.s_st + cl * LW;
+                    st[CS_PARTNER] = (double)partner;
+                    st[CS_WASX] = (double)src;   // (free during the launch: the LOCAL number the record comes from)
+                }
+            }
             __builtin_amdgcn_s_setprio(1);
             if (nfull0 == PR_ZR - 1) persist_simulate<NP, true>(z0, nfull0, extra0, Y.s_theta, Y.s_part, 0, 0, A.ts != nullptr, tw1);
             else persist_simulate<NP, false>(z0, nfull0, extra0, Y.s_theta, Y.s_part, 0, 0, A.ts != nullptr, tw1);

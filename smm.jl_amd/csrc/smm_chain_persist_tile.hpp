@@ -376,8 +376,10 @@ __global__ __launch_bounds__(WG) void k_chain_persist_tile(const PersistArgs A) 
         if (A.ts && tid == 0) { ts0 = wall_clock64(); if (t != t0) s_ts[0] += ts0 - s_ts[7]; }
         // ---- the walk over the cone's sub-levels, on local slots: wave 0 alone, no barriers ----
         if (exch && wave == 0) {
-            const int nsub = (int)(s_hdr[((t - 1) & 3) * 16] & 0xffffu);
-            lean_walk_levels<64, 0, true, WalkNoGuard, PCT>(nullptr, 1, L.pbase, (uint32_t)(64 * lane), nsub, lane, 0, A.thr, WalkNoGuard(), L.thbase);
+            uint32_t hw, pw0;   // the cone's header word (nsub) and the lane's first pair word: one LDS round trip
+            lean_sub64_head(L.hbase + (uint32_t)((t - 1) & 3) * 64u, L.pbase, lane, hw, pw0);
+            const int nsub = (int)((uint32_t)__builtin_amdgcn_readfirstlane((int)hw) & 0xffffu);
+            lean_walk_sub64<0, true, WalkNoGuard, PCT>(L.pbase, nsub, lane, pw0, A.thr, WalkNoGuard(), L.thbase);
         }
         PR_BARRIER();   // B1
         unsigned long long ts1 = 0;

@@ -12,7 +12,9 @@
 //     {order_key32(value), chain} of the chains those pairs name, out of the array the accept step wrote (slot8[]) — a few KB
 //     instead of 100;
 //   * lets wave 0 walk the sub-levels alone (lean_walk_levels on 64 lanes: no barriers; a lone wave needs ~190 cycles per level
-//     whatever its width — the dependency depth is what the exchange costs, not the population).
+//     whatever its width — the dependency depth is what the exchange costs, not the population).  (The prologues of this file keep
+//     lean_walk_levels; k_chain_persist_loc and k_chain_persist_tile walk the same lists with lean_walk_sub64, which is written for
+//     exactly this case — a lone wave, whole sub-levels — and needs ~110 cycles per sub-level.)
 // Whenever a cone does not fit CONE_LEVELS sub-levels the whole iteration is walked the old way (cone_ok[w] == 0: every workgroup
 // decides the same).  min_improve == 0, dist_fun = -, like the key walk itself.
 // ------------------------------------------------------------------------------------------

@@ -178,3 +178,89 @@ __device__ inline void lean_walk_levels(const double* __restrict__ vsrc, const i
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
 }
+
+// ------------------------------------------------------------------------------------------
+// The walk of k_chain_persist_loc and k_chain_persist_tile: a LONE wave over `nsub` sub-levels of exactly 64 padded pair words at LDS offset pbase — the same
+// semantics as lean_walk_levels<64, US, WIDE, GUARD, PCT>(vsrc, vstride, pbase, 64 * lane, nsub, lane, 0, thr, guard, thr_base), without
+// what a lone wave on whole sub-levels never needs: no table of level starts and no readlane of it, no width test, no loop over a
+// level wider than the workgroup, no idle level, no barrier.  The word address and the stamp advance by constants per sub-level
+// (256 bytes, 64 << 16): the address as the DS offset immediate of a trip unrolled by four, the stamp as one add.
+// The lane's FIRST pair word comes from the caller, who requests it in the LDS round trip that tells it nsub (lean_sub64_head: the
+// word's address does not depend on nsub; past the list it is garbage that is not used).
+// ------------------------------------------------------------------------------------------
+// the word at LDS offset hoff (the same for all lanes) and this lane's first pair word, in one LDS round trip
+__device__ inline void lean_sub64_head(const uint32_t hoff, const uint32_t pbase, const int lane, uint32_t& hdr, uint32_t& pw) {
+    asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(hdr), "=&v"(pw) : "v"(hoff), "v"(pbase + 4u * (uint32_t)lane) : "memory");
+}
+#define LEAN_SUB64_OFF(o) " offset:" #o "\n\t"
+// one sub-level: `pw` is the lane's pair word of it and becomes the next sub-level's, read at ptr + OFF together with the slots
+template <int US, bool WIDE, class GUARD, bool PCT, int OFF>
+__device__ __forceinline__ void lean_sub64_level(const uint32_t ptr, const uint32_t stamp, uint32_t& pw, const double thr, const GUARD& guard, const uint32_t thr_base) {
+    static_assert(OFF == 256 || OFF == 512 || OFF == 768 || OFF == 1024, "the word of the next sub-level within a trip of four");
+    uint32_t ai, aj;
+    lean_decode<US>(pw, ai, aj);
+    uint32_t pwn;
+    if constexpr (WIDE) {
+        u32x4_t si, sj;
+        double thr_l = thr;
+#define LEAN_SUB64_WIDE(o) \
+        if constexpr (PCT) /* (the threshold of position i rides in the same LDS round trip) */ \
+            asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b32 %2, %6" LEAN_SUB64_OFF(o) "ds_read_b64 %3, %7\n\ts_waitcnt lgkmcnt(0)" \
+                         : "=&v"(si), "=&v"(sj), "=&v"(pwn), "=&v"(thr_l) : "v"(ai), "v"(aj), "v"(ptr), "v"(thr_base + (ai >> 1)) : "memory"); \
+        else \
+            asm volatile("ds_read_b128 %0, %3\n\tds_read_b128 %1, %4\n\tds_read_b32 %2, %5" LEAN_SUB64_OFF(o) "s_waitcnt lgkmcnt(0)" \
+                         : "=&v"(si), "=&v"(sj), "=&v"(pwn) : "v"(ai), "v"(aj), "v"(ptr) : "memory")
+        if constexpr (OFF == 256) { LEAN_SUB64_WIDE(256); } else if constexpr (OFF == 512) { LEAN_SUB64_WIDE(512); }
+        else if constexpr (OFF == 768) { LEAN_SUB64_WIDE(768); } else { LEAN_SUB64_WIDE(1024); }
+#undef LEAN_SUB64_WIDE
+        const double vi = __hiloint2double((int)si.y, (int)si.x), vj = __hiloint2double((int)sj.y, (int)sj.x);
+        if (vi - vj > thr_l) {   // dist_fun = -, AlgoBGP.jl:688; swap_ev_ij!, :739-744; the stamp stands for set_exchanged!, :747-748
+            const u32x4_t ni = {sj.x, sj.y, (sj.z & 0xffffu) | stamp, 0u}, nj = {si.x, si.y, (si.z & 0xffffu) | stamp, 0u};
+            asm volatile("ds_write_b128 %0, %2\n\tds_write_b128 %1, %3" :: "v"(ai), "v"(aj), "v"(ni), "v"(nj) : "memory");
+        }
+    } else {
+        u32x2_t si, sj;
+#define LEAN_SUB64_KEY(o) \
+        asm volatile("ds_read_b64 %0, %3\n\tds_read_b64 %1, %4\n\tds_read_b32 %2, %5" LEAN_SUB64_OFF(o) "s_waitcnt lgkmcnt(0)" \
+                     : "=&v"(si), "=&v"(sj), "=&v"(pwn) : "v"(ai), "v"(aj), "v"(ptr) : "memory")
+        if constexpr (OFF == 256) { LEAN_SUB64_KEY(256); } else if constexpr (OFF == 512) { LEAN_SUB64_KEY(512); }
+        else if constexpr (OFF == 768) { LEAN_SUB64_KEY(768); } else { LEAN_SUB64_KEY(1024); }
+#undef LEAN_SUB64_KEY
+        bool swap = si.x > sj.x;
+        const bool tie = si.x == sj.x;
+        if (__builtin_expect(__ballot(tie) != 0ull, 0)) {   // the keys do not decide: the exact values (dist_fun = -, AlgoBGP.jl:688)
+            if (tie) swap = walk_value(guard, nullptr, 1, si.y & 0xffffu) - walk_value(guard, nullptr, 1, sj.y & 0xffffu) > 0.0;
+        }
+        if (swap) {   // swap_ev_ij!, :739-744; the stamp stands for set_exchanged!, :747-748
+            const u32x2_t ni = {sj.x, (sj.y & 0xffffu) | stamp}, nj = {si.x, (si.y & 0xffffu) | stamp};
+            asm volatile("ds_write_b64 %0, %2\n\tds_write_b64 %1, %3" :: "v"(ai), "v"(aj), "v"(ni), "v"(nj) : "memory");
+        }
+    }
+    pw = pwn;
+}
+#undef LEAN_SUB64_OFF
+template <int US, bool WIDE = false, class GUARD = WalkNoGuard, bool PCT = false>
+__device__ inline void lean_walk_sub64(const uint32_t pbase, const int nsub, const int lane, uint32_t pw, const double thr = 0.0, const GUARD& guard = GUARD(),
+                                       const uint32_t thr_base = 0u) {
+    static_assert(!std::is_same<GUARD, WalkNoGuard>::value || WIDE, "a key tie reads the exact values through the guard: there is no plain array here");
+    constexpr uint32_t SUBST = 64u << 16;                     // the stamp's advance per sub-level: 64 words
+    uint32_t ptr = pbase + 4u * (uint32_t)lane;               // this lane's word of the trip's first sub-level
+    uint32_t stamp = ((uint32_t)lane + 1u) << 16;             // 1 + the position of that word
+    int left = nsub;
+    // (the common case falls through; a taken branch per FOUR sub-levels)
+#pragma clang loop unroll(disable)
+    for (; left >= 4; left -= 4) {
+        lean_sub64_level<US, WIDE, GUARD, PCT, 256>(ptr, stamp, pw, thr, guard, thr_base);
+        lean_sub64_level<US, WIDE, GUARD, PCT, 512>(ptr, stamp + SUBST, pw, thr, guard, thr_base);
+        lean_sub64_level<US, WIDE, GUARD, PCT, 768>(ptr, stamp + 2u * SUBST, pw, thr, guard, thr_base);
+        lean_sub64_level<US, WIDE, GUARD, PCT, 1024>(ptr, stamp + 3u * SUBST, pw, thr, guard, thr_base);
+        ptr += 1024u; stamp += 4u * SUBST;
+    }
+    if (left & 2) {
+        lean_sub64_level<US, WIDE, GUARD, PCT, 256>(ptr, stamp, pw, thr, guard, thr_base);
+        lean_sub64_level<US, WIDE, GUARD, PCT, 512>(ptr, stamp + SUBST, pw, thr, guard, thr_base);
+        ptr += 512u; stamp += 2u * SUBST;
+    }
+    if (left & 1) lean_sub64_level<US, WIDE, GUARD, PCT, 256>(ptr, stamp, pw, thr, guard, thr_base);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
