@@ -3,7 +3,9 @@ to the contract restated in hist_ref.py over the history downloaded with smm_get
 three selections, two windows, explicit / NULL / per-chain groups, autodetected and given ranges and pairs; the C3 layout (pooled
 groups of many workgroups through the global atomics); dense2 at np = 50 (parameter batches, bins past LDS, batches of groups); the
 test build's seams at small size; a map-reduce user objective; crafted histories; p2p shards; invalid arguments and subsets of
-outputs; a twin context that was never asked; and host.histogram / histogram2d against numpy on params(c), without a download."""
+outputs; a twin context that was never asked; and host.histogram / histogram2d against numpy on params(c), without a download.
+The crafted histories here draw from a small pool over ranges whose edges are exact in binary; draws that ride the edges of awkward
+ranges (numpy's index corrections by one, the LDS limits, the degenerate tables) are in tests/test_gpu_hist_edges.py."""
 import ctypes as C
 import os
 import re
