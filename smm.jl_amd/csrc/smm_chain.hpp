@@ -1,4 +1,4 @@
-// the chain kernel: tile reduction, simulation, objectives, block moves, inline exchange walk, k_chain_iter, k_flush, k_eval_batch — part of libsmmhip (included by smmhip.hip inside its anonymous namespace; gfx950 device code).
+// the chain kernel: tile reduction, simulation, objectives, block moves, the lean inline exchange walks (the 16-byte-slot ones: smm_walk_slots.hpp), k_chain_iter, k_flush, k_eval_batch — part of libsmmhip (included by smmhip.hip inside its anonymous namespace; gfx950 device code).
 #pragma once
 // ------------------------------------------------------------------------------------------
 // Transposed wave reduction: every lane holds CT partial sums a[0..CT); on return lane l holds the
@@ -640,139 +640,8 @@ __device__ inline void copy_strided(double* dst, const double* src, const int n,
     for (int k = r; k < n; k += nr) dst[k] = src[k];
 }
 
-// ------------------------------------------------------------------------------------------
-// exchangeMoves! inside the chain kernel (single shard, N_global <= XLVL_MAX).
-// The level walk of k_exch_resolve_lvl (below) costs ~7 us as a kernel of one workgroup plus a ~2.5 us
-// kernel boundary.  Executed redundantly by EVERY tile in the prologue of the next k_chain_iter it costs
-// the walk's ~4 us inside a kernel that is latency-structured anyway, and the boundary and the xres round
-// trip disappear.  Same plan (k_exch_plan: pairs grouped by dependency level), same arithmetic, same result;
-// the working set is 16 bytes per chain + 4 bytes per pair of LDS, the pair list overlaid by the tile's own
-// blocks once the walk is over: 80 KB at N = 4096, so two tiles still share a CU.  Thresholds: one scalar when min_improve is uniform, else read from the plan (L2).
-// ------------------------------------------------------------------------------------------
-constexpr int XLVL_MAX = 4096;
-struct __attribute__((aligned(16))) XSlot {  // one chain during the walk: 16 bytes, moved with one ds_read/write_b128
-    double val;
-    uint32_t src, partner;
-};
-// LDS of a tile with the inline walk: [XSlot slot[Ng]] [pairs[K] u32, later overlaid by the tile's own blocks]
-__host__ __device__ inline size_t walk_slot_bytes(int Ng) { return (size_t)Ng * sizeof(XSlot); }
-
-template <int NT>
-__device__ inline void exchange_walk_tile(const KParams& P, const int tx, unsigned char* lds, const int tid, const int ts_tile = 0) {
-    const int Ng = P.Ng, K = P.plan_K;
-    const int w = tx - P.plan_t0;
-    XSlot* slot = (XSlot*)lds;                              // [Ng]
-    uint32_t* pairs = (uint32_t*)(lds + walk_slot_bytes(Ng));   // [K]
-    const uint32_t* __restrict__ g_off = P.lv_off + (size_t)w * (K + 2);
-    const uint32_t* __restrict__ g_pairs = P.lv_pairs + (size_t)w * K;
-    const double* __restrict__ g_mi = P.lv_mi + (size_t)w * K;
-    const bool mi_u = P.mi_uniform != 0;
-    const double mi_v = P.mi_value;
-    // one round trip of global loads
-    constexpr int PT = XLVL_MAX / NT;
-    const int lane = tid & 63;
-    double v_[PT];
-    uint32_t pq_[PT];
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {
-        const int g = tid + r * NT;
-        v_[r] = g < Ng ? P.vals[g] : 0.0;
-    }
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {
-        const int q = tid + r * NT;
-        pq_[r] = q < K ? g_pairs[q] : 0u;
-    }
-    const uint32_t ev = g_off[min(lane, K)];   // lane l: end of level l
-    const int nlev = (int)g_off[K + 1];
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {
-        const int g = tid + r * NT;
-        if (g < Ng) {
-            XSlot s_;
-            s_.val = v_[r]; s_.src = (uint32_t)g; s_.partner = 0;
-            slot[g] = s_;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {
-        const int q = tid + r * NT;
-        if (q < K) pairs[q] = pq_[r];
-    }
-    for (int q = tid + PT * NT; q < K; q += NT) pairs[q] = g_pairs[q];   // injected pair lists longer than XLVL_MAX
-    auto level_end = [&](int l) -> uint32_t {
-        const int lc = min(l, nlev - 1);
-        return lc < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)ev, lc) : g_off[lc];
-    };
-    // The level sizes fall off geometrically.  The narrow tail (every remaining level <= 64 pairs) is walked by
-    // wave 0 alone: LDS operations of one wave complete in order, so its levels need no workgroup barrier and
-    // cost one LDS round trip each (a barrier level of a tile costs ~0.45 us next to a second walking tile).
-    int ltail = nlev;
-    if (nlev > 0 && nlev <= 64 && !(P.dbg & 128)) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)ev, 1, 64);
-        const unsigned long long wide = __ballot(lane < nlev && ev - (lane > 0 ? lo : 0u) > 64u);
-        ltail = wide ? 64 - __builtin_clzll(wide) : 0;
-    }
-    __syncthreads();
-    if (P.ts && tid == 0) P.ts[(size_t)ts_tile * 8 + 5] = wall_clock64();   // staged
-    uint32_t b = 0;
-    uint32_t e = nlev > 0 ? level_end(0) : 0u;
-    uint32_t e2 = nlev > 0 ? level_end(1) : 0u;
-    uint32_t pw = (b + tid < e) ? pairs[b + tid] : 0u;
-    double m = mi_u ? mi_v : ((b + tid < e) ? g_mi[b + tid] : 0.0);
-    // (the loops twice: the default dist_fun `-` pays nothing for the menu)
-    auto levels = [&](auto gen) {
-        const int dk = decltype(gen)::value ? P.dist_fun : 0;
-#pragma clang loop unroll(disable)
-        for (int l = 0; l < ltail; ++l) {
-            const uint32_t e3 = level_end(l + 2);
-            // this thread's first pair of the next level is fetched while this level runs
-            const uint32_t pw2 = (e + tid < e2) ? pairs[e + tid] : 0u;
-            const double m2 = mi_u ? mi_v : ((e + tid < e2) ? g_mi[e + tid] : 0.0);
-            for (uint32_t pos = b + tid; pos < e; pos += NT) {
-                if (pos != b + tid) { pw = pairs[pos]; m = mi_u ? mi_v : g_mi[pos]; }
-                const uint32_t i = pw & 0xffffu, j = pw >> 16;
-                const XSlot si = slot[i], sj = slot[j];
-                if (dist_fun_eval(dk, si.val, sj.val) > m) {   // dist_fun (default -), AlgoBGP.jl:688
-                    XSlot ni, nj;                           // swap_ev_ij!, :739-744; set_exchanged!, :747-748
-                    ni.val = sj.val; ni.src = sj.src; ni.partner = j + 1;
-                    nj.val = si.val; nj.src = si.src; nj.partner = i + 1;
-                    slot[i] = ni;
-                    slot[j] = nj;
-                }
-            }
-            b = e; e = e2; e2 = e3; pw = pw2; m = m2;
-            __syncthreads();
-        }
-        if (ltail < nlev) {
-            if (tid < 64) {   // (pw, m) already hold this lane's pair of level ltail, e its end, e2 the next end
-                constexpr uint32_t NOPAIR = 0xffffffffu;   // i == j == 0xffff never occurs (chain ids < XLVL_MAX)
-                uint32_t cpw = (b + tid < e) ? pw : NOPAIR;
-#pragma clang loop unroll(disable)
-                for (int l = ltail; l < nlev; ++l) {
-                    const uint32_t e3 = level_end(l + 2);
-                    const uint32_t npw = (e + tid < e2) ? pairs[e + tid] : NOPAIR;
-                    const double m2 = mi_u ? mi_v : ((e + tid < e2) ? g_mi[e + tid] : 0.0);
-                    if (cpw != NOPAIR) {
-                        const uint32_t i = cpw & 0xffffu, j = cpw >> 16;
-                        const XSlot si = slot[i], sj = slot[j];
-                        if (dist_fun_eval(dk, si.val, sj.val) > m) {
-                            XSlot ni, nj;
-                            ni.val = sj.val; ni.src = sj.src; ni.partner = j + 1;
-                            nj.val = si.val; nj.src = si.src; nj.partner = i + 1;
-                            slot[i] = ni;
-                            slot[j] = nj;
-                        }
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    cpw = npw; m = m2; e = e2; e2 = e3;
-                }
-            }
-            __syncthreads();
-        }
-    };
-    if (P.dist_fun != 0) levels(std::true_type{}); else levels(std::false_type{});
-}
+// (the exchange walk on 16-byte slots — XLVL_MAX, XSlot, exchange_walk_tile, exchange_walk_fast: smm_walk_slots.hpp)
+#include "smm_walk_slots.hpp"
 
 // The lean walk of smm_walk_lean.hpp in k_chain_iter (one min_improve >= 0 for all chains, dist_fun = -; the plan in its padded
 // form): 16-byte slots {value, src | stamp << 16} built from the chains' values — with min_improve == 0 too, whose plan (made for
@@ -780,6 +649,9 @@ __device__ inline void exchange_walk_tile(const KParams& P, const int tx, unsign
 // slots behind the chains'.  The control wave of every tile of the workgroup takes its chains' result (src | partner << 32, as
 // k_exch_resolve_* write it) into xr before the tile's blocks may overwrite the pair list.  false (nothing done, no barrier
 // passed): this iteration's plan has more than 31 levels — the caller walks with exchange_walk_tile.
+// (written out in full, like exchange_walk_tile_keys below and exchange_walk_lean in smm_chain_norm.hpp: on the shared staging pieces of
+// smm_walk_lean.hpp the register allocation of k_chain_iter / k_chain_iter_norm moved, and k_chain_iter<0, 8, 1, true> ran 0.25 us longer — MEASUREMENTS.md.
+// The layout's numbers and the reading of the plan's header word are the shared ones)
 template <int NT>
 __device__ inline bool exchange_walk_tile_lean(const KParams& P, const int tx, unsigned char* lds, const int tid, const bool valid, const int gc,
                                                unsigned long long& xr, const int ts_tile) {
@@ -788,8 +660,8 @@ __device__ inline bool exchange_walk_tile_lean(const KParams& P, const int tx, u
     const uint32_t* __restrict__ g_offp = P.lv_offp + (size_t)w * LV_OFFP;
     const uint4* __restrict__ g_pairs = (const uint4*)(P.lv_pairs_p + (size_t)w * P.plan_Kp);
     const int lane = tid & 63;
-    const uint32_t Ng4 = (uint32_t)((Ng + 3) & ~3);
-    const uint32_t pbase = 16u * (Ng4 + 2u);              // LDS offset of the pair words
+    const uint32_t Ng4 = lean_Ng4(Ng);
+    const uint32_t pbase = LeanLayout<LEAN_TILE16>::pbase(Ng4);              // LDS offset of the pair words
     constexpr int PT = XLVL_MAX / NT;                     // chains per lane
     constexpr int PR = (XLVL_MAX + 64 * LV_MAXLEV + 4 * NT - 1) / (4 * NT);   // rounds of 16-byte loads for the pair words
     const uint32_t ov = g_offp[min(lane, LV_OFFP - 1)];   // lane l: first word of level l; lane 33: levels; lane 34: the plan fits
@@ -805,8 +677,9 @@ __device__ inline bool exchange_walk_tile_lean(const KParams& P, const int tx, u
         const int q4 = tid + r * NT;
         p_[r] = 4 * q4 < P.plan_Kp ? g_pairs[q4] : make_uint4(0u, 0u, 0u, 0u);
     }
-    const int nlev = __builtin_amdgcn_readlane((int)ov, 33);
-    if (__builtin_amdgcn_readlane((int)ov, 34) == 0 || (uint32_t)(size_t)lds != 0u) return false;
+    const LeanPlanHead head = lean_plan_head(ov);
+    const int nlev = head.nlev;
+    if (!head.fits || (uint32_t)(size_t)lds != 0u) return false;
 #pragma unroll
     for (int r = 0; r < PT; ++r) {
         const int g = tid + r * NT;
@@ -849,8 +722,8 @@ __device__ inline bool exchange_walk_tile_keys(const KParams& P, const int tx, u
     const uint32_t* __restrict__ g_offp = P.lv_offp + (size_t)w * LV_OFFP;
     const uint4* __restrict__ g_pairs = (const uint4*)(P.lv_pairs_p + (size_t)w * P.plan_Kp);
     const int lane = tid & 63;
-    const uint32_t Ng4 = (uint32_t)((Ng + 3) & ~3);
-    const uint32_t pbase = 8u * (Ng4 + 4u);               // LDS offset of the pair words
+    const uint32_t Ng4 = lean_Ng4(Ng);
+    const uint32_t pbase = LeanLayout<LEAN_KEYS>::pbase(Ng4);               // LDS offset of the pair words
     constexpr int PR = (XLDS_MAX + 64 * LV_MAXLEV + 4 * NT - 1) / (4 * NT);   // rounds of 16-byte loads for the pair words
     const uint32_t ov = g_offp[min(lane, LV_OFFP - 1)];   // lane l: first word of level l; lane 33: levels; lane 34: the plan fits
     // the chains' slots as the accept step wrote them ({order_key32(value), chain}; a NaN value set the sticky flag): two per 16 bytes
@@ -868,8 +741,9 @@ __device__ inline bool exchange_walk_tile_keys(const KParams& P, const int tx, u
         const int q4 = tid + r * NT;
         p_[r] = 4 * q4 < P.plan_Kp ? g_pairs[q4] : make_uint4(0u, 0u, 0u, 0u);
     }
-    const int nlev = __builtin_amdgcn_readlane((int)ov, 33);
-    if (__builtin_amdgcn_readlane((int)ov, 34) == 0 || __builtin_amdgcn_readlane((int)wflags, 0) != 0 || (uint32_t)(size_t)lds != 0u) return false;
+    const LeanPlanHead head = lean_plan_head(ov);
+    const int nlev = head.nlev;
+    if (!head.fits || __builtin_amdgcn_readlane((int)wflags, 0) != 0 || (uint32_t)(size_t)lds != 0u) return false;
     uint2* slot = (uint2*)lds;
 #pragma unroll
     for (int r = 0; r < SR; ++r) {
@@ -896,139 +770,6 @@ __device__ inline bool exchange_walk_tile_keys(const KParams& P, const int tx, u
     if (gc2 >= 0) *src2 = slot[gc2].y & 0xffffu;   // (the dense kind: the record source of the chain this lane loads)
     __syncthreads();   // (from here on the tile's blocks may overwrite the pair list)
     return true;
-}
-
-// The same walk with the level loop written for latency: a level is ONE LDS round trip (both 16-byte slots of a pair with a
-// ds_read_b128 each), the compare, the two 16-byte writes of a swap and the barrier; the next level's pair word is fetched
-// ahead; nothing else is in the loop (thresholds: a scalar when min_improve is uniform — the loop is instantiated twice).
-// The level walk is latency, not bandwidth: a level with a handful of pairs costs almost what a level with a thousand does
-// (measured per level of the first form: 1784 cycles for 1000 pairs, ~850 for 50), so what counts is the dependent chain
-// per level.  FINAL_BARRIER = false: only the walking wave 0 reads the result (its own LDS operations complete in order).
-constexpr uint32_t XNOPAIR = 0xffffffffu;   // i == j == 0xffff never occurs (chain ids < XLVL_MAX)
-// (inline asm: left to itself the compiler reads only the 8 value bytes first and fetches src with a second, dependent LDS
-// read inside the swap branch — two round trips per level instead of one.  The asm's own LDS operations are invisible to the
-// compiler's counters, hence the explicit waits: after the reads, and walk_wait_lds() before every barrier.)
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-__device__ inline void walk_pair(const uint32_t slot_base, const uint32_t pw, const double m) {
-    const uint32_t i = pw & 0xffffu, j = pw >> 16;
-    const uint32_t ai = slot_base + i * 16u, aj = slot_base + j * 16u;
-    u32x4_t si, sj;
-    asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(si), "=&v"(sj) : "v"(ai), "v"(aj) : "memory");
-    const double vi = __builtin_bit_cast(double, ((unsigned long long)si.y << 32) | si.x);
-    const double vj = __builtin_bit_cast(double, ((unsigned long long)sj.y << 32) | sj.x);
-    if (vi - vj > m) {                                   // dist_fun = -, AlgoBGP.jl:688
-        u32x4_t ni = sj, nj = si;                        // swap_ev_ij!, :739-744; set_exchanged!, :747-748
-        ni.w = j + 1; nj.w = i + 1;
-        asm volatile("ds_write_b128 %0, %2\n\tds_write_b128 %1, %3" :: "v"(ai), "v"(aj), "v"(ni), "v"(nj) : "memory");
-    }
-}
-__device__ inline void walk_wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-template <int NT, bool MI_U, bool FINAL_BARRIER>
-__device__ inline void walk_levels(const KParams& P, const uint32_t slot, const uint32_t* pairs, const double* __restrict__ g_mi, const uint32_t ev,
-                                   const uint32_t* __restrict__ g_off, const int nlev, const int ltail, const int tid) {
-    const double mi_v = P.mi_value;
-    auto level_end = [&](int l) -> uint32_t {
-        const int lc = min(l, nlev - 1);
-        return lc < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)ev, lc) : g_off[lc];
-    };
-    // (level ends and this wave's first position are scalars: a wave without a pair in a level runs no vector instruction for it)
-    uint32_t b = 0;
-    uint32_t e = nlev > 0 ? level_end(0) : 0u;
-    uint32_t e2 = nlev > 0 ? level_end(1) : 0u;
-    uint32_t pw = (b + tid < e) ? pairs[b + tid] : XNOPAIR;
-    double m = MI_U ? mi_v : ((b + tid < e) ? g_mi[b + tid] : 0.0);
-#pragma clang loop unroll(disable)
-    for (int l = 0; l < ltail; ++l) {
-        const uint32_t e3 = level_end(l + 2);
-        uint32_t pw2 = XNOPAIR;
-        double m2 = mi_v;
-        {   // this thread's first pair of the next level
-            pw2 = (e + tid < e2) ? pairs[e + tid] : XNOPAIR;
-            if constexpr (!MI_U) m2 = (e + tid < e2) ? g_mi[e + tid] : 0.0;
-        }
-        {
-            if (pw != XNOPAIR) walk_pair(slot, pw, m);
-            for (uint32_t pos = b + tid + NT; pos < e; pos += NT) walk_pair(slot, pairs[pos], MI_U ? mi_v : g_mi[pos]);   // levels wider than the workgroup
-        }
-        b = e; e = e2; e2 = e3; pw = pw2; m = m2;
-        walk_wait_lds();
-        __syncthreads();
-        if (P.ts_levels && tid == 0 && blockIdx.x == 0 && l < 30) P.ts[(size_t)8 * 60000 + 16 + l] = clock64();
-    }
-    if (P.ts && tid == 0 && blockIdx.x == 0) { P.ts[(size_t)8 * 60000 + 14] = (unsigned long long)ltail; P.ts[(size_t)8 * 60000 + 7] = (unsigned long long)nlev; }
-    if (ltail < nlev) {
-        if (tid < 64) {   // the narrow tail: wave 0 alone, no barriers (pw, m hold this lane's pair of level ltail, e its end, e2 the next end)
-#pragma clang loop unroll(disable)
-            for (int l = ltail; l < nlev; ++l) {
-                const uint32_t e3 = level_end(l + 2);
-                const uint32_t pw2 = (e + tid < e2) ? pairs[e + tid] : XNOPAIR;
-                double m2 = mi_v;
-                if constexpr (!MI_U) m2 = (e + tid < e2) ? g_mi[e + tid] : 0.0;
-                if (pw != XNOPAIR) walk_pair(slot, pw, m);
-                __builtin_amdgcn_wave_barrier();
-                pw = pw2; m = m2; e = e2; e2 = e3;
-                if (P.ts_levels && tid == 0 && blockIdx.x == 0 && l < 30) { walk_wait_lds(); P.ts[(size_t)8 * 60000 + 16 + l] = clock64(); }
-            }
-            walk_wait_lds();
-        }
-        if constexpr (FINAL_BARRIER) __syncthreads();
-    }
-}
-
-struct WalkNoWork { __device__ inline void operator()() const {} };
-// while_loading: work of the caller that needs no memory (it runs between the request of the walk's inputs and their arrival)
-template <int NT, bool FINAL_BARRIER, class F = WalkNoWork>
-__device__ inline void exchange_walk_fast(const KParams& P, const int tx, unsigned char* lds, const int tid, const int ts_tile,
-                                          F while_loading = F()) {
-    const int Ng = P.Ng, K = P.plan_K;
-    const int w = tx - P.plan_t0;
-    uint4* slot = (uint4*)lds;                                  // [Ng] {value lo, value hi, src, partner}
-    uint32_t* pairs = (uint32_t*)(lds + walk_slot_bytes(Ng));   // [K]
-    const uint32_t* __restrict__ g_off = P.lv_off + (size_t)w * (K + 2);
-    const uint32_t* __restrict__ g_pairs = P.lv_pairs + (size_t)w * K;
-    const double* __restrict__ g_mi = P.lv_mi + (size_t)w * K;
-    constexpr int PT = XLVL_MAX / NT;
-    const int lane = tid & 63;
-    double v_[PT];
-    uint32_t pq_[PT];
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {   // one round trip of global loads
-        const int g = tid + r * NT;
-        v_[r] = g < Ng ? P.vals[g] : 0.0;
-    }
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {
-        const int q = tid + r * NT;
-        pq_[r] = q < K ? g_pairs[q] : 0u;
-    }
-    const uint32_t ev = g_off[min(lane, K)];   // lane l: end of level l
-    const int nlev = (int)g_off[K + 1];
-    while_loading();
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {
-        const int g = tid + r * NT;
-        const unsigned long long uv = __builtin_bit_cast(unsigned long long, v_[r]);
-        if (g < Ng) slot[g] = make_uint4((uint32_t)uv, (uint32_t)(uv >> 32), (uint32_t)g, 0u);
-    }
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {
-        const int q = tid + r * NT;
-        if (q < K) pairs[q] = pq_[r];
-    }
-    for (int q = tid + PT * NT; q < K; q += NT) pairs[q] = g_pairs[q];   // injected pair lists longer than XLVL_MAX
-    // the narrow tail (every remaining level <= 64 pairs) is walked by wave 0 alone
-    int ltail = nlev;
-    if (nlev > 0 && nlev <= 64) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)ev, 1, 64);
-        const unsigned long long wide = __ballot(lane < nlev && ev - (lane > 0 ? lo : 0u) > 64u);
-        ltail = wide ? 64 - __builtin_clzll(wide) : 0;
-    }
-    __syncthreads();
-    if (P.ts && tid == 0) P.ts[(size_t)ts_tile * 8 + 5] = wall_clock64();   // staged
-    const uint32_t slot_base = (uint32_t)(size_t)lds;   // LDS byte address of the chain slots
-    // (dist_fun = - only: k_chain_iter_norm does not walk inline for the other entries of the menu — the host sees to it)
-    if (P.mi_uniform) walk_levels<NT, true, FINAL_BARRIER>(P, slot_base, pairs, g_mi, ev, g_off, nlev, ltail, tid);
-    else walk_levels<NT, false, FINAL_BARRIER>(P, slot_base, pairs, g_mi, ev, g_off, nlev, ltail, tid);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -146,7 +146,8 @@ __device__ inline void lds_dma16(const void* gsrc, const uint32_t lds_dst) {
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
-// (the lean exchange walk itself: smm_walk_lean.hpp)
+// (the lean exchange walk itself: smm_walk_lean.hpp; request and commit are written out here, not taken from its staging pieces: with those the
+// kernels' scalar registers were allocated differently, k_chain_iter_norm<4, true> with twice the spills — MEASUREMENTS.md)
 // false (nothing done): this iteration's plan does not fit the form (more than 31 levels), a NaN value is among the chains',
 // or the dynamic LDS does not start at address 0 — the caller runs the 16-byte walk.  The result is in LDS (slots at lds);
 // only wave 0 may read it without a barrier.
@@ -157,8 +158,8 @@ __device__ inline bool exchange_walk_lean(const KParams& P, const int tx, unsign
     const uint32_t* __restrict__ g_offp = P.lv_offp + (size_t)w * LV_OFFP;
     const uint4* __restrict__ g_pairs = (const uint4*)(P.lv_pairs_p + (size_t)w * P.plan_Kp);
     const int lane = tid & 63;
-    const uint32_t Ng4 = (uint32_t)((Ng + 3) & ~3);
-    const uint32_t pbase = 8u * (Ng4 + 4u);   // LDS offset of the pair words
+    const uint32_t Ng4 = lean_Ng4(Ng);
+    const uint32_t pbase = LeanLayout<LEAN_KEYS>::pbase(Ng4);   // LDS offset of the pair words
     // one round trip of 16-byte loads: the slots of the chains 4 tid .. 4 tid + 3, the pair words 4 tid .. and 4 (tid + NT) ..
     // (the arrays are padded; words past the padded length are never looked at)
     // (everything is requested before anything is looked at: a load issued behind the first wait is a round trip of its own)
@@ -175,8 +176,9 @@ __device__ inline bool exchange_walk_lean(const KParams& P, const int tx, unsign
         if (wv * 256 + 128 < Ng) lds_dma16(gs + wv * 128 + 64 + lane, (uint32_t)(wv * 2048 + 1024));
         if (4 * (wv * 64) < P.plan_Kp) lds_dma16(g_pairs + tid, pbase + (uint32_t)(wv * 1024));
         if (4 * (wv * 64 + NT) < P.plan_Kp) lds_dma16(g_pairs + tid + NT, pbase + (uint32_t)((wv + 16) * 1024));
-        const int nlev_d = __builtin_amdgcn_readlane((int)ov, 33);
-        const bool bad = __builtin_amdgcn_readlane((int)ov, 34) == 0 || __builtin_amdgcn_readlane((int)wflags, 0) != 0;
+        const LeanPlanHead head = lean_plan_head(ov);
+        const int nlev_d = head.nlev;
+        const bool bad = !head.fits || __builtin_amdgcn_readlane((int)wflags, 0) != 0;
         const int ltail_d = lean_walk_tail(ov, nlev_d, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (tid == 0) ((uint4*)lds)[2 * (Ng4 / 4)] = make_uint4(1u, 0u, 2u, 0u);   // the two dummy slots: keys 1 < 2, "no swap"
@@ -191,8 +193,9 @@ __device__ inline bool exchange_walk_lean(const KParams& P, const int tx, unsign
     uint4 p0 = make_uint4(0u, 0u, 0u, 0u), p1 = p0;
     if (4 * tid < P.plan_Kp) p0 = g_pairs[tid];
     if (4 * (tid + NT) < P.plan_Kp) p1 = g_pairs[tid + NT];
-    const int nlev = __builtin_amdgcn_readlane((int)ov, 33);
-    if (__builtin_amdgcn_readlane((int)ov, 34) == 0 || __builtin_amdgcn_readlane((int)wflags, 0) != 0 || (uint32_t)(size_t)lds != 0u) return false;
+    const LeanPlanHead head = lean_plan_head(ov);
+    const int nlev = head.nlev;
+    if (!head.fits || __builtin_amdgcn_readlane((int)wflags, 0) != 0 || (uint32_t)(size_t)lds != 0u) return false;
     if (4 * tid < Ng) { ((uint4*)lds)[2 * tid] = s0; ((uint4*)lds)[2 * tid + 1] = s1; }
     if (4 * tid < P.plan_Kp) ((uint4*)(lds + pbase))[tid] = p0;
     if (4 * (tid + NT) < P.plan_Kp) ((uint4*)(lds + pbase))[tid + NT] = p1;
@@ -215,37 +218,19 @@ __device__ inline bool exchange_walk_lean_wide(const KParams& P, const int tx, u
     constexpr int NT = NORM_WG;
     const int Ng = P.Ng;
     const int w = tx - P.plan_t0;
-    const uint32_t* __restrict__ g_offp = P.lv_offp + (size_t)w * LV_OFFP;
-    const uint4* __restrict__ g_pairs = (const uint4*)(P.lv_pairs_p + (size_t)w * P.plan_Kp);
-    const int lane = tid & 63;
-    const uint32_t Ng4 = (uint32_t)((Ng + 3) & ~3);
-    const uint32_t pbase = 16u * (Ng4 + 1u);   // LDS offset of the pair words
-    const uint32_t ov = g_offp[min(lane, LV_OFFP - 1)];   // lane l: first word of level l; lane 33: levels; lane 34: the plan fits
-    constexpr int PT = XLVL_MAX / NT;                     // chains per lane: tid, tid + NT, ... (16-byte LDS writes at a 16-byte lane stride)
-    double v_[PT];
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {
-        const int g = tid + r * NT;
-        v_[r] = g < Ng ? P.vals[g] : 0.0;
-    }
-    uint4 p0 = make_uint4(0u, 0u, 0u, 0u), p1 = p0;
-    if (4 * tid < P.plan_Kp) p0 = g_pairs[tid];
-    if (4 * (tid + NT) < P.plan_Kp) p1 = g_pairs[tid + NT];
-    const int nlev = __builtin_amdgcn_readlane((int)ov, 33);
-    if (__builtin_amdgcn_readlane((int)ov, 34) == 0 || (uint32_t)(size_t)lds != 0u) return false;
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {
-        const int g = tid + r * NT;
-        if (g < Ng) ((uint4*)lds)[g] = make_uint4((uint32_t)__double2loint(v_[r]), (uint32_t)__double2hiint(v_[r]), (uint32_t)g, 0u);
-    }
-    if (4 * tid < P.plan_Kp) ((uint4*)(lds + pbase))[tid] = p0;
-    if (4 * (tid + NT) < P.plan_Kp) ((uint4*)(lds + pbase))[tid + NT] = p1;
-    if (tid == 0) ((uint4*)lds)[Ng4] = make_uint4(0u, 0u, 0u, 0u);   // the dummy pair's slot: 0 - 0 > min_improve is false
-    const int ltail = lean_walk_tail(ov, nlev, lane);
+    const uint32_t Ng4 = lean_Ng4(Ng);
+    LeanPlanRegs<NT, XLVL_MAX> plan;
+    LeanValueRegs<NT, XLVL_MAX> vals;   // chains tid, tid + NT, ... (16-byte LDS writes at a 16-byte lane stride)
+    plan.request_ov(P, w, tid);
+    vals.request(P.vals, 1, Ng, tid);
+    plan.request_pairs(P, w, tid);
+    const LeanPlanHead head = lean_plan_head(plan.ov);
+    if (!head.fits || (uint32_t)(size_t)lds != 0u) return false;
+    vals.commit<LEAN_WIDE>(lds, Ng, tid);
+    const int ltail = plan.commit<LEAN_WIDE>(P, lds, Ng4, tid, head.nlev);
     __syncthreads();
     if (P.ts && tid == 0) P.ts[(size_t)ts_tile * 8 + 5] = wall_clock64();   // staged
-    if (P.lean_unit == 16) lean_walk_levels<NORM_WG, 0, true>(nullptr, 0, pbase, ov, nlev, tid, ltail, P.mi_value);
-    else lean_walk_levels<NORM_WG, 1, true>(nullptr, 0, pbase, ov, nlev, tid, ltail, P.mi_value);
+    lean_walk<NT, LEAN_WIDE>(P.lean_unit, nullptr, 0, Ng4, plan.ov, head.nlev, tid, ltail, P.mi_value);
     return true;
 }
 
@@ -258,25 +243,18 @@ template <int NMAX>   // the largest population the staging loops serve: XLVL_MA
 __device__ inline bool exchange_walk_lean_p2p(const KParams& P, const int tx, unsigned char* lds, const int tid, const int ts_tile) {
     constexpr int NT = NORM_WG;
     constexpr int SR = NMAX / (4 * NT);                                       // rounds of four slots per lane
-    constexpr int PR = (NMAX + 64 * LV_MAXLEV + 4 * NT - 1) / (4 * NT);        // rounds of four pair words per lane
+    using L = LeanLayout<LEAN_KEYS>;
     const int Ng = P.Ng;
     const int w = tx - P.plan_t0;
-    const uint32_t* __restrict__ g_offp = P.lv_offp + (size_t)w * LV_OFFP;
-    const uint4* __restrict__ g_pairs = (const uint4*)(P.lv_pairs_p + (size_t)w * P.plan_Kp);
     const int lane = tid & 63;
-    const uint32_t Ng4 = (uint32_t)((Ng + 3) & ~3);
-    const uint32_t pbase = 8u * (Ng4 + 4u);   // LDS offset of the pair words
+    const uint32_t Ng4 = lean_Ng4(Ng);
     const unsigned char* mine = P.p2p_self;
     const uint4* g_slots = (const uint4*)(mine + p2p_slot_off(P, tx & 1));
-    const uint32_t ov = g_offp[min(lane, LV_OFFP - 1)];   // lane l: first word of level l; lane 33: levels; lane 34: the plan fits
+    LeanPlanRegs<NT, NMAX> plan;
+    plan.request_ov(P, w, tid);
     // (the NaN word carries the publication epoch of the NaN it reports: a word left by an earlier publication — a state since rolled back — means nothing)
     const uint32_t wflags = *(const uint32_t*)(mine + 128 * (size_t)P2P_MAXG + 0 * (size_t)(tid & 1)) == P.p2p_epoch ? 1u : 0u;
-    uint4 p_[PR];
-#pragma unroll
-    for (int r = 0; r < PR; ++r) {
-        const int q4 = tid + r * NT;
-        p_[r] = 4 * q4 < P.plan_Kp ? g_pairs[q4] : make_uint4(0u, 0u, 0u, 0u);
-    }
+    plan.request_pairs(P, w, tid);
     // the slots, past the caches (p2p_load16_sys), all in flight together with the plan words above
     uint4 s_[2 * SR];
     {
@@ -305,8 +283,8 @@ __device__ inline bool exchange_walk_lean_p2p(const KParams& P, const int tx, un
     }
     (void)gave_up;
     if (timed_out) report_error(P, 3, tx + 1, P.offset);   // (everybody goes on to the barriers below; the failure is reported)
-    const int nlev = __builtin_amdgcn_readlane((int)ov, 33);
-    bool form_ok = __builtin_amdgcn_readlane((int)ov, 34) != 0 && __builtin_amdgcn_readfirstlane((int)wflags) == 0 && (uint32_t)(size_t)lds == 0u;
+    const LeanPlanHead head = lean_plan_head(plan.ov);
+    bool form_ok = head.fits && __builtin_amdgcn_readfirstlane((int)wflags) == 0 && (uint32_t)(size_t)lds == 0u;
     {   // a NaN value: its slot says so itself (P2P_KEY_NAN arrives with the tag that validated the word; the window's NaN word, read at
         // the top, may lag behind the slots).  Every wave must decide the same: a byte per wave in the two spare slots behind the dummy pair's
         bool nan_seen = false;
@@ -320,7 +298,7 @@ __device__ inline bool exchange_walk_lean_p2p(const KParams& P, const int tx, un
             }
         }
         const bool wnan = __ballot(nan_seen) != 0ull;
-        if (lane == 0) lds[8u * (Ng4 + 2u) + (uint32_t)(tid >> 6)] = wnan ? (unsigned char)1 : (unsigned char)0;
+        if (lane == 0) lds[L::spare(Ng4) + (uint32_t)(tid >> 6)] = wnan ? (unsigned char)1 : (unsigned char)0;
     }
 #pragma unroll
     for (int r = 0; r < SR; ++r) {
@@ -330,23 +308,16 @@ __device__ inline bool exchange_walk_lean_p2p(const KParams& P, const int tx, un
             ((uint4*)lds)[2 * q + 1] = make_uint4(s_[2 * r + 1].x, s_[2 * r + 1].y & 0xffffu, s_[2 * r + 1].z, s_[2 * r + 1].w & 0xffffu);
         }
     }
-#pragma unroll
-    for (int r = 0; r < PR; ++r) {
-        const int q4 = tid + r * NT;
-        if (4 * q4 < P.plan_Kp) ((uint4*)(lds + pbase))[q4] = p_[r];
-    }
-    if (tid == 0) ((uint4*)lds)[2 * (Ng4 / 4)] = make_uint4(1u, 0u, 2u, 0u);   // the two dummy slots: keys 1 < 2, "no swap"
-    const int ltail = lean_walk_tail(ov, nlev, lane);
+    const int ltail = plan.template commit<LEAN_KEYS>(P, lds, Ng4, tid, head.nlev);
     __syncthreads();
     if (P.ts && tid == 0) P.ts[(size_t)ts_tile * 8 + 5] = wall_clock64();   // staged
     {
-        const uint4 nf = *(const uint4*)(lds + 8u * (Ng4 + 2u));   // the 16 waves' bytes
+        const uint4 nf = *(const uint4*)(lds + L::spare(Ng4));   // the 16 waves' bytes
         if ((nf.x | nf.y | nf.z | nf.w) != 0u) form_ok = false;
     }
     if (!form_ok) return false;   // (wave-uniform AND the same in every wave: the plan is what it is for the whole launch, the NaN bytes are read behind the barrier)
     const P2PWalkValues values{P, tx};
-    if (NMAX <= XLVL_MAX || P.lean_unit == 8) lean_walk_levels<NORM_WG, 0, false, P2PWalkValues>(nullptr, 1, pbase, ov, nlev, tid, ltail, 0.0, values);
-    else lean_walk_levels<NORM_WG, 1, false, P2PWalkValues>(nullptr, 1, pbase, ov, nlev, tid, ltail, 0.0, values);
+    lean_walk<NT, LEAN_KEYS, P2PWalkValues, NMAX <= XLVL_MAX>(P.lean_unit, nullptr, 1, Ng4, plan.ov, head.nlev, tid, ltail, 0.0, values);
     return true;
 }
 

@@ -30,7 +30,7 @@ constexpr int PG_TRIES = 2;        // proposal tries whose normals are made ahea
 
 __host__ __device__ inline int persist_gen_rngw(int np) { return (1 + PG_TRIES * np + 1) & ~1; }
 __host__ __device__ inline size_t persist_gen_smem_bytes(int Ng, int np, int RW, int HW) {
-    const size_t slots = (size_t)(((Ng + 3) & ~3) + 4) * 8;
+    const size_t slots = LeanLayout<LEAN_KEYS>::slot_bytes(Ng);
     const size_t lists = 2 * (size_t)CONE_LEVELS * 64 * 4 + 2 * (size_t)CONE_GCAP * 2 + 4 * 16 * 4;
     const size_t dbl = (size_t)PG_CT * PG_MAXP + (size_t)PG_CT * PR_STW + 2 * (size_t)PG_CT * RW + 2 * (size_t)PG_CT * persist_gen_rngw(np) + 2 * (size_t)PG_CT * HW +
                        5 * PG_MAXP + 16;
@@ -57,9 +57,9 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistArgs
     const int RNGW = persist_gen_rngw(np);
     const int NPC = (RW + 3) / 4;                     // 16-byte pieces of a record per lane of a chain's quad
     const int NPH = HW / 2;
-    const int US = 8 * (Ng4 + 2) <= 65536 ? 0 : 1;   // pair words hold the slots' byte offsets, halved where 16 bits would not reach (smm_walk_lean.hpp)
+    const int US = LeanLayout<LEAN_KEYS>::unit4((uint32_t)Ng4) == 8 ? 0 : 1;   // pair words hold the slots' byte offsets, halved where 16 bits would not reach (smm_walk_lean.hpp)
     // ---- LDS ----
-    const uint32_t pbase = 8u * (uint32_t)(Ng4 + 4);
+    const uint32_t pbase = LeanLayout<LEAN_KEYS>::pbase((uint32_t)Ng4);
     const uint32_t gbase = pbase + 2u * CONE_LEVELS * 64 * 4;
     const uint32_t hbase = gbase + 2u * CONE_GCAP * 2;
     uint2* slots = (uint2*)lds;
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(1024, 4) void k_chain_persist_gen(const PersistArgs
         const uint32_t* hd = s_hdr + (tx & 3) * 16;
         const int nsub1 = (int)(hd[0] & 0xffffu);
         const uint32_t unit = 8u >> US;
-        const uint32_t dummy = (unit * (uint32_t)Ng4) | ((unit * (uint32_t)(Ng4 + 1)) << 16);
+        const uint32_t dummy = LeanLayout<LEAN_KEYS>::dummy_word(unit, (uint32_t)Ng4);
         uint32_t* pw = (uint32_t*)(lds + pbase) + (tx & 1) * (CONE_LEVELS * 64);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {

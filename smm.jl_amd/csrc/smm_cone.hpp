@@ -29,8 +29,9 @@ __device__ inline bool exchange_walk_tile_cone(const KParams& P, const int tx, u
     const int w = tx - P.plan_t0;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t Ng4 = (uint32_t)((Ng + 3) & ~3);
-    const uint32_t pbase = 8u * (Ng4 + 4u);               // LDS offset of the pair words (the key walk's layout)
+    using L = LeanLayout<LEAN_KEYS>;                      // (the key walk's layout)
+    const uint32_t Ng4 = lean_Ng4(Ng);
+    const uint32_t pbase = L::pbase(Ng4);
     // everything that depends on nothing is requested first
     const uint32_t okw = P.cone_ok[w];
     const uint32_t wflags = P.walk_flags[0];
@@ -46,7 +47,7 @@ __device__ inline bool exchange_walk_tile_cone(const KParams& P, const int tx, u
     if (okw == 0u || wflags != 0u || (uint32_t)(size_t)lds != 0u) return false;
     const int nsub = __builtin_amdgcn_readlane((int)hv, 0) & 0xffff;   // (high half: the persistent kernel's gather count)
     uint2* slot = (uint2*)lds;
-    const uint32_t dummy = ((8u >> US) * Ng4) | (((8u >> US) * (Ng4 + 1u)) << 16);   // the two slots behind the chains': keys 1 < 2, "no swap"
+    const uint32_t dummy = L::dummy_word(8u >> US, Ng4);   // the two slots behind the chains': keys 1 < 2, "no swap"
 #pragma unroll
     for (int r = 0; r < RND; ++r) {
         const int s = wv + NWV * r;
@@ -62,16 +63,12 @@ __device__ inline bool exchange_walk_tile_cone(const KParams& P, const int tx, u
         }
     }
     if (tid < P.cone_ct) slot[c_own] = own;                // (chains without a pair: their slot is the result)
-    if (tid == NT - 1) { slot[Ng4] = make_uint2(1u, 0u); slot[Ng4 + 1] = make_uint2(2u, 0u); }
+    if (tid == NT - 1) L::put_dummies(lds, Ng4);
     __syncthreads();
     if (P.ts && tid == 0) P.ts[(size_t)ts_tile * 8 + 5] = wall_clock64();   // staged
     if (tid < 64) lean_walk_levels<64, US>(P.vals, 1, pbase, (uint32_t)(64 * lane), nsub, tid, 0);
     __syncthreads();   // (the walk was wave 0's alone; the control waves of the tiles read now)
-    if (valid) {
-        const uint32_t meta = slot[gc].y;
-        const uint32_t partner = lean_partner<US>(lds, pbase, meta, (uint32_t)gc);
-        xr = (unsigned long long)(meta & 0xffffu) | ((unsigned long long)partner << 32);
-    }
+    if (valid) xr = lean_result<LEAN_KEYS>(lds, Ng4, 8 >> US, (uint32_t)gc);
     if (gc2 >= 0) *src2 = slot[gc2].y & 0xffffu;
     __syncthreads();   // (from here on the tile's blocks may overwrite the pair list)
     return true;

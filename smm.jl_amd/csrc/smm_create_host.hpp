@@ -275,7 +275,7 @@ void choose_forms(Ctx* c, int objective_id, bool ask = true, int per_cu = -1) {
     if (F.lean_plan) {
         P.lean_wide = F.lean_wide ? 1 : 0;
         P.plan_Kp = lean_walk_Kp(P.plan_K);
-        P.lean_unit = F.lean_wide ? lean_wide_unit(P.Ng) : lean_walk_unit(P.Ng);
+        P.lean_unit = F.lean_wide ? LeanLayout<LEAN_WIDE>::unit(P.Ng) : LeanLayout<LEAN_KEYS>::unit(P.Ng);
     }
     if (F.cone_tiles) { P.cone_tiles = F.cone_tiles; P.cone_ct = F.cone_ct; }
 }

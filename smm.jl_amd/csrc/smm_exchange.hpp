@@ -152,51 +152,22 @@ __global__ __launch_bounds__(LWG) void k_exch_resolve_lvl(const KParams P, const
     }
     for (int q = tid + PT * LWG; q < K; q += LWG) { pairs[q] = g_pairs[q]; mi[q] = g_mi[q]; }  // K > XLVL_MAX: injected long pair lists
     // Level ends: lane l of every wave holds the end of level l (one coalesced load, read back with
-    // v_readlane).  The level loop stays ROLLED on purpose: the kernel runs once per iteration on a CU whose
+    // v_readlane).  The level loop (slot_walk_levels) stays ROLLED on purpose: the kernel runs once per iteration on a CU whose
     // instruction cache has been flushed by the chain kernel in between, so every byte of straight-line code
     // is an instruction-fetch miss.
-    auto level_end = [&](int l) -> uint32_t {
-        const int lc = min(l, nlev - 1);
-        return lc < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)ev, lc) : g_off[lc];
-    };
     const int ltail = nlev;
     __syncthreads();
     XTS(1);
-    uint32_t b = 0;
-    int lvc = 0;
-    unsigned long long* lts = (unsigned long long*)(pairs + K + (K & 1));   // [64] level stamps (debug)
+    struct Debug {   // the debug switches (dbg & 32: no pairs; & 64: no barriers) and the level stamps
+        const KParams& P; unsigned long long* lts; const unsigned long long cyc0; const int tid; int lvc;
+        __device__ __forceinline__ bool skip_pairs() const { return (P.dbg & 32) != 0; }
+        __device__ __forceinline__ bool skip_barrier() const { return (P.dbg & 64) != 0; }
+        __device__ __forceinline__ void level_done() { if (P.ts && tid == 0) { lts[lvc & 31] = clock64() - cyc0; ++lvc; } }
+    } dbg{P, (unsigned long long*)(pairs + K + (K & 1)), cyc0, tid, 0};   // lts[64]: level stamps (debug)
+    unsigned long long* lts = dbg.lts;
     if (P.ts && tid == 0) lts[63] = clock64() - cyc0;
-    uint32_t e = nlev > 0 ? level_end(0) : 0u;
-    uint32_t e2 = nlev > 0 ? level_end(1) : 0u;
-    uint32_t pw = (b + tid < e) ? pairs[b + tid] : 0u;
-    double m = (b + tid < e) ? mi[b + tid] : 0.0;
-    // (the loop twice: the default dist_fun `-` pays nothing for the menu)
-    auto levels = [&](auto gen) {
-        const int dk = decltype(gen)::value ? P.dist_fun : 0;
-#pragma clang loop unroll(disable)
-        for (int l = 0; l < ltail; ++l) {
-            const uint32_t e3 = level_end(l + 2);
-            // this thread's first pair of the next level (LDS) is fetched while this level runs
-            const uint32_t pw2 = (e + tid < e2) ? pairs[e + tid] : 0u;
-            const double m2 = (e + tid < e2) ? mi[e + tid] : 0.0;
-            for (uint32_t pos = b + tid; pos < e && !(P.dbg & 32); pos += LWG) {
-                if (pos != b + tid) { pw = pairs[pos]; m = mi[pos]; }
-                const uint32_t i = pw & 0xffffu, j = pw >> 16;
-                const XSlot si = slot[i], sj = slot[j];
-                if (dist_fun_eval(dk, si.val, sj.val) > m) {   // dist_fun (default -), AlgoBGP.jl:688
-                    XSlot ni, nj;                           // swap_ev_ij!, :739-744; set_exchanged!, :747-748
-                    ni.val = sj.val; ni.src = sj.src; ni.partner = j + 1;
-                    nj.val = si.val; nj.src = si.src; nj.partner = i + 1;
-                    slot[i] = ni;
-                    slot[j] = nj;
-                }
-            }
-            b = e; e = e2; e2 = e3; pw = pw2; m = m2;
-            if (!(P.dbg & 64)) __syncthreads();
-            if (P.ts && tid == 0) { lts[lvc & 31] = clock64() - cyc0; ++lvc; }
-        }
-    };
-    if (P.dist_fun != 0) levels(std::true_type{}); else levels(std::false_type{});
+    slot_walk_levels<LWG, false>(P.dist_fun, SlotWalkPlan{pairs, g_off, nullptr, ev, nlev, nlev}, SlotsAoS{slot}, WalkThr{mi, false, 0.0}, tid, dbg);
+    const int lvc = dbg.lvc;
     if (P.ts && tid == 0) {
         P.ts[(size_t)8 * 60000 + 15] = lts[63];
         for (int l = 0; l < min(lvc, 32); ++l) P.ts[(size_t)8 * 60000 + 16 + l] = lts[l];
@@ -251,40 +222,8 @@ __device__ inline void resolve_lvl_soa_body(const KParams& P, const int t, const
         const int q = tid + r * LWG;
         if (q < K) pairs[q] = pq_[r];
     }
-    auto level_end = [&](int l) -> uint32_t {
-        const int lc = min(l, nlev - 1);
-        return lc < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)ev, lc) : g_off[lc];
-    };
     __syncthreads();
-    uint32_t b = 0;
-    uint32_t e = nlev > 0 ? level_end(0) : 0u;
-    uint32_t e2 = nlev > 0 ? level_end(1) : 0u;
-    uint32_t pw = (b + tid < e) ? pairs[b + tid] : 0u;
-    double m = mi_u ? mi_v : ((b + tid < e) ? g_mi[b + tid] : 0.0);
-    // (the loop twice: the default dist_fun `-` pays nothing for the menu)
-    auto levels = [&](auto gen) {
-        const int dk = decltype(gen)::value ? P.dist_fun : 0;
-#pragma clang loop unroll(disable)
-        for (int l = 0; l < nlev; ++l) {
-            const uint32_t e3 = level_end(l + 2);
-            const uint32_t pw2 = (e + tid < e2) ? pairs[e + tid] : 0u;
-            const double m2 = mi_u ? mi_v : ((e + tid < e2) ? g_mi[e + tid] : 0.0);
-            for (uint32_t pos = b + tid; pos < e; pos += LWG) {
-                if (pos != b + tid) { pw = pairs[pos]; m = mi_u ? mi_v : g_mi[pos]; }
-                const uint32_t i = pw & 0xffffu, j = pw >> 16;
-                const double vi = val[i], vj = val[j];
-                const uint32_t si = sp[i], sj = sp[j];
-                if (dist_fun_eval(dk, vi, vj) > m) {    // dist_fun (default -), AlgoBGP.jl:688
-                    val[i] = vj; val[j] = vi;               // swap_ev_ij!, :739-744; set_exchanged!, :747-748
-                    sp[i] = (sj & 0xffffu) | ((j + 1) << 16);
-                    sp[j] = (si & 0xffffu) | ((i + 1) << 16);
-                }
-            }
-            b = e; e = e2; e2 = e3; pw = pw2; m = m2;
-            __syncthreads();
-        }
-    };
-    if (P.dist_fun != 0) levels(std::true_type{}); else levels(std::false_type{});
+    slot_walk_levels<LWG, false>(P.dist_fun, SlotWalkPlan{pairs, g_off, nullptr, ev, nlev, nlev}, SlotsSoA{val, sp}, WalkThr{g_mi, mi_u, mi_v}, tid);
     for (int g = tid; g < Ng; g += LWG) {
         const uint32_t s_ = sp[g];
         P.xres[g] = (unsigned long long)(s_ & 0xffffu) | ((unsigned long long)(s_ >> 16) << 32);
@@ -303,109 +242,54 @@ __global__ __launch_bounds__(LWG) void k_exch_resolve_lvl_soa(const KParams P, c
 // (as a function, in the same launch) when this iteration's plan has more than 31 levels or a chain value is NaN.
 __global__ __launch_bounds__(XWG) void k_exch_resolve_lean(const KParams P, const int t, const double* __restrict__ gathered) {
     extern __shared__ __attribute__((aligned(16))) unsigned char xsm[];
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int Ng = P.Ng;
     const int w = t - P.plan_t0;
-    const uint32_t* __restrict__ g_offp = P.lv_offp + (size_t)w * LV_OFFP;
-    const uint4* __restrict__ g_pairs = (const uint4*)(P.lv_pairs_p + (size_t)w * P.plan_Kp);
     const double* __restrict__ vsrc = gathered ? gathered : P.vals;
     const int vstride = gathered ? P.RW : 1;
-    const uint32_t Ng4 = (uint32_t)((Ng + 3) & ~3);
-    const uint32_t pbase = 8u * (Ng4 + 4u);
-    constexpr int PT = XLDS_MAX / XWG;                 // chains per lane
-    constexpr int PR = (XLDS_MAX + 64 * LV_MAXLEV + 4 * XWG - 1) / (4 * XWG);   // rounds of 16-byte loads for the pair words
+    const uint32_t Ng4 = lean_Ng4(Ng);
     XTS(0);
-    const uint32_t ov = g_offp[min(lane, LV_OFFP - 1)];   // lane l: first word of level l; lane 33: levels; lane 34: the plan fits
-    double v_[PT];
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {   // one round trip: the chains' values (a strided read of the gathered records) and the pair words
-        const int g = tid + r * XWG;
-        v_[r] = g < Ng ? vsrc[(size_t)g * vstride] : 0.0;
-    }
-    uint4 p_[PR];
-#pragma unroll
-    for (int r = 0; r < PR; ++r) {
-        const int q4 = tid + r * XWG;
-        p_[r] = 4 * q4 < P.plan_Kp ? g_pairs[q4] : make_uint4(0u, 0u, 0u, 0u);
-    }
-    if (P.lean_wide) {   // one min_improve > 0 (or NaN): 16-byte slots of values (smm_walk_lean.hpp)
-        const int nlev = __builtin_amdgcn_readlane((int)ov, 33);
-        if (__builtin_amdgcn_readlane((int)ov, 34) == 0 || (uint32_t)(size_t)xsm != 0u) { resolve_lvl_soa_body<XWG>(P, t, gathered, xsm); return; }
-        const uint32_t pbw = 16u * (Ng4 + 1u);
-        uint4* slot = (uint4*)xsm;
-#pragma unroll
-        for (int r = 0; r < PT; ++r) {
-            const int g = tid + r * XWG;
-            if (g < Ng) slot[g] = make_uint4((uint32_t)__double2loint(v_[r]), (uint32_t)__double2hiint(v_[r]), (uint32_t)g, 0u);
-        }
-#pragma unroll
-        for (int r = 0; r < PR; ++r) {
-            const int q4 = tid + r * XWG;
-            if (4 * q4 < P.plan_Kp) ((uint4*)(xsm + pbw))[q4] = p_[r];
-        }
-        if (tid == 0) slot[Ng4] = make_uint4(0u, 0u, 0u, 0u);   // the dummy pair's slot: 0 - 0 > min_improve is false
-        const int ltail = lean_walk_tail(ov, nlev, lane);
+    // one round trip: the chains' values (a strided read of the gathered records) and the pair words
+    LeanPlanRegs<XWG, XLDS_MAX> plan;
+    LeanValueRegs<XWG, XLDS_MAX> vals;
+    plan.request_ov(P, w, tid);
+    vals.request(vsrc, vstride, Ng, tid);
+    plan.request_pairs(P, w, tid);
+    // (LAY: a compile-time form of P.lean_wide)
+    auto walk = [&](auto lay, const int nlev) {
+        constexpr int LAY = decltype(lay)::value;
+        vals.template commit<LAY>(xsm, Ng, tid);
+        const int ltail = plan.template commit<LAY>(P, xsm, Ng4, tid, nlev);
         __syncthreads();
         XTS(1);
-        if (P.lean_unit == 16) lean_walk_levels<XWG, 0, true>(nullptr, 0, pbw, ov, nlev, tid, ltail, P.mi_value);
-        else lean_walk_levels<XWG, 1, true>(nullptr, 0, pbw, ov, nlev, tid, ltail, P.mi_value);
+        lean_walk<XWG, LAY>(P.lean_unit, vsrc, vstride, Ng4, plan.ov, nlev, tid, ltail, P.mi_value);
         __syncthreads();
         XTS(2);
 #pragma unroll
-        for (int r = 0; r < PT; ++r) {
+        for (int r = 0; r < vals.PT; ++r) {   // (unrolled: the chains' dependent LDS reads overlap)
             const int g = tid + r * XWG;
-            if (g < Ng) {
-                const uint32_t meta = slot[g].z;
-                const uint32_t partner = P.lean_unit == 16 ? lean_partner<0, 4>(xsm, pbw, meta, (uint32_t)g) : lean_partner<1, 4>(xsm, pbw, meta, (uint32_t)g);
-                P.xres[g] = (unsigned long long)(meta & 0xffffu) | ((unsigned long long)partner << 32);
-            }
+            if (g < Ng) P.xres[g] = lean_result<LAY>(xsm, Ng4, P.lean_unit, (uint32_t)g);
         }
         XTS(4);
+    };
+    if (P.lean_wide) {   // one min_improve > 0 (or NaN): 16-byte slots of values (smm_walk_lean.hpp)
+        const LeanPlanHead head = lean_plan_head(plan.ov);
+        if (!head.fits || (uint32_t)(size_t)xsm != 0u) { resolve_lvl_soa_body<XWG>(P, t, gathered, xsm); return; }
+        walk(std::integral_constant<int, LEAN_WIDE>{}, head.nlev);
         return;
     }
-    uint32_t* s_nan = (uint32_t*)(xsm + 8u * (Ng4 + 2u));   // (a spare slot behind the dummy pair's)
+    uint32_t* s_nan = (uint32_t*)(xsm + LeanLayout<LEAN_KEYS>::spare(Ng4));   // (a spare slot behind the dummy pair's)
     if (tid == 0) *s_nan = 0u;
     __syncthreads();
-    bool nan = false;
-#pragma unroll
-    for (int r = 0; r < PT; ++r) nan = nan || v_[r] != v_[r];
-    if (nan) *s_nan = 1u;
-    const int nlev = __builtin_amdgcn_readlane((int)ov, 33);
-    const bool fits = __builtin_amdgcn_readlane((int)ov, 34) != 0 && (uint32_t)(size_t)xsm == 0u;
+    if (vals.any_nan()) *s_nan = 1u;
+    const LeanPlanHead head = lean_plan_head(plan.ov);
+    const bool fits = head.fits && (uint32_t)(size_t)xsm == 0u;
     __syncthreads();
     const bool has_nan = *s_nan != 0u;
     __syncthreads();
     if (!fits || has_nan) { resolve_lvl_soa_body<XWG>(P, t, gathered, xsm); return; }
-    uint2* slot = (uint2*)xsm;
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {
-        const int g = tid + r * XWG;
-        if (g < Ng) slot[g] = make_uint2(order_key32(v_[r]), (uint32_t)g);
-    }
-#pragma unroll
-    for (int r = 0; r < PR; ++r) {
-        const int q4 = tid + r * XWG;
-        if (4 * q4 < P.plan_Kp) ((uint4*)(xsm + pbase))[q4] = p_[r];
-    }
-    if (tid == 0) { slot[Ng4] = make_uint2(1u, 0u); slot[Ng4 + 1] = make_uint2(2u, 0u); }   // the dummy pair's slots: keys 1 < 2, "no swap"
-    const int ltail = lean_walk_tail(ov, nlev, lane);
-    __syncthreads();
-    XTS(1);
-    if (P.lean_unit == 8) lean_walk_levels<XWG, 0>(vsrc, vstride, pbase, ov, nlev, tid, ltail);
-    else lean_walk_levels<XWG, 1>(vsrc, vstride, pbase, ov, nlev, tid, ltail);
-    __syncthreads();
-    XTS(2);
-#pragma unroll
-    for (int r = 0; r < PT; ++r) {
-        const int g = tid + r * XWG;
-        if (g < Ng) {
-            const uint32_t meta = slot[g].y;
-            const uint32_t partner = P.lean_unit == 8 ? lean_partner<0>(xsm, pbase, meta, (uint32_t)g) : lean_partner<1>(xsm, pbase, meta, (uint32_t)g);
-            P.xres[g] = (unsigned long long)(meta & 0xffffu) | ((unsigned long long)partner << 32);
-        }
-    }
-    XTS(4);
-    if (P.ts && tid == 0) P.ts[(size_t)8 * 60000 + 7] = (unsigned long long)nlev;
+    walk(std::integral_constant<int, LEAN_KEYS>{}, head.nlev);
+    if (P.ts && tid == 0) P.ts[(size_t)8 * 60000 + 7] = (unsigned long long)head.nlev;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -20,10 +20,11 @@ int persist_tiles_rank(const Forms& F, int N) {
     const int ct = F.persist == PERSIST_TILE ? PT_CT : NORM_CT;
     return F.persist == PERSIST_GEN ? N / PG_CT : (N + ct - 1) / ct;
 }
-size_t key_slot_bytes(int Ng) { return (size_t)(((Ng + 3) & ~3) + 4) * 8; }   // the key walk's 8-byte chain slots
+size_t key_slot_bytes(int Ng) { return LeanLayout<LEAN_KEYS>::slot_bytes(Ng); }   // the key walk's 8-byte chain slots
+size_t lean_bytes(int Ng, int K, bool wide) { return wide ? LeanLayout<LEAN_WIDE>::bytes(Ng, K) : LeanLayout<LEAN_KEYS>::bytes(Ng, K); }   // slots and padded pair list of a lean walk
 // what k_chain_iter_norm keeps in front of its tile for the inline walk: pair list NOT overlaid; room for either walk (16-byte slots, or the lean walk)
 size_t norm_walk_bytes(int Ng, int K, bool wide) {
-    return std::max(walk_slot_bytes(Ng) + (((size_t)K * 4 + 15) & ~(size_t)15), ((wide ? lean_wide_bytes(Ng, K) : lean_walk_bytes(Ng, K)) + 15) & ~(size_t)15);
+    return std::max(walk_slot_bytes(Ng) + (((size_t)K * 4 + 15) & ~(size_t)15), (lean_bytes(Ng, K, wide) + 15) & ~(size_t)15);
 }
 size_t norm_smem(const Ctx* c, const Forms& F) {   // k_chain_iter_norm: [walk: chain slots | pair list] theta, partial sums, parked state
     const size_t b = (size_t)F.tile_off * sizeof(double) + norm_tile_doubles(c->P.np) * sizeof(double);
@@ -36,14 +37,14 @@ size_t tile_smem(const Ctx* c, const Forms& F, int ct, int tpw = 1) {   // dynam
     if (!F.inline_walk) return tiles;
     if (F.dense_keys) return std::max(tiles, key_slot_bytes(c->P.Ng) + std::max((size_t)CONE_LEVELS * 64 * 4, Kp4));
     if (F.gen_keys) return key_slot_bytes(c->P.Ng) + std::max(tiles, Kp4);
-    return F.gen_lean ? tile_lean_slot_bytes(c->P.Ng) + std::max(tiles, Kp4) : walk_slot_bytes(c->P.Ng) + std::max(tiles, (size_t)c->P.plan_K * 4);
+    return F.gen_lean ? LeanLayout<LEAN_TILE16>::slot_bytes(c->P.Ng) + std::max(tiles, Kp4) : walk_slot_bytes(c->P.Ng) + std::max(tiles, (size_t)c->P.plan_K * 4);
 }
 size_t cone_chains_lds_bytes(int Ng) { return (size_t)Ng * 4; }   // k_cone_chains: a word per chain
 size_t plan_lds_bytes(int Ng, int K) { return (size_t)(Ng + 2) * 4 + (size_t)K * 8 + (size_t)K * 4 + 128 + 16; }
 size_t resolve_lds_bytes(int Ng) { return (size_t)Ng * 16 + 16; }   // (the ticket kernel: test build only)
 size_t resolve_lvl_soa_bytes(int Ng, int K) { return (size_t)Ng * 12 + (size_t)K * 4 + 16; }
 size_t resolve_lvl_bytes(int Ng, int K) { return (size_t)Ng * 16 + (size_t)K * 12 + 64 * 8 + 64; }
-size_t resolve_lean_bytes(int Ng, int K, bool wide) { return std::max(wide ? lean_wide_bytes(Ng, K) : lean_walk_bytes(Ng, K), resolve_lvl_soa_bytes(Ng, K)); }
+size_t resolve_lean_bytes(int Ng, int K, bool wide) { return std::max(lean_bytes(Ng, K, wide), resolve_lvl_soa_bytes(Ng, K)); }
 // the rules select_forms states once
 bool one_threshold(const KParams& P) { return P.mi_uniform && !(P.mi_value < 0.0); }   // one threshold >= 0 (or NaN: nothing ever swaps) for all chains
 bool one_threshold_nonzero(const KParams& P) { return one_threshold(P) && P.mi_value != 0.0; }   // ... and not 0: the walks on 16-byte slots of values
@@ -89,7 +90,7 @@ Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
     F.tpw = (F.inline_walk && !F.norm_fast && (is_sim(c->obj) ? F.ct == 8 : c->obj != SMM_OBJ_DENSE) && ((N + 7) / 8 > n_cus || H.tpw == 2) &&
              H.tpw != 1 && tile_smem(c, F, tile_ct, 2) <= LDS_CU) ? 2 : 1;
     // k_chain_iter on the lean walk (16-byte slots, padded pair list) where its somewhat larger LDS keeps the same budget
-    const Forms lean = walking(false, false, true, F.tpw, tile_lean_slot_bytes(Ng));
+    const Forms lean = walking(false, false, true, F.tpw, LeanLayout<LEAN_TILE16>::slot_bytes(Ng));
     if (F.inline_walk && !F.norm_fast && one_threshold(P) && minus && K <= XLDS_MAX && !H.key_walk_off && (mi0 || wide_fits) &&
         tile_smem(c, lean, tile_ct, F.tpw) <= (F.tpw == 2 ? LDS_CU : LDS_HALF)) F = lean;
     // single shards of 4096 < N <= 8192 chains without a simulation (C4): the key walk inline, two 16-chain tiles per workgroup
@@ -99,7 +100,7 @@ Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
     // the dense objective (C5): its tile fills a CU's LDS, so the key walk's slots and lists lie UNDER the tile's blocks
     const Forms under = walking(true, true, false, 1, 0);
     if (!F.inline_walk && !H.inline_walk_off && !H.dense_keys_off && c->obj == SMM_OBJ_DENSE && N == Ng && Ng >= 2 && Ng <= XLVL_MAX && K <= XLVL_MAX &&
-        lds && mi0 && minus && !H.key_walk_off && lean_walk_unit(Ng) == 8 && tile_smem(c, under, 16, 1) <= LDS_CU) F = under;
+        lds && mi0 && minus && !H.key_walk_off && LeanLayout<LEAN_KEYS>::unit(Ng) == 8 && tile_smem(c, under, 16, 1) <= LDS_CU) F = under;
     // the candidates for the cone tables and the persistent kernels.  The workgroups' cones of the inline key walk (smm_cone.hpp):
     const bool want_cone = F.gen_keys && !H.no_cone && (F.dense_keys ? (N % 16 == 0 && N / 16 <= 256) : (F.tpw == 2 && N % 32 == 0 && N / 32 <= 256));
     const int cone_ct = F.dense_keys ? 16 : 32;

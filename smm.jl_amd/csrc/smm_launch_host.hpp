@@ -370,7 +370,7 @@ void launch_resolve_p(Ctx* c, const KParams& P_in, int t, const double* gathered
 void launch_resolve(Ctx* c, int t, const double* gathered) { launch_resolve_p(c, c->P, t, gathered); }
 
 // ---- the p2p form of the sharded iteration (smm_p2p.hpp, include/smmhip.h) ----
-size_t p2p_walk_bytes(const Ctx* c) { return (lean_walk_bytes(c->P.Ng, c->P.plan_K) + 15) & ~(size_t)15; }
+size_t p2p_walk_bytes(const Ctx* c) { return (LeanLayout<LEAN_KEYS>::bytes(c->P.Ng, c->P.plan_K) + 15) & ~(size_t)15; }
 void launch_chain_iter_norm_p2p(Ctx* c, int t, int flags) {
     KParams P = c->P;
     point_values(c, P, t - 1, t);

@@ -274,9 +274,9 @@ __global__ __launch_bounds__(XWG) void k_exch_plan(const KParams P, const int t0
     __syncthreads();
     const uint32_t sc8 = (uint32_t)P.lean_unit;   // a word holds 8 i (byte offsets of the 8-byte slots) or, for more than 8190 chains, 4 i
     if (lean) {
-        const uint32_t Ng4 = (uint32_t)((Ng + 3) & ~3);
+        const uint32_t Ng4 = lean_Ng4(Ng);
         // two slots behind the chains' whose keys say "no swap"; wide form: one slot, value 0, as both sides
-        const uint32_t dummy = P.lean_wide ? (sc8 * Ng4) * 0x10001u : (sc8 * Ng4) | ((sc8 * (Ng4 + 1u)) << 16);
+        const uint32_t dummy = P.lean_wide ? LeanLayout<LEAN_WIDE>::dummy_word(sc8, Ng4) : LeanLayout<LEAN_KEYS>::dummy_word(sc8, Ng4);
         for (uint32_t q = tid; q < s_pst[nlev + 1]; q += XWG) o_pp[q] = dummy;
     }
     __syncthreads();
@@ -409,7 +409,9 @@ __global__ __launch_bounds__(XWG) void k_exch_plan(const KParams P, const int t0
                             if ((int)(sub >> 2) == y) hw[1 + y] |= cnt_s << (8u * (sub & 3u));
                     }
             }
-            hw[0] = sub < (uint32_t)CONE_LEVELS ? sub : (uint32_t)CONE_LEVELS;
+            // (a cone past its caps is listed EMPTY: the persistent kernels walk the iteration before the launch is given up, and a cut list would
+            // name chains whose slots nobody gathered — what the LDS held before the launch would become a record's index)
+            hw[0] = sub <= (uint32_t)CONE_LEVELS ? sub : 0u;
             if (sub > (uint32_t)CONE_LEVELS) atomicOr(&s_bad, 1u);
 #pragma unroll
             for (int x = 0; x < CONE_HDRW; ++x) o_hdr[(size_t)(b0 + b) * CONE_HDRW + x] = hw[x];
@@ -460,8 +462,8 @@ __global__ __launch_bounds__(XWG) void k_exch_plan(const KParams P, const int t0
             __syncthreads();
             for (int b = tid; b < nb; b += XWG) {
                 const uint32_t g = gcnt[b];
-                if (g > (uint32_t)CONE_GCAP) atomicOr(&s_bad, 1u);
-                o_hdr[(size_t)(b0 + b) * CONE_HDRW] |= (g < (uint32_t)CONE_GCAP ? g : (uint32_t)CONE_GCAP) << 16;
+                if (g > (uint32_t)CONE_GCAP) { atomicOr(&s_bad, 1u); o_hdr[(size_t)(b0 + b) * CONE_HDRW] = 0u; }   // (listed empty, as above)
+                else o_hdr[(size_t)(b0 + b) * CONE_HDRW] |= g << 16;
             }
         }
     }

@@ -27,15 +27,49 @@
 // the two reads).  LDS: slots uint4[Ng4 + 1] | pair words u32[plan_Kp]; up to ~7400 chains fit the 160 KB.
 // ------------------------------------------------------------------------------------------
 __host__ __device__ inline int lean_walk_Kp(int K) { return (K + 64 * LV_MAXLEV + 3) & ~3; }
-__host__ __device__ inline size_t lean_walk_bytes(int Ng, int K) { return (size_t)(((Ng + 3) & ~3) + 4) * 8 + (size_t)lean_walk_Kp(K) * 4; }
-__host__ __device__ inline int lean_walk_unit(int Ng) { return 8 * (((Ng + 3) & ~3) + 2) <= 65536 ? 8 : 4; }   // KParams::lean_unit
-__host__ __device__ inline size_t lean_wide_bytes(int Ng, int K) { return (size_t)(((Ng + 3) & ~3) + 1) * 16 + (size_t)lean_walk_Kp(K) * 4; }
-__host__ __device__ inline int lean_wide_unit(int Ng) { return 16 * (((Ng + 3) & ~3) + 1) <= 65536 ? 16 : 8; }    // KParams::lean_unit, wide form (8: up to 8188 chains)
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-// k_chain_iter's inline walk on this form: 16-byte slots whatever the threshold, two zero-valued dummy slots (the plan may be the
-// key form's, whose dummy pair names two slots)
-__host__ __device__ inline size_t tile_lean_slot_bytes(int Ng) { return (size_t)(((Ng + 3) & ~3) + 2) * 16; }
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+// ------------------------------------------------------------------------------------------
+// The three slot layouts, each number once.  LDS from address 0: slots[Ng4 + PAD] | pair words u32[plan_Kp].
+//   LEAN_KEYS    8-byte slots {order key, src | stamp << 16}; the dummy pair is the two slots behind the chains', keys 1 < 2;
+//                a spare slot behind those (votes of the waves: a NaN value among the chains'); 4 slots of padding in all
+//   LEAN_WIDE    16-byte slots {value, src | stamp << 16, -}; the dummy pair is (d, d), d the one zero slot behind the chains'
+//   LEAN_TILE16  k_chain_iter's inline walk: 16-byte slots whatever the threshold, TWO zero slots behind the chains' — the plan
+//                may be the key form's, whose dummy pair names two slots and whose offsets are read doubled
+// ------------------------------------------------------------------------------------------
+enum { LEAN_KEYS = 0, LEAN_WIDE = 1, LEAN_TILE16 = 2 };
+__host__ __device__ constexpr uint32_t lean_Ng4(int Ng) { return (uint32_t)((Ng + 3) & ~3); }
+template <int LAY>
+struct LeanLayout {
+    static constexpr bool WIDE = LAY != LEAN_KEYS;                     // lean_walk_levels' slot form
+    static constexpr int SL = WIDE ? 4 : 3;                            // log2 of the slot size
+    static constexpr uint32_t SLOT = 1u << SL;
+    static constexpr uint32_t PAD = LAY == LEAN_KEYS ? 4u : LAY == LEAN_WIDE ? 1u : 2u;   // slots between the chains' and the pair words
+    static constexpr uint32_t DUMMIES = LAY == LEAN_WIDE ? 1u : 2u;
+    __host__ __device__ static constexpr uint32_t pbase(uint32_t Ng4) { return SLOT * (Ng4 + PAD); }   // LDS offset of the pair words
+    __host__ __device__ static constexpr uint32_t spare(uint32_t Ng4) {   // 16 bytes nobody walks
+        static_assert(LAY == LEAN_KEYS, "only the key layout has a spare slot: behind the dummies of the other two the pair words begin");
+        return SLOT * (Ng4 + DUMMIES);
+    }
+    __host__ __device__ static constexpr size_t slot_bytes(int Ng) { return (size_t)pbase(lean_Ng4(Ng)); }
+    __host__ __device__ static constexpr size_t bytes(int Ng, int K) { return slot_bytes(Ng) + (size_t)lean_walk_Kp(K) * 4; }
+    // KParams::lean_unit of a plan made for this layout: what a pair word counts its two 16-bit offsets in — bytes where they reach
+    // the last dummy slot, else halves (keys: up to 8190 chains in bytes; wide: 4092, and 8188 halved)
+    __host__ __device__ static constexpr int unit4(uint32_t Ng4) { return SLOT * (Ng4 + DUMMIES) <= 65536u ? (int)SLOT : (int)SLOT / 2; }
+    __host__ __device__ static constexpr int unit(int Ng) { return unit4(lean_Ng4(Ng)); }
+    // the pair word of the dummy pair in a plan of that unit
+    __host__ __device__ static constexpr uint32_t dummy_word(uint32_t unit, uint32_t Ng4) {
+        return DUMMIES == 1u ? (unit * Ng4) * 0x10001u : (unit * Ng4) | ((unit * (Ng4 + 1u)) << 16);
+    }
+    // the dummy slots' contents (no swap ever: keys 1 < 2; 0 - 0 > min_improve is false for min_improve >= 0 or NaN)
+    __device__ static inline void put_dummies(unsigned char* lds, const uint32_t Ng4) {
+        if constexpr (LAY == LEAN_KEYS) ((uint4*)lds)[Ng4 / 2] = make_uint4(1u, 0u, 2u, 0u);
+        else {
+            ((uint4*)lds)[Ng4] = make_uint4(0u, 0u, 0u, 0u);
+            if constexpr (DUMMIES == 2u) ((uint4*)lds)[Ng4 + 1u] = make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+};
 
 // LDS byte offsets of the two slots of a pair word (US = 1: the word holds them halved, KParams::lean_unit == 4)
 template <int US>
@@ -177,6 +211,100 @@ __device__ inline void lean_walk_levels(const double* __restrict__ vsrc, const i
         if (l < nlev) level(l, true);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// Staging and read-out of a walk of the WHOLE list, in the phases every site goes through in this order:
+//   request  the plan's header word and pair words, and what the slots are made of, into registers — everything before anything is
+//            looked at (a load issued behind the first wait is a round trip of its own)
+//   decide   lean_plan_head: the number of levels, and whether the plan has the padded form at all; the site adds its own conditions
+//   commit   the slots, the pair words behind them, the dummy slots; the first level of the narrow tail.  The barrier is the site's.
+//   walk     lean_walk: lean_walk_levels for the layout and the plan's unit
+//   read out lean_result: src | (1 + last partner) << 32, as k_exch_resolve_* write it
+// NT lanes; NMAX: the largest population the loops serve (their trip counts are compile-time).
+// Callers: exchange_walk_lean_wide, exchange_walk_lean_p2p (smm_chain_norm.hpp), both branches of k_exch_resolve_lean (smm_exchange.hpp).  Three sites
+// keep their request and commit written out, on this file's layout numbers and lean_plan_head: exchange_walk_lean (smm_chain_norm.hpp),
+// exchange_walk_tile_lean and exchange_walk_tile_keys (smm_chain.hpp) — on these pieces their kernels, which spill scalar registers in the
+// prologue, were allocated differently (MEASUREMENTS.md).
+// ------------------------------------------------------------------------------------------
+template <int NT, int NMAX>
+struct LeanPlanRegs {
+    static constexpr int PR = (NMAX + 64 * LV_MAXLEV + 4 * NT - 1) / (4 * NT);   // rounds of 16-byte loads for the pair words
+    uint32_t ov;     // lane l: first word of level l; lane 33: levels; lane 34: the plan fits
+    uint4 p_[PR];
+    __device__ static inline const uint4* pairs(const KParams& P, const int w) { return (const uint4*)(P.lv_pairs_p + (size_t)w * P.plan_Kp); }
+    __device__ __forceinline__ void request_ov(const KParams& P, const int w, const int tid) {
+        ov = (P.lv_offp + (size_t)w * LV_OFFP)[min(tid & 63, LV_OFFP - 1)];
+    }
+    __device__ __forceinline__ void request_pairs(const KParams& P, const int w, const int tid) {
+        const uint4* __restrict__ g_pairs = pairs(P, w);
+#pragma unroll
+        for (int r = 0; r < PR; ++r) {
+            const int q4 = tid + r * NT;
+            p_[r] = 4 * q4 < P.plan_Kp ? g_pairs[q4] : make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+    // pair words and dummy slots into LDS; returns the first level of the narrow tail
+    template <int LAY>
+    __device__ __forceinline__ int commit(const KParams& P, unsigned char* lds, const uint32_t Ng4, const int tid, const int nlev) const {
+#pragma unroll
+        for (int r = 0; r < PR; ++r) {
+            const int q4 = tid + r * NT;
+            if (4 * q4 < P.plan_Kp) ((uint4*)(lds + LeanLayout<LAY>::pbase(Ng4)))[q4] = p_[r];
+        }
+        if (tid == 0) LeanLayout<LAY>::put_dummies(lds, Ng4);
+        return lean_walk_tail(ov, nlev, tid & 63);
+    }
+};
+struct LeanPlanHead { int nlev; bool fits; };
+__device__ inline LeanPlanHead lean_plan_head(const uint32_t ov) {
+    return {__builtin_amdgcn_readlane((int)ov, 33), __builtin_amdgcn_readlane((int)ov, 34) != 0};
+}
+// slot source: the chains' values at vsrc[g * vstride], chains tid, tid + NT, ...
+template <int NT, int NMAX>
+struct LeanValueRegs {
+    static constexpr int PT = NMAX / NT;   // chains per lane
+    double v_[PT];
+    __device__ __forceinline__ void request(const double* __restrict__ vsrc, const int vstride, const int Ng, const int tid) {
+#pragma unroll
+        for (int r = 0; r < PT; ++r) {
+            const int g = tid + r * NT;
+            v_[r] = g < Ng ? vsrc[(size_t)g * vstride] : 0.0;
+        }
+    }
+    __device__ __forceinline__ bool any_nan() const {
+        bool nan = false;
+#pragma unroll
+        for (int r = 0; r < PT; ++r) nan = nan || v_[r] != v_[r];
+        return nan;
+    }
+    template <int LAY>
+    __device__ __forceinline__ void commit(unsigned char* lds, const int Ng, const int tid) const {
+#pragma unroll
+        for (int r = 0; r < PT; ++r) {
+            const int g = tid + r * NT;
+            if (g < Ng) {
+                if constexpr (LAY == LEAN_KEYS) ((uint2*)lds)[g] = make_uint2(order_key32(v_[r]), (uint32_t)g);
+                else ((uint4*)lds)[g] = make_uint4((uint32_t)__double2loint(v_[r]), (uint32_t)__double2hiint(v_[r]), (uint32_t)g, 0u);
+            }
+        }
+    }
+};
+// the levels, for the layout and the plan's unit (KParams::lean_unit).  BYTES: the site serves no population whose plan halves its offsets
+template <int NT, int LAY, class GUARD = WalkNoGuard, bool BYTES = false>
+__device__ __forceinline__ void lean_walk(const int unit, const double* __restrict__ vsrc, const int vstride, const uint32_t Ng4, const uint32_t ov,
+                                          const int nlev, const int tid, const int ltail, const double thr = 0.0, const GUARD& guard = GUARD()) {
+    using L = LeanLayout<LAY>;
+    if (BYTES || unit == (int)L::SLOT) lean_walk_levels<NT, 0, L::WIDE, GUARD>(vsrc, vstride, L::pbase(Ng4), ov, nlev, tid, ltail, thr, guard);
+    else lean_walk_levels<NT, 1, L::WIDE, GUARD>(vsrc, vstride, L::pbase(Ng4), ov, nlev, tid, ltail, thr, guard);
+}
+// chain g's record source and 1 + its last exchange partner (0: none) after the walk: src | partner << 32
+template <int LAY>
+__device__ inline unsigned long long lean_result(const unsigned char* lds, const uint32_t Ng4, const int unit, const uint32_t g) {
+    using L = LeanLayout<LAY>;
+    const uint32_t meta = *(const uint32_t*)(lds + L::SLOT * g + (L::WIDE ? 8u : 4u));
+    const uint32_t partner = unit == (int)L::SLOT ? lean_partner<0, L::SL>(lds, L::pbase(Ng4), meta, g) : lean_partner<1, L::SL>(lds, L::pbase(Ng4), meta, g);
+    return (unsigned long long)(meta & 0xffffu) | ((unsigned long long)partner << 32);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -378,7 +378,10 @@ def test_the_forms_and_context_creation_live_in_their_host_files_with_each_rule_
     three = main + user + forms + launch + create   # (the three files this code stood in, and the two that took the rest of smmhip.hip's)
     assert len(re.findall(r"160 \* 1024", three)) == 1 and "160 * 1024" in forms
     assert not re.findall(r"\b80 \* 1024", three)
-    assert len(re.findall(r"\(\(\(\w+ \+ 3\) & ~3\) \+ 4\) \* 8", three)) == 1 and "size_t key_slot_bytes(int Ng)" in forms
+    # (the key walk's slot block: the host takes it from the layout description of smm_walk_lean.hpp, the one place that states it)
+    assert not re.findall(r"\(\(\(\w+ \+ 3\) & ~3\) \+ \d+\) \* (?:8|16)", "\n".join(code.values()))
+    assert "size_t key_slot_bytes(int Ng) { return LeanLayout<LEAN_KEYS>::slot_bytes(Ng); }" in forms
+    assert "\n".join(code.values()).count("SLOT * (Ng4 + PAD)") == 1 and "SLOT * (Ng4 + PAD)" in code["smm_walk_lean.hpp"]
     a = create.index("int check_create_args(")
     refusals = re.findall(r'fail\(nullptr, SMM_ERR_\w+, "([^"]+)"\)', create[a:create.index("\n}\n", a)])
     assert len(refusals) == 17 and len(set(refusals)) == 17
