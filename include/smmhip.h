@@ -878,6 +878,61 @@ int  smm_get_profile(void* ctx, int32_t t0, int32_t t1, int32_t select, const in
                      int32_t bins, const double* range /* [np][2] or NULL */, const int32_t* pairs /* [n_pairs][2] */,
                      int32_t n_pairs, int32_t bins2, smm_profile_t* out);
 
+/* Highest-density intervals, half-sample modes and Gaussian kernel densities of the draws of groups of chains, computed on the device from
+ * the history it holds, over the 0-based iterations [t0, t1): for each group and parameter the shortest interval holding a given mass of
+ * the pooled draws (ArviZ's hdi of a unimodal sample; smm_get_chain_stats' and every quantile's intervals are equal-tailed), the
+ * half-sample mode (Bickel & Fruehwirth 2006: the marginal mode, which best — the argmin of the objective — is not), and the kernel
+ * density on a grid of n_grid points with its bandwidth and its highest grid point.  Groups, select (0 all rows, 1 accepted rows, 2 the
+ * state series through a(t)), the window and the pooled column x of (group g, parameter k) are exactly smm_get_histogram's: the members
+ * in ascending local index, each in iteration order; per-chain results: group = 0 .. N-1; group NULL with n_groups == 1: every local
+ * chain in group 0; a shard reports its own local chains.  Caller-allocated; any pointer may be NULL (not computed).  Read-only and
+ * ordered like smm_get_chain_stats (it settles, flushes and synchronises, and changes no state, history or generator).  Device memory:
+ * the reducers' scratch and result buffer.  A parameter takes 16 bytes per pooled row of the scratch (the packed column and its sorted
+ * keys; 32 and the digit tables of smm_get_rank_diag's sort where a column has 8193 rows or more) and goes with as many other
+ * parameters as fit (the scratch is grown where needed to one parameter); [G][np] and [n_mass][G][np] results stay on the device for the
+ * call, the curves are produced and copied out in batches of groups that fit 256 MiB (at least one group; a group takes n_grid x 8 x
+ * (2 + its chunks of 8192 rows) bytes per parameter of the batch).  SMM_ERR_INVALID_ARG: NULL ctx or out, a bad window, select outside
+ * [0, 2], n_groups < 0, group NULL with n_groups != 1, a group id outside [-1, n_groups), n_mass < 0, mass NULL with n_mass > 0, a mass
+ * outside (0, 1] or NaN, hdi_lo or hdi_hi requested with n_mass == 0, n_grid neither 0 nor in [2, 4096], grid, density or kde_mode
+ * requested with n_grid == 0, a range row not finite or with lo > hi, a bw entry not finite or not > 0, a group whose pooled rows
+ * would number more than 2^31 - 1; nothing is written then.
+ *
+ * Numerical contract (every operation rounded on its own, no fma outside smm_exp; counts and indexes 64-bit).  m = count; s = x sorted
+ * by the IEEE total order (-0 before +0); S(.) the chain-stats sum (pw over chunks of 8192 from the group's first draw), mean, quantile
+ * the chain-stats ones on the pooled column, var smm_get_trace's (ddof 1):
+ *   status     : 1: a NaN or +-inf in the column: every double output of (g, k) NaN, kde_status 1, count still reported.
+ *                2: m == 0: every double output NaN, kde_status 1.
+ *   HDI of mass p : k = min((int64)floor(p * (double)m), m - 1) (one rounded product); w_i = s[i + k] - s[i], i in [0, m - k);
+ *                i* the first minimum of w (np.argmin); hdi_lo = s[i*], hdi_hi = s[i* + k].
+ *   mode       : lo = 0, n = m; while n > 3: h = (n + 1) / 2, w_i = s[lo + i + h - 1] - s[lo + i] for i in [0, n - h + 1), lo += the first
+ *                argmin, n = h.  n == 1: s[lo]; n == 2: (s[lo] + s[lo + 1]) / 2; n == 3: a = s[lo + 1] - s[lo], b = s[lo + 2] - s[lo + 1]:
+ *                a < b: (s[lo] + s[lo + 1]) / 2; b < a: (s[lo + 1] + s[lo + 2]) / 2; else s[lo + 1].
+ *   bandwidth  : h = bw[k] where given; else R's bw.nrd0: sd = sqrt(var(x)) (NaN for m < 2), a = (quantile(0.75) - quantile(0.25)) / 1.34,
+ *                l = sd < a ? sd : a; l == 0: l = sd; still 0: l = |x[0]| (the first pooled draw); still 0: l = 1.0;
+ *                h = (0.9 * l) * smm_exp(-0.2 * smm_log((double)m)).  h not finite or not > 0: kde_status 1, bw as computed, grid,
+ *                density and kde_mode NaN.
+ *   grid       : (lo, hi) = range[k] where given, else lo = s[0] - 3.0 * h, hi = s[m - 1] + 3.0 * h; hi - lo not finite: kde_status 2,
+ *                grid, density and kde_mode NaN.  Else smm_get_histogram's linspace with b = n_grid - 1: delta = hi - lo,
+ *                step = delta / b; step != 0: g[j] = j step + lo, else g[j] = (j / b) delta + lo; g[b] = hi.
+ *   density    : rh = 1.0 / h; u = (g[j] - x[i]) * rh; e_ij = smm_exp(-0.5 * (u * u)); D_j = S(e_.j) over i in pooled order;
+ *                density[j] = (D_j / (double)m) / (h * 2.5066282746310002).
+ *   kde_mode   : g[first argmax of density] (np.argmax: the first NaN where there is one). */
+typedef struct {            /* caller-allocated; any pointer may be NULL = not computed */
+    int64_t* count;         /* [G]              rows selected for the group                                   */
+    int32_t* status;        /* [G][np]          0 ok, 1 a non-finite draw in the column, 2 empty column       */
+    double*  hdi_lo;        /* [n_mass][G][np]                                                                */
+    double*  hdi_hi;        /* [n_mass][G][np]                                                                */
+    double*  mode;          /* [G][np]          half-sample mode                                              */
+    double*  bw;            /* [G][np]          bandwidth used                                                */
+    int32_t* kde_status;    /* [G][np]          0 ok, 1 no usable bandwidth, 2 grid width not finite          */
+    double*  grid;          /* [G][np][n_grid]                                                                */
+    double*  density;       /* [G][np][n_grid]                                                                */
+    double*  kde_mode;      /* [G][np]          grid point of the first maximum of density                    */
+} smm_density_t;
+int  smm_get_density(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group /* [N] or NULL */, int32_t n_groups,
+                     const double* mass, int32_t n_mass, int32_t n_grid, const double* range /* [np][2] or NULL */,
+                     const double* bw /* [np] or NULL */, smm_density_t* out);
+
 /* Covariances of the chains' draws and the proposal factor between steps — adaptive Metropolis (Haario et al.) on top of chol_L: a
  * pilot run, then each chain's proposal shaped by the covariance of its own draws, without leaving the device.
  *

@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_adjustment, hip_profile, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_adjustment, hip_profile, hip_density, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_set_population!, hip_scatter_population!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
@@ -189,6 +189,19 @@ struct SmmProfile
     min_chain2::Ptr{Int32}
     min_iter2::Ptr{Int32}
     v_mean2::Ptr{Cdouble}
+end
+
+struct SmmDensity
+    count::Ptr{Int64}
+    status::Ptr{Int32}
+    hdi_lo::Ptr{Cdouble}
+    hdi_hi::Ptr{Cdouble}
+    mode::Ptr{Cdouble}
+    bw::Ptr{Cdouble}
+    kde_status::Ptr{Int32}
+    grid::Ptr{Cdouble}
+    density::Ptr{Cdouble}
+    kde_mode::Ptr{Cdouble}
 end
 
 struct SmmGroupStats
@@ -652,6 +665,46 @@ function hip_profile(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :acce
     return (count = count, status = st, edges = edges, n = n, n_scored = nsc, v_min = vmin, min_chain = mch, min_iter = mit,
             theta_at_min = theta, v_mean = vmean, m_mean = mmean, edges2 = edges2, n2 = n2, n_scored2 = nsc2, v_min2 = vmin2,
             min_chain2 = mch2, min_iter2 = mit2, v_mean2 = vmean2)
+end
+
+"""
+    hip_density(h, t0, t1; select = :accepted, groups = nothing, mass = [0.94], n_grid = 128, range = nothing, bw = nothing) -> NamedTuple
+
+Highest-density intervals, half-sample modes and Gaussian kernel densities of the draws of groups of chains over iterations
+`t0+1 .. t1`, on the device (`smm_get_density`) without downloading the history.  `select`, `groups` and `range` as `hip_histogram`;
+`mass`: the intervals' masses in (0, 1]; `n_grid`: grid points of the density (0: none); `bw`: a bandwidth per parameter, `nothing`:
+R's `bw.nrd0` of each column; `range = nothing`: three bandwidths past each column's extremes.  Returns `count[g]`, `status[k, g]`
+(0 ok, 1 a non-finite draw, 2 no draw), `hdi_lo[k, g, p]`, `hdi_hi[k, g, p]`, `mode[k, g]`, `bw[k, g]`, `kde_status[k, g]`,
+`grid[:, k, g]`, `density[:, k, g]`, `kde_mode[k, g]` (the header's row-major arrays).
+"""
+function hip_density(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :accepted,
+                     groups::Union{Nothing,AbstractVector{<:Integer}} = nothing, mass::AbstractVector{<:Real} = [0.94],
+                     n_grid::Integer = 128, range::Union{Nothing,AbstractMatrix{<:Real}} = nothing,
+                     bw::Union{Nothing,AbstractVector{<:Real}} = nothing)
+    N, np = h.N, h.np
+    g = groups === nothing ? Int32[] : Vector{Int32}(groups)
+    groups === nothing || length(g) == N || throw(ArgumentError("groups needs one entry per chain"))
+    ng = groups === nothing ? 1 : (isempty(g) ? 0 : Int(maximum(g)) + 1)
+    rg = range === nothing ? Float64[] : vec(Matrix{Float64}(permutedims(range)))   # row k = (lo, hi)
+    bv = bw === nothing ? Float64[] : Vector{Float64}(bw)
+    bw === nothing || length(bv) == np || throw(ArgumentError("bw needs one entry per parameter"))
+    ms = Vector{Float64}(mass)
+    nms, ngr = length(ms), Int(n_grid)
+    count = Vector{Int64}(undef, ng); st = Matrix{Int32}(undef, np, ng)
+    hlo = Array{Float64}(undef, np, ng, nms); hhi = Array{Float64}(undef, np, ng, nms)
+    md = Matrix{Float64}(undef, np, ng); obw = Matrix{Float64}(undef, np, ng); kst = Matrix{Int32}(undef, np, ng)
+    grid = Array{Float64}(undef, ngr, np, ng); dens = Array{Float64}(undef, ngr, np, ng); kmode = Matrix{Float64}(undef, np, ng)
+    opt(a, T, on) = on ? pointer(a) : Ptr{T}(C_NULL)
+    GC.@preserve g rg bv ms count st hlo hhi md obw kst grid dens kmode begin
+        ds = SmmDensity(pointer(count), pointer(st), opt(hlo, Cdouble, nms > 0), opt(hhi, Cdouble, nms > 0), pointer(md), pointer(obw),
+                        pointer(kst), opt(grid, Cdouble, ngr > 0), opt(dens, Cdouble, ngr > 0), opt(kmode, Cdouble, ngr > 0))
+        check(h.ctx, ccall(sym(:smm_get_density), Cint,
+                           (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Int32}, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ref{SmmDensity}),
+                           h.ctx, t0, t1, HIST_SELECT[select], groups === nothing ? Ptr{Int32}(C_NULL) : pointer(g), ng,
+                           opt(ms, Cdouble, nms > 0), nms, ngr, opt(rg, Cdouble, range !== nothing), opt(bv, Cdouble, bw !== nothing), ds))
+    end
+    return (count = count, status = st, hdi_lo = hlo, hdi_hi = hhi, mode = md, bw = obw, kde_status = kst, grid = grid, density = dens,
+            kde_mode = kmode)
 end
 
 """

@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, profile_objective, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, profile_objective, posterior_density, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -424,6 +424,31 @@ function profile_objective(algo::MAlgoBGPHip; window = nothing, select::Symbol =
     end
     return SMMHip.hip_profile(hip, t0, t1; select = select, groups = groups, bins = bins, range = range, pairs = pairs, bins2 = bins2,
                               moments = moments)
+end
+
+"""
+    posterior_density(algo; window = nothing, select = :accepted, groups = nothing, mass = [0.94], n_grid = 128, range = nothing,
+                      bw = nothing) -> NamedTuple
+
+The intervals, modes and density curves of a posterior report, computed on the device from the history it holds
+(`SMMHip.hip_density`), without `sync_chains!`: per group and parameter the highest-density interval of each `mass`
+(`hdi_lo[k, g, p]`, `hdi_hi[k, g, p]`: the shortest interval holding that share of the draws, where `CI` and the quantiles are
+equal-tailed), the half-sample `mode[k, g]` of the marginal (which `best`, the argmin of the objective, is not), and the Gaussian kernel
+density `density[:, k, g]` on `grid[:, k, g]` with its bandwidth `bw[k, g]` (R's `bw.nrd0` unless given) and its highest grid point
+`kde_mode[k, g]`.  Groups and window as `chain_histogram`.  `status[k, g]` != 0: a non-finite draw in the column (1) or no draw (2);
+`kde_status[k, g]` != 0: no usable bandwidth (1: fewer than two draws) or a grid whose width is not finite (2).  Not a method of `SMM`.
+"""
+function posterior_density(algo::MAlgoBGPHip; window = nothing, select::Symbol = :accepted, groups = nothing,
+                           mass::AbstractVector{<:Real} = [0.94], n_grid::Integer = 128, range = nothing, bw = nothing)
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    t0, t1 = window === nothing ? (0, SMMHip.hip_iter(hip)) : window
+    if groups === nothing
+        ids = Dict{Float64,Int32}()
+        opts = getfield(algo, :opts)
+        groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
+    end
+    return SMMHip.hip_density(hip, t0, t1; select = select, groups = groups, mass = mass, n_grid = n_grid, range = range, bw = bw)
 end
 
 """

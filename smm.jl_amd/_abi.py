@@ -171,6 +171,13 @@ class smm_profile_t(C.Structure):
     ]
 
 
+class smm_density_t(C.Structure):
+    _fields_ = [
+        ("count", C.POINTER(C.c_int64)), ("status", c_int32_p), ("hdi_lo", c_double_p), ("hdi_hi", c_double_p), ("mode", c_double_p),
+        ("bw", c_double_p), ("kde_status", c_int32_p), ("grid", c_double_p), ("density", c_double_p), ("kde_mode", c_double_p),
+    ]
+
+
 class smm_population_t(C.Structure):
     _fields_ = [
         ("start", c_double_p), ("value", c_double_p), ("pick", c_int32_p), ("evaluated", C.c_int64),
@@ -237,6 +244,8 @@ SYMBOLS = [
                                      C.c_double, c_double_p, C.c_int32, C.POINTER(smm_adjustment_t)]),
     ("smm_get_profile", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32, c_double_p, c_int32_p,
                                    C.c_int32, C.c_int32, C.POINTER(smm_profile_t)]),
+    ("smm_get_density", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_double_p, C.c_int32, C.c_int32,
+                                   c_double_p, c_double_p, C.POINTER(smm_density_t)]),
     ("smm_get_chain_cov", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
     ("smm_get_proposal", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_proposal", C.c_int, [C.c_void_p, c_double_p]),

@@ -384,6 +384,35 @@ class BGPContext:
                                               pr.ctypes.data_as(A.c_int32_p) if npr else None, npr, b2, C.byref(s)))
         return r
 
+    def density(self, t0=0, t1=None, select="accepted", groups=None, mass=(0.94,), n_grid=128, range=None, bw=None, n_groups=None):
+        """highest-density intervals, half-sample modes and Gaussian kernel densities of the draws of groups of local chains over
+        iterations [t0, t1), on the device (smm_get_density, include/smmhip.h): a dict of numpy arrays count [n_groups], status / mode
+        [n_groups][np], hdi_lo / hdi_hi [len(mass)][n_groups][np] and, with n_grid > 0, bw / kde_status / kde_mode [n_groups][np], grid /
+        density [n_groups][np][n_grid].  select, groups, n_groups and range as in histogram(); mass: the intervals' masses in (0, 1];
+        bw: a bandwidth per parameter, None: R's bw.nrd0 of each column; range None: three bandwidths past each column's extremes"""
+        t1 = self._t1(t1)
+        np_ = self.np
+        sel = self._select(select)
+        g, gp, ng = self._groups("density", groups, n_groups)
+        if isinstance(range, dict):
+            if sorted(range) != list(_builtins.range(np_)):
+                raise ValueError("density: a range dict names every parameter index 0 .. np-1")
+            range = [range[k] for k in _builtins.range(np_)]
+        rg = None if range is None else np.ascontiguousarray(range, np.float64).reshape(np_, 2)
+        bwv = None if bw is None else np.ascontiguousarray(np.broadcast_to(np.asarray(bw, np.float64), (np_,)))
+        m = A.f64(mass).reshape(-1)
+        ngr = int(n_grid)
+        r = dict(count=np.empty(ng, np.int64), status=np.empty((ng, np_), np.int32), mode=np.empty((ng, np_)), bw=np.empty((ng, np_)),
+                 kde_status=np.empty((ng, np_), np.int32))
+        if len(m):
+            r.update(hdi_lo=np.empty((len(m), ng, np_)), hdi_hi=np.empty((len(m), ng, np_)))
+        if ngr != 0:
+            r.update(kde_mode=np.empty((ng, np_)), grid=np.empty((ng, np_, max(ngr, 0))), density=np.empty((ng, np_, max(ngr, 0))))
+        s = self._out(A.smm_density_t, r)
+        self._check(self._fn("get_density")(self._ctx, int(t0), int(t1), sel, gp, ng, A.dptr(m) if len(m) else None, len(m), ngr,
+                                            A.dptr(rg) if rg is not None else None, A.dptr(bwv) if bwv is not None else None, C.byref(s)))
+        return r
+
     def trace(self, t0=0, t1=None, stride=1, select="state", moments=False, groups=None, probs=(), n_groups=None):
         """the population per iteration over the kept iterations t0, t0 + stride, .. < t1, reduced across the chains of each group on the
         device (smm_get_trace, include/smmhip.h): a dict of numpy arrays iter [nt], n_chains [n_groups], count / n_accepted / n_exchanged /

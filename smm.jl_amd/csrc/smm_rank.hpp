@@ -16,6 +16,8 @@
 //                       in order — a value's place among its wave's equal digits by ballots —, which keeps every pass stable.
 //   k_rank_count / k_rank_scan / k_rank_scatter : the same pass for a longer column spread over up to RANK_NBLK workgroups: the
 //                       segments' counts to a global table [256][segments], one workgroup's digit-major scan of it, the scatter.
+//                       The three sort kernels and k_rank_sort_small also sort the columns of a plain (offset, length) table
+//                       (RankBatch::tab_off / tab_len: smm_get_density's long columns); rank_sort_columns launches them for both.
 //   k_rank_ties       : rank2 = 2 L + E + 1 of every sorted position from the ends of its tie run (its neighbours where the run is the
 //                       value alone, else a binary search of the sorted keys), written back by pooled index.
 //   k_rank_order      : one lane per column: median, q05 and q95 read from the sorted keys (the chain-stats order statistics).
@@ -45,10 +47,15 @@ struct RankBatch {
     const int* large;    // [G] the ordinal of a group among its batch's long columns
     int g0, gn, s0, sb, S, q0, mtot, h, n;
     long long Mtot;
+    // a plain column table instead (the sort alone, for smm_get_density): column g has tab_len[g] values from tab_off[g] of its series
+    const long long* tab_off = nullptr;
+    const long long* tab_len = nullptr;
 };
-__device__ __forceinline__ long long rank_col_len(const RankBatch& b, int g) { return 2ll * (b.gm0[g + 1] - b.gm0[g]) * b.h; }
+__device__ __forceinline__ long long rank_col_len(const RankBatch& b, int g) {
+    return b.tab_len ? b.tab_len[g] : 2ll * (b.gm0[g + 1] - b.gm0[g]) * b.h;
+}
 __device__ __forceinline__ long long rank_col_off(const RankBatch& b, int g, int sl) {
-    return (long long)sl * b.Mtot + (long long)(2 * b.gm0[g] - b.q0) * b.h;
+    return (long long)sl * b.Mtot + (b.tab_off ? b.tab_off[g] : (long long)(2 * b.gm0[g] - b.q0) * b.h);
 }
 
 __global__ __launch_bounds__(RANK_WG) void k_rank_gather(const double* __restrict__ hrec, int N, int HW, int np, int t0, RankBatch b,

@@ -1,8 +1,9 @@
 // the host side of the history reducers — part of libsmmhip (included once by smmhip.hip, behind its host helpers; hiprtc never sees it).
 // The family: smm_get_chain_stats, smm_get_chain_cov, smm_get_proposal / _set_ / _adapt_, smm_get_chain_diag, smm_get_group_stats,
-// smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws, smm_get_moment_stats, smm_get_adjustment, smm_get_profile (kernels:
+// smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws, smm_get_moment_stats, smm_get_adjustment, smm_get_profile,
+// smm_get_density (kernels:
 // smm_stats.hpp, smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_moments.hpp, smm_adjust.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp,
-// smm_draws.hpp, smm_profile.hpp;
+// smm_draws.hpp, smm_profile.hpp, smm_density.hpp;
 // the walk over a chain's window that their gathers share: smm_window.hpp).
 // What they share is stated here once: the frame of a call (api_call of smmhip.hip), the checks of the arguments they have in common (check_groups,
 // check_probs, check_select), the prelude and the window behind them (settled_window: reader_prelude and check_window of smmhip.hip), the
@@ -296,6 +297,25 @@ void pool_order(Ctx* c, void* d, const PoolDev& pd, const PoolPlan& pp, const Or
                    (const long long*)pd.rk.in(d), (const unsigned long long*)pd.pre.in(d), gnan, dprobs, nq, omed, quant);
 }
 
+// the segmented radix sort of smm_rank.hpp over the batch's columns (b: smm_get_rank_diag's split chains, or smm_get_density's plain
+// column table): the keys KA with their indexes IA sorted in place through KB / IB; columns of at most RANK_SMALL values by one
+// workgroup each, the longer ones (any_large; table: their digit counts) pass by pass over the grid
+void rank_sort_columns(Ctx* c, const RankBatch& b, bool any_large, unsigned long long* KA, unsigned* IA, unsigned long long* KB, unsigned* IB,
+                       int* table) {
+    const dim3 cols(b.gn, b.sb), blocks(b.gn, b.sb, RANK_NBLK);
+    launch_checked(c, k_rank_sort_small, cols, dim3(RANK_WG), 0, b, KA, IA, KB, IB);
+    for (int pass = 0; pass < 8 && any_large; ++pass) {
+        unsigned long long* Kin = (pass & 1) ? KB : KA;
+        unsigned long long* Kout = (pass & 1) ? KA : KB;
+        unsigned* Iin = (pass & 1) ? IB : IA;
+        unsigned* Iout = (pass & 1) ? IA : IB;
+        launch_checked(c, k_rank_count, blocks, dim3(RANK_WG), 0, b, pass, (const unsigned long long*)Kin, table);
+        launch_checked(c, k_rank_scan, cols, dim3(RANK_WG), 0, b, table);
+        launch_checked(c, k_rank_scatter, blocks, dim3(RANK_WG), 0, b, pass, (const unsigned long long*)Kin, (const unsigned*)Iin, Kout, Iout,
+                       (const int*)table);
+    }
+}
+
 // the reducers' dynamic LDS (smm_ctx_create): a chunk of draws (k_stats_column, k_cov_center, k_diag_acov, k_group_*, k_trace_column),
 // the partner ids of a pass (k_stats_mode), the counters and edges of a batch of parameters or pairs (k_hist_count, k_hist_pairs), a
 // split chain (k_rank_chain_mom, k_rank_acov), the three matrices of a group (k_moment_solve: 3 x 64 x 65 doubles), the two of
@@ -315,6 +335,10 @@ void reducer_kernel_attributes() {
     HIPCHK(hipFuncSetAttribute((const void*)k_moment_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * MAX_DIM * (MAX_DIM + 1) * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_adjust_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * MAX_DIM * (MAX_DIM + 1) * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_prof_chunk, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_dens_small, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_dens_mode_fin, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_dens_chunk_dev, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_dens_kde, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
 }
 
 }  // namespace
@@ -945,17 +969,7 @@ int smm_get_rank_diag(void* ctx, int32_t t0, int32_t t1, int32_t max_lag, int32_
                 auto rank_columns = [&](int fold) {   // rank2 of every column of the batch: of x, or of |x - med|
                     launch_checked(c, k_rank_keys, dim3(gn, sbb, nbz), dim3(RANK_WG), 0, b, fold, (const double*)(Y + E), (const double*)ord.in(d),
                                    KA, IA, flag.in(d));
-                    launch_checked(c, k_rank_sort_small, cols, dim3(RANK_WG), 0, b, KA, IA, KB, IB);
-                    for (int pass = 0; pass < 8 && nlarge > 0; ++pass) {
-                        unsigned long long* Kin = (pass & 1) ? KB : KA;
-                        unsigned long long* Kout = (pass & 1) ? KA : KB;
-                        unsigned* Iin = (pass & 1) ? IB : IA;
-                        unsigned* Iout = (pass & 1) ? IA : IB;
-                        launch_checked(c, k_rank_count, dim3(gn, sbb, RANK_NBLK), dim3(RANK_WG), 0, b, pass, (const unsigned long long*)Kin, table);
-                        launch_checked(c, k_rank_scan, cols, dim3(RANK_WG), 0, b, table);
-                        launch_checked(c, k_rank_scatter, dim3(gn, sbb, RANK_NBLK), dim3(RANK_WG), 0, b, pass, (const unsigned long long*)Kin,
-                                       (const unsigned*)Iin, Kout, Iout, (const int*)table);
-                    }
+                    rank_sort_columns(c, b, nlarge > 0, KA, IA, KB, IB, table);
                     launch_checked(c, k_rank_ties, dim3(gn, sbb, nbz), dim3(RANK_WG), 0, b, (const unsigned long long*)KA, (const unsigned*)IA, R2);
                 };
                 rank_columns(0);
@@ -1557,6 +1571,185 @@ int smm_get_profile(void* ctx, int32_t t0, int32_t t1, int32_t select, const int
             for (size_t i = 0; i < N; ++i)
                 if (grp.gid[i] >= 0) out->count[grp.gid[i]] += cnt[i];
         }
+        return SMM_OK;
+    });
+}
+
+// --- highest-density intervals, half-sample modes and kernel densities of groups of chains (smm_density.hpp) -------------------------------
+
+int smm_get_density(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups, const double* mass,
+                    int32_t n_mass, int32_t n_grid, const double* range, const double* bw, smm_density_t* out) {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        const size_t N = c->P.N, np = c->P.np;
+        if (const int rc = check_select(c, select)) return rc;
+        if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
+        if (n_mass < 0 || (n_mass > 0 && !mass)) return fail(c, SMM_ERR_INVALID_ARG, "n_mass < 0, or mass NULL with n_mass > 0");
+        for (int p = 0; p < n_mass; ++p)
+            if (!(mass[p] > 0.0 && mass[p] <= 1.0)) return fail(c, SMM_ERR_INVALID_ARG, "a mass must lie in (0, 1]");
+        if (n_mass == 0 && (out->hdi_lo || out->hdi_hi)) return fail(c, SMM_ERR_INVALID_ARG, "hdi_lo or hdi_hi requested with n_mass == 0");
+        if (n_grid != 0 && (n_grid < 2 || n_grid > 4096)) return fail(c, SMM_ERR_INVALID_ARG, "n_grid must be 0 or lie in [2, 4096]");
+        if (n_grid == 0 && (out->grid || out->density || out->kde_mode))
+            return fail(c, SMM_ERR_INVALID_ARG, "grid, density or kde_mode requested with n_grid == 0");
+        if (range)
+            for (size_t k = 0; k < np; ++k)
+                if (!(std::isfinite(range[2 * k]) && std::isfinite(range[2 * k + 1]) && range[2 * k] <= range[2 * k + 1]))
+                    return fail(c, SMM_ERR_INVALID_ARG, "a range row must be finite with lo <= hi");
+        if (bw)
+            for (size_t k = 0; k < np; ++k)
+                if (!(std::isfinite(bw[k]) && bw[k] > 0.0)) return fail(c, SMM_ERR_INVALID_ARG, "a bw entry must be finite and > 0");
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t G = n_groups, NM = out->hdi_lo || out->hdi_hi ? n_mass : 0, NG = out->grid || out->density || out->kde_mode ? n_grid : 0;
+        const int n = t1 - t0;
+        const bool kde = out->bw || out->kde_status || NG > 0, rule = kde && !bw;
+        const Groups grp = group_members(group, G, N);
+        if ((size_t)grp.longest * (size_t)n > (size_t)INT_MAX)
+            return fail(c, SMM_ERR_INVALID_ARG, "a group whose pooled rows would number more than 2^31 - 1");
+        DevBuf<int> dci(2 * N);
+        const PoolPlan pp = pool_plan(grp, pool_counts(c, grp, t0, n, select, dci.p));
+        if (out->count) std::copy(pp.gm.begin(), pp.gm.end(), out->count);
+        if (G == 0) return SMM_OK;
+        // the plan.  Short columns (below the wide minimum) are sorted in LDS, the others by the radix sort: nl of them, nbig past one
+        // workgroup's sort; NB blocks per grid-wide window argmin, nlev grid-wide levels of the longest column's mode
+        const long long thr = c->H.group_wide_min, Mtot = pp.Mtot;
+        const int NC = pp.NC;
+        std::vector<int> sgrp, wgrp, large, cgrp(NC);
+        std::vector<long long> toff, tlen;
+        long long wmax = 0, smax = 0;
+        int nbig = 0;
+        for (size_t g = 0; g < G; ++g) {
+            for (int ch = pp.gch0[g]; ch < pp.gch0[g + 1]; ++ch) cgrp[ch] = (int)g;
+            if (pp.gm[g] < thr) { sgrp.push_back((int)g); smax = std::max(smax, pp.gm[g]); continue; }
+            wgrp.push_back((int)g); toff.push_back(pp.G0[g]); tlen.push_back(pp.gm[g]);
+            large.push_back(pp.gm[g] > RANK_SMALL ? nbig++ : 0);
+            wmax = std::max(wmax, pp.gm[g]);
+        }
+        const size_t nl = wgrp.size();
+        const long long per = std::min<long long>(DENS_WG * 16, std::max<long long>(1, thr - 1));
+        const int NB = (int)std::min<long long>(DENS_NB_MAX, std::max<long long>(1, (wmax + per - 1) / per));
+        int nlev = 0;
+        for (long long q = wmax; q > 3 && q >= thr; q = (q + 1) / 2) ++nlev;
+        // a parameter of every group takes its packed column and its sorted keys of the scratch, with long columns also the sort's second
+        // key buffer, both index buffers and the digit tables; as many parameters at a time as fit
+        const size_t one = std::max<size_t>(16, (size_t)Mtot * (nl ? 32 : 16) + (size_t)nbig * RANK_TABLE * 4);
+        reducer_scratch(c, one);
+        const size_t hook = c->H.stats_scratch;
+        const size_t budget = hook ? std::min(c->st_scr_bytes, std::max(hook, one)) : c->st_scr_bytes;
+        const size_t kb = std::max<size_t>(1, std::min(np, budget / one));
+        // the curves go out in batches of groups: a group takes its grid, its density and its chunks' sums of every parameter of the batch
+        struct GB { size_t g0, gn; int c0, nc; };
+        std::vector<GB> plan;
+        size_t gnx = 0, ncx = 0;
+        for (size_t g0 = 0; g0 < G && NG > 0;) {
+            GB b{g0, 0, pp.gch0[g0], 0};
+            size_t bytes = 0;
+            while (b.g0 + b.gn < G) {
+                const int nc = pp.gch0[b.g0 + b.gn + 1] - pp.gch0[b.g0 + b.gn];
+                const size_t add = kb * NG * 8 * (2 + (size_t)nc);
+                if (b.gn > 0 && bytes + add > reducer_batch_cap(c)) break;
+                bytes += add; ++b.gn; b.nc += nc;
+            }
+            gnx = std::max(gnx, b.gn); ncx = std::max(ncx, (size_t)b.nc);
+            plan.push_back(b);
+            g0 += b.gn;
+        }
+        Carve Rv;   // 8-byte slices first
+        const auto dmass = Rv.take<double>(NM), drng = Rv.take<double>(range ? 2 * np : 0), dbw = Rv.take<double>(bw ? np : 0),
+                   mean = Rv.take<double>(G * np), csum = Rv.take<double>(rule ? kb * NC : 0), cdev = Rv.take<double>(rule ? kb * NC : 0),
+                   obw = Rv.take<double>(G * np), glo = Rv.take<double>(G * np), ghi = Rv.take<double>(G * np), omode = Rv.take<double>(G * np),
+                   okmode = Rv.take<double>(G * np), hlo = Rv.take<double>(NM * G * np), hhi = Rv.take<double>(NM * G * np),
+                   partw = Rv.take<double>(nl * kb * NB), csk = Rv.take<double>(kb * ncx * NG), gridb = Rv.take<double>(gnx * kb * NG),
+                   densb = Rv.take<double>(gnx * kb * NG);
+        const auto off = Rv.take<long long>(N), dG0 = Rv.take<long long>(G + 1), dgm = Rv.take<long long>(G), cst = Rv.take<long long>(NC),
+                   dtoff = Rv.take<long long>(nl), dtlen = Rv.take<long long>(nl), mlo = Rv.take<long long>(nl * kb),
+                   mn = Rv.take<long long>(nl * kb), parti = Rv.take<long long>(nl * kb * NB);
+        const auto gch0 = Rv.take<int>(G + 1), clen = Rv.take<int>(NC), dcgrp = Rv.take<int>(NC), dsgrp = Rv.take<int>(sgrp.size()),
+                   dwgrp = Rv.take<int>(nl), dlarge = Rv.take<int>(nl), gnan = Rv.take<int>(G * np), cnan = Rv.take<int>(rule ? kb * NC : 0),
+                   status = Rv.take<int>(G * np), kst = Rv.take<int>(G * np);
+        void* d = reducer_result(c, Rv.bytes);
+        up(c, d, dmass, mass, NM); up(c, d, drng, range, 2 * np); up(c, d, dbw, bw, np);
+        up(c, d, off, pp.off); up(c, d, dG0, pp.G0); up(c, d, dgm, pp.gm); up(c, d, cst, pp.cst); up(c, d, dtoff, toff); up(c, d, dtlen, tlen);
+        up(c, d, gch0, pp.gch0); up(c, d, clen, pp.clen); up(c, d, dcgrp, cgrp); up(c, d, dsgrp, sgrp); up(c, d, dwgrp, wgrp);
+        up(c, d, dlarge, large);
+        HIPCHK(hipMemsetAsync(status.in(d), 0, G * np * 4, c->stream));   // (k_dens_keys only raises it)
+        double* col = (double*)c->st_scr;
+        unsigned long long* KA = (unsigned long long*)(col + kb * (size_t)Mtot);
+        unsigned long long* KB = KA + kb * (size_t)Mtot;
+        unsigned* IA = (unsigned*)(KB + kb * (size_t)Mtot);
+        unsigned* IB = IA + kb * (size_t)Mtot;
+        int* table = (int*)(IB + kb * (size_t)Mtot);
+        const double *pmass = dmass.in(d), *prng = range ? drng.in(d) : nullptr, *pbw = bw ? dbw.in(d) : nullptr;
+        const long long *pG0 = dG0.in(d), *pgm = dgm.in(d), *pcst = cst.in(d), *ptoff = dtoff.in(d), *ptlen = dtlen.in(d);
+        const int *pgch0 = gch0.in(d), *pclen = clen.in(d), *pcgrp = dcgrp.in(d), *pwgrp = dwgrp.in(d), *pst = status.in(d), *pkst = kst.in(d);
+        double *phlo = NM ? hlo.in(d) : nullptr, *phhi = NM ? hhi.in(d) : nullptr, *pmode = out->mode ? omode.in(d) : nullptr;
+        for (size_t k0 = 0; k0 < np; k0 += kb) {   // batches of parameters: the packed columns [kbb][Mtot]
+            const int kbb = (int)std::min(kb, np - k0);
+            launch_checked(c, k_group_gather, dim3(N), dim3(STATS_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select,
+                           (const int*)dci.p, (const long long*)off.in(d), (const int*)nullptr, (int)k0, kbb, Mtot, 0, 0, (const double*)nullptr,
+                           (int)np, col, dci.p + N, 0, (int*)nullptr);
+            if (rule && NC > 0) {   // the variance's two sums, chunk by chunk
+                launch_checked(c, k_group_chunk_sum, dim3(NC, kbb), dim3(STATS_WG), (size_t)STATS_LDS_N * 8, (const double*)col, Mtot, pcst, pclen,
+                               NC, csum.in(d), cnan.in(d));
+                launch_checked(c, k_group_mean, dim3((unsigned)((G * kbb + 255) / 256)), dim3(256), 0, (const double*)csum.in(d),
+                               (const int*)cnan.in(d), NC, pgch0, pgm, (int)G, (int)k0, kbb, (int)np, mean.in(d), gnan.in(d));
+                launch_checked(c, k_dens_chunk_dev, dim3(NC, kbb), dim3(DENS_WG), (size_t)STATS_LDS_N * 8, (const double*)col, Mtot, pcst, pclen,
+                               pcgrp, NC, (int)k0, (int)np, (const double*)mean.in(d), cdev.in(d));
+            }
+            if (!sgrp.empty())
+                launch_checked(c, k_dens_small, dim3((unsigned)sgrp.size(), kbb), dim3(DENS_WG), (size_t)sort_lds_n((int)smax) * 8,
+                               (const double*)col, Mtot, (const int*)dsgrp.in(d), pG0, pgm, (int)G, (int)k0, (int)np, pmass, (int)NM, KA,
+                               status.in(d), phlo, phhi, pmode);
+            if (nl > 0) {
+                const unsigned nbz = (unsigned)std::min<long long>(RANK_NBLK, std::max<long long>(1, (wmax + RANK_SMALL - 1) / RANK_SMALL));
+                launch_checked(c, k_dens_keys, dim3((unsigned)nl, kbb, nbz), dim3(DENS_WG), 0, (const double*)col, Mtot, pwgrp, ptoff, ptlen,
+                               (int)k0, (int)np, KA, IA, status.in(d), mlo.in(d), mn.in(d));
+                const RankBatch b{nullptr, nullptr, nullptr, dlarge.in(d), 0, (int)nl, 0, kbb, 0, 0, 0, 0, 0, Mtot, ptoff, ptlen};
+                rank_sort_columns(c, b, nbig > 0, KA, IA, KB, IB, table);
+                auto window = [&](int what) {   // one grid-wide argmin of every long column: the blocks' minima, then the finish
+                    launch_checked(c, k_dens_win, dim3((unsigned)nl, kbb, NB), dim3(DENS_WG), 0, (const unsigned long long*)KA, Mtot, pwgrp,
+                                   ptoff, ptlen, (int)k0, (int)np, pst, what, pmass, thr, (const long long*)mlo.in(d),
+                                   (const long long*)mn.in(d), partw.in(d), parti.in(d));
+                    launch_checked(c, k_dens_win_fin, dim3((unsigned)nl, kbb), dim3(64), 0, (const unsigned long long*)KA, Mtot, pwgrp, ptoff,
+                                   ptlen, (int)G, (int)k0, (int)np, pst, what, pmass, thr, NB, (const double*)partw.in(d),
+                                   (const long long*)parti.in(d), mlo.in(d), mn.in(d), phlo, phhi);
+                };
+                for (int p = 0; p < (int)NM; ++p) window(p);
+                if (pmode) {
+                    for (int lev = 0; lev < nlev; ++lev) window(-1);
+                    launch_checked(c, k_dens_mode_fin, dim3((unsigned)nl, kbb), dim3(DENS_WG), (size_t)STATS_LDS_N * 8,
+                                   (const unsigned long long*)KA, Mtot, pwgrp, ptoff, (int)k0, (int)np, pst, (const long long*)mlo.in(d),
+                                   (const long long*)mn.in(d), pmode);
+                }
+            }
+            if (kde)
+                launch_checked(c, k_dens_bw, dim3((unsigned)((G * kbb + 255) / 256)), dim3(256), 0, (const double*)col,
+                               (const unsigned long long*)KA, Mtot, pG0, pgm, pgch0, NC, (int)G, (int)k0, kbb, (int)np, pst,
+                               (const double*)cdev.in(d), pbw, prng, obw.in(d), glo.in(d), ghi.in(d), kst.in(d));
+            for (const GB& b : plan) {   // (none without a curve asked for)
+                if (b.nc > 0)
+                    launch_checked(c, k_dens_kde, dim3(b.nc, (unsigned)((NG + DENS_TILE - 1) / DENS_TILE), kbb), dim3(DENS_WG),
+                                   (size_t)STATS_LDS_N * 8, (const double*)col, Mtot, pcst, pclen, pcgrp, b.c0, (int)k0, (int)np, (int)NG, pkst,
+                                   (const double*)obw.in(d), (const double*)glo.in(d), (const double*)ghi.in(d), csk.in(d));
+                launch_checked(c, k_dens_finish, dim3((unsigned)b.gn, kbb), dim3(64), 0, (const double*)csk.in(d), pgm, pgch0, (int)b.g0, b.c0,
+                               b.nc, (int)k0, (int)np, (int)NG, pkst, (const double*)obw.in(d), (const double*)glo.in(d),
+                               (const double*)ghi.in(d), out->grid ? gridb.in(d) : (double*)nullptr,
+                               out->density ? densb.in(d) : (double*)nullptr, out->kde_mode ? okmode.in(d) : (double*)nullptr);
+                // the batch's [gn][kbb][n_grid] block to its place in the caller's [G][np][n_grid]
+                // (contiguous there when the batch holds every parameter)
+                const size_t rows = (size_t)kbb == np ? 1 : b.gn, per = (size_t)kbb * NG * (b.gn / rows);
+                for (size_t gl = 0; gl < rows; ++gl) {
+                    const size_t at = ((b.g0 + gl) * np + k0) * NG;
+                    down(c, d, gridb.at(gl * per), out->grid ? out->grid + at : nullptr, per);
+                    down(c, d, densb.at(gl * per), out->density ? out->density + at : nullptr, per);
+                }
+                HIPCHK(hipStreamSynchronize(c->stream));   // (the next batch reuses the tables)
+            }
+        }
+        down(c, d, status, out->status, G * np); down(c, d, kst, out->kde_status, G * np);
+        down(c, d, hlo, out->hdi_lo, NM * G * np); down(c, d, hhi, out->hdi_hi, NM * G * np);
+        down(c, d, omode, out->mode, G * np); down(c, d, obw, out->bw, G * np);
+        if (NG > 0) down(c, d, okmode, out->kde_mode, G * np);
+        HIPCHK(hipStreamSynchronize(c->stream));
         return SMM_OK;
     });
 }

@@ -79,6 +79,7 @@ using namespace smm;
 #include "smm_profile.hpp"
 #include "smm_trace.hpp"
 #include "smm_rank.hpp"
+#include "smm_density.hpp"
 #include "smm_draws.hpp"
 #include "smm_population.hpp"
 

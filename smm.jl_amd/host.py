@@ -595,6 +595,88 @@ def histogram2d(x, pair, bins=10, range=None, window=None, accepted_only=True, s
     return out[0] if j is not None else out
 
 
+def _density_call(x, window, accepted_only, state, **kw):
+    """(chain index or None, the device's density dict) of a chain (alone in group 0) or of the groups of an algo"""
+    if isinstance(x, BGPChain):
+        algo, j = x._algo, x._j
+        g = np.full(algo._ctx.N, -1, np.int32)
+        g[j] = 0
+        kw["n_groups"] = 1
+    else:
+        algo, j = x, None
+        g = np.asarray(_default_groups(algo) if kw.get("groups") is None else kw["groups"], np.int32)
+    kw.pop("groups", None)
+    t0, t1 = (0, algo.i) if window is None else (int(window[0]), int(window[1]))
+    sel = "state" if state else "accepted" if accepted_only else "all"
+    return j, algo._ctx.density(t0, t1, sel, g, **kw)
+
+
+def _density_raise(st):
+    """a column the device could not summarise (include/smmhip.h: smm_get_density's status)"""
+    if st == 1:
+        raise ValueError("a draw of the column is not finite")
+    if st == 2:
+        raise ValueError("the column holds no draw")
+
+
+def hdi(x, mass=0.94, window=None, accepted_only=True, state=False, groups=None):
+    """the highest-density interval of every parameter: the shortest interval holding `mass` of the draws (ArviZ's hdi of a unimodal
+    sample; CI and the quantiles are equal-tailed), found on the device (include/smmhip.h: smm_get_density) without downloading the
+    history: an OrderedDict name -> (lo, hi) for a chain, a list of them (one per group) for an algo, whose groups default to those of
+    rhat / pooled.  window, accepted_only, state as in histogram()"""
+    names = ps2s_names(x.m)
+    j, r = _density_call(x, window, accepted_only, state, groups=groups, mass=(float(mass),), n_grid=0)
+    out = []
+    for g in _builtins_range(r["count"].shape[0]):
+        d = OrderedDict()
+        for i, k in enumerate(names):
+            _density_raise(r["status"][g, i])
+            d[k] = (float(r["hdi_lo"][0, g, i]), float(r["hdi_hi"][0, g, i]))
+        out.append(d)
+    return out[0] if j is not None else out
+
+
+def mode(x, window=None, accepted_only=True, state=False, groups=None):
+    """the half-sample mode of every parameter's draws (Bickel & Fruehwirth 2006: the marginal posterior mode, which `best`, the argmin
+    of the objective, is not), found on the device (smm_get_density): an OrderedDict name -> mode for a chain, a list of them (one per
+    group) for an algo.  Arguments as hdi()"""
+    names = ps2s_names(x.m)
+    j, r = _density_call(x, window, accepted_only, state, groups=groups, mass=(), n_grid=0)
+    out = []
+    for g in _builtins_range(r["count"].shape[0]):
+        d = OrderedDict()
+        for i, k in enumerate(names):
+            _density_raise(r["status"][g, i])
+            d[k] = float(r["mode"][g, i])
+        out.append(d)
+    return out[0] if j is not None else out
+
+
+def kde(x, n_grid=128, bw=None, range=None, window=None, accepted_only=True, state=False, groups=None):
+    """the Gaussian kernel density of every parameter's draws on a grid of n_grid points, summed on the device (smm_get_density) without
+    downloading the history: an OrderedDict name -> (grid, density, bandwidth) for a chain, a list of them (one per group) for an algo.
+    bw: a bandwidth, one per parameter (in order) or name -> bandwidth, None: R's bw.nrd0 of the column; range: [np][2] or
+    name -> (lo, hi), None: three bandwidths past the column's extremes.  A column without a usable bandwidth (fewer than two draws)
+    or with a grid whose width is not finite raises"""
+    names = ps2s_names(x.m)
+    if isinstance(bw, dict):
+        bw = [bw[k] for k in names]
+    j, r = _density_call(x, window, accepted_only, state, groups=groups, mass=(), n_grid=int(n_grid), bw=bw,
+                         range=_hist_range(range, names))
+    out = []
+    for g in _builtins_range(r["count"].shape[0]):
+        d = OrderedDict()
+        for i, k in enumerate(names):
+            _density_raise(r["status"][g, i])
+            if r["kde_status"][g, i] == 1:
+                raise ValueError("no usable bandwidth for {} (bw = {})".format(k, r["bw"][g, i]))
+            if r["kde_status"][g, i] == 2:
+                raise ValueError("the grid of {} has a width that is not finite".format(k))
+            d[k] = (r["grid"][g, i].copy(), r["density"][g, i].copy(), float(r["bw"][g, i]))
+        out.append(d)
+    return out[0] if j is not None else out
+
+
 def _profile_call(x, window, accepted_only, state, **kw):
     """(chain index or None, the device's profile dict) of a chain (alone in group 0) or of the groups of an algo"""
     if isinstance(x, BGPChain):
