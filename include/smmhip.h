@@ -933,6 +933,57 @@ int  smm_get_density(void* ctx, int32_t t0, int32_t t1, int32_t select, const in
                      const double* mass, int32_t n_mass, int32_t n_grid, const double* range /* [np][2] or NULL */,
                      const double* bw /* [np] or NULL */, smm_density_t* out);
 
+/* The posterior of user functions of each draw — Stan's "generated quantities": an elasticity, a ratio of two parameters, a welfare
+ * number, an untargeted statistic built from the simulated moments, each with its interval, computed on the device from the history it
+ * holds without downloading it (the delta method on smm_get_moment_stats' Jacobian is a linearisation that the draws make unnecessary).
+ *
+ * smm_register_user_transform(source, n_out, &id): the source is HIP/C++ text defining ONE function with this exact signature
+ * (SMM_USER_TRANSFORM expands to the required linkage):
+ *
+ *   SMM_USER_TRANSFORM(const double* theta, int np, const double* sim_moments, int nm, double value,
+ *                      const double* mom, const double* w, const double* udata, int n_udata,
+ *                      const double* tdata, int n_tdata, double* out, int n_out)
+ *
+ * It must be a deterministic function of its arguments: theta, sim_moments and value of one history row exactly as smm_get_history
+ * returns them, the context's mom, w and udata = obj_params, and tdata, a vector given per call (the policy values of a counterfactual,
+ * say).  out[0..n_out) holds NaN on entry; an output left unwritten stays NaN.  It may call smm_exp(double) and smm_log(double), the
+ * contract's functions (above), at global scope.  1 <= n_out <= 64.  Compiled at registration with the user objectives' options
+ * (hiprtc, --offload-arch=gfx950 -O3 -ffp-contract=off -fno-fast-math -std=c++17), which make + - * /, sqrt, smm_exp and smm_log
+ * reproducible bit for bit.  The handles are a range of their own (from 0), not the objectives'.  SMM_ERR_INVALID_ARG: a NULL argument,
+ * n_out outside [1, 64], or a source that does not compile (the compiler's log in smm_last_error(NULL)); SMM_ERR_HIP: no hiprtc.
+ *
+ * smm_get_derived(ctx, id, ...), with Q = the transform's n_out: group g's pooled rows are those of smm_get_histogram — the members in
+ * ascending local index, each in iteration order; select 0 all rows of [t0, t1), 1 the rows with accepted != 0, 2 the state series, row
+ * a(t) looking back before t0; groups, group NULL with n_groups == 1 and shards as in smm_get_group_stats (a shard reports its own
+ * local chains).  The derived column q of a group is y_q[i] = output q of the function on pooled row i; for a select 2 row with no a(t)
+ * the function is not called and every output of the row is NaN.  Caller-allocated; any pointer may be NULL (not computed).  Read-only
+ * and ordered like smm_get_chain_stats (it settles, flushes and synchronises, and changes no state, history or generator).  Device
+ * memory: the reducers' scratch and result buffer.  An output takes 8 bytes per pooled row of the scratch and goes with as many other
+ * outputs as fit beside the row indexes of one chunk of 8192 rows (the scratch is grown, up to 256 MiB, to every output and row index
+ * of the context's capacity, and beyond that where needed to one output); the rows go through the function in batches of chunks,
+ * every batch of outputs runs the function on every row again, and so does cov, which takes one chunk of every output at a time or
+ * more.  SMM_ERR_INVALID_ARG: NULL ctx or out, an unknown transform_id, a bad window,
+ * select outside [0, 2], n_groups < 0, group NULL with n_groups != 1, a group id outside [-1, n_groups), n_probs < 0, probs NULL with
+ * n_probs > 0, a prob outside [0, 1], quantile requested without probs, n_tdata < 0 or > 4096, tdata NULL with n_tdata > 0; nothing is
+ * written then.
+ *
+ * Numerical contract: mean, median, quantile and cov are smm_get_group_stats' on the columns y_q in place of the parameter columns
+ * (the chunked pairwise sum over chunks of 8192 rows from the group's first row, numpy's _lerp order statistics on the IEEE total
+ * order, cov = S(d_j d_k) / (m - 1) with d = y - mean); NaN propagates as it does there; m == 0: NaN everywhere; m < 2: cov NaN.
+ * Values that are not finite are not dropped: n_nonfinite counts the rows of each column that are NaN or +-inf. */
+typedef struct {            /* caller-allocated; any pointer may be NULL = not computed */
+    int64_t* count;         /* [G]        selected rows pooled in the group                   */
+    int32_t* n_chains;      /* [G]                                                            */
+    int64_t* n_nonfinite;   /* [G][Q]     rows whose output q is NaN or +-inf                 */
+    double*  mean;          /* [G][Q]                                                         */
+    double*  median;        /* [G][Q]                                                         */
+    double*  quantile;      /* [n_probs][G][Q]                                                */
+    double*  cov;           /* [G][Q][Q]  both triangles                                      */
+} smm_derived_t;
+int  smm_register_user_transform(const char* hip_source, int32_t n_out, int32_t* transform_id_out);
+int  smm_get_derived(void* ctx, int32_t transform_id, int32_t t0, int32_t t1, int32_t select, const int32_t* group /* [N] or NULL */,
+                     int32_t n_groups, const double* tdata, int32_t n_tdata, const double* probs, int32_t n_probs, smm_derived_t* out);
+
 /* Covariances of the chains' draws and the proposal factor between steps — adaptive Metropolis (Haario et al.) on top of chol_L: a
  * pilot run, then each chain's proposal shaped by the covariance of its own draws, without leaving the device.
  *

@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_adjustment, hip_profile, hip_density, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_adjustment, hip_profile, hip_density, hip_register_transform, hip_derived, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_set_population!, hip_scatter_population!
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
@@ -202,6 +202,16 @@ struct SmmDensity
     grid::Ptr{Cdouble}
     density::Ptr{Cdouble}
     kde_mode::Ptr{Cdouble}
+end
+
+struct SmmDerived
+    count::Ptr{Int64}
+    n_chains::Ptr{Int32}
+    n_nonfinite::Ptr{Int64}
+    mean::Ptr{Cdouble}
+    median::Ptr{Cdouble}
+    quantile::Ptr{Cdouble}
+    cov::Ptr{Cdouble}
 end
 
 struct SmmGroupStats
@@ -705,6 +715,53 @@ function hip_density(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :acce
     end
     return (count = count, status = st, hdi_lo = hlo, hdi_hi = hhi, mode = md, bw = obw, kde_status = kst, grid = grid, density = dens,
             kde_mode = kmode)
+end
+
+"""
+    hip_register_transform(src, n_out) -> transform id
+
+A user function of one history row for `hip_derived` (include/smmhip.h): `src` defines
+`SMM_USER_TRANSFORM(theta, np, sim_moments, nm, value, mom, w, udata, n_udata, tdata, n_tdata, out, n_out)`, a deterministic function
+writing `out[0 .. n_out)` (NaN on entry), `1 <= n_out <= 64`; it may call `smm_exp` and `smm_log`.  Throws with the compiler's log if
+the source does not compile.
+"""
+function hip_register_transform(src::AbstractString, n_out::Integer)
+    id = Ref{Int32}(-1)
+    rc = ccall(sym(:smm_register_user_transform), Cint, (Cstring, Int32, Ref{Int32}), src, Int32(n_out), id)
+    rc == 0 || throw(SMMHipError(Int(rc), last_error(Ptr{Cvoid}(C_NULL))))
+    return Int(id[])
+end
+
+"""
+    hip_derived(h, transform, n_out, t0, t1; select = :accepted, groups = nothing, probs = Float64[], tdata = Float64[]) -> NamedTuple
+
+The posterior of a user function of each draw (Stan's generated quantities) over the pooled rows of groups of chains over iterations
+`t0+1 .. t1`, evaluated and summarised on the device (`smm_get_derived`) without downloading the history.  `transform`, `n_out`: the
+handle of `hip_register_transform` and its outputs; `select` and `groups` as `hip_histogram`; `tdata`: the vector the function
+receives as `tdata`.  Returns `count[g]`, `n_chains[g]`, `n_nonfinite[q, g]`, `mean[q, g]`, `median[q, g]`, `quantile[q, g, p]`,
+`cov[q, q2, g]` (the header's row-major arrays).
+"""
+function hip_derived(h::HipBGP, transform::Integer, n_out::Integer, t0::Integer, t1::Integer; select::Symbol = :accepted,
+                     groups::Union{Nothing,AbstractVector{<:Integer}} = nothing, probs::AbstractVector{<:Real} = Float64[],
+                     tdata::AbstractVector{<:Real} = Float64[])
+    N, Q = h.N, Int(n_out)
+    g = groups === nothing ? Int32[] : Vector{Int32}(groups)
+    groups === nothing || length(g) == N || throw(ArgumentError("groups needs one entry per chain"))
+    ng = groups === nothing ? 1 : (isempty(g) ? 0 : Int(maximum(g)) + 1)
+    pr = Vector{Float64}(probs); td = Vector{Float64}(tdata)
+    npr, ntd = length(pr), length(td)
+    count = Vector{Int64}(undef, ng); nch = Vector{Int32}(undef, ng); nnf = Matrix{Int64}(undef, Q, ng)
+    mean = Matrix{Float64}(undef, Q, ng); med = Matrix{Float64}(undef, Q, ng); quant = Array{Float64}(undef, Q, ng, npr)
+    cov = Array{Float64}(undef, Q, Q, ng)
+    opt(a, T, on) = on ? pointer(a) : Ptr{T}(C_NULL)
+    GC.@preserve g pr td count nch nnf mean med quant cov begin
+        ds = SmmDerived(pointer(count), pointer(nch), pointer(nnf), pointer(mean), pointer(med), opt(quant, Cdouble, npr > 0), pointer(cov))
+        check(h.ctx, ccall(sym(:smm_get_derived), Cint,
+                           (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Int32}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ref{SmmDerived}),
+                           h.ctx, transform, t0, t1, HIST_SELECT[select], groups === nothing ? Ptr{Int32}(C_NULL) : pointer(g), ng,
+                           opt(td, Cdouble, ntd > 0), ntd, opt(pr, Cdouble, npr > 0), npr, ds))
+    end
+    return (count = count, n_chains = nch, n_nonfinite = nnf, mean = mean, median = med, quantile = quant, cov = cov)
 end
 
 """

@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, profile_objective, posterior_density, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -449,6 +449,32 @@ function posterior_density(algo::MAlgoBGPHip; window = nothing, select::Symbol =
         groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
     end
     return SMMHip.hip_density(hip, t0, t1; select = select, groups = groups, mass = mass, n_grid = n_grid, range = range, bw = bw)
+end
+
+"""
+    posterior_derived(algo, source, n_out; window = nothing, select = :accepted, groups = nothing, probs = [0.025, 0.975],
+                      tdata = Float64[]) -> NamedTuple
+
+The posterior of a function of the parameters and the simulated moments (Stan's generated quantities: an elasticity, a ratio of two
+parameters, a welfare number, an untargeted statistic), evaluated on every pooled draw and summarised on the device from the history
+it holds (`SMMHip.hip_derived`), without `sync_chains!` and without the delta method's linearisation.  `source`: HIP text defining
+`SMM_USER_TRANSFORM(theta, np, sim_moments, nm, value, mom, w, udata, n_udata, tdata, n_tdata, out, n_out)` (include/smmhip.h), or the
+handle `SMMHip.hip_register_transform` gave for it; `tdata`: the vector it receives as `tdata`.  Per group and output `mean[q, g]`,
+`median[q, g]`, `quantile[q, g, p]`, `cov[q, q2, g]` and `n_nonfinite[q, g]`, the rows whose output is NaN or infinite (they are not
+dropped).  Groups and window as `chain_histogram`.  Not a method of `SMM`.
+"""
+function posterior_derived(algo::MAlgoBGPHip, source, n_out::Integer; window = nothing, select::Symbol = :accepted, groups = nothing,
+                           probs::AbstractVector{<:Real} = [0.025, 0.975], tdata::AbstractVector{<:Real} = Float64[])
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    t0, t1 = window === nothing ? (0, SMMHip.hip_iter(hip)) : window
+    if groups === nothing
+        ids = Dict{Float64,Int32}()
+        opts = getfield(algo, :opts)
+        groups = [get!(ids, a, Int32(length(ids))) for a in chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))]
+    end
+    id = source isa Integer ? Int(source) : SMMHip.hip_register_transform(source, n_out)
+    return SMMHip.hip_derived(hip, id, n_out, t0, t1; select = select, groups = groups, probs = probs, tdata = tdata)
 end
 
 """

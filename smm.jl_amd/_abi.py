@@ -178,6 +178,13 @@ class smm_density_t(C.Structure):
     ]
 
 
+class smm_derived_t(C.Structure):
+    _fields_ = [
+        ("count", C.POINTER(C.c_int64)), ("n_chains", c_int32_p), ("n_nonfinite", C.POINTER(C.c_int64)), ("mean", c_double_p),
+        ("median", c_double_p), ("quantile", c_double_p), ("cov", c_double_p),
+    ]
+
+
 class smm_population_t(C.Structure):
     _fields_ = [
         ("start", c_double_p), ("value", c_double_p), ("pick", c_int32_p), ("evaluated", C.c_int64),
@@ -246,6 +253,9 @@ SYMBOLS = [
                                    C.c_int32, C.c_int32, C.POINTER(smm_profile_t)]),
     ("smm_get_density", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_double_p, C.c_int32, C.c_int32,
                                    c_double_p, c_double_p, C.POINTER(smm_density_t)]),
+    ("smm_register_user_transform", C.c_int, [C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
+    ("smm_get_derived", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_double_p, C.c_int32,
+                                   c_double_p, C.c_int32, C.POINTER(smm_derived_t)]),
     ("smm_get_chain_cov", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
     ("smm_get_proposal", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_proposal", C.c_int, [C.c_void_p, c_double_p]),

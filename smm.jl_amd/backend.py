@@ -413,6 +413,23 @@ class BGPContext:
                                             A.dptr(rg) if rg is not None else None, A.dptr(bwv) if bwv is not None else None, C.byref(s)))
         return r
 
+    def derived(self, transform, t0=0, t1=None, select="accepted", groups=None, probs=(), tdata=(), n_groups=None):
+        """the posterior of a user function of each draw, over the pooled rows of groups of local chains over iterations [t0, t1), on
+        the device (smm_get_derived, include/smmhip.h): a dict of numpy arrays count / n_chains [n_groups], n_nonfinite / mean / median
+        [n_groups][Q], quantile [len(probs)][n_groups][Q], cov [n_groups][Q][Q], Q = the transform's n_out.  transform: what
+        user_transform() returned; select, groups and n_groups as in histogram(); tdata: the call's vector for the function"""
+        t1 = self._t1(t1)
+        sel = self._select(select)
+        g, gp, ng = self._groups("derived", groups, n_groups)
+        p, td = A.f64(probs).reshape(-1), A.f64(tdata).reshape(-1)
+        Q = transform.n_out
+        r = dict(count=np.empty(ng, np.int64), n_chains=np.empty(ng, np.int32), n_nonfinite=np.empty((ng, Q), np.int64),
+                 mean=np.empty((ng, Q)), median=np.empty((ng, Q)), quantile=np.empty((len(p), ng, Q)), cov=np.empty((ng, Q, Q)))
+        s = self._out(A.smm_derived_t, r, () if len(p) else ("quantile",))
+        self._check(self._fn("get_derived")(self._ctx, transform.handle(self._lib), int(t0), int(t1), sel, gp, ng,
+                                            A.dptr(td) if len(td) else None, len(td), A.dptr(p) if len(p) else None, len(p), C.byref(s)))
+        return r
+
     def trace(self, t0=0, t1=None, stride=1, select="state", moments=False, groups=None, probs=(), n_groups=None):
         """the population per iteration over the kept iterations t0, t0 + stride, .. < t1, reduced across the chains of each group on the
         device (smm_get_trace, include/smmhip.h): a dict of numpy arrays iter [nt], n_chains [n_groups], count / n_accepted / n_exchanged /
@@ -658,6 +675,33 @@ def register_user_objective(source, n_sums=None, lanes=256, rng=False):
     if rc != 0:
         raise RuntimeError("smm_register_user_objective failed (%d): %s" % (rc, lib.smm_last_error(None).decode()))
     return int(oid.value)
+
+
+class UserTransform:
+    """a user function of one history row (SMM_USER_TRANSFORM, include/smmhip.h) with n_out outputs: compiled for the device when it is
+    made, its handle kept per loaded library (the handles of smm_register_user_transform are the library's own)"""
+
+    def __init__(self, source, n_out):
+        self.source, self.n_out = source, int(n_out)
+        self._handles = {}
+        self.handle(A.load())
+
+    def handle(self, lib):
+        if id(lib) not in self._handles:
+            tid = C.c_int32(-1)
+            rc = lib.smm_register_user_transform(self.source.encode(), self.n_out, C.byref(tid))
+            if rc != 0:
+                raise A.SMMHipError(rc, "smm_register_user_transform failed: %s" % lib.smm_last_error(None).decode())
+            self._handles[id(lib)] = int(tid.value)
+        return self._handles[id(lib)]
+
+
+def user_transform(source, n_out):
+    """Compile a user transform for the device (smm_register_user_transform, include/smmhip.h): `source` defines
+    SMM_USER_TRANSFORM(theta, np, sim_moments, nm, value, mom, w, udata, n_udata, tdata, n_tdata, out, n_out), a deterministic function of
+    one history row writing out[0 .. n_out); it may call smm_exp and smm_log.  Returns what BGPContext.derived and host.derived take.
+    Raises SMMHipError with the compiler's log if the source does not compile."""
+    return UserTransform(source, n_out)
 
 
 def hip_context(problem, opts, tables=None):

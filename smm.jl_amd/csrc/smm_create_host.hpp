@@ -421,6 +421,7 @@ void smm_ctx_destroy(void* ctx) {
     if (c->red_res) (void)hipFree(c->red_res);
     if (c->umod) (void)hipModuleUnload(c->umod);
     if (c->pmod) (void)hipModuleUnload(c->pmod);
+    for (const auto& tm : c->tmods) (void)hipModuleUnload(tm.second);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->pev) (void)hipEventDestroy(e);

@@ -1,9 +1,9 @@
 // the host side of the history reducers — part of libsmmhip (included once by smmhip.hip, behind its host helpers; hiprtc never sees it).
 // The family: smm_get_chain_stats, smm_get_chain_cov, smm_get_proposal / _set_ / _adapt_, smm_get_chain_diag, smm_get_group_stats,
 // smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws, smm_get_moment_stats, smm_get_adjustment, smm_get_profile,
-// smm_get_density (kernels:
+// smm_get_density, smm_get_derived (kernels:
 // smm_stats.hpp, smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_moments.hpp, smm_adjust.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp,
-// smm_draws.hpp, smm_profile.hpp, smm_density.hpp;
+// smm_draws.hpp, smm_profile.hpp, smm_density.hpp, smm_derived.hpp and, around a user's transform, smm_user_host.hpp's kernel text;
 // the walk over a chain's window that their gathers share: smm_window.hpp).
 // What they share is stated here once: the frame of a call (api_call of smmhip.hip), the checks of the arguments they have in common (check_groups,
 // check_probs, check_select), the prelude and the window behind them (settled_window: reader_prelude and check_window of smmhip.hip), the
@@ -1750,6 +1750,167 @@ int smm_get_density(void* ctx, int32_t t0, int32_t t1, int32_t select, const int
         down(c, d, omode, out->mode, G * np); down(c, d, obw, out->bw, G * np);
         if (NG > 0) down(c, d, okmode, out->kde_mode, G * np);
         HIPCHK(hipStreamSynchronize(c->stream));
+        return SMM_OK;
+    });
+}
+
+}  // extern "C"
+
+// --- the posterior of user functions of each draw (smm_derived.hpp; the kernel around the user's function: smm_user_host.hpp) -----------
+
+namespace {
+
+// the kernel of a registered transform in this context: its module is loaded when the context first asks for it
+hipFunction_t derived_kernel(Ctx* c, int32_t transform_id) {
+    hipModule_t mod = nullptr;
+    for (const auto& tm : c->tmods)
+        if (tm.first == transform_id) mod = tm.second;
+    if (!mod) {
+        int n_out = 0;
+        std::vector<char> code;
+        user_transform_get(transform_id, &n_out, &code);
+        HIPCHK(hipModuleLoadData(&mod, code.data()));
+        c->tmods.emplace_back(transform_id, mod);
+    }
+    hipFunction_t fn = nullptr;
+    HIPCHK(hipModuleGetFunction(&fn, mod, "smm_user_transform_kernel"));
+    return fn;
+}
+
+// rows a workgroup of the transform's kernel stages: 256, or what 64 KiB of LDS hold at HW + 1 doubles and an index per row (whole
+// waves where that is 64 or more)
+constexpr size_t DERIVED_LDS_BYTES = (size_t)64 << 10;
+int derived_rows_per_wg(int HW) {
+    const int fit = (int)(DERIVED_LDS_BYTES / ((size_t)(HW + 2) * 8));
+    return fit >= 256 ? 256 : fit >= 64 ? fit & ~63 : fit;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smm_get_derived(void* ctx, int32_t transform_id, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups,
+                    const double* tdata, int32_t n_tdata, const double* probs, int32_t n_probs, smm_derived_t* out) {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        int n_out = 0;
+        if (!user_transform_get(transform_id, &n_out, nullptr))
+            return fail(c, SMM_ERR_INVALID_ARG, "transform_id is no handle of smm_register_user_transform");
+        if (const int rc = check_select(c, select)) return rc;
+        if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
+        if (const int rc = check_probs(c, probs, n_probs, out->quantile != nullptr)) return rc;
+        if (n_tdata < 0 || n_tdata > 4096 || (n_tdata > 0 && !tdata))
+            return fail(c, SMM_ERR_INVALID_ARG, "n_tdata outside [0, 4096], or tdata NULL with n_tdata > 0");
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t N = P.N, Q = n_out, G = n_groups, nq = out->quantile ? n_probs : 0, L = STATS_LDS_N;
+        const int n = t1 - t0;
+        const bool med = out->median != nullptr, ord = med || nq > 0, cov = out->cov != nullptr,
+                   cols = out->mean || ord || cov || out->n_nonfinite;
+        const Groups grp = group_members(group, G, N);
+        DevBuf<int> dci(2 * N);
+        const PoolPlan pp = pool_plan(grp, pool_counts(c, grp, t0, n, select, dci.p));
+        const OrderPlan op = order_plan(c, pp, med, probs, nq);
+        const long long Mtot = pp.Mtot;
+        const int NC = pp.NC;
+        std::vector<int> cgrp(NC);
+        for (size_t g = 0; g < G; ++g)
+            for (int ch = pp.gch0[g]; ch < pp.gch0[g + 1]; ++ch) cgrp[ch] = (int)g;
+        // the plan.  The scratch holds the packed columns of a batch of outputs, [qb][Mtot], and behind them the row indexes of a batch
+        // of chunks (rcap rows: at least one chunk); for the covariance, every output of a batch of chunks centred, [Q][Nbc][8192], and
+        // behind them the batch's row indexes.  A batch of either kind runs the transform again, so the scratch is grown to every
+        // output and the row indexes of the context's whole capacity where the cap allows that.
+        size_t qb = 0, rcap = 0, Nbc = 0;
+        if (Mtot > 0 && cols) {
+            const size_t cap_rows = N * (size_t)P.T;
+            reducer_scratch(c, std::max({(cap_rows + L) * 8, cov ? (Q + 1) * L * 8 : 0, std::min(reducer_batch_cap(c), (Q + 1) * cap_rows * 8)}));
+            const size_t least = std::max(((size_t)Mtot + L) * 8, cov ? (Q + 1) * L * 8 : 0), hook = c->H.stats_scratch;
+            const size_t budget = hook ? std::min(c->st_scr_bytes, std::max(hook, least)) : c->st_scr_bytes;
+            qb = std::min(Q, (budget - L * 8) / ((size_t)Mtot * 8));
+            rcap = (budget - qb * (size_t)Mtot * 8) / 8;
+            Nbc = std::min<size_t>(NC, budget / ((Q + 1) * L * 8));
+        }
+        Carve Rv;   // 8-byte slices first
+        const auto mean = Rv.take<double>(G * Q), median = Rv.take<double>(G * Q), quant = Rv.take<double>(nq * G * Q),
+                   covo = Rv.take<double>(cov ? G * Q * Q : 0), csum = Rv.take<double>(qb * NC),
+                   csum2 = Rv.take<double>(cov ? Q * Q * NC : 0), dtd = Rv.take<double>(n_tdata);
+        const auto nnf = Rv.take<unsigned long long>(G * Q);
+        const PoolDev pd(Rv, pp, op, op.wgrp.size() * qb);   // (the long columns of a batch of outputs)
+        const auto cnan = Rv.take<int>(qb * NC), gnan = Rv.take<int>(G * Q), dcgrp = Rv.take<int>(NC);
+        void* d = reducer_result(c, Rv.bytes);
+        pd.upload(c, d, pp, op);
+        up(c, d, dtd, tdata, n_tdata); up(c, d, dcgrp, cgrp);
+        HIPCHK(hipMemsetAsync(nnf.in(d), 0, G * Q * 8, c->stream));
+        const int *dgid = dci.p, *dcnt = dci.p + N, *dgch0 = pd.gch0.in(d), *dclen = pd.clen.in(d);
+        const long long* dgm = pd.gm.in(d);
+        if (qb > 0) {
+            const hipFunction_t fn = derived_kernel(c, transform_id);
+            const int R = derived_rows_per_wg(P.HW);
+            const size_t smem = (size_t)R * (P.HW + 2) * 8;
+            double* col = (double*)c->st_scr;
+            // the chunks [cb0, cb0 + nb) through the transform: their rows' indexes (k_derived_rows), then the user's kernel, which
+            // stores the outputs [q0, q0 + qn) packed (chunked == 0: col [qn][Mtot]) or all of them centred and chunked ([Q][nb][8192])
+            auto transform = [&](int cb0, int nb, int q0, int qn, int chunked, long long* ridx) {
+                long long p0 = pp.cst[cb0], p1 = pp.cst[cb0 + nb - 1] + pp.clen[cb0 + nb - 1], cstride = chunked ? (long long)L : Mtot;
+                launch_checked(c, k_derived_rows, dim3(N), dim3(WINDOW_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, dgid,
+                               (const long long*)pd.off.in(d), dcnt, p0, p1, ridx);
+                int longest = 0;
+                for (int ch = cb0; ch < cb0 + nb; ++ch) longest = std::max(longest, pp.clen[ch]);
+                // (tdata is never NULL on the device: a function that reads past n_tdata == 0 reads the result buffer, not address 0)
+                const double *hrec = P.hrec, *mom = P.mom, *w = P.w, *ud = P.objp, *td = dtd.in(d), *gmean = mean.in(d);
+                const long long *cridx = ridx, *cst = pd.cst.in(d);
+                const int* pcgrp = dcgrp.in(d);
+                int HW = P.HW, np = P.np, nm = P.nm, nud = c->n_objp, ntd = n_tdata, rows = R;
+                unsigned long long* pnnf = nnf.in(d);
+                void* args[] = {(void*)&hrec, (void*)&HW, (void*)&np, (void*)&nm, (void*)&cridx, (void*)&p0, (void*)&cst, (void*)&dclen,
+                                (void*)&pcgrp, (void*)&cb0, (void*)&rows, (void*)&mom, (void*)&w, (void*)&ud, (void*)&nud, (void*)&td,
+                                (void*)&ntd, (void*)&q0, (void*)&qn, (void*)&cstride, (void*)&chunked, (void*)&nb, (void*)&gmean,
+                                (void*)&col, (void*)&pnnf};
+                HIPCHK(hipModuleLaunchKernel(fn, (unsigned)((longest + R - 1) / R), (unsigned)nb, 1, 256, 1, 1, (unsigned)smem, c->stream, args,
+                                             nullptr));
+            };
+            for (size_t q0 = 0; q0 < Q; q0 += qb) {   // batches of outputs: the packed columns [qn][Mtot], filled in batches of chunks
+                const int qn = (int)std::min(qb, Q - q0);
+                long long* ridx = (long long*)(col + (size_t)qn * Mtot);
+                for (int cb0 = 0, nb; cb0 < NC; cb0 += nb) {
+                    size_t rows = pp.clen[cb0];
+                    for (nb = 1; cb0 + nb < NC && rows + pp.clen[cb0 + nb] <= rcap; ++nb) rows += pp.clen[cb0 + nb];
+                    transform(cb0, nb, (int)q0, qn, 0, ridx);
+                }
+                launch_checked(c, k_group_chunk_sum, dim3(NC, qn), dim3(STATS_WG), (size_t)STATS_LDS_N * 8, (const double*)col, Mtot,
+                               (const long long*)pd.cst.in(d), dclen, NC, csum.in(d), cnan.in(d));
+                launch_checked(c, k_group_mean, dim3((unsigned)((G * qn + 255) / 256)), dim3(256), 0, (const double*)csum.in(d),
+                               (const int*)cnan.in(d), NC, dgch0, dgm, (int)G, (int)q0, qn, (int)Q, mean.in(d), gnan.in(d));
+                if (ord)
+                    pool_order(c, d, pd, pp, op, col, qn, (int)q0, (int)Q, gnan.in(d), med ? median.in(d) : nullptr, quant.in(d));
+            }
+            if (cov) {   // batches of chunks: every output recomputed and centred; each chunk's pair sums, then the groups'
+                const int nt = ((int)Q + COV_T - 1) / COV_T, ntiles = nt * (nt + 1) / 2;
+                for (int cb0 = 0; cb0 < NC; cb0 += (int)Nbc) {
+                    const int nb = std::min((int)Nbc, NC - cb0);
+                    transform(cb0, nb, 0, (int)Q, 1, (long long*)(col + Q * (size_t)nb * L));
+                    launch_checked(c, k_cov_pairs, dim3(nb, ntiles), dim3(COV_WG), 0, (const double*)col, STATS_LDS_N, NC, cb0, nb, (int)Q,
+                                   dclen, csum2.in(d), 1);
+                }
+            }
+        }
+        if (cov && G > 0)
+            launch_checked(c, k_group_cov, dim3((unsigned)((G * Q * (Q + 1) / 2 + 255) / 256)), dim3(256), 0, (const double*)csum2.in(d),
+                           NC, dgch0, dgm, (int)G, (int)Q, covo.in(d));
+        if (qb > 0) {   // (no row in any group: every summary NaN, filled below)
+            down(c, d, mean, out->mean, G * Q);
+            down(c, d, median, out->median, G * Q);
+            down(c, d, quant, out->quantile, nq * G * Q);
+        }
+        down(c, d, covo, out->cov, G * Q * Q);
+        down(c, d, nnf, out->n_nonfinite, G * Q);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (qb == 0) {
+            if (out->mean) std::fill(out->mean, out->mean + G * Q, NAN);
+            if (out->median) std::fill(out->median, out->median + G * Q, NAN);
+            if (out->quantile) std::fill(out->quantile, out->quantile + nq * G * Q, NAN);
+        }
+        if (out->count) std::copy(pp.gm.begin(), pp.gm.end(), out->count);
+        if (out->n_chains) std::copy(grp.n_chains.begin(), grp.n_chains.end(), out->n_chains);
         return SMM_OK;
     });
 }

@@ -3,6 +3,8 @@
 // the way through hiprtc (rtc_compile), the texts around a user's source (the preludes, the evaluation kernels and the map-reduce
 // reduction they share), the device headers a persistent form is made of (PERSIST_HEADERS and each form's tail), one record per
 // persistent form (UserCode, by UserForm), which of them a context wants (user_form_wanted) and how it is compiled (user_form_compile).
+// User transforms (smm_register_user_transform: functions of one history row for smm_get_derived) are registered here too, in a
+// registry of their own, with the text of the kernel that runs them (USER_KERNEL_TRANSFORM; launched by smm_reducers_host.hpp).
 #pragma once
 
 namespace {
@@ -151,6 +153,74 @@ const char* USER_KERNEL_LANES_RNG =
     "}\n";
 #undef USER_REDUCE_LANES
 
+// user transforms (smm_register_user_transform, smm_get_derived): a function of one history row, with the contract's exponential and
+// logarithm at global scope — compiled with the library's own headers (g_embedded)
+struct UserTransform { std::vector<char> code; int n_out = 0; };
+std::vector<UserTransform> g_user_transforms;   // (handle = index: a range of its own, not the objectives')
+const char* USER_PRELUDE_TRANSFORM =
+    "#include <stdint.h>\n#include \"smm_rng.hpp\"\n"
+    "__device__ inline double smm_exp(double x) { return smm::smm_exp(x); }\n"
+    "__device__ inline double smm_log(double x) { return smm::smm_log(x); }\n"
+    "#define SMM_USER_TRANSFORM extern \"C\" __device__ void smm_user_transform\n"
+    "extern \"C\" __device__ void smm_user_transform(const double* theta, int np, const double* sim_moments, int nm, double value,\n"
+    "                                              const double* mom, const double* w, const double* udata, int n_udata,\n"
+    "                                              const double* tdata, int n_tdata, double* out, int n_out);\n";
+// The rows of a batch through the user's function (SMM_NOUT = n_out, SMM_H_PARAMS / SMM_H_VALUE = the record's H_PARAMS / H_VALUE).
+// Workgroup (blockIdx.x, blockIdx.y) takes rows [R blockIdx.x, R blockIdx.x + R) of chunk cb0 + blockIdx.y (clen rows from pooled row
+// cst, all of group cgrp); ridx [pooled row - p0] is a row's index in hrec, -1: none (every output stays NaN).  The rows are read two
+// words per lane, consecutive lanes consecutive words, and staged in LDS at a stride of HW + 1 doubles (HW is even: odd, so that the
+// lanes' reads of one word of their own rows fall into different banks), the R row indexes behind them; then one lane per row.
+// Packed form (chunked == 0): outputs [q0, q0 + qb) to col [qb][cstride] at the pooled row, and the rows that are not finite counted
+// into nnf [G][SMM_NOUT] (a wave's count by its first active lane).  Chunked form: every output, centred by its group's mean gmean
+// [G][SMM_NOUT], to col [SMM_NOUT][nbc][cstride] at (chunk - cb0, row in chunk), as k_group_gather's chunked form lays them out.
+const char* USER_KERNEL_TRANSFORM =
+    "\nextern \"C\" __global__ __launch_bounds__(256) void smm_user_transform_kernel(const double* __restrict__ hrec, int HW, int np, int nm,\n"
+    "        const long long* __restrict__ ridx, long long p0, const long long* __restrict__ cst, const int* __restrict__ clen,\n"
+    "        const int* __restrict__ cgrp, int cb0, int R, const double* mom, const double* w, const double* udata, int n_udata,\n"
+    "        const double* tdata, int n_tdata, int q0, int qb, long long cstride, int chunked, int nbc, const double* __restrict__ gmean,\n"
+    "        double* __restrict__ col, unsigned long long* __restrict__ nnf) {\n"
+    "    extern __shared__ double smm_rows[];\n"
+    "    const int ch = cb0 + (int)blockIdx.y, tid = (int)threadIdx.x, i0 = (int)blockIdx.x * R, len = clen[ch];\n"
+    "    if (i0 >= len) return;\n"
+    "    const int nr = min(R, len - i0), S = HW + 1, h2 = HW >> 1;\n"
+    "    const long long pos0 = cst[ch] + i0;\n"
+    "    long long* rix = (long long*)(smm_rows + (size_t)R * S);\n"
+    "    for (int r = tid; r < nr; r += 256) rix[r] = ridx[pos0 - p0 + r];\n"
+    "    __syncthreads();\n"
+    "    for (int e = tid; e < nr * h2; e += 256) {\n"
+    "        const int r = e / h2, j = e - r * h2;\n"
+    "        const long long ri = rix[r];\n"
+    "        if (ri < 0) continue;\n"
+    "        const double2 v = ((const double2*)(hrec + (size_t)ri * HW))[j];\n"
+    "        smm_rows[r * S + 2 * j] = v.x;\n"
+    "        smm_rows[r * S + 2 * j + 1] = v.y;\n"
+    "    }\n"
+    "    __syncthreads();\n"
+    "    if (tid >= nr) return;\n"
+    "    double out[SMM_NOUT];\n"
+    "#pragma unroll\n"
+    "    for (int q = 0; q < SMM_NOUT; ++q) out[q] = __longlong_as_double(0x7ff8000000000000ll);\n"
+    "    const double* row = smm_rows + tid * S;\n"
+    "    if (rix[tid] >= 0)\n"
+    "        smm_user_transform(row + SMM_H_PARAMS, np, row + SMM_H_PARAMS + np, nm, row[SMM_H_VALUE], mom, w, udata, n_udata, tdata, n_tdata,\n"
+    "                           out, SMM_NOUT);\n"
+    "    const int g = cgrp[ch];\n"
+    "    const int first = __ffsll((long long)__ballot(1)) - 1;\n"
+    "#pragma unroll\n"
+    "    for (int q = 0; q < SMM_NOUT; ++q) {\n"
+    "        if (q < q0 || q >= q0 + qb) continue;\n"
+    "        const double v = out[q];\n"
+    "        if (chunked) {\n"
+    "            col[((size_t)q * nbc + (size_t)blockIdx.y) * cstride + i0 + tid] = v - gmean[(size_t)g * SMM_NOUT + q];\n"
+    "            continue;\n"
+    "        }\n"
+    "        col[(size_t)(q - q0) * cstride + pos0 + tid] = v;\n"
+    "        const bool bad = (__double_as_longlong(v) & 0x7ff0000000000000ll) == 0x7ff0000000000000ll;\n"
+    "        const unsigned long long m = __ballot(bad);\n"
+    "        if (m != 0ull && (tid & 63) == first) atomicAdd(&nnf[(size_t)g * SMM_NOUT + q], (unsigned long long)__popcll(m));\n"
+    "    }\n"
+    "}\n";
+
 // what a persistent form's translation unit includes behind the user's source: these, then its own kernel's headers (every one of them,
 // and what they include in turn, must be among the Makefile's EMBED: tests/test_user_objective.py compiles each form without a device)
 const char* const PERSIST_HEADERS[] = {"smm_params.hpp", "smm_walk_lean.hpp", "smm_propose.hpp", "smm_chain.hpp", "smm_p2p.hpp", "smm_chain_norm.hpp", "smm_chain_persist.hpp"};
@@ -269,9 +339,39 @@ int register_user_source(const std::string& src, int n_sums, int lanes, int32_t*
     return SMM_OK;
 }
 
+// a registered transform's outputs, and its code where the caller still has to load it (code != NULL); false: no such handle
+bool user_transform_get(int32_t transform_id, int* n_out, std::vector<char>* code) {
+    std::lock_guard<std::mutex> lock(g_user_mutex);
+    if (transform_id < 0 || transform_id >= (int32_t)g_user_transforms.size()) return false;
+    const UserTransform& u = g_user_transforms[transform_id];
+    *n_out = u.n_out;
+    if (code) *code = u.code;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
+
+int smm_register_user_transform(const char* hip_source, int32_t n_out, int32_t* transform_id_out) {
+    if (!hip_source || !transform_id_out) { g_create_err = "smm_register_user_transform: null argument"; return SMM_ERR_INVALID_ARG; }
+    if (n_out < 1 || n_out > 64) { g_create_err = "smm_register_user_transform: need 1 <= n_out <= 64"; return SMM_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lock(g_user_mutex);
+    UserTransform u;
+    u.n_out = n_out;
+    const std::string nout = "-DSMM_NOUT=" + std::to_string(n_out), hp = "-DSMM_H_PARAMS=" + std::to_string((int)H_PARAMS),
+                      hv = "-DSMM_H_VALUE=" + std::to_string((int)H_VALUE);
+    std::string log;
+    const int rc = rtc_compile(std::string(USER_PRELUDE_TRANSFORM) + hip_source + USER_KERNEL_TRANSFORM, "smm_user_transform.hip", true,
+                               {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", nout.c_str(), hp.c_str(),
+                                hv.c_str()},
+                               u.code, log);
+    if (rc < 0) { g_create_err = log; return SMM_ERR_HIP; }
+    if (rc == 0) { g_create_err = "user transform does not compile:\n" + log; return SMM_ERR_INVALID_ARG; }
+    g_user_transforms.push_back(std::move(u));
+    *transform_id_out = (int32_t)g_user_transforms.size() - 1;
+    return SMM_OK;
+}
 
 int smm_register_user_objective(const char* hip_source, int32_t* objective_id_out) {
     if (!hip_source || !objective_id_out) { g_create_err = "smm_register_user_objective: null argument"; return SMM_ERR_INVALID_ARG; }

@@ -80,6 +80,7 @@ using namespace smm;
 #include "smm_trace.hpp"
 #include "smm_rank.hpp"
 #include "smm_density.hpp"
+#include "smm_derived.hpp"
 #include "smm_draws.hpp"
 #include "smm_population.hpp"
 
@@ -256,6 +257,7 @@ struct Ctx {
     hipModule_t pmod = nullptr;     // ... and the persistent kernel compiled with it inside: k_chain_persist_gen (SMM_GEN_USER), or
     hipFunction_t pfn = nullptr;    //     k_chain_persist_tile with its map-reduce form (SMM_TILE_USER)
     int u_nsums = 1;                // ... its partial sums per lane
+    std::vector<std::pair<int32_t, hipModule_t>> tmods;   // user transforms (smm_get_derived): the modules this context has loaded, by handle
     int pop_kind = 0, pop_M = 0; // the starting population installed on this context: 0 none, 1 smm_set_population, 2 smm_scatter_population (smm_describe)
     double pop_spread = 0.0;
 

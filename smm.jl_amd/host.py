@@ -504,6 +504,29 @@ def pooled(algo, groups=None, window=None, accepted_only=True, level=0.95):
             for j in range(r["count"].shape[0])]
 
 
+def derived(algo, transform, names=None, t0=0, t1=None, select="accepted", groups=None, probs=(0.025, 0.975), tdata=()):
+    """the posterior of a user function of each draw (Stan's generated quantities: an elasticity, a ratio of parameters, a statistic of
+    the simulated moments) over each group's pooled rows of iterations [t0, t1) (default: the whole run), evaluated and summarised on
+    the device (include/smmhip.h: smm_get_derived) without downloading the history: one OrderedDict per group, keyed like pooled()'s —
+    count, chains, mean / median (name -> value), CI (name -> the quantiles of probs), cov (ndarray [Q][Q]) — and n_nonfinite
+    (name -> rows whose value is NaN or infinite).  transform: what user_transform(source, n_out) returned; names: the Q outputs' names
+    (default out0, out1, ..); select: "all", "accepted" or "state"; groups: a group id per chain (-1 = none), by default those of
+    rhat; tdata: the vector the function receives as tdata"""
+    Q = transform.n_out
+    names = ["out%d" % q for q in _builtins_range(Q)] if names is None else list(names)
+    if len(names) != Q or len(set(names)) != Q:
+        raise ValueError("derived: names must be %d distinct names, one per output" % Q)
+    g = np.asarray(_default_groups(algo) if groups is None else groups, np.int32)
+    r = algo._ctx.derived(transform, int(t0), algo.i if t1 is None else int(t1), select, g, probs, tdata)
+    return [OrderedDict(count=int(r["count"][j]), chains=int(r["n_chains"][j]),
+                        n_nonfinite=OrderedDict((k, int(r["n_nonfinite"][j, i])) for i, k in enumerate(names)),
+                        mean=OrderedDict((k, float(r["mean"][j, i])) for i, k in enumerate(names)),
+                        median=OrderedDict((k, float(r["median"][j, i])) for i, k in enumerate(names)),
+                        CI=OrderedDict((k, r["quantile"][:, j, i].copy()) for i, k in enumerate(names)),
+                        cov=r["cov"][j].copy())
+            for j in _builtins_range(r["count"].shape[0])]
+
+
 def _hist_call(x, window, accepted_only, state, **kw):
     """(algo, chain index or None, the device's histogram dict) of a chain (alone in group 0) or of the groups of an algo"""
     if isinstance(x, BGPChain):
