@@ -1082,6 +1082,45 @@ typedef struct {            /* caller-allocated, any pointer may be NULL */
 } smm_population_t;
 int  smm_set_population(void* ctx, const double* starts /* [np][N], host */, smm_population_t* out);
 int  smm_scatter_population(void* ctx, int32_t M, double spread, int32_t keep_init, smm_population_t* out);
+
+/* The estimate: K cyclic coordinate searches on grids, advancing together on the device (the reference's optSlices, slices.jl:114-242, from
+ * many starts: every chain's or every temperature group's best point, say).  Valid on any context at any iteration; it never changes the
+ * chains, the history, the generator's position or which kernel form the next step takes.  A stream objective draws from opts.seed, as
+ * smm_eval_batch does (common random numbers).  Ordered on smm_stream behind everything enqueued before (a persistent launch is settled
+ * first) and synchronised before it returns; a hard error nobody has been told of yet is returned once, and nothing runs.
+ *
+ * Numerical contract (every operation rounded on its own, no fma), per search s, independent of every other search; G = npoints:
+ *   Ranges: [lo_k, hi_k] start at [lb_k, ub_k]; bestp = the start, which must lie inside and must not be NaN (else SMM_ERR_INVALID_ARG with
+ *   the 1-based search and parameter in the message; nothing runs).
+ *   Grid of step (cycle, k) — numpy's linspace(lo_k, hi_k, G): with d = hi - lo and step = d / (G - 1), x_g = g * step + lo for g < G - 1 and
+ *   x_(G-1) = hi; if step == 0, x_g = (g / (G - 1)) * d + lo.  Candidate g is bestp with coordinate k replaced by x_g.
+ *   Select: the candidate with the smallest FINITE value wins — strict <, the lowest g wins ties, the status is not consulted (slices.jl:181).
+ *   The winner becomes bestp, its value and moments the search's, as evaluated (never evaluated again) — even when it is worse than the
+ *   previous value: the reference's behaviour.  With no finite value bestp stays.  dvec_k = old_k - new_k.
+ *   End of cycle: if update is not NaN, for every k: r = (hi - lo) / 2, lo = max(bestp_k - update * r, lo), hi = min(bestp_k + update * r, hi)
+ *   (both from the old lo and hi).  delta = sqrt(sum_k dvec_k^2): squares rounded, added left to right from k = 0, correctly rounded
+ *   square root.  The search stops converged when delta <= tol, unconverged after max_cycles cycles; a search that stopped costs nothing more.
+ *   evaluated: the sum of G over every step of every search still running.
+ * It differs from the reference only where that is undefined: a cap on the cycles, and a result (+inf, NaN moments) before the first finite value.
+ *   SMM_ERR_INVALID_ARG: K < 1, npoints < 2, (int64)K * npoints >= 2^31, tol negative or NaN, update not NaN and <= 0, max_cycles < 1, starts NULL.
+ *   Scratch: values, moments and status of a step take G x ((nm + 1) x 8 + 4) bytes per search (a user objective's candidates G x np x 8 more;
+ *   the built-in objectives' candidates are never written: their evaluation kernel builds each from bestp and the one replaced coordinate);
+ *   the running searches go in batches under 64 MiB (at least one search per batch); freed before the call returns.  The host reads 4
+ *   bytes per cycle — the number of searches that go on. */
+typedef struct {             /* caller-allocated; any pointer may be NULL = not returned */
+    double*  best;           /* [np][K]  the point each search ended at                      */
+    double*  value;          /* [K]      objective there; +inf while no finite grid value was ever seen */
+    double*  sim_moments;    /* [nm][K]  simulated moments there; NaN in that case           */
+    double*  lo;             /* [np][K]  final search ranges                                 */
+    double*  hi;             /* [np][K]                                                      */
+    double*  delta;          /* [K]      norm of the last cycle's moves                      */
+    double*  cycle_value;    /* [max_cycles][K] value after each cycle; NaN past a search's last cycle */
+    int32_t* cycles;         /* [K]      cycles run                                          */
+    int32_t* converged;      /* [K]      1: delta <= tol; 0: stopped by max_cycles           */
+    int64_t  evaluated;      /* out: objective evaluations performed                         */
+} smm_opt_slices_t;
+int  smm_opt_slices(void* ctx, const double* starts /* [np][K], host */, int32_t K, int32_t npoints,
+                    double tol, double update /* NaN = ranges never shrink */, int32_t max_cycles, smm_opt_slices_t* out);
 int  smm_get_timing(void* ctx, smm_timing_t* out);
 /* on = 1: bracket every kernel of smm_bgp_step with hipEvents on the ctx stream so that
  * smm_get_timing reports iter_kernel_ms / exch_kernel_ms (sums over the last step; each bracket

@@ -18,7 +18,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
 export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_adjustment, hip_profile, hip_density, hip_register_transform, hip_derived, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
-export hip_set_population!, hip_scatter_population!
+export hip_set_population!, hip_scatter_population!, hip_opt_slices
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
 const ABI_VERSION = 3
@@ -253,6 +253,19 @@ struct SmmPopulation
     start::Ptr{Cdouble}
     value::Ptr{Cdouble}
     pick::Ptr{Int32}
+    evaluated::Int64
+end
+
+struct SmmOptSlices
+    best::Ptr{Cdouble}
+    value::Ptr{Cdouble}
+    sim_moments::Ptr{Cdouble}
+    lo::Ptr{Cdouble}
+    hi::Ptr{Cdouble}
+    delta::Ptr{Cdouble}
+    cycle_value::Ptr{Cdouble}
+    cycles::Ptr{Int32}
+    converged::Ptr{Int32}
     evaluated::Int64
 end
 
@@ -1004,6 +1017,37 @@ of width `spread` (in [0, 1]-space) around the initial value, the best valid one
 function hip_scatter_population!(h::HipBGP, M::Integer; spread::Real = 1.0, keep_init::Bool = true)
     return population_call(h, out -> ccall(sym(:smm_scatter_population), Cint, (Ptr{Cvoid}, Cint, Cdouble, Cint, Ptr{SmmPopulation}),
                                            h.ctx, M, Float64(spread), keep_init ? 1 : 0, out))
+end
+
+"""
+    hip_opt_slices(h, starts, npoints; tol = 1e-5, update = nothing, max_cycles = 1000)
+        -> (best, value, sim_moments, lo, hi, delta, cycle_value, cycles, converged, evaluated)
+
+`K = size(starts, 1)` cyclic coordinate searches on grids of `npoints` values (optSlices, slices.jl:114-242), `starts[s, k]` (search,
+parameter), advancing together on the device (`smm_opt_slices`): one evaluation launch per coordinate step for all running searches, 4
+bytes read back per cycle.  The chains of the context are not touched.  `update = nothing`: the ranges never shrink.  `best`, `lo`, `hi`
+are `(K, np)`, `sim_moments` `(K, nm)`, `cycle_value` `(K, max_cycles)` (NaN past a search's last cycle); `value[s] == Inf` while
+search `s` never saw a finite value.
+"""
+function hip_opt_slices(h::HipBGP, starts::Matrix{Float64}, npoints::Integer; tol::Real = 1e-5, update::Union{Nothing, Real} = nothing,
+                        max_cycles::Integer = 1000)
+    size(starts, 2) == h.np || throw(ArgumentError("starts must be (K, np) with np = $(h.np)"))
+    K = size(starts, 1)
+    mc = max(Int(max_cycles), 0)
+    best = Matrix{Float64}(undef, K, h.np); lo = similar(best); hi = similar(best)
+    value = Vector{Float64}(undef, K); delta = similar(value)
+    simm = Matrix{Float64}(undef, K, h.nm); cycle_value = Matrix{Float64}(undef, K, mc)
+    cycles = Vector{Int32}(undef, K); converged = Vector{Int32}(undef, K)
+    evaluated = 0
+    GC.@preserve starts best lo hi value delta simm cycle_value cycles converged begin
+        out = Ref(SmmOptSlices(pointer(best), pointer(value), pointer(simm), pointer(lo), pointer(hi), pointer(delta), pointer(cycle_value),
+                               pointer(cycles), pointer(converged), 0))
+        check(h.ctx, ccall(sym(:smm_opt_slices), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cdouble, Cdouble, Cint, Ptr{SmmOptSlices}),
+                           h.ctx, pointer(starts), K, npoints, Float64(tol), update === nothing ? NaN : Float64(update), max_cycles, out))
+        evaluated = Int(out[].evaluated)
+    end
+    return (best = best, value = value, sim_moments = simm, lo = lo, hi = hi, delta = delta, cycle_value = cycle_value, cycles = cycles,
+            converged = converged .!= 0, evaluated = evaluated)
 end
 
 "per-chain state: what `save` / `readMalgo` / `restart!` need besides the history (AlgoAbstract.jl:83-102)"

@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, optSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -816,6 +816,32 @@ function doSlicesHip(m::MProb, npoints::Int; opts::Dict = Dict())
         SMM.add!(res, pp, ev)
     end
     return res
+end
+
+"""
+    optSlicesHip(m, npoints; starts = nothing, tol = 1e-5, update = nothing, max_cycles = 1000, opts = Dict()) -> Vector{Dict}
+
+`optSlices(m, npoints)` (slices.jl:114-242) from many starts, the whole search on the device (`SMMHip.hip_opt_slices`): the searches advance
+together, one evaluation launch per coordinate step, 4 bytes read back per cycle.  `starts`: a vector of parameter dicts (`nothing`: the
+initial value).  Per start the reference's `Dict(:best => Dict(:p => ..., :value => ...), :iterations => n, :converged => Bool)`; a start
+that never saw a finite value keeps its point and has value `Inf`.  (No `:history`: the evaluations never visit the host.)
+"""
+function optSlicesHip(m::MProb, npoints::Int; starts = nothing, tol::Real = 1e-5, update = nothing, max_cycles::Int = 1000, opts::Dict = Dict())
+    ps = starts === nothing ? Any[m.initial_value] : starts
+    pk = collect(keys(m.params_to_sample))
+    P = Float64[p[k] for p in ps, k in pk]                      # K x np
+    h = eval_context(m, opts)
+    r = SMMHip.hip_opt_slices(h, P, npoints; tol = tol, update = update, max_cycles = max_cycles)
+    SMMHip.hip_destroy!(h)
+    out = Dict[]
+    for (s, p0) in enumerate(ps)
+        p = deepcopy(p0)
+        for (j, k) in enumerate(pk)
+            p[k] = r.best[s, j]
+        end
+        push!(out, Dict(:best => Dict(:p => p, :value => r.value[s]), :iterations => Int(r.cycles[s]), :converged => r.converged[s]))
+    end
+    return out
 end
 
 "`FD_gradient(m, p)` (econometrics.jl:29-85): the 1 + k (forward) or 2k (central) evaluations in one batch; rows in the order of `p`"

@@ -191,6 +191,13 @@ class smm_population_t(C.Structure):
     ]
 
 
+class smm_opt_slices_t(C.Structure):
+    _fields_ = [
+        ("best", c_double_p), ("value", c_double_p), ("sim_moments", c_double_p), ("lo", c_double_p), ("hi", c_double_p),
+        ("delta", c_double_p), ("cycle_value", c_double_p), ("cycles", c_int32_p), ("converged", c_int32_p), ("evaluated", C.c_int64),
+    ]
+
+
 class smm_timing_t(C.Structure):
     _fields_ = [
         ("step_ms", C.c_double), ("iter_kernel_ms", C.c_double), ("exch_kernel_ms", C.c_double),
@@ -264,6 +271,8 @@ SYMBOLS = [
     ("smm_set_state", C.c_int, [C.c_void_p, C.POINTER(smm_state_t), C.POINTER(smm_history_t)]),
     ("smm_set_population", C.c_int, [C.c_void_p, c_double_p, C.POINTER(smm_population_t)]),
     ("smm_scatter_population", C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.POINTER(smm_population_t)]),
+    ("smm_opt_slices", C.c_int, [C.c_void_p, c_double_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                 C.POINTER(smm_opt_slices_t)]),
     ("smm_get_timing", C.c_int, [C.c_void_p, C.POINTER(smm_timing_t)]),
     ("smm_get_Z", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_profiling", C.c_int, [C.c_void_p, C.c_int32]),

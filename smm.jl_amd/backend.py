@@ -624,6 +624,25 @@ class BGPContext:
         -1 = initial_value), evaluated"""
         return self._population(lambda out: self._fn("scatter_population")(self._ctx, int(M), float(spread), int(bool(keep_init)), out))
 
+    # --- the estimate (include/smmhip.h: smm_opt_slices) ------------------------------------------------------------------------
+    def opt_slices(self, starts, npoints, tol=1e-5, update=None, max_cycles=1000):
+        """K cyclic coordinate searches on grids of npoints values, starts [np][K], advancing together on the device (smm_opt_slices:
+        optSlices of slices.jl from many starts; the context's chains are not touched).  update=None: the ranges never shrink.
+        Returns a dict: best [np][K], value [K], sim_moments [nm][K], lo / hi [np][K], delta [K], cycle_value [max_cycles][K],
+        cycles [K], converged [K], evaluated"""
+        st = A.f64(starts)
+        if st.ndim != 2 or st.shape[0] != self.np:
+            raise ValueError("opt_slices: starts must be [np][K] with np = %d, got %s" % (self.np, st.shape))
+        K, mc = st.shape[1], max(int(max_cycles), 0)
+        r = dict(best=np.empty((self.np, K)), value=np.empty(K), sim_moments=np.empty((self.nm, K)), lo=np.empty((self.np, K)),
+                 hi=np.empty((self.np, K)), delta=np.empty(K), cycle_value=np.empty((mc, K)), cycles=np.empty(K, np.int32),
+                 converged=np.empty(K, np.int32))
+        s = self._out(A.smm_opt_slices_t, r)
+        self._check(self._fn("opt_slices")(self._ctx, A.dptr(st), K, int(npoints), float(tol), float("nan") if update is None else float(update),
+                                           int(max_cycles), C.byref(s)))
+        r["evaluated"] = int(s.evaluated)
+        return r
+
     def timing(self):
         t = A.smm_timing_t()
         self._check(self._fn("get_timing")(self._ctx, C.byref(t)))

@@ -125,6 +125,36 @@ def optSlices(m, npoints, parallel=False, tol=1e-5, update=None, filename=None, 
     return dout
 
 
+def opt_starts(m, starts):
+    """starts as the device takes them, [np][K] over the sampled parameters: None (initial_value), an array, or a list of parameter dicts"""
+    names = ps2s_names(m)
+    if starts is None:
+        starts = [m.initial_value]
+    if len(starts) and isinstance(starts[0], dict):
+        starts = [[float(d[k]) for d in starts] for k in names]
+    return np.array(starts, float).reshape(len(names), -1)
+
+
+def opt_results(m, r):
+    """smm_opt_slices' arrays as the reference's results, one per start: {"best": {"p", "value"}, "iterations", "converged"}"""
+    names = ps2s_names(m)
+    out = []
+    for s in range(len(r["value"])):
+        p = OrderedDict(m.initial_value)
+        p.update((k, float(r["best"][i, s])) for i, k in enumerate(names))
+        out.append({"best": {"p": p, "value": float(r["value"][s])}, "iterations": int(r["cycles"][s]), "converged": bool(r["converged"][s])})
+    return out
+
+
+def optSlicesDevice(m, npoints, starts=None, tol=1e-5, update=None, maxiter=1000, ctx=None):
+    """optSlices from many starts, the whole search on the device (smm_opt_slices, include/smmhip.h: K searches advance together, one
+    evaluation launch per coordinate step, 4 bytes read back per cycle).  starts: None (initial_value), [np][K] over the sampled
+    parameters, or a list of parameter dicts.  Returns a list with, per start, the reference's {"best": {"p", "value"}, "iterations",
+    "converged"} (no "history": the evaluations never visit the host; a start that never saw a finite value has value inf)."""
+    ctx = _eval_context(m, _flat_problem(m)) if ctx is None else ctx
+    return opt_results(m, ctx.opt_slices(opt_starts(m, starts), npoints, tol, update, maxiter))
+
+
 # ------------------------------------------------------------------------------------------
 # econometrics.jl
 # ------------------------------------------------------------------------------------------

@@ -1072,6 +1072,38 @@ def scatter_start(algo, M=64, spread=1.0, keep_init=True):
     return _install_start(algo, algo._ctx.scatter_population(M, spread, keep_init))
 
 
+def polish(algo, npoints, per="chain", tol=1e-5, update=None, maxiter=1000, groups=None):
+    """the estimate: a coordinate search on grids of npoints values (optSlices, slices.jl:114-242) from every chain's best point
+    (per="chain") or from the best point of every group of chains (per="group": a group id per chain in `groups`, -1 = none; by default
+    those of rhat), all searches at once on the device (smm_opt_slices).  The best points are those chain_stats reports (best_value,
+    best_iter over the accepted draws); the chains are not touched.  Returns the searches' results sorted by value, each the reference's
+    {"best": {"p", "value"}, "iterations", "converged"} and "start": {"chain" or "group", "p", "value"}"""
+    from .callers import opt_results
+    if per not in ("chain", "group"):
+        raise ValueError('polish: per must be "chain" or "group"')
+    if algo.i == 0:
+        raise ValueError("polish: no completed iteration to start from")
+    st = algo._chain_stats(True, ())
+    bv, bi = np.asarray(st["best_value"], float), np.asarray(st["best_iter"])
+    if per == "chain":
+        who = [(j, j) for j in range(len(bv))]
+    else:
+        g = np.asarray(_default_groups(algo) if groups is None else groups, int)
+        who = []
+        for gid in sorted(set(int(x) for x in g if x >= 0)):
+            members = np.flatnonzero(g == gid)
+            ok = members[~np.isnan(bv[members])]
+            members = ok if len(ok) else members
+            who.append((gid, int(members[np.argmin(bv[members])])))   # (argmin: the lowest chain among equals)
+    P = algo._history().params   # [t][np][N]
+    starts = np.array([[P[int(bi[j]) - 1, k, j] for _, j in who] for k in range(P.shape[1])], float).reshape(P.shape[1], len(who))
+    res = opt_results(algo.m, algo._ctx.opt_slices(starts, npoints, tol, update, maxiter))
+    names = ps2s_names(algo.m)
+    for s, (r, (label, j)) in enumerate(zip(res, who)):
+        r["start"] = {per: label, "p": OrderedDict((k, float(starts[i, s])) for i, k in enumerate(names)), "value": float(bv[j])}
+    return sorted(res, key=lambda r: r["best"]["value"])   # (stable: equal values keep the order of their starts)
+
+
 def set_proposal(algo, L):
     """install proposal factor(s) between iterations (smm_set_proposal): [np][np] on a shared-factor run, [N][np][np] per chain"""
     algo._ctx.set_proposal(L)
