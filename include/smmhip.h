@@ -819,6 +819,72 @@ int  smm_get_adjustment(void* ctx, int32_t t0, int32_t t1, int32_t select, const
                         double tol, int32_t kernel, const double* scale /* [nm] or NULL */, double ridge, const double* probs,
                         int32_t n_probs, smm_adjustment_t* out);
 
+/* The target posterior from every temperature, computed on the device from the history it holds.  Chain c accepts with
+ * exp(acc_tuner[c] (v_old - v_new)) (AlgoBGP.jl:344), so its state series samples the density proportional to exp(-acc_tuner[c] v(theta))
+ * on the box.  Every scored row of chain c is importance-reweighted from the chain's own temperature to the target a* = targets[r] by
+ * exp((acc_tuner[c] - a*) v); each chain is self-normalised, so the unknown normalisers drop out, and the chains of a group are combined
+ * by their effective sample sizes.  The one statistical assumption: each chain's state series targets exp(-acc_tuner v); BGP's exchange
+ * moves respect this only approximately.  select 2 (the state series through a(t)) is the selection the theory is about; 0 (all rows)
+ * and 1 (the accepted rows) are offered as the other group readers offer them.  Window, groups and select are exactly those of
+ * smm_get_moment_stats (a shard reports its own local chains; group NULL with n_groups == 1: every local chain in group 0); acc_tuner is
+ * the chain's own, indexed by its global id.  Caller-allocated; any pointer may be NULL (not computed).  Read-only and ordered like
+ * smm_get_chain_stats (it settles, flushes and synchronises, and changes no state, history or generator).  Device memory:
+ * smm_get_chain_stats' scratch, grown where needed to 5 x N x maxiter x 8 bytes (per scored row its history row and chain, its value, its
+ * weight, its integer weight, and one column of parameters) plus (np + nm + 3) x 8192 x 8 bytes (the columns of one chunk) plus at most
+ * 256 MiB (further chunks and parameter columns, no more than the context's capacity can fill); the rows are
+ * taken in batches of chunks (whose np^2 pair sums per chunk stay under 256 MiB of the result buffer) and the select's parameters in
+ * batches of columns; the targets run one after another over the same packed columns.  SMM_ERR_INVALID_ARG: NULL ctx or out, a bad
+ * window, select outside [0, 2], n_groups < 0, group NULL with n_groups != 1, a group id outside [-1, n_groups), n_targets outside
+ * [1, 64], targets NULL, a target that is not finite or < 0, n_probs < 0, probs NULL with n_probs > 0, a prob outside [0, 1] or NaN,
+ * quantile without probs; nothing is written then.  R = n_targets, G = n_groups, N the local chains.
+ *
+ * Numerical contract (every operation rounded on its own, no fma outside smm_exp / smm_log; counts and integer weights 64-bit):
+ *   scored row : a selected row whose value has |v| <= DBL_MAX; a select-2 row with no a(t) is not scored.  count includes the unscored
+ *                rows, nothing else does.
+ *   per member chain c and target r, over the chain's scored rows in iteration order (n_c of them) as one contiguous column:
+ *     d = acc_tuner[c] - targets[r]; lw_i = d * v_i; L = max_i lw_i; w_i = smm_exp(lw_i - L), 0.0 where lw_i - L is -inf (smm_exp(0.0) is
+ *     exactly 1.0: k = 0, r = 0, p = 0, ldexp(1.0 + 0.0, 0); the row that attains L has w = 1).
+ *     sw = S_c(w_i), sw2 = S_c(w_i * w_i), S_c the chain-stats pairwise sum (chunks of 8192 from the chain's first scored row).
+ *     chain_ess = (sw * sw) / sw2; chain_logz = L + smm_log(sw / (double) n_c), the log normaliser ratio log Z(a*) / Z(a_c);
+ *     f_c = sw / sw2.  n_c == 0, or a chain in no group: chain_ess 0, chain_logz NaN, and the chain contributes no row.
+ *   row weight : u_i = w_i * f_c: every chain is self-normalised and enters with its own effective sample size (the u of chain c add up
+ *                to chain_ess up to rounding).
+ *   group      : over the members' scored rows in pooled order (members in ascending local index, each in iteration order, packed);
+ *                S the chunked pairwise sum of smm_get_group_stats, chunks of 8192 counted from the group's first scored row.
+ *     sum_u = S(u_i); ess = (sum_u * sum_u) / S(u_i * u_i).
+ *     mean_j = S(u_i * theta_ij) / sum_u; value_mean and m_mean_k the same with v_i and s_ik in place of theta_ij.
+ *     e_ij = sqrt(u_i) * (theta_ij - mean_j); cov_jk = C_jk / sum_u, C smm_get_adjustment's pair sums (smm_get_chain_cov's per chunk,
+ *     the chunks' sums added in order from 0.0): the weighted population form, without a Bessel factor; mirrored entries hold the same
+ *     value.
+ *     n_kept: the rows with u_i > 0.
+ *     quantile: F = the largest f_c among the members with n_c > 0; q_i = (int64) ceil((u_i / F) * 1048576.0), at least 1 for a kept
+ *     row and at most 2^20 (u_i <= f_c <= F); Q = the sum of them; from there smm_get_adjustment's rule: target = max(1, (int64)
+ *     ceil(p * (double) Q)); the quantile is the smallest theta_.j among the kept rows for which the q of the rows with theta <= it add
+ *     up to at least target: the inverted weighted CDF over the IEEE total order (-0.0 before +0.0), one of the rows' own doubles.
+ *   status per (r, g), the first that applies: 1 fewer than 2 scored rows; 2 a non-finite parameter in a scored row; 3 a member's L, or
+ *                sum_u, is not finite (d * v overflowed); 0 otherwise.  For 1 to 3 every double of (r, g) is NaN and n_kept 0; the
+ *                per-chain outputs keep the values defined above.  A NaN simulated moment in a scored row propagates into that moment's
+ *                mean only. */
+typedef struct {             /* caller-allocated; any pointer may be NULL = not computed                                        */
+    int64_t* count;          /* [G]                   rows selected                                                             */
+    int64_t* n_scored;       /* [G]                   rows that carry a weight                                                  */
+    int32_t* n_chains;       /* [G]                   member chains                                                             */
+    int32_t* status;         /* [R][G]                0 ok, 1 fewer than 2 scored rows, 2 non-finite parameter, 3 overflow      */
+    int32_t* chain_n;        /* [N]                   a chain's scored rows; 0 for a chain in no group                          */
+    double*  chain_ess;      /* [R][N]                per-chain effective sample size                                           */
+    double*  chain_logz;     /* [R][N]                per-chain log normaliser ratio log Z(a*) / Z(a_c)                         */
+    int64_t* n_kept;         /* [R][G]                rows with u > 0                                                           */
+    double*  sum_u;          /* [R][G]                sum of the row weights                                                    */
+    double*  ess;            /* [R][G]                effective sample size of the group (Kish)                                 */
+    double*  mean;           /* [R][G][np]            weighted parameter mean                                                   */
+    double*  cov;            /* [R][G][np][np]        weighted population covariance, both triangles                            */
+    double*  value_mean;     /* [R][G]                weighted mean of the objective value                                      */
+    double*  m_mean;         /* [R][G][nm]            weighted mean of each simulated moment                                    */
+    double*  quantile;       /* [n_probs][R][G][np]   weighted quantiles of the parameters                                      */
+} smm_reweighted_t;
+int  smm_get_reweighted(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group /* [N] or NULL */, int32_t n_groups,
+                        const double* targets, int32_t n_targets, const double* probs, int32_t n_probs, smm_reweighted_t* out);
+
 /* The objective and the simulated moments binned along parameters, computed on the device from the history it holds: for each group of
  * chains and each parameter, over smm_get_histogram's bins of that parameter, the profile of the objective (the smallest value among the
  * rows of the bin and the row that attains it, with its full parameter vector: the lower envelope a slice plot draws, over everywhere the

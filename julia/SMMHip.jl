@@ -17,7 +17,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
        hip_register_objective, hip_register_objective_rng, hip_record_doubles
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
-export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_adjustment, hip_profile, hip_density, hip_register_transform, hip_derived, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
+export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_adjustment, hip_reweighted, hip_profile, hip_density, hip_register_transform, hip_derived, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
 export hip_set_population!, hip_scatter_population!, hip_opt_slices
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
@@ -151,6 +151,24 @@ struct SmmAdjustment
     adj_sd::Ptr{Cdouble}
     adj_quantile::Ptr{Cdouble}
     n_outside::Ptr{Int64}
+end
+
+struct SmmReweighted
+    count::Ptr{Int64}
+    n_scored::Ptr{Int64}
+    n_chains::Ptr{Int32}
+    status::Ptr{Int32}
+    chain_n::Ptr{Int32}
+    chain_ess::Ptr{Cdouble}
+    chain_logz::Ptr{Cdouble}
+    n_kept::Ptr{Int64}
+    sum_u::Ptr{Cdouble}
+    ess::Ptr{Cdouble}
+    mean::Ptr{Cdouble}
+    cov::Ptr{Cdouble}
+    value_mean::Ptr{Cdouble}
+    m_mean::Ptr{Cdouble}
+    quantile::Ptr{Cdouble}
 end
 
 struct SmmMomentStats
@@ -937,6 +955,46 @@ function hip_adjustment(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :s
     end
     return (count = count, n_chains = nch, status = st, n_kept = kept, bandwidth = bw, sum_w = sw, ess = ess, x_mean = xmean,
             raw_mean = rmean, beta = beta, adj_mean = amean, adj_sd = asd, adj_quantile = aq, n_outside = nout)
+end
+
+"""
+    hip_reweighted(h, t0, t1; select = :state, groups = nothing, targets = [1.0], probs = Float64[]) -> NamedTuple
+
+The target posterior from every temperature over iterations `t0+1 .. t1`, on the device (`smm_get_reweighted`) without downloading the
+history: every scored row of a chain is importance-reweighted from the chain's own `acc_tuner` to each of `targets` (1 to 64 finite
+values >= 0), each chain self-normalised, the chains of a group combined by their effective sample sizes.  It assumes that each chain's
+state series targets `exp(-acc_tuner * v)`; BGP's exchange moves respect this only approximately.  `select`: `:all`, `:accepted` or
+`:state` (the selection the theory is about).  `groups[chain]` holds 0-based group ids (-1 = none); `nothing`: every chain in one
+group.  Returns `count[g]`, `n_scored[g]`, `n_chains[g]`, `chain_n[c]`, `status[g, r]` (0 ok, 1 fewer than 2 scored rows, 2 a
+non-finite parameter, 3 the weights overflowed), `chain_ess[c, r]`, `chain_logz[c, r]`, `n_kept[g, r]`, `sum_u[g, r]`, `ess[g, r]`,
+`mean[k, g, r]`, `cov[k, j, g, r]`, `value_mean[g, r]`, `m_mean[m, g, r]` and `quantile[k, g, r, p]` (the header's row-major arrays).
+"""
+function hip_reweighted(h::HipBGP, t0::Integer, t1::Integer; select::Symbol = :state,
+                        groups::Union{Nothing,AbstractVector{<:Integer}} = nothing, targets::AbstractVector{<:Real} = [1.0],
+                        probs::AbstractVector{<:Real} = Float64[])
+    N, np, nm = h.N, h.np, h.nm
+    g = groups === nothing ? Int32[] : Vector{Int32}(groups)
+    groups === nothing || length(g) == N || throw(ArgumentError("groups needs one entry per chain"))
+    ng = groups === nothing ? 1 : (isempty(g) ? 0 : Int(maximum(g)) + 1)
+    tg = Vector{Float64}(targets); R = length(tg)
+    1 <= R <= 64 || throw(ArgumentError("targets needs 1 to 64 entries"))
+    p = Vector{Float64}(probs); nq = length(p)
+    count = Vector{Int64}(undef, ng); nsc = Vector{Int64}(undef, ng); nch = Vector{Int32}(undef, ng); st = Matrix{Int32}(undef, ng, R)
+    cn = Vector{Int32}(undef, N); cess = Matrix{Float64}(undef, N, R); clz = Matrix{Float64}(undef, N, R)
+    kept = Matrix{Int64}(undef, ng, R); su = Matrix{Float64}(undef, ng, R); ess = Matrix{Float64}(undef, ng, R)
+    mean = Array{Float64}(undef, np, ng, R); cov = Array{Float64}(undef, np, np, ng, R); vm = Matrix{Float64}(undef, ng, R)
+    mm = Array{Float64}(undef, nm, ng, R); q = Array{Float64}(undef, np, ng, R, nq)
+    GC.@preserve g tg p count nsc nch st cn cess clz kept su ess mean cov vm mm q begin
+        rw = SmmReweighted(pointer(count), pointer(nsc), pointer(nch), pointer(st), pointer(cn), pointer(cess), pointer(clz),
+                           pointer(kept), pointer(su), pointer(ess), pointer(mean), pointer(cov), pointer(vm), pointer(mm),
+                           nq > 0 ? pointer(q) : Ptr{Cdouble}(C_NULL))
+        check(h.ctx, ccall(sym(:smm_get_reweighted), Cint,
+                           (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Int32}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ref{SmmReweighted}),
+                           h.ctx, t0, t1, HIST_SELECT[select], groups === nothing ? Ptr{Int32}(C_NULL) : pointer(g), ng, pointer(tg), R,
+                           nq > 0 ? pointer(p) : Ptr{Cdouble}(C_NULL), nq, rw))
+    end
+    return (count = count, n_scored = nsc, n_chains = nch, status = st, chain_n = cn, chain_ess = cess, chain_logz = clz, n_kept = kept,
+            sum_u = su, ess = ess, mean = mean, cov = cov, value_mean = vm, m_mean = mm, quantile = q)
 end
 
 # the factor(s) between the header's row-major [np][np] / [N][np][np] and Julia's L[k, j] / L[k, j, c]

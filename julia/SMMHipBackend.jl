@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, optSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, posterior_tempered, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, optSlicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -594,6 +594,31 @@ function regression_adjust(algo::MAlgoBGPHip; window = nothing, select::Symbol =
                               probs = [(1 - level) / 2, 1 - (1 - level) / 2])
     return (count = r.count, n_chains = r.n_chains, status = r.status, n_kept = r.n_kept, ess = r.ess, raw_mean = r.raw_mean,
             adj_mean = r.adj_mean, adj_sd = r.adj_sd, band = r.adj_quantile, n_outside = r.n_outside)
+end
+
+"""
+    posterior_tempered(algo; target = nothing, window = nothing, select = :state, groups = nothing, level = 0.95) -> NamedTuple
+
+The target posterior from every temperature, on the device (`SMMHip.hip_reweighted`): every chain's draws importance-reweighted from its
+own `acc_tuners` entry to `target` (default: the largest entry, the coldest chain's), each chain self-normalised and entering with its
+own effective sample size, so the warmer chains' evaluations are not thrown away.  It assumes that each chain's state series targets
+`exp(-acc_tuner * v)`; BGP's exchange moves respect this only approximately.  `groups`: 0-based ids per chain (-1 = none), by default
+every chain in one group.  Returns `target`, `count[g]`, `n_scored[g]`, `n_chains[g]`, `status[g]`, `n_kept[g]`, `ess[g]`,
+`mean[k, g]`, `cov[k, j, g]`, `value_mean[g]`, `m_mean[m, g]`, `band[k, g, 1:2]` (the weighted quantiles at `level`), `chain_ess[c]`
+and `chain_logz[c]`.  Not a method of `SMM`: the reference has no such function.
+"""
+function posterior_tempered(algo::MAlgoBGPHip; target = nothing, window = nothing, select::Symbol = :state, groups = nothing,
+                            level::Real = 0.95)
+    flush_steps!(algo)
+    hip = getfield(algo, :hip)
+    t0, t1 = window === nothing ? (0, SMMHip.hip_iter(hip)) : window
+    opts = getfield(algo, :opts)
+    a = target === nothing ? maximum(chain_vector(opts, "acc_tuners", 2.0, Int(opts["N"]))) : Float64(target)
+    r = SMMHip.hip_reweighted(hip, t0, t1; select = select, groups = groups, targets = [a],
+                              probs = [(1 - level) / 2, 1 - (1 - level) / 2])
+    return (target = a, count = r.count, n_scored = r.n_scored, n_chains = r.n_chains, status = r.status[:, 1], n_kept = r.n_kept[:, 1],
+            ess = r.ess[:, 1], mean = r.mean[:, :, 1], cov = r.cov[:, :, :, 1], value_mean = r.value_mean[:, 1], m_mean = r.m_mean[:, :, 1],
+            band = r.quantile[:, :, 1, :], chain_ess = r.chain_ess[:, 1], chain_logz = r.chain_logz[:, 1])
 end
 
 """

@@ -161,6 +161,15 @@ class smm_adjustment_t(C.Structure):
     ]
 
 
+class smm_reweighted_t(C.Structure):
+    _fields_ = [
+        ("count", C.POINTER(C.c_int64)), ("n_scored", C.POINTER(C.c_int64)), ("n_chains", c_int32_p), ("status", c_int32_p),
+        ("chain_n", c_int32_p), ("chain_ess", c_double_p), ("chain_logz", c_double_p), ("n_kept", C.POINTER(C.c_int64)),
+        ("sum_u", c_double_p), ("ess", c_double_p), ("mean", c_double_p), ("cov", c_double_p), ("value_mean", c_double_p),
+        ("m_mean", c_double_p), ("quantile", c_double_p),
+    ]
+
+
 class smm_profile_t(C.Structure):
     _fields_ = [
         ("count", C.POINTER(C.c_int64)), ("status", c_int32_p), ("edges", c_double_p), ("n", C.POINTER(C.c_int64)),
@@ -256,6 +265,8 @@ SYMBOLS = [
                                        C.POINTER(smm_moment_stats_t)]),
     ("smm_get_adjustment", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_double, C.c_int32, c_double_p,
                                      C.c_double, c_double_p, C.c_int32, C.POINTER(smm_adjustment_t)]),
+    ("smm_get_reweighted", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_double_p, C.c_int32, c_double_p,
+                                     C.c_int32, C.POINTER(smm_reweighted_t)]),
     ("smm_get_profile", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32, c_double_p, c_int32_p,
                                    C.c_int32, C.c_int32, C.POINTER(smm_profile_t)]),
     ("smm_get_density", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, c_double_p, C.c_int32, C.c_int32,

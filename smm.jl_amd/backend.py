@@ -526,6 +526,29 @@ class BGPContext:
                                                C.byref(s)))
         return r
 
+    def reweighted(self, t0=0, t1=None, select="state", groups=None, targets=(1.0,), probs=(), n_groups=None):
+        """the target posterior from every temperature: the scored rows of groups of local chains over iterations [t0, t1)
+        importance-reweighted from each chain's own acc_tuner to every target, on the device (smm_get_reweighted, include/smmhip.h): a
+        dict of numpy arrays count / n_scored / n_chains [n_groups], chain_n [N], chain_ess / chain_logz [R][N], status / n_kept /
+        sum_u / ess / value_mean [R][n_groups], mean [R][n_groups][np], cov [R][n_groups][np][np], m_mean [R][n_groups][nm], quantile
+        [len(probs)][R][n_groups][np], R = len(targets).  select and groups as in moment_stats ("state" is the selection the theory is
+        about); targets: 1 to 64 finite values >= 0 on acc_tuner's scale"""
+        t1 = self._t1(t1)
+        p, tg = A.f64(probs).reshape(-1), A.f64(targets).reshape(-1)
+        np_, nm, N = self.np, self.nm, self.N
+        sel = self._select(select)
+        g, gp, ng = self._groups("reweighted", groups, n_groups)
+        G, R = max(ng, 0), len(tg)
+        r = dict(count=np.empty(G, np.int64), n_scored=np.empty(G, np.int64), n_chains=np.empty(G, np.int32),
+                 status=np.empty((R, G), np.int32), chain_n=np.empty(N, np.int32), chain_ess=np.empty((R, N)), chain_logz=np.empty((R, N)),
+                 n_kept=np.empty((R, G), np.int64), sum_u=np.empty((R, G)), ess=np.empty((R, G)), mean=np.empty((R, G, np_)),
+                 cov=np.empty((R, G, np_, np_)), value_mean=np.empty((R, G)), m_mean=np.empty((R, G, nm)),
+                 quantile=np.empty((len(p), R, G, np_)))
+        s = self._out(A.smm_reweighted_t, r, () if len(p) else ("quantile",))
+        self._check(self._fn("get_reweighted")(self._ctx, int(t0), int(t1), sel, gp, ng, A.dptr(tg) if R else None, R,
+                                               A.dptr(p) if len(p) else None, len(p), C.byref(s)))
+        return r
+
     def profile(self, t0=0, t1=None, select="accepted", groups=None, bins=20, range=None, pairs=(), bins2=None, n_groups=None,
                 moments=True):
         """the objective and the simulated moments binned along parameters over iterations [t0, t1), on the device (smm_get_profile,

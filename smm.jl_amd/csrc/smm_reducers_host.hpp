@@ -1,8 +1,8 @@
 // the host side of the history reducers — part of libsmmhip (included once by smmhip.hip, behind its host helpers; hiprtc never sees it).
 // The family: smm_get_chain_stats, smm_get_chain_cov, smm_get_proposal / _set_ / _adapt_, smm_get_chain_diag, smm_get_group_stats,
-// smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws, smm_get_moment_stats, smm_get_adjustment, smm_get_profile,
-// smm_get_density, smm_get_derived (kernels:
-// smm_stats.hpp, smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_moments.hpp, smm_adjust.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp,
+// smm_get_histogram, smm_get_trace, smm_get_rank_diag, smm_get_draws, smm_get_moment_stats, smm_get_adjustment, smm_get_reweighted,
+// smm_get_profile, smm_get_density, smm_get_derived (kernels:
+// smm_stats.hpp, smm_cov.hpp, smm_diag.hpp, smm_group.hpp, smm_moments.hpp, smm_adjust.hpp, smm_reweight.hpp, smm_hist.hpp, smm_trace.hpp, smm_rank.hpp,
 // smm_draws.hpp, smm_profile.hpp, smm_density.hpp, smm_derived.hpp and, around a user's transform, smm_user_host.hpp's kernel text;
 // the walk over a chain's window that their gathers share: smm_window.hpp).
 // What they share is stated here once: the frame of a call (api_call of smmhip.hip), the checks of the arguments they have in common (check_groups,
@@ -319,7 +319,7 @@ void rank_sort_columns(Ctx* c, const RankBatch& b, bool any_large, unsigned long
 // the reducers' dynamic LDS (smm_ctx_create): a chunk of draws (k_stats_column, k_cov_center, k_diag_acov, k_group_*, k_trace_column),
 // the partner ids of a pass (k_stats_mode), the counters and edges of a batch of parameters or pairs (k_hist_count, k_hist_pairs), a
 // split chain (k_rank_chain_mom, k_rank_acov), the three matrices of a group (k_moment_solve: 3 x 64 x 65 doubles), the two of
-// k_adjust_solve, a chunk of a segment (k_prof_chunk)
+// k_adjust_solve, a chunk of a chain's weights (k_rw_chain), a chunk of a segment (k_prof_chunk)
 void reducer_kernel_attributes() {
     HIPCHK(hipFuncSetAttribute((const void*)k_stats_column, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_cov_center, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
@@ -334,6 +334,7 @@ void reducer_kernel_attributes() {
     HIPCHK(hipFuncSetAttribute((const void*)k_rank_acov, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_moment_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * MAX_DIM * (MAX_DIM + 1) * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_adjust_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * MAX_DIM * (MAX_DIM + 1) * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_rw_chain, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_prof_chunk, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_dens_small, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_dens_mode_fin, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
@@ -1365,6 +1366,207 @@ int smm_get_adjustment(void* ctx, int32_t t0, int32_t t1, int32_t select, const 
         down(c, d, o_rm, out->raw_mean, G * np); down(c, d, o_beta, out->beta, G * nm * np); down(c, d, o_am, out->adj_mean, G * np);
         down(c, d, o_sd, out->adj_sd, G * np); down(c, d, o_q, out->adj_quantile, nq * G * np); down(c, d, nout, out->n_outside, G * np);
         HIPCHK(hipStreamSynchronize(c->stream));
+        return SMM_OK;
+    });
+}
+
+// --- the target posterior from every temperature (smm_reweight.hpp) ----------------------------------------------------------------------
+
+int smm_get_reweighted(void* ctx, int32_t t0, int32_t t1, int32_t select, const int32_t* group, int32_t n_groups, const double* targets,
+                       int32_t n_targets, const double* probs, int32_t n_probs, smm_reweighted_t* out) {
+    return api_call(ctx, out != nullptr, [&](Ctx* c) -> int {
+        if (const int rc = check_select(c, select)) return rc;
+        if (const int rc = check_groups(c, group, n_groups, GROUPS_DEFAULT_ONE)) return rc;
+        if (n_targets < 1 || n_targets > 64 || !targets) return fail(c, SMM_ERR_INVALID_ARG, "n_targets must lie in [1, 64], targets not NULL");
+        for (int r = 0; r < n_targets; ++r)
+            if (!(std::isfinite(targets[r]) && targets[r] >= 0.0)) return fail(c, SMM_ERR_INVALID_ARG, "a target must be finite and >= 0");
+        if (const int rc = check_probs(c, probs, n_probs, out->quantile != nullptr)) return rc;
+        if (const int rc = settled_window(c, t0, t1)) return rc;
+        const KParams& P = c->P;
+        const size_t N = P.N, np = P.np, nm = P.nm, D = np + nm, D1 = D + 1, DC = D + 3, G = n_groups, R = n_targets,
+                     nq = out->quantile ? n_probs : 0;
+        const int n = t1 - t0;
+        const bool wants_cov = out->cov != nullptr;
+        const bool grp_out = nq > 0 || wants_cov || out->status || out->n_kept || out->sum_u || out->ess || out->mean || out->value_mean ||
+                             out->m_mean;
+        const bool chain_out = out->chain_ess || out->chain_logz;
+        const Groups grp = group_members(group, G, N);
+        // the counting walk: every chain's selected and scored rows
+        DevBuf<int> dci(3 * N);   // the chains' groups, then cnt [2][N]
+        int *dgid = dci.p, *dcnt = dci.p + N, *dnsc = dci.p + 2 * N;
+        std::vector<int> cnt(2 * N);
+        HIPCHK(hipMemcpyAsync(dgid, grp.gid.data(), N * 4, hipMemcpyHostToDevice, c->stream));
+        launch_checked(c, k_rw_walk, dim3(N), dim3(RW_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, (const int*)dgid,
+                       (const long long*)nullptr, 1, dcnt, (int*)nullptr, (int*)nullptr, (double*)nullptr);
+        HIPCHK(hipMemcpyAsync(cnt.data(), dcnt, 2 * N * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        const std::vector<int> nsc(cnt.begin() + N, cnt.end());
+        const PoolPlan pp = pool_plan(grp, nsc);   // the pooled index space of the scored rows
+        const long long Mtot = pp.Mtot;
+        const int NC = pp.NC;
+        for (size_t g = 0; g < G && out->count; ++g) {
+            out->count[g] = 0;
+            for (int i = grp.gmem0[g]; i < grp.gmem0[g + 1]; ++i) out->count[g] += cnt[grp.mem[i]];
+        }
+        if (out->n_scored) std::copy(pp.gm.begin(), pp.gm.end(), out->n_scored);
+        if (out->n_chains) std::copy(grp.n_chains.begin(), grp.n_chains.end(), out->n_chains);
+        if (out->chain_n) std::copy(nsc.begin(), nsc.end(), out->chain_n);
+        if (!grp_out && !chain_out) return SMM_OK;
+        // a chain without a scored row (or in no group) takes no part: chain_ess 0, chain_logz NaN
+        auto idle_chains = [&] {
+            for (size_t r = 0; r < R; ++r)
+                for (size_t i = 0; i < N; ++i)
+                    if (nsc[i] == 0) {
+                        if (out->chain_ess) out->chain_ess[r * N + i] = 0.0;
+                        if (out->chain_logz) out->chain_logz[r * N + i] = NAN;
+                    }
+        };
+        if (Mtot == 0) {   // no scored row in any group: status 1, the doubles NaN, the integers 0
+            auto nan = [](double* p, size_t k) { if (p) std::fill(p, p + k, NAN); };
+            if (out->status) std::fill(out->status, out->status + R * G, 1);
+            if (out->n_kept) std::fill(out->n_kept, out->n_kept + R * G, 0);
+            nan(out->sum_u, R * G); nan(out->ess, R * G); nan(out->mean, R * G * np); nan(out->cov, R * G * np * np);
+            nan(out->value_mean, R * G); nan(out->m_mean, R * G * nm); nan(out->quantile, nq * R * G * np);
+            idle_chains();
+            return SMM_OK;
+        }
+        std::vector<int> act;   // the member chains with a scored row
+        for (int i : grp.mem)
+            if (nsc[i] > 0) act.push_back(i);
+        // the batch plan.  The scratch: four packed columns (history row and chain, v, w, q), Nbc chunks of the D + 3 columns (whose
+        // np x np pair sums stay under the result cap), and for the select jb packed columns of parameters.  Five columns and one
+        // chunk are the minimum; up to the batch cap more is asked for, so that a window that fills the capacity is not taken one
+        // chunk and one parameter at a time
+        const size_t col8 = (size_t)Mtot * 8, chunk8 = DC * STATS_LDS_N * 8, cap8 = N * (size_t)P.T * 8;
+        const size_t room = std::min(reducer_batch_cap(c), 2 * ((cap8 / 8 / STATS_LDS_N + N) * chunk8 + np * cap8));
+        reducer_scratch(c, 5 * cap8 + chunk8 + room);
+        const size_t hook = c->H.stats_scratch;
+        const size_t budget = hook ? std::min(c->st_scr_bytes, std::max(hook, 5 * col8 + chunk8)) : c->st_scr_bytes;
+        const size_t avail = budget - 5 * col8;   // (at least one chunk)
+        const int Nbc = (int)std::max<size_t>(1, std::min({(size_t)NC, avail / 2 / chunk8, reducer_batch_cap(c) / (np * np * 8)}));
+        const size_t jb = std::min(np, 1 + (avail - Nbc * chunk8) / col8);
+        std::vector<int> cgrp(NC);
+        for (size_t g = 0; g < G; ++g) std::fill(cgrp.begin() + pp.gch0[g], cgrp.begin() + pp.gch0[g + 1], (int)g);
+        std::vector<long long> lcst(Nbc);
+        for (int i = 0; i < Nbc; ++i) lcst[i] = (long long)i * STATS_LDS_N;
+        const int Rq = (int)nq;   // the weighted select: every group's columns of a batch of parameters, nq targets each
+        const size_t nwc = Rq ? G * jb : 0;
+        const int WB = nwc ? (int)std::min(nwc, std::max((size_t)1, GROUP_HIST_CAP / ((size_t)Rq * GROUP_BINS * 8))) : 0;
+        Carve Rv;   // 8-byte slices first
+        const auto sums = Rv.take<double>(G * DC), mu = Rv.take<double>(G * D1), acc = Rv.take<double>(G * np * np),
+                   csum = Rv.take<double>(DC * Nbc), csum2 = Rv.take<double>(np * np * (size_t)Nbc), fc = Rv.take<double>(N),
+                   Lc = Rv.take<double>(N), F = Rv.take<double>(G), dprobs = Rv.take<double>(nq), tq = Rv.take<double>(nq * G * np);
+        const auto o_cess = Rv.take<double>(R * N), o_clz = Rv.take<double>(R * N), o_su = Rv.take<double>(R * G), o_ess = Rv.take<double>(R * G),
+                   o_mean = Rv.take<double>(R * G * np), o_cov = Rv.take<double>(wants_cov ? R * G * np * np : 0),
+                   o_vm = Rv.take<double>(R * G), o_mm = Rv.take<double>(R * G * nm);
+        const auto o_kept = Rv.take<long long>(R * G), dlcst = Rv.take<long long>(Nbc), srem = Rv.take<long long>(nwc * Rq),
+                   doff = Rv.take<long long>(N), dG0 = Rv.take<long long>(G + 1), dgm = Rv.take<long long>(G), dcst = Rv.take<long long>(NC);
+        const auto nkept = Rv.take<unsigned long long>(G), qsum = Rv.take<unsigned long long>(G),
+                   spre = Rv.take<unsigned long long>(nwc * Rq), sghist = Rv.take<unsigned long long>((size_t)WB * Rq * GROUP_BINS);
+        const auto dact = Rv.take<int>(act.size()), dmem = Rv.take<int>(grp.mem.size()), dgmem0 = Rv.take<int>(G + 1),
+                   dgch0 = Rv.take<int>(G + 1), dclen = Rv.take<int>(NC), dcgrp = Rv.take<int>(NC), cnan = Rv.take<int>(DC * Nbc),
+                   gbad = Rv.take<int>(G), bad3 = Rv.take<int>(G), st = Rv.take<int>(G), o_st = Rv.take<int>(R * G);
+        void* d = reducer_result(c, Rv.bytes);
+        up(c, d, dprobs, probs, nq); up(c, d, dlcst, lcst); up(c, d, doff, pp.off); up(c, d, dG0, pp.G0); up(c, d, dgm, pp.gm);
+        up(c, d, dcst, pp.cst); up(c, d, dact, act); up(c, d, dmem, grp.mem); up(c, d, dgmem0, grp.gmem0); up(c, d, dgch0, pp.gch0);
+        up(c, d, dclen, pp.clen); up(c, d, dcgrp, cgrp);
+        auto clear = [&](auto sl, size_t count) { HIPCHK(hipMemsetAsync(sl.in(d), 0, count * sizeof(*sl.in(d)), c->stream)); };
+        clear(gbad, G);
+        int* src = (int*)c->st_scr;                                // [Mtot] the history row of a pooled row
+        int* rowc = src + Mtot;                                    // [Mtot] its chain
+        double* vcol = (double*)c->st_scr + Mtot;                  // [Mtot] its value
+        double* wcol = vcol + Mtot;                                // [Mtot] its weight w (of the target at hand)
+        long long* qcol = (long long*)(wcol + Mtot);               // [Mtot] its integer weight q
+        double* buf = wcol + 2 * Mtot;                             // [DC][Nbc][STATS_LDS_N]
+        double* ts = buf + (size_t)DC * Nbc * STATS_LDS_N;         // [jb][Mtot]
+        launch_checked(c, k_rw_walk, dim3(N), dim3(RW_WG), 0, (const double*)P.hrec, (int)N, P.HW, t0, n, (int)select, (const int*)dgid,
+                       (const long long*)doff.in(d), 0, dcnt, src, rowc, vcol);
+        auto chunk_batches = [&](auto body) {
+            for (int cb0 = 0; cb0 < NC; cb0 += Nbc) {
+                const int nb = std::min(Nbc, NC - cb0);
+                body(RwRows{buf, nb, cb0, (int)np, (int)nm, (int)N, P.HW, (const int*)dclen.in(d), (const int*)dcgrp.in(d),
+                            (const long long*)dcst.in(d), (const double*)P.hrec, (const int*)src, (const int*)rowc, (const double*)vcol,
+                            (const double*)wcol, (const double*)fc.in(d), (const double*)F.in(d)});
+            }
+        };
+        auto rows = [&](const RwRows& a, int mode, int j0, int jbb) {
+            launch_checked(c, k_rw_rows, dim3(STATS_LDS_N / RW_WG, a.nb), dim3(RW_WG), 0, a, mode, (const double*)mu.in(d), qcol,
+                           nkept.in(d), qsum.in(d), gbad.in(d), j0, jbb, Mtot, ts);
+        };
+        long long wmax = 0;
+        for (size_t g = 0; g < G; ++g) wmax = std::max(wmax, pp.gm[g]);
+        const long long per = std::min<long long>(STATS_WG * 16, std::max<long long>(1, c->H.group_wide_min - 1));   // (smm_get_adjustment's)
+        const int B = (int)std::min<long long>(1024, std::max<long long>(1, (wmax + per - 1) / per));
+        const int nt = ((int)np + COV_T - 1) / COV_T, ntiles = nt * (nt + 1) / 2;
+        auto want = [&](const void* p, auto sl) { return p ? sl.in(d) : nullptr; };
+        for (size_t r = 0; r < R; ++r) {   // the targets one after another over the same packed columns
+            launch_checked(c, k_rw_chain, dim3((unsigned)act.size()), dim3(RW_WG), (size_t)STATS_LDS_N * 8, (const int*)dact.in(d),
+                           (const long long*)doff.in(d), (const int*)dnsc, (const double*)P.cs, (const double*)vcol, targets[r], wcol,
+                           fc.in(d), Lc.in(d), out->chain_ess ? o_cess.in(d) + r * N : nullptr,
+                           out->chain_logz ? o_clz.in(d) + r * N : nullptr);
+            if (!grp_out) continue;
+            launch_checked(c, k_rw_group, dim3((unsigned)((G + 63) / 64)), dim3(64), 0, (const int*)dmem.in(d), (const int*)dgmem0.in(d),
+                           (const int*)dnsc, (const double*)fc.in(d), (const double*)Lc.in(d), (int)G, F.in(d), bad3.in(d));
+            clear(sums, G * DC); clear(nkept, G); clear(qsum, G);   // (the running sums from 0.0)
+            chunk_batches([&](const RwRows& a) {   // the weights; the sums of u theta, u s, u v, u and u u
+                rows(a, 1, 0, 0);
+                launch_checked(c, k_group_chunk_sum, dim3(a.nb, DC), dim3(STATS_WG), (size_t)STATS_LDS_N * 8, (const double*)buf,
+                               (long long)a.nb * STATS_LDS_N, (const long long*)dlcst.in(d), (const int*)dclen.in(d) + a.cb0, a.nb,
+                               csum.in(d), cnan.in(d));
+                launch_checked(c, k_adjust_sum_acc, dim3((unsigned)((G * DC + 255) / 256)), dim3(256), 0, (const double*)csum.in(d), a.nb,
+                               a.cb0, (const int*)dgch0.in(d), (int)G, (int)DC, sums.in(d));
+            });
+            launch_checked(c, k_adjust_means, dim3((unsigned)((G * D1 + 255) / 256)), dim3(256), 0, (const double*)sums.in(d), (int)G,
+                           (int)D1, mu.in(d));
+            if (wants_cov) {
+                clear(acc, G * np * np);
+                chunk_batches([&](const RwRows& a) {   // the centred, weighted parameter columns; their pair sums
+                    rows(a, 2, 0, 0);
+                    launch_checked(c, k_cov_pairs, dim3(a.nb, ntiles), dim3(COV_WG), 0, (const double*)buf, STATS_LDS_N, a.nb, 0, a.nb,
+                                   (int)np, (const int*)dclen.in(d) + a.cb0, csum2.in(d), 1);
+                    launch_checked(c, k_moment_cov_acc, dim3((unsigned)((G * np * (np + 1) / 2 + 255) / 256)), dim3(256), 0,
+                                   (const double*)csum2.in(d), a.nb, a.cb0, (const int*)dgch0.in(d), (int)G, (int)np, acc.in(d));
+                });
+            }
+            const RwOut ro{want(out->status, o_st.at(r * G)), want(out->n_kept, o_kept.at(r * G)), want(out->sum_u, o_su.at(r * G)),
+                           want(out->ess, o_ess.at(r * G)), want(out->mean, o_mean.at(r * G * np)),
+                           want(out->cov, o_cov.at(wants_cov ? r * G * np * np : 0)), want(out->value_mean, o_vm.at(r * G)),
+                           want(out->m_mean, o_mm.at(r * G * nm))};
+            launch_checked(c, k_rw_finish, dim3((unsigned)G), dim3(64), 0, (const double*)sums.in(d), (const double*)mu.in(d),
+                           (const double*)acc.in(d), (const long long*)dgm.in(d), (const int*)gbad.in(d), (const int*)bad3.in(d),
+                           (const unsigned long long*)nkept.in(d), (int)np, (int)nm, st.in(d), ro);
+            if (!Rq) continue;
+            for (size_t j0 = 0; j0 < np; j0 += jb) {   // batches of parameters: their packed columns, then their weighted quantiles
+                const int jbb = (int)std::min(jb, np - j0);
+                if (r == 0 || jb < np)
+                    for (int cb0 = 0; cb0 < NC; cb0 += 65535) {   // (every chunk at once: the packed columns need no chunk buffer)
+                        RwRows a{buf, std::min(65535, NC - cb0), cb0, (int)np, (int)nm, (int)N, P.HW, (const int*)dclen.in(d),
+                                 (const int*)dcgrp.in(d), (const long long*)dcst.in(d), (const double*)P.hrec, (const int*)src,
+                                 (const int*)rowc, (const double*)vcol, (const double*)wcol, (const double*)fc.in(d), (const double*)F.in(d)};
+                        rows(a, 3, (int)j0, jbb);
+                    }
+                const int nw = (int)G * jbb;
+                launch_checked(c, k_adjust_targets, dim3((unsigned)((nw * Rq + 255) / 256)), dim3(256), 0, (const unsigned long long*)qsum.in(d),
+                               (const int*)st.in(d), (const double*)dprobs.in(d), (int)G, jbb, Rq, srem.in(d), spre.in(d));
+                HIPCHK(hipMemsetAsync(sghist.in(d), 0, (size_t)WB * Rq * GROUP_BINS * 8, c->stream));   // (k_group_pick zeroes it again)
+                radix_digits(c, nw, Rq, WB, sghist.in(d), srem.in(d), spre.in(d), [&](int w0, int wn, int dg) {
+                    launch_checked(c, k_adjust_hist, dim3(wn, B, (Rq + ADJ_RB - 1) / ADJ_RB), dim3(STATS_WG), 0, (const double*)ts,
+                                   (const long long*)qcol, Mtot, (const long long*)dG0.in(d), (const long long*)dgm.in(d), jbb, Rq, dg, w0,
+                                   per, (const long long*)srem.in(d), (const unsigned long long*)spre.in(d), sghist.in(d));
+                });
+                launch_checked(c, k_adjust_finish, dim3((unsigned)((nw * Rq + 255) / 256)), dim3(256), 0,
+                               (const unsigned long long*)spre.in(d), (const int*)st.in(d), (int)G, (int)np, (int)j0, jbb, Rq, tq.in(d));
+            }
+            // the target's quantiles [nq][G][np] into the caller's [nq][R][G][np]
+            HIPCHK(hipMemcpy2DAsync(out->quantile + r * G * np, R * G * np * 8, tq.in(d), G * np * 8, G * np * 8, nq, hipMemcpyDeviceToHost,
+                                    c->stream));
+        }
+        down(c, d, o_cess, out->chain_ess, R * N); down(c, d, o_clz, out->chain_logz, R * N); down(c, d, o_st, out->status, R * G);
+        down(c, d, o_kept, out->n_kept, R * G); down(c, d, o_su, out->sum_u, R * G); down(c, d, o_ess, out->ess, R * G);
+        down(c, d, o_mean, out->mean, R * G * np); down(c, d, o_cov, out->cov, R * G * np * np); down(c, d, o_vm, out->value_mean, R * G);
+        down(c, d, o_mm, out->m_mean, R * G * nm);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        idle_chains();
         return SMM_OK;
     });
 }

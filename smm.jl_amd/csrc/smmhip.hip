@@ -75,6 +75,7 @@ using namespace smm;
 #include "smm_group.hpp"
 #include "smm_moments.hpp"
 #include "smm_adjust.hpp"
+#include "smm_reweight.hpp"
 #include "smm_hist.hpp"
 #include "smm_profile.hpp"
 #include "smm_trace.hpp"

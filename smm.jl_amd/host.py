@@ -901,6 +901,56 @@ def adjusted(algo, groups=None, window=None, state=True, tol=0.2, kernel="epanec
             for j in _builtins_range(r["count"].shape[0])]
 
 
+def tempered(algo, target=None, per=None, window=None, state=True, level=0.95, accepted_only=True):
+    """the target posterior from every temperature, from the device (include/smmhip.h: smm_get_reweighted) without downloading the
+    history: every chain's draws importance-reweighted from its own acc_tuners entry to `target` (default: the largest acc_tuners
+    entry, the coldest chain's), each chain self-normalised and entering with its own effective sample size.  It assumes that each
+    chain's state series targets exp(-acc_tuner v); BGP's exchange moves respect this only approximately.  One OrderedDict per group
+    with target, count, n_scored, chains, status (0 ok; 1 too few rows; 2 a non-finite parameter; 3 the weights overflowed), n_kept,
+    ess, value_mean and, keyed by ps2s_names, mean, sd (from the weighted population covariance) and band ([lo, hi]: the weighted
+    quantiles at `level`), keyed by ms_names m_mean, and cov [np][np].  per: a group id per chain (-1 = none), by default every chain
+    in one group; window and state as in moment_fit"""
+    t0, t1 = (0, algo.i) if window is None else (int(window[0]), int(window[1]))
+    a = float(np.max(algo._acc_tuner)) if target is None else float(target)
+    g = None if per is None else np.asarray(per, np.int32)
+    sel = "state" if state else "accepted" if accepted_only else "all"
+    q = ((1 - level) / 2, 1 - (1 - level) / 2)
+    r = algo._ctx.reweighted(t0, t1, sel, g, (a,), q)
+    ps, ms = ps2s_names(algo.m), ms_names(algo.m)
+    return [OrderedDict(target=a, count=int(r["count"][j]), n_scored=int(r["n_scored"][j]), chains=int(r["n_chains"][j]),
+                        status=int(r["status"][0, j]), n_kept=int(r["n_kept"][0, j]), ess=float(r["ess"][0, j]),
+                        value_mean=float(r["value_mean"][0, j]),
+                        mean=OrderedDict((k, float(r["mean"][0, j, i])) for i, k in enumerate(ps)),
+                        sd=OrderedDict((k, float(np.sqrt(r["cov"][0, j, i, i]))) for i, k in enumerate(ps)),
+                        band=OrderedDict((k, r["quantile"][:, 0, j, i].copy()) for i, k in enumerate(ps)),
+                        m_mean=OrderedDict((k, float(r["m_mean"][0, j, i])) for i, k in enumerate(ms)),
+                        cov=r["cov"][0, j].copy())
+            for j in _builtins_range(r["count"].shape[0])]
+
+
+def ladder_logz(algo, window=None, state=True, accepted_only=True):
+    """the log normaliser along the temperature ladder, from the device (smm_get_reweighted's chain_logz): the distinct acc_tuners
+    entries in ascending order a_0 < a_1 < ..; step k is the estimate of log Z(a_{k+1}) / Z(a_k) from the chains at a_k reweighted to
+    their colder neighbour (the mean of their chain_logz, each chain alone in its estimate), and logz their running sum from 0 at a_0:
+    the stepping-stone estimate.  Returns OrderedDict(acc_tuner [K], step [K - 1], logz [K], n_chains [K]); a step whose chains have
+    no scored row is NaN.  One call with one target per rung (at most 64 rungs above the first)"""
+    t0, t1 = (0, algo.i) if window is None else (int(window[0]), int(window[1]))
+    sel = "state" if state else "accepted" if accepted_only else "all"
+    acc = np.asarray(algo._acc_tuner, float)
+    rungs = np.unique(acc)
+    if len(rungs) - 1 > 64:
+        raise ValueError("ladder_logz: at most 65 distinct acc_tuners entries")
+    step = np.empty(max(len(rungs) - 1, 0))
+    if len(step):
+        r = algo._ctx.reweighted(t0, t1, sel, None, tuple(rungs[1:]), ())
+        for k in _builtins_range(len(step)):
+            z = r["chain_logz"][k, acc == rungs[k]]
+            z = z[~np.isnan(z)]
+            step[k] = z.mean() if len(z) else np.nan
+    return OrderedDict(acc_tuner=rungs, step=step, logz=np.concatenate([[0.0], np.cumsum(step)]),
+                       n_chains=np.array([(acc == a).sum() for a in rungs], np.int64))
+
+
 def summary(x):
     """summary(c::BGPChain) AlgoBGP.jl:197-206 / summary(m::MAlgoBGP) :541-550"""
     if isinstance(x, MAlgoBGP):
