@@ -1187,6 +1187,63 @@ typedef struct {             /* caller-allocated; any pointer may be NULL = not 
 } smm_opt_slices_t;
 int  smm_opt_slices(void* ctx, const double* starts /* [np][K], host */, int32_t K, int32_t npoints,
                     double tol, double update /* NaN = ranges never shrink */, int32_t max_cycles, smm_opt_slices_t* out);
+
+/* The estimate, second optimiser: K Nelder–Mead (simplex) searches inside the box [lb, ub], advancing together on the device — for curved or
+ * rotated valleys, which a coordinate search cannot follow.  Valid on any context at any iteration; it never changes the chains, the history,
+ * the generator's position or which kernel form the next step takes.  A stream objective draws from opts.seed, as smm_eval_batch does.
+ * Ordered on smm_stream behind everything enqueued before (a persistent launch is settled first) and synchronised before it returns; a
+ * hard error nobody has been told of yet is returned once, and nothing runs.
+ *
+ * Numerical contract: scipy's _minimize_neldermead with bounds and a given initial_simplex, made exact — every operation rounded on its own,
+ * no fma; per search, independent of every other search.  N = np, vertices sim[0..N], values fsim[0..N].
+ *   Coefficients, computed once in double on the host as Python computes them: rho = 1; chi = 2, psi = 0.5, sigma = 0.5, or with adaptive != 0
+ *   chi = 1 + 2/N, psi = 0.75 - 1/(2N), sigma = 1 - 1/N.  The products (1 + rho), (1 + rho chi), rho chi, (1 + psi rho), psi rho and (1 - psi)
+ *   are formed on the host too and reach the kernels as doubles.
+ *   Initial simplex: sim[0] = the start, which must lie inside the box and must not be NaN (else SMM_ERR_INVALID_ARG with the 1-based search
+ *   and parameter in the message; nothing runs); sim[k + 1] = the start with coordinate k replaced by y = x_k + step * (ub_k - lb_k); if
+ *   y > ub_k then y = 2 * ub_k - y; then y = min(max(y, lb_k), ub_k).  All N + 1 vertices are evaluated.
+ *   Sort, after the initial evaluation and at the end of every iteration: stable, ascending in fsim, NaN last, +inf just before NaN; equal
+ *   values keep their current order (np.argsort(kind="stable")).
+ *   No finite value (departure 1 from scipy, which would shrink until maxiter): after any sort, if fsim[0] is not finite the search stops with
+ *   status 2.
+ *   The loop, while fewer than max_iter iterations have run (else the search stops with status 0):
+ *   Convergence: size_x = max |sim[j][k] - sim[0][k]| over j >= 1 and all k, size_f = max |fsim[0] - fsim[j]| over j >= 1; the search stops
+ *   converged, status 1, when size_x <= xatol && size_f <= fatol; a NaN in either maximum (size_f is then NaN) makes the test false.  size_x
+ *   and size_f are NaN for a search that stopped before its first test.
+ *   Centroid and reflection: xbar_k = (sim[0][k] + sim[1][k] + ... + sim[N-1][k]) / N, added left to right; xr = clip((1 + rho) * xbar -
+ *   rho * sim[N]); fxr its value.  clip(x) = min(max(x, lb), ub) per coordinate.
+ *   Branches, scipy's comparisons literally (a NaN fails every <):
+ *     fxr < fsim[0]:        xe = clip((1 + rho chi) * xbar - rho chi * sim[N]); take xe if fxe < fxr (expansion), else take xr (reflection);
+ *     else fxr < fsim[N-1]: take xr (reflection);
+ *     else fxr < fsim[N]:   xc = clip((1 + psi rho) * xbar - psi rho * sim[N]); take xc if fxc <= fxr (outside contraction), else shrink;
+ *     else:                 xcc = clip((1 - psi) * xbar + psi * sim[N]); take xcc if fxcc < fsim[N] (inside contraction), else shrink.
+ *   "Take" replaces sim[N], its value and its moments — as evaluated, never evaluated again.
+ *   Shrink: sim[j] = clip(sim[0] + sigma * (sim[j] - sim[0])) for j = 1 .. N, each evaluated.
+ *   The objective's status is not consulted (as in smm_opt_slices).  value = fsim[0] of the final sort (departure 2: scipy reports
+ *   np.min(fsim), NaN whenever a vertex's value is; value is what best was evaluated to).  n_eval counts exactly the evaluations above; evaluated is their sum over the searches (evaluations that pad a launch are never counted).
+ *   SMM_ERR_INVALID_ARG: starts NULL, K < 1, (int64)K * (np + 1) >= 2^31, step outside (0, 1] or NaN, xatol or fatol negative or NaN,
+ *   max_iter < 1.
+ *   Scratch: a search takes (np + 2) ((np + nm + 1) x 8 + 4) + (2 np + nm + 1) x 8 + 20 bytes — per vertex its coordinates, moments,
+ *   value and place in the order, once more for an evaluation launch (no launch evaluates more than one point per search: the initial
+ *   simplex and a shrink go vertex by vertex), and the iteration's points and lists; the searches go in batches under smm_opt_slices'
+ *   64 MiB (at least one search per batch), one batch after another; freed before the call returns.  The host reads three 4-byte counts
+ *   per iteration: the searches that need a second point, that shrink, that go on. */
+typedef struct {             /* caller-allocated; any pointer may be NULL = not returned */
+    double*  best;           /* [np][K]        vertex 0 of the final simplex                 */
+    double*  value;          /* [K]            its objective value                           */
+    double*  sim_moments;    /* [nm][K]        moments as evaluated at that vertex           */
+    double*  simplex;        /* [np+1][np][K]  the final simplex                             */
+    double*  simplex_value;  /* [np+1][K]      its values, in final sorted order             */
+    double*  size_x;         /* [K]            the two quantities of the last convergence test */
+    double*  size_f;         /* [K]                                                          */
+    int32_t* iterations;     /* [K]            iterations run                                */
+    int32_t* status;         /* [K]            1 converged, 0 stopped by max_iter, 2 no finite value */
+    int32_t* moves;          /* [5][K]         iterations that ended in reflection, expansion, outside contraction, inside contraction, shrink */
+    int32_t* n_eval;         /* [K]            evaluations of this search                    */
+    int64_t  evaluated;      /* out: objective evaluations performed                         */
+} smm_opt_simplex_t;
+int  smm_opt_simplex(void* ctx, const double* starts /* [np][K], host */, int32_t K, double step, int32_t adaptive, double xatol, double fatol,
+                     int32_t max_iter, smm_opt_simplex_t* out);
 int  smm_get_timing(void* ctx, smm_timing_t* out);
 /* on = 1: bracket every kernel of smm_bgp_step with hipEvents on the ctx stream so that
  * smm_get_timing reports iter_kernel_ms / exch_kernel_ms (sums over the last step; each bracket

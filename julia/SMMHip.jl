@@ -18,7 +18,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
 export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_adjustment, hip_reweighted, hip_profile, hip_density, hip_register_transform, hip_derived, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
-export hip_set_population!, hip_scatter_population!, hip_opt_slices
+export hip_set_population!, hip_scatter_population!, hip_opt_slices, hip_opt_simplex
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
 const ABI_VERSION = 3
@@ -284,6 +284,21 @@ struct SmmOptSlices
     cycle_value::Ptr{Cdouble}
     cycles::Ptr{Int32}
     converged::Ptr{Int32}
+    evaluated::Int64
+end
+
+struct SmmOptSimplex
+    best::Ptr{Cdouble}
+    value::Ptr{Cdouble}
+    sim_moments::Ptr{Cdouble}
+    simplex::Ptr{Cdouble}
+    simplex_value::Ptr{Cdouble}
+    size_x::Ptr{Cdouble}
+    size_f::Ptr{Cdouble}
+    iterations::Ptr{Int32}
+    status::Ptr{Int32}
+    moves::Ptr{Int32}
+    n_eval::Ptr{Int32}
     evaluated::Int64
 end
 
@@ -1106,6 +1121,39 @@ function hip_opt_slices(h::HipBGP, starts::Matrix{Float64}, npoints::Integer; to
     end
     return (best = best, value = value, sim_moments = simm, lo = lo, hi = hi, delta = delta, cycle_value = cycle_value, cycles = cycles,
             converged = converged .!= 0, evaluated = evaluated)
+end
+
+"""
+    hip_opt_simplex(h, starts; step = 0.05, adaptive = false, xatol = 1e-4, fatol = 1e-4, max_iter = nothing)
+        -> (best, value, sim_moments, simplex, simplex_value, size_x, size_f, iterations, status, moves, n_eval, evaluated)
+
+`K = size(starts, 1)` Nelder–Mead searches inside the parameter box, `starts[s, k]` (search, parameter), advancing together on the device
+(`smm_opt_simplex`: scipy's bounded Nelder–Mead made exact; the initial simplex is `step` of each parameter's range wide): three 4-byte
+counts read back per iteration.  The chains of the context are not touched.  `max_iter = nothing`: 200 per parameter.  `best` is
+`(K, np)`, `sim_moments` `(K, nm)`, `simplex` `(K, np, np + 1)` (search, parameter, vertex), `simplex_value` `(K, np + 1)`, `moves` `(K, 5)`:
+iterations that ended in reflection, expansion, outside contraction, inside contraction, shrink; `status[s]`: 1 converged, 0 stopped by
+`max_iter`, 2 no finite value at any vertex.
+"""
+function hip_opt_simplex(h::HipBGP, starts::Matrix{Float64}; step::Real = 0.05, adaptive::Bool = false, xatol::Real = 1e-4, fatol::Real = 1e-4,
+                         max_iter::Union{Nothing, Integer} = nothing)
+    size(starts, 2) == h.np || throw(ArgumentError("starts must be (K, np) with np = $(h.np)"))
+    K = size(starts, 1)
+    mi = max_iter === nothing ? 200 * h.np : Int(max_iter)
+    best = Matrix{Float64}(undef, K, h.np); simm = Matrix{Float64}(undef, K, h.nm)
+    simplex = Array{Float64, 3}(undef, K, h.np, h.np + 1); simplex_value = Matrix{Float64}(undef, K, h.np + 1)
+    value = Vector{Float64}(undef, K); size_x = similar(value); size_f = similar(value)
+    iterations = Vector{Int32}(undef, K); status = similar(iterations); n_eval = similar(iterations)
+    moves = Matrix{Int32}(undef, K, 5)
+    evaluated = 0
+    GC.@preserve starts best simm simplex simplex_value value size_x size_f iterations status n_eval moves begin
+        out = Ref(SmmOptSimplex(pointer(best), pointer(value), pointer(simm), pointer(simplex), pointer(simplex_value), pointer(size_x),
+                                pointer(size_f), pointer(iterations), pointer(status), pointer(moves), pointer(n_eval), 0))
+        check(h.ctx, ccall(sym(:smm_opt_simplex), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cdouble, Cint, Cdouble, Cdouble, Cint, Ptr{SmmOptSimplex}),
+                           h.ctx, pointer(starts), K, Float64(step), adaptive ? 1 : 0, Float64(xatol), Float64(fatol), mi, out))
+        evaluated = Int(out[].evaluated)
+    end
+    return (best = best, value = value, sim_moments = simm, simplex = simplex, simplex_value = simplex_value, size_x = size_x, size_f = size_f,
+            iterations = iterations, status = status, moves = moves, n_eval = n_eval, evaluated = evaluated)
 end
 
 "per-chain state: what `save` / `readMalgo` / `restart!` need besides the history (AlgoAbstract.jl:83-102)"

@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, posterior_tempered, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, optSlicesHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, posterior_tempered, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, optSlicesHip, optSimplexHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -865,6 +865,34 @@ function optSlicesHip(m::MProb, npoints::Int; starts = nothing, tol::Real = 1e-5
             p[k] = r.best[s, j]
         end
         push!(out, Dict(:best => Dict(:p => p, :value => r.value[s]), :iterations => Int(r.cycles[s]), :converged => r.converged[s]))
+    end
+    return out
+end
+
+"""
+    optSimplexHip(m; starts = nothing, step = 0.05, adaptive = false, xatol = 1e-4, fatol = 1e-4, max_iter = nothing, opts = Dict()) -> Vector{Dict}
+
+Nelder–Mead inside the parameter box from many starts, the whole search on the device (`SMMHip.hip_opt_simplex`): for valleys that do not
+run along the axes, which `optSlicesHip` cannot follow.  `starts`: a vector of parameter dicts (`nothing`: the initial value).  Per start
+`Dict(:best => Dict(:p => ..., :value => ...), :iterations => n, :converged => Bool, :status => 0 | 1 | 2, :n_eval => n, :moves => [5])`;
+status 2: no vertex of the simplex had a finite value.
+"""
+function optSimplexHip(m::MProb; starts = nothing, step::Real = 0.05, adaptive::Bool = false, xatol::Real = 1e-4, fatol::Real = 1e-4,
+                       max_iter = nothing, opts::Dict = Dict())
+    ps = starts === nothing ? Any[m.initial_value] : starts
+    pk = collect(keys(m.params_to_sample))
+    P = Float64[p[k] for p in ps, k in pk]                      # K x np
+    h = eval_context(m, opts)
+    r = SMMHip.hip_opt_simplex(h, P; step = step, adaptive = adaptive, xatol = xatol, fatol = fatol, max_iter = max_iter)
+    SMMHip.hip_destroy!(h)
+    out = Dict[]
+    for (s, p0) in enumerate(ps)
+        p = deepcopy(p0)
+        for (j, k) in enumerate(pk)
+            p[k] = r.best[s, j]
+        end
+        push!(out, Dict(:best => Dict(:p => p, :value => r.value[s]), :iterations => Int(r.iterations[s]), :converged => r.status[s] == 1,
+                        :status => Int(r.status[s]), :n_eval => Int(r.n_eval[s]), :moves => Int.(r.moves[s, :])))
     end
     return out
 end

@@ -207,6 +207,14 @@ class smm_opt_slices_t(C.Structure):
     ]
 
 
+class smm_opt_simplex_t(C.Structure):
+    _fields_ = [
+        ("best", c_double_p), ("value", c_double_p), ("sim_moments", c_double_p), ("simplex", c_double_p), ("simplex_value", c_double_p),
+        ("size_x", c_double_p), ("size_f", c_double_p), ("iterations", c_int32_p), ("status", c_int32_p), ("moves", c_int32_p),
+        ("n_eval", c_int32_p), ("evaluated", C.c_int64),
+    ]
+
+
 class smm_timing_t(C.Structure):
     _fields_ = [
         ("step_ms", C.c_double), ("iter_kernel_ms", C.c_double), ("exch_kernel_ms", C.c_double),
@@ -284,6 +292,8 @@ SYMBOLS = [
     ("smm_scatter_population", C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.POINTER(smm_population_t)]),
     ("smm_opt_slices", C.c_int, [C.c_void_p, c_double_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                  C.POINTER(smm_opt_slices_t)]),
+    ("smm_opt_simplex", C.c_int, [C.c_void_p, c_double_p, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                  C.POINTER(smm_opt_simplex_t)]),
     ("smm_get_timing", C.c_int, [C.c_void_p, C.POINTER(smm_timing_t)]),
     ("smm_get_Z", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_profiling", C.c_int, [C.c_void_p, C.c_int32]),

@@ -647,7 +647,7 @@ class BGPContext:
         -1 = initial_value), evaluated"""
         return self._population(lambda out: self._fn("scatter_population")(self._ctx, int(M), float(spread), int(bool(keep_init)), out))
 
-    # --- the estimate (include/smmhip.h: smm_opt_slices) ------------------------------------------------------------------------
+    # --- the estimate (include/smmhip.h: smm_opt_slices, smm_opt_simplex) ------------------------------------------------------------------------
     def opt_slices(self, starts, npoints, tol=1e-5, update=None, max_cycles=1000):
         """K cyclic coordinate searches on grids of npoints values, starts [np][K], advancing together on the device (smm_opt_slices:
         optSlices of slices.jl from many starts; the context's chains are not touched).  update=None: the ranges never shrink.
@@ -663,6 +663,24 @@ class BGPContext:
         s = self._out(A.smm_opt_slices_t, r)
         self._check(self._fn("opt_slices")(self._ctx, A.dptr(st), K, int(npoints), float(tol), float("nan") if update is None else float(update),
                                            int(max_cycles), C.byref(s)))
+        r["evaluated"] = int(s.evaluated)
+        return r
+
+    def opt_simplex(self, starts, step=0.05, adaptive=False, xatol=1e-4, fatol=1e-4, max_iter=None):
+        """K Nelder–Mead searches inside the box, starts [np][K], advancing together on the device (smm_opt_simplex: scipy's bounded
+        Nelder–Mead made exact, the initial simplex `step` of each range wide; the context's chains are not touched).  max_iter=None:
+        200 * np.  Returns a dict: best [np][K], value [K], sim_moments [nm][K], simplex [np+1][np][K], simplex_value [np+1][K], size_x /
+        size_f [K], iterations [K], status [K] (1 converged, 0 max_iter, 2 no finite value), moves [5][K], n_eval [K], evaluated"""
+        st = A.f64(starts)
+        if st.ndim != 2 or st.shape[0] != self.np:
+            raise ValueError("opt_simplex: starts must be [np][K] with np = %d, got %s" % (self.np, st.shape))
+        K, V = st.shape[1], self.np + 1
+        r = dict(best=np.empty((self.np, K)), value=np.empty(K), sim_moments=np.empty((self.nm, K)), simplex=np.empty((V, self.np, K)),
+                 simplex_value=np.empty((V, K)), size_x=np.empty(K), size_f=np.empty(K), iterations=np.empty(K, np.int32),
+                 status=np.empty(K, np.int32), moves=np.empty((5, K), np.int32), n_eval=np.empty(K, np.int32))
+        s = self._out(A.smm_opt_simplex_t, r)
+        self._check(self._fn("opt_simplex")(self._ctx, A.dptr(st), K, float(step), int(bool(adaptive)), float(xatol), float(fatol),
+                                            200 * self.np if max_iter is None else int(max_iter), C.byref(s)))
         r["evaluated"] = int(s.evaluated)
         return r
 

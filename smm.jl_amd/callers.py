@@ -155,6 +155,24 @@ def optSlicesDevice(m, npoints, starts=None, tol=1e-5, update=None, maxiter=1000
     return opt_results(m, ctx.opt_slices(opt_starts(m, starts), npoints, tol, update, maxiter))
 
 
+def simplex_results(m, r):
+    """smm_opt_simplex' arrays as the same records, one per start: "iterations" the simplex iterations run, "converged" status == 1; and
+    "status", "n_eval" and "moves" (reflection, expansion, outside contraction, inside contraction, shrink)"""
+    out = opt_results(m, dict(best=r["best"], value=r["value"], cycles=r["iterations"], converged=r["status"] == 1))
+    for s, o in enumerate(out):
+        o.update(status=int(r["status"][s]), n_eval=int(r["n_eval"][s]), moves=[int(x) for x in r["moves"][:, s]])
+    return out
+
+
+def optSimplexDevice(m, starts=None, step=0.05, adaptive=False, xatol=1e-4, fatol=1e-4, maxiter=None, ctx=None):
+    """Nelder–Mead inside the parameter box from many starts, the whole search on the device (smm_opt_simplex, include/smmhip.h: scipy's
+    bounded Nelder–Mead made exact; K searches advance together, three 4-byte counts read back per iteration).  starts as optSlicesDevice
+    takes them; maxiter=None: 200 per parameter.  Returns a list with, per start, {"best": {"p", "value"}, "iterations", "converged",
+    "status", "n_eval", "moves"}."""
+    ctx = _eval_context(m, _flat_problem(m)) if ctx is None else ctx
+    return simplex_results(m, ctx.opt_simplex(opt_starts(m, starts), step, adaptive, xatol, fatol, maxiter))
+
+
 # ------------------------------------------------------------------------------------------
 # econometrics.jl
 # ------------------------------------------------------------------------------------------

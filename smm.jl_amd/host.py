@@ -1122,13 +1122,20 @@ def scatter_start(algo, M=64, spread=1.0, keep_init=True):
     return _install_start(algo, algo._ctx.scatter_population(M, spread, keep_init))
 
 
-def polish(algo, npoints, per="chain", tol=1e-5, update=None, maxiter=1000, groups=None):
+def polish(algo, npoints, per="chain", tol=1e-5, update=None, maxiter=1000, groups=None, method="slices", **simplex):
     """the estimate: a coordinate search on grids of npoints values (optSlices, slices.jl:114-242) from every chain's best point
     (per="chain") or from the best point of every group of chains (per="group": a group id per chain in `groups`, -1 = none; by default
     those of rhat), all searches at once on the device (smm_opt_slices).  The best points are those chain_stats reports (best_value,
     best_iter over the accepted draws); the chains are not touched.  Returns the searches' results sorted by value, each the reference's
-    {"best": {"p", "value"}, "iterations", "converged"} and "start": {"chain" or "group", "p", "value"}"""
-    from .callers import opt_results
+    {"best": {"p", "value"}, "iterations", "converged"} and "start": {"chain" or "group", "p", "value"}.
+    method="simplex": Nelder–Mead searches inside the box instead (smm_opt_simplex), for valleys that do not run along the axes; npoints,
+    tol, update and maxiter are ignored and the search's options go through keywords (step, adaptive, xatol, fatol, max_iter); the records
+    carry "status", "n_eval" and "moves" too."""
+    from .callers import opt_results, simplex_results
+    if method not in ("slices", "simplex"):
+        raise ValueError('polish: method must be "slices" or "simplex"')
+    if simplex and method != "simplex":
+        raise TypeError("polish: %s belong to method=\"simplex\"" % sorted(simplex))
     if per not in ("chain", "group"):
         raise ValueError('polish: per must be "chain" or "group"')
     if algo.i == 0:
@@ -1147,7 +1154,10 @@ def polish(algo, npoints, per="chain", tol=1e-5, update=None, maxiter=1000, grou
             who.append((gid, int(members[np.argmin(bv[members])])))   # (argmin: the lowest chain among equals)
     P = algo._history().params   # [t][np][N]
     starts = np.array([[P[int(bi[j]) - 1, k, j] for _, j in who] for k in range(P.shape[1])], float).reshape(P.shape[1], len(who))
-    res = opt_results(algo.m, algo._ctx.opt_slices(starts, npoints, tol, update, maxiter))
+    if method == "simplex":
+        res = simplex_results(algo.m, algo._ctx.opt_simplex(starts, **simplex))
+    else:
+        res = opt_results(algo.m, algo._ctx.opt_slices(starts, npoints, tol, update, maxiter))
     names = ps2s_names(algo.m)
     for s, (r, (label, j)) in enumerate(zip(res, who)):
         r["start"] = {per: label, "p": OrderedDict((k, float(starts[i, s])) for i, k in enumerate(names)), "value": float(bv[j])}
