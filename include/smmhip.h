@@ -1244,6 +1244,89 @@ typedef struct {             /* caller-allocated; any pointer may be NULL = not 
 } smm_opt_simplex_t;
 int  smm_opt_simplex(void* ctx, const double* starts /* [np][K], host */, int32_t K, double step, int32_t adaptive, double xatol, double fatol,
                      int32_t max_iter, smm_opt_simplex_t* out);
+
+/* Sample without chains: the adaptive population Monte Carlo ABC sampler of Lenormand, Jabot & Deffuant (2013), the whole loop on the
+ * device.  The algorithm is likelihood-free, so a posterior read off a history is an ABC posterior (smm_get_adjustment); the standard
+ * sampler for ABC is not MCMC but population Monte Carlo: P particles per generation, evaluated independently — no accept step, no
+ * exchange, no serial dependence; a generation is one batched evaluation plus reductions.  The prior is uniform on the box [lb, ub]; the
+ * context's objective value is the distance.  P = n_particles, A = n_keep; scale 2.0 is the paper's kernel.  Valid on any context at any
+ * iteration; it never changes the chains, the history, the generator's position or which kernel form the next step takes.  A stream
+ * objective draws from opts.seed, as smm_eval_batch does.  Ordered on smm_stream behind everything enqueued before (a persistent launch is
+ * settled first) and synchronised before it returns; a hard error nobody has been told of yet is returned once, and nothing runs.
+ *
+ * Numerical contract (every operation rounded on its own, no fma outside smm_exp; integers 64-bit).  All particle arithmetic is in unit
+ * space, u = (theta - lb) / (ub - lb), where the prior density is 1; theta_k = u_k * (ub_k - lb_k) + lb_k, as mapto_ab and the proposal
+ * compute it.  Philox blocks are philox_stream(opts.seed, STREAM_PMC = 8, counter) of smm_rng.hpp; u53 its uniform in [0, 1).
+ *   Generation 0: particle j in [0, P), parameter k: the block at counter {j, 0, k >> 1, 0}; u = u53(x0, x1) for even k, u53(x2, x3) for odd k.
+ *     All P particles are evaluated; lw_j = 0.0.
+ *   Distance: rho = value where status >= 1 and |value| <= DBL_MAX; otherwise rho = +inf and the particle is counted in n_invalid (the
+ *     status is consulted here, unlike in the optimisers: a failed simulation is not a posterior draw).
+ *   Select, after every generation: the candidates are the kept particles in stored order, then the new ones in j order.  A' = min(A,
+ *     candidates with finite rho); the A' candidates with the smallest rho are kept — ordered by smm_get_chain_stats' sort keys, the IEEE
+ *     total order (-0.0 before +0.0), ties to the earlier candidate — and stored in candidate order (a stable compaction).  eps_g = the
+ *     largest kept rho (NaN when A' = 0); n_new_kept_g = the new ones among the kept.  A' < 2: the run stops with status 2.
+ *   Sampling weights of the kept: M = max lw; w_i = smm_exp(lw_i - M); q_i = (int64) ceil(w_i * 1048576.0), at least 1; Q = sum q_i;
+ *     wn_i = (double) q_i / (double) Q; ess_g = ((double) Q * (double) Q) / (double) sum q_i^2.  Integer sums: none depends on an order.
+ *     A' = 0: ess_g NaN.
+ *   Stop, after the select and the weights of generation g, the first that applies: A' < 2: status 2; g >= 1 and p_acc_g <= p_acc_min:
+ *     status 1; g == max_gen: status 0.  p_acc_g = (double)(new particles of g with rho < eps_(g-1)) / (double)(P - A'), A' the previous
+ *     generation's, rho as it stands after the underflow rule below; p_acc_0 NaN.  eps never increases: the kept set is always the best
+ *     of a superset.
+ *   Kernel covariance (when the run goes on): mean_k = S(wn_i * u_ik); C_kl = S(e_ik * e_il), e_ik = sqrt(wn_i) * (u_ik - mean_k) —
+ *     smm_get_reweighted's pair sums; S the chunked pairwise sum of smm_get_group_stats, chunks of 8192 from the first kept particle.
+ *     Sigma_kl = scale * C_kl, then Sigma_kk = Sigma_kk + ridge.  L = chol(Sigma) by smm_adapt_proposal's rule; a pivot with !(s > 0) stops
+ *     the run with status 3, and the kept set is the result.  logc = -((double) np * 0.9189385332046727) - t, t = 0.0, t = t + smm_log(L_kk)
+ *     over k ascending.
+ *   Whitening: z = L^-1 u by forward substitution: s = u_k, then s = s - L_km * z_m for m = 0 .. k-1 in that order, z_k = s / L_kk.
+ *   New particle j in [0, P - A'), generation g >= 1.  Parent: v = u53(x0, x1) of the block at counter {j, g, 0, 1}; r = min((int64)(v *
+ *     (double) Q), Q - 1); the parent is the kept i with prefix_i <= r < prefix_i + q_i, prefix the exclusive integer prefix of q in stored
+ *     order.  Normals: n_2m and n_2m+1 are box_muller of the block at counter {j, g, m, 2}.  Step: y_k = L_k0 * n_0, then + L_km * n_m left
+ *     to right up to m = k, exactly as the Cholesky step of smm_propose.hpp; u_k = u_parent,k + y_k.  The particle is inside when
+ *     0 <= u_k <= 1 for every k (inclusive; a NaN fails).  An outside particle is not evaluated: rho = +inf, counted in n_outside.
+ *   Importance weight of a new particle with a finite rho (weights of particles that cannot be kept are never reported, so the others are
+ *     not computed), over the previous generation's kept i in stored order: d2 = (z_0 - z_i0)^2, then + (z_k - z_ik)^2 left to right;
+ *     t_i = wn_i * smm_exp(-0.5 * d2).  D = T(t): blocks of 256 consecutive kept particles from the first; each block's terms added left to
+ *     right from 0.0; the block sums added left to right from 0.0 — never a function of grid or scheduling.  lw = -(smm_log(D) + logc).
+ *     D < DBL_MIN: rho = +inf, counted in n_underflow.
+ *   Summary of the final kept set, in parameter space: mean_k = S(wn_i * theta_ik); cov_kl = S(e_ik * e_il) with e on theta, without scale or
+ *     ridge (the weighted population form; both triangles hold the same value); quantile p: smm_get_adjustment's integer rule on the q_i:
+ *     target = max(1, (int64) ceil(p * (double) Q)), the smallest kept theta_.k at which the q of the rows with theta <= it reach the
+ *     target, over the IEEE total order, one of the rows' own doubles.  ess = the last generation's ess_g.  n_kept = 0: all NaN.
+ *   Rows past n_kept are NaN (born: -1); entries of generations past the last are NaN or -1.  evaluated = P + the inside particles of every
+ *     later generation.
+ *   SMM_ERR_INVALID_ARG: n_particles > 2^22 (so that sum q^2 fits 63 bits), n_keep < 2 or >= n_particles, max_gen < 0, p_acc_min outside
+ *     [0, 1) or NaN, scale not > 0, ridge negative or not finite, n_probs < 0, probs NULL with n_probs > 0, a prob outside [0, 1] or NaN;
+ *     nothing runs then.
+ *   Scratch: the particles stay resident — u, z, theta, moments, rho, lw for P new particles and twice for A kept ones, q, its prefix, wn and a
+ *     second copy of z by particle (up to 512 bytes each) for the kept — plus 64 block sums of T per new particle (512 P bytes) and one evaluation launch's parameters, moments, value and
+ *     status ((np + nm + 1) x 8 + 4 bytes an evaluation), the inside particles going in batches under smm_opt_slices' 64 MiB; freed before
+ *     the call returns.  The host reads two small counts per generation: the particles inside, then A' and whether the run goes on. */
+typedef struct {              /* caller-allocated; any pointer may be NULL = not returned; G1 = max_gen + 1 */
+    double*  theta;           /* [np][A]     the kept particles, in stored order                   */
+    double*  value;           /* [A]         their distances                                       */
+    double*  sim_moments;     /* [nm][A]     their moments as evaluated                            */
+    double*  weight;          /* [A]         wn: the normalised sampling weights                   */
+    double*  logw;            /* [A]         lw                                                    */
+    int32_t* born;            /* [A]         the generation each was proposed in                   */
+    double*  eps;             /* [G1]        the largest kept distance after each generation       */
+    double*  p_acc;           /* [G1]        NaN at generation 0                                   */
+    double*  gen_ess;         /* [G1]                                                              */
+    int32_t* n_outside;       /* [G1]        new particles outside the box                         */
+    int32_t* n_invalid;       /* [G1]        evaluated particles without a valid finite value      */
+    int32_t* n_underflow;     /* [G1]        new particles whose kernel mixture underflowed        */
+    int32_t* n_new_kept;      /* [G1]        new particles among the kept                          */
+    double*  mean;            /* [np]                                                              */
+    double*  cov;             /* [np][np]                                                          */
+    double*  quantile;        /* [n_probs][np]                                                     */
+    double   ess;             /* out: the last generation's ess                                    */
+    int32_t  n_kept;          /* out: A' of the last generation                                    */
+    int32_t  generations;     /* out: the last generation run                                      */
+    int32_t  status;          /* out: 0 max_gen, 1 p_acc <= p_acc_min, 2 fewer than 2 finite particles, 3 kernel covariance not PD */
+    int32_t  reserved;
+    int64_t  evaluated;       /* out: objective evaluations performed                              */
+} smm_abc_pmc_t;
+int  smm_abc_pmc(void* ctx, int32_t n_particles /* P */, int32_t n_keep /* A */, int32_t max_gen, double p_acc_min, double scale /* 2.0 is the paper's */,
+                 double ridge, const double* probs, int32_t n_probs, smm_abc_pmc_t* out);
 int  smm_get_timing(void* ctx, smm_timing_t* out);
 /* on = 1: bracket every kernel of smm_bgp_step with hipEvents on the ctx stream so that
  * smm_get_timing reports iter_kernel_ms / exch_kernel_ms (sums over the last step; each bracket

@@ -18,7 +18,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
 export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_adjustment, hip_reweighted, hip_profile, hip_density, hip_register_transform, hip_derived, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
-export hip_set_population!, hip_scatter_population!, hip_opt_slices, hip_opt_simplex
+export hip_set_population!, hip_scatter_population!, hip_opt_slices, hip_opt_simplex, hip_abc_pmc
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
 const ABI_VERSION = 3
@@ -299,6 +299,31 @@ struct SmmOptSimplex
     status::Ptr{Int32}
     moves::Ptr{Int32}
     n_eval::Ptr{Int32}
+    evaluated::Int64
+end
+
+struct SmmAbcPmc
+    theta::Ptr{Cdouble}
+    value::Ptr{Cdouble}
+    sim_moments::Ptr{Cdouble}
+    weight::Ptr{Cdouble}
+    logw::Ptr{Cdouble}
+    born::Ptr{Int32}
+    eps::Ptr{Cdouble}
+    p_acc::Ptr{Cdouble}
+    gen_ess::Ptr{Cdouble}
+    n_outside::Ptr{Int32}
+    n_invalid::Ptr{Int32}
+    n_underflow::Ptr{Int32}
+    n_new_kept::Ptr{Int32}
+    mean::Ptr{Cdouble}
+    cov::Ptr{Cdouble}
+    quantile::Ptr{Cdouble}
+    ess::Cdouble
+    n_kept::Int32
+    generations::Int32
+    status::Int32
+    reserved::Int32
     evaluated::Int64
 end
 
@@ -1154,6 +1179,41 @@ function hip_opt_simplex(h::HipBGP, starts::Matrix{Float64}; step::Real = 0.05, 
     end
     return (best = best, value = value, sim_moments = simm, simplex = simplex, simplex_value = simplex_value, size_x = size_x, size_f = size_f,
             iterations = iterations, status = status, moves = moves, n_eval = n_eval, evaluated = evaluated)
+end
+
+"""
+    hip_abc_pmc(h, n_particles, n_keep; max_gen = 20, p_acc_min = 0.05, scale = 2.0, ridge = 0.0, probs = Float64[])
+        -> (theta, value, sim_moments, weight, logw, born, eps, p_acc, gen_ess, n_outside, n_invalid, n_underflow, n_new_kept, mean, cov,
+            quantile, ess, n_kept, generations, status, evaluated)
+
+Sample without chains: the adaptive population Monte Carlo ABC sampler of Lenormand, Jabot & Deffuant (2013) on the device (`smm_abc_pmc`):
+a uniform prior on the box, the objective value as the distance, `n_particles` particles a generation of which the best `n_keep` are kept.
+The chains of the context are not touched.  `theta` is `(n_keep, np)`, `sim_moments` `(n_keep, nm)`, rows past `n_kept` NaN; the
+per-generation vectors have `max_gen + 1` entries, NaN or -1 past the last generation; `quantile` is `(np, length(probs))`.  `status`: 0
+stopped by `max_gen`, 1 `p_acc <= p_acc_min`, 2 fewer than 2 finite particles, 3 kernel covariance not positive definite.
+"""
+function hip_abc_pmc(h::HipBGP, n_particles::Integer, n_keep::Integer; max_gen::Integer = 20, p_acc_min::Real = 0.05, scale::Real = 2.0,
+                     ridge::Real = 0.0, probs::Vector{Float64} = Float64[])
+    A = max(Int(n_keep), 0); G1 = max(Int(max_gen), 0) + 1; nq = length(probs)
+    theta = Matrix{Float64}(undef, A, h.np); simm = Matrix{Float64}(undef, A, h.nm)
+    value = Vector{Float64}(undef, A); weight = similar(value); logw = similar(value); born = Vector{Int32}(undef, A)
+    eps = Vector{Float64}(undef, G1); p_acc = similar(eps); gen_ess = similar(eps)
+    n_outside = Vector{Int32}(undef, G1); n_invalid = similar(n_outside); n_underflow = similar(n_outside); n_new_kept = similar(n_outside)
+    mean = Vector{Float64}(undef, h.np); cov = Matrix{Float64}(undef, h.np, h.np); quantile = Matrix{Float64}(undef, h.np, nq)
+    res = nothing
+    GC.@preserve probs theta simm value weight logw born eps p_acc gen_ess n_outside n_invalid n_underflow n_new_kept mean cov quantile begin
+        out = Ref(SmmAbcPmc(pointer(theta), pointer(value), pointer(simm), pointer(weight), pointer(logw), pointer(born), pointer(eps),
+                            pointer(p_acc), pointer(gen_ess), pointer(n_outside), pointer(n_invalid), pointer(n_underflow), pointer(n_new_kept),
+                            pointer(mean), pointer(cov), pointer(quantile), 0.0, 0, 0, 0, 0, 0))
+        check(h.ctx, ccall(sym(:smm_abc_pmc), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Cint, Ptr{SmmAbcPmc}),
+                           h.ctx, n_particles, n_keep, max_gen, Float64(p_acc_min), Float64(scale), Float64(ridge),
+                           nq > 0 ? pointer(probs) : Ptr{Cdouble}(C_NULL), nq, out))
+        res = out[]
+    end
+    return (theta = theta, value = value, sim_moments = simm, weight = weight, logw = logw, born = born, eps = eps, p_acc = p_acc,
+            gen_ess = gen_ess, n_outside = n_outside, n_invalid = n_invalid, n_underflow = n_underflow, n_new_kept = n_new_kept, mean = mean,
+            cov = cov, quantile = quantile, ess = res.ess, n_kept = Int(res.n_kept), generations = Int(res.generations), status = Int(res.status),
+            evaluated = Int(res.evaluated))
 end
 
 "per-chain state: what `save` / `readMalgo` / `restart!` need besides the history (AlgoAbstract.jl:83-102)"

@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, posterior_tempered, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, optSlicesHip, optSimplexHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, posterior_tempered, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, optSlicesHip, optSimplexHip, abcPMCHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -895,6 +895,26 @@ function optSimplexHip(m::MProb; starts = nothing, step::Real = 0.05, adaptive::
                         :status => Int(r.status[s]), :n_eval => Int(r.n_eval[s]), :moves => Int.(r.moves[s, :])))
     end
     return out
+end
+
+"""
+    abcPMCHip(m, n_particles; keep = 0.5, max_gen = 20, p_acc_min = 0.05, scale = 2.0, ridge = 0.0, probs = [0.025, 0.5, 0.975], opts = Dict()) -> Dict
+
+Sample without chains (`SMMHip.hip_abc_pmc`): the population Monte Carlo ABC sampler over the box of `m` with its objective value as the
+distance; `keep`: the kept fraction of the particles (or, `>= 2`, their number).  `Dict(:mean => Dict(name => value), :cov => Matrix,
+:quantile => Dict(name => [per prob]), :draws => (theta (n_kept, np), weight), :eps, :p_acc, :status, :ess, :generations, :evaluated)`.
+"""
+function abcPMCHip(m::MProb, n_particles::Integer; keep::Real = 0.5, max_gen::Integer = 20, p_acc_min::Real = 0.05, scale::Real = 2.0,
+                   ridge::Real = 0.0, probs::Vector{Float64} = [0.025, 0.5, 0.975], opts::Dict = Dict())
+    A = keep >= 2 ? Int(keep) : Int(floor(keep * n_particles))
+    pk = collect(keys(m.params_to_sample))
+    h = eval_context(m, opts)
+    r = SMMHip.hip_abc_pmc(h, n_particles, A; max_gen = max_gen, p_acc_min = p_acc_min, scale = scale, ridge = ridge, probs = probs)
+    SMMHip.hip_destroy!(h)
+    n, g = r.n_kept, r.generations
+    return Dict(:mean => Dict(k => r.mean[j] for (j, k) in enumerate(pk)), :cov => r.cov,
+                :quantile => Dict(k => r.quantile[j, :] for (j, k) in enumerate(pk)), :draws => (r.theta[1:n, :], r.weight[1:n]),
+                :eps => r.eps[1:g + 1], :p_acc => r.p_acc[1:g + 1], :status => r.status, :ess => r.ess, :generations => g, :evaluated => r.evaluated)
 end
 
 "`FD_gradient(m, p)` (econometrics.jl:29-85): the 1 + k (forward) or 2k (central) evaluations in one batch; rows in the order of `p`"

@@ -215,6 +215,16 @@ class smm_opt_simplex_t(C.Structure):
     ]
 
 
+class smm_abc_pmc_t(C.Structure):
+    _fields_ = [
+        ("theta", c_double_p), ("value", c_double_p), ("sim_moments", c_double_p), ("weight", c_double_p), ("logw", c_double_p),
+        ("born", c_int32_p), ("eps", c_double_p), ("p_acc", c_double_p), ("gen_ess", c_double_p), ("n_outside", c_int32_p),
+        ("n_invalid", c_int32_p), ("n_underflow", c_int32_p), ("n_new_kept", c_int32_p), ("mean", c_double_p), ("cov", c_double_p),
+        ("quantile", c_double_p), ("ess", C.c_double), ("n_kept", C.c_int32), ("generations", C.c_int32), ("status", C.c_int32),
+        ("reserved", C.c_int32), ("evaluated", C.c_int64),
+    ]
+
+
 class smm_timing_t(C.Structure):
     _fields_ = [
         ("step_ms", C.c_double), ("iter_kernel_ms", C.c_double), ("exch_kernel_ms", C.c_double),
@@ -294,6 +304,8 @@ SYMBOLS = [
                                  C.POINTER(smm_opt_slices_t)]),
     ("smm_opt_simplex", C.c_int, [C.c_void_p, c_double_p, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                   C.POINTER(smm_opt_simplex_t)]),
+    ("smm_abc_pmc", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, c_double_p, C.c_int32,
+                              C.POINTER(smm_abc_pmc_t)]),
     ("smm_get_timing", C.c_int, [C.c_void_p, C.POINTER(smm_timing_t)]),
     ("smm_get_Z", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_profiling", C.c_int, [C.c_void_p, C.c_int32]),

@@ -684,6 +684,26 @@ class BGPContext:
         r["evaluated"] = int(s.evaluated)
         return r
 
+    # --- sampling without chains (include/smmhip.h: smm_abc_pmc) ----------------------------------------------------------------------------------
+    def abc_pmc(self, n_particles, n_keep, max_gen=20, p_acc_min=0.05, scale=2.0, ridge=0.0, probs=()):
+        """the adaptive population Monte Carlo ABC sampler on the device (smm_abc_pmc: Lenormand, Jabot & Deffuant 2013; uniform prior on the
+        box, the objective value as the distance; the context's chains are not touched).  Returns a dict: theta [np][A], value [A],
+        sim_moments [nm][A], weight / logw [A], born [A], the per-generation eps, p_acc, gen_ess, n_outside, n_invalid, n_underflow,
+        n_new_kept [max_gen + 1], mean [np], cov [np][np], quantile [len(probs)][np], and the scalars ess, n_kept, generations, status
+        (0 max_gen, 1 p_acc <= p_acc_min, 2 fewer than 2 finite particles, 3 kernel covariance not positive definite), evaluated"""
+        Ap, G1 = max(int(n_keep), 0), max(int(max_gen), 0) + 1
+        pr = A.f64(list(probs))
+        r = dict(theta=np.empty((self.np, Ap)), value=np.empty(Ap), sim_moments=np.empty((self.nm, Ap)), weight=np.empty(Ap), logw=np.empty(Ap),
+                 born=np.empty(Ap, np.int32), eps=np.empty(G1), p_acc=np.empty(G1), gen_ess=np.empty(G1), n_outside=np.empty(G1, np.int32),
+                 n_invalid=np.empty(G1, np.int32), n_underflow=np.empty(G1, np.int32), n_new_kept=np.empty(G1, np.int32),
+                 mean=np.empty(self.np), cov=np.empty((self.np, self.np)), quantile=np.empty((len(pr), self.np)))
+        s = self._out(A.smm_abc_pmc_t, r)
+        self._check(self._fn("abc_pmc")(self._ctx, int(n_particles), int(n_keep), int(max_gen), float(p_acc_min), float(scale), float(ridge),
+                                        A.dptr(pr) if len(pr) else None, len(pr), C.byref(s)))
+        for f in ("ess", "n_kept", "generations", "status", "evaluated"):
+            r[f] = getattr(s, f)
+        return r
+
     def timing(self):
         t = A.smm_timing_t()
         self._check(self._fn("get_timing")(self._ctx, C.byref(t)))

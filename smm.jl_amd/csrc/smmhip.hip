@@ -86,6 +86,7 @@ using namespace smm;
 #include "smm_population.hpp"
 #include "smm_optslices.hpp"
 #include "smm_optsimplex.hpp"
+#include "smm_pmc.hpp"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -477,6 +478,7 @@ void eval_round_trip(Ctx* c, const double* params, int32_t M, double* value, dou
 #include "smm_population_host.hpp"
 #include "smm_optslices_host.hpp"
 #include "smm_optsimplex_host.hpp"
+#include "smm_pmc_host.hpp"
 #include "smm_create_host.hpp"
 
 extern "C" {

@@ -1164,6 +1164,39 @@ def polish(algo, npoints, per="chain", tol=1e-5, update=None, maxiter=1000, grou
     return sorted(res, key=lambda r: r["best"]["value"])   # (stable: equal values keep the order of their starts)
 
 
+class ABCPMCResult:
+    """what abc_pmc returns: the final weighted particles of smm_abc_pmc under the MProb's parameter names.  raw: the call's arrays"""
+
+    def __init__(self, names, raw):
+        self.names, self.raw = list(names), raw
+        self.n_kept, self.generations, self.status, self.ess, self.evaluated = (raw[f] for f in ("n_kept", "generations", "status", "ess", "evaluated"))
+        self.eps = raw["eps"][:self.generations + 1]
+        self.p_acc = raw["p_acc"][:self.generations + 1]
+
+    def mean(self):
+        return OrderedDict((k, float(v)) for k, v in zip(self.names, self.raw["mean"]))
+
+    def cov(self):
+        return np.array(self.raw["cov"])
+
+    def quantile(self):
+        """{name: [the quantile at each of the call's probs]}"""
+        return OrderedDict((k, [float(v) for v in self.raw["quantile"][:, i]]) for i, k in enumerate(self.names))
+
+    def draws(self):
+        """(theta [np][n_kept], weight [n_kept]): the kept particles and their normalised weights"""
+        n = self.n_kept
+        return np.array(self.raw["theta"][:, :n]), np.array(self.raw["weight"][:n])
+
+
+def abc_pmc(algo, n_particles, keep=0.5, max_gen=20, p_acc_min=0.05, scale=2.0, ridge=0.0, probs=(0.025, 0.5, 0.975)):
+    """sample without chains: the adaptive population Monte Carlo ABC sampler on the device (smm_abc_pmc; Lenormand, Jabot & Deffuant 2013)
+    over the MProb's box with its objective value as the distance; keep is the kept fraction of the particles (or, >= 2, their number).  The
+    chains of algo are not touched.  Returns an ABCPMCResult: mean(), cov(), quantile(), draws(), eps, p_acc, status, ess, evaluated"""
+    A = int(keep) if keep >= 2 else int(np.floor(keep * n_particles))
+    return ABCPMCResult(ps2s_names(algo.m), algo._ctx.abc_pmc(n_particles, A, max_gen, p_acc_min, scale, ridge, probs))
+
+
 def set_proposal(algo, L):
     """install proposal factor(s) between iterations (smm_set_proposal): [np][np] on a shared-factor run, [N][np][np] per chain"""
     algo._ctx.set_proposal(L)
