@@ -4,7 +4,8 @@ oracle's Philox and its elementary functions (oracle.contract_math: log, exp, si
 chain_cov_ref's chunked pairwise sum and Cholesky order; reweight_ref's total order and integer-weight quantile.  The generation loop, the
 select, the integer CDF, the whitening and the blocked sum T are stated here.  One evaluator call per generation: also the host loop the
 library offered before the device call (tools/abc_pmc_time.py).  Beyond the contract it keeps, per generation, what the tests assert on the
-restatement alone (`trace`: Sigma, L, logc, the parents, r, the prefix, the new particles' u, inside, D)."""
+restatement alone (`trace`: Sigma, L, logc, the parents, r, the prefix, the new particles' u, inside, D; `selects`: every generation's
+candidate distances, how many of them are old, and the candidates kept)."""
 import numpy as np
 
 import chain_cov_ref as CR
@@ -187,7 +188,7 @@ def abc_pmc(O, evaluator, seed, lb, ub, nm, P, A, max_gen, p_acc_min=0.05, scale
     G1 = max_gen + 1
     gen = dict(eps=np.full(G1, np.nan), p_acc=np.full(G1, np.nan), gen_ess=np.full(G1, np.nan), n_outside=np.full(G1, -1, np.int32),
                n_invalid=np.full(G1, -1, np.int32), n_underflow=np.full(G1, -1, np.int32), n_new_kept=np.full(G1, -1, np.int32))
-    trace = []
+    trace, selects = [], []
 
     def evaluate(theta):
         v, sm, st = evaluator(np.ascontiguousarray(theta))
@@ -212,7 +213,8 @@ def abc_pmc(O, evaluator, seed, lb, ub, nm, P, A, max_gen, p_acc_min=0.05, scale
         keep = select(cand["rho"], A)
         K = {f: (v[:, keep] if v.ndim == 2 else v[keep]) for f, v in cand.items()}
         Ap = len(keep)
-        gen["eps"][g] = K["rho"].max() if Ap else np.nan
+        gen["eps"][g] = K["rho"][np.argmax(RW.total_order_key(K["rho"]))] if Ap else np.nan      # (by the select's order: +0.0 above -0.0)
+        selects.append(dict(rho=cand["rho"], nk_old=nk_old, keep=keep))
         gen["n_new_kept"][g] = int((keep >= nk_old).sum())
         if g >= 1:
             gen["p_acc"][g] = np.float64(n_acc) / np.float64(n_new)
@@ -274,16 +276,19 @@ def abc_pmc(O, evaluator, seed, lb, ub, nm, P, A, max_gen, p_acc_min=0.05, scale
         out["quantile"] = np.array([[RW.weighted_quantile(K["th"][k], q, p) for k in range(npar)] for p in probs]).reshape(nq, npar)
     else:
         out["mean"], out["cov"], out["quantile"] = np.full(npar, np.nan), np.full((npar, npar), np.nan), np.full((nq, npar), np.nan)
-    out.update(ess=float(gen["gen_ess"][g]), n_kept=Ap, generations=g, status=status, evaluated=evaluated, trace=trace, q=q, kept_u=K["u"])
+    out.update(ess=float(gen["gen_ess"][g]), n_kept=Ap, generations=g, status=status, evaluated=evaluated, trace=trace, selects=selects, q=q, kept_u=K["u"])
     return out
 
 
 def assert_equal(got, want):
-    """every output field bit for bit (NaN equal to NaN), and the scalars"""
+    """every output field bit for bit (NaN equal to NaN; a zero's sign counts: -0.0 is not +0.0), and the scalars"""
     for f in FIELDS:
         a, b = np.asarray(got[f]), np.asarray(want[f])
         assert a.shape == b.shape, (f, a.shape, b.shape)
         assert np.array_equal(a, b, equal_nan=a.dtype.kind == "f"), (f, a, b)
+        if a.dtype.kind == "f":
+            num = ~(np.isnan(a) | np.isnan(b))
+            assert np.array_equal(np.signbit(a)[num], np.signbit(b)[num]), (f, a, b)
     for f in SCALARS:
         a, b = got[f], want[f]
         assert a == b or (f == "ess" and np.isnan(a) and np.isnan(b)), (f, a, b)
