@@ -1245,6 +1245,74 @@ typedef struct {             /* caller-allocated; any pointer may be NULL = not 
 int  smm_opt_simplex(void* ctx, const double* starts /* [np][K], host */, int32_t K, double step, int32_t adaptive, double xatol, double fatol,
                      int32_t max_iter, smm_opt_simplex_t* out);
 
+/* The estimate, third optimiser: K Levenberg–Marquardt searches inside the box [lb, ub], advancing together on the device — the first that
+ * uses what an SMM objective is: a weighted sum of squared moment discrepancies, whose simulated moments every evaluation returns beside the
+ * value.  An iteration costs np + 1 evaluations and up (a forward-difference Jacobian of the moments, then tries), and a search tens of
+ * iterations.  Valid on any context at any iteration; it never changes the chains, the history, the generator's position or which kernel
+ * form the next step takes.  A stream objective draws from opts.seed, as smm_eval_batch does (common random numbers: the differences of
+ * the Jacobian are differences in the parameters alone).  Ordered on smm_stream behind everything enqueued before (a persistent launch is
+ * settled first) and synchronised before it returns; a hard error nobody has been told of yet is returned once, and nothing runs.
+ *
+ * Numerical contract (every operation rounded on its own, no fma), per search, independent of every other search:
+ *   Weights: s_j = w_j if it is finite and not zero, else 1.0 (smm_get_moment_stats' rule).
+ *   Residual: r_j = (sim_j - mom_j) / s_j.  F = 0.0 + r_0^2 + r_1^2 + ...: squares rounded, added in ascending j.  The search minimises F, not
+ *   the objective's value: for objfunc_norm, dense_sim and dense_sim2 value is F / nm up to rounding; the banana's value is not its moment
+ *   distance (its moments are constant: every search ends with status 4), and a user objective's value is whatever its source makes it.
+ *   value is reported as evaluated and never consulted, and neither is the objective's status (as in the other two searches).
+ *   Start: x = the start, which must lie inside the box and must not be NaN (else SMM_ERR_INVALID_ARG with the 1-based search and parameter in
+ *   the message; nothing runs).  It is evaluated; if any r_j is not finite the search stops with status 2.  lambda = lambda0.
+ *   An iteration, while fewer than max_iter have run:
+ *   Jacobian: h_k = fd_step * (ub_k - lb_k); y = x_k + h_k, and if y > ub_k then y = x_k - h_k; d_k = y - x_k as rounded; point k is x with
+ *   coordinate k replaced by y; all np points are evaluated; J_jk = (r_j(point k) - r_j) / d_k.  A J_jk that is not finite: status 2.
+ *   Normal equations: g_k = 0.0 + J_0k r_0 + J_1k r_1 + ...; A_kl = 0.0 + J_0k J_0l + J_1k J_1l + ... for l <= k, mirrored; products rounded,
+ *   added in ascending j.
+ *   Active set: coordinate k is active when (x_k == lb_k && g_k > 0) || (x_k == ub_k && g_k < 0), free otherwise.  Then, in this order:
+ *   if a free k has A_kk == 0, no moment moves with that parameter and the search stops with status 4; if |g_k| <= gtol for every free k
+ *   (max |g_k| over the free k <= gtol), or no k is free, the search stops with status 1.  For an active k row and column k of A become 0,
+ *   A_kk = 1 and g_k = 0 (grad reports g before that).
+ *   Tries, at most max_tries per iteration: B = A with B_kk = A_kk + lambda * A_kk; L = B's lower Cholesky factor and delta = the solution
+ *   of L L' delta = -g by forward, then back substitution, both in smm_get_moment_stats' order; x_new = min(max(x + delta, lb), ub) per
+ *   coordinate, which is evaluated.  A pivot that is not > 0 is a failed try without an evaluation.  The try is accepted when r_new is all
+ *   finite and F_new < F; a failed try gives lambda = lambda * lambda_up.
+ *   On acceptance x, r, F, value and the moments are replaced, as evaluated (never evaluated again); step = max_k |x_new,k - x_k|, dF = F -
+ *   F_new, lambda = max(lambda / lambda_down, 1e-300); if step <= xtol || dF <= ftol * F_new the search stops with status 1; after max_iter
+ *   iterations it stops with status 0; else the next iteration begins.
+ *   If lambda is no longer finite after a failed try, or max_tries tries of an iteration failed, the search stops with status 3: no descent
+ *   was found — at a minimum, the normal ending.
+ *   Counts: iterations counts Jacobians, tries every try (a failed pivot too), n_eval exactly the evaluations above: 1, np per iteration and
+ *   one per try with a factor; evaluated is their sum over the searches.  Evaluations that pad a launch are never counted: a round of tries
+ *   is one launch of one point per search in it, in which a search without a factor — and, in an iteration's first round, one that stopped
+ *   at its normal equations — has x evaluated and the result ignored.
+ *   Results of a search that stopped before its first Jacobian: grad and jac NaN, active 0; step and dF are NaN before the first accepted try.
+ *   SMM_ERR_INVALID_ARG: starts NULL, K < 1, (int64)K * np >= 2^31, fd_step outside (0, 0.5] or NaN, lambda0 <= 0 or not finite,
+ *   lambda_up <= 1, lambda_down < 1 (or NaN), xtol, ftol or gtol negative or NaN, max_iter < 1, max_tries < 1.
+ *   Scratch: a search takes np ((nm + 1) x 8 + 4) + np x 8 + (nm + np^2 + np) x 8 + 32 bytes — moments, value and status of the Jacobian
+ *   launch's np evaluations, a trial point, its residuals, A, x_new, flags and list entries; a user objective's Jacobian points are written
+ *   out, np^2 x 8 instead of np x 8 (the built-in objectives' are never written: their evaluation kernel builds each from x and the one
+ *   shifted coordinate) —; the searches go in batches under smm_opt_slices' 64 MiB (at least one search per batch), one batch after
+ *   another; freed before the call returns.  The results' K x (3 np + nm + 9) x 8 bytes or so (and jac's K nm np x 8 when it is asked for)
+ *   hold x, F and lambda of the running searches and are not part of that.  The host reads one 4-byte count per round of tries — the
+ *   searches that try again — and one per iteration — the searches that go on. */
+typedef struct {             /* caller-allocated; any pointer may be NULL = not returned */
+    double*  best;           /* [np][K]      the point each search ended at                  */
+    double*  value;          /* [K]          objective value there, as evaluated             */
+    double*  sim_moments;    /* [nm][K]      simulated moments there, as evaluated           */
+    double*  ssr;            /* [K]          F, the sum of squared residuals, there          */
+    double*  grad;           /* [np][K]      the last g, before the active set zeroes it     */
+    double*  jac;            /* [nm][np][K]  the last Jacobian of the residuals              */
+    double*  lambda;         /* [K]          the final lambda                                */
+    double*  step;           /* [K]          step and dF of the last accepted try; NaN before one */
+    double*  dF;             /* [K]                                                          */
+    int32_t* active;         /* [np][K]      the last active set, 1 = active                 */
+    int32_t* iterations;     /* [K]          iterations run                                  */
+    int32_t* tries;          /* [K]          tries made                                      */
+    int32_t* n_eval;         /* [K]          evaluations of this search                      */
+    int32_t* status;         /* [K]          1 converged, 0 stopped by max_iter, 2 a residual or Jacobian entry not finite, 3 no descent found, 4 a parameter moves no moment */
+    int64_t  evaluated;      /* out: objective evaluations performed, the sum of n_eval      */
+} smm_opt_lm_t;
+int  smm_opt_lm(void* ctx, const double* starts /* [np][K], host */, int32_t K, double fd_step, double lambda0, double lambda_up,
+                double lambda_down, double xtol, double ftol, double gtol, int32_t max_iter, int32_t max_tries, smm_opt_lm_t* out);
+
 /* Sample without chains: the adaptive population Monte Carlo ABC sampler of Lenormand, Jabot & Deffuant (2013), the whole loop on the
  * device.  The algorithm is likelihood-free, so a posterior read off a history is an ABC posterior (smm_get_adjustment); the standard
  * sampler for ABC is not MCMC but population Monte Carlo: P particles per generation, evaluated independently — no accept step, no

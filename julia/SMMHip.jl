@@ -18,7 +18,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
 export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_adjustment, hip_reweighted, hip_profile, hip_density, hip_register_transform, hip_derived, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
-export hip_set_population!, hip_scatter_population!, hip_opt_slices, hip_opt_simplex, hip_abc_pmc
+export hip_set_population!, hip_scatter_population!, hip_opt_slices, hip_opt_simplex, hip_opt_lm, hip_abc_pmc
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
 const ABI_VERSION = 3
@@ -299,6 +299,24 @@ struct SmmOptSimplex
     status::Ptr{Int32}
     moves::Ptr{Int32}
     n_eval::Ptr{Int32}
+    evaluated::Int64
+end
+
+struct SmmOptLM
+    best::Ptr{Cdouble}
+    value::Ptr{Cdouble}
+    sim_moments::Ptr{Cdouble}
+    ssr::Ptr{Cdouble}
+    grad::Ptr{Cdouble}
+    jac::Ptr{Cdouble}
+    lambda::Ptr{Cdouble}
+    step::Ptr{Cdouble}
+    dF::Ptr{Cdouble}
+    active::Ptr{Int32}
+    iterations::Ptr{Int32}
+    tries::Ptr{Int32}
+    n_eval::Ptr{Int32}
+    status::Ptr{Int32}
     evaluated::Int64
 end
 
@@ -1179,6 +1197,41 @@ function hip_opt_simplex(h::HipBGP, starts::Matrix{Float64}; step::Real = 0.05, 
     end
     return (best = best, value = value, sim_moments = simm, simplex = simplex, simplex_value = simplex_value, size_x = size_x, size_f = size_f,
             iterations = iterations, status = status, moves = moves, n_eval = n_eval, evaluated = evaluated)
+end
+
+"""
+    hip_opt_lm(h, starts; fd_step = 1e-4, lambda0 = 1e-3, lambda_up = 10, lambda_down = 10, xtol = 1e-8, ftol = 1e-12, gtol = 0.0,
+               max_iter = 100, max_tries = 12)
+        -> (best, value, sim_moments, ssr, grad, jac, lambda, step, dF, active, iterations, tries, n_eval, status, evaluated)
+
+`K = size(starts, 1)` Levenberg–Marquardt searches inside the parameter box, `starts[s, k]` (search, parameter), advancing together on the
+device (`smm_opt_lm`: least squares on the moments' residuals `(sim - mom) / s` with forward-difference Jacobians, `fd_step` of each
+parameter's range wide): one 4-byte count read back per round of tries and one per iteration.  The chains of the context are not touched.
+`best` and `grad` are `(K, np)`, `sim_moments` `(K, nm)`, `jac` `(K, np, nm)` (search, parameter, moment), `active` `(K, np)`; `ssr` is
+the sum of squared residuals, which the search minimises; `status[s]`: 1 converged, 0 stopped by `max_iter`, 2 a residual or Jacobian
+entry not finite, 3 no descent found, 4 a parameter moves no moment.
+"""
+function hip_opt_lm(h::HipBGP, starts::Matrix{Float64}; fd_step::Real = 1e-4, lambda0::Real = 1e-3, lambda_up::Real = 10, lambda_down::Real = 10,
+                    xtol::Real = 1e-8, ftol::Real = 1e-12, gtol::Real = 0.0, max_iter::Integer = 100, max_tries::Integer = 12)
+    size(starts, 2) == h.np || throw(ArgumentError("starts must be (K, np) with np = $(h.np)"))
+    K = size(starts, 1)
+    best = Matrix{Float64}(undef, K, h.np); grad = similar(best); simm = Matrix{Float64}(undef, K, h.nm)
+    jac = Array{Float64, 3}(undef, K, h.np, h.nm)
+    value = Vector{Float64}(undef, K); ssr = similar(value); lambda = similar(value); step = similar(value); dF = similar(value)
+    active = Matrix{Int32}(undef, K, h.np)
+    iterations = Vector{Int32}(undef, K); tries = similar(iterations); n_eval = similar(iterations); status = similar(iterations)
+    evaluated = 0
+    GC.@preserve starts best grad simm jac value ssr lambda step dF active iterations tries n_eval status begin
+        out = Ref(SmmOptLM(pointer(best), pointer(value), pointer(simm), pointer(ssr), pointer(grad), pointer(jac), pointer(lambda),
+                           pointer(step), pointer(dF), pointer(active), pointer(iterations), pointer(tries), pointer(n_eval), pointer(status), 0))
+        check(h.ctx, ccall(sym(:smm_opt_lm), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble,
+                                                    Cint, Cint, Ptr{SmmOptLM}),
+                           h.ctx, pointer(starts), K, Float64(fd_step), Float64(lambda0), Float64(lambda_up), Float64(lambda_down), Float64(xtol),
+                           Float64(ftol), Float64(gtol), Int(max_iter), Int(max_tries), out))
+        evaluated = Int(out[].evaluated)
+    end
+    return (best = best, value = value, sim_moments = simm, ssr = ssr, grad = grad, jac = jac, lambda = lambda, step = step, dF = dF,
+            active = active .!= 0, iterations = iterations, tries = tries, n_eval = n_eval, status = status, evaluated = evaluated)
 end
 
 """

@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, posterior_tempered, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, optSlicesHip, optSimplexHip, abcPMCHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, posterior_tempered, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, optSlicesHip, optSimplexHip, optLMHip, abcPMCHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -893,6 +893,38 @@ function optSimplexHip(m::MProb; starts = nothing, step::Real = 0.05, adaptive::
         end
         push!(out, Dict(:best => Dict(:p => p, :value => r.value[s]), :iterations => Int(r.iterations[s]), :converged => r.status[s] == 1,
                         :status => Int(r.status[s]), :n_eval => Int(r.n_eval[s]), :moves => Int.(r.moves[s, :])))
+    end
+    return out
+end
+
+"""
+    optLMHip(m; starts = nothing, fd_step = 1e-4, lambda0 = 1e-3, lambda_up = 10, lambda_down = 10, xtol = 1e-8, ftol = 1e-12, gtol = 0.0,
+             max_iter = 100, max_tries = 12, opts = Dict()) -> Vector{Dict}
+
+Levenberg–Marquardt inside the parameter box from many starts, the whole search on the device (`SMMHip.hip_opt_lm`): least squares on the
+moments' residuals, the one optimiser here that follows the gradient of the moments.  `starts`: a vector of parameter dicts (`nothing`:
+the initial value).  Per start `Dict(:best => Dict(:p => ..., :value => ...), :iterations => n, :converged => Bool, :status => 0 .. 4,
+:n_eval => n, :tries => n, :ssr => F, :lambda => lambda)`; status 3: no descent found (at a minimum, the normal ending); 4: a parameter
+moves no moment.
+"""
+function optLMHip(m::MProb; starts = nothing, fd_step::Real = 1e-4, lambda0::Real = 1e-3, lambda_up::Real = 10, lambda_down::Real = 10,
+                  xtol::Real = 1e-8, ftol::Real = 1e-12, gtol::Real = 0.0, max_iter::Integer = 100, max_tries::Integer = 12, opts::Dict = Dict())
+    ps = starts === nothing ? Any[m.initial_value] : starts
+    pk = collect(keys(m.params_to_sample))
+    P = Float64[p[k] for p in ps, k in pk]                      # K x np
+    h = eval_context(m, opts)
+    r = SMMHip.hip_opt_lm(h, P; fd_step = fd_step, lambda0 = lambda0, lambda_up = lambda_up, lambda_down = lambda_down, xtol = xtol, ftol = ftol,
+                          gtol = gtol, max_iter = max_iter, max_tries = max_tries)
+    SMMHip.hip_destroy!(h)
+    out = Dict[]
+    for (s, p0) in enumerate(ps)
+        p = deepcopy(p0)
+        for (j, k) in enumerate(pk)
+            p[k] = r.best[s, j]
+        end
+        push!(out, Dict(:best => Dict(:p => p, :value => r.value[s]), :iterations => Int(r.iterations[s]), :converged => r.status[s] == 1,
+                        :status => Int(r.status[s]), :n_eval => Int(r.n_eval[s]), :tries => Int(r.tries[s]), :ssr => r.ssr[s],
+                        :lambda => r.lambda[s]))
     end
     return out
 end

@@ -13,6 +13,6 @@ from .host import (CI, ABCPMCResult, BGPChain, abc_pmc, adapt_proposal, scatter_
                    evaluateObjective, fill, dense_sim, dense_sim2, history, mean, median, ms_names, objfunc_norm, param, paramd, params,
                    ps2s_names, ps_names, readMalgo, restart, run, save, serialNormal, setMoments, setValue, snorm_impl,
                    summary, trace, user_objective)
-from .callers import (FD_gradient, Slice, doSlices, evaluateObjectives, getSigma, get_stdErrors, optSimplexDevice, optSlices, optSlicesDevice, range_length)
+from .callers import (FD_gradient, Slice, doSlices, evaluateObjectives, getSigma, get_stdErrors, optLMDevice, optSimplexDevice, optSlices, optSlicesDevice, range_length)
 
 __all__ = [n for n in dir() if not n.startswith("_")] + ["_abi"]

@@ -215,6 +215,14 @@ class smm_opt_simplex_t(C.Structure):
     ]
 
 
+class smm_opt_lm_t(C.Structure):
+    _fields_ = [
+        ("best", c_double_p), ("value", c_double_p), ("sim_moments", c_double_p), ("ssr", c_double_p), ("grad", c_double_p),
+        ("jac", c_double_p), ("lambda", c_double_p), ("step", c_double_p), ("dF", c_double_p), ("active", c_int32_p),
+        ("iterations", c_int32_p), ("tries", c_int32_p), ("n_eval", c_int32_p), ("status", c_int32_p), ("evaluated", C.c_int64),
+    ]
+
+
 class smm_abc_pmc_t(C.Structure):
     _fields_ = [
         ("theta", c_double_p), ("value", c_double_p), ("sim_moments", c_double_p), ("weight", c_double_p), ("logw", c_double_p),
@@ -304,6 +312,8 @@ SYMBOLS = [
                                  C.POINTER(smm_opt_slices_t)]),
     ("smm_opt_simplex", C.c_int, [C.c_void_p, c_double_p, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                   C.POINTER(smm_opt_simplex_t)]),
+    ("smm_opt_lm", C.c_int, [C.c_void_p, c_double_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                             C.c_double, C.c_int32, C.c_int32, C.POINTER(smm_opt_lm_t)]),
     ("smm_abc_pmc", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, c_double_p, C.c_int32,
                               C.POINTER(smm_abc_pmc_t)]),
     ("smm_get_timing", C.c_int, [C.c_void_p, C.POINTER(smm_timing_t)]),

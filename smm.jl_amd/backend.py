@@ -647,7 +647,7 @@ class BGPContext:
         -1 = initial_value), evaluated"""
         return self._population(lambda out: self._fn("scatter_population")(self._ctx, int(M), float(spread), int(bool(keep_init)), out))
 
-    # --- the estimate (include/smmhip.h: smm_opt_slices, smm_opt_simplex) ------------------------------------------------------------------------
+    # --- the estimate (include/smmhip.h: smm_opt_slices, smm_opt_simplex, smm_opt_lm) ------------------------------------------------------------------------
     def opt_slices(self, starts, npoints, tol=1e-5, update=None, max_cycles=1000):
         """K cyclic coordinate searches on grids of npoints values, starts [np][K], advancing together on the device (smm_opt_slices:
         optSlices of slices.jl from many starts; the context's chains are not touched).  update=None: the ranges never shrink.
@@ -681,6 +681,28 @@ class BGPContext:
         s = self._out(A.smm_opt_simplex_t, r)
         self._check(self._fn("opt_simplex")(self._ctx, A.dptr(st), K, float(step), int(bool(adaptive)), float(xatol), float(fatol),
                                             200 * self.np if max_iter is None else int(max_iter), C.byref(s)))
+        r["evaluated"] = int(s.evaluated)
+        return r
+
+    def opt_lm(self, starts, fd_step=1e-4, lambda0=1e-3, lambda_up=10, lambda_down=10, xtol=1e-8, ftol=1e-12, gtol=0.0, max_iter=100,
+               max_tries=12):
+        """K Levenberg–Marquardt searches inside the box, starts [np][K], advancing together on the device (smm_opt_lm: least squares on the
+        moments' residuals (sim - mom) / s with forward-difference Jacobians, fd_step of each range wide; the context's chains are not
+        touched).  Returns a dict: best [np][K], value [K], sim_moments [nm][K], ssr [K], grad [np][K], jac [nm][np][K], lambda / step / dF
+        [K], active [np][K], iterations / tries / n_eval [K], status [K] (1 converged, 0 max_iter, 2 not finite, 3 no descent found, 4 a
+        parameter moves no moment), evaluated"""
+        st = A.f64(starts)
+        if st.ndim != 2 or st.shape[0] != self.np:
+            raise ValueError("opt_lm: starts must be [np][K] with np = %d, got %s" % (self.np, st.shape))
+        K = st.shape[1]
+        i32 = lambda *shape: np.empty(shape, np.int32)      # noqa: E731
+        r = dict(best=np.empty((self.np, K)), value=np.empty(K), sim_moments=np.empty((self.nm, K)), ssr=np.empty(K), grad=np.empty((self.np, K)),
+                 jac=np.empty((self.nm, self.np, K)), step=np.empty(K), dF=np.empty(K), active=i32(self.np, K), iterations=i32(K), tries=i32(K),
+                 n_eval=i32(K), status=i32(K))
+        r["lambda"] = np.empty(K)
+        s = self._out(A.smm_opt_lm_t, r)
+        self._check(self._fn("opt_lm")(self._ctx, A.dptr(st), K, float(fd_step), float(lambda0), float(lambda_up), float(lambda_down), float(xtol),
+                                       float(ftol), float(gtol), int(max_iter), int(max_tries), C.byref(s)))
         r["evaluated"] = int(s.evaluated)
         return r
 

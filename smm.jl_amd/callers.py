@@ -173,6 +173,26 @@ def optSimplexDevice(m, starts=None, step=0.05, adaptive=False, xatol=1e-4, fato
     return simplex_results(m, ctx.opt_simplex(opt_starts(m, starts), step, adaptive, xatol, fatol, maxiter))
 
 
+def lm_results(m, r):
+    """smm_opt_lm's arrays as the same records, one per start: "iterations" the iterations run, "converged" status == 1; and "status",
+    "n_eval", "tries", "lambda" and "ssr" (the sum of squared residuals, which the search minimises)"""
+    out = opt_results(m, dict(best=r["best"], value=r["value"], cycles=r["iterations"], converged=r["status"] == 1))
+    for s, o in enumerate(out):
+        o.update(status=int(r["status"][s]), n_eval=int(r["n_eval"][s]), tries=int(r["tries"][s]), ssr=float(r["ssr"][s]))
+        o["lambda"] = float(r["lambda"][s])
+    return out
+
+
+def optLMDevice(m, starts=None, fd_step=1e-4, lambda0=1e-3, lambda_up=10, lambda_down=10, xtol=1e-8, ftol=1e-12, gtol=0.0, maxiter=100,
+                max_tries=12, ctx=None):
+    """Levenberg–Marquardt inside the parameter box from many starts, the whole search on the device (smm_opt_lm, include/smmhip.h: least
+    squares on the moments' residuals with forward-difference Jacobians; K searches advance together, one 4-byte count read back per round
+    of tries and one per iteration).  starts as optSlicesDevice takes them.  Returns a list with, per start, {"best": {"p", "value"},
+    "iterations", "converged", "status", "n_eval", "tries", "ssr", "lambda"}."""
+    ctx = _eval_context(m, _flat_problem(m)) if ctx is None else ctx
+    return lm_results(m, ctx.opt_lm(opt_starts(m, starts), fd_step, lambda0, lambda_up, lambda_down, xtol, ftol, gtol, maxiter, max_tries))
+
+
 # ------------------------------------------------------------------------------------------
 # econometrics.jl
 # ------------------------------------------------------------------------------------------

@@ -15,7 +15,7 @@
 // Files: smm_params.hpp (parameter block, layouts), smm_accept.hpp (the accept step's rules, written once for every kernel), smm_chain.hpp (chain kernel and its parts), smm_lookahead.hpp (k_pregen_rng,
 // k_exch_plan), smm_exchange.hpp (stand-alone exchange kernels), this file (host: the types, the call frame, the reader prelude, the plain entry points), smm_user_host.hpp (user objectives: registration and their persistent forms, one way through hiprtc), smm_forms_host.hpp (which forms a context runs and the LDS they take: select_forms),
 // smm_launch_host.hpp (the look-ahead windows, the three tables of kernel instantiations, the choosers, the launchers), smm_create_host.hpp (context creation, step by step), smm_run_host.hpp (the run's host side:
-// stepping, settling, the sharded protocol), smm_reducers_host.hpp (the history reducers' host side), smm_population_host.hpp (the starting population's), smm_optslices_host.hpp (smm_opt_slices: the coordinate searches' loop), smm_optsimplex_host.hpp (smm_opt_simplex: the simplex searches' loop).
+// stepping, settling, the sharded protocol), smm_reducers_host.hpp (the history reducers' host side), smm_population_host.hpp (the starting population's), smm_optslices_host.hpp (smm_opt_slices: the coordinate searches' loop), smm_optsimplex_host.hpp (smm_opt_simplex: the simplex searches' loop), smm_optlm_host.hpp (smm_opt_lm: the Levenberg–Marquardt searches' loop).
 // Everything that does not depend on the chains' state is produced ahead of the dependent loop by
 // wide, latency-tolerant kernels, one window of iterations at a time:
 //   k_pregen_rng      : proposal normals (first tries) and the MH uniforms (probs_acc, :85)
@@ -86,6 +86,7 @@ using namespace smm;
 #include "smm_population.hpp"
 #include "smm_optslices.hpp"
 #include "smm_optsimplex.hpp"
+#include "smm_optlm.hpp"
 #include "smm_pmc.hpp"
 
 // ------------------------------------------------------------------------------------------
@@ -133,7 +134,7 @@ struct Hooks {
     long long group_wide_min = STATS_LDS_N + 1;   // pooled columns of at least so many draws take the grid-wide select (1 .. STATS_LDS_N + 1)
     int hist_lds_bins = 1 << 30;   // bins (1-D) and bins2 (2-D) above this count into global memory, not LDS (1 ..)
     size_t pop_scratch = 0;        // the candidate scratch cap of smm_scatter_population instead of POP_SCRATCH_CAP (0: that cap): several batches of chains at small sizes
-    size_t opt_scratch = 0;        // the scratch cap of smm_opt_slices and smm_opt_simplex instead of OPT_SCRATCH_CAP (0: that cap): several batches of searches at small sizes
+    size_t opt_scratch = 0;        // the scratch cap of smm_opt_slices, smm_opt_simplex and smm_opt_lm instead of OPT_SCRATCH_CAP (0: that cap): several batches of searches at small sizes
     bool opt_materialise = false;  // smm_opt_slices writes the built-in objectives' candidates out too and evaluates them with k_eval_batch (tools/opt_slices_time.py)
 };
 Hooks read_hooks() {
@@ -478,6 +479,7 @@ void eval_round_trip(Ctx* c, const double* params, int32_t M, double* value, dou
 #include "smm_population_host.hpp"
 #include "smm_optslices_host.hpp"
 #include "smm_optsimplex_host.hpp"
+#include "smm_optlm_host.hpp"
 #include "smm_pmc_host.hpp"
 #include "smm_create_host.hpp"
 

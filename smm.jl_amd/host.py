@@ -1130,12 +1130,14 @@ def polish(algo, npoints, per="chain", tol=1e-5, update=None, maxiter=1000, grou
     {"best": {"p", "value"}, "iterations", "converged"} and "start": {"chain" or "group", "p", "value"}.
     method="simplex": Nelder–Mead searches inside the box instead (smm_opt_simplex), for valleys that do not run along the axes; npoints,
     tol, update and maxiter are ignored and the search's options go through keywords (step, adaptive, xatol, fatol, max_iter); the records
-    carry "status", "n_eval" and "moves" too."""
-    from .callers import opt_results, simplex_results
-    if method not in ("slices", "simplex"):
-        raise ValueError('polish: method must be "slices" or "simplex"')
-    if simplex and method != "simplex":
-        raise TypeError("polish: %s belong to method=\"simplex\"" % sorted(simplex))
+    carry "status", "n_eval" and "moves" too.
+    method="lm": Levenberg–Marquardt searches on the moments' residuals (smm_opt_lm), in the same way: the keywords are fd_step, lambda0,
+    lambda_up, lambda_down, xtol, ftol, gtol, max_iter and max_tries, and the records carry "status", "n_eval", "tries", "ssr" and "lambda"."""
+    from .callers import lm_results, opt_results, simplex_results
+    if method not in ("slices", "simplex", "lm"):
+        raise ValueError('polish: method must be "slices", "simplex" or "lm"')
+    if simplex and method == "slices":
+        raise TypeError("polish: %s belong to method=\"simplex\" or \"lm\"" % sorted(simplex))
     if per not in ("chain", "group"):
         raise ValueError('polish: per must be "chain" or "group"')
     if algo.i == 0:
@@ -1156,6 +1158,8 @@ def polish(algo, npoints, per="chain", tol=1e-5, update=None, maxiter=1000, grou
     starts = np.array([[P[int(bi[j]) - 1, k, j] for _, j in who] for k in range(P.shape[1])], float).reshape(P.shape[1], len(who))
     if method == "simplex":
         res = simplex_results(algo.m, algo._ctx.opt_simplex(starts, **simplex))
+    elif method == "lm":
+        res = lm_results(algo.m, algo._ctx.opt_lm(starts, **simplex))
     else:
         res = opt_results(algo.m, algo._ctx.opt_slices(starts, npoints, tol, update, maxiter))
     names = ps2s_names(algo.m)
