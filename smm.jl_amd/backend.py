@@ -648,15 +648,20 @@ class BGPContext:
         return self._population(lambda out: self._fn("scatter_population")(self._ctx, int(M), float(spread), int(bool(keep_init)), out))
 
     # --- the estimate (include/smmhip.h: smm_opt_slices, smm_opt_simplex, smm_opt_lm) ------------------------------------------------------------------------
+    def _opt_starts(self, name, starts):
+        """an optimiser's starts as the library reads them, [np][K] of float64, and K"""
+        st = A.f64(starts)
+        if st.ndim != 2 or st.shape[0] != self.np:
+            raise ValueError("%s: starts must be [np][K] with np = %d, got %s" % (name, self.np, st.shape))
+        return st, st.shape[1]
+
     def opt_slices(self, starts, npoints, tol=1e-5, update=None, max_cycles=1000):
         """K cyclic coordinate searches on grids of npoints values, starts [np][K], advancing together on the device (smm_opt_slices:
         optSlices of slices.jl from many starts; the context's chains are not touched).  update=None: the ranges never shrink.
         Returns a dict: best [np][K], value [K], sim_moments [nm][K], lo / hi [np][K], delta [K], cycle_value [max_cycles][K],
         cycles [K], converged [K], evaluated"""
-        st = A.f64(starts)
-        if st.ndim != 2 or st.shape[0] != self.np:
-            raise ValueError("opt_slices: starts must be [np][K] with np = %d, got %s" % (self.np, st.shape))
-        K, mc = st.shape[1], max(int(max_cycles), 0)
+        st, K = self._opt_starts("opt_slices", starts)
+        mc = max(int(max_cycles), 0)
         r = dict(best=np.empty((self.np, K)), value=np.empty(K), sim_moments=np.empty((self.nm, K)), lo=np.empty((self.np, K)),
                  hi=np.empty((self.np, K)), delta=np.empty(K), cycle_value=np.empty((mc, K)), cycles=np.empty(K, np.int32),
                  converged=np.empty(K, np.int32))
@@ -671,10 +676,8 @@ class BGPContext:
         Nelder–Mead made exact, the initial simplex `step` of each range wide; the context's chains are not touched).  max_iter=None:
         200 * np.  Returns a dict: best [np][K], value [K], sim_moments [nm][K], simplex [np+1][np][K], simplex_value [np+1][K], size_x /
         size_f [K], iterations [K], status [K] (1 converged, 0 max_iter, 2 no finite value), moves [5][K], n_eval [K], evaluated"""
-        st = A.f64(starts)
-        if st.ndim != 2 or st.shape[0] != self.np:
-            raise ValueError("opt_simplex: starts must be [np][K] with np = %d, got %s" % (self.np, st.shape))
-        K, V = st.shape[1], self.np + 1
+        st, K = self._opt_starts("opt_simplex", starts)
+        V = self.np + 1
         r = dict(best=np.empty((self.np, K)), value=np.empty(K), sim_moments=np.empty((self.nm, K)), simplex=np.empty((V, self.np, K)),
                  simplex_value=np.empty((V, K)), size_x=np.empty(K), size_f=np.empty(K), iterations=np.empty(K, np.int32),
                  status=np.empty(K, np.int32), moves=np.empty((5, K), np.int32), n_eval=np.empty(K, np.int32))
@@ -691,10 +694,7 @@ class BGPContext:
         touched).  Returns a dict: best [np][K], value [K], sim_moments [nm][K], ssr [K], grad [np][K], jac [nm][np][K], lambda / step / dF
         [K], active [np][K], iterations / tries / n_eval [K], status [K] (1 converged, 0 max_iter, 2 not finite, 3 no descent found, 4 a
         parameter moves no moment), evaluated"""
-        st = A.f64(starts)
-        if st.ndim != 2 or st.shape[0] != self.np:
-            raise ValueError("opt_lm: starts must be [np][K] with np = %d, got %s" % (self.np, st.shape))
-        K = st.shape[1]
+        st, K = self._opt_starts("opt_lm", starts)
         i32 = lambda *shape: np.empty(shape, np.int32)      # noqa: E731
         r = dict(best=np.empty((self.np, K)), value=np.empty(K), sim_moments=np.empty((self.nm, K)), ssr=np.empty(K), grad=np.empty((self.np, K)),
                  jac=np.empty((self.nm, self.np, K)), step=np.empty(K), dF=np.empty(K), active=i32(self.np, K), iterations=i32(K), tries=i32(K),

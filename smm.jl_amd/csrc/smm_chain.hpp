@@ -1260,24 +1260,25 @@ __global__ void k_flush(const KParams P, const int t_next, const double* __restr
     for (int f = 0; f < RW; ++f) rec_out[(size_t)c * RW + f] = rec_in[(size_t)s * RW + f];
 }
 
-// batched evaluateObjective(m,p), mprob.jl:175-188: params [np][M] -> value, simM [nm][M], status
-template <int KIND, int CT>
-__global__ __launch_bounds__(WG, 4) void k_eval_batch(const KParams P, const double* __restrict__ params, const int M,
-                                                      double* __restrict__ value, double* __restrict__ simM,
-                                                      int8_t* __restrict__ status) {
+// One tile of CT evaluations out of n, evaluation i = blockIdx.x * CT + lane: what every batched evaluation kernel of the built-in
+// objectives runs (k_eval_batch here; the estimators' k_eval_slice and k_eval_lm, smm_evalscratch.hpp) -> value [n], simM [nm][n], status
+// [n].  The kernels differ in where a tile's parameters come from: fill(S, tid) writes S.theta [CT][np] — 0.0 for the evaluations past
+// n — before the first barrier.
+template <int KIND, int CT, class Fill>
+__device__ __forceinline__ void eval_tile(const KParams& P, const int n, Fill fill, double* __restrict__ out_value, double* __restrict__ out_simM,
+                                          int8_t* __restrict__ out_status) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     TileSmem S;
     S.carve(smem, CT, P.np, P.nm, P.RW, P.HW, P.RBW, KIND != 0);
     const int tid = threadIdx.x;
     const int i = blockIdx.x * CT + tid;
-    const bool chain_lane = (tid < CT) && (i < M);
+    const bool chain_lane = (tid < CT) && (i < n);
     double za[ZU];
     ZBuf zb;
     if constexpr (KIND == 1) { zb.init(P, tid); sim_load_chunk(zb, P, 0, 0, za); }
     if (tid >= 64 && tid < 128)
         for (int k = tid - 64; k < P.nm; k += 64) { S.mom[k] = P.mom[k]; S.w[k] = P.w[k]; }
-    if (tid < CT)
-        for (int k = 0; k < P.np; ++k) S.theta[tid * P.np + k] = chain_lane ? params[(size_t)k * M + i] : 0.0;
+    fill(S, tid);
     __syncthreads();
     if constexpr (KIND == 1) {
         simulate_tile<CT>(P, zb, S.theta, S.part, tid, za);
@@ -1291,10 +1292,22 @@ __global__ __launch_bounds__(WG, 4) void k_eval_batch(const KParams P, const dou
         int st;
         double* sm = S.h + tid * P.HW;
         finish_objective<CT>(P, S.theta + tid * P.np, S.part, S.mom, S.w, tid, sm, v, st);
-        value[i] = v;
-        status[i] = (int8_t)st;
-        for (int k = 0; k < P.nm; ++k) simM[(size_t)k * M + i] = sm[k];
+        out_value[i] = v;
+        out_status[i] = (int8_t)st;
+        for (int k = 0; k < P.nm; ++k) out_simM[(size_t)k * n + i] = sm[k];
     }
+}
+
+// batched evaluateObjective(m,p), mprob.jl:175-188: params [np][M] -> value, simM [nm][M], status
+template <int KIND, int CT>
+__global__ __launch_bounds__(WG, 4) void k_eval_batch(const KParams P, const double* __restrict__ params, const int M,
+                                                      double* __restrict__ value, double* __restrict__ simM,
+                                                      int8_t* __restrict__ status) {
+    eval_tile<KIND, CT>(P, M, [&](const TileSmem& S, const int tid) {   // (lanes tid < CT: np loads each)
+        const int i = blockIdx.x * CT + tid;
+        if (tid < CT)
+            for (int k = 0; k < P.np; ++k) S.theta[tid * P.np + k] = i < M ? params[(size_t)k * M + i] : 0.0;
+    }, value, simM, status);
 }
 
 // objfunc_norm with options[:noseed] = true (ObjExamples.jl:71-75): every evaluation draws its own shock matrix (the

@@ -375,9 +375,8 @@ void lds_limits(Ctx* c) {
         const ExchInstance I = exch_instance(id, c->P.Ng);
         if (I.fn && I.cap && on[I.group]) HIPCHK(hipFuncSetAttribute(I.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)I.cap));
     }
-    for (const void* fn : {(const void*)k_eval_batch<1, 8>, (const void*)k_eval_batch<2, 16>, (const void*)k_eval_batch<0, 8>})
-        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CU));
-    slice_lds_limits();   // (k_eval_slice, the same instances: smm_optslices_host.hpp)
+    for (int family = 0; family < EF_COUNT; ++family)   // (every row of eval_instance)
+        for (int kind = 0; kind < 3; ++kind) HIPCHK(hipFuncSetAttribute(eval_instance(family, kind).fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CU));
     // (every kernel chain_kernel / chain_kernel_p2p can pick: what chain_instance names)
     for (int family = 0; family < CF_COUNT; ++family)
         for (int np = 1; np <= 4; ++np)

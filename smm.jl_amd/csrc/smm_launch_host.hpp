@@ -1,6 +1,6 @@
 // which kernel a launch takes and how it is launched — part of libsmmhip (included once by smmhip.hip, between smm_forms_host.hpp and
-// smm_run_host.hpp; hiprtc never sees it): the look-ahead windows (ensure_windows), the three tables that name every instantiation of
-// a kernel family a launch can take (chain_instance, exch_instance, persist_instance), the choosers that pick a row and decide nothing
+// smm_run_host.hpp; hiprtc never sees it): the look-ahead windows (ensure_windows), the four tables that name every instantiation of
+// a kernel family a launch can take (chain_instance, eval_instance, exch_instance, persist_instance), the choosers that pick a row and decide nothing
 // else (chain_kernel*, resolve_*, persist_kernel), and the launchers.  The tables stand in this order, and their rows in theirs: the
 // kernels are emitted, and a few numbered, in the order in which the host code names them.
 #pragma once
@@ -231,23 +231,38 @@ void launch_user_kernel(Ctx* c, const double* theta, int n, double* simM, double
         HIPCHK(hipModuleLaunchKernel(fn, (unsigned)((n + 127) / 128), 1, 1, 128, 1, 1, 0, c->stream, args, nullptr));
 }
 
-// n evaluations on device pointers, onto the context's stream (smm_eval_batch and the starting population share it): the built-in objectives read
-// params [np][n] and write simM [nm][n] and status as int8; a user objective's kernel (launch_user_kernel) reads theta [n][np] and writes
-// simM [n][nm] and status as int
+// ---- the batched evaluation kernels of the built-in objectives (eval_tile, smm_chain.hpp) ----
+// Every instantiation of them is named in eval_instance() and nowhere else: a family — k_eval_batch on candidates that were written, the
+// estimators' k_eval_slice and k_eval_lm on points that never are — by obj_kind() (1: simulated, 2: dense, 0: closed form), and the tile
+// it takes.  launch_eval_tiles launches the context's row of a family, lds_limits raises every row's dynamic LDS limit.
+enum EvalFamily { EF_BATCH, EF_SLICE, EF_LM, EF_COUNT };
+struct EvalKernel { const void* fn; int ct; };
+EvalKernel eval_instance(int family, int kind) {
+#define EVAL(KERN) (kind == 1 ? EvalKernel{(const void*)KERN<1, 8>, 8} : kind == 2 ? EvalKernel{(const void*)KERN<2, 16>, 16} : EvalKernel{(const void*)KERN<0, 8>, 8})
+    switch (family) {
+        case EF_BATCH: return EVAL(k_eval_batch);
+        case EF_SLICE: return EVAL(k_eval_slice);
+        default: return EVAL(k_eval_lm);
+    }
+#undef EVAL
+}
+// n evaluations by the context's row of `family`, onto its stream (args: the kernel's own)
+void launch_eval_tiles(Ctx* c, int family, int n, void** args) {
+    const EvalKernel K = eval_instance(family, obj_kind(c->obj));
+    HIPCHK(hipLaunchKernel(K.fn, dim3((unsigned)((n + K.ct - 1) / K.ct)), dim3(WG), args, tile_smem_base(c, K.ct), c->stream));
+}
+
+// n evaluations on device pointers, onto the context's stream (smm_eval_batch and the estimators share it), in the layouts EvalScratch
+// states (smm_evalscratch.hpp): the built-in objectives' k_eval_batch, or a user objective's kernel (launch_user_kernel)
 void launch_eval_dev(Ctx* c, const double* params, int n, double* value, double* simM, void* status) {
-    const KParams& P = c->P;
     if (c->obj == SMM_OBJ_USER) {
         launch_user_kernel(c, params, n, simM, value, (int*)status);
         return;
     }
-    constexpr int CT = 8;
-    if (is_sim(c->obj))
-        hipLaunchKernelGGL((k_eval_batch<1, CT>), dim3((n + CT - 1) / CT), dim3(WG), tile_smem_base(c, CT), c->stream, P, params, n, value, simM, (int8_t*)status);
-    else if (c->obj == SMM_OBJ_DENSE)
-        hipLaunchKernelGGL((k_eval_batch<2, 16>), dim3((n + 15) / 16), dim3(WG), tile_smem_base(c, 16), c->stream, P, params, n, value, simM, (int8_t*)status);
-    else
-        hipLaunchKernelGGL((k_eval_batch<0, CT>), dim3((n + CT - 1) / CT), dim3(WG), tile_smem_base(c, CT), c->stream, P, params, n, value, simM, (int8_t*)status);
-    HIPCHK(hipGetLastError());
+    const KParams& P = c->P;
+    int8_t* st = (int8_t*)status;
+    void* args[] = {(void*)&P, (void*)&params, (void*)&n, (void*)&value, (void*)&simM, (void*)&st};
+    launch_eval_tiles(c, EF_BATCH, n, args);
 }
 
 void launch_chain_iter(Ctx* c, int t, int flags) {

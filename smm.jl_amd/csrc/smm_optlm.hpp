@@ -1,6 +1,6 @@
 // smm_opt_lm: K Levenberg–Marquardt searches inside the parameter box advancing together, on the moments' residuals r_j = (sim_j - mom_j) /
 // s_j with forward-difference Jacobians — part of libsmmhip (included by smmhip.hip inside its anonymous namespace behind smm_optsimplex.hpp,
-// whose clip, scratch accessors and list compaction it uses; gfx950 device code; hiprtc never sees it).  Host side: smm_optlm_host.hpp;
+// whose clip it uses; scratch view, evaluation tile and list compaction: smm_evalscratch.hpp; gfx950 device code; hiprtc never sees it).  Host side: smm_optlm_host.hpp;
 // contract: include/smmhip.h (smm_opt_lm).  Every state kernel takes one wave (a workgroup of 64) per search, a lane per parameter
 // (np <= 64); every sum of the contract runs in ascending index inside one lane, nothing is reduced across lanes but maxima and ballots.
 // The factorisation and the substitutions are moment_chol's and moment_subst's (smm_moments.hpp).  Every operation is rounded on its own
@@ -13,9 +13,9 @@
 #pragma once
 
 // the results, [.][K] with the search the fastest index (search s = s0 + b) — x, F, lambda and the counters of a running search live in
-// them —, the state of one batch of nb searches that is no result, and one launch's scratch in the layouts the evaluation kernels fix
+// them —, the state of one batch of nb searches that is no result, and one launch's scratch (smm_evalscratch.hpp)
 struct LmArgs {
-    int K, nb, s0, user, max_iter, max_tries;
+    int K, nb, s0, max_iter, max_tries;
     double fd_step, lambda0, lambda_up, lambda_down, xtol, ftol, gtol;
     double* r;               // [nb][nm]     the residuals at x
     double* A;               // [nb][np][np] J'J with the active set applied, the lower triangle
@@ -24,9 +24,7 @@ struct LmArgs {
     int32_t* piv;            // [nb] the current try failed at a pivot: its evaluation pads the launch
     int32_t* f_try;          // [nb] the search makes (another) try
     int32_t* f_go;           // [nb] the search goes on into the next iteration
-    double* s_cand;          // trial points [np][n] (user: [n][np]); a user objective's Jacobian points [n x np][np]
-    double* s_value;
-    double* s_simM;
+    EvalScratch E;           // the candidates: one trial point per search, or a user objective's Jacobian points [n x np][np]
     double* best;            // [np][K]
     double* value;           // [K]
     double* sim_moments;     // [nm][K]
@@ -68,7 +66,7 @@ __global__ __launch_bounds__(64) void k_lm_init(const KParams P, const LmArgs A,
         A.best[(size_t)lane * K + s] = x;
         A.grad[(size_t)lane * K + s] = nan;
         A.active[(size_t)lane * K + s] = 0;
-        A.s_cand[A.user ? (size_t)b * N + lane : (size_t)lane * A.nb + b] = x;
+        A.E.put_cand((size_t)A.nb, (size_t)b, lane, x);
         if (A.jac)
             for (int j = 0; j < nm; ++j) A.jac[((size_t)j * N + lane) * K + s] = nan;
     }
@@ -84,7 +82,7 @@ __device__ inline bool lm_take_residuals(const KParams& P, const LmArgs& A, cons
     const int nm = P.nm;
     bool fin = true;
     for (int j = lane; j < nm; j += 64) {
-        const double rj = lm_residual(A.s_simM[A.user ? i * (size_t)nm + j : (size_t)j * n + i], P.mom[j], P.w[j]);
+        const double rj = lm_residual(A.E.mom(n, i, j), P.mom[j], P.w[j]);
         res[j] = rj;
         fin = fin && lm_finite(rj);
     }
@@ -103,9 +101,9 @@ __device__ inline void lm_file(const KParams& P, const LmArgs& A, const int lane
     const size_t s = (size_t)A.s0 + b, K = (size_t)A.K;
     for (int j = lane; j < nm; j += 64) {
         A.r[(size_t)b * nm + j] = res[j];
-        A.sim_moments[(size_t)j * K + s] = A.s_simM[A.user ? i * (size_t)nm + j : (size_t)j * n + i];
+        A.sim_moments[(size_t)j * K + s] = A.E.mom(n, i, j);
     }
-    if (lane == 0) { A.value[s] = A.s_value[i]; A.ssr[s] = F; }
+    if (lane == 0) { A.value[s] = A.E.value_of(i); A.ssr[s] = F; }
 }
 
 // the start's evaluation: a residual that is not finite stops the search with status 2
@@ -132,50 +130,17 @@ __global__ __launch_bounds__(256) void k_lm_candidates(const KParams P, const Lm
     const int j = (int)(t % (size_t)np), k = (int)(i % (size_t)np);
     const size_t at = (size_t)j * A.K + (size_t)A.s0 + list[i / (size_t)np];
     const double x = A.best[at];
-    A.s_cand[A.user ? i * (size_t)np + j : (size_t)j * n + i] = j == k ? lm_shift(x, P.lb[j], P.ub[j], A.fd_step) : x;
+    A.E.put_cand(n, i, j, j == k ? lm_shift(x, P.lb[j], P.ub[j], A.fd_step) : x);
 }
 
-// k_eval_slice's mould (smm_optslices.hpp) on the Jacobian's points, which are never written: the tile's theta comes from the search's x
-// and the one shifted coordinate.  Evaluation i = a * np + k of n -> value [n], simM [nm][n], status [n]
+// eval_tile on the Jacobian's points, which are never written: the tile's theta comes from the search's x and the one shifted coordinate.
+// Evaluation i = a * np + k of n -> value [n], simM [nm][n], status [n]
 template <int KIND, int CT>
 __global__ __launch_bounds__(WG, 4) void k_eval_lm(const KParams P, const LmArgs A, const int32_t* __restrict__ list, const int n, int8_t* __restrict__ status) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    TileSmem S;
-    S.carve(smem, CT, P.np, P.nm, P.RW, P.HW, P.RBW, KIND != 0);
-    const int tid = threadIdx.x;
-    const int i = blockIdx.x * CT + tid;
-    const bool chain_lane = (tid < CT) && (i < n);
-    double za[ZU];
-    ZBuf zb;
-    if constexpr (KIND == 1) { zb.init(P, tid); sim_load_chunk(zb, P, 0, 0, za); }
-    if (tid >= 64 && tid < 128)
-        for (int m = tid - 64; m < P.nm; m += 64) { S.mom[m] = P.mom[m]; S.w[m] = P.w[m]; }
-    for (int e = tid; e < CT * P.np; e += WG) {
-        const int cl = e / P.np, j = e - cl * P.np, ie = blockIdx.x * CT + cl;
-        double x = 0.0;
-        if (ie < n) {
-            x = A.best[(size_t)j * A.K + (size_t)A.s0 + list[ie / P.np]];
-            if (j == ie % P.np) x = lm_shift(x, P.lb[j], P.ub[j], A.fd_step);
-        }
-        S.theta[e] = x;
-    }
-    __syncthreads();
-    if constexpr (KIND == 1) {
-        simulate_tile<CT>(P, zb, S.theta, S.part, tid, za);
-        __syncthreads();
-    } else if constexpr (KIND == 2) {
-        dense_tile<CT>(P, S.theta, S.part, tid);
-        __syncthreads();
-    }
-    if (chain_lane) {
-        double v;
-        int st;
-        double* sm = S.h + tid * P.HW;
-        finish_objective<CT>(P, S.theta + tid * P.np, S.part, S.mom, S.w, tid, sm, v, st);
-        A.s_value[i] = v;
-        status[i] = (int8_t)st;
-        for (int m = 0; m < P.nm; ++m) A.s_simM[(size_t)m * n + i] = sm[m];
-    }
+    eval_tile_of<KIND, CT>(P, n, [&](const int ie, const int j) {
+        const double x = A.best[(size_t)j * A.K + (size_t)A.s0 + list[ie / P.np]];
+        return j == ie % P.np ? lm_shift(x, P.lb[j], P.ub[j], A.fd_step) : x;
+    }, A.E, status);
 }
 
 // The normal equations of running search a from its np Jacobian evaluations a * np + k of n: J, g, A, the active set and the stops that
@@ -199,7 +164,7 @@ __global__ __launch_bounds__(64) void k_lm_normal(const KParams P, const LmArgs 
         const double d = y - x;
         const size_t i = (size_t)a * N + k;
         for (int j = 0; j < nm; ++j) {
-            const double rk = lm_residual(A.s_simM[A.user ? i * (size_t)nm + j : (size_t)j * n + i], P.mom[j], P.w[j]);
+            const double rk = lm_residual(A.E.mom(n, i, j), P.mom[j], P.w[j]);
             const double diff = rk - r[j];
             const double Jjk = diff / d;
             J[(size_t)j * N + k] = Jjk;
@@ -285,7 +250,7 @@ __global__ __launch_bounds__(64) void k_lm_step(const KParams P, const LmArgs A,
     if (k < N) {
         const double xn = padded ? x : sx_clip(x + delta[k], P.lb[k], P.ub[k]);
         A.xnew[(size_t)b * N + k] = xn;
-        A.s_cand[A.user ? (size_t)a * N + k : (size_t)k * n + a] = xn;
+        A.E.put_cand(n, (size_t)a, k, xn);
     }
     if (lane == 0) A.piv[b] = trying && bad != 0 ? 1 : 0;
 }

@@ -1,5 +1,5 @@
-// the host side of smm_opt_lm (kernels: smm_optlm.hpp) — part of libsmmhip (included once by smmhip.hip, behind smm_opt_simplex' host side; the
-// scratch cap and its seam are smm_opt_slices'; hiprtc never sees it).  The searches go in batches whose state and launch scratch stay under
+// the host side of smm_opt_lm (kernels: smm_optlm.hpp; the estimators' frame: smm_estimate_host.hpp) — part of libsmmhip (included once by
+// smmhip.hip, behind smm_opt_simplex' host side; hiprtc never sees it).  The searches go in batches whose state and launch scratch stay under
 // the cap; a batch runs to its end before the next starts.  One lock-step iteration of a batch: the Jacobian's np points of every running
 // search in ONE evaluation launch (the built-in objectives: k_eval_lm, the points never written; a user objective: k_lm_candidates and its
 // own kernel) -> k_lm_normal -> rounds of tries, the first over all running searches (those that stopped at their normal equations pad it),
@@ -15,13 +15,6 @@ namespace {
 size_t lm_bytes_per_search(const KParams& P, bool user) {
     const size_t np = P.np, nm = P.nm;
     return np * ((nm + 1) * 8 + 4) + (user ? np * np : np) * 8 + (nm + np * np + np) * 8 + 32;
-}
-
-struct LmKernel { const void* fn; int ct; };
-LmKernel lm_kernel(const Ctx* c) {
-    if (is_sim(c->obj)) return {(const void*)k_eval_lm<1, 8>, 8};
-    if (c->obj == SMM_OBJ_DENSE) return {(const void*)k_eval_lm<2, 16>, 16};
-    return {(const void*)k_eval_lm<0, 8>, 8};
 }
 
 struct LmBufs {
@@ -43,12 +36,7 @@ extern "C" {
 int smm_opt_lm(void* ctx, const double* starts, int32_t K, double fd_step, double lambda0, double lambda_up, double lambda_down, double xtol,
                double ftol, double gtol, int32_t max_iter, int32_t max_tries, smm_opt_lm_t* out) {
     return api_call(ctx, true, [&](Ctx* c) -> int {
-        // settled and finished, and a hard error nobody has been told of reported once, as smm_opt_slices does (nothing runs then)
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        (void)check_device_error(c);
-        if (c->failed && !c->failed_told) { c->failed_told = true; return c->failed; }
+        if (const int rc = estimate_enter(c)) return rc;
         const KParams& P = c->P;
         if (!starts) return fail(c, SMM_ERR_INVALID_ARG, "smm_opt_lm: starts is NULL");
         if (K < 1) return fail(c, SMM_ERR_INVALID_ARG, "smm_opt_lm: K < 1");
@@ -65,46 +53,26 @@ int smm_opt_lm(void* ctx, const double* starts, int32_t K, double fd_step, doubl
         static_assert(MAX_DIM <= 64, "the state kernels take a lane per parameter");
         const size_t Ks = (size_t)K, np = P.np, nm = P.nm;
         const int N = P.np;
-        std::vector<double> lb(np), ub(np);
-        HIPCHK(hipMemcpy(lb.data(), P.lb, np * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ub.data(), P.ub, np * 8, hipMemcpyDeviceToHost));
-        for (size_t s = 0; s < Ks; ++s)
-            for (size_t k = 0; k < np; ++k) {
-                const double x = starts[k * Ks + s];
-                if (!(x >= lb[k] && x <= ub[k])) {
-                    char b[192];
-                    snprintf(b, sizeof b, "smm_opt_lm: the start of search %d, parameter %d is %g: outside [%g, %g]", (int)s + 1, (int)k + 1, x, lb[k], ub[k]);
-                    return fail(c, SMM_ERR_INVALID_ARG, b);
-                }
-            }
+        if (const int rc = starts_in_box(c, "smm_opt_lm", "search", 1, starts, Ks)) return rc;
         const bool user = c->obj == SMM_OBJ_USER;
-        const int nb_max = (int)std::min<size_t>(Ks, std::max<size_t>(1, opt_scratch_cap(c) / lm_bytes_per_search(P, user)));
+        const int nb_max = batch_size(c, Ks, lm_bytes_per_search(P, user));
         LmBufs B(P, Ks, (size_t)nb_max, user, out && out->jac);
         LmArgs A{};
-        A.K = K; A.user = user ? 1 : 0; A.max_iter = max_iter; A.max_tries = max_tries;
+        A.K = K; A.max_iter = max_iter; A.max_tries = max_tries;
         A.fd_step = fd_step; A.lambda0 = lambda0; A.lambda_up = lambda_up; A.lambda_down = lambda_down; A.xtol = xtol; A.ftol = ftol; A.gtol = gtol;
         A.r = B.r.p; A.A = B.A.p; A.xnew = B.xnew.p; A.itry = B.itry.p; A.piv = B.piv.p; A.f_try = B.f_try.p; A.f_go = B.f_go.p;
-        A.s_cand = B.s_cand.p; A.s_value = B.s_value.p; A.s_simM = B.s_simM.p;
+        A.E = eval_scratch(c, B.s_cand.p, B.s_value.p, B.s_simM.p, B.s_status.p);
         A.best = B.best.p; A.value = B.value.p; A.sim_moments = B.sim_moments.p; A.ssr = B.ssr.p; A.grad = B.grad.p;
         A.jac = out && out->jac ? B.jac.p : nullptr;
         A.lambda = B.lambda.p; A.step = B.step.p; A.dF = B.dF.p; A.active = B.active.p; A.iterations = B.iterations.p; A.tries = B.tries.p;
         A.n_eval = B.n_eval.p; A.status = B.status.p;
         HIPCHK(hipMemcpyAsync(B.starts.p, starts, Ks * np * 8, hipMemcpyHostToDevice, c->stream));
-        const LmKernel E = lm_kernel(c);
-        if (!user) HIPCHK(hipFuncSetAttribute(E.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CU));
         const size_t lds_normal = (nm * np + nm) * 8, lds_step = (np * (np + 1) + np + 1) * 8;
         int32_t* run[2] = {B.run0.p, B.run1.p};
         int32_t* trying[2] = {B.trying0.p, B.trying1.p};
         const dim3 wave(64);
         // the entries of `list` (nullptr: the batch) whose flag is set into `to`; their number comes back: the one read of a phase
-        auto compact = [&](const int32_t* list, int n_in, const int32_t* flag, int32_t* to) -> int {
-            int32_t n_to = 0;
-            hipLaunchKernelGGL(k_sx_compact, dim3(1), dim3(SX_CP_WG), 0, c->stream, list, n_in, flag, to, B.count.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(&n_to, B.count.p, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            return (int)n_to;
-        };
+        auto compact = [&](const int32_t* list, int n_in, const int32_t* flag, int32_t* to) { return compact_count(c, list, n_in, flag, to, B.count.p); };
         // the np Jacobian points of each of the n_run searches of `list`
         auto eval_jacobian = [&](const int32_t* list, int n_run) {
             const int n = n_run * N;
@@ -112,19 +80,19 @@ int smm_opt_lm(void* ctx, const double* starts, int32_t K, double fd_step, doubl
                 const size_t work = (size_t)n * np;
                 hipLaunchKernelGGL(k_lm_candidates, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, c->stream, P, A, list, (size_t)n);
                 HIPCHK(hipGetLastError());
-                launch_eval_dev(c, A.s_cand, n, A.s_value, A.s_simM, B.s_status.p);
+                launch_eval_dev(c, A.E, n);
                 return;
             }
-            int8_t* st = (int8_t*)B.s_status.p;
+            int8_t* st = (int8_t*)A.E.status;
             void* args[] = {(void*)&P, (void*)&A, (void*)&list, (void*)&n, (void*)&st};
-            HIPCHK(hipLaunchKernel(E.fn, dim3((unsigned)((n + E.ct - 1) / E.ct)), dim3(WG), args, tile_smem_base(c, E.ct), c->stream));
+            launch_eval_tiles(c, EF_LM, n, args);
         };
         for (int s0 = 0; s0 < K; s0 += nb_max) {
             const int nb = std::min(nb_max, K - s0);
             A.s0 = s0; A.nb = nb;
             hipLaunchKernelGGL(k_lm_init, dim3((unsigned)nb), wave, 0, c->stream, P, A, (const double*)B.starts.p);
             HIPCHK(hipGetLastError());
-            launch_eval_dev(c, A.s_cand, nb, A.s_value, A.s_simM, B.s_status.p);
+            launch_eval_dev(c, A.E, nb);
             hipLaunchKernelGGL(k_lm_start, dim3((unsigned)nb), wave, 0, c->stream, P, A);
             HIPCHK(hipGetLastError());
             int n_run = compact(nullptr, nb, A.f_go, run[0]);
@@ -139,7 +107,7 @@ int smm_opt_lm(void* ctx, const double* starts, int32_t K, double fd_step, doubl
                     const size_t n = (size_t)n_try;
                     hipLaunchKernelGGL(k_lm_step, dim3((unsigned)n_try), wave, lds_step, c->stream, P, A, tl, n);
                     HIPCHK(hipGetLastError());
-                    launch_eval_dev(c, A.s_cand, n_try, A.s_value, A.s_simM, B.s_status.p);
+                    launch_eval_dev(c, A.E, n_try);
                     hipLaunchKernelGGL(k_lm_judge, dim3((unsigned)n_try), wave, 0, c->stream, P, A, tl, n);
                     HIPCHK(hipGetLastError());
                     int32_t* to = trying[round & 1];
@@ -151,12 +119,12 @@ int smm_opt_lm(void* ctx, const double* starts, int32_t K, double fd_step, doubl
         }
         HIPCHK(hipStreamSynchronize(c->stream));
         if (out) {
-            auto down = [&](void* dst, const void* src, size_t bytes) { if (dst) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream)); };
-            down(out->best, B.best.p, Ks * np * 8); down(out->value, B.value.p, Ks * 8); down(out->sim_moments, B.sim_moments.p, Ks * nm * 8);
-            down(out->ssr, B.ssr.p, Ks * 8); down(out->grad, B.grad.p, Ks * np * 8); down(out->jac, B.jac.p, Ks * nm * np * 8);
-            down(out->lambda, B.lambda.p, Ks * 8); down(out->step, B.step.p, Ks * 8); down(out->dF, B.dF.p, Ks * 8);
-            down(out->active, B.active.p, Ks * np * 4); down(out->iterations, B.iterations.p, Ks * 4); down(out->tries, B.tries.p, Ks * 4);
-            down(out->n_eval, B.n_eval.p, Ks * 4); down(out->status, B.status.p, Ks * 4);
+            const Download down{c};
+            down(out->best, B.best.p, Ks * np); down(out->value, B.value.p, Ks); down(out->sim_moments, B.sim_moments.p, Ks * nm);
+            down(out->ssr, B.ssr.p, Ks); down(out->grad, B.grad.p, Ks * np); down(out->jac, B.jac.p, Ks * nm * np);
+            down(out->lambda, B.lambda.p, Ks); down(out->step, B.step.p, Ks); down(out->dF, B.dF.p, Ks);
+            down(out->active, B.active.p, Ks * np); down(out->iterations, B.iterations.p, Ks); down(out->tries, B.tries.p, Ks);
+            down(out->n_eval, B.n_eval.p, Ks); down(out->status, B.status.p, Ks);
             std::vector<int32_t> ne(Ks);
             HIPCHK(hipMemcpyAsync(ne.data(), B.n_eval.p, Ks * 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));

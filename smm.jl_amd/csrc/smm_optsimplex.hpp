@@ -3,15 +3,14 @@
 // sees it).  Host side: smm_optsimplex_host.hpp; contract: include/smmhip.h (smm_opt_simplex).  Every state kernel takes one wave (a
 // workgroup of 64) per search, a lane per coordinate (np <= 64), so the centroid's left-to-right sum is in-lane.  A simplex is never moved:
 // the N + 1 <= 65 values are ranked by counting and the permutation position -> row is what the sort rewrites.  Lists of searches (running,
-// second point, shrinking) are compacted in ascending order by one workgroup (k_sx_compact).  Every operation is rounded on its own
-// (-ffp-contract=off).
+// second point, shrinking) are compacted in ascending order by one workgroup (k_compact, smm_evalscratch.hpp).  Every operation is rounded
+// on its own (-ffp-contract=off).
 #pragma once
 
-// the state of one batch of nb searches, the search b of the batch the slowest index, one launch's scratch in the layouts the evaluation kernels
-// fix (the built-in objectives read candidates [np][n] and write simM [nm][n]; a user objective's kernel reads [n][np] and writes [n][nm]),
-// and the results, [.][K] with the search the fastest index (search s = s0 + b)
+// the state of one batch of nb searches, the search b of the batch the slowest index, one launch's scratch (smm_evalscratch.hpp), and the
+// results, [.][K] with the search the fastest index (search s = s0 + b)
 struct SxArgs {
-    int K, nb, s0, user, max_iter;
+    int K, nb, s0, max_iter;
     double xatol, fatol;
     double step;
     double c_r, rho;         // (1 + rho), rho
@@ -29,9 +28,7 @@ struct SxArgs {
     double* fxr;             // [nb]
     int32_t* kind;           // [nb] the second point this iteration needs: 0 none, 1 expansion, 2 outside, 3 inside contraction
     int32_t* flag;           // [nb] what the next compaction keeps
-    double* s_cand;
-    double* s_value;         // [n]
-    double* s_simM;
+    EvalScratch E;
     double* best;            // [np][K]
     double* value;           // [K]
     double* sim_moments;     // [nm][K]
@@ -49,12 +46,6 @@ __device__ inline double sx_clip(const double x, const double lb, const double u
     const double y = x < lb ? lb : x;   // (np.clip: minimum(maximum(x, lb), ub))
     return y > ub ? ub : y;
 }
-__device__ inline void sx_put_cand(const SxArgs& A, const int np, const size_t n, const size_t i, const int k, const double x) {
-    A.s_cand[A.user ? i * (size_t)np + k : (size_t)k * n + i] = x;
-}
-__device__ inline double sx_get_mom(const SxArgs& A, const int nm, const size_t n, const size_t i, const int f) {
-    return A.s_simM[A.user ? i * (size_t)nm + f : (size_t)f * n + i];
-}
 // ascending, NaN last, +inf just before NaN
 __device__ inline bool sx_less(const double a, const double b) {
     if (a != a) return false;
@@ -66,7 +57,7 @@ __device__ inline void sx_take_scratch(const KParams& P, const SxArgs& A, const 
     const int N = P.np, nm = P.nm;
     const int row = A.perm[(size_t)b * (N + 1) + N];
     if (lane < N) A.sim[((size_t)b * (N + 1) + row) * N + lane] = x;
-    for (int m = lane; m < nm; m += 64) A.mom[((size_t)b * (N + 1) + row) * nm + m] = sx_get_mom(A, nm, n, i, m);
+    for (int m = lane; m < nm; m += 64) A.mom[((size_t)b * (N + 1) + row) * nm + m] = A.E.mom(n, i, m);
     if (lane == 0) A.fsim[(size_t)b * (N + 1) + N] = f;
 }
 
@@ -105,7 +96,7 @@ __global__ __launch_bounds__(64) void k_sx_vertex(const KParams P, const SxArgs 
     const int lane = (int)threadIdx.x, a = (int)blockIdx.x, N = P.np;
     const int b = list ? list[a] : a;
     const size_t at = (size_t)b * (N + 1);
-    if (lane < N) sx_put_cand(A, N, n, (size_t)a, lane, A.sim[(at + A.perm[at + pos]) * N + lane]);
+    if (lane < N) A.E.put_cand(n, (size_t)a, lane, A.sim[(at + A.perm[at + pos]) * N + lane]);
 }
 // ... and its value and moments, as evaluated, into the state
 __global__ __launch_bounds__(64) void k_sx_store(const KParams P, const SxArgs A, const int32_t* __restrict__ list, const int pos, const size_t n) {
@@ -113,9 +104,9 @@ __global__ __launch_bounds__(64) void k_sx_store(const KParams P, const SxArgs A
     const int b = list ? list[a] : a;
     const size_t at = (size_t)b * (N + 1);
     const int row = A.perm[at + pos];
-    for (int m = lane; m < nm; m += 64) A.mom[(at + row) * nm + m] = sx_get_mom(A, nm, n, (size_t)a, m);
+    for (int m = lane; m < nm; m += 64) A.mom[(at + row) * nm + m] = A.E.mom(n, (size_t)a, m);
     if (lane == 0) {
-        A.fsim[at + pos] = A.s_value[a];
+        A.fsim[at + pos] = A.E.value_of(a);
         A.n_eval[(size_t)A.s0 + b] += 1;
     }
 }
@@ -189,41 +180,6 @@ __global__ __launch_bounds__(64) void k_sx_sort(const KParams P, const SxArgs A,
     }
 }
 
-// The entries of list_in (nullptr: 0 .. n_in - 1) whose flag is set into list_out in ascending order, their number into n_out: one workgroup,
-// ballots and prefix counts, no atomics (k_os_cycle_end's scheme)
-constexpr int SX_CP_WG = 1024;
-__global__ __launch_bounds__(SX_CP_WG) void k_sx_compact(const int32_t* __restrict__ list_in, const int n_in, const int32_t* __restrict__ flag,
-                                                         int32_t* __restrict__ list_out, int32_t* __restrict__ n_out) {
-    __shared__ int wtot[SX_CP_WG / 64];
-    __shared__ int base;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) base = 0;
-    __syncthreads();
-    for (int a_first = 0; a_first < n_in; a_first += SX_CP_WG) {
-        const int a = a_first + tid;
-        bool keep = false;
-        int b = 0;
-        if (a < n_in) {
-            b = list_in ? list_in[a] : a;
-            keep = flag[b] != 0;
-        }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wtot[wave] = __popcll(m);
-        __syncthreads();
-        int before = base;
-        for (int w = 0; w < wave; ++w) before += wtot[w];
-        if (keep) list_out[before + __popcll(m & ((1ull << lane) - 1ull))] = b;
-        __syncthreads();
-        if (tid == 0) {
-            int tot = base;
-            for (int w = 0; w < SX_CP_WG / 64; ++w) tot += wtot[w];
-            base = tot;
-        }
-        __syncthreads();
-    }
-    if (tid == 0) *n_out = base;
-}
-
 // centroid of the N best vertices, added left to right, and the reflected point of running search a: evaluation a of n
 __global__ __launch_bounds__(64) void k_sx_reflect(const KParams P, const SxArgs A, const int32_t* __restrict__ list, const size_t n) {
     const int lane = (int)threadIdx.x, a = (int)blockIdx.x, N = P.np;
@@ -238,7 +194,7 @@ __global__ __launch_bounds__(64) void k_sx_reflect(const KParams P, const SxArgs
     const double xr = sx_clip(t1 - t2, P.lb[lane], P.ub[lane]);
     A.xbar[(size_t)b * N + lane] = xbar;
     A.xr[(size_t)b * N + lane] = xr;
-    sx_put_cand(A, N, n, (size_t)a, lane, xr);
+    A.E.put_cand(n, (size_t)a, lane, xr);
 }
 
 // scipy's comparisons on fxr, literally (a NaN fails every <): the reflected point is taken, or the search needs a second point (kind, flag)
@@ -246,13 +202,13 @@ __global__ __launch_bounds__(64) void k_sx_decide(const KParams P, const SxArgs 
     const int lane = (int)threadIdx.x, a = (int)blockIdx.x, N = P.np, nm = P.nm;
     const int b = list[a];
     const size_t s = (size_t)A.s0 + b, at = (size_t)b * (N + 1);
-    const double fxr = A.s_value[a], f0 = A.fsim[at], fn1 = A.fsim[at + N - 1], fN = A.fsim[at + N];
+    const double fxr = A.E.value_of(a), f0 = A.fsim[at], fn1 = A.fsim[at + N - 1], fN = A.fsim[at + N];
     int kind;
     if (fxr < f0) kind = 1;
     else if (fxr < fn1) kind = 0;
     else if (fxr < fN) kind = 2;
     else kind = 3;
-    for (int m = lane; m < nm; m += 64) A.mr[(size_t)b * nm + m] = sx_get_mom(A, nm, n, (size_t)a, m);
+    for (int m = lane; m < nm; m += 64) A.mr[(size_t)b * nm + m] = A.E.mom(n, (size_t)a, m);
     if (kind == 0) sx_take_scratch(P, A, b, lane, lane < N ? A.xr[(size_t)b * N + lane] : 0.0, fxr, n, (size_t)a);
     if (lane == 0) {
         A.fxr[b] = fxr;
@@ -277,7 +233,7 @@ __global__ __launch_bounds__(64) void k_sx_second(const KParams P, const SxArgs 
     else { t1 = A.c_i * xbar; t2 = A.psi * xn; x = t1 + t2; }
     x = sx_clip(x, P.lb[lane], P.ub[lane]);
     A.xbar[(size_t)b * N + lane] = x;   // (the centroid has served: the second point takes its place until k_sx_accept)
-    sx_put_cand(A, N, n, (size_t)a, lane, x);
+    A.E.put_cand(n, (size_t)a, lane, x);
 }
 
 // the second point's value against fxr (expansion: fxe < fxr; outside contraction: fxc <= fxr) or the worst vertex's (inside: fxcc < fsim[N]):
@@ -287,7 +243,7 @@ __global__ __launch_bounds__(64) void k_sx_accept(const KParams P, const SxArgs 
     const int b = list[a];
     const size_t s = (size_t)A.s0 + b, at = (size_t)b * (N + 1), K = (size_t)A.K;
     const int kind = A.kind[b];
-    const double f2 = A.s_value[a], fxr = A.fxr[b], fN = A.fsim[at + N];
+    const double f2 = A.E.value_of(a), fxr = A.fxr[b], fN = A.fsim[at + N];
     const bool take2 = kind == 1 ? f2 < fxr : kind == 2 ? f2 <= fxr : f2 < fN;
     const bool shrink = !take2 && kind != 1;
     int move;

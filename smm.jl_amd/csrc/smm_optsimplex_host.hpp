@@ -1,5 +1,5 @@
-// the host side of smm_opt_simplex (kernels: smm_optsimplex.hpp) — part of libsmmhip (included once by smmhip.hip, behind smm_opt_slices' host
-// side, whose scratch cap and seam it shares; hiprtc never sees it).  The searches go in batches whose state and launch scratch stay under the
+// the host side of smm_opt_simplex (kernels: smm_optsimplex.hpp; the estimators' frame: smm_estimate_host.hpp) — part of libsmmhip (included
+// once by smmhip.hip, behind smm_opt_slices' host side; hiprtc never sees it).  The searches go in batches whose state and launch scratch stay under the
 // cap; a batch runs to its end before the next starts.  One lock-step iteration of a batch: k_sx_reflect -> evaluation of the running
 // searches' xr -> k_sx_decide -> the searches that need a second point compacted -> k_sx_second -> evaluation -> k_sx_accept -> the searches
 // that shrink compacted -> k_sx_shrink -> their vertices 1 .. N evaluated, one launch a vertex -> k_sx_sort -> the searches that go on
@@ -37,12 +37,7 @@ extern "C" {
 int smm_opt_simplex(void* ctx, const double* starts, int32_t K, double step, int32_t adaptive, double xatol, double fatol, int32_t max_iter,
                     smm_opt_simplex_t* out) {
     return api_call(ctx, true, [&](Ctx* c) -> int {
-        // settled and finished, and a hard error nobody has been told of reported once, as smm_opt_slices does (nothing runs then)
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        (void)check_device_error(c);
-        if (c->failed && !c->failed_told) { c->failed_told = true; return c->failed; }
+        if (const int rc = estimate_enter(c)) return rc;
         const KParams& P = c->P;
         if (!starts) return fail(c, SMM_ERR_INVALID_ARG, "smm_opt_simplex: starts is NULL");
         if (K < 1) return fail(c, SMM_ERR_INVALID_ARG, "smm_opt_simplex: K < 1");
@@ -54,22 +49,11 @@ int smm_opt_simplex(void* ctx, const double* starts, int32_t K, double step, int
         static_assert(MAX_DIM <= 64, "the state kernels take a lane per coordinate");
         const size_t Ks = (size_t)K, np = P.np, nm = P.nm, V = np + 1;
         const int N = P.np;
-        std::vector<double> lb(np), ub(np);
-        HIPCHK(hipMemcpy(lb.data(), P.lb, np * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ub.data(), P.ub, np * 8, hipMemcpyDeviceToHost));
-        for (size_t s = 0; s < Ks; ++s)
-            for (size_t k = 0; k < np; ++k) {
-                const double x = starts[k * Ks + s];
-                if (!(x >= lb[k] && x <= ub[k])) {
-                    char b[192];
-                    snprintf(b, sizeof b, "smm_opt_simplex: the start of search %d, parameter %d is %g: outside [%g, %g]", (int)s + 1, (int)k + 1, x, lb[k], ub[k]);
-                    return fail(c, SMM_ERR_INVALID_ARG, b);
-                }
-            }
-        const int nb_max = (int)std::min<size_t>(Ks, std::max<size_t>(1, opt_scratch_cap(c) / simplex_bytes_per_search(P)));
+        if (const int rc = starts_in_box(c, "smm_opt_simplex", "search", 1, starts, Ks)) return rc;
+        const int nb_max = batch_size(c, Ks, simplex_bytes_per_search(P));
         SimplexBufs B(P, Ks, (size_t)nb_max);
         SxArgs A{};
-        A.K = K; A.user = c->obj == SMM_OBJ_USER ? 1 : 0; A.max_iter = max_iter; A.xatol = xatol; A.fatol = fatol; A.step = step;
+        A.K = K; A.max_iter = max_iter; A.xatol = xatol; A.fatol = fatol; A.step = step;
         // the coefficients and their products, once, in double, as Python computes them
         const double dim = (double)N;
         const double rho = 1.0, chi = adaptive ? 1.0 + 2.0 / dim : 2.0, psi = adaptive ? 0.75 - 1.0 / (2.0 * dim) : 0.5, sigma = adaptive ? 1.0 - 1.0 / dim : 0.5;
@@ -79,22 +63,15 @@ int smm_opt_simplex(void* ctx, const double* starts, int32_t K, double step, int
         A.psi = psi; A.c_i = 1.0 - psi;
         A.sigma = sigma;
         A.sim = B.sim.p; A.mom = B.mom.p; A.fsim = B.fsim.p; A.perm = B.perm.p; A.xbar = B.xbar.p; A.xr = B.xr.p; A.mr = B.mr.p; A.fxr = B.fxr.p;
-        A.kind = B.kind.p; A.flag = B.flag.p; A.s_cand = B.s_cand.p; A.s_value = B.s_value.p; A.s_simM = B.s_simM.p;
+        A.kind = B.kind.p; A.flag = B.flag.p; A.E = eval_scratch(c, B.s_cand.p, B.s_value.p, B.s_simM.p, B.s_status.p);
         A.best = B.best.p; A.value = B.value.p; A.sim_moments = B.sim_moments.p; A.simplex = B.simplex.p; A.simplex_value = B.simplex_value.p;
         A.size_x = B.size_x.p; A.size_f = B.size_f.p; A.iterations = B.iterations.p; A.status = B.status.p; A.moves = B.moves.p; A.n_eval = B.n_eval.p;
         HIPCHK(hipMemcpyAsync(B.starts.p, starts, Ks * np * 8, hipMemcpyHostToDevice, c->stream));
         int32_t* run[2] = {B.run0.p, B.run1.p};
         const dim3 wave(64);
         // the flagged entries of `list` (nullptr: the batch) into `to`; their number comes back: the one read of a phase
-        auto compact = [&](const int32_t* list, int n_in, int32_t* to) -> int {
-            int32_t n_to = 0;
-            hipLaunchKernelGGL(k_sx_compact, dim3(1), dim3(SX_CP_WG), 0, c->stream, list, n_in, (const int32_t*)A.flag, to, B.count.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(&n_to, B.count.p, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            return (int)n_to;
-        };
-        auto eval = [&](size_t n) { launch_eval_dev(c, A.s_cand, (int)n, A.s_value, A.s_simM, B.s_status.p); };
+        auto compact = [&](const int32_t* list, int n_in, int32_t* to) { return compact_count(c, list, n_in, A.flag, to, B.count.p); };
+        auto eval = [&](size_t n) { launch_eval_dev(c, A.E, (int)n); };
         int64_t evaluated = 0;
         // the vertices at positions p0 .. p1 of the listed searches (nullptr: the batch), a launch of n evaluations per position, filed as evaluated
         auto evaluate_vertices = [&](const int32_t* list, int n, int p0, int p1) {
@@ -150,12 +127,12 @@ int smm_opt_simplex(void* ctx, const double* starts, int32_t K, double step, int
         }
         HIPCHK(hipStreamSynchronize(c->stream));
         if (out) {
-            auto down = [&](void* dst, const void* src, size_t bytes) { if (dst) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream)); };
-            down(out->best, B.best.p, Ks * np * 8); down(out->value, B.value.p, Ks * 8); down(out->sim_moments, B.sim_moments.p, Ks * nm * 8);
-            down(out->simplex, B.simplex.p, Ks * V * np * 8); down(out->simplex_value, B.simplex_value.p, Ks * V * 8);
-            down(out->size_x, B.size_x.p, Ks * 8); down(out->size_f, B.size_f.p, Ks * 8);
-            down(out->iterations, B.iterations.p, Ks * 4); down(out->status, B.status.p, Ks * 4); down(out->moves, B.moves.p, Ks * 5 * 4);
-            down(out->n_eval, B.n_eval.p, Ks * 4);
+            const Download down{c};
+            down(out->best, B.best.p, Ks * np); down(out->value, B.value.p, Ks); down(out->sim_moments, B.sim_moments.p, Ks * nm);
+            down(out->simplex, B.simplex.p, Ks * V * np); down(out->simplex_value, B.simplex_value.p, Ks * V);
+            down(out->size_x, B.size_x.p, Ks); down(out->size_f, B.size_f.p, Ks);
+            down(out->iterations, B.iterations.p, Ks); down(out->status, B.status.p, Ks); down(out->moves, B.moves.p, Ks * 5);
+            down(out->n_eval, B.n_eval.p, Ks);
             HIPCHK(hipStreamSynchronize(c->stream));
             out->evaluated = evaluated;
         }

@@ -5,10 +5,9 @@
 // ends in k_os_cycle_end, which drops the searches that stopped.  Every operation is rounded on its own (-ffp-contract=off).
 #pragma once
 
-// the searches' state, [.][K] with the search the fastest index, and one step's scratch in the layouts the evaluation kernels fix (the
-// built-in objectives write simM [nm][n] and status int8; a user objective's kernel reads theta [n][np] and writes simM [n][nm], status int)
+// the searches' state, [.][K] with the search the fastest index, and one step's scratch (smm_evalscratch.hpp)
 struct OsArgs {
-    int K, G, user, max_cycles;
+    int K, G, max_cycles;
     double tol, update;      // update NaN: the ranges never shrink
     double* bestp;           // [np][K] the point each search stands at
     double* lo;              // [np][K] the search ranges
@@ -20,9 +19,7 @@ struct OsArgs {
     double* cycle_value;     // [max_cycles][K]
     int32_t* cycles;         // [K]
     int32_t* converged;      // [K]
-    double* s_cand;          // the step's candidates, where they are materialised: [n][np] (user) or [np][n]
-    double* s_value;         // [n]
-    double* s_simM;
+    EvalScratch E;           // (the step's candidates only where they are materialised)
 };
 
 // numpy's linspace(lo, hi, G)[g], G >= 2: step = (hi - lo) / (G - 1), x_g = g * step + lo, the last point hi itself; a step that rounds to
@@ -64,51 +61,18 @@ __global__ __launch_bounds__(256) void k_os_candidates(const KParams P, const Os
     const int s = act[a0 + i / A.G], g = i % A.G;
     const size_t at = (size_t)j * A.K + s;
     const double x = j == k ? os_grid(A.lo[at], A.hi[at], A.G, g) : A.bestp[at];
-    A.s_cand[A.user ? (size_t)i * np + j : (size_t)j * n + i] = x;
+    A.E.put_cand((size_t)n, (size_t)i, j, x);
 }
 
-// k_eval_batch (smm_chain.hpp) on candidates that are never written: the tile's theta comes from the search's bestp column and the one
-// replaced coordinate.  Evaluation i of n -> value [n], simM [nm][n], status [n]
+// eval_tile on candidates that are never written: the tile's theta comes from the search's bestp column and the one replaced coordinate.
+// Evaluation i of n -> value [n], simM [nm][n], status [n]
 template <int KIND, int CT>
 __global__ __launch_bounds__(WG, 4) void k_eval_slice(const KParams P, const OsArgs A, const int32_t* __restrict__ act, const int k, const int a0, const int n,
                                                       int8_t* __restrict__ status) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    TileSmem S;
-    S.carve(smem, CT, P.np, P.nm, P.RW, P.HW, P.RBW, KIND != 0);
-    const int tid = threadIdx.x;
-    const int i = blockIdx.x * CT + tid;
-    const bool chain_lane = (tid < CT) && (i < n);
-    double za[ZU];
-    ZBuf zb;
-    if constexpr (KIND == 1) { zb.init(P, tid); sim_load_chunk(zb, P, 0, 0, za); }
-    if (tid >= 64 && tid < 128)
-        for (int m = tid - 64; m < P.nm; m += 64) { S.mom[m] = P.mom[m]; S.w[m] = P.w[m]; }
-    for (int e = tid; e < CT * P.np; e += WG) {   // (all lanes: np loads per chain, the searches of a tile side by side in every column)
-        const int cl = e / P.np, j = e - cl * P.np, ie = blockIdx.x * CT + cl;
-        double x = 0.0;
-        if (ie < n) {
-            const size_t at = (size_t)j * A.K + act[a0 + ie / A.G];
-            x = j == k ? os_grid(A.lo[at], A.hi[at], A.G, ie % A.G) : A.bestp[at];
-        }
-        S.theta[e] = x;
-    }
-    __syncthreads();
-    if constexpr (KIND == 1) {
-        simulate_tile<CT>(P, zb, S.theta, S.part, tid, za);
-        __syncthreads();
-    } else if constexpr (KIND == 2) {
-        dense_tile<CT>(P, S.theta, S.part, tid);
-        __syncthreads();
-    }
-    if (chain_lane) {
-        double v;
-        int st;
-        double* sm = S.h + tid * P.HW;
-        finish_objective<CT>(P, S.theta + tid * P.np, S.part, S.mom, S.w, tid, sm, v, st);
-        A.s_value[i] = v;
-        status[i] = (int8_t)st;
-        for (int m = 0; m < P.nm; ++m) A.s_simM[(size_t)m * n + i] = sm[m];
-    }
+    eval_tile_of<KIND, CT>(P, n, [&](const int ie, const int j) {
+        const size_t at = (size_t)j * A.K + act[a0 + ie / A.G];
+        return j == k ? os_grid(A.lo[at], A.hi[at], A.G, ie % A.G) : A.bestp[at];
+    }, A.E, status);
 }
 
 // One wave per active search of the batch: the grid point with the smallest finite value, ties to the lowest g, by a butterfly over the
@@ -125,7 +89,7 @@ __global__ __launch_bounds__(64 * OS_WPB) void k_os_select(const KParams P, cons
     double bv = INFINITY;
     int bg = NONE;
     for (int g = lane; g < G; g += 64) {
-        const double v = A.s_value[j0 + g];
+        const double v = A.E.value_of(j0 + g);
         if (v < bv && v > -INFINITY) { bv = v; bg = g; }   // (finite and strictly lower; ascending g: an equal value keeps the lower one)
     }
 #pragma unroll
@@ -140,7 +104,7 @@ __global__ __launch_bounds__(64 * OS_WPB) void k_os_select(const KParams P, cons
         return;
     }
     const size_t jw = j0 + (size_t)bg;
-    for (int f = lane; f < nm; f += 64) A.simM[(size_t)f * A.K + s] = A.s_simM[A.user ? jw * (size_t)nm + f : (size_t)f * n + jw];
+    for (int f = lane; f < nm; f += 64) A.simM[(size_t)f * A.K + s] = A.E.mom(n, jw, f);
     if (lane == 0) {
         const double old = A.bestp[at], x = os_grid(A.lo[at], A.hi[at], G, bg);
         A.bestp[at] = x;
@@ -151,17 +115,14 @@ __global__ __launch_bounds__(64 * OS_WPB) void k_os_select(const KParams P, cons
 
 // The end of cycle `cyc` (0-based) for the n_act searches of act_in, by one workgroup: the ranges shrink around bestp (update not NaN), delta =
 // sqrt(sum of the squared moves, left to right), the search stops converged at delta <= tol or unconverged after max_cycles cycles; then the
-// searches that go on into act_out in ascending order — ballots and prefix counts, no atomics — and their number into n_out.
-constexpr int OS_CE_WG = 1024;
-__global__ __launch_bounds__(OS_CE_WG) void k_os_cycle_end(const KParams P, const OsArgs A, const int32_t* __restrict__ act_in, const int n_act, const int cyc,
+// searches that go on into act_out in ascending order (compact_push, smm_evalscratch.hpp) and their number into n_out.
+__global__ __launch_bounds__(COMPACT_WG) void k_os_cycle_end(const KParams P, const OsArgs A, const int32_t* __restrict__ act_in, const int n_act, const int cyc,
                                                            int32_t* __restrict__ act_out, int32_t* __restrict__ n_out) {
-    __shared__ int wtot[OS_CE_WG / 64];
-    __shared__ int base;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, np = P.np;
+    __shared__ CompactLds L;
+    const int tid = (int)threadIdx.x, np = P.np;
     const size_t K = (size_t)A.K;
-    if (tid == 0) base = 0;
-    __syncthreads();
-    for (int a_first = 0; a_first < n_act; a_first += OS_CE_WG) {
+    compact_begin(L);
+    for (int a_first = 0; a_first < n_act; a_first += COMPACT_WG) {
         const int a = a_first + tid;
         bool keep = false;
         int s = 0;
@@ -189,19 +150,7 @@ __global__ __launch_bounds__(OS_CE_WG) void k_os_cycle_end(const KParams P, cons
             A.converged[s] = delta <= A.tol ? 1 : 0;
             keep = delta > A.tol && cyc + 1 < A.max_cycles;
         }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wtot[wave] = __popcll(m);
-        __syncthreads();
-        int before = base;
-        for (int w = 0; w < wave; ++w) before += wtot[w];
-        if (keep) act_out[before + __popcll(m & ((1ull << lane) - 1ull))] = s;
-        __syncthreads();
-        if (tid == 0) {
-            int tot = base;
-            for (int w = 0; w < OS_CE_WG / 64; ++w) tot += wtot[w];
-            base = tot;
-        }
-        __syncthreads();
+        compact_push(L, keep, s, act_out);
     }
-    if (tid == 0) *n_out = base;
+    if (tid == 0) *n_out = L.base;
 }

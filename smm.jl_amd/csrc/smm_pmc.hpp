@@ -10,8 +10,8 @@
 //                    particles' z once more by particle (kzT [i][NPC]) for the weight kernel.
 //   k_pmc_propose  : a lane per new particle: the parent by a binary search of the integer prefix, the normals of its Philox blocks through
 //                    LDS, the Cholesky step of smm_propose.hpp, the inside test.
-//   k_pmc_gather, k_pmc_scatter : the compacted list of inside particles into a launch's scratch in the layout the evaluation kernel fixes, and
-//                    its values back as distances.
+//   k_pmc_gather, k_pmc_scatter : the compacted list of inside particles into a launch's scratch (smm_evalscratch.hpp), and its values back
+//                    as distances.
 //   k_pmc_kernel   : THE HOT PATH, O(kept x new x np).  One lane owns a new particle with a finite distance, its z in registers (NPC, np rounded up to
 //                    a multiple of 4 and padded with zeros, is a template parameter so that they are); blockIdx.y owns one block of PMC_TB consecutive kept
 //                    particles.  A kept particle is the same for every lane of a wave, so its row of kzT and its wn come through the scalar
@@ -70,31 +70,30 @@ __global__ __launch_bounds__(256) void k_pmc_generate(const KParams P, const int
     }
 }
 
-// evaluations [off, off + n) of the list (nullptr: the particles themselves) into the launch's scratch
-__global__ __launch_bounds__(256) void k_pmc_gather(const int np, const int user, const int32_t* __restrict__ list, const int off, const int n,
-                                                    const double* __restrict__ theta, const size_t stride, double* __restrict__ s_cand) {
+// evaluations [off, off + n) of the list (nullptr: the particles themselves) into the launch's scratch (smm_evalscratch.hpp)
+__global__ __launch_bounds__(256) void k_pmc_gather(const EvalScratch E, const int32_t* __restrict__ list, const int off, const int n,
+                                                    const double* __restrict__ theta, const size_t stride) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (size_t)n * np) return;
+    if (e >= (size_t)n * E.np) return;
     const int k = (int)(e / (size_t)n), i = (int)(e - (size_t)k * n);
     const int j = list ? list[off + i] : off + i;
-    s_cand[user ? (size_t)i * np + k : (size_t)k * n + i] = theta[(size_t)k * stride + j];
+    E.put_cand((size_t)n, (size_t)i, k, theta[(size_t)k * stride + j]);
 }
 
 // ... and back: the distance is the value where the status is >= 1 and |value| <= DBL_MAX, else +inf and the particle counts as invalid
-__global__ __launch_bounds__(256) void k_pmc_scatter(const int nm, const int user, const int32_t* __restrict__ list, const int off, const int n,
-                                                     const double* __restrict__ s_value, const double* __restrict__ s_simM, const void* __restrict__ s_status,
+__global__ __launch_bounds__(256) void k_pmc_scatter(const EvalScratch E, const int32_t* __restrict__ list, const int off, const int n,
                                                      double* __restrict__ rho, double* __restrict__ mom, const size_t stride, int32_t* __restrict__ flagw,
                                                      int32_t* __restrict__ n_invalid) {
     const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (i >= n) return;
     const int j = list ? list[off + i] : off + i;
-    const int st = user ? ((const int32_t*)s_status)[i] : (int)((const int8_t*)s_status)[i];
-    const double v = s_value[i];
+    const int st = E.status_of((size_t)i);
+    const double v = E.value_of((size_t)i);
     const bool ok = st >= 1 && __builtin_fabs(v) <= 1.7976931348623157e308;
     rho[j] = ok ? v : __builtin_huge_val();
     flagw[j] = ok ? 1 : 0;
     if (!ok) atomicAdd(n_invalid, 1);
-    for (int f = 0; f < nm; ++f) mom[(size_t)f * stride + j] = s_simM[user ? (size_t)i * nm + f : (size_t)f * n + i];
+    for (int f = 0; f < E.nm; ++f) mom[(size_t)f * stride + j] = E.mom((size_t)n, (size_t)i, f);
 }
 
 // the sampling weights of the kept set (nk = ctl->nk particles, lw): M = max lw, w = smm_exp(lw - M), q = (int64) ceil(w 2^20) >= 1, pre their

@@ -1,6 +1,6 @@
-// the host side of smm_abc_pmc (kernels: smm_pmc.hpp) — part of libsmmhip (included once by smmhip.hip, behind the optimisers' host sides, whose
-// scratch cap and seam it shares; hiprtc never sees it).  One generation g >= 1: k_pmc_whiten of the kept -> k_pmc_propose -> the inside
-// particles compacted (the first read: their number) -> their evaluation in batches under the cap (k_pmc_gather, launch_eval_dev,
+// the host side of smm_abc_pmc (kernels: smm_pmc.hpp; the estimators' frame: smm_estimate_host.hpp) — part of libsmmhip (included once by
+// smmhip.hip, behind the optimisers' host sides; hiprtc never sees it).  One generation g >= 1: k_pmc_whiten of the kept -> k_pmc_propose ->
+// the inside particles compacted (the first read: their number) -> their evaluation in batches under the cap (k_pmc_gather, launch_eval_dev,
 // k_pmc_scatter) -> the particles with a finite distance compacted -> k_pmc_whiten of the new -> k_pmc_kernel and k_pmc_combine, a pass of
 // PMC_PASS blocks of T at a time -> k_pmc_logw -> k_pmc_select -> k_pmc_move -> k_pmc_weights -> k_pmc_mean, k_pmc_pairs, k_pmc_chol for the next
 // generation (the second read: A' and whether the run goes on).  Generation 0 is k_pmc_generate, the evaluation of all P and the same tail.
@@ -54,12 +54,7 @@ extern "C" {
 int smm_abc_pmc(void* ctx, int32_t n_particles, int32_t n_keep, int32_t max_gen, double p_acc_min, double scale, double ridge, const double* probs,
                 int32_t n_probs, smm_abc_pmc_t* out) {
     return api_call(ctx, true, [&](Ctx* c) -> int {
-        // settled and finished, and a hard error nobody has been told of reported once, as smm_opt_simplex does (nothing runs then)
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        (void)check_device_error(c);
-        if (c->failed && !c->failed_told) { c->failed_told = true; return c->failed; }
+        if (const int rc = estimate_enter(c)) return rc;
         if (n_particles > (1 << 22)) return fail(c, SMM_ERR_INVALID_ARG, "smm_abc_pmc: n_particles must not exceed 2^22");
         if (n_keep < 2 || n_keep >= n_particles) return fail(c, SMM_ERR_INVALID_ARG, "smm_abc_pmc: n_keep must be in [2, n_particles)");
         if (max_gen < 0) return fail(c, SMM_ERR_INVALID_ARG, "smm_abc_pmc: max_gen < 0");
@@ -70,12 +65,13 @@ int smm_abc_pmc(void* ctx, int32_t n_particles, int32_t n_keep, int32_t max_gen,
         for (int r = 0; r < n_probs; ++r)
             if (!(probs[r] >= 0.0 && probs[r] <= 1.0)) return fail(c, SMM_ERR_INVALID_ARG, "smm_abc_pmc: a prob outside [0, 1]");
         const KParams& K = c->P;
-        const int np = K.np, nm = K.nm, P = n_particles, A = n_keep, user = c->obj == SMM_OBJ_USER ? 1 : 0;
+        const int np = K.np, nm = K.nm, P = n_particles, A = n_keep;
         const size_t Ps = (size_t)P, As = (size_t)A, G1 = (size_t)max_gen + 1, nq = (size_t)n_probs;
         // a launch's scratch: per evaluation its parameters, moments, value and status
         const size_t per_eval = (size_t)(np + nm + 1) * 8 + 4;
-        const int nb_max = (int)std::min<size_t>(Ps, std::max<size_t>(1, opt_scratch_cap(c) / per_eval));
+        const int nb_max = batch_size(c, Ps, per_eval);
         PmcBufs B(K, Ps, As, (size_t)nb_max, G1, nq);
+        const EvalScratch E = eval_scratch(c, B.s_cand.p, B.s_value.p, B.s_simM.p, B.s_status.p);
         HIPCHK(hipFuncSetAttribute((const void*)k_pmc_mean, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
         HIPCHK(hipFuncSetAttribute((const void*)k_pmc_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, STATS_LDS_N * 8));
         const hipStream_t s = c->stream;
@@ -103,11 +99,10 @@ int smm_abc_pmc(void* ctx, int32_t n_particles, int32_t n_keep, int32_t max_gen,
         auto evaluate = [&](const int32_t* list, int n, double* nrho) {
             for (int off = 0; off < n; off += nb_max) {
                 const int nb = std::min(nb_max, n - off);
-                hipLaunchKernelGGL(k_pmc_gather, blocks((size_t)nb * np, 256), dim3(256), 0, s, np, user, list, off, nb, (const double*)B.nth.p, Ps, B.s_cand.p);
+                hipLaunchKernelGGL(k_pmc_gather, blocks((size_t)nb * np, 256), dim3(256), 0, s, E, list, off, nb, (const double*)B.nth.p, Ps);
                 HIPCHK(hipGetLastError());
-                launch_eval_dev(c, B.s_cand.p, nb, B.s_value.p, B.s_simM.p, B.s_status.p);
-                hipLaunchKernelGGL(k_pmc_scatter, blocks((size_t)nb, 256), dim3(256), 0, s, nm, user, list, off, nb, (const double*)B.s_value.p,
-                                   (const double*)B.s_simM.p, (const void*)B.s_status.p, nrho, B.nmom.p, Ps, B.flagw.p, B.g_ninv.p + g);
+                launch_eval_dev(c, E, nb);
+                hipLaunchKernelGGL(k_pmc_scatter, blocks((size_t)nb, 256), dim3(256), 0, s, E, list, off, nb, nrho, B.nmom.p, Ps, B.flagw.p, B.g_ninv.p + g);
                 HIPCHK(hipGetLastError());
             }
             evaluated += (int64_t)n;
@@ -151,7 +146,7 @@ int smm_abc_pmc(void* ctx, int32_t n_particles, int32_t n_keep, int32_t max_gen,
             hipLaunchKernelGGL(k_pmc_propose, blocks((size_t)n_new, 64), dim3(64), 0, s, K, (const PmcCtl*)ctl, g, n_new, (const double*)B.L.p, (const long long*)B.kpre.p,
                                (const double*)kept[cur].u, As, B.nu.p, B.nth.p, nrho, B.nlw.p, Ps, B.inside_flag.p, B.flagw.p);
             HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_sx_compact, dim3(1), dim3(SX_CP_WG), 0, s, (const int32_t*)nullptr, n_new, (const int32_t*)B.inside_flag.p, B.inside.p, &ctl->n_inside);
+            hipLaunchKernelGGL(k_compact, dim3(1), dim3(COMPACT_WG), 0, s, (const int32_t*)nullptr, n_new, (const int32_t*)B.inside_flag.p, B.inside.p, &ctl->n_inside);
             HIPCHK(hipGetLastError());
             int32_t n_inside = 0;
             HIPCHK(hipMemcpyAsync(&n_inside, &ctl->n_inside, 4, hipMemcpyDeviceToHost, s));
@@ -159,7 +154,7 @@ int smm_abc_pmc(void* ctx, int32_t n_particles, int32_t n_keep, int32_t max_gen,
             n_outside[g] = n_new - n_inside;
             if (n_inside > 0) {
                 evaluate(B.inside.p, n_inside, nrho);
-                hipLaunchKernelGGL(k_sx_compact, dim3(1), dim3(SX_CP_WG), 0, s, (const int32_t*)nullptr, n_new, (const int32_t*)B.flagw.p, B.wlist.p, &ctl->n_w);
+                hipLaunchKernelGGL(k_compact, dim3(1), dim3(COMPACT_WG), 0, s, (const int32_t*)nullptr, n_new, (const int32_t*)B.flagw.p, B.wlist.p, &ctl->n_w);
                 HIPCHK(hipGetLastError());
                 hipLaunchKernelGGL(k_pmc_whiten, blocks((size_t)n_new, 256), dim3(256), 0, s, n_new, np, (const double*)B.L.p, (const double*)B.nu.p, B.nz.p, Ps, (double*)nullptr, 0);
                 HIPCHK(hipGetLastError());
@@ -196,12 +191,12 @@ int smm_abc_pmc(void* ctx, int32_t n_particles, int32_t n_keep, int32_t max_gen,
         HIPCHK(hipMemcpyAsync(&h_ctl, ctl, sizeof h_ctl, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         if (out) {
-            auto down = [&](void* dst, const void* src, size_t bytes) { if (dst) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s)); };
-            down(out->theta, fin.th, As * np * 8); down(out->value, fin.rho, As * 8); down(out->sim_moments, fin.mom, As * nm * 8);
-            down(out->weight, B.kwn.p, As * 8); down(out->logw, fin.lw, As * 8); down(out->born, fin.born, As * 4);
-            down(out->eps, B.g_eps.p, G1 * 8); down(out->p_acc, B.g_pacc.p, G1 * 8); down(out->gen_ess, B.g_ess.p, G1 * 8);
-            down(out->n_invalid, B.g_ninv.p, G1 * 4); down(out->n_underflow, B.g_nund.p, G1 * 4); down(out->n_new_kept, B.g_nnk.p, G1 * 4);
-            down(out->mean, B.mean.p, (size_t)np * 8); down(out->cov, B.C.p, (size_t)np * np * 8); down(out->quantile, B.quant.p, nq * np * 8);
+            const Download down{c};
+            down(out->theta, fin.th, As * np); down(out->value, fin.rho, As); down(out->sim_moments, fin.mom, As * nm);
+            down(out->weight, B.kwn.p, As); down(out->logw, fin.lw, As); down(out->born, fin.born, As);
+            down(out->eps, B.g_eps.p, G1); down(out->p_acc, B.g_pacc.p, G1); down(out->gen_ess, B.g_ess.p, G1);
+            down(out->n_invalid, B.g_ninv.p, G1); down(out->n_underflow, B.g_nund.p, G1); down(out->n_new_kept, B.g_nnk.p, G1);
+            down(out->mean, B.mean.p, (size_t)np); down(out->cov, B.C.p, (size_t)np * np); down(out->quantile, B.quant.p, nq * np);
             HIPCHK(hipStreamSynchronize(s));
             // rows past n_kept, and the counts of generations that never ran
             const double nan = std::numeric_limits<double>::quiet_NaN();

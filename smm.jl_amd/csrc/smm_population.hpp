@@ -3,15 +3,9 @@
 // (smm_set_population, smm_scatter_population).  Both kernels move a few hundred bytes per chain next to the evaluations between them.
 #pragma once
 
-// one batch of chains [c0, c0 + nb) of the context and their M candidates each, j = b * M + m the candidate's index in the batch (n = nb * M).
-// The evaluation kernels fix the layouts: the built-in objectives read params [np][n] and write simM [nm][n], status int8; a user objective's
-// kernel reads theta [n][np] and writes simM [n][nm], status int.
+// one batch of chains [c0, c0 + nb) of the context and their M candidates each, j = b * M + m the candidate's index in the batch (n = nb * M)
 struct PopArgs {
-    double* cand;            // the candidates, in the layout the context's evaluation kernel reads
-    const double* value;     // [n]
-    const double* simM;
-    const void* status;
-    int user;                // 1: a user objective's layouts
+    EvalScratch E;           // the candidates and their evaluations (smm_evalscratch.hpp)
     int c0, nb, M, n;
     double spread;
     int keep_init, force;    // force: candidate 0 is the start whatever it evaluates to (smm_set_population)
@@ -24,10 +18,6 @@ struct PopArgs {
     int32_t* o_pick;         // [N]
     uint32_t* nan_flag;      // set when a NaN value is installed
 };
-
-__device__ inline size_t pop_at(const PopArgs& A, const int width, const int k, const size_t j) {
-    return A.user ? j * (size_t)width + (size_t)k : (size_t)k * (size_t)A.n + j;
-}
 
 // candidate m of global chain g, parameters 2q and 2q + 1 (include/smmhip.h: STREAM_POP): one thread per (candidate, parameter pair)
 __global__ __launch_bounds__(256) void k_pop_candidates(const KParams P, const PopArgs A) {
@@ -49,7 +39,7 @@ __global__ __launch_bounds__(256) void k_pop_candidates(const KParams P, const P
         const double step = u * (hi - lo);
         const double x01 = lo + step;
         const double sc = x01 * span;
-        A.cand[pop_at(A, P.np, k, j)] = sc + lbk;               // mapto_ab, mprob.jl:271
+        A.E.put_cand((size_t)A.n, j, k, sc + lbk);                // mapto_ab, mprob.jl:271
     }
 }
 
@@ -70,8 +60,8 @@ __global__ __launch_bounds__(64 * POP_WPB) void k_pop_select(const KParams P, co
         bm = 0;
     } else {
         for (int m = lane; m < A.M; m += 64) {
-            const double v = A.value[j0 + m];
-            const int st = A.user ? ((const int*)A.status)[j0 + m] : (int)((const int8_t*)A.status)[j0 + m];
+            const double v = A.E.value_of(j0 + m);
+            const int st = A.E.status_of(j0 + m);
             if (st >= 1 && v >= 0.0 && v < INFINITY && v < bv) { bv = v; bm = m; }   // (ascending m: an equal value keeps the lower one)
         }
 #pragma unroll
@@ -85,12 +75,12 @@ __global__ __launch_bounds__(64 * POP_WPB) void k_pop_select(const KParams P, co
     }
     const int pick = bm;
     const size_t jw = j0 + (size_t)(pick < 0 ? 0 : pick);
-    const double value = pick < 0 ? A.init_value : A.value[jw];
+    const double value = pick < 0 ? A.init_value : A.E.value_of(jw);
     double* hr = P.hrec + (size_t)c * P.HW;          // row 0
     double* ro = A.rec_out + (size_t)c * P.RW;
     for (int f = lane; f < np + nm; f += 64) {
-        const double x = f < np ? (pick < 0 ? P.init[f] : A.cand[pop_at(A, np, f, jw)])
-                                : (pick < 0 ? A.init_simM[f - np] : A.simM[pop_at(A, nm, f - np, jw)]);
+        const double x = f < np ? (pick < 0 ? P.init[f] : A.E.cand[A.E.at(np, (size_t)A.n, jw, f)])
+                                : (pick < 0 ? A.init_simM[f - np] : A.E.mom((size_t)A.n, jw, f - np));
         hr[H_PARAMS + f] = x;
         ro[3 + f] = x;
         if (f < np) A.o_start[(size_t)f * N + c] = x;

@@ -1,7 +1,8 @@
 // the host side of the starting population (smm_set_population, smm_scatter_population; kernels: smm_population.hpp) — part of libsmmhip
-// (included once by smmhip.hip, behind its host helpers; hiprtc never sees it).  Both calls share one frame: settle and refuse (pop_enter),
-// evaluate initial_value or nothing, then per batch of chains candidates -> the context's evaluation kernel on device pointers
-// (launch_eval_dev) -> k_pop_select, which writes the chains' completed iteration 1; then the bookkeeping of smm_set_state for iter == 1.
+// (included once by smmhip.hip, behind the estimators' frame, smm_estimate_host.hpp; hiprtc never sees it).  Both calls share one frame:
+// settle and refuse (pop_enter), evaluate initial_value or nothing, then per batch of chains candidates -> the context's evaluation kernel
+// on device pointers (launch_eval_dev) -> k_pop_select, which writes the chains' completed iteration 1; then the bookkeeping of
+// smm_set_state for iter == 1.
 #pragma once
 
 namespace {
@@ -20,14 +21,9 @@ struct PopBufs {
           o_pick(P.N), flag(1) {}
 };
 
-// what both calls do before they look at their arguments: settle, report a failure nobody has been told of (once, as smm_set_state), refuse a
-// context that has stepped
+// what both calls do before they look at their arguments: the estimators' prologue, then refuse a failed context and one that has stepped
 int pop_enter(Ctx* c) {
-    HIPCHK(hipSetDevice(c->device));
-    settle_persist(c);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)check_device_error(c);
-    if (c->failed && !c->failed_told) { c->failed_told = true; return c->failed; }
+    if (const int rc = estimate_enter(c)) return rc;
     if (c->failed) return told(c);
     if (c->run.iter != 0) return fail(c, SMM_ERR_STATE, "the starting population is installed before the first iteration only (completed iterations: " + std::to_string(c->run.iter) + ")");
     if (c->P.T < 1) return fail(c, SMM_ERR_MAXITER, "maxiter == 0: no room for the chains' first iteration");
@@ -44,9 +40,10 @@ void pop_finish(Ctx* c, PopBufs& B, smm_population_t* out, int64_t evaluated, in
     const KParams& P = c->P;
     uint32_t flag = 0;
     HIPCHK(hipMemcpyAsync(&flag, B.flag.p, 4, hipMemcpyDeviceToHost, c->stream));
-    if (out && out->start) HIPCHK(hipMemcpyAsync(out->start, B.o_start.p, (size_t)P.np * P.N * 8, hipMemcpyDeviceToHost, c->stream));
-    if (out && out->value) HIPCHK(hipMemcpyAsync(out->value, B.o_value.p, (size_t)P.N * 8, hipMemcpyDeviceToHost, c->stream));
-    if (out && out->pick) HIPCHK(hipMemcpyAsync(out->pick, B.o_pick.p, (size_t)P.N * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out) {
+        const Download down{c};
+        down(out->start, B.o_start.p, (size_t)P.np * P.N); down(out->value, B.o_value.p, (size_t)P.N); down(out->pick, B.o_pick.p, (size_t)P.N);
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     if (out) out->evaluated = evaluated;
     c->nan_values = flag != 0u;
@@ -64,8 +61,7 @@ void pop_finish(Ctx* c, PopBufs& B, smm_population_t* out, int64_t evaluated, in
 
 PopArgs pop_args(Ctx* c, PopBufs& B) {
     PopArgs A{};
-    A.cand = B.cand.p; A.value = B.value.p; A.simM = B.simM.p; A.status = B.status.p;
-    A.user = c->obj == SMM_OBJ_USER ? 1 : 0;
+    A.E = eval_scratch(c, B.cand.p, B.value.p, B.simM.p, B.status.p);
     A.init_simM = B.i_simM.p;
     A.rec_out = c->rec[c->run.cur];
     A.o_start = B.o_start.p; A.o_value = B.o_value.p; A.o_pick = B.o_pick.p; A.nan_flag = B.flag.p;
@@ -82,29 +78,18 @@ int smm_set_population(void* ctx, const double* starts, smm_population_t* out) {
         if (!starts) return fail(c, SMM_ERR_INVALID_ARG, "smm_set_population: starts is NULL");
         const KParams& P = c->P;
         const size_t N = P.N, np = P.np;
-        std::vector<double> lb(np), ub(np);
-        HIPCHK(hipMemcpy(lb.data(), P.lb, np * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ub.data(), P.ub, np * 8, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < N; ++i)
-            for (size_t k = 0; k < np; ++k) {
-                const double x = starts[k * N + i];
-                if (!(x >= lb[k] && x <= ub[k])) {
-                    char b[192];
-                    snprintf(b, sizeof b, "smm_set_population: the start of chain %d, parameter %d is %g: outside [%g, %g]", P.offset + (int)i + 1, (int)k + 1, x, lb[k], ub[k]);
-                    return fail(c, SMM_ERR_INVALID_ARG, b);
-                }
-            }
+        if (const int rc = starts_in_box(c, "smm_set_population", "chain", P.offset + 1, starts, N)) return rc;
         PopBufs B(P, N);
         PopArgs A = pop_args(c, B);
         std::vector<double> tp;   // (alive until pop_finish has synchronised)
-        if (A.user) {   // a user objective's kernel reads [N][np]
+        if (A.E.user) {   // a user objective's kernel reads [N][np]
             tp.resize(N * np);
             for (size_t i = 0; i < N; ++i)
                 for (size_t k = 0; k < np; ++k) tp[i * np + k] = starts[k * N + i];
         }
-        HIPCHK(hipMemcpyAsync(B.cand.p, A.user ? tp.data() : starts, N * np * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(B.cand.p, A.E.user ? tp.data() : starts, N * np * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemsetAsync(B.flag.p, 0, 4, c->stream));
-        launch_eval_dev(c, B.cand.p, (int)N, B.value.p, B.simM.p, B.status.p);
+        launch_eval_dev(c, A.E, (int)N);
         A.c0 = 0; A.nb = (int)N; A.M = 1; A.n = (int)N; A.force = 1;
         pop_launch_select(c, A);
         pop_finish(c, B, out, (int64_t)N, 1, 0, 0.0);
@@ -120,7 +105,7 @@ int smm_scatter_population(void* ctx, int32_t M, double spread, int32_t keep_ini
         if (!(spread > 0.0 && spread <= 1.0)) return fail(c, SMM_ERR_INVALID_ARG, "smm_scatter_population: spread must lie in (0, 1]");
         if ((int64_t)M * (int64_t)P.Ng >= ((int64_t)1 << 31)) return fail(c, SMM_ERR_INVALID_ARG, "smm_scatter_population: M x N_global must stay below 2^31");
         const size_t per_chain = (size_t)M * ((size_t)(P.np + P.nm + 1) * 8 + 4);
-        const int nb_max = (int)std::min<size_t>((size_t)P.N, std::max<size_t>(1, pop_scratch_cap(c) / per_chain));
+        const int nb_max = batch_size(pop_scratch_cap(c), (size_t)P.N, per_chain);
         PopBufs B(P, (size_t)nb_max * (size_t)M);
         PopArgs A = pop_args(c, B);
         HIPCHK(hipMemsetAsync(B.flag.p, 0, 4, c->stream));
@@ -130,14 +115,14 @@ int smm_scatter_population(void* ctx, int32_t M, double spread, int32_t keep_ini
         HIPCHK(hipMemcpyAsync(&A.init_value, B.i_value.p, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(&ist, B.i_status.p, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        A.init_status = A.user ? (int)ist : (int)(int8_t)(ist & 0xff);   // (the built-in kernels write one int8)
+        A.init_status = A.E.status_of_word(ist);
         A.M = M; A.spread = spread; A.keep_init = keep_init != 0; A.force = 0;
         for (int c0 = 0; c0 < P.N; c0 += nb_max) {
             A.c0 = c0; A.nb = std::min(nb_max, P.N - c0); A.n = A.nb * M;
             const size_t work = (size_t)A.n * (size_t)((P.np + 1) / 2);
             hipLaunchKernelGGL(k_pop_candidates, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, c->stream, P, A);
             HIPCHK(hipGetLastError());
-            launch_eval_dev(c, B.cand.p, A.n, B.value.p, B.simM.p, B.status.p);
+            launch_eval_dev(c, A.E, A.n);
             pop_launch_select(c, A);
         }
         pop_finish(c, B, out, (int64_t)M * P.N + 1, 2, M, spread);

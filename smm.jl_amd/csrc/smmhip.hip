@@ -14,8 +14,8 @@
 //                       populations, and whenever the result is needed before the next chain kernel).
 // Files: smm_params.hpp (parameter block, layouts), smm_accept.hpp (the accept step's rules, written once for every kernel), smm_chain.hpp (chain kernel and its parts), smm_lookahead.hpp (k_pregen_rng,
 // k_exch_plan), smm_exchange.hpp (stand-alone exchange kernels), this file (host: the types, the call frame, the reader prelude, the plain entry points), smm_user_host.hpp (user objectives: registration and their persistent forms, one way through hiprtc), smm_forms_host.hpp (which forms a context runs and the LDS they take: select_forms),
-// smm_launch_host.hpp (the look-ahead windows, the three tables of kernel instantiations, the choosers, the launchers), smm_create_host.hpp (context creation, step by step), smm_run_host.hpp (the run's host side:
-// stepping, settling, the sharded protocol), smm_reducers_host.hpp (the history reducers' host side), smm_population_host.hpp (the starting population's), smm_optslices_host.hpp (smm_opt_slices: the coordinate searches' loop), smm_optsimplex_host.hpp (smm_opt_simplex: the simplex searches' loop), smm_optlm_host.hpp (smm_opt_lm: the Levenberg–Marquardt searches' loop).
+// smm_launch_host.hpp (the look-ahead windows, the four tables of kernel instantiations, the choosers, the launchers), smm_create_host.hpp (context creation, step by step), smm_run_host.hpp (the run's host side:
+// stepping, settling, the sharded protocol), smm_reducers_host.hpp (the history reducers' host side), smm_estimate_host.hpp (the frame of the estimators that evaluate points off the chains; device side: smm_evalscratch.hpp), smm_population_host.hpp (the starting population's), smm_optslices_host.hpp (smm_opt_slices: the coordinate searches' loop), smm_optsimplex_host.hpp (smm_opt_simplex: the simplex searches' loop), smm_optlm_host.hpp (smm_opt_lm: the Levenberg–Marquardt searches' loop), smm_pmc_host.hpp (smm_abc_pmc: the sampler's generations).
 // Everything that does not depend on the chains' state is produced ahead of the dependent loop by
 // wide, latency-tolerant kernels, one window of iterations at a time:
 //   k_pregen_rng      : proposal normals (first tries) and the MH uniforms (probs_acc, :85)
@@ -83,6 +83,7 @@ using namespace smm;
 #include "smm_density.hpp"
 #include "smm_derived.hpp"
 #include "smm_draws.hpp"
+#include "smm_evalscratch.hpp"
 #include "smm_population.hpp"
 #include "smm_optslices.hpp"
 #include "smm_optsimplex.hpp"
@@ -476,6 +477,7 @@ void eval_round_trip(Ctx* c, const double* params, int32_t M, double* value, dou
 }  // namespace
 
 #include "smm_reducers_host.hpp"
+#include "smm_estimate_host.hpp"
 #include "smm_population_host.hpp"
 #include "smm_optslices_host.hpp"
 #include "smm_optsimplex_host.hpp"
@@ -628,14 +630,7 @@ int smm_set_state(void* ctx, const smm_state_t* s, const smm_history_t* h) {
         if (s->iter > 0 && (!h->value || !h->prob || !h->curr_val || !h->best_val || !h->params || !h->sim_moments ||
                             !h->best_id || !h->exchanged || !h->accepted || !h->status))
             return fail(c, SMM_ERR_INVALID_ARG, "smm_set_state needs every field of smm_history_t");
-        HIPCHK(hipSetDevice(c->device));
-        settle_persist(c);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        // a hard error nobody has been TOLD of yet (raised on the device by steps this caller enqueued and never synchronised; the state readers
-        // do not raise): this call is the recovery from a failure, it must not be the place where one disappears — it reports it, once, and uploads
-        // nothing; the caller's next smm_set_state goes through (tests/test_gpu_error_enumeration.py: every `... step ss` sequence lost its error here)
-        (void)check_device_error(c);
-        if (c->failed && !c->failed_told) { c->failed_told = true; return c->failed; }
+        if (const int rc = estimate_enter(c)) return rc;   // (an untold failure is reported here, once: smm_estimate_host.hpp)
         KParams& P = c->P;
         const size_t N = P.N, RW = P.RW, HW = P.HW, np = P.np, nm = P.nm;
         std::vector<double> cs(N * CSW), rec(N * RW, 0.0);

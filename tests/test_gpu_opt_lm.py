@@ -233,7 +233,7 @@ def test_small_scratch_gives_the_same_results_in_batches_of_two(S, hooks, monkey
 
 
 def test_more_searches_than_one_pass_of_the_list_compaction(S, O):
-    """K = 1025: k_sx_compact's workgroup of 1024 takes each list in two passes, the second of one search"""
+    """K = 1025: k_compact's workgroup of 1024 takes each list in two passes, the second of one search"""
     prob, opts = cm.serial_normal(N=3, T=4, ns=500)
     h = S.hip_context(prob, opts)
     st = np.random.default_rng(7).uniform(prob.lb[:, None], prob.ub[:, None], (2, 1025))
@@ -268,12 +268,14 @@ def test_invalid_arguments_are_refused_and_nothing_runs(S):
     assert fn(h._ctx, None, 1, *args) == A.SMM_ERR_INVALID_ARG
     # K x np = 2^31 does not fit an int32 (refused before a start is read)
     assert fn(h._ctx, A.dptr(A.f64(st)), 2 ** 30, *args) == A.SMM_ERR_INVALID_ARG
-    for bad in (3.0000001, nan):
+    for bad, msg in ((3.0000001, "smm_opt_lm: the start of search 5, parameter 1 is 3: outside [-3, 3]"),
+                     (nan, "smm_opt_lm: the start of search 5, parameter 1 is nan: outside [-3, 3]")):
         s2 = st.copy()
         s2[0, 4] = bad
         with pytest.raises(S.SMMHipError) as e:
             h.opt_lm(s2)
         assert e.value.code == A.SMM_ERR_INVALID_ARG and "search 5, parameter 1" in str(e.value)
+        assert str(e.value).split(": ", 1)[1] == msg
     assert h.state().iter == 3
     h.opt_lm(st, fd_step=0.5, lambda_down=1.0, max_iter=3)     # ... and the context is usable afterwards (the arguments' edges are inside)
     h.step(3); plain.step(6)

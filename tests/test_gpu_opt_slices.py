@@ -229,12 +229,14 @@ def test_invalid_arguments_are_refused_and_nothing_runs(S):
             call()
         assert e.value.code == A.SMM_ERR_INVALID_ARG and "smm_opt_slices" in str(e.value), i
     assert h._fn("opt_slices")(h._ctx, None, 1, 5, 1e-5, nan, 10, None) == A.SMM_ERR_INVALID_ARG
-    for bad in (3.0000001, nan):
+    for bad, msg in ((3.0000001, "smm_opt_slices: the start of search 5, parameter 1 is 3: outside [-3, 3]"),
+                     (nan, "smm_opt_slices: the start of search 5, parameter 1 is nan: outside [-3, 3]")):
         s2 = st.copy()
         s2[0, 4] = bad
         with pytest.raises(S.SMMHipError) as e:
             h.opt_slices(s2, 5)
         assert e.value.code == A.SMM_ERR_INVALID_ARG and "search 5, parameter 1" in str(e.value)
+        assert str(e.value).split(": ", 1)[1] == msg
     assert h.state().iter == 3
     h.opt_slices(st, 5, 0.02, 0.5, 3)     # ... and the context is usable afterwards
     h.step(3); plain.step(6)

@@ -201,12 +201,14 @@ def test_set_population_with_distinct_starts(S, O):
 def test_set_population_refuses_starts_outside_the_box(S, O):
     prob, opts = norm_case()
     h, plain = S.hip_context(prob, opts), S.hip_context(prob, opts)
-    for bad in (3.0000001, np.nan):
+    for bad, msg in ((3.0000001, "smm_set_population: the start of chain 5, parameter 1 is 3: outside [-3, 3]"),
+                     (np.nan, "smm_set_population: the start of chain 5, parameter 1 is nan: outside [-3, 3]")):
         starts = np.repeat(prob.init[:, None], 70, axis=1)
         starts[0, 4] = bad
         with pytest.raises(S.SMMHipError) as e:
             h.set_population(starts)
         assert e.value.code == S._abi.SMM_ERR_INVALID_ARG and "chain 5, parameter 1" in str(e.value)
+        assert str(e.value).split(": ", 1)[1] == msg
     for M, spread in ((0, 1.0), (4, 0.0), (4, 1.5), (4, np.nan), (2 ** 31 // 70 + 1, 1.0)):
         with pytest.raises(S.SMMHipError) as e:
             h.scatter_population(M, spread)

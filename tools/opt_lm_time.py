@@ -9,7 +9,7 @@ of the repetitions after one warm call.
 Time per kernel: --device-only runs smm_opt_lm alone, `reps` times after one warm call — the run to put under a kernel trace
 (rocprofv3 --kernel-trace --stats --output-format csv -- python tools/opt_lm_time.py c5 --device-only --reps 1); --kernel-stats FILE reads
 that trace's kernel_stats.csv and prints, per kernel of the call, launches, total and mean time, and the sums for the evaluation
-(k_eval_lm, k_eval_batch), the state kernels (k_lm_*) and the list compaction (k_sx_compact).
+(k_eval_lm, k_eval_batch), the state kernels (k_lm_*) and the list compaction (k_compact).
   python tools/opt_lm_time.py [c4|c5 ...] [--reps 3] [--max-iter 100] [--fd-step 1e-4] [--device-only] [--kernel-stats FILE]"""
 import csv
 import os
@@ -34,7 +34,7 @@ def arg(name, default, kind):
 
 def kernel_stats(path):
     """the rows of a kernel_stats.csv (Name, Calls, TotalDurationNs, ...) that belong to the call, and the sums by family"""
-    fam = {"evaluation": r"\bk_eval_(?:lm|batch)\b", "state": r"\bk_lm_\w+", "compaction": r"\bk_sx_compact\b"}
+    fam = {"evaluation": r"\bk_eval_(?:lm|batch)\b", "state": r"\bk_lm_\w+", "compaction": r"\bk_compact\b"}
     tot = dict.fromkeys(fam, 0.0)
     for row in csv.DictReader(open(path)):
         name = row["Name"]
