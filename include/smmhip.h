@@ -1395,6 +1395,62 @@ typedef struct {              /* caller-allocated; any pointer may be NULL = not
 } smm_abc_pmc_t;
 int  smm_abc_pmc(void* ctx, int32_t n_particles /* P */, int32_t n_keep /* A */, int32_t max_gen, double p_acc_min, double scale /* 2.0 is the paper's */,
                  double ridge, const double* probs, int32_t n_probs, smm_abc_pmc_t* out);
+
+/* Identify: variance-based global sensitivity over a box — the Sobol' first-order and total-order indices of the objective value and of
+ * every simulated moment with respect to every parameter: which parameters move which moments, and how much of that is interaction
+ * (total - first).  smm_get_moment_stats answers locally and linearly, where the chains went; smm_opt_lm's status 4 at one point; this over
+ * the whole box [lo, hi] (NULL, NULL: the context's [lb, ub]) under the uniform distribution.  N = n_base base points need N (np + 2)
+ * independent evaluations: no accept step, no exchange, no serial dependence.  F = nm + 1 outputs: output 0 is the objective value, output
+ * 1 + f simulated moment f.  Valid on any context at any iteration; it never changes the chains, the history, the generator's position or
+ * which kernel form the next step takes.  A stream objective draws from opts.seed, as smm_eval_batch does.  Ordered on smm_stream behind
+ * everything enqueued before (a persistent launch is settled first) and synchronised before it returns; a hard error nobody has been told
+ * of yet is returned once, and nothing runs.
+ *
+ * Numerical contract (every operation rounded on its own, no fma).
+ *   Points: Philox blocks are philox_stream(opts.seed, STREAM_GSA = 9, counter) of smm_rng.hpp; u53 its uniform in [0, 1).  Base point j in
+ *     [0, N), parameter k: a_jk = u53(x0, x1) for even k, u53(x2, x3) for odd k, of the block at counter {j, 0, k >> 1, 0}; b_jk the same at
+ *     counter {j, 1, k >> 1, 0}.  theta = u * (hi_k - lo_k) + lo_k.  Matrix m = 0 is A, m = 1 is B, m = 2 + i is A with coordinate i taken
+ *     from B: yA_j, yB_j and yABi_j are the outputs at base point j.
+ *   Validity: an evaluation is valid when status >= 1 and all F of its outputs are finite (|y| <= DBL_MAX); the others of the N (np + 2)
+ *     are counted in n_invalid.  Base point j is complete when all np + 2 of its evaluations are valid; an incomplete one adds no term
+ *     anywhere (skipped, not zero-filled).  n = n_complete, as a double in every division.
+ *   Centre: a pilot evaluates a_j for j < min(N, 256) once more; centre_f = T(y_f over the pilot's valid evaluations) / (double) their
+ *     number, 0.0 without one.  The pilot's invalid evaluations are not counted in n_invalid.  The first-order estimator is unbiased under
+ *     any constant shift of yB; the centre removes the variance a large mean adds; being a pilot it does not depend on the batch size.
+ *   T, the sum over base points in j order: blocks of 256 consecutive j from 0; a block's terms added left to right from 0.0, skipping
+ *     incomplete points; the block sums added left to right from 0.0 — never a function of grid, batch size or scheduling.
+ *   Per output f: mean = T(yA) / n; var = T(d * d) / n, d = yA - mean: a second pass.
+ *   Per (f, i): p_j = (yB_j - centre_f) * (yABi_j - yA_j); q_j = e * e, e = yA_j - yABi_j; h_j = 0.5 * q_j.
+ *     v_first = T(p) / n (Saltelli et al. 2010); v_total = T(q) / (2.0 * n) (Jansen 1999); first = v_first / var; total = v_total / var.
+ *     se_first = sqrt(r / n) / var, r = T(p * p) / n - v_first * v_first, a negative r replaced by 0.0; se_total the same with
+ *     r = T(h * h) / n - v_total * v_total: what is summed for it is the square of half of q.  The standard errors are those of the
+ *     numerators alone: they ignore var's own sampling error.  The square root is IEEE's.
+ *   Divisions are plain IEEE (0 / 0 gives NaN): a constant output has numerators of exactly 0.0 and a var of 0.0 or of the rounding of a
+ *     mean of equal values, so its indices are 0.0 or NaN; n = 0 gives NaN everywhere but in centre.  lo_k == hi_k is allowed: the
+ *     parameter is frozen, and its indices are 0 or NaN as the arithmetic gives.
+ *   evaluated = N (np + 2) + min(N, 256).
+ *   SMM_ERR_INVALID_ARG: n_base < 1 or > 2^20, exactly one of lo and hi NULL, any !(lb_k <= lo_k <= hi_k <= ub_k) (a NaN too); nothing
+ *     runs then.
+ *   Scratch: resident are yA [F][N], a flag per base point, the block sums — 4 x F x np doubles per block of T for the pairs, F for yA — and
+ *     the pilot's launch (at most 256 evaluations); one evaluation launch's parameters, moments, value and status ((np + nm + 1) x 8 + 4
+ *     bytes an evaluation, np + 2 evaluations a base point), the base points going in batches under smm_opt_slices' 64 MiB (at least one
+ *     base point per batch; a block of T that spans batches goes on from its partial sums); the built-in objectives' points are never
+ *     written.  Freed before the call returns.  The host reads nothing per batch. */
+typedef struct {              /* caller-allocated; any pointer may be NULL = not returned; F = nm + 1 */
+    double*  mean;            /* [F]                                                               */
+    double*  var;             /* [F]                                                               */
+    double*  centre;          /* [F]                                                               */
+    double*  first;           /* [F][np]     S1                                                    */
+    double*  total;           /* [F][np]     ST                                                    */
+    double*  v_first;         /* [F][np]     the numerators                                        */
+    double*  v_total;         /* [F][np]                                                           */
+    double*  se_first;        /* [F][np]                                                           */
+    double*  se_total;        /* [F][np]                                                           */
+    int64_t  n_complete;      /* out: base points with np + 2 valid evaluations                    */
+    int64_t  n_invalid;       /* out: invalid evaluations among the N (np + 2)                     */
+    int64_t  evaluated;       /* out: objective evaluations performed                              */
+} smm_sens_sobol_t;
+int  smm_sens_sobol(void* ctx, int32_t n_base /* N */, const double* lo, const double* hi /* [np] host, NULL = lb / ub */, smm_sens_sobol_t* out);
 int  smm_get_timing(void* ctx, smm_timing_t* out);
 /* on = 1: bracket every kernel of smm_bgp_step with hipEvents on the ctx stream so that
  * smm_get_timing reports iter_kernel_ms / exch_kernel_ms (sums over the last step; each bracket

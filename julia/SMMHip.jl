@@ -18,7 +18,7 @@ export HipBGP, hip_create, hip_destroy!, hip_step!, hip_iter, hip_history, hip_s
 export hip_eval_batch_noseed, hip_stream, hip_sync, hip_local_step!, hip_export_records!, hip_exchange!, hip_sharded_step!, hip_sharded_finish!,
        hip_a2a_capacity, hip_export_values!, hip_a2a_pack!, hip_a2a_apply!, hip_record_doubles
 export hip_chain_stats, hip_chain_cov, hip_chain_diag, hip_rank_diag, hip_get_draws, hip_moment_stats, hip_adjustment, hip_reweighted, hip_profile, hip_density, hip_register_transform, hip_derived, hip_group_stats, hip_histogram, hip_trace, hip_get_proposal, hip_set_proposal!, hip_adapt_proposal!
-export hip_set_population!, hip_scatter_population!, hip_opt_slices, hip_opt_simplex, hip_opt_lm, hip_abc_pmc
+export hip_set_population!, hip_scatter_population!, hip_opt_slices, hip_opt_simplex, hip_opt_lm, hip_abc_pmc, hip_sens_sobol
 export hip_step_async!, hip_p2p_init, hip_p2p_attach!, hip_p2p_step!, hip_p2p_finish!, hip_set_persistent!, hip_persistent_info, P2P_HANDLE_BYTES
 
 const ABI_VERSION = 3
@@ -342,6 +342,21 @@ struct SmmAbcPmc
     generations::Int32
     status::Int32
     reserved::Int32
+    evaluated::Int64
+end
+
+struct SmmSensSobol
+    mean::Ptr{Cdouble}
+    var::Ptr{Cdouble}
+    centre::Ptr{Cdouble}
+    first::Ptr{Cdouble}
+    total::Ptr{Cdouble}
+    v_first::Ptr{Cdouble}
+    v_total::Ptr{Cdouble}
+    se_first::Ptr{Cdouble}
+    se_total::Ptr{Cdouble}
+    n_complete::Int64
+    n_invalid::Int64
     evaluated::Int64
 end
 
@@ -1267,6 +1282,34 @@ function hip_abc_pmc(h::HipBGP, n_particles::Integer, n_keep::Integer; max_gen::
             gen_ess = gen_ess, n_outside = n_outside, n_invalid = n_invalid, n_underflow = n_underflow, n_new_kept = n_new_kept, mean = mean,
             cov = cov, quantile = quantile, ess = res.ess, n_kept = Int(res.n_kept), generations = Int(res.generations), status = Int(res.status),
             evaluated = Int(res.evaluated))
+end
+
+"""
+    hip_sens_sobol(h, n_base; lo = nothing, hi = nothing)
+        -> (mean, var, centre, first, total, v_first, v_total, se_first, se_total, n_complete, n_invalid, evaluated)
+
+Identify: variance-based global sensitivity on the device (`smm_sens_sobol`): the Sobol' first-order and total-order indices of the objective
+value and of every simulated moment with respect to every parameter, from `n_base * (np + 2)` evaluations over the box `[lo, hi]` (both
+`nothing`: the context's bounds).  The chains of the context are not touched.  The tables are `(np, nm + 1)`: column 1 is the value,
+column `1 + f` moment `f`; `mean`, `var` and `centre` have `nm + 1` entries.
+"""
+function hip_sens_sobol(h::HipBGP, n_base::Integer; lo::Union{Nothing,Vector{Float64}} = nothing, hi::Union{Nothing,Vector{Float64}} = nothing)
+    F = h.nm + 1
+    mean = Vector{Float64}(undef, F); var = similar(mean); centre = similar(mean)
+    first = Matrix{Float64}(undef, h.np, F); total = similar(first); v_first = similar(first); v_total = similar(first)
+    se_first = similar(first); se_total = similar(first)
+    lo === nothing || length(lo) == h.np || error("hip_sens_sobol: lo takes one entry per parameter")
+    hi === nothing || length(hi) == h.np || error("hip_sens_sobol: hi takes one entry per parameter")
+    res = nothing
+    GC.@preserve lo hi mean var centre first total v_first v_total se_first se_total begin
+        out = Ref(SmmSensSobol(pointer(mean), pointer(var), pointer(centre), pointer(first), pointer(total), pointer(v_first), pointer(v_total),
+                               pointer(se_first), pointer(se_total), 0, 0, 0))
+        check(h.ctx, ccall(sym(:smm_sens_sobol), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{SmmSensSobol}), h.ctx, n_base,
+                           lo === nothing ? Ptr{Cdouble}(C_NULL) : pointer(lo), hi === nothing ? Ptr{Cdouble}(C_NULL) : pointer(hi), out))
+        res = out[]
+    end
+    return (mean = mean, var = var, centre = centre, first = first, total = total, v_first = v_first, v_total = v_total, se_first = se_first,
+            se_total = se_total, n_complete = Int(res.n_complete), n_invalid = Int(res.n_invalid), evaluated = Int(res.evaluated))
 end
 
 "per-chain state: what `save` / `readMalgo` / `restart!` need besides the history (AlgoAbstract.jl:83-102)"

@@ -33,7 +33,7 @@ import SMM: MAlgo, MAlgoBGP, MProb, Eval, BGPChain, Slice, computeNextIteration!
 import Base: getproperty, show
 using ..SMMHip
 
-export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, posterior_tempered, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, optSlicesHip, optSimplexHip, optLMHip, abcPMCHip, FD_gradient_hip, getSigmaHip
+export MAlgoBGPHip, sync_chains!, flush_steps!, chain_stats, chain_diag, rank_diag, posterior_draws, moment_fit, sensitivity, regression_adjust, posterior_tempered, profile_objective, posterior_density, posterior_derived, pooled_summary, chain_histogram, population_trace, adapt_proposal!, scatter_start!, hip_context, serialNormalHip, evaluateObjectivesHip, doSlicesHip, optSlicesHip, optSimplexHip, optLMHip, abcPMCHip, sobolIndicesHip, FD_gradient_hip, getSigmaHip
 
 """
     MAlgoBGPHip(m::MProb, opts::Dict)
@@ -947,6 +947,32 @@ function abcPMCHip(m::MProb, n_particles::Integer; keep::Real = 0.5, max_gen::In
     return Dict(:mean => Dict(k => r.mean[j] for (j, k) in enumerate(pk)), :cov => r.cov,
                 :quantile => Dict(k => r.quantile[j, :] for (j, k) in enumerate(pk)), :draws => (r.theta[1:n, :], r.weight[1:n]),
                 :eps => r.eps[1:g + 1], :p_acc => r.p_acc[1:g + 1], :status => r.status, :ess => r.ess, :generations => g, :evaluated => r.evaluated)
+end
+
+"""
+    sobolIndicesHip(m, n_base = 4096; box = nothing, opts = Dict()) -> Dict
+
+Identify (`SMMHip.hip_sens_sobol`): the Sobol' first-order and total-order indices of the objective value and of every moment of `m` with
+respect to every sampled parameter, over its box or over a sub-box `box = Dict(name => (lo, hi))`.  `Dict(:first, :total, :interaction,
+:se_first, :se_total => Dict(output => Dict(name => index)), :mean, :var => Dict(output => value), :n_complete, :n_invalid, :evaluated)`,
+the outputs being `:value` and the moments' names.
+"""
+function sobolIndicesHip(m::MProb, n_base::Integer = 4096; box = nothing, opts::Dict = Dict())
+    pk = collect(keys(m.params_to_sample))
+    outs = vcat(Any[:value], collect(keys(m.moments)))
+    lo = hi = nothing
+    if box !== nothing
+        lo = Float64[haskey(box, k) ? box[k][1] : m.params_to_sample[k][:lb] for k in pk]
+        hi = Float64[haskey(box, k) ? box[k][2] : m.params_to_sample[k][:ub] for k in pk]
+    end
+    h = eval_context(m, opts)
+    r = SMMHip.hip_sens_sobol(h, n_base; lo = lo, hi = hi)
+    SMMHip.hip_destroy!(h)
+    table(a) = Dict(o => Dict(k => a[j, f] for (j, k) in enumerate(pk)) for (f, o) in enumerate(outs))
+    return Dict(:first => table(r.first), :total => table(r.total), :interaction => table(r.total .- r.first), :se_first => table(r.se_first),
+                :se_total => table(r.se_total), :mean => Dict(o => r.mean[f] for (f, o) in enumerate(outs)),
+                :var => Dict(o => r.var[f] for (f, o) in enumerate(outs)), :n_complete => r.n_complete, :n_invalid => r.n_invalid,
+                :evaluated => r.evaluated)
 end
 
 "`FD_gradient(m, p)` (econometrics.jl:29-85): the 1 + k (forward) or 2k (central) evaluations in one batch; rows in the order of `p`"

@@ -233,6 +233,14 @@ class smm_abc_pmc_t(C.Structure):
     ]
 
 
+class smm_sens_sobol_t(C.Structure):
+    _fields_ = [
+        ("mean", c_double_p), ("var", c_double_p), ("centre", c_double_p), ("first", c_double_p), ("total", c_double_p),
+        ("v_first", c_double_p), ("v_total", c_double_p), ("se_first", c_double_p), ("se_total", c_double_p),
+        ("n_complete", C.c_int64), ("n_invalid", C.c_int64), ("evaluated", C.c_int64),
+    ]
+
+
 class smm_timing_t(C.Structure):
     _fields_ = [
         ("step_ms", C.c_double), ("iter_kernel_ms", C.c_double), ("exch_kernel_ms", C.c_double),
@@ -316,6 +324,7 @@ SYMBOLS = [
                              C.c_double, C.c_int32, C.c_int32, C.POINTER(smm_opt_lm_t)]),
     ("smm_abc_pmc", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, c_double_p, C.c_int32,
                               C.POINTER(smm_abc_pmc_t)]),
+    ("smm_sens_sobol", C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, C.POINTER(smm_sens_sobol_t)]),
     ("smm_get_timing", C.c_int, [C.c_void_p, C.POINTER(smm_timing_t)]),
     ("smm_get_Z", C.c_int, [C.c_void_p, c_double_p]),
     ("smm_set_profiling", C.c_int, [C.c_void_p, C.c_int32]),

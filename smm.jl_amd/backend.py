@@ -726,6 +726,26 @@ class BGPContext:
             r[f] = getattr(s, f)
         return r
 
+    # --- global sensitivity (include/smmhip.h: smm_sens_sobol) -------------------------------------------------------------------------------------
+    def sens_sobol(self, n_base, lo=None, hi=None):
+        """variance-based global sensitivity on the device (smm_sens_sobol: Sobol' first-order and total-order indices of the objective value
+        and of every simulated moment over the box [lo, hi], None = [lb, ub]; n_base (np + 2) evaluations; the context's chains are not
+        touched).  Returns a dict: mean / var / centre [F], first / total / v_first / v_total / se_first / se_total [F][np] (F = nm + 1:
+        output 0 is the value, 1 + f moment f), and the scalars n_complete, n_invalid, evaluated"""
+        F = self.nm + 1
+        box = [None if b is None else A.f64(list(np.asarray(b, float).reshape(-1))) for b in (lo, hi)]
+        for b in box:
+            if b is not None and len(b) != self.np:
+                raise ValueError("sens_sobol: lo and hi take one entry per parameter")
+        r = dict(mean=np.empty(F), var=np.empty(F), centre=np.empty(F))
+        for f in ("first", "total", "v_first", "v_total", "se_first", "se_total"):
+            r[f] = np.empty((F, self.np))
+        s = self._out(A.smm_sens_sobol_t, r)
+        self._check(self._fn("sens_sobol")(self._ctx, int(n_base), *[None if b is None else A.dptr(b) for b in box], C.byref(s)))
+        for f in ("n_complete", "n_invalid", "evaluated"):
+            r[f] = int(getattr(s, f))
+        return r
+
     def timing(self):
         t = A.smm_timing_t()
         self._check(self._fn("get_timing")(self._ctx, C.byref(t)))

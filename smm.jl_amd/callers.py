@@ -11,7 +11,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .host import Eval, _eval_context, _flat_problem, ms_names, ps2s_names
+from .host import Eval, _eval_context, _flat_problem, _sobol_result, ms_names, ps2s_names
 
 
 def device_evaluator(m, P, noseed_base=None):
@@ -191,6 +191,14 @@ def optLMDevice(m, starts=None, fd_step=1e-4, lambda0=1e-3, lambda_up=10, lambda
     "iterations", "converged", "status", "n_eval", "tries", "ssr", "lambda"}."""
     ctx = _eval_context(m, _flat_problem(m)) if ctx is None else ctx
     return lm_results(m, ctx.opt_lm(opt_starts(m, starts), fd_step, lambda0, lambda_up, lambda_down, xtol, ftol, gtol, maxiter, max_tries))
+
+
+def sobolIndicesDevice(m, n_base=4096, box=None, ctx=None):
+    """variance-based global sensitivity over the MProb's box, on the device (smm_sens_sobol, include/smmhip.h: the Sobol' first-order and
+    total-order indices of the objective value and of every moment; the weighted descendant of the reference's sobolsearch.jl, which only
+    evaluates the objective over a space-filling set).  box: None, or {name: (lo, hi)} for a sub-box.  Returns host.SobolResult."""
+    ctx = _eval_context(m, _flat_problem(m)) if ctx is None else ctx
+    return _sobol_result(m, ctx, n_base, box)
 
 
 # ------------------------------------------------------------------------------------------

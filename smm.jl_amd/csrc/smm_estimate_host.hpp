@@ -1,6 +1,6 @@
 // the host frame of the estimators that evaluate many points off the chains (device side: smm_evalscratch.hpp) — part of libsmmhip (included
 // once by smmhip.hip, in front of smm_population_host.hpp; hiprtc never sees it).  What the starting population, smm_opt_slices,
-// smm_opt_simplex, smm_opt_lm and smm_abc_pmc share, each rule once: the prologue (estimate_enter, smm_set_state's too), the starts inside
+// smm_opt_simplex, smm_opt_lm, smm_abc_pmc and smm_sens_sobol share, each rule once: the prologue (estimate_enter, smm_set_state's too), the starts inside
 // the box, the batch a scratch cap allows, a launch's scratch as a view, the compacted list's count read back, the results' way out.  An
 // estimator's own file keeps its argument checks, its buffers, its argument block and its loop.
 #pragma once

@@ -1,5 +1,5 @@
 // what the estimators that evaluate many points off the chains share on the device — the starting population, smm_opt_slices,
-// smm_opt_simplex, smm_opt_lm, smm_abc_pmc: the view of one evaluation launch's scratch, the evaluation tile on points that are never
+// smm_opt_simplex, smm_opt_lm, smm_abc_pmc, smm_sens_sobol: the view of one evaluation launch's scratch, the evaluation tile on points that are never
 // written, and the compaction of a list — part of libsmmhip (included by smmhip.hip inside its anonymous namespace, in front of
 // smm_population.hpp; gfx950 device code; hiprtc never sees it).  Host side: smm_estimate_host.hpp.
 #pragma once

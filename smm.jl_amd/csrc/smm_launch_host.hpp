@@ -233,16 +233,17 @@ void launch_user_kernel(Ctx* c, const double* theta, int n, double* simM, double
 
 // ---- the batched evaluation kernels of the built-in objectives (eval_tile, smm_chain.hpp) ----
 // Every instantiation of them is named in eval_instance() and nowhere else: a family — k_eval_batch on candidates that were written, the
-// estimators' k_eval_slice and k_eval_lm on points that never are — by obj_kind() (1: simulated, 2: dense, 0: closed form), and the tile
+// estimators' k_eval_slice, k_eval_lm and k_eval_sobol on points that never are — by obj_kind() (1: simulated, 2: dense, 0: closed form), and the tile
 // it takes.  launch_eval_tiles launches the context's row of a family, lds_limits raises every row's dynamic LDS limit.
-enum EvalFamily { EF_BATCH, EF_SLICE, EF_LM, EF_COUNT };
+enum EvalFamily { EF_BATCH, EF_SLICE, EF_LM, EF_SOBOL, EF_COUNT };
 struct EvalKernel { const void* fn; int ct; };
 EvalKernel eval_instance(int family, int kind) {
 #define EVAL(KERN) (kind == 1 ? EvalKernel{(const void*)KERN<1, 8>, 8} : kind == 2 ? EvalKernel{(const void*)KERN<2, 16>, 16} : EvalKernel{(const void*)KERN<0, 8>, 8})
     switch (family) {
         case EF_BATCH: return EVAL(k_eval_batch);
         case EF_SLICE: return EVAL(k_eval_slice);
-        default: return EVAL(k_eval_lm);
+        case EF_LM: return EVAL(k_eval_lm);
+        default: return EVAL(k_eval_sobol);
     }
 #undef EVAL
 }

@@ -15,7 +15,7 @@
 
 namespace smm {
 
-enum : uint32_t { STREAM_U = 1, STREAM_PROP = 2, STREAM_Z = 3, STREAM_PAIRS = 4, STREAM_USER = 6, STREAM_POP = 7, STREAM_PMC = 8 };   // (5: the dense objectives' generated matrices; 7: the candidates of smm_scatter_population; 8: the particles of smm_abc_pmc)
+enum : uint32_t { STREAM_U = 1, STREAM_PROP = 2, STREAM_Z = 3, STREAM_PAIRS = 4, STREAM_USER = 6, STREAM_POP = 7, STREAM_PMC = 8, STREAM_GSA = 9 };   // (5: the dense objectives' generated matrices; 7: the candidates of smm_scatter_population; 8: the particles of smm_abc_pmc; 9: the base points of smm_sens_sobol)
 
 struct U4 { uint32_t x, y, z, w; };
 

@@ -15,7 +15,7 @@
 // Files: smm_params.hpp (parameter block, layouts), smm_accept.hpp (the accept step's rules, written once for every kernel), smm_chain.hpp (chain kernel and its parts), smm_lookahead.hpp (k_pregen_rng,
 // k_exch_plan), smm_exchange.hpp (stand-alone exchange kernels), this file (host: the types, the call frame, the reader prelude, the plain entry points), smm_user_host.hpp (user objectives: registration and their persistent forms, one way through hiprtc), smm_forms_host.hpp (which forms a context runs and the LDS they take: select_forms),
 // smm_launch_host.hpp (the look-ahead windows, the four tables of kernel instantiations, the choosers, the launchers), smm_create_host.hpp (context creation, step by step), smm_run_host.hpp (the run's host side:
-// stepping, settling, the sharded protocol), smm_reducers_host.hpp (the history reducers' host side), smm_estimate_host.hpp (the frame of the estimators that evaluate points off the chains; device side: smm_evalscratch.hpp), smm_population_host.hpp (the starting population's), smm_optslices_host.hpp (smm_opt_slices: the coordinate searches' loop), smm_optsimplex_host.hpp (smm_opt_simplex: the simplex searches' loop), smm_optlm_host.hpp (smm_opt_lm: the Levenberg–Marquardt searches' loop), smm_pmc_host.hpp (smm_abc_pmc: the sampler's generations).
+// stepping, settling, the sharded protocol), smm_reducers_host.hpp (the history reducers' host side), smm_estimate_host.hpp (the frame of the estimators that evaluate points off the chains; device side: smm_evalscratch.hpp), smm_population_host.hpp (the starting population's), smm_optslices_host.hpp (smm_opt_slices: the coordinate searches' loop), smm_optsimplex_host.hpp (smm_opt_simplex: the simplex searches' loop), smm_optlm_host.hpp (smm_opt_lm: the Levenberg–Marquardt searches' loop), smm_pmc_host.hpp (smm_abc_pmc: the sampler's generations), smm_sobol_host.hpp (smm_sens_sobol: the batches of base points).
 // Everything that does not depend on the chains' state is produced ahead of the dependent loop by
 // wide, latency-tolerant kernels, one window of iterations at a time:
 //   k_pregen_rng      : proposal normals (first tries) and the MH uniforms (probs_acc, :85)
@@ -89,6 +89,7 @@ using namespace smm;
 #include "smm_optsimplex.hpp"
 #include "smm_optlm.hpp"
 #include "smm_pmc.hpp"
+#include "smm_sobol.hpp"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -483,6 +484,7 @@ void eval_round_trip(Ctx* c, const double* params, int32_t M, double* value, dou
 #include "smm_optsimplex_host.hpp"
 #include "smm_optlm_host.hpp"
 #include "smm_pmc_host.hpp"
+#include "smm_sobol_host.hpp"
 #include "smm_create_host.hpp"
 
 extern "C" {

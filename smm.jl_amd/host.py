@@ -1201,6 +1201,63 @@ def abc_pmc(algo, n_particles, keep=0.5, max_gen=20, p_acc_min=0.05, scale=2.0, 
     return ABCPMCResult(ps2s_names(algo.m), algo._ctx.abc_pmc(n_particles, A, max_gen, p_acc_min, scale, ridge, probs))
 
 
+class SobolResult:
+    """what global_sensitivity returns: the Sobol' indices of smm_sens_sobol as tables, output name ("value", then the moment names) ->
+    parameter name -> index.  raw: the call's arrays"""
+
+    def __init__(self, params, moments, raw):
+        self.params, self.outputs, self.raw = list(params), ["value"] + list(moments), raw
+        self.n_complete, self.n_invalid, self.evaluated = (raw[f] for f in ("n_complete", "n_invalid", "evaluated"))
+
+    def _table(self, a):
+        return OrderedDict((o, OrderedDict((k, float(a[f, i])) for i, k in enumerate(self.params))) for f, o in enumerate(self.outputs))
+
+    def first(self):
+        return self._table(self.raw["first"])
+
+    def total(self):
+        return self._table(self.raw["total"])
+
+    def interaction(self):
+        """total - first: what a parameter moves only together with others"""
+        return self._table(self.raw["total"] - self.raw["first"])
+
+    def se(self):
+        """{"first": table, "total": table}: the standard errors of the two indices"""
+        return {"first": self._table(self.raw["se_first"]), "total": self._table(self.raw["se_total"])}
+
+    def ranking(self, output="value"):
+        """the parameters sorted by their total index on `output`, the largest first (a NaN last; equal ones in the MProb's order)"""
+        t = self.raw["total"][self.outputs.index(output)]
+        return [self.params[i] for i in sorted(range(len(self.params)), key=lambda i: (np.isnan(t[i]), -t[i] if not np.isnan(t[i]) else 0.0))]
+
+    def unidentified(self, tol=1e-3):
+        """the parameters whose total index on every moment is at most tol (no moment moves with them anywhere in the box: the global
+        form of smm_opt_lm's status 4); a NaN index — a constant moment — counts as not moving"""
+        t = self.raw["total"][1:]
+        return [k for i, k in enumerate(self.params) if all(not (v > tol) for v in t[:, i])]
+
+
+def global_sensitivity(algo, n_base=4096, box=None):
+    """identify: variance-based global sensitivity on the device (smm_sens_sobol): the Sobol' first-order and total-order indices of the
+    objective value and of every simulated moment with respect to every sampled parameter, from n_base (np + 2) evaluations over the
+    MProb's box, or over a sub-box around an estimate: box = {name: (lo, hi)}, the parameters it does not name keep their bounds.  The
+    chains of algo are not touched.  Returns a SobolResult: first(), total(), interaction(), se(), ranking(output), unidentified(tol)"""
+    return _sobol_result(algo.m, algo._ctx, n_base, box)
+
+
+def _sobol_result(m, ctx, n_base, box):
+    names = ps2s_names(m)
+    lo = hi = None
+    if box is not None:
+        unknown = [k for k in box if k not in names]
+        if unknown:
+            raise KeyError("global_sensitivity: %s are no sampled parameters" % unknown)
+        bounds = [box.get(k, (m.params_to_sample[k]["lb"], m.params_to_sample[k]["ub"])) for k in names]
+        lo, hi = [float(b[0]) for b in bounds], [float(b[1]) for b in bounds]
+    return SobolResult(names, ms_names(m), ctx.sens_sobol(n_base, lo, hi))
+
+
 def set_proposal(algo, L):
     """install proposal factor(s) between iterations (smm_set_proposal): [np][np] on a shared-factor run, [N][np][np] per chain"""
     algo._ctx.set_proposal(L)
