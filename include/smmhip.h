@@ -1504,6 +1504,13 @@ int  smm_set_profiling(void* ctx, int32_t on);
  * smm_get_persistent: whether the next step would take this form; launches of it so far; repairs so far. */
 int  smm_set_persistent(void* ctx, int32_t on);
 int  smm_get_persistent(void* ctx, int32_t* available, int32_t* launches, int32_t* repairs);
+/* The exchange plan of a window of iterations depends on (seed, iteration) alone.  A single shard on the locally numbered persistent form
+ * (persistent=loc) of up to some 4390 chains has the NEXT window's plan made beside the chain kernel — a small kernel on a second stream,
+ * in the registers and the LDS the chain kernel leaves on every compute unit — instead of ahead of it on the main stream; the first
+ * window, and one a jump (smm_set_state) or a step pattern asks for that is not the one planned ahead, are planned on the main stream
+ * as ever.  Results are the same to the bit; the host waits for nothing more.  beside: whether this context plans that way; the plan
+ * windows entered so far that were planned beside / on the main stream.  Any pointer may be NULL. */
+int  smm_get_plan_beside(void* ctx, int32_t* beside, int32_t* windows_beside, int32_t* windows_instream);
 /* one line naming the forms this context was given at creation — per-iteration chain kernel, where the exchange is walked, the stand-alone
  * resolution, the persistent form, the look-ahead plan and its window: "chain=iter_norm walk=inline_lean exchange=lean persistent=loc
  * plan=lds window=256" (diagnostic; tests/test_gpu_forms.py holds the table of what is chosen when) */

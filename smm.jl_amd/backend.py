@@ -771,6 +771,12 @@ class BGPContext:
         self._check(self._fn("get_persistent")(self._ctx, C.byref(a), C.byref(l), C.byref(r)))
         return bool(a.value), int(l.value), int(r.value)
 
+    def plan_beside_info(self):
+        """(does the context plan its next exchange window beside the persistent kernel, windows planned beside so far, windows planned on the main stream)"""
+        b, wb, wi = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._check(self._fn("get_plan_beside")(self._ctx, C.byref(b), C.byref(wb), C.byref(wi)))
+        return bool(b.value), int(wb.value), int(wi.value)
+
     def Z(self):
         z = np.empty((self.nm, self.problem.ns))
         self._check(self._fn("get_Z")(self._ctx, A.dptr(z)))

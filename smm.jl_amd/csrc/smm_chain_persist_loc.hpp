@@ -32,6 +32,7 @@
 constexpr int PL_LOCN = NORM_CT + CONE_GCAP + 2;                          // local slots: own chains, gathered chains, the dummy pair's
 constexpr uint32_t PL_PBASE = ((16u * PL_LOCN + 127u) & ~127u);          // LDS offset of the pair lists (slots: 16 bytes reserved each, from address 0)
 constexpr int PL_HASH = 1024;                                             // slots of the re-numbering table (<= 512 entries)
+constexpr int PL_VGPR_HALF = 60;                                          // the kernel's register cap, as amdgpu_num_vgpr counts it (x 2 = 120 allocated)
 // SMMHIP_TS: the simulation phase wave by wave (tools/persist_waves.py) — 8 words per wave behind the tiles' 8 of the phase stamps, for the
 // first PL_TSW_TILES tiles: sums over the launch's iterations of the wall clock when the wave leaves BB [0], has issued its last add [1], has stored
 // its partials [2], and when the control wave's wait for them ends / a worker's side job of the iteration ends [3]; HW_ID [4]; iterations [5];
@@ -159,8 +160,10 @@ __device__ __attribute__((noinline)) PlGather3 pl_wait_gather3(const PrWait W, c
 
 // (PCT: thresholds by chain — WIDE single shards only; a form of its own so that ONE threshold for all chains pays nothing for it: 11.84 -> 12.06 us per iteration when
 // the per-position read was always there, 12.27 as a run-time branch)
+// (120 of the 128 registers four waves per SIMD could have: the 32 left on every SIMD hold a wave of the next window's plan, k_exch_plan_bg,
+// beside this kernel — smm_lookahead.hpp.  The attribute counts each half of the unified file: 60 is 120.)
 template <int NP, bool WIDE, bool SH, bool PCT = false>
-__global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistArgs A) {
+__global__ __launch_bounds__(NORM_WG, 4) __attribute__((amdgpu_num_vgpr(PL_VGPR_HALF))) void k_chain_persist_loc(const PersistArgs A) {
     static_assert(!PCT || (WIDE && !SH), "thresholds by chain: the wide walk of a single shard");
     static_assert(NP == 1 || NP == 2, "one moment per half of the workgroup");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -186,6 +189,9 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
     auto exch_on = [&](const int tx) { return exch_any && tx >= A.exch_from; };   // AlgoBGP.jl:637
 
     if (error_before(*(const volatile unsigned long long*)A.err, t0)) return;   // an EARLIER launch raised a hard error
+    // every wave of this kernel ahead of the waves of the next window's plan, which run beside it at priority 0 (k_exch_plan_bg); the adds
+    // one step above that, where they stood one step above 0
+    __builtin_amdgcn_s_setprio(1);
 
     // ---- once per launch: the tile's chain state and records, the constants, wave 0's shocks into LDS ----
     if (tid < 64) {
@@ -495,14 +501,14 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
             unsigned long long tw0 = 0, tw1 = 0, tw2 = 0;
             if (A.ts) tw0 = wall_clock64();
             if (simw) {
-                __builtin_amdgcn_s_setprio(1);   // the adds before any side job of a wave that is done with them (make_rng's FP64, the tables, the lists)
+                __builtin_amdgcn_s_setprio(2);   // the adds before any side job of a wave that is done with them (make_rng's FP64, the tables, the lists)
                 if (nfull == PR_ZR - 1) persist_simulate<NP, true>(z, nfull, extra, Y.s_theta, Y.s_part, h, wih, A.ts != nullptr, tw1);
                 else persist_simulate<NP, false>(z, nfull, extra, Y.s_theta, Y.s_part, h, wih, A.ts != nullptr, tw1);
                 if (A.ts) tw2 = wall_clock64();
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 const int lane3 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
                 if (lane3 == 0) __hip_atomic_fetch_add(Y.s_arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __builtin_amdgcn_s_setprio(0);
+                __builtin_amdgcn_s_setprio(1);
             }
             const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
             const bool lists = t < t1 && exch_on(t);
@@ -742,13 +748,13 @@ __global__ __launch_bounds__(NORM_WG, 4) void k_chain_persist_loc(const PersistA
                     st[CS_WASX] = (double)src;   // (free during the launch: the LOCAL number the record comes from)
                 }
             }
-            __builtin_amdgcn_s_setprio(1);
+            __builtin_amdgcn_s_setprio(2);
             if (nfull0 == PR_ZR - 1) persist_simulate<NP, true>(z0, nfull0, extra0, Y.s_theta, Y.s_part, 0, 0, A.ts != nullptr, tw1);
             else persist_simulate<NP, false>(z0, nfull0, extra0, Y.s_theta, Y.s_part, 0, 0, A.ts != nullptr, tw1);
             if (A.ts) tw2 = wall_clock64();
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (lane_a == 0) __hip_atomic_fetch_add(Y.s_arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(1);
         }
         {
             const unsigned want = (unsigned)(8 * NP) * (unsigned)rel;

@@ -280,6 +280,26 @@ void choose_forms(Ctx* c, int objective_id, bool ask = true, int per_cu = -1) {
     if (F.cone_tiles) { P.cone_tiles = F.cone_tiles; P.cone_ct = F.cone_ct; }
 }
 
+// Does the context plan its next window BESIDE its persistent chain kernel (k_exch_plan_bg on a second stream) instead of ahead of it on the
+// main stream?  A single shard on k_chain_persist_loc with the LDS plan, whose pairs' state fits that kernel's LDS (plan_bg_fits: up to
+// some 4390 chains), and one chain workgroup plus one background workgroup resident on a compute unit by arithmetic:
+//   registers   4 waves x 120 (PL_VGPR_HALF) + 1 wave x 32 (PBG_VGPR_HALF) = 512 per lane and SIMD, the whole file;
+//   wave slots  16 + 4 of 32;
+//   LDS         persist_loc_smem_bytes(np) + PBG_LDS, each rounded up to the granule of 1280 bytes, within the unit's 160 KiB;
+//   PBG_LDS     more than half the unit's: a second background workgroup never takes the room of a chain workgroup.
+// (tests/test_plan_beside_budget.py holds the kernels to these figures.)  SMMHIP_PLAN_AHEAD=0 of the test build switches the path off.
+constexpr size_t LDS_GRANULE = 1280;
+bool plan_beside_resident(int np) {
+    auto up = [](size_t b) { return (b + LDS_GRANULE - 1) / LDS_GRANULE * LDS_GRANULE; };
+    return up(persist_loc_smem_bytes(np)) + up(PBG_LDS + PBG_LDS_STATIC) <= LDS_CU && PBG_LDS > LDS_HALF && 4 * 2 * PL_VGPR_HALF + 2 * PBG_VGPR_HALF <= 512;
+}
+void choose_plan_beside(Ctx* c) {
+    const Forms& F = c->F;
+    const KParams& P = c->P;
+    c->plan_beside = F.plan == PLAN_LDS && F.persist == PERSIST_LOC && !F.persist_sh && P.N == P.Ng && F.cone_tiles > 0 && F.cone_gather && F.plan_cap >= 2 &&
+                     !c->H.plan_ahead_off && plan_bg_fits(P.Ng, P.plan_K) && plan_beside_resident(P.np);
+}
+
 // the look-ahead tables: the window of randomness blocks, the plan window's set of level tables (c->win) and what the forms add to it
 void alloc_windows(Ctx* c) {
     KParams& P = c->P;
@@ -310,6 +330,20 @@ void alloc_windows(Ctx* c) {
         HIPCHK(hipMemset(P.walk_flags, 0, 16));
     }
     if (F.cone_big || F.persist_sh_big) c->cb_scratch = dalloc<uint32_t>(c, W * cone_big_scratch_words(P.Ng, P.plan_K));
+    if (c->plan_beside) {   // the LDS plan's second set of tables (the first: the window's own): twice the plan tables' memory, nothing else
+        HIPCHK(hipStreamCreateWithFlags(&c->pstream, hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&c->ev_free, hipEventDisableTiming));
+        static_cast<LevelTables&>(c->ps[0]) = c->win;
+        c->ps[0].plan = c->win_plan; c->ps[0].plan_mi = c->win_plan_mi; c->ps[0].lv_pairs_p = c->win_lv_pairs_p; c->ps[0].lv_offp = c->win_lv_offp;
+        alloc_level_tables(c, c->ps[1], false, (size_t)F.cone_tiles, F.cone_gather);
+        c->ps[1].plan = dalloc<unsigned long long>(c, W * K);
+        c->ps[1].plan_mi = dalloc<double>(c, W * K);
+        if (F.lean_plan) {
+            c->ps[1].lv_pairs_p = dalloc<uint32_t>(c, W * P.plan_Kp + 512);
+            c->ps[1].lv_offp = dalloc<uint32_t>(c, W * LV_OFFP);
+        }
+        for (Ctx::PlanSet& S : c->ps) HIPCHK(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+    }
     if (F.plan_ahead) {   // the big plan's second set of tables (the first: the window's own)
         HIPCHK(hipStreamCreateWithFlags(&c->pstream, hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&c->ev_free, hipEventDisableTiming));
@@ -441,6 +475,7 @@ int smm_ctx_create(const smm_problem_t* prob, const smm_bgp_opts_t* opts, const 
         if (const char* why = create_facts(c, prob, opts, tab)) throw std::string(why);
         upload_inputs(c, prob, opts, tab);
         choose_forms(c, prob->objective_id);
+        choose_plan_beside(c);
         alloc_windows(c);
         init_state(c, opts);
         if (c->F.persist != PERSIST_NONE) alloc_persist(c);

@@ -154,6 +154,8 @@ Forms select_forms(const Ctx* c, const Hooks& H, const DeviceFacts& dev) {
     if (want_gen_small || want_user) plan_iter += persist_tiles * cone_gather_iter + 4;                     // cone tables: the small gen form's
     F.win_cap = pregen ? (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)768 << 20) / rb_iter)) : 1;
     F.win_cap = std::min(F.win_cap, P.T);
+    // (one set of tables is counted: a context that plans beside its persistent kernel — choose_plan_beside, smm_create_host.hpp — allocates a second set
+    // of the LDS plan's, so up to twice this budget; at 4096 chains 2 x 0.65 GB, and the window stays at its 256 iterations)
     F.plan_cap = (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)1536 << 20) / plan_iter));
     F.plan_cap = std::max(1, std::min(std::min(F.plan_cap, P.T), H.plan_cap));
     // the exchange: the big plan's forms

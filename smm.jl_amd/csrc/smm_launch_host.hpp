@@ -49,6 +49,21 @@ void plan_window_into(Ctx* c, int k, int t) {
     S.t0 = t; S.w = W;
 }
 
+// the same for the LDS plan of a context that plans beside its persistent chain kernel (Ctx::plan_beside): one launch of k_exch_plan_bg, one
+// small workgroup per iteration, which the chain kernel's workgroups leave room for on every compute unit (smm_lookahead.hpp).  No copy
+// of the cone flags to the host: the persistent kernel looks at them itself, the per-iteration forms never did
+void plan_beside_into(Ctx* c, int k, int t) {
+    Ctx::PlanSet& S = c->ps[k];
+    KParams Pw = c->P;
+    HIPCHK(hipEventRecord(c->ev_free, c->stream));
+    HIPCHK(hipStreamWaitEvent(c->pstream, c->ev_free, 0));
+    point_tables(Pw, S);
+    const int W = std::min(c->F.plan_cap, Pw.T - t + 1);
+    launch_exch(c, XI_PLAN_BG, dim3(W), PBG_LDS, c->pstream, Pw, t, S.plan, S.plan_mi, S.lv_pairs, S.lv_mi, S.lv_off, S.lv_pairs_p, S.lv_offp);
+    HIPCHK(hipEventRecord(S.done, c->pstream));
+    S.t0 = t; S.w = W;
+}
+
 // iteration t lies behind the plan window, the exchange of t - 1 is still to be walked: does the window planned ahead hold both?
 bool plan_ahead_covers(const Ctx* c, int t) {
     const Ctx::PlanSet& S = c->ps[c->ps_act ^ 1];
@@ -104,7 +119,35 @@ void ensure_windows(Ctx* c, int t, bool rng = true) {
         }
         point_tables(P, c->win);
     }
-    if (c->F.plan == PLAN_LDS && P.Ng > 1 && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
+    if (c->F.plan == PLAN_LDS && c->plan_beside && P.Ng > 1 && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
+        // the window planned beside the chain kernels of the one before it, if it is the one needed (the same rule as the big plans'); else
+        // — the first window, a jump, a step pattern that asks for another start — k_exch_plan on the main stream into the active set, as
+        // ever.  The host waits for neither: the persistent kernel reads the cone flags itself
+        const int nx = c->ps_act ^ 1;
+        Ctx::PlanSet& A = c->ps[nx];
+        if (A.w > 0 && (A.t0 == t || (A.t0 == t - 1 && A.w >= 2))) {
+            HIPCHK(hipStreamWaitEvent(c->stream, A.done, 0));
+            c->ps_act = nx;
+            ++c->windows_beside;
+        } else {
+            Ctx::PlanSet& S = c->ps[c->ps_act];
+            KParams Pw = P;
+            point_tables(Pw, S);
+            const int W = std::min(c->F.plan_cap, P.T - t + 1);
+            launch_exch(c, XI_PLAN, dim3(W), plan_smem(P.Ng, P.plan_K, true), c->stream, Pw, t, S.plan, S.plan_mi, S.lv_pairs, S.lv_mi, S.lv_off, S.lv_pairs_p, S.lv_offp);
+            S.t0 = t; S.w = W;
+            ++c->windows_instream;
+        }
+        Ctx::PlanSet& S = c->ps[c->ps_act];
+        c->plan_t0 = S.t0; c->plan_w = S.w;
+        P.plan = S.plan; P.plan_mi = S.plan_mi; P.plan_t0 = S.t0;
+        point_tables(P, S);
+        P.lv_pairs_p = S.lv_pairs_p; P.lv_offp = S.lv_offp;
+        // the next window, into the set that the launches enqueued so far read: it starts with the LAST iteration of this one, where the
+        // persistent kernel's next launch finds the exchange it left pending (launch_chain_persist)
+        c->ps[c->ps_act ^ 1].w = 0;
+        if (S.t0 + S.w <= P.T) plan_beside_into(c, c->ps_act ^ 1, S.t0 + S.w - (S.w >= 2 && c->F.plan_cap >= 2 ? 1 : 0));
+    } else if (c->F.plan == PLAN_LDS && P.Ng > 1 && !(t >= c->plan_t0 && t < c->plan_t0 + c->plan_w)) {
         const int W = std::min(c->F.plan_cap, P.T - t + 1);
         launch_exch(c, XI_PLAN, dim3(W), plan_smem(P.Ng, P.plan_K, c->F.cone || c->F.persist != PERSIST_NONE), c->stream, P, t, c->win_plan, c->win_plan_mi,
                     c->win.lv_pairs, c->win.lv_mi, c->win.lv_off, c->win_lv_pairs_p, c->win_lv_offp);
@@ -335,6 +378,7 @@ ExchInstance exch_instance(int id, int Ng) {
         case XI_ROWS_WIN_PLDS: return {(const void*)k_exch_resolve_rows<true, true>, XWG, rows_part, XG_KEYS, "rows_window", true};
         case XI_ROWS_WIN: return {(const void*)k_exch_resolve_rows<false, true>, XWG, rows_all, XG_KEYS, "rows_window", true};
         case XI_APPLY: return {(const void*)k_exch_apply, 256, 0, XG_BIG, "apply", false};   // (the three-phase calls: the resolved swaps into the records)
+        case XI_PLAN_BG: return {(const void*)k_exch_plan_bg, PBG_WG, PBG_LDS, XG_LDS, "plan_bg", false};   // (the next window's plan, beside the persistent chain kernel)
         default: return {nullptr, 0, 0, XG_LDS, id == XI_TICKETS ? "tickets" : "lvl", false};   // (a row of the test build)
     }
 }

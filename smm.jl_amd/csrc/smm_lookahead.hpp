@@ -473,3 +473,321 @@ __global__ __launch_bounds__(XWG) void k_exch_plan(const KParams P, const int t0
 }
 // LDS of the cone passes (k_exch_plan's request is the larger of this and its own)
 __host__ __device__ inline size_t plan_cone_bytes() { return (size_t)152 * 1024; }
+
+// ------------------------------------------------------------------------------------------
+// k_exch_plan_bg: k_exch_plan's tables — the same words with the same meaning — from a workgroup made to run BESIDE k_chain_persist_loc
+// instead of ahead of it: the plan of a window depends on (seed, iteration) alone, so the next window's is made on a second stream while
+// the chain kernels of the current one run (smm_launch_host.hpp, plan_beside_into).  The chain kernel leaves 32 registers per lane on
+// every SIMD, some 85 KB of LDS and half the wave slots of a CU; this kernel takes that and nothing more:
+//   * 256 threads, one wave per SIMD, at most 32 registers (spills: nobody waits for this kernel), priority 0 throughout;
+//   * what k_exch_plan keeps in registers per pair (ranks, predecessors, last-pair flags, chains, level) lives in LDS: 11 bytes per pair;
+//   * the cone bits take what is left of PBG_LDS behind that state: 32 or 64 tiles per pass instead of 128 (the propagation is repeated per pass);
+//   * PBG_LDS > 80 KB: two of these workgroups never share a CU, so none ever keeps a chain workgroup from being placed.
+// A population whose state does not fit (plan_bg_fits) keeps k_exch_plan on the main stream.
+// ------------------------------------------------------------------------------------------
+constexpr int PBG_WG = 256;
+constexpr int PBG_VGPR_HALF = 16;                   // as amdgpu_num_vgpr counts it (x 2 = 32 allocated)
+constexpr size_t PBG_LDS = (size_t)82 * 1024;       // the request, whatever the population
+constexpr size_t PBG_LDS_STATIC = 256;              // what the compiler may add to it (__syncthreads_or's words); tests/test_plan_beside_budget.py holds the code object to it
+constexpr size_t PBG_HDR = 512;                    // bytes in front of the pairs' state: level starts (2 x 34 words), wave sums, nlev, bad
+__host__ __device__ inline size_t plan_bg_pairs(const int K) { return ((size_t)K + 7) & ~(size_t)7; }
+__host__ __device__ inline size_t plan_bg_state_bytes(const int K) { return PBG_HDR + 11 * plan_bg_pairs(K); }   // (a multiple of 8)
+// the three uses of the LDS behind the state: buckets (cursor per chain, 2K list positions), levels (second copy, histogram), one pass of cones at 32 tiles and 32 levels
+__host__ __device__ inline bool plan_bg_fits(const int Ng, const int K) {
+    if (K < 1 || K > XLDS_MAX || Ng > XLDS_MAX) return false;
+    const size_t st = plan_bg_state_bytes(K), mx = (size_t)(Ng > K ? Ng : K) + 2;
+    const size_t a = (size_t)(Ng + 2) * 4 + (size_t)K * 4, b = plan_bg_pairs(K) * 2 + mx * 4, c = (size_t)K * 4 + (size_t)32 * (LV_MAXLEV + 1) * 4 + 32 * 4;
+    return st + a <= PBG_LDS && st + b <= PBG_LDS && st + c <= PBG_LDS;
+}
+// exclusive scan of a[0..n) in place by the whole workgroup (wsum: 4 words; barriers inside)
+__device__ inline void plan_bg_scan(uint32_t* a, const int n, uint32_t* wsum, const int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const int per = (n + PBG_WG - 1) / PBG_WG, c0 = tid * per;
+    uint32_t sum = 0;
+    for (int u = 0; u < per; ++u) sum += c0 + u < n ? a[c0 + u] : 0u;
+    uint32_t incl = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t run = incl - sum;
+    for (int w = 0; w < wave; ++w) run += wsum[w];
+    for (int u = 0; u < per; ++u)
+        if (c0 + u < n) { const uint32_t v = a[c0 + u]; a[c0 + u] = run; run += v; }
+    __syncthreads();
+}
+__global__ __launch_bounds__(PBG_WG) __attribute__((amdgpu_num_vgpr(PBG_VGPR_HALF))) void k_exch_plan_bg(
+    const KParams P, const int t0, unsigned long long* __restrict__ plan, double* __restrict__ plan_mi, uint32_t* __restrict__ lv_pairs,
+    double* __restrict__ lv_mi, uint32_t* __restrict__ lv_off, uint32_t* __restrict__ lv_pairs_p, uint32_t* __restrict__ lv_offp) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char xsm[];
+    constexpr uint16_t NONE = 0xffffu;
+    const int tid = threadIdx.x;
+    const int t = t0 + blockIdx.x;
+    const int Ng = P.Ng, K = P.plan_K;
+    const size_t Kp = plan_bg_pairs(K);
+    uint32_t* hdr = (uint32_t*)xsm;
+    uint32_t *s_lst = hdr, *s_pst = hdr + 34, *wsum = hdr + 68, *s_nlev = hdr + 76, *s_bad = hdr + 77;
+    uint16_t* pi = (uint16_t*)(xsm + PBG_HDR);   // [Kp] each: the pair's chains, its predecessors on them (first: its ranks), its level
+    uint16_t *pj = pi + Kp, *prei = pj + Kp, *prej = prei + Kp, *lvl = prej + Kp;
+    uint8_t* flg = (uint8_t*)(lvl + Kp);         // [Kp]: bit 0 / 1: the pair is the last one of its chain i / j
+    unsigned char* tmp = xsm + plan_bg_state_bytes(K);
+    uint32_t* cnt = (uint32_t*)tmp;              // [Ng+2]  histogram -> cursor
+    uint16_t* ep = (uint16_t*)(cnt + Ng + 2);    // [2K]  list positions bucketed by chain
+    unsigned long long* out = plan + (size_t)blockIdx.x * K;
+    double* out_mi = plan_mi + (size_t)blockIdx.x * K;
+    auto stamp = [&](const int k) { if (P.ts && blockIdx.x == 0 && tid == 0) P.ts[(size_t)8 * 60000 + 90 + k] = wall_clock64(); };
+
+    stamp(0);
+    if (tid == 0) { *s_nlev = 0u; *s_bad = 0u; }
+    for (int c = tid; c < Ng; c += PBG_WG) cnt[c] = 0;
+    if (P.pairtab) {
+        for (int q = tid; q < K; q += PBG_WG) {
+            pi[q] = (uint16_t)P.pairtab[((size_t)(t - 1) * K + q) * 2];
+            pj[q] = (uint16_t)P.pairtab[((size_t)(t - 1) * K + q) * 2 + 1];
+        }
+    } else {
+        PairPerm pp;
+        pp.init(P.seed, (uint32_t)t, (uint64_t)Ng * (uint64_t)(Ng - 1) / 2);
+        for (int q = tid; q < K; q += PBG_WG) {
+            int32_t i, j;
+            pair_unrank(pp.eval((uint64_t)q), i, j);
+            pi[q] = (uint16_t)i;
+            pj[q] = (uint16_t)j;
+        }
+    }
+    __syncthreads();
+    stamp(1);
+    for (int q = tid; q < K; q += PBG_WG) {  // histogram of endpoints
+        atomicAdd(&cnt[pi[q]], 1u);
+        atomicAdd(&cnt[pj[q]], 1u);
+    }
+    __syncthreads();
+    plan_bg_scan(cnt, Ng, wsum, tid);   // -> bucket start
+    for (int q = tid; q < K; q += PBG_WG) {  // scatter (order inside a bucket is arbitrary)
+        ep[atomicAdd(&cnt[pi[q]], 1u)] = (uint16_t)q;
+        ep[atomicAdd(&cnt[pj[q]], 1u)] = (uint16_t)q;
+    }
+    __syncthreads();  // now cnt[c] == end of chain c's bucket
+    for (int q = tid; q < K; q += PBG_WG) {  // rank = number of smaller list positions in the bucket
+        const uint32_t i = pi[q], j = pj[q];
+        uint32_t b = i ? cnt[i - 1] : 0u, e = cnt[i], ri = 0, rj = 0;
+        for (uint32_t x = b; x < e; ++x) ri += ((uint32_t)ep[x] < (uint32_t)q) ? 1u : 0u;
+        b = j ? cnt[j - 1] : 0u; e = cnt[j];
+        for (uint32_t x = b; x < e; ++x) rj += ((uint32_t)ep[x] < (uint32_t)q) ? 1u : 0u;
+        out[q] = (unsigned long long)i | ((unsigned long long)j << 16) | ((unsigned long long)ri << 32) | ((unsigned long long)rj << 48);
+        out_mi[q] = P.min_improve_g[i];  // the threshold of the pair's colder chain, AlgoBGP.jl:688
+        prei[q] = (uint16_t)ri; prej[q] = (uint16_t)rj;
+    }
+    __syncthreads();
+    stamp(2);
+    // ---- dependency levels (k_exch_plan): buckets re-written in rank order, the predecessor of rank r is the entry of rank r-1 ----
+    for (int q = tid; q < K; q += PBG_WG) {
+        const uint32_t i = pi[q], j = pj[q];
+        ep[(i ? cnt[i - 1] : 0u) + prei[q]] = (uint16_t)q;
+        ep[(j ? cnt[j - 1] : 0u) + prej[q]] = (uint16_t)q;
+    }
+    __syncthreads();
+    for (int q = tid; q < K; q += PBG_WG) {   // ranks -> predecessors, in place
+        const uint32_t i = pi[q], j = pj[q], ri = prei[q], rj = prej[q];
+        const uint32_t bi = i ? cnt[i - 1] : 0u, bj = j ? cnt[j - 1] : 0u;
+        prei[q] = ri ? ep[bi + ri - 1] : NONE;
+        prej[q] = rj ? ep[bj + rj - 1] : NONE;
+        flg[q] = (uint8_t)((bi + ri + 1u == cnt[i] ? 1u : 0u) | (bj + rj + 1u == cnt[j] ? 2u : 0u));
+    }
+    __syncthreads();  // cnt / ep are free from here on
+    uint16_t* lvl_b = (uint16_t*)tmp;                 // [Kp]: the levels' second copy (one barrier per sweep)
+    uint32_t* lhist = (uint32_t*)(lvl_b + Kp);        // [max(Ng, K) + 2]
+    const int nh = (Ng > K ? Ng : K) + 2;
+    for (int q = tid; q < K; q += PBG_WG) { lvl[q] = 0; lvl_b[q] = 0; }
+    __syncthreads();
+    {
+        const uint16_t* cur = lvl;
+        uint16_t* nxt = lvl_b;
+        int changed = 1;
+        while (changed) {  // Jacobi sweeps: converges after (number of levels) sweeps; cur[q] is what the sweep before wrote for q
+            int mine = 0;
+            for (int q = tid; q < K; q += PBG_WG) {
+                const uint32_t p1 = prei[q], p2 = prej[q];
+                const uint32_t a = p1 != NONE ? cur[p1] : 0u, b = p2 != NONE ? cur[p2] : 0u;
+                const bool known = (p1 == NONE || a) && (p2 == NONE || b);
+                const uint16_t nl = known ? (uint16_t)(1u + (a > b ? a : b)) : (uint16_t)0;
+                if (nl != cur[q]) mine = 1;
+                nxt[q] = nl;
+            }
+            changed = __syncthreads_or(mine);
+            const uint16_t* x = cur; cur = nxt; nxt = (uint16_t*)x;
+        }
+        // (converged: the last sweep changed nothing, both copies hold the levels; everything below reads lvl)
+    }
+    stamp(3);
+    // counting sort of the pairs by level
+    for (int c = tid; c < nh; c += PBG_WG) lhist[c] = 0;
+    __syncthreads();
+    {
+        uint32_t mx = 0;
+        for (int q = tid; q < K; q += PBG_WG) { const uint32_t l = lvl[q]; atomicAdd(&lhist[l], 1u); mx = l > mx ? l : mx; }
+        atomicMax(s_nlev, mx);
+    }
+    __syncthreads();
+    const int nlev = (int)*s_nlev;
+    plan_bg_scan(lhist, nlev + 1, wsum, tid);   // lhist[c] = number of pairs in levels < c (level c starts here)
+    uint32_t* o_off = lv_off + (size_t)blockIdx.x * (K + 2);
+    for (int l = tid; l < nlev; l += PBG_WG) o_off[l] = (l + 2 <= nlev) ? lhist[l + 2] : (uint32_t)K;
+    if (tid == 0) o_off[K + 1] = (uint32_t)nlev;
+    const bool lean = lv_pairs_p != nullptr && nlev <= LV_MAXLEV;
+    uint32_t* o_pp = lv_pairs_p ? lv_pairs_p + (size_t)blockIdx.x * P.plan_Kp : nullptr;
+    if (lv_offp && tid == 0) {
+        uint32_t* o = lv_offp + (size_t)blockIdx.x * LV_OFFP;
+        o[33] = (uint32_t)nlev; o[34] = lean ? 1u : 0u;
+        if (lean) {
+            uint32_t acc = 0;
+            for (int c = 1; c <= nlev; ++c) {
+                s_lst[c] = lhist[c]; s_pst[c] = acc; o[c - 1] = acc;
+                acc += ((c + 1 <= nlev ? lhist[c + 1] : (uint32_t)K) - lhist[c] + 63u) & ~63u;
+            }
+            s_pst[nlev + 1] = acc; o[nlev] = acc;
+        }
+    }
+    __syncthreads();
+    const uint32_t sc8 = (uint32_t)P.lean_unit;
+    if (lean) {
+        const uint32_t Ng4 = lean_Ng4(Ng);
+        const uint32_t dummy = P.lean_wide ? LeanLayout<LEAN_WIDE>::dummy_word(sc8, Ng4) : LeanLayout<LEAN_KEYS>::dummy_word(sc8, Ng4);
+        for (uint32_t q = tid; q < s_pst[nlev + 1]; q += PBG_WG) o_pp[q] = dummy;
+    }
+    __syncthreads();
+    uint32_t* o_pairs = lv_pairs + (size_t)blockIdx.x * K;
+    double* o_mi = lv_mi + (size_t)blockIdx.x * K;
+    for (int q = tid; q < K; q += PBG_WG) {
+        const uint32_t lv = lvl[q];
+        const uint32_t pos = atomicAdd(&lhist[lv], 1u);
+        const uint32_t i = pi[q], j = pj[q];
+        o_pairs[pos] = i | (j << 16);
+        o_mi[pos] = P.min_improve_g[i];
+        if (lean) o_pp[s_pst[lv] + (pos - s_lst[lv])] = (sc8 * i) | ((sc8 * j) << 16);
+    }
+    stamp(4);
+    // ---- the cones (k_exch_plan, smm_cone.hpp): as many tiles per pass as their bits fit the LDS behind the pairs' state ----
+    if (P.cone_ok == nullptr) return;
+    const int tiles = P.cone_tiles;
+    uint32_t* o_ok = (uint32_t*)P.cone_ok + blockIdx.x;
+    if (!lean) {   // (a deep plan: the walk's own fallback serves the iteration)
+        if (tid == 0) *o_ok = 0u;
+        return;
+    }
+    const int LS = nlev + 1;
+    int wpp = (int)((PBG_LDS - plan_bg_state_bytes(K)) / ((size_t)K * 4 + (size_t)32 * LS * 4 + 32 * 4));   // words of bits per pair and pass
+    if (wpp > (tiles + 31) / 32) wpp = (tiles + 31) / 32;
+    if (wpp < 1) { if (tid == 0) *o_ok = 0u; return; }
+    uint32_t* need = (uint32_t*)tmp;                 // [K][wpp]
+    uint32_t* lcnt = need + (size_t)K * wpp;         // [32 wpp][LS]: pairs of (tile, level); then: where the level's words start
+    uint32_t* gcnt = lcnt + (size_t)32 * wpp * LS;   // [32 wpp]: chains of other tiles in the cone (the persistent kernel's gather list)
+    uint16_t* o_gl = P.cone_gather ? P.cone_gather + (size_t)blockIdx.x * tiles * CONE_GCAP : nullptr;
+    uint32_t* o_hdr = (uint32_t*)P.cone_hdr + (size_t)blockIdx.x * tiles * CONE_HDRW;
+    uint32_t* o_cp = (uint32_t*)P.cone_pairs + (size_t)blockIdx.x * tiles * (CONE_LEVELS * 64);
+    const uint32_t ct = (uint32_t)P.cone_ct;
+    for (int b0 = 0; b0 < tiles; b0 += 32 * wpp) {   // tiles b0 .. b0 + 32 wpp - 1
+        const int nb = min(32 * wpp, tiles - b0);
+        __syncthreads();
+        for (int x = tid; x < K * wpp + 32 * wpp * LS + 32 * wpp; x += PBG_WG) need[x] = 0u;
+        __syncthreads();
+        for (int q = tid; q < K; q += PBG_WG) {   // seeds: the chains' last pairs
+            const uint32_t f = flg[q];
+            if (f & 1u) {
+                const uint32_t b = ((uint32_t)pi[q] - (uint32_t)P.offset) / ct - (uint32_t)b0;
+                if (b < (uint32_t)nb) atomicOr(&need[(size_t)q * wpp + (b >> 5)], 1u << (b & 31u));
+            }
+            if (f & 2u) {
+                const uint32_t b = ((uint32_t)pj[q] - (uint32_t)P.offset) / ct - (uint32_t)b0;
+                if (b < (uint32_t)nb) atomicOr(&need[(size_t)q * wpp + (b >> 5)], 1u << (b & 31u));
+            }
+        }
+        stamp(5);
+        __syncthreads();
+        for (int l = nlev; l >= 2; --l) {   // OR-ed into the predecessors level by level from the last level down
+            for (int q = tid; q < K; q += PBG_WG)
+                if (lvl[q] == l) {
+                    const uint32_t p1 = prei[q], p2 = prej[q];
+                    for (int w = 0; w < wpp; ++w) {
+                        const uint32_t v = need[(size_t)q * wpp + w];
+                        if (v) {
+                            if (p1 != NONE) atomicOr(&need[(size_t)p1 * wpp + w], v);
+                            if (p2 != NONE) atomicOr(&need[(size_t)p2 * wpp + w], v);
+                        }
+                    }
+                }
+            __syncthreads();
+        }
+        stamp(6);
+        for (int q = tid; q < K; q += PBG_WG) {   // count
+            const uint32_t lv = lvl[q];
+            for (int w = 0; w < wpp; ++w) {
+                uint32_t bits = need[(size_t)q * wpp + w];
+                while (bits) {
+                    const uint32_t b = (uint32_t)w * 32u + (uint32_t)__builtin_ctz(bits);
+                    bits &= bits - 1u;
+                    atomicAdd(&lcnt[b * LS + lv], 1u);
+                }
+            }
+        }
+        __syncthreads();
+        stamp(7);
+        for (int b = tid; b < nb; b += PBG_WG) {   // sub-levels: counts out, starting words in (header words through global memory: no register array)
+            uint32_t sub = 0;
+            uint32_t* oh = o_hdr + (size_t)(b0 + b) * CONE_HDRW;
+            for (int x = 0; x < CONE_HDRW; ++x) oh[x] = 0u;
+            for (int l = 1; l <= nlev; ++l) {
+                const uint32_t n = lcnt[b * LS + l];
+                lcnt[b * LS + l] = sub * 64u;
+                for (uint32_t x = 0; x < n; x += 64u, ++sub)
+                    if (sub < (uint32_t)CONE_LEVELS) {
+                        const uint32_t cnt_s = n - x < 64u ? n - x : 64u;
+                        oh[1 + (sub >> 2)] |= cnt_s << (8u * (sub & 3u));
+                    }
+            }
+            // (a cone past its caps is listed EMPTY, as k_exch_plan lists it)
+            oh[0] = sub <= (uint32_t)CONE_LEVELS ? sub : 0u;
+            if (sub > (uint32_t)CONE_LEVELS) atomicOr(s_bad, 1u);
+        }
+        __syncthreads();
+        stamp(8);
+        for (int q = tid; q < K; q += PBG_WG) {   // scatter
+            const uint32_t i = pi[q], j = pj[q], lv = lvl[q];
+            const uint32_t word = (sc8 * i) | ((sc8 * j) << 16);
+            // a chain is in the cones its FIRST pair is in: that is where its initial slot is needed
+            const bool gi = o_gl && prei[q] == NONE, gj = o_gl && prej[q] == NONE;
+            const uint32_t ti = (i - (uint32_t)P.offset) / ct, tj = (j - (uint32_t)P.offset) / ct;
+            for (int w = 0; w < wpp; ++w) {
+                uint32_t bits = need[(size_t)q * wpp + w];
+                while (bits) {
+                    const uint32_t bb = (uint32_t)w * 32u + (uint32_t)__builtin_ctz(bits);
+                    bits &= bits - 1u;
+                    const uint32_t dst = atomicAdd(&lcnt[bb * LS + lv], 1u);
+                    if (dst < (uint32_t)(CONE_LEVELS * 64)) o_cp[(size_t)(b0 + bb) * (CONE_LEVELS * 64) + dst] = word;
+                    if (gi && ti != (uint32_t)b0 + bb) {
+                        const uint32_t g = atomicAdd(&gcnt[bb], 1u);
+                        if (g < (uint32_t)CONE_GCAP) o_gl[(size_t)(b0 + bb) * CONE_GCAP + g] = (uint16_t)i;
+                    }
+                    if (gj && tj != (uint32_t)b0 + bb) {
+                        const uint32_t g = atomicAdd(&gcnt[bb], 1u);
+                        if (g < (uint32_t)CONE_GCAP) o_gl[(size_t)(b0 + bb) * CONE_GCAP + g] = (uint16_t)j;
+                    }
+                }
+            }
+        }
+        if (o_gl) {
+            __syncthreads();
+            for (int b = tid; b < nb; b += PBG_WG) {
+                const uint32_t g = gcnt[b];
+                if (g > (uint32_t)CONE_GCAP) { atomicOr(s_bad, 1u); o_hdr[(size_t)(b0 + b) * CONE_HDRW] = 0u; }   // (listed empty, as above)
+                else o_hdr[(size_t)(b0 + b) * CONE_HDRW] |= g << 16;
+            }
+        }
+    }
+    __syncthreads();
+    stamp(9);
+    if (tid == 0) *o_ok = *s_bad ? 0u : 1u;
+}

@@ -227,7 +227,7 @@ struct PersistKernel { const void* fn; hipFunction_t mfn; dim3 grid, block; size
 // a row of exch_instance's table (cap: the dynamic LDS limit raised at creation where the context's forms include the row's group, 0: the default
 // will do; stamped: takes the dispatch's own stamps in profiling mode 2), and a chooser's pick for one launch (the row, this launch's dynamic LDS)
 enum ExchId { XI_CONE_CHAINS, XI_CONE_TILES, XI_PLAN_BIG, XI_PLAN, XI_LEAN, XI_LVL_256, XI_LVL_512, XI_LVL, XI_LVL_SOA, XI_TICKETS, XI_KEYS, XI_ROWS_PLDS,
-              XI_ROWS, XI_KEY_PLDS, XI_KEY, XI_LVL_BIG, XI_ANY, XI_ROWS_WIN_OWN, XI_ROWS_WIN_PLDS, XI_ROWS_WIN, XI_APPLY, XI_COUNT };
+              XI_ROWS, XI_KEY_PLDS, XI_KEY, XI_LVL_BIG, XI_ANY, XI_ROWS_WIN_OWN, XI_ROWS_WIN_PLDS, XI_ROWS_WIN, XI_APPLY, XI_PLAN_BG, XI_COUNT };
 enum ExchGroup { XG_BIG, XG_KEYS, XG_LDS, XG_CONE_BIG };
 struct ExchInstance { const void* fn; unsigned block; size_t cap; ExchGroup group; const char* name; bool stamped; };
 struct ExchLaunch { int id; size_t smem; };
@@ -310,7 +310,16 @@ struct Ctx {
         uint32_t* ok_host = nullptr;   // (pinned) cone_ok as the host reads it
         hipEvent_t done = nullptr;
         int t0 = 0, w = 0;             // iterations [t0, t0 + w) are (being) planned into this set
+        // (plan_beside: the LDS plan's own tables of the set — the ranked pair list, its thresholds, the lean walk's padded list)
+        unsigned long long* plan = nullptr;
+        double* plan_mi = nullptr;
+        uint32_t *lv_pairs_p = nullptr, *lv_offp = nullptr;
     } ps[2];
+    // ... and so are the LDS plan's of a single shard on k_chain_persist_loc whose plan fits k_exch_plan_bg (plan_bg_fits): that kernel runs
+    // BESIDE the chain kernel, in the registers and the LDS it leaves (choose_plan_beside); the host waits for nothing.  Not a field of
+    // Forms: what select_forms decides is what it decided before there was this path
+    bool plan_beside = false;
+    int windows_beside = 0, windows_instream = 0;   // plan windows entered so far: planned beside the chain kernel / on the main stream (smm_get_plan_beside)
     int ps_act = 0;                      // the set the chain kernels read
     hipStream_t pstream = nullptr;
     hipEvent_t ev_free = nullptr;        // main stream: every launch that reads the set about to be planned into has been enqueued before it (plan_window_into)
@@ -707,6 +716,15 @@ int smm_get_persistent(void* ctx, int32_t* available, int32_t* launches, int32_t
     return SMM_OK;
 }
 
+int smm_get_plan_beside(void* ctx, int32_t* beside, int32_t* windows_beside, int32_t* windows_instream) {
+    return api_call(ctx, true, [&](Ctx* c) -> int {
+        if (beside) *beside = c->plan_beside ? 1 : 0;
+        if (windows_beside) *windows_beside = c->windows_beside;
+        if (windows_instream) *windows_instream = c->windows_instream;
+        return SMM_OK;
+    });
+}
+
 int smm_set_profiling(void* ctx, int32_t on) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return SMM_ERR_INVALID_ARG;
@@ -740,6 +758,84 @@ int smm_debug_ts_waves(void* ctx, unsigned long long* out, int n_wg) {
 }
 
 #ifdef SMM_TEST_HOOKS
+// debug (test build only, not part of the public header; touches no device): the sizes the residency of k_exch_plan_bg beside k_chain_persist_loc
+// is argued from — out[0] persist_loc_smem_bytes(np), [1] the background kernel's LDS request, [2] the LDS of a compute unit, [3] the allocation
+// granule, [4] / [5] the largest population (pairs = chains) the background form takes / 1 if it takes (Ng, K), [6] the static LDS the residency allows the compiler to add
+int smm_debug_plan_beside_budget(int np, int Ng, int K, long long* out) {
+    if (!out || np < 1 || np > 2) return SMM_ERR_INVALID_ARG;
+    out[0] = (long long)persist_loc_smem_bytes(np); out[1] = (long long)PBG_LDS; out[2] = (long long)LDS_CU; out[3] = (long long)LDS_GRANULE;
+    int n = 0;
+    while (plan_bg_fits(n + 1, n + 1)) ++n;
+    out[4] = n; out[5] = plan_bg_fits(Ng, K) && plan_beside_resident(np) ? 1 : 0; out[6] = (long long)PBG_LDS_STATIC;
+    return SMM_OK;
+}
+// (the two seams below on a context of the LDS plan that does NOT plan beside — a population past the persistent form's 4096 chains —: the two sets are
+// made on first use, with cone tables of 16-chain tiles, so that k_exch_plan_bg can be held against k_exch_plan up to the last population its LDS takes,
+// which no context reaches on a device of 256 compute units.  Returns the tiles of the sets' cone tables, 0: not a context of the LDS plan)
+static int debug_plan_sets(Ctx* c) {
+    if (c->plan_beside) return c->P.cone_tiles;
+    if (c->F.plan != PLAN_LDS || !c->F.lean_plan || c->F.plan_ahead) return 0;
+    const int tiles = (c->P.N + NORM_CT - 1) / NORM_CT;
+    if (!c->ps[0].plan) {
+        const size_t W = (size_t)c->F.plan_cap, K = (size_t)c->P.plan_K;
+        for (Ctx::PlanSet& S : c->ps) {
+            alloc_level_tables(c, S, false, (size_t)tiles, true);
+            S.plan = dalloc<unsigned long long>(c, W * K); S.plan_mi = dalloc<double>(c, W * K);
+            S.lv_pairs_p = dalloc<uint32_t>(c, W * c->P.plan_Kp + 512); S.lv_offp = dalloc<uint32_t>(c, W * LV_OFFP);
+        }
+    }
+    return tiles;
+}
+// debug (test build only): the tables of the plan set `which` (0 / 1: by index; -1: the active one) for iteration S.t0 + w, copied out after both streams
+// have drained — info: t0, w of the set, nlev, cone_ok, K, tiles; plan [K] words, lv_pairs [K], lv_off [K + 2], offp [LV_OFFP], pairs_p [plan_Kp],
+// hdr [tiles][CONE_HDRW], cone pairs [tiles][CONE_LEVELS * 64], gather [tiles][CONE_GCAP] (tests/test_gpu_plan_beside.py: k_exch_plan_bg's against k_exch_plan's)
+int smm_debug_plan_tables(void* ctx, int which, int w, int32_t* info, unsigned long long* plan, uint32_t* lv_pairs, uint32_t* lv_off, uint32_t* offp, uint32_t* pairs_p,
+                          uint32_t* hdr, uint32_t* cpairs, uint16_t* gather) {
+    return api_call(ctx, info != nullptr, [&](Ctx* c) -> int {
+        HIPCHK(hipSetDevice(c->device));
+        const size_t tiles = (size_t)debug_plan_sets(c);
+        if (!tiles) return SMM_ERR_INVALID_ARG;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->pstream) HIPCHK(hipStreamSynchronize(c->pstream));
+        const Ctx::PlanSet& S = c->ps[which < 0 ? c->ps_act : (which & 1)];
+        const KParams& P = c->P;
+        const size_t K = (size_t)P.plan_K;
+        uint32_t ok = 0, nlev = 0;
+        HIPCHK(hipMemcpy(&ok, S.cone_ok + w, 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&nlev, S.lv_off + (size_t)w * (K + 2) + K + 1, 4, hipMemcpyDeviceToHost));
+        info[0] = S.t0; info[1] = S.w; info[2] = (int32_t)nlev; info[3] = (int32_t)ok; info[4] = (int32_t)K; info[5] = (int32_t)tiles; info[6] = P.plan_Kp; info[7] = S.lv_pairs_p ? 1 : 0;
+        if (plan) HIPCHK(hipMemcpy(plan, S.plan + (size_t)w * K, K * 8, hipMemcpyDeviceToHost));
+        if (lv_pairs) HIPCHK(hipMemcpy(lv_pairs, S.lv_pairs + (size_t)w * K, K * 4, hipMemcpyDeviceToHost));
+        if (lv_off) HIPCHK(hipMemcpy(lv_off, S.lv_off + (size_t)w * (K + 2), (K + 2) * 4, hipMemcpyDeviceToHost));
+        if (offp && S.lv_offp) HIPCHK(hipMemcpy(offp, S.lv_offp + (size_t)w * LV_OFFP, LV_OFFP * 4, hipMemcpyDeviceToHost));
+        if (pairs_p && S.lv_pairs_p) HIPCHK(hipMemcpy(pairs_p, S.lv_pairs_p + (size_t)w * P.plan_Kp, (size_t)P.plan_Kp * 4, hipMemcpyDeviceToHost));
+        if (hdr) HIPCHK(hipMemcpy(hdr, S.cone_hdr + (size_t)w * tiles * CONE_HDRW, tiles * CONE_HDRW * 4, hipMemcpyDeviceToHost));
+        if (cpairs) HIPCHK(hipMemcpy(cpairs, S.cone_pairs + (size_t)w * tiles * (CONE_LEVELS * 64), tiles * CONE_LEVELS * 64 * 4, hipMemcpyDeviceToHost));
+        if (gather && S.cone_gather) HIPCHK(hipMemcpy(gather, S.cone_gather + (size_t)w * tiles * CONE_GCAP, tiles * CONE_GCAP * 2, hipMemcpyDeviceToHost));
+        return SMM_OK;
+    });
+}
+// debug (test build only): the plan window from iteration t on by k_exch_plan_bg (bg != 0) or k_exch_plan into plan set `which`, on the main stream
+int smm_debug_plan_into(void* ctx, int which, int t, int bg) {
+    return api_call(ctx, true, [&](Ctx* c) -> int {
+        if (t < 1 || t > c->P.T || (bg && !plan_bg_fits(c->P.Ng, c->P.plan_K))) return SMM_ERR_INVALID_ARG;
+        HIPCHK(hipSetDevice(c->device));
+        const int tiles = debug_plan_sets(c);
+        if (!tiles) return SMM_ERR_INVALID_ARG;
+        if (c->pstream) HIPCHK(hipStreamSynchronize(c->pstream));
+        Ctx::PlanSet& S = c->ps[which & 1];
+        KParams Pw = c->P;
+        point_tables(Pw, S);
+        if (!c->plan_beside) { Pw.cone_tiles = tiles; Pw.cone_ct = NORM_CT; }
+        const int W = std::min(c->F.plan_cap, Pw.T - t + 1);
+        launch_exch(c, bg ? XI_PLAN_BG : XI_PLAN, dim3(W), bg ? PBG_LDS : plan_smem(Pw.Ng, Pw.plan_K, true), c->stream, Pw, t, S.plan, S.plan_mi, S.lv_pairs, S.lv_mi, S.lv_off,
+                    S.lv_pairs_p, S.lv_offp);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        S.t0 = t; S.w = W;
+        if (c->plan_beside && (which & 1) == c->ps_act) { c->plan_t0 = t; c->plan_w = W; c->P.plan_t0 = t; }
+        return SMM_OK;
+    });
+}
 // debug (test build only, not part of the public header): the look-ahead window starting at iteration t, planned now; milliseconds of its
 // kernels on the stream (tools/exp/shard_plan_time.py: what a shard of 8 x 4096 spends on its plan per window)
 int smm_debug_plan_window(void* ctx, int t, double* ms_out, int* window_out) {

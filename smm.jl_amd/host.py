@@ -1258,6 +1258,12 @@ def _sobol_result(m, ctx, n_base, box):
     return SobolResult(names, ms_names(m), ctx.sens_sobol(n_base, lo, hi))
 
 
+def plan_beside(algo):
+    """(the run plans each next exchange window beside its persistent kernel, windows planned that way so far, windows planned on the
+    main stream): smm_get_plan_beside"""
+    return algo._ctx.plan_beside_info()
+
+
 def set_proposal(algo, L):
     """install proposal factor(s) between iterations (smm_set_proposal): [np][np] on a shared-factor run, [N][np][np] per chain"""
     algo._ctx.set_proposal(L)
